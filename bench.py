@@ -5,6 +5,8 @@ achieved HBM GB/s of the fused kernel against the ~8 TB/s roofline and the
 NumPy oracle timed on this box's host cores as a baseline.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR   # + what the last timed step computed, as DIR/*.npy
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full               # + every other leg (see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N ...          # no launcher: this process starts the N ranks itself (launch_ranks)
@@ -21,6 +23,11 @@ that are already resident in HBM:
     channel histograms -> percentile white-balance tables -> fused kernel
     (band de-interleave, table lookup, three float32 index planes written,
     min/max/sum/coverage per index) -> fold of per-tile records -> global fold.
+
+A plain run sets up, warms up, times --steps steps of --mode, writes --dump-outputs if given and prints the line.
+Everything else moves behind --full: the other modes (all of them with one GPU, or with --all-modes), the self-check
+(`verified`), the exact global medians, the per-launch events of the first timed step, the device's streaming probe,
+the uint16 and image-like content legs and the NumPy CPU baseline.  The --no-* / --cpu-* options select among those.
 """
 from __future__ import annotations
 
@@ -95,7 +102,17 @@ def parse():
     ap.add_argument("--no-smooth-leg", dest="smooth_leg", action="store_false",
                     help="skip the statistics-only modes on image-like (smooth, natural) content")
     ap.add_argument("--no-verify", dest="verify", action="store_false", help="skip the self-check after the timed region")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: other modes, self-check, global medians, per-launch "
+                         "events, streaming probe, uint16 and image-like legs, CPU baseline (the options above pick among them; "
+                         "without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, rank 0; "
+                         "see dump_outputs; bench_outputs/ is git-ignored)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 class Runner:
@@ -289,6 +306,56 @@ class Runner:
         out["modes_compared"] = names
         out["ok"] = bool(out["records"] and same and out["planes"] is not False and out.get("medians", True))
         return out
+
+
+RECORD_FIELDS = ("sum", "sumsq", "count", "above", "nans", "min", "max", "threshold")
+DUMP_SEED = 20240607
+DUMP_PLANE_TILES = 8                 # tiles of the last chunk whose planes are sampled
+DUMP_PLANE_PIXELS = 1 << 19          # pixels sampled per tile (the same positions in every sampled tile)
+DUMP_BUDGET_BYTES = 60_000_000
+
+
+def _records_f64(rec):
+    """STATS_DTYPE records [...] -> float64 [..., 8 + HIST_BINS]: RECORD_FIELDS, then the 50-bin histogram (exact below 2^53)."""
+    cols = [rec[f].astype(np.float64)[..., None] for f in RECORD_FIELDS] + [rec["hist"].astype(np.float64)]
+    return np.concatenate(cols, axis=-1)
+
+
+def dump_outputs(runner, mode, glob, path):
+    """What the timed path handed its caller in the LAST timed step, as float32 / float64 .npy files under ``path``
+    (axis "index" in the order of the mode's indices, NDVI / GNDVI / NDWI):
+      global_stats.npy   float64 [index, 58]          the global record per index (RECORD_FIELDS + 50-bin histogram)
+      tile_stats.npy     float64 [tile, index, 58]    this rank's per-tile records
+      tile_medians.npy   float64 [tile, index]        the exact per-tile medians (median modes only)
+      plane_<INDEX>.npy  float32 [tile, pixel]        planes-writing modes: a seeded sample of the output planes the ring holds
+                                                      after the step (DUMP_PLANE_TILES tiles of the last chunk, the same
+                                                      DUMP_PLANE_PIXELS flat pixel positions in each)
+    Inputs and sample positions depend on the arguments only, so two builds compare file for file.  Under 60 MB in all."""
+    ffi, b = runner.ffi, runner.batch
+    indices, write, _, _ = MODES[mode]
+    ids = [ffi.INDEX_IDS[t] for t in indices]
+    ffi.call("lars_synchronize", None)
+    out = {"global_stats": _records_f64(np.asarray(glob)[ids]),
+           "tile_stats": _records_f64(runner.stats.download(ffi.STATS_DTYPE, (b.ntiles, 3))[:, ids])}
+    if mode in MEDIAN_MODES:
+        med = b._medians_from_pairs(runner.pairs.download(np.float32, (b.ntiles, 2, 2)), indices)
+        out["tile_medians"] = np.ascontiguousarray(med[:, ids])
+    if write:
+        outs = runner.outputs_for(indices, write)
+        ring = outs.slots
+        last_chunk = ((b.ntiles - 1) // ring) * ring
+        rng = np.random.default_rng(DUMP_SEED)
+        tiles = np.sort(rng.choice(np.arange(last_chunk, b.ntiles), size=min(DUMP_PLANE_TILES, b.ntiles - last_chunk), replace=False))
+        room = DUMP_BUDGET_BYTES - sum(a.nbytes for a in out.values())
+        npos = int(min(b.npix, DUMP_PLANE_PIXELS, room // (4 * len(indices) * len(tiles))))
+        pos = np.sort(rng.choice(b.npix, size=npos, replace=False))
+        for t in indices:
+            out[f"plane_{t}"] = np.stack([outs.host_index(t, int(tile) % ring, 1).reshape(-1)[pos] for tile in tiles])
+    os.makedirs(path, exist_ok=True)
+    for name, arr in out.items():
+        assert arr.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(path, f"{name}.npy"), arr)
+    return sorted(out)
 
 
 def _cpu_tile_job(job):
@@ -745,7 +812,13 @@ def main():
     npix_rank = args.tiles * args.tile * args.tile
     if args.all_modes is None:
         args.all_modes = world == 1          # N > 1: only the headline mode is timed unless --all-modes (the line stays cheap)
-    dt, timed, glob = runner.run(args.mode, args.steps, args.warmup, per_launch=True)
+    if not args.full:
+        # a plain run: the headline figure and nothing else
+        args.all_modes = args.verify = args.probe = args.u16_leg = args.smooth_leg = False
+        args.no_cpu_baseline = True
+    dt, timed, glob = runner.run(args.mode, args.steps, args.warmup, per_launch=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(runner, args.mode, glob, args.dump_outputs)
     total_pix = npix_rank * world * args.steps
     value = total_pix / dt / 1e6
     local_step_ms = runner.last_local_dt / args.steps * 1e3

@@ -11,12 +11,12 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(extra_env, *args):
+def run_bench(extra_env, *args, full=True):
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29731",
                LARS_RDZV_TOKEN=f"bench{os.getpid()}", **extra_env)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--tiles", "6", "--tile", "512", "--ring", "4", "--steps", "2",
            "--warmup", "1", "--no-probe", "--placement-trials", "2", *(a for a in args if a != "--all-modes"),
-           *(() if "--all-modes" in args else ("--no-all-modes",))]
+           *(() if "--all-modes" in args else ("--no-all-modes",)), *(("--full",) if full else ())]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -118,6 +118,56 @@ def test_bench_all_modes_and_their_self_check():
         assert "median" in line["global_stats"][name]
 
 
+def test_plain_line_is_lean_and_dumps_what_the_last_step_computed(tmp_path):
+    """Without --full the line carries the headline only (no other modes, self-check, medians, probe or CPU baseline);
+    --dump-outputs writes the last timed step's records and a sample of its planes, the same in two runs and equal to the
+    oracle on the sampled tiles (6 tiles, ring of 4: tiles 4 and 5 are in the ring after the step, every pixel sampled)."""
+    import warnings
+
+    import numpy as np
+
+    import bench
+    from oracle import index_oracle as orc
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        line = run_bench({}, "--dump-outputs", str(tmp_path / run), full=False)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "global_stats", "roofline"):
+            assert key in line, key
+        assert line["steps"] == 2 and line["verified"] is None and line["cpu_baseline"] is None and "modes" not in line
+        assert "device_probe_GBs" not in line and line["roofline"]["first_step_launch_ms"] is None
+        assert abs(line["value"] - 6 * 512 * 512 / (line["ms_per_step"] * 1e-3) / 1e6) <= 1e-6 * line["value"]
+        files = sorted(os.listdir(tmp_path / run))
+        assert files == ["global_stats.npy", "plane_GNDVI.npy", "plane_NDVI.npy", "plane_NDWI.npy", "tile_stats.npy"], files
+        dump = {f[:-4]: np.load(tmp_path / run / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in dump.values())
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64 * 10**6
+        lines.append(line)
+        dumps.append(dump)
+    assert lines[0]["global_stats"] == lines[1]["global_stats"]
+    for name in dumps[0]:
+        assert dumps[0][name].tobytes() == dumps[1][name].tobytes(), name
+    d = dumps[0]
+    assert d["global_stats"].shape == (3, 58) and d["tile_stats"].shape == (6, 3, 58)
+    assert list(d["global_stats"][:, 2]) == [6 * 512 * 512] * 3
+    for k, t in enumerate(("NDVI", "GNDVI", "NDWI")):
+        g = dict(zip(bench.RECORD_FIELDS, d["global_stats"][k]))
+        want = lines[0]["global_stats"][t]
+        assert g["min"] == want["min"] and g["max"] == want["max"] and g["sum"] / g["count"] == want["mean"], t
+        assert g["count"] == d["tile_stats"][:, k, 2].sum() and g["above"] == d["tile_stats"][:, k, 3].sum(), t
+        assert d["plane_" + t].shape == (2, 512 * 512) and d["plane_" + t].dtype == np.float32
+    for i, tile in enumerate((4, 5)):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            wb = orc.wb_app(orc.synth_tile_u8(1234, tile, 512, 512, profile="vegetation"))
+        for k, t in enumerate(("NDVI", "GNDVI", "NDWI")):
+            plane = orc.index_app(wb, t)
+            assert np.array_equal(d["plane_" + t][i].view(np.uint32), plane.reshape(-1).view(np.uint32)), (tile, t)
+            part = orc.tile_partials(plane, t)
+            rec = dict(zip(bench.RECORD_FIELDS, d["tile_stats"][tile, k]))
+            assert rec["sum"] == part["sum"] and rec["count"] == part["count"] and rec["above"] == part["above"], (tile, t)
+            assert rec["min"] == part["min"] and rec["max"] == part["max"], (tile, t)
+
+
 @pytest.mark.parametrize("transport", ["rccl", "torch", "auto"])
 def test_bench_statistics_fold_transports_agree(transport):
     """One rank through each transport (auto = the pre-flight vote, which librccl wins on this image): same global
@@ -142,7 +192,7 @@ def test_ranks_on_one_gpu_equal_one_process_over_all_tiles(tmp_path, ranks, all_
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     common = ["--tile", "512", "--ring", "4", "--steps", "2", "--warmup", "1", "--no-probe", "--placement-trials", "2", "--no-cpu-baseline",
-              *(["--all-modes", "--no-u16-leg"] if all_modes else [])]
+              "--full", *(["--all-modes", "--no-u16-leg"] if all_modes else [])]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(port + ranks), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--tiles", str(per_rank), *common]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
@@ -183,7 +233,7 @@ def test_plain_bench_gpus_2_starts_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it: bench.py starts the two ranks itself (both on GPU 0,
     statistics over gloo) and rank 0's line says so; global statistics equal one process over the same 12 tiles."""
     common = ["--tile", "512", "--ring", "4", "--steps", "2", "--warmup", "1", "--no-probe", "--placement-trials", "0",
-              "--no-cpu-baseline", "--no-all-modes"]
+              "--no-cpu-baseline", "--no-all-modes", "--full"]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--tiles", "6", *common],
                          env=_clean_env(LARS_COMM="gloo", LARS_DEVICE="0"), capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]

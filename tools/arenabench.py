@@ -25,7 +25,7 @@ def main():
     args = ap.parse_args()
     fracs = []
     for i in range(args.runs):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-all-modes", "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--full", "--no-all-modes", "--no-cpu-baseline",
                "--no-probe", "--no-verify", "--arena", args.arena, "--placement-trials", str(args.trials), *args.rest]
         out = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, timeout=900)
         if out.returncode != 0:

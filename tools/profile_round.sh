@@ -13,12 +13,12 @@ mkdir -p "$OUT" "$R/profiles"
 cd /tmp && export TMPDIR=/tmp
 if [ "${PMC_ONLY:-0}" != "1" ]; then
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$R/bench.py" --steps 3 --warmup 1 \
-    --no-cpu-baseline --no-probe > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.err"
+    --full --no-cpu-baseline --no-probe > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.err"
 fi
 # (the smooth-content leg stays out of the counter passes: its batch is fetched with another mix of 64- and 128-byte requests, which the
 #  FETCH_SIZE formula counts differently -- 9.38 M instead of 6.29 M KiB for the same 12 GiB in the same time -- and the summaries average per kernel name)
 for c in FETCH_SIZE WRITE_SIZE; do
     rocprofv3 --pmc $c --output-format csv -d "$OUT/pmc_$c" -- python3 "$R/bench.py" --steps 2 --warmup 1 --tiles 256 \
-        --no-cpu-baseline --no-probe --no-verify --no-u16-leg --no-smooth-leg --arena plain --placement-trials 0 > /dev/null 2> "$OUT/pmc_$c.err"
+        --full --no-cpu-baseline --no-probe --no-verify --no-u16-leg --no-smooth-leg --arena plain --placement-trials 0 > /dev/null 2> "$OUT/pmc_$c.err"
 done
 echo "collected under gpurun_out/prof_$ROUND; back in the container: python tools/collect_profiles.py $ROUND"
