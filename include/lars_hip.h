@@ -425,6 +425,14 @@ int lars_h_threshold_mask_f32(const float *x, int64_t n, float threshold, uint8_
  * fixed-point resampler.  out is host [new_h][new_w][channels]. */
 int lars_h_resize_lanczos_u8(const uint8_t *img, int64_t h, int64_t w, int channels, int64_t new_h, int64_t new_w,
                              uint8_t *out);
+/* gallery thumbnail -- process-images.py:186-189: img.thumbnail(size, Image.Resampling.LANCZOS, reducing_gap), bit-identical
+ * to Pillow, on the plan lars_image_processing_amd.api.thumbnail_plan computes: img is the decoded (after draft) uint8 image
+ * [h][w][channels] (1 L, 3 RGB, 4 RGBA: premultiplied alpha, as Pillow resizes RGBA); Image.reduce((fx, fy)) over
+ * reduce_box = {x0, y0, x1, y1} (skipped when fx = fy = 1 and the box is the whole image); then the LANCZOS passes from
+ * the float box = {x0, y0, x1, y1} of the reduced image to new_w x new_h, an axis only where it changes, vertical first
+ * when vertical_first != 0 (Image.resize's tall-image branch).  out is host [new_h][new_w][channels]. */
+int lars_h_thumbnail_u8(const uint8_t *img, int64_t h, int64_t w, int channels, int fx, int fy, const int reduce_box[4],
+                        const float box[4], int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out);
 
 /* align_images -- process-images.py:515-565 for two uint8 images of the same shape ([h][w][3] or [h][w]):
  * out_aligned = moving registered onto fixed, shift = {dy, dx} (what phase_cross_correlation returns). */

@@ -26,6 +26,8 @@ from .api import (  # noqa: F401
     index_histogram,
     preprocess_large_image,
     process_image,
+    thumbnail,
+    thumbnail_plan,
     time_series_points,
     timeseries_row,
 )

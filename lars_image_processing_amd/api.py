@@ -16,6 +16,7 @@ this module                     reference
 ``analyze_index(idx, t)``       process-images.py:492
 ``analyze_ndvi_statistics``     process-ndvi.py:50
 ``preprocess_large_image``      process-images.py:398  (Pillow LANCZOS down-scale)
+``thumbnail``                   process-images.py:186  (Pillow LANCZOS gallery thumbnail; a new object, not in place)
 ``align_images``                process-images.py:515  (phase correlation + shift)
 ``calculate_index_statistics_by_timeframe``  process-images.py:619 (pandas table)
 ``time_series_points``          process-images.py:814-832 (the numbers ``create_time_series_plot`` draws)
@@ -40,6 +41,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -51,7 +53,7 @@ __all__ = [
     "fix_white_balance", "correct_white_balance", "fix_white_balance_rgnir",
     "calculate_index", "calculate_ndvi", "analyze_index", "analyze_index_statistics",
     "analyze_ndvi_statistics", "index_histogram", "classification_mask", "colorize_index", "process_image",
-    "timeseries_row", "colormap_lut", "preprocess_large_image", "align_images", "change_detection",
+    "timeseries_row", "colormap_lut", "preprocess_large_image", "thumbnail", "thumbnail_plan", "align_images", "change_detection",
     "colorize_difference", "calculate_index_statistics_by_timeframe", "time_series_points",
     "calculate_ndvi_array", "generate_ndvi_report", "download_processed_images",
     "create_index_visualization", "create_comparison_view", "create_time_series_plot", "create_change_detection_visualization",
@@ -121,6 +123,130 @@ def preprocess_large_image(img_array, max_dimension=1024):
     c = 1 if arr.ndim == 2 else arr.shape[2]
     out = np.empty((new_h, new_w) if arr.ndim == 2 else (new_h, new_w, c), dtype=np.uint8)
     _ffi.call("lars_h_resize_lanczos_u8", _ffi.ptr(arr), h, w, c, new_h, new_w, _ffi.ptr(out))
+    return out
+
+
+# ---------------------------------------------------------------------------
+# gallery thumbnails
+# ---------------------------------------------------------------------------
+_LANCZOS_SUPPORT = 3.0                      # Image._filters_support[LANCZOS]
+_THUMB_MODES = {"L": 1, "RGB": 3, "RGBA": 4}
+_THUMB_CHANNELS = {1: "L", 3: "RGB", 4: "RGBA"}
+
+
+class ThumbnailPlan(NamedTuple):
+    """What ``Image.thumbnail(size, LANCZOS, reducing_gap)`` does to the decoded pixels (``thumbnail_plan``)."""
+    size: tuple            # (w, h) of the thumbnail
+    factor: tuple          # (fx, fy) of Image.reduce; (1, 1) = no reduce
+    reduce_box: tuple      # (x0, y0, x1, y1) of the decoded image the reduce reads (_get_safe_box), or the whole image
+    box: tuple             # (x0, y0, x1, y1) of the LANCZOS passes in the reduced image, rounded to float32 as Pillow's C code holds it
+    vertical_first: bool   # Image.resize's tall-image branch: the vertical pass runs before the horizontal one
+    premultiply: bool      # RGBA: resampled as RGBa, without the reduce
+
+
+def thumbnail_size(src_size, size):
+    """``preserve_aspect_ratio`` of ``Image.thumbnail``: the (w, h) a (w, h) source becomes, ``None`` if it already fits."""
+    x, y = (math.floor(v) for v in size)
+    width, height = src_size
+    if x >= width and y >= height:
+        return None
+
+    def round_aspect(number, key):
+        return max(min(math.floor(number), math.ceil(number), key=key), 1)
+
+    aspect = width / height
+    if x / y >= aspect:
+        x = round_aspect(y * aspect, key=lambda n: abs(aspect - n / y))
+    else:
+        y = round_aspect(x / aspect, key=lambda n: 0 if n == 0 else abs(aspect - x / n))
+    return x, y
+
+
+def thumbnail_plan(src_size, size=(400, 400), reducing_gap=2.0, draft_box=None, image_size=None, rgba=False):
+    """Pillow 12's ``Image.thumbnail(size, LANCZOS, reducing_gap)`` policy as numbers; no GPU involved.
+
+    ``src_size`` is the (w, h) the caller sees before ``draft``, ``image_size`` the (w, h) of the decoded pixels
+    (after ``draft``; default ``src_size``) and ``draft_box`` the box ``draft`` returned (``None``: the whole image).
+    Returns ``None`` where Pillow leaves the image alone, else a ``ThumbnailPlan``.  Raises ``ValueError`` for a
+    ``reducing_gap`` below 1.0 where Pillow would resize.  The only place these rules live: ``thumbnail`` and the C
+    entry point ``lars_h_thumbnail_u8`` take its numbers as they are.
+    """
+    final = thumbnail_size(src_size, size)
+    if final is None:
+        return None
+    w, h = image_size if image_size is not None else src_size
+    if (w, h) == final:                                   # thumbnail: `if self.size != final_size`
+        return None
+    if reducing_gap is not None and reducing_gap < 1.0:
+        raise ValueError("reducing_gap must be 1.0 or greater")
+    box = (0, 0, w, h) if draft_box is None else tuple(draft_box)
+    factor, reduce_box = (1, 1), (0, 0, w, h)
+    # resize(): RGBA converts to RGBa and resizes again without reducing_gap
+    if reducing_gap is not None and not rgba:
+        fx = int((box[2] - box[0]) / final[0] / reducing_gap) or 1
+        fy = int((box[3] - box[1]) / final[1] / reducing_gap) or 1
+        if fx > 1 or fy > 1:
+            # _get_safe_box
+            filter_support = _LANCZOS_SUPPORT - 0.5
+            support_x = filter_support * ((box[2] - box[0]) / final[0])
+            support_y = filter_support * ((box[3] - box[1]) / final[1])
+            reduce_box = (max(0, int(box[0] - support_x)), max(0, int(box[1] - support_y)),
+                          min(w, math.ceil(box[2] + support_x)), min(h, math.ceil(box[3] + support_y)))
+            factor = (fx, fy)
+            box = ((box[0] - reduce_box[0]) / fx, (box[1] - reduce_box[1]) / fy,
+                   (box[2] - reduce_box[0]) / fx, (box[3] - reduce_box[1]) / fy)
+            w = -(-(reduce_box[2] - reduce_box[0]) // fx)
+            h = -(-(reduce_box[3] - reduce_box[1]) // fy)
+    return ThumbnailPlan(size=final, factor=factor, reduce_box=reduce_box,
+                         box=tuple(float(np.float32(v)) for v in box),
+                         vertical_first=h > w * 100 and final[1] < h, premultiply=rgba)
+
+
+def thumbnail(image, size=(400, 400), reducing_gap=2.0):
+    """``img.thumbnail(size, Image.Resampling.LANCZOS, reducing_gap)`` (process-images.py:186-189), bit for bit, on the GPU.
+
+    ``image``: a PIL image in mode L, RGB or RGBA, or a uint8 ndarray [H, W], [H, W, 3] or [H, W, 4] (the same three
+    modes).  Returns a NEW object of the same kind -- unlike Pillow, which changes the image in place -- or ``image``
+    itself, without touching the GPU, where Pillow would leave the image as it is.  A JPEG-backed PIL image is
+    ``draft``-ed first exactly as Pillow does (this changes the caller's image object, as Pillow's call does); decoding
+    stays Pillow's.  Other modes raise ``TypeError``: there is no CPU fallback.
+    """
+    pil = _is_pil(image)
+    if pil:
+        mode = image.mode
+        if mode not in _THUMB_MODES:
+            raise TypeError(f"thumbnail: PIL images in mode L, RGB or RGBA (got mode {mode!r})")
+        src_size = image.size
+    else:
+        arr = np.asarray(image)
+        if arr.dtype != np.uint8 or not (arr.ndim == 2 or (arr.ndim == 3 and arr.shape[2] in (3, 4))):
+            raise TypeError(f"thumbnail: uint8 arrays [H, W], [H, W, 3] or [H, W, 4] (got {arr.dtype}, shape {arr.shape})")
+        mode = _THUMB_CHANNELS[1 if arr.ndim == 2 else arr.shape[2]]
+        src_size = (arr.shape[1], arr.shape[0])
+    if thumbnail_size(src_size, size) is None:
+        return image
+    draft_box = None
+    if pil:
+        if reducing_gap is not None:
+            res = image.draft(None, (int(size[0] * reducing_gap), int(size[1] * reducing_gap)))
+            if res is not None:
+                draft_box = res[1]
+        arr = np.asarray(image)
+        if image.mode != mode:
+            raise TypeError(f"thumbnail: the decoder turned mode {mode!r} into {image.mode!r}")
+    plan = thumbnail_plan(src_size, size, reducing_gap, draft_box, (arr.shape[1], arr.shape[0]), rgba=mode == "RGBA")
+    if plan is None:
+        return image
+    arr = np.ascontiguousarray(arr)
+    h, w = arr.shape[:2]
+    c = _THUMB_MODES[mode]
+    new_w, new_h = plan.size
+    out = np.empty((new_h, new_w) if c == 1 else (new_h, new_w, c), dtype=np.uint8)
+    _ffi.call("lars_h_thumbnail_u8", _ffi.ptr(arr), h, w, c, plan.factor[0], plan.factor[1], (C.c_int * 4)(*plan.reduce_box),
+              (C.c_float * 4)(*plan.box), new_h, new_w, int(plan.vertical_first), _ffi.ptr(out))
+    if pil:
+        from PIL import Image
+        return Image.fromarray(out)
     return out
 
 

@@ -11,6 +11,11 @@
 // The weights are computed on the host with the same double arithmetic and libm sin() as Pillow
 // (-ffp-contract=off); the two passes and the alpha handling run on the GPU in integers, so the
 // result is bit-identical to Pillow's (tests/golden/resize_outputs.npz: outputs of the reference).
+//
+// The gallery thumbnail (Image.thumbnail(size, LANCZOS, reducing_gap), process-images.py:186-189) runs the same passes
+// over a fractional float box, after Pillow's integer Image.reduce (k_reduce, Reduce.c); the policy that picks the box,
+// the reduce factors and the pass order is host Python (api.thumbnail_plan).
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -107,7 +112,8 @@ __global__ __launch_bounds__(256) void k_unpremultiply_rgba(uint8_t *__restrict_
     }
 }
 
-// Resample.c: lanczos_filter / precompute_coeffs / normalize_coeffs_8bpc for the box (0, in_size)
+// Resample.c: lanczos_filter / precompute_coeffs / normalize_coeffs_8bpc for the box (in0, in1) of an axis of in_size
+// samples.  The box is float, as Pillow's C code holds it: in1 - in0 is a float subtraction.
 static double rs_sinc(double x)
 {
     if (x == 0.0) return 1.0;
@@ -119,9 +125,8 @@ static double rs_lanczos(double x)
     if (-3.0 <= x && x < 3.0) return rs_sinc(x) * rs_sinc(x / 3);
     return 0.0;
 }
-static int rs_coeffs(int in_size, int out_size, std::vector<int> &bounds, std::vector<int> &kk)
+static int rs_coeffs(int in_size, float in0, float in1, int out_size, std::vector<int> &bounds, std::vector<int> &kk)
 {
-    const float in0 = 0.0f, in1 = (float)in_size;
     const double scale = (double)(in1 - in0) / out_size;
     double filterscale = scale;
     if (filterscale < 1.0) filterscale = 1.0;
@@ -155,31 +160,183 @@ static int rs_coeffs(int in_size, int out_size, std::vector<int> &bounds, std::v
     return ksize;
 }
 
+// The passes of ImagingResampleInner: each runs only where its axis changes (need_h / need_v, Pillow's rule), horizontal
+// first, or vertical first for Image.resize's tall-image branch.  Returns the buffer that holds the result (src when
+// neither pass runs); tmp holds max(h * nw, nh * w) * C bytes.
 template <int C>
-static void launch_passes(hipStream_t s, const uint8_t *src, uint8_t *tmp, uint8_t *dst, int h, int w, int nh, int nw,
-                          const int *bh, const int *kh, int ksh, const int *bv, const int *kv, int ksv)
+static const uint8_t *launch_passes(hipStream_t s, const uint8_t *src, uint8_t *tmp, uint8_t *dst, int h, int w, int nh, int nw,
+                                    bool need_h, bool need_v, bool vertical_first, const int *bh, const int *kh, int ksh,
+                                    const int *bv, const int *kv, int ksv)
 {
+    auto grid = [](long long n) { return dim3((unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256)); };
     const uint8_t *cur = src;
-    if (nw != w) {
-        uint8_t *o = nh != h ? tmp : dst;
-        const long long n = (long long)h * nw;
-        hipLaunchKernelGGL((k_resample_h<C>), dim3((unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256)), dim3(256), 0, s, cur, o, h,
-                           w, nw, ksh, bh, kh);
+    if (vertical_first && need_v) {
+        uint8_t *o = need_h ? tmp : dst;
+        hipLaunchKernelGGL((k_resample_v<C>), grid((long long)nh * w), dim3(256), 0, s, cur, o, h, nh, w, ksv, bv, kv);
         cur = o;
+        h = nh;
     }
-    if (nh != h) {
-        const long long n = (long long)nh * nw;
-        hipLaunchKernelGGL((k_resample_v<C>), dim3((unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256)), dim3(256), 0, s, cur, dst,
-                           h, nh, nw, ksv, bv, kv);
+    if (need_h) {
+        uint8_t *o = need_v && !vertical_first ? tmp : dst;
+        hipLaunchKernelGGL((k_resample_h<C>), grid((long long)h * nw), dim3(256), 0, s, cur, o, h, w, nw, ksh, bh, kh);
+        cur = o;
+        w = nw;
     }
+    if (need_v && !vertical_first) {
+        hipLaunchKernelGGL((k_resample_v<C>), grid((long long)nh * w), dim3(256), 0, s, cur, dst, h, nh, w, ksv, bv, kv);
+        cur = dst;
+    }
+    return cur;
+}
+
+// Reduce.c (ImagingReduce and ImagingReduceCorners, 8 bits per channel) over the box [x0, x0 + bw) x [y0, y0 + bh) of
+// in [.][w_in][C]: output cell (ox, oy) = the fx x fy block from (x0 + ox * fx, y0 + oy * fy), clipped to the box (the
+// partial cells of the last column and row), out = ((sum + n / 2) * mult) >> 24 in uint32 for the block's n pixels.
+// mult = (uint32)(2^32 / (float)(256 n)) depends only on whether the cell is clipped in x, in y or both: the host
+// computes the four values in float32 as Pillow does.  Adjacent lanes take adjacent cells of a row, so a wave reads
+// one stretch of each source row.
+template <int C>
+__global__ __launch_bounds__(256) void k_reduce(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, int w_in, int x0, int y0,
+                                                int bw, int bh, int fx, int fy, int ow, int oh, unsigned int mult_full,
+                                                unsigned int mult_x, unsigned int mult_y, unsigned int mult_xy)
+{
+    const long long n = (long long)oh * ow;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const int oy = (int)(i / ow), ox = (int)(i - (long long)oy * ow);
+        const int cw = min(fx, bw - ox * fx), ch = min(fy, bh - oy * fy);
+        const uint8_t *p = in + ((long long)(y0 + oy * fy) * w_in + x0 + (long long)ox * fx) * C;
+        unsigned int acc[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = 0u;
+        for (int y = 0; y < ch; ++y) {
+            const uint8_t *row = p + (long long)y * w_in * C;
+            for (int x = 0; x < cw; ++x) {
+#pragma unroll
+                for (int c = 0; c < C; ++c) acc[c] += row[x * C + c];
+            }
+        }
+        const bool px = cw < fx, py = ch < fy;
+        const unsigned int mult = px ? (py ? mult_xy : mult_x) : (py ? mult_y : mult_full);
+        const unsigned int amend = (unsigned int)(cw * ch) / 2u;
+#pragma unroll
+        for (int c = 0; c < C; ++c) out[i * C + c] = (uint8_t)(((acc[c] + amend) * mult) >> 24);
+    }
+}
+
+// Reduce.c division_UINT32(n, 8)
+static unsigned int rd_mult(long long n)
+{
+    const float max_int = 4294967296.0f;
+    return (unsigned int)(max_int / (float)(unsigned int)(256 * n));
+}
+
+template <int C>
+static void launch_reduce(hipStream_t s, const uint8_t *in, uint8_t *out, int w_in, const int rb[4], int fx, int fy, int ow, int oh)
+{
+    const int bw = rb[2] - rb[0], bh = rb[3] - rb[1];
+    const int rx = bw % fx, ry = bh % fy;
+    const unsigned int m_full = rd_mult((long long)fx * fy), m_x = rd_mult((long long)(rx ? rx : fx) * fy),
+                       m_y = rd_mult((long long)fx * (ry ? ry : fy)), m_xy = rd_mult((long long)(rx ? rx : fx) * (ry ? ry : fy));
+    const long long n = (long long)ow * oh;
+    hipLaunchKernelGGL((k_reduce<C>), dim3((unsigned)((n + 255) / 256 > 8192 ? 8192 : (n + 255) / 256)), dim3(256), 0, s, in, out, w_in,
+                       rb[0], rb[1], bw, bh, fx, fy, ow, oh, m_full, m_x, m_y, m_xy);
 }
 
 }  // namespace lars
 
 using namespace lars;
 
+// Image.thumbnail(size, LANCZOS, reducing_gap) of a host uint8 image [h][w][channels] -- process-images.py:186-189, the
+// gallery thumbnails -- on the numbers of api.thumbnail_plan: premultiply (channels 4), Image.reduce((fx, fy)) over
+// reduce_box, the LANCZOS passes over the float box of the reduced image, un-premultiply.  One upload, one download.
+extern "C" int lars_h_thumbnail_u8(const uint8_t *img, int64_t h, int64_t w, int channels, int fx, int fy, const int reduce_box[4],
+                                   const float box[4], int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out)
+{
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!img || !out || !reduce_box || !box || h <= 0 || w <= 0 || new_h <= 0 || new_w <= 0 || h > (1 << 24) || w > (1 << 24) ||
+        new_h > (1 << 24) || new_w > (1 << 24) || fx < 1 || fy < 1 || (long long)fx * fy >= (1 << 24))
+        return fail(LARS_ERR_INVALID, "lars_h_thumbnail_u8: bad arguments");
+    if (channels != 1 && channels != 3 && channels != 4)
+        return fail(LARS_ERR_UNSUPPORTED, "lars_h_thumbnail_u8: 1, 3 or 4 channels (got %d)", channels);
+    const int *rb = reduce_box;
+    if (rb[0] < 0 || rb[1] < 0 || rb[2] > w || rb[3] > h || rb[2] <= rb[0] || rb[3] <= rb[1])
+        return fail(LARS_ERR_INVALID, "lars_h_thumbnail_u8: reduce box (%d, %d, %d, %d) outside the %lld x %lld image", rb[0], rb[1], rb[2],
+                    rb[3], (long long)w, (long long)h);
+    const bool reduce = fx != 1 || fy != 1 || rb[0] != 0 || rb[1] != 0 || rb[2] != w || rb[3] != h;
+    const int rw = (rb[2] - rb[0] + fx - 1) / fx, rh = (rb[3] - rb[1] + fy - 1) / fy;
+    // `!(a < b)` also refuses NaN
+    if (!(box[0] >= 0.0f) || !(box[1] >= 0.0f) || !(box[2] <= (float)rw) || !(box[3] <= (float)rh) || !(box[0] < box[2]) ||
+        !(box[1] < box[3]))
+        return fail(LARS_ERR_INVALID, "lars_h_thumbnail_u8: box outside the %d x %d reduced image", rw, rh);
+    // ImagingResampleInner's need_horizontal / need_vertical
+    const bool need_h = new_w != rw || box[0] != 0.0f || box[2] != (float)new_w;
+    const bool need_v = new_h != rh || box[1] != 0.0f || box[3] != (float)new_h;
+    std::vector<int> bh, kh, bv, kv;
+    const int ksh = need_h ? rs_coeffs(rw, box[0], box[2], (int)new_w, bh, kh) : 0;
+    const int ksv = need_v ? rs_coeffs(rh, box[1], box[3], (int)new_h, bv, kv) : 0;
+    const size_t in_bytes = (size_t)h * w * channels, red_bytes = reduce ? (size_t)rh * rw * channels : 0,
+                 tmp_bytes = std::max((size_t)rh * new_w, (size_t)new_h * rw) * channels, out_bytes = (size_t)new_h * new_w * channels;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t need = al(in_bytes) * (channels == 4 ? 2 : 1) + al(red_bytes) + al(tmp_bytes) + al(out_bytes) + al(bh.size() * 4) +
+                        al(kh.size() * 4) + al(bv.size() * 4) + al(kv.size() * 4) + 1024;
+    LARS_TRY(ws_reserve(c, need));
+    char *p = static_cast<char *>(c->ws);
+    uint8_t *d_in = reinterpret_cast<uint8_t *>(p); p += al(in_bytes);
+    uint8_t *d_pre = nullptr;
+    if (channels == 4) { d_pre = reinterpret_cast<uint8_t *>(p); p += al(in_bytes); }
+    uint8_t *d_red = reinterpret_cast<uint8_t *>(p); p += al(red_bytes);
+    uint8_t *d_tmp = reinterpret_cast<uint8_t *>(p); p += al(tmp_bytes);
+    uint8_t *d_out = reinterpret_cast<uint8_t *>(p); p += al(out_bytes);
+    int *d_bh = reinterpret_cast<int *>(p); p += al(bh.size() * 4);
+    int *d_kh = reinterpret_cast<int *>(p); p += al(kh.size() * 4);
+    int *d_bv = reinterpret_cast<int *>(p); p += al(bv.size() * 4);
+    int *d_kv = reinterpret_cast<int *>(p);
+    hipStream_t s = c->stream;
+    LARS_HIP_TRY(hipMemcpyAsync(d_in, img, in_bytes, hipMemcpyHostToDevice, s));
+    if (need_h) {
+        LARS_HIP_TRY(hipMemcpyAsync(d_bh, bh.data(), bh.size() * 4, hipMemcpyHostToDevice, s));
+        LARS_HIP_TRY(hipMemcpyAsync(d_kh, kh.data(), kh.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    if (need_v) {
+        LARS_HIP_TRY(hipMemcpyAsync(d_bv, bv.data(), bv.size() * 4, hipMemcpyHostToDevice, s));
+        LARS_HIP_TRY(hipMemcpyAsync(d_kv, kv.data(), kv.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    const uint8_t *cur = d_in;
+    if (channels == 4) {
+        const long long npix = (long long)h * w;
+        hipLaunchKernelGGL(k_premultiply_rgba, dim3((unsigned)((npix + 255) / 256 > 8192 ? 8192 : (npix + 255) / 256)), dim3(256), 0, s, d_in,
+                           d_pre, npix);
+        cur = d_pre;
+    }
+    if (reduce) {
+        if (channels == 1) launch_reduce<1>(s, cur, d_red, (int)w, rb, fx, fy, rw, rh);
+        else if (channels == 3) launch_reduce<3>(s, cur, d_red, (int)w, rb, fx, fy, rw, rh);
+        else launch_reduce<4>(s, cur, d_red, (int)w, rb, fx, fy, rw, rh);
+        cur = d_red;
+    }
+    const bool vfirst = vertical_first != 0;
+    if (channels == 1)
+        cur = launch_passes<1>(s, cur, d_tmp, d_out, rh, rw, (int)new_h, (int)new_w, need_h, need_v, vfirst, d_bh, d_kh, ksh, d_bv, d_kv, ksv);
+    else if (channels == 3)
+        cur = launch_passes<3>(s, cur, d_tmp, d_out, rh, rw, (int)new_h, (int)new_w, need_h, need_v, vfirst, d_bh, d_kh, ksh, d_bv, d_kv, ksv);
+    else
+        cur = launch_passes<4>(s, cur, d_tmp, d_out, rh, rw, (int)new_h, (int)new_w, need_h, need_v, vfirst, d_bh, d_kh, ksh, d_bv, d_kv, ksv);
+    if (channels == 4) {
+        // cur is d_pre, d_red, d_tmp or d_out here: never the caller's upload
+        const long long npix = (long long)new_h * new_w;
+        hipLaunchKernelGGL(k_unpremultiply_rgba, dim3((unsigned)((npix + 255) / 256 > 8192 ? 8192 : (npix + 255) / 256)), dim3(256), 0, s,
+                           const_cast<uint8_t *>(cur), npix);
+    }
+    LARS_TRY(launch_check("lars_h_thumbnail_u8"));
+    LARS_HIP_TRY(hipMemcpyAsync(out, cur, out_bytes, hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipStreamSynchronize(s));
+    return LARS_OK;
+}
+
 // PIL.Image.resize((new_w, new_h), LANCZOS) of a host uint8 image [h][w][channels], channels 1, 3 or 4
-// (4 = RGBA: premultiplied-alpha path) -- the arithmetic of preprocess_large_image, process-images.py:419-420.
+// (4 = RGBA: premultiplied-alpha path) -- the arithmetic of preprocess_large_image, process-images.py:419-420: what
+// lars_h_thumbnail_u8 computes with no reduce and the whole image as the box.
 extern "C" int lars_h_resize_lanczos_u8(const uint8_t *img, int64_t h, int64_t w, int channels, int64_t new_h, int64_t new_w,
                                         uint8_t *out)
 {
@@ -189,53 +346,7 @@ extern "C" int lars_h_resize_lanczos_u8(const uint8_t *img, int64_t h, int64_t w
         return fail(LARS_ERR_INVALID, "lars_h_resize_lanczos_u8: bad arguments");
     if (channels != 1 && channels != 3 && channels != 4)
         return fail(LARS_ERR_UNSUPPORTED, "lars_h_resize_lanczos_u8: 1, 3 or 4 channels (got %d)", channels);
-    std::vector<int> bh, kh, bv, kv;
-    const int ksh = rs_coeffs((int)w, (int)new_w, bh, kh);
-    const int ksv = rs_coeffs((int)h, (int)new_h, bv, kv);
-    const size_t in_bytes = (size_t)h * w * channels, tmp_bytes = (size_t)h * new_w * channels,
-                 out_bytes = (size_t)new_h * new_w * channels;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t need = al(in_bytes) * 2 + al(tmp_bytes) + al(out_bytes) + al(bh.size() * 4) + al(kh.size() * 4) + al(bv.size() * 4) +
-                        al(kv.size() * 4) + 1024;
-    LARS_TRY(ws_reserve(c, need));
-    char *p = static_cast<char *>(c->ws);
-    uint8_t *d_in = reinterpret_cast<uint8_t *>(p); p += al(in_bytes);
-    uint8_t *d_pre = reinterpret_cast<uint8_t *>(p); p += al(in_bytes);
-    uint8_t *d_tmp = reinterpret_cast<uint8_t *>(p); p += al(tmp_bytes);
-    uint8_t *d_out = reinterpret_cast<uint8_t *>(p); p += al(out_bytes);
-    int *d_bh = reinterpret_cast<int *>(p); p += al(bh.size() * 4);
-    int *d_kh = reinterpret_cast<int *>(p); p += al(kh.size() * 4);
-    int *d_bv = reinterpret_cast<int *>(p); p += al(bv.size() * 4);
-    int *d_kv = reinterpret_cast<int *>(p);
-    hipStream_t s = c->stream;
-    LARS_HIP_TRY(hipMemcpyAsync(d_in, img, in_bytes, hipMemcpyHostToDevice, s));
-    LARS_HIP_TRY(hipMemcpyAsync(d_bh, bh.data(), bh.size() * 4, hipMemcpyHostToDevice, s));
-    LARS_HIP_TRY(hipMemcpyAsync(d_kh, kh.data(), kh.size() * 4, hipMemcpyHostToDevice, s));
-    LARS_HIP_TRY(hipMemcpyAsync(d_bv, bv.data(), bv.size() * 4, hipMemcpyHostToDevice, s));
-    LARS_HIP_TRY(hipMemcpyAsync(d_kv, kv.data(), kv.size() * 4, hipMemcpyHostToDevice, s));
-    const uint8_t *src = d_in;
-    if (channels == 4) {
-        const long long npix = (long long)h * w;
-        hipLaunchKernelGGL(k_premultiply_rgba, dim3((unsigned)((npix + 255) / 256 > 8192 ? 8192 : (npix + 255) / 256)), dim3(256), 0, s, d_in,
-                           d_pre, npix);
-        src = d_pre;
-    }
-    if (new_h == h && new_w == w) {
-        LARS_HIP_TRY(hipMemcpyAsync(d_out, src, in_bytes, hipMemcpyDeviceToDevice, s));
-    } else if (channels == 1) {
-        launch_passes<1>(s, src, d_tmp, d_out, (int)h, (int)w, (int)new_h, (int)new_w, d_bh, d_kh, ksh, d_bv, d_kv, ksv);
-    } else if (channels == 3) {
-        launch_passes<3>(s, src, d_tmp, d_out, (int)h, (int)w, (int)new_h, (int)new_w, d_bh, d_kh, ksh, d_bv, d_kv, ksv);
-    } else {
-        launch_passes<4>(s, src, d_tmp, d_out, (int)h, (int)w, (int)new_h, (int)new_w, d_bh, d_kh, ksh, d_bv, d_kv, ksv);
-    }
-    if (channels == 4) {
-        const long long npix = (long long)new_h * new_w;
-        hipLaunchKernelGGL(k_unpremultiply_rgba, dim3((unsigned)((npix + 255) / 256 > 8192 ? 8192 : (npix + 255) / 256)), dim3(256), 0, s,
-                           d_out, npix);
-    }
-    LARS_TRY(launch_check("lars_h_resize_lanczos_u8"));
-    LARS_HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    return LARS_OK;
+    const int whole[4] = {0, 0, (int)w, (int)h};
+    const float box[4] = {0.0f, 0.0f, (float)w, (float)h};
+    return lars_h_thumbnail_u8(img, h, w, channels, 1, 1, whole, box, new_h, new_w, 0, out);
 }
