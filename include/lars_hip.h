@@ -449,6 +449,35 @@ int lars_h_change_detection(const uint8_t *early, const uint8_t *late, int64_t h
 int lars_h_colormap_norm_f32(const float *x, int64_t n, float vmin, float vmax, const uint8_t *lut_rgba,
                              uint8_t *out_rgba);
 
+/* PNG files of 8-bit pictures, built on the device -- the Image.fromarray(x).save(png) that ends every index picture of the
+ * batch driver (backend-process.py:49-73) and of the ZIP export (process-images.py:567-617).  img is uint8 [h][w][channels]:
+ * 1 (L, or P when palette_rgba is given: palette_len RGBA entries, written as PLTE + tRNS), 3 (RGB) or 4 (RGBA); 8 bits,
+ * no interlace, 1 <= h, w <= 2^24.  The pixels decode exactly to img; the compressed bytes are this library's own (libpng's
+ * filter heuristic per row, one literal-only dynamic Huffman block per 32 KiB of filtered data, one IDAT chunk each).  The
+ * same input always gives the same bytes.
+ * lars_png_bound: the largest file any input of that shape can give (0 for a shape that cannot be encoded); pure host code.
+ * lars_png_scratch_bytes: device scratch of lars_d_encode_png_u8.
+ * lars_d_encode_png_u8: device img / palette_rgba / out (out_cap >= lars_png_bound) / scratch; enqueues on stream and
+ * writes the file's length to the device int64 *out_len_dev.
+ * lars_h_encode_png_u8: host img / palette_rgba / out; one upload, then the length, then out_len bytes into out. */
+size_t lars_png_bound(int64_t h, int64_t w, int channels);
+size_t lars_png_scratch_bytes(int64_t h, int64_t w, int channels);
+int lars_d_encode_png_u8(const uint8_t *img, int64_t h, int64_t w, int channels, const uint8_t *palette_rgba, int palette_len,
+                         uint8_t *out, size_t out_cap, int64_t *out_len_dev, void *scratch, void *stream);
+int lars_h_encode_png_u8(const uint8_t *img, int64_t h, int64_t w, int channels, const uint8_t *palette_rgba, int palette_len,
+                         uint8_t *out, size_t out_cap, int64_t *out_len);
+/* lars_h_process_image with every requested index picture encoded as a PNG on the device (backend-process.py:49-73 per
+ * file): png_mode 1 encodes the RGBA colormap picture of cmap_lut[k], png_mode 2 a palette (P) picture of the colormap
+ * entries with cmap_lut[k] as its 256-entry palette.  cmap_lut[k] and out_png[k] (host, png_cap bytes, at least
+ * lars_png_bound(h, w, 4) or (h, w, 1)) are needed for every index in index_mask; png_len[k] receives the file's length.
+ * The colormap planes never leave the device. */
+int lars_h_process_image_png(const void *img, int64_t h, int64_t w, int channels, int dtype,
+                             int apply_wb, uint32_t index_mask, int want_hist,
+                             uint8_t *out_wb, float *const out_index[3],
+                             lars_stats *stats /* [3] */, float *medians /* [3][2] */,
+                             const uint8_t *const cmap_lut[3], int png_mode,
+                             uint8_t *const out_png[3], size_t png_cap, int64_t png_len[3]);
+
 /* ------------------------------------------------------------------ image files (host only, no GPU work) */
 /* TIFF 6.0 LZW (compression 5, MSB-first codes, early width change) of one strip / tile: decodes at most ndst bytes
  * into dst, *nout = bytes produced.  For lars_image_processing_amd/tiffio.py, which reads the multi-sample 16-bit

@@ -19,6 +19,7 @@ from .api import (  # noqa: F401
     colorize_index,
     colormap_lut,
     correct_white_balance,
+    encode_png,
     download_processed_images,
     fix_white_balance,
     fix_white_balance_rgnir,

@@ -17,6 +17,7 @@ this module                     reference
 ``analyze_ndvi_statistics``     process-ndvi.py:50
 ``preprocess_large_image``      process-images.py:398  (Pillow LANCZOS down-scale)
 ``thumbnail``                   process-images.py:186  (Pillow LANCZOS gallery thumbnail; a new object, not in place)
+``encode_png``                  backend-process.py:70, process-images.py:567-617 (``Image.fromarray(x).save(png)``: same pixels)
 ``align_images``                process-images.py:515  (phase correlation + shift)
 ``calculate_index_statistics_by_timeframe``  process-images.py:619 (pandas table)
 ``time_series_points``          process-images.py:814-832 (the numbers ``create_time_series_plot`` draws)
@@ -53,7 +54,7 @@ __all__ = [
     "fix_white_balance", "correct_white_balance", "fix_white_balance_rgnir",
     "calculate_index", "calculate_ndvi", "analyze_index", "analyze_index_statistics",
     "analyze_ndvi_statistics", "index_histogram", "classification_mask", "colorize_index", "process_image",
-    "timeseries_row", "colormap_lut", "preprocess_large_image", "thumbnail", "thumbnail_plan", "align_images", "change_detection",
+    "timeseries_row", "colormap_lut", "preprocess_large_image", "thumbnail", "thumbnail_plan", "encode_png", "align_images", "change_detection",
     "colorize_difference", "calculate_index_statistics_by_timeframe", "time_series_points",
     "calculate_ndvi_array", "generate_ndvi_report", "download_processed_images",
     "create_index_visualization", "create_comparison_view", "create_time_series_plot", "create_change_detection_visualization",
@@ -494,8 +495,54 @@ def colorize_index(index_array, index_type):
     return out
 
 
+# ---------------------------------------------------------------------------
+# PNG files built on the device
+# ---------------------------------------------------------------------------
+_PNG_CHANNELS = (1, 3, 4)
+
+
+def png_bound(h, w, channels):
+    """The largest file ``encode_png`` can return for an ``h x w`` picture of ``channels`` samples (``lars_png_bound``;
+    host code, no device needed)."""
+    return int(_ffi.load().lars_png_bound(int(h), int(w), int(channels)))
+
+
+def encode_png(array, palette=None):
+    """PNG file (``bytes``) of a uint8 picture, encoded on the GPU: ``[H, W]`` (mode L), ``[H, W, 3]`` (RGB) or ``[H, W, 4]``
+    (RGBA); with ``palette`` (``N x 4`` uint8 RGBA, N <= 256) a ``[H, W]`` array is written as mode P with PLTE + tRNS.
+
+    ``Image.open(io.BytesIO(b))`` gives back exactly ``array`` (``.convert("RGBA")`` the palette's colours for P); the
+    compressed bytes are not zlib's.  The same input always gives the same bytes.  What ``Image.fromarray(array).save(f,
+    "PNG")`` does at the end of every index picture (backend-process.py:70) and ZIP entry (process-images.py:567-617).
+    """
+    arr = np.asarray(array)
+    if arr.dtype != np.uint8:
+        raise TypeError(f"encode_png: uint8 pictures only, got {arr.dtype}")
+    if arr.ndim == 3 and arr.shape[2] == 1:
+        arr = arr[:, :, 0]
+    if arr.ndim not in (2, 3) or (arr.ndim == 3 and arr.shape[2] not in _PNG_CHANNELS):
+        raise ValueError(f"encode_png: shape [H, W], [H, W, 3] or [H, W, 4] expected, got {arr.shape}")
+    h, w = arr.shape[:2]
+    c = 1 if arr.ndim == 2 else arr.shape[2]
+    if not (1 <= h <= 1 << 24 and 1 <= w <= 1 << 24):
+        raise ValueError(f"encode_png: {h} x {w} picture (1 to 2^24 on each side)")
+    pal, npal = None, 0
+    if palette is not None:
+        pal = np.ascontiguousarray(np.asarray(palette), dtype=np.uint8)
+        if c != 1:
+            raise ValueError("encode_png: a palette needs a [H, W] array of entries")
+        if pal.ndim != 2 or pal.shape[1] != 4 or not 1 <= pal.shape[0] <= 256:
+            raise ValueError(f"encode_png: palette must be N x 4 RGBA with 1 <= N <= 256, got {pal.shape}")
+        npal = pal.shape[0]
+    arr = np.ascontiguousarray(arr)
+    out = np.empty(png_bound(h, w, c), dtype=np.uint8)
+    n = C.c_int64(0)
+    _ffi.call("lars_h_encode_png_u8", _ffi.ptr(arr), h, w, c, _ffi.ptr(pal), npal, _ffi.ptr(out), out.nbytes, C.byref(n))
+    return out[:n.value].tobytes()
+
+
 def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_arrays=True, want_hist=False,
-                  want_rgba=False, want_entries=False):
+                  want_rgba=False, want_entries=False, want_png=False):
     """White balance -> indices -> statistics of one image in ONE upload.
 
     What the Streamlit comparison path does with three separate calls per index
@@ -505,7 +552,15 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
     ``want_rgba``) returns ``entry``: the colormap entry of every pixel, uint8 ``[h, w]``, computed on the
     device -- ``colormap_lut(name)[entry]`` is the RGBA image, and a palette PNG needs nothing else
     (one byte per pixel crosses PCIe; backend-process.py:40-47 per pixel).
+    ``want_png=True`` adds ``png``: the PNG file (``bytes``) of the RGBA colormap picture, encoded on the device
+    (``encode_png``); ``want_png="palette"`` a mode-P file of the colormap entries with the colormap as its palette.  Either
+    way only the file crosses PCIe.
     """
+    png_mode = 0 if want_png is False else 1 if want_png is True else 2 if isinstance(want_png, str) and want_png == "palette" else None
+    if png_mode is None:
+        raise ValueError(f"process_image: want_png must be False, True or 'palette', got {want_png!r}")
+    if png_mode and (want_rgba or want_entries):
+        raise ValueError("process_image: want_png replaces want_rgba / want_entries (the pictures stay on the device)")
     if want_rgba and want_entries:
         raise ValueError("process_image: want_rgba or want_entries, not both (they share the output slot of the C ABI)")
     arr = _as_image(img_array, "process_image")
@@ -532,9 +587,23 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
             rgbas[k] = _empty((h, w), dtype=np.uint8)          # no table: the entry plane comes back in the RGBA slot
     stats = (Stats * 3)()
     med = np.zeros((3, 2), dtype=np.float32)
-    p_out, p_rgba, p_lut = _ffi.ptr3(outs), _ffi.ptr3(rgbas), _ffi.ptr3(luts)
-    _ffi.call("lars_h_process_image", _ffi.ptr(arr), h, w, c, code, int(bool(white_balance)), mask, int(want_hist),
-              _ffi.ptr(out_wb), C.byref(p_out), C.byref(stats), _ffi.ptr(med), C.byref(p_rgba), C.byref(p_lut))
+    pngs = [None] * 3
+    if png_mode:
+        cap = png_bound(h, w, 4 if png_mode == 1 else 1)
+        for t in indices:
+            k = INDEX_IDS[t]
+            luts[k] = colormap_lut(_colormap_for(t))
+            pngs[k] = np.empty(cap, dtype=np.uint8)
+        lens = np.zeros(3, dtype=np.int64)
+        p_out, p_lut, p_png = _ffi.ptr3(outs), _ffi.ptr3(luts), _ffi.ptr3(pngs)
+        _ffi.call("lars_h_process_image_png", _ffi.ptr(arr), h, w, c, code, int(bool(white_balance)), mask, int(want_hist),
+                  _ffi.ptr(out_wb), C.byref(p_out), C.byref(stats), _ffi.ptr(med), C.byref(p_lut), png_mode, C.byref(p_png), cap,
+                  _ffi.ptr(lens))
+        pngs = [None if p is None else p[:lens[k]].tobytes() for k, p in enumerate(pngs)]
+    else:
+        p_out, p_rgba, p_lut = _ffi.ptr3(outs), _ffi.ptr3(rgbas), _ffi.ptr3(luts)
+        _ffi.call("lars_h_process_image", _ffi.ptr(arr), h, w, c, code, int(bool(white_balance)), mask, int(want_hist),
+                  _ffi.ptr(out_wb), C.byref(p_out), C.byref(stats), _ffi.ptr(med), C.byref(p_rgba), C.byref(p_lut))
     result = {"corrected": out_wb, "indices": {}}
     for t in indices:
         k = INDEX_IDS[t]
@@ -545,6 +614,7 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
             "index": outs[k],
             "rgba": rgbas[k] if want_rgba else None,
             "entry": rgbas[k] if want_entries else None,
+            "png": pngs[k],
             "hist": np.array(list(st.hist), dtype=np.int64) if want_hist else None,
             "stats": {
                 f"Mean {t}": st.sum / st.count,

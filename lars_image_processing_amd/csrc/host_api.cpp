@@ -39,6 +39,10 @@ struct ImageJob {
     uint8_t *out_rgba[3];
     const uint8_t *cmap[3];
     double *pcts;                 // [3][2]
+    int png_mode;                 // 0 none, 1 RGBA colormap pictures, 2 palette pictures of the colormap entries (PNG on the device)
+    uint8_t *out_png[3];
+    size_t png_cap;
+    int64_t *png_len;             // [3]
 };
 
 struct Layout {
@@ -46,6 +50,9 @@ struct Layout {
     float *idx[3]; lars_stats *stats; float *med; char *sel; uint8_t *rgba[3]; uint8_t *cmap[3];
     uint8_t *entry[3];             // colormap entry planes (out_rgba[k] without a cmap_lut[k]): one byte per pixel
     float *pairs; char *selq;      // statistics + medians without planes (lars_d_stats_medians)
+    uint8_t *png[3], *pal[3];      // PNG files of the index pictures, palettes of the P pictures
+    int64_t *png_len; char *png_scratch;
+    size_t png_bound;
     size_t total;
 };
 
@@ -60,7 +67,7 @@ bool select_route(const ImageJob &j)
 // the planes never exist on the device either
 bool recompute_route(const ImageJob &j)
 {
-    if (!select_route(j) || !j.want_stats) return false;
+    if (!select_route(j) || !j.want_stats || j.png_mode) return false;
     if (j.mask != 1u && j.mask != 2u && j.mask != 4u && j.mask != 7u) return false;
     for (int k = 0; k < 3; ++k)
         if (j.out_index[k] || j.out_rgba[k]) return false;
@@ -81,14 +88,22 @@ Layout plan(const ImageJob &j, void *base)
     L.pcts = j.apply_wb ? c.take<double>(6) : nullptr;
     L.wb = (j.apply_wb && j.out_wb) ? c.take<uint8_t>(npix * j.channels) : nullptr;
     const bool select = select_route(j);
+    const int png_channels = j.png_mode == 1 ? 4 : 1;
+    L.png_bound = j.png_mode ? lars_png_bound(j.h, j.w, png_channels) : 0;
     for (int k = 0; k < 3; ++k) {
         const bool on = (j.mask >> k) & 1u;
-        const bool entries = on && j.out_rgba[k] && !j.cmap[k];             // the entry plane is derived from the float32 plane on the device
+        // the entry plane is derived from the float32 plane on the device
+        const bool entries = on && ((j.out_rgba[k] && !j.cmap[k]) || j.png_mode == 2);
+        const bool rgba = on && j.cmap[k] && (j.out_rgba[k] || j.png_mode == 1);
         L.idx[k] = (on && (j.out_index[k] || entries || (j.want_median && !select))) ? c.take<float>(npix) : nullptr;
-        L.rgba[k] = (on && j.out_rgba[k] && j.cmap[k]) ? c.take<uint8_t>(npix * 4) : nullptr;
-        L.cmap[k] = (on && j.out_rgba[k] && j.cmap[k]) ? c.take<uint8_t>(1024) : nullptr;
+        L.rgba[k] = rgba ? c.take<uint8_t>(npix * 4) : nullptr;
+        L.cmap[k] = rgba ? c.take<uint8_t>(1024) : nullptr;
         L.entry[k] = entries ? c.take<uint8_t>(npix + 4) : nullptr;
+        L.pal[k] = (on && j.png_mode == 2) ? c.take<uint8_t>(1024) : nullptr;
+        L.png[k] = (on && j.png_mode) ? c.take<uint8_t>(L.png_bound) : nullptr;
     }
+    L.png_len = j.png_mode ? c.take<int64_t>(3) : nullptr;
+    L.png_scratch = j.png_mode ? c.take<char>(lars_png_scratch_bytes(j.h, j.w, png_channels)) : nullptr;
     L.stats = c.take<lars_stats>(3);
     L.med = c.take<float>(6);
     L.sel = c.take<char>(3 * ((lars_select_scratch_bytes() + 255) & ~(size_t)255));
@@ -160,12 +175,19 @@ int run_image(const ImageJob &j)
     for (int k = 0; k < 3; ++k) {
         if (!((j.mask >> k) & 1u)) continue;
         if (j.out_index[k]) LARS_HIP_TRY(hipMemcpyAsync(j.out_index[k], L.idx[k], npix * 4, hipMemcpyDeviceToHost, s));
-        if (L.rgba[k]) LARS_HIP_TRY(hipMemcpyAsync(j.out_rgba[k], L.rgba[k], npix * 4, hipMemcpyDeviceToHost, s));
+        if (L.rgba[k] && j.out_rgba[k]) LARS_HIP_TRY(hipMemcpyAsync(j.out_rgba[k], L.rgba[k], npix * 4, hipMemcpyDeviceToHost, s));
         if (L.entry[k]) {                                   // one byte per pixel crosses PCIe instead of four (or a float32 plane)
             LARS_TRY(lars_d_colormap_entry_f32(L.idx[k], (int64_t)npix, L.entry[k], s));
-            LARS_HIP_TRY(hipMemcpyAsync(j.out_rgba[k], L.entry[k], npix, hipMemcpyDeviceToHost, s));
+            if (j.out_rgba[k]) LARS_HIP_TRY(hipMemcpyAsync(j.out_rgba[k], L.entry[k], npix, hipMemcpyDeviceToHost, s));
+        }
+        if (L.png[k]) {                                     // the picture stays on the device; only its PNG file crosses PCIe
+            if (L.pal[k]) LARS_HIP_TRY(hipMemcpyAsync(L.pal[k], j.cmap[k], 1024, hipMemcpyHostToDevice, s));
+            LARS_TRY(lars_d_encode_png_u8(j.png_mode == 1 ? L.rgba[k] : L.entry[k], j.h, j.w, j.png_mode == 1 ? 4 : 1, L.pal[k],
+                                          L.pal[k] ? 256 : 0, L.png[k], L.png_bound, L.png_len + k, L.png_scratch, s));
         }
     }
+    int64_t hlen[3] = {0, 0, 0};
+    if (L.png_len) LARS_HIP_TRY(hipMemcpyAsync(hlen, L.png_len, sizeof hlen, hipMemcpyDeviceToHost, s));
     lars_stats hstats[3];
     float hmed[6];
     double hp[6];
@@ -189,6 +211,16 @@ int run_image(const ImageJob &j)
         if (j.want_median && j.medians) { j.medians[2 * k] = hmed[2 * k]; j.medians[2 * k + 1] = hmed[2 * k + 1]; }
     }
     if (j.apply_wb && j.pcts) memcpy(j.pcts, hp, sizeof hp);
+    if (j.png_mode) {
+        for (int k = 0; k < 3; ++k) {
+            if (!L.png[k]) continue;
+            if (hlen[k] <= 0 || (size_t)hlen[k] > j.png_cap)
+                return fail(LARS_ERR_HIP, "lars_h_process_image_png: file %d has %lld bytes (capacity %zu)", k, (long long)hlen[k], j.png_cap);
+            LARS_HIP_TRY(hipMemcpyAsync(j.out_png[k], L.png[k], (size_t)hlen[k], hipMemcpyDeviceToHost, s));
+        }
+        LARS_HIP_TRY(hipStreamSynchronize(s));
+        for (int k = 0; k < 3; ++k) j.png_len[k] = L.png[k] ? hlen[k] : 0;
+    }
     return LARS_OK;
 }
 
@@ -270,6 +302,36 @@ int lars_h_process_image(const void *img, int64_t h, int64_t w, int channels, in
     j.stats = stats; j.want_stats = stats != nullptr; j.want_hist = want_hist;
     j.medians = medians; j.want_median = medians != nullptr;
     if (!index_mask && !(apply_wb && out_wb)) return fail(LARS_ERR_INVALID, "lars_h_process_image: nothing requested");
+    return run_image(j);
+}
+
+int lars_h_process_image_png(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                             int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                             const uint8_t *const cmap_lut[3], int png_mode, uint8_t *const out_png[3], size_t png_cap,
+                             int64_t png_len[3])
+{
+    if (png_mode != 1 && png_mode != 2) return fail(LARS_ERR_INVALID, "lars_h_process_image_png: png_mode must be 1 (RGBA) or 2 (P)");
+    if (!index_mask || (index_mask & ~LARS_MASK_ALL) || !cmap_lut || !out_png || !png_len)
+        return fail(LARS_ERR_INVALID, "lars_h_process_image_png: indices, colormaps and PNG outputs are required");
+    if (h <= 0 || w <= 0 || h > (1 << 24) || w > (1 << 24))
+        return fail(LARS_ERR_INVALID, "lars_h_process_image_png: %lld x %lld image", (long long)h, (long long)w);
+    const size_t bound = lars_png_bound(h, w, png_mode == 1 ? 4 : 1);
+    for (int k = 0; k < 3; ++k)
+        if (((index_mask >> k) & 1u) && (!cmap_lut[k] || !out_png[k]))
+            return fail(LARS_ERR_INVALID, "lars_h_process_image_png: index %d needs cmap_lut and out_png", k);
+    if (png_cap < bound) return fail(LARS_ERR_INVALID, "lars_h_process_image_png: png_cap %zu < lars_png_bound %zu", png_cap, bound);
+    ImageJob j;
+    memset(&j, 0, sizeof j);
+    j.img = img; j.h = h; j.w = w; j.channels = channels; j.dtype = dtype;
+    j.apply_wb = apply_wb; j.mask = index_mask; j.out_wb = out_wb;
+    for (int k = 0; k < 3; ++k) {
+        j.out_index[k] = out_index ? out_index[k] : nullptr;
+        j.cmap[k] = cmap_lut[k];
+        j.out_png[k] = out_png[k];
+    }
+    j.stats = stats; j.want_stats = stats != nullptr; j.want_hist = want_hist;
+    j.medians = medians; j.want_median = medians != nullptr;
+    j.png_mode = png_mode; j.png_cap = png_cap; j.png_len = png_len;
     return run_image(j);
 }
 

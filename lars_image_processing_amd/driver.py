@@ -25,18 +25,27 @@ EXTENSIONS = {".tif", ".tiff", ".png", ".jpg", ".jpeg"}      # backend-process.p
 # zlib level of the per-pixel colormap PNGs: encoding, not the GPU, bounds the directory driver (a 2048x2048 RGBA map takes
 # 1.2 s at Pillow's default level 6 and 0.6 s at level 1, for a smaller file on colormap images); same pixels either way
 LUT_PNG_LEVEL = 1
+PNG_ENCODERS = ("pillow", "device")
 
 
-def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png"):
+def _check_png_encoder(png_encoder):
+    if png_encoder not in PNG_ENCODERS:
+        raise ValueError(f"png_encoder must be 'pillow' or 'device', got {png_encoder!r}")
+
+
+def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png",
+                  png_encoder="pillow"):
     """One file: same outputs as backend-process.py:49-73.  Returns the statistics dicts.
     ``full_depth=True`` reads three-sample 16-bit TIFFs at their full depth (``tiffio.read_image``; Pillow, hence the
     reference, keeps their high bytes only).  ``lut_format="tiff"`` writes the colormap images as
     uncompressed RGBA TIFFs ``<name>_<index>.tif`` instead of PNGs: PNG compression of a 4096 x 4096 map takes seconds,
     the GPU work milliseconds.  ``lut_format="png8"`` writes palette PNGs (one byte per pixel = the colormap entry, the
     colormap as the palette): ``Image.open(p).convert("RGBA")`` gives the pixels of the RGBA file, from a quarter of the
-    bytes to compress."""
+    bytes to compress.  ``png_encoder="device"`` encodes the PNG / png8 pictures on the GPU (``api.encode_png``: same pixels,
+    only the files cross PCIe) instead of with Pillow."""
     if lut_format not in ("png", "png8", "tiff"):
         raise ValueError(f"lut_format must be 'png', 'png8' or 'tiff', got {lut_format!r}")
+    _check_png_encoder(png_encoder)
     from PIL import Image
     from .tiffio import read_image
     image_path, output_dir = Path(image_path), Path(output_dir)
@@ -46,9 +55,14 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
         raise ValueError(f"{image_path.name}: expected an image with at least 3 channels, got shape {arr.shape}")
     indices = list(indices or [])
     palette = lut_format == "png8"
-    # palette files: the colormap entry of every pixel comes from the device, one byte per pixel (lars_h_process_image)
-    res = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False, want_rgba=not palette,
-                            want_entries=palette) if indices else None
+    device_png = png_encoder == "device" and lut_format != "tiff"
+    if device_png:                                  # the pictures stay on the device, their PNG files come back
+        res = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False,
+                                want_png="palette" if palette else True) if indices else None
+    else:
+        # palette files: the colormap entry of every pixel comes from the device, one byte per pixel (lars_h_process_image)
+        res = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False, want_rgba=not palette,
+                                want_entries=palette) if indices else None
     corrected = res["corrected"] if res else api.fix_white_balance(arr)
     if process_wb:
         (output_dir / "white_balanced").mkdir(parents=True, exist_ok=True)
@@ -59,7 +73,9 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
         (output_dir / t).mkdir(parents=True, exist_ok=True)
         out = output_dir / t / f"{name}_{t.lower()}.png"
         entry = res["indices"][t]
-        if lut_format == "tiff":
+        if device_png:
+            out.write_bytes(entry["png"])
+        elif lut_format == "tiff":
             from .tiffio import write_tiff
             write_tiff(out.with_suffix(".tif"), entry["rgba"])
         elif palette:
@@ -86,11 +102,13 @@ def files_of_rank(files, rank=0, world=1):
 
 def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, process_gndvi=False,
                   process_ndwi=True, workers=4, verbose=True, full_depth=False, lut_format="png", rank=0, world=1,
-                  device=None):
+                  device=None, png_encoder="pillow"):
     """backend-process.py:75-97 with its module constants as arguments.  Returns ``{file name: stats | error}``.
     ``rank`` / ``world``: one process per GPU, each takes its block of the sorted file list (``files_of_rank``); the output
     directories are shared, the file names distinct.  ``device``: the GPU ordinal every worker thread binds (the library's
-    context is per thread and defaults to device 0); None leaves the threads' binding alone."""
+    context is per thread and defaults to device 0); None leaves the threads' binding alone.  ``png_encoder``: see
+    ``process_image``."""
+    _check_png_encoder(png_encoder)
     input_path, output_path = Path(input_dir), Path(output_dir)
     indices = [t for t, on in (("NDVI", process_ndvi), ("GNDVI", process_gndvi), ("NDWI", process_ndwi)) if on]
     files = files_of_rank(sorted(f for f in input_path.glob("*") if f.suffix.lower() in EXTENSIONS), rank, world)
@@ -102,7 +120,7 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
         try:
             if verbose:
                 print(f"Processing {idx}/{total}: {f.name}")
-            return f.name, process_image(f, output_path, process_wb, indices or None, full_depth, lut_format)
+            return f.name, process_image(f, output_path, process_wb, indices or None, full_depth, lut_format, png_encoder)
         except Exception as e:                              # same policy as upstream :96-97
             if verbose:
                 print(f"Error processing {f.name}: {str(e)}")
@@ -125,29 +143,39 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
     return results
 
 
-def export_zip(image_array, selected_indices, corrected_array=None):
+def export_zip(image_array, selected_indices, corrected_array=None, png_encoder="pillow"):
     """ZIP of the processed images of one upload (``download_processed_images``,
     process-images.py:567-617): ``white_balanced.png`` + ``<INDEX>_visualization.png`` per index, the latter as
     full-resolution per-pixel colormap images (one GPU pass for white balance, every index and every colormap).
     ``corrected_array`` (the cached white-balanced image the UI keeps, process-images.py:1132) skips the
-    white-balance step.
+    white-balance step.  ``png_encoder="device"`` encodes every PNG of the archive on the GPU (``api.encode_png``; same
+    pixels): the colormap pictures never leave the device.
     """
+    _check_png_encoder(png_encoder)
     import io
     import zipfile
     from PIL import Image
     indices = list(selected_indices)
+    device = png_encoder == "device"
+    want = {"want_png": True} if device else {"want_rgba": True}
     if corrected_array is not None:
-        res = api.process_image(np.asarray(corrected_array), indices=indices, white_balance=False, want_arrays=False, want_rgba=True)
+        res = api.process_image(np.asarray(corrected_array), indices=indices, white_balance=False, want_arrays=False, **want)
         corrected = np.asarray(corrected_array)
     else:
-        res = api.process_image(np.asarray(image_array), indices=indices, white_balance=True, want_arrays=False, want_rgba=True)
+        res = api.process_image(np.asarray(image_array), indices=indices, white_balance=True, want_arrays=False, **want)
         corrected = res["corrected"]
     buf = io.BytesIO()
     with zipfile.ZipFile(buf, "w", zipfile.ZIP_DEFLATED) as zf:
-        png = io.BytesIO()
-        Image.fromarray(corrected).save(png, format="PNG")
-        zf.writestr("white_balanced.png", png.getvalue())
+        if device:
+            zf.writestr("white_balanced.png", api.encode_png(corrected))
+        else:
+            png = io.BytesIO()
+            Image.fromarray(corrected).save(png, format="PNG")
+            zf.writestr("white_balanced.png", png.getvalue())
         for t in indices:
+            if device:
+                zf.writestr(f"{t}_visualization.png", res["indices"][t]["png"])
+                continue
             png = io.BytesIO()
             Image.fromarray(res["indices"][t]["rgba"], "RGBA").save(png, format="PNG", compress_level=LUT_PNG_LEVEL)
             zf.writestr(f"{t}_visualization.png", png.getvalue())
@@ -170,13 +198,15 @@ def main(argv=None):
     ap.add_argument("--workers", type=int, default=4)
     ap.add_argument("--full-depth", action="store_true")
     ap.add_argument("--lut-format", default="png", choices=["png", "png8", "tiff"])
+    ap.add_argument("--png-encoder", default="pillow", choices=list(PNG_ENCODERS),
+                    help="'device' encodes the index PNGs on the GPU (same pixels, only the files cross PCIe)")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     from .dist import env_rank_world
     rank, local_rank, world = env_rank_world()
     res = batch_process(args.input_dir, args.output_dir, args.wb, args.ndvi, args.gndvi, args.ndwi, args.workers,
                         not args.quiet, args.full_depth, args.lut_format, rank, world,
-                        device=local_rank if world > 1 else None)
+                        device=local_rank if world > 1 else None, png_encoder=args.png_encoder)
     failed = {k: str(v) for k, v in res.items() if isinstance(v, Exception)}
     print(json.dumps({"rank": rank, "world": world, "files": len(res), "failed": failed}))
     return 1 if failed else 0
