@@ -48,6 +48,7 @@ import numpy as np
 
 from . import _ffi
 from ._ffi import INDEX_IDS, INDEX_NAMES, Stats
+from .batch import index_mask
 from .hostpool import empty as _empty        # large result arrays reuse released buffers (no first-touch page faults)
 
 __all__ = [
@@ -571,9 +572,7 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
         if t not in INDEX_IDS:
             raise ValueError(f"Unknown index type: {t}")
     h, w, c = arr.shape
-    mask = 0
-    for t in indices:
-        mask |= 1 << INDEX_IDS[t]
+    mask = index_mask(indices)
     out_wb = _empty((h, w, c), dtype=np.uint8) if white_balance else None
     outs, rgbas, luts = [None] * 3, [None] * 3, [None] * 3
     for t in indices:

@@ -57,6 +57,44 @@ def get_stats_route():
     return _STATS_ROUTE
 
 
+def index_mask(indices):
+    """Bit ``INDEX_IDS[t]`` set for every index ``t`` of ``indices``."""
+    mask = 0
+    for t in indices:
+        mask |= 1 << INDEX_IDS[t]
+    return mask
+
+
+def joint_serves(code, channels, ntiles, npix):
+    """What ``lars_d_stats_joint`` serves: uint8 tiles with 3 (RGNir) or 4 (RGBA: alpha ignored) channels, 4-byte aligned."""
+    return code == _ffi.U8 and channels in (3, 4) and (ntiles == 1 or npix % 4 == 0)
+
+
+def plan_process(code, channels, ntiles, npix, indices, white_balance, hist, medians, sumsq, route,
+                 outputs=False, wb_plane=False, reuse=False):
+    """The route ``TileBatch.process`` takes (its docstring's table): ``outputs`` whether planes are given, ``wb_plane`` whether
+    they include a white-balanced image, ``reuse`` whether the batch's tables are reused.  "measure": ``route="auto"`` leaves the
+    choice to ``pick_stats_route``, plan again with what it picked.  ``white_balance`` does not matter: every route serves both."""
+    if route not in ("auto", "joint", "classic"):
+        raise ValueError(f"route must be auto, joint or classic, not {route!r}")
+    if reuse and not outputs and route == "joint":
+        raise ValueError("route='joint' derives the tables from its own counts: it cannot honour recompute_tables=False")
+    one_read = route != "classic" and not reuse and joint_serves(code, channels, ntiles, npix) and bool(indices)
+    if one_read and not outputs:
+        return "measure" if route == "auto" and not medians and not sumsq else "one-read"
+    if route == "joint" and not outputs:
+        raise ValueError("route='joint' serves uint8 tiles with 3 or 4 channels (4-byte aligned) only")
+    # Planes without a white-balanced image (that needs all three tables; bench.py's Runner.joint_then_planes copies this rule):
+    # for one value stream the one-read pass costs what the channel-histogram pass costs and spares the plane-writing kernel its
+    # statistics (28.7 instead of 30.5 ms for the NDVI plane: profiles/r04_ndvi_plane_step_ways.txt); medians and the 50-bin
+    # histograms come out of its counted cells for any set of indices (48.9 instead of 51.7 ms per 1024 tiles with hist).
+    if one_read and not wb_plane and (medians or hist or select_streams(indices) in (1, 2)):
+        return "one-read+planes"
+    if medians and code == _ffi.U8 and channels == 3 and npix * 6 < (1 << 30) and (ntiles == 1 or npix % 4 == 0):
+        return "select" if not outputs and index_mask(indices) in (1, 2, 4, 7) else "per-pixel+select"
+    return "per-pixel+radix" if medians else "per-pixel"
+
+
 def channels_of(indices, whole_image=False):
     """Channels (0 red, 1 green, 2 NIR) whose white-balance tables a pass over ``indices`` reads."""
     if whole_image:
@@ -115,6 +153,10 @@ class TileBatch:
         self._table_channels = set()       # channels whose tables are valid (a one-read pass fills only those its indices read)
         self._hist_channels = set()        # channels whose 256-bin histograms are valid (a one-read pass fills them only on request)
         self._rgn_variant = 0              # flavour of the tables in force (process-rgn.py's extra inner clip = 1)
+        self._joint_scratch = None         # run_joint's scratch (window records, hand-over lists), grown on demand
+        self._joint_tiles = self.ntiles    # tiles the last run_joint covered
+        self._selq = None                  # select_histogram's counts
+        self.last_route = None             # the route the last process() took (plan_process)
 
     # -- construction -----------------------------------------------------
     @classmethod
@@ -373,9 +415,7 @@ class TileBatch:
         starts = list(range(0, self.ntiles, count))
         if len(starts) > 16:
             starts = [starts[int(round(i * (len(starts) - 1) / 15.0))] for i in range(16)]
-        mask = 0
-        for t in indices:
-            mask |= 1 << INDEX_IDS[t]
+        mask = index_mask(indices)
         wb_on = self.table is not None
         launches = [self.fused_args(indices, wb_on, stats, False, outs, None, st, min(count, self.ntiles - st), raw=True) for st in starts]
         while len(launches) < 4:
@@ -417,10 +457,7 @@ class TileBatch:
             if self.table is None:
                 raise RuntimeError("compute_wb_tables() first")
             a.wb_table = self.table.ptr + tile_start * self.table_bytes
-        mask = 0
-        for t in indices:
-            mask |= 1 << INDEX_IDS[t]
-        a.index_mask = mask
+        a.index_mask = index_mask(indices)
         a.flags = ((_ffi.F_STATS if stats is not None else 0) | (_ffi.F_HIST if (stats is not None and hist) else 0) |
                    (_ffi.F_SUMSQ if (stats is not None and sumsq) else 0) | (_ffi.F_RAW if (stats is not None and raw) else 0))
         if stats is not None:
@@ -447,13 +484,10 @@ class TileBatch:
         """Per-index fold of this batch's per-tile records ON THE DEVICE (``lars_d_stats_fold``): ``out`` (a DeviceBuffer of
         3 records, allocated when None) receives what ``local_fold`` computes on the host, bit for bit -- the three
         records a rank contributes to the global statistics, so that only 3 x 472 bytes leave the device."""
-        mask = 0
-        for t in indices:
-            mask |= 1 << INDEX_IDS[t]
         if out is None:
             out = DeviceBuffer(3 * STATS_DTYPE.itemsize)
             out.zero(stream)
-        _ffi.call("lars_d_stats_fold", C.c_void_p(stats.ptr), self.ntiles, mask, C.c_void_p(out.ptr), stream)
+        _ffi.call("lars_d_stats_fold", C.c_void_p(stats.ptr), self.ntiles, index_mask(indices), C.c_void_p(out.ptr), stream)
         return out
 
     def run_fused_chunks(self, indices, white_balance, stats, hist, outputs, stream=None, sumsq=False, launch_events=None):
@@ -469,9 +503,7 @@ class TileBatch:
             if launch_events and len(launch_events) > 1:
                 _ffi.call("lars_event_record", launch_events[1], stream)
             return 1
-        mask = 0
-        for t in indices:
-            mask |= 1 << INDEX_IDS[t]
+        mask = index_mask(indices)
         if stats is not None:
             _ffi.call("lars_d_stats_begin", C.c_void_p(stats.ptr), self.ntiles, mask, stream)
         launches = 0
@@ -493,8 +525,8 @@ class TileBatch:
 
     # -- statistics from one read: joint byte-pair histograms (csrc/joint.hip) ----
     def can_joint(self):
-        """What ``lars_d_stats_joint`` serves: uint8 tiles with 3 (RGNir) or 4 (RGBA: alpha ignored) channels."""
-        return self.code == _ffi.U8 and self.channels in (3, 4) and (self.ntiles == 1 or self.npix % 4 == 0)
+        """What ``lars_d_stats_joint`` serves (``joint_serves``)."""
+        return joint_serves(self.code, self.channels, self.ntiles, self.npix)
 
     def run_joint(self, indices, white_balance, stats, hist=False, sumsq=False, pairs=None, stream=None, rgn_variant=0,
                   tile_count=None, channel_hist=False):
@@ -505,12 +537,10 @@ class TileBatch:
         ``self.hist``.  Without the histograms a pass over both value streams may count red and green clamped to windows
         around their percentiles, both pair tables of a tile chunk in ONE workgroup (csrc/joint_win.hip): same records,
         percentiles, tables and medians, one reader per byte instead of two."""
-        mask = 0
-        for t in indices:
-            mask |= 1 << INDEX_IDS[t]
+        mask = index_mask(indices)
         need = int(_ffi.load().lars_joint_scratch_bytes(self.ntiles, self.npix, mask))
-        if getattr(self, "_joint_scratch", None) is None or self._joint_scratch.nbytes < need:
-            if getattr(self, "_joint_scratch", None) is not None:
+        if self._joint_scratch is None or self._joint_scratch.nbytes < need:
+            if self._joint_scratch is not None:
                 _ffi.call("lars_synchronize", stream)
                 self._joint_scratch.free()
             self._joint_scratch = DeviceBuffer(need)
@@ -552,18 +582,18 @@ class TileBatch:
         """(tiles the last ``run_joint`` counted on windowed tables, tiles among them whose window missed and that were
         counted again) -- after the pass's stream has finished."""
         w, r = C.c_int64(0), C.c_int64(0)
-        if getattr(self, "_joint_scratch", None) is None:
+        if self._joint_scratch is None:
             return 0, 0
-        _ffi.call("lars_joint_window_report", C.c_void_p(self._joint_scratch.ptr), getattr(self, "_joint_tiles", self.ntiles), C.byref(w), C.byref(r))
+        _ffi.call("lars_joint_window_report", C.c_void_p(self._joint_scratch.ptr), self._joint_tiles, C.byref(w), C.byref(r))
         return int(w.value), int(r.value)
 
     def joint_window_modes(self):
         """(tiles the last ``run_joint`` counted on full tables by two readers, on windowed red and green rows with NIR whole, on three
         windows) -- after the pass's stream has finished."""
-        if getattr(self, "_joint_scratch", None) is None:
+        if self._joint_scratch is None:
             return 0, 0, 0
         counts = (C.c_int64 * 3)()
-        _ffi.call("lars_joint_window_modes", C.c_void_p(self._joint_scratch.ptr), getattr(self, "_joint_tiles", self.ntiles), counts)
+        _ffi.call("lars_joint_window_modes", C.c_void_p(self._joint_scratch.ptr), self._joint_tiles, counts)
         return int(counts[0]), int(counts[1]), int(counts[2])
 
     def check_joint(self, stream=None):
@@ -571,7 +601,7 @@ class TileBatch:
         (its published counts would be truncated; cannot happen while a workgroup counts at most 2^24 pixels, which the
         chunking guarantees).  Every consumer of ``run_joint`` calls this before it trusts the records."""
         _ffi.call("lars_synchronize", stream)
-        if getattr(self, "_joint_scratch", None) is not None and int(self._joint_scratch.download(np.uint32, (1,))[0]):
+        if self._joint_scratch is not None and int(self._joint_scratch.download(np.uint32, (1,))[0]):
             raise RuntimeError("lars_d_stats_joint: a workgroup's hand-over list overflowed (a chunk of more than 2^24 pixels?)")
 
     def pick_stats_route(self, indices, white_balance=True, sample=256, min_pixels=1 << 29):
@@ -635,138 +665,120 @@ class TileBatch:
 
     def process(self, indices=INDEX_NAMES, white_balance=True, hist=False, outputs=None, stream=None,
                 recompute_tables=True, medians=False, sumsq=False, route=None, rgn_variant=None, channel_hist=False):
-        """Both passes over the whole batch; returns per-tile records
-        (structured ndarray ``[ntiles, 3]`` of STATS_DTYPE; rows of indices not
-        requested are zero).  ``hist`` adds the 50-bin histograms, ``sumsq`` the sums of squares
-        (``summarize()['std']``).  ``medians=True`` also returns ``float64[ntiles, 3]``
-        with np.median of each tile's index plane, exact: uint8 RGNir tiles take the
-        two-level select on recomputed values (planes or not); other tiles a batched radix
-        select on the float32 planes, which must then be written -- a small ring is
-        allocated when ``outputs`` has none.  ``route``: see ``set_stats_route`` (None = the module's setting).
+        """Both passes over the whole batch; returns per-tile records (structured ndarray ``[ntiles, 3]`` of STATS_DTYPE;
+        rows of indices not requested are zero).  ``hist`` adds the 50-bin histograms, ``sumsq`` the sums of squares
+        (``summarize()['std']``).  ``medians=True`` also returns ``float64[ntiles, 3]`` with np.median of each tile's
+        index plane, exact (NaN for indices not requested).  ``route``: see ``set_stats_route`` (None = the module's setting).
+
+        ``plan_process`` picks the route, ``last_route`` names the one taken:
+
+          route             taken when                                                                launches
+          one-read          no outputs, route != "classic", tables not reused, can_joint(), an index  run_joint
+          one-read+planes   as one-read, but index planes, no wb plane; medians, hist or one stream   run_joint, run_fused_chunks without stats
+          select            uint8 RGNir, medians, npix * 6 < 2^30, one tile or npix % 4 == 0;         lars_d_stats_medians
+                            no outputs, one index or all three
+          per-pixel+select  as select, but with outputs or two of the three indices                   run_fused_chunks, tile_medians
+          per-pixel         everything else without medians                                           run_fused_chunks
+          per-pixel+radix   everything else with medians (own ring if ``outputs`` lacks a plane)      per chunk: lars_d_fused, then
+                                                                                                      lars_d_median_pair_batch_f32
+        route="auto" measures (``pick_stats_route``) where one-read could run without outputs, medians or sumsq.  The
+        per-pixel routes compute the white-balance tables first unless they reuse the batch's.
 
         Tables: ``recompute_tables=False`` uses the white-balance tables the batch already holds (``compute_wb_tables``,
-        any ``rgn_variant``) when they cover the channels this pass reads -- such a pass runs on the per-pixel route, the
+        any ``rgn_variant``) when they cover the channels this pass reads -- such a pass runs on a per-pixel route, the
         one-read route derives its tables from its own counts -- and computes them otherwise.  ``rgn_variant`` (None: 0
         for tables computed here, whatever the reused tables are) selects the flavour of tables computed here.
-        ``channel_hist=True``: the 256-bin channel histograms (``host_hist``) are wanted too -- the per-pixel route always
-        leaves them, the one-read route only on request (and then counts on full tables: ``run_joint``)."""
+        ``channel_hist=True``: the 256-bin channel histograms (``host_hist``) are wanted too -- the per-pixel routes always
+        leave them, the one-read routes only on request (and then count on full tables: ``run_joint``)."""
         route = _STATS_ROUTE if route is None else route
         variant = 0 if rgn_variant is None else int(rgn_variant)
-        need = channels_of(indices, outputs is not None and outputs.wb is not None)
-        reuse = (white_balance and not recompute_tables and self.table is not None and need <= self._table_channels
-                 and (rgn_variant is None or variant == self._rgn_variant))
-        if reuse and outputs is None and route == "joint":
-            raise ValueError("route='joint' derives the tables from its own counts: it cannot honour recompute_tables=False")
-        may_joint = outputs is None and route != "classic" and not reuse and self.can_joint() and bool(indices)
-        if route == "auto" and may_joint and not medians and not sumsq:
-            route = self.pick_stats_route(indices, white_balance)
-            may_joint = route != "classic"
-        if may_joint:
-            # nothing to write: one read of the tiles serves the percentiles, the statistics and the medians
-            stats = self.new_stats()
-            stats.zero(stream)
-            pairs_dev = DeviceBuffer(self.ntiles * 4 * 4) if medians else None
-            self.run_joint(indices, white_balance, stats, hist, sumsq, pairs_dev, stream, rgn_variant=variant, channel_hist=channel_hist)
-            self.check_joint(stream)
-            rec = stats.download(STATS_DTYPE, (self.ntiles, 3))
-            stats.free()
-            if not medians:
-                return rec
-            med = self._medians_from_pairs(pairs_dev.download(np.float32, (self.ntiles, 2, 2)), indices)
-            pairs_dev.free()
-            return rec, med
-        if route == "joint" and outputs is None:
-            raise ValueError("route='joint' serves uint8 tiles with 3 channels (4-byte aligned) only")
-        if (outputs is not None and outputs.wb is None and route != "classic" and not reuse and self.can_joint() and bool(indices)
-                and (medians or hist or select_streams(indices) in (1, 2))):
-            # Planes wanted (no white-balanced image: that needs all three tables).  Where the one-read pass costs no more than
-            # the channel-histogram pass it replaces -- one value stream: 8.5 ms per 1024 tiles of 4096 x 4096 either way -- it
-            # delivers the tables AND the statistics, and the plane-writing kernel runs without its statistics registers and
-            # flush: 28.7 instead of 30.5 ms for the NDVI plane (profiles/r04_ndvi_plane_step_ways.txt).  With medians it wins
-            # for any set of indices (the medians come with the same read instead of two more passes), and so it does with the 50-bin
-            # histograms: they fall out of the counted cells, where the plane-writing kernel pays LDS atomics for them (0.76 against
-            # 0.82 of the roofline): 48.9 instead of 51.7 ms per 1024 tiles on windowed tables, the same on full ones.
-            stats = self.new_stats()
-            stats.zero(stream)
-            pairs_dev = DeviceBuffer(self.ntiles * 4 * 4) if medians else None
-            self.run_joint(indices, white_balance, stats, hist, sumsq, pairs_dev, stream, rgn_variant=variant, channel_hist=channel_hist)
-            self.run_fused_chunks(indices, white_balance, None, False, outputs, stream)
-            self.check_joint(stream)
-            rec = stats.download(STATS_DTYPE, (self.ntiles, 3))
-            stats.free()
-            if not medians:
-                return rec
-            med = self._medians_from_pairs(pairs_dev.download(np.float32, (self.ntiles, 2, 2)), indices)
-            pairs_dev.free()
-            return rec, med
+        wb_plane = outputs is not None and outputs.wb is not None
+        reuse = (white_balance and not recompute_tables and self.table is not None
+                 and channels_of(indices, wb_plane) <= self._table_channels and (rgn_variant is None or variant == self._rgn_variant))
+
+        def plan(r):
+            return plan_process(self.code, self.channels, self.ntiles, self.npix, indices, white_balance, hist, medians, sumsq, r,
+                                outputs is not None, wb_plane, reuse)
+
+        taken = plan(route)
+        if taken == "measure":
+            taken = plan(self.pick_stats_route(indices, white_balance))
+        self.last_route = taken
+        if taken in ("one-read", "one-read+planes"):
+            return self._run_one_read(indices, white_balance, hist, sumsq, medians, outputs, stream, variant, channel_hist)
         if white_balance and not reuse:
             self.compute_wb_tables(stream, rgn_variant=variant)
         stats = self.new_stats()
         stats.zero(stream)                                  # same stream as the kernels that accumulate into it
-        # uint8 RGNir tiles: medians come from the two-level select on recomputed values (two passes over the 3-byte
-        # pixels), whether or not planes are written; other tiles take the radix select over stored planes below
-        select = (medians and self.code == _ffi.U8 and self.channels == 3 and self.npix * 6 < (1 << 30)
-                  and (self.ntiles == 1 or self.npix % 4 == 0))
-        if select:
-            mask = 0
-            for t in indices:
-                mask |= 1 << INDEX_IDS[t]
-            if outputs is None and mask in (1, 2, 4, 7):
-                # nothing to write: the statistics kernel also counts the select's bucket pass, one slot pass follows --
-                # 3 B per pixel each, everything on the device
-                pairs_dev = DeviceBuffer(self.ntiles * 4 * 4)
-                scratch = DeviceBuffer(int(_ffi.load().lars_quotient_median_scratch_bytes(self.ntiles)))
-                args = self.fused_args(indices, white_balance, stats, hist, None, stream, sumsq=sumsq)
-                _ffi.call("lars_d_stats_medians", C.byref(args), C.c_void_p(pairs_dev.ptr), C.c_void_p(scratch.ptr))
-                _ffi.call("lars_synchronize", stream)
-                med = self._medians_from_pairs(pairs_dev.download(np.float32, (self.ntiles, 2, 2)), indices)
-                pairs_dev.free()
-                scratch.free()
-            else:                                           # planes wanted, or two of the three indices
-                self.run_fused_chunks(indices, white_balance, stats, hist, outputs, stream, sumsq)
-                med = self.tile_medians(indices, white_balance, stream)
-            rec = stats.download(STATS_DTYPE, (self.ntiles, 3))
-            stats.free()
-            return rec, med
-        own_outputs = None
-        if medians and (outputs is None or any(outputs.index[INDEX_IDS[t]] is None for t in indices)):
-            # a temporary ring: one plain allocation, never the arena search (seconds and several arenas' worth of memory per call)
-            own_outputs = outputs = self.make_outputs(indices=indices, index=True, ring=min(self.ntiles, 16), arena="plain")
-        med_dev = sel = None
-        if medians:
-            med_dev = DeviceBuffer(self.ntiles * 3 * 2 * 4)
-            med_dev.zero(stream)
-            sel = DeviceBuffer(outputs.slots * int(_ffi.load().lars_select_scratch_bytes()))
-        chunk = self.ntiles if outputs is None else outputs.slots
-        if not medians:
-            self.run_fused_chunks(indices, white_balance, stats, hist, outputs, stream, sumsq)
-        for start in range(0, self.ntiles if medians else 0, chunk):
-            count = min(chunk, self.ntiles - start)
-            self.run_fused(self.fused_args(indices, white_balance, stats, hist, outputs, stream, start, count, sumsq=sumsq))
-            if medians:
-                for t in indices:
-                    k = INDEX_IDS[t]
-                    # medians land in med_dev[k][tile][2]
-                    _ffi.call("lars_d_median_pair_batch_f32", C.c_void_p(outputs.index[k].ptr), self.npix, count, self.npix,
-                              C.c_void_p(med_dev.ptr + (k * self.ntiles + start) * 8), C.c_void_p(sel.ptr), stream)
-        _ffi.call("lars_synchronize", stream)
+        run = {"select": self._run_select, "per-pixel+select": self._run_fused_select, "per-pixel": self._run_fused,
+               "per-pixel+radix": self._run_fused_radix}[taken]
+        return run(indices, white_balance, stats, hist, sumsq, outputs, stream)
+
+    def _records(self, stats):
         rec = stats.download(STATS_DTYPE, (self.ntiles, 3))
         stats.free()
+        return rec
+
+    def _run_one_read(self, indices, white_balance, hist, sumsq, medians, outputs, stream, variant, channel_hist):
+        """Routes one-read and, with ``outputs``, one-read+planes: one read of the tiles serves the percentiles, the
+        statistics and the medians; the planes come from the plane-writing kernel without its statistics."""
+        stats = self.new_stats()
+        stats.zero(stream)
+        pairs = DeviceBuffer(self.ntiles * 4 * 4) if medians else None
+        self.run_joint(indices, white_balance, stats, hist, sumsq, pairs, stream, rgn_variant=variant, channel_hist=channel_hist)
+        if outputs is not None:
+            self.run_fused_chunks(indices, white_balance, None, False, outputs, stream)
+        self.check_joint(stream)
+        rec = self._records(stats)
         if not medians:
             return rec
-        pairs = med_dev.download(np.float32, (3, self.ntiles, 2))
-        med = ((pairs[:, :, 0] + pairs[:, :, 1]) / np.float32(2)).astype(np.float64).T.copy()   # float32 mean of the middles
-        for t in INDEX_NAMES:
-            if t not in indices:
-                med[:, INDEX_IDS[t]] = np.nan
-        med_dev.free()
+        med = self._medians_from_pairs(pairs.download(np.float32, (self.ntiles, 2, 2)), indices)
+        pairs.free()
+        return rec, med
+
+    def _run_select(self, indices, white_balance, stats, hist, sumsq, outputs, stream):
+        """Route select: the statistics kernel also counts the select's bucket pass, one slot pass follows (3 B per pixel each)."""
+        args = self.fused_args(indices, white_balance, stats, hist, None, stream, sumsq=sumsq)
+        med = self._per_tile_select(indices, stream, lambda pairs, scratch: _ffi.call("lars_d_stats_medians", C.byref(args), pairs, scratch))
+        return self._records(stats), med
+
+    def _run_fused_select(self, indices, white_balance, stats, hist, sumsq, outputs, stream):
+        self.run_fused_chunks(indices, white_balance, stats, hist, outputs, stream, sumsq)
+        med = self.tile_medians(indices, white_balance, stream)
+        return self._records(stats), med
+
+    def _run_fused(self, indices, white_balance, stats, hist, sumsq, outputs, stream):
+        self.run_fused_chunks(indices, white_balance, stats, hist, outputs, stream, sumsq)
+        _ffi.call("lars_synchronize", stream)
+        return self._records(stats)
+
+    def _run_fused_radix(self, indices, white_balance, stats, hist, sumsq, outputs, stream):
+        """Route per-pixel+radix: a radix select over the planes after every fused launch.  Without the planes in ``outputs``, a
+        ring of its own: one plain allocation, never the arena search (seconds and several arenas' worth of memory per call)."""
+        own_outputs = None
+        if outputs is None or any(outputs.index[INDEX_IDS[t]] is None for t in indices):
+            own_outputs = outputs = self.make_outputs(indices=indices, index=True, ring=min(self.ntiles, 16), arena="plain")
+        pairs = DeviceBuffer(self.ntiles * 3 * 2 * 4)       # [index][tile][2 middle values]
+        pairs.zero(stream)
+        sel = DeviceBuffer(outputs.slots * int(_ffi.load().lars_select_scratch_bytes()))
+        for start in range(0, self.ntiles, outputs.slots):
+            count = min(outputs.slots, self.ntiles - start)
+            self.run_fused(self.fused_args(indices, white_balance, stats, hist, outputs, stream, start, count, sumsq=sumsq))
+            for t in indices:
+                k = INDEX_IDS[t]
+                _ffi.call("lars_d_median_pair_batch_f32", C.c_void_p(outputs.index[k].ptr), self.npix, count, self.npix,
+                          C.c_void_p(pairs.ptr + (k * self.ntiles + start) * 8), C.c_void_p(sel.ptr), stream)
+        _ffi.call("lars_synchronize", stream)
+        rec = self._records(stats)
+        med = pair_medians(pairs.download(np.float32, (3, self.ntiles, 2)), indices, per_index=True)
+        pairs.free()
         sel.free()
         if own_outputs is not None:
             own_outputs.free()
         return rec, med
 
     def free(self):
-        for b in (self.tiles, self.hist, self.table, self.percentiles, getattr(self, "_joint_scratch", None)):
+        for b in (self.tiles, self.hist, self.table, self.percentiles, self._joint_scratch, self._selq):
             if b is not None:
                 b.free()
 
@@ -775,26 +787,26 @@ class TileBatch:
         (``lars_d_quotient_median_pairs``: per-tile two-level select on recomputed values, all on the device)."""
         if white_balance and (self.table is None or not channels_of(indices) <= self._table_channels):
             raise RuntimeError("compute_wb_tables() first")
-        pairs_dev = DeviceBuffer(self.ntiles * 4 * 4)
+        return self._per_tile_select(indices, stream, lambda pairs, scratch: _ffi.call(
+            "lars_d_quotient_median_pairs", C.c_void_p(self.tiles.ptr), self.ntiles, self.npix, self.channels, self.code,
+            C.c_void_p(self.table.ptr) if white_balance else None, select_streams(indices), pairs, scratch, stream))
+
+    def _per_tile_select(self, indices, stream, launch):
+        """``launch(pairs, scratch)`` enqueues a per-tile two-level select on ``stream``: wait for it, return its medians."""
+        pairs = DeviceBuffer(self.ntiles * 4 * 4)
         scratch = DeviceBuffer(int(_ffi.load().lars_quotient_median_scratch_bytes(self.ntiles)))
-        _ffi.call("lars_d_quotient_median_pairs", C.c_void_p(self.tiles.ptr), self.ntiles, self.npix, self.channels, self.code,
-                  C.c_void_p(self.table.ptr) if white_balance else None, select_streams(indices), C.c_void_p(pairs_dev.ptr),
-                  C.c_void_p(scratch.ptr), stream)
+        launch(C.c_void_p(pairs.ptr), C.c_void_p(scratch.ptr))
         _ffi.call("lars_synchronize", stream)
-        pairs = pairs_dev.download(np.float32, (self.ntiles, 2, 2))
-        pairs_dev.free()
+        med = self._medians_from_pairs(pairs.download(np.float32, (self.ntiles, 2, 2)), indices)
+        pairs.free()
         scratch.free()
-        return self._medians_from_pairs(pairs, indices)
+        return med
 
     def _medians_from_pairs(self, pairs, indices):
         """float32[ntiles][2 streams][2 middle values] -> float64[ntiles, 3] (np.median semantics; NDWI = -GNDVI)."""
-        mid = ((pairs[:, :, 0] + pairs[:, :, 1]) / np.float32(2)).astype(np.float32)          # float32 mean of the middles
-        med = np.full((self.ntiles, 3), np.nan, dtype=np.float64)
-        for t in indices:
-            k = INDEX_IDS[t]
-            med[:, k] = mid[:, 0] if t == "NDVI" else (mid[:, 1] if t == "GNDVI" else np.float32(0) - mid[:, 1])
-            if np.isnan(med[:, k]).any():
-                raise RuntimeError("exact median select did not settle (values outside the uint8 quotient domain?)")
+        med = pair_medians(pairs, indices)
+        if any(np.isnan(med[:, INDEX_IDS[t]]).any() for t in indices):
+            raise RuntimeError("exact median select did not settle (values outside the uint8 quotient domain?)")
         return med
 
     # -- exact medians of the whole batch (all tiles, all ranks) ------------
@@ -806,7 +818,7 @@ class TileBatch:
             raise TypeError("exact batch medians need uint8 tiles with 3 channels")
         if white_balance and self.table is None:
             raise RuntimeError("compute_wb_tables() first")
-        if getattr(self, "_selq", None) is None:
+        if self._selq is None:
             self._selq = DeviceBuffer(2 * 2 * SELECT_BINS * 8)
         self._selq.zero(stream)
         b = np.ascontiguousarray(np.asarray(buckets, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32).reshape(4)    # window starts are int32
@@ -907,7 +919,7 @@ class BatchOutputs:
         return self.wb.download(np.uint8, (count, b.h, b.w, b.channels), slot * b.npix * b.channels)
 
     def free(self):
-        for b in self.index + self.rgba + self.luts + [self.wb, self.arena, getattr(self, "arena2", None)]:
+        for b in self.index + self.rgba + self.luts + [self.wb, self.arena, self.arena2]:
             if b is not None:
                 b.free()
         self.index, self.rgba, self.arena, self.arena2 = [None] * 3, [None] * 3, None, None
@@ -1136,11 +1148,18 @@ def select_order_statistics(pass_fn, n_local, comm=None, streams=3, windowed=Tru
     return values
 
 
-def medians_from_pairs(values, indices=INDEX_NAMES):
-    """np.median semantics (mean of the two middle values in float32); NDWI = -GNDVI shares GNDVI's statistics."""
-    out = {}
+def pair_medians(pairs, indices, per_index=False):
+    """Middle values -> float64[n, 3]: np.median semantics (the float32 mean of the two middle values), NaN for indices not
+    requested.  ``pairs``: float32[n][2 streams][2] (NDVI, GNDVI; NDWI = -GNDVI), or with ``per_index`` float32[3][n][2]."""
+    mid = ((pairs[..., 0] + pairs[..., 1]) / np.float32(2)).astype(np.float32)
+    med = np.full((mid.shape[1] if per_index else mid.shape[0], 3), np.nan, dtype=np.float64)
     for t in indices:
-        s = 0 if t == "NDVI" else 1
-        m = np.float32(np.float32(values[s, 0] + values[s, 1]) / np.float32(2))
-        out[t] = float(np.float32(0) - m) if t == "NDWI" else float(m)
-    return out
+        k = INDEX_IDS[t]
+        med[:, k] = mid[k] if per_index else (mid[:, 0] if t == "NDVI" else (mid[:, 1] if t == "GNDVI" else np.float32(0) - mid[:, 1]))
+    return med
+
+
+def medians_from_pairs(values, indices=INDEX_NAMES):
+    """float32[2 streams][2 middle values] -> {index: median} (``pair_medians``)."""
+    med = pair_medians(values[None], indices)[0]
+    return {t: float(med[INDEX_IDS[t]]) for t in indices}

@@ -79,10 +79,12 @@ def main():
             if not b.can_joint():
                 raise AssertionError("can_joint() is False")
             rc = b.process(indices=indices, white_balance=wb, hist=hist, sumsq=sumsq, medians=med, route="classic")
+            assert b.last_route.startswith("per-pixel") or b.last_route == "select", b.last_route
             if wb:
                 tab_c, pct_c, hist_c = b.host_tables(), b.host_percentiles(), b.host_hist()
                 b.table.zero(); b.percentiles.zero(); b.hist.zero()
             rj = b.process(indices=indices, white_balance=wb, hist=hist, sumsq=sumsq, medians=med, route="joint", channel_hist=window == 0)
+            assert b.last_route == "one-read", b.last_route
             nwin, nrec = b.joint_window_report()
             windowed[window] = windowed.get(window, 0) + nwin
             recounted[window] = recounted.get(window, 0) + nrec

@@ -29,6 +29,14 @@ def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
+def assert_route(b, auto, classic=None):
+    """``b.last_route`` under the fixture's route setting: ``auto`` under "auto" (a tuple: any route the measurement may pick),
+    ``classic`` (default: the same as ``auto``) under "classic"."""
+    from lars_image_processing_amd import batch
+    want = auto if batch.get_stats_route() == "auto" or classic is None else classic
+    assert b.last_route in (want if isinstance(want, tuple) else (want,)), (b.last_route, want)
+
+
 @pytest.mark.parametrize("profile", ["uniform", "vegetation"])
 @pytest.mark.parametrize("shape", [(64, 64), (30, 50), (33, 35)])
 def test_device_generator_equals_host_generator(lars, profile, shape):
@@ -48,6 +56,7 @@ def test_batch_matches_oracle_per_tile(lars, profile, shape):
     tiles = b.host_tiles()
     outs = b.make_outputs(index=True, wb=True, rgba=True)
     rec = b.process(hist=True, sumsq=True, outputs=outs)
+    assert_route(b, "per-pixel")
     tables = b.host_tables()
     pcts = b.host_percentiles()
     wb = outs.host_wb(0, ntiles)
@@ -105,6 +114,7 @@ def test_one_rank_share_of_the_sharded_batch(lars):
     n, ntiles, first = 4096 * 4096, 2048, 3 * 2048                       # the share of rank 3
     b = lars.TileBatch.synthetic(ntiles, 4096, 4096, seed=1234, profile="vegetation", first_tile=first)
     rec = b.process(hist=True)
+    assert_route(b, ("one-read", "per-pixel"), "per-pixel")
     assert rec.shape == (ntiles, 3)
     assert (rec["count"] == n).all() and (rec["hist"].sum(axis=2) == n).all()
     assert (rec["min"] >= -1).all() and (rec["max"] <= 1).all() and (rec["min"] <= rec["max"]).all()
@@ -147,8 +157,10 @@ def test_device_fold_equals_host_fold(lars, ntiles):
 def test_stats_only_equals_stats_with_outputs_and_ring(lars):
     b = lars.TileBatch.synthetic(8, 128, 128, seed=7, profile="vegetation")
     rec_a = b.process(hist=True, sumsq=True)
+    assert_route(b, "one-read", "per-pixel")
     outs = b.make_outputs(index=True, ring=3)
     rec_b = b.process(hist=True, sumsq=True, outputs=outs)
+    assert_route(b, "one-read+planes", "per-pixel")
     assert (rec_a["sumsq"] > 0).all() and (b.process(hist=True)["sumsq"] == 0).all()      # only on request
     np.testing.assert_allclose(rec_a["sumsq"], rec_b["sumsq"], rtol=1e-12, atol=2.0 ** -26)   # rounded to 2^-32 once per workgroup
     rec_a["sumsq"] = rec_b["sumsq"] = 0     # every other field is order-independent, hence identical
@@ -173,12 +185,14 @@ def test_single_index_masks_leave_other_records_untouched(lars):
     tiles = b.host_tiles()
     for k, t in enumerate(TYPES):
         rec = b.process(indices=(t,), white_balance=False)
+        assert_route(b, "one-read", "per-pixel")
         for j in range(3):
             if j != k:
                 assert rec[:, j].tobytes() == bytes(rec[:, j].nbytes)
         part = orc.tile_partials(orc.index_app(tiles[1], t), t)
         assert float(rec[1, k]["sum"]) == part["sum"] and float(rec[1, k]["min"]) == part["min"]
     rec2 = b.process(indices=("NDVI", "NDWI"), white_balance=False)       # two-index mask -> generic kernel
+    assert_route(b, "one-read", "per-pixel")
     assert rec2[:, 1].tobytes() == bytes(rec2[:, 1].nbytes)
     part = orc.tile_partials(orc.index_app(tiles[2], "NDWI"), "NDWI")
     assert float(rec2[2, 2]["sum"]) == part["sum"] and int(rec2[2, 2]["above"]) == part["above"]
@@ -191,6 +205,7 @@ def test_full_size_tile_properties(lars):
     b = lars.TileBatch.synthetic(2, 4096, 4096, seed=1234, profile="vegetation")
     outs = b.make_outputs(index=True, wb=True)
     rec = b.process(hist=True, outputs=outs)
+    assert_route(b, "per-pixel")
     n = 4096 * 4096
     for i in range(2):
         for k in range(3):
@@ -219,6 +234,7 @@ def test_full_size_tile_properties(lars):
     assert lb.summarize(lb.merge_records(rec[:, 0]))["count"] == 2 * n
     # exact medians at full size, none of them through a stored plane: per tile and over both tiles
     rec_m, med = b.process(medians=True)
+    assert_route(b, "one-read", "select")
     assert med[1, 0] == float(np.median(ndvi))
     assert float(rec_m[1, 0]["sum"]) == float(rec[1, 0]["sum"]) and int(rec_m[1, 0]["above"]) == int(rec[1, 0]["above"])
     both = np.concatenate([outs.host_index("NDVI", 0, 1)[0].ravel(), ndvi.ravel()])
@@ -250,6 +266,7 @@ def test_tuning_does_not_change_results(lars):
             for bpt in (0, 1, 7):
                 _ffi.set_tuning(fused_impl=impl, hist_impl=impl, nt_stores=nt, blocks_per_tile=bpt)
                 rec = b.process(hist=True, sumsq=True, outputs=outs)
+                assert_route(b, "one-read+planes", "per-pixel")
                 sumsq = rec["sumsq"].copy()
                 rec["sumsq"] = 0            # the only order-dependent field (double sums of squares)
                 got = (rec.tobytes(), outs.host_index("NDWI", 0, 4).tobytes(), b.host_tables().tobytes())
@@ -271,6 +288,7 @@ def test_rccl_communicator_single_rank(lars):
     comm = dist.Comm(0, 1, uid)
     b = lars.TileBatch.synthetic(3, 64, 64, seed=5)
     rec = b.process(hist=True)
+    assert_route(b, "one-read", "per-pixel")
     local = lb.local_fold(rec)
     glob = comm.allreduce_stats(local)
     assert glob.tobytes() == local.tobytes()
@@ -303,6 +321,7 @@ def test_uint16_batch_against_oracle(lars, kind):
     b = lars.TileBatch.from_host(tiles)
     outs = b.make_outputs(index=True, wb=True, rgba=True)
     rec = b.process(hist=True, outputs=outs)
+    assert_route(b, "per-pixel")
     pcts = b.host_percentiles()
     tables = b.host_tables()
     wb = outs.host_wb(0, n)
@@ -328,6 +347,7 @@ def test_uint16_batch_against_oracle(lars, kind):
     # raw uint16 indices (no white balance): operands up to 65535
     outs_raw = b.make_outputs(index=True)
     b.process(white_balance=False, outputs=outs_raw)
+    assert_route(b, "per-pixel")
     for t in TYPES:
         np.testing.assert_array_equal(bits(outs_raw.host_index(t, 1, 1)[0]), bits(orc.index_app(tiles[1], t)))
     outs_raw.free()
@@ -400,6 +420,7 @@ def test_uint16_full_size_tile(lars):
     b = lars.TileBatch.from_host(tile[None])
     outs = b.make_outputs(indices=("NDVI",), index=True, rgba=True)
     rec = b.process(indices=("NDVI",), hist=True, outputs=outs)
+    assert_route(b, "per-pixel")
     pcts = b.host_percentiles()[0]
     luts = []
     for c in range(3):
@@ -430,6 +451,7 @@ def test_uint16_rgba_channels_take_generic_path(lars):
     b = lars.TileBatch.from_host(tiles)
     outs = b.make_outputs(index=True, wb=True)
     b.process(outputs=outs)
+    assert_route(b, "per-pixel")
     wb = outs.host_wb(0, 2)
     for i in range(2):
         with warnings.catch_warnings():
@@ -450,6 +472,7 @@ def test_output_ring_placement_trials(lars):
     # the three index planes are slices of one allocation, in index order
     assert [tuned.index[k].ptr - tuned.arena.ptr for k in range(3)] == [0, tuned.plane_bytes, 2 * tuned.plane_bytes]
     rec_a = b.process(outputs=plain)
+    assert_route(b, "per-pixel")
     ndvi_a = plain.host_index("NDVI", 1, 1)
     rec_b = b.process(outputs=tuned)
     np.testing.assert_array_equal(bits(tuned.host_index("NDVI", 1, 1)), bits(ndvi_a))
@@ -490,6 +513,7 @@ def test_planes_stay_aligned_inside_the_arena(lars):
     assert o.plane_bytes % 256 == 0 and all(o.index[k].ptr % 256 == 0 for k in range(3))
     assert o.arena_report["kind"] == "plain hipMalloc"
     rec = odd.process(outputs=o)
+    assert_route(odd, "per-pixel")
     assert _ffi.get_tuning("last_fused_kernel") in (1, 2)
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -513,6 +537,7 @@ def test_rgba_tiles_and_two_index_masks_take_the_fast_kernels(lars):
     o3, o4 = b3.make_outputs(index=True, wb=True, rgba=True), b4.make_outputs(index=True, wb=True, rgba=True)
     rec3 = b3.process(hist=True, sumsq=True, outputs=o3)
     rec4 = b4.process(hist=True, sumsq=True, outputs=o4)
+    assert b3.last_route == b4.last_route == "per-pixel"
     assert _ffi.get_tuning("last_fused_kernel") == 5
     np.testing.assert_allclose(rec3["sumsq"], rec4["sumsq"], rtol=1e-12, atol=2.0 ** -26)
     rec3["sumsq"] = rec4["sumsq"] = 0
@@ -529,6 +554,7 @@ def test_rgba_tiles_and_two_index_masks_take_the_fast_kernels(lars):
     for route in ("joint", "classic"):
         r3, m3 = b3.process(medians=True, route="classic")
         r4, m4 = b4.process(medians=True, route=route)
+        assert b3.last_route == "select" and b4.last_route == ("one-read" if route == "joint" else "per-pixel+radix")
         assert r3.tobytes() == r4.tobytes(), route
         np.testing.assert_array_equal(m3, m4)
     # a single RGBA tile whose pixel count is not a multiple of 4, without white balance
@@ -540,6 +566,7 @@ def test_rgba_tiles_and_two_index_masks_take_the_fast_kernels(lars):
     np.testing.assert_array_equal(bits(oo.host_index("GNDVI", 0, 1)[0]), bits(want))
     assert float(ro[0, 1]["sum"]) == orc.tile_partials(want, "GNDVI")["sum"]
     assert odd.process(white_balance=False, route="joint").tobytes() == ro.tobytes()
+    assert odd.last_route == "one-read"
     oo.free(); odd.free()
     # two-index masks: three-index kernel, third plane and record untouched
     full = b3.process(hist=True)
@@ -547,6 +574,7 @@ def test_rgba_tiles_and_two_index_masks_take_the_fast_kernels(lars):
         op = b3.make_outputs(indices=pair, index=True)
         for route in ("classic", "joint"):
             rp = b3.process(indices=pair, hist=True, outputs=op if route == "classic" else None, route=route)
+            assert b3.last_route == ("per-pixel" if route == "classic" else "one-read")
             if route == "classic":
                 assert _ffi.get_tuning("last_fused_kernel") in (1, 2)
             for k, t in enumerate(TYPES):
@@ -557,6 +585,7 @@ def test_rgba_tiles_and_two_index_masks_take_the_fast_kernels(lars):
         for t in pair:
             np.testing.assert_array_equal(bits(op.host_index(t, 0, 5)), bits(o3.host_index(t, 0, 5)))
         rs = b3.process(indices=pair, route="classic")                 # statistics only through the per-pixel kernel
+        assert b3.last_route == "per-pixel"
         assert _ffi.get_tuning("last_fused_kernel") in (1, 2)
         for k, t in enumerate(TYPES):
             if t in pair:
@@ -568,6 +597,7 @@ def test_rgba_tiles_and_two_index_masks_take_the_fast_kernels(lars):
 def test_batch_medians_are_numpy_medians(lars):
     b = lars.TileBatch.synthetic(21, 64, 96, seed=13, profile="vegetation")        # 21 tiles over a ring of 16: two chunks
     rec, med = b.process(medians=True)
+    assert_route(b, "one-read", "select")
     tiles = b.host_tiles()
     for i in (0, 7, 15, 16, 20):
         with warnings.catch_warnings():
@@ -589,6 +619,7 @@ def test_batch_medians_are_numpy_medians(lars):
     # ring holds the last chunk's planes
     outs = b.make_outputs(index=True, ring=8)
     rec_o, med_o = b.process(medians=True, outputs=outs)
+    assert_route(b, "one-read+planes", "per-pixel+select")
     np.testing.assert_array_equal(med_o, med)
     assert rec_o["count"].tolist() == rec["count"].tolist() and rec_o["min"].tolist() == rec["min"].tolist()
     with warnings.catch_warnings():
@@ -602,6 +633,7 @@ def test_batch_medians_are_numpy_medians(lars):
     wide = lars.TileBatch.from_host(np.random.default_rng(4).integers(0, 65536, (2, 40, 48, 3), dtype=np.uint16))
     for bb in (odd, wide):
         _, med_p = bb.process(medians=True)
+        assert bb.last_route == "per-pixel+radix"
         for i in range(bb.ntiles):
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore")
@@ -611,6 +643,7 @@ def test_batch_medians_are_numpy_medians(lars):
         bb.free()
     big = lars.TileBatch.synthetic(3, 512, 384, seed=3, profile="uniform")         # several workgroups per tile
     _, med_b = big.process(medians=True)
+    assert_route(big, "one-read", "select")
     for i in range(3):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
@@ -620,9 +653,11 @@ def test_batch_medians_are_numpy_medians(lars):
     big.free()
     # one index, two indices (separate statistics pass), and the 50-bin histograms next to the medians
     rec1, med1 = b.process(indices=("NDVI",), medians=True)
+    assert_route(b, "one-read", "select")
     np.testing.assert_array_equal(med1[:, 0], med[:, 0])
     assert np.isnan(med1[:, 1:]).all() and rec1[3, 0]["sum"] == rec[3, 0]["sum"]
     rec5, med5 = b.process(indices=("NDVI", "NDWI"), medians=True)
+    assert_route(b, "one-read", "per-pixel+select")
     np.testing.assert_array_equal(med5[:, [0, 2]], med[:, [0, 2]])
     assert np.isnan(med5[:, 1]).all()
     rech, medh = b.process(medians=True, hist=True)
@@ -633,9 +668,11 @@ def test_batch_medians_are_numpy_medians(lars):
     for k, t in enumerate(TYPES):
         np.testing.assert_array_equal(rech[7, k]["hist"], orc.hist50(orc.index_app(wb7, t)))
     rec2, med2 = b.process(indices=("NDWI",), medians=True, white_balance=False)
+    assert_route(b, "one-read", "select")
     assert np.isnan(med2[:, 0]).all() and med2[3, 2] == float(np.median(orc.index_app(tiles[3], "NDWI")))
     odd = lars.TileBatch.synthetic(2, 5, 7, seed=1)                                # odd sample count: single middle element
     _, m = odd.process(medians=True, white_balance=False)
+    assert odd.last_route == "per-pixel+radix"
     assert m[1, 0] == float(np.median(orc.index_app(odd.host_tiles()[1], "NDVI")))
     b.free(); odd.free()
 
@@ -702,6 +739,7 @@ def test_bad_arguments_fail_cleanly(lars):
         lars.fix_white_balance(np.zeros((4, 4, 3), dtype=complex))
     # the library still works afterwards
     rec = b.process(indices=("NDVI",))
+    assert_route(b, "one-read", "per-pixel")
     assert int(rec[0, 0]["count"]) == 256
     b.free()
 
@@ -764,6 +802,7 @@ def test_caller_stream_is_ordered_against_the_zeroing(lars):
     b = lars.TileBatch.synthetic(9, 128, 192, seed=77, profile="vegetation")
     b.compute_wb_tables()
     want_rec, want_med = b.process(medians=True, recompute_tables=False)
+    assert b.last_route == "select"                                 # tables reused: never the one-read route
     want_hist = b.select_histogram(True, [0, 0, 0, 0])
     s = C.c_void_p()
     _ffi.call("lars_stream_create", C.byref(s))
@@ -775,6 +814,7 @@ def test_caller_stream_is_ordered_against_the_zeroing(lars):
             np.testing.assert_array_equal(b.select_histogram(True, [0, 0, 0, 0], stream=s), want_hist)
         outs = b.make_outputs(index=True, ring=4)
         rec2, med2 = b.process(medians=True, recompute_tables=True, outputs=outs, stream=s)
+        assert_route(b, "one-read+planes", "per-pixel+select")
         assert rec2.tobytes() == want_rec.tobytes()
         np.testing.assert_array_equal(med2, want_med)
         outs.free()
@@ -812,6 +852,7 @@ def test_one_pass_medians_and_their_fallback(lars, profile, indices):
         for mode in (1, 2, 0):
             _ffi.set_tuning(selq_window=mode)
             rec, med = b.process(indices=indices, medians=True)
+            assert_route(b, "one-read", "select" if len(indices) in (1, 3) else "per-pixel+select")
             results[mode] = rec.tobytes()
             np.testing.assert_array_equal(med, want, err_msg=f"selq_window={mode}")
             # the medians on their own (what a launch that writes planes uses): prediction + one window sweep + fallback
@@ -835,6 +876,7 @@ def test_one_pass_medians_at_the_ends_of_the_range(lars):
     tiles = [top, bottom, split, near, mostly]
     b = lars.TileBatch.from_host(np.stack(tiles))
     rec, med = b.process(medians=True, white_balance=False)
+    assert_route(b, "one-read", "select")
     for i, tile in enumerate(tiles):
         for k, t in enumerate(TYPES):
             assert med[i, k] == float(np.median(orc.index_app(tile, t))), (i, t)

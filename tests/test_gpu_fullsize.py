@@ -65,6 +65,7 @@ def test_chunked_ring_launches_at_bench_size():
             assert int(rec[tile, k]["above"]) == int((plane > thr).sum())
     # the one-read route over the same 130 tiles: the same records
     rec_j = b.process(route="joint")
+    assert b.last_route == "one-read"
     assert rec_j.tobytes() == rec.tobytes()
     outs.free(); stats.free(); b.free()
 

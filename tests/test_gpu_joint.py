@@ -77,6 +77,7 @@ def test_joint_route_equals_classic_route(lars, profile, shape, ntiles, window):
             np.testing.assert_array_equal(med_c, med_j)
             # without the optional parts: sums of squares and bins stay zero
             rec_p = b.process(indices=indices, white_balance=wb, route="joint")
+            assert b.last_route == "one-read"
             assert (rec_p["sumsq"] == 0).all() and (rec_p["hist"] == 0).all()
             rec_p["hist"] = rec_j["hist"]; rec_p["sumsq"] = rec_j["sumsq"]
             assert rec_p.tobytes() == rec_j.tobytes()
@@ -93,6 +94,7 @@ def test_joint_route_equals_classic_route(lars, profile, shape, ntiles, window):
                     np.testing.assert_array_equal(got_tab[:, c], want_tab[:, c])
     # and against the oracle / NumPy directly (all three indices, white balance)
     rec, med = b.process(hist=True, medians=True, route="joint")
+    assert b.last_route == "one-read"
     for i in range(ntiles):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
@@ -133,6 +135,7 @@ def test_joint_counters_never_overflow(lars, blocks, window):
         _ffi.set_tuning(blocks_per_tile=blocks)
         for wb in (False, True):
             rec_j, med_j = b.process(white_balance=wb, hist=True, medians=True, route="joint")
+            assert b.last_route == "one-read"
             _ffi.set_tuning(blocks_per_tile=0)
             rec_c, med_c = b.process(white_balance=wb, hist=True, medians=True, route="classic")
             _ffi.set_tuning(blocks_per_tile=blocks)
@@ -165,6 +168,7 @@ def test_joint_full_size_tiles(lars):
             for window in (1, 0, 2, 4, 5):
                 _ffi.set_tuning(blocks_per_tile=blocks, joint_window=window)
                 rec_j, med_j = b.process(hist=True, medians=True, route="joint")
+                assert b.last_route == "one-read"
                 # the default: all six tiles on windowed tables (96 + 128 values; the one-colour tile: 3 + 3), nothing recounted;
                 # 4 / 5: on three windows (NIR as well: sweeps and hand-over lists of that kernel at full size), none / all recounted
                 assert b.joint_window_report() == {1: (6, 0), 0: (0, 0), 2: (6, 6), 4: (6, 0), 5: (6, 6)}[window]
@@ -203,8 +207,10 @@ def test_measured_route_choice(lars):
         chosen = b.pick_stats_route(TYPES, min_pixels=0)
         assert chosen in ("joint", "classic") and b.pick_stats_route(TYPES) == chosen and set(b._route_ms) == {"joint", "classic"}
         rec = b.process()
+        assert b.last_route == {"joint": "one-read", "classic": "per-pixel"}[chosen]
         assert rec.tobytes() == b.process(route="joint").tobytes() == b.process(route="classic").tobytes()
         rec_m, med = b.process(medians=True)                        # medians: always the one-read route
+        assert b.last_route == "one-read"
         assert rec_m.tobytes() == rec.tobytes()
         b.free()
     small = lars.TileBatch.synthetic(3, 64, 64, seed=1)
@@ -248,12 +254,14 @@ def test_route_timing_leaves_the_tables_alone_and_supplied_tables_are_used(lars)
     instead of silently taking the one-read route with flavour 0; (iii) the host getters refuse half-filled tables."""
     b = lars.TileBatch.synthetic(40, 1024, 1024, seed=31, profile="vegetation")
     want = b.process(route="classic")
+    assert b.last_route == "per-pixel"
     want_tab = b.host_tables()
     # (i) fresh batch state, route timing first
     b2 = lars.TileBatch.synthetic(40, 1024, 1024, seed=31, profile="vegetation")
     assert b2.pick_stats_route(("NDVI", "GNDVI", "NDWI"), min_pixels=0) in ("joint", "classic") and set(b2._route_ms) == {"joint", "classic"}
     assert b2.table is None and b2._table_channels == set()
     got = b2.process(recompute_tables=False, route="classic")          # no tables yet: they are computed, over ALL tiles
+    assert b2.last_route == "per-pixel"
     assert got.tobytes() == want.tobytes()
     np.testing.assert_array_equal(b2.host_tables(), want_tab)
     b2.compute_wb_tables()
@@ -265,17 +273,21 @@ def test_route_timing_leaves_the_tables_alone_and_supplied_tables_are_used(lars)
     b2.compute_wb_tables(rgn_variant=1)
     tab1 = b2.host_tables()
     rec1 = b2.process(recompute_tables=False)                            # route from the module's setting ("auto")
+    assert b2.last_route == "per-pixel"                                 # tables reused: never the one-read route
     assert b2._rgn_variant == 1
     np.testing.assert_array_equal(b2.host_tables(), tab1)
     ref1 = b2.process(recompute_tables=False, route="classic")
+    assert b2.last_route == "per-pixel"
     assert rec1.tobytes() == ref1.tobytes()
     rec1j = b2.process(rgn_variant=1, route="joint")                    # the one-read route computes the same flavour itself
+    assert b2.last_route == "one-read"
     assert rec1j.tobytes() == ref1.tobytes()
     np.testing.assert_array_equal(b2.host_tables(), tab1)
     with pytest.raises(ValueError):
         b2.process(recompute_tables=False, route="joint")
     # (iii) a one-read pass over NDVI alone with another flavour leaves green invalid
     b2.process(indices=("NDVI",), route="joint")                         # flavour 0 again: red and NIR rows only
+    assert b2.last_route == "one-read"
     assert b2._table_channels == {0, 2}
     with pytest.raises(RuntimeError):
         b2.host_tables()
@@ -329,6 +341,7 @@ def test_hot_cells_survive_the_16_bit_counters(lars, kind, window):
             for blocks, depth in ((0, 6), (1, 6), (0, 12), (3, 8)):
                 _ffi.set_tuning(blocks_per_tile=blocks, joint_depth=depth, joint_win_depth={6: 15, 12: 12, 8: 5}[depth] if blocks else 4)
                 got, got_med = b.process(indices=indices, hist=True, medians=True, route="joint")
+                assert b.last_route == "one-read"
                 assert got.tobytes() == want.tobytes(), (kind, indices, blocks, depth)
                 np.testing.assert_array_equal(got_med, want_med)
                 for c in sorted(lars.batch.channels_of(indices)):
@@ -366,6 +379,7 @@ def test_windowed_and_full_tiles_in_one_batch(lars, channels):
             for blocks in (0, 1, 3):
                 _ffi.set_tuning(joint_window=window, blocks_per_tile=blocks)
                 got, got_med = b.process(hist=True, medians=True, route="joint")
+                assert b.last_route == "one-read"
                 report = b.joint_window_report()
                 assert expect is None or report == expect, (window, report)
                 if window in (2, 5):
@@ -393,10 +407,12 @@ def test_windowed_ragged_single_tile_and_flavours(lars):
         for variant in (0, 1):
             b.compute_wb_tables(rgn_variant=variant)
             want = b.process(hist=True, sumsq=True, recompute_tables=False, route="classic")
+            assert b.last_route == "per-pixel"
             want_tab = b.host_tables()
             for window in (3, 0, 2, 4, 5):
                 _ffi.set_tuning(joint_window=window)
                 got = b.process(hist=True, sumsq=True, rgn_variant=variant, route="joint")
+                assert b.last_route == "one-read"
                 assert b.joint_window_report() == {3: (1, 0), 0: (0, 0), 2: (1, 1), 4: (1, 0), 5: (1, 1)}[window]
                 assert b.joint_window_modes() == {3: (0, 1, 0), 0: (1, 0, 0), 2: (0, 1, 0), 4: (0, 0, 1), 5: (0, 0, 1)}[window]
                 same_records(want, got)
@@ -434,6 +450,7 @@ def test_three_windows_where_two_do_not_fit(lars):
                 for blocks in (0, 3):
                     _ffi.set_tuning(joint_window=window, blocks_per_tile=blocks)
                     got, got_med = b.process(hist=True, medians=True, route="joint")
+                    assert b.last_route == "one-read"
                     assert b.joint_window_modes() == modes and b.joint_window_report()[1] == recounted, (shape, window)
                     assert got.tobytes() == want.tobytes(), (shape, window, blocks)
                     np.testing.assert_array_equal(got_med, want_med)
@@ -554,6 +571,7 @@ def test_a_window_that_misses_by_itself_is_recounted(lars):
         want_tab, want_pct = b.host_tables(), b.host_percentiles()
         assert want_pct[0, 0, 0] < 30 and want_pct[1, 0, 0] < 30            # the 2nd percentile of red lies among the dark pixels
         got, got_med = b.process(hist=True, medians=True, route="joint")
+        assert b.last_route == "one-read"
         assert b.joint_window_report() == (2, 1)                             # both tiles windowed, the first one counted again
         assert got.tobytes() == want.tobytes()
         np.testing.assert_array_equal(got_med, want_med)
