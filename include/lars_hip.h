@@ -478,6 +478,43 @@ int lars_h_process_image_png(const void *img, int64_t h, int64_t w, int channels
                              const uint8_t *const cmap_lut[3], int png_mode,
                              uint8_t *const out_png[3], size_t png_cap, int64_t png_len[3]);
 
+/* PNG files decoded on the device -- the Image.open(io.BytesIO(img_bytes)) + np.array(img) of load_image_from_db
+ * (process-images.py:181-193) and the img.thumbnail((400, 400), LANCZOS) after it (process-images.py:186-189).
+ * Covered: bit depth 8, no interlace, colour types 0 (L), 2 (RGB), 3 (P: the palette indices), 4 (LA), 6 (RGBA); the
+ * pixels come out as Pillow's np.asarray gives them, uint8 [h][w][channels].  IDAT CRCs and the Adler-32 trailer are always
+ * checked (Pillow checks neither) whenever the stream decodes to exactly the image's bytes.  A stream that decodes to more
+ * (data past the image, which Pillow ignores) has its extra bytes dropped, not stored -- their length is bounded only by
+ * 1032 x the compressed size -- so the Adler-32 over all of them cannot be formed and that trailer is not checked.
+ * lars_png_info: pure host code.  Validates the chunk layout of file[0..len) (signature, IHDR first, IDATs consecutive,
+ * IEND, every chunk inside the file, the CRC of every chunk but IDAT) and fills info[LARS_PNG_INFO_N] = { width, height,
+ * bit depth, colour type, interlace, channels, IDAT payload bytes, IDAT chunks, APNG, supported }; idat_table (may be NULL
+ * with idat_cap 0) receives { payload offset, payload length } of the first idat_cap IDAT chunks.
+ * lars_png_decode_scratch_bytes: device scratch of lars_d_decode_png_u8 (0 for a shape it cannot decode).
+ * lars_d_decode_png_u8: device file / idat_table (info[7] pairs, as lars_png_info gave them) / out (h * w * channels bytes)
+ * / scratch; enqueues on stream and writes { LARS_PNGD_* status, detail } to the device int32 status_dev[2].
+ * lars_h_decode_png_u8: host file in, host pixels out (out_cap >= h * w * channels); one upload, one download.
+ * lars_h_thumbnail_png_u8: host file in (modes L, RGB, RGBA), lars_h_thumbnail_u8's plan numbers, host thumbnail out; the
+ * decoded pixels never leave the device. */
+#define LARS_PNG_INFO_N 10
+enum {
+    LARS_PNGD_OK = 0,
+    LARS_PNGD_CRC = 1,           /* detail: IDAT chunk index */
+    LARS_PNGD_ZLIB_HEADER = 2,   /* detail: CMF << 8 | FLG */
+    LARS_PNGD_DEFLATE = 3,       /* detail: 1 block type, 2 stored length, 3 code lengths, 4 invalid code, 5 truncated */
+    LARS_PNGD_FAR = 4,           /* a copy reaches before the stream start; detail: low 31 bits of the output position */
+    LARS_PNGD_SHORT = 5,         /* too few decoded bytes; detail: min(decoded, 2^31 - 1) */
+    LARS_PNGD_ADLER = 6,
+    LARS_PNGD_FILTER = 7,        /* a filter byte above 4; detail: the row */
+    LARS_PNGD_INTERNAL = 8       /* a bounded wait ran out or a table overflowed; detail: which */
+};
+int lars_png_info(const uint8_t *file, int64_t len, int64_t info[LARS_PNG_INFO_N], int64_t *idat_table, int64_t idat_cap);
+size_t lars_png_decode_scratch_bytes(int64_t h, int64_t w, int channels, int64_t idat_bytes, int64_t idat_count);
+int lars_d_decode_png_u8(const uint8_t *file, const int64_t *idat_table, int64_t idat_count, int64_t idat_bytes, int64_t h,
+                         int64_t w, int channels, uint8_t *out, int32_t *status_dev, void *scratch, void *stream);
+int lars_h_decode_png_u8(const uint8_t *file, int64_t len, uint8_t *out, size_t out_cap);
+int lars_h_thumbnail_png_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
+                            int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out);
+
 /* ------------------------------------------------------------------ image files (host only, no GPU work) */
 /* TIFF 6.0 LZW (compression 5, MSB-first codes, early width change) of one strip / tile: decodes at most ndst bytes
  * into dst, *nout = bytes produced.  For lars_image_processing_amd/tiffio.py, which reads the multi-sample 16-bit

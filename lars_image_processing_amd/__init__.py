@@ -19,6 +19,7 @@ from .api import (  # noqa: F401
     colorize_index,
     colormap_lut,
     correct_white_balance,
+    decode_png,
     encode_png,
     download_processed_images,
     fix_white_balance,
@@ -26,9 +27,11 @@ from .api import (  # noqa: F401
     generate_ndvi_report,
     index_histogram,
     preprocess_large_image,
+    png_info,
     process_image,
     thumbnail,
     thumbnail_plan,
+    thumbnail_png,
     time_series_points,
     timeseries_row,
 )

@@ -152,6 +152,11 @@ SIGNATURES = {
     "lars_h_encode_png_u8": (_I, [_P, _I64, _I64, _I, _P, _I, _P, _SZ, C.POINTER(_I64)]),
     "lars_h_process_image_png": (_I, [_P, _I64, _I64, _I, _I, _I, _U32, _I, _P, C.POINTER(_P * 3), _P, _P,
                                       C.POINTER(_P * 3), _I, C.POINTER(_P * 3), _SZ, _P]),
+    "lars_png_info": (_I, [_P, _I64, _P, _P, _I64]),
+    "lars_png_decode_scratch_bytes": (_SZ, [_I64, _I64, _I, _I64, _I64]),
+    "lars_d_decode_png_u8": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I, _P, _P, _P, _P]),
+    "lars_h_decode_png_u8": (_I, [_P, _I64, _P, _SZ]),
+    "lars_h_thumbnail_png_u8": (_I, [_P, _I64, _I, _I, C.POINTER(_I), C.POINTER(_F), _I64, _I64, _I, _P]),
     "lars_comm_available": (_I, []),
     "lars_comm_unique_id": (_I, [_P]),
     "lars_comm_init": (_I, [C.POINTER(_P), _I, _I, _P]),

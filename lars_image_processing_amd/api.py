@@ -18,6 +18,8 @@ this module                     reference
 ``preprocess_large_image``      process-images.py:398  (Pillow LANCZOS down-scale)
 ``thumbnail``                   process-images.py:186  (Pillow LANCZOS gallery thumbnail; a new object, not in place)
 ``encode_png``                  backend-process.py:70, process-images.py:567-617 (``Image.fromarray(x).save(png)``: same pixels)
+``decode_png``                  process-images.py:181-193 (``np.array(Image.open(io.BytesIO(img_bytes)))``: same array)
+``thumbnail_png``               process-images.py:186-189 from the file's bytes (decode + thumbnail, pixels stay on the GPU)
 ``align_images``                process-images.py:515  (phase correlation + shift)
 ``calculate_index_statistics_by_timeframe``  process-images.py:619 (pandas table)
 ``time_series_points``          process-images.py:814-832 (the numbers ``create_time_series_plot`` draws)
@@ -55,7 +57,8 @@ __all__ = [
     "fix_white_balance", "correct_white_balance", "fix_white_balance_rgnir",
     "calculate_index", "calculate_ndvi", "analyze_index", "analyze_index_statistics",
     "analyze_ndvi_statistics", "index_histogram", "classification_mask", "colorize_index", "process_image",
-    "timeseries_row", "colormap_lut", "preprocess_large_image", "thumbnail", "thumbnail_plan", "encode_png", "align_images", "change_detection",
+    "timeseries_row", "colormap_lut", "preprocess_large_image", "thumbnail", "thumbnail_plan", "encode_png",
+    "png_info", "decode_png", "thumbnail_png", "align_images", "change_detection",
     "colorize_difference", "calculate_index_statistics_by_timeframe", "time_series_points",
     "calculate_ndvi_array", "generate_ndvi_report", "download_processed_images",
     "create_index_visualization", "create_comparison_view", "create_time_series_plot", "create_change_detection_visualization",
@@ -540,6 +543,106 @@ def encode_png(array, palette=None):
     n = C.c_int64(0)
     _ffi.call("lars_h_encode_png_u8", _ffi.ptr(arr), h, w, c, _ffi.ptr(pal), npal, _ffi.ptr(out), out.nbytes, C.byref(n))
     return out[:n.value].tobytes()
+
+
+# ---------------------------------------------------------------------------
+# PNG files decoded on the device
+# ---------------------------------------------------------------------------
+_PNG_INFO_N = 10
+# Pillow's PngImagePlugin._MODES: (bit depth, colour type) -> mode
+_PNG_MODES = {(1, 0): "1", (2, 0): "L", (4, 0): "L", (8, 0): "L", (16, 0): "I;16", (8, 2): "RGB", (16, 2): "RGB",
+              (1, 3): "P", (2, 3): "P", (4, 3): "P", (8, 3): "P", (8, 4): "LA", (16, 4): "RGBA", (8, 6): "RGBA",
+              (16, 6): "RGBA"}
+
+
+def _png_bytes(data, who):
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        arr = np.frombuffer(data, dtype=np.uint8)
+    elif isinstance(data, np.ndarray) and data.dtype == np.uint8 and data.ndim == 1:
+        arr = data
+    else:
+        raise TypeError(f"{who}: a whole PNG file as bytes, bytearray, memoryview or 1-D uint8 array expected, got {type(data).__name__}")
+    return np.ascontiguousarray(arr)
+
+
+def _png_info(arr):
+    lib = _ffi.load()
+    info = (C.c_int64 * _PNG_INFO_N)()
+    if lib.lars_png_info(_ffi.ptr(arr), arr.size, info, None, 0) != 0:
+        raise ValueError(lib.lars_last_error().decode("utf-8", "replace"))
+    return list(info)
+
+
+def png_info(data):
+    """The chunk layout of a PNG file, validated on the host (``lars_png_info``; no device needed).
+
+    Returns ``width``, ``height``, ``bit_depth``, ``color_type``, ``interlace``, ``mode`` (Pillow's name for it),
+    ``channels``, ``idat_bytes`` and ``supported`` (what ``decode_png`` decodes: bit depth 8, no interlace, not APNG).
+    Raises ``ValueError`` for structural damage: bad signature, missing or misplaced IHDR / IDAT / IEND, a chunk running
+    past the end of the file, a bad CRC in a chunk other than IDAT (IDAT CRCs are checked where they are gathered).
+    """
+    w, h, depth, ctype, interlace, channels, idat_bytes, _nidat, _apng, supported = _png_info(_png_bytes(data, "png_info"))
+    return {"width": w, "height": h, "bit_depth": depth, "color_type": ctype, "interlace": interlace,
+            "mode": _PNG_MODES[(depth, ctype)], "channels": channels, "idat_bytes": idat_bytes, "supported": bool(supported)}
+
+
+def _png_check(arr, who):
+    w, h, depth, ctype, interlace, channels, _b, _n, apng, supported = _png_info(arr)
+    if not supported:
+        what = "APNG" if apng else "interlaced" if interlace else f"bit depth {depth}"
+        raise NotImplementedError(f"{who}: {what} PNG files are not supported (8-bit, non-interlaced only)")
+    if not (1 <= h <= 1 << 24 and 1 <= w <= 1 << 24) or h * (1 + w * channels) > (1 << 31) - 1:
+        raise ValueError(f"{who}: {w} x {h} picture of {channels} channels is too large")
+    return h, w, ctype, channels
+
+
+def _png_call(name, *args):
+    try:
+        _ffi.call(name, *args)
+    except _ffi.LarsError as e:
+        if e.code == -1:                                  # LARS_ERR_INVALID: the file's contents
+            raise ValueError(str(e)) from None
+        raise
+
+
+def decode_png(data):
+    """``np.asarray(Image.open(io.BytesIO(data)))`` of a PNG file, decoded on the GPU (process-images.py:181-193).
+
+    ``data``: the whole file as ``bytes``, ``bytearray``, ``memoryview`` or a 1-D uint8 array.  Bit depth 8, no interlace,
+    colour types 0 (L, ``[H, W]``), 2 (RGB, ``[H, W, 3]``), 3 (P: the palette indices, ``[H, W]``), 4 (LA, ``[H, W, 2]``) and
+    6 (RGBA, ``[H, W, 4]``); ancillary chunks are skipped.  Other variants raise ``NotImplementedError``; damaged files
+    raise ``ValueError`` saying what is wrong.  Stricter than Pillow on purpose: the CRC of every IDAT chunk and the
+    zlib stream's Adler-32 trailer are always checked.  One exception: a stream that decodes to more bytes than the image
+    needs (Pillow ignores the extra data) has the extra bytes dropped, not stored -- they could be up to 1032 times the
+    compressed size -- so the Adler-32 over the whole stream cannot be formed, and that trailer is not checked.  Limits: 1 <= h, w <= 2^24 and
+    ``h * (1 + w * channels) < 2^31``.  No CPU fallback.
+    """
+    arr = _png_bytes(data, "decode_png")
+    h, w, _ctype, c = _png_check(arr, "decode_png")
+    out = np.empty((h, w) if c == 1 else (h, w, c), dtype=np.uint8)
+    _png_call("lars_h_decode_png_u8", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
+    return out
+
+
+def thumbnail_png(data, size=(400, 400), reducing_gap=2.0):
+    """``np.asarray`` of ``Image.open(io.BytesIO(data))`` after ``.thumbnail(size, LANCZOS, reducing_gap)``, bit for bit
+    (process-images.py:186-189), from the file's bytes: the decoded pixels stay on the GPU and go straight into the
+    thumbnail kernels, only the thumbnail comes back.  Modes L, RGB and RGBA; others raise ``TypeError`` as ``thumbnail``
+    does.  ``draft`` does nothing for PNG, so ``thumbnail_plan(..., draft_box=None)`` is the whole plan; a file that
+    already fits comes back as ``decode_png`` gives it.  Errors of the file as ``decode_png``."""
+    arr = _png_bytes(data, "thumbnail_png")
+    h, w, ctype, c = _png_check(arr, "thumbnail_png")
+    if ctype not in (0, 2, 6):
+        raise TypeError(f"thumbnail_png: PNG files in mode L, RGB or RGBA (got mode {_PNG_MODES[(8, ctype)]!r})")
+    plan = thumbnail_plan((w, h), size, reducing_gap, None, None, rgba=c == 4)
+    if plan is None:
+        return decode_png(arr)
+    new_w, new_h = plan.size
+    out = np.empty((new_h, new_w) if c == 1 else (new_h, new_w, c), dtype=np.uint8)
+    _png_call("lars_h_thumbnail_png_u8", _ffi.ptr(arr), arr.size, plan.factor[0], plan.factor[1],
+              (C.c_int * 4)(*plan.reduce_box), (C.c_float * 4)(*plan.box), new_h, new_w, int(plan.vertical_first),
+              _ffi.ptr(out))
+    return out
 
 
 def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_arrays=True, want_hist=False,

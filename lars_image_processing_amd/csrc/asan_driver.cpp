@@ -5,6 +5,7 @@
 //   kind 0  lars_h_tiff_lzw_decode(src = bytes, dst of a bytes)
 //   kind 1  lars_h_tiff_lzw_decode_chunks: bytes = { u64 offsets[a], u64 counts[a], file... }, chunk_bytes = b, 3 threads
 //   kind 2  lars_stats_merge over nbytes / sizeof(lars_stats) records (a = how many to pass; 0 must be refused)
+//   kind 3  lars_png_info over a PNG file = bytes, with an IDAT table of a entries
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -61,6 +62,12 @@ int main(int argc, char **argv)
             memset(&out, 0, sizeof out);
             const int rc = lars_stats_merge(reinterpret_cast<const lars_stats *>(src), (int64_t)a, &out);
             printf("%ld merge rc=%d h=%016llx\n", ncase, rc, rc == 0 ? fnv(&out, sizeof out) : 0ull);
+        } else if (kind == 3) {
+            int64_t info[LARS_PNG_INFO_N];
+            std::vector<int64_t> table((size_t)a * 2 + 1, 0);
+            const int rc = lars_png_info(src, nbytes, info, a ? table.data() : nullptr, a);
+            printf("%ld png rc=%d h=%016llx t=%016llx\n", ncase, rc, rc == 0 ? fnv(info, sizeof info) : 0ull,
+                   rc == 0 ? fnv(table.data(), (size_t)a * 16) : 0ull);
         } else {
             fprintf(stderr, "unknown case kind %u\n", kind);
             return 2;

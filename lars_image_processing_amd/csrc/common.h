@@ -33,6 +33,10 @@ struct ThreadCtx {
 int ensure_ctx(ThreadCtx **out);                 // initialises device 0 on first use
 int ws_reserve(ThreadCtx *c, size_t bytes);      // grow-only; synchronises when it grows
 int scratch_reserve(ThreadCtx *c, size_t bytes);
+// resize.hip: lars_h_thumbnail_u8 on a host or device image (need_out: only the workspace size)
+int thumbnail_u8_impl(ThreadCtx *c, const uint8_t *img, bool on_device, char *ws, size_t *need_out, int64_t h, int64_t w,
+                      int channels, int fx, int fy, const int reduce_box[4], const float box[4], int64_t new_h, int64_t new_w,
+                      int vertical_first, uint8_t *out);
 inline hipStream_t pick_stream(ThreadCtx *c, void *stream) {
     return stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
 }

@@ -1,0 +1,1197 @@
+// PNG decoding of 8-bit, non-interlaced pictures on the device.
+//
+// Reference: load_image_from_db (process-images.py:181-193) opens every stored picture with Image.open(io.BytesIO(...))
+// and np.array(img) or img.thumbnail(...): zlib's inflate and libpng-style unfiltering on one host core.  Here the
+// compressed file goes up once and the pixels (or only the thumbnail, lars_h_thumbnail_png_u8) come back.
+//
+// Inflate is serial by nature; the speculation below is checked against the exact serial chain before anything is used,
+// so it only changes the speed, never the result.  The host parser (png_parse.cpp) gives the IDAT table.
+//   k_pd_chunk_scan  one workgroup: output offset of each IDAT payload (exclusive scan of the lengths).
+//   k_pd_gather      one workgroup per IDAT chunk: payload into one contiguous stream, CRC-32 of type + payload (per-thread
+//                    pieces shifted by x^(8 * bytes after them) mod P, as k_png_idat builds them) against the stored CRC.
+//   k_pd_mark        one thread per bit offset: does a dynamic block start here that zlib's inflate would accept (HLIT,
+//                    HDIST bounds, complete code-length code, repeats inside the table, literal/length and distance codes
+//                    neither over-subscribed nor incomplete but for zlib's single-code case, an end-of-block code)?
+//                    One ballot mask per wave and one count per workgroup.
+//   k_pd_scan_u32    one workgroup: exclusive scan of those counts.  k_pd_compact: the sorted candidate list (no atomics).
+//   k_pd_pass_a      one wave per candidate: Huffman tables in LDS, decode to end-of-block counting only (capped), record
+//                    end bit, BFINAL, byte count, validity, and every PD_CK symbols a checkpoint (bit position, bytes so far).
+//   k_pd_walk        one wave: the zlib header, then from bit 16 the true chain of blocks.  At a start that is a valid
+//                    candidate it jumps to the candidate's end; anywhere else (stored and fixed-Huffman blocks, capped or
+//                    missed candidates) it decodes the block itself, exactly.  Gives the true block list and output offsets.
+//   k_pd_pass_b      one wave per segment of a true block (PD_CK symbols from a checkpoint, or a whole block the walker
+//                    decoded itself): decode again, literals straight into place, copies as source indices
+//                    (src[i] = i - dist); a copy from before the stream start is an error.  Bytes past the image are dropped.
+//   k_pd_jump        copy resolution by pointer jumping, src[i] = src[src[i]], one launch per round, at most
+//                    ceil(log2 n) + 1 rounds, each exits at once when the round before changed nothing.
+//   k_pd_resolve     bytes from their sources into rows padded to 16 bytes (and a filter byte per row), Adler-32 partial
+//                    sums per workgroup; k_pd_adler combines and checks them.
+//   k_pd_unfilter    one workgroup per image: lane i of a wave owns row 64k + i and at step t reconstructs the 16-byte
+//                    chunk t - i of a tile of PD_TILE columns, byte by byte in registers; the chunk above comes from lane
+//                    i - 1 one step earlier (__shfl_up), the upper-left bytes are the previous ones.  The waves take 64-row
+//                    groups in turn; a group waits for the tile above it with a bounded LDS spin (workgroup-scope acquire /
+//                    release), never across workgroups.  k_pd_rows drops the padding.
+// Every error is a status code (LARS_PNGD_*) in device memory; every kernel after a failing one returns at once.
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "common.h"
+
+namespace lars {
+
+#define PD_FB 10                       // bits of the first-level Huffman lookup (longer codes: canonical bit-by-bit decode)
+#define PD_BATCH 256                   // symbols decoded by the serial lane between two expansions by the whole wave
+#define PD_CAP_SYMBOLS (1 << 17)       // pass A gives up after this many symbols (the walker then decodes the block)
+#define PD_CK 4096                     // symbols per pass-B segment of a block pass A has checkpointed
+#define PD_CKMAX (PD_CAP_SYMBOLS / PD_CK)
+#define PD_MARK_THREADS 256
+#define PD_TILE 2048                   // unfilter: columns per tile (a multiple of 16)
+#define PD_UNF_WAVES 16
+#define PD_AHEAD 4                     // unfilter: loads issued this many steps before their use
+#define PD_CRC_POLY 0xEDB88320u
+#define PD_ADLER_MOD 65521u
+#define PD_RESOLVE_BYTES 64            // bytes per thread of k_pd_resolve
+#define PD_WAIT_TICKS 1000000000ull    // wall-clock ticks (100 MHz) of one bounded unfilter wait: 10 s
+
+struct PdCtl {
+    int status[2];
+    unsigned int ncand;
+    unsigned int nblocks;
+    unsigned long long total;          // decoded bytes of the whole stream
+    unsigned long long adler_byte;     // stream byte of the Adler-32 trailer
+    unsigned int changed[64];          // k_pd_jump: round r changed something
+    unsigned long long adler_sums[2];
+};
+
+struct PdCand {                        // one block-start candidate
+    unsigned long long pos, end, bytes;
+    unsigned int valid, final_, nck, pad_;  // nck: checkpoints pass A left (candidates below the slot count only)
+};
+
+struct PdCheck {                       // pass A's state after every PD_CK symbols of a block: bit position, bytes so far
+    unsigned long long pos, out;
+};
+
+struct PdBlock {                       // one segment of a block of the true chain that writes image bytes
+    unsigned long long pos;            // the block's header
+    unsigned long long start;          // bit to decode from (0: after the header)
+    unsigned long long out;            // output byte of that bit
+    unsigned int limit, pad_;          // most symbols to decode (0xFFFFFFFF: to end-of-block)
+};
+
+__device__ inline void pd_fail(PdCtl *ctl, int code, int detail)
+{
+    if (atomicCAS(&ctl->status[0], 0, code) == 0) ctl->status[1] = detail;
+}
+
+__device__ inline bool pd_failed(const PdCtl *ctl) { return *(volatile const int *)&ctl->status[0] != 0; }
+
+// ---- bit reader over the gathered stream (LSB first; the stream is padded with zero words) ---------------------------
+struct BitReader {
+    const unsigned int *w;
+    unsigned long long nw, wt, buf;      // wt: the next word to take
+    uint4 cur, nxt;                      // the aligned quad holding word wt and the one after it (loaded ahead)
+    int cnt;
+    __device__ __forceinline__ uint4 quad(unsigned long long q) const
+    {
+        return q + 4 <= nw ? *reinterpret_cast<const uint4 *>(w + q) : make_uint4(0u, 0u, 0u, 0u);
+    }
+    __device__ __forceinline__ unsigned int take()
+    {
+        const unsigned int v = (wt & 2) ? ((wt & 1) ? cur.w : cur.z) : ((wt & 1) ? cur.y : cur.x);
+        ++wt;
+        if ((wt & 3) == 0) { cur = nxt; nxt = quad(wt + 4); }
+        return v;
+    }
+    __device__ __forceinline__ void init(const unsigned int *words, unsigned long long nwords, unsigned long long pos)
+    {
+        w = words; nw = nwords; wt = pos >> 5;
+        cur = quad(wt & ~3ull);
+        nxt = quad((wt & ~3ull) + 4);
+        const int sh = (int)(pos & 31);
+        buf = (unsigned long long)take() >> sh;
+        cnt = 32 - sh;
+        refill();
+    }
+    __device__ __forceinline__ void refill()
+    {
+        if (cnt <= 32) {
+            buf |= (unsigned long long)take() << cnt;
+            cnt += 32;
+        }
+    }
+    __device__ __forceinline__ unsigned int bits(int n)                 // n <= 32 - with at least n bits in buf
+    {
+        const unsigned int v = (unsigned int)(buf & ((1ull << n) - 1));
+        buf >>= n; cnt -= n;
+        return v;
+    }
+    __device__ __forceinline__ unsigned int need(int n) { if (cnt < n) refill(); return bits(n); }
+    __device__ __forceinline__ unsigned long long pos() const { return wt * 32 - (unsigned long long)cnt; }
+};
+
+__constant__ unsigned short c_lbase[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115,
+                                           131, 163, 195, 227, 258};
+__constant__ unsigned char c_lext[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
+__constant__ unsigned short c_dbase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537,
+                                           2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
+__constant__ unsigned char c_dext[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
+__constant__ unsigned char c_clorder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+
+// canonical decode, one bit at a time (puff's algorithm); count[1..maxlen], symbols sorted by (length, value); -1: no code
+__device__ __forceinline__ int pd_slow_decode(unsigned long long b, const unsigned short *count, const unsigned short *sym, int maxlen, int *used)
+{
+    int code = 0, first = 0, index = 0;
+    for (int len = 1; len <= maxlen; ++len) {
+        code |= (int)(b & 1); b >>= 1;
+        const int c = count[len];
+        if (code - c < first) { *used = len; return sym[index + (code - first)]; }
+        index += c; first += c; first <<= 1; code <<= 1;
+    }
+    return -1;
+}
+
+// zlib's inflate_table acceptance: 0 ok, 1 over-subscribed or incomplete (except a single code of length 1 for lengths and
+// distances; an empty distance code is accepted and fails when used)
+__device__ inline int pd_code_check(const unsigned short *count, bool codes)
+{
+    int max = 15;
+    while (max >= 1 && count[max] == 0) --max;
+    if (max == 0) return codes ? 1 : 0;
+    int left = 1;
+    for (int len = 1; len <= 15; ++len) {
+        left <<= 1;
+        left -= count[len];
+        if (left < 0) return 1;
+    }
+    if (left > 0 && (codes || max != 1)) return 1;
+    return 0;
+}
+
+// ---- k_pd_mark: header test at one bit offset, thread-local ---------------------------------------------------------
+__device__ bool pd_dynamic_ok(const unsigned int *words, unsigned long long nw, unsigned long long nbits, unsigned long long pos)
+{
+    if (pos + 17 > nbits) return false;
+    {
+        // pre-filter on a raw window of at least 97 bits: block type 2, HLIT / HDIST bounds, a complete code-length code
+        // (implied by the full test below, which most offsets never reach)
+        const unsigned long long wi = pos >> 5;
+        const int sh = (int)(pos & 31);
+        unsigned long long a = words[wi] | (unsigned long long)words[wi + 1] << 32;
+        unsigned long long b = words[wi + 2] | (unsigned long long)words[wi + 3] << 32;
+        if (sh) { a = (a >> sh) | (b << (64 - sh)); b >>= sh; }
+        if (((a >> 1) & 3) != 2 || ((a >> 3) & 31) > 29 || ((a >> 8) & 31) > 29) return false;
+        const int ncode = (int)((a >> 13) & 15) + 4;
+        int kraft = 0;
+        for (int i = 0; i < ncode; ++i) {
+            const int o = 17 + 3 * i;
+            const unsigned int len = (unsigned int)((o >= 64 ? (b >> (o - 64)) : o > 61 ? ((a >> o) | (b << (64 - o))) : (a >> o)) & 7);
+            if (len) kraft += 128 >> len;
+        }
+        if (kraft != 128) return false;
+    }
+    BitReader br;
+    br.init(words, nw, pos);
+    br.bits(1);
+    if (br.bits(2) != 2) return false;
+    const int nlen = (int)br.bits(5) + 257, ndist = (int)br.bits(5) + 1, ncode = (int)br.bits(4) + 4;
+    if (nlen > 286 || ndist > 30) return false;
+    unsigned short cl[19];
+    for (int i = 0; i < 19; ++i) cl[i] = 0;
+    for (int i = 0; i < ncode; ++i) cl[c_clorder[i]] = (unsigned short)br.need(3);
+    unsigned short count[16], sym[19], offs[16];
+    for (int i = 0; i < 16; ++i) count[i] = 0;
+    for (int i = 0; i < 19; ++i) count[cl[i]]++;
+    count[0] = 0;
+    if (pd_code_check(count, true)) return false;
+    offs[1] = 0;
+    for (int l = 1; l < 15; ++l) offs[l + 1] = offs[l] + count[l];
+    for (int s = 0; s < 19; ++s) if (cl[s]) sym[offs[cl[s]]++] = (unsigned short)s;
+    unsigned short lcount[16], dcount[16];
+    for (int i = 0; i < 16; ++i) { lcount[i] = 0; dcount[i] = 0; }
+    int idx = 0, prev = 0, eob = 0;
+    const int n = nlen + ndist;
+    while (idx < n) {
+        br.refill();
+        int used = 0;
+        const int s = pd_slow_decode(br.buf, count, sym, 7, &used);
+        if (s < 0) return false;
+        br.bits(used);
+        int len, rep;
+        if (s < 16) { len = s; rep = 1; }
+        else if (s == 16) { if (idx == 0) return false; len = prev; rep = 3 + (int)br.bits(2); }
+        else if (s == 17) { len = 0; rep = 3 + (int)br.bits(3); }
+        else { len = 0; rep = 11 + (int)br.bits(7); }
+        if (idx + rep > n) return false;
+        for (int k = 0; k < rep; ++k, ++idx) {
+            if (idx < nlen) { lcount[len]++; if (idx == 256) eob = len; }
+            else dcount[len]++;
+        }
+        prev = len;
+        if (br.pos() > nbits) return false;
+    }
+    lcount[0] = 0; dcount[0] = 0;
+    return eob != 0 && !pd_code_check(lcount, false) && !pd_code_check(dcount, false);
+}
+
+// ---- one block, decoded by a whole wave (blockDim.x == 64) ---------------------------------------------------------
+struct PdLds {
+    unsigned short lfast[1 << PD_FB], dfast[1 << PD_FB];
+    unsigned short lcnt[16], dcnt[16], lsym[288], dsym[32], clcnt[16], clsym[19];
+    unsigned char lens[320];
+    unsigned long long rec_o[PD_BATCH];
+    unsigned int rec_d[PD_BATCH], rec_l[PD_BATCH];
+    // header / result, written by lane 0
+    int kind, err, final_, done, nrec;
+    unsigned long long data_pos, end, bytes;
+    unsigned int stored_len;
+};
+
+// lane 0: the block header at pos into L (kind 0 stored, 1 fixed, 2 dynamic; err LARS_PNGD_DEFLATE detail or 0)
+__device__ void pd_header(PdLds &L, const unsigned int *words, unsigned long long nw, unsigned long long nbits, unsigned long long pos)
+{
+    L.err = 0;
+    if (pos + 3 > nbits) { L.err = 5; return; }
+    BitReader br;
+    br.init(words, nw, pos);
+    L.final_ = (int)br.bits(1);
+    const int type = (int)br.bits(2);
+    L.kind = type;
+    if (type == 3) { L.err = 1; return; }
+    if (type == 0) {
+        const unsigned long long p = (br.pos() + 7) & ~7ull;
+        if (p + 32 > nbits) { L.err = 5; return; }
+        const uint8_t *bytes = reinterpret_cast<const uint8_t *>(words);
+        const unsigned int len = bytes[p / 8] | (unsigned int)bytes[p / 8 + 1] << 8;
+        const unsigned int nlen = bytes[p / 8 + 2] | (unsigned int)bytes[p / 8 + 3] << 8;
+        if (len != (~nlen & 0xFFFFu)) { L.err = 2; return; }
+        L.data_pos = p + 32;
+        L.stored_len = len;
+        if (L.data_pos + 8ull * len > nbits) { L.err = 5; return; }
+        return;
+    }
+    int nlen = 288, ndist = 32;
+    if (type == 1) {
+        for (int i = 0; i < 288; ++i) L.lens[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8;
+        for (int i = 0; i < 32; ++i) L.lens[288 + i] = 5;
+    } else {
+        nlen = (int)br.bits(5) + 257;
+        ndist = (int)br.bits(5) + 1;
+        const int ncode = (int)br.bits(4) + 4;
+        if (nlen > 286 || ndist > 30) { L.err = 3; return; }
+        unsigned char cl[19];
+        for (int i = 0; i < 19; ++i) cl[i] = 0;
+        for (int i = 0; i < ncode; ++i) cl[c_clorder[i]] = (unsigned char)br.need(3);
+        for (int i = 0; i < 16; ++i) L.clcnt[i] = 0;
+        for (int i = 0; i < 19; ++i) L.clcnt[cl[i]]++;
+        L.clcnt[0] = 0;
+        if (pd_code_check(L.clcnt, true)) { L.err = 3; return; }
+        unsigned short offs[16];
+        offs[1] = 0;
+        for (int l = 1; l < 15; ++l) offs[l + 1] = offs[l] + L.clcnt[l];
+        for (int s = 0; s < 19; ++s) if (cl[s]) L.clsym[offs[cl[s]]++] = (unsigned short)s;
+        unsigned char tmp[316];
+        int idx = 0;
+        const int n = nlen + ndist;
+        while (idx < n) {
+            br.refill();
+            int used = 0;
+            const int s = pd_slow_decode(br.buf, L.clcnt, L.clsym, 7, &used);
+            if (s < 0) { L.err = 3; return; }
+            br.bits(used);
+            int len, rep;
+            if (s < 16) { len = s; rep = 1; }
+            else if (s == 16) { if (idx == 0) { L.err = 3; return; } len = tmp[idx - 1]; rep = 3 + (int)br.bits(2); }
+            else if (s == 17) { len = 0; rep = 3 + (int)br.bits(3); }
+            else { len = 0; rep = 11 + (int)br.bits(7); }
+            if (idx + rep > n) { L.err = 3; return; }
+            for (int k = 0; k < rep; ++k) tmp[idx++] = (unsigned char)len;
+            if (br.pos() > nbits) { L.err = 5; return; }
+        }
+        for (int i = 0; i < 288; ++i) L.lens[i] = i < nlen ? tmp[i] : 0;
+        for (int i = 0; i < 32; ++i) L.lens[288 + i] = i < ndist ? tmp[nlen + i] : 0;
+        if (L.lens[256] == 0) { L.err = 3; return; }
+    }
+    for (int i = 0; i < 16; ++i) { L.lcnt[i] = 0; L.dcnt[i] = 0; }
+    for (int i = 0; i < 288; ++i) L.lcnt[L.lens[i]]++;
+    for (int i = 0; i < 32; ++i) L.dcnt[L.lens[288 + i]]++;
+    L.lcnt[0] = 0; L.dcnt[0] = 0;
+    if (pd_code_check(L.lcnt, false) || pd_code_check(L.dcnt, false)) { L.err = 3; return; }
+    unsigned short lo[16], dof[16];
+    lo[1] = 0; dof[1] = 0;
+    for (int l = 1; l < 15; ++l) { lo[l + 1] = lo[l] + L.lcnt[l]; dof[l + 1] = dof[l] + L.dcnt[l]; }
+    for (int s = 0; s < 288; ++s) if (L.lens[s]) L.lsym[lo[L.lens[s]]++] = (unsigned short)s;
+    for (int s = 0; s < 32; ++s) if (L.lens[288 + s]) L.dsym[dof[L.lens[288 + s]]++] = (unsigned short)s;
+    L.data_pos = br.pos();
+}
+
+// all lanes: first-level tables, entry = symbol << 4 | length, 0 for "longer than PD_FB bits or no code"
+__device__ __forceinline__ void pd_fast_tables(PdLds &L)
+{
+    for (int e = threadIdx.x; e < (1 << PD_FB); e += blockDim.x) {
+        int used = 0;
+        int s = pd_slow_decode((unsigned long long)e, L.lcnt, L.lsym, PD_FB, &used);
+        L.lfast[e] = s < 0 ? 0 : (unsigned short)(s << 4 | used);
+        s = pd_slow_decode((unsigned long long)e, L.dcnt, L.dsym, PD_FB, &used);
+        L.dfast[e] = s < 0 ? 0 : (unsigned short)(s << 4 | used);
+    }
+}
+
+__device__ __forceinline__ int pd_symbol(BitReader &br, const unsigned short *fast, const unsigned short *cnt, const unsigned short *sym)
+{
+    const unsigned short v = fast[br.buf & ((1u << PD_FB) - 1)];
+    if (v) { br.bits(v & 15); return v >> 4; }
+    int used = 0;
+    const int s = pd_slow_decode(br.buf, cnt, sym, 15, &used);
+    if (s >= 0) br.bits(used);
+    return s;
+}
+
+// The block at pos, by the whole wave.  write: literals into lit[base + k], source indices into src (copies point back),
+// nothing at or past `need`.  cap: most symbols before giving up (L.done = 2).  Results in L: err (LARS_PNGD_DEFLATE
+// detail, or -1 for a copy from before the stream start), end, bytes, final_, done (1 finished).
+__device__ __forceinline__ void pd_block(PdLds &L, const unsigned int *words, unsigned long long nw, unsigned long long nbits, unsigned long long pos,
+                         bool write, unsigned long long base, unsigned long long need, uint8_t *lit, int *src, unsigned int cap,
+                         unsigned long long start = 0, PdCheck *ckp = nullptr, unsigned int *nck = nullptr)
+{
+    const int lane = threadIdx.x;
+    if (lane == 0) { pd_header(L, words, nw, nbits, pos); L.done = 0; L.bytes = 0; }
+    __syncthreads();
+    if (L.err) return;
+    if (L.kind == 0) {
+        const unsigned int n = L.stored_len;
+        if (write) {
+            const uint8_t *bytes = reinterpret_cast<const uint8_t *>(words) + L.data_pos / 8;
+            for (unsigned int k = lane; k < n; k += blockDim.x) {
+                const unsigned long long o = base + k;
+                if (o < need) { lit[o] = bytes[k]; src[o] = (int)o; }
+            }
+        }
+        __syncthreads();
+        if (lane == 0) { L.end = L.data_pos + 8ull * n; L.bytes = n; L.done = 1; }
+        __syncthreads();
+        return;
+    }
+    pd_fast_tables(L);
+    __syncthreads();
+    BitReader br;
+    if (lane == 0) br.init(words, nw, start ? start : L.data_pos);
+    unsigned long long out = 0;
+    unsigned int nsym = 0;
+    if (!write) {
+        // counting only: one lane, no records, no barriers; the end of the stream and the cap are checked every 256
+        // symbols (past the end the reader gives zero bits, and every symbol takes at least one)
+        if (lane == 0) {
+            int err = 0, done = 0;
+            for (;;) {
+                br.refill();
+                const int s = pd_symbol(br, L.lfast, L.lcnt, L.lsym);
+                if (s < 256) {
+                    if (s < 0) { err = 4; break; }
+                    ++out;
+                } else if (s == 256) {
+                    done = 1;
+                    break;
+                } else {
+                    const int ls = s - 257;
+                    if (ls >= 29) { err = 4; break; }
+                    out += c_lbase[ls] + br.bits(c_lext[ls]);
+                    br.refill();
+                    const int ds = pd_symbol(br, L.dfast, L.dcnt, L.dsym);
+                    if (ds < 0 || ds >= 30) { err = 4; break; }
+                    br.bits(c_dext[ds]);
+                }
+                if ((++nsym & 255u) == 0) {
+                    if (br.pos() > nbits) { err = 5; break; }
+                    if (ckp && (nsym & (PD_CK - 1)) == 0 && nsym <= PD_CAP_SYMBOLS) {
+                        ckp[nsym / PD_CK - 1].pos = br.pos();
+                        ckp[nsym / PD_CK - 1].out = out;
+                    }
+                    if (nsym >= cap) { done = 2; break; }
+                }
+            }
+            if (br.pos() > nbits) { err = 5; done = 0; }
+            L.err = err; L.done = done; L.end = br.pos(); L.bytes = out;
+            if (nck) *nck = min(nsym / PD_CK, (unsigned int)PD_CKMAX);
+        }
+        __syncthreads();
+        return;
+    }
+    for (;;) {
+        if (lane == 0) {
+            int nrec = 0;
+            while (nrec < PD_BATCH) {
+                br.refill();
+                const int s = pd_symbol(br, L.lfast, L.lcnt, L.lsym);
+                if (s < 0) { L.err = 4; break; }
+                if (s < 256) {
+                    L.rec_o[nrec] = out; L.rec_d[nrec] = 0; L.rec_l[nrec] = (unsigned int)s; ++nrec;
+                    ++out;
+                } else if (s == 256) {
+                    L.done = 1;
+                    break;
+                } else {
+                    const int ls = s - 257;
+                    if (ls >= 29) { L.err = 4; break; }
+                    const unsigned int len = c_lbase[ls] + br.bits(c_lext[ls]);
+                    br.refill();
+                    const int ds = pd_symbol(br, L.dfast, L.dcnt, L.dsym);
+                    if (ds < 0 || ds >= 30) { L.err = 4; break; }
+                    const unsigned int dist = c_dbase[ds] + br.bits(c_dext[ds]);
+                    if (write && dist > base + out) { L.err = -1; break; }
+                    L.rec_o[nrec] = out; L.rec_d[nrec] = dist; L.rec_l[nrec] = len; ++nrec;
+                    out += len;
+                }
+                if (br.pos() > nbits) { L.err = 5; break; }
+                if (++nsym >= cap) { L.done = 2; break; }
+            }
+            L.nrec = nrec;
+        }
+        __syncthreads();
+        if (write) {
+            const int nrec = L.nrec;
+            for (int r = lane; r < nrec; r += blockDim.x) {
+                const unsigned long long o = base + L.rec_o[r];
+                const unsigned int d = L.rec_d[r];
+                if (d == 0) {
+                    if (o < need) { lit[o] = (uint8_t)L.rec_l[r]; src[o] = (int)o; }
+                } else {
+                    const unsigned int len = L.rec_l[r];
+                    for (unsigned int k = 0; k < len && o + k < need; ++k) src[o + k] = (int)(o + k - d);
+                }
+            }
+        }
+        const bool stop = L.err != 0 || L.done != 0;
+        __syncthreads();
+        if (stop) break;
+    }
+    if (lane == 0) { L.end = br.pos(); L.bytes = out; }
+    __syncthreads();
+}
+
+// ---- CRC-32 pieces (as png.hip's k_png_idat) -------------------------------------------------------------------------
+__device__ inline unsigned int pd_crc_multmodp(unsigned int a, unsigned int b)
+{
+    unsigned int m = 1u << 31, p = 0;
+    for (;;) {
+        if (a & m) {
+            p ^= b;
+            if ((a & (m - 1)) == 0) break;
+        }
+        m >>= 1;
+        b = (b & 1u) ? (b >> 1) ^ PD_CRC_POLY : b >> 1;
+    }
+    return p;
+}
+
+__device__ inline unsigned int pd_crc_x2nmodp(const unsigned int *x2n, unsigned long long n, unsigned int k)
+{
+    unsigned int p = 1u << 31;
+    while (n) {
+        if (n & 1) p = pd_crc_multmodp(x2n[k & 31], p);
+        n >>= 1;
+        ++k;
+    }
+    return p;
+}
+
+// one workgroup: off[i] = sum of len[0..i) over the IDAT table { offset, length } pairs
+__global__ __launch_bounds__(1024) void k_pd_chunk_scan(const long long *__restrict__ table, long long n,
+                                                         unsigned long long *__restrict__ off)
+{
+    __shared__ unsigned long long part[1024];
+    const int tid = threadIdx.x;
+    const long long per = (n + 1023) / 1024, lo = min(n, tid * per), hi = min(n, lo + per);
+    unsigned long long s = 0;
+    for (long long i = lo; i < hi; ++i) s += (unsigned long long)table[2 * i + 1];
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long run = 0;
+        for (int t = 0; t < 1024; ++t) { const unsigned long long v = part[t]; part[t] = run; run += v; }
+    }
+    __syncthreads();
+    unsigned long long run = part[tid];
+    for (long long i = lo; i < hi; ++i) { off[i] = run; run += (unsigned long long)table[2 * i + 1]; }
+}
+
+#define PD_GATHER_THREADS 256
+
+// one workgroup per IDAT chunk (grid-stride): payload into the stream, CRC check
+__global__ __launch_bounds__(PD_GATHER_THREADS) void k_pd_gather(const uint8_t *__restrict__ file, const long long *__restrict__ table,
+                                                                 long long n, const unsigned long long *__restrict__ off,
+                                                                 uint8_t *__restrict__ stream, PdCtl *ctl)
+{
+    __shared__ unsigned int tab[256];
+    __shared__ unsigned int x2n[32];
+    __shared__ unsigned int part[PD_GATHER_THREADS];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 256; i += PD_GATHER_THREADS) {
+        unsigned int c = (unsigned int)i;
+        for (int k = 0; k < 8; ++k) c = (c & 1u) ? PD_CRC_POLY ^ (c >> 1) : c >> 1;
+        tab[i] = c;
+    }
+    if (tid == 0) {
+        unsigned int p = 1u << 30;               // x^1
+        x2n[0] = p;
+        for (int i = 1; i < 32; ++i) x2n[i] = p = pd_crc_multmodp(p, p);
+    }
+    __syncthreads();
+    for (long long k = blockIdx.x; k < n; k += gridDim.x) {
+        const unsigned long long src = (unsigned long long)table[2 * k];
+        const unsigned int m = (unsigned int)table[2 * k + 1];
+        const uint8_t *z = file + src;
+        uint8_t *dst = stream + off[k];
+        for (unsigned int j = tid; j < m; j += PD_GATHER_THREADS) dst[j] = z[j];
+        const unsigned int len = m + 4u;
+        const unsigned int chunk = (len + PD_GATHER_THREADS - 1) / PD_GATHER_THREADS;
+        const unsigned int lo = min(len, tid * chunk), hi = min(len, lo + chunk);
+        unsigned int crc = 0xFFFFFFFFu;
+        for (unsigned int j = lo; j < hi; ++j) crc = tab[(crc ^ (unsigned int)z[(long long)j - 4]) & 255u] ^ (crc >> 8);  // z - 4: "IDAT"
+        crc = hi > lo ? ~crc : 0u;
+        part[tid] = crc ? pd_crc_multmodp(pd_crc_x2nmodp(x2n, len - hi, 3), crc) : 0u;
+        __syncthreads();
+        for (int half = PD_GATHER_THREADS / 2; half > 0; half >>= 1) {
+            if (tid < half) part[tid] ^= part[tid + half];
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const uint8_t *c = z + m;
+            const unsigned int want = (unsigned int)c[0] << 24 | (unsigned int)c[1] << 16 | (unsigned int)c[2] << 8 | c[3];
+            if (part[0] != want) pd_fail(ctl, LARS_PNGD_CRC, (int)min(k, 0x7FFFFFFFll));
+        }
+        __syncthreads();
+    }
+}
+
+// one thread per bit offset: ballot mask per wave, candidate count per workgroup
+__global__ __launch_bounds__(PD_MARK_THREADS) void k_pd_mark(const unsigned int *__restrict__ words, unsigned long long nw,
+                                                             unsigned long long nbits, unsigned long long *__restrict__ masks,
+                                                             unsigned int *__restrict__ wgcnt, const PdCtl *ctl)
+{
+    __shared__ unsigned int cnt[PD_MARK_THREADS / 64];
+    const unsigned long long pos = (unsigned long long)blockIdx.x * PD_MARK_THREADS + threadIdx.x;
+    const bool ok = !pd_failed(ctl) && pos >= 16 && pos < nbits && pd_dynamic_ok(words, nw, nbits, pos);
+    const unsigned long long m = __ballot(ok);
+    const int wave = threadIdx.x / 64;
+    if ((threadIdx.x & 63) == 0) {
+        masks[(unsigned long long)blockIdx.x * (PD_MARK_THREADS / 64) + wave] = m;
+        cnt[wave] = (unsigned int)__popcll(m);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned int s = 0;
+        for (int i = 0; i < PD_MARK_THREADS / 64; ++i) s += cnt[i];
+        wgcnt[blockIdx.x] = s;
+    }
+}
+
+// one workgroup: exclusive scan of n counts in place; ctl->ncand = min(total, cap)
+__global__ __launch_bounds__(1024) void k_pd_scan_u32(unsigned int *__restrict__ v, long long n, unsigned int cap, PdCtl *ctl)
+{
+    __shared__ unsigned long long part[1024];
+    const int tid = threadIdx.x;
+    const long long per = (n + 1023) / 1024, lo = min(n, tid * per), hi = min(n, lo + per);
+    unsigned long long s = 0;
+    for (long long i = lo; i < hi; ++i) s += v[i];
+    part[tid] = s;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long run = 0;
+        for (int t = 0; t < 1024; ++t) { const unsigned long long x = part[t]; part[t] = run; run += x; }
+        ctl->ncand = (unsigned int)min(run, (unsigned long long)cap);
+    }
+    __syncthreads();
+    unsigned long long run = part[tid];
+    for (long long i = lo; i < hi; ++i) {
+        const unsigned int x = v[i];
+        v[i] = (unsigned int)min(run, 0xFFFFFFFFull);
+        run += x;
+    }
+}
+
+__global__ __launch_bounds__(PD_MARK_THREADS) void k_pd_compact(const unsigned long long *__restrict__ masks,
+                                                                const unsigned int *__restrict__ wgbase, unsigned int cap,
+                                                                PdCand *__restrict__ cands)
+{
+    const int wave = threadIdx.x / 64, lane = threadIdx.x & 63;
+    const unsigned long long *mk = masks + (unsigned long long)blockIdx.x * (PD_MARK_THREADS / 64);
+    const unsigned long long m = mk[wave];
+    if (!((m >> lane) & 1ull)) return;
+    unsigned long long idx = wgbase[blockIdx.x];
+    for (int i = 0; i < wave; ++i) idx += (unsigned long long)__popcll(mk[i]);
+    idx += (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
+    if (idx < cap) cands[idx].pos = (unsigned long long)blockIdx.x * PD_MARK_THREADS + threadIdx.x;
+}
+
+// one wave per candidate (grid-stride): counting decode, capped
+__global__ __launch_bounds__(64) void k_pd_pass_a(const unsigned int *__restrict__ words, unsigned long long nw,
+                                                  unsigned long long nbits, PdCand *__restrict__ cands, PdCheck *__restrict__ checks,
+                                                  unsigned int nslot, const PdCtl *ctl)
+{
+    __shared__ PdLds L;
+    __shared__ unsigned int nck;
+    if (pd_failed(ctl)) return;
+    const unsigned int n = ctl->ncand;
+    for (unsigned int c = blockIdx.x; c < n; c += gridDim.x) {
+        const unsigned long long pos = cands[c].pos;
+        if (threadIdx.x == 0) nck = 0;
+        pd_block(L, words, nw, nbits, pos, false, 0, 0, nullptr, nullptr, PD_CAP_SYMBOLS, 0,
+                 c < nslot ? checks + (unsigned long long)c * PD_CKMAX : nullptr, c < nslot ? &nck : nullptr);
+        if (threadIdx.x == 0) {
+            PdCand r;
+            r.pos = pos;
+            r.valid = L.err == 0 && L.done == 1;
+            r.end = L.end;
+            r.bytes = L.bytes;
+            r.final_ = (unsigned int)L.final_;
+            r.nck = L.kind == 0 ? 0u : nck;
+            r.pad_ = 0;
+            cands[c] = r;
+        }
+        __syncthreads();
+    }
+}
+
+// one wave: the zlib header, then the exact chain of blocks
+__global__ __launch_bounds__(64) void k_pd_walk(const unsigned int *__restrict__ words, unsigned long long nw, unsigned long long nbits,
+                                                const PdCand *__restrict__ cands, const PdCheck *__restrict__ checks,
+                                                unsigned int nslot, PdBlock *__restrict__ blocks, unsigned int block_cap,
+                                                unsigned long long need, PdCtl *ctl)
+{
+    __shared__ PdLds L;
+    __shared__ int stop;
+    __shared__ unsigned long long s_pos, s_out;
+    __shared__ unsigned int s_nb;
+    __shared__ int s_hit;
+    __shared__ unsigned int s_ci;
+    __shared__ PdCand s_c;
+    const int lane = threadIdx.x;
+    if (pd_failed(ctl)) return;
+    if (lane == 0) {
+        const uint8_t *b = reinterpret_cast<const uint8_t *>(words);
+        const unsigned int cmf = b[0], flg = b[1];
+        stop = 0;
+        if (nbits < 16 || (cmf & 15) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 != 0 || (flg & 32)) {
+            pd_fail(ctl, LARS_PNGD_ZLIB_HEADER, nbits < 16 ? -1 : (int)((cmf << 8) | flg));
+            stop = 1;
+        }
+        s_pos = 16; s_out = 0; s_nb = 0;
+    }
+    __syncthreads();
+    if (stop) return;
+    const unsigned int ncand = ctl->ncand;
+    for (;;) {
+        if (lane == 0) {
+            // binary search of the sorted candidate list
+            unsigned int lo = 0, hi = ncand;
+            while (lo < hi) {
+                const unsigned int mid = (lo + hi) / 2;
+                if (cands[mid].pos < s_pos) lo = mid + 1; else hi = mid;
+            }
+            s_hit = lo < ncand && cands[lo].pos == s_pos && cands[lo].valid;
+            if (s_hit) { s_c = cands[lo]; s_ci = lo; }
+        }
+        __syncthreads();
+        unsigned long long end, bytes;
+        int fin;
+        if (s_hit) {
+            end = s_c.end; bytes = s_c.bytes; fin = (int)s_c.final_;
+        } else {
+            pd_block(L, words, nw, nbits, s_pos, false, 0, 0, nullptr, nullptr, 0xFFFFFFFFu);
+            if (L.err) {
+                if (lane == 0) pd_fail(ctl, LARS_PNGD_DEFLATE, L.err);
+                return;
+            }
+            end = L.end; bytes = L.bytes; fin = L.final_;
+        }
+        if (lane == 0) {
+            if (bytes && s_out < need) {
+                // a checkpointed block becomes nck + 1 segments of PD_CK symbols; any other block one segment
+                const unsigned int nck = (s_hit && s_ci < nslot) ? s_c.nck : 0u;
+                if (s_nb + nck + 1 > block_cap) { pd_fail(ctl, LARS_PNGD_INTERNAL, 1); stop = 1; }
+                else {
+                    PdBlock sg;
+                    sg.pos = s_pos; sg.start = 0; sg.out = s_out; sg.limit = nck ? PD_CK : 0xFFFFFFFFu; sg.pad_ = 0;
+                    blocks[s_nb++] = sg;
+                    for (unsigned int i = 1; i <= nck; ++i) {
+                        const PdCheck ck = checks[(unsigned long long)s_ci * PD_CKMAX + i - 1];
+                        if (s_out + ck.out >= need) break;
+                        sg.start = ck.pos; sg.out = s_out + ck.out; sg.limit = i == nck ? 0xFFFFFFFFu : PD_CK;
+                        blocks[s_nb++] = sg;
+                    }
+                }
+            }
+            s_out += bytes;
+            s_pos = end;
+            if (fin) stop = stop ? stop : 2;
+        }
+        __syncthreads();
+        if (stop) break;
+    }
+    if (lane == 0 && stop == 2) {
+        ctl->nblocks = s_nb;
+        ctl->total = s_out;
+        ctl->adler_byte = (s_pos + 7) / 8;
+        // too few bytes is reported by k_pd_jump, after pass B had the chance to find a bad distance (zlib's order)
+        if (s_out == need && ctl->adler_byte + 4 > nbits / 8) pd_fail(ctl, LARS_PNGD_DEFLATE, 5);
+    }
+}
+
+// one wave per segment of a true block (grid-stride): literals into place, copies as source indices
+__global__ __launch_bounds__(64) void k_pd_pass_b(const unsigned int *__restrict__ words, unsigned long long nw, unsigned long long nbits,
+                                                  const PdBlock *__restrict__ blocks, unsigned long long need, uint8_t *__restrict__ lit,
+                                                  int *__restrict__ src, PdCtl *ctl)
+{
+    __shared__ PdLds L;
+    if (pd_failed(ctl)) return;
+    const unsigned int n = ctl->nblocks;
+    for (unsigned int b = blockIdx.x; b < n; b += gridDim.x) {
+        const PdBlock blk = blocks[b];
+        pd_block(L, words, nw, nbits, blk.pos, true, blk.out, need, lit, src, blk.limit, blk.start);
+        if (threadIdx.x == 0 && L.err)
+            pd_fail(ctl, L.err < 0 ? LARS_PNGD_FAR : LARS_PNGD_DEFLATE, L.err < 0 ? (int)(blk.out & 0x7FFFFFFF) : L.err);
+        __syncthreads();
+    }
+}
+
+// one round of pointer jumping (in place: a source read mid-round is older or newer, both lie on the same chain)
+__global__ __launch_bounds__(256) void k_pd_jump(int *__restrict__ src, long long n, int round, PdCtl *ctl)
+{
+    if (pd_failed(ctl) || (round > 0 && *(volatile unsigned int *)&ctl->changed[round - 1] == 0)) return;
+    if (ctl->total < (unsigned long long)n) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) pd_fail(ctl, LARS_PNGD_SHORT, (int)min(ctl->total, 0x7FFFFFFFull));
+        return;
+    }
+    bool ch = false;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int s = src[i];
+        if (s == (int)i) continue;
+        if (s < 0 || (long long)s > i) { pd_fail(ctl, LARS_PNGD_INTERNAL, 2); return; }
+        const int t = src[s];
+        if (t != s) { src[i] = t; ch = true; }
+    }
+    if (__ballot(ch) && (threadIdx.x & 63) == 0) ctl->changed[round] = 1u;
+}
+
+// bytes from their sources (a source is always a literal), into rows padded to rbp bytes and a filter byte per row;
+// Adler-32 partial sums
+__global__ __launch_bounds__(256) void k_pd_resolve(const uint8_t *__restrict__ lit, const int *__restrict__ src, long long n,
+                                                    unsigned int rb, unsigned int rbp, uint8_t *__restrict__ fpad,
+                                                    uint8_t *__restrict__ ftype, unsigned long long *__restrict__ parts, PdCtl *ctl)
+{
+    __shared__ unsigned long long r1[256], r2[256];
+    if (pd_failed(ctl)) return;
+    const long long lo = ((long long)blockIdx.x * 256 + threadIdx.x) * PD_RESOLVE_BYTES, hi = min(n, lo + PD_RESOLVE_BYTES);
+    unsigned long long s1 = 0, s2 = 0;
+    for (long long i = lo; i < hi; ++i) {
+        const int s = src[i];
+        unsigned int v;
+        if (s == (int)i) v = lit[i];
+        else if (s >= 0 && (long long)s < i) v = lit[s];
+        else { pd_fail(ctl, LARS_PNGD_INTERNAL, 3); v = 0; }
+        const unsigned int r = (unsigned int)i / (rb + 1u), col = (unsigned int)i - r * (rb + 1u);
+        if (col == 0) ftype[r] = (uint8_t)v;
+        else fpad[(unsigned long long)r * rbp + col - 1] = (uint8_t)v;
+        s1 += v;
+        s2 += (unsigned long long)(n - i) * v;
+    }
+    r1[threadIdx.x] = s1 % PD_ADLER_MOD;
+    r2[threadIdx.x] = s2 % PD_ADLER_MOD;
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {
+        if (threadIdx.x < half) { r1[threadIdx.x] += r1[threadIdx.x + half]; r2[threadIdx.x] += r2[threadIdx.x + half]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { parts[2 * blockIdx.x] = r1[0] % PD_ADLER_MOD; parts[2 * blockIdx.x + 1] = r2[0] % PD_ADLER_MOD; }
+}
+
+// one workgroup: Adler-32 = (n + sum (n - i) x_i) << 16 | (1 + sum x_i), mod 65521, against the trailer
+__global__ __launch_bounds__(256) void k_pd_adler(const unsigned long long *__restrict__ parts, long long nparts, long long n,
+                                                  const uint8_t *__restrict__ stream, PdCtl *ctl)
+{
+    __shared__ unsigned long long r1[256], r2[256];
+    if (pd_failed(ctl)) return;
+    unsigned long long s1 = 0, s2 = 0;
+    for (long long i = threadIdx.x; i < nparts; i += 256) { s1 += parts[2 * i]; s2 += parts[2 * i + 1]; }
+    r1[threadIdx.x] = s1 % PD_ADLER_MOD;
+    r2[threadIdx.x] = s2 % PD_ADLER_MOD;
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {
+        if (threadIdx.x < half) { r1[threadIdx.x] += r1[threadIdx.x + half]; r2[threadIdx.x] += r2[threadIdx.x + half]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0 && ctl->total == (unsigned long long)n) {        // more data than the image: not checked
+        const unsigned int a = (unsigned int)((1 + r1[0]) % PD_ADLER_MOD);
+        const unsigned int b = (unsigned int)(((unsigned long long)n % PD_ADLER_MOD + r2[0]) % PD_ADLER_MOD);
+        const uint8_t *t = stream + ctl->adler_byte;
+        const unsigned int want = (unsigned int)t[0] << 24 | (unsigned int)t[1] << 16 | (unsigned int)t[2] << 8 | t[3];
+        if ((b << 16 | a) != want) pd_fail(ctl, LARS_PNGD_ADLER, 0);
+    }
+}
+
+__device__ __forceinline__ unsigned int pd_recon(int f, unsigned int x, unsigned int a, unsigned int b, unsigned int c)
+{
+    switch (f) {
+    case 1: return (x + a) & 255u;
+    case 2: return (x + b) & 255u;
+    case 3: return (x + ((a + b) >> 1)) & 255u;
+    case 4: {
+        const int p = (int)a + (int)b - (int)c;
+        const int pa = abs(p - (int)a), pb = abs(p - (int)b), pc = abs(p - (int)c);
+        return (x + ((pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c))) & 255u;
+    }
+    default: return x;
+    }
+}
+
+__device__ __forceinline__ unsigned int pd_byte(const uint4 &v, int k)          // k: a compile-time constant after unrolling
+{
+    const unsigned int d = k < 4 ? v.x : k < 8 ? v.y : k < 12 ? v.z : v.w;
+    return (d >> (8 * (k & 3))) & 255u;
+}
+
+__device__ __forceinline__ uint4 pd_shfl_up(const uint4 &v)
+{
+    return make_uint4(__shfl_up(v.x, 1, 64), __shfl_up(v.y, 1, 64), __shfl_up(v.z, 1, 64), __shfl_up(v.w, 1, 64));
+}
+
+// one workgroup of PD_UNF_WAVES waves: the skewed wavefront (see the top of the file), 16 bytes per lane and step.  Rows are
+// padded to rbp (a multiple of 16) bytes in fpad and opad; lane i of a wave reconstructs chunk t - i of its row at step t.
+__global__ __launch_bounds__(64 * PD_UNF_WAVES) void k_pd_unfilter(const uint8_t *__restrict__ fpad, const uint8_t *__restrict__ ftype,
+                                                                   long long h, long long rbp, int bpp, uint8_t *__restrict__ opad,
+                                                                   PdCtl *ctl)
+{
+    __shared__ unsigned int prog[PD_UNF_WAVES];
+    __shared__ int abort_;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x / 64, nwaves = blockDim.x / 64;
+    if (threadIdx.x < PD_UNF_WAVES) prog[threadIdx.x] = 0;
+    if (threadIdx.x == 0) abort_ = 0;
+    __syncthreads();
+    if (pd_failed(ctl)) return;
+    const long long nchunk = rbp / 16, ngroups = (h + 63) / 64, tchunks = PD_TILE / 16, ncb = (nchunk + tchunks - 1) / tchunks;
+    const int sh = 8 * (bpp - 1);
+    for (long long g = wave; g < ngroups; g += nwaves) {
+        const long long row = g * 64 + lane;
+        const bool active = row < h;
+        int f = active ? ftype[row] : 0;
+        if (f > 4) { pd_fail(ctl, LARS_PNGD_FILTER, (int)min(row, 0x7FFFFFFFll)); f = 0; }
+        const uint4 *xrow = reinterpret_cast<const uint4 *>(fpad + row * rbp);
+        uint4 *orow = reinterpret_cast<uint4 *>(opad + row * rbp);
+        const uint4 *uprow = reinterpret_cast<const uint4 *>(opad + (row - 1) * rbp);
+        unsigned int ha = 0, hc = 0;
+        uint4 prev = make_uint4(0u, 0u, 0u, 0u);
+        for (long long cb = 0; cb < ncb; ++cb) {
+            if (g > 0) {
+                // the tile above: group g - 1, tile cb, finished by wave (g - 1) % nwaves
+                const unsigned int want = (unsigned int)((g - 1) * ncb + cb + 1);
+                const unsigned int *p = &prog[(g - 1) % nwaves];
+                const unsigned long long t0 = wall_clock64();
+                while (__hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < want) {
+                    if (__hip_atomic_load(&abort_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return;
+                    if (wall_clock64() - t0 > PD_WAIT_TICKS) {
+                        if (lane == 0) {
+                            pd_fail(ctl, LARS_PNGD_INTERNAL, 4);
+                            __hip_atomic_store(&abort_, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        }
+                        return;
+                    }
+                    __builtin_amdgcn_s_sleep(2);
+                }
+            }
+            const long long k0 = cb * tchunks, k1 = min(nchunk, k0 + tchunks);
+            const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+            // loads run PD_AHEAD steps ahead of their use (a ring of registers, indexed by constants after unrolling)
+            uint4 xr[PD_AHEAD], ur[PD_AHEAD];
+#pragma unroll
+            for (int q = 0; q < PD_AHEAD; ++q) {
+                const long long kq = k0 + q - lane;
+                const bool vq = active && kq >= k0 && kq < k1;
+                xr[q] = vq ? xrow[kq] : zero;
+                ur[q] = (vq && lane == 0 && row > 0) ? uprow[kq] : zero;
+            }
+            const long long steps = (k1 - k0) + 63;
+            for (long long t = 0; t < steps; t += PD_AHEAD) {
+#pragma unroll
+                for (int q = 0; q < PD_AHEAD; ++q) {
+                    const long long k = k0 + t + q - lane;
+                    const bool v = active && k >= k0 && k < k1;
+                    const uint4 x = xr[q], u0 = ur[q];
+                    const long long kf = k + PD_AHEAD;
+                    const bool vf = active && kf >= k0 && kf < k1;
+                    xr[q] = vf ? xrow[kf] : zero;
+                    ur[q] = (vf && lane == 0 && row > 0) ? uprow[kf] : zero;
+                    const uint4 fromleft = pd_shfl_up(prev);   // lane - 1's chunk k of the row above, made one step earlier
+                    const uint4 up = lane == 0 ? u0 : fromleft;
+                    if (v) {
+                        unsigned int o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                        for (int j = 0; j < 16; ++j) {
+                            const unsigned int bb = pd_byte(up, j);
+                            const unsigned int a = (ha >> sh) & 255u, c = (hc >> sh) & 255u;
+                            const unsigned int r = pd_recon(f, pd_byte(x, j), a, bb, c);
+                            ha = (ha << 8) | r;
+                            hc = (hc << 8) | bb;
+                            o[j >> 2] |= r << (8 * (j & 3));
+                        }
+                        prev = make_uint4(o[0], o[1], o[2], o[3]);
+                        orow[k] = prev;
+                    }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            if (lane == 0) __hip_atomic_store(&prog[wave], (unsigned int)(g * ncb + cb + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+}
+
+// padded rows -> [h][rb]
+__global__ __launch_bounds__(256) void k_pd_rows(const uint8_t *__restrict__ opad, long long h, long long rb, long long rbp,
+                                                 uint8_t *__restrict__ out, const PdCtl *ctl)
+{
+    if (pd_failed(ctl)) return;
+    const long long n = h * rb;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / rb;
+        out[i] = opad[r * rbp + (i - r * rb)];
+    }
+}
+
+struct PdLayout {
+    unsigned long long nbits, nw, nmark, ncap, bcap, need, nparts, rbp, nslot;
+    size_t ctl, off, words, masks, wgcnt, cands, checks, blocks, lit, src, parts, fpad, ftype, opad, bytes;
+};
+
+static bool pd_shape_ok(int64_t h, int64_t w, int channels)
+{
+    if (h < 1 || w < 1 || h > (1 << 24) || w > (1 << 24) || channels < 1 || channels > 4) return false;
+    return (unsigned long long)h * (1ull + (unsigned long long)w * channels) <= 0x7FFFFFFFull;
+}
+
+static PdLayout pd_layout(int64_t h, int64_t w, int channels, int64_t idat_bytes, int64_t idat_count)
+{
+    PdLayout L{};
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    L.need = (unsigned long long)h * (1ull + (unsigned long long)w * channels);
+    L.nbits = (unsigned long long)idat_bytes * 8;
+    L.nw = (((unsigned long long)idat_bytes + 3) / 4 + 4 + 3) & ~3ull;   // whole quads, at least 4 zero words
+    L.nmark = (L.nbits + PD_MARK_THREADS - 1) / PD_MARK_THREADS;
+    L.ncap = L.nbits / 64 + 256;
+    // segments: at most one per block that writes image bytes, plus one per checkpoint
+    L.bcap = std::min(L.nbits / 18, L.need) + 2 + L.need / PD_CK + PD_CKMAX;
+    L.nslot = std::min(L.ncap, L.nbits / 4096 + 256);   // candidates that keep checkpoints (the rest: one segment per block)
+    L.nparts = (L.need + 256ull * PD_RESOLVE_BYTES - 1) / (256ull * PD_RESOLVE_BYTES);
+    size_t o = 0;
+    L.ctl = o; o += al(sizeof(PdCtl));
+    L.off = o; o += al((size_t)idat_count * 8);
+    L.words = o; o += al(L.nw * 4);
+    L.masks = o; o += al(L.nmark * (PD_MARK_THREADS / 64) * 8);
+    L.wgcnt = o; o += al(L.nmark * 4);
+    L.cands = o; o += al(L.ncap * sizeof(PdCand));
+    L.checks = o; o += al(L.nslot * PD_CKMAX * sizeof(PdCheck));
+    L.blocks = o; o += al(L.bcap * sizeof(PdBlock));
+    L.lit = o; o += al(L.need);
+    L.src = o; o += al(L.need * 4);
+    L.parts = o; o += al(L.nparts * 16);
+    L.rbp = ((unsigned long long)w * channels + 15) & ~15ull;
+    L.fpad = o; o += al((size_t)h * L.rbp);
+    L.ftype = o; o += al((size_t)h);
+    L.opad = o; o += al((size_t)h * L.rbp);
+    L.bytes = o;
+    return L;
+}
+
+static const char *pd_deflate_what(int d)
+{
+    switch (d) {
+    case 1: return "invalid block type";
+    case 2: return "stored block length does not match its complement";
+    case 3: return "invalid code lengths";
+    case 4: return "invalid code";
+    case 5: return "stream truncated";
+    default: return "error";
+    }
+}
+
+// the message of a device status
+static int pd_status_fail(const char *who, const int st[2])
+{
+    switch (st[0]) {
+    case LARS_PNGD_CRC: return fail(LARS_ERR_INVALID, "%s: bad CRC in IDAT chunk %d", who, st[1]);
+    case LARS_PNGD_ZLIB_HEADER: return fail(LARS_ERR_INVALID, "%s: bad zlib header (CMF/FLG %#06x%s)", who, st[1],
+                                             st[1] >= 0 && (st[1] & 32) ? ", preset dictionary" : "");
+    case LARS_PNGD_DEFLATE: return fail(LARS_ERR_INVALID, "%s: deflate error: %s", who, pd_deflate_what(st[1]));
+    case LARS_PNGD_FAR: return fail(LARS_ERR_INVALID, "%s: deflate error: copy distance too far back (block at output byte %d)", who, st[1]);
+    case LARS_PNGD_SHORT: return fail(LARS_ERR_INVALID, "%s: too few decoded bytes (%d)", who, st[1]);
+    case LARS_PNGD_ADLER: return fail(LARS_ERR_INVALID, "%s: Adler-32 mismatch", who);
+    case LARS_PNGD_FILTER: return fail(LARS_ERR_INVALID, "%s: bad filter byte in row %d", who, st[1]);
+    default: return fail(LARS_ERR_HIP, "%s: internal decoder status %d (%d)", who, st[0], st[1]);
+    }
+}
+
+// host file -> the device image: parse, upload, decode; d_img is h * w * channels bytes; status read back (one sync)
+static int pd_decode_to_device(ThreadCtx *c, const char *who, const uint8_t *file, int64_t len, const int64_t info[LARS_PNG_INFO_N],
+                               const std::vector<int64_t> &table, char *ws, uint8_t **d_img_out)
+{
+    const int64_t w = info[0], h = info[1], ch = info[5], nidat = info[7], idat = info[6];
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    char *p = ws;
+    uint8_t *d_file = reinterpret_cast<uint8_t *>(p); p += al((size_t)len);
+    int64_t *d_tab = reinterpret_cast<int64_t *>(p); p += al((size_t)nidat * 16);
+    uint8_t *d_img = reinterpret_cast<uint8_t *>(p); p += al((size_t)h * w * ch);
+    int32_t *d_st = reinterpret_cast<int32_t *>(p); p += 256;
+    hipStream_t s = c->stream;
+    LARS_HIP_TRY(hipMemcpyAsync(d_file, file, (size_t)len, hipMemcpyHostToDevice, s));
+    LARS_HIP_TRY(hipMemcpyAsync(d_tab, table.data(), (size_t)nidat * 16, hipMemcpyHostToDevice, s));
+    LARS_TRY(lars_d_decode_png_u8(d_file, d_tab, nidat, idat, h, w, (int)ch, d_img, d_st, p, s));
+    int st[2] = {0, 0};
+    LARS_HIP_TRY(hipMemcpyAsync(st, d_st, sizeof st, hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipStreamSynchronize(s));
+    if (st[0]) return pd_status_fail(who, st);
+    *d_img_out = d_img;
+    return LARS_OK;
+}
+
+static size_t pd_host_ws_bytes(int64_t len, const int64_t info[LARS_PNG_INFO_N])
+{
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    return al((size_t)len) + al((size_t)info[7] * 16) + al((size_t)info[1] * info[0] * info[5]) + 256 +
+           lars_png_decode_scratch_bytes(info[1], info[0], (int)info[5], info[6], info[7]);
+}
+
+// parse + checks shared by the host entry points
+static int pd_parse(const char *who, const uint8_t *file, int64_t len, int64_t info[LARS_PNG_INFO_N], std::vector<int64_t> &table)
+{
+    if (!file || len <= 0) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    LARS_TRY(lars_png_info(file, len, info, nullptr, 0));
+    if (!info[9])
+        return fail(LARS_ERR_UNSUPPORTED, "%s: %s PNG (bit depth %lld, interlace %lld) is not supported", who,
+                    info[8] ? "APNG" : info[4] ? "interlaced" : "this", (long long)info[2], (long long)info[4]);
+    if (!pd_shape_ok(info[1], info[0], (int)info[5]))
+        return fail(LARS_ERR_INVALID, "%s: %lld x %lld x %lld picture is too large", who, (long long)info[1], (long long)info[0],
+                    (long long)info[5]);
+    table.assign((size_t)info[7] * 2, 0);
+    return lars_png_info(file, len, info, table.data(), info[7]);
+}
+
+}  // namespace lars
+
+using namespace lars;
+
+extern "C" {
+
+size_t lars_png_decode_scratch_bytes(int64_t h, int64_t w, int channels, int64_t idat_bytes, int64_t idat_count)
+{
+    if (!pd_shape_ok(h, w, channels) || idat_bytes < 0 || idat_count < 1 || idat_bytes > (1ll << 40)) return 0;
+    return pd_layout(h, w, channels, idat_bytes, idat_count).bytes;
+}
+
+int lars_d_decode_png_u8(const uint8_t *file, const int64_t *idat_table, int64_t idat_count, int64_t idat_bytes, int64_t h, int64_t w,
+                         int channels, uint8_t *out, int32_t *status_dev, void *scratch, void *stream)
+{
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!file || !idat_table || !out || !status_dev || !scratch || idat_count < 1 || idat_bytes < 0 || idat_bytes > (1ll << 40))
+        return fail(LARS_ERR_INVALID, "lars_d_decode_png_u8: bad arguments");
+    if (!pd_shape_ok(h, w, channels))
+        return fail(LARS_ERR_INVALID, "lars_d_decode_png_u8: %lld x %lld x %d picture", (long long)h, (long long)w, channels);
+    const PdLayout L = pd_layout(h, w, channels, idat_bytes, idat_count);
+    if (L.nmark >= (1ull << 31) || L.ncap >= (1ull << 32) || L.bcap >= (1ull << 32))
+        return fail(LARS_ERR_UNSUPPORTED, "lars_d_decode_png_u8: %lld IDAT bytes", (long long)idat_bytes);
+    char *sc = static_cast<char *>(scratch);
+    PdCtl *ctl = reinterpret_cast<PdCtl *>(sc + L.ctl);
+    unsigned long long *off = reinterpret_cast<unsigned long long *>(sc + L.off);
+    unsigned int *words = reinterpret_cast<unsigned int *>(sc + L.words);
+    unsigned long long *masks = reinterpret_cast<unsigned long long *>(sc + L.masks);
+    unsigned int *wgcnt = reinterpret_cast<unsigned int *>(sc + L.wgcnt);
+    PdCand *cands = reinterpret_cast<PdCand *>(sc + L.cands);
+    PdCheck *checks = reinterpret_cast<PdCheck *>(sc + L.checks);
+    PdBlock *blocks = reinterpret_cast<PdBlock *>(sc + L.blocks);
+    uint8_t *lit = reinterpret_cast<uint8_t *>(sc + L.lit);
+    int *src = reinterpret_cast<int *>(sc + L.src);
+    unsigned long long *parts = reinterpret_cast<unsigned long long *>(sc + L.parts);
+    hipStream_t s = pick_stream(c, stream);
+    const long long *tab = reinterpret_cast<const long long *>(idat_table);
+    LARS_HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(PdCtl), s));
+    LARS_HIP_TRY(hipMemsetAsync(reinterpret_cast<char *>(words) + idat_bytes, 0, L.nw * 4 - (size_t)idat_bytes, s));   // zero tail
+    hipLaunchKernelGGL(k_pd_chunk_scan, dim3(1), dim3(1024), 0, s, tab, (long long)idat_count, off);
+    hipLaunchKernelGGL(k_pd_gather, dim3((unsigned)std::min<int64_t>(idat_count, 4096)), dim3(PD_GATHER_THREADS), 0, s, file, tab,
+                       (long long)idat_count, off, reinterpret_cast<uint8_t *>(words), ctl);
+    if (L.nmark) {
+        hipLaunchKernelGGL(k_pd_mark, dim3((unsigned)L.nmark), dim3(PD_MARK_THREADS), 0, s, words, L.nw, L.nbits, masks, wgcnt, ctl);
+        hipLaunchKernelGGL(k_pd_scan_u32, dim3(1), dim3(1024), 0, s, wgcnt, (long long)L.nmark, (unsigned int)L.ncap, ctl);
+        hipLaunchKernelGGL(k_pd_compact, dim3((unsigned)L.nmark), dim3(PD_MARK_THREADS), 0, s, masks, wgcnt, (unsigned int)L.ncap, cands);
+        hipLaunchKernelGGL(k_pd_pass_a, dim3(4096), dim3(64), 0, s, words, L.nw, L.nbits, cands, checks, (unsigned int)L.nslot, ctl);
+    }
+    hipLaunchKernelGGL(k_pd_walk, dim3(1), dim3(64), 0, s, words, L.nw, L.nbits, cands, checks, (unsigned int)L.nslot, blocks,
+                       (unsigned int)L.bcap, L.need, ctl);
+    hipLaunchKernelGGL(k_pd_pass_b, dim3(4096), dim3(64), 0, s, words, L.nw, L.nbits, blocks, L.need, lit, src, ctl);
+    int rounds = 1;
+    while ((1ull << (rounds - 1)) < L.need && rounds < 64) ++rounds;
+    const unsigned jgrid = (unsigned)std::min<unsigned long long>((L.need + 255) / 256, 16384);
+    for (int r = 0; r < rounds; ++r) hipLaunchKernelGGL(k_pd_jump, dim3(jgrid), dim3(256), 0, s, src, (long long)L.need, r, ctl);
+    uint8_t *fpad = reinterpret_cast<uint8_t *>(sc + L.fpad), *ftype = reinterpret_cast<uint8_t *>(sc + L.ftype),
+            *opad = reinterpret_cast<uint8_t *>(sc + L.opad);
+    const long long rb = (long long)w * channels;
+    if ((unsigned long long)rb != L.rbp) LARS_HIP_TRY(hipMemsetAsync(fpad, 0, (size_t)h * L.rbp, s));   // zero padding columns
+    hipLaunchKernelGGL(k_pd_resolve, dim3((unsigned)L.nparts), dim3(256), 0, s, lit, src, (long long)L.need, (unsigned int)rb,
+                       (unsigned int)L.rbp, fpad, ftype, parts, ctl);
+    hipLaunchKernelGGL(k_pd_adler, dim3(1), dim3(256), 0, s, parts, (long long)L.nparts, (long long)L.need,
+                       reinterpret_cast<const uint8_t *>(words), ctl);
+    const long long ngroups = (h + 63) / 64;
+    const int nwaves = (int)std::min<long long>(ngroups, PD_UNF_WAVES);
+    hipLaunchKernelGGL(k_pd_unfilter, dim3(1), dim3(64 * nwaves), 0, s, fpad, ftype, (long long)h, (long long)L.rbp, channels, opad, ctl);
+    const unsigned rgrid = (unsigned)std::min<long long>((h * rb + 255) / 256, 8192);
+    hipLaunchKernelGGL(k_pd_rows, dim3(rgrid), dim3(256), 0, s, opad, (long long)h, rb, (long long)L.rbp, out, ctl);
+    LARS_HIP_TRY(hipMemcpyAsync(status_dev, ctl->status, 8, hipMemcpyDeviceToDevice, s));
+    return launch_check("lars_d_decode_png_u8");
+}
+
+// host file in, host pixels out: one upload, the status, one download
+int lars_h_decode_png_u8(const uint8_t *file, int64_t len, uint8_t *out, size_t out_cap)
+{
+    static const char *who = "lars_h_decode_png_u8";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!out) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    int64_t info[LARS_PNG_INFO_N];
+    std::vector<int64_t> table;
+    LARS_TRY(pd_parse(who, file, len, info, table));
+    const size_t bytes = (size_t)info[1] * info[0] * info[5];
+    if (out_cap < bytes) return fail(LARS_ERR_INVALID, "%s: out_cap %zu < %zu", who, out_cap, bytes);
+    LARS_TRY(ws_reserve(c, pd_host_ws_bytes(len, info)));
+    uint8_t *d_img = nullptr;
+    LARS_TRY(pd_decode_to_device(c, who, file, len, info, table, static_cast<char *>(c->ws), &d_img));
+    LARS_HIP_TRY(hipMemcpyAsync(out, d_img, bytes, hipMemcpyDeviceToHost, c->stream));
+    LARS_HIP_TRY(hipStreamSynchronize(c->stream));
+    return LARS_OK;
+}
+
+// host file in, thumbnail out: the decoded pixels go straight into the thumbnail kernels (resize.hip)
+int lars_h_thumbnail_png_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
+                            int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out)
+{
+    static const char *who = "lars_h_thumbnail_png_u8";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!out || !reduce_box || !box) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    int64_t info[LARS_PNG_INFO_N];
+    std::vector<int64_t> table;
+    LARS_TRY(pd_parse(who, file, len, info, table));
+    if (info[3] != 0 && info[3] != 2 && info[3] != 6)
+        return fail(LARS_ERR_UNSUPPORTED, "%s: modes L, RGB and RGBA (colour type %lld)", who, (long long)info[3]);
+    const int64_t h = info[1], w = info[0];
+    const int ch = (int)info[5];
+    size_t tneed = 0;
+    LARS_TRY(thumbnail_u8_impl(c, nullptr, true, nullptr, &tneed, h, w, ch, fx, fy, reduce_box, box, new_h, new_w, vertical_first, out));
+    const size_t front = (pd_host_ws_bytes(len, info) + 255) & ~(size_t)255;
+    LARS_TRY(ws_reserve(c, front + tneed));
+    uint8_t *d_img = nullptr;
+    LARS_TRY(pd_decode_to_device(c, who, file, len, info, table, static_cast<char *>(c->ws), &d_img));
+    return thumbnail_u8_impl(c, d_img, true, static_cast<char *>(c->ws) + front, nullptr, h, w, ch, fx, fy, reduce_box, box, new_h,
+                             new_w, vertical_first, out);
+}
+
+}  // extern "C"

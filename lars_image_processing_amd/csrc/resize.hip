@@ -249,12 +249,14 @@ using namespace lars;
 // Image.thumbnail(size, LANCZOS, reducing_gap) of a host uint8 image [h][w][channels] -- process-images.py:186-189, the
 // gallery thumbnails -- on the numbers of api.thumbnail_plan: premultiply (channels 4), Image.reduce((fx, fy)) over
 // reduce_box, the LANCZOS passes over the float box of the reduced image, un-premultiply.  One upload, one download.
-extern "C" int lars_h_thumbnail_u8(const uint8_t *img, int64_t h, int64_t w, int channels, int fx, int fy, const int reduce_box[4],
-                                   const float box[4], int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out)
+// The body of lars_h_thumbnail_u8.  img is a host image (uploaded to the start of ws) or, with on_device, a device image
+// read in place (lars_h_thumbnail_png_u8: the decoded PNG).  With need_out set it only checks the arguments and gives the
+// workspace bytes ws must hold; otherwise ws (at least that many bytes of device memory) is used and out filled.
+int lars::thumbnail_u8_impl(ThreadCtx *c, const uint8_t *img, bool on_device, char *ws, size_t *need_out, int64_t h, int64_t w,
+                            int channels, int fx, int fy, const int reduce_box[4], const float box[4], int64_t new_h, int64_t new_w,
+                            int vertical_first, uint8_t *out)
 {
-    ThreadCtx *c;
-    LARS_TRY(ensure_ctx(&c));
-    if (!img || !out || !reduce_box || !box || h <= 0 || w <= 0 || new_h <= 0 || new_w <= 0 || h > (1 << 24) || w > (1 << 24) ||
+    if ((!img && !need_out) || !out || !reduce_box || !box || h <= 0 || w <= 0 || new_h <= 0 || new_w <= 0 || h > (1 << 24) || w > (1 << 24) ||
         new_h > (1 << 24) || new_w > (1 << 24) || fx < 1 || fy < 1 || (long long)fx * fy >= (1 << 24))
         return fail(LARS_ERR_INVALID, "lars_h_thumbnail_u8: bad arguments");
     if (channels != 1 && channels != 3 && channels != 4)
@@ -278,11 +280,16 @@ extern "C" int lars_h_thumbnail_u8(const uint8_t *img, int64_t h, int64_t w, int
     const size_t in_bytes = (size_t)h * w * channels, red_bytes = reduce ? (size_t)rh * rw * channels : 0,
                  tmp_bytes = std::max((size_t)rh * new_w, (size_t)new_h * rw) * channels, out_bytes = (size_t)new_h * new_w * channels;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t need = al(in_bytes) * (channels == 4 ? 2 : 1) + al(red_bytes) + al(tmp_bytes) + al(out_bytes) + al(bh.size() * 4) +
+    // a device image is read in place: no upload copy
+    const size_t need = (on_device ? 0 : al(in_bytes)) + (channels == 4 ? al(in_bytes) : 0) + al(red_bytes) + al(tmp_bytes) + al(out_bytes) + al(bh.size() * 4) +
                         al(kh.size() * 4) + al(bv.size() * 4) + al(kv.size() * 4) + 1024;
-    LARS_TRY(ws_reserve(c, need));
-    char *p = static_cast<char *>(c->ws);
-    uint8_t *d_in = reinterpret_cast<uint8_t *>(p); p += al(in_bytes);
+    if (need_out) {
+        *need_out = need;
+        return LARS_OK;
+    }
+    char *p = ws;
+    uint8_t *d_in = on_device ? const_cast<uint8_t *>(img) : reinterpret_cast<uint8_t *>(p);
+    if (!on_device) p += al(in_bytes);
     uint8_t *d_pre = nullptr;
     if (channels == 4) { d_pre = reinterpret_cast<uint8_t *>(p); p += al(in_bytes); }
     uint8_t *d_red = reinterpret_cast<uint8_t *>(p); p += al(red_bytes);
@@ -293,7 +300,7 @@ extern "C" int lars_h_thumbnail_u8(const uint8_t *img, int64_t h, int64_t w, int
     int *d_bv = reinterpret_cast<int *>(p); p += al(bv.size() * 4);
     int *d_kv = reinterpret_cast<int *>(p);
     hipStream_t s = c->stream;
-    LARS_HIP_TRY(hipMemcpyAsync(d_in, img, in_bytes, hipMemcpyHostToDevice, s));
+    if (!on_device) LARS_HIP_TRY(hipMemcpyAsync(d_in, img, in_bytes, hipMemcpyHostToDevice, s));
     if (need_h) {
         LARS_HIP_TRY(hipMemcpyAsync(d_bh, bh.data(), bh.size() * 4, hipMemcpyHostToDevice, s));
         LARS_HIP_TRY(hipMemcpyAsync(d_kh, kh.data(), kh.size() * 4, hipMemcpyHostToDevice, s));
@@ -332,6 +339,19 @@ extern "C" int lars_h_thumbnail_u8(const uint8_t *img, int64_t h, int64_t w, int
     LARS_HIP_TRY(hipMemcpyAsync(out, cur, out_bytes, hipMemcpyDeviceToHost, s));
     LARS_HIP_TRY(hipStreamSynchronize(s));
     return LARS_OK;
+}
+
+extern "C" int lars_h_thumbnail_u8(const uint8_t *img, int64_t h, int64_t w, int channels, int fx, int fy, const int reduce_box[4],
+                                   const float box[4], int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out)
+{
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!img) return fail(LARS_ERR_INVALID, "lars_h_thumbnail_u8: bad arguments");
+    size_t need = 0;
+    LARS_TRY(thumbnail_u8_impl(c, img, false, nullptr, &need, h, w, channels, fx, fy, reduce_box, box, new_h, new_w, vertical_first, out));
+    LARS_TRY(ws_reserve(c, need));
+    return thumbnail_u8_impl(c, img, false, static_cast<char *>(c->ws), nullptr, h, w, channels, fx, fy, reduce_box, box, new_h, new_w,
+                             vertical_first, out);
 }
 
 // PIL.Image.resize((new_w, new_h), LANCZOS) of a host uint8 image [h][w][channels], channels 1, 3 or 4

@@ -309,16 +309,27 @@ def write_tiff(path, array, rows_per_strip=None, tile=None, byteorder="<", plana
     return overflow_at + len(overflow)
 
 
-def read_image(path, full_depth=False):
+def read_image(path, full_depth=False, png_decoder="pillow"):
     """Any raster the pipeline takes -> ``ndarray``.
 
     ``full_depth=False``: ``np.array(PIL.Image.open(path))``, what the reference does (backend-process.py:52) --
     Pillow opens a three-sample 16-bit TIFF as 8-bit RGB (the high bytes), so the reference never sees the low bytes.
     ``full_depth=True``: such files come back as the ``[H, W, C]`` uint16 array they hold (this module's reader);
     every other file still goes through Pillow.
+    ``png_decoder="device"``: a ``.png`` file with the PNG signature whose IHDR ``api.png_info`` calls supported is decoded
+    on the GPU (``api.decode_png``, the same array as Pillow's); decided up front, not a fallback: its errors are raised.
     """
     from PIL import Image
+    if png_decoder not in ("pillow", "device"):
+        raise ValueError(f"png_decoder must be 'pillow' or 'device', got {png_decoder!r}")
     p = str(path)
+    if png_decoder == "device" and p.lower().endswith(".png"):
+        from . import api
+        with open(p, "rb") as f:
+            data = f.read()
+        # a file without the PNG signature (a JPEG under a .png name, say) is not the decoder's: Pillow opens it by content
+        if data[:8] == b"\x89PNG\r\n\x1a\n" and api.png_info(data)["supported"]:
+            return api.decode_png(data)
     if full_depth and p.lower().endswith((".tif", ".tiff")):
         try:
             arr = read_tiff(p)
