@@ -13,24 +13,15 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import time
 
 import numpy as np
 
 from . import _ffi
+from . import arena as _arena
 from ._ffi import FusedArgs, INDEX_IDS, INDEX_NAMES, STATS_DTYPE, DeviceBuffer, DeviceSlice
+from .arena import arena_placements  # noqa: F401  (its callers know it as batch.arena_placements)
 
 MAX_TILES_PER_LAUNCH = 65535      # grid.y limit
-ARENA_MIN_BYTES = 2 << 30         # smaller arenas run alike wherever they land
-ARENA_SPREAD_PLANE_BYTES = 2 << 30  # planes from this size on are worth a placement search (and its spare room)
-ARENA_TRIALS = 4                  # allocations of the default search at most (each is tried with every placement of its planes)
-ARENA_CLASS_GAP = 0.93            # the search ends once its best candidate is 7 % under its worst: both classes seen (they are ~18 % apart)
-ARENA_WARM_MS = 30.0              # untimed launches before a candidate is timed: after an idle gap a fast arena needs ~22 ms to reach its level
-ARENA_SPAN_BYTES = 20 << 30       # how far from the first planes the last ones may be placed inside an allocation (the memory changes kind every 6-16 GiB)
-ARENA_SPAN_STEP = 4 << 30         # ... in steps of
-ARENA_CROSS_TRIALS = 6            # pairs of allocations tried with the planes split between them when every allocation is of one kind
-ARENA_EXTRA_BLOCKS = 24           # ... and after those, small allocations for the second half of the planes alone: stretches of one kind
-                                  # reach 72 GiB in some processes (tools/lab/kindmap.py), and the allocations held so far have used most of one
 
 
 # How statistics-only passes over uint8 RGNir batches run (no output planes):
@@ -103,24 +94,6 @@ def channels_of(indices, whole_image=False):
     for t in indices:
         need |= {2, 0} if t == "NDVI" else {2, 1}
     return need
-
-
-def arena_placements(nplanes, plane_bytes, nbytes):
-    """Byte offsets of ``nplanes`` planes of ``plane_bytes`` inside an allocation of ``nbytes`` that ``TileBatch.make_outputs`` tries:
-    packed back to back, then the first ceil(n / 2) planes packed at the start and the rest packed from 8, 12, 16, 20 GiB on
-    (every multiple of ARENA_SPAN_STEP beyond the first cluster up to ARENA_SPAN_BYTES that still fits).  Device memory changes kind
-    every 6-16 GiB along an allocation and a launch is fast when its planes are split between the kinds (make_outputs)."""
-    n_first = (nplanes + 1) // 2
-    first_bytes, second_bytes = n_first * plane_bytes, (nplanes - n_first) * plane_bytes
-    packed = tuple(j * plane_bytes for j in range(nplanes))
-    out = [packed]
-    if nplanes < 2:
-        return out
-    start = ((first_bytes + ARENA_SPAN_STEP - 1) // ARENA_SPAN_STEP) * ARENA_SPAN_STEP
-    for s0 in range(start, ARENA_SPAN_BYTES + 1, ARENA_SPAN_STEP):
-        if s0 > first_bytes and s0 + second_bytes <= nbytes:
-            out.append(packed[:n_first] + tuple(s0 + j * plane_bytes for j in range(nplanes - n_first)))
-    return out
 
 
 def shard_range(ntiles, rank, world):
@@ -239,167 +212,46 @@ class TileBatch:
         """Allocate output planes.  ``ring`` < ntiles reuses a ring of that many
         tile slots (same HBM traffic, bounded footprint) -- see BatchOutputs.
 
-        The float32 index planes (and RGBA8 planes) live in ONE allocation (an arena).  How fast the write-bound fused
-        kernel runs into a multi-GiB arena depends on WHERE its planes lie: device memory comes in two kinds that alternate
-        along an allocation in stretches of 6-16 GiB, and a launch whose write streams are split between the kinds runs 18 %
-        faster than one whose planes all lie in one kind (2.49-2.52 against 3.01-3.15 ms per 64-tile launch of the headline
-        kernel; profiles/r04_arena_two_kinds.txt).  Three 4 GiB planes packed into 12 GiB see a change of kind in three
-        allocations of ten; with room to spare inside the allocation a placement that does can be found in three of four.
+        The float32 index planes (and RGBA8 planes) live in ONE allocation (an arena).  Where in device memory the planes of a
+        multi-GiB arena lie decides how fast the plane-writing kernel runs (two classes 18 % apart): why, and the search that
+        finds a fast placement, are lars_image_processing_amd/arena.py's.
         ``arena``:
-          "auto"      multi-GiB arenas: ONE allocation with up to ARENA_SPAN_BYTES of room beyond the first planes (24 GiB for
-                      three planes of 4 GiB, less if the device is short of memory), and the planes are tried in a handful of
-                      placements inside it -- packed, and with the second half of the planes further out in steps of 4 GiB up
-                      to 20 GiB from the start -- each timed with the batch's own launches (``_probe_arena``).  If no placement is 7 % faster than another the
-                      allocation is of one kind throughout: another one is taken (up to ``placement_trials``, default
-                      ARENA_TRIALS), and the search ends as soon as both classes have been seen.  If every allocation was of one
-                      kind (two fresh processes in ten on some boxes), the first half of the planes stays in one allocation and
-                      the rest goes to another (allocations differ in kind among each other): up to ARENA_CROSS_TRIALS pairs;
-                      such outputs keep BOTH allocations.  The fastest (allocation, placement) is kept, other allocations are freed.  Smaller arenas (they run alike wherever they land)
-                      are one packed allocation
+          "auto"      arenas of 2 GiB and more with two or more planes of 2 GiB and more each: one allocation with room to spare
+                      (24 GiB for three planes of 4 GiB, less if the device is short of memory), the planes timed in a handful of
+                      placements inside it with the batch's own launches (``_probe_arena``); further allocations (up to
+                      ``placement_trials``, default ARENA_TRIALS), then the planes split between two allocations, until both
+                      speed classes have been seen.  The fastest (allocation, placement) is kept -- WITH its spare room, or
+                      both allocations of a split -- and the other allocations are freed.  While it runs the search holds at
+                      worst 4 allocations of 24 GiB and 24 of 4 GiB (192 GiB) for 12 GiB of planes.  Smaller arenas (they run
+                      alike wherever they land) are one packed allocation
           "plain"     one packed allocation as it comes, unless ``placement_trials`` asks for a search among packed ones
         ``pick="slowest"`` keeps the slowest candidate instead (a diagnostic: what a process without a fast arena sees).
         ``outs.arena_report`` = {kind, search_ms, chosen_ms, post_free_ms, rejected, candidate_ms, placements, ...}."""
         outs = BatchOutputs(self, indices, index, wb, rgba, ring, allocate=False)
         nplanes = len(outs._index_ids) + len(outs._rgba_ids)
-        report = {"kind": "none"} if not nplanes else None
-        if nplanes and arena not in ("auto", "plain"):
-            raise ValueError("arena must be auto or plain")
-        if pick not in ("fastest", "slowest"):
-            raise ValueError("pick must be fastest or slowest")
-        packed_bytes = nplanes * outs.plane_bytes
-        big = bool(nplanes) and nplanes * outs.slots * self.npix * 4 >= ARENA_MIN_BYTES
-        # Room inside the allocation and several placements: only where it can pay -- two or more planes of ARENA_SPREAD_PLANE_BYTES
-        # (2 GiB) or more each (planes of 1 GiB show no difference between placements: profiles/r04_arena_two_kinds.txt) -- and only
-        # if the caller did not ask for one trial at most.  Such an arena KEEPS its spare room while the outputs live:
-        # report["arena_bytes"] against the packed size (24 instead of 12 GiB for three planes of 4 GiB).
-        spread = (arena == "auto" and big and nplanes >= 2 and outs.plane_bytes >= ARENA_SPREAD_PLANE_BYTES
-                  and (placement_trials is None or int(placement_trials) > 1))
-        if placement_trials is None:
-            # one plane: nothing to split -- sixteen 4 GiB single-plane arenas measured within 1 % of each other (profiles/r04_ndvi_plane_step_ways.txt)
-            placement_trials = ARENA_TRIALS if spread else 0
-        if not nplanes or (placement_trials <= 1 and not spread):
-            if nplanes:
-                outs.adopt_arena(DeviceBuffer(packed_bytes))
-                report = {"kind": "plain hipMalloc", "search_ms": 0.0, "chosen_ms": None, "post_free_ms": None, "rejected": 0}
-            outs.arena_report = report
+        plan = _arena.plan_arena(nplanes, outs.plane_bytes, outs.slots * self.npix * 4, arena, placement_trials, pick)
+        if plan.kind != "search":
+            if plan.kind == "packed":
+                outs.adopt_arena(DeviceBuffer(nplanes * outs.plane_bytes))
+            outs.arena_report = _arena.unsearched_report(plan)
             return outs
-        t_search = time.perf_counter()
-        free_b, total_b = C.c_size_t(), C.c_size_t()
-        # Two clusters: ceil(n / 2) planes at the start, the rest further out.  The other split of an odd number ((0, 16, 20) for three planes)
-        # was measured too: 1 % slower than (0, 4, 16) although it balances the launch's four streams, the read included, more often -- and
-        # the 28 GiB it needs came from one kind of memory throughout in three of six fresh processes, where the first 24 GiB of a fresh
-        # process showed both classes in eleven of thirteen (profiles/r04_arena_fresh_processes.txt).
-        n_first = (nplanes + 1) // 2                                       # planes of the first cluster; the rest form the second
-        second_bytes = (nplanes - n_first) * outs.plane_bytes
 
-        def placements_for(nbytes):
-            return arena_placements(nplanes, outs.plane_bytes, nbytes)
+        def free_bytes():
+            free_b, total_b = C.c_size_t(), C.c_size_t()
+            _ffi.call("lars_mem_info", C.byref(free_b), C.byref(total_b))
+            return free_b.value
 
         stats = self.new_stats()
-        cands = []                                                         # (ms, allocation index, offsets)
-        arenas, malloc_ms = [], []
-        stopped = "placement_trials"
         try:
-            while len(arenas) < max(1, int(placement_trials)):
-                _ffi.call("lars_mem_info", C.byref(free_b), C.byref(total_b))
-                want = packed_bytes
-                if spread:
-                    want = max(packed_bytes, min(ARENA_SPAN_BYTES + second_bytes, free_b.value - (16 << 30)))
-                if free_b.value < want + (8 << 30):                        # keep 8 GiB of headroom for the caller
-                    if arenas:
-                        stopped = "device memory"
-                        break
-                    want = packed_bytes                                    # the first arena must exist whatever the headroom
-                t0 = time.perf_counter()
-                try:
-                    buf = DeviceBuffer(want)
-                except _ffi.LarsError:
-                    if not arenas:
-                        raise
-                    stopped = "device memory"
-                    break
-                malloc_ms.append((time.perf_counter() - t0) * 1e3)
-                arenas.append(buf)
-                for k, offsets in enumerate(placements_for(want)):
-                    outs.adopt_arena(buf, offsets)
-                    cands.append((self._probe_arena(outs, indices, stats, warm_ms=ARENA_WARM_MS if k == 0 else 5.0), len(arenas) - 1, offsets))
-                times = [c[0] for c in cands]
-                if len(cands) >= 2 and min(times) <= ARENA_CLASS_GAP * max(times):
-                    stopped = "both classes seen"
-                    break
-            # Every allocation of ONE kind throughout (no placement 7 % under another; seen for all four 24 GiB allocations of some
-            # processes: profiles/r05_arena_first_process.txt): allocations differ in kind among each other -- their slow levels do,
-            # 3.01 against 3.09 ms -- so the first cluster of planes stays in one and the rest goes to another, tried from the pair
-            # whose levels lie furthest apart.  Both allocations are then kept.
-            times = [c[0] for c in cands]
-            if (spread and pick == "fastest" and stopped != "both classes seen" and len(arenas) >= 2
-                    and min(times) > ARENA_CLASS_GAP * max(times)):
-                level = [float(np.mean([t for t, a, _ in cands if a == j])) for j in range(len(arenas))]
-                pairs = sorted(((abs(level[i] - level[j]), i, j) for i in range(len(arenas)) for j in range(len(arenas)) if i != j), reverse=True)
-                first = tuple(j * outs.plane_bytes for j in range(n_first))
-                second = tuple(j * outs.plane_bytes for j in range(nplanes - n_first))
-                for _, i, j in pairs[:ARENA_CROSS_TRIALS]:
-                    outs.adopt_two_arenas(arenas[i], first, arenas[j], second)
-                    cands.append((self._probe_arena(outs, indices, stats, warm_ms=5.0), (i, j), first + second))
-                    if cands[-1][0] <= ARENA_CLASS_GAP * max(times):
-                        stopped = "both classes seen: planes split between two allocations"
-                        break
-                # ... and if all of them are of the SAME kind: small allocations for the second cluster alone (while the large ones are
-                # held they come from other memory), next to the first cluster in the first allocation
-                while stopped == "placement_trials" and len(arenas) < int(placement_trials) + ARENA_EXTRA_BLOCKS:
-                    _ffi.call("lars_mem_info", C.byref(free_b), C.byref(total_b))
-                    if free_b.value < second_bytes + (8 << 30):
-                        break
-                    t0 = time.perf_counter()
-                    try:
-                        arenas.append(DeviceBuffer(second_bytes))
-                    except _ffi.LarsError:
-                        break
-                    malloc_ms.append((time.perf_counter() - t0) * 1e3)
-                    outs.adopt_two_arenas(arenas[0], first, arenas[-1], second)
-                    cands.append((self._probe_arena(outs, indices, stats, warm_ms=5.0), (0, len(arenas) - 1), first + second))
-                    if cands[-1][0] <= ARENA_CLASS_GAP * max(times):
-                        stopped = "both classes seen: second half of the planes in an allocation of its own"
-        except BaseException:
-            # a failed probe launch or allocation: nothing of the search may stay behind, and `outs` must not point into a freed arena
-            _ffi.call("lars_synchronize", None)
-            outs.arena = outs.arena2 = None
-            for buf in arenas:
-                buf.free()
+            found = _arena.search(outs, plan, pick, alloc=DeviceBuffer, free_bytes=free_bytes,
+                                  probe=lambda placement, warm_ms: self._probe_arena(outs, indices, stats, warm_ms),
+                                  synchronize=lambda: _ffi.call("lars_synchronize", None))
+        finally:
             stats.free()
-            raise
-        times = [c[0] for c in cands]
-        best = int(np.argmin(times) if pick == "fastest" else np.argmax(times))
-        chosen_ms, chosen_alloc, chosen_offsets = cands[best]
-        keep = set(chosen_alloc) if isinstance(chosen_alloc, tuple) else {chosen_alloc}
-        if isinstance(chosen_alloc, tuple):
-            outs.adopt_two_arenas(arenas[chosen_alloc[0]], chosen_offsets[:n_first], arenas[chosen_alloc[1]], chosen_offsets[n_first:])
-        else:
-            outs.adopt_arena(arenas[chosen_alloc], chosen_offsets)
-        for j, buf in enumerate(arenas):
-            if j not in keep:
-                buf.free()
-        _ffi.call("lars_synchronize", None)
-        # the survivor once more, now that the rejected allocations are gone: the figure the steps should reproduce
-        post_free = self._probe_arena(outs, indices, stats) if len(arenas) > 1 else float(chosen_ms)
-        stats.free()
-        gib = float(1 << 30)
-        kept_bytes = sum(arenas[j].nbytes for j in keep)
-        outs.placement_ms = {"arenas": [float(x) for x in times], "chosen": float(chosen_ms)}
-        outs.arena_report = {
-            "kind": f"plain hipMalloc of {kept_bytes / gib:.1f} GiB{' in two allocations' if len(keep) > 1 else ''}, the {pick} of {len(cands)} "
-                    f"placements of the planes in {len(arenas)} allocation(s), timed with the batch's own launches (search ended by: {stopped})",
-            "search_ms": (time.perf_counter() - t_search) * 1e3, "chosen_ms": float(chosen_ms), "post_free_ms": float(post_free),
-            "rejected": len(arenas) - len(keep), "candidate_ms": [float(x) for x in times], "malloc_ms": [float(x) for x in malloc_ms],
-            "placements": [{"allocation": list(a) if isinstance(a, tuple) else int(a), "offsets_gib": [round(o / gib, 3) for o in offs], "ms": float(t)}
-                           for t, a, offs in cands],
-            "chosen_offsets_gib": [round(o / gib, 3) for o in chosen_offsets],
-            "arena_bytes": int(kept_bytes), "packed_bytes": int(packed_bytes), "allocations": len(arenas),
-            "transient_bytes": int(sum(b.nbytes for b in arenas)),
-            "probe": f">= {ARENA_WARM_MS:.0f} ms of untimed launches per allocation, then per placement one timed pass of launches over the batch's chunks"}
+        outs.placement_ms, outs.arena_report = _arena.report(found)
         return outs
 
-    def _probe_arena(self, outs, indices, stats, warm_ms=ARENA_WARM_MS):
+    def _probe_arena(self, outs, indices, stats, warm_ms=_arena.ARENA_WARM_MS):
         """Milliseconds per fused launch into ``outs`` at the level a step sees: the step's own launch sequence (one launch
         per ring of tile slots over the batch, LARS_F_RAW records; sixteen evenly spaced chunks of a longer sequence).
 
@@ -867,42 +719,41 @@ class BatchOutputs:
                 self.luts[k].upload(colormap_lut(_colormap_for(t)))
         self.wb = DeviceBuffer(self.slots * batch.npix * batch.channels) if wb else None
 
-    def adopt_arena(self, arena, offsets=None):
-        """Point the planes at ``arena`` (the caller frees whatever arena was in use before).  ``offsets``: byte offset of every
-        plane inside the arena (index planes in the order of INDEX_NAMES, then the RGBA planes; multiples of 256), packed
-        back to back when None."""
-        nplanes = len(self._index_ids) + len(self._rgba_ids)
-        if offsets is None:
-            offsets = tuple(j * self.plane_bytes for j in range(nplanes))
-        offsets = tuple(int(o) for o in offsets)
-        assert len(offsets) == nplanes and all(o % 256 == 0 and o + self.plane_bytes <= arena.nbytes for o in offsets)
-        order = sorted(offsets)
-        assert all(b - a >= self.plane_bytes for a, b in zip(order, order[1:])), "planes overlap"
-        self.arena = arena
-        self.arena2 = None
-        self.plane_offsets = offsets
+    def adopt(self, buffers, placement):
+        """Point the planes at ``placement`` (the caller frees whatever was in use before): per plane -- index planes in the order
+        of INDEX_NAMES, then the RGBA planes -- ``(i, offset)``, the plane ``offset`` bytes (a multiple of 256) into ``buffers[i]``.
+        At most two buffers hold planes: ``arena`` (the first plane's) and ``arena2`` (None unless the planes are split)."""
+        placement = tuple((int(i), int(o)) for i, o in placement)
+        assert len(placement) == len(self._index_ids) + len(self._rgba_ids)
+        used = list(dict.fromkeys(i for i, _ in placement))
+        assert len(used) <= 2
+        for i in used:
+            inside = sorted(o for a, o in placement if a == i)
+            assert all(o % 256 == 0 and o + self.plane_bytes <= buffers[i].nbytes for o in inside)
+            assert all(b - a >= self.plane_bytes for a, b in zip(inside, inside[1:])), "planes overlap"
+        self.arena = buffers[used[0]] if used else None
+        self.arena2 = buffers[used[1]] if len(used) > 1 else None
+        self.plane_offsets = tuple(o for _, o in placement)
+        slices = [DeviceSlice(buffers[i], o, self.plane_bytes) for i, o in placement]
         for j, k in enumerate(self._index_ids):
-            self.index[k] = DeviceSlice(arena, offsets[j], self.plane_bytes)
+            self.index[k] = slices[j]
         for j, k in enumerate(self._rgba_ids):
-            self.rgba[k] = DeviceSlice(arena, offsets[len(self._index_ids) + j], self.plane_bytes)
+            self.rgba[k] = slices[len(self._index_ids) + j]
+
+    def adopt_arena(self, arena, offsets=None):
+        """All planes inside ``arena`` at ``offsets``, packed back to back when None."""
+        if offsets is None:
+            offsets = _arena.packed(len(self._index_ids) + len(self._rgba_ids), self.plane_bytes)
+        self.adopt([arena], [(0, o) for o in offsets])
 
     def adopt_two_arenas(self, arena, offsets, arena2, offsets2):
         """The first ``len(offsets)`` planes inside ``arena``, the rest inside ``arena2`` (both stay owned by these outputs):
         what ``TileBatch.make_outputs`` falls back to when every allocation it took is of ONE kind of memory throughout."""
-        offsets, offsets2 = tuple(int(o) for o in offsets), tuple(int(o) for o in offsets2)
-        nplanes = len(self._index_ids) + len(self._rgba_ids)
-        assert len(offsets) + len(offsets2) == nplanes
-        for buf, offs in ((arena, offsets), (arena2, offsets2)):
-            assert all(o % 256 == 0 and o + self.plane_bytes <= buf.nbytes for o in offs)
-            order = sorted(offs)
-            assert all(b - a >= self.plane_bytes for a, b in zip(order, order[1:])), "planes overlap"
-        self.arena, self.arena2 = arena, arena2
-        self.plane_offsets = offsets + offsets2
-        where = [(arena, o) for o in offsets] + [(arena2, o) for o in offsets2]
-        for j, k in enumerate(self._index_ids):
-            self.index[k] = DeviceSlice(where[j][0], where[j][1], self.plane_bytes)
-        for j, k in enumerate(self._rgba_ids):
-            self.rgba[k] = DeviceSlice(*where[len(self._index_ids) + j], self.plane_bytes)
+        self.adopt([arena, arena2], [(0, o) for o in offsets] + [(1, o) for o in offsets2])
+
+    def forget_planes(self):
+        """No plane points anywhere any more (their arenas were freed, or are about to be)."""
+        self.index, self.rgba, self.arena, self.arena2 = [None] * 3, [None] * 3, None, None
 
     def host_index(self, index_type, slot=0, count=1):
         k = INDEX_IDS[index_type]
@@ -922,7 +773,7 @@ class BatchOutputs:
         for b in self.index + self.rgba + self.luts + [self.wb, self.arena, self.arena2]:
             if b is not None:
                 b.free()
-        self.index, self.rgba, self.arena, self.arena2 = [None] * 3, [None] * 3, None, None
+        self.forget_planes()
 
 
 # ---------------------------------------------------------------------------

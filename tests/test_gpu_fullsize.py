@@ -113,15 +113,15 @@ def test_placement_search_of_a_multi_gib_arena():
     single.free(); auto.free()
     # Every allocation of one kind throughout (forced here: no gap between candidates counts as a class): the planes are split between two
     # allocations, tried pair by pair; whatever wins, the planes written there are the same bits, and both allocations belong to the outputs.
-    gap, trials = lars.batch.ARENA_CLASS_GAP, lars.batch.ARENA_TRIALS
-    lars.batch.ARENA_CLASS_GAP, lars.batch.ARENA_TRIALS = 0.0, 2
+    gap, trials = lars.arena.ARENA_CLASS_GAP, lars.arena.ARENA_TRIALS
+    lars.arena.ARENA_CLASS_GAP, lars.arena.ARENA_TRIALS = 0.0, 2
     try:
         cross = b.make_outputs(index=True, ring=ring)
     finally:
-        lars.batch.ARENA_CLASS_GAP, lars.batch.ARENA_TRIALS = gap, trials
+        lars.arena.ARENA_CLASS_GAP, lars.arena.ARENA_TRIALS = gap, trials
     rep = cross.arena_report
     split = [p for p in rep["placements"] if isinstance(p["allocation"], list)]
-    extra = lars.batch.ARENA_EXTRA_BLOCKS                           # then small allocations for the third plane alone, next to allocation 0's first two
+    extra = lars.arena.ARENA_EXTRA_BLOCKS                           # then small allocations for the third plane alone, next to allocation 0's first two
     assert rep["allocations"] == 2 + extra and len(split) == 2 + extra
     assert {tuple(p["allocation"]) for p in split} == {(0, 1), (1, 0)} | {(0, 2 + k) for k in range(extra)}
     assert rep["rejected"] == rep["allocations"] - (2 if cross.arena2 is not None else 1)
