@@ -340,9 +340,12 @@ int lars_d_synth_u8(uint8_t *tiles, int64_t ntiles, int64_t first_tile, int64_t 
  * predicted from a subsample and the histogram inside it; a tile whose window missed takes the two radix passes)|1 (always the two
  * radix passes)|3 (windows that miss on purpose: exercises the fall-back),
  * "selq_window" 1 (one-pass medians)|0 (always two select passes)|2 (wrong windows: exercises the fallback), "selq_list_wgs"
- * workgroups per select pass over the tiles a window missed (0 = 2048).  Results never depend on them.  Read-only:
+ * workgroups per select pass over the tiles a window missed (0 = 2048), "jpeg_subseq_bits" 32 .. 65536: the bits of entropy data one
+ * lane of the JPEG decoder takes (lars_d_decode_jpeg_u8; 32 = the longest code plus its extra bits, rounded up).
+ * Results never depend on them.  Read-only:
  * "last_fused_kernel" = the kernel family the last lars_d_fused launched (1 k_fused_u8c3, 2 k_fused_v2, 3 its uint16 form,
- * 4 k_fused_generic: one pixel per lane, 5 k_fused_u8c3 for RGBA uint8 tiles). */
+ * 4 k_fused_generic: one pixel per lane, 5 k_fused_u8c3 for RGBA uint8 tiles), "jpeg_last_rounds" = the synchronisation rounds
+ * that decoded anything in the last lars_h_decode_jpeg_u8 / lars_h_thumbnail_jpeg_u8 of the process (+100 when the serial finish ran). */
 int lars_set_tuning(const char *key, int value);
 int lars_get_tuning(const char *key, int *value);
 
@@ -514,6 +517,50 @@ int lars_d_decode_png_u8(const uint8_t *file, const int64_t *idat_table, int64_t
 int lars_h_decode_png_u8(const uint8_t *file, int64_t len, uint8_t *out, size_t out_cap);
 int lars_h_thumbnail_png_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
                             int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out);
+
+/* Baseline JPEG files decoded on the device -- the same Image.open(io.BytesIO(img_bytes)) + np.array(img) of
+ * load_image_from_db (process-images.py:181-193) for the format the cameras write, and the thumbnail after it.
+ * Covered: SOF0 / SOF1 (Huffman, 8 bit), one interleaved scan, one component (L, [h][w]) or YCbCr at 4:4:4, 4:2:2 or 4:2:0
+ * (RGB, [h][w][3]), restart intervals.  The pixels are libjpeg's JDCT_ISLOW ones with fancy upsampling: what Pillow's
+ * np.asarray gives, bit for bit.  Damaged entropy data is an error here (Pillow pads it with grey).
+ * lars_jpeg_info: pure host code.  Walks the marker segments of file[0..len), checks every length and table, and fills
+ * info[LARS_JPEG_INFO_N] = { width, height, components, frame marker (0xC0 ...), precision, h0, v0, h1, v1, h2, v2 (sampling),
+ * restart interval, entropy segment offset, entropy segment length, supported, LARS_JPEG_REASON_* }.
+ * lars_jpeg_decode_scratch_bytes: device scratch of lars_d_decode_jpeg_u8 for that info (0 for what it cannot decode).
+ * lars_d_decode_jpeg_u8: file_dev = the whole file on the device, head = its first info[12] bytes on the HOST (the tables are
+ * read from there before the call returns), info as lars_jpeg_info gave it, out = h * w * components bytes on the device;
+ * enqueues on stream and writes { LARS_JPGD_* status, detail } to the device int32 status_dev[2].
+ * lars_h_decode_jpeg_u8: host file in, host pixels out (out_cap >= h * w * components); one upload, one download.
+ * lars_h_thumbnail_jpeg_u8: host file in, lars_h_thumbnail_u8's plan numbers, host thumbnail out; the decoded pixels
+ * never leave the device.  The decoder runs at full scale: the caller checks that Pillow's draft() would too. */
+#define LARS_JPEG_INFO_N 16
+enum {
+    LARS_JPEG_REASON_NONE = 0,
+    LARS_JPEG_REASON_PROGRESSIVE = 1,  /* SOF2 */
+    LARS_JPEG_REASON_FRAME = 2,        /* lossless, arithmetic or hierarchical frame */
+    LARS_JPEG_REASON_PRECISION = 3,    /* not 8 bit */
+    LARS_JPEG_REASON_SCANS = 4,        /* more than one scan, or a scan that does not hold every component in order */
+    LARS_JPEG_REASON_COMPONENTS = 5,   /* 2 or 4 components (CMYK / YCCK) */
+    LARS_JPEG_REASON_COLORSPACE = 6,   /* RGB stored as such (Adobe transform 0, component ids R G B) */
+    LARS_JPEG_REASON_SAMPLING = 7,     /* other than 4:4:4, 4:2:2, 4:2:0 */
+    LARS_JPEG_REASON_DNL = 8,          /* height given by a DNL marker */
+    LARS_JPEG_REASON_SIZE = 9          /* h * w * components >= 2^31 */
+};
+enum {
+    LARS_JPGD_OK = 0,
+    LARS_JPGD_RESTART = 1,       /* detail: restart markers found; one is missing, extra or out of sequence */
+    LARS_JPGD_CODE = 2,          /* a bit pattern that is no code of the table in use; detail: the subsequence */
+    LARS_JPGD_COEF = 3,          /* a coefficient index past 63; detail: the subsequence */
+    LARS_JPGD_BLOCKS = 4,        /* the entropy data does not hold the frame's blocks; detail: blocks found (capped) */
+    LARS_JPGD_INTERNAL = 5
+};
+int lars_jpeg_info(const uint8_t *file, int64_t len, int64_t info[LARS_JPEG_INFO_N]);
+size_t lars_jpeg_decode_scratch_bytes(const int64_t info[LARS_JPEG_INFO_N]);
+int lars_d_decode_jpeg_u8(const uint8_t *file_dev, const uint8_t *head, const int64_t info[LARS_JPEG_INFO_N], uint8_t *out,
+                          int32_t *status_dev, void *scratch, void *stream);
+int lars_h_decode_jpeg_u8(const uint8_t *file, int64_t len, uint8_t *out, size_t out_cap);
+int lars_h_thumbnail_jpeg_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
+                             int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out);
 
 /* ------------------------------------------------------------------ image files (host only, no GPU work) */
 /* TIFF 6.0 LZW (compression 5, MSB-first codes, early width change) of one strip / tile: decodes at most ndst bytes

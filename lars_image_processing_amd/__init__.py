@@ -19,6 +19,7 @@ from .api import (  # noqa: F401
     colorize_index,
     colormap_lut,
     correct_white_balance,
+    decode_jpeg,
     decode_png,
     encode_png,
     download_processed_images,
@@ -26,10 +27,13 @@ from .api import (  # noqa: F401
     fix_white_balance_rgnir,
     generate_ndvi_report,
     index_histogram,
+    jpeg_draft_scale,
+    jpeg_info,
     preprocess_large_image,
     png_info,
     process_image,
     thumbnail,
+    thumbnail_jpeg,
     thumbnail_plan,
     thumbnail_png,
     time_series_points,

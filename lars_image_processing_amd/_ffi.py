@@ -157,6 +157,11 @@ SIGNATURES = {
     "lars_d_decode_png_u8": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I, _P, _P, _P, _P]),
     "lars_h_decode_png_u8": (_I, [_P, _I64, _P, _SZ]),
     "lars_h_thumbnail_png_u8": (_I, [_P, _I64, _I, _I, C.POINTER(_I), C.POINTER(_F), _I64, _I64, _I, _P]),
+    "lars_jpeg_info": (_I, [_P, _I64, _P]),
+    "lars_jpeg_decode_scratch_bytes": (_SZ, [_P]),
+    "lars_d_decode_jpeg_u8": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "lars_h_decode_jpeg_u8": (_I, [_P, _I64, _P, _SZ]),
+    "lars_h_thumbnail_jpeg_u8": (_I, [_P, _I64, _I, _I, C.POINTER(_I), C.POINTER(_F), _I64, _I64, _I, _P]),
     "lars_comm_available": (_I, []),
     "lars_comm_unique_id": (_I, [_P]),
     "lars_comm_init": (_I, [C.POINTER(_P), _I, _I, _P]),

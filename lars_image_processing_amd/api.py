@@ -20,6 +20,8 @@ this module                     reference
 ``encode_png``                  backend-process.py:70, process-images.py:567-617 (``Image.fromarray(x).save(png)``: same pixels)
 ``decode_png``                  process-images.py:181-193 (``np.array(Image.open(io.BytesIO(img_bytes)))``: same array)
 ``thumbnail_png``               process-images.py:186-189 from the file's bytes (decode + thumbnail, pixels stay on the GPU)
+``decode_jpeg``                 process-images.py:181-193, backend-process.py:52 for JPEG files (same array as Pillow's)
+``thumbnail_jpeg``              process-images.py:186-189 from a JPEG file's bytes, where ``draft`` keeps full scale
 ``align_images``                process-images.py:515  (phase correlation + shift)
 ``calculate_index_statistics_by_timeframe``  process-images.py:619 (pandas table)
 ``time_series_points``          process-images.py:814-832 (the numbers ``create_time_series_plot`` draws)
@@ -58,7 +60,7 @@ __all__ = [
     "calculate_index", "calculate_ndvi", "analyze_index", "analyze_index_statistics",
     "analyze_ndvi_statistics", "index_histogram", "classification_mask", "colorize_index", "process_image",
     "timeseries_row", "colormap_lut", "preprocess_large_image", "thumbnail", "thumbnail_plan", "encode_png",
-    "png_info", "decode_png", "thumbnail_png", "align_images", "change_detection",
+    "png_info", "decode_png", "thumbnail_png", "jpeg_info", "decode_jpeg", "thumbnail_jpeg", "jpeg_draft_scale", "align_images", "change_detection",
     "colorize_difference", "calculate_index_statistics_by_timeframe", "time_series_points",
     "calculate_ndvi_array", "generate_ndvi_report", "download_processed_images",
     "create_index_visualization", "create_comparison_view", "create_time_series_plot", "create_change_detection_visualization",
@@ -205,6 +207,21 @@ def thumbnail_plan(src_size, size=(400, 400), reducing_gap=2.0, draft_box=None, 
     return ThumbnailPlan(size=final, factor=factor, reduce_box=reduce_box,
                          box=tuple(float(np.float32(v)) for v in box),
                          vertical_first=h > w * 100 and final[1] < h, premultiply=rgba)
+
+
+def jpeg_draft_scale(src_size, size=(400, 400), reducing_gap=2.0):
+    """The scale (1, 2, 4 or 8) ``Image.thumbnail(size, ..., reducing_gap)`` makes the JPEG *decoder* work at, through
+    ``JpegImageFile.draft(None, (int(size[0] * reducing_gap), int(size[1] * reducing_gap)))``: the largest of 8, 4, 2, 1 not
+    above ``min(w // requested_w, h // requested_h)``.  1 when the image already fits (``thumbnail`` returns before ``draft``)
+    or ``reducing_gap`` is ``None``.  No GPU involved."""
+    if reducing_gap is None or thumbnail_size(src_size, size) is None:
+        return 1
+    req = (int(size[0] * reducing_gap), int(size[1] * reducing_gap))
+    scale = min(src_size[0] // req[0], src_size[1] // req[1])
+    for s in (8, 4, 2, 1):
+        if scale >= s:
+            break
+    return s
 
 
 def thumbnail(image, size=(400, 400), reducing_gap=2.0):
@@ -561,7 +578,7 @@ def _png_bytes(data, who):
     elif isinstance(data, np.ndarray) and data.dtype == np.uint8 and data.ndim == 1:
         arr = data
     else:
-        raise TypeError(f"{who}: a whole PNG file as bytes, bytearray, memoryview or 1-D uint8 array expected, got {type(data).__name__}")
+        raise TypeError(f"{who}: a whole {'JPEG' if 'jpeg' in who else 'PNG'} file as bytes, bytearray, memoryview or 1-D uint8 array expected, got {type(data).__name__}")
     return np.ascontiguousarray(arr)
 
 
@@ -640,6 +657,93 @@ def thumbnail_png(data, size=(400, 400), reducing_gap=2.0):
     new_w, new_h = plan.size
     out = np.empty((new_h, new_w) if c == 1 else (new_h, new_w, c), dtype=np.uint8)
     _png_call("lars_h_thumbnail_png_u8", _ffi.ptr(arr), arr.size, plan.factor[0], plan.factor[1],
+              (C.c_int * 4)(*plan.reduce_box), (C.c_float * 4)(*plan.box), new_h, new_w, int(plan.vertical_first),
+              _ffi.ptr(out))
+    return out
+
+
+# ---------------------------------------------------------------------------
+# JPEG files decoded on the device
+# ---------------------------------------------------------------------------
+_JPEG_INFO_N = 16
+_JPEG_REASONS = {0: None, 1: "progressive (SOF2)", 2: "lossless, arithmetic-coded or hierarchical frame", 3: "precision other than 8 bit",
+                 4: "more than one scan", 5: "2 or 4 components (CMYK / YCCK)", 6: "RGB stored as such (no YCbCr transform)",
+                 7: "sampling other than 4:4:4, 4:2:2 or 4:2:0", 8: "DNL marker", 9: "h * w * channels >= 2^31"}
+_JPEG_FRAMES = {0xC0: "baseline", 0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless"}
+
+
+def _jpeg_info(arr):
+    lib = _ffi.load()
+    info = (C.c_int64 * _JPEG_INFO_N)()
+    if lib.lars_jpeg_info(_ffi.ptr(arr), arr.size, info) != 0:
+        raise ValueError(lib.lars_last_error().decode("utf-8", "replace"))
+    return list(info)
+
+
+def jpeg_info(data):
+    """The marker segments of a JPEG file, validated on the host (``lars_jpeg_info``; no device needed).
+
+    Returns ``size`` (w, h), ``width``, ``height``, ``components``, ``mode`` (Pillow's: L, RGB or CMYK), ``frame`` (baseline,
+    extended sequential, progressive, ...), ``precision``, ``sampling`` ((h, v) per component), ``restart_interval``,
+    ``entropy_offset``, ``entropy_bytes``, ``supported`` (what ``decode_jpeg`` decodes) and ``reason`` (``None``, or why not).
+    Raises ``ValueError`` for structural damage: no SOI, a segment length that leaves the file, no SOS, SOS before the frame
+    header, a missing quantisation or Huffman table, an oversubscribed Huffman table.
+    """
+    i = _jpeg_info(_png_bytes(data, "jpeg_info"))
+    w, h, nc = i[0], i[1], i[2]
+    return {"size": (w, h), "width": w, "height": h, "components": nc, "mode": {1: "L", 3: "RGB", 4: "CMYK"}.get(nc),
+            "frame": _JPEG_FRAMES.get(i[3], f"SOF{i[3] - 0xC0}"), "precision": i[4],
+            "sampling": tuple((i[5 + 2 * c], i[6 + 2 * c]) for c in range(min(nc, 3))), "restart_interval": i[11],
+            "entropy_offset": i[12], "entropy_bytes": i[13], "supported": bool(i[14]), "reason": _JPEG_REASONS.get(i[15], str(i[15]))}
+
+
+def _jpeg_check(arr, who):
+    i = _jpeg_info(arr)
+    if not i[14]:
+        raise NotImplementedError(f"{who}: JPEG files with {_JPEG_REASONS.get(i[15], i[15])} are not supported "
+                                  "(baseline / extended sequential, 8 bit, one scan, L or YCbCr at 4:4:4, 4:2:2, 4:2:0)")
+    return i[1], i[0], i[2]
+
+
+def decode_jpeg(data):
+    """``np.asarray(Image.open(io.BytesIO(data)))`` of a JPEG file, decoded on the GPU (process-images.py:181-193).
+
+    ``data``: the whole file as ``bytes``, ``bytearray``, ``memoryview`` or a 1-D uint8 array.  Baseline and extended
+    sequential Huffman files of 8 bits with one scan: one component (L, ``[H, W]``) or YCbCr at 4:4:4, 4:2:2 or 4:2:0
+    (RGB, ``[H, W, 3]``), with or without restart markers; the arithmetic is libjpeg's (``JDCT_ISLOW``, fancy upsampling),
+    so the array is Pillow's bit for bit.  EXIF orientation is not applied (``Image.open`` does not either).  Other
+    variants (``jpeg_info(data)["reason"]``) raise ``NotImplementedError`` before anything is launched; damaged files raise
+    ``ValueError`` saying what is wrong.  Stricter than Pillow on purpose: entropy data that ends early, an invalid code, a
+    coefficient past 63 and a missing or misnumbered restart marker are errors.  No CPU fallback.
+    """
+    arr = _png_bytes(data, "decode_jpeg")
+    h, w, c = _jpeg_check(arr, "decode_jpeg")
+    out = np.empty((h, w) if c == 1 else (h, w, c), dtype=np.uint8)
+    _png_call("lars_h_decode_jpeg_u8", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
+    return out
+
+
+def thumbnail_jpeg(data, size=(400, 400), reducing_gap=2.0):
+    """``np.asarray`` of ``Image.open(io.BytesIO(data))`` after ``.thumbnail(size, LANCZOS, reducing_gap)``, bit for bit
+    (process-images.py:186-189), from a JPEG file's bytes: the decoded pixels stay on the GPU and go straight into the
+    thumbnail kernels, only the thumbnail comes back.  Pillow's ``thumbnail`` first lets ``draft`` switch the decoder to
+    1/2, 1/4 or 1/8 scale; this decoder works at full scale only, so where ``jpeg_draft_scale`` is above 1 (both sides of
+    the image at least twice ``size * reducing_gap``) it raises ``NotImplementedError``.  A file that already fits comes
+    back as ``decode_jpeg`` gives it.  Errors of the file as ``decode_jpeg``."""
+    arr = _png_bytes(data, "thumbnail_jpeg")
+    h, w, c = _jpeg_check(arr, "thumbnail_jpeg")
+    if reducing_gap is not None and reducing_gap < 1.0 and thumbnail_size((w, h), size) is not None:
+        raise ValueError("reducing_gap must be 1.0 or greater")
+    scale = jpeg_draft_scale((w, h), size, reducing_gap)
+    if scale != 1:
+        raise NotImplementedError(f"thumbnail_jpeg: Pillow's draft() decodes this {w} x {h} file at 1/{scale} scale for size {tuple(size)}; "
+                                  "scaled decoding is not supported")
+    plan = thumbnail_plan((w, h), size, reducing_gap, None, None)
+    if plan is None:
+        return decode_jpeg(arr)
+    new_w, new_h = plan.size
+    out = np.empty((new_h, new_w) if c == 1 else (new_h, new_w, c), dtype=np.uint8)
+    _png_call("lars_h_thumbnail_jpeg_u8", _ffi.ptr(arr), arr.size, plan.factor[0], plan.factor[1],
               (C.c_int * 4)(*plan.reduce_box), (C.c_float * 4)(*plan.box), new_h, new_w, int(plan.vertical_first),
               _ffi.ptr(out))
     return out

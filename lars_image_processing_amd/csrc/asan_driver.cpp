@@ -6,6 +6,7 @@
 //   kind 1  lars_h_tiff_lzw_decode_chunks: bytes = { u64 offsets[a], u64 counts[a], file... }, chunk_bytes = b, 3 threads
 //   kind 2  lars_stats_merge over nbytes / sizeof(lars_stats) records (a = how many to pass; 0 must be refused)
 //   kind 3  lars_png_info over a PNG file = bytes, with an IDAT table of a entries
+//   kind 4  lars_jpeg_info over a JPEG file = bytes
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -68,6 +69,10 @@ int main(int argc, char **argv)
             const int rc = lars_png_info(src, nbytes, info, a ? table.data() : nullptr, a);
             printf("%ld png rc=%d h=%016llx t=%016llx\n", ncase, rc, rc == 0 ? fnv(info, sizeof info) : 0ull,
                    rc == 0 ? fnv(table.data(), (size_t)a * 16) : 0ull);
+        } else if (kind == 4) {
+            int64_t info[LARS_JPEG_INFO_N];
+            const int rc = lars_jpeg_info(src, nbytes, info);
+            printf("%ld jpeg rc=%d h=%016llx\n", ncase, rc, rc == 0 ? fnv(info, sizeof info) : 0ull);
         } else {
             fprintf(stderr, "unknown case kind %u\n", kind);
             return 2;

@@ -111,6 +111,8 @@ struct Tuning {
     int out_stride_planes = 0; // laboratory build (LARS_LAB_LAYOUT) only: k > 1 = the fused kernel steps k x npix from tile to tile in its index planes
     int joint_depth = 6;       // joint.hip: 12-byte loads in flight per lane of the counting kernel (4 | 6 | 8 | 12)
     int joint_win_depth = 15;  // joint_win.hip: loads in flight per lane of the windowed counting kernel: 5 | 15 (a sweep every 15 steps), 4 | 6 | 12 (every 12)
+    int jpeg_subseq_bits = 512;  // jpeg_decode.hip: bits of entropy data per lane of the self-synchronising decode (32 .. 65536)
+    int jpeg_last_rounds = 0;  // read-only: rounds of k_jd_pass that decoded anything in the last lars_h_decode_jpeg_u8 / lars_h_thumbnail_jpeg_u8 (+100: k_jd_finish ran)
     int joint_window = 1;      // joint_win.hip: 1 windowed pair tables (one reader per tile chunk) where they fit, 0 never, 2 test hook (windows that miss)
 };
 Tuning &tuning();

@@ -1,0 +1,935 @@
+// Baseline JPEG decoding (SOF0 / SOF1, Huffman, 8 bit, one interleaved scan) on the device.
+//
+// Reference: load_image_from_db (process-images.py:181-193) and backend-process.py:52 open every stored picture with
+// Image.open(...) and np.array(img) or img.thumbnail(...): libjpeg on one host core.  Here the file goes up once and the
+// pixels (or only the thumbnail, lars_h_thumbnail_jpeg_u8) come back.  The pixel arithmetic is libjpeg's JDCT_ISLOW with
+// fancy upsampling, integer for integer, so the array is the one Pillow returns.
+//
+// The Huffman scan is serial by nature.  It is cut into subsequences of S bits ("jpeg_subseq_bits"), one lane each, and
+// the decoder states at their borders are found by iteration; a border counts only once it equals what the exact chain
+// from the last true synchronisation point (scan start, restart marker) gives, so the speculation changes the speed,
+// never the result.  The host parser (jpeg_parse.cpp) gives the tables and the byte range of the entropy data.
+//   k_jd_setup      one workgroup: Huffman decode tables (9-bit look-up + canonical lists) and quantisation tables of
+//                   the three components into scratch, from the kernel's own arguments.
+//   k_jd_mark       one thread per byte of the entropy segment: kept (data) or dropped (the 00 of FF 00, fill FFs,
+//                   restart markers), restart marker or not; counts per workgroup.  k_jd_exscan: their exclusive scans.
+//   k_jd_compact    the data bytes in one contiguous stream, the stream offset at which each restart interval starts,
+//                   the sequence check of the markers (RSTm follows RSTm-1).
+//   k_jd_intervals  subsequences per restart interval (at least one), the marker count against the frame's;
+//                   k_jd_subs: the table of subsequences (binary search of the interval).
+//   k_jd_pass       round 0: every lane decodes its subsequence from the assumed state (block 0 of an MCU, coefficient
+//                   0) -- true for the first subsequence of an interval -- counting blocks only, and records where and in
+//                   which state it left.  Then, in every round, a lane whose recorded entry differs from what its
+//                   predecessor left takes that as its entry and decodes again, over and over inside the workgroup
+//                   (at most 256 times) until no border inside it moves; the border between two workgroups is taken up
+//                   by the next round.  A round in which no lane decoded ends the iteration (later rounds return at
+//                   once).  A stream that synchronises within a workgroup's 256 subsequences needs three rounds.
+//   k_jd_finish     one wave, only when the last round still changed something: walks the borders in order and redoes
+//                   what disagrees, serially.  Exact by construction, slow only for streams that never synchronise.
+//   k_jd_check      an invalid code or a coefficient index past 63 on the exact chain: the smallest such subsequence.
+//   k_jd_verify     block index at which every interval starts (scan of the block counts) against the frame's.
+//   k_jd_write      every lane decodes its subsequence again from its true entry and writes coefficients: int16,
+//                   natural order, [block in scan order][64], DC as the difference.
+//   k_jd_mcu_sums   DC differences per MCU and component; their scan gives DC = prefix(MCU) - prefix(interval start) +
+//                   the differences inside the MCU (unsigned arithmetic: the wrap cancels).
+//   k_jd_idct       eight lanes per block: dequantise, column pass, row pass (workspace in LDS, padded against bank
+//                   conflicts), libjpeg's range limit, 8 bytes per lane into the component plane.
+//   k_jd_color      one thread per pixel: fancy (triangle) upsampling of Cb / Cr where the chroma plane is wider than
+//                   two samples, replication else, YCbCr -> RGB in 16-bit fixed point, [h][w][3] or [h][w].
+// Every loop is bounded by the length of the data, every index is checked against its buffer; an error is a status code
+// (LARS_JPGD_*) in device memory and every kernel after a failing one returns at once.
+#include <string.h>
+
+#include <algorithm>
+
+#include "common.h"
+#include "jpeg_parse.h"
+
+namespace lars {
+
+#define JD_ROUNDS 8                       // parallel rounds before k_jd_finish takes what is left
+#define JD_LOOK 9                         // bits of the Huffman look-up table
+#define JD_MARK_THREADS 1024
+#define JD_INVALID_CODE 0xFFFFFFFFFFFFFFFEull
+#define JD_INVALID_COEF 0xFFFFFFFFFFFFFFFDull
+#define JD_IS_INVALID(x) ((x) >= JD_INVALID_COEF)
+
+typedef unsigned long long jd_u64;
+
+struct JdTablesArg {                      // by value to k_jd_setup: per component, DC tables 0..2 and AC tables 3..5
+    uint16_t qt[3][64];
+    uint8_t hcount[6][16];
+    uint8_t hval[6][256];
+};
+
+struct JdHuff {
+    uint16_t look[1 << JD_LOOK];          // (length << 8) | symbol of the code that starts these bits, 0: longer than JD_LOOK
+    int maxcode[18];                      // largest code of length l (-1: none); [17] stops the search
+    int valoff[17];                       // index into val of the first code of length l, minus that code
+    uint8_t val[256];
+};
+
+struct JdTables {
+    JdHuff huff[6];
+    uint16_t qt[3][64];
+    uint8_t zigzag[64];
+};
+
+struct JdCtl {
+    int status[2];
+    jd_u64 errkey;                        // smallest (subsequence << 2 | kind) of an invalid exit on the exact chain
+    unsigned int changed[JD_ROUNDS + 1];
+    unsigned int kept_total, mark_total, nsub_total, block_total, bad_marker;
+};
+
+struct JdSub {
+    jd_u64 start, end, iend;              // bit positions in the compact stream: own range, end of the restart interval
+    unsigned int interval, first;
+};
+
+struct JdGeo {
+    int w, h, ncomp, hs, vs;              // sampling of component 0 (the others are 1 x 1)
+    int bpm, ny;                          // blocks per MCU, of which component 0's
+    int mcux, mcuy;
+    unsigned int nmcu, nblocks, ri, nint; // ri: MCUs per restart interval (nmcu when there are no restarts)
+    int pw[3], ph[3];                     // plane sizes in samples
+    unsigned int poff[3];                 // plane offsets in bytes
+    unsigned int pblocks[4];              // blocks of the planes before component c
+};
+
+__constant__ uint8_t c_jd_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                        41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                        30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+__device__ inline void jd_fail(JdCtl *ctl, int code, int detail)
+{
+    if (atomicCAS(&ctl->status[0], 0, code) == 0) ctl->status[1] = detail;
+}
+
+// ------------------------------------------------------------------------------------------------- tables
+__global__ __launch_bounds__(64) void k_jd_setup(JdTablesArg a, JdTables *T)
+{
+    const int t = threadIdx.x;
+    for (int i = t; i < 3 * 64; i += 64) T->qt[i / 64][i % 64] = a.qt[i / 64][i % 64];
+    T->zigzag[t] = c_jd_zigzag[t];
+    if (t >= 6) return;
+    JdHuff *H = &T->huff[t];
+    for (int i = 0; i < (1 << JD_LOOK); ++i) H->look[i] = 0;
+    for (int i = 0; i < 256; ++i) H->val[i] = a.hval[t][i];
+    int code = 0, k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        const int n = a.hcount[t][l - 1];
+        H->valoff[l] = k - code;
+        if (n) {
+            if (l <= JD_LOOK) {
+                for (int i = 0; i < n; ++i) {
+                    const int first = (code + i) << (JD_LOOK - l), fill = 1 << (JD_LOOK - l);
+                    for (int f = 0; f < fill && first + f < (1 << JD_LOOK); ++f)
+                        H->look[first + f] = (uint16_t)(l << 8 | a.hval[t][(k + i) & 255]);
+                }
+            }
+            k += n;
+            code += n;
+            H->maxcode[l] = code - 1;
+        } else {
+            H->maxcode[l] = -1;
+        }
+        code <<= 1;
+    }
+    H->maxcode[0] = -1;
+    H->maxcode[17] = 0x7FFFFFFF;
+    H->valoff[0] = 0;
+}
+
+// ------------------------------------------------------------------------------------------------- marker scan
+// what byte i of the entropy segment is: bit 0 kept (data), bit 1 the FF of a restart marker
+__device__ inline int jd_classify(const uint8_t *seg, long long n, long long i)
+{
+    const int cur = seg[i], prev = i > 0 ? seg[i - 1] : 0, next = i + 1 < n ? seg[i + 1] : 0x100;
+    if (cur == 0xFF) {
+        if (next == 0x00) return 1;
+        if (next >= 0xD0 && next <= 0xD7) return 2;
+        return 0;                                         // a fill byte, or the last byte of the segment
+    }
+    if (prev == 0xFF && (cur == 0x00 || (cur >= 0xD0 && cur <= 0xD7))) return 0;
+    return 1;
+}
+
+__global__ __launch_bounds__(JD_MARK_THREADS) void k_jd_mark(const uint8_t *seg, long long n, unsigned int *keepcnt, unsigned int *markcnt)
+{
+    __shared__ unsigned int s_keep, s_mark;
+    if (threadIdx.x == 0) s_keep = s_mark = 0;
+    __syncthreads();
+    const long long i = (long long)blockIdx.x * JD_MARK_THREADS + threadIdx.x;
+    const int c = i < n ? jd_classify(seg, n, i) : 0;
+    const jd_u64 bk = __ballot(c & 1), bm = __ballot(c & 2);
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&s_keep, (unsigned int)__popcll(bk));
+        atomicAdd(&s_mark, (unsigned int)__popcll(bm));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        keepcnt[blockIdx.x] = s_keep;
+        markcnt[blockIdx.x] = s_mark;
+    }
+}
+
+// exclusive scan of in[0..n) by one workgroup per channel (blockIdx.x * stride), chunk after chunk; in == out is fine
+__global__ __launch_bounds__(1024) void k_jd_exscan(const unsigned int *in, unsigned int *out, long long n, long long stride, unsigned int *total)
+{
+    __shared__ unsigned int wsum[16];
+    __shared__ unsigned int chunk_sum;
+    in += (long long)blockIdx.x * stride;
+    out += (long long)blockIdx.x * stride;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    unsigned int carry = 0;
+    for (long long base = 0; base < n; base += 1024) {
+        const long long i = base + tid;
+        const unsigned int v = i < n ? in[i] : 0u;
+        unsigned int incl = v;
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned int t = __shfl_up(incl, d);
+            if (lane >= d) incl += t;
+        }
+        if (lane == 63) wsum[wv] = incl;
+        __syncthreads();
+        if (wv == 0) {
+            const unsigned int s = lane < 16 ? wsum[lane] : 0u;
+            unsigned int si = s;
+            for (int d = 1; d < 16; d <<= 1) {
+                const unsigned int t = __shfl_up(si, d);
+                if (lane >= d) si += t;
+            }
+            if (lane < 16) wsum[lane] = si - s;
+            if (lane == 15) chunk_sum = si;
+        }
+        __syncthreads();
+        if (i < n) out[i] = carry + wsum[wv] + incl - v;
+        carry += chunk_sum;
+        __syncthreads();
+    }
+    if (tid == 0 && total) total[blockIdx.x] = carry;
+}
+
+__global__ __launch_bounds__(JD_MARK_THREADS) void k_jd_compact(const uint8_t *seg, long long n, const unsigned int *keepoff,
+                                                                const unsigned int *markoff, unsigned int nint, uint8_t *compact,
+                                                                jd_u64 *cbyte, JdCtl *ctl)
+{
+    __shared__ unsigned int wk[JD_MARK_THREADS / 64], wm[JD_MARK_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const long long i = (long long)blockIdx.x * JD_MARK_THREADS + tid;
+    const int c = i < n ? jd_classify(seg, n, i) : 0;
+    const jd_u64 bk = __ballot(c & 1), bm = __ballot(c & 2);
+    if (lane == 0) {
+        wk[wv] = (unsigned int)__popcll(bk);
+        wm[wv] = (unsigned int)__popcll(bm);
+    }
+    __syncthreads();
+    unsigned int pk = keepoff[blockIdx.x], pm = markoff[blockIdx.x];
+    for (int v = 0; v < wv; ++v) {
+        pk += wk[v];
+        pm += wm[v];
+    }
+    const jd_u64 below = (1ull << lane) - 1;
+    pk += (unsigned int)__popcll(bk & below);
+    pm += (unsigned int)__popcll(bm & below);
+    if (c & 1) compact[pk] = seg[i];                      // pk < kept bytes <= n
+    if (c & 2) {
+        if (seg[i + 1] != 0xD0 + (pm & 7)) atomicOr(&ctl->bad_marker, 1u);   // c & 2 implies i + 1 < n
+        if (pm + 1 < nint) cbyte[pm + 1] = pk;            // the interval after marker pm starts at the next kept byte
+    }
+}
+
+__global__ void k_jd_intervals(jd_u64 *cbyte, unsigned int nint, unsigned int sbits, unsigned int *nsubs, JdCtl *ctl)
+{
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ctl->mark_total != nint - 1 || ctl->bad_marker) {
+        if (i == 0) jd_fail(ctl, LARS_JPGD_RESTART, (int)min(ctl->mark_total, 0x7FFFFFFFu));
+        if (i < nint) nsubs[i] = 0;
+        return;
+    }
+    if (i >= nint) return;
+    const jd_u64 a = i == 0 ? 0ull : cbyte[i], b = i + 1 == nint ? (jd_u64)ctl->kept_total : cbyte[i + 1];
+    if (i == 0) {
+        cbyte[0] = 0;
+        cbyte[nint] = ctl->kept_total;
+    }
+    const jd_u64 bits = (b - a) * 8;
+    nsubs[i] = (unsigned int)max((bits + sbits - 1) / sbits, 1ull);
+}
+
+__global__ void k_jd_subs(const jd_u64 *cbyte, const unsigned int *suboff, unsigned int nint, unsigned int sbits, unsigned int cap,
+                          JdSub *subs, JdCtl *ctl)
+{
+    if (ctl->status[0]) return;
+    const unsigned int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const unsigned int total = ctl->nsub_total;
+    if (total > cap) {
+        if (j == 0) jd_fail(ctl, LARS_JPGD_INTERNAL, 1);
+        return;
+    }
+    if (j >= total) return;
+    unsigned int lo = 0, hi = nint - 1;                   // the last interval whose first subsequence is <= j
+    while (lo < hi) {
+        const unsigned int mid = (lo + hi + 1) >> 1;
+        if (suboff[mid] <= j) lo = mid; else hi = mid - 1;
+    }
+    const jd_u64 ibeg = cbyte[lo] * 8, iend = cbyte[lo + 1] * 8;
+    const unsigned int local = j - suboff[lo];
+    JdSub s;
+    s.start = min(ibeg + (jd_u64)local * sbits, iend);
+    s.end = min(s.start + sbits, iend);
+    s.iend = iend;
+    s.interval = lo;
+    s.first = local == 0;
+    subs[j] = s;
+}
+
+// ------------------------------------------------------------------------------------------------- entropy decode
+__device__ inline unsigned int jd_peek32(const unsigned int *words, jd_u64 pos)
+{
+    const jd_u64 i = pos >> 5;
+    const unsigned int a = __builtin_bswap32(words[i]), b = __builtin_bswap32(words[i + 1]);
+    const unsigned int sh = (unsigned int)pos & 31u;
+    return sh ? (a << sh) | (b >> (32 - sh)) : a;
+}
+
+__device__ inline jd_u64 jd_pack(jd_u64 pos, int b, int k) { return pos << 10 | (jd_u64)b << 6 | (jd_u64)k; }
+
+// Decodes from (pos, block b of the MCU, coefficient k) until pos >= end; symbols that would cross iend are not taken
+// (the padding of the interval's last byte).  Returns the packed exit state or JD_INVALID_*; cnt = blocks completed.
+// WRITE: coefficients go to coef[blk][...] while blk < nblocks.  At most end - pos iterations: every symbol has a bit.
+template <bool WRITE>
+__device__ jd_u64 jd_run(const JdTables *T, const unsigned int *words, jd_u64 st, jd_u64 end, jd_u64 iend, int bpm, int ny,
+                         unsigned int *cnt_out, short *coef, unsigned int blk, unsigned int nblocks)
+{
+    jd_u64 pos = st >> 10;
+    int b = (int)(st >> 6) & 15, k = (int)st & 63;
+    unsigned int cnt = 0;
+    while (pos < end) {
+        const int comp = b < ny ? 0 : b - ny + 1;
+        const JdHuff *H = &T->huff[k == 0 ? comp : 3 + comp];
+        const unsigned int w = jd_peek32(words, pos);
+        int len, sym;
+        const unsigned int e = H->look[w >> (32 - JD_LOOK)];
+        if (e) {
+            len = (int)(e >> 8);
+            sym = (int)(e & 255);
+        } else {
+            len = JD_LOOK + 1;
+            while ((int)(w >> (32 - len)) > H->maxcode[len]) ++len;   // maxcode[17] stops it
+            if (len > 16) {
+                if (pos + 16 > iend) { pos = iend; break; }          // padding at the end of the interval
+                *cnt_out = cnt;
+                return JD_INVALID_CODE;
+            }
+            sym = H->val[((int)(w >> (32 - len)) + H->valoff[len]) & 255];
+        }
+        const int s = sym & 15;
+        if (pos + len + s > iend) { pos = iend; break; }
+        int v = 0;
+        if (s) {
+            v = (int)((w << len) >> (32 - s));
+            if (v < (1 << (s - 1))) v -= (1 << s) - 1;
+        }
+        pos += len + s;
+        bool done = false;
+        if (k == 0) {
+            if (WRITE && blk < nblocks) coef[(size_t)blk * 64] = (short)v;
+            k = 1;
+        } else {
+            const int r = sym >> 4;
+            if (s == 0) {
+                if (r == 15) { k += 16; done = k > 63; }
+                else done = true;
+            } else {
+                k += r;
+                if (k > 63) {
+                    *cnt_out = cnt;
+                    return JD_INVALID_COEF;
+                }
+                if (WRITE && blk < nblocks) coef[(size_t)blk * 64 + T->zigzag[k]] = (short)v;
+                ++k;
+                done = k > 63;
+            }
+        }
+        if (done) {
+            ++cnt;
+            ++blk;
+            k = 0;
+            b = b + 1 == bpm ? 0 : b + 1;
+        }
+    }
+    *cnt_out = cnt;
+    return jd_pack(pos, b, k);
+}
+
+__device__ inline void jd_load_tables(JdTables *dst, const JdTables *src)
+{
+    const unsigned int *s = reinterpret_cast<const unsigned int *>(src);
+    unsigned int *d = reinterpret_cast<unsigned int *>(dst);
+    for (unsigned int i = threadIdx.x; i < sizeof(JdTables) / 4; i += blockDim.x) d[i] = s[i];
+    __syncthreads();
+}
+static_assert(sizeof(JdTables) % 4 == 0, "JdTables is copied by words");
+
+__global__ __launch_bounds__(256) void k_jd_pass(const JdTables *Tg, const unsigned int *words, const JdSub *subs, jd_u64 *in, jd_u64 *out,
+                                                 unsigned int *cnt, int round, int bpm, int ny, JdCtl *ctl)
+{
+    __shared__ JdTables T;
+    if (ctl->status[0]) return;
+    if (round > 1 && ctl->changed[round - 1] == 0) return;
+    const unsigned int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = j < ctl->nsub_total;
+    JdSub s{};
+    jd_u64 my_in = 0;
+    bool loaded = false, did = false;
+    if (live) s = subs[j];
+    if (round == 0) {
+        jd_load_tables(&T, Tg);
+        loaded = true;
+        if (live) {
+            unsigned int n = 0;
+            my_in = jd_pack(s.start, 0, 0);
+            const jd_u64 o = jd_run<false>(&T, words, my_in, s.end, s.iend, bpm, ny, &n, nullptr, 0, 0);
+            in[j] = my_in;
+            cnt[j] = n;
+            __atomic_store_n(&out[j], o, __ATOMIC_RELAXED);
+        }
+    } else if (live) {
+        my_in = in[j];
+    }
+    // The borders inside the workgroup, until none of them moves: at most one iteration per lane.  The border to the
+    // workgroup before is looked at from round 1 on, when that workgroup has written it.
+    for (int it = 0; it < 256; ++it) {
+        __syncthreads();
+        bool need = false;
+        jd_u64 st = 0;
+        if (live && !s.first && (threadIdx.x > 0 || round > 0)) {
+            st = __atomic_load_n(&out[j - 1], __ATOMIC_RELAXED);
+            need = !JD_IS_INVALID(st) && st != my_in;
+        }
+        if (!__syncthreads_or(need)) break;
+        if (!loaded) {
+            jd_load_tables(&T, Tg);
+            loaded = true;
+        }
+        if (need) {
+            unsigned int n = 0;
+            const jd_u64 o = jd_run<false>(&T, words, st, s.end, s.iend, bpm, ny, &n, nullptr, 0, 0);
+            my_in = st;
+            in[j] = st;
+            cnt[j] = n;
+            __atomic_store_n(&out[j], o, __ATOMIC_RELAXED);
+            did = true;
+        }
+    }
+    if (did && round > 0) atomicAdd(&ctl->changed[round], 1u);
+}
+
+// what the rounds left: the borders in order, one wave, each lane owning one subsequence of a group of 64
+__global__ __launch_bounds__(64) void k_jd_finish(const JdTables *Tg, const unsigned int *words, const JdSub *subs, jd_u64 *in, jd_u64 *out,
+                                                  unsigned int *cnt, int bpm, int ny, JdCtl *ctl)
+{
+    __shared__ JdTables T;
+    if (ctl->status[0] || ctl->changed[JD_ROUNDS] == 0) return;
+    jd_load_tables(&T, Tg);
+    const unsigned int total = ctl->nsub_total;
+    const int lane = threadIdx.x;
+    jd_u64 carry = JD_INVALID_CODE;                       // exit of the subsequence before the group
+    for (unsigned int base = 0; base < total; base += 64) {
+        const unsigned int j = base + lane;
+        const bool live = j < total;
+        JdSub s{};
+        jd_u64 my_in = 0, my_out = 0;
+        if (live) {
+            s = subs[j];
+            my_in = in[j];
+            my_out = out[j];
+        }
+        const jd_u64 before = __shfl_up(my_out, 1);
+        const jd_u64 prev = lane == 0 ? carry : before;
+        const bool differs = live && !s.first && !JD_IS_INVALID(prev) && prev != my_in;
+        if (__ballot(differs) != 0) {
+            for (int l = 0; l < 64 && base + l < total; ++l) {
+                const jd_u64 p = l == 0 ? carry : __shfl(my_out, l - 1);
+                if (lane == l && !s.first && !JD_IS_INVALID(p) && p != my_in) {
+                    unsigned int n = 0;
+                    my_out = jd_run<false>(&T, words, p, s.end, s.iend, bpm, ny, &n, nullptr, 0, 0);
+                    in[j] = p;
+                    cnt[j] = n;
+                    out[j] = my_out;
+                }
+            }
+        }
+        carry = __shfl(my_out, 63);                       // a group that is not full is the last one
+    }
+}
+
+__global__ void k_jd_check(const jd_u64 *out, JdCtl *ctl)
+{
+    if (ctl->status[0]) return;
+    const unsigned int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= ctl->nsub_total) return;
+    const jd_u64 o = out[j];
+    if (JD_IS_INVALID(o)) atomicMin(&ctl->errkey, (jd_u64)j << 2 | (o == JD_INVALID_CODE ? 1u : 2u));
+}
+
+// pre = exclusive scan of cnt: every interval must start at the block the frame says, and the total must be the frame's
+__global__ void k_jd_verify(const unsigned int *pre, const unsigned int *suboff, JdGeo g, JdCtl *ctl)
+{
+    if (ctl->status[0]) return;
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ctl->errkey != ~0ull) {
+        if (i == 0) jd_fail(ctl, (ctl->errkey & 3) == 1 ? LARS_JPGD_CODE : LARS_JPGD_COEF, (int)min(ctl->errkey >> 2, (jd_u64)0x7FFFFFFF));
+        return;
+    }
+    if (i >= g.nint) return;
+    const unsigned int want = i * g.ri * (unsigned int)g.bpm;
+    bool bad = pre[suboff[i]] != want;
+    if (i == 0) bad = bad || ctl->block_total != g.nblocks;
+    if (bad) jd_fail(ctl, LARS_JPGD_BLOCKS, (int)min(ctl->block_total, 0x7FFFFFFFu));
+}
+
+__global__ __launch_bounds__(256) void k_jd_write(const JdTables *Tg, const unsigned int *words, const JdSub *subs, const jd_u64 *in,
+                                                  const unsigned int *pre, int bpm, int ny, unsigned int nblocks, short *coef, JdCtl *ctl)
+{
+    __shared__ JdTables T;
+    if (ctl->status[0]) return;
+    jd_load_tables(&T, Tg);
+    const unsigned int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= ctl->nsub_total) return;
+    const JdSub s = subs[j];
+    unsigned int n = 0;
+    jd_run<true>(&T, words, in[j], s.end, s.iend, bpm, ny, &n, coef, pre[j], nblocks);
+}
+
+// ------------------------------------------------------------------------------------------------- DC, IDCT, colour
+__global__ void k_jd_mcu_sums(const short *coef, JdGeo g, unsigned int *sums, const JdCtl *ctl)
+{
+    if (ctl->status[0]) return;
+    const unsigned int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= g.nmcu) return;
+    const short *c = coef + (size_t)m * g.bpm * 64;
+    unsigned int y = 0;
+    for (int b = 0; b < g.ny; ++b) y += (unsigned int)(int)c[b * 64];
+    sums[m] = y;
+    for (int k = 1; k < g.ncomp; ++k) sums[(size_t)k * g.nmcu + m] = (unsigned int)(int)c[(g.ny + k - 1) * 64];
+}
+
+#define JD_F_0_298631336 2446
+#define JD_F_0_390180644 3196
+#define JD_F_0_541196100 4433
+#define JD_F_0_765366865 6270
+#define JD_F_0_899976223 7373
+#define JD_F_1_175875602 9633
+#define JD_F_1_501321110 12299
+#define JD_F_1_847759065 15137
+#define JD_F_1_961570560 16069
+#define JD_F_2_053119869 16819
+#define JD_F_2_562915447 20995
+#define JD_F_3_072711026 25172
+
+// one 8-point pass of jidctint.c's jpeg_idct_islow: x in, x out, descale by sh with rounding
+template <int SH>
+__device__ inline void jd_idct8(int x[8])
+{
+    int z1 = (x[2] + x[6]) * JD_F_0_541196100;
+    const int t2 = z1 + x[6] * (-JD_F_1_847759065), t3 = z1 + x[2] * JD_F_0_765366865;
+    const int t0 = (int)((unsigned int)(x[0] + x[4]) << 13), t1 = (int)((unsigned int)(x[0] - x[4]) << 13);
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    int a0 = x[7], a1 = x[5], a2 = x[3], a3 = x[1];
+    z1 = a0 + a3;
+    int z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3;
+    const int z5 = (z3 + z4) * JD_F_1_175875602;
+    a0 *= JD_F_0_298631336;
+    a1 *= JD_F_2_053119869;
+    a2 *= JD_F_3_072711026;
+    a3 *= JD_F_1_501321110;
+    z1 *= -JD_F_0_899976223;
+    z2 *= -JD_F_2_562915447;
+    z3 *= -JD_F_1_961570560;
+    z4 *= -JD_F_0_390180644;
+    z3 += z5;
+    z4 += z5;
+    a0 += z1 + z3;
+    a1 += z2 + z4;
+    a2 += z2 + z3;
+    a3 += z1 + z4;
+    const int half = 1 << (SH - 1);
+    x[0] = (t10 + a3 + half) >> SH;
+    x[7] = (t10 - a3 + half) >> SH;
+    x[1] = (t11 + a2 + half) >> SH;
+    x[6] = (t11 - a2 + half) >> SH;
+    x[2] = (t12 + a1 + half) >> SH;
+    x[5] = (t12 - a1 + half) >> SH;
+    x[3] = (t13 + a0 + half) >> SH;
+    x[4] = (t13 - a0 + half) >> SH;
+}
+
+#define JD_WS_STRIDE 72                   // words per block in LDS: 64 + 8, so that the blocks of a wave start on different banks
+
+__global__ __launch_bounds__(256) void k_jd_idct(const short *coef, const unsigned int *dcpre, const JdTables *Tg, JdGeo g, uint8_t *planes,
+                                                 const JdCtl *ctl)
+{
+    __shared__ int ws[32 * JD_WS_STRIDE];
+    __shared__ int qt[3][64];
+    if (ctl->status[0]) return;
+    for (int i = threadIdx.x; i < 192; i += 256) qt[i / 64][i % 64] = Tg->qt[i / 64][i % 64];
+    __syncthreads();
+    const unsigned int pb = blockIdx.x * 32 + (threadIdx.x >> 3);   // block in plane order
+    const int r = threadIdx.x & 7;
+    const bool live = pb < g.pblocks[3];
+    int comp = 0, bx = 0, by = 0;
+    int *w = ws + (threadIdx.x >> 3) * JD_WS_STRIDE;
+    int x[8];
+    if (live) {
+        comp = pb >= g.pblocks[2] ? 2 : pb >= g.pblocks[1] ? 1 : 0;
+        const unsigned int local = pb - g.pblocks[comp];
+        const int hs = comp == 0 ? g.hs : 1, vs = comp == 0 ? g.vs : 1;
+        const int bw = g.mcux * hs;
+        by = (int)(local / bw);
+        bx = (int)(local % bw);
+        const unsigned int m = (unsigned int)(by / vs) * g.mcux + (unsigned int)(bx / hs);
+        const int inner = comp == 0 ? (by % vs) * hs + (bx % hs) : g.ny + comp - 1;
+        const size_t blk = (size_t)m * g.bpm + inner;
+        const uint4 raw = *reinterpret_cast<const uint4 *>(coef + blk * 64 + r * 8);   // row r: 8 coefficients
+        const unsigned int rw[4] = {raw.x, raw.y, raw.z, raw.w};
+        for (int i = 0; i < 4; ++i) {
+            x[2 * i] = (int)(short)(rw[i] & 0xFFFF);
+            x[2 * i + 1] = (int)(short)(rw[i] >> 16);
+        }
+        if (r == 0) {                                     // the DC: differences summed from the start of the restart interval
+            const unsigned int m0 = m / g.ri * g.ri;
+            const unsigned int *P = dcpre + (size_t)comp * g.nmcu;
+            unsigned int dc = P[m] - P[m0];
+            const short *mc = coef + (size_t)m * g.bpm * 64;
+            if (comp == 0) for (int b = 0; b <= inner; ++b) dc += (unsigned int)(int)mc[b * 64];
+            else dc += (unsigned int)(int)mc[inner * 64];
+            x[0] = (int)(short)dc;
+        }
+        for (int i = 0; i < 8; ++i) w[r * 8 + i] = x[i] * qt[comp][r * 8 + i];
+    }
+    __syncthreads();
+    if (live) {
+        for (int i = 0; i < 8; ++i) x[i] = w[i * 8 + r];  // column r
+        jd_idct8<11>(x);
+    }
+    __syncthreads();
+    if (live) for (int i = 0; i < 8; ++i) w[i * 8 + r] = x[i];
+    __syncthreads();
+    if (live) {
+        for (int i = 0; i < 8; ++i) x[i] = w[r * 8 + i];  // row r
+        jd_idct8<18>(x);
+        unsigned int lo = 0, hi = 0;
+        for (int i = 0; i < 8; ++i) {
+            int v = x[i] & 1023;                          // libjpeg's range-limit table: 10 bits, signed, centred on 128
+            if (v >= 512) v -= 1024;
+            v = min(255, max(0, v + 128));
+            if (i < 4) lo |= (unsigned int)v << (8 * i); else hi |= (unsigned int)v << (8 * (i - 4));
+        }
+        uint8_t *dst = planes + g.poff[comp] + (size_t)(by * 8 + r) * g.pw[comp] + bx * 8;   // plane widths are multiples of 8
+        *reinterpret_cast<uint2 *>(dst) = make_uint2(lo, hi);
+    }
+}
+
+__device__ inline int jd_chroma(const uint8_t *P, int pw, int cw, int chh, int hs, int vs, int x, int y)
+{
+    if (hs == 1) return P[(size_t)y * pw + x];
+    const int cx = x >> 1;
+    if (cw <= 2) return P[(size_t)(vs == 2 ? y >> 1 : y) * pw + cx];        // libjpeg replicates narrow planes
+    if (vs == 1) {
+        const int a = P[(size_t)y * pw + cx];
+        if (x & 1) return cx == cw - 1 ? a : (3 * a + P[(size_t)y * pw + cx + 1] + 2) >> 2;
+        return cx == 0 ? a : (3 * a + P[(size_t)y * pw + cx - 1] + 1) >> 2;
+    }
+    const int cy = y >> 1;
+    const int fy = (y & 1) ? min(cy + 1, chh - 1) : max(cy - 1, 0);
+    const uint8_t *n = P + (size_t)cy * pw, *f = P + (size_t)fy * pw;
+    const int t = 3 * n[cx] + f[cx];
+    if (x & 1) return cx == cw - 1 ? (4 * t + 7) >> 4 : (3 * t + 3 * n[cx + 1] + f[cx + 1] + 7) >> 4;
+    return cx == 0 ? (4 * t + 8) >> 4 : (3 * t + 3 * n[cx - 1] + f[cx - 1] + 8) >> 4;
+}
+
+__global__ __launch_bounds__(256) void k_jd_color(const uint8_t *planes, JdGeo g, uint8_t *out, const JdCtl *ctl)
+{
+    if (ctl->status[0]) return;
+    const long long n = (long long)g.w * g.h;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < n; p += (long long)gridDim.x * 256) {
+        const int y = (int)(p / g.w), x = (int)(p % g.w);
+        const int Y = planes[g.poff[0] + (size_t)y * g.pw[0] + x];
+        if (g.ncomp == 1) {
+            out[p] = (uint8_t)Y;
+            continue;
+        }
+        const int cw = (g.w + g.hs - 1) / g.hs, chh = (g.h + g.vs - 1) / g.vs;
+        const int cb = jd_chroma(planes + g.poff[1], g.pw[1], cw, chh, g.hs, g.vs, x, y) - 128;
+        const int cr = jd_chroma(planes + g.poff[2], g.pw[2], cw, chh, g.hs, g.vs, x, y) - 128;
+        const int R = Y + ((91881 * cr + 32768) >> 16);
+        const int G = Y + ((-22554 * cb - 46802 * cr + 32768) >> 16);
+        const int B = Y + ((116130 * cb + 32768) >> 16);
+        out[p * 3] = (uint8_t)min(255, max(0, R));
+        out[p * 3 + 1] = (uint8_t)min(255, max(0, G));
+        out[p * 3 + 2] = (uint8_t)min(255, max(0, B));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------- host side
+struct JdLayout {
+    JdGeo g;
+    jd_u64 elen, nwg, nsub_cap;
+    unsigned int sbits;
+    size_t ctl, tables, keepcnt, markcnt, compact, cbyte, nsubs, suboff, subs, in, out, cnt, pre, coef, sums, planes, bytes;
+};
+
+// info as lars_jpeg_info gave it; false for what the decoder does not take
+static bool jd_layout(const int64_t info[LARS_JPEG_INFO_N], int sbits, JdLayout *Lp)
+{
+    JdLayout L{};
+    const int64_t w = info[0], h = info[1], nc = info[2];
+    if (!info[14] || w < 1 || h < 1 || w > 65535 || h > 65535 || (nc != 1 && nc != 3) || h * w * nc >= (1ll << 31)) return false;
+    if (info[12] < 0 || info[13] < 0 || info[13] > (1ll << 40) || info[11] < 0 || info[11] > 65535) return false;
+    const int hs = nc == 1 ? 1 : (int)info[5], vs = nc == 1 ? 1 : (int)info[6];
+    if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return false;
+    JdGeo &g = L.g;
+    g.w = (int)w; g.h = (int)h; g.ncomp = (int)nc; g.hs = hs; g.vs = vs;
+    g.ny = hs * vs;
+    g.bpm = g.ny + (int)nc - 1;
+    g.mcux = (int)((w + 8 * hs - 1) / (8 * hs));
+    g.mcuy = (int)((h + 8 * vs - 1) / (8 * vs));
+    g.nmcu = (unsigned int)g.mcux * g.mcuy;
+    g.nblocks = g.nmcu * g.bpm;
+    g.ri = info[11] > 0 && (unsigned int)info[11] < g.nmcu ? (unsigned int)info[11] : g.nmcu;
+    g.nint = (g.nmcu + g.ri - 1) / g.ri;
+    unsigned int off = 0, blocks = 0;
+    for (int c = 0; c < 3; ++c) {
+        g.pblocks[c] = blocks;
+        if (c >= nc) { g.pw[c] = g.ph[c] = 0; g.poff[c] = off; continue; }
+        g.pw[c] = g.mcux * (c == 0 ? hs : 1) * 8;
+        g.ph[c] = g.mcuy * (c == 0 ? vs : 1) * 8;
+        g.poff[c] = off;
+        off += (unsigned int)g.pw[c] * g.ph[c];           // < 2^32: each plane is at most 65536^2 / 1, checked by h * w * nc above
+        blocks += (unsigned int)(g.pw[c] / 8) * (g.ph[c] / 8);
+    }
+    g.pblocks[3] = blocks;
+    L.elen = (jd_u64)info[13];
+    L.sbits = (unsigned int)sbits;
+    L.nwg = (L.elen + JD_MARK_THREADS - 1) / JD_MARK_THREADS;
+    L.nsub_cap = L.elen * 8 / L.sbits + g.nint + 1;
+    if (L.nsub_cap >= (1ull << 31) || L.nwg >= (1ull << 31)) return false;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    size_t o = 0;
+    L.ctl = o; o += al(sizeof(JdCtl));
+    L.tables = o; o += al(sizeof(JdTables));
+    L.keepcnt = o; o += al((L.nwg + 1) * 4);
+    L.markcnt = o; o += al((L.nwg + 1) * 4);
+    L.compact = o; o += al(L.elen + 16);
+    L.cbyte = o; o += al(((size_t)g.nint + 1) * 8);
+    L.nsubs = o; o += al(((size_t)g.nint + 1) * 4);
+    L.suboff = o; o += al(((size_t)g.nint + 1) * 4);
+    L.subs = o; o += al(L.nsub_cap * sizeof(JdSub));
+    L.in = o; o += al(L.nsub_cap * 8);
+    L.out = o; o += al(L.nsub_cap * 8);
+    L.cnt = o; o += al(L.nsub_cap * 4);
+    L.pre = o; o += al(L.nsub_cap * 4);
+    L.coef = o; o += al((size_t)g.nblocks * 128);
+    L.sums = o; o += al((size_t)g.nmcu * 4 * 3);
+    L.planes = o; o += al((size_t)off);
+    L.bytes = o;
+    *Lp = L;
+    return true;
+}
+
+static int jd_status_fail(const char *who, const int st[2])
+{
+    switch (st[0]) {
+    case LARS_JPGD_RESTART: return fail(LARS_ERR_INVALID, "%s: a restart marker is missing or out of sequence (%d found)", who, st[1]);
+    case LARS_JPGD_CODE: return fail(LARS_ERR_INVALID, "%s: entropy data holds a bit pattern that is no Huffman code of its table (subsequence %d)", who, st[1]);
+    case LARS_JPGD_COEF: return fail(LARS_ERR_INVALID, "%s: entropy data runs past coefficient 63 of a block (subsequence %d)", who, st[1]);
+    case LARS_JPGD_BLOCKS: return fail(LARS_ERR_INVALID, "%s: entropy data does not hold the frame's blocks (it ends early or is damaged; %d blocks found)", who, st[1]);
+    default: return fail(LARS_ERR_HIP, "%s: internal decoder status %d (%d)", who, st[0], st[1]);
+    }
+}
+
+static const char *jd_reason(int64_t r)
+{
+    switch (r) {
+    case LARS_JPEG_REASON_PROGRESSIVE: return "progressive";
+    case LARS_JPEG_REASON_FRAME: return "lossless, arithmetic-coded or hierarchical";
+    case LARS_JPEG_REASON_PRECISION: return "not 8-bit";
+    case LARS_JPEG_REASON_SCANS: return "multi-scan";
+    case LARS_JPEG_REASON_COMPONENTS: return "2- or 4-component (CMYK / YCCK)";
+    case LARS_JPEG_REASON_COLORSPACE: return "RGB-stored";
+    case LARS_JPEG_REASON_SAMPLING: return "unusually sampled";
+    case LARS_JPEG_REASON_DNL: return "DNL";
+    case LARS_JPEG_REASON_SIZE: return "too large";
+    default: return "these";
+    }
+}
+
+static int jd_parse(const char *who, const uint8_t *file, int64_t len, int64_t info[LARS_JPEG_INFO_N])
+{
+    if (!file || len <= 0) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    LARS_TRY(lars_jpeg_info(file, len, info));
+    if (!info[14]) return fail(LARS_ERR_UNSUPPORTED, "%s: %s JPEG files are not supported", who, jd_reason(info[15]));
+    return LARS_OK;
+}
+
+static size_t jd_host_ws_bytes(int64_t len, const int64_t info[LARS_JPEG_INFO_N])
+{
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    return al((size_t)len) + al((size_t)info[0] * info[1] * info[2]) + 256 + lars_jpeg_decode_scratch_bytes(info);
+}
+
+// host file -> the device image: upload, decode, status read back (one sync)
+static int jd_decode_to_device(ThreadCtx *c, const char *who, const uint8_t *file, int64_t len, const int64_t info[LARS_JPEG_INFO_N],
+                               char *ws, uint8_t **d_img_out)
+{
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    char *p = ws;
+    uint8_t *d_file = reinterpret_cast<uint8_t *>(p); p += al((size_t)len);
+    uint8_t *d_img = reinterpret_cast<uint8_t *>(p); p += al((size_t)info[0] * info[1] * info[2]);
+    int32_t *d_st = reinterpret_cast<int32_t *>(p); p += 256;
+    hipStream_t s = c->stream;
+    LARS_HIP_TRY(hipMemcpyAsync(d_file, file, (size_t)len, hipMemcpyHostToDevice, s));
+    LARS_TRY(lars_d_decode_jpeg_u8(d_file, file, info, d_img, d_st, p, s));
+    int st[2] = {0, 0};
+    JdCtl ctl;                                            // the control block opens the scratch: the rounds that decoded anything
+    LARS_HIP_TRY(hipMemcpyAsync(st, d_st, sizeof st, hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipMemcpyAsync(&ctl, p, sizeof ctl, hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipStreamSynchronize(s));
+    if (st[0]) return jd_status_fail(who, st);
+    int rounds = 1;
+    for (int r = 1; r <= JD_ROUNDS; ++r) rounds += ctl.changed[r] != 0;
+    tuning().jpeg_last_rounds = rounds + (ctl.changed[JD_ROUNDS] != 0 ? 100 : 0);
+    *d_img_out = d_img;
+    return LARS_OK;
+}
+
+}  // namespace lars
+
+using namespace lars;
+
+extern "C" {
+
+size_t lars_jpeg_decode_scratch_bytes(const int64_t info[LARS_JPEG_INFO_N])
+{
+    JdLayout L;
+    if (!info || !jd_layout(info, tuning().jpeg_subseq_bits, &L)) return 0;
+    return L.bytes;
+}
+
+int lars_d_decode_jpeg_u8(const uint8_t *file_dev, const uint8_t *head, const int64_t info[LARS_JPEG_INFO_N], uint8_t *out,
+                          int32_t *status_dev, void *scratch, void *stream)
+{
+    static const char *who = "lars_d_decode_jpeg_u8";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!file_dev || !head || !info || !out || !status_dev || !scratch) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    JdLayout L;
+    if (!jd_layout(info, tuning().jpeg_subseq_bits, &L)) return fail(LARS_ERR_INVALID, "%s: info describes no file this decoder takes", who);
+    JpegHeader H;
+    LARS_TRY(jpeg_parse(head, info[12], &H, false));
+    if (!H.supported || H.w != info[0] || H.h != info[1] || H.ncomp != info[2] || H.eoff != info[12] || H.ri != info[11] ||
+        (H.ncomp == 3 && (H.hs[0] != info[5] || H.vs[0] != info[6])))
+        return fail(LARS_ERR_INVALID, "%s: head and info do not describe the same file", who);
+    JdTablesArg A;
+    memset(&A, 0, sizeof A);
+    for (int k = 0; k < H.ncomp; ++k) {
+        memcpy(A.qt[k], H.qt[H.tq[k]], sizeof A.qt[k]);
+        memcpy(A.hcount[k], H.hcount[H.td[k]], 16);
+        memcpy(A.hval[k], H.hval[H.td[k]], 256);
+        memcpy(A.hcount[3 + k], H.hcount[4 + H.ta[k]], 16);
+        memcpy(A.hval[3 + k], H.hval[4 + H.ta[k]], 256);
+    }
+    const JdGeo &g = L.g;
+    char *sc = static_cast<char *>(scratch);
+    JdCtl *ctl = reinterpret_cast<JdCtl *>(sc + L.ctl);
+    JdTables *T = reinterpret_cast<JdTables *>(sc + L.tables);
+    unsigned int *keepcnt = reinterpret_cast<unsigned int *>(sc + L.keepcnt), *markcnt = reinterpret_cast<unsigned int *>(sc + L.markcnt);
+    uint8_t *compact = reinterpret_cast<uint8_t *>(sc + L.compact);
+    jd_u64 *cbyte = reinterpret_cast<jd_u64 *>(sc + L.cbyte);
+    unsigned int *nsubs = reinterpret_cast<unsigned int *>(sc + L.nsubs), *suboff = reinterpret_cast<unsigned int *>(sc + L.suboff);
+    JdSub *subs = reinterpret_cast<JdSub *>(sc + L.subs);
+    jd_u64 *in = reinterpret_cast<jd_u64 *>(sc + L.in), *outs = reinterpret_cast<jd_u64 *>(sc + L.out);
+    unsigned int *cnt = reinterpret_cast<unsigned int *>(sc + L.cnt), *pre = reinterpret_cast<unsigned int *>(sc + L.pre);
+    short *coef = reinterpret_cast<short *>(sc + L.coef);
+    unsigned int *sums = reinterpret_cast<unsigned int *>(sc + L.sums);
+    uint8_t *planes = reinterpret_cast<uint8_t *>(sc + L.planes);
+    const unsigned int *words = reinterpret_cast<const unsigned int *>(compact);
+    const uint8_t *seg = file_dev + info[12];
+    const long long elen = (long long)L.elen;
+    hipStream_t s = pick_stream(c, stream);
+    LARS_HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(JdCtl), s));
+    LARS_HIP_TRY(hipMemsetAsync(&ctl->errkey, 0xFF, sizeof(jd_u64), s));
+    LARS_HIP_TRY(hipMemsetAsync(coef, 0, (size_t)g.nblocks * 128, s));
+    LARS_HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)L.nsub_cap * 4, s));       // the scan of the counts runs over the whole capacity
+    hipLaunchKernelGGL(k_jd_setup, dim3(1), dim3(64), 0, s, A, T);
+    if (L.nwg) {
+        hipLaunchKernelGGL(k_jd_mark, dim3((unsigned)L.nwg), dim3(JD_MARK_THREADS), 0, s, seg, elen, keepcnt, markcnt);
+        hipLaunchKernelGGL(k_jd_exscan, dim3(1), dim3(1024), 0, s, keepcnt, keepcnt, (long long)L.nwg, 0ll, &ctl->kept_total);
+        hipLaunchKernelGGL(k_jd_exscan, dim3(1), dim3(1024), 0, s, markcnt, markcnt, (long long)L.nwg, 0ll, &ctl->mark_total);
+        hipLaunchKernelGGL(k_jd_compact, dim3((unsigned)L.nwg), dim3(JD_MARK_THREADS), 0, s, seg, elen, keepcnt, markcnt, g.nint, compact, cbyte, ctl);
+    }
+    hipLaunchKernelGGL(k_jd_intervals, dim3((g.nint + 255) / 256), dim3(256), 0, s, cbyte, g.nint, L.sbits, nsubs, ctl);
+    hipLaunchKernelGGL(k_jd_exscan, dim3(1), dim3(1024), 0, s, nsubs, suboff, (long long)g.nint, 0ll, &ctl->nsub_total);
+    const unsigned int sgrid = (unsigned int)((L.nsub_cap + 255) / 256);
+    hipLaunchKernelGGL(k_jd_subs, dim3(sgrid), dim3(256), 0, s, cbyte, suboff, g.nint, L.sbits, (unsigned int)L.nsub_cap, subs, ctl);
+    for (int r = 0; r <= JD_ROUNDS; ++r)
+        hipLaunchKernelGGL(k_jd_pass, dim3(sgrid), dim3(256), 0, s, T, words, subs, in, outs, cnt, r, g.bpm, g.ny, ctl);
+    hipLaunchKernelGGL(k_jd_finish, dim3(1), dim3(64), 0, s, T, words, subs, in, outs, cnt, g.bpm, g.ny, ctl);
+    hipLaunchKernelGGL(k_jd_check, dim3(sgrid), dim3(256), 0, s, outs, ctl);
+    hipLaunchKernelGGL(k_jd_exscan, dim3(1), dim3(1024), 0, s, cnt, pre, (long long)L.nsub_cap, 0ll, &ctl->block_total);
+    hipLaunchKernelGGL(k_jd_verify, dim3((g.nint + 255) / 256), dim3(256), 0, s, pre, suboff, g, ctl);
+    hipLaunchKernelGGL(k_jd_write, dim3(sgrid), dim3(256), 0, s, T, words, subs, in, pre, g.bpm, g.ny, g.nblocks, coef, ctl);
+    hipLaunchKernelGGL(k_jd_mcu_sums, dim3((g.nmcu + 255) / 256), dim3(256), 0, s, coef, g, sums, ctl);
+    hipLaunchKernelGGL(k_jd_exscan, dim3((unsigned)g.ncomp), dim3(1024), 0, s, sums, sums, (long long)g.nmcu, (long long)g.nmcu, (unsigned int *)nullptr);
+    hipLaunchKernelGGL(k_jd_idct, dim3((g.pblocks[3] + 31) / 32), dim3(256), 0, s, coef, sums, T, g, planes, ctl);
+    const long long npix = (long long)g.w * g.h;
+    hipLaunchKernelGGL(k_jd_color, dim3((unsigned)std::min<long long>((npix + 255) / 256, 16384)), dim3(256), 0, s, planes, g, out, ctl);
+    LARS_HIP_TRY(hipMemcpyAsync(status_dev, ctl->status, 8, hipMemcpyDeviceToDevice, s));
+    return launch_check(who);
+}
+
+// host file in, host pixels out: one upload, the status, one download
+int lars_h_decode_jpeg_u8(const uint8_t *file, int64_t len, uint8_t *out, size_t out_cap)
+{
+    static const char *who = "lars_h_decode_jpeg_u8";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!out) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    int64_t info[LARS_JPEG_INFO_N];
+    LARS_TRY(jd_parse(who, file, len, info));
+    const size_t bytes = (size_t)info[0] * info[1] * info[2];
+    if (out_cap < bytes) return fail(LARS_ERR_INVALID, "%s: out_cap %zu < %zu", who, out_cap, bytes);
+    LARS_TRY(ws_reserve(c, jd_host_ws_bytes(len, info)));
+    uint8_t *d_img = nullptr;
+    LARS_TRY(jd_decode_to_device(c, who, file, len, info, static_cast<char *>(c->ws), &d_img));
+    LARS_HIP_TRY(hipMemcpyAsync(out, d_img, bytes, hipMemcpyDeviceToHost, c->stream));
+    LARS_HIP_TRY(hipStreamSynchronize(c->stream));
+    return LARS_OK;
+}
+
+// host file in, thumbnail out: the decoded pixels go straight into the thumbnail kernels (resize.hip)
+int lars_h_thumbnail_jpeg_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
+                             int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out)
+{
+    static const char *who = "lars_h_thumbnail_jpeg_u8";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!out || !reduce_box || !box) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    int64_t info[LARS_JPEG_INFO_N];
+    LARS_TRY(jd_parse(who, file, len, info));
+    const int64_t h = info[1], w = info[0];
+    const int ch = (int)info[2];
+    size_t tneed = 0;
+    LARS_TRY(thumbnail_u8_impl(c, nullptr, true, nullptr, &tneed, h, w, ch, fx, fy, reduce_box, box, new_h, new_w, vertical_first, out));
+    const size_t front = (jd_host_ws_bytes(len, info) + 255) & ~(size_t)255;
+    LARS_TRY(ws_reserve(c, front + tneed));
+    uint8_t *d_img = nullptr;
+    LARS_TRY(jd_decode_to_device(c, who, file, len, info, static_cast<char *>(c->ws), &d_img));
+    return thumbnail_u8_impl(c, d_img, true, static_cast<char *>(c->ws) + front, nullptr, h, w, ch, fx, fy, reduce_box, box, new_h,
+                             new_w, vertical_first, out);
+}
+
+}  // extern "C"

@@ -305,6 +305,10 @@ int lars_set_tuning(const char *key, int value)
         if (value != 1 && value != 3 && value != 5) return fail(LARS_ERR_INVALID, "lars_set_tuning: u16_hist_impl is 5, 1 or 3 (got %d)", value);
         t.u16_hist_impl = value;
     }
+    else if (!strcmp(key, "jpeg_subseq_bits")) {
+        if (value < 32 || value > 65536) return fail(LARS_ERR_INVALID, "lars_set_tuning: jpeg_subseq_bits is 32 .. 65536 (got %d)", value);
+        t.jpeg_subseq_bits = value;
+    }
     else return fail(LARS_ERR_INVALID, "lars_set_tuning: unknown key %s", key);
     return LARS_OK;
 }
@@ -324,6 +328,8 @@ int lars_get_tuning(const char *key, int *value)
     else if (!strcmp(key, "out_stride_planes")) *value = t.out_stride_planes;
     else if (!strcmp(key, "u16_hist_impl")) *value = t.u16_hist_impl;
     else if (!strcmp(key, "last_fused_kernel")) *value = t.last_fused_kernel;
+    else if (!strcmp(key, "jpeg_subseq_bits")) *value = t.jpeg_subseq_bits;
+    else if (!strcmp(key, "jpeg_last_rounds")) *value = t.jpeg_last_rounds;
     else return fail(LARS_ERR_INVALID, "lars_get_tuning: unknown key %s", key);
     return LARS_OK;
 }

@@ -309,7 +309,7 @@ def write_tiff(path, array, rows_per_strip=None, tile=None, byteorder="<", plana
     return overflow_at + len(overflow)
 
 
-def read_image(path, full_depth=False, png_decoder="pillow"):
+def read_image(path, full_depth=False, png_decoder="pillow", jpeg_decoder="pillow"):
     """Any raster the pipeline takes -> ``ndarray``.
 
     ``full_depth=False``: ``np.array(PIL.Image.open(path))``, what the reference does (backend-process.py:52) --
@@ -318,11 +318,22 @@ def read_image(path, full_depth=False, png_decoder="pillow"):
     every other file still goes through Pillow.
     ``png_decoder="device"``: a ``.png`` file with the PNG signature whose IHDR ``api.png_info`` calls supported is decoded
     on the GPU (``api.decode_png``, the same array as Pillow's); decided up front, not a fallback: its errors are raised.
+    ``jpeg_decoder="device"``: the same for a ``.jpg`` / ``.jpeg`` file that starts with ``FF D8`` and that ``api.jpeg_info``
+    calls supported (``api.decode_jpeg``); every other file goes to Pillow as before.
     """
     from PIL import Image
     if png_decoder not in ("pillow", "device"):
         raise ValueError(f"png_decoder must be 'pillow' or 'device', got {png_decoder!r}")
+    if jpeg_decoder not in ("pillow", "device"):
+        raise ValueError(f"jpeg_decoder must be 'pillow' or 'device', got {jpeg_decoder!r}")
     p = str(path)
+    if jpeg_decoder == "device" and p.lower().endswith((".jpg", ".jpeg")):
+        from . import api
+        with open(p, "rb") as f:
+            data = f.read()
+        # a file that does not start with SOI is not the decoder's: Pillow opens it by content
+        if data[:2] == b"\xff\xd8" and api.jpeg_info(data)["supported"]:
+            return api.decode_jpeg(data)
     if png_decoder == "device" and p.lower().endswith(".png"):
         from . import api
         with open(p, "rb") as f:

@@ -1,0 +1,392 @@
+"""CPU side of the device JPEG decoder: the NumPy model against the installed Pillow, jpeg_info (lars_jpeg_info, host code),
+argument checks before the library is called, the draft rule, the driver / CLI option, and the sanitizer build replaying
+JPEG files through the marker parser."""
+import ctypes as C
+import io
+import os
+import shutil
+import struct
+import subprocess
+import sys
+from pathlib import Path
+
+import numpy as np
+import pytest
+from PIL import Image
+
+import lars_image_processing_amd as lars
+from lars_image_processing_amd import _ffi, api, driver, tiffio
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+import jpeg_model  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "lars_image_processing_amd", "csrc")
+ASAN_BIN = os.path.join(ROOT, "build", "asan", "lars_host_asan")
+
+
+def _no_device(*_a, **_k):
+    raise AssertionError("the library was called")
+
+
+def jpeg(arr, **save):
+    b = io.BytesIO()
+    (arr if isinstance(arr, Image.Image) else Image.fromarray(arr)).save(b, "JPEG", **save)
+    return b.getvalue()
+
+
+def want(b):
+    return np.asarray(Image.open(io.BytesIO(b)))
+
+
+def picture(kind, h, w, mode, seed=0):
+    """Seeded test content: a smooth field, noise, or one flat colour; [h, w] for L, [h, w, 3] for RGB."""
+    if kind == "noise":
+        a = np.random.default_rng(seed).integers(0, 256, (h, w, 3), dtype=np.uint8)
+    elif kind == "flat":
+        a = np.empty((h, w, 3), np.uint8)
+        a[:] = (200, 90, 30)
+    else:
+        y, x = np.mgrid[0:h, 0:w]
+        a = np.dstack([(y * 5 + x * 3) % 256, (x * 4) % 256, (y * 7) % 256]).astype(np.uint8)
+    return a[:, :, 0].copy() if mode == "L" else a
+
+
+SIZES = [(1, 1), (1, 2), (2, 3), (3, 4), (3, 5), (1, 6), (16, 16), (17, 33), (33, 47), (40, 8)]   # (h, w): widths 1-6, heights 1-3
+SAVES = {
+    "default": {},
+    "444": {"subsampling": 0},
+    "422": {"subsampling": 1},
+    "420": {"subsampling": 2},
+    "q1": {"quality": 1},
+    "q25": {"quality": 25},
+    "q100": {"quality": 100},
+    "optimize": {"optimize": True},
+    "rst blocks": {"restart_marker_blocks": 3},
+    "rst rows": {"restart_marker_rows": 1},
+    "rst 1": {"restart_marker_blocks": 1},
+}
+
+
+def table():
+    """name -> file: the small Pillow-written files every decoder here must reproduce."""
+    out = {}
+    for mode in ("L", "RGB"):
+        for h, w in SIZES:
+            for kind in ("smooth", "noise"):
+                for name, save in SAVES.items():
+                    if mode == "L" and name in ("444", "422", "420"):
+                        continue
+                    if (h, w) not in ((3, 5), (17, 33), (33, 47)) and name not in ("default", "444", "422", "q1"):
+                        continue                            # the full list of options on three sizes, the core ones on all
+                    out[f"{mode} {h}x{w} {kind} {name}"] = jpeg(picture(kind, h, w, mode, seed=h * 100 + w), **save)
+        for name in ("default", "422", "q100", "rst rows", "optimize"):
+            if mode == "L" and name == "422":
+                continue
+            out[f"{mode} 150x301 smooth {name}"] = jpeg(picture("smooth", 150, 301, mode), **SAVES[name])
+    return out
+
+
+TABLE = table()
+
+
+@pytest.mark.parametrize("name", sorted(TABLE))
+def test_model_equals_pillow(name):
+    b = TABLE[name]
+    ref = want(b)
+    got = jpeg_model.decode(b)
+    assert got.dtype == ref.dtype and got.shape == ref.shape
+    assert got.tobytes() == ref.tobytes()
+
+
+def test_model_on_a_quality_1_file_needs_the_wrapping_range_limit():
+    """Quality 1 noise leaves the clamped range: the model (and libjpeg) wrap at 10 bits there; a plain clamp differs."""
+    b = jpeg(picture("noise", 33, 47, "RGB", seed=5), quality=1)
+    assert jpeg_model.decode(b).tobytes() == want(b).tobytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# jpeg_info
+# ---------------------------------------------------------------------------------------------------------------------
+def segments(b):
+    """(marker, offset of the FF, length field) of the segments up to and including SOS."""
+    pos, out = 2, []
+    while True:
+        m = b[pos + 1]
+        (n,) = struct.unpack(">H", b[pos + 2:pos + 4])
+        out.append((m, pos, n))
+        if m == 0xDA:
+            return out
+        pos += 2 + n
+
+
+def find(b, marker):
+    return next((pos, n) for m, pos, n in segments(b) if m == marker)
+
+
+def unsupported_files():
+    rgb = picture("smooth", 24, 40, "RGB")
+    base = jpeg(rgb, subsampling=0)
+    out = {
+        "progressive": (jpeg(rgb, progressive=True), "progressive"),
+        "keep_rgb": (jpeg(rgb, keep_rgb=True), "RGB stored"),
+        "cmyk": (jpeg(Image.fromarray(rgb).convert("CMYK")), "4 components"),
+    }
+    # a second scan after the first one's data: the bytes between SOS and EOI once more
+    sos, n = find(base, 0xDA)
+    assert base[-2:] == b"\xff\xd9"
+    out["two scans"] = (base[:-2] + base[sos:-2] + b"\xff\xd9", "more than one scan")
+    # Y sampled 1 x 2: only the frame header is patched, the reason is decided before the entropy data is looked at
+    sof, n = find(base, 0xC0)
+    patched = bytearray(base)
+    assert patched[sof + 11] == 0x11
+    patched[sof + 11] = 0x12
+    out["1x2 sampling"] = (bytes(patched), "sampling")
+    return out
+
+
+@pytest.mark.parametrize("name", sorted(TABLE)[::7])
+def test_jpeg_info_agrees_with_pillow(monkeypatch, name):
+    monkeypatch.setattr(_ffi, "call", _no_device)
+    b = TABLE[name]
+    im = Image.open(io.BytesIO(b))
+    info = lars.jpeg_info(b)
+    assert info["size"] == im.size and info["mode"] == im.mode
+    assert info["supported"] is True and info["reason"] is None
+    assert info["frame"] == "baseline" and info["precision"] == 8
+    sos, n = find(b, 0xDA)
+    assert info["entropy_offset"] == sos + 2 + n
+    assert info["entropy_offset"] + info["entropy_bytes"] == len(b) - 2          # up to EOI
+    if im.mode == "RGB":
+        assert info["sampling"][0] == {0: (1, 1), 1: (2, 1), 2: (2, 2)}[{"444": 0, "422": 1}.get(name.split()[-1], 2)] or "q100" in name
+    for data in (bytearray(b), memoryview(b), np.frombuffer(b, np.uint8)):
+        assert lars.jpeg_info(data) == info
+
+
+def test_jpeg_info_restart_interval_and_trailing_bytes(monkeypatch):
+    monkeypatch.setattr(_ffi, "call", _no_device)
+    b = jpeg(picture("smooth", 33, 47, "RGB"), restart_marker_blocks=3)
+    info = lars.jpeg_info(b)
+    assert info["restart_interval"] == 3
+    assert lars.jpeg_info(b + b"trailing bytes after EOI") == info
+    # fill bytes before a marker, a comment and an APP segment are skipped
+    dqt, _n = find(b, 0xDB)
+    padded = b[:dqt] + b"\xff\xff\xff" + b"\xff\xfe\x00\x05abc" + b"\xff\xe5\x00\x04xy" + b[dqt:]
+    assert lars.jpeg_info(padded)["supported"]
+    assert jpeg_model.decode(padded).tobytes() == want(b).tobytes()
+
+
+@pytest.mark.parametrize("name", sorted(unsupported_files()))
+def test_unsupported_variants(monkeypatch, name):
+    monkeypatch.setattr(_ffi, "call", _no_device)
+    b, word = unsupported_files()[name]
+    info = lars.jpeg_info(b)
+    assert info["supported"] is False
+    assert word in info["reason"], info["reason"]
+    with pytest.raises(NotImplementedError, match=word):
+        lars.decode_jpeg(b)
+    with pytest.raises(NotImplementedError, match=word):
+        lars.thumbnail_jpeg(b, (8, 8))
+
+
+def damaged_files():
+    b = jpeg(picture("smooth", 24, 40, "RGB"))
+    out = {"empty": b"", "no SOI": b"\x00\x00" + b[2:], "only SOI": b[:2], "a PNG": b"\x89PNG\r\n\x1a\n" + bytes(40)}
+    dqt, n = find(b, 0xDB)
+    bad = bytearray(b)
+    bad[dqt + 2:dqt + 4] = struct.pack(">H", len(b))
+    out["segment length leaves the file"] = bytes(bad)
+    bad = bytearray(b)
+    bad[dqt + 2:dqt + 4] = struct.pack(">H", 1)
+    out["segment length 1"] = bytes(bad)
+    sos, n = find(b, 0xDA)
+    out["missing SOS"] = b[:sos] + b"\xff\xd9"
+    out["cut before SOS"] = b[:sos]
+    out["cut inside SOS"] = b[:sos + 5]
+    sof, n = find(b, 0xC0)
+    out["SOF after SOS"] = b[:sof] + b[sof + 2 + n:sos + 2 + find(b, 0xDA)[1]] + b[sof:sof + 2 + n] + b[sos + 2 + find(b, 0xDA)[1]:]
+    dht, n = find(b, 0xC4)
+    segs = [s for s in segments(b) if s[0] == 0xC4]
+    no_dht = bytearray(b)
+    for _m, pos, n in reversed(segs):
+        del no_dht[pos:pos + 2 + n]
+    out["missing DHT"] = bytes(no_dht)
+    no_dqt = bytearray(b)
+    for _m, pos, n in reversed([s for s in segments(b) if s[0] == 0xDB]):
+        del no_dqt[pos:pos + 2 + n]
+    out["missing DQT"] = bytes(no_dqt)
+    over = bytearray(b)
+    over[dht + 5] = 3                                       # three codes of length 1
+    out["oversubscribed Huffman table"] = bytes(over)
+    return out
+
+
+@pytest.mark.parametrize("case", sorted(damaged_files()))
+def test_structural_damage_raises_before_the_device(monkeypatch, case):
+    monkeypatch.setattr(_ffi, "call", _no_device)
+    data = damaged_files()[case]
+    with pytest.raises(ValueError):
+        lars.jpeg_info(data)
+    with pytest.raises(ValueError):
+        lars.decode_jpeg(data)
+    with pytest.raises(ValueError):
+        lars.thumbnail_jpeg(data)
+
+
+@pytest.mark.parametrize("data", [None, "a string", 12, np.zeros(4, np.uint16), np.zeros((2, 2), np.uint8)])
+def test_bad_arguments_refused_before_the_library(monkeypatch, data):
+    monkeypatch.setattr(_ffi, "call", _no_device)
+    for f in (lars.jpeg_info, lars.decode_jpeg, lars.thumbnail_jpeg):
+        with pytest.raises(TypeError, match="JPEG"):
+            f(data)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the draft rule
+# ---------------------------------------------------------------------------------------------------------------------
+def test_draft_rule_agrees_with_pillow():
+    tiny = {}
+    seen = set()
+    for w in (1, 7, 100, 399, 400, 401, 799, 800, 801, 1599, 1600, 1601, 2048, 3200, 4096, 6400, 6401):
+        for h in (1, 50, 400, 800, 1536, 1600, 2048, 3199, 3200, 4096, 6400):
+            if (w, h) not in tiny:
+                # only the frame header matters to draft(): a one-block file patched to the size
+                b = bytearray(jpeg(np.zeros((8, 8), np.uint8)))
+                sof, _n = find(bytes(b), 0xC0)
+                b[sof + 5:sof + 9] = struct.pack(">HH", h, w)
+                tiny[(w, h)] = bytes(b)
+            for size in ((400, 400), (800, 800), (128, 128), (300, 200)):
+                for gap in (None, 1.0, 2.0, 3.0):
+                    im = Image.open(io.BytesIO(tiny[(w, h)]))
+                    assert im.size == (w, h)
+                    scale = 1
+                    if api.thumbnail_size((w, h), size) is not None and gap is not None:   # Image.thumbnail's own order
+                        im.draft(None, (int(size[0] * gap), int(size[1] * gap)))
+                        scale = im.decoderconfig[0]
+                    assert api.jpeg_draft_scale((w, h), size, gap) == scale, (w, h, size, gap)
+                    seen.add(scale)
+    assert seen == {1, 2, 4, 8}
+    assert api.jpeg_draft_scale((2048, 1536), (800, 800)) == 1          # the gallery file
+    assert api.jpeg_draft_scale((2048, 2048), (400, 400)) == 2
+    assert api.jpeg_draft_scale((4096, 4096), (400, 400)) == 4
+
+
+def test_thumbnail_jpeg_refuses_scaled_decoding_before_the_library(monkeypatch):
+    monkeypatch.setattr(_ffi, "call", _no_device)
+    b = bytearray(jpeg(np.zeros((8, 8), np.uint8)))
+    sof, _n = find(bytes(b), 0xC0)
+    b[sof + 5:sof + 9] = struct.pack(">HH", 2048, 2048)
+    with pytest.raises(NotImplementedError, match="1/2 scale"):
+        lars.thumbnail_jpeg(bytes(b))
+    with pytest.raises(ValueError, match="reducing_gap"):
+        lars.thumbnail_jpeg(TABLE["RGB 33x47 smooth default"], (4, 4), reducing_gap=0.5)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# driver and CLI
+# ---------------------------------------------------------------------------------------------------------------------
+def test_bad_jpeg_decoder_refused_before_the_library(monkeypatch, tmp_path):
+    monkeypatch.setattr(_ffi, "call", _no_device)
+    f = tmp_path / "a.jpg"
+    f.write_bytes(TABLE["RGB 33x47 smooth default"])
+    with pytest.raises(ValueError, match="jpeg_decoder"):
+        tiffio.read_image(f, jpeg_decoder="gpu")
+    with pytest.raises(ValueError, match="jpeg_decoder"):
+        driver.process_image(f, tmp_path / "out", jpeg_decoder="torch")
+    with pytest.raises(ValueError, match="jpeg_decoder"):
+        driver.batch_process(tmp_path, tmp_path / "out", jpeg_decoder=None, verbose=False)
+    # the default stays Pillow, and an unsupported JPEG goes to Pillow even with the device decoder
+    assert np.array_equal(tiffio.read_image(f), np.array(Image.open(f)))
+    g = tmp_path / "b.jpeg"
+    g.write_bytes(unsupported_files()["progressive"][0])
+    assert np.array_equal(tiffio.read_image(g, jpeg_decoder="device"), np.array(Image.open(g)))
+
+
+def test_a_non_jpeg_file_named_jpg_stays_with_pillow(monkeypatch, tmp_path):
+    monkeypatch.setattr(_ffi, "call", _no_device)
+    f = tmp_path / "picture.jpg"
+    Image.fromarray(np.zeros((8, 8, 3), np.uint8)).save(f, "PNG")
+    assert np.array_equal(tiffio.read_image(f, jpeg_decoder="device"), np.array(Image.open(f)))
+
+
+def test_a_supported_jpeg_goes_to_the_decoder(monkeypatch, tmp_path):
+    calls = []
+    monkeypatch.setattr(api, "decode_jpeg", lambda data: calls.append(len(data)) or "decoded")
+    f = tmp_path / "a.JPG"
+    f.write_bytes(TABLE["RGB 33x47 smooth default"])
+    assert tiffio.read_image(f, jpeg_decoder="device") == "decoded"
+    assert calls == [len(TABLE["RGB 33x47 smooth default"])]
+
+
+def test_cli_offers_the_jpeg_decoder(capsys):
+    with pytest.raises(SystemExit):
+        driver.main(["--help"])
+    assert "--jpeg-decoder" in capsys.readouterr().out
+
+
+def test_new_functions_are_exported():
+    for name in ("decode_jpeg", "jpeg_info", "thumbnail_jpeg", "jpeg_draft_scale"):
+        assert getattr(lars, name) is getattr(api, name)
+        assert name in api.__all__
+
+
+def test_tuning_key_bounds():
+    lib = _ffi.load()
+    v = C.c_int(0)
+    assert lib.lars_get_tuning(b"jpeg_subseq_bits", C.byref(v)) == 0 and 32 <= v.value <= 65536
+    default = v.value
+    assert lib.lars_set_tuning(b"jpeg_subseq_bits", 31) != 0      # below the longest code plus its extra bits
+    assert lib.lars_set_tuning(b"jpeg_subseq_bits", 65537) != 0
+    assert lib.lars_set_tuning(b"jpeg_subseq_bits", 32) == 0
+    assert lib.lars_get_tuning(b"jpeg_subseq_bits", C.byref(v)) == 0 and v.value == 32
+    assert lib.lars_set_tuning(b"jpeg_subseq_bits", default) == 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the sanitizer build (same skip rules as test_asan_cpu.py)
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def asan_bin():
+    if _ffi.device_count() > 0:
+        pytest.skip("sanitizer target is for the build container, not the GPU box")
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    subprocess.check_call(["make", "-C", CSRC, "asan"], stdout=subprocess.DEVNULL)
+    return ASAN_BIN
+
+
+def fnv(data):
+    h = 1469598103934665603
+    for byte in bytes(data):
+        h = ((h ^ byte) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
+    return h
+
+
+def lib_jpeg_info(b):
+    arr = np.frombuffer(bytes(b) + b"\0", dtype=np.uint8)
+    info = (C.c_int64 * 16)()
+    rc = _ffi.load().lars_jpeg_info(_ffi.ptr(arr), len(b), info)
+    return rc, fnv(bytes(info)) if rc == 0 else 0
+
+
+def test_sanitizer_replays_jpeg_files(asan_bin, tmp_path):
+    files = list(TABLE.values())[::5] + [b for b, _w in unsupported_files().values()] + list(damaged_files().values())
+    cases = []
+    for b in files:
+        cases.append(b)
+        cases += [b[:cut] for cut in range(0, len(b), 97)]    # truncated at every 97th byte
+    path = tmp_path / "cases.bin"
+    with open(path, "wb") as f:
+        for b in cases:
+            f.write(struct.pack("<4I", 4, 0, 0, len(b)) + b)
+    run = subprocess.run([asan_bin, str(path)], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-3000:]
+    assert "ERROR" not in run.stderr and "runtime error" not in run.stderr, run.stderr[-3000:]
+    lines = run.stdout.splitlines()
+    assert lines[-1] == f"done {len(cases)} cases"
+    ok = 0
+    for line, b in zip(lines, cases):
+        rc, h = lib_jpeg_info(b)
+        assert line.split(" ", 1)[1] == f"jpeg rc={rc} h={h:016x}", line
+        ok += rc == 0
+    assert ok >= len(files) - len(damaged_files())
