@@ -2,8 +2,8 @@
 //
 // Reference: load_image_from_db (process-images.py:181-193) and backend-process.py:52 open every stored picture with
 // Image.open(...) and np.array(img) or img.thumbnail(...): libjpeg on one host core.  Here the file goes up once and the
-// pixels (or only the thumbnail, lars_h_thumbnail_jpeg_u8) come back.  The pixel arithmetic is libjpeg's JDCT_ISLOW with
-// fancy upsampling, integer for integer, so the array is the one Pillow returns.
+// pixels (or only the thumbnail, lars_h_thumbnail_jpeg_u8) come back.  The pixel arithmetic is libjpeg-turbo's JDCT_ISLOW
+// (the SIMD code's narrowing, see jd_idct8) with fancy upsampling, integer for integer, so the array is the one Pillow returns.
 //
 // The Huffman scan is serial by nature.  It is cut into subsequences of S bits ("jpeg_subseq_bits"), one lane each, and
 // the decoder states at their borders are found by iteration; a border counts only once it equals what the exact chain
@@ -33,7 +33,8 @@
 //   k_jd_mcu_sums   DC differences per MCU and component; their scan gives DC = prefix(MCU) - prefix(interval start) +
 //                   the differences inside the MCU (unsigned arithmetic: the wrap cancels).
 //   k_jd_idct       eight lanes per block: dequantise, column pass, row pass (workspace in LDS, padded against bank
-//                   conflicts), libjpeg's range limit, 8 bytes per lane into the component plane.
+//                   conflicts), narrowing by saturation as libjpeg-turbo's SIMD code does it, 8 bytes per lane into the
+//                   component plane.
 //   k_jd_color      one thread per pixel: fancy (triangle) upsampling of Cb / Cr where the chroma plane is wider than
 //                   two samples, replication else, YCbCr -> RGB in 16-bit fixed point, [h][w][3] or [h][w].
 // Every loop is bounded by the length of the data, every index is checked against its buffer; an error is a status code
@@ -530,41 +531,38 @@ __global__ void k_jd_mcu_sums(const short *coef, JdGeo g, unsigned int *sums, co
 #define JD_F_2_562915447 20995
 #define JD_F_3_072711026 25172
 
-// one 8-point pass of jidctint.c's jpeg_idct_islow: x in, x out, descale by sh with rounding
+__device__ inline int jd_wrap16(int v) { return (int)(short)v; }
+__device__ inline int jd_sat16(int v) { return min(32767, max(-32768, v)); }
+
+// One 8-point pass of the slow-integer IDCT, x in, x out, in the arithmetic of libjpeg-turbo's SIMD jsimd_idct_islow
+// (what Pillow runs; SSE2 and AVX2 give the same).  Inside the 10-bit window around the sample centre this is
+// jidctint.c's jpeg_idct_islow bit for bit; outside it the SIMD code is its own rule: the inputs are 16-bit lanes, so
+// the sums formed before a multiplication (x0 +- x4, x7 + x3, x5 + x1) wrap at 16 bits; every rotation is one
+// multiply-add with the constants folded; 32-bit sums wrap (unsigned here); the descaled result saturates to 16 bits.
 template <int SH>
 __device__ inline void jd_idct8(int x[8])
 {
-    int z1 = (x[2] + x[6]) * JD_F_0_541196100;
-    const int t2 = z1 + x[6] * (-JD_F_1_847759065), t3 = z1 + x[2] * JD_F_0_765366865;
-    const int t0 = (int)((unsigned int)(x[0] + x[4]) << 13), t1 = (int)((unsigned int)(x[0] - x[4]) << 13);
-    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    int a0 = x[7], a1 = x[5], a2 = x[3], a3 = x[1];
-    z1 = a0 + a3;
-    int z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3;
-    const int z5 = (z3 + z4) * JD_F_1_175875602;
-    a0 *= JD_F_0_298631336;
-    a1 *= JD_F_2_053119869;
-    a2 *= JD_F_3_072711026;
-    a3 *= JD_F_1_501321110;
-    z1 *= -JD_F_0_899976223;
-    z2 *= -JD_F_2_562915447;
-    z3 *= -JD_F_1_961570560;
-    z4 *= -JD_F_0_390180644;
-    z3 += z5;
-    z4 += z5;
-    a0 += z1 + z3;
-    a1 += z2 + z4;
-    a2 += z2 + z3;
-    a3 += z1 + z4;
-    const int half = 1 << (SH - 1);
-    x[0] = (t10 + a3 + half) >> SH;
-    x[7] = (t10 - a3 + half) >> SH;
-    x[1] = (t11 + a2 + half) >> SH;
-    x[6] = (t11 - a2 + half) >> SH;
-    x[2] = (t12 + a1 + half) >> SH;
-    x[5] = (t12 - a1 + half) >> SH;
-    x[3] = (t13 + a0 + half) >> SH;
-    x[4] = (t13 - a0 + half) >> SH;
+    typedef unsigned int u;
+    const u t2 = (u)(x[2] * JD_F_0_541196100) + (u)(x[6] * (JD_F_0_541196100 - JD_F_1_847759065));
+    const u t3 = (u)(x[2] * (JD_F_0_541196100 + JD_F_0_765366865)) + (u)(x[6] * JD_F_0_541196100);
+    const u t0 = (u)jd_wrap16(x[0] + x[4]) << 13, t1 = (u)jd_wrap16(x[0] - x[4]) << 13;
+    const u t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    const int s3 = jd_wrap16(x[7] + x[3]), s4 = jd_wrap16(x[5] + x[1]);
+    const u z3 = (u)(s3 * (JD_F_1_175875602 - JD_F_1_961570560)) + (u)(s4 * JD_F_1_175875602);
+    const u z4 = (u)(s3 * JD_F_1_175875602) + (u)(s4 * (JD_F_1_175875602 - JD_F_0_390180644));
+    const u a0 = (u)(x[7] * (JD_F_0_298631336 - JD_F_0_899976223)) + (u)(x[1] * -JD_F_0_899976223) + z3;
+    const u a1 = (u)(x[5] * (JD_F_2_053119869 - JD_F_2_562915447)) + (u)(x[3] * -JD_F_2_562915447) + z4;
+    const u a2 = (u)(x[5] * -JD_F_2_562915447) + (u)(x[3] * (JD_F_3_072711026 - JD_F_2_562915447)) + z3;
+    const u a3 = (u)(x[7] * -JD_F_0_899976223) + (u)(x[1] * (JD_F_1_501321110 - JD_F_0_899976223)) + z4;
+    const u half = 1u << (SH - 1);
+    x[0] = jd_sat16((int)(t10 + a3 + half) >> SH);
+    x[7] = jd_sat16((int)(t10 - a3 + half) >> SH);
+    x[1] = jd_sat16((int)(t11 + a2 + half) >> SH);
+    x[6] = jd_sat16((int)(t11 - a2 + half) >> SH);
+    x[2] = jd_sat16((int)(t12 + a1 + half) >> SH);
+    x[5] = jd_sat16((int)(t12 - a1 + half) >> SH);
+    x[3] = jd_sat16((int)(t13 + a0 + half) >> SH);
+    x[4] = jd_sat16((int)(t13 - a0 + half) >> SH);
 }
 
 #define JD_WS_STRIDE 72                   // words per block in LDS: 64 + 8, so that the blocks of a wave start on different banks
@@ -583,6 +581,7 @@ __global__ __launch_bounds__(256) void k_jd_idct(const short *coef, const unsign
     int comp = 0, bx = 0, by = 0;
     int *w = ws + (threadIdx.x >> 3) * JD_WS_STRIDE;
     int x[8];
+    bool ac_row = false;
     if (live) {
         comp = pb >= g.pblocks[2] ? 2 : pb >= g.pblocks[1] ? 1 : 0;
         const unsigned int local = pb - g.pblocks[comp];
@@ -608,12 +607,22 @@ __global__ __launch_bounds__(256) void k_jd_idct(const short *coef, const unsign
             else dc += (unsigned int)(int)mc[inner * 64];
             x[0] = (int)(short)dc;
         }
-        for (int i = 0; i < 8; ++i) w[r * 8 + i] = x[i] * qt[comp][r * 8 + i];
+        for (int i = 0; i < 8; ++i) {
+            ac_row = ac_row || (r > 0 && x[i] != 0);
+            w[r * 8 + i] = jd_wrap16(x[i] * qt[comp][r * 8 + i]);   // the product keeps its low 16 bits
+        }
     }
+    // a block whose rows 1-7 are all zero takes the SIMD code's short cut in the column pass: DC * 4, wrapping at 16 bits
+    const bool dc_only = ((__ballot(ac_row) >> (threadIdx.x & 56)) & 0xFFull) == 0;
     __syncthreads();
     if (live) {
         for (int i = 0; i < 8; ++i) x[i] = w[i * 8 + r];  // column r
-        jd_idct8<11>(x);
+        if (dc_only) {
+            const int v = jd_wrap16((int)((unsigned int)x[0] << 2));
+            for (int i = 0; i < 8; ++i) x[i] = v;
+        } else {
+            jd_idct8<11>(x);
+        }
     }
     __syncthreads();
     if (live) for (int i = 0; i < 8; ++i) w[i * 8 + r] = x[i];
@@ -623,9 +632,7 @@ __global__ __launch_bounds__(256) void k_jd_idct(const short *coef, const unsign
         jd_idct8<18>(x);
         unsigned int lo = 0, hi = 0;
         for (int i = 0; i < 8; ++i) {
-            int v = x[i] & 1023;                          // libjpeg's range-limit table: 10 bits, signed, centred on 128
-            if (v >= 512) v -= 1024;
-            v = min(255, max(0, v + 128));
+            const int v = min(127, max(-128, x[i])) + 128;  // packed with signed saturation to 8 bits, then centred
             if (i < 4) lo |= (unsigned int)v << (8 * i); else hi |= (unsigned int)v << (8 * (i - 4));
         }
         uint8_t *dst = planes + g.poff[comp] + (size_t)(by * 8 + r) * g.pw[comp] + bx * 8;   // plane widths are multiples of 8

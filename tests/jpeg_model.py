@@ -1,7 +1,7 @@
 """NumPy / pure-Python model of the baseline JPEG decoder the device code is written against (helper, not collected).
 
-``decode(file)`` restates libjpeg's ``JDCT_ISLOW`` path with fancy upsampling -- what Pillow returns at full scale -- with a
-plain sequential entropy decoder in front: one bit reader, one restart interval after the other.  It is as strict as
+``decode(file)`` restates libjpeg-turbo's ``JDCT_ISLOW`` path (its SIMD arithmetic, see ``idct_blocks``) with fancy upsampling
+-- what Pillow returns at full scale -- with a plain sequential entropy decoder in front: one bit reader, one restart interval after the other.  It is as strict as
 ``lars.decode_jpeg``: entropy data that ends early, a bit pattern that is no code, a coefficient index past 63, a restart
 marker that is missing or out of sequence and a block count that is not the frame's raise ``ValueError``.
 ``test_jpeg_decode_cpu.py`` pins it to the installed Pillow bit for bit; the GPU tests use it to confirm that their damaged
@@ -113,12 +113,11 @@ def decode_interval(data, tables, nblocks_mcu, coefs, first_block):
     """Blocks of one restart interval into ``coefs`` (DC as the difference); returns how many it held.  A symbol that
     would cross the end of the interval is the padding of its last byte: decoding stops there."""
     nbits = len(data) * 8
-    big = int.from_bytes(data + b"\0\0\0\0", "big")
-    total = nbits + 32
+    buf = data + b"\0\0\0\0\0"
     pos, b, k, blk = 0, 0, 0, first_block
     while pos < nbits:
         tab = tables[b][0 if k == 0 else 1]
-        window = (big >> (total - pos - 32)) & 0xFFFFFFFF
+        window = (int.from_bytes(buf[pos >> 3:(pos >> 3) + 5], "big") >> (8 - (pos & 7))) & 0xFFFFFFFF
         sym = None
         for ln in range(1, 17):
             sym = tab.get((ln, window >> (32 - ln)))
@@ -164,34 +163,50 @@ FIX = {name: int(round(x * 8192)) for name, x in dict(
     f1_501=1.501321110, f1_847=1.847759065, f1_961=1.961570560, f2_053=2.053119869, f2_562=2.562915447, f3_072=3.072711026).items()}
 
 
+def wrap(x, bits):
+    """Two's-complement wrap of an integer array to ``bits`` bits."""
+    half = 1 << (bits - 1)
+    return ((x + half) & ((1 << bits) - 1)) - half
+
+
 def idct_pass(x, shift):
-    """One 8-point pass of jidctint.c over the second-to-last axis of ``x`` ([..., 8, n])."""
+    """One 8-point pass of the slow-integer IDCT over the second-to-last axis of ``x`` ([..., 8, n]) in the arithmetic of
+    libjpeg-turbo's SIMD code: inputs are 16-bit lanes, so the four sums that are formed before a multiplication
+    (x0 + x4, x0 - x4, x7 + x3, x5 + x1) wrap at 16 bits; each rotation is one multiply-add with the constants folded,
+    exact in 32 bits; the 32-bit sums wrap; the descaled result is packed with signed saturation to 16 bits."""
     F = FIX
     x0, x1, x2, x3, x4, x5, x6, x7 = (x[..., i, :] for i in range(8))
-    z1 = (x2 + x6) * F["f0_541"]
-    t2 = z1 + x6 * -F["f1_847"]
-    t3 = z1 + x2 * F["f0_765"]
-    t0 = (x0 + x4) << 13
-    t1 = (x0 - x4) << 13
+    t2 = x2 * F["f0_541"] + x6 * (F["f0_541"] - F["f1_847"])
+    t3 = x2 * (F["f0_541"] + F["f0_765"]) + x6 * F["f0_541"]
+    t0 = wrap(x0 + x4, 16) << 13
+    t1 = wrap(x0 - x4, 16) << 13
     t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
-    a0, a1, a2, a3 = x7, x5, x3, x1
-    z1, z2, z3, z4 = a0 + a3, a1 + a2, a0 + a2, a1 + a3
-    z5 = (z3 + z4) * F["f1_175"]
-    a0, a1, a2, a3 = a0 * F["f0_298"], a1 * F["f2_053"], a2 * F["f3_072"], a3 * F["f1_501"]
-    z1, z2, z3, z4 = z1 * -F["f0_899"], z2 * -F["f2_562"], z3 * -F["f1_961"] + z5, z4 * -F["f0_390"] + z5
-    a0, a1, a2, a3 = a0 + z1 + z3, a1 + z2 + z4, a2 + z2 + z3, a3 + z1 + z4
+    z3, z4 = wrap(x7 + x3, 16), wrap(x5 + x1, 16)
+    z3, z4 = z3 * (F["f1_175"] - F["f1_961"]) + z4 * F["f1_175"], z3 * F["f1_175"] + z4 * (F["f1_175"] - F["f0_390"])
+    a0 = x7 * (F["f0_298"] - F["f0_899"]) + x1 * -F["f0_899"] + z3
+    a1 = x5 * (F["f2_053"] - F["f2_562"]) + x3 * -F["f2_562"] + z4
+    a2 = x5 * -F["f2_562"] + x3 * (F["f3_072"] - F["f2_562"]) + z3
+    a3 = x7 * -F["f0_899"] + x1 * (F["f1_501"] - F["f0_899"]) + z4
     half = 1 << (shift - 1)
     rows = [t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3]
-    return np.stack([(r + half) >> shift for r in rows], axis=-2)
+    return np.stack([np.clip(wrap(r + half, 32) >> shift, -32768, 32767) for r in rows], axis=-2)
 
 
-def idct_blocks(c):
-    """Dequantised coefficients [n, 8, 8] (int64) -> samples [n, 8, 8] through libjpeg's range-limit table."""
-    ws = idct_pass(c, 11)                                    # columns
+def idct_blocks(coef, quant):
+    """Coefficients [n, 8, 8] and their quantisation table [8, 8] -> samples [n, 8, 8] as libjpeg-turbo's SIMD
+    ``jsimd_idct_islow`` gives them (SSE2 and AVX2 alike), which is what Pillow's wheels run.  Inside the 10-bit window
+    around the sample centre it is libjpeg's C code (jidctint.c) bit for bit; outside, where the C code wraps through its
+    range-limit table, the SIMD code narrows by saturation: the product of coefficient and quantiser keeps its low 16
+    bits; a block whose coefficients of rows 1-7 are all zero (row 0 may hold AC terms) takes a short cut in the column
+    pass, row 0 * 4 wrapping at 16 bits; every other column result saturates at 16 bits; the row results saturate to 16
+    and then to 8 bits."""
+    x = wrap(coef * quant, 16)
+    dc_only = (coef[:, 1:, :] == 0).all(axis=(1, 2))         # the coefficients, not the products: a quantiser may be 0
+    ws = idct_pass(x, 11)                                    # columns
+    short = np.broadcast_to(wrap(x[:, :1, :] << 2, 16), x.shape)
+    ws = np.where(dc_only[:, None, None], short, ws)
     out = idct_pass(ws.swapaxes(-1, -2), 18).swapaxes(-1, -2)   # rows
-    v = out & 1023
-    v = np.where(v < 512, v, v - 1024)                      # the table wraps at 10 bits: not a plain clamp
-    return np.clip(v + 128, 0, 255)
+    return np.clip(out, -128, 127) + 128
 
 
 def upsample(P, w, h, hf, vf):
@@ -259,13 +274,14 @@ def decode(d):
             idx = [b for b in range(bpm) if owner[b] == ci]
             seg = coefs[i:i + per, idx, 0]
             coefs[i:i + per, idx, 0] = np.cumsum(seg.reshape(-1)).reshape(seg.shape)
+    coefs = wrap(coefs, 16)                                  # a coefficient is stored in 16 bits, the running DC too
     planes, b0 = [], 0
     for ci, (_cid, ch, cv, tq) in enumerate(comps):
         if tq not in q:
             raise ValueError("missing quantisation table")
-        blocks = coefs[:, b0:b0 + ch * cv] * np.array(q[tq], np.int64)
+        blocks = coefs[:, b0:b0 + ch * cv]
         b0 += ch * cv
-        px = idct_blocks(blocks.reshape(-1, 8, 8)).reshape(mh, mw, cv, ch, 8, 8)
+        px = idct_blocks(blocks.reshape(-1, 8, 8), np.array(q[tq], np.int64).reshape(8, 8)).reshape(mh, mw, cv, ch, 8, 8)
         planes.append(px.transpose(0, 2, 4, 1, 3, 5).reshape(mh * cv * 8, mw * ch * 8))
     if len(comps) == 1:
         return planes[0][:h, :w].astype(np.uint8)

@@ -1,5 +1,4 @@
 """decode_jpeg / thumbnail_jpeg / jpeg_decoder="device" on the GPU: every array equals Pillow's, byte for byte."""
-import ctypes as C
 import io
 import sys
 import threading
@@ -14,29 +13,10 @@ from lars_image_processing_amd import _ffi, api, driver, tiffio
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import jpeg_model  # noqa: E402
+from jpeg_gpu_common import device_entry_point_with_guards, get_bits, same, subseq_bits  # noqa: E402,F401
 from test_jpeg_decode_cpu import TABLE, find, jpeg, picture, want  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def same(b):
-    got, ref = lars.decode_jpeg(b), want(b)
-    assert got.dtype == ref.dtype and got.shape == ref.shape, (got.dtype, got.shape, ref.dtype, ref.shape)
-    assert got.tobytes() == ref.tobytes()
-
-
-def get_bits():
-    v = C.c_int(0)
-    _ffi.call("lars_get_tuning", b"jpeg_subseq_bits", C.byref(v))
-    return v.value
-
-
-@pytest.fixture
-def subseq_bits():
-    """Sets "jpeg_subseq_bits" for a test and puts the default back afterwards."""
-    default = get_bits()
-    yield lambda v: _ffi.call("lars_set_tuning", b"jpeg_subseq_bits", int(v))
-    _ffi.call("lars_set_tuning", b"jpeg_subseq_bits", default)
 
 
 def one_over_f(h, w, channels, seed):
@@ -108,36 +88,7 @@ def test_a_stream_that_never_synchronises_by_itself(subseq_bits):
 
 def test_device_entry_point_on_a_callers_stream_with_guards():
     b = jpeg(one_over_f(301, 517, 3, seed=4), restart_marker_blocks=7)
-    ref = want(b)
-    info = (C.c_int64 * 16)()
-    file = np.frombuffer(b, np.uint8)
-    assert _ffi.load().lars_jpeg_info(_ffi.ptr(file), file.size, info) == 0
-    need = _ffi.load().lars_jpeg_decode_scratch_bytes(info)
-    assert need > 0
-    guard, nbytes = 4096, ref.size
-    d_file, d_out, d_scratch, d_status, stream = (C.c_void_p() for _ in range(5))
-    _ffi.call("lars_malloc", C.byref(d_file), file.size)
-    _ffi.call("lars_malloc", C.byref(d_out), nbytes + 2 * guard)
-    _ffi.call("lars_malloc", C.byref(d_scratch), need)
-    _ffi.call("lars_malloc", C.byref(d_status), 8)
-    _ffi.call("lars_stream_create", C.byref(stream))
-    try:
-        _ffi.call("lars_memcpy_h2d", d_file, _ffi.ptr(file), file.size)
-        _ffi.call("lars_memset", d_out, 0xA5, nbytes + 2 * guard, stream)
-        head = np.ascontiguousarray(file[:info[12]])       # only the head stays on the host
-        _ffi.call("lars_d_decode_jpeg_u8", d_file, _ffi.ptr(head), info, C.c_void_p(d_out.value + guard), d_status, d_scratch, stream)
-        _ffi.call("lars_synchronize", stream)
-        got = np.empty(nbytes + 2 * guard, np.uint8)
-        status = np.empty(2, np.int32)
-        _ffi.call("lars_memcpy_d2h", _ffi.ptr(got), d_out, got.size)
-        _ffi.call("lars_memcpy_d2h", _ffi.ptr(status), d_status, 8)
-    finally:
-        _ffi.call("lars_stream_destroy", stream)
-        for p in (d_file, d_out, d_scratch, d_status):
-            _ffi.call("lars_free", p)
-    assert status.tolist() == [0, 0]
-    assert (got[:guard] == 0xA5).all() and (got[-guard:] == 0xA5).all()
-    assert got[guard:-guard].tobytes() == ref.tobytes()
+    device_entry_point_with_guards(b, want(b))
 
 
 @pytest.mark.parametrize("mode", ["L", "RGB"])
