@@ -562,6 +562,29 @@ int lars_h_decode_jpeg_u8(const uint8_t *file, int64_t len, uint8_t *out, size_t
 int lars_h_thumbnail_jpeg_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
                              int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out);
 
+/* Baseline JPEG files of 8-bit pictures, built on the device -- the Image.fromarray(corrected).save(save_path) that ends the
+ * camera path (process-rgn.py:47 with :72-73; process-ndvi.py:114 reads the file back) and the img.save(buffer, format=img.format)
+ * of an upload (process-images.py:247).  img is uint8 [h][w][channels]: 1 (L, one component) or 3 (RGB, stored as YCbCr);
+ * quality 1..100; subsampling 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0, Pillow's numbers (one channel: the data do not depend on it,
+ * the sampling byte of the frame header does, as in Pillow's files); 1 <= h, w <= 65500 and h * w * channels < 2^31.  The file is byte for byte what Pillow on libjpeg-turbo writes with these arguments and its other
+ * defaults: JFIF 1.01 header, the annex K tables scaled by the quality, the standard Huffman tables, one interleaved scan,
+ * no restart markers.
+ * lars_jpeg_bound: the largest file any picture of that shape can give at any quality (0 for a shape that cannot be
+ * encoded): every block at its longest code per coefficient, every byte of that stuffed.  Pure host code.
+ * lars_jpeg_header: pure host code.  The file's bytes up to and including SOS into out; returns their number, 0 (and the
+ * error message set) for bad arguments or an out_cap that is too small (640 always suffices).
+ * lars_jpeg_encode_scratch_bytes: device scratch of lars_d_encode_jpeg_u8 (0 for a shape that cannot be encoded).
+ * lars_d_encode_jpeg_u8: device img / out (out_cap >= lars_jpeg_bound) / scratch; enqueues on stream and writes the file's
+ * length to the device int64 *out_len_dev (0: a buffer overflowed, which the bound rules out).
+ * lars_h_encode_jpeg_u8: host img / out; one upload, then the length, then out_len bytes into out. */
+size_t lars_jpeg_bound(int64_t h, int64_t w, int channels, int subsampling);
+int64_t lars_jpeg_header(int64_t h, int64_t w, int channels, int subsampling, int quality, uint8_t *out, size_t out_cap);
+size_t lars_jpeg_encode_scratch_bytes(int64_t h, int64_t w, int channels, int subsampling);
+int lars_d_encode_jpeg_u8(const uint8_t *img, int64_t h, int64_t w, int channels, int quality, int subsampling, uint8_t *out,
+                          size_t out_cap, int64_t *out_len_dev, void *scratch, void *stream);
+int lars_h_encode_jpeg_u8(const uint8_t *img, int64_t h, int64_t w, int channels, int quality, int subsampling, uint8_t *out,
+                          size_t out_cap, int64_t *out_len);
+
 /* ------------------------------------------------------------------ image files (host only, no GPU work) */
 /* TIFF 6.0 LZW (compression 5, MSB-first codes, early width change) of one strip / tile: decodes at most ndst bytes
  * into dst, *nout = bytes produced.  For lars_image_processing_amd/tiffio.py, which reads the multi-sample 16-bit

@@ -20,6 +20,7 @@ from .api import (  # noqa: F401
     colormap_lut,
     correct_white_balance,
     decode_jpeg,
+    encode_jpeg,
     decode_png,
     encode_png,
     download_processed_images,

@@ -162,6 +162,11 @@ SIGNATURES = {
     "lars_d_decode_jpeg_u8": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "lars_h_decode_jpeg_u8": (_I, [_P, _I64, _P, _SZ]),
     "lars_h_thumbnail_jpeg_u8": (_I, [_P, _I64, _I, _I, C.POINTER(_I), C.POINTER(_F), _I64, _I64, _I, _P]),
+    "lars_jpeg_bound": (_SZ, [_I64, _I64, _I, _I]),
+    "lars_jpeg_header": (_I64, [_I64, _I64, _I, _I, _I, _P, _SZ]),
+    "lars_jpeg_encode_scratch_bytes": (_SZ, [_I64, _I64, _I, _I]),
+    "lars_d_encode_jpeg_u8": (_I, [_P, _I64, _I64, _I, _I, _I, _P, _SZ, _P, _P, _P]),
+    "lars_h_encode_jpeg_u8": (_I, [_P, _I64, _I64, _I, _I, _I, _P, _SZ, C.POINTER(_I64)]),
     "lars_comm_available": (_I, []),
     "lars_comm_unique_id": (_I, [_P]),
     "lars_comm_init": (_I, [C.POINTER(_P), _I, _I, _P]),

@@ -20,6 +20,7 @@ this module                     reference
 ``encode_png``                  backend-process.py:70, process-images.py:567-617 (``Image.fromarray(x).save(png)``: same pixels)
 ``decode_png``                  process-images.py:181-193 (``np.array(Image.open(io.BytesIO(img_bytes)))``: same array)
 ``thumbnail_png``               process-images.py:186-189 from the file's bytes (decode + thumbnail, pixels stay on the GPU)
+``encode_jpeg``                 process-rgn.py:47 with :72-73, process-images.py:247 (``img.save(f, "JPEG")``: the same file, byte for byte)
 ``decode_jpeg``                 process-images.py:181-193, backend-process.py:52 for JPEG files (same array as Pillow's)
 ``thumbnail_jpeg``              process-images.py:186-189 from a JPEG file's bytes, where ``draft`` keeps full scale
 ``align_images``                process-images.py:515  (phase correlation + shift)
@@ -60,7 +61,7 @@ __all__ = [
     "calculate_index", "calculate_ndvi", "analyze_index", "analyze_index_statistics",
     "analyze_ndvi_statistics", "index_histogram", "classification_mask", "colorize_index", "process_image",
     "timeseries_row", "colormap_lut", "preprocess_large_image", "thumbnail", "thumbnail_plan", "encode_png",
-    "png_info", "decode_png", "thumbnail_png", "jpeg_info", "decode_jpeg", "thumbnail_jpeg", "jpeg_draft_scale", "align_images", "change_detection",
+    "png_info", "decode_png", "thumbnail_png", "jpeg_info", "decode_jpeg", "encode_jpeg", "thumbnail_jpeg", "jpeg_draft_scale", "align_images", "change_detection",
     "colorize_difference", "calculate_index_statistics_by_timeframe", "time_series_points",
     "calculate_ndvi_array", "generate_ndvi_report", "download_processed_images",
     "create_index_visualization", "create_comparison_view", "create_time_series_plot", "create_change_detection_visualization",
@@ -312,14 +313,23 @@ def fix_white_balance(img_array):
 correct_white_balance = fix_white_balance
 
 
-def fix_white_balance_rgnir(image_path, save_path=None):
-    """process-rgn.py:4-49: file in; array out, or file out when ``save_path`` is given."""
+def fix_white_balance_rgnir(image_path, save_path=None, jpeg_encoder="pillow"):
+    """process-rgn.py:4-49: file in; array out, or file out when ``save_path`` is given.
+
+    ``jpeg_encoder="device"`` writes a ``save_path`` ending in ``.jpg`` / ``.jpeg`` with ``encode_jpeg`` (the GPU): byte
+    for byte the file Pillow would have written.  Every other file, and the default, go through Pillow."""
     from PIL import Image
+    if jpeg_encoder not in ("pillow", "device"):
+        raise ValueError(f"jpeg_encoder must be 'pillow' or 'device', got {jpeg_encoder!r}")
     arr = _as_image(np.array(Image.open(image_path)), "fix_white_balance_rgnir")
     corrected = _wb_array(arr, variant=1)
     corrected = np.ascontiguousarray(corrected[:, :, :3])        # np.dstack of three planes (:41)
     if save_path:
-        Image.fromarray(corrected).save(save_path)
+        if jpeg_encoder == "device" and os.fspath(save_path).lower().endswith((".jpg", ".jpeg")):
+            with open(save_path, "wb") as f:
+                f.write(encode_jpeg(corrected))
+        else:
+            Image.fromarray(corrected).save(save_path)
         return None
     return corrected
 
@@ -559,6 +569,56 @@ def encode_png(array, palette=None):
     out = np.empty(png_bound(h, w, c), dtype=np.uint8)
     n = C.c_int64(0)
     _ffi.call("lars_h_encode_png_u8", _ffi.ptr(arr), h, w, c, _ffi.ptr(pal), npal, _ffi.ptr(out), out.nbytes, C.byref(n))
+    return out[:n.value].tobytes()
+
+
+# ---------------------------------------------------------------------------
+# JPEG files built on the device
+# ---------------------------------------------------------------------------
+_JPEG_SUBSAMPLING = {"4:4:4": 0, "4:2:2": 1, "4:2:0": 2, 0: 0, 1: 1, 2: 2}
+
+
+def jpeg_bound(h, w, channels, subsampling=2):
+    """The largest file ``encode_jpeg`` can return for an ``h x w`` picture of ``channels`` samples at any quality
+    (``lars_jpeg_bound``; host code, no device needed); 0 for a shape that cannot be encoded."""
+    return int(_ffi.load().lars_jpeg_bound(int(h), int(w), int(channels), int(subsampling)))
+
+
+def encode_jpeg(array, quality=75, subsampling="4:2:0"):
+    """Baseline JPEG file (``bytes``) of a uint8 picture, encoded on the GPU: ``[H, W]`` (mode L) or ``[H, W, 3]`` (RGB, stored
+    as YCbCr).  ``quality`` 1 to 100; ``subsampling`` ``"4:4:4"``, ``"4:2:2"``, ``"4:2:0"`` or Pillow's 0, 1, 2 (for
+    ``[H, W]`` the data do not depend on it; as in Pillow's files, one byte of the frame header does).  1 <= H, W <= 65500 and fewer than 2^31 samples.
+
+    The bytes are exactly those of ``Image.fromarray(array).save(f, "JPEG", quality=quality, subsampling=subsampling)`` with
+    Pillow on libjpeg-turbo: what ends the camera path (process-rgn.py:47 with :72-73) and an upload kept in its own format
+    (process-images.py:247).  ``optimize``, progressive files, restart intervals and metadata are not covered.
+    """
+    arr = np.asarray(array)
+    if arr.dtype != np.uint8:
+        raise TypeError(f"encode_jpeg: uint8 pictures only, got {arr.dtype}")
+    if arr.ndim == 3 and arr.shape[2] == 1:
+        arr = arr[:, :, 0]
+    if arr.ndim == 3 and arr.shape[2] == 4:
+        raise TypeError("encode_jpeg: cannot write mode RGBA as JPEG")
+    if arr.ndim not in (2, 3) or (arr.ndim == 3 and arr.shape[2] != 3):
+        raise ValueError(f"encode_jpeg: shape [H, W] or [H, W, 3] expected, got {arr.shape}")
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)):
+        raise TypeError(f"encode_jpeg: quality must be an int, got {quality!r}")
+    if not 1 <= quality <= 100:
+        raise ValueError(f"encode_jpeg: quality 1 to 100, got {quality}")
+    if isinstance(subsampling, bool) or not isinstance(subsampling, (str, int)) or subsampling not in _JPEG_SUBSAMPLING:
+        raise ValueError(f"encode_jpeg: subsampling '4:4:4', '4:2:2', '4:2:0' or 0, 1, 2, got {subsampling!r}")
+    h, w = arr.shape[:2]
+    c = 1 if arr.ndim == 2 else 3
+    if not (1 <= h <= 65500 and 1 <= w <= 65500):
+        raise ValueError(f"encode_jpeg: {h} x {w} picture (1 to 65500 on each side)")
+    if h * w * c >= 1 << 31:
+        raise ValueError(f"encode_jpeg: {h} x {w} x {c} samples (fewer than 2^31)")
+    sub = _JPEG_SUBSAMPLING[subsampling]
+    arr = np.ascontiguousarray(arr)
+    out = np.empty(jpeg_bound(h, w, c, sub), dtype=np.uint8)
+    n = C.c_int64(0)
+    _ffi.call("lars_h_encode_jpeg_u8", _ffi.ptr(arr), h, w, c, int(quality), sub, _ffi.ptr(out), out.nbytes, C.byref(n))
     return out[:n.value].tobytes()
 
 

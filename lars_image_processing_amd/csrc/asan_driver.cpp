@@ -7,6 +7,7 @@
 //   kind 2  lars_stats_merge over nbytes / sizeof(lars_stats) records (a = how many to pass; 0 must be refused)
 //   kind 3  lars_png_info over a PNG file = bytes, with an IDAT table of a entries
 //   kind 4  lars_jpeg_info over a JPEG file = bytes
+//   kind 5  lars_jpeg_header and lars_jpeg_bound: bytes = int32 { h, w, channels, subsampling, quality }, out of a bytes
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -73,6 +74,15 @@ int main(int argc, char **argv)
             int64_t info[LARS_JPEG_INFO_N];
             const int rc = lars_jpeg_info(src, nbytes, info);
             printf("%ld jpeg rc=%d h=%016llx\n", ncase, rc, rc == 0 ? fnv(info, sizeof info) : 0ull);
+        } else if (kind == 5) {
+            int v[5];
+            if (nbytes != sizeof v) { fprintf(stderr, "bad header case\n"); return 2; }
+            memcpy(v, src, sizeof v);
+            unsigned char *dst = static_cast<unsigned char *>(malloc(a ? a : 1));
+            const long long n = lars_jpeg_header(v[0], v[1], v[2], v[3], v[4], dst, a);
+            printf("%ld jpeghead n=%lld h=%016llx bound=%zu\n", ncase, n, n > 0 ? fnv(dst, (size_t)n) : 0ull,
+                   lars_jpeg_bound(v[0], v[1], v[2], v[3]));
+            free(dst);
         } else {
             fprintf(stderr, "unknown case kind %u\n", kind);
             return 2;
