@@ -493,12 +493,24 @@ int lars_h_process_image_png(const void *img, int64_t h, int64_t w, int channels
  * bit depth, colour type, interlace, channels, IDAT payload bytes, IDAT chunks, APNG, supported }; idat_table (may be NULL
  * with idat_cap 0) receives { payload offset, payload length } of the first idat_cap IDAT chunks.
  * lars_png_decode_scratch_bytes: device scratch of lars_d_decode_png_u8 (0 for a shape it cannot decode).
- * lars_d_decode_png_u8: device file / idat_table (info[7] pairs, as lars_png_info gave them) / out (h * w * channels bytes)
+ * lars_d_decode_png_u8: device file / idat_table (info[LARS_PNG_INFO_IDAT_COUNT] pairs, as lars_png_info gave them) / out (h * w * channels bytes)
  * / scratch; enqueues on stream and writes { LARS_PNGD_* status, detail } to the device int32 status_dev[2].
  * lars_h_decode_png_u8: host file in, host pixels out (out_cap >= h * w * channels); one upload, one download.
  * lars_h_thumbnail_png_u8: host file in (modes L, RGB, RGBA), lars_h_thumbnail_u8's plan numbers, host thumbnail out; the
  * decoded pixels never leave the device. */
 #define LARS_PNG_INFO_N 10
+enum {                           /* positions in lars_png_info's info[] */
+    LARS_PNG_INFO_WIDTH = 0,
+    LARS_PNG_INFO_HEIGHT = 1,
+    LARS_PNG_INFO_BIT_DEPTH = 2,
+    LARS_PNG_INFO_COLOR_TYPE = 3,
+    LARS_PNG_INFO_INTERLACE = 4,
+    LARS_PNG_INFO_CHANNELS = 5,
+    LARS_PNG_INFO_IDAT_BYTES = 6,
+    LARS_PNG_INFO_IDAT_COUNT = 7,
+    LARS_PNG_INFO_APNG = 8,
+    LARS_PNG_INFO_SUPPORTED = 9
+};
 enum {
     LARS_PNGD_OK = 0,
     LARS_PNGD_CRC = 1,           /* detail: IDAT chunk index */
@@ -527,13 +539,28 @@ int lars_h_thumbnail_png_u8(const uint8_t *file, int64_t len, int fx, int fy, co
  * info[LARS_JPEG_INFO_N] = { width, height, components, frame marker (0xC0 ...), precision, h0, v0, h1, v1, h2, v2 (sampling),
  * restart interval, entropy segment offset, entropy segment length, supported, LARS_JPEG_REASON_* }.
  * lars_jpeg_decode_scratch_bytes: device scratch of lars_d_decode_jpeg_u8 for that info (0 for what it cannot decode).
- * lars_d_decode_jpeg_u8: file_dev = the whole file on the device, head = its first info[12] bytes on the HOST (the tables are
+ * lars_d_decode_jpeg_u8: file_dev = the whole file on the device, head = its first info[LARS_JPEG_INFO_ENTROPY_OFFSET] bytes on the HOST (the tables are
  * read from there before the call returns), info as lars_jpeg_info gave it, out = h * w * components bytes on the device;
  * enqueues on stream and writes { LARS_JPGD_* status, detail } to the device int32 status_dev[2].
  * lars_h_decode_jpeg_u8: host file in, host pixels out (out_cap >= h * w * components); one upload, one download.
  * lars_h_thumbnail_jpeg_u8: host file in, lars_h_thumbnail_u8's plan numbers, host thumbnail out; the decoded pixels
  * never leave the device.  The decoder runs at full scale: the caller checks that Pillow's draft() would too. */
 #define LARS_JPEG_INFO_N 16
+#define LARS_JPEG_INFO_SAMPLING_STRIDE 2   /* component c: info[LARS_JPEG_INFO_H0 + 2 c], info[LARS_JPEG_INFO_V0 + 2 c], c = 0, 1, 2 */
+enum {                           /* positions in lars_jpeg_info's info[] */
+    LARS_JPEG_INFO_WIDTH = 0,
+    LARS_JPEG_INFO_HEIGHT = 1,
+    LARS_JPEG_INFO_COMPONENTS = 2,
+    LARS_JPEG_INFO_FRAME = 3,
+    LARS_JPEG_INFO_PRECISION = 4,
+    LARS_JPEG_INFO_H0 = 5,
+    LARS_JPEG_INFO_V0 = 6,
+    LARS_JPEG_INFO_RESTART_INTERVAL = 11,
+    LARS_JPEG_INFO_ENTROPY_OFFSET = 12,
+    LARS_JPEG_INFO_ENTROPY_BYTES = 13,
+    LARS_JPEG_INFO_SUPPORTED = 14,
+    LARS_JPEG_INFO_REASON = 15
+};
 enum {
     LARS_JPEG_REASON_NONE = 0,
     LARS_JPEG_REASON_PROGRESSIVE = 1,  /* SOF2 */

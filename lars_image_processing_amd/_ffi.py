@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
+from typing import NamedTuple
 
 import numpy as np
 
@@ -62,6 +63,54 @@ class FusedArgs(C.Structure):
         ("out_rgba", C.c_void_p * 3), ("cmap_lut", C.c_void_p * 3),
         ("stats", C.c_void_p), ("stream", C.c_void_p),
     ]
+
+
+class PngInfo(NamedTuple):
+    """``info[LARS_PNG_INFO_N]`` of ``lars_png_info``: the field order is the header's ``LARS_PNG_INFO_*`` (tests/test_abi_cpu.py).
+    ``PngInfo(*info)`` names a filled array, ``PngInfo.array()`` makes an empty one."""
+    width: int
+    height: int
+    bit_depth: int
+    color_type: int
+    interlace: int
+    channels: int
+    idat_bytes: int
+    idat_count: int
+    apng: int
+    supported: int
+
+    @classmethod
+    def array(cls):
+        return (C.c_int64 * len(cls._fields))()
+
+
+class JpegInfo(NamedTuple):
+    """``info[LARS_JPEG_INFO_N]`` of ``lars_jpeg_info``, in the order of the header's ``LARS_JPEG_INFO_*``; ``h0, v0 .. h2, v2``
+    are the sampling factors of the components."""
+    width: int
+    height: int
+    components: int
+    frame: int
+    precision: int
+    h0: int
+    v0: int
+    h1: int
+    v1: int
+    h2: int
+    v2: int
+    restart_interval: int
+    entropy_offset: int
+    entropy_bytes: int
+    supported: int
+    reason: int
+
+    @classmethod
+    def array(cls):
+        return (C.c_int64 * len(cls._fields))()
+
+    @property
+    def sampling(self):
+        return ((self.h0, self.v0), (self.h1, self.v1), (self.h2, self.v2))
 
 
 # name -> (restype, argtypes).  Every symbol include/lars_hip.h declares.

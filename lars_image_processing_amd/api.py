@@ -532,6 +532,14 @@ def colorize_index(index_array, index_type):
 _PNG_CHANNELS = (1, 3, 4)
 
 
+def _uint8_picture(array, who):
+    """What ``encode_png`` and ``encode_jpeg`` open with: the array, uint8 or refused, ``[H, W, 1]`` taken as ``[H, W]``."""
+    arr = np.asarray(array)
+    if arr.dtype != np.uint8:
+        raise TypeError(f"{who}: uint8 pictures only, got {arr.dtype}")
+    return arr[:, :, 0] if arr.ndim == 3 and arr.shape[2] == 1 else arr
+
+
 def png_bound(h, w, channels):
     """The largest file ``encode_png`` can return for an ``h x w`` picture of ``channels`` samples (``lars_png_bound``;
     host code, no device needed)."""
@@ -546,11 +554,7 @@ def encode_png(array, palette=None):
     compressed bytes are not zlib's.  The same input always gives the same bytes.  What ``Image.fromarray(array).save(f,
     "PNG")`` does at the end of every index picture (backend-process.py:70) and ZIP entry (process-images.py:567-617).
     """
-    arr = np.asarray(array)
-    if arr.dtype != np.uint8:
-        raise TypeError(f"encode_png: uint8 pictures only, got {arr.dtype}")
-    if arr.ndim == 3 and arr.shape[2] == 1:
-        arr = arr[:, :, 0]
+    arr = _uint8_picture(array, "encode_png")
     if arr.ndim not in (2, 3) or (arr.ndim == 3 and arr.shape[2] not in _PNG_CHANNELS):
         raise ValueError(f"encode_png: shape [H, W], [H, W, 3] or [H, W, 4] expected, got {arr.shape}")
     h, w = arr.shape[:2]
@@ -593,11 +597,7 @@ def encode_jpeg(array, quality=75, subsampling="4:2:0"):
     Pillow on libjpeg-turbo: what ends the camera path (process-rgn.py:47 with :72-73) and an upload kept in its own format
     (process-images.py:247).  ``optimize``, progressive files, restart intervals and metadata are not covered.
     """
-    arr = np.asarray(array)
-    if arr.dtype != np.uint8:
-        raise TypeError(f"encode_jpeg: uint8 pictures only, got {arr.dtype}")
-    if arr.ndim == 3 and arr.shape[2] == 1:
-        arr = arr[:, :, 0]
+    arr = _uint8_picture(array, "encode_jpeg")
     if arr.ndim == 3 and arr.shape[2] == 4:
         raise TypeError("encode_jpeg: cannot write mode RGBA as JPEG")
     if arr.ndim not in (2, 3) or (arr.ndim == 3 and arr.shape[2] != 3):
@@ -625,29 +625,48 @@ def encode_jpeg(array, quality=75, subsampling="4:2:0"):
 # ---------------------------------------------------------------------------
 # PNG files decoded on the device
 # ---------------------------------------------------------------------------
-_PNG_INFO_N = 10
 # Pillow's PngImagePlugin._MODES: (bit depth, colour type) -> mode
 _PNG_MODES = {(1, 0): "1", (2, 0): "L", (4, 0): "L", (8, 0): "L", (16, 0): "I;16", (8, 2): "RGB", (16, 2): "RGB",
               (1, 3): "P", (2, 3): "P", (4, 3): "P", (8, 3): "P", (8, 4): "LA", (16, 4): "RGBA", (8, 6): "RGBA",
               (16, 6): "RGBA"}
 
 
-def _png_bytes(data, who):
+def _file_bytes(data, who, fmt):
+    """The bytes of a whole ``fmt`` ("PNG", "JPEG") file as a contiguous 1-D uint8 array."""
     if isinstance(data, (bytes, bytearray, memoryview)):
         arr = np.frombuffer(data, dtype=np.uint8)
     elif isinstance(data, np.ndarray) and data.dtype == np.uint8 and data.ndim == 1:
         arr = data
     else:
-        raise TypeError(f"{who}: a whole {'JPEG' if 'jpeg' in who else 'PNG'} file as bytes, bytearray, memoryview or 1-D uint8 array expected, got {type(data).__name__}")
+        raise TypeError(f"{who}: a whole {fmt} file as bytes, bytearray, memoryview or 1-D uint8 array expected, got {type(data).__name__}")
     return np.ascontiguousarray(arr)
+
+
+def _file_call(name, *args):
+    """``_ffi.call`` of a decoder: LARS_ERR_INVALID there speaks of the file's contents and becomes ``ValueError``."""
+    try:
+        _ffi.call(name, *args)
+    except _ffi.LarsError as e:
+        if e.code == -1:
+            raise ValueError(str(e)) from None
+        raise
+
+
+def _file_thumbnail(name, arr, plan, c):
+    """The call both ``thumbnail_png`` and ``thumbnail_jpeg`` end in: ``plan`` applied to the decoded file on the device."""
+    new_w, new_h = plan.size
+    out = np.empty((new_h, new_w) if c == 1 else (new_h, new_w, c), dtype=np.uint8)
+    _file_call(name, _ffi.ptr(arr), arr.size, plan.factor[0], plan.factor[1], (C.c_int * 4)(*plan.reduce_box),
+               (C.c_float * 4)(*plan.box), new_h, new_w, int(plan.vertical_first), _ffi.ptr(out))
+    return out
 
 
 def _png_info(arr):
     lib = _ffi.load()
-    info = (C.c_int64 * _PNG_INFO_N)()
+    info = _ffi.PngInfo.array()
     if lib.lars_png_info(_ffi.ptr(arr), arr.size, info, None, 0) != 0:
         raise ValueError(lib.lars_last_error().decode("utf-8", "replace"))
-    return list(info)
+    return _ffi.PngInfo(*info)
 
 
 def png_info(data):
@@ -658,28 +677,21 @@ def png_info(data):
     Raises ``ValueError`` for structural damage: bad signature, missing or misplaced IHDR / IDAT / IEND, a chunk running
     past the end of the file, a bad CRC in a chunk other than IDAT (IDAT CRCs are checked where they are gathered).
     """
-    w, h, depth, ctype, interlace, channels, idat_bytes, _nidat, _apng, supported = _png_info(_png_bytes(data, "png_info"))
-    return {"width": w, "height": h, "bit_depth": depth, "color_type": ctype, "interlace": interlace,
-            "mode": _PNG_MODES[(depth, ctype)], "channels": channels, "idat_bytes": idat_bytes, "supported": bool(supported)}
+    i = _png_info(_file_bytes(data, "png_info", "PNG"))
+    return {"width": i.width, "height": i.height, "bit_depth": i.bit_depth, "color_type": i.color_type, "interlace": i.interlace,
+            "mode": _PNG_MODES[(i.bit_depth, i.color_type)], "channels": i.channels, "idat_bytes": i.idat_bytes,
+            "supported": bool(i.supported)}
 
 
 def _png_check(arr, who):
-    w, h, depth, ctype, interlace, channels, _b, _n, apng, supported = _png_info(arr)
-    if not supported:
-        what = "APNG" if apng else "interlaced" if interlace else f"bit depth {depth}"
+    i = _png_info(arr)
+    w, h, ctype, channels = i.width, i.height, i.color_type, i.channels
+    if not i.supported:
+        what = "APNG" if i.apng else "interlaced" if i.interlace else f"bit depth {i.bit_depth}"
         raise NotImplementedError(f"{who}: {what} PNG files are not supported (8-bit, non-interlaced only)")
     if not (1 <= h <= 1 << 24 and 1 <= w <= 1 << 24) or h * (1 + w * channels) > (1 << 31) - 1:
         raise ValueError(f"{who}: {w} x {h} picture of {channels} channels is too large")
     return h, w, ctype, channels
-
-
-def _png_call(name, *args):
-    try:
-        _ffi.call(name, *args)
-    except _ffi.LarsError as e:
-        if e.code == -1:                                  # LARS_ERR_INVALID: the file's contents
-            raise ValueError(str(e)) from None
-        raise
 
 
 def decode_png(data):
@@ -694,10 +706,10 @@ def decode_png(data):
     compressed size -- so the Adler-32 over the whole stream cannot be formed, and that trailer is not checked.  Limits: 1 <= h, w <= 2^24 and
     ``h * (1 + w * channels) < 2^31``.  No CPU fallback.
     """
-    arr = _png_bytes(data, "decode_png")
+    arr = _file_bytes(data, "decode_png", "PNG")
     h, w, _ctype, c = _png_check(arr, "decode_png")
     out = np.empty((h, w) if c == 1 else (h, w, c), dtype=np.uint8)
-    _png_call("lars_h_decode_png_u8", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
+    _file_call("lars_h_decode_png_u8", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
     return out
 
 
@@ -707,37 +719,34 @@ def thumbnail_png(data, size=(400, 400), reducing_gap=2.0):
     thumbnail kernels, only the thumbnail comes back.  Modes L, RGB and RGBA; others raise ``TypeError`` as ``thumbnail``
     does.  ``draft`` does nothing for PNG, so ``thumbnail_plan(..., draft_box=None)`` is the whole plan; a file that
     already fits comes back as ``decode_png`` gives it.  Errors of the file as ``decode_png``."""
-    arr = _png_bytes(data, "thumbnail_png")
+    arr = _file_bytes(data, "thumbnail_png", "PNG")
     h, w, ctype, c = _png_check(arr, "thumbnail_png")
     if ctype not in (0, 2, 6):
         raise TypeError(f"thumbnail_png: PNG files in mode L, RGB or RGBA (got mode {_PNG_MODES[(8, ctype)]!r})")
     plan = thumbnail_plan((w, h), size, reducing_gap, None, None, rgba=c == 4)
     if plan is None:
         return decode_png(arr)
-    new_w, new_h = plan.size
-    out = np.empty((new_h, new_w) if c == 1 else (new_h, new_w, c), dtype=np.uint8)
-    _png_call("lars_h_thumbnail_png_u8", _ffi.ptr(arr), arr.size, plan.factor[0], plan.factor[1],
-              (C.c_int * 4)(*plan.reduce_box), (C.c_float * 4)(*plan.box), new_h, new_w, int(plan.vertical_first),
-              _ffi.ptr(out))
-    return out
+    return _file_thumbnail("lars_h_thumbnail_png_u8", arr, plan, c)
 
 
 # ---------------------------------------------------------------------------
 # JPEG files decoded on the device
 # ---------------------------------------------------------------------------
-_JPEG_INFO_N = 16
-_JPEG_REASONS = {0: None, 1: "progressive (SOF2)", 2: "lossless, arithmetic-coded or hierarchical frame", 3: "precision other than 8 bit",
-                 4: "more than one scan", 5: "2 or 4 components (CMYK / YCCK)", 6: "RGB stored as such (no YCbCr transform)",
-                 7: "sampling other than 4:4:4, 4:2:2 or 4:2:0", 8: "DNL marker", 9: "h * w * channels >= 2^31"}
+# why a file is not decoded, by the header's LARS_JPEG_REASON_* names, in the order of their values (tests/test_abi_cpu.py)
+_JPEG_REASONS = {"NONE": None, "PROGRESSIVE": "progressive (SOF2)", "FRAME": "lossless, arithmetic-coded or hierarchical frame",
+                 "PRECISION": "precision other than 8 bit", "SCANS": "more than one scan", "COMPONENTS": "2 or 4 components (CMYK / YCCK)",
+                 "COLORSPACE": "RGB stored as such (no YCbCr transform)", "SAMPLING": "sampling other than 4:4:4, 4:2:2 or 4:2:0",
+                 "DNL": "DNL marker", "SIZE": "h * w * channels >= 2^31"}
+_JPEG_REASON_TEXT = dict(enumerate(_JPEG_REASONS.values()))
 _JPEG_FRAMES = {0xC0: "baseline", 0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless"}
 
 
 def _jpeg_info(arr):
     lib = _ffi.load()
-    info = (C.c_int64 * _JPEG_INFO_N)()
+    info = _ffi.JpegInfo.array()
     if lib.lars_jpeg_info(_ffi.ptr(arr), arr.size, info) != 0:
         raise ValueError(lib.lars_last_error().decode("utf-8", "replace"))
-    return list(info)
+    return _ffi.JpegInfo(*info)
 
 
 def jpeg_info(data):
@@ -749,20 +758,20 @@ def jpeg_info(data):
     Raises ``ValueError`` for structural damage: no SOI, a segment length that leaves the file, no SOS, SOS before the frame
     header, a missing quantisation or Huffman table, an oversubscribed Huffman table.
     """
-    i = _jpeg_info(_png_bytes(data, "jpeg_info"))
-    w, h, nc = i[0], i[1], i[2]
+    i = _jpeg_info(_file_bytes(data, "jpeg_info", "JPEG"))
+    w, h, nc = i.width, i.height, i.components
     return {"size": (w, h), "width": w, "height": h, "components": nc, "mode": {1: "L", 3: "RGB", 4: "CMYK"}.get(nc),
-            "frame": _JPEG_FRAMES.get(i[3], f"SOF{i[3] - 0xC0}"), "precision": i[4],
-            "sampling": tuple((i[5 + 2 * c], i[6 + 2 * c]) for c in range(min(nc, 3))), "restart_interval": i[11],
-            "entropy_offset": i[12], "entropy_bytes": i[13], "supported": bool(i[14]), "reason": _JPEG_REASONS.get(i[15], str(i[15]))}
+            "frame": _JPEG_FRAMES.get(i.frame, f"SOF{i.frame - 0xC0}"), "precision": i.precision,
+            "sampling": i.sampling[:min(nc, 3)], "restart_interval": i.restart_interval, "entropy_offset": i.entropy_offset,
+            "entropy_bytes": i.entropy_bytes, "supported": bool(i.supported), "reason": _JPEG_REASON_TEXT.get(i.reason, str(i.reason))}
 
 
 def _jpeg_check(arr, who):
     i = _jpeg_info(arr)
-    if not i[14]:
-        raise NotImplementedError(f"{who}: JPEG files with {_JPEG_REASONS.get(i[15], i[15])} are not supported "
+    if not i.supported:
+        raise NotImplementedError(f"{who}: JPEG files with {_JPEG_REASON_TEXT.get(i.reason, i.reason)} are not supported "
                                   "(baseline / extended sequential, 8 bit, one scan, L or YCbCr at 4:4:4, 4:2:2, 4:2:0)")
-    return i[1], i[0], i[2]
+    return i.height, i.width, i.components
 
 
 def decode_jpeg(data):
@@ -776,10 +785,10 @@ def decode_jpeg(data):
     ``ValueError`` saying what is wrong.  Stricter than Pillow on purpose: entropy data that ends early, an invalid code, a
     coefficient past 63 and a missing or misnumbered restart marker are errors.  No CPU fallback.
     """
-    arr = _png_bytes(data, "decode_jpeg")
+    arr = _file_bytes(data, "decode_jpeg", "JPEG")
     h, w, c = _jpeg_check(arr, "decode_jpeg")
     out = np.empty((h, w) if c == 1 else (h, w, c), dtype=np.uint8)
-    _png_call("lars_h_decode_jpeg_u8", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
+    _file_call("lars_h_decode_jpeg_u8", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
     return out
 
 
@@ -790,7 +799,7 @@ def thumbnail_jpeg(data, size=(400, 400), reducing_gap=2.0):
     1/2, 1/4 or 1/8 scale; this decoder works at full scale only, so where ``jpeg_draft_scale`` is above 1 (both sides of
     the image at least twice ``size * reducing_gap``) it raises ``NotImplementedError``.  A file that already fits comes
     back as ``decode_jpeg`` gives it.  Errors of the file as ``decode_jpeg``."""
-    arr = _png_bytes(data, "thumbnail_jpeg")
+    arr = _file_bytes(data, "thumbnail_jpeg", "JPEG")
     h, w, c = _jpeg_check(arr, "thumbnail_jpeg")
     if reducing_gap is not None and reducing_gap < 1.0 and thumbnail_size((w, h), size) is not None:
         raise ValueError("reducing_gap must be 1.0 or greater")
@@ -801,12 +810,7 @@ def thumbnail_jpeg(data, size=(400, 400), reducing_gap=2.0):
     plan = thumbnail_plan((w, h), size, reducing_gap, None, None)
     if plan is None:
         return decode_jpeg(arr)
-    new_w, new_h = plan.size
-    out = np.empty((new_h, new_w) if c == 1 else (new_h, new_w, c), dtype=np.uint8)
-    _png_call("lars_h_thumbnail_jpeg_u8", _ffi.ptr(arr), arr.size, plan.factor[0], plan.factor[1],
-              (C.c_int * 4)(*plan.reduce_box), (C.c_float * 4)(*plan.box), new_h, new_w, int(plan.vertical_first),
-              _ffi.ptr(out))
-    return out
+    return _file_thumbnail("lars_h_thumbnail_jpeg_u8", arr, plan, c)
 
 
 def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_arrays=True, want_hist=False,

@@ -33,10 +33,36 @@ struct ThreadCtx {
 int ensure_ctx(ThreadCtx **out);                 // initialises device 0 on first use
 int ws_reserve(ThreadCtx *c, size_t bytes);      // grow-only; synchronises when it grows
 int scratch_reserve(ThreadCtx *c, size_t bytes);
-// resize.hip: lars_h_thumbnail_u8 on a host or device image (need_out: only the workspace size)
-int thumbnail_u8_impl(ThreadCtx *c, const uint8_t *img, bool on_device, char *ws, size_t *need_out, int64_t h, int64_t w,
-                      int channels, int fx, int fy, const int reduce_box[4], const float box[4], int64_t new_h, int64_t new_w,
-                      int vertical_first, uint8_t *out);
+
+// One allocation cut into buffers.  take<T>(count) gives the next 256-byte aligned stretch of count elements; on a null
+// base it only counts.  A plan (a function that lists the buffers of an area once) therefore runs twice: on Carver(nullptr)
+// for the size, on the area for the pointers.
+struct Carver {
+    char *base;
+    size_t off = 0;
+    explicit Carver(void *b) : base(static_cast<char *>(b)) {}
+    template <typename T>
+    T *take(size_t count)
+    {
+        off = (off + 255) & ~(size_t)255;
+        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+        off += count * sizeof(T);
+        return p;
+    }
+    size_t bytes() const { return (off + 255) & ~(size_t)255; }   // the 256-byte aligned end
+};
+
+// plan(Carver &) on the calling thread's workspace: sized on a null carver, reserved, then pointed
+template <typename Plan>
+int ws_plan(ThreadCtx *c, Plan &&plan)
+{
+    Carver size(nullptr);
+    plan(size);
+    LARS_TRY(ws_reserve(c, size.bytes() + 256));
+    Carver cv(c->ws);
+    plan(cv);
+    return LARS_OK;
+}
 inline hipStream_t pick_stream(ThreadCtx *c, void *stream) {
     return stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;
 }

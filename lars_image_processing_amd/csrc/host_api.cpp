@@ -11,20 +11,6 @@ using namespace lars;
 
 namespace {
 
-struct Carver {
-    char *base;
-    size_t off = 0;
-    explicit Carver(void *b) : base(static_cast<char *>(b)) {}
-    template <typename T>
-    T *take(size_t count)
-    {
-        off = (off + 255) & ~(size_t)255;
-        T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
 struct ImageJob {
     const void *img;
     int64_t h, w;
@@ -53,7 +39,6 @@ struct Layout {
     uint8_t *png[3], *pal[3];      // PNG files of the index pictures, palettes of the P pictures
     int64_t *png_len; char *png_scratch;
     size_t png_bound;
-    size_t total;
 };
 
 // Medians of uint8 RGNir images come from the two-level select on recomputed values (select_q.hip): two passes over the
@@ -74,9 +59,8 @@ bool recompute_route(const ImageJob &j)
     return true;
 }
 
-Layout plan(const ImageJob &j, void *base)
+Layout plan(const ImageJob &j, Carver &c)
 {
-    Carver c(base);
     Layout L;
     const size_t npix = (size_t)j.h * j.w;
     const size_t esz = j.dtype == LARS_U8 ? 1 : 2;
@@ -109,7 +93,6 @@ Layout plan(const ImageJob &j, void *base)
     L.sel = c.take<char>(3 * ((lars_select_scratch_bytes() + 255) & ~(size_t)255));
     L.pairs = select ? c.take<float>(4) : nullptr;
     L.selq = select ? c.take<char>(lars_quotient_median_scratch_bytes(1)) : nullptr;
-    L.total = c.off + 256;
     return L;
 }
 
@@ -123,9 +106,8 @@ int run_image(const ImageJob &j)
     if (j.mask & ~LARS_MASK_ALL) return fail(LARS_ERR_INVALID, "unknown index bits in mask");
     const size_t npix = (size_t)j.h * j.w;
     const size_t esz = j.dtype == LARS_U8 ? 1 : 2;
-    Layout L = plan(j, nullptr);
-    LARS_TRY(ws_reserve(c, L.total));
-    L = plan(j, c->ws);
+    Layout L;
+    LARS_TRY(ws_plan(c, [&](Carver &cv) { L = plan(j, cv); }));
     hipStream_t s = c->stream;
 
     LARS_HIP_TRY(hipMemcpyAsync(L.img, j.img, npix * j.channels * esz, hipMemcpyHostToDevice, s));
@@ -232,15 +214,17 @@ static int analyze_impl(const T *x, int64_t n, T thr, int want_hist, lars_stats 
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (!x || n <= 0 || !out) return fail(LARS_ERR_INVALID, "lars_h_analyze: bad arguments");
-    Carver cv(nullptr);
-    cv.take<T>(n); cv.take<lars_stats>(1); cv.take<T>(2); cv.take<double>(1); cv.take<char>(lars_select_scratch_bytes());
-    LARS_TRY(ws_reserve(c, cv.off + 256));
-    Carver d(c->ws);
-    T *dx = d.take<T>(n);
-    lars_stats *dst = d.take<lars_stats>(1);
-    T *dmed = d.take<T>(2);
-    double *dss = d.take<double>(1);
-    char *dsel = d.take<char>(lars_select_scratch_bytes());
+    T *dx, *dmed;
+    lars_stats *dst;
+    double *dss;
+    char *dsel;
+    LARS_TRY(ws_plan(c, [&](Carver &d) {
+        dx = d.take<T>(n);
+        dst = d.take<lars_stats>(1);
+        dmed = d.take<T>(2);
+        dss = d.take<double>(1);
+        dsel = d.take<char>(lars_select_scratch_bytes());
+    }));
     hipStream_t s = c->stream;
     LARS_HIP_TRY(hipMemcpyAsync(dx, x, (size_t)n * sizeof(T), hipMemcpyHostToDevice, s));
     if (sizeof(T) == 4) {
@@ -341,11 +325,8 @@ int lars_h_calculate_index_planes(const float *red, const float *green, const fl
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (!red || !green || !nir || !out || n <= 0) return fail(LARS_ERR_INVALID, "lars_h_calculate_index_planes: bad arguments");
-    Carver cv(nullptr);
-    cv.take<float>(n); cv.take<float>(n); cv.take<float>(n); cv.take<float>(n);
-    LARS_TRY(ws_reserve(c, cv.off + 256));
-    Carver d(c->ws);
-    float *dr = d.take<float>(n), *dg = d.take<float>(n), *dn = d.take<float>(n), *dout = d.take<float>(n);
+    float *dr, *dg, *dn, *dout;
+    LARS_TRY(ws_plan(c, [&](Carver &d) { dr = d.take<float>(n), dg = d.take<float>(n), dn = d.take<float>(n), dout = d.take<float>(n); }));
     hipStream_t s = c->stream;
     // only the two bands the index reads cross PCIe
     const float *ha = index_id == LARS_NDWI ? green : nir;
@@ -367,12 +348,9 @@ int lars_h_ndvi_f64(const void *img, int64_t h, int64_t w, int channels, int dty
     if (!img || !out || h <= 0 || w <= 0 || channels < 3) return fail(LARS_ERR_INVALID, "lars_h_ndvi_f64: bad arguments");
     if (dtype != LARS_U8 && dtype != LARS_U16) return fail(LARS_ERR_INVALID, "lars_h_ndvi_f64: dtype");
     const size_t npix = (size_t)h * w, esz = dtype == LARS_U8 ? 1 : 2;
-    Carver cv(nullptr);
-    cv.take<uint8_t>(npix * channels * esz); cv.take<double>(npix);
-    LARS_TRY(ws_reserve(c, cv.off + 256));
-    Carver d(c->ws);
-    uint8_t *dimg = d.take<uint8_t>(npix * channels * esz);
-    double *dout = d.take<double>(npix);
+    uint8_t *dimg;
+    double *dout;
+    LARS_TRY(ws_plan(c, [&](Carver &d) { dimg = d.take<uint8_t>(npix * channels * esz), dout = d.take<double>(npix); }));
     hipStream_t s = c->stream;
     LARS_HIP_TRY(hipMemcpyAsync(dimg, img, npix * channels * esz, hipMemcpyHostToDevice, s));
     LARS_TRY(lars_d_ndvi_f64(dimg, (int64_t)npix, channels, dtype, dout, s));
@@ -396,12 +374,9 @@ int lars_h_threshold_mask_f32(const float *x, int64_t n, float threshold, uint8_
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (!x || !out_mask || n <= 0) return fail(LARS_ERR_INVALID, "lars_h_threshold_mask_f32: bad arguments");
-    Carver cv(nullptr);
-    cv.take<float>(n); cv.take<uint8_t>((size_t)n + 4);
-    LARS_TRY(ws_reserve(c, cv.off + 256));
-    Carver d(c->ws);
-    float *dx = d.take<float>(n);
-    uint8_t *dm = d.take<uint8_t>((size_t)n + 4);
+    float *dx;
+    uint8_t *dm;
+    LARS_TRY(ws_plan(c, [&](Carver &d) { dx = d.take<float>(n), dm = d.take<uint8_t>((size_t)n + 4); }));
     hipStream_t s = c->stream;
     LARS_HIP_TRY(hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, s));
     LARS_TRY(lars_d_threshold_mask_f32(dx, n, threshold, dm, s));
@@ -410,46 +385,33 @@ int lars_h_threshold_mask_f32(const float *x, int64_t n, float threshold, uint8_
     return LARS_OK;
 }
 
-int lars_h_colormap_f32(const float *x, int64_t n, const uint8_t *lut_rgba, uint8_t *out_rgba)
+// lars_h_colormap_f32 (range == nullptr) and lars_h_colormap_norm_f32 (range = {vmin, vmax})
+static int colormap_impl(const char *who, const float *x, int64_t n, const float *range, const uint8_t *lut_rgba, uint8_t *out_rgba)
 {
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
-    if (!x || !lut_rgba || !out_rgba || n <= 0) return fail(LARS_ERR_INVALID, "lars_h_colormap_f32: bad arguments");
-    Carver cv(nullptr);
-    cv.take<float>(n); cv.take<uint8_t>(1024); cv.take<uint8_t>((size_t)n * 4);
-    LARS_TRY(ws_reserve(c, cv.off + 256));
-    Carver d(c->ws);
-    float *dx = d.take<float>(n);
-    uint8_t *dl = d.take<uint8_t>(1024);
-    uint8_t *dout = d.take<uint8_t>((size_t)n * 4);
+    if (!x || !lut_rgba || !out_rgba || n <= 0) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    float *dx;
+    uint8_t *dl, *dout;
+    LARS_TRY(ws_plan(c, [&](Carver &d) { dx = d.take<float>(n), dl = d.take<uint8_t>(1024), dout = d.take<uint8_t>((size_t)n * 4); }));
     hipStream_t s = c->stream;
     LARS_HIP_TRY(hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, s));
     LARS_HIP_TRY(hipMemcpyAsync(dl, lut_rgba, 1024, hipMemcpyHostToDevice, s));
-    LARS_TRY(lars_d_colormap_f32(dx, n, dl, dout, s));
+    LARS_TRY(range ? lars_d_colormap_norm_f32(dx, n, range[0], range[1], dl, dout, s) : lars_d_colormap_f32(dx, n, dl, dout, s));
     LARS_HIP_TRY(hipMemcpyAsync(out_rgba, dout, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     LARS_HIP_TRY(hipStreamSynchronize(s));
     return LARS_OK;
 }
 
+int lars_h_colormap_f32(const float *x, int64_t n, const uint8_t *lut_rgba, uint8_t *out_rgba)
+{
+    return colormap_impl("lars_h_colormap_f32", x, n, nullptr, lut_rgba, out_rgba);
+}
+
 int lars_h_colormap_norm_f32(const float *x, int64_t n, float vmin, float vmax, const uint8_t *lut_rgba, uint8_t *out_rgba)
 {
-    ThreadCtx *c;
-    LARS_TRY(ensure_ctx(&c));
-    if (!x || !lut_rgba || !out_rgba || n <= 0) return fail(LARS_ERR_INVALID, "lars_h_colormap_norm_f32: bad arguments");
-    Carver cv(nullptr);
-    cv.take<float>(n); cv.take<uint8_t>(1024); cv.take<uint8_t>((size_t)n * 4);
-    LARS_TRY(ws_reserve(c, cv.off + 256));
-    Carver d(c->ws);
-    float *dx = d.take<float>(n);
-    uint8_t *dl = d.take<uint8_t>(1024);
-    uint8_t *dout = d.take<uint8_t>((size_t)n * 4);
-    hipStream_t s = c->stream;
-    LARS_HIP_TRY(hipMemcpyAsync(dx, x, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    LARS_HIP_TRY(hipMemcpyAsync(dl, lut_rgba, 1024, hipMemcpyHostToDevice, s));
-    LARS_TRY(lars_d_colormap_norm_f32(dx, n, vmin, vmax, dl, dout, s));
-    LARS_HIP_TRY(hipMemcpyAsync(out_rgba, dout, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    return LARS_OK;
+    const float range[2] = {vmin, vmax};
+    return colormap_impl("lars_h_colormap_norm_f32", x, n, range, lut_rgba, out_rgba);
 }
 
 // device-side registration of `moving` (device, uint8 [h][w][channels]) to `fixed`: estimate + apply
@@ -472,15 +434,16 @@ int lars_h_align_images(const uint8_t *fixed, const uint8_t *moving, int64_t h, 
     if (!fixed || !moving || !out_aligned || h <= 0 || w <= 0 || (channels != 1 && channels != 3))
         return fail(LARS_ERR_INVALID, "lars_h_align_images: two uint8 [h][w][3] (or [h][w]) images of the same shape are required");
     const size_t npix = (size_t)h * w, nbytes = npix * channels;
-    Carver cv(nullptr);
-    cv.take<uint8_t>(nbytes); cv.take<uint8_t>(nbytes); cv.take<uint8_t>(nbytes);
-    cv.take<double>(npix * 2); cv.take<double>(npix * 2); cv.take<char>(lars_phase_scratch_bytes()); cv.take<int64_t>(2);
-    LARS_TRY(ws_reserve(c, cv.off + 256));
-    Carver d(c->ws);
-    uint8_t *df = d.take<uint8_t>(nbytes), *dm = d.take<uint8_t>(nbytes), *da = d.take<uint8_t>(nbytes);
-    double *fa = d.take<double>(npix * 2), *fb = d.take<double>(npix * 2);
-    char *sc = d.take<char>(lars_phase_scratch_bytes());
-    int64_t *dshift = d.take<int64_t>(2);
+    uint8_t *df, *dm, *da;
+    double *fa, *fb;
+    char *sc;
+    int64_t *dshift;
+    LARS_TRY(ws_plan(c, [&](Carver &d) {
+        df = d.take<uint8_t>(nbytes), dm = d.take<uint8_t>(nbytes), da = d.take<uint8_t>(nbytes);
+        fa = d.take<double>(npix * 2), fb = d.take<double>(npix * 2);
+        sc = d.take<char>(lars_phase_scratch_bytes());
+        dshift = d.take<int64_t>(2);
+    }));
     hipStream_t s = c->stream;
     LARS_HIP_TRY(hipMemcpyAsync(df, fixed, nbytes, hipMemcpyHostToDevice, s));
     LARS_HIP_TRY(hipMemcpyAsync(dm, moving, nbytes, hipMemcpyHostToDevice, s));

@@ -43,7 +43,7 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "codec_host.h"
 #include "jpeg_parse.h"
 
 namespace lars {
@@ -682,21 +682,39 @@ __global__ __launch_bounds__(256) void k_jd_color(const uint8_t *planes, JdGeo g
 }
 
 // ------------------------------------------------------------------------------------------------- host side
-struct JdLayout {
+// lars_jpeg_info's info[] by name (sampling: component 0's, the others are checked to be 1 x 1)
+struct JpegInfo {
+    int64_t w, h, ncomp, hs0, vs0, ri, eoff, elen, supported, reason;
+    explicit JpegInfo(const int64_t *i)
+        : w(i[LARS_JPEG_INFO_WIDTH]), h(i[LARS_JPEG_INFO_HEIGHT]), ncomp(i[LARS_JPEG_INFO_COMPONENTS]), hs0(i[LARS_JPEG_INFO_H0]),
+          vs0(i[LARS_JPEG_INFO_V0]), ri(i[LARS_JPEG_INFO_RESTART_INTERVAL]), eoff(i[LARS_JPEG_INFO_ENTROPY_OFFSET]),
+          elen(i[LARS_JPEG_INFO_ENTROPY_BYTES]), supported(i[LARS_JPEG_INFO_SUPPORTED]), reason(i[LARS_JPEG_INFO_REASON])
+    {
+    }
+};
+
+// geometry and the device scratch of one file: what lars_jpeg_decode_scratch_bytes counts and lars_d_decode_jpeg_u8 points into
+struct JdPlan {
     JdGeo g;
     jd_u64 elen, nwg, nsub_cap;
     unsigned int sbits;
-    size_t ctl, tables, keepcnt, markcnt, compact, cbyte, nsubs, suboff, subs, in, out, cnt, pre, coef, sums, planes, bytes;
+    JdCtl *ctl;
+    JdTables *tables;
+    unsigned int *keepcnt, *markcnt, *nsubs, *suboff, *cnt, *pre, *sums;
+    uint8_t *compact, *planes;
+    jd_u64 *cbyte, *in, *out;
+    JdSub *subs;
+    short *coef;
 };
 
-// info as lars_jpeg_info gave it; false for what the decoder does not take
-static bool jd_layout(const int64_t info[LARS_JPEG_INFO_N], int sbits, JdLayout *Lp)
+// false for what the decoder does not take
+static bool jd_plan(const JpegInfo &I, int sbits, Carver &cv, JdPlan *Lp)
 {
-    JdLayout L{};
-    const int64_t w = info[0], h = info[1], nc = info[2];
-    if (!info[14] || w < 1 || h < 1 || w > 65535 || h > 65535 || (nc != 1 && nc != 3) || h * w * nc >= (1ll << 31)) return false;
-    if (info[12] < 0 || info[13] < 0 || info[13] > (1ll << 40) || info[11] < 0 || info[11] > 65535) return false;
-    const int hs = nc == 1 ? 1 : (int)info[5], vs = nc == 1 ? 1 : (int)info[6];
+    JdPlan L{};
+    const int64_t w = I.w, h = I.h, nc = I.ncomp;
+    if (!I.supported || w < 1 || h < 1 || w > 65535 || h > 65535 || (nc != 1 && nc != 3) || h * w * nc >= (1ll << 31)) return false;
+    if (I.eoff < 0 || I.elen < 0 || I.elen > (1ll << 40) || I.ri < 0 || I.ri > 65535) return false;
+    const int hs = nc == 1 ? 1 : (int)I.hs0, vs = nc == 1 ? 1 : (int)I.vs0;
     if (!((hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2))) return false;
     JdGeo &g = L.g;
     g.w = (int)w; g.h = (int)h; g.ncomp = (int)nc; g.hs = hs; g.vs = vs;
@@ -706,7 +724,7 @@ static bool jd_layout(const int64_t info[LARS_JPEG_INFO_N], int sbits, JdLayout 
     g.mcuy = (int)((h + 8 * vs - 1) / (8 * vs));
     g.nmcu = (unsigned int)g.mcux * g.mcuy;
     g.nblocks = g.nmcu * g.bpm;
-    g.ri = info[11] > 0 && (unsigned int)info[11] < g.nmcu ? (unsigned int)info[11] : g.nmcu;
+    g.ri = I.ri > 0 && (unsigned int)I.ri < g.nmcu ? (unsigned int)I.ri : g.nmcu;
     g.nint = (g.nmcu + g.ri - 1) / g.ri;
     unsigned int off = 0, blocks = 0;
     for (int c = 0; c < 3; ++c) {
@@ -719,30 +737,27 @@ static bool jd_layout(const int64_t info[LARS_JPEG_INFO_N], int sbits, JdLayout 
         blocks += (unsigned int)(g.pw[c] / 8) * (g.ph[c] / 8);
     }
     g.pblocks[3] = blocks;
-    L.elen = (jd_u64)info[13];
+    L.elen = (jd_u64)I.elen;
     L.sbits = (unsigned int)sbits;
     L.nwg = (L.elen + JD_MARK_THREADS - 1) / JD_MARK_THREADS;
     L.nsub_cap = L.elen * 8 / L.sbits + g.nint + 1;
     if (L.nsub_cap >= (1ull << 31) || L.nwg >= (1ull << 31)) return false;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t o = 0;
-    L.ctl = o; o += al(sizeof(JdCtl));
-    L.tables = o; o += al(sizeof(JdTables));
-    L.keepcnt = o; o += al((L.nwg + 1) * 4);
-    L.markcnt = o; o += al((L.nwg + 1) * 4);
-    L.compact = o; o += al(L.elen + 16);
-    L.cbyte = o; o += al(((size_t)g.nint + 1) * 8);
-    L.nsubs = o; o += al(((size_t)g.nint + 1) * 4);
-    L.suboff = o; o += al(((size_t)g.nint + 1) * 4);
-    L.subs = o; o += al(L.nsub_cap * sizeof(JdSub));
-    L.in = o; o += al(L.nsub_cap * 8);
-    L.out = o; o += al(L.nsub_cap * 8);
-    L.cnt = o; o += al(L.nsub_cap * 4);
-    L.pre = o; o += al(L.nsub_cap * 4);
-    L.coef = o; o += al((size_t)g.nblocks * 128);
-    L.sums = o; o += al((size_t)g.nmcu * 4 * 3);
-    L.planes = o; o += al((size_t)off);
-    L.bytes = o;
+    L.ctl = cv.take<JdCtl>(1);
+    L.tables = cv.take<JdTables>(1);
+    L.keepcnt = cv.take<unsigned int>(L.nwg + 1);
+    L.markcnt = cv.take<unsigned int>(L.nwg + 1);
+    L.compact = cv.take<uint8_t>(L.elen + 16);
+    L.cbyte = cv.take<jd_u64>((size_t)g.nint + 1);
+    L.nsubs = cv.take<unsigned int>((size_t)g.nint + 1);
+    L.suboff = cv.take<unsigned int>((size_t)g.nint + 1);
+    L.subs = cv.take<JdSub>(L.nsub_cap);
+    L.in = cv.take<jd_u64>(L.nsub_cap);
+    L.out = cv.take<jd_u64>(L.nsub_cap);
+    L.cnt = cv.take<unsigned int>(L.nsub_cap);
+    L.pre = cv.take<unsigned int>(L.nsub_cap);
+    L.coef = cv.take<short>((size_t)g.nblocks * 64);
+    L.sums = cv.take<unsigned int>((size_t)g.nmcu * 3);
+    L.planes = cv.take<uint8_t>((size_t)off);
     *Lp = L;
     return true;
 }
@@ -774,44 +789,39 @@ static const char *jd_reason(int64_t r)
     }
 }
 
-static int jd_parse(const char *who, const uint8_t *file, int64_t len, int64_t info[LARS_JPEG_INFO_N])
-{
-    if (!file || len <= 0) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
-    LARS_TRY(lars_jpeg_info(file, len, info));
-    if (!info[14]) return fail(LARS_ERR_UNSUPPORTED, "%s: %s JPEG files are not supported", who, jd_reason(info[15]));
-    return LARS_OK;
-}
+// the JPEG side of the host entry points (codec_host.h)
+struct JdFile : HostFile {
+    int64_t info[LARS_JPEG_INFO_N];
+    JdCtl ctl;
 
-static size_t jd_host_ws_bytes(int64_t len, const int64_t info[LARS_JPEG_INFO_N])
-{
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    return al((size_t)len) + al((size_t)info[0] * info[1] * info[2]) + 256 + lars_jpeg_decode_scratch_bytes(info);
-}
-
-// host file -> the device image: upload, decode, status read back (one sync)
-static int jd_decode_to_device(ThreadCtx *c, const char *who, const uint8_t *file, int64_t len, const int64_t info[LARS_JPEG_INFO_N],
-                               char *ws, uint8_t **d_img_out)
-{
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    char *p = ws;
-    uint8_t *d_file = reinterpret_cast<uint8_t *>(p); p += al((size_t)len);
-    uint8_t *d_img = reinterpret_cast<uint8_t *>(p); p += al((size_t)info[0] * info[1] * info[2]);
-    int32_t *d_st = reinterpret_cast<int32_t *>(p); p += 256;
-    hipStream_t s = c->stream;
-    LARS_HIP_TRY(hipMemcpyAsync(d_file, file, (size_t)len, hipMemcpyHostToDevice, s));
-    LARS_TRY(lars_d_decode_jpeg_u8(d_file, file, info, d_img, d_st, p, s));
-    int st[2] = {0, 0};
-    JdCtl ctl;                                            // the control block opens the scratch: the rounds that decoded anything
-    LARS_HIP_TRY(hipMemcpyAsync(st, d_st, sizeof st, hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipMemcpyAsync(&ctl, p, sizeof ctl, hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    if (st[0]) return jd_status_fail(who, st);
-    int rounds = 1;
-    for (int r = 1; r <= JD_ROUNDS; ++r) rounds += ctl.changed[r] != 0;
-    tuning().jpeg_last_rounds = rounds + (ctl.changed[JD_ROUNDS] != 0 ? 100 : 0);
-    *d_img_out = d_img;
-    return LARS_OK;
-}
+    int parse(const char *who_, const uint8_t *file_, int64_t len_)
+    {
+        who = who_; file = file_; len = len_;
+        if (!file || len <= 0) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+        LARS_TRY(lars_jpeg_info(file, len, info));
+        const JpegInfo I(info);
+        if (!I.supported) return fail(LARS_ERR_UNSUPPORTED, "%s: %s JPEG files are not supported", who, jd_reason(I.reason));
+        h = I.h; w = I.w; channels = (int)I.ncomp;
+        extra_bytes = 0;
+        scratch_bytes = lars_jpeg_decode_scratch_bytes(info);
+        return LARS_OK;
+    }
+    int enqueue(hipStream_t s)
+    {
+        LARS_TRY(lars_d_decode_jpeg_u8(d_file, file, info, d_img, d_status, d_scratch, s));
+        // the control block opens the scratch: the rounds that decoded anything
+        LARS_HIP_TRY(hipMemcpyAsync(&ctl, d_scratch, sizeof ctl, hipMemcpyDeviceToHost, s));
+        return LARS_OK;
+    }
+    int finish(const int st[2])
+    {
+        if (st[0]) return jd_status_fail(who, st);
+        int rounds = 1;
+        for (int r = 1; r <= JD_ROUNDS; ++r) rounds += ctl.changed[r] != 0;
+        tuning().jpeg_last_rounds = rounds + (ctl.changed[JD_ROUNDS] != 0 ? 100 : 0);
+        return LARS_OK;
+    }
+};
 
 }  // namespace lars
 
@@ -821,9 +831,10 @@ extern "C" {
 
 size_t lars_jpeg_decode_scratch_bytes(const int64_t info[LARS_JPEG_INFO_N])
 {
-    JdLayout L;
-    if (!info || !jd_layout(info, tuning().jpeg_subseq_bits, &L)) return 0;
-    return L.bytes;
+    JdPlan L;
+    Carver size(nullptr);
+    if (!info || !jd_plan(JpegInfo(info), tuning().jpeg_subseq_bits, size, &L)) return 0;
+    return size.bytes();
 }
 
 int lars_d_decode_jpeg_u8(const uint8_t *file_dev, const uint8_t *head, const int64_t info[LARS_JPEG_INFO_N], uint8_t *out,
@@ -833,12 +844,14 @@ int lars_d_decode_jpeg_u8(const uint8_t *file_dev, const uint8_t *head, const in
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (!file_dev || !head || !info || !out || !status_dev || !scratch) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
-    JdLayout L;
-    if (!jd_layout(info, tuning().jpeg_subseq_bits, &L)) return fail(LARS_ERR_INVALID, "%s: info describes no file this decoder takes", who);
+    const JpegInfo I(info);
+    JdPlan L;
+    Carver cv(scratch);
+    if (!jd_plan(I, tuning().jpeg_subseq_bits, cv, &L)) return fail(LARS_ERR_INVALID, "%s: info describes no file this decoder takes", who);
     JpegHeader H;
-    LARS_TRY(jpeg_parse(head, info[12], &H, false));
-    if (!H.supported || H.w != info[0] || H.h != info[1] || H.ncomp != info[2] || H.eoff != info[12] || H.ri != info[11] ||
-        (H.ncomp == 3 && (H.hs[0] != info[5] || H.vs[0] != info[6])))
+    LARS_TRY(jpeg_parse(head, I.eoff, &H, false));
+    if (!H.supported || H.w != I.w || H.h != I.h || H.ncomp != I.ncomp || H.eoff != I.eoff || H.ri != I.ri ||
+        (H.ncomp == 3 && (H.hs[0] != I.hs0 || H.vs[0] != I.vs0)))
         return fail(LARS_ERR_INVALID, "%s: head and info do not describe the same file", who);
     JdTablesArg A;
     memset(&A, 0, sizeof A);
@@ -850,50 +863,38 @@ int lars_d_decode_jpeg_u8(const uint8_t *file_dev, const uint8_t *head, const in
         memcpy(A.hval[3 + k], H.hval[4 + H.ta[k]], 256);
     }
     const JdGeo &g = L.g;
-    char *sc = static_cast<char *>(scratch);
-    JdCtl *ctl = reinterpret_cast<JdCtl *>(sc + L.ctl);
-    JdTables *T = reinterpret_cast<JdTables *>(sc + L.tables);
-    unsigned int *keepcnt = reinterpret_cast<unsigned int *>(sc + L.keepcnt), *markcnt = reinterpret_cast<unsigned int *>(sc + L.markcnt);
-    uint8_t *compact = reinterpret_cast<uint8_t *>(sc + L.compact);
-    jd_u64 *cbyte = reinterpret_cast<jd_u64 *>(sc + L.cbyte);
-    unsigned int *nsubs = reinterpret_cast<unsigned int *>(sc + L.nsubs), *suboff = reinterpret_cast<unsigned int *>(sc + L.suboff);
-    JdSub *subs = reinterpret_cast<JdSub *>(sc + L.subs);
-    jd_u64 *in = reinterpret_cast<jd_u64 *>(sc + L.in), *outs = reinterpret_cast<jd_u64 *>(sc + L.out);
-    unsigned int *cnt = reinterpret_cast<unsigned int *>(sc + L.cnt), *pre = reinterpret_cast<unsigned int *>(sc + L.pre);
-    short *coef = reinterpret_cast<short *>(sc + L.coef);
-    unsigned int *sums = reinterpret_cast<unsigned int *>(sc + L.sums);
-    uint8_t *planes = reinterpret_cast<uint8_t *>(sc + L.planes);
-    const unsigned int *words = reinterpret_cast<const unsigned int *>(compact);
-    const uint8_t *seg = file_dev + info[12];
+    JdCtl *ctl = L.ctl;
+    const unsigned int *words = reinterpret_cast<const unsigned int *>(L.compact);
+    const uint8_t *seg = file_dev + I.eoff;
     const long long elen = (long long)L.elen;
     hipStream_t s = pick_stream(c, stream);
     LARS_HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(JdCtl), s));
     LARS_HIP_TRY(hipMemsetAsync(&ctl->errkey, 0xFF, sizeof(jd_u64), s));
-    LARS_HIP_TRY(hipMemsetAsync(coef, 0, (size_t)g.nblocks * 128, s));
-    LARS_HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)L.nsub_cap * 4, s));       // the scan of the counts runs over the whole capacity
-    hipLaunchKernelGGL(k_jd_setup, dim3(1), dim3(64), 0, s, A, T);
+    LARS_HIP_TRY(hipMemsetAsync(L.coef, 0, (size_t)g.nblocks * 128, s));
+    LARS_HIP_TRY(hipMemsetAsync(L.cnt, 0, (size_t)L.nsub_cap * 4, s));       // the scan of the counts runs over the whole capacity
+    hipLaunchKernelGGL(k_jd_setup, dim3(1), dim3(64), 0, s, A, L.tables);
     if (L.nwg) {
-        hipLaunchKernelGGL(k_jd_mark, dim3((unsigned)L.nwg), dim3(JD_MARK_THREADS), 0, s, seg, elen, keepcnt, markcnt);
-        hipLaunchKernelGGL(k_jd_exscan, dim3(1), dim3(1024), 0, s, keepcnt, keepcnt, (long long)L.nwg, 0ll, &ctl->kept_total);
-        hipLaunchKernelGGL(k_jd_exscan, dim3(1), dim3(1024), 0, s, markcnt, markcnt, (long long)L.nwg, 0ll, &ctl->mark_total);
-        hipLaunchKernelGGL(k_jd_compact, dim3((unsigned)L.nwg), dim3(JD_MARK_THREADS), 0, s, seg, elen, keepcnt, markcnt, g.nint, compact, cbyte, ctl);
+        hipLaunchKernelGGL(k_jd_mark, dim3((unsigned)L.nwg), dim3(JD_MARK_THREADS), 0, s, seg, elen, L.keepcnt, L.markcnt);
+        hipLaunchKernelGGL(k_jd_exscan, dim3(1), dim3(1024), 0, s, L.keepcnt, L.keepcnt, (long long)L.nwg, 0ll, &ctl->kept_total);
+        hipLaunchKernelGGL(k_jd_exscan, dim3(1), dim3(1024), 0, s, L.markcnt, L.markcnt, (long long)L.nwg, 0ll, &ctl->mark_total);
+        hipLaunchKernelGGL(k_jd_compact, dim3((unsigned)L.nwg), dim3(JD_MARK_THREADS), 0, s, seg, elen, L.keepcnt, L.markcnt, g.nint, L.compact, L.cbyte, ctl);
     }
-    hipLaunchKernelGGL(k_jd_intervals, dim3((g.nint + 255) / 256), dim3(256), 0, s, cbyte, g.nint, L.sbits, nsubs, ctl);
-    hipLaunchKernelGGL(k_jd_exscan, dim3(1), dim3(1024), 0, s, nsubs, suboff, (long long)g.nint, 0ll, &ctl->nsub_total);
+    hipLaunchKernelGGL(k_jd_intervals, dim3((g.nint + 255) / 256), dim3(256), 0, s, L.cbyte, g.nint, L.sbits, L.nsubs, ctl);
+    hipLaunchKernelGGL(k_jd_exscan, dim3(1), dim3(1024), 0, s, L.nsubs, L.suboff, (long long)g.nint, 0ll, &ctl->nsub_total);
     const unsigned int sgrid = (unsigned int)((L.nsub_cap + 255) / 256);
-    hipLaunchKernelGGL(k_jd_subs, dim3(sgrid), dim3(256), 0, s, cbyte, suboff, g.nint, L.sbits, (unsigned int)L.nsub_cap, subs, ctl);
+    hipLaunchKernelGGL(k_jd_subs, dim3(sgrid), dim3(256), 0, s, L.cbyte, L.suboff, g.nint, L.sbits, (unsigned int)L.nsub_cap, L.subs, ctl);
     for (int r = 0; r <= JD_ROUNDS; ++r)
-        hipLaunchKernelGGL(k_jd_pass, dim3(sgrid), dim3(256), 0, s, T, words, subs, in, outs, cnt, r, g.bpm, g.ny, ctl);
-    hipLaunchKernelGGL(k_jd_finish, dim3(1), dim3(64), 0, s, T, words, subs, in, outs, cnt, g.bpm, g.ny, ctl);
-    hipLaunchKernelGGL(k_jd_check, dim3(sgrid), dim3(256), 0, s, outs, ctl);
-    hipLaunchKernelGGL(k_jd_exscan, dim3(1), dim3(1024), 0, s, cnt, pre, (long long)L.nsub_cap, 0ll, &ctl->block_total);
-    hipLaunchKernelGGL(k_jd_verify, dim3((g.nint + 255) / 256), dim3(256), 0, s, pre, suboff, g, ctl);
-    hipLaunchKernelGGL(k_jd_write, dim3(sgrid), dim3(256), 0, s, T, words, subs, in, pre, g.bpm, g.ny, g.nblocks, coef, ctl);
-    hipLaunchKernelGGL(k_jd_mcu_sums, dim3((g.nmcu + 255) / 256), dim3(256), 0, s, coef, g, sums, ctl);
-    hipLaunchKernelGGL(k_jd_exscan, dim3((unsigned)g.ncomp), dim3(1024), 0, s, sums, sums, (long long)g.nmcu, (long long)g.nmcu, (unsigned int *)nullptr);
-    hipLaunchKernelGGL(k_jd_idct, dim3((g.pblocks[3] + 31) / 32), dim3(256), 0, s, coef, sums, T, g, planes, ctl);
+        hipLaunchKernelGGL(k_jd_pass, dim3(sgrid), dim3(256), 0, s, L.tables, words, L.subs, L.in, L.out, L.cnt, r, g.bpm, g.ny, ctl);
+    hipLaunchKernelGGL(k_jd_finish, dim3(1), dim3(64), 0, s, L.tables, words, L.subs, L.in, L.out, L.cnt, g.bpm, g.ny, ctl);
+    hipLaunchKernelGGL(k_jd_check, dim3(sgrid), dim3(256), 0, s, L.out, ctl);
+    hipLaunchKernelGGL(k_jd_exscan, dim3(1), dim3(1024), 0, s, L.cnt, L.pre, (long long)L.nsub_cap, 0ll, &ctl->block_total);
+    hipLaunchKernelGGL(k_jd_verify, dim3((g.nint + 255) / 256), dim3(256), 0, s, L.pre, L.suboff, g, ctl);
+    hipLaunchKernelGGL(k_jd_write, dim3(sgrid), dim3(256), 0, s, L.tables, words, L.subs, L.in, L.pre, g.bpm, g.ny, g.nblocks, L.coef, ctl);
+    hipLaunchKernelGGL(k_jd_mcu_sums, dim3((g.nmcu + 255) / 256), dim3(256), 0, s, L.coef, g, L.sums, ctl);
+    hipLaunchKernelGGL(k_jd_exscan, dim3((unsigned)g.ncomp), dim3(1024), 0, s, L.sums, L.sums, (long long)g.nmcu, (long long)g.nmcu, (unsigned int *)nullptr);
+    hipLaunchKernelGGL(k_jd_idct, dim3((g.pblocks[3] + 31) / 32), dim3(256), 0, s, L.coef, L.sums, L.tables, g, L.planes, ctl);
     const long long npix = (long long)g.w * g.h;
-    hipLaunchKernelGGL(k_jd_color, dim3((unsigned)std::min<long long>((npix + 255) / 256, 16384)), dim3(256), 0, s, planes, g, out, ctl);
+    hipLaunchKernelGGL(k_jd_color, dim3((unsigned)std::min<long long>((npix + 255) / 256, 16384)), dim3(256), 0, s, L.planes, g, out, ctl);
     LARS_HIP_TRY(hipMemcpyAsync(status_dev, ctl->status, 8, hipMemcpyDeviceToDevice, s));
     return launch_check(who);
 }
@@ -905,16 +906,9 @@ int lars_h_decode_jpeg_u8(const uint8_t *file, int64_t len, uint8_t *out, size_t
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (!out) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
-    int64_t info[LARS_JPEG_INFO_N];
-    LARS_TRY(jd_parse(who, file, len, info));
-    const size_t bytes = (size_t)info[0] * info[1] * info[2];
-    if (out_cap < bytes) return fail(LARS_ERR_INVALID, "%s: out_cap %zu < %zu", who, out_cap, bytes);
-    LARS_TRY(ws_reserve(c, jd_host_ws_bytes(len, info)));
-    uint8_t *d_img = nullptr;
-    LARS_TRY(jd_decode_to_device(c, who, file, len, info, static_cast<char *>(c->ws), &d_img));
-    LARS_HIP_TRY(hipMemcpyAsync(out, d_img, bytes, hipMemcpyDeviceToHost, c->stream));
-    LARS_HIP_TRY(hipStreamSynchronize(c->stream));
-    return LARS_OK;
+    JdFile F;
+    LARS_TRY(F.parse(who, file, len));
+    return decode_file_to_host(c, F, out, out_cap);
 }
 
 // host file in, thumbnail out: the decoded pixels go straight into the thumbnail kernels (resize.hip)
@@ -925,18 +919,9 @@ int lars_h_thumbnail_jpeg_u8(const uint8_t *file, int64_t len, int fx, int fy, c
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (!out || !reduce_box || !box) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
-    int64_t info[LARS_JPEG_INFO_N];
-    LARS_TRY(jd_parse(who, file, len, info));
-    const int64_t h = info[1], w = info[0];
-    const int ch = (int)info[2];
-    size_t tneed = 0;
-    LARS_TRY(thumbnail_u8_impl(c, nullptr, true, nullptr, &tneed, h, w, ch, fx, fy, reduce_box, box, new_h, new_w, vertical_first, out));
-    const size_t front = (jd_host_ws_bytes(len, info) + 255) & ~(size_t)255;
-    LARS_TRY(ws_reserve(c, front + tneed));
-    uint8_t *d_img = nullptr;
-    LARS_TRY(jd_decode_to_device(c, who, file, len, info, static_cast<char *>(c->ws), &d_img));
-    return thumbnail_u8_impl(c, d_img, true, static_cast<char *>(c->ws) + front, nullptr, h, w, ch, fx, fy, reduce_box, box, new_h,
-                             new_w, vertical_first, out);
+    JdFile F;
+    LARS_TRY(F.parse(who, file, len));
+    return thumbnail_file(c, F, fx, fy, reduce_box, box, new_h, new_w, vertical_first, out);
 }
 
 }  // extern "C"

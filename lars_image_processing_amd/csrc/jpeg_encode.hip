@@ -22,7 +22,7 @@
 
 #include <algorithm>
 
-#include "common.h"
+#include "codec_host.h"
 #include "jpeg_tables.h"
 
 namespace lars {
@@ -453,31 +453,40 @@ __global__ __launch_bounds__(JE_THREADS) void k_je_stuff(const unsigned int *__r
     }
 }
 
-struct JeLayout {
-    size_t tables, ctl, coef, loc, wgsum, wgoff, words, ffcnt, ffoff, bytes;
+// the device scratch of one picture: what lars_jpeg_encode_scratch_bytes counts and lars_d_encode_jpeg_u8 points into
+struct JePlan {
     je_u64 cap_words;
     long long nwg, nchunks;                      // workgroups of k_je_size / k_je_write; chunks of the longest stream
+    JeTables *tables;
+    JeCtl *ctl;
+    short *coef;
+    unsigned int *loc, *wgsum, *words, *ffcnt;
+    je_u64 *wgoff, *ffoff;
 };
 
-static JeLayout je_layout(const JpegEncGeo &g)
+static JePlan je_plan(const JpegEncGeo &g, Carver &cv)
 {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    JeLayout L;
-    L.nwg = (g.nblocks + JE_THREADS - 1) / JE_THREADS;
+    JePlan P;
+    P.nwg = (g.nblocks + JE_THREADS - 1) / JE_THREADS;
     const je_u64 max_bits = (je_u64)g.nblocks * (je_u64)jpeg_enc_max_block_bits();
-    L.cap_words = (max_bits + 31) / 32 + 2;
-    L.nchunks = (long long)(((max_bits + 7) / 8 + JE_CHUNK - 1) / JE_CHUNK);
-    L.tables = 0;
-    L.ctl = L.tables + al(sizeof(JeTables));
-    L.coef = L.ctl + al(sizeof(JeCtl));
-    L.loc = L.coef + al((size_t)g.nblocks * 128);
-    L.wgsum = L.loc + al((size_t)g.nblocks * 4);
-    L.wgoff = L.wgsum + al((size_t)L.nwg * 4);
-    L.words = L.wgoff + al((size_t)L.nwg * 8);
-    L.ffcnt = L.words + al((size_t)L.cap_words * 4);
-    L.ffoff = L.ffcnt + al((size_t)L.nchunks * 4);
-    L.bytes = L.ffoff + al((size_t)L.nchunks * 8);
-    return L;
+    P.cap_words = (max_bits + 31) / 32 + 2;
+    P.nchunks = (long long)(((max_bits + 7) / 8 + JE_CHUNK - 1) / JE_CHUNK);
+    P.tables = cv.take<JeTables>(1);
+    P.ctl = cv.take<JeCtl>(1);
+    P.coef = cv.take<short>((size_t)g.nblocks * 64);
+    P.loc = cv.take<unsigned int>((size_t)g.nblocks);
+    P.wgsum = cv.take<unsigned int>((size_t)P.nwg);
+    P.wgoff = cv.take<je_u64>((size_t)P.nwg);
+    P.words = cv.take<unsigned int>((size_t)P.cap_words);
+    P.ffcnt = cv.take<unsigned int>((size_t)P.nchunks);
+    P.ffoff = cv.take<je_u64>((size_t)P.nchunks);
+    return P;
+}
+
+static int je_shape_fail(const char *who, int64_t h, int64_t w, int channels, int subsampling)
+{
+    return fail(LARS_ERR_UNSUPPORTED, "%s: 1 to 65500 on each side, 1 or 3 channels, subsampling 0 to 2, less than 2^31 samples (got %lld x %lld x %d, %d)",
+                who, (long long)h, (long long)w, channels, subsampling);
 }
 
 }  // namespace lars
@@ -490,7 +499,9 @@ size_t lars_jpeg_encode_scratch_bytes(int64_t h, int64_t w, int channels, int su
 {
     JpegEncGeo g;
     if (!jpeg_enc_geometry(h, w, channels, subsampling, &g)) return 0;
-    return je_layout(g).bytes;
+    Carver size(nullptr);
+    je_plan(g, size);
+    return size.bytes();
 }
 
 int lars_d_encode_jpeg_u8(const uint8_t *img, int64_t h, int64_t w, int channels, int quality, int subsampling, uint8_t *out,
@@ -502,13 +513,12 @@ int lars_d_encode_jpeg_u8(const uint8_t *img, int64_t h, int64_t w, int channels
     if (!img || !out || !out_len_dev || !scratch) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
     if (quality < 1 || quality > 100) return fail(LARS_ERR_INVALID, "%s: quality 1 to 100 (got %d)", who, quality);
     JpegEncGeo g;
-    if (!jpeg_enc_geometry(h, w, channels, subsampling, &g))
-        return fail(LARS_ERR_UNSUPPORTED, "%s: 1 to 65500 on each side, 1 or 3 channels, subsampling 0 to 2, less than 2^31 samples (got %lld x %lld x %d, %d)",
-                    who, (long long)h, (long long)w, channels, subsampling);
+    if (!jpeg_enc_geometry(h, w, channels, subsampling, &g)) return je_shape_fail(who, h, w, channels, subsampling);
     const size_t bound = lars_jpeg_bound(h, w, channels, subsampling);
     if (out_cap < bound) return fail(LARS_ERR_INVALID, "%s: out_cap %zu < lars_jpeg_bound %zu", who, out_cap, bound);
-    const JeLayout L = je_layout(g);
-    if (L.nwg >= (1ll << 31) || L.nchunks >= (1ll << 31)) return fail(LARS_ERR_UNSUPPORTED, "%s: %lld blocks", who, g.nblocks);
+    Carver cv(scratch);
+    const JePlan P = je_plan(g, cv);
+    if (P.nwg >= (1ll << 31) || P.nchunks >= (1ll << 31)) return fail(LARS_ERR_UNSUPPORTED, "%s: %lld blocks", who, g.nblocks);
 
     JeTables A;
     memset(&A, 0, sizeof A);
@@ -518,31 +528,21 @@ int lars_d_encode_jpeg_u8(const uint8_t *img, int64_t h, int64_t w, int channels
         jpeg_enc_qtable(quality, t, q);
         for (int i = 0; i < 64; ++i) A.div[t][i] = (uint16_t)(q[i] << 3);
     }
-    static const uint8_t zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                       41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                       30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-    memcpy(A.zigzag, zigzag, 64);
+    memcpy(A.zigzag, JE_ZIGZAG, 64);
     A.nhead = jpeg_enc_header(g, quality, A.head);
 
-    char *sc = static_cast<char *>(scratch);
-    JeTables *T = reinterpret_cast<JeTables *>(sc + L.tables);
-    JeCtl *ctl = reinterpret_cast<JeCtl *>(sc + L.ctl);
-    short *coef = reinterpret_cast<short *>(sc + L.coef);
-    unsigned int *loc = reinterpret_cast<unsigned int *>(sc + L.loc), *wgsum = reinterpret_cast<unsigned int *>(sc + L.wgsum);
-    je_u64 *wgoff = reinterpret_cast<je_u64 *>(sc + L.wgoff), *ffoff = reinterpret_cast<je_u64 *>(sc + L.ffoff);
-    unsigned int *words = reinterpret_cast<unsigned int *>(sc + L.words), *ffcnt = reinterpret_cast<unsigned int *>(sc + L.ffcnt);
     hipStream_t s = pick_stream(c, stream);
     const unsigned int tgrid = (unsigned int)((long long)g.mcuy * ((g.mcux + JE_MCUS - 1) / JE_MCUS));
-    const unsigned int zgrid = (unsigned int)std::min<je_u64>((L.cap_words + JE_THREADS - 1) / JE_THREADS, 4096);
-    hipLaunchKernelGGL(k_je_setup, dim3(1), dim3(64), 0, s, A, T, ctl);
-    hipLaunchKernelGGL(k_je_transform, dim3(tgrid), dim3(JE_THREADS), 0, s, img, g, T, coef);
-    hipLaunchKernelGGL(k_je_size, dim3((unsigned)L.nwg), dim3(JE_THREADS), 0, s, coef, g, T, loc, wgsum);
-    hipLaunchKernelGGL(k_je_exscan64, dim3(1), dim3(1024), 0, s, wgsum, wgoff, L.nwg, (const je_u64 *)nullptr, &ctl->total_bits);
-    hipLaunchKernelGGL(k_je_zero, dim3(zgrid), dim3(JE_THREADS), 0, s, words, L.cap_words, ctl);
-    hipLaunchKernelGGL(k_je_write, dim3((unsigned)L.nwg), dim3(JE_THREADS), 0, s, coef, g, T, loc, wgoff, words, L.cap_words, ctl);
-    hipLaunchKernelGGL(k_je_count, dim3((unsigned)L.nchunks), dim3(JE_THREADS), 0, s, words, ctl, ffcnt);
-    hipLaunchKernelGGL(k_je_exscan64, dim3(1), dim3(1024), 0, s, ffcnt, ffoff, L.nchunks, &ctl->total_bits, &ctl->total_ff);
-    hipLaunchKernelGGL(k_je_stuff, dim3((unsigned)L.nchunks), dim3(JE_THREADS), 0, s, words, ffoff, T, ctl, out, (je_u64)out_cap,
+    const unsigned int zgrid = (unsigned int)std::min<je_u64>((P.cap_words + JE_THREADS - 1) / JE_THREADS, 4096);
+    hipLaunchKernelGGL(k_je_setup, dim3(1), dim3(64), 0, s, A, P.tables, P.ctl);
+    hipLaunchKernelGGL(k_je_transform, dim3(tgrid), dim3(JE_THREADS), 0, s, img, g, P.tables, P.coef);
+    hipLaunchKernelGGL(k_je_size, dim3((unsigned)P.nwg), dim3(JE_THREADS), 0, s, P.coef, g, P.tables, P.loc, P.wgsum);
+    hipLaunchKernelGGL(k_je_exscan64, dim3(1), dim3(1024), 0, s, P.wgsum, P.wgoff, P.nwg, (const je_u64 *)nullptr, &P.ctl->total_bits);
+    hipLaunchKernelGGL(k_je_zero, dim3(zgrid), dim3(JE_THREADS), 0, s, P.words, P.cap_words, P.ctl);
+    hipLaunchKernelGGL(k_je_write, dim3((unsigned)P.nwg), dim3(JE_THREADS), 0, s, P.coef, g, P.tables, P.loc, P.wgoff, P.words, P.cap_words, P.ctl);
+    hipLaunchKernelGGL(k_je_count, dim3((unsigned)P.nchunks), dim3(JE_THREADS), 0, s, P.words, P.ctl, P.ffcnt);
+    hipLaunchKernelGGL(k_je_exscan64, dim3(1), dim3(1024), 0, s, P.ffcnt, P.ffoff, P.nchunks, &P.ctl->total_bits, &P.ctl->total_ff);
+    hipLaunchKernelGGL(k_je_stuff, dim3((unsigned)P.nchunks), dim3(JE_THREADS), 0, s, P.words, P.ffoff, P.tables, P.ctl, out, (je_u64)out_cap,
                        reinterpret_cast<long long *>(out_len_dev));
     return launch_check(who);
 }
@@ -556,29 +556,11 @@ int lars_h_encode_jpeg_u8(const uint8_t *img, int64_t h, int64_t w, int channels
     LARS_TRY(ensure_ctx(&c));
     if (!img || !out || !out_len) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
     const size_t bound = lars_jpeg_bound(h, w, channels, subsampling), scr = lars_jpeg_encode_scratch_bytes(h, w, channels, subsampling);
-    if (!bound || !scr)
-        return fail(LARS_ERR_UNSUPPORTED, "%s: 1 to 65500 on each side, 1 or 3 channels, subsampling 0 to 2, less than 2^31 samples (got %lld x %lld x %d, %d)",
-                    who, (long long)h, (long long)w, channels, subsampling);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t in_bytes = (size_t)h * w * channels;
-    LARS_TRY(ws_reserve(c, al(in_bytes) + al(bound) + al(scr) + 256));
-    char *p = static_cast<char *>(c->ws);
-    uint8_t *d_in = reinterpret_cast<uint8_t *>(p); p += al(in_bytes);
-    uint8_t *d_out = reinterpret_cast<uint8_t *>(p); p += al(bound);
-    char *d_scr = p; p += al(scr);
-    int64_t *d_len = reinterpret_cast<int64_t *>(p);
-    hipStream_t s = c->stream;
-    LARS_HIP_TRY(hipMemcpyAsync(d_in, img, in_bytes, hipMemcpyHostToDevice, s));
-    LARS_TRY(lars_d_encode_jpeg_u8(d_in, h, w, channels, quality, subsampling, d_out, bound, d_len, d_scr, s));
-    int64_t n = 0;
-    LARS_HIP_TRY(hipMemcpyAsync(&n, d_len, sizeof n, hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    if (n <= 0) return fail(LARS_ERR_HIP, "%s: the device did not finish the file", who);
-    if ((size_t)n > out_cap) return fail(LARS_ERR_INVALID, "%s: the file needs %lld bytes, out_cap is %zu", who, (long long)n, out_cap);
-    LARS_HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n, hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    *out_len = n;
-    return LARS_OK;
+    if (!bound || !scr) return je_shape_fail(who, h, w, channels, subsampling);
+    return encode_to_host(c, who, img, (size_t)h * w * channels, bound, scr, 0, out, out_cap, out_len,
+                          [&](const uint8_t *d_in, uint8_t *d_out, int64_t *d_len, char *d_scr, uint8_t *, hipStream_t s) -> int {
+                              return lars_d_encode_jpeg_u8(d_in, h, w, channels, quality, subsampling, d_out, bound, d_len, d_scr, s);
+                          });
 }
 
 }  // extern "C"

@@ -6,12 +6,9 @@
 
 #include "host_common.h"
 #include "jpeg_parse.h"
+#include "jpeg_tables.h"
 
 namespace {
-
-const uint8_t ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                            41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                            30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 int be16(const uint8_t *p) { return p[0] << 8 | p[1]; }
 
@@ -58,7 +55,7 @@ int jpeg_parse(const uint8_t *file, int64_t len, JpegHeader *H, bool scan_entrop
                 if (pq > 1 || tq > 3 || n - i - 1 < (pq ? 128 : 64)) return fail(LARS_ERR_INVALID, "jpeg: bad DQT segment at byte %lld", (long long)pos - 2);
                 ++i;
                 for (int k = 0; k < 64; ++k) {
-                    H->qt[tq][ZIGZAG[k]] = (uint16_t)(pq ? be16(s + i + 2 * k) : s[i + k]);
+                    H->qt[tq][lars::JE_ZIGZAG[k]] = (uint16_t)(pq ? be16(s + i + 2 * k) : s[i + k]);
                 }
                 i += pq ? 128 : 64;
                 H->q_set[tq] = 1;
@@ -192,19 +189,19 @@ extern "C" int lars_jpeg_info(const uint8_t *file, int64_t len, int64_t info[LAR
     memset(info, 0, sizeof(int64_t) * LARS_JPEG_INFO_N);
     JpegHeader H;
     LARS_TRY(jpeg_parse(file, len, &H, true));
-    info[0] = H.w;
-    info[1] = H.h;
-    info[2] = H.ncomp;
-    info[3] = H.sof;
-    info[4] = H.precision;
+    info[LARS_JPEG_INFO_WIDTH] = H.w;
+    info[LARS_JPEG_INFO_HEIGHT] = H.h;
+    info[LARS_JPEG_INFO_COMPONENTS] = H.ncomp;
+    info[LARS_JPEG_INFO_FRAME] = H.sof;
+    info[LARS_JPEG_INFO_PRECISION] = H.precision;
     for (int c = 0; c < 3 && c < H.ncomp; ++c) {
-        info[5 + 2 * c] = H.hs[c];
-        info[6 + 2 * c] = H.vs[c];
+        info[LARS_JPEG_INFO_H0 + LARS_JPEG_INFO_SAMPLING_STRIDE * c] = H.hs[c];
+        info[LARS_JPEG_INFO_V0 + LARS_JPEG_INFO_SAMPLING_STRIDE * c] = H.vs[c];
     }
-    info[11] = H.ri;
-    info[12] = H.eoff;
-    info[13] = H.elen;
-    info[14] = H.supported;
-    info[15] = H.reason;
+    info[LARS_JPEG_INFO_RESTART_INTERVAL] = H.ri;
+    info[LARS_JPEG_INFO_ENTROPY_OFFSET] = H.eoff;
+    info[LARS_JPEG_INFO_ENTROPY_BYTES] = H.elen;
+    info[LARS_JPEG_INFO_SUPPORTED] = H.supported;
+    info[LARS_JPEG_INFO_REASON] = H.reason;
     return LARS_OK;
 }

@@ -26,6 +26,8 @@ bool jpeg_enc_geometry(int64_t h, int64_t w, int channels, int subsampling, Jpeg
 // Annex K.1 table `which` (0 luminance, 1 chrominance) scaled as libjpeg's jpeg_set_quality does, natural order
 void jpeg_enc_qtable(int quality, int which, uint8_t out[64]);
 void jpeg_enc_codes(JpegEncCodes *c);
+// the zigzag scan: position k holds the natural (row-major) index of coefficient k
+extern const uint8_t JE_ZIGZAG[64];
 // the most bits one block can take: the longest DC code plus its extra bits, and that of an AC code for all 63 coefficients
 int jpeg_enc_max_block_bits();
 // SOI, APP0, DQT(s), SOF0, DHTs, SOS into out[LARS_JPEG_HEADER_MAX]; returns the length

@@ -21,7 +21,7 @@
 //                  chunk's CRC-32 (per-thread pieces shifted by x^(8 * bytes after them) mod P, then XOR).
 #include <string.h>
 
-#include "common.h"
+#include "codec_host.h"
 
 namespace lars {
 
@@ -552,35 +552,46 @@ __global__ __launch_bounds__(PNG_THREADS) void k_png_idat(const uint8_t *__restr
     if (tid == 0) put_be32(dst + 8 + m, part[0]);
 }
 
-struct PngLayout {
-    long long rowb, total, nseg;
-    size_t filt, z, seglen, adl, off, bytes;
-};
-
 static bool png_shape_ok(int64_t h, int64_t w, int channels)
 {
     return h > 0 && w > 0 && h <= (1 << 24) && w <= (1 << 24) && (channels == 1 || channels == 3 || channels == 4);
 }
 
-static PngLayout png_layout(int64_t h, int64_t w, int channels)
+// geometry and the device scratch of one picture: what lars_png_scratch_bytes counts and lars_d_encode_png_u8 points into
+struct PngPlan {
+    long long rowb, total, nseg;
+    uint8_t *filt, *z;
+    unsigned int *seglen, *adl;
+    unsigned long long *off;
+};
+
+static PngPlan png_plan(int64_t h, int64_t w, int channels, Carver &cv)
 {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    PngLayout L;
-    L.rowb = (long long)w * channels;
-    L.total = (long long)h * (L.rowb + 1);
-    L.nseg = (L.total + PNG_SEG - 1) / PNG_SEG;
-    L.filt = 0;
-    L.z = L.filt + al((size_t)L.total);
-    L.seglen = L.z + al((size_t)L.nseg * PNG_ZCAP);
-    L.adl = L.seglen + al((size_t)L.nseg * 4);
-    L.off = L.adl + al((size_t)L.nseg * 8);
-    L.bytes = L.off + al((size_t)L.nseg * 8);
-    return L;
+    PngPlan P;
+    P.rowb = (long long)w * channels;
+    P.total = (long long)h * (P.rowb + 1);
+    P.nseg = (P.total + PNG_SEG - 1) / PNG_SEG;
+    P.filt = cv.take<uint8_t>((size_t)P.total);
+    P.z = cv.take<uint8_t>((size_t)P.nseg * PNG_ZCAP);
+    P.seglen = cv.take<unsigned int>((size_t)P.nseg);
+    P.adl = cv.take<unsigned int>((size_t)P.nseg * 2);
+    P.off = cv.take<unsigned long long>((size_t)P.nseg);
+    return P;
 }
 
 static unsigned long long png_head_bytes(int color_type, int palette_len)
 {
     return 8ull + 25ull + (color_type == 3 ? 24ull + 4ull * palette_len : 0ull);
+}
+
+// the argument checks of both encode entry points; pointers: the caller's own pointers are all set
+static int png_encode_check(const char *who, bool pointers, int64_t h, int64_t w, int channels, const uint8_t *palette_rgba, int palette_len)
+{
+    if (!pointers || h <= 0 || w <= 0 || h > (1 << 24) || w > (1 << 24)) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    if (channels != 1 && channels != 3 && channels != 4) return fail(LARS_ERR_UNSUPPORTED, "%s: 1, 3 or 4 channels (got %d)", who, channels);
+    if (palette_rgba && (channels != 1 || palette_len < 1 || palette_len > 256))
+        return fail(LARS_ERR_INVALID, "%s: a palette needs one channel and 1..256 entries (got %d, %d)", who, channels, palette_len);
+    return LARS_OK;
 }
 
 }  // namespace lars
@@ -594,84 +605,56 @@ extern "C" {
 size_t lars_png_bound(int64_t h, int64_t w, int channels)
 {
     if (!png_shape_ok(h, w, channels)) return 0;
-    const PngLayout L = png_layout(h, w, channels);
-    return (size_t)L.total + (size_t)L.nseg * (5 + 12) + 6 + png_head_bytes(channels == 1 ? 3 : 2, 256) + 12;
+    Carver none(nullptr);
+    const PngPlan P = png_plan(h, w, channels, none);
+    return (size_t)P.total + (size_t)P.nseg * (5 + 12) + 6 + png_head_bytes(channels == 1 ? 3 : 2, 256) + 12;
 }
 
 size_t lars_png_scratch_bytes(int64_t h, int64_t w, int channels)
 {
     if (!png_shape_ok(h, w, channels)) return 0;
-    return png_layout(h, w, channels).bytes;
+    Carver size(nullptr);
+    png_plan(h, w, channels, size);
+    return size.bytes();
 }
 
 int lars_d_encode_png_u8(const uint8_t *img, int64_t h, int64_t w, int channels, const uint8_t *palette_rgba, int palette_len,
                          uint8_t *out, size_t out_cap, int64_t *out_len_dev, void *scratch, void *stream)
 {
+    static const char *who = "lars_d_encode_png_u8";
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
-    if (!img || !out || !out_len_dev || !scratch || h <= 0 || w <= 0 || h > (1 << 24) || w > (1 << 24))
-        return fail(LARS_ERR_INVALID, "lars_d_encode_png_u8: bad arguments");
-    if (channels != 1 && channels != 3 && channels != 4)
-        return fail(LARS_ERR_UNSUPPORTED, "lars_d_encode_png_u8: 1, 3 or 4 channels (got %d)", channels);
-    if (palette_rgba && (channels != 1 || palette_len < 1 || palette_len > 256))
-        return fail(LARS_ERR_INVALID, "lars_d_encode_png_u8: a palette needs one channel and 1..256 entries (got %d, %d)", channels,
-                    palette_len);
+    LARS_TRY(png_encode_check(who, img && out && out_len_dev && scratch, h, w, channels, palette_rgba, palette_len));
     const size_t bound = lars_png_bound(h, w, channels);
-    if (out_cap < bound)
-        return fail(LARS_ERR_INVALID, "lars_d_encode_png_u8: out_cap %zu < lars_png_bound %zu", out_cap, bound);
-    const PngLayout L = png_layout(h, w, channels);
-    if (L.nseg >= (1ll << 31)) return fail(LARS_ERR_UNSUPPORTED, "lars_d_encode_png_u8: %lld segments", L.nseg);
-    char *sc = static_cast<char *>(scratch);
-    uint8_t *filt = reinterpret_cast<uint8_t *>(sc + L.filt), *Z = reinterpret_cast<uint8_t *>(sc + L.z);
-    unsigned int *seglen = reinterpret_cast<unsigned int *>(sc + L.seglen), *adl = reinterpret_cast<unsigned int *>(sc + L.adl);
-    unsigned long long *off = reinterpret_cast<unsigned long long *>(sc + L.off);
+    if (out_cap < bound) return fail(LARS_ERR_INVALID, "%s: out_cap %zu < lars_png_bound %zu", who, out_cap, bound);
+    Carver cv(scratch);
+    const PngPlan P = png_plan(h, w, channels, cv);
+    if (P.nseg >= (1ll << 31)) return fail(LARS_ERR_UNSUPPORTED, "%s: %lld segments", who, P.nseg);
     const int color_type = palette_rgba ? 3 : (channels == 1 ? 0 : (channels == 3 ? 2 : 6));
     hipStream_t s = pick_stream(c, stream);
-    hipLaunchKernelGGL(k_png_filter, dim3((unsigned)h), dim3(PNG_THREADS), 0, s, img, L.rowb, channels, filt);
-    hipLaunchKernelGGL(k_png_deflate, dim3((unsigned)L.nseg), dim3(PNG_THREADS), 0, s, filt, L.total, L.nseg, Z, seglen, adl);
-    hipLaunchKernelGGL(k_png_frame, dim3(1), dim3(PNG_FRAME_THREADS), 0, s, L.nseg, L.total, Z, seglen, adl, off, (int)w, (int)h,
+    hipLaunchKernelGGL(k_png_filter, dim3((unsigned)h), dim3(PNG_THREADS), 0, s, img, P.rowb, channels, P.filt);
+    hipLaunchKernelGGL(k_png_deflate, dim3((unsigned)P.nseg), dim3(PNG_THREADS), 0, s, P.filt, P.total, P.nseg, P.z, P.seglen, P.adl);
+    hipLaunchKernelGGL(k_png_frame, dim3(1), dim3(PNG_FRAME_THREADS), 0, s, P.nseg, P.total, P.z, P.seglen, P.adl, P.off, (int)w, (int)h,
                        color_type, palette_rgba, palette_rgba ? palette_len : 0, png_head_bytes(color_type, palette_len), out,
                        (unsigned long long)out_cap, reinterpret_cast<long long *>(out_len_dev));
-    hipLaunchKernelGGL(k_png_idat, dim3((unsigned)L.nseg), dim3(PNG_THREADS), 0, s, Z, seglen, off, out, (unsigned long long)out_cap);
-    return launch_check("lars_d_encode_png_u8");
+    hipLaunchKernelGGL(k_png_idat, dim3((unsigned)P.nseg), dim3(PNG_THREADS), 0, s, P.z, P.seglen, P.off, out, (unsigned long long)out_cap);
+    return launch_check(who);
 }
 
 // host image in, PNG file out: one upload, then the file's length (one small read) and its bytes
 int lars_h_encode_png_u8(const uint8_t *img, int64_t h, int64_t w, int channels, const uint8_t *palette_rgba, int palette_len,
                          uint8_t *out, size_t out_cap, int64_t *out_len)
 {
+    static const char *who = "lars_h_encode_png_u8";
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
-    if (!img || !out || !out_len || h <= 0 || w <= 0 || h > (1 << 24) || w > (1 << 24))
-        return fail(LARS_ERR_INVALID, "lars_h_encode_png_u8: bad arguments");
-    if (channels != 1 && channels != 3 && channels != 4)
-        return fail(LARS_ERR_UNSUPPORTED, "lars_h_encode_png_u8: 1, 3 or 4 channels (got %d)", channels);
-    if (palette_rgba && (channels != 1 || palette_len < 1 || palette_len > 256))
-        return fail(LARS_ERR_INVALID, "lars_h_encode_png_u8: a palette needs one channel and 1..256 entries (got %d, %d)", channels,
-                    palette_len);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t in_bytes = (size_t)h * w * channels, bound = lars_png_bound(h, w, channels),
-                 scr = lars_png_scratch_bytes(h, w, channels);
-    LARS_TRY(ws_reserve(c, al(in_bytes) + al(bound) + al(scr) + 1024 + 256 + 256));
-    char *p = static_cast<char *>(c->ws);
-    uint8_t *d_in = reinterpret_cast<uint8_t *>(p); p += al(in_bytes);
-    uint8_t *d_out = reinterpret_cast<uint8_t *>(p); p += al(bound);
-    char *d_scr = p; p += al(scr);
-    uint8_t *d_pal = reinterpret_cast<uint8_t *>(p); p += 1024;
-    int64_t *d_len = reinterpret_cast<int64_t *>(p);
-    hipStream_t s = c->stream;
-    LARS_HIP_TRY(hipMemcpyAsync(d_in, img, in_bytes, hipMemcpyHostToDevice, s));
-    if (palette_rgba) LARS_HIP_TRY(hipMemcpyAsync(d_pal, palette_rgba, (size_t)palette_len * 4, hipMemcpyHostToDevice, s));
-    LARS_TRY(lars_d_encode_png_u8(d_in, h, w, channels, palette_rgba ? d_pal : nullptr, palette_len, d_out, bound, d_len, d_scr, s));
-    int64_t n = 0;
-    LARS_HIP_TRY(hipMemcpyAsync(&n, d_len, sizeof n, hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    if (n <= 0) return fail(LARS_ERR_HIP, "lars_h_encode_png_u8: the device did not finish the file");
-    if ((size_t)n > out_cap) return fail(LARS_ERR_INVALID, "lars_h_encode_png_u8: the file needs %lld bytes, out_cap is %zu", (long long)n, out_cap);
-    LARS_HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n, hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    *out_len = n;
-    return LARS_OK;
+    LARS_TRY(png_encode_check(who, img && out && out_len, h, w, channels, palette_rgba, palette_len));
+    const size_t bound = lars_png_bound(h, w, channels);
+    return encode_to_host(c, who, img, (size_t)h * w * channels, bound, lars_png_scratch_bytes(h, w, channels), 1024, out, out_cap, out_len,
+                          [&](const uint8_t *d_in, uint8_t *d_out, int64_t *d_len, char *d_scr, uint8_t *d_pal, hipStream_t s) -> int {
+                              if (palette_rgba) LARS_HIP_TRY(hipMemcpyAsync(d_pal, palette_rgba, (size_t)palette_len * 4, hipMemcpyHostToDevice, s));
+                              return lars_d_encode_png_u8(d_in, h, w, channels, palette_rgba ? d_pal : nullptr, palette_len, d_out, bound, d_len, d_scr, s);
+                          });
 }
 
 }  // extern "C"

@@ -37,7 +37,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "common.h"
+#include "codec_host.h"
 
 namespace lars {
 
@@ -959,9 +959,17 @@ __global__ __launch_bounds__(256) void k_pd_rows(const uint8_t *__restrict__ opa
     }
 }
 
-struct PdLayout {
+// sizes and the device scratch of one file: what lars_png_decode_scratch_bytes counts and lars_d_decode_png_u8 points into
+struct PdPlan {
     unsigned long long nbits, nw, nmark, ncap, bcap, need, nparts, rbp, nslot;
-    size_t ctl, off, words, masks, wgcnt, cands, checks, blocks, lit, src, parts, fpad, ftype, opad, bytes;
+    PdCtl *ctl;
+    unsigned long long *off, *masks, *parts;
+    unsigned int *words, *wgcnt;
+    PdCand *cands;
+    PdCheck *checks;
+    PdBlock *blocks;
+    uint8_t *lit, *fpad, *ftype, *opad;
+    int *src;
 };
 
 static bool pd_shape_ok(int64_t h, int64_t w, int channels)
@@ -970,37 +978,34 @@ static bool pd_shape_ok(int64_t h, int64_t w, int channels)
     return (unsigned long long)h * (1ull + (unsigned long long)w * channels) <= 0x7FFFFFFFull;
 }
 
-static PdLayout pd_layout(int64_t h, int64_t w, int channels, int64_t idat_bytes, int64_t idat_count)
+static PdPlan pd_plan(int64_t h, int64_t w, int channels, int64_t idat_bytes, int64_t idat_count, Carver &cv)
 {
-    PdLayout L{};
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    L.need = (unsigned long long)h * (1ull + (unsigned long long)w * channels);
-    L.nbits = (unsigned long long)idat_bytes * 8;
-    L.nw = (((unsigned long long)idat_bytes + 3) / 4 + 4 + 3) & ~3ull;   // whole quads, at least 4 zero words
-    L.nmark = (L.nbits + PD_MARK_THREADS - 1) / PD_MARK_THREADS;
-    L.ncap = L.nbits / 64 + 256;
+    PdPlan P{};
+    P.need = (unsigned long long)h * (1ull + (unsigned long long)w * channels);
+    P.nbits = (unsigned long long)idat_bytes * 8;
+    P.nw = (((unsigned long long)idat_bytes + 3) / 4 + 4 + 3) & ~3ull;   // whole quads, at least 4 zero words
+    P.nmark = (P.nbits + PD_MARK_THREADS - 1) / PD_MARK_THREADS;
+    P.ncap = P.nbits / 64 + 256;
     // segments: at most one per block that writes image bytes, plus one per checkpoint
-    L.bcap = std::min(L.nbits / 18, L.need) + 2 + L.need / PD_CK + PD_CKMAX;
-    L.nslot = std::min(L.ncap, L.nbits / 4096 + 256);   // candidates that keep checkpoints (the rest: one segment per block)
-    L.nparts = (L.need + 256ull * PD_RESOLVE_BYTES - 1) / (256ull * PD_RESOLVE_BYTES);
-    size_t o = 0;
-    L.ctl = o; o += al(sizeof(PdCtl));
-    L.off = o; o += al((size_t)idat_count * 8);
-    L.words = o; o += al(L.nw * 4);
-    L.masks = o; o += al(L.nmark * (PD_MARK_THREADS / 64) * 8);
-    L.wgcnt = o; o += al(L.nmark * 4);
-    L.cands = o; o += al(L.ncap * sizeof(PdCand));
-    L.checks = o; o += al(L.nslot * PD_CKMAX * sizeof(PdCheck));
-    L.blocks = o; o += al(L.bcap * sizeof(PdBlock));
-    L.lit = o; o += al(L.need);
-    L.src = o; o += al(L.need * 4);
-    L.parts = o; o += al(L.nparts * 16);
-    L.rbp = ((unsigned long long)w * channels + 15) & ~15ull;
-    L.fpad = o; o += al((size_t)h * L.rbp);
-    L.ftype = o; o += al((size_t)h);
-    L.opad = o; o += al((size_t)h * L.rbp);
-    L.bytes = o;
-    return L;
+    P.bcap = std::min(P.nbits / 18, P.need) + 2 + P.need / PD_CK + PD_CKMAX;
+    P.nslot = std::min(P.ncap, P.nbits / 4096 + 256);   // candidates that keep checkpoints (the rest: one segment per block)
+    P.nparts = (P.need + 256ull * PD_RESOLVE_BYTES - 1) / (256ull * PD_RESOLVE_BYTES);
+    P.rbp = ((unsigned long long)w * channels + 15) & ~15ull;
+    P.ctl = cv.take<PdCtl>(1);
+    P.off = cv.take<unsigned long long>((size_t)idat_count);
+    P.words = cv.take<unsigned int>(P.nw);
+    P.masks = cv.take<unsigned long long>(P.nmark * (PD_MARK_THREADS / 64));
+    P.wgcnt = cv.take<unsigned int>(P.nmark);
+    P.cands = cv.take<PdCand>(P.ncap);
+    P.checks = cv.take<PdCheck>(P.nslot * PD_CKMAX);
+    P.blocks = cv.take<PdBlock>(P.bcap);
+    P.lit = cv.take<uint8_t>(P.need);
+    P.src = cv.take<int>(P.need);
+    P.parts = cv.take<unsigned long long>(P.nparts * 2);
+    P.fpad = cv.take<uint8_t>((size_t)h * P.rbp);
+    P.ftype = cv.take<uint8_t>((size_t)h);
+    P.opad = cv.take<uint8_t>((size_t)h * P.rbp);
+    return P;
 }
 
 static const char *pd_deflate_what(int d)
@@ -1031,50 +1036,39 @@ static int pd_status_fail(const char *who, const int st[2])
     }
 }
 
-// host file -> the device image: parse, upload, decode; d_img is h * w * channels bytes; status read back (one sync)
-static int pd_decode_to_device(ThreadCtx *c, const char *who, const uint8_t *file, int64_t len, const int64_t info[LARS_PNG_INFO_N],
-                               const std::vector<int64_t> &table, char *ws, uint8_t **d_img_out)
-{
-    const int64_t w = info[0], h = info[1], ch = info[5], nidat = info[7], idat = info[6];
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    char *p = ws;
-    uint8_t *d_file = reinterpret_cast<uint8_t *>(p); p += al((size_t)len);
-    int64_t *d_tab = reinterpret_cast<int64_t *>(p); p += al((size_t)nidat * 16);
-    uint8_t *d_img = reinterpret_cast<uint8_t *>(p); p += al((size_t)h * w * ch);
-    int32_t *d_st = reinterpret_cast<int32_t *>(p); p += 256;
-    hipStream_t s = c->stream;
-    LARS_HIP_TRY(hipMemcpyAsync(d_file, file, (size_t)len, hipMemcpyHostToDevice, s));
-    LARS_HIP_TRY(hipMemcpyAsync(d_tab, table.data(), (size_t)nidat * 16, hipMemcpyHostToDevice, s));
-    LARS_TRY(lars_d_decode_png_u8(d_file, d_tab, nidat, idat, h, w, (int)ch, d_img, d_st, p, s));
-    int st[2] = {0, 0};
-    LARS_HIP_TRY(hipMemcpyAsync(st, d_st, sizeof st, hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    if (st[0]) return pd_status_fail(who, st);
-    *d_img_out = d_img;
-    return LARS_OK;
-}
+// the PNG side of the host entry points (codec_host.h)
+struct PdFile : HostFile {
+    int64_t ctype, idat_bytes, nidat;
+    std::vector<int64_t> table;
 
-static size_t pd_host_ws_bytes(int64_t len, const int64_t info[LARS_PNG_INFO_N])
-{
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    return al((size_t)len) + al((size_t)info[7] * 16) + al((size_t)info[1] * info[0] * info[5]) + 256 +
-           lars_png_decode_scratch_bytes(info[1], info[0], (int)info[5], info[6], info[7]);
-}
-
-// parse + checks shared by the host entry points
-static int pd_parse(const char *who, const uint8_t *file, int64_t len, int64_t info[LARS_PNG_INFO_N], std::vector<int64_t> &table)
-{
-    if (!file || len <= 0) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
-    LARS_TRY(lars_png_info(file, len, info, nullptr, 0));
-    if (!info[9])
-        return fail(LARS_ERR_UNSUPPORTED, "%s: %s PNG (bit depth %lld, interlace %lld) is not supported", who,
-                    info[8] ? "APNG" : info[4] ? "interlaced" : "this", (long long)info[2], (long long)info[4]);
-    if (!pd_shape_ok(info[1], info[0], (int)info[5]))
-        return fail(LARS_ERR_INVALID, "%s: %lld x %lld x %lld picture is too large", who, (long long)info[1], (long long)info[0],
-                    (long long)info[5]);
-    table.assign((size_t)info[7] * 2, 0);
-    return lars_png_info(file, len, info, table.data(), info[7]);
-}
+    // parse + checks shared by the host entry points
+    int parse(const char *who_, const uint8_t *file_, int64_t len_)
+    {
+        who = who_; file = file_; len = len_;
+        if (!file || len <= 0) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+        int64_t info[LARS_PNG_INFO_N];
+        LARS_TRY(lars_png_info(file, len, info, nullptr, 0));
+        h = info[LARS_PNG_INFO_HEIGHT]; w = info[LARS_PNG_INFO_WIDTH]; channels = (int)info[LARS_PNG_INFO_CHANNELS];
+        ctype = info[LARS_PNG_INFO_COLOR_TYPE]; idat_bytes = info[LARS_PNG_INFO_IDAT_BYTES]; nidat = info[LARS_PNG_INFO_IDAT_COUNT];
+        const long long depth = info[LARS_PNG_INFO_BIT_DEPTH], interlace = info[LARS_PNG_INFO_INTERLACE];
+        if (!info[LARS_PNG_INFO_SUPPORTED])
+            return fail(LARS_ERR_UNSUPPORTED, "%s: %s PNG (bit depth %lld, interlace %lld) is not supported", who,
+                        info[LARS_PNG_INFO_APNG] ? "APNG" : interlace ? "interlaced" : "this", depth, interlace);
+        if (!pd_shape_ok(h, w, channels))
+            return fail(LARS_ERR_INVALID, "%s: %lld x %lld x %lld picture is too large", who, (long long)h, (long long)w, (long long)channels);
+        extra_bytes = (size_t)nidat * 16;                 // the IDAT table
+        scratch_bytes = lars_png_decode_scratch_bytes(h, w, channels, idat_bytes, nidat);
+        table.assign((size_t)nidat * 2, 0);
+        return lars_png_info(file, len, info, table.data(), nidat);
+    }
+    int enqueue(hipStream_t s)
+    {
+        int64_t *d_tab = static_cast<int64_t *>(d_extra);
+        LARS_HIP_TRY(hipMemcpyAsync(d_tab, table.data(), extra_bytes, hipMemcpyHostToDevice, s));
+        return lars_d_decode_png_u8(d_file, d_tab, nidat, idat_bytes, h, w, channels, d_img, d_status, d_scratch, s);
+    }
+    int finish(const int st[2]) { return st[0] ? pd_status_fail(who, st) : LARS_OK; }
+};
 
 }  // namespace lars
 
@@ -1085,7 +1079,9 @@ extern "C" {
 size_t lars_png_decode_scratch_bytes(int64_t h, int64_t w, int channels, int64_t idat_bytes, int64_t idat_count)
 {
     if (!pd_shape_ok(h, w, channels) || idat_bytes < 0 || idat_count < 1 || idat_bytes > (1ll << 40)) return 0;
-    return pd_layout(h, w, channels, idat_bytes, idat_count).bytes;
+    Carver size(nullptr);
+    pd_plan(h, w, channels, idat_bytes, idat_count, size);
+    return size.bytes();
 }
 
 int lars_d_decode_png_u8(const uint8_t *file, const int64_t *idat_table, int64_t idat_count, int64_t idat_bytes, int64_t h, int64_t w,
@@ -1097,54 +1093,42 @@ int lars_d_decode_png_u8(const uint8_t *file, const int64_t *idat_table, int64_t
         return fail(LARS_ERR_INVALID, "lars_d_decode_png_u8: bad arguments");
     if (!pd_shape_ok(h, w, channels))
         return fail(LARS_ERR_INVALID, "lars_d_decode_png_u8: %lld x %lld x %d picture", (long long)h, (long long)w, channels);
-    const PdLayout L = pd_layout(h, w, channels, idat_bytes, idat_count);
-    if (L.nmark >= (1ull << 31) || L.ncap >= (1ull << 32) || L.bcap >= (1ull << 32))
+    Carver cv(scratch);
+    const PdPlan P = pd_plan(h, w, channels, idat_bytes, idat_count, cv);
+    if (P.nmark >= (1ull << 31) || P.ncap >= (1ull << 32) || P.bcap >= (1ull << 32))
         return fail(LARS_ERR_UNSUPPORTED, "lars_d_decode_png_u8: %lld IDAT bytes", (long long)idat_bytes);
-    char *sc = static_cast<char *>(scratch);
-    PdCtl *ctl = reinterpret_cast<PdCtl *>(sc + L.ctl);
-    unsigned long long *off = reinterpret_cast<unsigned long long *>(sc + L.off);
-    unsigned int *words = reinterpret_cast<unsigned int *>(sc + L.words);
-    unsigned long long *masks = reinterpret_cast<unsigned long long *>(sc + L.masks);
-    unsigned int *wgcnt = reinterpret_cast<unsigned int *>(sc + L.wgcnt);
-    PdCand *cands = reinterpret_cast<PdCand *>(sc + L.cands);
-    PdCheck *checks = reinterpret_cast<PdCheck *>(sc + L.checks);
-    PdBlock *blocks = reinterpret_cast<PdBlock *>(sc + L.blocks);
-    uint8_t *lit = reinterpret_cast<uint8_t *>(sc + L.lit);
-    int *src = reinterpret_cast<int *>(sc + L.src);
-    unsigned long long *parts = reinterpret_cast<unsigned long long *>(sc + L.parts);
+    PdCtl *ctl = P.ctl;
     hipStream_t s = pick_stream(c, stream);
     const long long *tab = reinterpret_cast<const long long *>(idat_table);
     LARS_HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(PdCtl), s));
-    LARS_HIP_TRY(hipMemsetAsync(reinterpret_cast<char *>(words) + idat_bytes, 0, L.nw * 4 - (size_t)idat_bytes, s));   // zero tail
-    hipLaunchKernelGGL(k_pd_chunk_scan, dim3(1), dim3(1024), 0, s, tab, (long long)idat_count, off);
+    LARS_HIP_TRY(hipMemsetAsync(reinterpret_cast<char *>(P.words) + idat_bytes, 0, P.nw * 4 - (size_t)idat_bytes, s));   // zero tail
+    hipLaunchKernelGGL(k_pd_chunk_scan, dim3(1), dim3(1024), 0, s, tab, (long long)idat_count, P.off);
     hipLaunchKernelGGL(k_pd_gather, dim3((unsigned)std::min<int64_t>(idat_count, 4096)), dim3(PD_GATHER_THREADS), 0, s, file, tab,
-                       (long long)idat_count, off, reinterpret_cast<uint8_t *>(words), ctl);
-    if (L.nmark) {
-        hipLaunchKernelGGL(k_pd_mark, dim3((unsigned)L.nmark), dim3(PD_MARK_THREADS), 0, s, words, L.nw, L.nbits, masks, wgcnt, ctl);
-        hipLaunchKernelGGL(k_pd_scan_u32, dim3(1), dim3(1024), 0, s, wgcnt, (long long)L.nmark, (unsigned int)L.ncap, ctl);
-        hipLaunchKernelGGL(k_pd_compact, dim3((unsigned)L.nmark), dim3(PD_MARK_THREADS), 0, s, masks, wgcnt, (unsigned int)L.ncap, cands);
-        hipLaunchKernelGGL(k_pd_pass_a, dim3(4096), dim3(64), 0, s, words, L.nw, L.nbits, cands, checks, (unsigned int)L.nslot, ctl);
+                       (long long)idat_count, P.off, reinterpret_cast<uint8_t *>(P.words), ctl);
+    if (P.nmark) {
+        hipLaunchKernelGGL(k_pd_mark, dim3((unsigned)P.nmark), dim3(PD_MARK_THREADS), 0, s, P.words, P.nw, P.nbits, P.masks, P.wgcnt, ctl);
+        hipLaunchKernelGGL(k_pd_scan_u32, dim3(1), dim3(1024), 0, s, P.wgcnt, (long long)P.nmark, (unsigned int)P.ncap, ctl);
+        hipLaunchKernelGGL(k_pd_compact, dim3((unsigned)P.nmark), dim3(PD_MARK_THREADS), 0, s, P.masks, P.wgcnt, (unsigned int)P.ncap, P.cands);
+        hipLaunchKernelGGL(k_pd_pass_a, dim3(4096), dim3(64), 0, s, P.words, P.nw, P.nbits, P.cands, P.checks, (unsigned int)P.nslot, ctl);
     }
-    hipLaunchKernelGGL(k_pd_walk, dim3(1), dim3(64), 0, s, words, L.nw, L.nbits, cands, checks, (unsigned int)L.nslot, blocks,
-                       (unsigned int)L.bcap, L.need, ctl);
-    hipLaunchKernelGGL(k_pd_pass_b, dim3(4096), dim3(64), 0, s, words, L.nw, L.nbits, blocks, L.need, lit, src, ctl);
+    hipLaunchKernelGGL(k_pd_walk, dim3(1), dim3(64), 0, s, P.words, P.nw, P.nbits, P.cands, P.checks, (unsigned int)P.nslot, P.blocks,
+                       (unsigned int)P.bcap, P.need, ctl);
+    hipLaunchKernelGGL(k_pd_pass_b, dim3(4096), dim3(64), 0, s, P.words, P.nw, P.nbits, P.blocks, P.need, P.lit, P.src, ctl);
     int rounds = 1;
-    while ((1ull << (rounds - 1)) < L.need && rounds < 64) ++rounds;
-    const unsigned jgrid = (unsigned)std::min<unsigned long long>((L.need + 255) / 256, 16384);
-    for (int r = 0; r < rounds; ++r) hipLaunchKernelGGL(k_pd_jump, dim3(jgrid), dim3(256), 0, s, src, (long long)L.need, r, ctl);
-    uint8_t *fpad = reinterpret_cast<uint8_t *>(sc + L.fpad), *ftype = reinterpret_cast<uint8_t *>(sc + L.ftype),
-            *opad = reinterpret_cast<uint8_t *>(sc + L.opad);
+    while ((1ull << (rounds - 1)) < P.need && rounds < 64) ++rounds;
+    const unsigned jgrid = (unsigned)std::min<unsigned long long>((P.need + 255) / 256, 16384);
+    for (int r = 0; r < rounds; ++r) hipLaunchKernelGGL(k_pd_jump, dim3(jgrid), dim3(256), 0, s, P.src, (long long)P.need, r, ctl);
     const long long rb = (long long)w * channels;
-    if ((unsigned long long)rb != L.rbp) LARS_HIP_TRY(hipMemsetAsync(fpad, 0, (size_t)h * L.rbp, s));   // zero padding columns
-    hipLaunchKernelGGL(k_pd_resolve, dim3((unsigned)L.nparts), dim3(256), 0, s, lit, src, (long long)L.need, (unsigned int)rb,
-                       (unsigned int)L.rbp, fpad, ftype, parts, ctl);
-    hipLaunchKernelGGL(k_pd_adler, dim3(1), dim3(256), 0, s, parts, (long long)L.nparts, (long long)L.need,
-                       reinterpret_cast<const uint8_t *>(words), ctl);
+    if ((unsigned long long)rb != P.rbp) LARS_HIP_TRY(hipMemsetAsync(P.fpad, 0, (size_t)h * P.rbp, s));   // zero padding columns
+    hipLaunchKernelGGL(k_pd_resolve, dim3((unsigned)P.nparts), dim3(256), 0, s, P.lit, P.src, (long long)P.need, (unsigned int)rb,
+                       (unsigned int)P.rbp, P.fpad, P.ftype, P.parts, ctl);
+    hipLaunchKernelGGL(k_pd_adler, dim3(1), dim3(256), 0, s, P.parts, (long long)P.nparts, (long long)P.need,
+                       reinterpret_cast<const uint8_t *>(P.words), ctl);
     const long long ngroups = (h + 63) / 64;
     const int nwaves = (int)std::min<long long>(ngroups, PD_UNF_WAVES);
-    hipLaunchKernelGGL(k_pd_unfilter, dim3(1), dim3(64 * nwaves), 0, s, fpad, ftype, (long long)h, (long long)L.rbp, channels, opad, ctl);
+    hipLaunchKernelGGL(k_pd_unfilter, dim3(1), dim3(64 * nwaves), 0, s, P.fpad, P.ftype, (long long)h, (long long)P.rbp, channels, P.opad, ctl);
     const unsigned rgrid = (unsigned)std::min<long long>((h * rb + 255) / 256, 8192);
-    hipLaunchKernelGGL(k_pd_rows, dim3(rgrid), dim3(256), 0, s, opad, (long long)h, rb, (long long)L.rbp, out, ctl);
+    hipLaunchKernelGGL(k_pd_rows, dim3(rgrid), dim3(256), 0, s, P.opad, (long long)h, rb, (long long)P.rbp, out, ctl);
     LARS_HIP_TRY(hipMemcpyAsync(status_dev, ctl->status, 8, hipMemcpyDeviceToDevice, s));
     return launch_check("lars_d_decode_png_u8");
 }
@@ -1156,17 +1140,9 @@ int lars_h_decode_png_u8(const uint8_t *file, int64_t len, uint8_t *out, size_t 
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (!out) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
-    int64_t info[LARS_PNG_INFO_N];
-    std::vector<int64_t> table;
-    LARS_TRY(pd_parse(who, file, len, info, table));
-    const size_t bytes = (size_t)info[1] * info[0] * info[5];
-    if (out_cap < bytes) return fail(LARS_ERR_INVALID, "%s: out_cap %zu < %zu", who, out_cap, bytes);
-    LARS_TRY(ws_reserve(c, pd_host_ws_bytes(len, info)));
-    uint8_t *d_img = nullptr;
-    LARS_TRY(pd_decode_to_device(c, who, file, len, info, table, static_cast<char *>(c->ws), &d_img));
-    LARS_HIP_TRY(hipMemcpyAsync(out, d_img, bytes, hipMemcpyDeviceToHost, c->stream));
-    LARS_HIP_TRY(hipStreamSynchronize(c->stream));
-    return LARS_OK;
+    PdFile F;
+    LARS_TRY(F.parse(who, file, len));
+    return decode_file_to_host(c, F, out, out_cap);
 }
 
 // host file in, thumbnail out: the decoded pixels go straight into the thumbnail kernels (resize.hip)
@@ -1177,21 +1153,11 @@ int lars_h_thumbnail_png_u8(const uint8_t *file, int64_t len, int fx, int fy, co
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (!out || !reduce_box || !box) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
-    int64_t info[LARS_PNG_INFO_N];
-    std::vector<int64_t> table;
-    LARS_TRY(pd_parse(who, file, len, info, table));
-    if (info[3] != 0 && info[3] != 2 && info[3] != 6)
-        return fail(LARS_ERR_UNSUPPORTED, "%s: modes L, RGB and RGBA (colour type %lld)", who, (long long)info[3]);
-    const int64_t h = info[1], w = info[0];
-    const int ch = (int)info[5];
-    size_t tneed = 0;
-    LARS_TRY(thumbnail_u8_impl(c, nullptr, true, nullptr, &tneed, h, w, ch, fx, fy, reduce_box, box, new_h, new_w, vertical_first, out));
-    const size_t front = (pd_host_ws_bytes(len, info) + 255) & ~(size_t)255;
-    LARS_TRY(ws_reserve(c, front + tneed));
-    uint8_t *d_img = nullptr;
-    LARS_TRY(pd_decode_to_device(c, who, file, len, info, table, static_cast<char *>(c->ws), &d_img));
-    return thumbnail_u8_impl(c, d_img, true, static_cast<char *>(c->ws) + front, nullptr, h, w, ch, fx, fy, reduce_box, box, new_h,
-                             new_w, vertical_first, out);
+    PdFile F;
+    LARS_TRY(F.parse(who, file, len));
+    if (F.ctype != 0 && F.ctype != 2 && F.ctype != 6)
+        return fail(LARS_ERR_UNSUPPORTED, "%s: modes L, RGB and RGBA (colour type %lld)", who, (long long)F.ctype);
+    return thumbnail_file(c, F, fx, fy, reduce_box, box, new_h, new_w, vertical_first, out);
 }
 
 }  // extern "C"

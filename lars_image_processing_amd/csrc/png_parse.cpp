@@ -67,13 +67,14 @@ extern "C" int lars_png_info(const uint8_t *file, int64_t len, int64_t info[LARS
             if (ihdr) return fail(LARS_ERR_INVALID, "png: misplaced IHDR at byte %lld (second IHDR)", (long long)pos);
             if (n != 13) return fail(LARS_ERR_INVALID, "png: IHDR of %u bytes (13 expected)", n);
             ihdr = true;
-            info[0] = be32(data);
-            info[1] = be32(data + 4);
-            info[2] = data[8];
-            info[3] = data[9];
-            info[4] = data[12];
-            if (info[0] == 0 || info[1] == 0 || info[0] > 0x7FFFFFFF || info[1] > 0x7FFFFFFF)
-                return fail(LARS_ERR_INVALID, "png: IHDR size %lld x %lld", (long long)info[0], (long long)info[1]);
+            const int64_t w = be32(data), h = be32(data + 4);
+            info[LARS_PNG_INFO_WIDTH] = w;
+            info[LARS_PNG_INFO_HEIGHT] = h;
+            info[LARS_PNG_INFO_BIT_DEPTH] = data[8];
+            info[LARS_PNG_INFO_COLOR_TYPE] = data[9];
+            info[LARS_PNG_INFO_INTERLACE] = data[12];
+            if (w == 0 || h == 0 || w > 0x7FFFFFFF || h > 0x7FFFFFFF)
+                return fail(LARS_ERR_INVALID, "png: IHDR size %lld x %lld", (long long)w, (long long)h);
             const int d = data[8], ct = data[9];
             const bool ok = (ct == 0 && (d == 1 || d == 2 || d == 4 || d == 8 || d == 16)) || (ct == 3 && (d == 1 || d == 2 || d == 4 || d == 8)) ||
                             ((ct == 2 || ct == 4 || ct == 6) && (d == 8 || d == 16));
@@ -104,10 +105,10 @@ extern "C" int lars_png_info(const uint8_t *file, int64_t len, int64_t info[LARS
     if (!nidat) return fail(LARS_ERR_INVALID, "png: missing IDAT");
     if (!iend) return fail(LARS_ERR_INVALID, "png: missing IEND (file truncated)");
     static const int chans[7] = {1, 0, 3, 1, 2, 0, 4};
-    info[5] = chans[info[3]];
-    info[6] = idat_bytes;
-    info[7] = nidat;
-    info[8] = apng;
-    info[9] = info[2] == 8 && info[4] == 0 && !apng;
+    info[LARS_PNG_INFO_CHANNELS] = chans[info[LARS_PNG_INFO_COLOR_TYPE]];
+    info[LARS_PNG_INFO_IDAT_BYTES] = idat_bytes;
+    info[LARS_PNG_INFO_IDAT_COUNT] = nidat;
+    info[LARS_PNG_INFO_APNG] = apng;
+    info[LARS_PNG_INFO_SUPPORTED] = info[LARS_PNG_INFO_BIT_DEPTH] == 8 && info[LARS_PNG_INFO_INTERLACE] == 0 && !apng;
     return LARS_OK;
 }

@@ -19,7 +19,7 @@
 #include <cmath>
 #include <vector>
 
-#include "common.h"
+#include "codec_host.h"
 
 namespace lars {
 
@@ -249,14 +249,12 @@ using namespace lars;
 // Image.thumbnail(size, LANCZOS, reducing_gap) of a host uint8 image [h][w][channels] -- process-images.py:186-189, the
 // gallery thumbnails -- on the numbers of api.thumbnail_plan: premultiply (channels 4), Image.reduce((fx, fy)) over
 // reduce_box, the LANCZOS passes over the float box of the reduced image, un-premultiply.  One upload, one download.
-// The body of lars_h_thumbnail_u8.  img is a host image (uploaded to the start of ws) or, with on_device, a device image
-// read in place (lars_h_thumbnail_png_u8: the decoded PNG).  With need_out set it only checks the arguments and gives the
-// workspace bytes ws must hold; otherwise ws (at least that many bytes of device memory) is used and out filled.
-int lars::thumbnail_u8_impl(ThreadCtx *c, const uint8_t *img, bool on_device, char *ws, size_t *need_out, int64_t h, int64_t w,
-                            int channels, int fx, int fy, const int reduce_box[4], const float box[4], int64_t new_h, int64_t new_w,
-                            int vertical_first, uint8_t *out)
+// The body of lars_h_thumbnail_u8 in three steps (codec_host.h): the decoders' thumbnail entry points run the same
+// steps on the decoded image, read in place on the device.
+int lars::thumbnail_prepare(int64_t h, int64_t w, int channels, int fx, int fy, const int reduce_box[4], const float box[4],
+                            int64_t new_h, int64_t new_w, int vertical_first, ThumbJob *Tp)
 {
-    if ((!img && !need_out) || !out || !reduce_box || !box || h <= 0 || w <= 0 || new_h <= 0 || new_w <= 0 || h > (1 << 24) || w > (1 << 24) ||
+    if (!reduce_box || !box || h <= 0 || w <= 0 || new_h <= 0 || new_w <= 0 || h > (1 << 24) || w > (1 << 24) ||
         new_h > (1 << 24) || new_w > (1 << 24) || fx < 1 || fy < 1 || (long long)fx * fy >= (1 << 24))
         return fail(LARS_ERR_INVALID, "lars_h_thumbnail_u8: bad arguments");
     if (channels != 1 && channels != 3 && channels != 4)
@@ -265,78 +263,82 @@ int lars::thumbnail_u8_impl(ThreadCtx *c, const uint8_t *img, bool on_device, ch
     if (rb[0] < 0 || rb[1] < 0 || rb[2] > w || rb[3] > h || rb[2] <= rb[0] || rb[3] <= rb[1])
         return fail(LARS_ERR_INVALID, "lars_h_thumbnail_u8: reduce box (%d, %d, %d, %d) outside the %lld x %lld image", rb[0], rb[1], rb[2],
                     rb[3], (long long)w, (long long)h);
-    const bool reduce = fx != 1 || fy != 1 || rb[0] != 0 || rb[1] != 0 || rb[2] != w || rb[3] != h;
-    const int rw = (rb[2] - rb[0] + fx - 1) / fx, rh = (rb[3] - rb[1] + fy - 1) / fy;
+    ThumbJob &T = *Tp;
+    T.h = h; T.w = w; T.new_h = new_h; T.new_w = new_w;
+    T.channels = channels; T.fx = fx; T.fy = fy;
+    for (int k = 0; k < 4; ++k) T.rb[k] = rb[k];
+    T.vertical_first = vertical_first != 0;
+    T.reduce = fx != 1 || fy != 1 || rb[0] != 0 || rb[1] != 0 || rb[2] != w || rb[3] != h;
+    const int rw = T.rw = (rb[2] - rb[0] + fx - 1) / fx, rh = T.rh = (rb[3] - rb[1] + fy - 1) / fy;
     // `!(a < b)` also refuses NaN
     if (!(box[0] >= 0.0f) || !(box[1] >= 0.0f) || !(box[2] <= (float)rw) || !(box[3] <= (float)rh) || !(box[0] < box[2]) ||
         !(box[1] < box[3]))
         return fail(LARS_ERR_INVALID, "lars_h_thumbnail_u8: box outside the %d x %d reduced image", rw, rh);
     // ImagingResampleInner's need_horizontal / need_vertical
-    const bool need_h = new_w != rw || box[0] != 0.0f || box[2] != (float)new_w;
-    const bool need_v = new_h != rh || box[1] != 0.0f || box[3] != (float)new_h;
-    std::vector<int> bh, kh, bv, kv;
-    const int ksh = need_h ? rs_coeffs(rw, box[0], box[2], (int)new_w, bh, kh) : 0;
-    const int ksv = need_v ? rs_coeffs(rh, box[1], box[3], (int)new_h, bv, kv) : 0;
-    const size_t in_bytes = (size_t)h * w * channels, red_bytes = reduce ? (size_t)rh * rw * channels : 0,
-                 tmp_bytes = std::max((size_t)rh * new_w, (size_t)new_h * rw) * channels, out_bytes = (size_t)new_h * new_w * channels;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // a device image is read in place: no upload copy
-    const size_t need = (on_device ? 0 : al(in_bytes)) + (channels == 4 ? al(in_bytes) : 0) + al(red_bytes) + al(tmp_bytes) + al(out_bytes) + al(bh.size() * 4) +
-                        al(kh.size() * 4) + al(bv.size() * 4) + al(kv.size() * 4) + 1024;
-    if (need_out) {
-        *need_out = need;
-        return LARS_OK;
-    }
-    char *p = ws;
-    uint8_t *d_in = on_device ? const_cast<uint8_t *>(img) : reinterpret_cast<uint8_t *>(p);
-    if (!on_device) p += al(in_bytes);
-    uint8_t *d_pre = nullptr;
-    if (channels == 4) { d_pre = reinterpret_cast<uint8_t *>(p); p += al(in_bytes); }
-    uint8_t *d_red = reinterpret_cast<uint8_t *>(p); p += al(red_bytes);
-    uint8_t *d_tmp = reinterpret_cast<uint8_t *>(p); p += al(tmp_bytes);
-    uint8_t *d_out = reinterpret_cast<uint8_t *>(p); p += al(out_bytes);
-    int *d_bh = reinterpret_cast<int *>(p); p += al(bh.size() * 4);
-    int *d_kh = reinterpret_cast<int *>(p); p += al(kh.size() * 4);
-    int *d_bv = reinterpret_cast<int *>(p); p += al(bv.size() * 4);
-    int *d_kv = reinterpret_cast<int *>(p);
+    T.need_h = new_w != rw || box[0] != 0.0f || box[2] != (float)new_w;
+    T.need_v = new_h != rh || box[1] != 0.0f || box[3] != (float)new_h;
+    T.ksh = T.need_h ? rs_coeffs(rw, box[0], box[2], (int)new_w, T.bh, T.kh) : 0;
+    T.ksv = T.need_v ? rs_coeffs(rh, box[1], box[3], (int)new_h, T.bv, T.kv) : 0;
+    return LARS_OK;
+}
+
+ThumbBufs lars::thumbnail_bufs(const ThumbJob &T, bool on_device, Carver &cv)
+{
+    const size_t C = (size_t)T.channels, in_bytes = (size_t)T.h * T.w * C;
+    ThumbBufs B;
+    B.in = on_device ? nullptr : cv.take<uint8_t>(in_bytes);     // a device image is read in place: no upload copy
+    B.pre = T.channels == 4 ? cv.take<uint8_t>(in_bytes) : nullptr;
+    B.red = cv.take<uint8_t>(T.reduce ? (size_t)T.rh * T.rw * C : 0);
+    B.tmp = cv.take<uint8_t>(std::max((size_t)T.rh * T.new_w, (size_t)T.new_h * T.rw) * C);
+    B.out = cv.take<uint8_t>((size_t)T.new_h * T.new_w * C);
+    B.bh = cv.take<int>(T.bh.size());
+    B.kh = cv.take<int>(T.kh.size());
+    B.bv = cv.take<int>(T.bv.size());
+    B.kv = cv.take<int>(T.kv.size());
+    cv.take<char>(1024);                                         // the slack this workspace has always ended in
+    return B;
+}
+
+int lars::thumbnail_run(ThreadCtx *c, const ThumbJob &T, const ThumbBufs &B, const uint8_t *img, bool on_device, uint8_t *out)
+{
+    const int channels = T.channels, rw = T.rw, rh = T.rh, nw = (int)T.new_w, nh = (int)T.new_h;
     hipStream_t s = c->stream;
-    if (!on_device) LARS_HIP_TRY(hipMemcpyAsync(d_in, img, in_bytes, hipMemcpyHostToDevice, s));
-    if (need_h) {
-        LARS_HIP_TRY(hipMemcpyAsync(d_bh, bh.data(), bh.size() * 4, hipMemcpyHostToDevice, s));
-        LARS_HIP_TRY(hipMemcpyAsync(d_kh, kh.data(), kh.size() * 4, hipMemcpyHostToDevice, s));
+    if (!on_device) LARS_HIP_TRY(hipMemcpyAsync(B.in, img, (size_t)T.h * T.w * channels, hipMemcpyHostToDevice, s));
+    if (T.need_h) {
+        LARS_HIP_TRY(hipMemcpyAsync(B.bh, T.bh.data(), T.bh.size() * 4, hipMemcpyHostToDevice, s));
+        LARS_HIP_TRY(hipMemcpyAsync(B.kh, T.kh.data(), T.kh.size() * 4, hipMemcpyHostToDevice, s));
     }
-    if (need_v) {
-        LARS_HIP_TRY(hipMemcpyAsync(d_bv, bv.data(), bv.size() * 4, hipMemcpyHostToDevice, s));
-        LARS_HIP_TRY(hipMemcpyAsync(d_kv, kv.data(), kv.size() * 4, hipMemcpyHostToDevice, s));
+    if (T.need_v) {
+        LARS_HIP_TRY(hipMemcpyAsync(B.bv, T.bv.data(), T.bv.size() * 4, hipMemcpyHostToDevice, s));
+        LARS_HIP_TRY(hipMemcpyAsync(B.kv, T.kv.data(), T.kv.size() * 4, hipMemcpyHostToDevice, s));
     }
-    const uint8_t *cur = d_in;
+    const uint8_t *cur = on_device ? img : B.in;
     if (channels == 4) {
-        const long long npix = (long long)h * w;
-        hipLaunchKernelGGL(k_premultiply_rgba, dim3((unsigned)((npix + 255) / 256 > 8192 ? 8192 : (npix + 255) / 256)), dim3(256), 0, s, d_in,
-                           d_pre, npix);
-        cur = d_pre;
+        const long long npix = (long long)T.h * T.w;
+        hipLaunchKernelGGL(k_premultiply_rgba, dim3((unsigned)((npix + 255) / 256 > 8192 ? 8192 : (npix + 255) / 256)), dim3(256), 0, s, cur,
+                           B.pre, npix);
+        cur = B.pre;
     }
-    if (reduce) {
-        if (channels == 1) launch_reduce<1>(s, cur, d_red, (int)w, rb, fx, fy, rw, rh);
-        else if (channels == 3) launch_reduce<3>(s, cur, d_red, (int)w, rb, fx, fy, rw, rh);
-        else launch_reduce<4>(s, cur, d_red, (int)w, rb, fx, fy, rw, rh);
-        cur = d_red;
+    if (T.reduce) {
+        if (channels == 1) launch_reduce<1>(s, cur, B.red, (int)T.w, T.rb, T.fx, T.fy, rw, rh);
+        else if (channels == 3) launch_reduce<3>(s, cur, B.red, (int)T.w, T.rb, T.fx, T.fy, rw, rh);
+        else launch_reduce<4>(s, cur, B.red, (int)T.w, T.rb, T.fx, T.fy, rw, rh);
+        cur = B.red;
     }
-    const bool vfirst = vertical_first != 0;
     if (channels == 1)
-        cur = launch_passes<1>(s, cur, d_tmp, d_out, rh, rw, (int)new_h, (int)new_w, need_h, need_v, vfirst, d_bh, d_kh, ksh, d_bv, d_kv, ksv);
+        cur = launch_passes<1>(s, cur, B.tmp, B.out, rh, rw, nh, nw, T.need_h, T.need_v, T.vertical_first, B.bh, B.kh, T.ksh, B.bv, B.kv, T.ksv);
     else if (channels == 3)
-        cur = launch_passes<3>(s, cur, d_tmp, d_out, rh, rw, (int)new_h, (int)new_w, need_h, need_v, vfirst, d_bh, d_kh, ksh, d_bv, d_kv, ksv);
+        cur = launch_passes<3>(s, cur, B.tmp, B.out, rh, rw, nh, nw, T.need_h, T.need_v, T.vertical_first, B.bh, B.kh, T.ksh, B.bv, B.kv, T.ksv);
     else
-        cur = launch_passes<4>(s, cur, d_tmp, d_out, rh, rw, (int)new_h, (int)new_w, need_h, need_v, vfirst, d_bh, d_kh, ksh, d_bv, d_kv, ksv);
+        cur = launch_passes<4>(s, cur, B.tmp, B.out, rh, rw, nh, nw, T.need_h, T.need_v, T.vertical_first, B.bh, B.kh, T.ksh, B.bv, B.kv, T.ksv);
     if (channels == 4) {
-        // cur is d_pre, d_red, d_tmp or d_out here: never the caller's upload
-        const long long npix = (long long)new_h * new_w;
+        // cur is B.pre, B.red, B.tmp or B.out here: never the caller's image
+        const long long npix = (long long)nh * nw;
         hipLaunchKernelGGL(k_unpremultiply_rgba, dim3((unsigned)((npix + 255) / 256 > 8192 ? 8192 : (npix + 255) / 256)), dim3(256), 0, s,
                            const_cast<uint8_t *>(cur), npix);
     }
     LARS_TRY(launch_check("lars_h_thumbnail_u8"));
-    LARS_HIP_TRY(hipMemcpyAsync(out, cur, out_bytes, hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipMemcpyAsync(out, cur, (size_t)nh * nw * channels, hipMemcpyDeviceToHost, s));
     LARS_HIP_TRY(hipStreamSynchronize(s));
     return LARS_OK;
 }
@@ -346,12 +348,12 @@ extern "C" int lars_h_thumbnail_u8(const uint8_t *img, int64_t h, int64_t w, int
 {
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
-    if (!img) return fail(LARS_ERR_INVALID, "lars_h_thumbnail_u8: bad arguments");
-    size_t need = 0;
-    LARS_TRY(thumbnail_u8_impl(c, img, false, nullptr, &need, h, w, channels, fx, fy, reduce_box, box, new_h, new_w, vertical_first, out));
-    LARS_TRY(ws_reserve(c, need));
-    return thumbnail_u8_impl(c, img, false, static_cast<char *>(c->ws), nullptr, h, w, channels, fx, fy, reduce_box, box, new_h, new_w,
-                             vertical_first, out);
+    if (!img || !out) return fail(LARS_ERR_INVALID, "lars_h_thumbnail_u8: bad arguments");
+    ThumbJob T;
+    LARS_TRY(thumbnail_prepare(h, w, channels, fx, fy, reduce_box, box, new_h, new_w, vertical_first, &T));
+    ThumbBufs B;
+    LARS_TRY(ws_plan(c, [&](Carver &cv) { B = thumbnail_bufs(T, false, cv); }));
+    return thumbnail_run(c, T, B, img, false, out);
 }
 
 // PIL.Image.resize((new_w, new_h), LANCZOS) of a host uint8 image [h][w][channels], channels 1, 3 or 4

@@ -39,7 +39,7 @@ def subseq_bits():
 def device_entry_point_with_guards(b, ref):
     """lars_d_decode_jpeg_u8 on a caller's stream into the middle of a buffer: the status is clean, the output is ``ref`` and
     the 4096 bytes on either side of it are untouched."""
-    info = (C.c_int64 * 16)()
+    info = _ffi.JpegInfo.array()
     file = np.frombuffer(b, np.uint8)
     assert _ffi.load().lars_jpeg_info(_ffi.ptr(file), file.size, info) == 0
     need = _ffi.load().lars_jpeg_decode_scratch_bytes(info)
@@ -54,7 +54,7 @@ def device_entry_point_with_guards(b, ref):
     try:
         _ffi.call("lars_memcpy_h2d", d_file, _ffi.ptr(file), file.size)
         _ffi.call("lars_memset", d_out, 0xA5, nbytes + 2 * guard, stream)
-        head = np.ascontiguousarray(file[:info[12]])       # only the head stays on the host
+        head = np.ascontiguousarray(file[:_ffi.JpegInfo(*info).entropy_offset])       # only the head stays on the host
         _ffi.call("lars_d_decode_jpeg_u8", d_file, _ffi.ptr(head), info, C.c_void_p(d_out.value + guard), d_status, d_scratch, stream)
         _ffi.call("lars_synchronize", stream)
         got = np.empty(nbytes + 2 * guard, np.uint8)

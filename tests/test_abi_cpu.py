@@ -68,6 +68,36 @@ def test_the_loaded_library_is_the_product_build():
                 assert gone not in text or name == "fused_v2.hip" and "#if" not in "".join(l for l in text.splitlines() if gone in l), (name, gone)
 
 
+def header_enum(prefix):
+    """{name without the prefix: value} of the header's ``prefix``NAME = value enumerators."""
+    text = open(os.path.join(ROOT, "include", "lars_hip.h")).read()
+    return {m.group(1): int(m.group(2)) for m in re.finditer(r"\b%s([A-Z0-9_]+) = (\d+)" % prefix, text)}
+
+
+def test_info_field_order_matches_header():
+    """The Python names of lars_png_info's / lars_jpeg_info's info[] (_ffi.PngInfo, _ffi.JpegInfo) stand at the positions the
+    header's LARS_PNG_INFO_* / LARS_JPEG_INFO_* enumerators give, and api's table of reasons follows LARS_JPEG_REASON_*."""
+    from lars_image_processing_amd import api
+    text = open(os.path.join(ROOT, "include", "lars_hip.h")).read()
+    png, jpeg = header_enum("LARS_PNG_INFO_"), header_enum("LARS_JPEG_INFO_")
+    assert len(png) == len(_ffi.PngInfo._fields) == int(re.search(r"#define LARS_PNG_INFO_N (\d+)", text).group(1)) == 10
+    assert sorted(png.values()) == list(range(10))
+    for name, k in png.items():
+        assert _ffi.PngInfo._fields[k] == name.lower(), (name, k)
+    assert len(_ffi.JpegInfo._fields) == int(re.search(r"#define LARS_JPEG_INFO_N (\d+)", text).group(1)) == 16
+    stride = int(re.search(r"#define LARS_JPEG_INFO_SAMPLING_STRIDE (\d+)", text).group(1))
+    named = dict(jpeg)
+    for c in (1, 2):                                          # the header names component 0's pair and the stride
+        named["H%d" % c], named["V%d" % c] = jpeg["H0"] + stride * c, jpeg["V0"] + stride * c
+    assert sorted(named.values()) == list(range(16))
+    for name, k in named.items():
+        assert _ffi.JpegInfo._fields[k] == name.lower(), (name, k)
+    assert len(_ffi.PngInfo.array()) == 10 and len(_ffi.JpegInfo.array()) == 16
+    reasons = header_enum("LARS_JPEG_REASON_")
+    assert sorted(reasons.values()) == list(range(len(reasons))) and len(reasons) == 10
+    assert list(api._JPEG_REASONS) == sorted(reasons, key=reasons.get)
+
+
 def test_struct_layouts_match_header():
     assert C.sizeof(_ffi.Stats) == 472 == _ffi.STATS_DTYPE.itemsize
     for name, _ in _ffi.Stats._fields_:

@@ -83,7 +83,7 @@ def split_ms(b, reps=20):
     the device from a resident file into a resident array (lars_d_decode_jpeg_u8), download of the array."""
     lib = _ffi.load()
     file = np.frombuffer(b, np.uint8)
-    info = (C.c_int64 * 16)()
+    info = _ffi.JpegInfo.array()
 
     def med(fn):
         fn()
@@ -97,7 +97,8 @@ def split_ms(b, reps=20):
         return float(np.median(ts)) * 1e3
 
     parse = med(lambda: lib.lars_jpeg_info(_ffi.ptr(file), file.size, info))
-    nbytes = int(info[0] * info[1] * info[2])
+    i = _ffi.JpegInfo(*info)
+    nbytes = int(i.width * i.height * i.components)
     out = np.empty(nbytes, np.uint8)
     d_file, d_out, d_scratch, d_status = (C.c_void_p() for _ in range(4))
     _ffi.call("lars_malloc", C.byref(d_file), file.size)
