@@ -332,7 +332,7 @@ int lars_d_synth_u8(uint8_t *tiles, int64_t ntiles, int64_t first_tile, int64_t 
                     uint32_t seed, int profile, void *stream);
 
 /* Tuning knobs (per process): "fused_impl" 0 (auto)|1|2, "hist_impl" 1|2, "nt_stores" 0|1, "blocks_per_tile" 0 = automatic
- * (also the chunks per tile of lars_d_stats_joint), "joint_depth" 4|6 loads in flight per lane of the counting kernel,
+ * (also the chunks per tile of lars_d_stats_joint), "joint_depth" 4|6|8|12 loads in flight per lane of the counting kernel,
  * "joint_window" 1 (windowed pair tables where they fit: lars_d_stats_joint)|0 (never)|2 (windows that miss on purpose: exercises the
  * recount; tiles of any size)|3 (as 1 for tiles of any size)|4 (three windows -- NIR as well -- wherever they fit, before two are tried; tiles
  * of any size)|5 (as 4 with NIR windows that miss on purpose), "joint_win_depth" 4|5|6|12|15 loads in flight per lane of the windowed counting kernel,

@@ -7,6 +7,7 @@ every compute call raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -306,6 +307,19 @@ def get_tuning(key):
     v = C.c_int(0)
     call("lars_get_tuning", key.encode(), C.byref(v))
     return v.value
+
+
+@contextlib.contextmanager
+def tuning(**kw):
+    """``with tuning(joint_window=0, fused_impl=1): ...`` sets the knobs for the block and puts back what they held before it,
+    whatever that was: after an exception too, and for the knobs already set when a later one is refused.  The state is one per
+    process, so tests and tools change it only through this."""
+    before = {k: get_tuning(k) for k in kw}
+    try:
+        set_tuning(**kw)
+        yield
+    finally:
+        set_tuning(**before)
 
 
 def device_count():

@@ -123,23 +123,23 @@ __host__ __device__ inline double hist_edge_f64(int i) {
 int launch_check(const char *what);
 void align_release();                            // drops the calling thread's cached FFT plan (lars_shutdown)
 
-// tuning knobs (lars_set_tuning)
+// tuning knobs: what each does and its default.  Their names and allowed values: the KNOBS table in runtime.cpp (lars_set_tuning).
 struct Tuning {
-    int fused_impl = 0;        // 0: automatic, 1: first-generation kernels (fused.hip), 2: fused_v2.hip
-    int hist_impl = 2;
+    int fused_impl = 0;        // generation of the fused kernels: automatic, fused.hip or fused_v2.hip
+    int hist_impl = 2;         // generation of the channel-histogram kernel
     int nt_stores = 0;         // non-temporal stores for the float32 planes
-    int blocks_per_tile = 0;   // 0 = automatic
-    int selq_window = 1;       // one-pass medians (select_q.hip): 1 predicted window, 0 always two passes, 2 wrong windows (test)
+    int blocks_per_tile = 0;   // workgroups (chunks) per tile; 0 = automatic
+    int selq_window = 1;       // one-pass medians (select_q.hip): predicted windows, always two passes, or wrong windows (test hook)
     int selq_list_wgs = 0;     // workgroups per launch of the classic select passes over the tiles a window missed (0 = 2048)
     int last_fused_kernel = 0; // read-only: the kernel family lars_d_fused launched last -- 1 k_fused_u8c3, 2 k_fused_v2, 3 uint16, 4 generic, 5 RGBA uint8
-    int u16_hist_impl = 5;     // uint16 percentiles (u16.hip): 5 one full pass on value windows (counts below + histograms inside), 1 always two
-                               // radix passes, 3 test hook (value windows that miss: every tile is flagged and takes the two passes as well)
+    int u16_hist_impl = 5;     // uint16 percentiles (u16.hip): one full pass on value windows (counts below + histograms inside), always two
+                               // radix passes, or a test hook (value windows that miss: every tile is flagged and takes the two passes as well)
     int out_stride_planes = 0; // laboratory build (LARS_LAB_LAYOUT) only: k > 1 = the fused kernel steps k x npix from tile to tile in its index planes
-    int joint_depth = 6;       // joint.hip: 12-byte loads in flight per lane of the counting kernel (4 | 6 | 8 | 12)
-    int joint_win_depth = 15;  // joint_win.hip: loads in flight per lane of the windowed counting kernel: 5 | 15 (a sweep every 15 steps), 4 | 6 | 12 (every 12)
-    int jpeg_subseq_bits = 512;  // jpeg_decode.hip: bits of entropy data per lane of the self-synchronising decode (32 .. 65536)
+    int joint_depth = 6;       // joint.hip: 12-byte loads in flight per lane of the counting kernel
+    int joint_win_depth = 15;  // joint_win.hip: loads in flight per lane of the windowed counting kernel (which also sets how often it sweeps)
+    int jpeg_subseq_bits = 512;  // jpeg_decode.hip: bits of entropy data per lane of the self-synchronising decode
     int jpeg_last_rounds = 0;  // read-only: rounds of k_jd_pass that decoded anything in the last lars_h_decode_jpeg_u8 / lars_h_thumbnail_jpeg_u8 (+100: k_jd_finish ran)
-    int joint_window = 1;      // joint_win.hip: 1 windowed pair tables (one reader per tile chunk) where they fit, 0 never, 2 test hook (windows that miss)
+    int joint_window = 1;      // joint_win.hip: windowed pair tables (one reader per tile chunk) where they fit, never, or test hooks (windows that miss)
 };
 Tuning &tuning();
 

@@ -85,6 +85,44 @@ int scratch_reserve(ThreadCtx *c, size_t bytes) { return reserve(&c->scratch, &c
 static Tuning g_tuning;
 Tuning &tuning() { return g_tuning; }
 
+// Every key of lars_set_tuning / lars_get_tuning: a new knob is one field of Tuning (common.h: what it does, its default) and one
+// row here (who may write it, which values it takes).  include/lars_hip.h describes the keys for users.
+struct Knob {
+    const char *name;
+    int Tuning::*field;
+    enum Access { SET, READ_ONLY, LAB_LAYOUT } access;   // LAB_LAYOUT: set in the laboratory build (make lablayout) only
+    bool (*allowed)(int);                                // nullptr: any integer
+    const char *domain;                                  // the allowed values as the error message names them
+};
+#ifdef LARS_LAB_LAYOUT
+static const bool kLabLayout = true;
+#else
+static const bool kLabLayout = false;
+#endif
+// The READ_ONLY rows are reports: plain ints that a launch from any thread writes, neither per thread nor atomic.
+static const Knob KNOBS[] = {
+    {"fused_impl", &Tuning::fused_impl, Knob::SET, nullptr, nullptr},
+    {"hist_impl", &Tuning::hist_impl, Knob::SET, nullptr, nullptr},
+    {"nt_stores", &Tuning::nt_stores, Knob::SET, nullptr, nullptr},
+    {"blocks_per_tile", &Tuning::blocks_per_tile, Knob::SET, nullptr, nullptr},
+    {"selq_window", &Tuning::selq_window, Knob::SET, nullptr, nullptr},
+    {"selq_list_wgs", &Tuning::selq_list_wgs, Knob::SET, nullptr, nullptr},
+    {"joint_depth", &Tuning::joint_depth, Knob::SET, [](int v) { return v == 4 || v == 6 || v == 8 || v == 12; }, "4, 6, 8 or 12"},
+    {"joint_window", &Tuning::joint_window, Knob::SET, [](int v) { return v >= 0 && v <= 5; }, "0 .. 5"},
+    {"joint_win_depth", &Tuning::joint_win_depth, Knob::SET, [](int v) { return v == 4 || v == 5 || v == 6 || v == 12 || v == 15; }, "4, 5, 6, 12 or 15"},
+    {"out_stride_planes", &Tuning::out_stride_planes, Knob::LAB_LAYOUT, nullptr, nullptr},
+    {"u16_hist_impl", &Tuning::u16_hist_impl, Knob::SET, [](int v) { return v == 5 || v == 1 || v == 3; }, "5, 1 or 3"},
+    {"jpeg_subseq_bits", &Tuning::jpeg_subseq_bits, Knob::SET, [](int v) { return v >= 32 && v <= 65536; }, "32 .. 65536"},
+    {"last_fused_kernel", &Tuning::last_fused_kernel, Knob::READ_ONLY, nullptr, nullptr},
+    {"jpeg_last_rounds", &Tuning::jpeg_last_rounds, Knob::READ_ONLY, nullptr, nullptr},
+};
+static const Knob *find_knob(const char *key)
+{
+    for (const Knob &k : KNOBS)
+        if (!strcmp(key, k.name)) return &k;
+    return nullptr;
+}
+
 int launch_check(const char *what)
 {
     hipError_t e = hipGetLastError();
@@ -274,63 +312,20 @@ unsigned int lars_build_flags(void)
 int lars_set_tuning(const char *key, int value)
 {
     if (!key) return fail(LARS_ERR_INVALID, "lars_set_tuning: NULL key");
-    Tuning &t = tuning();
-    if (!strcmp(key, "fused_impl")) t.fused_impl = value;
-    else if (!strcmp(key, "hist_impl")) t.hist_impl = value;
-    else if (!strcmp(key, "nt_stores")) t.nt_stores = value;
-    else if (!strcmp(key, "blocks_per_tile")) t.blocks_per_tile = value;
-    else if (!strcmp(key, "selq_window")) t.selq_window = value;
-    else if (!strcmp(key, "selq_list_wgs")) t.selq_list_wgs = value;
-    else if (!strcmp(key, "joint_depth")) {
-        if (value != 4 && value != 6 && value != 8 && value != 12) return fail(LARS_ERR_INVALID, "lars_set_tuning: joint_depth is 4, 6, 8 or 12 (got %d)", value);
-        t.joint_depth = value;
-    }
-    else if (!strcmp(key, "joint_window")) {
-        if (value < 0 || value > 5) return fail(LARS_ERR_INVALID, "lars_set_tuning: joint_window is 0 .. 5 (got %d)", value);
-        t.joint_window = value;
-    }
-    else if (!strcmp(key, "joint_win_depth")) {
-        if (value != 4 && value != 5 && value != 6 && value != 12 && value != 15)
-            return fail(LARS_ERR_INVALID, "lars_set_tuning: joint_win_depth is 4, 5, 6, 12 or 15 (got %d)", value);
-        t.joint_win_depth = value;
-    }
-    else if (!strcmp(key, "out_stride_planes")) {
-#ifdef LARS_LAB_LAYOUT
-        t.out_stride_planes = value;
-#else
-        return fail(LARS_ERR_INVALID, "lars_set_tuning: out_stride_planes exists in the laboratory build only (make lablayout); this library would ignore it");
-#endif
-    }
-    else if (!strcmp(key, "u16_hist_impl")) {
-        if (value != 1 && value != 3 && value != 5) return fail(LARS_ERR_INVALID, "lars_set_tuning: u16_hist_impl is 5, 1 or 3 (got %d)", value);
-        t.u16_hist_impl = value;
-    }
-    else if (!strcmp(key, "jpeg_subseq_bits")) {
-        if (value < 32 || value > 65536) return fail(LARS_ERR_INVALID, "lars_set_tuning: jpeg_subseq_bits is 32 .. 65536 (got %d)", value);
-        t.jpeg_subseq_bits = value;
-    }
-    else return fail(LARS_ERR_INVALID, "lars_set_tuning: unknown key %s", key);
+    const Knob *k = find_knob(key);
+    if (!k || k->access == Knob::READ_ONLY) return fail(LARS_ERR_INVALID, "lars_set_tuning: unknown key %s", key);
+    if (k->access == Knob::LAB_LAYOUT && !kLabLayout)
+        return fail(LARS_ERR_INVALID, "lars_set_tuning: %s exists in the laboratory build only (make lablayout); this library would ignore it", key);
+    if (k->allowed && !k->allowed(value)) return fail(LARS_ERR_INVALID, "lars_set_tuning: %s is %s (got %d)", key, k->domain, value);
+    tuning().*k->field = value;
     return LARS_OK;
 }
 int lars_get_tuning(const char *key, int *value)
 {
     if (!key || !value) return fail(LARS_ERR_INVALID, "lars_get_tuning: NULL");
-    const Tuning &t = tuning();
-    if (!strcmp(key, "fused_impl")) *value = t.fused_impl;
-    else if (!strcmp(key, "hist_impl")) *value = t.hist_impl;
-    else if (!strcmp(key, "nt_stores")) *value = t.nt_stores;
-    else if (!strcmp(key, "blocks_per_tile")) *value = t.blocks_per_tile;
-    else if (!strcmp(key, "selq_window")) *value = t.selq_window;
-    else if (!strcmp(key, "selq_list_wgs")) *value = t.selq_list_wgs;
-    else if (!strcmp(key, "joint_depth")) *value = t.joint_depth;
-    else if (!strcmp(key, "joint_window")) *value = t.joint_window;
-    else if (!strcmp(key, "joint_win_depth")) *value = t.joint_win_depth;
-    else if (!strcmp(key, "out_stride_planes")) *value = t.out_stride_planes;
-    else if (!strcmp(key, "u16_hist_impl")) *value = t.u16_hist_impl;
-    else if (!strcmp(key, "last_fused_kernel")) *value = t.last_fused_kernel;
-    else if (!strcmp(key, "jpeg_subseq_bits")) *value = t.jpeg_subseq_bits;
-    else if (!strcmp(key, "jpeg_last_rounds")) *value = t.jpeg_last_rounds;
-    else return fail(LARS_ERR_INVALID, "lars_get_tuning: unknown key %s", key);
+    const Knob *k = find_knob(key);
+    if (!k) return fail(LARS_ERR_INVALID, "lars_get_tuning: unknown key %s", key);
+    *value = tuning().*k->field;
     return LARS_OK;
 }
 

@@ -72,7 +72,6 @@ def main():
         # the one-read route's tables: 0 full, 3 windowed where they fit (tiles of any size), 2 windows that miss on purpose (recount),
         # 4 three windows (NIR as well) wherever they fit, 5 the same with NIR windows that miss
         window = int(rng.choice([0, 3, 3, 2, 4, 4, 5]))
-        _lars_ffi.set_tuning(joint_window=window)
         b = lars.TileBatch.from_host(tiles)
         what = f"case {case}: {kind} {ntiles}x{h}x{w}x{ch} {indices} wb={wb} hist={hist} sumsq={sumsq} medians={med} window={window}"
         try:
@@ -83,7 +82,8 @@ def main():
             if wb:
                 tab_c, pct_c, hist_c = b.host_tables(), b.host_percentiles(), b.host_hist()
                 b.table.zero(); b.percentiles.zero(); b.hist.zero()
-            rj = b.process(indices=indices, white_balance=wb, hist=hist, sumsq=sumsq, medians=med, route="joint", channel_hist=window == 0)
+            with _lars_ffi.tuning(joint_window=window):
+                rj = b.process(indices=indices, white_balance=wb, hist=hist, sumsq=sumsq, medians=med, route="joint", channel_hist=window == 0)
             assert b.last_route == "one-read", b.last_route
             nwin, nrec = b.joint_window_report()
             windowed[window] = windowed.get(window, 0) + nwin
@@ -114,7 +114,6 @@ def main():
         seen[kind] = seen.get(kind, 0) + 1
         if case % 50 == 49:
             print(f"{case + 1} cases ok", flush=True)
-    _lars_ffi.set_tuning(joint_window=1)
     print(f"{args.cases} random batches (seed {args.seed}): one-read route == per-pixel route; contents {dict((str(k), v) for k, v in seen.items())}; "
           f"tiles counted on windowed tables by joint_window setting {windowed}, recounted {recounted}")
     return 0

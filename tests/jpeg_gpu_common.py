@@ -23,17 +23,14 @@ def same(b, name=None):
 
 
 def get_bits():
-    v = C.c_int(0)
-    _ffi.call("lars_get_tuning", b"jpeg_subseq_bits", C.byref(v))
-    return v.value
+    return _ffi.get_tuning("jpeg_subseq_bits")
 
 
 @pytest.fixture
 def subseq_bits():
-    """Sets "jpeg_subseq_bits" for a test and puts the default back afterwards."""
-    default = get_bits()
-    yield lambda v: _ffi.call("lars_set_tuning", b"jpeg_subseq_bits", int(v))
-    _ffi.call("lars_set_tuning", b"jpeg_subseq_bits", default)
+    """A setter of "jpeg_subseq_bits" for a test; what the knob held before the test comes back after it."""
+    with _ffi.tuning(jpeg_subseq_bits=get_bits()):
+        yield lambda v: _ffi.set_tuning(jpeg_subseq_bits=v)
 
 
 def device_entry_point_with_guards(b, ref):

@@ -18,11 +18,10 @@ def lars(request):
     from lars_image_processing_amd import _ffi, batch
     assert _ffi.device_count() >= 1
     impl, route = request.param
-    _ffi.set_tuning(fused_impl=impl, hist_impl=impl)
-    batch.set_stats_route(route)
-    yield mod
-    _ffi.set_tuning(fused_impl=0, hist_impl=2)
-    batch.set_stats_route("auto")
+    with _ffi.tuning(fused_impl=impl, hist_impl=impl):
+        batch.set_stats_route(route)
+        yield mod
+        batch.set_stats_route("auto")
 
 
 def bits(a):
@@ -260,12 +259,11 @@ def test_tuning_does_not_change_results(lars):
     b = lars.TileBatch.synthetic(4, 200, 300, seed=11, profile="vegetation")
     outs = b.make_outputs(index=True)
     ref = None
-    keep = (_ffi.get_tuning("fused_impl"), _ffi.get_tuning("hist_impl"))
     for impl in (1, 2):
         for nt in (0, 1):
             for bpt in (0, 1, 7):
-                _ffi.set_tuning(fused_impl=impl, hist_impl=impl, nt_stores=nt, blocks_per_tile=bpt)
-                rec = b.process(hist=True, sumsq=True, outputs=outs)
+                with _ffi.tuning(fused_impl=impl, hist_impl=impl, nt_stores=nt, blocks_per_tile=bpt):
+                    rec = b.process(hist=True, sumsq=True, outputs=outs)
                 assert_route(b, "one-read+planes", "per-pixel")
                 sumsq = rec["sumsq"].copy()
                 rec["sumsq"] = 0            # the only order-dependent field (double sums of squares)
@@ -274,7 +272,6 @@ def test_tuning_does_not_change_results(lars):
                     ref, ref_sumsq = got, sumsq
                 assert got == ref, (impl, nt, bpt)
                 np.testing.assert_allclose(sumsq, ref_sumsq, rtol=1e-12)
-    _ffi.set_tuning(fused_impl=keep[0], hist_impl=keep[1], nt_stores=0, blocks_per_tile=0)
     outs.free()
     b.free()
 
@@ -389,15 +386,12 @@ def test_uint16_percentiles_one_pass_and_its_recount(lars):
     b = lars.TileBatch.from_host(tiles)
     b.compute_wb_tables()                                            # allocates the blobs (their padding is never written)
     got = {}
-    try:
-        for impl in (5, 1, 3):
-            _ffi.set_tuning(u16_hist_impl=impl)
+    for impl in (5, 1, 3):
+        with _ffi.tuning(u16_hist_impl=impl):
             b.table.zero(); b.percentiles.zero()
             b.compute_wb_tables()
             _ffi.call("lars_synchronize", None)
-            got[impl] = (b.host_percentiles().tobytes(), b.table.download(np.uint8, (b.ntiles, b.table_bytes)).tobytes())
-    finally:
-        _ffi.set_tuning(u16_hist_impl=5)
+        got[impl] = (b.host_percentiles().tobytes(), b.table.download(np.uint8, (b.ntiles, b.table_bytes)).tobytes())
     assert got[1] == got[3] == got[5]
     pcts = b.host_percentiles()
     for i in range(len(tiles)):
@@ -848,17 +842,14 @@ def test_one_pass_medians_and_their_fallback(lars, profile, indices):
         for t in indices:
             want[i, TYPES.index(t)] = float(np.median(orc.index_app(wb, t)))
     results = {}
-    try:
-        for mode in (1, 2, 0):
-            _ffi.set_tuning(selq_window=mode)
+    for mode in (1, 2, 0):
+        with _ffi.tuning(selq_window=mode):
             rec, med = b.process(indices=indices, medians=True)
             assert_route(b, "one-read", "select" if len(indices) in (1, 3) else "per-pixel+select")
             results[mode] = rec.tobytes()
             np.testing.assert_array_equal(med, want, err_msg=f"selq_window={mode}")
             # the medians on their own (what a launch that writes planes uses): prediction + one window sweep + fallback
             np.testing.assert_array_equal(b.tile_medians(indices), want, err_msg=f"tile_medians, selq_window={mode}")
-    finally:
-        _ffi.set_tuning(selq_window=1)
     assert results[1] == results[2] == results[0]
     b.free()
 

@@ -41,9 +41,8 @@ def window(request):
     (csrc/joint_win.hip; the default, 1, needs 2^20 pixels per tile), 2 windows that miss on purpose (every tile is recounted), 4 three
     windows (NIR as well) wherever they fit, 5 the same with NIR windows that miss."""
     from lars_image_processing_amd import _ffi
-    _ffi.set_tuning(joint_window=request.param)
-    yield request.param
-    _ffi.set_tuning(joint_window=1)
+    with _ffi.tuning(joint_window=request.param):
+        yield request.param
 
 
 WINDOWS = pytest.mark.parametrize("window", [0, 3, 2, 4, 5], indirect=True)
@@ -132,13 +131,11 @@ def test_joint_counters_never_overflow(lars, blocks, window):
     ])
     b = lars.TileBatch.from_host(tiles)
     try:
-        _ffi.set_tuning(blocks_per_tile=blocks)
         for wb in (False, True):
-            rec_j, med_j = b.process(white_balance=wb, hist=True, medians=True, route="joint")
-            assert b.last_route == "one-read"
-            _ffi.set_tuning(blocks_per_tile=0)
+            with _ffi.tuning(blocks_per_tile=blocks):
+                rec_j, med_j = b.process(white_balance=wb, hist=True, medians=True, route="joint")
+                assert b.last_route == "one-read"
             rec_c, med_c = b.process(white_balance=wb, hist=True, medians=True, route="classic")
-            _ffi.set_tuning(blocks_per_tile=blocks)
             assert rec_j.tobytes() == rec_c.tobytes()
             np.testing.assert_array_equal(med_j, med_c)
             for i in (0, 2, 3, 4):
@@ -150,7 +147,6 @@ def test_joint_counters_never_overflow(lars, blocks, window):
                     assert med_j[i, k] == float(np.median(plane)), (i, t, wb)
                     assert int(rec_j[i, k]["above"]) == orc.tile_partials(plane, t)["above"]
     finally:
-        _ffi.set_tuning(blocks_per_tile=0)
         b.free()
 
 
@@ -163,20 +159,17 @@ def test_joint_full_size_tiles(lars):
     const[...] = (9, 200, 77)
     b.tiles.upload(const, 5 * b.tile_bytes)                                          # tile 5: one colour
     rec_c, med_c = b.process(hist=True, medians=True, route="classic")
-    try:
-        for blocks in (1, 0, 5):
-            for window in (1, 0, 2, 4, 5):
-                _ffi.set_tuning(blocks_per_tile=blocks, joint_window=window)
+    for blocks in (1, 0, 5):
+        for window in (1, 0, 2, 4, 5):
+            with _ffi.tuning(blocks_per_tile=blocks, joint_window=window):
                 rec_j, med_j = b.process(hist=True, medians=True, route="joint")
-                assert b.last_route == "one-read"
-                # the default: all six tiles on windowed tables (96 + 128 values; the one-colour tile: 3 + 3), nothing recounted;
-                # 4 / 5: on three windows (NIR as well: sweeps and hand-over lists of that kernel at full size), none / all recounted
-                assert b.joint_window_report() == {1: (6, 0), 0: (0, 0), 2: (6, 6), 4: (6, 0), 5: (6, 6)}[window]
-                assert b.joint_window_modes() == {1: (0, 6, 0), 0: (6, 0, 0), 2: (0, 6, 0), 4: (0, 0, 6), 5: (0, 0, 6)}[window]
-                assert rec_j.tobytes() == rec_c.tobytes(), (blocks, window)
-                np.testing.assert_array_equal(med_j, med_c)
-    finally:
-        _ffi.set_tuning(blocks_per_tile=0, joint_window=1)
+            assert b.last_route == "one-read"
+            # the default: all six tiles on windowed tables (96 + 128 values; the one-colour tile: 3 + 3), nothing recounted;
+            # 4 / 5: on three windows (NIR as well: sweeps and hand-over lists of that kernel at full size), none / all recounted
+            assert b.joint_window_report() == {1: (6, 0), 0: (0, 0), 2: (6, 6), 4: (6, 0), 5: (6, 6)}[window]
+            assert b.joint_window_modes() == {1: (0, 6, 0), 0: (6, 0, 0), 2: (0, 6, 0), 4: (0, 0, 6), 5: (0, 0, 6)}[window]
+            assert rec_j.tobytes() == rec_c.tobytes(), (blocks, window)
+            np.testing.assert_array_equal(med_j, med_c)
     n = 4096 * 4096
     assert (rec_j["count"] == n).all() and (rec_j["hist"].sum(axis=2) == n).all()
     tile = b.host_tiles(3, 1)[0]
@@ -339,15 +332,14 @@ def test_hot_cells_survive_the_16_bit_counters(lars, kind, window):
             want, want_med = b.process(indices=indices, hist=True, medians=True, route="classic")
             want_tab = b.host_tables()
             for blocks, depth in ((0, 6), (1, 6), (0, 12), (3, 8)):
-                _ffi.set_tuning(blocks_per_tile=blocks, joint_depth=depth, joint_win_depth={6: 15, 12: 12, 8: 5}[depth] if blocks else 4)
-                got, got_med = b.process(indices=indices, hist=True, medians=True, route="joint")
+                with _ffi.tuning(blocks_per_tile=blocks, joint_depth=depth, joint_win_depth={6: 15, 12: 12, 8: 5}[depth] if blocks else 4):
+                    got, got_med = b.process(indices=indices, hist=True, medians=True, route="joint")
                 assert b.last_route == "one-read"
                 assert got.tobytes() == want.tobytes(), (kind, indices, blocks, depth)
                 np.testing.assert_array_equal(got_med, want_med)
                 for c in sorted(lars.batch.channels_of(indices)):
                     np.testing.assert_array_equal(b.host_tables(partial=True)[:, c], want_tab[:, c])
     finally:
-        _ffi.set_tuning(blocks_per_tile=0, joint_depth=6, joint_win_depth=15)
         b.free()
 
 
@@ -377,8 +369,8 @@ def test_windowed_and_full_tiles_in_one_batch(lars, channels):
         want_tab, want_pct = b.host_tables(), b.host_percentiles()
         for window, expect in ((3, (4, 0)), (2, None), (0, (0, 0)), (4, None), (5, None)):
             for blocks in (0, 1, 3):
-                _ffi.set_tuning(joint_window=window, blocks_per_tile=blocks)
-                got, got_med = b.process(hist=True, medians=True, route="joint")
+                with _ffi.tuning(joint_window=window, blocks_per_tile=blocks):
+                    got, got_med = b.process(hist=True, medians=True, route="joint")
                 assert b.last_route == "one-read"
                 report = b.joint_window_report()
                 assert expect is None or report == expect, (window, report)
@@ -391,7 +383,6 @@ def test_windowed_and_full_tiles_in_one_batch(lars, channels):
                 np.testing.assert_array_equal(b.host_tables(), want_tab)
                 assert b.host_percentiles().tobytes() == want_pct.tobytes()
     finally:
-        _ffi.set_tuning(joint_window=1, blocks_per_tile=0)
         b.free()
 
 
@@ -410,15 +401,14 @@ def test_windowed_ragged_single_tile_and_flavours(lars):
             assert b.last_route == "per-pixel"
             want_tab = b.host_tables()
             for window in (3, 0, 2, 4, 5):
-                _ffi.set_tuning(joint_window=window)
-                got = b.process(hist=True, sumsq=True, rgn_variant=variant, route="joint")
+                with _ffi.tuning(joint_window=window):
+                    got = b.process(hist=True, sumsq=True, rgn_variant=variant, route="joint")
                 assert b.last_route == "one-read"
                 assert b.joint_window_report() == {3: (1, 0), 0: (0, 0), 2: (1, 1), 4: (1, 0), 5: (1, 1)}[window]
                 assert b.joint_window_modes() == {3: (0, 1, 0), 0: (1, 0, 0), 2: (0, 1, 0), 4: (0, 0, 1), 5: (0, 0, 1)}[window]
                 same_records(want, got)
                 np.testing.assert_array_equal(b.host_tables(), want_tab)
     finally:
-        _ffi.set_tuning(joint_window=1)
         b.free()
 
 
@@ -448,8 +438,8 @@ def test_three_windows_where_two_do_not_fit(lars):
             want_tab, want_pct = b.host_tables(), b.host_percentiles()
             for window, modes, recounted in ((3, (0, 0, shape[0]), 0), (5, (0, 0, shape[0]), shape[0]), (0, (shape[0], 0, 0), 0)):
                 for blocks in (0, 3):
-                    _ffi.set_tuning(joint_window=window, blocks_per_tile=blocks)
-                    got, got_med = b.process(hist=True, medians=True, route="joint")
+                    with _ffi.tuning(joint_window=window, blocks_per_tile=blocks):
+                        got, got_med = b.process(hist=True, medians=True, route="joint")
                     assert b.last_route == "one-read"
                     assert b.joint_window_modes() == modes and b.joint_window_report()[1] == recounted, (shape, window)
                     assert got.tobytes() == want.tobytes(), (shape, window, blocks)
@@ -457,7 +447,6 @@ def test_three_windows_where_two_do_not_fit(lars):
                     np.testing.assert_array_equal(b.host_tables(), want_tab)
                     assert b.host_percentiles().tobytes() == want_pct.tobytes()
         finally:
-            _ffi.set_tuning(joint_window=1, blocks_per_tile=0)
             b.free()
 
 

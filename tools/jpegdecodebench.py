@@ -127,9 +127,8 @@ def main():
     if _ffi.device_count() < 1:
         sys.exit("jpegdecodebench: needs a gfx950 GPU (no CPU fallback)")
     import PIL
-    bits = C.c_int(0)
-    _ffi.call("lars_get_tuning", b"jpeg_subseq_bits", C.byref(bits))
-    res = {"device": _ffi.device_name(), "pillow": PIL.__version__, "files": args.files, "jpeg_subseq_bits": bits.value, "kinds": {}}
+    res = {"device": _ffi.device_name(), "pillow": PIL.__version__, "files": args.files, "jpeg_subseq_bits": _ffi.get_tuning("jpeg_subseq_bits"),
+           "kinds": {}}
     for name, (shape, size) in KINDS.items():
         files = [pil_jpeg(a) for a in pictures(shape, args.files, seed=11)]
         assert lars.jpeg_draft_scale((shape[1], shape[0]), size) == 1
@@ -146,17 +145,14 @@ def main():
             r["decode_speedup"] = r["pillow_load_ms"] / r["decode_jpeg_ms"]
             r["thumbnail_speedup"] = r["pillow_thumbnail_ms"] / r["thumbnail_jpeg_ms"]
         lars.decode_jpeg(files[0])
-        _ffi.call("lars_get_tuning", b"jpeg_last_rounds", C.byref(bits))
-        r["sync_rounds_first_file"] = bits.value
-        _ffi.call("lars_get_tuning", b"jpeg_subseq_bits", C.byref(bits))
+        r["sync_rounds_first_file"] = _ffi.get_tuning("jpeg_last_rounds")
         if args.split:
             r["split"] = split_ms(files[0])
         if args.sweep:
             r["sweep_decode_jpeg_ms"] = {}
             for v in (64, 128, 256, 512, 1024, 2048, 4096):
-                _ffi.call("lars_set_tuning", b"jpeg_subseq_bits", v)
-                r["sweep_decode_jpeg_ms"][str(v)] = per_file_ms(lars.decode_jpeg, files, True)
-            _ffi.call("lars_set_tuning", b"jpeg_subseq_bits", bits.value)
+                with _ffi.tuning(jpeg_subseq_bits=v):
+                    r["sweep_decode_jpeg_ms"][str(v)] = per_file_ms(lars.decode_jpeg, files, True)
         res["kinds"][name] = r
         print(name, json.dumps(r), flush=True)
     if args.json:

@@ -77,14 +77,13 @@ def main():
         times = {v: [] for v in variants}
         for _ in range(args.rounds + 1):
             for v in variants:
-                _ffi.set_tuning(hist_impl=v[0], blocks_per_tile=v[1])
-                times[v].append(timer.time(lambda: _ffi.call(
-                    "lars_d_channel_hist", C.c_void_p(b.tiles.ptr), b.ntiles, b.npix, 3, _ffi.U8,
-                    C.c_void_p(b.hist.ptr), None)))
+                with _ffi.tuning(hist_impl=v[0], blocks_per_tile=v[1]):
+                    times[v].append(timer.time(lambda: _ffi.call(
+                        "lars_d_channel_hist", C.c_void_p(b.tiles.ptr), b.ntiles, b.npix, 3, _ffi.U8,
+                        C.c_void_p(b.hist.ptr), None)))
         for v, t in times.items():
             med = float(np.median(t[1:]))
             results[f"hist impl={v[0]} bpt={v[1]}"] = {"ms": med, "min_ms": float(min(t[1:])), "GBs": npix * 3 / med / 1e6}
-        _ffi.set_tuning(blocks_per_tile=0)
 
     if "fused" in args.what:
         modes = [m for m in args.modes.split(",") if m]
@@ -108,7 +107,6 @@ def main():
                     if indices not in outs_cache:
                         outs_cache[indices] = b.make_outputs(indices=indices, index=True, ring=args.ring)
                     outs = outs_cache[indices]
-                _ffi.set_tuning(fused_impl=impl, nt_stores=nt, blocks_per_tile=bp)
 
                 def run():
                     if outs is None:
@@ -117,7 +115,8 @@ def main():
                         for start in range(0, b.ntiles, outs.slots):
                             cnt = min(outs.slots, b.ntiles - start)
                             b.run_fused(b.fused_args(indices, bool(wb), stats, hist, outs, None, start, cnt))
-                times[v].append(timer.time(run))
+                with _ffi.tuning(fused_impl=impl, nt_stores=nt, blocks_per_tile=bp):
+                    times[v].append(timer.time(run))
         for v, t in times.items():
             m, impl, nt, bp, wb = v
             med = float(np.median(t[1:]))

@@ -73,20 +73,18 @@ def main():
         for j, arena in enumerate(arenas):
             row = []
             for inter in (0, 1, 0, 1):
-                _ffi.set_tuning(out_stride_planes=3 if inter else 0)
-                ls = launches_for(arena, inter)
-                burst(ls)
-                t = burst(ls)
+                with _ffi.tuning(out_stride_planes=3 if inter else 0):
+                    ls = launches_for(arena, inter)
+                    burst(ls)
+                    t = burst(ls)
                 row.append(float(np.mean(t[1:])))
-            _ffi.set_tuning(out_stride_planes=0)
             print(f"round {rnd} arena {j}: planar {row[0]:.3f} interleaved {row[1]:.3f} planar {row[2]:.3f} interleaved {row[3]:.3f}", flush=True)
     # correctness of the interleaved form on one tile group: plane k of slot s at (3 s + k) * npix
-    _ffi.set_tuning(out_stride_planes=3)
-    ls = launches_for(arenas[0], 1)
-    b.run_fused(ls[-1])
-    _ffi.call("lars_synchronize", None)
+    with _ffi.tuning(out_stride_planes=3):
+        ls = launches_for(arenas[0], 1)
+        b.run_fused(ls[-1])
+        _ffi.call("lars_synchronize", None)
     got = arenas[0].download(np.float32, (3, b.npix), (3 * 5) * b.npix * 4)          # slot 5 of the last chunk
-    _ffi.set_tuning(out_stride_planes=0)
     ls = launches_for(arenas[1], 0)
     b.run_fused(ls[-1])
     _ffi.call("lars_synchronize", None)

@@ -35,16 +35,15 @@ def main():
     ref = None
     for _ in range(args.rounds + 1):
         for v in variants:
-            _ffi.set_tuning(selq_window=1 if v[0] == "window" else 0, selq_list_wgs=v[1])
-            _ffi.call("lars_synchronize", None)
-            t0 = time.perf_counter()
-            rec, med = b.process(medians=True, recompute_tables=False)
-            times[v].append((time.perf_counter() - t0) * 1e3)
+            with _ffi.tuning(selq_window=1 if v[0] == "window" else 0, selq_list_wgs=v[1]):
+                _ffi.call("lars_synchronize", None)
+                t0 = time.perf_counter()
+                rec, med = b.process(medians=True, recompute_tables=False)
+                times[v].append((time.perf_counter() - t0) * 1e3)
             med = np.asarray(med)
             if ref is None:
                 ref = med.copy()
             assert np.array_equal(ref, med, equal_nan=True), v
-    _ffi.set_tuning(selq_window=1, selq_list_wgs=0)
     npix = args.tiles * args.tile * args.tile
     for v, t in times.items():
         m = float(np.median(t[1:]))

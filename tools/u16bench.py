@@ -28,10 +28,9 @@ def main():
                        (3, "wb_prepare (windows that miss on purpose: full pass + the two radix passes)"),
                        (50, "wb_prepare (value windows once more)")):
         impl = 5 if impl == 50 else impl
-        _ffi.set_tuning(u16_hist_impl=impl)
-        t = timed(lambda: b.compute_wb_tables())
+        with _ffi.tuning(u16_hist_impl=impl):
+            t = timed(lambda: b.compute_wb_tables())
         res[name] = {"ms": t, "GBs_input_once": npix * 6 / t / 1e6, "frac_8TBs": npix * 6 / t / 1e6 / 8000}
-    _ffi.set_tuning(u16_hist_impl=5)
     stats = b.new_stats()
     outs = b.make_outputs(indices=("NDVI",), index=True, rgba=True)
     for name, kw, bpp in (("ndvi_f32+rgba+stats (configs[4])", dict(indices=("NDVI",), outputs=outs), 14),
