@@ -622,6 +622,62 @@ int lars_h_tiff_lzw_decode(const uint8_t *src, int64_t nsrc, uint8_t *dst, int64
 int lars_h_tiff_lzw_decode_chunks(const uint8_t *file, int64_t file_len, const uint64_t *offsets, const uint64_t *counts,
                                   int64_t nchunks, uint8_t *dst, int64_t chunk_bytes, int64_t *produced, int threads);
 
+/* TIFF files decoded on the device -- the Image.open(io.BytesIO(...)) of an upload (process-images.py:183, :228) for the first
+ * of the accepted extensions (process-images.py:1237, backend-process.py:88) and the format the reference writes itself
+ * (backend-process.py:57), plus the thumbnail after it (process-images.py:186-189).
+ * Covered: classic TIFF, first directory, either byte order, 8 or 16 bit unsigned samples (equal across samples), no
+ * compression or LZW, predictor 1 or 2, chunky or planar, strips or tiles.  The pixels come out as tiffio.read_tiff gives
+ * them: [h][w][samples] ([h][w] for one sample), uint8 or native-endian uint16.
+ * lars_tiff_info: pure host code.  Walks the first directory of file[0..len) by read_tiff's rules, checks every offset and
+ * count against len, and fills info[LARS_TIFF_INFO_N] (positions below); chunk_table (may be NULL with table_cap 0)
+ * receives { offset, byte count } of the first table_cap strips / tiles.  A valid file the device does not decode has
+ * supported 0 and a LARS_TIFF_REASON_*; structural damage is LARS_ERR_INVALID.
+ * lars_h_decode_tiff: host file in, host samples out (out_cap in BYTES >= h * w * samples * bits / 8); one upload, one download.
+ * lars_h_thumbnail_tiff_u8: host file in (8 bit, one BlackIsZero sample or RGB, no extra samples), lars_h_thumbnail_u8's
+ * plan numbers, host thumbnail out; the decoded pixels never leave the device. */
+#define LARS_TIFF_INFO_N 16
+enum {                           /* positions in lars_tiff_info's info[] */
+    LARS_TIFF_INFO_WIDTH = 0,
+    LARS_TIFF_INFO_HEIGHT = 1,
+    LARS_TIFF_INFO_SAMPLES = 2,
+    LARS_TIFF_INFO_BITS = 3,
+    LARS_TIFF_INFO_COMPRESSION = 4,
+    LARS_TIFF_INFO_PREDICTOR = 5,
+    LARS_TIFF_INFO_PLANAR = 6,
+    LARS_TIFF_INFO_BIG_ENDIAN = 7,
+    LARS_TIFF_INFO_PHOTOMETRIC = 8,   /* -1: the tag is missing */
+    LARS_TIFF_INFO_EXTRA_SAMPLES = 9,
+    LARS_TIFF_INFO_TILED = 10,
+    LARS_TIFF_INFO_CHUNK_W = 11,
+    LARS_TIFF_INFO_CHUNK_H = 12,
+    LARS_TIFF_INFO_CHUNKS = 13,
+    LARS_TIFF_INFO_SUPPORTED = 14,
+    LARS_TIFF_INFO_REASON = 15
+};
+enum {
+    LARS_TIFF_REASON_NONE = 0,
+    LARS_TIFF_REASON_BIGTIFF = 1,        /* 64-bit offsets (magic 43) */
+    LARS_TIFF_REASON_BITS = 2,           /* samples that are not all 8 or all 16 bits wide */
+    LARS_TIFF_REASON_SAMPLE_FORMAT = 3,  /* signed or floating-point samples */
+    LARS_TIFF_REASON_DEFLATE = 4,        /* compression 8 / 32946 (tiffio.read_tiff reads them) */
+    LARS_TIFF_REASON_PACKBITS = 5,
+    LARS_TIFF_REASON_JPEG = 6,           /* compression 6 / 7 */
+    LARS_TIFF_REASON_CCITT = 7,          /* compression 2, 3, 4 */
+    LARS_TIFF_REASON_COMPRESSION = 8,    /* any other scheme */
+    LARS_TIFF_REASON_PREDICTOR = 9,      /* other than 1 and 2 (floating-point predictor) */
+    LARS_TIFF_REASON_OLD_LZW = 10,       /* a strip in the old bit order (LSB first), which lars_h_tiff_lzw_decode refuses too */
+    LARS_TIFF_REASON_SIZE = 11           /* 2^31 or more decoded bytes (tile padding included) */
+};
+enum {
+    LARS_TIFD_OK = 0,
+    LARS_TIFD_CORRUPT = 1,       /* an LZW code the table does not hold; detail: the strip / tile */
+    LARS_TIFD_SHORT = 2          /* a strip / tile decodes to too few bytes; detail: the strip / tile */
+};
+int lars_tiff_info(const uint8_t *file, int64_t len, int64_t info[LARS_TIFF_INFO_N], int64_t *chunk_table, int64_t table_cap);
+int lars_h_decode_tiff(const uint8_t *file, int64_t len, void *out, size_t out_cap);
+int lars_h_thumbnail_tiff_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
+                             int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out);
+
 /* ------------------------------------------------------------------ multi-GPU */
 /* One process per GPU.  RCCL (librccl.so) is loaded on first use.  unique_id is
  * LARS_COMM_ID_BYTES bytes produced by lars_comm_unique_id() on rank 0 and

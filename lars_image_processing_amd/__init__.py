@@ -22,6 +22,7 @@ from .api import (  # noqa: F401
     decode_jpeg,
     encode_jpeg,
     decode_png,
+    decode_tiff,
     encode_png,
     download_processed_images,
     fix_white_balance,
@@ -37,6 +38,8 @@ from .api import (  # noqa: F401
     thumbnail_jpeg,
     thumbnail_plan,
     thumbnail_png,
+    thumbnail_tiff,
+    tiff_info,
     time_series_points,
     timeseries_row,
 )

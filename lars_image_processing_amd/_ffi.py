@@ -114,6 +114,30 @@ class JpegInfo(NamedTuple):
         return ((self.h0, self.v0), (self.h1, self.v1), (self.h2, self.v2))
 
 
+class TiffInfo(NamedTuple):
+    """``info[LARS_TIFF_INFO_N]`` of ``lars_tiff_info``, in the order of the header's ``LARS_TIFF_INFO_*``."""
+    width: int
+    height: int
+    samples: int
+    bits: int
+    compression: int
+    predictor: int
+    planar: int
+    big_endian: int
+    photometric: int
+    extra_samples: int
+    tiled: int
+    chunk_w: int
+    chunk_h: int
+    chunks: int
+    supported: int
+    reason: int
+
+    @classmethod
+    def array(cls):
+        return (C.c_int64 * len(cls._fields))()
+
+
 # name -> (restype, argtypes).  Every symbol include/lars_hip.h declares.
 _P, _I, _I64, _U32, _SZ, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_size_t, C.c_float, C.c_double
 SIGNATURES = {
@@ -212,6 +236,9 @@ SIGNATURES = {
     "lars_d_decode_jpeg_u8": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "lars_h_decode_jpeg_u8": (_I, [_P, _I64, _P, _SZ]),
     "lars_h_thumbnail_jpeg_u8": (_I, [_P, _I64, _I, _I, C.POINTER(_I), C.POINTER(_F), _I64, _I64, _I, _P]),
+    "lars_tiff_info": (_I, [_P, _I64, _P, _P, _I64]),
+    "lars_h_decode_tiff": (_I, [_P, _I64, _P, _SZ]),
+    "lars_h_thumbnail_tiff_u8": (_I, [_P, _I64, _I, _I, C.POINTER(_I), C.POINTER(_F), _I64, _I64, _I, _P]),
     "lars_jpeg_bound": (_SZ, [_I64, _I64, _I, _I]),
     "lars_jpeg_header": (_I64, [_I64, _I64, _I, _I, _I, _P, _SZ]),
     "lars_jpeg_encode_scratch_bytes": (_SZ, [_I64, _I64, _I, _I]),

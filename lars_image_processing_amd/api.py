@@ -632,7 +632,7 @@ _PNG_MODES = {(1, 0): "1", (2, 0): "L", (4, 0): "L", (8, 0): "L", (16, 0): "I;16
 
 
 def _file_bytes(data, who, fmt):
-    """The bytes of a whole ``fmt`` ("PNG", "JPEG") file as a contiguous 1-D uint8 array."""
+    """The bytes of a whole ``fmt`` ("PNG", "JPEG", "TIFF") file as a contiguous 1-D uint8 array."""
     if isinstance(data, (bytes, bytearray, memoryview)):
         arr = np.frombuffer(data, dtype=np.uint8)
     elif isinstance(data, np.ndarray) and data.dtype == np.uint8 and data.ndim == 1:
@@ -811,6 +811,116 @@ def thumbnail_jpeg(data, size=(400, 400), reducing_gap=2.0):
     if plan is None:
         return decode_jpeg(arr)
     return _file_thumbnail("lars_h_thumbnail_jpeg_u8", arr, plan, c)
+
+
+# ---------------------------------------------------------------------------
+# TIFF files decoded on the device
+# ---------------------------------------------------------------------------
+# why a file is not decoded, by the header's LARS_TIFF_REASON_* names, in the order of their values (tests/test_tiff_decode_cpu.py)
+_TIFF_REASONS = {"NONE": None, "BIGTIFF": "BigTIFF (64-bit offsets)", "BITS": "samples that are not all 8 or all 16 bits wide",
+                 "SAMPLE_FORMAT": "signed or floating-point samples", "DEFLATE": "Deflate compression (read_tiff reads it on the host)",
+                 "PACKBITS": "PackBits compression", "JPEG": "JPEG compression", "CCITT": "CCITT compression",
+                 "COMPRESSION": "an unknown compression scheme", "PREDICTOR": "a predictor other than 1 and 2",
+                 "OLD_LZW": "old-style (LSB-first) LZW", "SIZE": "2^31 or more decoded bytes"}
+_TIFF_REASON_TEXT = dict(enumerate(_TIFF_REASONS.values()))
+
+
+def _tiff_info(arr):
+    lib = _ffi.load()
+    info = _ffi.TiffInfo.array()
+    if lib.lars_tiff_info(_ffi.ptr(arr), arr.size, info, None, 0) != 0:
+        raise ValueError(lib.lars_last_error().decode("utf-8", "replace"))
+    return _ffi.TiffInfo(*info)
+
+
+def _tiff_shape(i):
+    return (i.height, i.width) if i.samples == 1 else (i.height, i.width, i.samples)
+
+
+def tiff_info(data):
+    """The first directory of a TIFF file, read on the host by ``tiffio.read_tiff``'s rules (``lars_tiff_info``; no device needed).
+
+    Returns ``width``, ``height``, ``samples``, ``bits``, ``compression``, ``predictor``, ``planar``, ``big_endian``,
+    ``photometric`` (-1: no such tag), ``extra_samples``, ``tiled``, ``chunk_w``, ``chunk_h``, ``chunks`` (strips / tiles),
+    ``dtype`` and ``shape`` of the array ``decode_tiff`` gives (``None`` where the directory does not say), ``supported`` and
+    ``reason`` (``None``, or why the device does not decode it: Deflate, PackBits, JPEG, CCITT, old-style LZW, other bit
+    depths, signed or float samples, BigTIFF, 2^31 bytes or more).  Raises ``ValueError`` for structural damage: no byte-order
+    mark, a directory, a tag's values or a strip / tile outside the file, a missing required tag, a wrong number of strips.
+    """
+    i = _tiff_info(_file_bytes(data, "tiff_info", "TIFF"))
+    out = i._asdict()
+    for k in ("big_endian", "tiled", "supported"):
+        out[k] = bool(out[k])
+    known = i.bits in (8, 16) and i.width > 0 and i.height > 0 and i.samples > 0
+    out["dtype"] = np.dtype(np.uint8 if i.bits == 8 else np.uint16) if known else None
+    out["shape"] = _tiff_shape(i) if known else None
+    out["reason"] = _TIFF_REASON_TEXT.get(i.reason, str(i.reason))
+    return out
+
+
+def _tiff_check(arr, who):
+    from .tiffio import TiffError
+    try:
+        i = _tiff_info(arr)
+    except ValueError as e:
+        raise TiffError(str(e)) from None
+    if not i.supported:
+        raise NotImplementedError(f"{who}: TIFF files with {_TIFF_REASON_TEXT.get(i.reason, i.reason)} are not decoded on the device "
+                                  "(classic TIFF, 8 or 16 bit unsigned samples, uncompressed or LZW)")
+    return i
+
+
+def _tiff_call(name, *args):
+    from .tiffio import TiffError
+    try:
+        _ffi.call(name, *args)
+    except _ffi.LarsError as e:
+        if e.code == -1:
+            raise TiffError(str(e)) from None
+        raise
+
+
+def decode_tiff(data):
+    """``tiffio.read_tiff(data)`` of a TIFF file, decoded on the GPU: the same array bit for bit, dtype and shape included
+    (the ``Image.open(io.BytesIO(...))`` of process-images.py:183 for the first accepted extension, at the file's full depth).
+
+    ``data``: the whole file as ``bytes``, ``bytearray``, ``memoryview`` or a 1-D uint8 array.  Classic TIFF, first
+    directory, either byte order, 8 or 16 bit unsigned samples, uncompressed or LZW, predictor 1 or 2, chunky or planar,
+    strips or tiles: ``[H, W, C]`` (``[H, W]`` for one sample) uint8 or native-endian uint16.  Other variants
+    (``tiff_info(data)["reason"]``) raise ``NotImplementedError`` before anything is launched; damaged files raise
+    ``tiffio.TiffError`` (a ``ValueError``) where ``read_tiff`` does.  No CPU fallback.
+    """
+    arr = _file_bytes(data, "decode_tiff", "TIFF")
+    i = _tiff_check(arr, "decode_tiff")
+    out = np.empty(_tiff_shape(i), dtype=np.uint8 if i.bits == 8 else np.uint16)
+    _tiff_call("lars_h_decode_tiff", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
+    return out
+
+
+def _tiff_is_pillow_u8(i):
+    """8-bit files Pillow opens as mode L or RGB with the samples as stored: one BlackIsZero sample, or RGB, no extra samples."""
+    return i.bits == 8 and i.extra_samples == 0 and ((i.samples == 1 and i.photometric == 1) or (i.samples == 3 and i.photometric == 2))
+
+
+def thumbnail_tiff(data, size=(400, 400), reducing_gap=2.0):
+    """``np.asarray`` of ``Image.open(io.BytesIO(data))`` after ``.thumbnail(size, LANCZOS, reducing_gap)``, bit for bit
+    (process-images.py:186-189), from a TIFF file's bytes: the decoded pixels stay on the GPU and go straight into the
+    thumbnail kernels, only the thumbnail comes back.  8-bit files with one sample (BlackIsZero) or three (RGB) and no
+    extra samples; others raise ``TypeError``.  ``draft`` does nothing for TIFF, so ``thumbnail_plan(..., draft_box=None)``
+    is the whole plan; a file that already fits comes back as ``decode_tiff`` gives it.  Errors of the file as ``decode_tiff``."""
+    arr = _file_bytes(data, "thumbnail_tiff", "TIFF")
+    i = _tiff_check(arr, "thumbnail_tiff")
+    if not _tiff_is_pillow_u8(i):
+        raise TypeError(f"thumbnail_tiff: 8-bit TIFF files in mode L or RGB (got {i.samples} samples of {i.bits} bits, "
+                        f"photometric {i.photometric}, {i.extra_samples} extra samples)")
+    plan = thumbnail_plan((i.width, i.height), size, reducing_gap, None, None)
+    if plan is None:
+        return decode_tiff(arr)
+    from .tiffio import TiffError
+    try:
+        return _file_thumbnail("lars_h_thumbnail_tiff_u8", arr, plan, i.samples)
+    except ValueError as e:
+        raise TiffError(str(e)) from None
 
 
 def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_arrays=True, want_hist=False,

@@ -1,4 +1,4 @@
-// Host steps that the file codecs share (png.hip, jpeg_encode.hip, png_decode.hip, jpeg_decode.hip) and the thumbnail
+// Host steps that the file codecs share (png.hip, jpeg_encode.hip, png_decode.hip, jpeg_decode.hip, tiff_decode.hip) and the thumbnail
 // steps they hand decoded pixels to (resize.hip).  Every workspace here is planned once (common.h: Carver, ws_plan).
 #pragma once
 #include <vector>
@@ -68,12 +68,13 @@ struct HostFile {
     const uint8_t *file;
     int64_t len, h, w;
     int channels;
+    int sample_bytes = 1;          // 2: a 16-bit picture (tiff_decode.hip), which travels as bytes
     size_t extra_bytes, scratch_bytes;
     uint8_t *d_file, *d_img;
     void *d_extra;
     int32_t *d_status;
     char *d_scratch;
-    size_t img_bytes() const { return (size_t)h * w * channels; }
+    size_t img_bytes() const { return (size_t)h * w * channels * sample_bytes; }
     void carve(Carver &cv)
     {
         d_file = cv.take<uint8_t>((size_t)len);

@@ -1,0 +1,377 @@
+// TIFF files decoded on the device (lars_h_decode_tiff, lars_h_thumbnail_tiff_u8): the whole file goes up once, every LZW
+// strip / tile is decoded by one wave into its own padded buffer, and one assembly pass writes the picture: byte order,
+// horizontal predictor, planar -> chunky, tile cropping.  The directory is read on the host (tiff_parse.cpp).
+//
+// The LZW stage never builds the string table.  Between two Clear codes ("a segment", codes c_0, c_1, ...):
+//   * code i is 9 bits wide for i <= 253, 10 for i <= 765, 11 for i <= 1789, 12 after that, so its bit offset is a closed
+//     form of i and 64 lanes read 64 codes at once;
+//   * table entry 258 + j is str(c_j) + first(str(c_{j+1})): with L_i the output length of code i and P its exclusive
+//     prefix sum, a code c_i >= 258 (j = c_i - 258 <= i - 1) has L_i = L_j + 1 and its output is a copy of the L_i bytes
+//     that start at P_j, already written earlier in the same segment (j = i - 1, KwKwK, overlaps its own first byte).
+// lars_h_tiff_lzw_decode (tiff_codec.cpp) is the specification: what it calls corrupt is corrupt here, at the same code.
+// tests/tiff_lzw_model.py restates the phases below in NumPy and checks every index they form.
+#include <algorithm>
+#include <vector>
+
+#include "codec_host.h"
+#include "common.h"
+
+namespace lars {
+
+namespace {
+
+constexpr int TD_PCAP = 3840;      // P[] entries kept per segment: entry 258 + j exists for j <= 3837 and needs P[j + 1]
+constexpr int TD_STAGE = 4096;     // bytes of one batch staged in LDS; the longest string is 3839 bytes
+constexpr int TD_CLEAR = 256, TD_EOI = 257, TD_FIRST = 258;
+
+struct TdGeom {
+    long long nchunks, full;       // bytes of a whole strip / tile = the pitch of the chunk buffers
+    int width, height, spp, bps;   // bps: bytes per sample
+    int planes, inner, across, down, chunk_w, chunk_h;
+    int tiled, predictor, big, lzw;
+};
+
+struct TdCtl {
+    int status[2];                 // LARS_TIFD_*, the strip / tile
+    int produced, pad;             // bytes that strip / tile gave
+};
+
+// bits in front of code i of a segment, and the width of code i
+__device__ inline unsigned long long td_bits_before(unsigned long long i)
+{
+    const unsigned long long a = i < 254 ? i : 254, b = i < 254 ? 0 : (i < 766 ? i - 254 : 512), c = i < 766 ? 0 : (i < 1790 ? i - 766 : 1024),
+                             d = i < 1790 ? 0 : i - 1790;
+    return 9 * a + 10 * b + 11 * c + 12 * d;
+}
+__device__ inline int td_width(unsigned long long i) { return i <= 253 ? 9 : i <= 765 ? 10 : i <= 1789 ? 11 : 12; }
+
+// stored rows of chunk k and the bytes the directory says it holds
+__device__ __host__ inline long long td_want(const TdGeom &g, long long k)
+{
+    const long long ty = (k / g.across) % g.down;
+    const long long left = (long long)g.height - ty * g.chunk_h;
+    const long long rows = g.tiled ? g.chunk_h : (left < g.chunk_h ? left : g.chunk_h);
+    return rows * g.chunk_w * g.inner * g.bps;
+}
+
+// One wave per strip / tile.  A batch is up to 64 codes of one segment: read, searched for Clear / EOI / the end of the input
+// / a code the table does not hold, given lengths and offsets, copied into the LDS stage (sources in front of the batch come
+// from the chunk buffer, sources inside it from the stage), and flushed.  produced[k]: bytes that came out; bad[k]: the
+// host decoder would have refused the stream before the chunk was full.
+__global__ __launch_bounds__(64) void k_td_lzw(const uint8_t *__restrict__ file, long long file_len, const long long *__restrict__ table,
+                                               TdGeom g, uint8_t *bufs, int *__restrict__ produced, int *__restrict__ bad)
+{
+    __shared__ unsigned int P[TD_PCAP];
+    __shared__ uint8_t stage[TD_STAGE];
+    const int lane = threadIdx.x;
+    const long long k = blockIdx.x;
+    if (k >= g.nchunks) return;
+    const long long off = table[2 * k], cnt = table[2 * k + 1];
+    if (off < 0 || cnt < 0 || off > file_len || cnt > file_len - off || g.full <= 0 || g.full >= (1ll << 31)) {   // the parser checked this
+        if (lane == 0) produced[k] = 0, bad[k] = 1;
+        return;
+    }
+    const uint8_t *src = file + off;
+    uint8_t *dst = bufs + k * g.full;
+    const unsigned int ndst = (unsigned int)g.full;
+    const unsigned long long nbits = (unsigned long long)cnt * 8;
+    unsigned long long seg_bit = 0;      // bit position of code 0 of the segment
+    unsigned long long seg_i = 0;        // codes of the segment already written
+    unsigned int op = 0;                 // bytes written
+    int err = 0;
+    for (;;) {
+        // ---- 64 codes by closed-form offsets
+        const unsigned long long i = seg_i + lane;
+        const unsigned long long at = seg_bit + td_bits_before(i);
+        const int width = td_width(i);
+        const bool avail = at + width <= nbits;
+        int code = 0;
+        if (avail) {
+            const unsigned long long byte = at >> 3;
+            unsigned int v = (unsigned int)src[byte] << 16;                       // byte < cnt: at + width <= 8 cnt
+            if (byte + 1 < (unsigned long long)cnt) v |= (unsigned int)src[byte + 1] << 8;
+            if (byte + 2 < (unsigned long long)cnt) v |= src[byte + 2];
+            code = (int)((v >> (24 - (int)(at & 7) - width)) & ((1u << width) - 1u));
+        }
+        // ---- the first Clear / EOI / end of input, the first code above the fill level (a non-literal first code is one)
+        const bool term = !avail || code == TD_CLEAR || code == TD_EOI;
+        const long long j = (long long)code - TD_FIRST;                           // the entry's index, for code >= 258
+        const bool wrong = !term && code >= TD_FIRST && j > (long long)i - 1;
+        const unsigned long long m_term = __ballot(term), m_wrong = __ballot(wrong);
+        const int n_term = m_term ? __ffsll((long long)m_term) - 1 : 64, n_wrong = m_wrong ? __ffsll((long long)m_wrong) - 1 : 64;
+        const int ndata = n_term < n_wrong ? n_term : n_wrong;
+        const bool active = lane < ndata;
+        // ---- lengths: L_i = 1, or L_j + 1 with j <= i - 1 <= 3837; j in front of the batch: from P[], inside it: from its lane
+        if (lane == 0 && seg_i < TD_PCAP) P[seg_i] = op;
+        __syncthreads();
+        const bool copy = active && code >= TD_FIRST;
+        const bool inside = copy && (unsigned long long)j >= seg_i;
+        int L = 0;
+        if (active) L = 1;
+        if (copy && !inside && j + 1 < TD_PCAP) L = (int)(P[j + 1] - P[j]) + 1;
+        bool need = inside;
+        const int jl = inside ? (int)((unsigned long long)j - seg_i) : 0;         // < lane
+        unsigned long long known = __ballot(!need);
+        while (known != ~0ull) {
+            const int from = __shfl(L, jl);
+            if (need && ((known >> jl) & 1)) L = from + 1, need = false;
+            known = __ballot(!need);
+        }
+        // ---- offsets: the inclusive scan of L
+        int incl = L;
+        for (int dlt = 1; dlt < 64; dlt <<= 1) {
+            const int up = __shfl_up(incl, dlt);
+            if (lane >= dlt) incl += up;
+        }
+        const unsigned long long start64 = (unsigned long long)op + (unsigned int)(incl - L), end64 = (unsigned long long)op + (unsigned int)incl;
+        // the host stops after a code that fills the chunk; a first code finds it full only when the literal before a Clear filled it
+        const bool stop = active && ((i >= 1 && end64 >= ndst) || (i == 0 && start64 >= ndst));
+        const unsigned long long m_stop = __ballot(stop);
+        const int n_stop = m_stop ? __ffsll((long long)m_stop) : 65;          // codes up to and including the stopping one
+        const int n_stage = __popcll(__ballot(active && incl <= TD_STAGE));   // incl grows with the lane: a prefix
+        int nproc = ndata;
+        if (n_stop < nproc) nproc = n_stop;
+        if (n_stage < nproc) nproc = n_stage;
+        const bool mine = lane < nproc;
+        const unsigned int start = (unsigned int)start64;                     // < 2^31 + 64 * 3839 for every lane that is `mine`
+        if (mine && i < TD_PCAP) P[i] = start;
+        // ---- bytes: rounds of lanes whose sources are written
+        __syncthreads();
+        unsigned int srcpos = 0;
+        if (mine && copy && j < TD_PCAP) srcpos = P[j];                       // j <= i - 1: in front of the batch or a lower lane of it
+        const int dep_a = (mine && inside) ? jl : -1;                         // the lane of code j
+        const int dep_b = (mine && copy && (unsigned long long)(j + 1) >= seg_i && jl + (inside ? 1 : 0) != lane)
+                              ? (inside ? jl + 1 : 0) : -1;                   // the lane of code j + 1, unless it is this one (KwKwK)
+        bool todo = mine;
+        unsigned long long done = __ballot(!todo);
+        while (done != ~0ull) {
+            const bool ready = todo && (dep_a < 0 || ((done >> dep_a) & 1)) && (dep_b < 0 || ((done >> dep_b) & 1));
+            if (ready) {
+                const unsigned int base = start - op;
+                if (!copy) {
+                    if (base < TD_STAGE) stage[base] = (uint8_t)code;
+                } else {
+                    for (int t = 0; t < L; ++t) {
+                        const unsigned int s = srcpos + t;
+                        uint8_t b = 0;
+                        if (s < op) b = dst[s];                               // s < op <= ndst
+                        else if (s - op < TD_STAGE) b = stage[s - op];
+                        if (base + t < TD_STAGE) stage[base + t] = b;
+                    }
+                }
+                todo = false;
+            }
+            __syncthreads();
+            done = __ballot(!todo);
+        }
+        // ---- flush, clipped to the chunk
+        const unsigned int total = nproc > 0 ? (unsigned int)__shfl(incl, nproc - 1) : 0;
+        for (unsigned int q = lane; q < total && q < TD_STAGE; q += 64)
+            if ((unsigned long long)op + q < ndst) dst[op + q] = stage[q];
+        __syncthreads();
+        // ---- what ended the batch
+        if (nproc > 0 && nproc == n_stop) { op = ndst; break; }               // the chunk is full
+        const unsigned long long op64 = (unsigned long long)op + total;
+        op = (unsigned int)op64;                                              // < ndst: no code stopped
+        seg_i += nproc;
+        if (nproc < ndata) continue;                                          // the stage was full
+        if (n_wrong < n_term) { err = 1; break; }
+        if (n_term == 64) continue;
+        const int tcode = __shfl(code, n_term);
+        const int tavail = __shfl((int)avail, n_term);
+        if (!tavail || tcode == TD_EOI) break;                                // out of input: what was decoded stands
+        seg_bit += td_bits_before(seg_i) + td_width(seg_i);                   // past the Clear
+        seg_i = 0;
+    }
+    if (lane == 0) produced[k] = (int)op, bad[k] = err;
+}
+
+// the first strip / tile the host decoder would refuse, else the first that gave too few bytes
+__global__ void k_td_check(TdGeom g, const int *__restrict__ produced, const int *__restrict__ bad, TdCtl *ctl)
+{
+    __shared__ unsigned long long first_bad, first_short;
+    if (threadIdx.x == 0) first_bad = first_short = ~0ull;
+    __syncthreads();
+    for (long long k = threadIdx.x; k < g.nchunks; k += blockDim.x) {
+        if (bad[k]) atomicMin(&first_bad, (unsigned long long)k);
+        else if (produced[k] < td_want(g, k)) atomicMin(&first_short, (unsigned long long)k);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (first_bad != ~0ull) ctl->status[0] = LARS_TIFD_CORRUPT, ctl->status[1] = (int)first_bad;
+        else if (first_short != ~0ull)
+            ctl->status[0] = LARS_TIFD_SHORT, ctl->status[1] = (int)first_short, ctl->produced = produced[first_short];
+    }
+}
+
+// One wave per row of a strip / tile that lies inside the picture: samples in file byte order -> native samples, the running
+// sum of predictor 2 as a wave scan per sample (it restarts with the row), planes interleaved, padding columns dropped.
+__global__ __launch_bounds__(256) void k_td_assemble(const uint8_t *__restrict__ file, long long file_len, const long long *__restrict__ table,
+                                                     TdGeom g, const uint8_t *__restrict__ bufs, uint8_t *__restrict__ out, const TdCtl *ctl)
+{
+    if (ctl->status[0]) return;
+    const int lane = threadIdx.x & 63;
+    const long long units = (long long)g.planes * g.height * g.across;
+    const long long nwaves = (long long)gridDim.x * (blockDim.x >> 6);
+    uint16_t *out16 = reinterpret_cast<uint16_t *>(out);
+    for (long long u = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); u < units; u += nwaves) {
+        const long long tx = u % g.across, y = (u / g.across) % g.height, p = u / g.across / g.height;
+        const long long ty = y / g.chunk_h, r = y % g.chunk_h;
+        const long long k = (p * g.down + ty) * g.across + tx;
+        const long long x0 = tx * g.chunk_w;
+        const long long cols = g.width - x0 < g.chunk_w ? g.width - x0 : g.chunk_w;
+        const long long row_bytes = (long long)g.chunk_w * g.inner * g.bps;
+        const uint8_t *src;
+        if (g.lzw) {
+            src = bufs + k * g.full + r * row_bytes;                         // r < chunk_h: inside the chunk buffer
+        } else {
+            const long long off = table[2 * k], cnt = table[2 * k + 1];
+            if (off < 0 || cnt < (r + 1) * row_bytes || off > file_len || cnt > file_len - off) continue;   // the parser checked this
+            src = file + off + r * row_bytes;
+        }
+        const long long o0 = (y * g.width + x0) * g.spp;                      // the row's first sample in the picture
+        if (g.predictor != 2) {
+            const long long n = cols * g.inner;
+            for (long long e = lane; e < n; e += 64) {
+                const long long o = g.planes > 1 ? o0 + e * g.spp + p : o0 + e;
+                if (g.bps == 1) out[o] = src[e];
+                else out16[o] = g.big ? (uint16_t)(src[2 * e] << 8 | src[2 * e + 1]) : (uint16_t)(src[2 * e + 1] << 8 | src[2 * e]);
+            }
+            continue;
+        }
+        for (int s = 0; s < g.inner; ++s) {
+            unsigned int carry = 0;
+            for (long long xb = 0; xb < cols; xb += 64) {
+                const long long x = xb + lane;
+                unsigned int v = 0;
+                if (x < cols) {
+                    const long long e = x * g.inner + s;
+                    v = g.bps == 1 ? src[e] : g.big ? (unsigned int)(src[2 * e] << 8 | src[2 * e + 1]) : (unsigned int)(src[2 * e + 1] << 8 | src[2 * e]);
+                }
+                for (int dlt = 1; dlt < 64; dlt <<= 1) {
+                    const unsigned int up = __shfl_up(v, dlt);
+                    if (lane >= dlt) v += up;
+                }
+                v += carry;
+                carry = __shfl(v, 63);
+                if (x < cols) {
+                    const long long o = o0 + x * g.spp + (g.planes > 1 ? p : s);
+                    if (g.bps == 1) out[o] = (uint8_t)v;
+                    else out16[o] = (uint16_t)v;
+                }
+            }
+        }
+    }
+}
+
+// the TIFF side of the host entry points (codec_host.h)
+struct TdFile : HostFile {
+    TdGeom g;
+    int64_t info[LARS_TIFF_INFO_N];
+    std::vector<int64_t> table;
+    TdCtl ctl_host;
+    TdCtl *d_ctl;
+    int *d_produced, *d_bad;
+    uint8_t *d_bufs;
+
+    void plan(Carver &cv)
+    {
+        d_ctl = cv.take<TdCtl>(1);
+        d_produced = cv.take<int>(g.lzw ? (size_t)g.nchunks : 0);
+        d_bad = cv.take<int>(g.lzw ? (size_t)g.nchunks : 0);
+        d_bufs = cv.take<uint8_t>(g.lzw ? (size_t)(g.nchunks * g.full) : 0);
+    }
+    int parse(const char *who_, const uint8_t *file_, int64_t len_)
+    {
+        who = who_; file = file_; len = len_;
+        if (!file || len <= 0) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+        LARS_TRY(lars_tiff_info(file, len, info, nullptr, 0));
+        if (!info[LARS_TIFF_INFO_SUPPORTED])
+            return fail(LARS_ERR_UNSUPPORTED, "%s: this TIFF file is not decoded on the device (LARS_TIFF_REASON %lld)", who,
+                        (long long)info[LARS_TIFF_INFO_REASON]);
+        h = info[LARS_TIFF_INFO_HEIGHT]; w = info[LARS_TIFF_INFO_WIDTH]; channels = (int)info[LARS_TIFF_INFO_SAMPLES];
+        sample_bytes = (int)info[LARS_TIFF_INFO_BITS] / 8;
+        const bool planar = info[LARS_TIFF_INFO_PLANAR] == 2;
+        g.nchunks = info[LARS_TIFF_INFO_CHUNKS];
+        g.width = (int)w; g.height = (int)h; g.spp = channels; g.bps = sample_bytes;
+        g.planes = planar ? channels : 1; g.inner = planar ? 1 : channels;
+        g.chunk_w = (int)info[LARS_TIFF_INFO_CHUNK_W]; g.chunk_h = (int)info[LARS_TIFF_INFO_CHUNK_H];
+        g.across = (int)((w + g.chunk_w - 1) / g.chunk_w); g.down = (int)((h + g.chunk_h - 1) / g.chunk_h);
+        g.tiled = (int)info[LARS_TIFF_INFO_TILED]; g.predictor = (int)info[LARS_TIFF_INFO_PREDICTOR];
+        g.big = (int)info[LARS_TIFF_INFO_BIG_ENDIAN]; g.lzw = info[LARS_TIFF_INFO_COMPRESSION] == 5;
+        g.full = (long long)g.chunk_h * g.chunk_w * g.inner * g.bps;
+        extra_bytes = (size_t)g.nchunks * 16;                 // the chunk table
+        Carver size(nullptr);
+        plan(size);
+        scratch_bytes = size.bytes();
+        table.assign((size_t)g.nchunks * 2, 0);
+        return lars_tiff_info(file, len, info, table.data(), g.nchunks);
+    }
+    int enqueue(hipStream_t s)
+    {
+        Carver cv(d_scratch);
+        plan(cv);
+        long long *d_tab = static_cast<long long *>(d_extra);
+        LARS_HIP_TRY(hipMemcpyAsync(d_tab, table.data(), extra_bytes, hipMemcpyHostToDevice, s));
+        LARS_HIP_TRY(hipMemsetAsync(d_ctl, 0, sizeof(TdCtl), s));
+        if (g.lzw) {
+            hipLaunchKernelGGL(k_td_lzw, dim3((unsigned)g.nchunks), dim3(64), 0, s, d_file, (long long)len, d_tab, g, d_bufs, d_produced, d_bad);
+            hipLaunchKernelGGL(k_td_check, dim3(1), dim3(256), 0, s, g, d_produced, d_bad, d_ctl);
+        }
+        const long long units = (long long)g.planes * g.height * g.across;
+        const unsigned grid = (unsigned)std::min<long long>((units + 3) / 4, 1 << 16);
+        hipLaunchKernelGGL(k_td_assemble, dim3(grid), dim3(256), 0, s, d_file, (long long)len, d_tab, g, d_bufs, d_img, d_ctl);
+        LARS_HIP_TRY(hipMemcpyAsync(d_status, d_ctl->status, 8, hipMemcpyDeviceToDevice, s));
+        LARS_HIP_TRY(hipMemcpyAsync(&ctl_host, d_ctl, sizeof ctl_host, hipMemcpyDeviceToHost, s));
+        return launch_check(who);
+    }
+    int finish(const int st[2])
+    {
+        switch (st[0]) {
+        case LARS_TIFD_OK: return LARS_OK;
+        case LARS_TIFD_CORRUPT: return fail(LARS_ERR_INVALID, "%s: corrupt LZW data in chunk %d", who, st[1]);
+        case LARS_TIFD_SHORT:
+            return fail(LARS_ERR_INVALID, "%s: strip / tile holds %d bytes, %lld expected", who, ctl_host.produced, td_want(g, st[1]));
+        default: return fail(LARS_ERR_HIP, "%s: internal decoder status %d (%d)", who, st[0], st[1]);
+        }
+    }
+};
+
+}  // namespace
+
+}  // namespace lars
+
+using namespace lars;
+
+extern "C" {
+
+// host file in, host samples out: one upload, the status, one download
+int lars_h_decode_tiff(const uint8_t *file, int64_t len, void *out, size_t out_cap)
+{
+    static const char *who = "lars_h_decode_tiff";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!out) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    TdFile F;
+    LARS_TRY(F.parse(who, file, len));
+    return decode_file_to_host(c, F, static_cast<uint8_t *>(out), out_cap);
+}
+
+// host file in, thumbnail out: the decoded pixels go straight into the thumbnail kernels (resize.hip)
+int lars_h_thumbnail_tiff_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
+                             int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out)
+{
+    static const char *who = "lars_h_thumbnail_tiff_u8";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!out || !reduce_box || !box) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    TdFile F;
+    LARS_TRY(F.parse(who, file, len));
+    const int64_t spp = F.info[LARS_TIFF_INFO_SAMPLES], photometric = F.info[LARS_TIFF_INFO_PHOTOMETRIC];
+    if (F.info[LARS_TIFF_INFO_BITS] != 8 || F.info[LARS_TIFF_INFO_EXTRA_SAMPLES] != 0 || !((spp == 1 && photometric == 1) || (spp == 3 && photometric == 2)))
+        return fail(LARS_ERR_UNSUPPORTED, "%s: 8-bit files of one BlackIsZero sample or RGB (%lld samples of %lld bits, photometric %lld)", who,
+                    (long long)spp, (long long)F.info[LARS_TIFF_INFO_BITS], (long long)photometric);
+    return thumbnail_file(c, F, fx, fy, reduce_box, box, new_h, new_w, vertical_first, out);
+}
+
+}  // extern "C"

@@ -28,6 +28,7 @@ LUT_PNG_LEVEL = 1
 PNG_ENCODERS = ("pillow", "device")
 PNG_DECODERS = ("pillow", "device")
 JPEG_DECODERS = ("pillow", "device")
+TIFF_DECODERS = ("pillow", "device")
 
 
 def _check_png_encoder(png_encoder):
@@ -45,8 +46,13 @@ def _check_jpeg_decoder(jpeg_decoder):
         raise ValueError(f"jpeg_decoder must be 'pillow' or 'device', got {jpeg_decoder!r}")
 
 
+def _check_tiff_decoder(tiff_decoder):
+    if tiff_decoder not in TIFF_DECODERS:
+        raise ValueError(f"tiff_decoder must be 'pillow' or 'device', got {tiff_decoder!r}")
+
+
 def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png",
-                  png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow"):
+                  png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow"):
     """One file: same outputs as backend-process.py:49-73.  Returns the statistics dicts.
     ``full_depth=True`` reads three-sample 16-bit TIFFs at their full depth (``tiffio.read_image``; Pillow, hence the
     reference, keeps their high bytes only).  ``lut_format="tiff"`` writes the colormap images as
@@ -56,17 +62,19 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     bytes to compress.  ``png_encoder="device"`` encodes the PNG / png8 pictures on the GPU (``api.encode_png``: same pixels,
     only the files cross PCIe) instead of with Pillow.  ``png_decoder="device"`` decodes the input on the GPU when it is a
     PNG file ``api.png_info`` calls supported (``tiffio.read_image``; same pixels as Pillow), ``jpeg_decoder="device"`` when
-    it is a JPEG file ``api.jpeg_info`` calls supported."""
+    it is a JPEG file ``api.jpeg_info`` calls supported, ``tiff_decoder="device"`` when it is a TIFF file ``api.tiff_info`` calls
+    supported and the array is the one read today (``tiffio.read_image``)."""
     if lut_format not in ("png", "png8", "tiff"):
         raise ValueError(f"lut_format must be 'png', 'png8' or 'tiff', got {lut_format!r}")
     _check_png_encoder(png_encoder)
     _check_png_decoder(png_decoder)
     _check_jpeg_decoder(jpeg_decoder)
+    _check_tiff_decoder(tiff_decoder)
     from PIL import Image
     from .tiffio import read_image
     image_path, output_dir = Path(image_path), Path(output_dir)
     name = image_path.stem
-    arr = read_image(image_path, full_depth, png_decoder, jpeg_decoder)
+    arr = read_image(image_path, full_depth, png_decoder, jpeg_decoder, tiff_decoder)
     if arr.ndim != 3 or arr.shape[2] < 3:
         raise ValueError(f"{image_path.name}: expected an image with at least 3 channels, got shape {arr.shape}")
     indices = list(indices or [])
@@ -118,15 +126,16 @@ def files_of_rank(files, rank=0, world=1):
 
 def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, process_gndvi=False,
                   process_ndwi=True, workers=4, verbose=True, full_depth=False, lut_format="png", rank=0, world=1,
-                  device=None, png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow"):
+                  device=None, png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow"):
     """backend-process.py:75-97 with its module constants as arguments.  Returns ``{file name: stats | error}``.
     ``rank`` / ``world``: one process per GPU, each takes its block of the sorted file list (``files_of_rank``); the output
     directories are shared, the file names distinct.  ``device``: the GPU ordinal every worker thread binds (the library's
     context is per thread and defaults to device 0); None leaves the threads' binding alone.  ``png_encoder``,
-    ``png_decoder``, ``jpeg_decoder``: see ``process_image``."""
+    ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``: see ``process_image``."""
     _check_png_encoder(png_encoder)
     _check_png_decoder(png_decoder)
     _check_jpeg_decoder(jpeg_decoder)
+    _check_tiff_decoder(tiff_decoder)
     input_path, output_path = Path(input_dir), Path(output_dir)
     indices = [t for t, on in (("NDVI", process_ndvi), ("GNDVI", process_gndvi), ("NDWI", process_ndwi)) if on]
     files = files_of_rank(sorted(f for f in input_path.glob("*") if f.suffix.lower() in EXTENSIONS), rank, world)
@@ -139,7 +148,7 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
             if verbose:
                 print(f"Processing {idx}/{total}: {f.name}")
             return f.name, process_image(f, output_path, process_wb, indices or None, full_depth, lut_format, png_encoder,
-                                         png_decoder, jpeg_decoder)
+                                         png_decoder, jpeg_decoder, tiff_decoder)
         except Exception as e:                              # same policy as upstream :96-97
             if verbose:
                 print(f"Error processing {f.name}: {str(e)}")
@@ -223,6 +232,8 @@ def main(argv=None):
                     help="'device' decodes supported PNG inputs on the GPU (same pixels; other files stay with Pillow)")
     ap.add_argument("--jpeg-decoder", default="pillow", choices=list(JPEG_DECODERS),
                     help="'device' decodes supported JPEG inputs on the GPU (same pixels; other files stay with Pillow)")
+    ap.add_argument("--tiff-decoder", default="pillow", choices=list(TIFF_DECODERS),
+                    help="'device' decodes supported TIFF inputs on the GPU (same samples; other files take today's path)")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     from .dist import env_rank_world
@@ -230,7 +241,7 @@ def main(argv=None):
     res = batch_process(args.input_dir, args.output_dir, args.wb, args.ndvi, args.gndvi, args.ndwi, args.workers,
                         not args.quiet, args.full_depth, args.lut_format, rank, world,
                         device=local_rank if world > 1 else None, png_encoder=args.png_encoder,
-                        png_decoder=args.png_decoder, jpeg_decoder=args.jpeg_decoder)
+                        png_decoder=args.png_decoder, jpeg_decoder=args.jpeg_decoder, tiff_decoder=args.tiff_decoder)
     failed = {k: str(v) for k, v in res.items() if isinstance(v, Exception)}
     print(json.dumps({"rank": rank, "world": world, "files": len(res), "failed": failed}))
     return 1 if failed else 0

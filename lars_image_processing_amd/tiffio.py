@@ -309,7 +309,7 @@ def write_tiff(path, array, rows_per_strip=None, tile=None, byteorder="<", plana
     return overflow_at + len(overflow)
 
 
-def read_image(path, full_depth=False, png_decoder="pillow", jpeg_decoder="pillow"):
+def read_image(path, full_depth=False, png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow"):
     """Any raster the pipeline takes -> ``ndarray``.
 
     ``full_depth=False``: ``np.array(PIL.Image.open(path))``, what the reference does (backend-process.py:52) --
@@ -320,13 +320,32 @@ def read_image(path, full_depth=False, png_decoder="pillow", jpeg_decoder="pillo
     on the GPU (``api.decode_png``, the same array as Pillow's); decided up front, not a fallback: its errors are raised.
     ``jpeg_decoder="device"``: the same for a ``.jpg`` / ``.jpeg`` file that starts with ``FF D8`` and that ``api.jpeg_info``
     calls supported (``api.decode_jpeg``); every other file goes to Pillow as before.
+    ``tiff_decoder="device"``: a ``.tif`` / ``.tiff`` file that ``api.tiff_info`` calls supported is decoded on the GPU
+    (``api.decode_tiff``) where this module's reader is used today (``full_depth=True`` and three-dimensional uint16 samples)
+    and, without ``full_depth``, where the array is Pillow's (8 bit, one BlackIsZero sample or RGB, no extra samples);
+    every other file takes the path it takes today.  Decided up front as well: the device's errors are raised.
     """
     from PIL import Image
     if png_decoder not in ("pillow", "device"):
         raise ValueError(f"png_decoder must be 'pillow' or 'device', got {png_decoder!r}")
     if jpeg_decoder not in ("pillow", "device"):
         raise ValueError(f"jpeg_decoder must be 'pillow' or 'device', got {jpeg_decoder!r}")
+    if tiff_decoder not in ("pillow", "device"):
+        raise ValueError(f"tiff_decoder must be 'pillow' or 'device', got {tiff_decoder!r}")
     p = str(path)
+    if tiff_decoder == "device" and p.lower().endswith((".tif", ".tiff")):
+        from . import api
+        with open(p, "rb") as f:
+            data = f.read()
+        # a file without the byte-order mark (a PNG under a .tif name, say) or with a broken directory is not the decoder's
+        if data[:2] in (b"II", b"MM"):
+            try:
+                i = api._tiff_info(np.frombuffer(data, dtype=np.uint8))
+            except ValueError:
+                i = None
+            if i is not None and i.supported:
+                if (full_depth and i.bits == 16 and i.samples > 1) or (not full_depth and api._tiff_is_pillow_u8(i)):
+                    return api.decode_tiff(data)
     if jpeg_decoder == "device" and p.lower().endswith((".jpg", ".jpeg")):
         from . import api
         with open(p, "rb") as f:
