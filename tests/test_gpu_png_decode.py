@@ -14,6 +14,7 @@ import lars_image_processing_amd as lars
 from lars_image_processing_amd import api, driver
 
 sys.path.insert(0, str(Path(__file__).resolve().parent))
+import deflate_writer  # noqa: E402
 from test_png_cpu import SIG, filter_rows  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -249,26 +250,10 @@ def test_trailing_data_after_the_image():
 
 
 def fixed_block(symbols):
-    """One final fixed-Huffman block of ("lit", byte) / ("copy", 3, distance 1..4) symbols, byte-aligned at the end."""
-    bits = []
-
-    def put(v, n):                                            # LSB first
-        bits.extend((v >> i) & 1 for i in range(n))
-
-    def code(c, n):                                           # Huffman codes go MSB first
-        bits.extend((c >> (n - 1 - i)) & 1 for i in range(n))
-
-    put(1, 1)
-    put(1, 2)
-    for s in symbols:
-        if s[0] == "lit":
-            code(0x30 + s[1], 8) if s[1] < 144 else code(0x190 + s[1] - 144, 9)
-        else:
-            code(1, 7)                                        # 257: length 3
-            code(s[2] - 1, 5)                                 # distance codes 0..3: distances 1..4
-    code(0, 7)                                                # 256: end of block
-    bits.extend([0] * (-len(bits) % 8))
-    return bytes(sum(b << i for i, b in enumerate(bits[k:k + 8])) for k in range(0, len(bits), 8))
+    """One final fixed-Huffman block of ("lit", byte) / ("copy", length, distance) symbols, byte-aligned at the end."""
+    sink = deflate_writer.BitSink()
+    deflate_writer.fixed_block(sink, symbols, final=True)
+    return sink.getvalue()
 
 
 def _image_and_stream():
