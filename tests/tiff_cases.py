@@ -8,8 +8,9 @@ import tempfile
 import numpy as np
 
 from lars_image_processing_amd import tiffio
+from lzw_writer import pack, unpack  # noqa: F401  (test_tiff_decode_cpu.py and test_gpu_tiff_decode.py use them from here)
 from test_tiffio import lzw_encode
-from tiff_lzw_model import CLEAR, EOI, FIRST, width_of
+from tiff_lzw_model import CLEAR, EOI, FIRST
 
 _LONG_TAGS = (256, 257, 273, 278, 279, 322, 323, 324, 325)
 
@@ -75,32 +76,7 @@ def one_strip_tiff(stream, nbytes):
 
 
 # ---- LZW streams as lists of codes ---------------------------------------------------------------------------------
-def unpack(stream):
-    """The codes of a stream, up to and including EOI, at the widths the decoder reads them."""
-    codes, at, i, nbits = [], 0, 0, len(stream) * 8
-    value = int.from_bytes(stream, "big")
-    while True:
-        w = width_of(i)
-        if at + w > nbits:
-            return codes
-        code = (value >> (nbits - at - w)) & ((1 << w) - 1)
-        at += w
-        codes.append(code)
-        if code == EOI:
-            return codes
-        i = 0 if code == CLEAR else i + 1
-
-
-def pack(codes):
-    """Codes -> bytes at the decoder's widths (a code too wide for its slot loses its high bits, as a damaged file's would)."""
-    acc, nbits, i = 0, 0, 0
-    for code in codes:
-        w = width_of(i)
-        acc = (acc << w) | (code & ((1 << w) - 1))
-        nbits += w
-        i = 0 if code == CLEAR else i + 1
-    pad = -nbits % 8
-    return (acc << pad).to_bytes((nbits + pad) // 8, "big")
+# unpack() and pack() live in lzw_writer.py, with the rest of the code-level tools
 
 
 def payloads():

@@ -22,9 +22,23 @@ def width_of(i):
     return 9 if i <= 253 else 10 if i <= 765 else 11 if i <= 1789 else 12
 
 
-def decode(src, ndst):
+def new_events():
+    """What decode() records about the paths a stream takes, for tests that assert their coverage: ``max_L`` the longest string,
+    ``max_i`` the largest index of a decoded code in its segment, ``stage_full`` batches cut because the stage was full,
+    ``pcap_batches`` batches begun with seg_i >= PCAP, ``totals`` the bytes of every batch, ``dep_b`` the kinds of second
+    dependency seen ("self": code j + 1 is the copying code itself, KwKwK; "lane0": j is the last code in front of the batch,
+    so the copy's source starts in the chunk buffer and ends in the stage; "inside": j + 1 is a lower lane; "none": both are
+    in front of the batch), ``fill_lanes`` / ``next_lanes`` / ``clear_lanes`` / ``eoi_lanes`` the lanes at which the fill-level
+    code, an entry with j + 1 == seg_i, a Clear and an EOI that ended a batch were seen, ``straddle_L`` the longest "lane0"
+    copy, ``rounds`` the most copy rounds a batch took, ``first_at`` the indices i at which a batch ended in Clear or EOI."""
+    return dict(max_L=0, max_i=-1, stage_full=0, pcap_batches=0, totals=set(), dep_b=set(), fill_lanes=set(), next_lanes=set(),
+                clear_lanes=set(), eoi_lanes=set(), straddle_L=0, rounds=0, first_at=set(), batches=0)
+
+
+def decode(src, ndst, events=None):
     """(bytes produced, bad): what the kernel leaves in produced[k] / bad[k] and in the chunk buffer for a stream ``src`` and a
-    chunk of ``ndst`` bytes (ndst >= 1)."""
+    chunk of ``ndst`` bytes (ndst >= 1).  ``events``: a new_events() record to fill in."""
+    ev = events if events is not None else new_events()
     src = bytes(src)
     cnt = len(src)
     assert ndst >= 1
@@ -32,8 +46,12 @@ def decode(src, ndst):
     dst = bytearray(ndst)
     P = [None] * PCAP
     seg_bit, seg_i, op, err = 0, 0, 0, 0
+    last_pos = -1
     while True:
-        stage = [None] * STAGE
+        pos = seg_bit + bits_before(seg_i)
+        assert pos > last_pos, "a batch that did not move on in the stream"
+        last_pos = pos
+        stage, when, owner = [None] * STAGE, [0] * STAGE, [0] * STAGE
         code, avail, term, wrong, idx = [0] * LANES, [False] * LANES, [False] * LANES, [False] * LANES, [0] * LANES
         for lane in range(LANES):
             i = idx[lane] = seg_i + lane
@@ -58,6 +76,9 @@ def decode(src, ndst):
         ndata = min(n_term, n_wrong)
         if seg_i < PCAP:
             P[seg_i] = op
+        else:
+            ev["pcap_batches"] += 1
+        ev["batches"] += 1
         # lengths
         L, need = [0] * LANES, [False] * LANES
         for lane in range(ndata):
@@ -93,6 +114,13 @@ def decode(src, ndst):
         n_stage = sum(1 for lane in range(ndata) if incl[lane] <= STAGE)
         nproc = min(ndata, n_stop, n_stage)
         assert nproc >= 1 or ndata == 0
+        ev["stage_full"] += n_stage < min(ndata, n_stop)
+        for lane in range(nproc):
+            ev["max_L"], ev["max_i"] = max(ev["max_L"], L[lane]), max(ev["max_i"], idx[lane])
+            if code[lane] - FIRST == idx[lane] - 1:
+                ev["fill_lanes"].add(lane)
+            if code[lane] - FIRST + 1 == seg_i:
+                ev["next_lanes"].add(lane)
         for lane in range(nproc):
             if idx[lane] < PCAP:
                 P[idx[lane]] = start[lane]
@@ -107,7 +135,7 @@ def decode(src, ndst):
                 base = start[lane] - op
                 if code[lane] < FIRST:
                     assert 0 <= base < STAGE
-                    stage[base] = code[lane]
+                    stage[base], when[base], owner[base] = code[lane], rounds, lane
                     todo[lane] = False
                     continue
                 j = code[lane] - FIRST
@@ -117,10 +145,14 @@ def decode(src, ndst):
                 lane_b = (jl + 1 if inside else 0)
                 dep_b = lane_b if (j + 1 >= seg_i and lane_b != lane) else -1
                 assert dep_a < lane and dep_b < lane
+                kind = "self" if lane_b == lane and j + 1 >= seg_i else "none" if dep_b < 0 else "inside" if inside else "lane0"
                 if (dep_a >= 0 and not done[dep_a]) or (dep_b >= 0 and not done[dep_b]):
                     continue
                 assert j < PCAP and P[j] is not None
                 srcpos = P[j]
+                ev["dep_b"].add(kind)
+                if kind == "lane0":
+                    ev["straddle_L"] = max(ev["straddle_L"], L[lane])
                 for t in range(L[lane]):
                     s = srcpos + t
                     if s < op:
@@ -128,13 +160,17 @@ def decode(src, ndst):
                         b = dst[s]
                     else:
                         assert 0 <= s - op < STAGE and stage[s - op] is not None, "a source byte that is not written yet"
+                        # the lanes of a round run side by side: a byte of another lane counts only from the round before
+                        assert owner[s - op] == lane or when[s - op] < rounds, "a source byte another lane writes in this round"
                         b = stage[s - op]
                     assert 0 <= base + t < STAGE
-                    stage[base + t] = b
+                    stage[base + t], when[base + t], owner[base + t] = b, rounds, lane
                 todo[lane] = False
             rounds += 1
             assert rounds <= 64
+        ev["rounds"] = max(ev["rounds"], rounds)
         total = incl[nproc - 1] if nproc > 0 else 0
+        ev["totals"].add(total)
         assert total <= STAGE
         for q in range(total):
             assert stage[q] is not None
@@ -153,8 +189,12 @@ def decode(src, ndst):
             break
         if n_term == 64:
             continue
+        if avail[n_term]:
+            ev["eoi_lanes" if code[n_term] == EOI else "clear_lanes"].add(n_term)
+            ev["first_at"].add(seg_i)
         if (not avail[n_term]) or code[n_term] == EOI:
             break
         seg_bit += bits_before(seg_i) + width_of(seg_i)
         seg_i = 0
+        P = [None] * PCAP                                                    # the kernel keeps the old offsets; reading one is an error here
     return bytes(dst[:op]), err
