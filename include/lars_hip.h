@@ -678,6 +678,36 @@ int lars_h_decode_tiff(const uint8_t *file, int64_t len, void *out, size_t out_c
 int lars_h_thumbnail_tiff_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
                              int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out);
 
+/* LZW TIFF files built on the device -- the Image.fromarray(corrected).save(".../<name>_wb.tif") of the batch job
+ * (backend-process.py:57) and the lut_format="tiff" pictures of the directory driver.  img is [h][w][channels] of uint8
+ * (itemsize 1) or native-endian uint16 (itemsize 2), channels 1..5.  The file is a classic little-endian TIFF: strips of
+ * rows_per_strip rows, chunky samples, Compression 5, Predictor 2 (horizontal differencing per sample modulo 2^bits, every
+ * row on its own) when predictor is not 0; strip data first, every strip on an even offset, then the directory with the tags
+ * and values of tiffio.write_tiff.  rows_per_strip 0: the largest row count whose uncompressed strip stays within the tuning
+ * knob tiff_strip_bytes (lars_set_tuning: 1 .. 1073741824, default 65536; at least one row); the files do depend on it.
+ * Every strip is the stream of the greedy encoder: the longest match in the table at every step, a Clear code when the
+ * table holds 4094 codes, a leading Clear, a trailing EndOfInformation, codes MSB first at TIFF's widths -- libtiff's bytes.
+ * lars_tiff_bound: pure host code.  The largest file any picture of that shape can give (0 for a shape that cannot be
+ * encoded): every input byte at most one 12-bit code, one Clear per 3836 codes, the leading Clear and EndOfInformation, one
+ * pad byte per strip, the header and the directory with its arrays.
+ * lars_tiff_encode_scratch_bytes: device scratch of lars_d_encode_tiff (0 for a shape that cannot be encoded).
+ * lars_d_encode_tiff: device img / out (both on even addresses) / scratch; enqueues on stream.  status_dev: two device ints,
+ * { LARS_TIFE_*, detail }; out_len_dev: the file's length, also under LARS_TIFE_NOSPACE (what out_cap would have had to be),
+ * where nothing of out is valid.  Any out_cap is taken; lars_tiff_bound always suffices.
+ * lars_h_encode_tiff: host img / out; one upload, then the status and the length, then out_len bytes into out. */
+enum {
+    LARS_TIFE_OK = 0,
+    LARS_TIFE_NOSPACE = 1,       /* the file is longer than out_cap; detail: 0 */
+    LARS_TIFE_TOO_LARGE = 2,     /* the file would reach 4 GiB; detail: 0 */
+    LARS_TIFE_OVERFLOW = 3       /* a strip outgrew its buffer, which the bound rules out; detail: the strip */
+};
+size_t lars_tiff_bound(int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip);
+size_t lars_tiff_encode_scratch_bytes(int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip);
+int lars_d_encode_tiff(const void *img, int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip, int predictor,
+                       uint8_t *out, size_t out_cap, int64_t *out_len_dev, int32_t *status_dev, void *scratch, void *stream);
+int lars_h_encode_tiff(const void *img, int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip, int predictor,
+                       uint8_t *out, size_t out_cap, int64_t *out_len);
+
 /* ------------------------------------------------------------------ multi-GPU */
 /* One process per GPU.  RCCL (librccl.so) is loaded on first use.  unique_id is
  * LARS_COMM_ID_BYTES bytes produced by lars_comm_unique_id() on rank 0 and

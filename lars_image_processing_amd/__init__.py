@@ -24,6 +24,7 @@ from .api import (  # noqa: F401
     decode_png,
     decode_tiff,
     encode_png,
+    encode_tiff,
     download_processed_images,
     fix_white_balance,
     fix_white_balance_rgnir,
@@ -39,6 +40,7 @@ from .api import (  # noqa: F401
     thumbnail_plan,
     thumbnail_png,
     thumbnail_tiff,
+    tiff_bound,
     tiff_info,
     time_series_points,
     timeseries_row,

@@ -623,6 +623,85 @@ def encode_jpeg(array, quality=75, subsampling="4:2:0"):
 
 
 # ---------------------------------------------------------------------------
+# TIFF files built on the device
+# ---------------------------------------------------------------------------
+def _tiff_picture(array, rows_per_strip, who):
+    """What ``encode_tiff`` opens with, before anything is launched: (C-contiguous ``[H, W, C]`` array, rows per strip or 0)."""
+    arr = np.asarray(array)
+    if arr.dtype not in (np.uint8, np.uint16):
+        raise TypeError(f"{who}: uint8 or uint16 pictures only, got {arr.dtype}")
+    if arr.ndim == 2:
+        arr = arr[:, :, None]
+    if arr.ndim != 3:
+        raise ValueError(f"{who}: shape [H, W] or [H, W, C] expected, got {arr.shape}")
+    if arr.size == 0:
+        raise ValueError(f"{who}: empty picture of shape {arr.shape}")
+    h, w, c = arr.shape
+    if not 1 <= c <= 5:
+        raise ValueError(f"{who}: 1 to 5 samples per pixel, got {c}")
+    if not (h <= 1 << 24 and w <= 1 << 24):
+        raise ValueError(f"{who}: {h} x {w} picture (1 to 2^24 on each side)")
+    if rows_per_strip is None:
+        rps = 0
+    else:
+        if isinstance(rows_per_strip, bool) or not isinstance(rows_per_strip, (int, np.integer)):
+            raise TypeError(f"{who}: rows_per_strip must be an int or None, got {rows_per_strip!r}")
+        if rows_per_strip < 1:
+            raise ValueError(f"{who}: rows_per_strip must be positive, got {rows_per_strip}")
+        rps = min(int(rows_per_strip), h)
+    if not arr.dtype.isnative:
+        arr = arr.astype(arr.dtype.newbyteorder("="))
+    return np.ascontiguousarray(arr), rps
+
+
+def tiff_bound(h, w, channels, itemsize, rows_per_strip=None):
+    """The largest file ``encode_tiff`` can return for an ``h x w`` picture of ``channels`` samples of ``itemsize`` bytes
+    (``lars_tiff_bound``; host code, no device needed); 0 for a shape that cannot be encoded.
+
+    The derivation, strip by strip: the stream opens with a Clear and ends with EndOfInformation; every other code but the
+    Clears that follow a full table stands for at least one input byte, so a strip of n bytes gives at most n of them; the
+    table is full after 3836 codes, so at most n // 3836 Clears follow; no code is wider than 12 bits.  That is
+    ``ceil(12 * (n + n // 3836 + 2) / 8)`` bytes, plus one where that is odd (strips start on even offsets).  Around the
+    strips: 8 bytes of header, a directory of at most 13 entries (2 + 12 * 13 + 4 bytes), BitsPerSample and SampleFormat
+    (``2 * channels`` bytes each), and 8 bytes of offset and byte count per strip.  ``rows_per_strip=None``: the rows the
+    knob ``tiff_strip_bytes`` gives, as in ``encode_tiff``."""
+    return int(_ffi.load().lars_tiff_bound(int(h), int(w), int(channels), int(itemsize), int(rows_per_strip or 0)))
+
+
+def encode_tiff(array, rows_per_strip=None, predictor=False):
+    """LZW TIFF file (``bytes``) of a picture, encoded on the GPU: ``[H, W]`` or ``[H, W, C]`` with C = 1..5, uint8 or uint16.
+
+    A classic little-endian TIFF with strips, chunky samples and Compression 5; ``predictor=True`` writes Predictor 2
+    (horizontal differencing per sample modulo 2^bits, every row on its own).  The directory holds the tags and values of
+    ``tiffio.write_tiff`` for the same array and ``rows_per_strip`` (RGB for C >= 3, BlackIsZero otherwise, samples past the
+    third as unspecified extra samples), strip data first, every strip on an even offset.  ``rows_per_strip=None``: the most
+    rows whose uncompressed strip stays within the tuning knob ``tiff_strip_bytes`` (65536, libtiff's and Pillow's strip
+    size), at least one.  Every strip is the greedy encoder's stream with a Clear code when the table holds 4094 codes: the
+    bytes libtiff writes for that strip.  What ``Image.fromarray(corrected).save(".../<name>_wb.tif")`` does for the batch
+    job's primary output (backend-process.py:57), compressed.
+
+    ``TypeError`` / ``ValueError`` for other dtypes, shapes, empty arrays or C > 5 before anything is launched;
+    ``tiffio.TiffError`` for a file that would reach 4 GiB.  No CPU fallback.
+    """
+    from .tiffio import TiffError
+    arr, rps = _tiff_picture(array, rows_per_strip, "encode_tiff")
+    h, w, c = arr.shape
+    bound = tiff_bound(h, w, c, arr.dtype.itemsize, rps)
+    if bound == 0:
+        raise ValueError(f"encode_tiff: strips of {rps or 'the default number of'} rows of {w * c * arr.dtype.itemsize} bytes are too long (2^30 bytes at most)")
+    out = np.empty(min(bound, 1 << 32), dtype=np.uint8)
+    n = C.c_int64(0)
+    try:
+        _ffi.call("lars_h_encode_tiff", _ffi.ptr(arr), h, w, c, arr.dtype.itemsize, rps, int(bool(predictor)), _ffi.ptr(out), out.nbytes,
+                  C.byref(n))
+    except _ffi.LarsError as e:
+        if e.code == -6 or (e.code == -1 and bound > out.nbytes):
+            raise TiffError("image too large for a classic TIFF (4 GiB)") from None
+        raise
+    return out[:n.value].tobytes()
+
+
+# ---------------------------------------------------------------------------
 # PNG files decoded on the device
 # ---------------------------------------------------------------------------
 # Pillow's PngImagePlugin._MODES: (bit depth, colour type) -> mode

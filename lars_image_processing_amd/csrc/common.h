@@ -139,6 +139,7 @@ struct Tuning {
     int joint_win_depth = 15;  // joint_win.hip: loads in flight per lane of the windowed counting kernel (which also sets how often it sweeps)
     int jpeg_subseq_bits = 512;  // jpeg_decode.hip: bits of entropy data per lane of the self-synchronising decode
     int jpeg_last_rounds = 0;  // read-only: rounds of k_jd_pass that decoded anything in the last lars_h_decode_jpeg_u8 / lars_h_thumbnail_jpeg_u8 (+100: k_jd_finish ran)
+    int tiff_strip_bytes = 65536;  // tiff_encode.hip: uncompressed bytes of a strip when the caller names no rows_per_strip (Pillow's / libtiff's 64 KiB)
     int joint_window = 1;      // joint_win.hip: windowed pair tables (one reader per tile chunk) where they fit, never, or test hooks (windows that miss)
 };
 Tuning &tuning();

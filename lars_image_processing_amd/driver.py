@@ -29,6 +29,7 @@ PNG_ENCODERS = ("pillow", "device")
 PNG_DECODERS = ("pillow", "device")
 JPEG_DECODERS = ("pillow", "device")
 TIFF_DECODERS = ("pillow", "device")
+TIFF_ENCODERS = ("pillow", "device")
 
 
 def _check_png_encoder(png_encoder):
@@ -51,8 +52,13 @@ def _check_tiff_decoder(tiff_decoder):
         raise ValueError(f"tiff_decoder must be 'pillow' or 'device', got {tiff_decoder!r}")
 
 
+def _check_tiff_encoder(tiff_encoder):
+    if tiff_encoder not in TIFF_ENCODERS:
+        raise ValueError(f"tiff_encoder must be 'pillow' or 'device', got {tiff_encoder!r}")
+
+
 def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png",
-                  png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow"):
+                  png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow", tiff_encoder="pillow"):
     """One file: same outputs as backend-process.py:49-73.  Returns the statistics dicts.
     ``full_depth=True`` reads three-sample 16-bit TIFFs at their full depth (``tiffio.read_image``; Pillow, hence the
     reference, keeps their high bytes only).  ``lut_format="tiff"`` writes the colormap images as
@@ -63,13 +69,16 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     only the files cross PCIe) instead of with Pillow.  ``png_decoder="device"`` decodes the input on the GPU when it is a
     PNG file ``api.png_info`` calls supported (``tiffio.read_image``; same pixels as Pillow), ``jpeg_decoder="device"`` when
     it is a JPEG file ``api.jpeg_info`` calls supported, ``tiff_decoder="device"`` when it is a TIFF file ``api.tiff_info`` calls
-    supported and the array is the one read today (``tiffio.read_image``)."""
+    supported and the array is the one read today (``tiffio.read_image``).  ``tiff_encoder="device"`` builds the TIFF files on
+    the GPU (``api.encode_tiff``: LZW strips, the same samples): ``<name>_wb.tif`` instead of Pillow's uncompressed file, and the
+    ``lut_format="tiff"`` pictures instead of ``tiffio.write_tiff``'s uncompressed ones."""
     if lut_format not in ("png", "png8", "tiff"):
         raise ValueError(f"lut_format must be 'png', 'png8' or 'tiff', got {lut_format!r}")
     _check_png_encoder(png_encoder)
     _check_png_decoder(png_decoder)
     _check_jpeg_decoder(jpeg_decoder)
     _check_tiff_decoder(tiff_decoder)
+    _check_tiff_encoder(tiff_encoder)
     from PIL import Image
     from .tiffio import read_image
     image_path, output_dir = Path(image_path), Path(output_dir)
@@ -90,8 +99,11 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     corrected = res["corrected"] if res else api.fix_white_balance(arr)
     if process_wb:
         (output_dir / "white_balanced").mkdir(parents=True, exist_ok=True)
-        Image.fromarray(corrected[:, :, :3] if corrected.shape[2] > 4 else corrected).save(
-            output_dir / "white_balanced" / f"{name}_wb.tif")
+        wb = corrected[:, :, :3] if corrected.shape[2] > 4 else corrected
+        if tiff_encoder == "device":
+            (output_dir / "white_balanced" / f"{name}_wb.tif").write_bytes(api.encode_tiff(wb))
+        else:
+            Image.fromarray(wb).save(output_dir / "white_balanced" / f"{name}_wb.tif")
     stats = {}
     for t in indices:
         (output_dir / t).mkdir(parents=True, exist_ok=True)
@@ -100,8 +112,11 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
         if device_png:
             out.write_bytes(entry["png"])
         elif lut_format == "tiff":
-            from .tiffio import write_tiff
-            write_tiff(out.with_suffix(".tif"), entry["rgba"])
+            if tiff_encoder == "device":
+                out.with_suffix(".tif").write_bytes(api.encode_tiff(entry["rgba"]))
+            else:
+                from .tiffio import write_tiff
+                write_tiff(out.with_suffix(".tif"), entry["rgba"])
         elif palette:
             im = Image.fromarray(entry["entry"], "P")
             im.putpalette(api.colormap_lut(api._colormap_for(t)).tobytes(), rawmode="RGBA")
@@ -126,12 +141,14 @@ def files_of_rank(files, rank=0, world=1):
 
 def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, process_gndvi=False,
                   process_ndwi=True, workers=4, verbose=True, full_depth=False, lut_format="png", rank=0, world=1,
-                  device=None, png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow"):
+                  device=None, png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow",
+                  tiff_encoder="pillow"):
     """backend-process.py:75-97 with its module constants as arguments.  Returns ``{file name: stats | error}``.
     ``rank`` / ``world``: one process per GPU, each takes its block of the sorted file list (``files_of_rank``); the output
     directories are shared, the file names distinct.  ``device``: the GPU ordinal every worker thread binds (the library's
     context is per thread and defaults to device 0); None leaves the threads' binding alone.  ``png_encoder``,
-    ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``: see ``process_image``."""
+    ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``, ``tiff_encoder``: see ``process_image``."""
+    _check_tiff_encoder(tiff_encoder)
     _check_png_encoder(png_encoder)
     _check_png_decoder(png_decoder)
     _check_jpeg_decoder(jpeg_decoder)
@@ -148,7 +165,7 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
             if verbose:
                 print(f"Processing {idx}/{total}: {f.name}")
             return f.name, process_image(f, output_path, process_wb, indices or None, full_depth, lut_format, png_encoder,
-                                         png_decoder, jpeg_decoder, tiff_decoder)
+                                         png_decoder, jpeg_decoder, tiff_decoder, tiff_encoder)
         except Exception as e:                              # same policy as upstream :96-97
             if verbose:
                 print(f"Error processing {f.name}: {str(e)}")
@@ -234,6 +251,8 @@ def main(argv=None):
                     help="'device' decodes supported JPEG inputs on the GPU (same pixels; other files stay with Pillow)")
     ap.add_argument("--tiff-decoder", default="pillow", choices=list(TIFF_DECODERS),
                     help="'device' decodes supported TIFF inputs on the GPU (same samples; other files take today's path)")
+    ap.add_argument("--tiff-encoder", default="pillow", choices=list(TIFF_ENCODERS),
+                    help="'device' builds <name>_wb.tif and the --lut-format tiff pictures on the GPU (LZW strips, same samples)")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     from .dist import env_rank_world
@@ -241,7 +260,8 @@ def main(argv=None):
     res = batch_process(args.input_dir, args.output_dir, args.wb, args.ndvi, args.gndvi, args.ndwi, args.workers,
                         not args.quiet, args.full_depth, args.lut_format, rank, world,
                         device=local_rank if world > 1 else None, png_encoder=args.png_encoder,
-                        png_decoder=args.png_decoder, jpeg_decoder=args.jpeg_decoder, tiff_decoder=args.tiff_decoder)
+                        png_decoder=args.png_decoder, jpeg_decoder=args.jpeg_decoder, tiff_decoder=args.tiff_decoder,
+                        tiff_encoder=args.tiff_encoder)
     failed = {k: str(v) for k, v in res.items() if isinstance(v, Exception)}
     print(json.dumps({"rank": rank, "world": world, "files": len(res), "failed": failed}))
     return 1 if failed else 0

@@ -1,0 +1,155 @@
+#!/usr/bin/env python3
+"""TIFF encoding for the batch job's primary output (backend-process.py:57, ``<name>_wb.tif``): ``encode_tiff`` on the GPU next
+to Pillow's ``Image.fromarray(a).save(BytesIO(), format="TIFF", compression="tiff_lzw")`` on one host core, in the same run on
+the same host.
+
+Pictures: seeded 1/f fields (tools/pngbench.py's ``field_1f``), the gallery picture 2048 x 1536 RGB and 4096 x 4096 RGB, with
+and without the horizontal predictor.  ``--files`` pictures per kind: four different fields, the others the same fields rolled
+by odd steps in both directions (other strips, the same statistics).  Per picture, host array in and the file's bytes out,
+ending in a device synchronise: the median over the pictures after a warm-up pass, the smaller of ``--runs`` such medians.
+Every file is read back first.  ``--split`` adds the parts of one call (upload, the kernels from a resident picture into a
+resident file, download of the file), ``--sweep`` the knob "tiff_strip_bytes" at 8192 .. 262144.
+
+    python tools/tiffencodebench.py [--files 20] [--runs 2] [--split] [--sweep] [--gpu-only] [--json out.json]
+
+Kernel times come from a separate run:  rocprofv3 --kernel-trace --stats -- python tools/tiffencodebench.py --gpu-only
+"""
+import argparse
+import ctypes as C
+import io
+import json
+import os
+import sys
+import time
+
+import numpy as np
+from PIL import Image
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import lars_image_processing_amd as lars  # noqa: E402
+from lars_image_processing_amd import _ffi, tiffio  # noqa: E402
+from jpegdecodebench import pictures  # noqa: E402
+
+KINDS = {"gallery_2048x1536_rgb": (1536, 2048), "rgb_4096x4096": (4096, 4096)}
+SWEEP = (8192, 16384, 32768, 65536, 131072, 262144)
+DISTINCT = 4
+
+
+def many_pictures(shape, n, seed):
+    base = pictures(shape, min(n, DISTINCT), seed)
+    return [np.ascontiguousarray(np.roll(base[k % len(base)], (97 * (k // len(base)), 131 * (k // len(base))), (0, 1))) for k in range(n)]
+
+
+def pil_tiff(a, predictor=False):
+    b = io.BytesIO()
+    Image.fromarray(a).save(b, format="TIFF", compression="tiff_lzw", **({"tiffinfo": {317: 2}} if predictor else {}))
+    return b.getvalue()
+
+
+def per_picture_ms(fn, arrays, gpu, runs):
+    """The smaller of ``runs`` medians over the pictures of the time of one call, after a warm-up pass over all of them."""
+    for a in arrays:
+        fn(a)
+    best = []
+    for _ in range(runs):
+        ts = []
+        for a in arrays:
+            if gpu:
+                _ffi.call("lars_synchronize", None)
+            t0 = time.perf_counter()
+            fn(a)
+            if gpu:
+                _ffi.call("lars_synchronize", None)
+            ts.append(time.perf_counter() - t0)
+        best.append(float(np.median(ts)) * 1e3)
+    return min(best)
+
+
+def split_ms(a, predictor, reps=20):
+    """The parts of one encode_tiff call, each timed on its own (median): upload of the picture, the kernels from a resident
+    picture into a resident file (lars_d_encode_tiff), download of the file's bytes."""
+    lib = _ffi.load()
+    h, w, c = a.shape
+    cap, need = lib.lars_tiff_bound(h, w, c, 1, 0), lib.lars_tiff_encode_scratch_bytes(h, w, c, 1, 0)
+
+    def med(fn):
+        fn()
+        ts = []
+        for _ in range(reps):
+            _ffi.call("lars_synchronize", None)
+            t0 = time.perf_counter()
+            fn()
+            _ffi.call("lars_synchronize", None)
+            ts.append(time.perf_counter() - t0)
+        return float(np.median(ts)) * 1e3
+
+    d_in, d_out, d_scratch, d_ans = (C.c_void_p() for _ in range(4))
+    _ffi.call("lars_malloc", C.byref(d_in), a.nbytes)
+    _ffi.call("lars_malloc", C.byref(d_out), cap)
+    _ffi.call("lars_malloc", C.byref(d_scratch), need)
+    _ffi.call("lars_malloc", C.byref(d_ans), 16)
+    try:
+        upload = med(lambda: _ffi.call("lars_memcpy_h2d", d_in, _ffi.ptr(a), a.nbytes))
+        device = med(lambda: _ffi.call("lars_d_encode_tiff", d_in, h, w, c, 1, 0, int(predictor), d_out, cap, d_ans, C.c_void_p(d_ans.value + 8),
+                                       d_scratch, None))
+        n = np.zeros(2, np.int64)
+        _ffi.call("lars_memcpy_d2h", _ffi.ptr(n), d_ans, 16)
+        assert n[1] == 0, "device status"
+        out = np.empty(int(n[0]), np.uint8)
+        download = med(lambda: _ffi.call("lars_memcpy_d2h", _ffi.ptr(out), d_out, out.size))
+    finally:
+        for p in (d_in, d_out, d_scratch, d_ans):
+            _ffi.call("lars_free", p)
+    assert np.array_equal(tiffio.read_tiff(out.tobytes()), a)
+    return {"upload_ms": upload, "device_encode_ms": device, "download_ms": download}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--files", type=int, default=20, help="pictures per kind (each timed once per run after the warm-up)")
+    ap.add_argument("--runs", type=int, default=2)
+    ap.add_argument("--gpu-only", action="store_true", help="skip the Pillow leg (for a kernel trace)")
+    ap.add_argument("--split", action="store_true", help="also time the parts of one call")
+    ap.add_argument("--sweep", action="store_true", help='also sweep "tiff_strip_bytes"')
+    ap.add_argument("--json", help="also write the figures to this file")
+    args = ap.parse_args()
+    if _ffi.device_count() < 1:
+        sys.exit("tiffencodebench: needs a gfx950 GPU (no CPU fallback)")
+    import PIL
+    res = {"device": _ffi.device_name(), "pillow": PIL.__version__, "files": args.files, "runs": args.runs,
+           "tiff_strip_bytes": _ffi.get_tuning("tiff_strip_bytes"), "kinds": {}}
+    for name, shape in KINDS.items():
+        arrays = many_pictures(shape, args.files, seed=11)
+        for predictor in (False, True):
+            files = [lars.encode_tiff(a, predictor=predictor) for a in arrays[:DISTINCT]]
+            for a, b in list(zip(arrays, files))[:2]:          # a fast wrong answer is no answer
+                assert np.array_equal(tiffio.read_tiff(b), a) and np.array_equal(np.asarray(Image.open(io.BytesIO(b))), a)
+            r = {"files": len(arrays), "mean_file_bytes": int(np.mean([len(b) for b in files])), "shape": [shape[0], shape[1], 3],
+                 "strips": len(tiffio._read_ifd(memoryview(files[0]), "<")[tiffio.STRIP_OFFSETS]),
+                 "encode_tiff_ms": per_picture_ms(lambda a: lars.encode_tiff(a, predictor=predictor), arrays, True, args.runs)}
+            if not args.gpu_only:
+                pil = pil_tiff(arrays[0], predictor)
+                r["pillow_file_bytes"] = len(pil)
+                r["pillow_strips"] = len(tiffio._read_ifd(memoryview(pil), "<")[tiffio.STRIP_OFFSETS])
+                r["pillow_save_ms"] = per_picture_ms(lambda a: pil_tiff(a, predictor), arrays, False, args.runs)
+                r["encode_speedup"] = r["pillow_save_ms"] / r["encode_tiff_ms"]
+            if args.split:
+                r["split"] = split_ms(arrays[0], predictor)
+            if args.sweep:
+                r["sweep_encode_tiff_ms"] = {}
+                for v in SWEEP:
+                    with _ffi.tuning(tiff_strip_bytes=v):
+                        r["sweep_encode_tiff_ms"][str(v)] = per_picture_ms(lambda a: lars.encode_tiff(a, predictor=predictor),
+                                                                           arrays[:DISTINCT + 1], True, args.runs)
+            key = name + ("_predictor" if predictor else "")
+            res["kinds"][key] = r
+            print(key, json.dumps(r), flush=True)
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
