@@ -544,7 +544,8 @@ int lars_h_thumbnail_png_u8(const uint8_t *file, int64_t len, int fx, int fy, co
  * enqueues on stream and writes { LARS_JPGD_* status, detail } to the device int32 status_dev[2].
  * lars_h_decode_jpeg_u8: host file in, host pixels out (out_cap >= h * w * components); one upload, one download.
  * lars_h_thumbnail_jpeg_u8: host file in, lars_h_thumbnail_u8's plan numbers, host thumbnail out; the decoded pixels
- * never leave the device.  The decoder runs at full scale: the caller checks that Pillow's draft() would too. */
+ * never leave the device.  The decoder runs at full scale: the caller checks that Pillow's draft() would too (or calls
+ * lars_h_thumbnail_jpeg_scaled_u8 below). */
 #define LARS_JPEG_INFO_N 16
 #define LARS_JPEG_INFO_SAMPLING_STRIDE 2   /* component c: info[LARS_JPEG_INFO_H0 + 2 c], info[LARS_JPEG_INFO_V0 + 2 c], c = 0, 1, 2 */
 enum {                           /* positions in lars_jpeg_info's info[] */
@@ -588,6 +589,23 @@ int lars_d_decode_jpeg_u8(const uint8_t *file_dev, const uint8_t *head, const in
 int lars_h_decode_jpeg_u8(const uint8_t *file, int64_t len, uint8_t *out, size_t out_cap);
 int lars_h_thumbnail_jpeg_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
                              int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out);
+
+/* The same files decoded at 1/scale, scale = 1, 2, 4 or 8 (anything else: LARS_ERR_INVALID) -- what load_image_from_db(...,
+ * thumbnail=True) really runs (process-images.py:186-189): img.thumbnail((400, 400)) calls draft(), and libjpeg decodes a
+ * camera file at 1/2, 1/4 or 1/8.  The picture is ceil(h / scale) x ceil(w / scale); the pixels are libjpeg-turbo's for
+ * scale_num / scale_denom = 1 / scale with JDCT_ISLOW and fancy upsampling, i.e. np.asarray(im) after im.draft() has set
+ * im.decoderconfig == (scale, 0), bit for bit.  scale 1 gives the bytes of the functions above.
+ * lars_jpeg_decode_scaled_scratch_bytes: device scratch of lars_d_decode_jpeg_scaled_u8 for that info and scale.
+ * lars_d_decode_jpeg_scaled_u8: lars_d_decode_jpeg_u8 with out = ceil(h / scale) * ceil(w / scale) * components bytes.
+ * lars_h_decode_jpeg_scaled_u8: host file in, host pixels of the scaled picture out.
+ * lars_h_thumbnail_jpeg_scaled_u8: host file in, the plan numbers for the SCALED picture (box: the one draft() returns,
+ * (0, 0, w / scale, h / scale), carried through the plan), host thumbnail out; the decoded pixels never leave the device. */
+size_t lars_jpeg_decode_scaled_scratch_bytes(const int64_t info[LARS_JPEG_INFO_N], int scale);
+int lars_d_decode_jpeg_scaled_u8(const uint8_t *file_dev, const uint8_t *head, const int64_t info[LARS_JPEG_INFO_N], int scale, uint8_t *out,
+                                 int32_t *status_dev, void *scratch, void *stream);
+int lars_h_decode_jpeg_scaled_u8(const uint8_t *file, int64_t len, int scale, uint8_t *out, size_t out_cap);
+int lars_h_thumbnail_jpeg_scaled_u8(const uint8_t *file, int64_t len, int scale, int fx, int fy, const int reduce_box[4], const float box[4],
+                                    int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out);
 
 /* Baseline JPEG files of 8-bit pictures, built on the device -- the Image.fromarray(corrected).save(save_path) that ends the
  * camera path (process-rgn.py:47 with :72-73; process-ndvi.py:114 reads the file back) and the img.save(buffer, format=img.format)

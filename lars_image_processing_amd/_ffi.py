@@ -236,6 +236,10 @@ SIGNATURES = {
     "lars_d_decode_jpeg_u8": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "lars_h_decode_jpeg_u8": (_I, [_P, _I64, _P, _SZ]),
     "lars_h_thumbnail_jpeg_u8": (_I, [_P, _I64, _I, _I, C.POINTER(_I), C.POINTER(_F), _I64, _I64, _I, _P]),
+    "lars_jpeg_decode_scaled_scratch_bytes": (_SZ, [_P, _I]),
+    "lars_d_decode_jpeg_scaled_u8": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
+    "lars_h_decode_jpeg_scaled_u8": (_I, [_P, _I64, _I, _P, _SZ]),
+    "lars_h_thumbnail_jpeg_scaled_u8": (_I, [_P, _I64, _I, _I, _I, C.POINTER(_I), C.POINTER(_F), _I64, _I64, _I, _P]),
     "lars_tiff_info": (_I, [_P, _I64, _P, _P, _I64]),
     "lars_h_decode_tiff": (_I, [_P, _I64, _P, _SZ]),
     "lars_h_thumbnail_tiff_u8": (_I, [_P, _I64, _I, _I, C.POINTER(_I), C.POINTER(_F), _I64, _I64, _I, _P]),

@@ -21,8 +21,8 @@ this module                     reference
 ``decode_png``                  process-images.py:181-193 (``np.array(Image.open(io.BytesIO(img_bytes)))``: same array)
 ``thumbnail_png``               process-images.py:186-189 from the file's bytes (decode + thumbnail, pixels stay on the GPU)
 ``encode_jpeg``                 process-rgn.py:47 with :72-73, process-images.py:247 (``img.save(f, "JPEG")``: the same file, byte for byte)
-``decode_jpeg``                 process-images.py:181-193, backend-process.py:52 for JPEG files (same array as Pillow's)
-``thumbnail_jpeg``              process-images.py:186-189 from a JPEG file's bytes, where ``draft`` keeps full scale
+``decode_jpeg``                 process-images.py:181-193, backend-process.py:52 for JPEG files (same array as Pillow's; ``scale=2, 4, 8``: after ``draft``)
+``thumbnail_jpeg``              process-images.py:186-189 from a JPEG file's bytes (``scaled=True``: also where ``draft`` decodes at 1/2, 1/4, 1/8)
 ``align_images``                process-images.py:515  (phase correlation + shift)
 ``calculate_index_statistics_by_timeframe``  process-images.py:619 (pandas table)
 ``time_series_points``          process-images.py:814-832 (the numbers ``create_time_series_plot`` draws)
@@ -853,7 +853,7 @@ def _jpeg_check(arr, who):
     return i.height, i.width, i.components
 
 
-def decode_jpeg(data):
+def decode_jpeg(data, scale=1):
     """``np.asarray(Image.open(io.BytesIO(data)))`` of a JPEG file, decoded on the GPU (process-images.py:181-193).
 
     ``data``: the whole file as ``bytes``, ``bytearray``, ``memoryview`` or a 1-D uint8 array.  Baseline and extended
@@ -863,29 +863,60 @@ def decode_jpeg(data):
     variants (``jpeg_info(data)["reason"]``) raise ``NotImplementedError`` before anything is launched; damaged files raise
     ``ValueError`` saying what is wrong.  Stricter than Pillow on purpose: entropy data that ends early, an invalid code, a
     coefficient past 63 and a missing or misnumbered restart marker are errors.  No CPU fallback.
+
+    ``scale``: 1 (the default: exactly the above), or 2, 4, 8 for libjpeg's decoding at 1/2, 1/4, 1/8 scale -- the array
+    ``np.asarray(im)`` gives after ``im.draft(...)`` has set ``im.decoderconfig == (scale, 0)``, bit for bit, of shape
+    ``(ceil(H / scale), ceil(W / scale)[, 3])``.  The scaling happens at the coefficients (reduced IDCTs), as in libjpeg.
+    Any other value raises ``ValueError``.
     """
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or scale not in (1, 2, 4, 8):
+        raise ValueError(f"decode_jpeg: scale 1, 2, 4 or 8, got {scale!r}")
     arr = _file_bytes(data, "decode_jpeg", "JPEG")
     h, w, c = _jpeg_check(arr, "decode_jpeg")
+    scale = int(scale)
+    if scale == 1:
+        out = np.empty((h, w) if c == 1 else (h, w, c), dtype=np.uint8)
+        _file_call("lars_h_decode_jpeg_u8", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
+        return out
+    h, w = -(-h // scale), -(-w // scale)
     out = np.empty((h, w) if c == 1 else (h, w, c), dtype=np.uint8)
-    _file_call("lars_h_decode_jpeg_u8", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
+    _file_call("lars_h_decode_jpeg_scaled_u8", _ffi.ptr(arr), arr.size, scale, _ffi.ptr(out), out.nbytes)
     return out
 
 
-def thumbnail_jpeg(data, size=(400, 400), reducing_gap=2.0):
+def thumbnail_jpeg(data, size=(400, 400), reducing_gap=2.0, scaled=False):
     """``np.asarray`` of ``Image.open(io.BytesIO(data))`` after ``.thumbnail(size, LANCZOS, reducing_gap)``, bit for bit
     (process-images.py:186-189), from a JPEG file's bytes: the decoded pixels stay on the GPU and go straight into the
     thumbnail kernels, only the thumbnail comes back.  Pillow's ``thumbnail`` first lets ``draft`` switch the decoder to
-    1/2, 1/4 or 1/8 scale; this decoder works at full scale only, so where ``jpeg_draft_scale`` is above 1 (both sides of
-    the image at least twice ``size * reducing_gap``) it raises ``NotImplementedError``.  A file that already fits comes
-    back as ``decode_jpeg`` gives it.  Errors of the file as ``decode_jpeg``."""
+    1/2, 1/4 or 1/8 scale where both sides of the image are at least twice ``size * reducing_gap`` (``jpeg_draft_scale``
+    above 1).
+
+    ``scaled=False`` (the default): the decoder works at full scale only and raises ``NotImplementedError`` where
+    ``jpeg_draft_scale`` is above 1.  ``scaled=True``: there the file is decoded at that scale on the device
+    (``decode_jpeg(data, scale)``) and the thumbnail kernels get the plan ``thumbnail_plan`` computes for the scaled
+    picture and the box ``draft`` returns, ``(0, 0, w / scale, h / scale)`` -- fractional where the size does not divide;
+    when the draft already lands on the final size the scaled decode is the answer.  Where the scale is 1 both settings
+    run the same code.  A file that already fits comes back as ``decode_jpeg`` gives it.  Errors of the file as
+    ``decode_jpeg``."""
+    if not isinstance(scaled, (bool, np.bool_)):
+        raise TypeError(f"thumbnail_jpeg: scaled must be True or False, got {scaled!r}")
     arr = _file_bytes(data, "thumbnail_jpeg", "JPEG")
     h, w, c = _jpeg_check(arr, "thumbnail_jpeg")
     if reducing_gap is not None and reducing_gap < 1.0 and thumbnail_size((w, h), size) is not None:
         raise ValueError("reducing_gap must be 1.0 or greater")
     scale = jpeg_draft_scale((w, h), size, reducing_gap)
-    if scale != 1:
+    if scale != 1 and not scaled:
         raise NotImplementedError(f"thumbnail_jpeg: Pillow's draft() decodes this {w} x {h} file at 1/{scale} scale for size {tuple(size)}; "
-                                  "scaled decoding is not supported")
+                                  "scaled decoding is not supported unless scaled=True is given")
+    if scale != 1:
+        plan = thumbnail_plan((w, h), size, reducing_gap, (0, 0, w / scale, h / scale), (-(-w // scale), -(-h // scale)))
+        if plan is None:
+            return decode_jpeg(arr, scale)
+        new_w, new_h = plan.size
+        out = np.empty((new_h, new_w) if c == 1 else (new_h, new_w, c), dtype=np.uint8)
+        _file_call("lars_h_thumbnail_jpeg_scaled_u8", _ffi.ptr(arr), arr.size, scale, plan.factor[0], plan.factor[1],
+                   (C.c_int * 4)(*plan.reduce_box), (C.c_float * 4)(*plan.box), new_h, new_w, int(plan.vertical_first), _ffi.ptr(out))
+        return out
     plan = thumbnail_plan((w, h), size, reducing_gap, None, None)
     if plan is None:
         return decode_jpeg(arr)

@@ -37,6 +37,14 @@
 //                   component plane.
 //   k_jd_color      one thread per pixel: fancy (triangle) upsampling of Cb / Cr where the chroma plane is wider than
 //                   two samples, replication else, YCbCr -> RGB in 16-bit fixed point, [h][w][3] or [h][w].
+// At 1/2, 1/4 and 1/8 scale (Pillow's draft; lars_*_jpeg_scaled_*) the entropy stage is the same and the scaling starts at
+// the coefficients, as in libjpeg: a block becomes 4 x 4, 2 x 2 or 1 x 1 samples (the chroma blocks of 4:2:0 twice that,
+// so that they need no upsampling), see "scaled decoding" below:
+//   k_jd_idct_reduced<4 | 2>   four lanes per block, 64 blocks per workgroup: the rows a size reads, dequantised, into LDS;
+//                   column pass, row pass, 4 or 2 bytes per lane into the component plane.
+//   k_jd_idct_dc    1 x 1: one lane per block, the DC alone.
+//   k_jd_color_scaled   one thread per pixel of the scaled picture: h2v1 triangle filter or replication for the chroma
+//                   of 4:2:2, nothing for the others, then the colour arithmetic of k_jd_color.
 // Every loop is bounded by the length of the data, every index is checked against its buffer; an error is a status code
 // (LARS_JPGD_*) in device memory and every kernel after a failing one returns at once.
 #include <string.h>
@@ -567,15 +575,15 @@ __device__ inline void jd_idct8(int x[8])
 
 #define JD_WS_STRIDE 72                   // words per block in LDS: 64 + 8, so that the blocks of a wave start on different banks
 
-__global__ __launch_bounds__(256) void k_jd_idct(const short *coef, const unsigned int *dcpre, const JdTables *Tg, JdGeo g, uint8_t *planes,
-                                                 const JdCtl *ctl)
+__global__ __launch_bounds__(256) void k_jd_idct(const short *coef, const unsigned int *dcpre, const JdTables *Tg, JdGeo g, unsigned int first,
+                                                 uint8_t *planes, const JdCtl *ctl)
 {
     __shared__ int ws[32 * JD_WS_STRIDE];
     __shared__ int qt[3][64];
     if (ctl->status[0]) return;
     for (int i = threadIdx.x; i < 192; i += 256) qt[i / 64][i % 64] = Tg->qt[i / 64][i % 64];
     __syncthreads();
-    const unsigned int pb = blockIdx.x * 32 + (threadIdx.x >> 3);   // block in plane order
+    const unsigned int pb = first + blockIdx.x * 32 + (threadIdx.x >> 3);   // block in plane order; first: 0, or where the chroma planes start
     const int r = threadIdx.x & 7;
     const bool live = pb < g.pblocks[3];
     int comp = 0, bx = 0, by = 0;
@@ -681,6 +689,225 @@ __global__ __launch_bounds__(256) void k_jd_color(const uint8_t *planes, JdGeo g
     }
 }
 
+// ------------------------------------------------------------------------------------------------- scaled decoding
+// libjpeg's reduced-size IDCTs (jidctred.c), restated in the arithmetic of libjpeg-turbo's SIMD code for 4 x 4 and 2 x 2 and
+// of its C code for 1 x 1 -- what Pillow runs after draft().  tests/jpeg_scaled_model.py is the same in NumPy.
+#define JD_R_1_847759065 15137
+#define JD_R_0_765366865 6270
+#define JD_R_0_211164243 1730
+#define JD_R_1_451774981 11893
+#define JD_R_2_172734803 17799
+#define JD_R_1_061594337 8697
+#define JD_R_0_509795579 4176
+#define JD_R_0_601344887 4926
+#define JD_R_0_899976223 7373
+#define JD_R_2_562915447 20995
+#define JD_R_0_720959822 5906
+#define JD_R_0_850430095 6967
+#define JD_R_1_272758580 10426
+#define JD_R_3_624509785 29692
+
+struct JdBlockAt {
+    int comp, bx, by, inner;              // component, block position in its plane, block inside the MCU
+    unsigned int m;                       // MCU
+    size_t blk;                           // block in scan order
+};
+
+// where block pb (plane order) lies, as k_jd_idct works it out
+__device__ inline JdBlockAt jd_block_at(const JdGeo &g, unsigned int pb)
+{
+    JdBlockAt a;
+    a.comp = pb >= g.pblocks[2] ? 2 : pb >= g.pblocks[1] ? 1 : 0;
+    const unsigned int local = pb - g.pblocks[a.comp];
+    const int hs = a.comp == 0 ? g.hs : 1, vs = a.comp == 0 ? g.vs : 1;
+    const int bw = g.mcux * hs;
+    a.by = (int)(local / bw);
+    a.bx = (int)(local % bw);
+    a.m = (unsigned int)(a.by / vs) * g.mcux + (unsigned int)(a.bx / hs);
+    a.inner = a.comp == 0 ? (a.by % vs) * hs + (a.bx % hs) : g.ny + a.comp - 1;
+    a.blk = (size_t)a.m * g.bpm + a.inner;
+    return a;
+}
+
+// the DC of that block: differences summed from the start of the restart interval, in 16 bits
+__device__ inline int jd_block_dc(const short *coef, const unsigned int *dcpre, const JdGeo &g, const JdBlockAt &a)
+{
+    const unsigned int m0 = a.m / g.ri * g.ri;
+    const unsigned int *P = dcpre + (size_t)a.comp * g.nmcu;
+    unsigned int dc = P[a.m] - P[m0];
+    const short *mc = coef + (size_t)a.m * g.bpm * 64;
+    if (a.comp == 0) for (int b = 0; b <= a.inner; ++b) dc += (unsigned int)(int)mc[b * 64];
+    else dc += (unsigned int)(int)mc[a.inner * 64];
+    return (int)(short)dc;
+}
+
+// The 4-point pass: x[4] is not read.  Every product is exact (16-bit input, 15-bit constant), the 32-bit sums wrap,
+// the descaled result saturates to 16 bits (the SIMD code packs it).
+template <int SH>
+__device__ inline void jd_idct4(const int x[8], int y[4])
+{
+    typedef unsigned int u;
+    const u t0 = (u)x[0] << 14;
+    const u t2 = (u)(x[2] * JD_R_1_847759065) + (u)(x[6] * -JD_R_0_765366865);
+    const u a0 = (u)(x[7] * -JD_R_0_211164243) + (u)(x[5] * JD_R_1_451774981) + (u)(x[3] * -JD_R_2_172734803) + (u)(x[1] * JD_R_1_061594337);
+    const u a2 = (u)(x[7] * -JD_R_0_509795579) + (u)(x[5] * -JD_R_0_601344887) + (u)(x[3] * JD_R_0_899976223) + (u)(x[1] * JD_R_2_562915447);
+    const u half = 1u << (SH - 1);
+    y[0] = jd_sat16((int)(t0 + t2 + a2 + half) >> SH);
+    y[3] = jd_sat16((int)(t0 + t2 - a2 + half) >> SH);
+    y[1] = jd_sat16((int)(t0 - t2 + a0 + half) >> SH);
+    y[2] = jd_sat16((int)(t0 - t2 - a0 + half) >> SH);
+}
+
+// The 2-point pass over entries 0, 1, 3, 5, 7 (x1 .. x7: 16-bit values; t10: entry 0 shifted up by 15, which in the row pass
+// wraps at 32 bits).  The results are 32-bit numbers.
+template <int SH>
+__device__ inline void jd_idct2(unsigned int t10, int x1, int x3, int x5, int x7, int y[2])
+{
+    typedef unsigned int u;
+    const u t0 = (u)(x7 * -JD_R_0_720959822) + (u)(x5 * JD_R_0_850430095) + (u)(x3 * -JD_R_1_272758580) + (u)(x1 * JD_R_3_624509785);
+    const u half = 1u << (SH - 1);
+    y[0] = (int)(t10 + t0 + half) >> SH;
+    y[1] = (int)(t10 - t0 + half) >> SH;
+}
+
+#define JD_RS_BLOCKS 64                   // blocks per workgroup, four lanes each: 16 blocks per wave
+#define JD_RS_IN 68                       // words per block of dequantised coefficients in LDS: 64 + 4.  The lanes of a wave read
+                                          // column c of their blocks at word 68 b + 8 i + c (+ lane): banks 4 b + lane, all 32 twice
+#define JD_RS_MID 36                      // words per block of column results, rows 9 words apart: a lane reads its row at
+                                          // 36 b + 9 lane + c, banks 4 b + 9 lane: all 32 twice again
+
+// Blocks first .. last - 1 (plane order) of components whose blocks become S x S samples, S = 4 or 2.  Lane l of a block
+// loads the coefficient rows a size reads (4 x 4: 0-3 and 5-7, lane 0 one row, the others two; 2 x 2: 0, 1, 3, 5, 7),
+// dequantises them into LDS, runs the column pass of one or two columns and the row pass of one row, and stores S bytes.
+// Planes are pw = (blocks across) * S bytes wide and start at multiples of 16 bytes (jd_plan), so the stores are aligned.
+template <int S>
+__global__ __launch_bounds__(256) void k_jd_idct_reduced(const short *coef, const unsigned int *dcpre, const JdTables *Tg, JdGeo g,
+                                                         unsigned int first, unsigned int last, uint8_t *planes, const JdCtl *ctl)
+{
+    static_assert(S == 4 || S == 2, "4 x 4 and 2 x 2; 8 x 8 is k_jd_idct, 1 x 1 k_jd_idct_dc");
+    __shared__ int win[JD_RS_BLOCKS * JD_RS_IN];
+    __shared__ int mid[JD_RS_BLOCKS * JD_RS_MID];
+    __shared__ int qt[3][64];
+    if (ctl->status[0]) return;
+    for (int i = threadIdx.x; i < 192; i += 256) qt[i / 64][i % 64] = Tg->qt[i / 64][i % 64];
+    __syncthreads();
+    const unsigned int pb = first + blockIdx.x * JD_RS_BLOCKS + (threadIdx.x >> 2);
+    const int l = threadIdx.x & 3;
+    const bool live = pb < last;
+    int *wi = win + (threadIdx.x >> 2) * JD_RS_IN, *wm = mid + (threadIdx.x >> 2) * JD_RS_MID;
+    JdBlockAt a{};
+    bool ac = false;
+    if (live) {
+        a = jd_block_at(g, pb);
+        // 4 x 4: rows l and, but for lane 0, l + 4.  2 x 2: rows 0 | 1, 5 | 3 | 7.
+        const int r0 = S == 4 ? l : (l == 0 ? 0 : l == 1 ? 1 : l == 2 ? 3 : 7);
+        const int r1 = S == 4 ? (l ? l + 4 : -1) : (l == 1 ? 5 : -1);
+        for (int k = 0; k < 2; ++k) {
+            const int r = k ? r1 : r0;
+            if (r < 0) continue;
+            const uint4 raw = *reinterpret_cast<const uint4 *>(coef + a.blk * 64 + r * 8);
+            const unsigned int rw[4] = {raw.x, raw.y, raw.z, raw.w};
+            int x[8];
+            for (int i = 0; i < 4; ++i) {
+                x[2 * i] = (int)(short)(rw[i] & 0xFFFF);
+                x[2 * i + 1] = (int)(short)(rw[i] >> 16);
+            }
+            if (r == 0) x[0] = jd_block_dc(coef, dcpre, g, a);
+            for (int i = 0; i < 8; ++i) {
+                ac = ac || (r > 0 && x[i] != 0);
+                wi[r * 8 + i] = jd_wrap16(x[i] * qt[a.comp][r * 8 + i]);   // the product keeps its low 16 bits
+            }
+        }
+    }
+    // 4 x 4: a block whose rows 1-3 and 5-7 are all zero takes the SIMD code's short cut in the column pass: row 0 * 4, wrapping at 16 bits
+    const bool cut = S == 4 && ((__ballot(ac) >> (threadIdx.x & 60)) & 0xFull) == 0;
+    __syncthreads();
+    if (live) {
+        if (S == 4) {
+            for (int c = l; c < 8; c += 4) {
+                if (c == 4) continue;                     // column 4 is never read by the row pass
+                int x[8], y[4];
+                for (int i = 0; i < 8; ++i) x[i] = i == 4 ? 0 : wi[i * 8 + c];
+                if (cut) y[0] = y[1] = y[2] = y[3] = jd_wrap16((int)((unsigned int)x[0] << 2));
+                else jd_idct4<12>(x, y);
+                for (int i = 0; i < 4; ++i) wm[i * 9 + c] = y[i];
+            }
+        } else {
+            for (int k = 0; k < 2; ++k) {                 // columns 0 | 1 | 3 | 5, 7
+                const int c = k ? 7 : (l == 0 ? 0 : 2 * l - 1);
+                if (k && l != 3) continue;
+                int y[2];
+                jd_idct2<13>((unsigned int)wi[c] << 15, wi[8 + c], wi[24 + c], wi[40 + c], wi[56 + c], y);
+                wm[c] = y[0];
+                wm[9 + c] = y[1];
+            }
+        }
+    }
+    __syncthreads();
+    if (live && l < S) {                                  // row l of the block
+        const int *row = wm + l * 9;
+        uint8_t *dst = planes + g.poff[a.comp] + (size_t)(a.by * S + l) * g.pw[a.comp] + a.bx * S;
+        if (S == 4) {
+            int x[8], y[4];
+            for (int i = 0; i < 8; ++i) x[i] = i == 4 ? 0 : row[i];
+            jd_idct4<19>(x, y);
+            unsigned int v = 0;
+            for (int i = 0; i < 4; ++i) v |= (unsigned int)(min(127, max(-128, y[i])) + 128) << (8 * i);   // signed saturation to 8 bits, then centred
+            *reinterpret_cast<unsigned int *>(dst) = v;
+        } else {
+            int y[2];                                     // column 0 stays a 32-bit number, the others were packed to 16 bits with saturation
+            jd_idct2<20>((unsigned int)row[0] << 15, jd_sat16(row[1]), jd_sat16(row[3]), jd_sat16(row[5]), jd_sat16(row[7]), y);
+            const unsigned int v = (unsigned int)(min(127, max(-128, y[0])) + 128) | (unsigned int)(min(127, max(-128, y[1])) + 128) << 8;
+            *reinterpret_cast<unsigned short *>(dst) = (unsigned short)v;
+        }
+    }
+}
+
+// 1 x 1: libjpeg's C code.  The quantiser is a signed 16-bit number there, the product is exact, and the result goes
+// through the range-limit table, which takes its index modulo 1024: 0-127 -> 128-255, 128-511 -> 255, 512-895 -> 0, 896-1023 -> 0-127.
+__global__ __launch_bounds__(256) void k_jd_idct_dc(const short *coef, const unsigned int *dcpre, const JdTables *Tg, JdGeo g, unsigned int first,
+                                                    unsigned int last, uint8_t *planes, const JdCtl *ctl)
+{
+    if (ctl->status[0]) return;
+    const unsigned int pb = first + blockIdx.x * 256 + threadIdx.x;
+    if (pb >= last) return;
+    const JdBlockAt a = jd_block_at(g, pb);
+    const int v = (jd_block_dc(coef, dcpre, g, a) * (int)(short)Tg->qt[a.comp][0] + 4) >> 3;
+    const int i = v & 1023;
+    planes[g.poff[a.comp] + (size_t)a.by * g.pw[a.comp] + a.bx] = (uint8_t)(i < 128 ? i + 128 : i < 512 ? 255 : i < 896 ? 0 : i - 896);
+}
+
+// One thread per pixel of the scaled picture (g.w x g.h, planes as jd_plan lays them out for the scale).  hf: how many
+// pixels a chroma sample covers horizontally (2 for 4:2:2, 1 else; vertically it is always 1: the chroma blocks of 4:2:0
+// are twice the luma's size).  fancy: libjpeg's h2v1 triangle filter (jd_chroma), which libjpeg-turbo leaves out at 1/8.
+__global__ __launch_bounds__(256) void k_jd_color_scaled(const uint8_t *planes, JdGeo g, int hf, int fancy, uint8_t *out, const JdCtl *ctl)
+{
+    if (ctl->status[0]) return;
+    const long long n = (long long)g.w * g.h;
+    const int cw = (g.w + hf - 1) / hf;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < n; p += (long long)gridDim.x * 256) {
+        const int y = (int)(p / g.w), x = (int)(p % g.w);
+        const int Y = planes[g.poff[0] + (size_t)y * g.pw[0] + x];
+        if (g.ncomp == 1) {
+            out[p] = (uint8_t)Y;
+            continue;
+        }
+        int c[2];
+        for (int k = 0; k < 2; ++k) {
+            const uint8_t *P = planes + g.poff[1 + k];
+            const int pw = g.pw[1 + k];
+            c[k] = (hf == 1 ? P[(size_t)y * pw + x] : fancy ? jd_chroma(P, pw, cw, g.h, 2, 1, x, y) : P[(size_t)y * pw + (x >> 1)]) - 128;
+        }
+        const int cb = c[0], cr = c[1];
+        const int R = Y + ((91881 * cr + 32768) >> 16);
+        const int G = Y + ((-22554 * cb - 46802 * cr + 32768) >> 16);
+        const int B = Y + ((116130 * cb + 32768) >> 16);
+        out[p * 3] = (uint8_t)min(255, max(0, R));
+        out[p * 3 + 1] = (uint8_t)min(255, max(0, G));
+        out[p * 3 + 2] = (uint8_t)min(255, max(0, B));
+    }
+}
+
 // ------------------------------------------------------------------------------------------------- host side
 // lars_jpeg_info's info[] by name (sampling: component 0's, the others are checked to be 1 x 1)
 struct JpegInfo {
@@ -694,8 +921,14 @@ struct JpegInfo {
 };
 
 // geometry and the device scratch of one file: what lars_jpeg_decode_scratch_bytes counts and lars_d_decode_jpeg_u8 points into
+// At scale 2, 4 or 8 (m = 8 / scale) gs is g with the picture and the planes of that scale: the picture is ceil(w / scale) x
+// ceil(h / scale); a block of component c becomes bs[c] samples wide and high -- m, doubled while it is below 8 and both
+// hmax * m and vmax * m stay multiples of h_c * bs * 2 and v_c * bs * 2 (libjpeg's rule: m for luma and for the chroma of
+// 4:2:2, 2 m for the chroma of 4:2:0) -- so plane c is (blocks across) * bs[c] bytes wide, (blocks down) * bs[c] rows high,
+// and every plane starts at a multiple of 16 bytes.  hf = 2 where the chroma planes are half as wide as the picture.
 struct JdPlan {
-    JdGeo g;
+    JdGeo g, gs;
+    int scale, bs[3], hf;
     jd_u64 elen, nwg, nsub_cap;
     unsigned int sbits;
     JdCtl *ctl;
@@ -708,9 +941,10 @@ struct JdPlan {
 };
 
 // false for what the decoder does not take
-static bool jd_plan(const JpegInfo &I, int sbits, Carver &cv, JdPlan *Lp)
+static bool jd_plan(const JpegInfo &I, int sbits, int scale, Carver &cv, JdPlan *Lp)
 {
     JdPlan L{};
+    if (scale != 1 && scale != 2 && scale != 4 && scale != 8) return false;
     const int64_t w = I.w, h = I.h, nc = I.ncomp;
     if (!I.supported || w < 1 || h < 1 || w > 65535 || h > 65535 || (nc != 1 && nc != 3) || h * w * nc >= (1ll << 31)) return false;
     if (I.eoff < 0 || I.elen < 0 || I.elen > (1ll << 40) || I.ri < 0 || I.ri > 65535) return false;
@@ -737,6 +971,29 @@ static bool jd_plan(const JpegInfo &I, int sbits, Carver &cv, JdPlan *Lp)
         blocks += (unsigned int)(g.pw[c] / 8) * (g.ph[c] / 8);
     }
     g.pblocks[3] = blocks;
+    L.scale = scale;
+    L.gs = g;
+    L.hf = 1;
+    for (int c = 0; c < 3; ++c) L.bs[c] = 8;
+    if (scale > 1) {
+        const int m = 8 / scale;
+        JdGeo &gs = L.gs;
+        gs.w = (int)((w + scale - 1) / scale);
+        gs.h = (int)((h + scale - 1) / scale);
+        off = 0;
+        for (int c = 0; c < nc; ++c) {
+            const int hc = c == 0 ? hs : 1, vc = c == 0 ? vs : 1;
+            int s = m;
+            while (s < 8 && (hs * m) % (hc * s * 2) == 0 && (vs * m) % (vc * s * 2) == 0) s *= 2;
+            L.bs[c] = s;
+            gs.pw[c] = g.mcux * hc * s;
+            gs.ph[c] = g.mcuy * vc * s;
+            gs.poff[c] = off;
+            off += ((unsigned int)gs.pw[c] * gs.ph[c] + 15u) & ~15u;    // no larger than at full scale
+        }
+        for (int c = (int)nc; c < 3; ++c) gs.poff[c] = off;
+        if (nc == 3) L.hf = hs * m / L.bs[1];
+    }
     L.elen = (jd_u64)I.elen;
     L.sbits = (unsigned int)sbits;
     L.nwg = (L.elen + JD_MARK_THREADS - 1) / JD_MARK_THREADS;
@@ -793,6 +1050,7 @@ static const char *jd_reason(int64_t r)
 struct JdFile : HostFile {
     int64_t info[LARS_JPEG_INFO_N];
     JdCtl ctl;
+    int scale = 1;                        // 2, 4, 8: h and w are the scaled picture's
 
     int parse(const char *who_, const uint8_t *file_, int64_t len_)
     {
@@ -801,14 +1059,15 @@ struct JdFile : HostFile {
         LARS_TRY(lars_jpeg_info(file, len, info));
         const JpegInfo I(info);
         if (!I.supported) return fail(LARS_ERR_UNSUPPORTED, "%s: %s JPEG files are not supported", who, jd_reason(I.reason));
-        h = I.h; w = I.w; channels = (int)I.ncomp;
+        if (scale != 1 && scale != 2 && scale != 4 && scale != 8) return fail(LARS_ERR_INVALID, "%s: scale 1, 2, 4 or 8, got %d", who, scale);
+        h = (I.h + scale - 1) / scale; w = (I.w + scale - 1) / scale; channels = (int)I.ncomp;
         extra_bytes = 0;
-        scratch_bytes = lars_jpeg_decode_scratch_bytes(info);
+        scratch_bytes = lars_jpeg_decode_scaled_scratch_bytes(info, scale);
         return LARS_OK;
     }
     int enqueue(hipStream_t s)
     {
-        LARS_TRY(lars_d_decode_jpeg_u8(d_file, file, info, d_img, d_status, d_scratch, s));
+        LARS_TRY(lars_d_decode_jpeg_scaled_u8(d_file, file, info, scale, d_img, d_status, d_scratch, s));
         // the control block opens the scratch: the rounds that decoded anything
         LARS_HIP_TRY(hipMemcpyAsync(&ctl, d_scratch, sizeof ctl, hipMemcpyDeviceToHost, s));
         return LARS_OK;
@@ -829,25 +1088,30 @@ using namespace lars;
 
 extern "C" {
 
-size_t lars_jpeg_decode_scratch_bytes(const int64_t info[LARS_JPEG_INFO_N])
+size_t lars_jpeg_decode_scratch_bytes(const int64_t info[LARS_JPEG_INFO_N]) { return lars_jpeg_decode_scaled_scratch_bytes(info, 1); }
+
+size_t lars_jpeg_decode_scaled_scratch_bytes(const int64_t info[LARS_JPEG_INFO_N], int scale)
 {
     JdPlan L;
     Carver size(nullptr);
-    if (!info || !jd_plan(JpegInfo(info), tuning().jpeg_subseq_bits, size, &L)) return 0;
+    if (!info || !jd_plan(JpegInfo(info), tuning().jpeg_subseq_bits, scale, size, &L)) return 0;
     return size.bytes();
 }
 
-int lars_d_decode_jpeg_u8(const uint8_t *file_dev, const uint8_t *head, const int64_t info[LARS_JPEG_INFO_N], uint8_t *out,
-                          int32_t *status_dev, void *scratch, void *stream)
+}  // extern "C"
+
+// lars_d_decode_jpeg_u8 (scale 1) and lars_d_decode_jpeg_scaled_u8
+static int jd_enqueue(const char *who, const uint8_t *file_dev, const uint8_t *head, const int64_t info[LARS_JPEG_INFO_N], int scale, uint8_t *out,
+                      int32_t *status_dev, void *scratch, void *stream)
 {
-    static const char *who = "lars_d_decode_jpeg_u8";
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (!file_dev || !head || !info || !out || !status_dev || !scratch) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
     const JpegInfo I(info);
     JdPlan L;
     Carver cv(scratch);
-    if (!jd_plan(I, tuning().jpeg_subseq_bits, cv, &L)) return fail(LARS_ERR_INVALID, "%s: info describes no file this decoder takes", who);
+    if (scale != 1 && scale != 2 && scale != 4 && scale != 8) return fail(LARS_ERR_INVALID, "%s: scale 1, 2, 4 or 8, got %d", who, scale);
+    if (!jd_plan(I, tuning().jpeg_subseq_bits, scale, cv, &L)) return fail(LARS_ERR_INVALID, "%s: info describes no file this decoder takes", who);
     JpegHeader H;
     LARS_TRY(jpeg_parse(head, I.eoff, &H, false));
     if (!H.supported || H.w != I.w || H.h != I.h || H.ncomp != I.ncomp || H.eoff != I.eoff || H.ri != I.ri ||
@@ -892,11 +1156,42 @@ int lars_d_decode_jpeg_u8(const uint8_t *file_dev, const uint8_t *head, const in
     hipLaunchKernelGGL(k_jd_write, dim3(sgrid), dim3(256), 0, s, L.tables, words, L.subs, L.in, L.pre, g.bpm, g.ny, g.nblocks, L.coef, ctl);
     hipLaunchKernelGGL(k_jd_mcu_sums, dim3((g.nmcu + 255) / 256), dim3(256), 0, s, L.coef, g, L.sums, ctl);
     hipLaunchKernelGGL(k_jd_exscan, dim3((unsigned)g.ncomp), dim3(1024), 0, s, L.sums, L.sums, (long long)g.nmcu, (long long)g.nmcu, (unsigned int *)nullptr);
-    hipLaunchKernelGGL(k_jd_idct, dim3((g.pblocks[3] + 31) / 32), dim3(256), 0, s, L.coef, L.sums, L.tables, g, L.planes, ctl);
-    const long long npix = (long long)g.w * g.h;
-    hipLaunchKernelGGL(k_jd_color, dim3((unsigned)std::min<long long>((npix + 255) / 256, 16384)), dim3(256), 0, s, L.planes, g, out, ctl);
+    if (scale == 1) {
+        hipLaunchKernelGGL(k_jd_idct, dim3((g.pblocks[3] + 31) / 32), dim3(256), 0, s, L.coef, L.sums, L.tables, g, 0u, L.planes, ctl);
+        const long long npix = (long long)g.w * g.h;
+        hipLaunchKernelGGL(k_jd_color, dim3((unsigned)std::min<long long>((npix + 255) / 256, 16384)), dim3(256), 0, s, L.planes, g, out, ctl);
+    } else {
+        // luma, then both chroma planes (their blocks have one size): each group with the kernel of its block size
+        const JdGeo &gs = L.gs;
+        for (int grp = 0; grp < (g.ncomp == 3 ? 2 : 1); ++grp) {
+            const unsigned int first = g.pblocks[grp], last = grp ? g.pblocks[3] : g.pblocks[1], n = last - first;
+            switch (L.bs[grp]) {
+            case 8: hipLaunchKernelGGL(k_jd_idct, dim3((n + 31) / 32), dim3(256), 0, s, L.coef, L.sums, L.tables, gs, first, L.planes, ctl); break;
+            case 4: hipLaunchKernelGGL(k_jd_idct_reduced<4>, dim3((n + JD_RS_BLOCKS - 1) / JD_RS_BLOCKS), dim3(256), 0, s, L.coef, L.sums, L.tables, gs, first, last, L.planes, ctl); break;
+            case 2: hipLaunchKernelGGL(k_jd_idct_reduced<2>, dim3((n + JD_RS_BLOCKS - 1) / JD_RS_BLOCKS), dim3(256), 0, s, L.coef, L.sums, L.tables, gs, first, last, L.planes, ctl); break;
+            default: hipLaunchKernelGGL(k_jd_idct_dc, dim3((n + 255) / 256), dim3(256), 0, s, L.coef, L.sums, L.tables, gs, first, last, L.planes, ctl); break;
+            }
+        }
+        const long long npix = (long long)gs.w * gs.h;
+        hipLaunchKernelGGL(k_jd_color_scaled, dim3((unsigned)std::min<long long>((npix + 255) / 256, 16384)), dim3(256), 0, s, L.planes, gs, L.hf,
+                           scale < 8 ? 1 : 0, out, ctl);
+    }
     LARS_HIP_TRY(hipMemcpyAsync(status_dev, ctl->status, 8, hipMemcpyDeviceToDevice, s));
     return launch_check(who);
+}
+
+extern "C" {
+
+int lars_d_decode_jpeg_u8(const uint8_t *file_dev, const uint8_t *head, const int64_t info[LARS_JPEG_INFO_N], uint8_t *out,
+                          int32_t *status_dev, void *scratch, void *stream)
+{
+    return jd_enqueue("lars_d_decode_jpeg_u8", file_dev, head, info, 1, out, status_dev, scratch, stream);
+}
+
+int lars_d_decode_jpeg_scaled_u8(const uint8_t *file_dev, const uint8_t *head, const int64_t info[LARS_JPEG_INFO_N], int scale, uint8_t *out,
+                                 int32_t *status_dev, void *scratch, void *stream)
+{
+    return jd_enqueue("lars_d_decode_jpeg_scaled_u8", file_dev, head, info, scale, out, status_dev, scratch, stream);
 }
 
 // host file in, host pixels out: one upload, the status, one download
@@ -911,6 +1206,19 @@ int lars_h_decode_jpeg_u8(const uint8_t *file, int64_t len, uint8_t *out, size_t
     return decode_file_to_host(c, F, out, out_cap);
 }
 
+// ... at 1/scale: out holds ceil(h / scale) * ceil(w / scale) * components bytes
+int lars_h_decode_jpeg_scaled_u8(const uint8_t *file, int64_t len, int scale, uint8_t *out, size_t out_cap)
+{
+    static const char *who = "lars_h_decode_jpeg_scaled_u8";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!out) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    JdFile F;
+    F.scale = scale;
+    LARS_TRY(F.parse(who, file, len));
+    return decode_file_to_host(c, F, out, out_cap);
+}
+
 // host file in, thumbnail out: the decoded pixels go straight into the thumbnail kernels (resize.hip)
 int lars_h_thumbnail_jpeg_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
                              int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out)
@@ -920,6 +1228,20 @@ int lars_h_thumbnail_jpeg_u8(const uint8_t *file, int64_t len, int fx, int fy, c
     LARS_TRY(ensure_ctx(&c));
     if (!out || !reduce_box || !box) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
     JdFile F;
+    LARS_TRY(F.parse(who, file, len));
+    return thumbnail_file(c, F, fx, fy, reduce_box, box, new_h, new_w, vertical_first, out);
+}
+
+// ... from the picture decoded at 1/scale: the plan's numbers are for that picture
+int lars_h_thumbnail_jpeg_scaled_u8(const uint8_t *file, int64_t len, int scale, int fx, int fy, const int reduce_box[4], const float box[4],
+                                    int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out)
+{
+    static const char *who = "lars_h_thumbnail_jpeg_scaled_u8";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!out || !reduce_box || !box) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    JdFile F;
+    F.scale = scale;
     LARS_TRY(F.parse(who, file, len));
     return thumbnail_file(c, F, fx, fy, reduce_box, box, new_h, new_w, vertical_first, out);
 }

@@ -10,9 +10,15 @@ refuses the others.  Per file, host bytes in and host array out, ending in a dev
 ``--files`` different files after a warm-up pass.  Every result is checked against Pillow's first.  ``--split`` adds the
 parts of one call (host parse, upload, decode on the device, download); ``--sweep`` the "jpeg_subseq_bits" sweep.
 
-    python tools/jpegdecodebench.py [--files 20] [--split] [--sweep] [--gpu-only] [--json out.json]
+The gallery legs (``GALLERY``) are what ``load_image_from_db(..., thumbnail=True)`` runs: ``thumbnail_jpeg(b, box,
+scaled=True)`` against Pillow's ``thumbnail(box, LANCZOS)``, which lets ``draft`` decode at the scale ``jpeg_draft_scale``
+names -- on the same files, in the same run.  The box of the application is 400 x 400: that is full scale for the 2048 x 1536
+files (their short side is below 4 x 400) and 1/4 for the 4096 x 4096 ones; 350 x 350 and 200 x 200 add 1/2 and 1/8.
+
+    python tools/jpegdecodebench.py [--files 20] [--split] [--sweep] [--gpu-only] [--only-gallery] [--json out.json]
 
 Kernel times come from a separate run:  rocprofv3 --kernel-trace --stats -- python tools/jpegdecodebench.py --gpu-only
+(with ``--only-gallery`` for the scaled decoder's kernels alone)
 """
 import argparse
 import ctypes as C
@@ -32,6 +38,7 @@ from lars_image_processing_amd import _ffi  # noqa: E402
 from pngbench import field_1f  # noqa: E402
 
 KINDS = {"gallery_2048x1536_rgb": ((1536, 2048), (800, 800)), "rgb_4096x4096": ((4096, 4096), (1100, 1100))}
+GALLERY = {"gallery_2048x1536_rgb": [((400, 400), 1), ((350, 350), 2)], "rgb_4096x4096": [((400, 400), 4), ((200, 200), 8)]}   # (box, draft scale)
 
 
 def pictures(shape, n, seed):
@@ -116,12 +123,32 @@ def split_ms(b, reps=20):
     return {"host_parse_ms": parse, "upload_ms": upload, "device_decode_ms": device, "download_ms": download}
 
 
+def gallery_legs(name, shape, files, gpu_only):
+    """thumbnail_jpeg(b, box, scaled=True) and decode_jpeg(b, scale) against Pillow's thumbnail (draft and all) per box."""
+    out = {}
+    for box, scale in GALLERY[name]:
+        assert lars.jpeg_draft_scale((shape[1], shape[0]), box) == scale
+        for b in files[:2]:
+            im = pil_thumb(b, box)
+            assert (im.decoderconfig[0] if im.decoderconfig else 1) == scale
+            assert lars.thumbnail_jpeg(b, box, scaled=True).tobytes() == np.asarray(im).tobytes()
+        r = {"draft_scale": scale,
+             "thumbnail_jpeg_scaled_ms": per_file_ms(lambda b: lars.thumbnail_jpeg(b, box, scaled=True), files, True),
+             "decode_jpeg_at_scale_ms": per_file_ms(lambda b: lars.decode_jpeg(b, scale), files, True)}
+        if not gpu_only:
+            r["pillow_thumbnail_ms"] = per_file_ms(lambda b: pil_thumb(b, box), files, False)
+            r["thumbnail_speedup"] = r["pillow_thumbnail_ms"] / r["thumbnail_jpeg_scaled_ms"]
+        out["%dx%d" % box] = r
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--files", type=int, default=20, help="files per kind (each timed once after the warm-up)")
     ap.add_argument("--gpu-only", action="store_true", help="skip the Pillow legs (for a kernel trace)")
     ap.add_argument("--split", action="store_true", help="also time the parts of one call")
     ap.add_argument("--sweep", action="store_true", help='also sweep "jpeg_subseq_bits"')
+    ap.add_argument("--only-gallery", action="store_true", help="only the gallery legs (scaled=True against Pillow's draft)")
     ap.add_argument("--json", help="also write the figures to this file")
     args = ap.parse_args()
     if _ffi.device_count() < 1:
@@ -132,6 +159,11 @@ def main():
     for name, (shape, size) in KINDS.items():
         files = [pil_jpeg(a) for a in pictures(shape, args.files, seed=11)]
         assert lars.jpeg_draft_scale((shape[1], shape[0]), size) == 1
+        if args.only_gallery:
+            r = {"files": len(files), "shape": [shape[0], shape[1], 3], "gallery": gallery_legs(name, shape, files, args.gpu_only)}
+            res["kinds"][name] = r
+            print(name, json.dumps(r), flush=True)
+            continue
         for b in files[:2]:                                   # a fast wrong answer is no answer
             assert lars.decode_jpeg(b).tobytes() == np.asarray(pil_decode(b)).tobytes()
             assert lars.thumbnail_jpeg(b, size).tobytes() == np.asarray(pil_thumb(b, size)).tobytes()
@@ -144,6 +176,7 @@ def main():
             r["pillow_thumbnail_ms"] = per_file_ms(lambda b: pil_thumb(b, size), files, False)
             r["decode_speedup"] = r["pillow_load_ms"] / r["decode_jpeg_ms"]
             r["thumbnail_speedup"] = r["pillow_thumbnail_ms"] / r["thumbnail_jpeg_ms"]
+        r["gallery"] = gallery_legs(name, shape, files, args.gpu_only)
         lars.decode_jpeg(files[0])
         r["sync_rounds_first_file"] = _ffi.get_tuning("jpeg_last_rounds")
         if args.split:
