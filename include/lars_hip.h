@@ -652,7 +652,13 @@ int lars_h_tiff_lzw_decode_chunks(const uint8_t *file, int64_t file_len, const u
  * supported 0 and a LARS_TIFF_REASON_*; structural damage is LARS_ERR_INVALID.
  * lars_h_decode_tiff: host file in, host samples out (out_cap in BYTES >= h * w * samples * bits / 8); one upload, one download.
  * lars_h_thumbnail_tiff_u8: host file in (8 bit, one BlackIsZero sample or RGB, no extra samples), lars_h_thumbnail_u8's
- * plan numbers, host thumbnail out; the decoded pixels never leave the device. */
+ * plan numbers, host thumbnail out; the decoded pixels never leave the device.
+ * lars_tiff_info_deflate, lars_h_decode_tiff_deflate, lars_h_thumbnail_tiff_deflate_u8: the same three for callers who opt in
+ * to Deflate on the device -- compression 8 (GDAL's COMPRESS=DEFLATE, tifffile, Pillow's tiff_adobe_deflate) and 32946, the
+ * files the uploads of process-images.py:1237 and backend-process.py:52, :88 most often are.  The walk treats such a file as
+ * it treats an LZW file (geometry, chunk table, predictor 1 / 2, the 2^31 limit on the padded chunks) and ends with
+ * supported 1; for every other file each gives what its sibling gives.  Every strip / tile is one zlib stream, judged as
+ * tiffio._chunk judges it: LARS_TIFD_CORRUPT, LARS_TIFD_PAST and LARS_TIFD_SHORT for the first such chunk in file order. */
 #define LARS_TIFF_INFO_N 16
 enum {                           /* positions in lars_tiff_info's info[] */
     LARS_TIFF_INFO_WIDTH = 0,
@@ -689,10 +695,15 @@ enum {
 enum {
     LARS_TIFD_OK = 0,
     LARS_TIFD_CORRUPT = 1,       /* an LZW code the table does not hold; detail: the strip / tile */
-    LARS_TIFD_SHORT = 2          /* a strip / tile decodes to too few bytes; detail: the strip / tile */
+    LARS_TIFD_SHORT = 2,         /* a strip / tile decodes to too few bytes; detail: the strip / tile */
+    LARS_TIFD_PAST = 3           /* a Deflate strip / tile goes on behind the bytes the directory gives it; detail: the strip / tile */
 };
 int lars_tiff_info(const uint8_t *file, int64_t len, int64_t info[LARS_TIFF_INFO_N], int64_t *chunk_table, int64_t table_cap);
 int lars_h_decode_tiff(const uint8_t *file, int64_t len, void *out, size_t out_cap);
+int lars_tiff_info_deflate(const uint8_t *file, int64_t len, int64_t info[LARS_TIFF_INFO_N], int64_t *chunk_table, int64_t table_cap);
+int lars_h_decode_tiff_deflate(const uint8_t *file, int64_t len, void *out, size_t out_cap);
+int lars_h_thumbnail_tiff_deflate_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
+                                     int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out);
 int lars_h_thumbnail_tiff_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
                              int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out);
 

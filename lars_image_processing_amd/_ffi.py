@@ -243,6 +243,9 @@ SIGNATURES = {
     "lars_tiff_info": (_I, [_P, _I64, _P, _P, _I64]),
     "lars_h_decode_tiff": (_I, [_P, _I64, _P, _SZ]),
     "lars_h_thumbnail_tiff_u8": (_I, [_P, _I64, _I, _I, C.POINTER(_I), C.POINTER(_F), _I64, _I64, _I, _P]),
+    "lars_tiff_info_deflate": (_I, [_P, _I64, _P, _P, _I64]),
+    "lars_h_decode_tiff_deflate": (_I, [_P, _I64, _P, _SZ]),
+    "lars_h_thumbnail_tiff_deflate_u8": (_I, [_P, _I64, _I, _I, C.POINTER(_I), C.POINTER(_F), _I64, _I64, _I, _P]),
     "lars_tiff_bound": (_SZ, [_I64, _I64, _I, _I, _I64]),
     "lars_tiff_encode_scratch_bytes": (_SZ, [_I64, _I64, _I, _I, _I64]),
     "lars_d_encode_tiff": (_I, [_P, _I64, _I64, _I, _I, _I64, _I, _P, _SZ, _P, _P, _P, _P]),

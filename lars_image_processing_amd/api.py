@@ -935,10 +935,10 @@ _TIFF_REASONS = {"NONE": None, "BIGTIFF": "BigTIFF (64-bit offsets)", "BITS": "s
 _TIFF_REASON_TEXT = dict(enumerate(_TIFF_REASONS.values()))
 
 
-def _tiff_info(arr):
+def _tiff_info(arr, deflate=False):
     lib = _ffi.load()
     info = _ffi.TiffInfo.array()
-    if lib.lars_tiff_info(_ffi.ptr(arr), arr.size, info, None, 0) != 0:
+    if (lib.lars_tiff_info_deflate if deflate else lib.lars_tiff_info)(_ffi.ptr(arr), arr.size, info, None, 0) != 0:
         raise ValueError(lib.lars_last_error().decode("utf-8", "replace"))
     return _ffi.TiffInfo(*info)
 
@@ -947,8 +947,10 @@ def _tiff_shape(i):
     return (i.height, i.width) if i.samples == 1 else (i.height, i.width, i.samples)
 
 
-def tiff_info(data):
+def tiff_info(data, deflate=False):
     """The first directory of a TIFF file, read on the host by ``tiffio.read_tiff``'s rules (``lars_tiff_info``; no device needed).
+    ``deflate=True`` answers for ``decode_tiff(data, deflate=True)`` (``lars_tiff_info_deflate``): a Deflate file is supported,
+    every other file reads as without the flag.
 
     Returns ``width``, ``height``, ``samples``, ``bits``, ``compression``, ``predictor``, ``planar``, ``big_endian``,
     ``photometric`` (-1: no such tag), ``extra_samples``, ``tiled``, ``chunk_w``, ``chunk_h``, ``chunks`` (strips / tiles),
@@ -957,7 +959,7 @@ def tiff_info(data):
     depths, signed or float samples, BigTIFF, 2^31 bytes or more).  Raises ``ValueError`` for structural damage: no byte-order
     mark, a directory, a tag's values or a strip / tile outside the file, a missing required tag, a wrong number of strips.
     """
-    i = _tiff_info(_file_bytes(data, "tiff_info", "TIFF"))
+    i = _tiff_info(_file_bytes(data, "tiff_info", "TIFF"), bool(deflate))
     out = i._asdict()
     for k in ("big_endian", "tiled", "supported"):
         out[k] = bool(out[k])
@@ -968,15 +970,15 @@ def tiff_info(data):
     return out
 
 
-def _tiff_check(arr, who):
+def _tiff_check(arr, who, deflate=False):
     from .tiffio import TiffError
     try:
-        i = _tiff_info(arr)
+        i = _tiff_info(arr, deflate)
     except ValueError as e:
         raise TiffError(str(e)) from None
     if not i.supported:
         raise NotImplementedError(f"{who}: TIFF files with {_TIFF_REASON_TEXT.get(i.reason, i.reason)} are not decoded on the device "
-                                  "(classic TIFF, 8 or 16 bit unsigned samples, uncompressed or LZW)")
+                                  "(classic TIFF, 8 or 16 bit unsigned samples, uncompressed or LZW; Deflate with deflate=True)")
     return i
 
 
@@ -990,7 +992,7 @@ def _tiff_call(name, *args):
         raise
 
 
-def decode_tiff(data):
+def decode_tiff(data, deflate=False):
     """``tiffio.read_tiff(data)`` of a TIFF file, decoded on the GPU: the same array bit for bit, dtype and shape included
     (the ``Image.open(io.BytesIO(...))`` of process-images.py:183 for the first accepted extension, at the file's full depth).
 
@@ -999,11 +1001,19 @@ def decode_tiff(data):
     strips or tiles: ``[H, W, C]`` (``[H, W]`` for one sample) uint8 or native-endian uint16.  Other variants
     (``tiff_info(data)["reason"]``) raise ``NotImplementedError`` before anything is launched; damaged files raise
     ``tiffio.TiffError`` (a ``ValueError``) where ``read_tiff`` does.  No CPU fallback.
+
+    ``deflate=True``: Deflate files (compression 8, what GDAL's ``COMPRESS=DEFLATE``, tifffile and Pillow's
+    ``tiff_adobe_deflate`` write, and 32946) are decoded as well, one zlib stream per strip / tile, refused where zlib
+    refuses them for ``read_tiff``: "corrupt Deflate data", "inflates past its N bytes", "holds N bytes, M expected", for
+    the first such strip / tile of the file.  One lane decodes a strip's symbols, so the gain comes from the number of
+    strips / tiles: a file written as one huge strip gains nothing and may lose against zlib on the host.  The default is
+    unchanged: without the flag a Deflate file raises ``NotImplementedError``.
     """
     arr = _file_bytes(data, "decode_tiff", "TIFF")
-    i = _tiff_check(arr, "decode_tiff")
+    deflate = bool(deflate)
+    i = _tiff_check(arr, "decode_tiff", deflate)
     out = np.empty(_tiff_shape(i), dtype=np.uint8 if i.bits == 8 else np.uint16)
-    _tiff_call("lars_h_decode_tiff", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
+    _tiff_call("lars_h_decode_tiff_deflate" if deflate else "lars_h_decode_tiff", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
     return out
 
 
@@ -1012,23 +1022,25 @@ def _tiff_is_pillow_u8(i):
     return i.bits == 8 and i.extra_samples == 0 and ((i.samples == 1 and i.photometric == 1) or (i.samples == 3 and i.photometric == 2))
 
 
-def thumbnail_tiff(data, size=(400, 400), reducing_gap=2.0):
+def thumbnail_tiff(data, size=(400, 400), reducing_gap=2.0, deflate=False):
     """``np.asarray`` of ``Image.open(io.BytesIO(data))`` after ``.thumbnail(size, LANCZOS, reducing_gap)``, bit for bit
     (process-images.py:186-189), from a TIFF file's bytes: the decoded pixels stay on the GPU and go straight into the
     thumbnail kernels, only the thumbnail comes back.  8-bit files with one sample (BlackIsZero) or three (RGB) and no
     extra samples; others raise ``TypeError``.  ``draft`` does nothing for TIFF, so ``thumbnail_plan(..., draft_box=None)``
-    is the whole plan; a file that already fits comes back as ``decode_tiff`` gives it.  Errors of the file as ``decode_tiff``."""
+    is the whole plan; a file that already fits comes back as ``decode_tiff`` gives it.  Errors of the file as ``decode_tiff``.
+    ``deflate=True``: Deflate files too, as in ``decode_tiff``."""
     arr = _file_bytes(data, "thumbnail_tiff", "TIFF")
-    i = _tiff_check(arr, "thumbnail_tiff")
+    deflate = bool(deflate)
+    i = _tiff_check(arr, "thumbnail_tiff", deflate)
     if not _tiff_is_pillow_u8(i):
         raise TypeError(f"thumbnail_tiff: 8-bit TIFF files in mode L or RGB (got {i.samples} samples of {i.bits} bits, "
                         f"photometric {i.photometric}, {i.extra_samples} extra samples)")
     plan = thumbnail_plan((i.width, i.height), size, reducing_gap, None, None)
     if plan is None:
-        return decode_tiff(arr)
+        return decode_tiff(arr, deflate=True) if deflate else decode_tiff(arr)
     from .tiffio import TiffError
     try:
-        return _file_thumbnail("lars_h_thumbnail_tiff_u8", arr, plan, i.samples)
+        return _file_thumbnail("lars_h_thumbnail_tiff_deflate_u8" if deflate else "lars_h_thumbnail_tiff_u8", arr, plan, i.samples)
     except ValueError as e:
         raise TiffError(str(e)) from None
 

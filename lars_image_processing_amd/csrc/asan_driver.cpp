@@ -9,6 +9,7 @@
 //   kind 4  lars_jpeg_info over a JPEG file = bytes
 //   kind 5  lars_jpeg_header and lars_jpeg_bound: bytes = int32 { h, w, channels, subsampling, quality }, out of a bytes
 //   kind 6  lars_tiff_info (tiff-info mode) over a TIFF file = bytes, with a chunk table of a entries
+//   kind 7  lars_tiff_info_deflate over the same
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -84,10 +85,10 @@ int main(int argc, char **argv)
             printf("%ld jpeghead n=%lld h=%016llx bound=%zu\n", ncase, n, n > 0 ? fnv(dst, (size_t)n) : 0ull,
                    lars_jpeg_bound(v[0], v[1], v[2], v[3]));
             free(dst);
-        } else if (kind == 6) {
+        } else if (kind == 6 || kind == 7) {
             int64_t info[LARS_TIFF_INFO_N];
             std::vector<int64_t> table((size_t)a * 2 + 1, 0);
-            const int rc = lars_tiff_info(src, nbytes, info, a ? table.data() : nullptr, a);
+            const int rc = (kind == 6 ? lars_tiff_info : lars_tiff_info_deflate)(src, nbytes, info, a ? table.data() : nullptr, a);
             printf("%ld tiff rc=%d h=%016llx t=%016llx\n", ncase, rc, rc == 0 ? fnv(info, sizeof info) : 0ull,
                    rc == 0 ? fnv(table.data(), (size_t)a * 16) : 0ull);
         } else {

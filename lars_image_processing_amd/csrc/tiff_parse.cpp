@@ -1,4 +1,5 @@
-// Host side of the TIFF decoder: the first directory of a classic TIFF file, validated without a device (lars_tiff_info).
+// Host side of the TIFF decoder: the first directory of a classic TIFF file, validated without a device (lars_tiff_info, and
+// lars_tiff_info_deflate for callers who opt in to Deflate on the device: the same walk with compression 8 / 32946 let through).
 // A C++ restatement of the directory walk in tiffio.read_tiff, with the same rules in the same order, so that a file the
 // Python reader refuses is refused here for the same cause.  Every offset and count is checked against the file length in
 // 64-bit arithmetic before it is used.  No HIP here: builds into liblars_hip.so and with plain g++ under AddressSanitizer /
@@ -47,7 +48,10 @@ const int TAGS[T_N] = {256, 257, 258, 259, 262, 273, 277, 278, 279, 284, 317, 32
 
 using namespace lars;
 
-extern "C" int lars_tiff_info(const uint8_t *file, int64_t len, int64_t info[LARS_TIFF_INFO_N], int64_t *chunk_table, int64_t table_cap)
+namespace {
+
+// the walk behind lars_tiff_info and lars_tiff_info_deflate; deflate: compression 8 / 32946 goes the way LZW goes
+int tiff_walk(const uint8_t *file, int64_t len, int64_t info[LARS_TIFF_INFO_N], int64_t *chunk_table, int64_t table_cap, bool deflate)
 {
     if (!file || len < 0 || !info || table_cap < 0 || (table_cap > 0 && !chunk_table))
         return fail(LARS_ERR_INVALID, "lars_tiff_info: bad arguments");
@@ -112,7 +116,8 @@ extern "C" int lars_tiff_info(const uint8_t *file, int64_t len, int64_t info[LAR
             if (d.value(tag[T_FORMAT], k) != 1) return unsupported(LARS_TIFF_REASON_SAMPLE_FORMAT);
     const int64_t compression = one(T_COMPRESSION, 1, false);
     info[LARS_TIFF_INFO_COMPRESSION] = compression;
-    if (compression != 1 && compression != 5) {
+    const bool inflated = deflate && (compression == 8 || compression == 32946);
+    if (compression != 1 && compression != 5 && !inflated) {
         switch (compression) {
         case 8: case 32946: return unsupported(LARS_TIFF_REASON_DEFLATE);
         case 32773: return unsupported(LARS_TIFF_REASON_PACKBITS);
@@ -165,7 +170,7 @@ extern "C" int lars_tiff_info(const uint8_t *file, int64_t len, int64_t info[LAR
         return fail(LARS_ERR_INVALID, "tiff: %lld strips / tiles, %lld expected", (long long)nchunks, (long long)(across * down * planes));
     info[LARS_TIFF_INFO_CHUNKS] = nchunks;
     const int64_t full = chunk_h * chunk_w * inner * bps;               // bytes of a whole strip / tile (< 2^31, see above)
-    if (compression == 5 && full * nchunks >= limit) return unsupported(LARS_TIFF_REASON_SIZE);   // the padded chunks, decoded
+    if ((compression == 5 || inflated) && full * nchunks >= limit) return unsupported(LARS_TIFF_REASON_SIZE);   // the padded chunks, decoded
     bool old_lzw = false;
     for (int64_t k = 0; k < nchunks; ++k) {
         const int64_t off = d.value(tag[t_off], k);
@@ -186,4 +191,17 @@ extern "C" int lars_tiff_info(const uint8_t *file, int64_t len, int64_t info[LAR
     if (old_lzw) return unsupported(LARS_TIFF_REASON_OLD_LZW);
     info[LARS_TIFF_INFO_SUPPORTED] = 1;
     return LARS_OK;
+}
+
+}  // namespace
+
+extern "C" int lars_tiff_info(const uint8_t *file, int64_t len, int64_t info[LARS_TIFF_INFO_N], int64_t *chunk_table, int64_t table_cap)
+{
+    return tiff_walk(file, len, info, chunk_table, table_cap, false);
+}
+
+extern "C" int lars_tiff_info_deflate(const uint8_t *file, int64_t len, int64_t info[LARS_TIFF_INFO_N], int64_t *chunk_table,
+                                      int64_t table_cap)
+{
+    return tiff_walk(file, len, info, chunk_table, table_cap, true);
 }

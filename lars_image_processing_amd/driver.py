@@ -28,7 +28,7 @@ LUT_PNG_LEVEL = 1
 PNG_ENCODERS = ("pillow", "device")
 PNG_DECODERS = ("pillow", "device")
 JPEG_DECODERS = ("pillow", "device")
-TIFF_DECODERS = ("pillow", "device")
+TIFF_DECODERS = ("pillow", "device", "device+deflate")
 TIFF_ENCODERS = ("pillow", "device")
 
 
@@ -49,7 +49,7 @@ def _check_jpeg_decoder(jpeg_decoder):
 
 def _check_tiff_decoder(tiff_decoder):
     if tiff_decoder not in TIFF_DECODERS:
-        raise ValueError(f"tiff_decoder must be 'pillow' or 'device', got {tiff_decoder!r}")
+        raise ValueError(f"tiff_decoder must be 'pillow', 'device' or 'device+deflate', got {tiff_decoder!r}")
 
 
 def _check_tiff_encoder(tiff_encoder):
@@ -69,7 +69,8 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     only the files cross PCIe) instead of with Pillow.  ``png_decoder="device"`` decodes the input on the GPU when it is a
     PNG file ``api.png_info`` calls supported (``tiffio.read_image``; same pixels as Pillow), ``jpeg_decoder="device"`` when
     it is a JPEG file ``api.jpeg_info`` calls supported, ``tiff_decoder="device"`` when it is a TIFF file ``api.tiff_info`` calls
-    supported and the array is the one read today (``tiffio.read_image``).  ``tiff_encoder="device"`` builds the TIFF files on
+    supported and the array is the one read today (``tiffio.read_image``); ``tiff_decoder="device+deflate"`` sends Deflate
+    TIFF files there as well (``api.decode_tiff(..., deflate=True)``).  ``tiff_encoder="device"`` builds the TIFF files on
     the GPU (``api.encode_tiff``: LZW strips, the same samples): ``<name>_wb.tif`` instead of Pillow's uncompressed file, and the
     ``lut_format="tiff"`` pictures instead of ``tiffio.write_tiff``'s uncompressed ones."""
     if lut_format not in ("png", "png8", "tiff"):
@@ -250,7 +251,8 @@ def main(argv=None):
     ap.add_argument("--jpeg-decoder", default="pillow", choices=list(JPEG_DECODERS),
                     help="'device' decodes supported JPEG inputs on the GPU (same pixels; other files stay with Pillow)")
     ap.add_argument("--tiff-decoder", default="pillow", choices=list(TIFF_DECODERS),
-                    help="'device' decodes supported TIFF inputs on the GPU (same samples; other files take today's path)")
+                    help="'device' decodes supported TIFF inputs on the GPU (same samples; other files take today's path); "
+                         "'device+deflate' decodes Deflate TIFF files there too")
     ap.add_argument("--tiff-encoder", default="pillow", choices=list(TIFF_ENCODERS),
                     help="'device' builds <name>_wb.tif and the --lut-format tiff pictures on the GPU (LZW strips, same samples)")
     ap.add_argument("--quiet", action="store_true")

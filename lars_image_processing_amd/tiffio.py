@@ -324,28 +324,30 @@ def read_image(path, full_depth=False, png_decoder="pillow", jpeg_decoder="pillo
     (``api.decode_tiff``) where this module's reader is used today (``full_depth=True`` and three-dimensional uint16 samples)
     and, without ``full_depth``, where the array is Pillow's (8 bit, one BlackIsZero sample or RGB, no extra samples);
     every other file takes the path it takes today.  Decided up front as well: the device's errors are raised.
+    ``tiff_decoder="device+deflate"``: the same, and a Deflate file (compression 8 / 32946), which ``"device"`` leaves to the
+    host, goes to ``api.decode_tiff(data, deflate=True)`` under the same two conditions.
     """
     from PIL import Image
     if png_decoder not in ("pillow", "device"):
         raise ValueError(f"png_decoder must be 'pillow' or 'device', got {png_decoder!r}")
     if jpeg_decoder not in ("pillow", "device"):
         raise ValueError(f"jpeg_decoder must be 'pillow' or 'device', got {jpeg_decoder!r}")
-    if tiff_decoder not in ("pillow", "device"):
-        raise ValueError(f"tiff_decoder must be 'pillow' or 'device', got {tiff_decoder!r}")
+    if tiff_decoder not in ("pillow", "device", "device+deflate"):
+        raise ValueError(f"tiff_decoder must be 'pillow', 'device' or 'device+deflate', got {tiff_decoder!r}")
     p = str(path)
-    if tiff_decoder == "device" and p.lower().endswith((".tif", ".tiff")):
+    if tiff_decoder != "pillow" and p.lower().endswith((".tif", ".tiff")):
         from . import api
         with open(p, "rb") as f:
             data = f.read()
         # a file without the byte-order mark (a PNG under a .tif name, say) or with a broken directory is not the decoder's
         if data[:2] in (b"II", b"MM"):
             try:
-                i = api._tiff_info(np.frombuffer(data, dtype=np.uint8))
+                i = api._tiff_info(np.frombuffer(data, dtype=np.uint8), tiff_decoder == "device+deflate")
             except ValueError:
                 i = None
             if i is not None and i.supported:
                 if (full_depth and i.bits == 16 and i.samples > 1) or (not full_depth and api._tiff_is_pillow_u8(i)):
-                    return api.decode_tiff(data)
+                    return api.decode_tiff(data, deflate=True) if tiff_decoder == "device+deflate" else api.decode_tiff(data)
     if jpeg_decoder == "device" and p.lower().endswith((".jpg", ".jpeg")):
         from . import api
         with open(p, "rb") as f:

@@ -5,7 +5,10 @@ thread pool) on every file, and an uncompressed copy of each file (the assembly 
 
 File sets: 20 gallery pictures (2048 x 1536 RGB, 8 bit, LZW with Pillow's defaults), 4096 x 4096 RGB 8-bit LZW with
 predictor from Pillow, and three-sample uint16 files with LZW and predictor from ``write_tiff`` plus the test encoder
-(``--side16``, 768 by default: the encoder is Python).  Per file kind, after a warm-up pass: the median over reps of the
+(``--side16``, 768 by default: the encoder is Python).  The Deflate legs (``decode_tiff(..., deflate=True)``, in the same
+run and by the same rules): the gallery pictures as Pillow writes them with ``tiff_adobe_deflate``, the 4096 x 4096 file with
+predictor, the uint16 file from ``write_tiff(deflate=True, predictor=True)``, and one 1024 x 1024 RGB file written as a
+single strip, which one lane decodes.  Per file kind, after a warm-up pass: the median over reps of the
 per-file time, host bytes in and host array out, each call ending in a device synchronise.  Every result is checked
 against ``read_tiff`` first.  Each kind runs in a child process of its own under a time limit.
 
@@ -29,7 +32,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-KINDS = ("gallery_rgb_lzw", "rgb_4096_lzw_predictor", "u16x3_lzw_predictor")
+KINDS = ("gallery_rgb_lzw", "rgb_4096_lzw_predictor", "u16x3_lzw_predictor",
+         "gallery_rgb_deflate", "rgb_4096_deflate_predictor", "u16x3_deflate_predictor", "rgb_1024_deflate_one_strip")
 LIMIT_S = 420
 
 
@@ -43,24 +47,29 @@ def files_of(kind, side16):
     """[(file, uncompressed copy, Pillow reads it)]"""
     from thumbbench import gallery
     import tiff_cases as tc
-    if kind == "gallery_rgb_lzw":
+    scheme = "tiff_adobe_deflate" if "deflate" in kind else "tiff_lzw"
+    if kind in ("gallery_rgb_lzw", "gallery_rgb_deflate"):
         pics = (gallery(7) + gallery(8))[:20]
-        return [(pil_tiff(a, compression="tiff_lzw"), pil_tiff(a), True) for a in pics]
-    if kind == "rgb_4096_lzw_predictor":
+        return [(pil_tiff(a, compression=scheme), pil_tiff(a), True) for a in pics]
+    if kind == "rgb_1024_deflate_one_strip":
+        a = np.ascontiguousarray(gallery(7)[0][:1024, :1024])
+        return [(tc.written(a, deflate=True, rows_per_strip=1024), tc.written(a, rows_per_strip=1024), True)]
+    if kind in ("rgb_4096_lzw_predictor", "rgb_4096_deflate_predictor"):
         rng = np.random.default_rng(5)
         y, x = np.mgrid[0:4096, 0:4096].astype(np.float32)
         out = []
         for k in range(3):
             base = np.stack([np.sin(x / (61 + 7 * k) + c) * np.cos(y / (47 + 5 * k) - c) for c in (0.0, 1.0, 2.0)], axis=-1)
             a = (127.5 + 100 * base + rng.normal(0, 6, base.shape)).clip(0, 255).astype(np.uint8)
-            out.append((pil_tiff(a, compression="tiff_lzw", tiffinfo={317: 2}), pil_tiff(a), True))
+            out.append((pil_tiff(a, compression=scheme, tiffinfo={317: 2}), pil_tiff(a), True))
         return out
     rng = np.random.default_rng(6)
     y, x = np.mgrid[0:side16, 0:side16].astype(np.float32)
     base = np.stack([np.sin(x / 61 + c) * np.cos(y / 47 - c) for c in (0.0, 1.0, 2.0)], axis=-1)
     a = (32768 + 25000 * base + rng.normal(0, 300, base.shape)).clip(0, 65535).astype(np.uint16)
-    return [(tc.lzw_tiff(a, rows_per_strip=max(1, 65536 // (side16 * 6)), predictor=True),
-             tc.written(a, rows_per_strip=max(1, 65536 // (side16 * 6)), predictor=True), False)]
+    rps = max(1, 65536 // (side16 * 6))
+    packed = tc.written(a, rows_per_strip=rps, predictor=True, deflate=True) if "deflate" in kind else tc.lzw_tiff(a, rows_per_strip=rps, predictor=True)
+    return [(packed, tc.written(a, rows_per_strip=rps, predictor=True), False)]
 
 
 def host_ms(fn, items, reps):
@@ -94,23 +103,26 @@ def run_kind(kind, args):
             ts.append((time.perf_counter() - t0) / len(items))
         return float(np.median(ts)) * 1e3
 
+    deflate = "deflate" in kind
+    decode = (lambda f: lars.decode_tiff(f, deflate=True)) if deflate else lars.decode_tiff
+    thumbnail = (lambda f: lars.thumbnail_tiff(f, deflate=True)) if deflate else lars.thumbnail_tiff
     sets = files_of(kind, args.side16)
     files, raws, pillow = [f for f, _r, _p in sets], [r for _f, r, _p in sets], sets[0][2]
     for f, r in zip(files[:2], raws[:2]):                      # a fast wrong answer is no answer
         want = tiffio.read_tiff(f)
-        for got in (lars.decode_tiff(f), lars.decode_tiff(r)):
+        for got in (decode(f), lars.decode_tiff(r)):
             assert got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes()
-    info = lars.tiff_info(files[0])
+    info = lars.tiff_info(files[0], deflate=deflate)
     out_bytes = int(np.prod(info["shape"])) * info["dtype"].itemsize
     dev = _ffi.DeviceBuffer(max(out_bytes, max(len(f) for f in files)))
     first = np.frombuffer(files[0], dtype=np.uint8)
     r = {"kind": kind, "device": _ffi.device_name(), "files": len(files), "reps": args.reps, "shape": list(info["shape"]),
          "dtype": str(info["dtype"]), "chunks": info["chunks"], "mean_file_bytes": int(np.mean([len(f) for f in files])),
-         "decode_tiff_ms": gpu_ms(lars.decode_tiff, files), "decode_tiff_uncompressed_ms": gpu_ms(lars.decode_tiff, raws),
+         "decode_tiff_ms": gpu_ms(decode, files), "decode_tiff_uncompressed_ms": gpu_ms(lars.decode_tiff, raws),
          "upload_ms": gpu_ms(lambda a: dev.upload(a), [first]), "download_ms": gpu_ms(lambda n: dev.download(np.uint8, (n,)), [out_bytes])}
     r["kernels_and_host_ms"] = r["decode_tiff_ms"] - r["upload_ms"] - r["download_ms"]
     if pillow:
-        r["thumbnail_tiff_ms"] = gpu_ms(lars.thumbnail_tiff, files)
+        r["thumbnail_tiff_ms"] = gpu_ms(thumbnail, files)
     if not args.gpu_only:
         r["read_tiff_ms"] = host_ms(tiffio.read_tiff, files, args.reps)
         r["speedup_over_read_tiff"] = r["read_tiff_ms"] / r["decode_tiff_ms"]
