@@ -646,6 +646,11 @@ int lars_h_tiff_lzw_decode_chunks(const uint8_t *file, int64_t file_len, const u
  * Covered: classic TIFF, first directory, either byte order, 8 or 16 bit unsigned samples (equal across samples), no
  * compression or LZW, predictor 1 or 2, chunky or planar, strips or tiles.  The pixels come out as tiffio.read_tiff gives
  * them: [h][w][samples] ([h][w] for one sample), uint8 or native-endian uint16.
+ * Float32 samples as well (BitsPerSample 32 with SampleFormat 3 for every sample, the type of the index planes): the same
+ * layouts and compressions with predictor 1, 2 (differencing of the 32-bit patterns modulo 2^32) or 3 (the floating-point
+ * predictor, libtiff's fpAcc: per row of a strip / tile, padding columns included, the running sum with the stride of a
+ * pixel's samples over four byte planes, most significant first in either byte order).  Native floats come out, bit for
+ * bit, whatever the file's byte order.  info[LARS_TIFF_INFO_BITS] == 32 means float32: no other 32-bit kind is decoded.
  * lars_tiff_info: pure host code.  Walks the first directory of file[0..len) by read_tiff's rules, checks every offset and
  * count against len, and fills info[LARS_TIFF_INFO_N] (positions below); chunk_table (may be NULL with table_cap 0)
  * receives { offset, byte count } of the first table_cap strips / tiles.  A valid file the device does not decode has
@@ -681,14 +686,14 @@ enum {                           /* positions in lars_tiff_info's info[] */
 enum {
     LARS_TIFF_REASON_NONE = 0,
     LARS_TIFF_REASON_BIGTIFF = 1,        /* 64-bit offsets (magic 43) */
-    LARS_TIFF_REASON_BITS = 2,           /* samples that are not all 8 or all 16 bits wide */
-    LARS_TIFF_REASON_SAMPLE_FORMAT = 3,  /* signed or floating-point samples */
+    LARS_TIFF_REASON_BITS = 2,           /* samples that are not all 8, all 16 or all 32 bits wide */
+    LARS_TIFF_REASON_SAMPLE_FORMAT = 3,  /* signed samples, floats of 8 or 16 bits, integers of 32 */
     LARS_TIFF_REASON_DEFLATE = 4,        /* compression 8 / 32946 (tiffio.read_tiff reads them) */
     LARS_TIFF_REASON_PACKBITS = 5,
     LARS_TIFF_REASON_JPEG = 6,           /* compression 6 / 7 */
     LARS_TIFF_REASON_CCITT = 7,          /* compression 2, 3, 4 */
     LARS_TIFF_REASON_COMPRESSION = 8,    /* any other scheme */
-    LARS_TIFF_REASON_PREDICTOR = 9,      /* other than 1 and 2 (floating-point predictor) */
+    LARS_TIFF_REASON_PREDICTOR = 9,      /* other than 1 and 2, or 3 without float32 samples */
     LARS_TIFF_REASON_OLD_LZW = 10,       /* a strip in the old bit order (LSB first), which lars_h_tiff_lzw_decode refuses too */
     LARS_TIFF_REASON_SIZE = 11           /* 2^31 or more decoded bytes (tile padding included) */
 };
@@ -736,6 +741,31 @@ int lars_d_encode_tiff(const void *img, int64_t h, int64_t w, int channels, int 
                        uint8_t *out, size_t out_cap, int64_t *out_len_dev, int32_t *status_dev, void *scratch, void *stream);
 int lars_h_encode_tiff(const void *img, int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip, int predictor,
                        uint8_t *out, size_t out_cap, int64_t *out_len);
+/* The same four for float32 samples -- the index planes themselves (NDVI, GNDVI, NDWI), losslessly, as the single-band float
+ * TIFF that GDAL, rasterio and QGIS exchange them in.  img is [h][w][channels] of native float32, channels 1..5.  The file is
+ * the one above with BitsPerSample 32 and SampleFormat 3 per sample and the directory of tiffio.write_float_tiff; predictor
+ * 0 writes no Predictor tag, any other value Predictor 3 (libtiff's fpDiff: every row as four planes of w * channels bytes,
+ * plane 0 the most significant byte of every sample, each byte minus the byte `channels` positions earlier, across the plane
+ * borders).  Strips, the knob, the streams (libtiff's bytes), the bound's derivation (a row has w * channels * 4 bytes),
+ * status_dev and LARS_TIFE_* are those of the integer entry points, which go on refusing itemsize 4. */
+size_t lars_tiff_f32_bound(int64_t h, int64_t w, int channels, int64_t rows_per_strip);
+size_t lars_tiff_f32_encode_scratch_bytes(int64_t h, int64_t w, int channels, int64_t rows_per_strip);
+int lars_d_encode_tiff_f32(const float *img, int64_t h, int64_t w, int channels, int64_t rows_per_strip, int predictor, uint8_t *out,
+                           size_t out_cap, int64_t *out_len_dev, int32_t *status_dev, void *scratch, void *stream);
+int lars_h_encode_tiff_f32(const float *img, int64_t h, int64_t w, int channels, int64_t rows_per_strip, int predictor, uint8_t *out,
+                           size_t out_cap, int64_t *out_len);
+/* lars_h_process_image with every requested index plane also encoded as a float32 TIFF on the device
+ * (lars_d_encode_tiff_f32, one sample, predictor and rows_per_strip as there): the plane an index file holds never crosses
+ * PCIe as 4 bytes per pixel, only its LZW file does.  out_tiff[k] (host, tiff_cap bytes, at least lars_tiff_f32_bound(h, w, 1,
+ * rows_per_strip)) is needed for every index in index_mask; tiff_len[k] receives the file's length.  out_index, out_rgba and
+ * cmap_lut as in lars_h_process_image; each may be NULL. */
+int lars_h_process_image_tiff_f32(const void *img, int64_t h, int64_t w, int channels, int dtype,
+                                  int apply_wb, uint32_t index_mask, int want_hist,
+                                  uint8_t *out_wb, float *const out_index[3],
+                                  lars_stats *stats /* [3] */, float *medians /* [3][2] */,
+                                  uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3],
+                                  int predictor, int64_t rows_per_strip,
+                                  uint8_t *const out_tiff[3], size_t tiff_cap, int64_t tiff_len[3]);
 
 /* ------------------------------------------------------------------ multi-GPU */
 /* One process per GPU.  RCCL (librccl.so) is loaded on first use.  unique_id is

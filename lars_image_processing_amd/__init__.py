@@ -25,6 +25,7 @@ from .api import (  # noqa: F401
     decode_tiff,
     encode_png,
     encode_tiff,
+    encode_tiff_f32,
     download_processed_images,
     fix_white_balance,
     fix_white_balance_rgnir,
@@ -41,11 +42,12 @@ from .api import (  # noqa: F401
     thumbnail_png,
     thumbnail_tiff,
     tiff_bound,
+    tiff_f32_bound,
     tiff_info,
     time_series_points,
     timeseries_row,
 )
 from .batch import TileBatch, local_fold, merge_records, shard_range, summarize, timeseries_rows  # noqa: F401
-from .tiffio import read_image, read_tiff, write_tiff  # noqa: F401
+from .tiffio import read_image, read_tiff, write_float_tiff, write_tiff  # noqa: F401
 
 __version__ = "0.1.0"

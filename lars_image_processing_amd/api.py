@@ -60,7 +60,7 @@ __all__ = [
     "fix_white_balance", "correct_white_balance", "fix_white_balance_rgnir",
     "calculate_index", "calculate_ndvi", "analyze_index", "analyze_index_statistics",
     "analyze_ndvi_statistics", "index_histogram", "classification_mask", "colorize_index", "process_image",
-    "timeseries_row", "colormap_lut", "preprocess_large_image", "thumbnail", "thumbnail_plan", "encode_png",
+    "timeseries_row", "colormap_lut", "preprocess_large_image", "thumbnail", "thumbnail_plan", "encode_png", "encode_tiff_f32", "tiff_f32_bound",
     "png_info", "decode_png", "thumbnail_png", "jpeg_info", "decode_jpeg", "encode_jpeg", "thumbnail_jpeg", "jpeg_draft_scale", "align_images", "change_detection",
     "colorize_difference", "calculate_index_statistics_by_timeframe", "time_series_points",
     "calculate_ndvi_array", "generate_ndvi_report", "download_processed_images",
@@ -625,10 +625,13 @@ def encode_jpeg(array, quality=75, subsampling="4:2:0"):
 # ---------------------------------------------------------------------------
 # TIFF files built on the device
 # ---------------------------------------------------------------------------
-def _tiff_picture(array, rows_per_strip, who):
-    """What ``encode_tiff`` opens with, before anything is launched: (C-contiguous ``[H, W, C]`` array, rows per strip or 0)."""
+def _tiff_picture(array, rows_per_strip, who, f32=False):
+    """What ``encode_tiff`` and ``encode_tiff_f32`` open with, before anything is launched: (C-contiguous ``[H, W, C]`` array, rows
+    per strip or 0)."""
     arr = np.asarray(array)
-    if arr.dtype not in (np.uint8, np.uint16):
+    if f32 and arr.dtype != np.float32:
+        raise TypeError(f"{who}: float32 pictures only, got {arr.dtype} (nothing is cast)")
+    if not f32 and arr.dtype not in (np.uint8, np.uint16):
         raise TypeError(f"{who}: uint8 or uint16 pictures only, got {arr.dtype}")
     if arr.ndim == 2:
         arr = arr[:, :, None]
@@ -694,6 +697,44 @@ def encode_tiff(array, rows_per_strip=None, predictor=False):
     try:
         _ffi.call("lars_h_encode_tiff", _ffi.ptr(arr), h, w, c, arr.dtype.itemsize, rps, int(bool(predictor)), _ffi.ptr(out), out.nbytes,
                   C.byref(n))
+    except _ffi.LarsError as e:
+        if e.code == -6 or (e.code == -1 and bound > out.nbytes):
+            raise TiffError("image too large for a classic TIFF (4 GiB)") from None
+        raise
+    return out[:n.value].tobytes()
+
+
+def tiff_f32_bound(h, w, channels, rows_per_strip=None):
+    """The largest file ``encode_tiff_f32`` can return for an ``h x w`` picture of ``channels`` float32 samples
+    (``lars_tiff_f32_bound``; host code, no device needed); 0 for a shape that cannot be encoded.  ``tiff_bound``'s derivation
+    with rows of ``w * channels * 4`` bytes: per strip of n bytes ``ceil(12 * (n + n // 3836 + 2) / 8)`` bytes, plus one where
+    that is odd; 8 bytes of header, 2 + 12 * 13 + 4 of directory, ``4 * channels`` of BitsPerSample and SampleFormat, 8 per
+    strip.  ``rows_per_strip=None``: the rows the knob ``tiff_strip_bytes`` gives."""
+    return int(_ffi.load().lars_tiff_f32_bound(int(h), int(w), int(channels), int(rows_per_strip or 0)))
+
+
+def encode_tiff_f32(array, rows_per_strip=None, predictor=False):
+    """LZW TIFF file (``bytes``) of float32 samples, encoded on the GPU: ``[H, W]`` or ``[H, W, C]`` with C = 1..5 -- an index plane
+    (``calculate_index``) kept bit for bit, in the file GDAL, rasterio and QGIS exchange such rasters in.
+
+    ``encode_tiff``'s file (classic, little-endian, strips, chunky, Compression 5, the same strip rule and knob) with
+    BitsPerSample 32 and SampleFormat 3; the directory is ``tiffio.write_float_tiff``'s.  ``predictor=True`` writes Predictor 3,
+    the floating-point predictor (libtiff's fpDiff: every row as four byte planes, most significant first, differenced across
+    the plane borders), computed from the picture as the encoder reads it.  Every strip is libtiff's stream for those bytes.
+
+    ``TypeError`` for any dtype but float32 (float64 is not cast), ``TypeError`` / ``ValueError`` for shapes, empty arrays or
+    C > 5, all before anything is launched; ``tiffio.TiffError`` for a file that would reach 4 GiB.  No CPU fallback.
+    """
+    from .tiffio import TiffError
+    arr, rps = _tiff_picture(array, rows_per_strip, "encode_tiff_f32", f32=True)
+    h, w, c = arr.shape
+    bound = tiff_f32_bound(h, w, c, rps)
+    if bound == 0:
+        raise ValueError(f"encode_tiff_f32: strips of {rps or 'the default number of'} rows of {w * c * 4} bytes are too long (2^30 bytes at most)")
+    out = np.empty(min(bound, 1 << 32), dtype=np.uint8)
+    n = C.c_int64(0)
+    try:
+        _ffi.call("lars_h_encode_tiff_f32", _ffi.ptr(arr), h, w, c, rps, int(bool(predictor)), _ffi.ptr(out), out.nbytes, C.byref(n))
     except _ffi.LarsError as e:
         if e.code == -6 or (e.code == -1 and bound > out.nbytes):
             raise TiffError("image too large for a classic TIFF (4 GiB)") from None
@@ -927,12 +968,15 @@ def thumbnail_jpeg(data, size=(400, 400), reducing_gap=2.0, scaled=False):
 # TIFF files decoded on the device
 # ---------------------------------------------------------------------------
 # why a file is not decoded, by the header's LARS_TIFF_REASON_* names, in the order of their values (tests/test_tiff_decode_cpu.py)
-_TIFF_REASONS = {"NONE": None, "BIGTIFF": "BigTIFF (64-bit offsets)", "BITS": "samples that are not all 8 or all 16 bits wide",
-                 "SAMPLE_FORMAT": "signed or floating-point samples", "DEFLATE": "Deflate compression (read_tiff reads it on the host)",
+_TIFF_REASONS = {"NONE": None, "BIGTIFF": "BigTIFF (64-bit offsets)", "BITS": "samples that are not all 8, all 16 or all 32 bits wide",
+                 "SAMPLE_FORMAT": "signed samples, floats of 8 or 16 bits or integers of 32", "DEFLATE": "Deflate compression (read_tiff reads it on the host)",
                  "PACKBITS": "PackBits compression", "JPEG": "JPEG compression", "CCITT": "CCITT compression",
-                 "COMPRESSION": "an unknown compression scheme", "PREDICTOR": "a predictor other than 1 and 2",
+                 "COMPRESSION": "an unknown compression scheme", "PREDICTOR": "a predictor other than 1 and 2 (3 goes with float32 samples only)",
                  "OLD_LZW": "old-style (LSB-first) LZW", "SIZE": "2^31 or more decoded bytes"}
 _TIFF_REASON_TEXT = dict(enumerate(_TIFF_REASONS.values()))
+
+
+_TIFF_DTYPES = {8: np.uint8, 16: np.uint16, 32: np.float32}      # bits == 32 means float32: no other 32-bit kind is supported
 
 
 def _tiff_info(arr, deflate=False):
@@ -956,15 +1000,15 @@ def tiff_info(data, deflate=False):
     ``photometric`` (-1: no such tag), ``extra_samples``, ``tiled``, ``chunk_w``, ``chunk_h``, ``chunks`` (strips / tiles),
     ``dtype`` and ``shape`` of the array ``decode_tiff`` gives (``None`` where the directory does not say), ``supported`` and
     ``reason`` (``None``, or why the device does not decode it: Deflate, PackBits, JPEG, CCITT, old-style LZW, other bit
-    depths, signed or float samples, BigTIFF, 2^31 bytes or more).  Raises ``ValueError`` for structural damage: no byte-order
+    depths, signed samples, BigTIFF, 2^31 bytes or more); ``bits == 32`` is float32.  Raises ``ValueError`` for structural damage: no byte-order
     mark, a directory, a tag's values or a strip / tile outside the file, a missing required tag, a wrong number of strips.
     """
     i = _tiff_info(_file_bytes(data, "tiff_info", "TIFF"), bool(deflate))
     out = i._asdict()
     for k in ("big_endian", "tiled", "supported"):
         out[k] = bool(out[k])
-    known = i.bits in (8, 16) and i.width > 0 and i.height > 0 and i.samples > 0
-    out["dtype"] = np.dtype(np.uint8 if i.bits == 8 else np.uint16) if known else None
+    known = i.bits in _TIFF_DTYPES and i.width > 0 and i.height > 0 and i.samples > 0
+    out["dtype"] = np.dtype(_TIFF_DTYPES[i.bits]) if known else None
     out["shape"] = _tiff_shape(i) if known else None
     out["reason"] = _TIFF_REASON_TEXT.get(i.reason, str(i.reason))
     return out
@@ -978,7 +1022,7 @@ def _tiff_check(arr, who, deflate=False):
         raise TiffError(str(e)) from None
     if not i.supported:
         raise NotImplementedError(f"{who}: TIFF files with {_TIFF_REASON_TEXT.get(i.reason, i.reason)} are not decoded on the device "
-                                  "(classic TIFF, 8 or 16 bit unsigned samples, uncompressed or LZW; Deflate with deflate=True)")
+                                  "(classic TIFF, 8 or 16 bit unsigned or float32 samples, uncompressed or LZW; Deflate with deflate=True)")
     return i
 
 
@@ -998,7 +1042,8 @@ def decode_tiff(data, deflate=False):
 
     ``data``: the whole file as ``bytes``, ``bytearray``, ``memoryview`` or a 1-D uint8 array.  Classic TIFF, first
     directory, either byte order, 8 or 16 bit unsigned samples, uncompressed or LZW, predictor 1 or 2, chunky or planar,
-    strips or tiles: ``[H, W, C]`` (``[H, W]`` for one sample) uint8 or native-endian uint16.  Other variants
+    strips or tiles: ``[H, W, C]`` (``[H, W]`` for one sample) uint8 or native-endian uint16.  Float32 files (BitsPerSample 32,
+    SampleFormat 3) in the same layouts, with predictor 1, 2 or 3 (the floating-point predictor): native float32.  Other variants
     (``tiff_info(data)["reason"]``) raise ``NotImplementedError`` before anything is launched; damaged files raise
     ``tiffio.TiffError`` (a ``ValueError``) where ``read_tiff`` does.  No CPU fallback.
 
@@ -1012,7 +1057,7 @@ def decode_tiff(data, deflate=False):
     arr = _file_bytes(data, "decode_tiff", "TIFF")
     deflate = bool(deflate)
     i = _tiff_check(arr, "decode_tiff", deflate)
-    out = np.empty(_tiff_shape(i), dtype=np.uint8 if i.bits == 8 else np.uint16)
+    out = np.empty(_tiff_shape(i), dtype=_TIFF_DTYPES[i.bits])
     _tiff_call("lars_h_decode_tiff_deflate" if deflate else "lars_h_decode_tiff", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
     return out
 
@@ -1046,7 +1091,7 @@ def thumbnail_tiff(data, size=(400, 400), reducing_gap=2.0, deflate=False):
 
 
 def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_arrays=True, want_hist=False,
-                  want_rgba=False, want_entries=False, want_png=False):
+                  want_rgba=False, want_entries=False, want_png=False, want_tiff=False):
     """White balance -> indices -> statistics of one image in ONE upload.
 
     What the Streamlit comparison path does with three separate calls per index
@@ -1059,7 +1104,15 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
     ``want_png=True`` adds ``png``: the PNG file (``bytes``) of the RGBA colormap picture, encoded on the device
     (``encode_png``); ``want_png="palette"`` a mode-P file of the colormap entries with the colormap as its palette.  Either
     way only the file crosses PCIe.
+    ``want_tiff=True`` adds ``tiff``: the float32 LZW TIFF file (``bytes``) of the index plane itself, encoded on the device
+    (``encode_tiff_f32``, one strip rule for all); ``want_tiff="predictor"`` writes it with Predictor 3.  The plane then need
+    not cross PCIe (``want_arrays=False``).  Not together with ``want_png`` (one kind of file per call).
     """
+    tiff_mode = 0 if want_tiff is False else 1 if want_tiff is True else 2 if isinstance(want_tiff, str) and want_tiff == "predictor" else None
+    if tiff_mode is None:
+        raise ValueError(f"process_image: want_tiff must be False, True or 'predictor', got {want_tiff!r}")
+    if tiff_mode and want_png is not False:
+        raise ValueError("process_image: want_tiff or want_png, not both (one kind of file per call)")
     png_mode = 0 if want_png is False else 1 if want_png is True else 2 if isinstance(want_png, str) and want_png == "palette" else None
     if png_mode is None:
         raise ValueError(f"process_image: want_png must be False, True or 'palette', got {want_png!r}")
@@ -1089,8 +1142,20 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
             rgbas[k] = _empty((h, w), dtype=np.uint8)          # no table: the entry plane comes back in the RGBA slot
     stats = (Stats * 3)()
     med = np.zeros((3, 2), dtype=np.float32)
-    pngs = [None] * 3
-    if png_mode:
+    pngs, tiffs = [None] * 3, [None] * 3
+    if tiff_mode:
+        cap = tiff_f32_bound(h, w, 1)
+        if cap == 0:
+            raise ValueError(f"process_image: a {h} x {w} plane is not encoded as a TIFF file (1 to 2^24 on each side)")
+        for t in indices:
+            tiffs[INDEX_IDS[t]] = np.empty(cap, dtype=np.uint8)
+        lens = np.zeros(3, dtype=np.int64)
+        p_out, p_rgba, p_lut, p_tiff = _ffi.ptr3(outs), _ffi.ptr3(rgbas), _ffi.ptr3(luts), _ffi.ptr3(tiffs)
+        _ffi.call("lars_h_process_image_tiff_f32", _ffi.ptr(arr), h, w, c, code, int(bool(white_balance)), mask, int(want_hist),
+                  _ffi.ptr(out_wb), C.byref(p_out), C.byref(stats), _ffi.ptr(med), C.byref(p_rgba), C.byref(p_lut), int(tiff_mode == 2), 0,
+                  C.byref(p_tiff), cap, _ffi.ptr(lens))
+        tiffs = [None if p is None else p[:lens[k]].tobytes() for k, p in enumerate(tiffs)]
+    elif png_mode:
         cap = png_bound(h, w, 4 if png_mode == 1 else 1)
         for t in indices:
             k = INDEX_IDS[t]
@@ -1117,6 +1182,7 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
             "rgba": rgbas[k] if want_rgba else None,
             "entry": rgbas[k] if want_entries else None,
             "png": pngs[k],
+            "tiff": tiffs[k],
             "hist": np.array(list(st.hist), dtype=np.int64) if want_hist else None,
             "stats": {
                 f"Mean {t}": st.sum / st.count,

@@ -68,7 +68,7 @@ struct HostFile {
     const uint8_t *file;
     int64_t len, h, w;
     int channels;
-    int sample_bytes = 1;          // 2: a 16-bit picture (tiff_decode.hip), which travels as bytes
+    int sample_bytes = 1;          // 2, 4: a 16-bit or float32 picture (tiff_decode.hip), which travels as bytes
     size_t extra_bytes, scratch_bytes;
     uint8_t *d_file, *d_img;
     void *d_extra;

@@ -29,7 +29,15 @@ struct ImageJob {
     uint8_t *out_png[3];
     size_t png_cap;
     int64_t *png_len;             // [3]
+    int tiff;                     // 0 none, 1 float32 TIFF files of the index planes (LZW on the device)
+    int tiff_predictor;
+    int64_t tiff_rps;
+    uint8_t *out_tiff[3];
+    size_t tiff_cap;
+    int64_t *tiff_len;            // [3]
 };
+
+struct TiffAnswer { int64_t len; int32_t status[2]; };
 
 struct Layout {
     uint8_t *img; uint32_t *hist; uint8_t *table; double *pcts; uint8_t *wb;
@@ -39,6 +47,9 @@ struct Layout {
     uint8_t *png[3], *pal[3];      // PNG files of the index pictures, palettes of the P pictures
     int64_t *png_len; char *png_scratch;
     size_t png_bound;
+    uint8_t *tif[3];               // float32 TIFF files of the index planes
+    TiffAnswer *tif_ans; char *tif_scratch;
+    size_t tif_bound;
 };
 
 // Medians of uint8 RGNir images come from the two-level select on recomputed values (select_q.hip): two passes over the
@@ -52,7 +63,7 @@ bool select_route(const ImageJob &j)
 // the planes never exist on the device either
 bool recompute_route(const ImageJob &j)
 {
-    if (!select_route(j) || !j.want_stats || j.png_mode) return false;
+    if (!select_route(j) || !j.want_stats || j.png_mode || j.tiff) return false;
     if (j.mask != 1u && j.mask != 2u && j.mask != 4u && j.mask != 7u) return false;
     for (int k = 0; k < 3; ++k)
         if (j.out_index[k] || j.out_rgba[k]) return false;
@@ -79,13 +90,17 @@ Layout plan(const ImageJob &j, Carver &c)
         // the entry plane is derived from the float32 plane on the device
         const bool entries = on && ((j.out_rgba[k] && !j.cmap[k]) || j.png_mode == 2);
         const bool rgba = on && j.cmap[k] && (j.out_rgba[k] || j.png_mode == 1);
-        L.idx[k] = (on && (j.out_index[k] || entries || (j.want_median && !select))) ? c.take<float>(npix) : nullptr;
+        L.idx[k] = (on && (j.out_index[k] || entries || j.tiff || (j.want_median && !select))) ? c.take<float>(npix) : nullptr;
         L.rgba[k] = rgba ? c.take<uint8_t>(npix * 4) : nullptr;
         L.cmap[k] = rgba ? c.take<uint8_t>(1024) : nullptr;
         L.entry[k] = entries ? c.take<uint8_t>(npix + 4) : nullptr;
         L.pal[k] = (on && j.png_mode == 2) ? c.take<uint8_t>(1024) : nullptr;
         L.png[k] = (on && j.png_mode) ? c.take<uint8_t>(L.png_bound) : nullptr;
     }
+    L.tif_bound = j.tiff ? lars_tiff_f32_bound(j.h, j.w, 1, j.tiff_rps) : 0;
+    for (int k = 0; k < 3; ++k) L.tif[k] = (j.tiff && ((j.mask >> k) & 1u)) ? c.take<uint8_t>(L.tif_bound) : nullptr;
+    L.tif_ans = j.tiff ? c.take<TiffAnswer>(3) : nullptr;
+    L.tif_scratch = j.tiff ? c.take<char>(lars_tiff_f32_encode_scratch_bytes(j.h, j.w, 1, j.tiff_rps)) : nullptr;
     L.png_len = j.png_mode ? c.take<int64_t>(3) : nullptr;
     L.png_scratch = j.png_mode ? c.take<char>(lars_png_scratch_bytes(j.h, j.w, png_channels)) : nullptr;
     L.stats = c.take<lars_stats>(3);
@@ -168,6 +183,14 @@ int run_image(const ImageJob &j)
                                           L.pal[k] ? 256 : 0, L.png[k], L.png_bound, L.png_len + k, L.png_scratch, s));
         }
     }
+    TiffAnswer htif[3] = {{0, {0, 0}}, {0, {0, 0}}, {0, {0, 0}}};
+    if (L.tif_ans) {                                        // the plane stays on the device; only its TIFF file crosses PCIe
+        for (int k = 0; k < 3; ++k)
+            if (L.tif[k])
+                LARS_TRY(lars_d_encode_tiff_f32(L.idx[k], j.h, j.w, 1, j.tiff_rps, j.tiff_predictor, L.tif[k], L.tif_bound, &L.tif_ans[k].len,
+                                                L.tif_ans[k].status, L.tif_scratch, s));
+        LARS_HIP_TRY(hipMemcpyAsync(htif, L.tif_ans, sizeof htif, hipMemcpyDeviceToHost, s));
+    }
     int64_t hlen[3] = {0, 0, 0};
     if (L.png_len) LARS_HIP_TRY(hipMemcpyAsync(hlen, L.png_len, sizeof hlen, hipMemcpyDeviceToHost, s));
     lars_stats hstats[3];
@@ -202,6 +225,17 @@ int run_image(const ImageJob &j)
         }
         LARS_HIP_TRY(hipStreamSynchronize(s));
         for (int k = 0; k < 3; ++k) j.png_len[k] = L.png[k] ? hlen[k] : 0;
+    }
+    if (j.tiff) {
+        for (int k = 0; k < 3; ++k) {
+            if (!L.tif[k]) continue;
+            if (htif[k].status[0] != LARS_TIFE_OK || htif[k].len <= 0 || (size_t)htif[k].len > j.tiff_cap || (size_t)htif[k].len > L.tif_bound)
+                return fail(LARS_ERR_HIP, "lars_h_process_image_tiff_f32: file %d has %lld bytes (capacity %zu, encoder status %d)", k,
+                            (long long)htif[k].len, j.tiff_cap, htif[k].status[0]);
+            LARS_HIP_TRY(hipMemcpyAsync(j.out_tiff[k], L.tif[k], (size_t)htif[k].len, hipMemcpyDeviceToHost, s));
+        }
+        LARS_HIP_TRY(hipStreamSynchronize(s));
+        for (int k = 0; k < 3; ++k) j.tiff_len[k] = L.tif[k] ? htif[k].len : 0;
     }
     return LARS_OK;
 }
@@ -316,6 +350,37 @@ int lars_h_process_image_png(const void *img, int64_t h, int64_t w, int channels
     j.stats = stats; j.want_stats = stats != nullptr; j.want_hist = want_hist;
     j.medians = medians; j.want_median = medians != nullptr;
     j.png_mode = png_mode; j.png_cap = png_cap; j.png_len = png_len;
+    return run_image(j);
+}
+
+int lars_h_process_image_tiff_f32(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                                  int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                                  uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], int predictor, int64_t rows_per_strip,
+                                  uint8_t *const out_tiff[3], size_t tiff_cap, int64_t tiff_len[3])
+{
+    static const char *who = "lars_h_process_image_tiff_f32";
+    if (!index_mask || (index_mask & ~LARS_MASK_ALL) || !out_tiff || !tiff_len)
+        return fail(LARS_ERR_INVALID, "%s: indices and TIFF outputs are required", who);
+    const size_t bound = lars_tiff_f32_bound(h, w, 1, rows_per_strip);
+    if (!bound)
+        return fail(LARS_ERR_INVALID, "%s: %lld x %lld image in strips of %lld rows (1 to 2^24 on each side, strips of at most 2^30 bytes)", who,
+                    (long long)h, (long long)w, (long long)rows_per_strip);
+    for (int k = 0; k < 3; ++k)
+        if (((index_mask >> k) & 1u) && !out_tiff[k]) return fail(LARS_ERR_INVALID, "%s: index %d needs out_tiff", who, k);
+    if (tiff_cap < bound) return fail(LARS_ERR_INVALID, "%s: tiff_cap %zu < lars_tiff_f32_bound %zu", who, tiff_cap, bound);
+    ImageJob j;
+    memset(&j, 0, sizeof j);
+    j.img = img; j.h = h; j.w = w; j.channels = channels; j.dtype = dtype;
+    j.apply_wb = apply_wb; j.mask = index_mask; j.out_wb = out_wb;
+    for (int k = 0; k < 3; ++k) {
+        j.out_index[k] = out_index ? out_index[k] : nullptr;
+        j.out_rgba[k] = out_rgba ? out_rgba[k] : nullptr;
+        j.cmap[k] = cmap_lut ? cmap_lut[k] : nullptr;
+        j.out_tiff[k] = out_tiff[k];
+    }
+    j.stats = stats; j.want_stats = stats != nullptr; j.want_hist = want_hist;
+    j.medians = medians; j.want_median = medians != nullptr;
+    j.tiff = 1; j.tiff_predictor = predictor; j.tiff_rps = rows_per_strip; j.tiff_cap = tiff_cap; j.tiff_len = tiff_len;
     return run_image(j);
 }
 

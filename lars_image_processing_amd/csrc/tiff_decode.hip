@@ -1,7 +1,8 @@
 // TIFF files decoded on the device (lars_h_decode_tiff, lars_h_thumbnail_tiff_u8 and their _deflate siblings): the whole file
 // goes up once, every LZW or Deflate strip / tile is decoded by one wave into its own padded buffer, and one assembly pass
 // writes the picture: byte order, horizontal predictor, planar -> chunky, tile cropping.  The directory is read on the host
-// (tiff_parse.cpp).
+// (tiff_parse.cpp).  Samples are 1 or 2 bytes of an unsigned integer or the 4 bytes of a float32, which the assembly pass moves
+// as 32-bit patterns; the floating-point predictor (3, libtiff's fpAcc) is its third branch.
 //
 // The LZW stage never builds the string table.  Between two Clear codes ("a segment", codes c_0, c_1, ...):
 //   * code i is 9 bits wide for i <= 253, 10 for i <= 765, 11 for i <= 1789, 12 after that, so its bit offset is a closed
@@ -36,7 +37,7 @@ constexpr unsigned int TD_ADLER = 65521u;
 
 struct TdGeom {
     long long nchunks, full;       // bytes of a whole strip / tile = the pitch of the chunk buffers
-    int width, height, spp, bps;   // bps: bytes per sample
+    int width, height, spp, bps;   // bps: bytes per sample (4: float32)
     int planes, inner, across, down, chunk_w, chunk_h;
     int tiled, predictor, big, codec;
 };
@@ -397,8 +398,23 @@ __global__ void k_td_check(TdGeom g, const int *__restrict__ produced, const int
     }
 }
 
+// sample e of a row in the file's byte order; byte loads, since an uncompressed strip starts wherever the file puts it
+__device__ inline unsigned int td_sample(const uint8_t *__restrict__ src, long long e, int bps, int big)
+{
+    if (bps == 1) return src[e];
+    if (bps == 2) return big ? (unsigned int)(src[2 * e] << 8 | src[2 * e + 1]) : (unsigned int)(src[2 * e + 1] << 8 | src[2 * e]);
+    const uint8_t *b = src + 4 * e;
+    return big ? (unsigned int)b[0] << 24 | (unsigned int)b[1] << 16 | (unsigned int)b[2] << 8 | b[3]
+               : (unsigned int)b[3] << 24 | (unsigned int)b[2] << 16 | (unsigned int)b[1] << 8 | b[0];
+}
+
 // One wave per row of a strip / tile that lies inside the picture: samples in file byte order -> native samples, the running
 // sum of predictor 2 as a wave scan per sample (it restarts with the row), planes interleaved, padding columns dropped.
+// Predictor 3 (float32 only): the row is four byte planes of chunk_w * inner bytes, most significant first in either byte
+// order, and the running sum with stride inner runs through all of them, padding columns included; so for each of the inner
+// residues the same scan walks 4 * chunk_w positions, position t being plane t / chunk_w of pixel t % chunk_w, with the carry
+// going from one group of 64 into the next and so from one plane into the next.  Each sum is one byte of one float and is
+// stored as that byte (plane 0 is byte 3 of the native little-endian sample): no lane ever holds two bytes of one sample.
 __global__ __launch_bounds__(256) void k_td_assemble(const uint8_t *__restrict__ file, long long file_len, const long long *__restrict__ table,
                                                      TdGeom g, const uint8_t *__restrict__ bufs, uint8_t *__restrict__ out, const TdCtl *ctl)
 {
@@ -407,6 +423,7 @@ __global__ __launch_bounds__(256) void k_td_assemble(const uint8_t *__restrict__
     const long long units = (long long)g.planes * g.height * g.across;
     const long long nwaves = (long long)gridDim.x * (blockDim.x >> 6);
     uint16_t *out16 = reinterpret_cast<uint16_t *>(out);
+    unsigned int *out32 = reinterpret_cast<unsigned int *>(out);
     for (long long u = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); u < units; u += nwaves) {
         const long long tx = u % g.across, y = (u / g.across) % g.height, p = u / g.across / g.height;
         const long long ty = y / g.chunk_h, r = y % g.chunk_h;
@@ -423,12 +440,36 @@ __global__ __launch_bounds__(256) void k_td_assemble(const uint8_t *__restrict__
             src = file + off + r * row_bytes;
         }
         const long long o0 = (y * g.width + x0) * g.spp;                      // the row's first sample in the picture
+        if (g.predictor == 3) {
+            if (g.bps != 4) continue;                                        // the parser lets it through with float32 only
+            const long long nt = 4ll * g.chunk_w;
+            for (int s = 0; s < g.inner; ++s) {
+                unsigned int carry = 0;                                      // only its low byte counts
+                for (long long tb = 0; tb < nt; tb += 64) {
+                    const long long t = tb + lane;
+                    unsigned int v = t < nt ? src[t * g.inner + s] : 0u;     // t * inner + s < 4 * chunk_w * inner = row_bytes
+                    for (int dlt = 1; dlt < 64; dlt <<= 1) {
+                        const unsigned int up = __shfl_up(v, dlt);
+                        if (lane >= dlt) v += up;
+                    }
+                    v += carry;
+                    carry = __shfl(v, 63);
+                    if (t < nt) {
+                        const long long bp = t / g.chunk_w, x = t - bp * g.chunk_w;
+                        if (x < cols) out[4 * (o0 + x * g.spp + (g.planes > 1 ? p : s)) + 3 - bp] = (uint8_t)v;
+                    }
+                }
+            }
+            continue;
+        }
         if (g.predictor != 2) {
             const long long n = cols * g.inner;
             for (long long e = lane; e < n; e += 64) {
                 const long long o = g.planes > 1 ? o0 + e * g.spp + p : o0 + e;
-                if (g.bps == 1) out[o] = src[e];
-                else out16[o] = g.big ? (uint16_t)(src[2 * e] << 8 | src[2 * e + 1]) : (uint16_t)(src[2 * e + 1] << 8 | src[2 * e]);
+                const unsigned int v = td_sample(src, e, g.bps, g.big);
+                if (g.bps == 1) out[o] = (uint8_t)v;
+                else if (g.bps == 2) out16[o] = (uint16_t)v;
+                else out32[o] = v;
             }
             continue;
         }
@@ -438,8 +479,7 @@ __global__ __launch_bounds__(256) void k_td_assemble(const uint8_t *__restrict__
                 const long long x = xb + lane;
                 unsigned int v = 0;
                 if (x < cols) {
-                    const long long e = x * g.inner + s;
-                    v = g.bps == 1 ? src[e] : g.big ? (unsigned int)(src[2 * e] << 8 | src[2 * e + 1]) : (unsigned int)(src[2 * e + 1] << 8 | src[2 * e]);
+                    v = td_sample(src, x * g.inner + s, g.bps, g.big);
                 }
                 for (int dlt = 1; dlt < 64; dlt <<= 1) {
                     const unsigned int up = __shfl_up(v, dlt);
@@ -450,7 +490,8 @@ __global__ __launch_bounds__(256) void k_td_assemble(const uint8_t *__restrict__
                 if (x < cols) {
                     const long long o = o0 + x * g.spp + (g.planes > 1 ? p : s);
                     if (g.bps == 1) out[o] = (uint8_t)v;
-                    else out16[o] = (uint16_t)v;
+                    else if (g.bps == 2) out16[o] = (uint16_t)v;
+                    else out32[o] = v;
                 }
             }
         }

@@ -1,4 +1,5 @@
-// TIFF files built on the device (lars_h_encode_tiff, lars_d_encode_tiff): every strip is LZW-coded by one wave into its own
+// TIFF files built on the device (lars_h_encode_tiff, lars_d_encode_tiff, and their _f32 siblings for float32 samples, whose
+// predictor is the floating-point one; everything but te_byte and three directory values is shared): every strip is LZW-coded by one wave into its own
 // buffer, one workgroup scans the strip lengths and writes the header and the directory, and one pass moves the strips to their
 // places, so that only the finished file crosses PCIe.
 //
@@ -32,8 +33,8 @@ constexpr int TE_MAX_ENTRIES = 13;                        // directory entries: 
 struct TeGeom {
     long long nstrips, pitch;      // pitch: bytes of one strip's buffer = te_strip_cap of a whole strip, rounded up to 4
     long long rowb;                // bytes of a row of the picture
-    int width, height, spp, bps;   // bps: bytes per sample
-    int rps, predictor;
+    int width, height, spp, bps;   // bps: bytes per sample; 4: float32 (SampleFormat 3)
+    int rps, predictor;            // predictor: 0 none, else horizontal differencing (2) or, for float32, the floating-point one (3)
 };
 
 // Upper bound of a strip's stream for n input bytes, its pad byte included.  Every code but the leading Clear, the Clears that
@@ -50,11 +51,24 @@ __device__ inline int te_width(int i) { return i <= 253 ? 9 : i <= 765 ? 10 : i 
 __device__ inline unsigned int te_hash(unsigned int key) { return (key * 2654435761u) >> 19; }      // 13 bits
 
 // byte B of the picture as the file stores it: the sample's byte, or with the predictor the byte of the sample minus the
-// sample of the pixel to its left (the first pixel of a row as it is), little-endian
+// sample of the pixel to its left (the first pixel of a row as it is), little-endian.  float32 with the predictor (libtiff's
+// fpDiff): the row is stored as four planes of width * spp bytes, plane 0 the most significant byte of every sample, and
+// byte q of that row is its plane byte minus the plane byte spp positions earlier, which may lie in the plane before
 __device__ inline unsigned int te_byte(const uint8_t *__restrict__ img, const TeGeom &g, long long B)
 {
     if (!g.predictor) return img[B];
     const long long q = B % g.rowb;                       // the byte within its row
+    if (g.bps == 4) {
+        const uint8_t *row = img + (B - q);
+        const long long wc = g.rowb >> 2;                 // samples of a row; q / wc <= 3
+        const long long pl = q / wc, e = q - pl * wc;
+        unsigned int v = row[4 * e + 3 - pl];
+        if (q >= g.spp) {
+            const long long q1 = q - g.spp, pl1 = q1 / wc, e1 = q1 - pl1 * wc;
+            v -= row[4 * e1 + 3 - pl1];
+        }
+        return v & 255u;
+    }
     if (g.bps == 1) return (unsigned int)(img[B] - (q >= g.spp ? img[B - g.spp] : 0)) & 255u;
     const uint16_t *s = reinterpret_cast<const uint16_t *>(img) + (B >> 1);       // rowb is even: B and q have the same parity
     const unsigned int v = (unsigned int)(s[0] - ((q >> 1) >= g.spp ? s[-g.spp] : 0)) & 0xFFFFu;
@@ -236,14 +250,15 @@ __global__ __launch_bounds__(TE_FRAME_THREADS) void k_te_frame(TeGeom g, const u
     p += te_entry(p, 278, 4, 1, (unsigned int)g.rps, true, 0);
     p += te_entry(p, 279, 4, (unsigned int)n, zlen[0], n == 1, (unsigned int)cnts_at);
     p += te_entry(p, 284, 3, 1, 1, true, 0);
-    if (g.predictor) p += te_entry(p, 317, 3, 1, 2, true, 0);
+    if (g.predictor) p += te_entry(p, 317, 3, 1, g.bps == 4 ? 3 : 2, true, 0);
     if (extra) p += te_entry(p, 338, 3, (unsigned int)extra, 0, true, 0);
-    p += te_entry(p, 339, 3, (unsigned int)c, 1, c < 3, (unsigned int)fmt_at);
+    const unsigned int format = g.bps == 4 ? 3 : 1;       // IEEE float : unsigned integer
+    p += te_entry(p, 339, 3, (unsigned int)c, format, c < 3, (unsigned int)fmt_at);
     te_put32(p, 0);                                       // no further directory
     if (c >= 3)
         for (int j = 0; j < c; ++j) {
             te_put16(out + bits_at + 2 * j, bits);
-            te_put16(out + fmt_at + 2 * j, 1);
+            te_put16(out + fmt_at + 2 * j, format);
         }
 }
 
@@ -263,10 +278,12 @@ __global__ __launch_bounds__(TE_PACK_THREADS) void k_te_pack(TeGeom g, const uin
     for (unsigned int j = threadIdx.x; j < m / 2; j += TE_PACK_THREADS) dst[j] = src[j];
 }
 
-// the strips of a picture, or false for a shape that is not encoded
-bool te_geometry(int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip, int predictor, TeGeom *g)
+// the strips of a picture, or false for a shape that is not encoded; itemsize 1 or 2: unsigned integers; 4, which only the
+// _f32 entry points hand in (f32): float32
+bool te_geometry(int64_t h, int64_t w, int channels, int itemsize, bool f32, int64_t rows_per_strip, int predictor, TeGeom *g)
 {
-    if (h < 1 || w < 1 || h > (1 << 24) || w > (1 << 24) || channels < 1 || channels > 5 || (itemsize != 1 && itemsize != 2) || rows_per_strip < 0)
+    if (h < 1 || w < 1 || h > (1 << 24) || w > (1 << 24) || channels < 1 || channels > 5 || rows_per_strip < 0 ||
+        !(f32 ? itemsize == 4 : (itemsize == 1 || itemsize == 2)))
         return false;
     g->rowb = (long long)w * channels * itemsize;
     long long rps = rows_per_strip ? rows_per_strip : std::max<long long>(1, tuning().tiff_strip_bytes / g->rowb);
@@ -301,12 +318,14 @@ size_t te_bound(const TeGeom &g)
            4 * (size_t)g.spp + 8 * (size_t)g.nstrips;
 }
 
-int te_check(const char *who, bool pointers, int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip, int predictor, TeGeom *g)
+int te_check(const char *who, bool pointers, int64_t h, int64_t w, int channels, int itemsize, bool f32, int64_t rows_per_strip, int predictor,
+             TeGeom *g)
 {
     if (!pointers) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
-    if (!te_geometry(h, w, channels, itemsize, rows_per_strip, predictor, g))
-        return fail(LARS_ERR_INVALID, "%s: %lld x %lld x %d samples of %d bytes in strips of %lld rows (1 to 2^24 on each side, 1 to 5 samples of 1 or 2 "
-                    "bytes, strips of at most 2^30 bytes)", who, (long long)h, (long long)w, channels, itemsize, (long long)rows_per_strip);
+    if (!te_geometry(h, w, channels, itemsize, f32, rows_per_strip, predictor, g))
+        return fail(LARS_ERR_INVALID, "%s: %lld x %lld x %d samples of %d bytes in strips of %lld rows (1 to 2^24 on each side, 1 to 5 samples of %s, "
+                    "strips of at most 2^30 bytes)", who, (long long)h, (long long)w, channels, itemsize, (long long)rows_per_strip,
+                    f32 ? "4 bytes" : "1 or 2 bytes");
     if (g->nstrips >= (1ll << 31)) return fail(LARS_ERR_UNSUPPORTED, "%s: %lld strips", who, g->nstrips);
     return LARS_OK;
 }
@@ -317,31 +336,28 @@ int te_check(const char *who, bool pointers, int64_t h, int64_t w, int channels,
 
 using namespace lars;
 
-extern "C" {
-
-size_t lars_tiff_bound(int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip)
+static size_t bound_of(int64_t h, int64_t w, int channels, int itemsize, bool f32, int64_t rows_per_strip)
 {
     TeGeom g;
-    return te_geometry(h, w, channels, itemsize, rows_per_strip, 0, &g) ? te_bound(g) : 0;
+    return te_geometry(h, w, channels, itemsize, f32, rows_per_strip, 0, &g) ? te_bound(g) : 0;
 }
 
-size_t lars_tiff_encode_scratch_bytes(int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip)
+static size_t scratch_of(int64_t h, int64_t w, int channels, int itemsize, bool f32, int64_t rows_per_strip)
 {
     TeGeom g;
-    if (!te_geometry(h, w, channels, itemsize, rows_per_strip, 0, &g)) return 0;
+    if (!te_geometry(h, w, channels, itemsize, f32, rows_per_strip, 0, &g)) return 0;
     Carver size(nullptr);
     te_plan(g, size);
     return size.bytes();
 }
 
-int lars_d_encode_tiff(const void *img, int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip, int predictor,
-                       uint8_t *out, size_t out_cap, int64_t *out_len_dev, int32_t *status_dev, void *scratch, void *stream)
+static int encode_on_device(const char *who, const void *img, int64_t h, int64_t w, int channels, int itemsize, bool f32, int64_t rows_per_strip,
+                            int predictor, uint8_t *out, size_t out_cap, int64_t *out_len_dev, int32_t *status_dev, void *scratch, void *stream)
 {
-    static const char *who = "lars_d_encode_tiff";
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     TeGeom g;
-    LARS_TRY(te_check(who, img && out && out_len_dev && status_dev && scratch, h, w, channels, itemsize, rows_per_strip, predictor, &g));
+    LARS_TRY(te_check(who, img && out && out_len_dev && status_dev && scratch, h, w, channels, itemsize, f32, rows_per_strip, predictor, &g));
     if (((uintptr_t)img | (uintptr_t)out) & 1) return fail(LARS_ERR_INVALID, "%s: img and out must be on even addresses", who);
     Carver cv(scratch);
     const TePlan P = te_plan(g, cv);
@@ -357,14 +373,13 @@ int lars_d_encode_tiff(const void *img, int64_t h, int64_t w, int channels, int 
 }
 
 // host picture in, file out: one upload, then the status and the length (one small read), then the file's bytes
-int lars_h_encode_tiff(const void *img, int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip, int predictor,
-                       uint8_t *out, size_t out_cap, int64_t *out_len)
+static int encode_to_host_tiff(const char *who, const void *img, int64_t h, int64_t w, int channels, int itemsize, bool f32,
+                               int64_t rows_per_strip, int predictor, uint8_t *out, size_t out_cap, int64_t *out_len)
 {
-    static const char *who = "lars_h_encode_tiff";
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     TeGeom g;
-    LARS_TRY(te_check(who, img && out && out_len, h, w, channels, itemsize, rows_per_strip, predictor, &g));
+    LARS_TRY(te_check(who, img && out && out_len, h, w, channels, itemsize, f32, rows_per_strip, predictor, &g));
     const size_t in_bytes = (size_t)h * g.rowb, dev_cap = std::min(te_bound(g), out_cap);
     Carver size(nullptr);
     te_plan(g, size);
@@ -379,7 +394,7 @@ int lars_h_encode_tiff(const void *img, int64_t h, int64_t w, int channels, int 
     }));
     hipStream_t s = c->stream;
     LARS_HIP_TRY(hipMemcpyAsync(d_in, img, in_bytes, hipMemcpyHostToDevice, s));
-    LARS_TRY(lars_d_encode_tiff(d_in, h, w, channels, itemsize, g.rps, predictor, d_out, dev_cap, &d_a->len, d_a->status, d_scr, s));
+    LARS_TRY(encode_on_device(who, d_in, h, w, channels, itemsize, f32, g.rps, predictor, d_out, dev_cap, &d_a->len, d_a->status, d_scr, s));
     LARS_HIP_TRY(hipMemcpyAsync(&a, d_a, sizeof a, hipMemcpyDeviceToHost, s));
     LARS_HIP_TRY(hipStreamSynchronize(s));
     switch (a.status[0]) {
@@ -394,6 +409,52 @@ int lars_h_encode_tiff(const void *img, int64_t h, int64_t w, int channels, int 
     LARS_HIP_TRY(hipStreamSynchronize(s));
     *out_len = a.len;
     return LARS_OK;
+}
+
+extern "C" {
+
+size_t lars_tiff_bound(int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip)
+{
+    return bound_of(h, w, channels, itemsize, false, rows_per_strip);
+}
+
+size_t lars_tiff_encode_scratch_bytes(int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip)
+{
+    return scratch_of(h, w, channels, itemsize, false, rows_per_strip);
+}
+
+int lars_d_encode_tiff(const void *img, int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip, int predictor,
+                       uint8_t *out, size_t out_cap, int64_t *out_len_dev, int32_t *status_dev, void *scratch, void *stream)
+{
+    return encode_on_device("lars_d_encode_tiff", img, h, w, channels, itemsize, false, rows_per_strip, predictor, out, out_cap,
+                            out_len_dev, status_dev, scratch, stream);
+}
+
+int lars_h_encode_tiff(const void *img, int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip, int predictor,
+                       uint8_t *out, size_t out_cap, int64_t *out_len)
+{
+    return encode_to_host_tiff("lars_h_encode_tiff", img, h, w, channels, itemsize, false, rows_per_strip, predictor, out, out_cap, out_len);
+}
+
+// the float32 siblings: the same strips, bound and kernels with four bytes per sample
+size_t lars_tiff_f32_bound(int64_t h, int64_t w, int channels, int64_t rows_per_strip) { return bound_of(h, w, channels, 4, true, rows_per_strip); }
+
+size_t lars_tiff_f32_encode_scratch_bytes(int64_t h, int64_t w, int channels, int64_t rows_per_strip)
+{
+    return scratch_of(h, w, channels, 4, true, rows_per_strip);
+}
+
+int lars_d_encode_tiff_f32(const float *img, int64_t h, int64_t w, int channels, int64_t rows_per_strip, int predictor, uint8_t *out,
+                           size_t out_cap, int64_t *out_len_dev, int32_t *status_dev, void *scratch, void *stream)
+{
+    return encode_on_device("lars_d_encode_tiff_f32", img, h, w, channels, 4, true, rows_per_strip, predictor, out, out_cap, out_len_dev, status_dev,
+                            scratch, stream);
+}
+
+int lars_h_encode_tiff_f32(const float *img, int64_t h, int64_t w, int channels, int64_t rows_per_strip, int predictor, uint8_t *out,
+                           size_t out_cap, int64_t *out_len)
+{
+    return encode_to_host_tiff("lars_h_encode_tiff_f32", img, h, w, channels, 4, true, rows_per_strip, predictor, out, out_cap, out_len);
 }
 
 }  // extern "C"

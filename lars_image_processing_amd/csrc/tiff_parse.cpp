@@ -1,7 +1,8 @@
 // Host side of the TIFF decoder: the first directory of a classic TIFF file, validated without a device (lars_tiff_info, and
 // lars_tiff_info_deflate for callers who opt in to Deflate on the device: the same walk with compression 8 / 32946 let through).
 // A C++ restatement of the directory walk in tiffio.read_tiff, with the same rules in the same order, so that a file the
-// Python reader refuses is refused here for the same cause.  Every offset and count is checked against the file length in
+// Python reader refuses is refused here for the same cause.  Samples are unsigned integers of 8 or 16 bits or float32 (32 bits
+// with SampleFormat 3; info's bits == 32 says so), the latter also with the floating-point predictor.  Every offset and count is checked against the file length in
 // 64-bit arithmetic before it is used.  No HIP here: builds into liblars_hip.so and with plain g++ under AddressSanitizer /
 // UBSan (`make asan`).
 #include <string.h>
@@ -110,10 +111,13 @@ int tiff_walk(const uint8_t *file, int64_t len, int64_t info[LARS_TIFF_INFO_N], 
         if (!same || (b.n != 1 && b.n != spp)) { info[LARS_TIFF_INFO_BITS] = bits; return unsupported(LARS_TIFF_REASON_BITS); }
     }
     info[LARS_TIFF_INFO_BITS] = bits;
-    if (bits != 8 && bits != 16) return unsupported(LARS_TIFF_REASON_BITS);
+    if (bits != 8 && bits != 16 && bits != 32) return unsupported(LARS_TIFF_REASON_BITS);
+    // 8 and 16 bits: unsigned integers (the default); 32 bits: IEEE floats, which the tag has to say for every value it holds
+    const int64_t format = bits == 32 ? 3 : 1;
+    if (bits == 32 && (!tag[T_FORMAT].present || tag[T_FORMAT].n == 0)) return unsupported(LARS_TIFF_REASON_SAMPLE_FORMAT);
     if (tag[T_FORMAT].present)
         for (int64_t k = 0; k < tag[T_FORMAT].n; ++k)
-            if (d.value(tag[T_FORMAT], k) != 1) return unsupported(LARS_TIFF_REASON_SAMPLE_FORMAT);
+            if (d.value(tag[T_FORMAT], k) != format) return unsupported(LARS_TIFF_REASON_SAMPLE_FORMAT);
     const int64_t compression = one(T_COMPRESSION, 1, false);
     info[LARS_TIFF_INFO_COMPRESSION] = compression;
     const bool inflated = deflate && (compression == 8 || compression == 32946);
@@ -128,7 +132,8 @@ int tiff_walk(const uint8_t *file, int64_t len, int64_t info[LARS_TIFF_INFO_N], 
     }
     const int64_t predictor = one(T_PREDICTOR, 1, false);
     info[LARS_TIFF_INFO_PREDICTOR] = predictor;
-    if (predictor != 1 && predictor != 2) return unsupported(LARS_TIFF_REASON_PREDICTOR);
+    // the floating-point predictor goes with float samples only
+    if (predictor != 1 && predictor != 2 && !(predictor == 3 && bits == 32)) return unsupported(LARS_TIFF_REASON_PREDICTOR);
     const int64_t planar = one(T_PLANAR, 1, false);
     info[LARS_TIFF_INFO_PLANAR] = planar;
     if (planar != 1 && planar != 2) return fail(LARS_ERR_INVALID, "tiff: planar configuration %lld", (long long)planar);

@@ -58,7 +58,8 @@ def _check_tiff_encoder(tiff_encoder):
 
 
 def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png",
-                  png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow", tiff_encoder="pillow"):
+                  png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow", tiff_encoder="pillow",
+                  index_tiff=False):
     """One file: same outputs as backend-process.py:49-73.  Returns the statistics dicts.
     ``full_depth=True`` reads three-sample 16-bit TIFFs at their full depth (``tiffio.read_image``; Pillow, hence the
     reference, keeps their high bytes only).  ``lut_format="tiff"`` writes the colormap images as
@@ -72,7 +73,9 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     supported and the array is the one read today (``tiffio.read_image``); ``tiff_decoder="device+deflate"`` sends Deflate
     TIFF files there as well (``api.decode_tiff(..., deflate=True)``).  ``tiff_encoder="device"`` builds the TIFF files on
     the GPU (``api.encode_tiff``: LZW strips, the same samples): ``<name>_wb.tif`` instead of Pillow's uncompressed file, and the
-    ``lut_format="tiff"`` pictures instead of ``tiffio.write_tiff``'s uncompressed ones."""
+    ``lut_format="tiff"`` pictures instead of ``tiffio.write_tiff``'s uncompressed ones.  ``index_tiff=True`` also writes the
+    index plane itself, ``<INDEX>/<name>_<index>_f32.tif``: a single-band float32 LZW TIFF with Predictor 3, encoded on the
+    GPU (``api.encode_tiff_f32``), the exact values the picture only colours; every other output is the same file."""
     if lut_format not in ("png", "png8", "tiff"):
         raise ValueError(f"lut_format must be 'png', 'png8' or 'tiff', got {lut_format!r}")
     _check_png_encoder(png_encoder)
@@ -90,9 +93,15 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     indices = list(indices or [])
     palette = lut_format == "png8"
     device_png = png_encoder == "device" and lut_format != "tiff"
+    planes = None                                   # the call whose entries hold the float32 TIFF files
     if device_png:                                  # the pictures stay on the device, their PNG files come back
         res = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False,
                                 want_png="palette" if palette else True) if indices else None
+        if index_tiff and indices:                  # one kind of file per call
+            planes = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False, want_tiff="predictor")
+    elif index_tiff and indices:
+        res = planes = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False, want_rgba=not palette,
+                                         want_entries=palette, want_tiff="predictor")
     else:
         # palette files: the colormap entry of every pixel comes from the device, one byte per pixel (lars_h_process_image)
         res = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False, want_rgba=not palette,
@@ -124,6 +133,8 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
             im.save(out, compress_level=LUT_PNG_LEVEL)
         else:
             Image.fromarray(entry["rgba"], "RGBA").save(out, compress_level=LUT_PNG_LEVEL)
+        if planes is not None:
+            (output_dir / t / f"{name}_{t.lower()}_f32.tif").write_bytes(planes["indices"][t]["tiff"])
         stats[t] = entry["stats"]
     return stats
 
@@ -143,12 +154,12 @@ def files_of_rank(files, rank=0, world=1):
 def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, process_gndvi=False,
                   process_ndwi=True, workers=4, verbose=True, full_depth=False, lut_format="png", rank=0, world=1,
                   device=None, png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow",
-                  tiff_encoder="pillow"):
+                  tiff_encoder="pillow", index_tiff=False):
     """backend-process.py:75-97 with its module constants as arguments.  Returns ``{file name: stats | error}``.
     ``rank`` / ``world``: one process per GPU, each takes its block of the sorted file list (``files_of_rank``); the output
     directories are shared, the file names distinct.  ``device``: the GPU ordinal every worker thread binds (the library's
     context is per thread and defaults to device 0); None leaves the threads' binding alone.  ``png_encoder``,
-    ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``, ``tiff_encoder``: see ``process_image``."""
+    ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``, ``tiff_encoder``, ``index_tiff``: see ``process_image``."""
     _check_tiff_encoder(tiff_encoder)
     _check_png_encoder(png_encoder)
     _check_png_decoder(png_decoder)
@@ -166,7 +177,7 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
             if verbose:
                 print(f"Processing {idx}/{total}: {f.name}")
             return f.name, process_image(f, output_path, process_wb, indices or None, full_depth, lut_format, png_encoder,
-                                         png_decoder, jpeg_decoder, tiff_decoder, tiff_encoder)
+                                         png_decoder, jpeg_decoder, tiff_decoder, tiff_encoder, index_tiff)
         except Exception as e:                              # same policy as upstream :96-97
             if verbose:
                 print(f"Error processing {f.name}: {str(e)}")
@@ -255,6 +266,8 @@ def main(argv=None):
                          "'device+deflate' decodes Deflate TIFF files there too")
     ap.add_argument("--tiff-encoder", default="pillow", choices=list(TIFF_ENCODERS),
                     help="'device' builds <name>_wb.tif and the --lut-format tiff pictures on the GPU (LZW strips, same samples)")
+    ap.add_argument("--index-tiff", action="store_true",
+                    help="also write <INDEX>/<name>_<index>_f32.tif: the float32 index plane as an LZW TIFF with Predictor 3, built on the GPU")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     from .dist import env_rank_world
@@ -263,7 +276,7 @@ def main(argv=None):
                         not args.quiet, args.full_depth, args.lut_format, rank, world,
                         device=local_rank if world > 1 else None, png_encoder=args.png_encoder,
                         png_decoder=args.png_decoder, jpeg_decoder=args.jpeg_decoder, tiff_decoder=args.tiff_decoder,
-                        tiff_encoder=args.tiff_encoder)
+                        tiff_encoder=args.tiff_encoder, index_tiff=args.index_tiff)
     failed = {k: str(v) for k, v in res.items() if isinstance(v, Exception)}
     print(json.dumps({"rank": rank, "world": world, "files": len(res), "failed": failed}))
     return 1 if failed else 0

@@ -8,6 +8,10 @@ samples of 8 or 16 bits, chunky or planar layout, strips or tiles, either byte o
 library's host-side decoder) or Deflate (compression 8 / 32946), with or without the horizontal predictor.  Anything else raises ``TiffError`` naming the
 feature -- never a silently wrong array.
 
+Float32 samples (BitsPerSample 32 with SampleFormat 3, the index planes' own type) are read in the same layouts, with
+predictor 1, 2 (integer differencing of the 32-bit patterns) or 3 (the floating-point predictor: libtiff's ``fpAcc``), and
+written by ``write_float_tiff``.
+
 No oracle exists in the reference for this loader; tests pin it by round trips, against Pillow on the
 files both can read (8-bit RGB, 16-bit single band), and against hand-assembled files.
 """
@@ -108,11 +112,71 @@ def _chunk(buf, offset, nbytes, compression, want):
     return raw[:want]
 
 
+def _float_predictor_undo(raw, rows, chunk_w, inner):
+    """Predictor 3 of ``rows`` rows of ``chunk_w`` pixels of ``inner`` float32 samples, undone (libtiff's fpAcc): per row the
+    running sum of the ``4 * chunk_w * inner`` bytes with stride ``inner``, across the four byte planes and the padding
+    columns; sample e is then bytes acc[e], acc[wc + e], acc[2 wc + e], acc[3 wc + e], most significant first, whatever the
+    file's byte order.  Returns native uint32 patterns ``[rows, chunk_w, inner]``."""
+    wc = chunk_w * inner
+    acc = np.cumsum(raw.reshape(rows, 4 * chunk_w, inner), axis=1, dtype=np.uint8).reshape(rows, 4, wc).astype(np.uint32)
+    return (acc[:, 0] << 24 | acc[:, 1] << 16 | acc[:, 2] << 8 | acc[:, 3]).reshape(rows, chunk_w, inner)
+
+
+def _float_predictor_apply(t):
+    """The inverse (libtiff's fpDiff): native uint32 patterns ``[rows, chunk_w, inner]`` -> uint8 ``[rows, 4 * chunk_w * inner]``."""
+    rows, chunk_w, inner = t.shape
+    u = t.reshape(rows, chunk_w * inner)
+    planes = np.stack([u >> 24, (u >> 16) & 255, (u >> 8) & 255, u & 255], axis=1).astype(np.uint8).reshape(rows, 4 * chunk_w, inner)
+    return np.concatenate([planes[:, :1], np.diff(planes, axis=1)], axis=1).reshape(rows, -1)
+
+
+def _lzw_encode(data):
+    """TIFF LZW stream of ``data`` by the greedy encoder with libtiff's Clear policy (a Clear once the table holds 4094 codes),
+    a leading Clear and EndOfInformation, codes MSB first, 9 to 12 bits wide.  Plain Python: for test files, not for speed."""
+    out, acc, nbits, i = bytearray(), 0, 0, 0
+
+    def emit(code):
+        nonlocal acc, nbits, i
+        width = 9 if i <= 253 else 10 if i <= 765 else 11 if i <= 1789 else 12
+        acc = (acc << width) | code
+        nbits += width
+        while nbits >= 8:
+            nbits -= 8
+            out.append((acc >> nbits) & 0xFF)
+        acc &= (1 << nbits) - 1
+        i = 0 if code == 256 else i + 1
+
+    emit(256)
+    table, nxt, w = {}, 258, -1
+    for byte in bytes(data):
+        if w < 0:
+            w = byte
+            continue
+        key = w << 8 | byte
+        code = table.get(key)
+        if code is not None:
+            w = code
+            continue
+        emit(w)
+        table[key] = nxt
+        nxt += 1
+        if nxt >= 4094:
+            emit(256)
+            table, nxt = {}, 258
+        w = byte
+    if w >= 0:
+        emit(w)
+    emit(257)
+    if nbits:
+        out.append((acc << (8 - nbits)) & 0xFF)
+    return bytes(out)
+
+
 MAX_DECODED_BYTES = 16 << 30      # refuse directories that claim more than this (a corrupt header must not allocate the host away)
 
 
 def read_tiff(path_or_bytes, max_bytes=MAX_DECODED_BYTES):
-    """``[H, W, C]`` (``[H, W]`` for one sample per pixel) uint8 / uint16 array of the first image of a TIFF."""
+    """``[H, W, C]`` (``[H, W]`` for one sample per pixel) uint8 / uint16 / float32 array of the first image of a TIFF."""
     if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
         buf = memoryview(path_or_bytes)
     else:
@@ -131,18 +195,18 @@ def read_tiff(path_or_bytes, max_bytes=MAX_DECODED_BYTES):
     if len(set(bits)) != 1 or len(bits) not in (1, spp):
         raise TiffError(f"samples of different widths {bits} are not supported")
     bits = int(bits[0])
-    if bits not in (8, 16):
-        raise TiffError(f"{bits}-bit samples are not supported (8 or 16)")
+    if bits not in (8, 16, 32):
+        raise TiffError(f"{bits}-bit samples are not supported (8, 16 or 32)")
     fmt = tags.get(SAMPLE_FORMAT) or (1,)
-    if any(int(f) != 1 for f in fmt):
-        raise TiffError(f"sample format {fmt} is not supported (unsigned integer only)")
+    if any(int(f) != (3 if bits == 32 else 1) for f in fmt):
+        raise TiffError(f"sample format {fmt} of {bits}-bit samples is not supported (unsigned integers of 8 or 16 bits, floats of 32)")
     compression = _one(tags, COMPRESSION, 1)
     if compression not in (1, 5, 8, 32946):
         names = {2: "CCITT", 6: "old JPEG", 7: "JPEG", 32773: "PackBits"}
         raise TiffError(f"compression {compression} ({names.get(compression, 'unknown')}) is not supported (none, LZW or Deflate)")
     predictor = _one(tags, PREDICTOR, 1)
-    if predictor not in (1, 2):
-        raise TiffError(f"predictor {predictor} is not supported")
+    if predictor not in (1, 2) and not (predictor == 3 and bits == 32):
+        raise TiffError(f"predictor {predictor} is not supported" + (" (the floating-point predictor goes with float samples)" if predictor == 3 else ""))
     planar = _one(tags, PLANAR_CONFIG, 1)
     if planar not in (1, 2):
         raise TiffError(f"planar configuration {planar}")
@@ -150,7 +214,8 @@ def read_tiff(path_or_bytes, max_bytes=MAX_DECODED_BYTES):
         raise TiffError("empty image")
     if width * height * spp * (bits // 8) > max_bytes:
         raise TiffError(f"image of {width} x {height} x {spp} x {bits} bits exceeds max_bytes={max_bytes}")
-    dtype = np.dtype(np.uint8 if bits == 8 else (endian + "u2"))
+    # float32 samples travel as their 32-bit patterns (predictor 2 differences them as integers) and are viewed as floats at the end
+    dtype = np.dtype(np.uint8 if bits == 8 else (endian + ("u2" if bits == 16 else "u4")))
     planes = spp if planar == 2 else 1                    # separately stored sample planes
     inner = 1 if planar == 2 else spp                     # samples per pixel inside one chunk
 
@@ -200,28 +265,22 @@ def read_tiff(path_or_bytes, max_bytes=MAX_DECODED_BYTES):
                 else:
                     raw = _chunk(buf, int(offsets[k]), int(counts[k]), compression, want)
                 k += 1
-                a = np.frombuffer(raw, dtype=dtype).reshape(stored_rows, chunk_w, inner)
+                if predictor == 3:
+                    a = _float_predictor_undo(np.frombuffer(raw, dtype=np.uint8), stored_rows, chunk_w, inner)
+                else:
+                    a = np.frombuffer(raw, dtype=dtype).reshape(stored_rows, chunk_w, inner)
                 if predictor == 2:
                     a = np.cumsum(a, axis=1, dtype=a.dtype.newbyteorder("="))         # wraps modulo 2^bits, as the predictor does
                 out[p, y0:y0 + rows_here, x0:x0 + cols_here] = a[:rows_here, :cols_here]
     img = out[0] if planar == 1 else np.ascontiguousarray(np.moveaxis(out[..., 0], 0, -1))
+    if bits == 32:
+        img = img.view(np.float32)
     return img[..., 0] if spp == 1 else img
 
 
-def write_tiff(path, array, rows_per_strip=None, tile=None, byteorder="<", planar=1, deflate=False, predictor=False):
-    """Write ``[H, W]`` / ``[H, W, C]`` uint8 or uint16 samples as a classic TIFF (strips, or tiles when
-    ``tile=(rows, cols)``).  Photometric: RGB for >= 3 samples, BlackIsZero otherwise; samples past the third are
-    declared unspecified extra samples.  Returns the number of bytes written."""
-    a = np.asarray(array)
-    if a.ndim == 2:
-        a = a[..., None]
-    if a.ndim != 3 or a.dtype not in (np.uint8, np.uint16) or a.size == 0:
-        raise TiffError("write_tiff takes a non-empty [H, W] or [H, W, C] uint8 / uint16 array")
-    if byteorder not in ("<", ">") or planar not in (1, 2):
-        raise TiffError("byteorder must be '<' or '>', planar 1 or 2")
+def _split(a, rows_per_strip, tile, planar):
+    """The strips or padded tiles of ``[H, W, C]`` samples in file order: (chunks ``[rows, cols, inner]``, rows per strip or None)."""
     h, w, c = a.shape
-    bits = a.dtype.itemsize * 8
-    dt = np.dtype(np.uint8 if bits == 8 else byteorder + "u2")
     planes = [a] if planar == 1 else [a[..., k:k + 1] for k in range(c)]
     chunks = []
     if tile:
@@ -235,19 +294,18 @@ def write_tiff(path, array, rows_per_strip=None, tile=None, byteorder="<", plana
                     part = pl[y0:y0 + th, x0:x0 + tw]
                     t[:part.shape[0], :part.shape[1]] = part
                     chunks.append(t)
-    else:
-        rps = h if not rows_per_strip else max(1, min(int(rows_per_strip), h))
-        for pl in planes:
-            for y0 in range(0, h, rps):
-                chunks.append(pl[y0:y0 + rps])
-    blobs = []
-    for t in chunks:
-        if predictor:
-            t = np.concatenate([t[:, :1], np.diff(t, axis=1)], axis=1)      # unsigned wrap-around = modulo 2^bits
-        raw = np.ascontiguousarray(t, dtype=a.dtype).astype(dt, copy=False)
-        # uncompressed chunks are written straight from the array's memory (no 64 MiB byte-string copies)
-        blobs.append(zlib.compress(raw.tobytes(), 6) if deflate else memoryview(raw.reshape(-1).view(np.uint8)))
+        return chunks, None
+    rps = h if not rows_per_strip else max(1, min(int(rows_per_strip), h))
+    for pl in planes:
+        for y0 in range(0, h, rps):
+            chunks.append(pl[y0:y0 + rps])
+    return chunks, rps
 
+
+def _write_file(path, blobs, shape, bits, sample_format, compression, predictor, tile, rps, byteorder, planar):
+    """The file of the encoded strips / tiles ``blobs``: header, data on even offsets, the directory with its tags ascending,
+    arrays of more than four bytes behind it.  Returns the number of bytes written."""
+    h, w, c = shape
     entries = []                                             # (tag, type, values)
 
     def add(tag, typ, *values):
@@ -256,16 +314,16 @@ def write_tiff(path, array, rows_per_strip=None, tile=None, byteorder="<", plana
     add(IMAGE_WIDTH, 4, w)
     add(IMAGE_LENGTH, 4, h)
     add(BITS_PER_SAMPLE, 3, *([bits] * c))
-    add(COMPRESSION, 3, 8 if deflate else 1)
+    add(COMPRESSION, 3, compression)
     add(PHOTOMETRIC, 3, 2 if c >= 3 else 1)
     add(SAMPLES_PER_PIXEL, 3, c)
     add(PLANAR_CONFIG, 3, planar)
-    if predictor:
-        add(PREDICTOR, 3, 2)
+    if predictor != 1:
+        add(PREDICTOR, 3, predictor)
     extra = c - 3 if c > 3 else (c - 1 if c == 2 else 0)
     if extra:
         add(EXTRA_SAMPLES, 3, *([0] * extra))
-    add(SAMPLE_FORMAT, 3, *([1] * c))
+    add(SAMPLE_FORMAT, 3, *([sample_format] * c))
     header = 8
     data_at = header
     offsets = []
@@ -307,6 +365,61 @@ def write_tiff(path, array, rows_per_strip=None, tile=None, byteorder="<", plana
         fh.write(ifd)
         fh.write(overflow)
     return overflow_at + len(overflow)
+
+
+def write_tiff(path, array, rows_per_strip=None, tile=None, byteorder="<", planar=1, deflate=False, predictor=False):
+    """Write ``[H, W]`` / ``[H, W, C]`` uint8 or uint16 samples as a classic TIFF (strips, or tiles when
+    ``tile=(rows, cols)``).  Photometric: RGB for >= 3 samples, BlackIsZero otherwise; samples past the third are
+    declared unspecified extra samples.  Returns the number of bytes written."""
+    a = np.asarray(array)
+    if a.ndim == 2:
+        a = a[..., None]
+    if a.ndim != 3 or a.dtype not in (np.uint8, np.uint16) or a.size == 0:
+        raise TiffError("write_tiff takes a non-empty [H, W] or [H, W, C] uint8 / uint16 array")
+    if byteorder not in ("<", ">") or planar not in (1, 2):
+        raise TiffError("byteorder must be '<' or '>', planar 1 or 2")
+    bits = a.dtype.itemsize * 8
+    dt = np.dtype(np.uint8 if bits == 8 else byteorder + "u2")
+    chunks, rps = _split(a, rows_per_strip, tile, planar)
+    blobs = []
+    for t in chunks:
+        if predictor:
+            t = np.concatenate([t[:, :1], np.diff(t, axis=1)], axis=1)      # unsigned wrap-around = modulo 2^bits
+        raw = np.ascontiguousarray(t, dtype=a.dtype).astype(dt, copy=False)
+        # uncompressed chunks are written straight from the array's memory (no 64 MiB byte-string copies)
+        blobs.append(zlib.compress(raw.tobytes(), 6) if deflate else memoryview(raw.reshape(-1).view(np.uint8)))
+    return _write_file(path, blobs, a.shape, bits, 1, 8 if deflate else 1, 2 if predictor else 1, tile, rps, byteorder, planar)
+
+
+def write_float_tiff(path, array, rows_per_strip=None, tile=None, byteorder="<", planar=1, deflate=False, lzw=False, predictor=1):
+    """Write ``[H, W]`` / ``[H, W, C]`` float32 samples as a classic TIFF: ``write_tiff``'s layouts and directory with
+    BitsPerSample 32 and SampleFormat 3.  ``predictor``: 1 none, 2 integer differencing of the 32-bit patterns (modulo
+    2^32, what libtiff does whatever the sample format), 3 the floating-point predictor (libtiff's fpDiff: per row the four
+    byte planes, most significant first in either byte order, differenced across the plane borders).  ``lzw=True`` codes
+    every strip / tile with a plain Python greedy encoder (libtiff's stream; slow), ``deflate=True`` with zlib.  No other
+    dtype is cast.  Returns the number of bytes written."""
+    a = np.asarray(array)
+    if a.ndim == 2:
+        a = a[..., None]
+    if a.ndim != 3 or a.dtype != np.float32 or a.size == 0:
+        raise TiffError("write_float_tiff takes a non-empty [H, W] or [H, W, C] float32 array")
+    if byteorder not in ("<", ">") or planar not in (1, 2):
+        raise TiffError("byteorder must be '<' or '>', planar 1 or 2")
+    if predictor not in (1, 2, 3) or isinstance(predictor, bool):
+        raise TiffError("predictor must be 1, 2 or 3")
+    if deflate and lzw:
+        raise TiffError("deflate or lzw, not both")
+    chunks, rps = _split(np.ascontiguousarray(a).view(np.uint32), rows_per_strip, tile, planar)
+    blobs = []
+    for t in chunks:
+        if predictor == 3:
+            raw = _float_predictor_apply(np.ascontiguousarray(t)).tobytes()
+        else:
+            if predictor == 2:
+                t = np.concatenate([t[:, :1], np.diff(t, axis=1)], axis=1)  # modulo 2^32
+            raw = np.ascontiguousarray(t).astype(byteorder + "u4", copy=False).tobytes()
+        blobs.append(zlib.compress(raw, 6) if deflate else _lzw_encode(raw) if lzw else raw)
+    return _write_file(path, blobs, a.shape, 32, 3, 8 if deflate else 5 if lzw else 1, predictor, tile, rps, byteorder, planar)
 
 
 def read_image(path, full_depth=False, png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow"):

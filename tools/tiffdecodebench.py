@@ -8,7 +8,9 @@ predictor from Pillow, and three-sample uint16 files with LZW and predictor from
 (``--side16``, 768 by default: the encoder is Python).  The Deflate legs (``decode_tiff(..., deflate=True)``, in the same
 run and by the same rules): the gallery pictures as Pillow writes them with ``tiff_adobe_deflate``, the 4096 x 4096 file with
 predictor, the uint16 file from ``write_tiff(deflate=True, predictor=True)``, and one 1024 x 1024 RGB file written as a
-single strip, which one lane decodes.  Per file kind, after a warm-up pass: the median over reps of the
+single strip, which one lane decodes.  The float legs (``f32_*``): the float32 NDVI plane of the 1/f pictures of
+``tiffencodebench.py`` at 4096 x 4096 and 2048 x 1536, computed by the library and written by Pillow with ``tiff_lzw``, with
+and without the floating-point predictor (317: 3); no thumbnails there.  Per file kind, after a warm-up pass: the median over reps of the
 per-file time, host bytes in and host array out, each call ending in a device synchronise.  Every result is checked
 against ``read_tiff`` first.  Each kind runs in a child process of its own under a time limit.
 
@@ -33,7 +35,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 KINDS = ("gallery_rgb_lzw", "rgb_4096_lzw_predictor", "u16x3_lzw_predictor",
-         "gallery_rgb_deflate", "rgb_4096_deflate_predictor", "u16x3_deflate_predictor", "rgb_1024_deflate_one_strip")
+         "gallery_rgb_deflate", "rgb_4096_deflate_predictor", "u16x3_deflate_predictor", "rgb_1024_deflate_one_strip",
+         "f32_4096_lzw", "f32_4096_lzw_predictor3", "f32_2048x1536_lzw", "f32_2048x1536_lzw_predictor3")
 LIMIT_S = 420
 
 
@@ -48,6 +51,12 @@ def files_of(kind, side16):
     from thumbbench import gallery
     import tiff_cases as tc
     scheme = "tiff_adobe_deflate" if "deflate" in kind else "tiff_lzw"
+    if kind.startswith("f32_"):
+        import lars_image_processing_amd as lars
+        from jpegdecodebench import pictures
+        planes = [lars.calculate_index(a, "NDVI") for a in pictures((4096, 4096) if "4096_" in kind else (1536, 2048), 2, seed=11)]
+        extra = {"tiffinfo": {317: 3}} if kind.endswith("predictor3") else {}
+        return [(pil_tiff(a, compression=scheme, **extra), pil_tiff(a), True) for a in planes]
     if kind in ("gallery_rgb_lzw", "gallery_rgb_deflate"):
         pics = (gallery(7) + gallery(8))[:20]
         return [(pil_tiff(a, compression=scheme), pil_tiff(a), True) for a in pics]
@@ -121,7 +130,8 @@ def run_kind(kind, args):
          "decode_tiff_ms": gpu_ms(decode, files), "decode_tiff_uncompressed_ms": gpu_ms(lars.decode_tiff, raws),
          "upload_ms": gpu_ms(lambda a: dev.upload(a), [first]), "download_ms": gpu_ms(lambda n: dev.download(np.uint8, (n,)), [out_bytes])}
     r["kernels_and_host_ms"] = r["decode_tiff_ms"] - r["upload_ms"] - r["download_ms"]
-    if pillow:
+    thumbs = pillow and info["bits"] == 8
+    if thumbs:
         r["thumbnail_tiff_ms"] = gpu_ms(thumbnail, files)
     if not args.gpu_only:
         r["read_tiff_ms"] = host_ms(tiffio.read_tiff, files, args.reps)
@@ -137,9 +147,10 @@ def run_kind(kind, args):
                 im.thumbnail((400, 400), Image.Resampling.LANCZOS)
                 return im
             r["pillow_load_ms"] = host_ms(pil_load, files, args.reps)
-            r["pillow_thumbnail_ms"] = host_ms(pil_thumb, files, args.reps)
             r["speedup_over_pillow"] = r["pillow_load_ms"] / r["decode_tiff_ms"]
-            r["thumbnail_speedup"] = r["pillow_thumbnail_ms"] / r["thumbnail_tiff_ms"]
+            if thumbs:
+                r["pillow_thumbnail_ms"] = host_ms(pil_thumb, files, args.reps)
+                r["thumbnail_speedup"] = r["pillow_thumbnail_ms"] / r["thumbnail_tiff_ms"]
     print(json.dumps(r), flush=True)
 
 
@@ -149,12 +160,13 @@ def main():
     ap.add_argument("--side16", type=int, default=768, help="side of the three-sample uint16 file")
     ap.add_argument("--gpu-only", action="store_true", help="skip the host legs (for a kernel trace)")
     ap.add_argument("--kind", choices=KINDS, help="run this kind in this process (what the parent starts per kind)")
+    ap.add_argument("--only", help="the parent runs only the kinds whose names start with this (f32: the float legs)")
     ap.add_argument("--json", help="also write the figures to this file")
     args = ap.parse_args()
     if args.kind:
         return run_kind(args.kind, args)
     res = {"reps": args.reps, "kinds": {}}
-    for kind in KINDS:                                         # one child per kind, each under its own time limit; stop at the first that fails
+    for kind in [k for k in KINDS if k.startswith(args.only or "")]:    # one child per kind, each under its own time limit; stop at the first that fails
         cmd = [sys.executable, os.path.abspath(__file__), "--kind", kind, "--reps", str(args.reps), "--side16", str(args.side16)]
         out = subprocess.run(cmd + (["--gpu-only"] if args.gpu_only else []), capture_output=True, text=True, timeout=LIMIT_S)
         if out.returncode != 0:

@@ -10,7 +10,13 @@ ending in a device synchronise: the median over the pictures after a warm-up pas
 Every file is read back first.  ``--split`` adds the parts of one call (upload, the kernels from a resident picture into a
 resident file, download of the file), ``--sweep`` the knob "tiff_strip_bytes" at 8192 .. 262144.
 
-    python tools/tiffencodebench.py [--files 20] [--runs 2] [--split] [--sweep] [--gpu-only] [--json out.json]
+The float leg (``--legs float`` alone, ``--legs all`` with the pictures): the float32 NDVI plane of the same 1/f pictures at
+4096 x 4096 and 2048 x 1536, computed by the library, through ``encode_tiff_f32`` with and without the floating-point
+predictor next to Pillow's ``Image.fromarray(plane).save(format="TIFF", compression="tiff_lzw", tiffinfo={317: 3})`` (and without
+the tag), file sizes of both; and ``process_image(want_tiff=...)``, where the planes never leave the device, next to the same
+call with ``want_arrays=True`` followed by ``encode_tiff_f32`` on the three host planes, in the same process.
+
+    python tools/tiffencodebench.py [--legs picture] [--files 20] [--runs 2] [--split] [--sweep] [--gpu-only] [--json out.json]
 
 Kernel times come from a separate run:  rocprofv3 --kernel-trace --stats -- python tools/tiffencodebench.py --gpu-only
 """
@@ -105,6 +111,59 @@ def split_ms(a, predictor, reps=20):
     return {"upload_ms": upload, "device_encode_ms": device, "download_ms": download}
 
 
+def pil_float_tiff(a, predictor=False):
+    b = io.BytesIO()
+    Image.fromarray(a).save(b, format="TIFF", compression="tiff_lzw", **({"tiffinfo": {317: 3}} if predictor else {}))
+    return b.getvalue()
+
+
+def same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def float_leg(args, res):
+    """encode_tiff_f32 on NDVI planes, and process_image(want_tiff=...) against planes that come back and go up again."""
+    for name, shape in (("ndvi_4096x4096_f32", (4096, 4096)), ("ndvi_2048x1536_f32", (1536, 2048))):
+        rgb = many_pictures(shape, min(args.files, DISTINCT), seed=11)
+        planes = [lars.calculate_index(a, "NDVI") for a in rgb]
+        for predictor in (False, True):
+            files = [lars.encode_tiff_f32(a, predictor=predictor) for a in planes[:2]]
+            for a, b in zip(planes, files):                    # a fast wrong answer is no answer
+                assert same_bits(tiffio.read_tiff(b), a) and same_bits(np.asarray(Image.open(io.BytesIO(b))), a) and same_bits(lars.decode_tiff(b), a)
+            r = {"files": len(planes), "mean_file_bytes": int(np.mean([len(b) for b in files])), "shape": list(shape), "plane_bytes": planes[0].nbytes,
+                 "strips": len(tiffio._read_ifd(memoryview(files[0]), "<")[tiffio.STRIP_OFFSETS]),
+                 "encode_tiff_f32_ms": per_picture_ms(lambda a: lars.encode_tiff_f32(a, predictor=predictor), planes, True, args.runs)}
+            if not args.gpu_only:
+                pil = pil_float_tiff(planes[0], predictor)
+                r["pillow_file_bytes"] = len(pil)
+                r["pillow_strips"] = len(tiffio._read_ifd(memoryview(pil), "<")[tiffio.STRIP_OFFSETS])
+                r["same_strips_as_pillow"] = bool(tiffio._read_ifd(memoryview(pil), "<")[tiffio.STRIP_BYTE_COUNTS] ==
+                                                  tiffio._read_ifd(memoryview(files[0]), "<")[tiffio.STRIP_BYTE_COUNTS])
+                r["pillow_save_ms"] = per_picture_ms(lambda a: pil_float_tiff(a, predictor), planes, False, args.runs)
+                r["encode_speedup"] = r["pillow_save_ms"] / r["encode_tiff_f32_ms"]
+            key = name + ("_predictor3" if predictor else "")
+            res["kinds"][key] = r
+            print(key, json.dumps(r), flush=True)
+        # the three index planes of one picture as files: on the device all the way, or down as arrays and up again
+        mode = "predictor"
+
+        def on_device(a):
+            return lars.process_image(a, want_arrays=False, want_tiff=mode)
+
+        def through_host(a):
+            got = lars.process_image(a, want_arrays=True)
+            return {t: lars.encode_tiff_f32(got["indices"][t]["index"], predictor=True) for t in got["indices"]}
+
+        one, two = on_device(rgb[0]), through_host(rgb[0])
+        assert all(one["indices"][t]["tiff"] == two[t] for t in two)
+        r = {"shape": list(shape), "indices": 3, "file_bytes": {t: len(b) for t, b in two.items()},
+             "process_image_want_tiff_ms": per_picture_ms(on_device, rgb, True, args.runs),
+             "process_image_arrays_then_encode_ms": per_picture_ms(through_host, rgb, True, args.runs)}
+        r["speedup"] = r["process_image_arrays_then_encode_ms"] / r["process_image_want_tiff_ms"]
+        res["kinds"][name + "_process_image"] = r
+        print(name + "_process_image", json.dumps(r), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--files", type=int, default=20, help="pictures per kind (each timed once per run after the warm-up)")
@@ -112,6 +171,8 @@ def main():
     ap.add_argument("--gpu-only", action="store_true", help="skip the Pillow leg (for a kernel trace)")
     ap.add_argument("--split", action="store_true", help="also time the parts of one call")
     ap.add_argument("--sweep", action="store_true", help='also sweep "tiff_strip_bytes"')
+    ap.add_argument("--legs", choices=["picture", "float", "all"], default="picture",
+                    help="picture: the RGB pictures through encode_tiff; float: NDVI planes through encode_tiff_f32; all: both")
     ap.add_argument("--json", help="also write the figures to this file")
     args = ap.parse_args()
     if _ffi.device_count() < 1:
@@ -119,7 +180,9 @@ def main():
     import PIL
     res = {"device": _ffi.device_name(), "pillow": PIL.__version__, "files": args.files, "runs": args.runs,
            "tiff_strip_bytes": _ffi.get_tuning("tiff_strip_bytes"), "kinds": {}}
-    for name, shape in KINDS.items():
+    if args.legs in ("float", "all"):
+        float_leg(args, res)
+    for name, shape in KINDS.items() if args.legs in ("picture", "all") else ():
         arrays = many_pictures(shape, args.files, seed=11)
         for predictor in (False, True):
             files = [lars.encode_tiff(a, predictor=predictor) for a in arrays[:DISTINCT]]
