@@ -530,6 +530,52 @@ int lars_h_decode_png_u8(const uint8_t *file, int64_t len, uint8_t *out, size_t 
 int lars_h_thumbnail_png_u8(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
                             int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out);
 
+/* The extended PNG decoder: every valid IHDR combination that is not APNG -- bit depths 1, 2, 4 and 16 and Adam7 interlace
+ * besides the above -- as the array Pillow's np.asarray gives:
+ *   colour type 0 (gray)     depth 1: one byte 0 / 1 per pixel (Pillow: bool); depth 2 / 4: uint8, sample x 85 / x 17;
+ *                            depth 8: uint8; depth 16: native-endian uint16 (mode I;16; the file is big-endian)
+ *   colour type 3 (palette)  uint8, the unscaled indices, whatever PLTE holds
+ *   colour type 2 / 6        depth 16: uint8, the high byte of every sample
+ *   colour type 4 (LA)       depth 8: [h][w][2]; depth 16: uint8 [h][w][4] = L, L, L, A of the high bytes (Pillow opens it as RGBA)
+ * Interlace changes nothing in the result.  The zlib stream is decoded by the kernels of lars_d_decode_png_u8; the rows
+ * of each pass are then unfiltered by a workgroup of their own and placed into the array.  An 8-bit file without
+ * interlace takes lars_d_decode_png_u8's path unchanged.
+ * lars_png_out_format: pure host code; channels and bytes per sample of that array for a (depth, colour type) pair.
+ * lars_png_layout: pure host code; the filtered stream of a w x h picture: passes[k * LARS_PNGX_PASS_N + LARS_PNGX_PASS_*] for
+ * each of the *npass non-empty passes (1 without interlace, up to 7 with; an Adam7 pass with no column or no row has no
+ * bytes at all, not even filter bytes) and *need, the stream's length (saturating at INT64_MAX).
+ * lars_png_decode_ex_scratch_bytes: device scratch of lars_d_decode_png_ex (0 for a picture it cannot decode: need must
+ * stay below 2^31 and both sides within 2^24).
+ * lars_d_decode_png_ex: as lars_d_decode_png_u8, with the IHDR numbers in place of channels; out holds h * w * channels *
+ * itemsize bytes of lars_png_out_format.  A LARS_PNGD_FILTER detail is pass << 24 | row within the pass (pass 1 to 7, 0
+ * without interlace).
+ * lars_h_decode_png_ex, lars_h_thumbnail_png_ex: the host entry points; the thumbnail takes files whose array is uint8
+ * L, RGB or RGBA (Pillow modes 1, I;16, P and LA are refused). */
+#define LARS_PNGX_PASS_N 10
+enum {                           /* positions in one pass of lars_png_layout's passes[] */
+    LARS_PNGX_PASS_X0 = 0,       /* first column and row of the pass in the picture */
+    LARS_PNGX_PASS_Y0 = 1,
+    LARS_PNGX_PASS_DX = 2,       /* column and row step */
+    LARS_PNGX_PASS_DY = 3,
+    LARS_PNGX_PASS_W = 4,        /* columns and rows of the pass */
+    LARS_PNGX_PASS_H = 5,
+    LARS_PNGX_PASS_ROW_BYTES = 6,/* ceil(W * channels * depth / 8), without the filter byte */
+    LARS_PNGX_PASS_OFFSET = 7,   /* of the pass's first filter byte in the stream */
+    LARS_PNGX_PASS_BPP = 8,      /* filter distance max(1, channels * depth / 8) */
+    LARS_PNGX_PASS_INDEX = 9     /* Adam7 pass number 1 to 7; 0 without interlace */
+};
+int lars_png_out_format(int depth, int color_type, int *channels, int *itemsize);
+int lars_png_layout(int64_t w, int64_t h, int depth, int color_type, int interlace, int64_t passes[7 * LARS_PNGX_PASS_N],
+                    int64_t *npass, int64_t *need);
+size_t lars_png_decode_ex_scratch_bytes(int64_t h, int64_t w, int depth, int color_type, int interlace, int64_t idat_bytes,
+                                        int64_t idat_count);
+int lars_d_decode_png_ex(const uint8_t *file, const int64_t *idat_table, int64_t idat_count, int64_t idat_bytes, int64_t h,
+                         int64_t w, int depth, int color_type, int interlace, uint8_t *out, int32_t *status_dev, void *scratch,
+                         void *stream);
+int lars_h_decode_png_ex(const uint8_t *file, int64_t len, uint8_t *out, size_t out_cap);
+int lars_h_thumbnail_png_ex(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
+                            int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out);
+
 /* Baseline JPEG files decoded on the device -- the same Image.open(io.BytesIO(img_bytes)) + np.array(img) of
  * load_image_from_db (process-images.py:181-193) for the format the cameras write, and the thumbnail after it.
  * Covered: SOF0 / SOF1 (Huffman, 8 bit), one interleaved scan, one component (L, [h][w]) or YCbCr at 4:4:4, 4:2:2 or 4:2:0

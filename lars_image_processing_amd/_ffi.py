@@ -231,6 +231,12 @@ SIGNATURES = {
     "lars_d_decode_png_u8": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I, _P, _P, _P, _P]),
     "lars_h_decode_png_u8": (_I, [_P, _I64, _P, _SZ]),
     "lars_h_thumbnail_png_u8": (_I, [_P, _I64, _I, _I, C.POINTER(_I), C.POINTER(_F), _I64, _I64, _I, _P]),
+    "lars_png_out_format": (_I, [_I, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "lars_png_layout": (_I, [_I64, _I64, _I, _I, _I, _P, C.POINTER(_I64), C.POINTER(_I64)]),
+    "lars_png_decode_ex_scratch_bytes": (_SZ, [_I64, _I64, _I, _I, _I, _I64, _I64]),
+    "lars_d_decode_png_ex": (_I, [_P, _P, _I64, _I64, _I64, _I64, _I, _I, _I, _P, _P, _P, _P]),
+    "lars_h_decode_png_ex": (_I, [_P, _I64, _P, _SZ]),
+    "lars_h_thumbnail_png_ex": (_I, [_P, _I64, _I, _I, C.POINTER(_I), C.POINTER(_F), _I64, _I64, _I, _P]),
     "lars_jpeg_info": (_I, [_P, _I64, _P]),
     "lars_jpeg_decode_scratch_bytes": (_SZ, [_P]),
     "lars_d_decode_jpeg_u8": (_I, [_P, _P, _P, _P, _P, _P, _P]),

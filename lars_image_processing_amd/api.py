@@ -789,23 +789,56 @@ def _png_info(arr):
     return _ffi.PngInfo(*info)
 
 
-def png_info(data):
+def _png_out_format(i):
+    """``(dtype, shape)`` of the array the extended decoder gives for the IHDR numbers ``i`` (``lars_png_out_format``, pure
+    host code): Pillow's ``np.asarray`` of the file."""
+    channels, itemsize = C.c_int(0), C.c_int(0)
+    lib = _ffi.load()
+    if lib.lars_png_out_format(i.bit_depth, i.color_type, C.byref(channels), C.byref(itemsize)) != 0:
+        raise ValueError(lib.lars_last_error().decode("utf-8", "replace"))
+    dtype = np.dtype(np.uint16) if itemsize.value == 2 else np.dtype(bool) if (i.bit_depth, i.color_type) == (1, 0) else np.dtype(np.uint8)
+    return dtype, (i.height, i.width) if channels.value == 1 else (i.height, i.width, channels.value)
+
+
+def _png_need(i):
+    """Filtered bytes of all passes (``lars_png_layout``, pure host code)."""
+    passes = (C.c_int64 * 70)()
+    npass, need = C.c_int64(0), C.c_int64(0)
+    lib = _ffi.load()
+    if lib.lars_png_layout(i.width, i.height, i.bit_depth, i.color_type, i.interlace, passes, C.byref(npass), C.byref(need)) != 0:
+        raise ValueError(lib.lars_last_error().decode("utf-8", "replace"))
+    return need.value
+
+
+def png_info(data, extended=False):
     """The chunk layout of a PNG file, validated on the host (``lars_png_info``; no device needed).
 
     Returns ``width``, ``height``, ``bit_depth``, ``color_type``, ``interlace``, ``mode`` (Pillow's name for it),
     ``channels``, ``idat_bytes`` and ``supported`` (what ``decode_png`` decodes: bit depth 8, no interlace, not APNG).
+    ``extended=True``: ``supported`` is what ``decode_png(data, extended=True)`` decodes -- every valid IHDR combination
+    that is not APNG -- and the dict gains ``dtype`` and ``shape`` of the array that call returns.
     Raises ``ValueError`` for structural damage: bad signature, missing or misplaced IHDR / IDAT / IEND, a chunk running
     past the end of the file, a bad CRC in a chunk other than IDAT (IDAT CRCs are checked where they are gathered).
     """
     i = _png_info(_file_bytes(data, "png_info", "PNG"))
-    return {"width": i.width, "height": i.height, "bit_depth": i.bit_depth, "color_type": i.color_type, "interlace": i.interlace,
-            "mode": _PNG_MODES[(i.bit_depth, i.color_type)], "channels": i.channels, "idat_bytes": i.idat_bytes,
-            "supported": bool(i.supported)}
+    out = {"width": i.width, "height": i.height, "bit_depth": i.bit_depth, "color_type": i.color_type, "interlace": i.interlace,
+           "mode": _PNG_MODES[(i.bit_depth, i.color_type)], "channels": i.channels, "idat_bytes": i.idat_bytes,
+           "supported": bool(i.supported)}
+    if extended:
+        out["supported"] = not i.apng
+        out["dtype"], out["shape"] = _png_out_format(i)
+    return out
 
 
-def _png_check(arr, who):
+def _png_check(arr, who, extended=False):
     i = _png_info(arr)
     w, h, ctype, channels = i.width, i.height, i.color_type, i.channels
+    if extended:
+        if i.apng:
+            raise NotImplementedError(f"{who}: APNG PNG files are not supported")
+        if not (1 <= h <= 1 << 24 and 1 <= w <= 1 << 24) or _png_need(i) > (1 << 31) - 1:
+            raise ValueError(f"{who}: {w} x {h} picture of {channels} channels at bit depth {i.bit_depth} is too large")
+        return i
     if not i.supported:
         what = "APNG" if i.apng else "interlaced" if i.interlace else f"bit depth {i.bit_depth}"
         raise NotImplementedError(f"{who}: {what} PNG files are not supported (8-bit, non-interlaced only)")
@@ -814,7 +847,7 @@ def _png_check(arr, who):
     return h, w, ctype, channels
 
 
-def decode_png(data):
+def decode_png(data, extended=False):
     """``np.asarray(Image.open(io.BytesIO(data)))`` of a PNG file, decoded on the GPU (process-images.py:181-193).
 
     ``data``: the whole file as ``bytes``, ``bytearray``, ``memoryview`` or a 1-D uint8 array.  Bit depth 8, no interlace,
@@ -825,21 +858,47 @@ def decode_png(data):
     needs (Pillow ignores the extra data) has the extra bytes dropped, not stored -- they could be up to 1032 times the
     compressed size -- so the Adler-32 over the whole stream cannot be formed, and that trailer is not checked.  Limits: 1 <= h, w <= 2^24 and
     ``h * (1 + w * channels) < 2^31``.  No CPU fallback.
+
+    ``extended=True`` also decodes bit depths 1, 2, 4 and 16 and Adam7-interlaced files, every valid IHDR combination that
+    is not APNG, to the array Pillow gives: ``bool`` for 1-bit gray, ``uint8`` samples times 85 / 17 for 2- / 4-bit gray,
+    native-endian ``uint16`` for 16-bit gray (mode ``I;16``), the unscaled indices for palettes of any depth, the high
+    byte of every sample for 16-bit RGB / RGBA, and ``[H, W, 4]`` = L, L, L, A of the high bytes for 16-bit LA (Pillow
+    opens it as RGBA).  Interlace changes nothing in the result.  The limit is then on the filtered bytes of all passes,
+    which must stay below 2^31; a bad filter byte is reported with its pass.
     """
     arr = _file_bytes(data, "decode_png", "PNG")
+    if extended:
+        i = _png_check(arr, "decode_png", True)
+        dtype, shape = _png_out_format(i)
+        out = np.empty(shape, dtype=np.uint8 if dtype == np.dtype(bool) else dtype)
+        _file_call("lars_h_decode_png_ex", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
+        return out.view(dtype)
     h, w, _ctype, c = _png_check(arr, "decode_png")
     out = np.empty((h, w) if c == 1 else (h, w, c), dtype=np.uint8)
     _file_call("lars_h_decode_png_u8", _ffi.ptr(arr), arr.size, _ffi.ptr(out), out.nbytes)
     return out
 
 
-def thumbnail_png(data, size=(400, 400), reducing_gap=2.0):
+def thumbnail_png(data, size=(400, 400), reducing_gap=2.0, extended=False):
     """``np.asarray`` of ``Image.open(io.BytesIO(data))`` after ``.thumbnail(size, LANCZOS, reducing_gap)``, bit for bit
     (process-images.py:186-189), from the file's bytes: the decoded pixels stay on the GPU and go straight into the
     thumbnail kernels, only the thumbnail comes back.  Modes L, RGB and RGBA; others raise ``TypeError`` as ``thumbnail``
     does.  ``draft`` does nothing for PNG, so ``thumbnail_plan(..., draft_box=None)`` is the whole plan; a file that
-    already fits comes back as ``decode_png`` gives it.  Errors of the file as ``decode_png``."""
+    already fits comes back as ``decode_png`` gives it.  Errors of the file as ``decode_png``.
+
+    ``extended=True`` takes every file ``decode_png(data, extended=True)`` decodes whose Pillow mode is L, RGB or RGBA: 2- and
+    4-bit gray, 16-bit RGB / LA / RGBA, and the interlaced ones.  Modes ``1``, ``I;16``, ``P`` and ``LA`` raise ``TypeError``."""
     arr = _file_bytes(data, "thumbnail_png", "PNG")
+    if extended:
+        i = _png_check(arr, "thumbnail_png", True)
+        mode = _PNG_MODES[(i.bit_depth, i.color_type)]
+        if mode not in ("L", "RGB", "RGBA"):
+            raise TypeError(f"thumbnail_png: PNG files in mode L, RGB or RGBA (got mode {mode!r})")
+        c = {"L": 1, "RGB": 3, "RGBA": 4}[mode]
+        plan = thumbnail_plan((i.width, i.height), size, reducing_gap, None, None, rgba=c == 4)
+        if plan is None:
+            return decode_png(arr, extended=True)
+        return _file_thumbnail("lars_h_thumbnail_png_ex", arr, plan, c)
     h, w, ctype, c = _png_check(arr, "thumbnail_png")
     if ctype not in (0, 2, 6):
         raise TypeError(f"thumbnail_png: PNG files in mode L, RGB or RGBA (got mode {_PNG_MODES[(8, ctype)]!r})")

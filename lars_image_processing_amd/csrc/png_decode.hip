@@ -1,4 +1,4 @@
-// PNG decoding of 8-bit, non-interlaced pictures on the device.
+// PNG decoding on the device: 8-bit, non-interlaced pictures, and behind a switch every other bit depth and Adam7 interlace.
 //
 // Reference: load_image_from_db (process-images.py:181-193) opens every stored picture with Image.open(io.BytesIO(...))
 // and np.array(img) or img.thumbnail(...): zlib's inflate and libpng-style unfiltering on one host core.  Here the
@@ -31,6 +31,13 @@
 //                    i - 1 one step earlier (__shfl_up), the upper-left bytes are the previous ones.  The waves take 64-row
 //                    groups in turn; a group waits for the tile above it with a bounded LDS spin (workgroup-scope acquire /
 //                    release), never across workgroups.  k_pd_rows drops the padding.
+// The extended decoder (lars_d_decode_png_ex: bit depths 1, 2, 4 and 16, Adam7 interlace) shares everything up to k_pd_jump:
+// an interlaced file is still one zlib stream.  After it, the layout of the stream comes from lars_png_layout (png_parse.cpp):
+//   k_pdx_resolve    as k_pd_resolve, each pass into its own block of padded rows and its own stretch of filter bytes.
+//   k_pdx_unfilter   one workgroup per non-empty pass, each with k_pd_unfilter's wavefront and a 64-bit history (bpp to 8).
+//   k_pdx_place      one thread per output pixel, along output rows: unpack 1 / 2 / 4 / 8 / 16-bit samples, scale, swap or
+//                    narrow them as Pillow does, write to (y0 + r * dy, x0 + c * dx).
+// An 8-bit file without interlace takes the kernels above, unchanged, through either entry point.
 // Every error is a status code (LARS_PNGD_*) in device memory; every kernel after a failing one returns at once.
 #include <string.h>
 
@@ -781,6 +788,215 @@ __global__ __launch_bounds__(256) void k_pd_rows(const uint8_t *__restrict__ opa
     }
 }
 
+// ---- the extended decoder: rows per pass, any bit depth --------------------------------------------------------------
+// What the kernels after the stream know of a file, passed by value.  Every pass has its own block of 16-byte-padded rows
+// in fpad / opad (pad_base) and its own stretch of filter bytes (row_base).
+struct PdxPass {
+    unsigned int off, rb, rbp, ph;      // first stream byte, row bytes, padded row bytes, rows
+    unsigned int x0, y0, ldx, ldy;      // first column and row, log2 of the column and row step
+    unsigned long long pad_base, row_base;
+    int index;                          // Adam7 pass number 1..7, 0 without interlace
+    unsigned int pw;                    // columns
+};
+#define PDX_SUB 0                       // 1, 2, 4 bits: one byte per sample, times mult
+#define PDX_BYTES 1                     // 8 bits: the pixel's bytes
+#define PDX_GRAY16 2                    // native-endian uint16
+#define PDX_HIGH 3                      // 16 bits: the high byte of every sample
+#define PDX_LA16 4                      // 16-bit LA: L, L, L, A of the high bytes
+struct PdxDev {
+    int npass, interlace, depth, inc;   // inc: samples per pixel in the file
+    int kind, mult, bpp, pad_;
+    int slot[8];                        // Adam7 pass number -> position in p, -1 for an empty pass
+    PdxPass p[7];
+};
+
+// k_pd_resolve with rows of a length per pass: each thread finds the pass, row and column of its first byte once and
+// steps from there
+__global__ __launch_bounds__(256) void k_pdx_resolve(const uint8_t *__restrict__ lit, const int *__restrict__ src, long long n,
+                                                     const PdxDev D, uint8_t *__restrict__ fpad, uint8_t *__restrict__ ftype,
+                                                     unsigned long long *__restrict__ parts, PdCtl *ctl)
+{
+    __shared__ unsigned long long r1[256], r2[256];
+    if (pd_failed(ctl)) return;
+    const long long lo = ((long long)blockIdx.x * 256 + threadIdx.x) * PD_RESOLVE_BYTES, hi = min(n, lo + PD_RESOLVE_BYTES);
+    unsigned long long s1 = 0, s2 = 0;
+    if (lo < hi) {
+        int p = 0;
+        while (p + 1 < D.npass && (unsigned int)lo >= D.p[p + 1].off) ++p;
+        PdxPass P = D.p[p];
+        long long end = p + 1 < D.npass ? (long long)D.p[p + 1].off : n;
+        unsigned int r = ((unsigned int)lo - P.off) / (P.rb + 1u), col = ((unsigned int)lo - P.off) - r * (P.rb + 1u);
+        for (long long i = lo; i < hi; ++i) {
+            if (i == end) {
+                ++p;
+                if (p >= D.npass) break;                 // cannot happen: the passes cover [0, n)
+                P = D.p[p];
+                end = p + 1 < D.npass ? (long long)D.p[p + 1].off : n;
+                r = 0; col = 0;
+            }
+            const int s = src[i];
+            unsigned int v;
+            if (s == (int)i) v = lit[i];
+            else if (s >= 0 && (long long)s < i) v = lit[s];
+            else { pd_fail(ctl, LARS_PNGD_INTERNAL, 3); v = 0; }
+            if (r < P.ph) {
+                if (col == 0) ftype[P.row_base + r] = (uint8_t)v;
+                else fpad[P.pad_base + (unsigned long long)r * P.rbp + col - 1] = (uint8_t)v;
+            }
+            if (++col > P.rb) { col = 0; ++r; }
+            s1 += v;
+            s2 += (unsigned long long)(n - i) * v;
+        }
+    }
+    r1[threadIdx.x] = s1 % PD_ADLER_MOD;
+    r2[threadIdx.x] = s2 % PD_ADLER_MOD;
+    __syncthreads();
+    for (int half = 128; half > 0; half >>= 1) {
+        if (threadIdx.x < half) { r1[threadIdx.x] += r1[threadIdx.x + half]; r2[threadIdx.x] += r2[threadIdx.x + half]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { parts[2 * blockIdx.x] = r1[0] % PD_ADLER_MOD; parts[2 * blockIdx.x + 1] = r2[0] % PD_ADLER_MOD; }
+}
+
+// one workgroup per pass: the passes are independent pictures, each unfiltered by k_pd_unfilter's skewed wavefront.  The
+// history of the last bpp bytes of the row and of the row above takes 64 bits here, which reaches bpp 8 (16-bit RGBA); the
+// kernel stands apart from k_pd_unfilter so that the 8-bit decoder compiles as it did.  Waves a small pass has no 64-row
+// group for do nothing; the bounded wait is workgroup-scope as there, and nothing waits across workgroups.  A bad filter
+// byte reports pass << 24 | row within the pass.
+__global__ __launch_bounds__(64 * PD_UNF_WAVES) void k_pdx_unfilter(const uint8_t *__restrict__ fpad, const uint8_t *__restrict__ ftype,
+                                                                    const PdxDev D, uint8_t *__restrict__ opad, PdCtl *ctl)
+{
+    __shared__ unsigned int prog[PD_UNF_WAVES];
+    __shared__ int abort_;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x / 64, nwaves = blockDim.x / 64;
+    if (threadIdx.x < PD_UNF_WAVES) prog[threadIdx.x] = 0;
+    if (threadIdx.x == 0) abort_ = 0;
+    __syncthreads();
+    if (pd_failed(ctl) || (int)blockIdx.x >= D.npass) return;
+    const PdxPass P = D.p[blockIdx.x];
+    const long long h = P.ph, rbp = P.rbp;
+    const int bpp = D.bpp;
+    fpad += P.pad_base; opad += P.pad_base; ftype += P.row_base;
+    const long long nchunk = rbp / 16, ngroups = (h + 63) / 64, tchunks = PD_TILE / 16, ncb = (nchunk + tchunks - 1) / tchunks;
+    const int sh = 8 * (bpp - 1);
+    for (long long g = wave; g < ngroups; g += nwaves) {
+        const long long row = g * 64 + lane;
+        const bool active = row < h;
+        int f = active ? ftype[row] : 0;
+        if (f > 4) { pd_fail(ctl, LARS_PNGD_FILTER, P.index << 24 | (int)min(row, 0xFFFFFFll)); f = 0; }
+        const uint4 *xrow = reinterpret_cast<const uint4 *>(fpad + row * rbp);
+        uint4 *orow = reinterpret_cast<uint4 *>(opad + row * rbp);
+        const uint4 *uprow = reinterpret_cast<const uint4 *>(opad + (row - 1) * rbp);
+        unsigned long long ha = 0, hc = 0;
+        uint4 prev = make_uint4(0u, 0u, 0u, 0u);
+        for (long long cb = 0; cb < ncb; ++cb) {
+            if (g > 0) {
+                // the tile above: group g - 1, tile cb, finished by wave (g - 1) % nwaves
+                const unsigned int want = (unsigned int)((g - 1) * ncb + cb + 1);
+                const unsigned int *p = &prog[(g - 1) % nwaves];
+                const unsigned long long t0 = wall_clock64();
+                while (__hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < want) {
+                    if (__hip_atomic_load(&abort_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return;
+                    if (wall_clock64() - t0 > PD_WAIT_TICKS) {
+                        if (lane == 0) {
+                            pd_fail(ctl, LARS_PNGD_INTERNAL, 4);
+                            __hip_atomic_store(&abort_, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        }
+                        return;
+                    }
+                    __builtin_amdgcn_s_sleep(2);
+                }
+            }
+            const long long k0 = cb * tchunks, k1 = min(nchunk, k0 + tchunks);
+            const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+            // loads run PD_AHEAD steps ahead of their use (a ring of registers, indexed by constants after unrolling)
+            uint4 xr[PD_AHEAD], ur[PD_AHEAD];
+#pragma unroll
+            for (int q = 0; q < PD_AHEAD; ++q) {
+                const long long kq = k0 + q - lane;
+                const bool vq = active && kq >= k0 && kq < k1;
+                xr[q] = vq ? xrow[kq] : zero;
+                ur[q] = (vq && lane == 0 && row > 0) ? uprow[kq] : zero;
+            }
+            const long long steps = (k1 - k0) + 63;
+            for (long long t = 0; t < steps; t += PD_AHEAD) {
+#pragma unroll
+                for (int q = 0; q < PD_AHEAD; ++q) {
+                    const long long k = k0 + t + q - lane;
+                    const bool v = active && k >= k0 && k < k1;
+                    const uint4 x = xr[q], u0 = ur[q];
+                    const long long kf = k + PD_AHEAD;
+                    const bool vf = active && kf >= k0 && kf < k1;
+                    xr[q] = vf ? xrow[kf] : zero;
+                    ur[q] = (vf && lane == 0 && row > 0) ? uprow[kf] : zero;
+                    const uint4 fromleft = pd_shfl_up(prev);   // lane - 1's chunk k of the row above, made one step earlier
+                    const uint4 up = lane == 0 ? u0 : fromleft;
+                    if (v) {
+                        unsigned int o[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                        for (int j = 0; j < 16; ++j) {
+                            const unsigned int bb = pd_byte(up, j);
+                            const unsigned int a = (unsigned int)(ha >> sh) & 255u, c = (unsigned int)(hc >> sh) & 255u;
+                            const unsigned int r = pd_recon(f, pd_byte(x, j), a, bb, c);
+                            ha = (ha << 8) | r;
+                            hc = (hc << 8) | bb;
+                            o[j >> 2] |= r << (8 * (j & 3));
+                        }
+                        prev = make_uint4(o[0], o[1], o[2], o[3]);
+                        orow[k] = prev;
+                    }
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            if (lane == 0) __hip_atomic_store(&prog[wave], (unsigned int)(g * ncb + cb + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+}
+
+// unfiltered pass rows -> the array Pillow gives.  One thread per output pixel, a workgroup along an output row, so the
+// stores of a row are contiguous whatever pass its pixels come from (the odd rows, half the picture, are pass 7 alone and
+// read contiguously too).
+__global__ __launch_bounds__(256) void k_pdx_place(const uint8_t *__restrict__ opad, const PdxDev D, long long h, long long w,
+                                                   uint8_t *__restrict__ out, const PdCtl *ctl)
+{
+    if (pd_failed(ctl)) return;
+    const long long x = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (x >= w) return;
+    for (long long y = blockIdx.y; y < h; y += gridDim.y) {
+        int pn = 0;
+        if (D.interlace) pn = (y & 1) ? 7 : (x & 1) ? 6 : (y & 2) ? 5 : (x & 2) ? 4 : (y & 4) ? 3 : (x & 4) ? 2 : 1;
+        const int slot = D.slot[pn];
+        if (slot < 0 || slot >= D.npass) continue;      // cannot happen: a pass that holds a pixel is not empty
+        const PdxPass P = D.p[slot];
+        const unsigned int r = ((unsigned int)y - P.y0) >> P.ldy, c = ((unsigned int)x - P.x0) >> P.ldx;
+        if (r >= P.ph || c >= P.pw) continue;
+        const uint8_t *row = opad + P.pad_base + (unsigned long long)r * P.rbp;
+        const unsigned long long px = (unsigned long long)y * w + x;
+        switch (D.kind) {
+        case PDX_SUB: {
+            const unsigned int bit = c * D.depth;        // < 2^24 * 4
+            const unsigned int v = (row[bit >> 3] >> (8 - D.depth - (bit & 7u))) & ((1u << D.depth) - 1u);
+            out[px] = (uint8_t)(v * D.mult);
+            break;
+        }
+        case PDX_BYTES:
+            for (int k = 0; k < D.inc; ++k) out[px * D.inc + k] = row[(unsigned long long)c * D.inc + k];
+            break;
+        case PDX_GRAY16:
+            reinterpret_cast<unsigned short *>(out)[px] = (unsigned short)(row[2ull * c] << 8 | row[2ull * c + 1]);
+            break;
+        case PDX_HIGH:
+            for (int k = 0; k < D.inc; ++k) out[px * D.inc + k] = row[2ull * ((unsigned long long)c * D.inc + k)];
+            break;
+        default: {                                       // PDX_LA16
+            const unsigned int l = row[4ull * c], a = row[4ull * c + 2];
+            reinterpret_cast<unsigned int *>(out)[px] = l | l << 8 | l << 16 | a << 24;
+            break;
+        }
+        }
+    }
+}
+
 // sizes and the device scratch of one file: what lars_png_decode_scratch_bytes counts and lars_d_decode_png_u8 points into
 struct PdPlan {
     unsigned long long nbits, nw, nmark, ncap, bcap, need, nparts, rbp, nslot;
@@ -800,10 +1016,10 @@ static bool pd_shape_ok(int64_t h, int64_t w, int channels)
     return (unsigned long long)h * (1ull + (unsigned long long)w * channels) <= 0x7FFFFFFFull;
 }
 
-static PdPlan pd_plan(int64_t h, int64_t w, int channels, int64_t idat_bytes, int64_t idat_count, Carver &cv)
+// the stream's part of a plan: everything up to the resolved bytes, for a filtered stream of `need` bytes
+static void pd_plan_stream(PdPlan &P, unsigned long long need, int64_t idat_bytes, int64_t idat_count, Carver &cv)
 {
-    PdPlan P{};
-    P.need = (unsigned long long)h * (1ull + (unsigned long long)w * channels);
+    P.need = need;
     P.nbits = (unsigned long long)idat_bytes * 8;
     P.nw = (((unsigned long long)idat_bytes + 3) / 4 + 4 + 3) & ~3ull;   // whole quads, at least 4 zero words
     P.nmark = (P.nbits + PD_MARK_THREADS - 1) / PD_MARK_THREADS;
@@ -812,7 +1028,6 @@ static PdPlan pd_plan(int64_t h, int64_t w, int channels, int64_t idat_bytes, in
     P.bcap = std::min(P.nbits / 18, P.need) + 2 + P.need / PD_CK + PD_CKMAX;
     P.nslot = std::min(P.ncap, P.nbits / 4096 + 256);   // candidates that keep checkpoints (the rest: one segment per block)
     P.nparts = (P.need + 256ull * PD_RESOLVE_BYTES - 1) / (256ull * PD_RESOLVE_BYTES);
-    P.rbp = ((unsigned long long)w * channels + 15) & ~15ull;
     P.ctl = cv.take<PdCtl>(1);
     P.off = cv.take<unsigned long long>((size_t)idat_count);
     P.words = cv.take<unsigned int>(P.nw);
@@ -824,10 +1039,74 @@ static PdPlan pd_plan(int64_t h, int64_t w, int channels, int64_t idat_bytes, in
     P.lit = cv.take<uint8_t>(P.need);
     P.src = cv.take<int>(P.need);
     P.parts = cv.take<unsigned long long>(P.nparts * 2);
+}
+
+static PdPlan pd_plan(int64_t h, int64_t w, int channels, int64_t idat_bytes, int64_t idat_count, Carver &cv)
+{
+    PdPlan P{};
+    pd_plan_stream(P, (unsigned long long)h * (1ull + (unsigned long long)w * channels), idat_bytes, idat_count, cv);
+    P.rbp = ((unsigned long long)w * channels + 15) & ~15ull;
     P.fpad = cv.take<uint8_t>((size_t)h * P.rbp);
     P.ftype = cv.take<uint8_t>((size_t)h);
     P.opad = cv.take<uint8_t>((size_t)h * P.rbp);
     return P;
+}
+
+// the extended decoder's plan: the layout of the file (lars_png_layout) as the kernels take it, and the scratch
+struct PdxPlan {
+    PdPlan P;
+    PdxDev D;
+    unsigned long long pad_bytes, rows;  // all passes: padded row bytes, rows
+    long long max_groups;                // 64-row groups of the tallest pass
+    int channels, itemsize;              // of the array
+    bool plain;                          // 8 bits, no interlace: lars_d_decode_png_u8's path
+};
+
+static bool pdx_layout(int64_t h, int64_t w, int depth, int ctype, int interlace, PdxPlan &X)
+{
+    int64_t passes[7 * LARS_PNGX_PASS_N], npass = 0, need = 0;
+    if (h < 1 || w < 1 || h > (1 << 24) || w > (1 << 24)) return false;
+    if (lars_png_out_format(depth, ctype, &X.channels, &X.itemsize) != LARS_OK) return false;
+    if (lars_png_layout(w, h, depth, ctype, interlace, passes, &npass, &need) != LARS_OK) return false;
+    if (npass < 1 || npass > 7 || need < 1 || need > 0x7FFFFFFFll) return false;
+    PdxDev &D = X.D;
+    memset(&D, 0, sizeof D);
+    static const int chans[7] = {1, 0, 3, 1, 2, 0, 4};
+    D.npass = (int)npass; D.interlace = interlace; D.depth = depth; D.inc = chans[ctype];
+    D.kind = depth < 8 ? PDX_SUB : depth == 8 ? PDX_BYTES : ctype == 0 ? PDX_GRAY16 : ctype == 4 ? PDX_LA16 : PDX_HIGH;
+    D.mult = (ctype == 0 && depth > 1 && depth < 8) ? 255 / ((1 << depth) - 1) : 1;
+    for (int k = 0; k < 8; ++k) D.slot[k] = -1;
+    X.pad_bytes = 0; X.rows = 0; X.max_groups = 0;
+    for (int k = 0; k < D.npass; ++k) {
+        const int64_t *q = passes + k * LARS_PNGX_PASS_N;
+        PdxPass &p = D.p[k];
+        p.off = (unsigned int)q[LARS_PNGX_PASS_OFFSET];
+        p.rb = (unsigned int)q[LARS_PNGX_PASS_ROW_BYTES];
+        p.rbp = (p.rb + 15u) & ~15u;
+        p.ph = (unsigned int)q[LARS_PNGX_PASS_H]; p.pw = (unsigned int)q[LARS_PNGX_PASS_W];
+        p.x0 = (unsigned int)q[LARS_PNGX_PASS_X0]; p.y0 = (unsigned int)q[LARS_PNGX_PASS_Y0];
+        p.ldx = 0; p.ldy = 0;
+        while ((1ll << p.ldx) < q[LARS_PNGX_PASS_DX]) ++p.ldx;
+        while ((1ll << p.ldy) < q[LARS_PNGX_PASS_DY]) ++p.ldy;
+        p.pad_base = X.pad_bytes; p.row_base = X.rows;
+        p.index = (int)q[LARS_PNGX_PASS_INDEX];
+        D.bpp = (int)q[LARS_PNGX_PASS_BPP];
+        D.slot[p.index] = k;
+        X.pad_bytes += (unsigned long long)p.ph * p.rbp;
+        X.rows += p.ph;
+        X.max_groups = std::max<long long>(X.max_groups, ((long long)p.ph + 63) / 64);
+    }
+    X.P.need = (unsigned long long)need;
+    X.plain = depth == 8 && !interlace;
+    return true;
+}
+
+static void pdx_plan(PdxPlan &X, int64_t idat_bytes, int64_t idat_count, Carver &cv)
+{
+    pd_plan_stream(X.P, X.P.need, idat_bytes, idat_count, cv);
+    X.P.fpad = cv.take<uint8_t>((size_t)X.pad_bytes);
+    X.P.ftype = cv.take<uint8_t>((size_t)X.rows);
+    X.P.opad = cv.take<uint8_t>((size_t)X.pad_bytes);
 }
 
 static const char *pd_deflate_what(int d)
@@ -843,7 +1122,7 @@ static const char *pd_deflate_what(int d)
 }
 
 // the message of a device status
-static int pd_status_fail(const char *who, const int st[2])
+static int pd_status_fail(const char *who, const int st[2], bool ex = false)
 {
     switch (st[0]) {
     case LARS_PNGD_CRC: return fail(LARS_ERR_INVALID, "%s: bad CRC in IDAT chunk %d", who, st[1]);
@@ -853,7 +1132,9 @@ static int pd_status_fail(const char *who, const int st[2])
     case LARS_PNGD_FAR: return fail(LARS_ERR_INVALID, "%s: deflate error: copy distance too far back (block at output byte %d)", who, st[1]);
     case LARS_PNGD_SHORT: return fail(LARS_ERR_INVALID, "%s: too few decoded bytes (%d)", who, st[1]);
     case LARS_PNGD_ADLER: return fail(LARS_ERR_INVALID, "%s: Adler-32 mismatch", who);
-    case LARS_PNGD_FILTER: return fail(LARS_ERR_INVALID, "%s: bad filter byte in row %d", who, st[1]);
+    case LARS_PNGD_FILTER:
+        if (ex && (st[1] >> 24)) return fail(LARS_ERR_INVALID, "%s: bad filter byte in row %d of pass %d", who, st[1] & 0xFFFFFF, st[1] >> 24);
+        return fail(LARS_ERR_INVALID, "%s: bad filter byte in row %d", who, ex ? st[1] & 0xFFFFFF : st[1]);
     default: return fail(LARS_ERR_HIP, "%s: internal decoder status %d (%d)", who, st[0], st[1]);
     }
 }
@@ -861,25 +1142,37 @@ static int pd_status_fail(const char *who, const int st[2])
 // the PNG side of the host entry points (codec_host.h)
 struct PdFile : HostFile {
     int64_t ctype, idat_bytes, nidat;
+    int depth, interlace;
+    bool ex;                                              // the extended decoder: every IHDR combination but APNG
     std::vector<int64_t> table;
 
     // parse + checks shared by the host entry points
-    int parse(const char *who_, const uint8_t *file_, int64_t len_)
+    int parse(const char *who_, const uint8_t *file_, int64_t len_, bool ex_ = false)
     {
-        who = who_; file = file_; len = len_;
+        who = who_; file = file_; len = len_; ex = ex_;
         if (!file || len <= 0) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
         int64_t info[LARS_PNG_INFO_N];
         LARS_TRY(lars_png_info(file, len, info, nullptr, 0));
         h = info[LARS_PNG_INFO_HEIGHT]; w = info[LARS_PNG_INFO_WIDTH]; channels = (int)info[LARS_PNG_INFO_CHANNELS];
         ctype = info[LARS_PNG_INFO_COLOR_TYPE]; idat_bytes = info[LARS_PNG_INFO_IDAT_BYTES]; nidat = info[LARS_PNG_INFO_IDAT_COUNT];
-        const long long depth = info[LARS_PNG_INFO_BIT_DEPTH], interlace = info[LARS_PNG_INFO_INTERLACE];
-        if (!info[LARS_PNG_INFO_SUPPORTED])
+        const long long d = info[LARS_PNG_INFO_BIT_DEPTH], il = info[LARS_PNG_INFO_INTERLACE];
+        depth = (int)d; interlace = (int)il;
+        if (ex ? info[LARS_PNG_INFO_APNG] != 0 : !info[LARS_PNG_INFO_SUPPORTED])
             return fail(LARS_ERR_UNSUPPORTED, "%s: %s PNG (bit depth %lld, interlace %lld) is not supported", who,
-                        info[LARS_PNG_INFO_APNG] ? "APNG" : interlace ? "interlaced" : "this", depth, interlace);
-        if (!pd_shape_ok(h, w, channels))
-            return fail(LARS_ERR_INVALID, "%s: %lld x %lld x %lld picture is too large", who, (long long)h, (long long)w, (long long)channels);
+                        info[LARS_PNG_INFO_APNG] ? "APNG" : il ? "interlaced" : "this", d, il);
+        if (ex) {
+            PdxPlan X{};
+            if (!pdx_layout(h, w, depth, (int)ctype, interlace, X))
+                return fail(LARS_ERR_INVALID, "%s: %lld x %lld picture (bit depth %lld, colour type %lld) is too large", who, (long long)h,
+                            (long long)w, d, (long long)ctype);
+            channels = X.channels; sample_bytes = X.itemsize;
+            scratch_bytes = lars_png_decode_ex_scratch_bytes(h, w, depth, (int)ctype, interlace, idat_bytes, nidat);
+        } else {
+            if (!pd_shape_ok(h, w, channels))
+                return fail(LARS_ERR_INVALID, "%s: %lld x %lld x %lld picture is too large", who, (long long)h, (long long)w, (long long)channels);
+            scratch_bytes = lars_png_decode_scratch_bytes(h, w, channels, idat_bytes, nidat);
+        }
         extra_bytes = (size_t)nidat * 16;                 // the IDAT table
-        scratch_bytes = lars_png_decode_scratch_bytes(h, w, channels, idat_bytes, nidat);
         table.assign((size_t)nidat * 2, 0);
         return lars_png_info(file, len, info, table.data(), nidat);
     }
@@ -887,10 +1180,34 @@ struct PdFile : HostFile {
     {
         int64_t *d_tab = static_cast<int64_t *>(d_extra);
         LARS_HIP_TRY(hipMemcpyAsync(d_tab, table.data(), extra_bytes, hipMemcpyHostToDevice, s));
+        if (ex) return lars_d_decode_png_ex(d_file, d_tab, nidat, idat_bytes, h, w, depth, (int)ctype, interlace, d_img, d_status, d_scratch, s);
         return lars_d_decode_png_u8(d_file, d_tab, nidat, idat_bytes, h, w, channels, d_img, d_status, d_scratch, s);
     }
-    int finish(const int st[2]) { return st[0] ? pd_status_fail(who, st) : LARS_OK; }
+    int finish(const int st[2]) { return st[0] ? pd_status_fail(who, st, ex && !(depth == 8 && !interlace)) : LARS_OK; }
 };
+
+// the stream's kernels, shared by both decoders: IDAT payloads to the stream's bytes and the source index of each
+static void pd_enqueue_stream(const PdPlan &P, const uint8_t *file, const int64_t *idat_table, int64_t idat_count, hipStream_t s)
+{
+    PdCtl *ctl = P.ctl;
+    const long long *tab = reinterpret_cast<const long long *>(idat_table);
+    hipLaunchKernelGGL(k_pd_chunk_scan, dim3(1), dim3(1024), 0, s, tab, (long long)idat_count, P.off);
+    hipLaunchKernelGGL(k_pd_gather, dim3((unsigned)std::min<int64_t>(idat_count, 4096)), dim3(PD_GATHER_THREADS), 0, s, file, tab,
+                       (long long)idat_count, P.off, reinterpret_cast<uint8_t *>(P.words), ctl);
+    if (P.nmark) {
+        hipLaunchKernelGGL(k_pd_mark, dim3((unsigned)P.nmark), dim3(PD_MARK_THREADS), 0, s, P.words, P.nw, P.nbits, P.masks, P.wgcnt, ctl);
+        hipLaunchKernelGGL(k_pd_scan_u32, dim3(1), dim3(1024), 0, s, P.wgcnt, (long long)P.nmark, (unsigned int)P.ncap, ctl);
+        hipLaunchKernelGGL(k_pd_compact, dim3((unsigned)P.nmark), dim3(PD_MARK_THREADS), 0, s, P.masks, P.wgcnt, (unsigned int)P.ncap, P.cands);
+        hipLaunchKernelGGL(k_pd_pass_a, dim3(4096), dim3(64), 0, s, P.words, P.nw, P.nbits, P.cands, P.checks, (unsigned int)P.nslot, ctl);
+    }
+    hipLaunchKernelGGL(k_pd_walk, dim3(1), dim3(64), 0, s, P.words, P.nw, P.nbits, P.cands, P.checks, (unsigned int)P.nslot, P.blocks,
+                       (unsigned int)P.bcap, P.need, ctl);
+    hipLaunchKernelGGL(k_pd_pass_b, dim3(4096), dim3(64), 0, s, P.words, P.nw, P.nbits, P.blocks, P.need, P.lit, P.src, ctl);
+    int rounds = 1;
+    while ((1ull << (rounds - 1)) < P.need && rounds < 64) ++rounds;
+    const unsigned jgrid = (unsigned)std::min<unsigned long long>((P.need + 255) / 256, 16384);
+    for (int r = 0; r < rounds; ++r) hipLaunchKernelGGL(k_pd_jump, dim3(jgrid), dim3(256), 0, s, P.src, (long long)P.need, r, ctl);
+}
 
 }  // namespace lars
 
@@ -921,25 +1238,9 @@ int lars_d_decode_png_u8(const uint8_t *file, const int64_t *idat_table, int64_t
         return fail(LARS_ERR_UNSUPPORTED, "lars_d_decode_png_u8: %lld IDAT bytes", (long long)idat_bytes);
     PdCtl *ctl = P.ctl;
     hipStream_t s = pick_stream(c, stream);
-    const long long *tab = reinterpret_cast<const long long *>(idat_table);
     LARS_HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(PdCtl), s));
     LARS_HIP_TRY(hipMemsetAsync(reinterpret_cast<char *>(P.words) + idat_bytes, 0, P.nw * 4 - (size_t)idat_bytes, s));   // zero tail
-    hipLaunchKernelGGL(k_pd_chunk_scan, dim3(1), dim3(1024), 0, s, tab, (long long)idat_count, P.off);
-    hipLaunchKernelGGL(k_pd_gather, dim3((unsigned)std::min<int64_t>(idat_count, 4096)), dim3(PD_GATHER_THREADS), 0, s, file, tab,
-                       (long long)idat_count, P.off, reinterpret_cast<uint8_t *>(P.words), ctl);
-    if (P.nmark) {
-        hipLaunchKernelGGL(k_pd_mark, dim3((unsigned)P.nmark), dim3(PD_MARK_THREADS), 0, s, P.words, P.nw, P.nbits, P.masks, P.wgcnt, ctl);
-        hipLaunchKernelGGL(k_pd_scan_u32, dim3(1), dim3(1024), 0, s, P.wgcnt, (long long)P.nmark, (unsigned int)P.ncap, ctl);
-        hipLaunchKernelGGL(k_pd_compact, dim3((unsigned)P.nmark), dim3(PD_MARK_THREADS), 0, s, P.masks, P.wgcnt, (unsigned int)P.ncap, P.cands);
-        hipLaunchKernelGGL(k_pd_pass_a, dim3(4096), dim3(64), 0, s, P.words, P.nw, P.nbits, P.cands, P.checks, (unsigned int)P.nslot, ctl);
-    }
-    hipLaunchKernelGGL(k_pd_walk, dim3(1), dim3(64), 0, s, P.words, P.nw, P.nbits, P.cands, P.checks, (unsigned int)P.nslot, P.blocks,
-                       (unsigned int)P.bcap, P.need, ctl);
-    hipLaunchKernelGGL(k_pd_pass_b, dim3(4096), dim3(64), 0, s, P.words, P.nw, P.nbits, P.blocks, P.need, P.lit, P.src, ctl);
-    int rounds = 1;
-    while ((1ull << (rounds - 1)) < P.need && rounds < 64) ++rounds;
-    const unsigned jgrid = (unsigned)std::min<unsigned long long>((P.need + 255) / 256, 16384);
-    for (int r = 0; r < rounds; ++r) hipLaunchKernelGGL(k_pd_jump, dim3(jgrid), dim3(256), 0, s, P.src, (long long)P.need, r, ctl);
+    pd_enqueue_stream(P, file, idat_table, idat_count, s);
     const long long rb = (long long)w * channels;
     if ((unsigned long long)rb != P.rbp) LARS_HIP_TRY(hipMemsetAsync(P.fpad, 0, (size_t)h * P.rbp, s));   // zero padding columns
     hipLaunchKernelGGL(k_pd_resolve, dim3((unsigned)P.nparts), dim3(256), 0, s, P.lit, P.src, (long long)P.need, (unsigned int)rb,
@@ -953,6 +1254,54 @@ int lars_d_decode_png_u8(const uint8_t *file, const int64_t *idat_table, int64_t
     hipLaunchKernelGGL(k_pd_rows, dim3(rgrid), dim3(256), 0, s, P.opad, (long long)h, rb, (long long)P.rbp, out, ctl);
     LARS_HIP_TRY(hipMemcpyAsync(status_dev, ctl->status, 8, hipMemcpyDeviceToDevice, s));
     return launch_check("lars_d_decode_png_u8");
+}
+
+size_t lars_png_decode_ex_scratch_bytes(int64_t h, int64_t w, int depth, int color_type, int interlace, int64_t idat_bytes, int64_t idat_count)
+{
+    PdxPlan X{};
+    if (idat_bytes < 0 || idat_count < 1 || idat_bytes > (1ll << 40) || !pdx_layout(h, w, depth, color_type, interlace, X)) return 0;
+    if (X.plain) return lars_png_decode_scratch_bytes(h, w, X.D.inc, idat_bytes, idat_count);
+    Carver size(nullptr);
+    pdx_plan(X, idat_bytes, idat_count, size);
+    return size.bytes();
+}
+
+int lars_d_decode_png_ex(const uint8_t *file, const int64_t *idat_table, int64_t idat_count, int64_t idat_bytes, int64_t h, int64_t w,
+                         int depth, int color_type, int interlace, uint8_t *out, int32_t *status_dev, void *scratch, void *stream)
+{
+    static const char *who = "lars_d_decode_png_ex";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!file || !idat_table || !out || !status_dev || !scratch || idat_count < 1 || idat_bytes < 0 || idat_bytes > (1ll << 40))
+        return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    PdxPlan X{};
+    if (!pdx_layout(h, w, depth, color_type, interlace, X))
+        return fail(LARS_ERR_INVALID, "%s: %lld x %lld picture, bit depth %d, colour type %d, interlace %d", who, (long long)h, (long long)w,
+                    depth, color_type, interlace);
+    if (X.plain) return lars_d_decode_png_u8(file, idat_table, idat_count, idat_bytes, h, w, X.D.inc, out, status_dev, scratch, stream);
+    if ((X.D.kind == PDX_GRAY16 && (uintptr_t)out % 2) || (X.D.kind == PDX_LA16 && (uintptr_t)out % 4))
+        return fail(LARS_ERR_INVALID, "%s: out must be aligned to its %d-byte pixels", who, X.channels * X.itemsize);
+    Carver cv(scratch);
+    pdx_plan(X, idat_bytes, idat_count, cv);
+    const PdPlan &P = X.P;
+    if (P.nmark >= (1ull << 31) || P.ncap >= (1ull << 32) || P.bcap >= (1ull << 32))
+        return fail(LARS_ERR_UNSUPPORTED, "%s: %lld IDAT bytes", who, (long long)idat_bytes);
+    PdCtl *ctl = P.ctl;
+    hipStream_t s = pick_stream(c, stream);
+    LARS_HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(PdCtl), s));
+    LARS_HIP_TRY(hipMemsetAsync(reinterpret_cast<char *>(P.words) + idat_bytes, 0, P.nw * 4 - (size_t)idat_bytes, s));   // zero tail
+    pd_enqueue_stream(P, file, idat_table, idat_count, s);
+    LARS_HIP_TRY(hipMemsetAsync(P.fpad, 0, (size_t)X.pad_bytes, s));                                                     // zero padding columns
+    hipLaunchKernelGGL(k_pdx_resolve, dim3((unsigned)P.nparts), dim3(256), 0, s, P.lit, P.src, (long long)P.need, X.D, P.fpad, P.ftype,
+                       P.parts, ctl);
+    hipLaunchKernelGGL(k_pd_adler, dim3(1), dim3(256), 0, s, P.parts, (long long)P.nparts, (long long)P.need,
+                       reinterpret_cast<const uint8_t *>(P.words), ctl);
+    const int nwaves = (int)std::min<long long>(X.max_groups, PD_UNF_WAVES);
+    hipLaunchKernelGGL(k_pdx_unfilter, dim3((unsigned)X.D.npass), dim3(64 * nwaves), 0, s, P.fpad, P.ftype, X.D, P.opad, ctl);
+    hipLaunchKernelGGL(k_pdx_place, dim3((unsigned)((w + 255) / 256), (unsigned)std::min<int64_t>(h, 32768)), dim3(256), 0, s, P.opad, X.D,
+                       (long long)h, (long long)w, out, ctl);
+    LARS_HIP_TRY(hipMemcpyAsync(status_dev, ctl->status, 8, hipMemcpyDeviceToDevice, s));
+    return launch_check(who);
 }
 
 // host file in, host pixels out: one upload, the status, one download
@@ -979,6 +1328,32 @@ int lars_h_thumbnail_png_u8(const uint8_t *file, int64_t len, int fx, int fy, co
     LARS_TRY(F.parse(who, file, len));
     if (F.ctype != 0 && F.ctype != 2 && F.ctype != 6)
         return fail(LARS_ERR_UNSUPPORTED, "%s: modes L, RGB and RGBA (colour type %lld)", who, (long long)F.ctype);
+    return thumbnail_file(c, F, fx, fy, reduce_box, box, new_h, new_w, vertical_first, out);
+}
+
+int lars_h_decode_png_ex(const uint8_t *file, int64_t len, uint8_t *out, size_t out_cap)
+{
+    static const char *who = "lars_h_decode_png_ex";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!out) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    PdFile F;
+    LARS_TRY(F.parse(who, file, len, true));
+    return decode_file_to_host(c, F, out, out_cap);
+}
+
+int lars_h_thumbnail_png_ex(const uint8_t *file, int64_t len, int fx, int fy, const int reduce_box[4], const float box[4],
+                            int64_t new_h, int64_t new_w, int vertical_first, uint8_t *out)
+{
+    static const char *who = "lars_h_thumbnail_png_ex";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!out || !reduce_box || !box) return fail(LARS_ERR_INVALID, "%s: bad arguments", who);
+    PdFile F;
+    LARS_TRY(F.parse(who, file, len, true));
+    // Pillow's modes L, RGB and RGBA: not 1 (1-bit gray), I;16, P or LA (8-bit gray + alpha)
+    if (F.sample_bytes != 1 || F.ctype == 3 || (F.ctype == 0 && F.depth == 1) || (F.channels != 1 && F.channels != 3 && F.channels != 4))
+        return fail(LARS_ERR_UNSUPPORTED, "%s: modes L, RGB and RGBA (colour type %lld, bit depth %d)", who, (long long)F.ctype, F.depth);
     return thumbnail_file(c, F, fx, fy, reduce_box, box, new_h, new_w, vertical_first, out);
 }
 

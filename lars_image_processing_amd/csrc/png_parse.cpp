@@ -112,3 +112,65 @@ extern "C" int lars_png_info(const uint8_t *file, int64_t len, int64_t info[LARS
     info[LARS_PNG_INFO_SUPPORTED] = info[LARS_PNG_INFO_BIT_DEPTH] == 8 && info[LARS_PNG_INFO_INTERLACE] == 0 && !apng;
     return LARS_OK;
 }
+
+// ---- the layout of the filtered stream and of the decoded array (extended decoder) ------------------------------------
+namespace {
+
+bool ihdr_pair_ok(int d, int ct)
+{
+    return (ct == 0 && (d == 1 || d == 2 || d == 4 || d == 8 || d == 16)) || (ct == 3 && (d == 1 || d == 2 || d == 4 || d == 8)) ||
+           ((ct == 2 || ct == 4 || ct == 6) && (d == 8 || d == 16));
+}
+
+int file_channels(int ct)
+{
+    static const int chans[7] = {1, 0, 3, 1, 2, 0, 4};
+    return chans[ct];
+}
+
+}  // namespace
+
+extern "C" int lars_png_out_format(int depth, int color_type, int *channels, int *itemsize)
+{
+    if (!channels || !itemsize) return fail(LARS_ERR_INVALID, "lars_png_out_format: bad arguments");
+    if (color_type < 0 || color_type > 6 || !ihdr_pair_ok(depth, color_type))
+        return fail(LARS_ERR_INVALID, "png: bit depth %d with colour type %d", depth, color_type);
+    // Pillow: 16-bit gray stays 16 bits (I;16); 16-bit LA opens as RGBA (L, L, L, A); every other 16-bit sample gives its high
+    // byte; 1 / 2 / 4-bit samples fill a byte each
+    *itemsize = (color_type == 0 && depth == 16) ? 2 : 1;
+    *channels = (color_type == 4 && depth == 16) ? 4 : file_channels(color_type);
+    return LARS_OK;
+}
+
+extern "C" int lars_png_layout(int64_t w, int64_t h, int depth, int color_type, int interlace, int64_t passes[7 * LARS_PNGX_PASS_N],
+                               int64_t *npass, int64_t *need)
+{
+    if (!passes || !npass || !need) return fail(LARS_ERR_INVALID, "lars_png_layout: bad arguments");
+    *npass = 0;
+    *need = 0;
+    if (w < 1 || h < 1 || w > 0x7FFFFFFF || h > 0x7FFFFFFF || interlace < 0 || interlace > 1)
+        return fail(LARS_ERR_INVALID, "png: size %lld x %lld, interlace %d", (long long)w, (long long)h, interlace);
+    if (color_type < 0 || color_type > 6 || !ihdr_pair_ok(depth, color_type))
+        return fail(LARS_ERR_INVALID, "png: bit depth %d with colour type %d", depth, color_type);
+    static const int ax0[7] = {0, 4, 0, 2, 0, 1, 0}, ay0[7] = {0, 0, 4, 0, 2, 0, 1};
+    static const int adx[7] = {8, 8, 4, 4, 2, 2, 1}, ady[7] = {8, 8, 8, 4, 4, 2, 2};
+    const int64_t bits = (int64_t)file_channels(color_type) * depth;     // 1 .. 64 per pixel
+    const int64_t bpp = bits < 8 ? 1 : bits / 8;
+    int64_t n = 0, total = 0;
+    for (int p = 0; p < (interlace ? 7 : 1); ++p) {
+        const int64_t x0 = interlace ? ax0[p] : 0, y0 = interlace ? ay0[p] : 0, dx = interlace ? adx[p] : 1, dy = interlace ? ady[p] : 1;
+        const int64_t pw = (w - x0 + dx - 1) / dx, ph = (h - y0 + dy - 1) / dy;
+        if (pw <= 0 || ph <= 0) continue;                                // an empty pass: no bytes at all
+        const int64_t rb = (pw * bits + 7) / 8;                          // < 2^34
+        int64_t *q = passes + n * LARS_PNGX_PASS_N;
+        q[LARS_PNGX_PASS_X0] = x0; q[LARS_PNGX_PASS_Y0] = y0; q[LARS_PNGX_PASS_DX] = dx; q[LARS_PNGX_PASS_DY] = dy;
+        q[LARS_PNGX_PASS_W] = pw; q[LARS_PNGX_PASS_H] = ph; q[LARS_PNGX_PASS_ROW_BYTES] = rb; q[LARS_PNGX_PASS_OFFSET] = total;
+        q[LARS_PNGX_PASS_BPP] = bpp; q[LARS_PNGX_PASS_INDEX] = interlace ? p + 1 : 0;
+        // ph * (rb + 1) can reach 2^31 * 2^35: saturate, never wrap
+        total = (rb + 1 > INT64_MAX / ph || ph * (rb + 1) > INT64_MAX - total) ? INT64_MAX : total + ph * (rb + 1);
+        ++n;
+    }
+    *npass = n;
+    *need = total;
+    return LARS_OK;
+}

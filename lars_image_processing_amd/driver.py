@@ -26,7 +26,7 @@ EXTENSIONS = {".tif", ".tiff", ".png", ".jpg", ".jpeg"}      # backend-process.p
 # 1.2 s at Pillow's default level 6 and 0.6 s at level 1, for a smaller file on colormap images); same pixels either way
 LUT_PNG_LEVEL = 1
 PNG_ENCODERS = ("pillow", "device")
-PNG_DECODERS = ("pillow", "device")
+PNG_DECODERS = ("pillow", "device", "device+extended")
 JPEG_DECODERS = ("pillow", "device")
 TIFF_DECODERS = ("pillow", "device", "device+deflate")
 TIFF_ENCODERS = ("pillow", "device")
@@ -39,7 +39,7 @@ def _check_png_encoder(png_encoder):
 
 def _check_png_decoder(png_decoder):
     if png_decoder not in PNG_DECODERS:
-        raise ValueError(f"png_decoder must be 'pillow' or 'device', got {png_decoder!r}")
+        raise ValueError(f"png_decoder must be 'pillow', 'device' or 'device+extended', got {png_decoder!r}")
 
 
 def _check_jpeg_decoder(jpeg_decoder):
@@ -68,7 +68,8 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     colormap as the palette): ``Image.open(p).convert("RGBA")`` gives the pixels of the RGBA file, from a quarter of the
     bytes to compress.  ``png_encoder="device"`` encodes the PNG / png8 pictures on the GPU (``api.encode_png``: same pixels,
     only the files cross PCIe) instead of with Pillow.  ``png_decoder="device"`` decodes the input on the GPU when it is a
-    PNG file ``api.png_info`` calls supported (``tiffio.read_image``; same pixels as Pillow), ``jpeg_decoder="device"`` when
+    PNG file ``api.png_info`` calls supported (``tiffio.read_image``; same pixels as Pillow), ``png_decoder="device+extended"`` also the
+    1-, 2-, 4- and 16-bit and interlaced files (``api.decode_png(data, extended=True)``), ``jpeg_decoder="device"`` when
     it is a JPEG file ``api.jpeg_info`` calls supported, ``tiff_decoder="device"`` when it is a TIFF file ``api.tiff_info`` calls
     supported and the array is the one read today (``tiffio.read_image``); ``tiff_decoder="device+deflate"`` sends Deflate
     TIFF files there as well (``api.decode_tiff(..., deflate=True)``).  ``tiff_encoder="device"`` builds the TIFF files on
@@ -258,7 +259,8 @@ def main(argv=None):
     ap.add_argument("--png-encoder", default="pillow", choices=list(PNG_ENCODERS),
                     help="'device' encodes the index PNGs on the GPU (same pixels, only the files cross PCIe)")
     ap.add_argument("--png-decoder", default="pillow", choices=list(PNG_DECODERS),
-                    help="'device' decodes supported PNG inputs on the GPU (same pixels; other files stay with Pillow)")
+                    help="'device' decodes 8-bit non-interlaced PNG inputs on the GPU (same pixels; other files stay with Pillow), "
+                         "'device+extended' also 1-, 2-, 4- and 16-bit and interlaced ones")
     ap.add_argument("--jpeg-decoder", default="pillow", choices=list(JPEG_DECODERS),
                     help="'device' decodes supported JPEG inputs on the GPU (same pixels; other files stay with Pillow)")
     ap.add_argument("--tiff-decoder", default="pillow", choices=list(TIFF_DECODERS),

@@ -431,6 +431,9 @@ def read_image(path, full_depth=False, png_decoder="pillow", jpeg_decoder="pillo
     every other file still goes through Pillow.
     ``png_decoder="device"``: a ``.png`` file with the PNG signature whose IHDR ``api.png_info`` calls supported is decoded
     on the GPU (``api.decode_png``, the same array as Pillow's); decided up front, not a fallback: its errors are raised.
+    ``png_decoder="device+extended"``: the same, and the files ``"device"`` leaves to Pillow -- bit depths 1, 2, 4 and 16 and
+    Adam7 interlace -- go to ``api.decode_png(data, extended=True)``, again the same array as Pillow's: a 16-bit gray file
+    comes back as the uint16 ``I;16`` array with or without ``full_depth``.
     ``jpeg_decoder="device"``: the same for a ``.jpg`` / ``.jpeg`` file that starts with ``FF D8`` and that ``api.jpeg_info``
     calls supported (``api.decode_jpeg``); every other file goes to Pillow as before.
     ``tiff_decoder="device"``: a ``.tif`` / ``.tiff`` file that ``api.tiff_info`` calls supported is decoded on the GPU
@@ -441,8 +444,8 @@ def read_image(path, full_depth=False, png_decoder="pillow", jpeg_decoder="pillo
     host, goes to ``api.decode_tiff(data, deflate=True)`` under the same two conditions.
     """
     from PIL import Image
-    if png_decoder not in ("pillow", "device"):
-        raise ValueError(f"png_decoder must be 'pillow' or 'device', got {png_decoder!r}")
+    if png_decoder not in ("pillow", "device", "device+extended"):
+        raise ValueError(f"png_decoder must be 'pillow', 'device' or 'device+extended', got {png_decoder!r}")
     if jpeg_decoder not in ("pillow", "device"):
         raise ValueError(f"jpeg_decoder must be 'pillow' or 'device', got {jpeg_decoder!r}")
     if tiff_decoder not in ("pillow", "device", "device+deflate"):
@@ -468,13 +471,14 @@ def read_image(path, full_depth=False, png_decoder="pillow", jpeg_decoder="pillo
         # a file that does not start with SOI is not the decoder's: Pillow opens it by content
         if data[:2] == b"\xff\xd8" and api.jpeg_info(data)["supported"]:
             return api.decode_jpeg(data)
-    if png_decoder == "device" and p.lower().endswith(".png"):
+    if png_decoder != "pillow" and p.lower().endswith(".png"):
         from . import api
+        extended = {"extended": True} if png_decoder == "device+extended" else {}       # "device" calls as it always did
         with open(p, "rb") as f:
             data = f.read()
         # a file without the PNG signature (a JPEG under a .png name, say) is not the decoder's: Pillow opens it by content
-        if data[:8] == b"\x89PNG\r\n\x1a\n" and api.png_info(data)["supported"]:
-            return api.decode_png(data)
+        if data[:8] == b"\x89PNG\r\n\x1a\n" and api.png_info(data, **extended)["supported"]:
+            return api.decode_png(data, **extended)
     if full_depth and p.lower().endswith((".tif", ".tiff")):
         try:
             arr = read_tiff(p)
