@@ -6,7 +6,8 @@
 // The stream of a strip is specified before the kernel: it is the greedy encoder's (tests/lzw_writer.py, encode(data,
 // clear_at=4094)), which is libtiff's.  A leading Clear; at every step the longest string the table holds; after each code the
 // string plus the next byte becomes entry 258, 259, ...; once the table holds 4094 codes (3836 entries added) a Clear goes
-// out and the table starts again; the last string's code, then EndOfInformation.  Code i of a segment (the codes between two
+// out and the table starts again; the last string's code, a Clear too where that code is the 3836th of its segment (libtiff
+// counts it as an entry although none is added), then EndOfInformation.  Code i of a segment (the codes between two
 // Clears, the Clear that ends it included) is 9 bits wide for i <= 253, 10 for i <= 765, 11 for i <= 1789, 12 after that;
 // codes are packed MSB first.
 //
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(64) void k_te_lzw(const uint8_t *__restrict__ img, 
     auto emit = [&](int code) {
         const int width = te_width(i);
         acc = (acc << width) | (unsigned int)code;
-        nbits += width;                                   // <= 7 + 12
+        nbits += width;                                   // <= 7 + 12; 7 + 12 + 9 for EndOfInformation behind the last Clear
         while (nbits >= 8) {
             nbits -= 8;
             if (op < cap) { if (lane == 0) dst[op] = (uint8_t)(acc >> nbits); }
@@ -147,6 +148,14 @@ __global__ __launch_bounds__(64) void k_te_lzw(const uint8_t *__restrict__ img, 
         }
     }
     if (w >= 0) emit(w);
+    // libtiff's LZWPostEncode counts the last code as an entry: a table that is full by that count is cleared before
+    // EndOfInformation.  The Clear is code 3837 of its segment, 12 bits, and goes into the accumulator in front of
+    // EndOfInformation, which then has 9 bits: at most 7 + 12 + 9 bits, written by the one emit below.
+    if (nxt + 1 >= TE_CLEAR_AT) {
+        acc = (acc << 12) | (unsigned int)TE_CLEAR;
+        nbits += 12;
+        i = 0;
+    }
     emit(TE_EOI);
     if (nbits) {
         if (op < cap) { if (lane == 0) dst[op] = (uint8_t)(acc << (8 - nbits)); }

@@ -166,6 +166,8 @@ def _lzw_encode(data):
         w = byte
     if w >= 0:
         emit(w)
+        if nxt + 1 >= 4094:               # libtiff counts the last code as an entry: a full table is cleared before EndOfInformation
+            emit(256)
     emit(257)
     if nbits:
         out.append((acc << (8 - nbits)) & 0xFF)

@@ -86,7 +86,8 @@ def plaintext(codes):
 
 def encode(data, clear_at=None, frozen_run=0, leading_clear=True, eoi=True):
     """The codes of a greedy encoder.  ``clear_at``: send Clear once the encoder's table holds that many codes (259 .. 4096; 4094
-    is what libtiff does, small values clear early); None: never, the table freezes at 4096 and the frozen table goes on
+    is what libtiff does, and as libtiff does a Clear then also follows a last code that would have brought the table to 4094; small
+    values clear early); None: never, the table freezes at 4096 and the frozen table goes on
     being used.  ``frozen_run``: with clear_at 4096, that many more codes are sent from the frozen table before the Clear (a
     deferred clear)."""
     assert clear_at is None or FIRST < clear_at <= MAXCODES
@@ -110,6 +111,8 @@ def encode(data, clear_at=None, frozen_run=0, leading_clear=True, eoi=True):
         w = bytes([byte])
     if w:
         codes.append(table[w])
+        if clear_at == 4094 and nxt + 1 >= clear_at:        # libtiff's LZWPostEncode counts the last code as an entry and clears a full table
+            codes.append(CLEAR)
     if eoi:
         codes.append(EOI)
     return codes

@@ -98,17 +98,23 @@ def test_lengths_that_end_at_a_width_change(index):
 
 
 def test_lengths_round_the_table_full_clear():
-    """The shortest input whose stream holds a table-full Clear (the Clear, one literal, EOI), one byte less (code index 3835 is the
-    last, no Clear) and one and two more."""
+    """The shortest input whose stream holds a table-full Clear: its last code is the 3836th of the segment, no entry follows it,
+    and libtiff clears the table all the same (the Clear, EOI at 9 bits).  One byte less (no Clear), one more (the Clear, one
+    literal, EOI), two and three more."""
     n = length_with(RANDOM[:8000], 2, lambda c: c.count(lz.CLEAR))
-    for m in (n - 1, n, n + 1, n + 2):
+    for m in (n - 1, n, n + 1, n + 2, n + 3):
         data = RANDOM[:m]
         want = spec(data)
         assert want.count(lz.CLEAR) == (1 if m < n else 2)
-        assert model_codes(data) == want
+        ev = model.new_events()
+        assert model_codes(data, ev) == want and ev["final_clear"] == (m == n) and ev["clears"] == (m >= n)
+        assert lz.plaintext(want) == data
     at = spec(RANDOM[:n])
-    assert at[-3] == lz.CLEAR and at[-2] < 256 and len(at) == 1 + model.SEG_CODES + 3
-    assert data_codes_in_last_segment(spec(RANDOM[:n - 1])) == model.SEG_CODES
+    assert at[-2] == lz.CLEAR and at[-3] != lz.CLEAR and len(at) == 1 + model.SEG_CODES + 2
+    assert lz.bit_length(at) == lz.bit_length(at[:-2]) + 12 + 9           # the Clear has 12 bits, EOI behind it 9
+    after = spec(RANDOM[:n + 1])
+    assert after[-3] == lz.CLEAR and after[-2] < 256 and len(after) == 1 + model.SEG_CODES + 3 and after[:-2] == at[:-1]
+    assert data_codes_in_last_segment(spec(RANDOM[:n - 1])) < model.SEG_CODES
 
 
 def directory(blob):

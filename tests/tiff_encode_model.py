@@ -79,8 +79,12 @@ def file_byte(img8, img16, g, B):
 def new_events():
     """What encode_strip() records for tests that assert coverage: ``clears`` table-full Clears, ``widths`` the code widths
     used, ``max_steps`` the longest probe sequence in steps of 64 slots, ``max_taken`` the most slots taken, ``wrapped`` a probe
-    window that wrapped round the table's end."""
-    return dict(clears=0, widths=set(), max_steps=0, max_taken=0, wrapped=False)
+    window that wrapped round the table's end; ``match_step`` / ``insert_step`` the deepest step (counted from 0) at which a
+    match was found / an empty slot was taken, -1 for never; ``wrapped_late`` a window that wrapped on a step after the first;
+    ``wrap_step`` the deepest such step; ``final_clear`` the Clear in front of EndOfInformation that follows a last code which
+    is the 3836th of its segment."""
+    return dict(clears=0, widths=set(), max_steps=0, max_taken=0, wrapped=False, match_step=-1, insert_step=-1, wrapped_late=False,
+                wrap_step=-1, final_clear=False)
 
 
 def encode_strip(img8, img16, g, k, events=None):
@@ -104,7 +108,7 @@ def encode_strip(img8, img16, g, k, events=None):
         codes.append(code)
         state["acc"] = (state["acc"] << width) | code
         state["nbits"] += width
-        assert state["nbits"] <= 19 and state["acc"] < 1 << 32
+        assert state["nbits"] <= (28 if code == EOI else 19) and state["acc"] < 1 << 32
         while state["nbits"] >= 8:
             state["nbits"] -= 8
             if state["op"] < cap:
@@ -133,8 +137,12 @@ def encode_strip(img8, img16, g, k, events=None):
             found, slot_at = -1, -1
             for step in range(SLOTS // LANES):
                 slots = [(h0 + step * LANES + lane) & (SLOTS - 1) for lane in range(LANES)]
+                assert all(0 <= q < SLOTS for q in slots)
                 if slots[-1] < slots[0]:
                     ev["wrapped"] = True
+                    if step >= 1:
+                        ev["wrapped_late"] = True
+                        ev["wrap_step"] = max(ev["wrap_step"], step)
                 hits = [lane for lane in range(LANES) if tab[slots[lane]] == 0 or tab[slots[lane]] >> 12 == key]
                 if hits:
                     first = hits[0]
@@ -142,8 +150,10 @@ def encode_strip(img8, img16, g, k, events=None):
                     if vv:
                         found = vv & 4095
                         assert FIRST <= found < nxt
+                        ev["match_step"] = max(ev["match_step"], step)
                     else:
                         slot_at = slots[first]
+                        ev["insert_step"] = max(ev["insert_step"], step)
                     ev["max_steps"] = max(ev["max_steps"], step + 1)
                     break
             if found >= 0:
@@ -164,6 +174,14 @@ def encode_strip(img8, img16, g, k, events=None):
                 nxt, taken = FIRST, 0
             w = byte
     emit(w)
+    if nxt + 1 >= CLEAR_AT:                                   # libtiff's LZWPostEncode: the last code counts as an entry
+        assert width_of(state["i"]) == 12 and state["nbits"] < 8
+        codes.append(CLEAR)                                   # into the accumulator, in front of EndOfInformation: one emit writes both
+        state["acc"] = (state["acc"] << 12) | CLEAR
+        state["nbits"] += 12
+        state["i"] = 0
+        ev["clears"] += 1
+        ev["final_clear"] = True
     emit(EOI)
     if state["nbits"]:
         if state["op"] < cap:
