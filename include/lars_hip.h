@@ -812,6 +812,42 @@ int lars_h_process_image_tiff_f32(const void *img, int64_t h, int64_t w, int cha
                                   uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3],
                                   int predictor, int64_t rows_per_strip,
                                   uint8_t *const out_tiff[3], size_t tiff_cap, int64_t tiff_len[3]);
+/* Deflate TIFF files built on the device: the entry points above with Compression 8 (GDAL's COMPRESS=DEFLATE, the usual choice
+ * with a predictor for float rasters).  Arguments, strips, the knob tiff_strip_bytes, the directory (tiffio.write_tiff(...,
+ * deflate=True) / write_float_tiff(..., deflate=True) for the same array, rows_per_strip and predictor), status_dev, LARS_TIFE_*
+ * and the 4 GiB refusal are those of the LZW entry points; only the strips' streams differ, and they are coded in parallel: one
+ * workgroup per 32768 stored bytes of a strip.  The stream of a strip of n stored bytes (after the predictor, little-endian):
+ * 78 01; for every part of 32768 bytes (the last may be shorter) one block -- dynamic Huffman over literals only (zlib's
+ * Z_HUFFMAN_ONLY), or stored where that is not shorter; behind a dynamic block that is not the strip's last an empty stored
+ * block (00 00 FF FF after three zero bits and the padding), so that every part ends on a byte boundary; BFINAL on the last;
+ * the Adler-32 of the n bytes.  A function of the strip's bytes alone; any inflate reads it (lars_h_decode_tiff_deflate too).
+ * lars_tiff_deflate_bound: pure host code; per strip 2 header bytes, its n bytes, 5 bytes per part (a stored block's header;
+ * a dynamic block with its flush is only chosen where it is no longer), 4 checksum bytes and one pad byte, then the header and
+ * the directory with its arrays as in lars_tiff_bound; 0 for a shape that cannot be encoded.
+ * lars_tiff_deflate_encode_scratch_bytes: device scratch of lars_d_encode_tiff_deflate (about twice the picture: the staged
+ * predictor output and one slot per part). */
+size_t lars_tiff_deflate_bound(int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip);
+size_t lars_tiff_deflate_encode_scratch_bytes(int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip);
+int lars_d_encode_tiff_deflate(const void *img, int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip, int predictor,
+                               uint8_t *out, size_t out_cap, int64_t *out_len_dev, int32_t *status_dev, void *scratch, void *stream);
+int lars_h_encode_tiff_deflate(const void *img, int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip, int predictor,
+                               uint8_t *out, size_t out_cap, int64_t *out_len);
+/* ... and for float32 samples (Predictor 3 when predictor is not 0), as lars_*_encode_tiff_f32 */
+size_t lars_tiff_float32_deflate_bound(int64_t h, int64_t w, int channels, int64_t rows_per_strip);
+size_t lars_tiff_float32_deflate_encode_scratch_bytes(int64_t h, int64_t w, int channels, int64_t rows_per_strip);
+int lars_d_encode_tiff_deflate_float32(const float *img, int64_t h, int64_t w, int channels, int64_t rows_per_strip, int predictor, uint8_t *out,
+                                   size_t out_cap, int64_t *out_len_dev, int32_t *status_dev, void *scratch, void *stream);
+int lars_h_encode_tiff_deflate_float32(const float *img, int64_t h, int64_t w, int channels, int64_t rows_per_strip, int predictor, uint8_t *out,
+                                   size_t out_cap, int64_t *out_len);
+/* lars_h_process_image_tiff_f32 with the compression named: 5 (LZW, the same call) or 8 (Deflate: lars_d_encode_tiff_deflate_float32,
+ * tiff_cap at least lars_tiff_float32_deflate_bound(h, w, 1, rows_per_strip)); any other value is LARS_ERR_INVALID. */
+int lars_h_process_image_tiff_float32(const void *img, int64_t h, int64_t w, int channels, int dtype,
+                                              int apply_wb, uint32_t index_mask, int want_hist,
+                                              uint8_t *out_wb, float *const out_index[3],
+                                              lars_stats *stats /* [3] */, float *medians /* [3][2] */,
+                                              uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3],
+                                              int compression, int predictor, int64_t rows_per_strip,
+                                              uint8_t *const out_tiff[3], size_t tiff_cap, int64_t tiff_len[3]);
 
 /* ------------------------------------------------------------------ multi-GPU */
 /* One process per GPU.  RCCL (librccl.so) is loaded on first use.  unique_id is

@@ -262,6 +262,16 @@ SIGNATURES = {
     "lars_h_encode_tiff_f32": (_I, [_P, _I64, _I64, _I, _I64, _I, _P, _SZ, C.POINTER(_I64)]),
     "lars_h_process_image_tiff_f32": (_I, [_P, _I64, _I64, _I, _I, _I, _U32, _I, _P, C.POINTER(_P * 3), _P, _P,
                                            C.POINTER(_P * 3), C.POINTER(_P * 3), _I, _I64, C.POINTER(_P * 3), _SZ, _P]),
+    "lars_tiff_deflate_bound": (_SZ, [_I64, _I64, _I, _I, _I64]),
+    "lars_tiff_deflate_encode_scratch_bytes": (_SZ, [_I64, _I64, _I, _I, _I64]),
+    "lars_d_encode_tiff_deflate": (_I, [_P, _I64, _I64, _I, _I, _I64, _I, _P, _SZ, _P, _P, _P, _P]),
+    "lars_h_encode_tiff_deflate": (_I, [_P, _I64, _I64, _I, _I, _I64, _I, _P, _SZ, C.POINTER(_I64)]),
+    "lars_tiff_float32_deflate_bound": (_SZ, [_I64, _I64, _I, _I64]),
+    "lars_tiff_float32_deflate_encode_scratch_bytes": (_SZ, [_I64, _I64, _I, _I64]),
+    "lars_d_encode_tiff_deflate_float32": (_I, [_P, _I64, _I64, _I, _I64, _I, _P, _SZ, _P, _P, _P, _P]),
+    "lars_h_encode_tiff_deflate_float32": (_I, [_P, _I64, _I64, _I, _I64, _I, _P, _SZ, C.POINTER(_I64)]),
+    "lars_h_process_image_tiff_float32": (_I, [_P, _I64, _I64, _I, _I, _I, _U32, _I, _P, C.POINTER(_P * 3), _P, _P,
+                                                       C.POINTER(_P * 3), C.POINTER(_P * 3), _I, _I, _I64, C.POINTER(_P * 3), _SZ, _P]),
     "lars_jpeg_bound": (_SZ, [_I64, _I64, _I, _I]),
     "lars_jpeg_header": (_I64, [_I64, _I64, _I, _I, _I, _P, _SZ]),
     "lars_jpeg_encode_scratch_bytes": (_SZ, [_I64, _I64, _I, _I]),

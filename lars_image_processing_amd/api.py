@@ -657,7 +657,14 @@ def _tiff_picture(array, rows_per_strip, who, f32=False):
     return np.ascontiguousarray(arr), rps
 
 
-def tiff_bound(h, w, channels, itemsize, rows_per_strip=None):
+def _tiff_compression(compression, who):
+    """``compression`` of the TIFF encoders, checked before anything is launched: True for ``"deflate"``, False for ``"lzw"``."""
+    if not isinstance(compression, str) or compression not in ("lzw", "deflate"):
+        raise ValueError(f"{who}: compression must be 'lzw' or 'deflate', got {compression!r}")
+    return compression == "deflate"
+
+
+def tiff_bound(h, w, channels, itemsize, rows_per_strip=None, compression="lzw"):
     """The largest file ``encode_tiff`` can return for an ``h x w`` picture of ``channels`` samples of ``itemsize`` bytes
     (``lars_tiff_bound``; host code, no device needed); 0 for a shape that cannot be encoded.
 
@@ -667,12 +674,18 @@ def tiff_bound(h, w, channels, itemsize, rows_per_strip=None):
     ``ceil(12 * (n + n // 3836 + 2) / 8)`` bytes, plus one where that is odd (strips start on even offsets).  Around the
     strips: 8 bytes of header, a directory of at most 13 entries (2 + 12 * 13 + 4 bytes), BitsPerSample and SampleFormat
     (``2 * channels`` bytes each), and 8 bytes of offset and byte count per strip.  ``rows_per_strip=None``: the rows the
-    knob ``tiff_strip_bytes`` gives, as in ``encode_tiff``."""
-    return int(_ffi.load().lars_tiff_bound(int(h), int(w), int(channels), int(itemsize), int(rows_per_strip or 0)))
+    knob ``tiff_strip_bytes`` gives, as in ``encode_tiff``.
+
+    ``compression="deflate"`` (``lars_tiff_deflate_bound``): per strip of n bytes in ``p = ceil(n / 32768)`` parts, 2 bytes of
+    zlib header, the n bytes, 5 bytes per part (a stored block's header; a dynamic block with its flush is only written where it
+    is no longer than the stored form), 4 bytes of Adler-32 -- ``n + 5 * p + 6`` -- plus one where that is odd; around the strips
+    the same."""
+    name = "lars_tiff_deflate_bound" if _tiff_compression(compression, "tiff_bound") else "lars_tiff_bound"
+    return int(getattr(_ffi.load(), name)(int(h), int(w), int(channels), int(itemsize), int(rows_per_strip or 0)))
 
 
-def encode_tiff(array, rows_per_strip=None, predictor=False):
-    """LZW TIFF file (``bytes``) of a picture, encoded on the GPU: ``[H, W]`` or ``[H, W, C]`` with C = 1..5, uint8 or uint16.
+def encode_tiff(array, rows_per_strip=None, predictor=False, compression="lzw"):
+    """LZW or Deflate TIFF file (``bytes``) of a picture, encoded on the GPU: ``[H, W]`` or ``[H, W, C]`` with C = 1..5, uint8 or uint16.
 
     A classic little-endian TIFF with strips, chunky samples and Compression 5; ``predictor=True`` writes Predictor 2
     (horizontal differencing per sample modulo 2^bits, every row on its own).  The directory holds the tags and values of
@@ -683,20 +696,27 @@ def encode_tiff(array, rows_per_strip=None, predictor=False):
     bytes libtiff writes for that strip.  What ``Image.fromarray(corrected).save(".../<name>_wb.tif")`` does for the batch
     job's primary output (backend-process.py:57), compressed.
 
-    ``TypeError`` / ``ValueError`` for other dtypes, shapes, empty arrays or C > 5 before anything is launched;
+    ``compression="deflate"`` writes Compression 8 instead, the same strips, directory (``tiffio.write_tiff(..., deflate=True)``'s)
+    and predictor: every strip is a zlib stream whose 32768-byte parts are coded in parallel, each as a dynamic Huffman block over
+    literals only (zlib's ``Z_HUFFMAN_ONLY``) or a stored block where that is not shorter, with an empty stored block between
+    parts.  No string matching: on predicted data that gives up little, on flat pictures a great deal (LZW is the smaller file
+    there).  Any inflate reads it; ``decode_tiff(..., deflate=True)`` does on the device.
+
+    ``TypeError`` / ``ValueError`` for other dtypes, shapes, empty arrays, C > 5 or another ``compression`` before anything is launched;
     ``tiffio.TiffError`` for a file that would reach 4 GiB.  No CPU fallback.
     """
     from .tiffio import TiffError
+    deflate = _tiff_compression(compression, "encode_tiff")
     arr, rps = _tiff_picture(array, rows_per_strip, "encode_tiff")
     h, w, c = arr.shape
-    bound = tiff_bound(h, w, c, arr.dtype.itemsize, rps)
+    bound = tiff_bound(h, w, c, arr.dtype.itemsize, rps, compression)
     if bound == 0:
         raise ValueError(f"encode_tiff: strips of {rps or 'the default number of'} rows of {w * c * arr.dtype.itemsize} bytes are too long (2^30 bytes at most)")
     out = np.empty(min(bound, 1 << 32), dtype=np.uint8)
     n = C.c_int64(0)
     try:
-        _ffi.call("lars_h_encode_tiff", _ffi.ptr(arr), h, w, c, arr.dtype.itemsize, rps, int(bool(predictor)), _ffi.ptr(out), out.nbytes,
-                  C.byref(n))
+        _ffi.call("lars_h_encode_tiff_deflate" if deflate else "lars_h_encode_tiff", _ffi.ptr(arr), h, w, c, arr.dtype.itemsize, rps,
+                  int(bool(predictor)), _ffi.ptr(out), out.nbytes, C.byref(n))
     except _ffi.LarsError as e:
         if e.code == -6 or (e.code == -1 and bound > out.nbytes):
             raise TiffError("image too large for a classic TIFF (4 GiB)") from None
@@ -704,37 +724,44 @@ def encode_tiff(array, rows_per_strip=None, predictor=False):
     return out[:n.value].tobytes()
 
 
-def tiff_f32_bound(h, w, channels, rows_per_strip=None):
+def tiff_f32_bound(h, w, channels, rows_per_strip=None, compression="lzw"):
     """The largest file ``encode_tiff_f32`` can return for an ``h x w`` picture of ``channels`` float32 samples
     (``lars_tiff_f32_bound``; host code, no device needed); 0 for a shape that cannot be encoded.  ``tiff_bound``'s derivation
     with rows of ``w * channels * 4`` bytes: per strip of n bytes ``ceil(12 * (n + n // 3836 + 2) / 8)`` bytes, plus one where
     that is odd; 8 bytes of header, 2 + 12 * 13 + 4 of directory, ``4 * channels`` of BitsPerSample and SampleFormat, 8 per
-    strip.  ``rows_per_strip=None``: the rows the knob ``tiff_strip_bytes`` gives."""
-    return int(_ffi.load().lars_tiff_f32_bound(int(h), int(w), int(channels), int(rows_per_strip or 0)))
+    strip.  ``rows_per_strip=None``: the rows the knob ``tiff_strip_bytes`` gives.  ``compression="deflate"``
+    (``lars_tiff_float32_deflate_bound``): ``n + 5 * ceil(n / 32768) + 6`` bytes per strip, plus one where that is odd, as in
+    ``tiff_bound``."""
+    name = "lars_tiff_float32_deflate_bound" if _tiff_compression(compression, "tiff_f32_bound") else "lars_tiff_f32_bound"
+    return int(getattr(_ffi.load(), name)(int(h), int(w), int(channels), int(rows_per_strip or 0)))
 
 
-def encode_tiff_f32(array, rows_per_strip=None, predictor=False):
-    """LZW TIFF file (``bytes``) of float32 samples, encoded on the GPU: ``[H, W]`` or ``[H, W, C]`` with C = 1..5 -- an index plane
+def encode_tiff_f32(array, rows_per_strip=None, predictor=False, compression="lzw"):
+    """LZW or Deflate TIFF file (``bytes``) of float32 samples, encoded on the GPU: ``[H, W]`` or ``[H, W, C]`` with C = 1..5 -- an index plane
     (``calculate_index``) kept bit for bit, in the file GDAL, rasterio and QGIS exchange such rasters in.
 
     ``encode_tiff``'s file (classic, little-endian, strips, chunky, Compression 5, the same strip rule and knob) with
     BitsPerSample 32 and SampleFormat 3; the directory is ``tiffio.write_float_tiff``'s.  ``predictor=True`` writes Predictor 3,
     the floating-point predictor (libtiff's fpDiff: every row as four byte planes, most significant first, differenced across
     the plane borders), computed from the picture as the encoder reads it.  Every strip is libtiff's stream for those bytes.
+    ``compression="deflate"``: Compression 8 with ``encode_tiff``'s Deflate streams, the directory of
+    ``tiffio.write_float_tiff(..., deflate=True)`` -- with ``predictor=True`` what GDAL writes for COMPRESS=DEFLATE PREDICTOR=3.
 
-    ``TypeError`` for any dtype but float32 (float64 is not cast), ``TypeError`` / ``ValueError`` for shapes, empty arrays or
-    C > 5, all before anything is launched; ``tiffio.TiffError`` for a file that would reach 4 GiB.  No CPU fallback.
+    ``TypeError`` for any dtype but float32 (float64 is not cast), ``TypeError`` / ``ValueError`` for shapes, empty arrays,
+    C > 5 or another ``compression``, all before anything is launched; ``tiffio.TiffError`` for a file that would reach 4 GiB.  No CPU fallback.
     """
     from .tiffio import TiffError
+    deflate = _tiff_compression(compression, "encode_tiff_f32")
     arr, rps = _tiff_picture(array, rows_per_strip, "encode_tiff_f32", f32=True)
     h, w, c = arr.shape
-    bound = tiff_f32_bound(h, w, c, rps)
+    bound = tiff_f32_bound(h, w, c, rps, compression)
     if bound == 0:
         raise ValueError(f"encode_tiff_f32: strips of {rps or 'the default number of'} rows of {w * c * 4} bytes are too long (2^30 bytes at most)")
     out = np.empty(min(bound, 1 << 32), dtype=np.uint8)
     n = C.c_int64(0)
     try:
-        _ffi.call("lars_h_encode_tiff_f32", _ffi.ptr(arr), h, w, c, rps, int(bool(predictor)), _ffi.ptr(out), out.nbytes, C.byref(n))
+        _ffi.call("lars_h_encode_tiff_deflate_float32" if deflate else "lars_h_encode_tiff_f32", _ffi.ptr(arr), h, w, c, rps, int(bool(predictor)),
+                  _ffi.ptr(out), out.nbytes, C.byref(n))
     except _ffi.LarsError as e:
         if e.code == -6 or (e.code == -1 and bound > out.nbytes):
             raise TiffError("image too large for a classic TIFF (4 GiB)") from None
@@ -1165,11 +1192,14 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
     way only the file crosses PCIe.
     ``want_tiff=True`` adds ``tiff``: the float32 LZW TIFF file (``bytes``) of the index plane itself, encoded on the device
     (``encode_tiff_f32``, one strip rule for all); ``want_tiff="predictor"`` writes it with Predictor 3.  The plane then need
-    not cross PCIe (``want_arrays=False``).  Not together with ``want_png`` (one kind of file per call).
+    not cross PCIe (``want_arrays=False``).  ``want_tiff="deflate"`` and ``"deflate+predictor"`` write the Deflate file instead
+    (``encode_tiff_f32(..., compression="deflate")``).  Not together with ``want_png`` (one kind of file per call).
     """
-    tiff_mode = 0 if want_tiff is False else 1 if want_tiff is True else 2 if isinstance(want_tiff, str) and want_tiff == "predictor" else None
+    tiff_modes = {"predictor": 2, "deflate": 3, "deflate+predictor": 4}
+    tiff_mode = 0 if want_tiff is False else 1 if want_tiff is True else tiff_modes.get(want_tiff) if isinstance(want_tiff, str) else None
     if tiff_mode is None:
-        raise ValueError(f"process_image: want_tiff must be False, True or 'predictor', got {want_tiff!r}")
+        raise ValueError(f"process_image: want_tiff must be False, True or 'predictor' ('deflate' or 'deflate+predictor' for Deflate), "
+                         f"got {want_tiff!r}")
     if tiff_mode and want_png is not False:
         raise ValueError("process_image: want_tiff or want_png, not both (one kind of file per call)")
     png_mode = 0 if want_png is False else 1 if want_png is True else 2 if isinstance(want_png, str) and want_png == "palette" else None
@@ -1203,16 +1233,21 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
     med = np.zeros((3, 2), dtype=np.float32)
     pngs, tiffs = [None] * 3, [None] * 3
     if tiff_mode:
-        cap = tiff_f32_bound(h, w, 1)
+        tiff_deflate = tiff_mode >= 3
+        cap = tiff_f32_bound(h, w, 1, compression="deflate" if tiff_deflate else "lzw")
         if cap == 0:
             raise ValueError(f"process_image: a {h} x {w} plane is not encoded as a TIFF file (1 to 2^24 on each side)")
         for t in indices:
             tiffs[INDEX_IDS[t]] = np.empty(cap, dtype=np.uint8)
         lens = np.zeros(3, dtype=np.int64)
         p_out, p_rgba, p_lut, p_tiff = _ffi.ptr3(outs), _ffi.ptr3(rgbas), _ffi.ptr3(luts), _ffi.ptr3(tiffs)
-        _ffi.call("lars_h_process_image_tiff_f32", _ffi.ptr(arr), h, w, c, code, int(bool(white_balance)), mask, int(want_hist),
-                  _ffi.ptr(out_wb), C.byref(p_out), C.byref(stats), _ffi.ptr(med), C.byref(p_rgba), C.byref(p_lut), int(tiff_mode == 2), 0,
-                  C.byref(p_tiff), cap, _ffi.ptr(lens))
+        head = (_ffi.ptr(arr), h, w, c, code, int(bool(white_balance)), mask, int(want_hist), _ffi.ptr(out_wb), C.byref(p_out), C.byref(stats),
+                _ffi.ptr(med), C.byref(p_rgba), C.byref(p_lut))
+        tail = (int(tiff_mode in (2, 4)), 0, C.byref(p_tiff), cap, _ffi.ptr(lens))
+        if tiff_deflate:
+            _ffi.call("lars_h_process_image_tiff_float32", *head, 8, *tail)
+        else:
+            _ffi.call("lars_h_process_image_tiff_f32", *head, *tail)
         tiffs = [None if p is None else p[:lens[k]].tobytes() for k, p in enumerate(tiffs)]
     elif png_mode:
         cap = png_bound(h, w, 4 if png_mode == 1 else 1)

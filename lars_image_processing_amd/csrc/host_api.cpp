@@ -29,7 +29,8 @@ struct ImageJob {
     uint8_t *out_png[3];
     size_t png_cap;
     int64_t *png_len;             // [3]
-    int tiff;                     // 0 none, 1 float32 TIFF files of the index planes (LZW on the device)
+    int tiff;                     // 0 none, 1 float32 TIFF files of the index planes (encoded on the device)
+    int tiff_compression;         // 5 LZW, 8 Deflate
     int tiff_predictor;
     int64_t tiff_rps;
     uint8_t *out_tiff[3];
@@ -97,10 +98,12 @@ Layout plan(const ImageJob &j, Carver &c)
         L.pal[k] = (on && j.png_mode == 2) ? c.take<uint8_t>(1024) : nullptr;
         L.png[k] = (on && j.png_mode) ? c.take<uint8_t>(L.png_bound) : nullptr;
     }
-    L.tif_bound = j.tiff ? lars_tiff_f32_bound(j.h, j.w, 1, j.tiff_rps) : 0;
+    const bool tif_deflate = j.tiff_compression == 8;
+    L.tif_bound = !j.tiff ? 0 : tif_deflate ? lars_tiff_float32_deflate_bound(j.h, j.w, 1, j.tiff_rps) : lars_tiff_f32_bound(j.h, j.w, 1, j.tiff_rps);
     for (int k = 0; k < 3; ++k) L.tif[k] = (j.tiff && ((j.mask >> k) & 1u)) ? c.take<uint8_t>(L.tif_bound) : nullptr;
     L.tif_ans = j.tiff ? c.take<TiffAnswer>(3) : nullptr;
-    L.tif_scratch = j.tiff ? c.take<char>(lars_tiff_f32_encode_scratch_bytes(j.h, j.w, 1, j.tiff_rps)) : nullptr;
+    L.tif_scratch = !j.tiff ? nullptr : c.take<char>(tif_deflate ? lars_tiff_float32_deflate_encode_scratch_bytes(j.h, j.w, 1, j.tiff_rps)
+                                                                 : lars_tiff_f32_encode_scratch_bytes(j.h, j.w, 1, j.tiff_rps));
     L.png_len = j.png_mode ? c.take<int64_t>(3) : nullptr;
     L.png_scratch = j.png_mode ? c.take<char>(lars_png_scratch_bytes(j.h, j.w, png_channels)) : nullptr;
     L.stats = c.take<lars_stats>(3);
@@ -187,8 +190,8 @@ int run_image(const ImageJob &j)
     if (L.tif_ans) {                                        // the plane stays on the device; only its TIFF file crosses PCIe
         for (int k = 0; k < 3; ++k)
             if (L.tif[k])
-                LARS_TRY(lars_d_encode_tiff_f32(L.idx[k], j.h, j.w, 1, j.tiff_rps, j.tiff_predictor, L.tif[k], L.tif_bound, &L.tif_ans[k].len,
-                                                L.tif_ans[k].status, L.tif_scratch, s));
+                LARS_TRY((j.tiff_compression == 8 ? lars_d_encode_tiff_deflate_float32 : lars_d_encode_tiff_f32)(
+                    L.idx[k], j.h, j.w, 1, j.tiff_rps, j.tiff_predictor, L.tif[k], L.tif_bound, &L.tif_ans[k].len, L.tif_ans[k].status, L.tif_scratch, s));
         LARS_HIP_TRY(hipMemcpyAsync(htif, L.tif_ans, sizeof htif, hipMemcpyDeviceToHost, s));
     }
     int64_t hlen[3] = {0, 0, 0};
@@ -353,21 +356,22 @@ int lars_h_process_image_png(const void *img, int64_t h, int64_t w, int channels
     return run_image(j);
 }
 
-int lars_h_process_image_tiff_f32(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
-                                  int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
-                                  uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], int predictor, int64_t rows_per_strip,
-                                  uint8_t *const out_tiff[3], size_t tiff_cap, int64_t tiff_len[3])
+static int process_image_tiff(const char *who, int compression, const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb,
+                              uint32_t index_mask, int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                              uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], int predictor, int64_t rows_per_strip,
+                              uint8_t *const out_tiff[3], size_t tiff_cap, int64_t tiff_len[3])
 {
-    static const char *who = "lars_h_process_image_tiff_f32";
     if (!index_mask || (index_mask & ~LARS_MASK_ALL) || !out_tiff || !tiff_len)
         return fail(LARS_ERR_INVALID, "%s: indices and TIFF outputs are required", who);
-    const size_t bound = lars_tiff_f32_bound(h, w, 1, rows_per_strip);
+    const size_t bound = compression == 8 ? lars_tiff_float32_deflate_bound(h, w, 1, rows_per_strip) : lars_tiff_f32_bound(h, w, 1, rows_per_strip);
     if (!bound)
         return fail(LARS_ERR_INVALID, "%s: %lld x %lld image in strips of %lld rows (1 to 2^24 on each side, strips of at most 2^30 bytes)", who,
                     (long long)h, (long long)w, (long long)rows_per_strip);
     for (int k = 0; k < 3; ++k)
         if (((index_mask >> k) & 1u) && !out_tiff[k]) return fail(LARS_ERR_INVALID, "%s: index %d needs out_tiff", who, k);
-    if (tiff_cap < bound) return fail(LARS_ERR_INVALID, "%s: tiff_cap %zu < lars_tiff_f32_bound %zu", who, tiff_cap, bound);
+    if (tiff_cap < bound)
+        return fail(LARS_ERR_INVALID, "%s: tiff_cap %zu < %s %zu", who, tiff_cap, compression == 8 ? "lars_tiff_float32_deflate_bound" : "lars_tiff_f32_bound",
+                    bound);
     ImageJob j;
     memset(&j, 0, sizeof j);
     j.img = img; j.h = h; j.w = w; j.channels = channels; j.dtype = dtype;
@@ -380,8 +384,29 @@ int lars_h_process_image_tiff_f32(const void *img, int64_t h, int64_t w, int cha
     }
     j.stats = stats; j.want_stats = stats != nullptr; j.want_hist = want_hist;
     j.medians = medians; j.want_median = medians != nullptr;
-    j.tiff = 1; j.tiff_predictor = predictor; j.tiff_rps = rows_per_strip; j.tiff_cap = tiff_cap; j.tiff_len = tiff_len;
+    j.tiff = 1; j.tiff_compression = compression; j.tiff_predictor = predictor; j.tiff_rps = rows_per_strip; j.tiff_cap = tiff_cap;
+    j.tiff_len = tiff_len;
     return run_image(j);
+}
+
+int lars_h_process_image_tiff_f32(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                                  int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                                  uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], int predictor, int64_t rows_per_strip,
+                                  uint8_t *const out_tiff[3], size_t tiff_cap, int64_t tiff_len[3])
+{
+    return process_image_tiff("lars_h_process_image_tiff_f32", 5, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index,
+                              stats, medians, out_rgba, cmap_lut, predictor, rows_per_strip, out_tiff, tiff_cap, tiff_len);
+}
+
+int lars_h_process_image_tiff_float32(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                                              int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                                              uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], int compression, int predictor,
+                                              int64_t rows_per_strip, uint8_t *const out_tiff[3], size_t tiff_cap, int64_t tiff_len[3])
+{
+    static const char *who = "lars_h_process_image_tiff_float32";
+    if (compression != 5 && compression != 8) return fail(LARS_ERR_INVALID, "%s: compression must be 5 (LZW) or 8 (Deflate), got %d", who, compression);
+    return process_image_tiff(who, compression, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians,
+                              out_rgba, cmap_lut, predictor, rows_per_strip, out_tiff, tiff_cap, tiff_len);
 }
 
 int lars_h_calculate_index_planes(const float *red, const float *green, const float *nir, int64_t n, int index_id,

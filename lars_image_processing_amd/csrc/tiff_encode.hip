@@ -15,10 +15,21 @@
 // code (12 bits); 0 is an empty slot (no entry has code 0).  At most 3836 slots are taken, so a probe sequence meets an
 // empty slot; the 64 lanes look at 64 consecutive slots per step, so it ends after at most 8192 / 64 steps.
 // tests/tiff_encode_model.py restates the phases below in NumPy and checks every index they form.
+//
+// Deflate (lars_*_encode_tiff_deflate*, Compression 8) replaces k_te_lzw by kernels that code a strip in parallel; the directory, the
+// strip rule, the status codes and the placement of the strips are the LZW path's.  The stream of a strip, specified before the
+// kernels (tests/tiff_deflate_encode_model.py builds it byte for byte): the strip has n stored bytes (after the predictor,
+// little-endian) and p = ceil(n / 32768) parts.  The stream opens with 78 01.  Part i covers bytes [32768 i, min(n, 32768 (i + 1)))
+// and is the block deflate_segment (deflate_device.h) writes for them -- a dynamic literal-only Huffman block, or a stored block
+// where the dynamic one would not be shorter.  A dynamic block of a part that is not the last is followed by three zero bits, the
+// padding to a byte and 00 00 FF FF (an empty stored block), so that every part ends on a byte boundary (a stored block does
+// anyway); the last part carries BFINAL and is padded to a byte; a strip of one part is first and last at once.  The Adler-32 of
+// the n bytes, big-endian, ends the stream.  The stream is a function of the strip's bytes alone.
 #include <algorithm>
 
 #include "codec_host.h"
 #include "common.h"
+#include "deflate_device.h"
 
 namespace lars {
 
@@ -190,9 +201,9 @@ __device__ inline int te_entry(uint8_t *p, int tag, int typ, unsigned int n, uns
 }
 
 // The scan of the strip lengths (each rounded up to even) and everything of the file that is not strip data: the header, the
-// directory in tiffio.write_tiff's order (tags ascending; arrays of more than four bytes after the directory, in the order of
+// directory (Compression: 5 or 8) in tiffio.write_tiff's order (tags ascending; arrays of more than four bytes after the directory, in the order of
 // their tags), the strip offsets and byte counts, the file's length.  One workgroup.
-__global__ __launch_bounds__(TE_FRAME_THREADS) void k_te_frame(TeGeom g, const unsigned int *__restrict__ zlen,
+__global__ __launch_bounds__(TE_FRAME_THREADS) void k_te_frame(TeGeom g, int compression, const unsigned int *__restrict__ zlen,
                                                               unsigned long long *__restrict__ off, uint8_t *__restrict__ out,
                                                               unsigned long long out_cap, long long *out_len, int *status)
 {
@@ -252,7 +263,7 @@ __global__ __launch_bounds__(TE_FRAME_THREADS) void k_te_frame(TeGeom g, const u
     p += te_entry(p, 256, 4, 1, (unsigned int)g.width, true, 0);
     p += te_entry(p, 257, 4, 1, (unsigned int)g.height, true, 0);
     p += te_entry(p, 258, 3, (unsigned int)c, bits, c < 3, (unsigned int)bits_at);
-    p += te_entry(p, 259, 3, 1, 5, true, 0);
+    p += te_entry(p, 259, 3, 1, (unsigned int)compression, true, 0);
     p += te_entry(p, 262, 3, 1, c >= 3 ? 2 : 1, true, 0);
     p += te_entry(p, 273, 4, (unsigned int)n, 8u, n == 1, (unsigned int)offs_at);
     p += te_entry(p, 277, 3, 1, (unsigned int)c, true, 0);
@@ -285,6 +296,127 @@ __global__ __launch_bounds__(TE_PACK_THREADS) void k_te_pack(TeGeom g, const uin
     const uint16_t *src = reinterpret_cast<const uint16_t *>(zbuf + k * g.pitch);
     uint16_t *dst = reinterpret_cast<uint16_t *>(out + o);
     for (unsigned int j = threadIdx.x; j < m / 2; j += TE_PACK_THREADS) dst[j] = src[j];
+}
+
+// ---- Deflate ---------------------------------------------------------------------------------------------------------------------
+constexpr int TZ_STAGE_THREADS = 256, TZ_STAGE_BYTES = 4 * TZ_STAGE_THREADS;     // k_tz_stage: four stored bytes per thread
+constexpr int TZ_JOIN_THREADS = 256;
+
+// Upper bound of a strip's stream for n input bytes, its pad byte included: the header 78 01; per part its bytes and five more
+// (a stored block is BFINAL/BTYPE, LEN, NLEN and the bytes; the dynamic block, with its three flush bits, padding and 00 00 FF FF
+// where the part is not the last, is chosen only where it is no longer than that); the Adler-32; one byte more brings the next
+// strip to an even offset.
+__host__ __device__ inline long long tz_parts(long long n) { return (n + DEFLATE_SEG - 1) / DEFLATE_SEG; }
+__host__ __device__ inline long long tz_strip_cap(long long n)
+{
+    const long long bytes = 2 + n + 5 * tz_parts(n) + 4;
+    return bytes + (bytes & 1);
+}
+
+__device__ inline long long tz_strip_bytes(const TeGeom &g, long long k)
+{
+    const long long left = (long long)g.height - k * g.rps;
+    return (left < g.rps ? left : (long long)g.rps) * g.rowb;
+}
+
+// The picture as the file stores it (te_byte), for the predictors; without one the picture's own bytes are the stored bytes and
+// nothing is staged.  Strips are consecutive rows, so strip k's stored bytes are stage[k * rps * rowb ...), contiguous.  One
+// workgroup per TZ_STAGE_BYTES bytes of a row: blockIdx.x = row * chunks + chunk.
+__global__ __launch_bounds__(TZ_STAGE_THREADS) void k_tz_stage(const uint8_t *__restrict__ img, TeGeom g, long long chunks,
+                                                              uint8_t *__restrict__ stage)
+{
+    const long long y = blockIdx.x / chunks, q0 = (blockIdx.x - y * chunks) * TZ_STAGE_BYTES + 4 * threadIdx.x;
+    if (y >= g.height) return;
+    const long long B = y * g.rowb + q0;
+    for (int j = 0; j < 4 && q0 + j < g.rowb; ++j) stage[B + j] = (uint8_t)te_byte(img, g, B + j);
+}
+
+// One workgroup per (strip, part): slot = strip * pf + part, pf the parts of a whole strip (the last strip may have fewer: its
+// other slots stay unused).  The part's block goes to Z + slot * DEFLATE_ZCAP.
+__global__ __launch_bounds__(DEFLATE_THREADS) void k_tz_deflate(const uint8_t *__restrict__ stored, TeGeom g, long long pf,
+                                                               uint8_t *__restrict__ Z, unsigned int *__restrict__ seglen,
+                                                               unsigned int *__restrict__ adl)
+{
+    const long long slot = blockIdx.x, k = slot / pf, i = slot - k * pf;
+    if (k >= g.nstrips) return;
+    const long long n = tz_strip_bytes(g, k), at = i * DEFLATE_SEG;
+    if (at >= n) return;                                  // uniform: the whole workgroup leaves
+    const int m = (int)(n - at < DEFLATE_SEG ? n - at : DEFLATE_SEG);
+    deflate_segment(stored + k * g.rps * g.rowb + at, m, i == 0, at + m == n, Z + slot * DEFLATE_ZCAP, seglen + slot, adl + 2 * slot);
+}
+
+// One workgroup per strip: where each part starts within the strip's stream (an exclusive scan of the parts' lengths, 256 parts
+// per round, the sum carried on), the strip's length, and the Adler-32 of the strip behind its last part.  With a_i = sum of part
+// i's bytes and b_i = sum of (n_i - j) * byte_j, both mod 65521, and r_i bytes of the strip behind part i, the checksum's halves
+// are 1 + sum a_i and n + sum (b_i + r_i a_i), reduced mod 65521 at every step: no product exceeds 65520^2 < 2^32.
+__global__ __launch_bounds__(TZ_JOIN_THREADS) void k_tz_join(TeGeom g, long long pf, uint8_t *__restrict__ Z,
+                                                            const unsigned int *__restrict__ seglen, const unsigned int *__restrict__ adl,
+                                                            unsigned int *__restrict__ partoff, unsigned int *__restrict__ zlen)
+{
+    __shared__ unsigned int scan[TZ_JOIN_THREADS];
+    __shared__ unsigned long long a1[TZ_JOIN_THREADS], a2[TZ_JOIN_THREADS];
+    const int tid = threadIdx.x;
+    const long long k = blockIdx.x;
+    if (k >= g.nstrips) return;
+    const long long n = tz_strip_bytes(g, k), p = tz_parts(n), slot0 = k * pf;
+    unsigned int carry = 0;                               // a strip's stream has at most tz_strip_cap(2^30) < 2^32 bytes
+    unsigned long long A = 0, B = 0;
+    for (long long i0 = 0; i0 < p; i0 += TZ_JOIN_THREADS) {
+        const long long i = i0 + tid;
+        const unsigned int len = i < p ? seglen[slot0 + i] : 0u;
+        scan[tid] = len;
+        __syncthreads();
+        for (int d = 1; d < TZ_JOIN_THREADS; d <<= 1) {   // inclusive scan
+            const unsigned int v = tid >= d ? scan[tid - d] : 0u;
+            __syncthreads();
+            scan[tid] += v;
+            __syncthreads();
+        }
+        if (i < p) {
+            partoff[slot0 + i] = carry + scan[tid] - len;
+            const long long at = i * DEFLATE_SEG, ni = n - at < DEFLATE_SEG ? n - at : DEFLATE_SEG;
+            const unsigned long long after = (unsigned long long)(n - at - ni) % 65521ull;
+            A = (A + adl[2 * (slot0 + i)]) % 65521ull;
+            B = (B + adl[2 * (slot0 + i) + 1] + after * adl[2 * (slot0 + i)]) % 65521ull;
+        }
+        carry += scan[TZ_JOIN_THREADS - 1];
+        __syncthreads();
+    }
+    a1[tid] = A;
+    a2[tid] = B;
+    __syncthreads();
+    for (int half = TZ_JOIN_THREADS / 2; half > 0; half >>= 1) {
+        if (tid < half) { a1[tid] = (a1[tid] + a1[tid + half]) % 65521ull; a2[tid] = (a2[tid] + a2[tid + half]) % 65521ull; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const unsigned int s1 = (unsigned int)((1ull + a1[0]) % 65521ull);
+        const unsigned int s2 = (unsigned int)(((unsigned long long)n % 65521ull + a2[0]) % 65521ull);
+        uint8_t *zl = Z + (slot0 + p - 1) * DEFLATE_ZCAP + seglen[slot0 + p - 1] - 4;      // the last part's length counts these four
+        zl[0] = (uint8_t)(s2 >> 8); zl[1] = (uint8_t)s2; zl[2] = (uint8_t)(s1 >> 8); zl[3] = (uint8_t)s1;
+        zlen[k] = carry;
+    }
+}
+
+// one workgroup per (strip, part): the part's bytes to their place in the strip at off[strip]; the last part adds the pad byte
+__global__ __launch_bounds__(TE_PACK_THREADS) void k_tz_pack(TeGeom g, long long pf, const uint8_t *__restrict__ Z,
+                                                            const unsigned int *__restrict__ seglen, const unsigned int *__restrict__ partoff,
+                                                            const unsigned int *__restrict__ zlen, const unsigned long long *__restrict__ off,
+                                                            uint8_t *__restrict__ out, unsigned long long out_cap, const int *__restrict__ status)
+{
+    if (status[0]) return;
+    const long long slot = blockIdx.x, k = slot / pf, i = slot - k * pf;
+    if (k >= g.nstrips) return;
+    const long long n = tz_strip_bytes(g, k), p = tz_parts(n);
+    if (i >= p) return;
+    const unsigned int m = seglen[slot];
+    const unsigned long long o = off[k] + partoff[slot];
+    const bool pad = i == p - 1 && (zlen[k] & 1u);
+    if (m > (unsigned int)DEFLATE_ZCAP || o + m + (pad ? 1ull : 0ull) > out_cap) return;   // k_te_frame refused such a file
+    const uint8_t *src = Z + slot * DEFLATE_ZCAP;
+    uint8_t *dst = out + o;
+    for (unsigned int j = threadIdx.x; j < m; j += TE_PACK_THREADS) dst[j] = src[j];
+    if (pad && threadIdx.x == 0) dst[m] = 0;
 }
 
 // the strips of a picture, or false for a shape that is not encoded; itemsize 1 or 2: unsigned integers; 4, which only the
@@ -339,29 +471,66 @@ int te_check(const char *who, bool pointers, int64_t h, int64_t w, int channels,
     return LARS_OK;
 }
 
+// Deflate: the slots of the parts (pf per strip), the staged picture, and what the join step leaves
+struct TzPlan {
+    long long pf, slots, chunks;   // chunks: workgroups of k_tz_stage per row
+    uint8_t *stage, *z;
+    unsigned int *seglen, *adl, *partoff, *zlen;
+    unsigned long long *off;
+};
+
+TzPlan tz_plan(const TeGeom &g, Carver &cv)
+{
+    TzPlan P;
+    P.pf = tz_parts((long long)g.rps * g.rowb);
+    P.slots = g.nstrips * P.pf;
+    P.chunks = (g.rowb + TZ_STAGE_BYTES - 1) / TZ_STAGE_BYTES;
+    P.stage = cv.take<uint8_t>((size_t)g.height * (size_t)g.rowb);      // used with a predictor only; the size does not ask
+    P.z = cv.take<uint8_t>((size_t)P.slots * DEFLATE_ZCAP);
+    P.seglen = cv.take<unsigned int>((size_t)P.slots);
+    P.adl = cv.take<unsigned int>((size_t)P.slots * 2);
+    P.partoff = cv.take<unsigned int>((size_t)P.slots);
+    P.zlen = cv.take<unsigned int>((size_t)g.nstrips);
+    P.off = cv.take<unsigned long long>((size_t)g.nstrips);
+    return P;
+}
+
+// te_bound with the Deflate strips: tz_strip_cap per strip (the last one may be shorter), the header, the directory at its
+// largest, BitsPerSample and SampleFormat arrays, StripOffsets and StripByteCounts
+size_t tz_bound(const TeGeom &g)
+{
+    const long long last = ((long long)g.height - (g.nstrips - 1) * g.rps) * g.rowb;
+    return 8 + (size_t)((g.nstrips - 1) * tz_strip_cap((long long)g.rps * g.rowb) + tz_strip_cap(last)) + 2 + 12 * TE_MAX_ENTRIES + 4 +
+           4 * (size_t)g.spp + 8 * (size_t)g.nstrips;
+}
+
 }  // namespace
 
 }  // namespace lars
 
 using namespace lars;
 
-static size_t bound_of(int64_t h, int64_t w, int channels, int itemsize, bool f32, int64_t rows_per_strip)
+// compression: TIFF's own codes, 5 (LZW) or 8 (Deflate)
+static size_t bound_of(int64_t h, int64_t w, int channels, int itemsize, bool f32, int64_t rows_per_strip, int compression = 5)
 {
     TeGeom g;
-    return te_geometry(h, w, channels, itemsize, f32, rows_per_strip, 0, &g) ? te_bound(g) : 0;
+    if (!te_geometry(h, w, channels, itemsize, f32, rows_per_strip, 0, &g)) return 0;
+    return compression == 8 ? tz_bound(g) : te_bound(g);
 }
 
-static size_t scratch_of(int64_t h, int64_t w, int channels, int itemsize, bool f32, int64_t rows_per_strip)
+static size_t scratch_of(int64_t h, int64_t w, int channels, int itemsize, bool f32, int64_t rows_per_strip, int compression = 5)
 {
     TeGeom g;
     if (!te_geometry(h, w, channels, itemsize, f32, rows_per_strip, 0, &g)) return 0;
     Carver size(nullptr);
-    te_plan(g, size);
+    if (compression == 8) tz_plan(g, size);
+    else te_plan(g, size);
     return size.bytes();
 }
 
 static int encode_on_device(const char *who, const void *img, int64_t h, int64_t w, int channels, int itemsize, bool f32, int64_t rows_per_strip,
-                            int predictor, uint8_t *out, size_t out_cap, int64_t *out_len_dev, int32_t *status_dev, void *scratch, void *stream)
+                            int predictor, uint8_t *out, size_t out_cap, int64_t *out_len_dev, int32_t *status_dev, void *scratch, void *stream,
+                            int compression = 5)
 {
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
@@ -369,12 +538,32 @@ static int encode_on_device(const char *who, const void *img, int64_t h, int64_t
     LARS_TRY(te_check(who, img && out && out_len_dev && status_dev && scratch, h, w, channels, itemsize, f32, rows_per_strip, predictor, &g));
     if (((uintptr_t)img | (uintptr_t)out) & 1) return fail(LARS_ERR_INVALID, "%s: img and out must be on even addresses", who);
     Carver cv(scratch);
+    if (compression == 8) {
+        const TzPlan P = tz_plan(g, cv);
+        if (P.slots >= (1ll << 31) || (long long)g.height * P.chunks >= (1ll << 31))
+            return fail(LARS_ERR_UNSUPPORTED, "%s: %lld parts of strips, %lld rows of %lld bytes", who, P.slots, (long long)g.height, g.rowb);
+        hipStream_t s = pick_stream(c, stream);
+        LARS_HIP_TRY(hipMemsetAsync(status_dev, 0, 2 * sizeof(int32_t), s));
+        LARS_HIP_TRY(hipMemsetAsync(out_len_dev, 0, sizeof(int64_t), s));
+        const uint8_t *stored = static_cast<const uint8_t *>(img);      // little-endian host: without a predictor the samples are the stored bytes
+        if (g.predictor) {
+            hipLaunchKernelGGL(k_tz_stage, dim3((unsigned)(g.height * P.chunks)), dim3(TZ_STAGE_THREADS), 0, s, stored, g, P.chunks, P.stage);
+            stored = P.stage;
+        }
+        hipLaunchKernelGGL(k_tz_deflate, dim3((unsigned)P.slots), dim3(DEFLATE_THREADS), 0, s, stored, g, P.pf, P.z, P.seglen, P.adl);
+        hipLaunchKernelGGL(k_tz_join, dim3((unsigned)g.nstrips), dim3(TZ_JOIN_THREADS), 0, s, g, P.pf, P.z, P.seglen, P.adl, P.partoff, P.zlen);
+        hipLaunchKernelGGL(k_te_frame, dim3(1), dim3(TE_FRAME_THREADS), 0, s, g, 8, P.zlen, P.off, out, (unsigned long long)out_cap,
+                           reinterpret_cast<long long *>(out_len_dev), status_dev);
+        hipLaunchKernelGGL(k_tz_pack, dim3((unsigned)P.slots), dim3(TE_PACK_THREADS), 0, s, g, P.pf, P.z, P.seglen, P.partoff, P.zlen, P.off, out,
+                           (unsigned long long)out_cap, status_dev);
+        return launch_check(who);
+    }
     const TePlan P = te_plan(g, cv);
     hipStream_t s = pick_stream(c, stream);
     LARS_HIP_TRY(hipMemsetAsync(status_dev, 0, 2 * sizeof(int32_t), s));
     LARS_HIP_TRY(hipMemsetAsync(out_len_dev, 0, sizeof(int64_t), s));
     hipLaunchKernelGGL(k_te_lzw, dim3((unsigned)g.nstrips), dim3(64), 0, s, static_cast<const uint8_t *>(img), g, P.zbuf, P.zlen, status_dev);
-    hipLaunchKernelGGL(k_te_frame, dim3(1), dim3(TE_FRAME_THREADS), 0, s, g, P.zlen, P.off, out, (unsigned long long)out_cap,
+    hipLaunchKernelGGL(k_te_frame, dim3(1), dim3(TE_FRAME_THREADS), 0, s, g, 5, P.zlen, P.off, out, (unsigned long long)out_cap,
                        reinterpret_cast<long long *>(out_len_dev), status_dev);
     hipLaunchKernelGGL(k_te_pack, dim3((unsigned)g.nstrips), dim3(TE_PACK_THREADS), 0, s, g, P.zbuf, P.zlen, P.off, out,
                        (unsigned long long)out_cap, status_dev);
@@ -383,15 +572,16 @@ static int encode_on_device(const char *who, const void *img, int64_t h, int64_t
 
 // host picture in, file out: one upload, then the status and the length (one small read), then the file's bytes
 static int encode_to_host_tiff(const char *who, const void *img, int64_t h, int64_t w, int channels, int itemsize, bool f32,
-                               int64_t rows_per_strip, int predictor, uint8_t *out, size_t out_cap, int64_t *out_len)
+                               int64_t rows_per_strip, int predictor, uint8_t *out, size_t out_cap, int64_t *out_len, int compression = 5)
 {
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     TeGeom g;
     LARS_TRY(te_check(who, img && out && out_len, h, w, channels, itemsize, f32, rows_per_strip, predictor, &g));
-    const size_t in_bytes = (size_t)h * g.rowb, dev_cap = std::min(te_bound(g), out_cap);
+    const size_t in_bytes = (size_t)h * g.rowb, dev_cap = std::min(compression == 8 ? tz_bound(g) : te_bound(g), out_cap);
     Carver size(nullptr);
-    te_plan(g, size);
+    if (compression == 8) tz_plan(g, size);
+    else te_plan(g, size);
     struct Answer { int64_t len; int32_t status[2]; } a = {0, {0, 0}}, *d_a;
     uint8_t *d_in, *d_out;
     char *d_scr;
@@ -403,7 +593,8 @@ static int encode_to_host_tiff(const char *who, const void *img, int64_t h, int6
     }));
     hipStream_t s = c->stream;
     LARS_HIP_TRY(hipMemcpyAsync(d_in, img, in_bytes, hipMemcpyHostToDevice, s));
-    LARS_TRY(encode_on_device(who, d_in, h, w, channels, itemsize, f32, g.rps, predictor, d_out, dev_cap, &d_a->len, d_a->status, d_scr, s));
+    LARS_TRY(encode_on_device(who, d_in, h, w, channels, itemsize, f32, g.rps, predictor, d_out, dev_cap, &d_a->len, d_a->status, d_scr, s,
+                              compression));
     LARS_HIP_TRY(hipMemcpyAsync(&a, d_a, sizeof a, hipMemcpyDeviceToHost, s));
     LARS_HIP_TRY(hipStreamSynchronize(s));
     switch (a.status[0]) {
@@ -464,6 +655,54 @@ int lars_h_encode_tiff_f32(const float *img, int64_t h, int64_t w, int channels,
                            size_t out_cap, int64_t *out_len)
 {
     return encode_to_host_tiff("lars_h_encode_tiff_f32", img, h, w, channels, 4, true, rows_per_strip, predictor, out, out_cap, out_len);
+}
+
+// Deflate (Compression 8): the same arguments, strips, knob, status codes and 4 GiB refusal; only the strips' streams differ
+size_t lars_tiff_deflate_bound(int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip)
+{
+    return bound_of(h, w, channels, itemsize, false, rows_per_strip, 8);
+}
+
+size_t lars_tiff_deflate_encode_scratch_bytes(int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip)
+{
+    return scratch_of(h, w, channels, itemsize, false, rows_per_strip, 8);
+}
+
+int lars_d_encode_tiff_deflate(const void *img, int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip, int predictor,
+                               uint8_t *out, size_t out_cap, int64_t *out_len_dev, int32_t *status_dev, void *scratch, void *stream)
+{
+    return encode_on_device("lars_d_encode_tiff_deflate", img, h, w, channels, itemsize, false, rows_per_strip, predictor, out, out_cap,
+                            out_len_dev, status_dev, scratch, stream, 8);
+}
+
+int lars_h_encode_tiff_deflate(const void *img, int64_t h, int64_t w, int channels, int itemsize, int64_t rows_per_strip, int predictor,
+                               uint8_t *out, size_t out_cap, int64_t *out_len)
+{
+    return encode_to_host_tiff("lars_h_encode_tiff_deflate", img, h, w, channels, itemsize, false, rows_per_strip, predictor, out, out_cap,
+                               out_len, 8);
+}
+
+size_t lars_tiff_float32_deflate_bound(int64_t h, int64_t w, int channels, int64_t rows_per_strip)
+{
+    return bound_of(h, w, channels, 4, true, rows_per_strip, 8);
+}
+
+size_t lars_tiff_float32_deflate_encode_scratch_bytes(int64_t h, int64_t w, int channels, int64_t rows_per_strip)
+{
+    return scratch_of(h, w, channels, 4, true, rows_per_strip, 8);
+}
+
+int lars_d_encode_tiff_deflate_float32(const float *img, int64_t h, int64_t w, int channels, int64_t rows_per_strip, int predictor, uint8_t *out,
+                                   size_t out_cap, int64_t *out_len_dev, int32_t *status_dev, void *scratch, void *stream)
+{
+    return encode_on_device("lars_d_encode_tiff_deflate_float32", img, h, w, channels, 4, true, rows_per_strip, predictor, out, out_cap, out_len_dev,
+                            status_dev, scratch, stream, 8);
+}
+
+int lars_h_encode_tiff_deflate_float32(const float *img, int64_t h, int64_t w, int channels, int64_t rows_per_strip, int predictor, uint8_t *out,
+                                   size_t out_cap, int64_t *out_len)
+{
+    return encode_to_host_tiff("lars_h_encode_tiff_deflate_float32", img, h, w, channels, 4, true, rows_per_strip, predictor, out, out_cap, out_len, 8);
 }
 
 }  // extern "C"

@@ -29,7 +29,7 @@ PNG_ENCODERS = ("pillow", "device")
 PNG_DECODERS = ("pillow", "device", "device+extended")
 JPEG_DECODERS = ("pillow", "device")
 TIFF_DECODERS = ("pillow", "device", "device+deflate")
-TIFF_ENCODERS = ("pillow", "device")
+TIFF_ENCODERS = ("pillow", "device", "device+deflate")
 
 
 def _check_png_encoder(png_encoder):
@@ -54,7 +54,7 @@ def _check_tiff_decoder(tiff_decoder):
 
 def _check_tiff_encoder(tiff_encoder):
     if tiff_encoder not in TIFF_ENCODERS:
-        raise ValueError(f"tiff_encoder must be 'pillow' or 'device', got {tiff_encoder!r}")
+        raise ValueError(f"tiff_encoder must be 'pillow' or 'device' ('device+deflate' for Deflate strips), got {tiff_encoder!r}")
 
 
 def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png",
@@ -76,7 +76,9 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     the GPU (``api.encode_tiff``: LZW strips, the same samples): ``<name>_wb.tif`` instead of Pillow's uncompressed file, and the
     ``lut_format="tiff"`` pictures instead of ``tiffio.write_tiff``'s uncompressed ones.  ``index_tiff=True`` also writes the
     index plane itself, ``<INDEX>/<name>_<index>_f32.tif``: a single-band float32 LZW TIFF with Predictor 3, encoded on the
-    GPU (``api.encode_tiff_f32``), the exact values the picture only colours; every other output is the same file."""
+    GPU (``api.encode_tiff_f32``), the exact values the picture only colours; every other output is the same file.
+    ``tiff_encoder="device+deflate"`` is ``"device"`` with Deflate strips (Compression 8, ``compression="deflate"``), and the
+    ``index_tiff`` file follows it: Deflate with Predictor 3."""
     if lut_format not in ("png", "png8", "tiff"):
         raise ValueError(f"lut_format must be 'png', 'png8' or 'tiff', got {lut_format!r}")
     _check_png_encoder(png_encoder)
@@ -95,14 +97,16 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     palette = lut_format == "png8"
     device_png = png_encoder == "device" and lut_format != "tiff"
     planes = None                                   # the call whose entries hold the float32 TIFF files
+    compression = "deflate" if tiff_encoder == "device+deflate" else "lzw"
+    plane_tiff = "deflate+predictor" if compression == "deflate" else "predictor"
     if device_png:                                  # the pictures stay on the device, their PNG files come back
         res = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False,
                                 want_png="palette" if palette else True) if indices else None
         if index_tiff and indices:                  # one kind of file per call
-            planes = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False, want_tiff="predictor")
+            planes = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False, want_tiff=plane_tiff)
     elif index_tiff and indices:
         res = planes = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False, want_rgba=not palette,
-                                         want_entries=palette, want_tiff="predictor")
+                                         want_entries=palette, want_tiff=plane_tiff)
     else:
         # palette files: the colormap entry of every pixel comes from the device, one byte per pixel (lars_h_process_image)
         res = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False, want_rgba=not palette,
@@ -111,8 +115,8 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     if process_wb:
         (output_dir / "white_balanced").mkdir(parents=True, exist_ok=True)
         wb = corrected[:, :, :3] if corrected.shape[2] > 4 else corrected
-        if tiff_encoder == "device":
-            (output_dir / "white_balanced" / f"{name}_wb.tif").write_bytes(api.encode_tiff(wb))
+        if tiff_encoder != "pillow":
+            (output_dir / "white_balanced" / f"{name}_wb.tif").write_bytes(api.encode_tiff(wb, compression=compression))
         else:
             Image.fromarray(wb).save(output_dir / "white_balanced" / f"{name}_wb.tif")
     stats = {}
@@ -123,8 +127,8 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
         if device_png:
             out.write_bytes(entry["png"])
         elif lut_format == "tiff":
-            if tiff_encoder == "device":
-                out.with_suffix(".tif").write_bytes(api.encode_tiff(entry["rgba"]))
+            if tiff_encoder != "pillow":
+                out.with_suffix(".tif").write_bytes(api.encode_tiff(entry["rgba"], compression=compression))
             else:
                 from .tiffio import write_tiff
                 write_tiff(out.with_suffix(".tif"), entry["rgba"])
@@ -267,7 +271,8 @@ def main(argv=None):
                     help="'device' decodes supported TIFF inputs on the GPU (same samples; other files take today's path); "
                          "'device+deflate' decodes Deflate TIFF files there too")
     ap.add_argument("--tiff-encoder", default="pillow", choices=list(TIFF_ENCODERS),
-                    help="'device' builds <name>_wb.tif and the --lut-format tiff pictures on the GPU (LZW strips, same samples)")
+                    help="'device' builds <name>_wb.tif and the --lut-format tiff pictures on the GPU (LZW strips, same samples); "
+                         "'device+deflate' the same with Deflate strips, also for --index-tiff")
     ap.add_argument("--index-tiff", action="store_true",
                     help="also write <INDEX>/<name>_<index>_f32.tif: the float32 index plane as an LZW TIFF with Predictor 3, built on the GPU")
     ap.add_argument("--quiet", action="store_true")

@@ -16,7 +16,11 @@ predictor next to Pillow's ``Image.fromarray(plane).save(format="TIFF", compress
 the tag), file sizes of both; and ``process_image(want_tiff=...)``, where the planes never leave the device, next to the same
 call with ``want_arrays=True`` followed by ``encode_tiff_f32`` on the three host planes, in the same process.
 
-    python tools/tiffencodebench.py [--legs picture] [--files 20] [--runs 2] [--split] [--sweep] [--gpu-only] [--json out.json]
+``--compression deflate`` runs every leg with ``compression="deflate"`` (``want_tiff="deflate+predictor"``) next to Pillow's
+``compression="tiff_adobe_deflate"`` instead, ``--compression both`` the LZW legs and then the Deflate legs in the same run, by
+the same rules; the Deflate entries carry ``_deflate`` in their names.
+
+    python tools/tiffencodebench.py [--legs picture] [--compression lzw] [--files 20] [--runs 2] [--split] [--sweep] [--gpu-only] [--json out.json]
 
 Kernel times come from a separate run:  rocprofv3 --kernel-trace --stats -- python tools/tiffencodebench.py --gpu-only
 """
@@ -47,9 +51,12 @@ def many_pictures(shape, n, seed):
     return [np.ascontiguousarray(np.roll(base[k % len(base)], (97 * (k // len(base)), 131 * (k // len(base))), (0, 1))) for k in range(n)]
 
 
-def pil_tiff(a, predictor=False):
+PILLOW = {"lzw": "tiff_lzw", "deflate": "tiff_adobe_deflate"}
+
+
+def pil_tiff(a, predictor=False, compression="lzw"):
     b = io.BytesIO()
-    Image.fromarray(a).save(b, format="TIFF", compression="tiff_lzw", **({"tiffinfo": {317: 2}} if predictor else {}))
+    Image.fromarray(a).save(b, format="TIFF", compression=PILLOW[compression], **({"tiffinfo": {317: 2}} if predictor else {}))
     return b.getvalue()
 
 
@@ -72,12 +79,14 @@ def per_picture_ms(fn, arrays, gpu, runs):
     return min(best)
 
 
-def split_ms(a, predictor, reps=20):
+def split_ms(a, predictor, reps=20, compression="lzw"):
     """The parts of one encode_tiff call, each timed on its own (median): upload of the picture, the kernels from a resident
     picture into a resident file (lars_d_encode_tiff), download of the file's bytes."""
     lib = _ffi.load()
     h, w, c = a.shape
-    cap, need = lib.lars_tiff_bound(h, w, c, 1, 0), lib.lars_tiff_encode_scratch_bytes(h, w, c, 1, 0)
+    mid = "_deflate" if compression == "deflate" else ""
+    cap = getattr(lib, f"lars_tiff{mid}_bound")(h, w, c, 1, 0)
+    need = getattr(lib, f"lars_tiff{mid}_encode_scratch_bytes")(h, w, c, 1, 0)
 
     def med(fn):
         fn()
@@ -97,7 +106,7 @@ def split_ms(a, predictor, reps=20):
     _ffi.call("lars_malloc", C.byref(d_ans), 16)
     try:
         upload = med(lambda: _ffi.call("lars_memcpy_h2d", d_in, _ffi.ptr(a), a.nbytes))
-        device = med(lambda: _ffi.call("lars_d_encode_tiff", d_in, h, w, c, 1, 0, int(predictor), d_out, cap, d_ans, C.c_void_p(d_ans.value + 8),
+        device = med(lambda: _ffi.call("lars_d_encode_tiff" + mid, d_in, h, w, c, 1, 0, int(predictor), d_out, cap, d_ans, C.c_void_p(d_ans.value + 8),
                                        d_scratch, None))
         n = np.zeros(2, np.int64)
         _ffi.call("lars_memcpy_d2h", _ffi.ptr(n), d_ans, 16)
@@ -111,9 +120,9 @@ def split_ms(a, predictor, reps=20):
     return {"upload_ms": upload, "device_encode_ms": device, "download_ms": download}
 
 
-def pil_float_tiff(a, predictor=False):
+def pil_float_tiff(a, predictor=False, compression="lzw"):
     b = io.BytesIO()
-    Image.fromarray(a).save(b, format="TIFF", compression="tiff_lzw", **({"tiffinfo": {317: 3}} if predictor else {}))
+    Image.fromarray(a).save(b, format="TIFF", compression=PILLOW[compression], **({"tiffinfo": {317: 3}} if predictor else {}))
     return b.getvalue()
 
 
@@ -121,38 +130,45 @@ def same_bits(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-def float_leg(args, res):
+def float_leg(args, res, comp="lzw"):
     """encode_tiff_f32 on NDVI planes, and process_image(want_tiff=...) against planes that come back and go up again."""
+    deflate = comp == "deflate"
+    tag = "_deflate" if deflate else ""
+
+    def decode(b):
+        return lars.decode_tiff(b, deflate=True) if deflate else lars.decode_tiff(b)
+
     for name, shape in (("ndvi_4096x4096_f32", (4096, 4096)), ("ndvi_2048x1536_f32", (1536, 2048))):
         rgb = many_pictures(shape, min(args.files, DISTINCT), seed=11)
         planes = [lars.calculate_index(a, "NDVI") for a in rgb]
         for predictor in (False, True):
-            files = [lars.encode_tiff_f32(a, predictor=predictor) for a in planes[:2]]
+            files = [lars.encode_tiff_f32(a, predictor=predictor, compression=comp) for a in planes[:2]]
             for a, b in zip(planes, files):                    # a fast wrong answer is no answer
-                assert same_bits(tiffio.read_tiff(b), a) and same_bits(np.asarray(Image.open(io.BytesIO(b))), a) and same_bits(lars.decode_tiff(b), a)
+                assert same_bits(tiffio.read_tiff(b), a) and same_bits(np.asarray(Image.open(io.BytesIO(b))), a) and same_bits(decode(b), a)
             r = {"files": len(planes), "mean_file_bytes": int(np.mean([len(b) for b in files])), "shape": list(shape), "plane_bytes": planes[0].nbytes,
                  "strips": len(tiffio._read_ifd(memoryview(files[0]), "<")[tiffio.STRIP_OFFSETS]),
-                 "encode_tiff_f32_ms": per_picture_ms(lambda a: lars.encode_tiff_f32(a, predictor=predictor), planes, True, args.runs)}
+                 "encode_tiff_f32_ms": per_picture_ms(lambda a: lars.encode_tiff_f32(a, predictor=predictor, compression=comp), planes, True,
+                                                      args.runs)}
             if not args.gpu_only:
-                pil = pil_float_tiff(planes[0], predictor)
+                pil = pil_float_tiff(planes[0], predictor, comp)
                 r["pillow_file_bytes"] = len(pil)
                 r["pillow_strips"] = len(tiffio._read_ifd(memoryview(pil), "<")[tiffio.STRIP_OFFSETS])
                 r["same_strips_as_pillow"] = bool(tiffio._read_ifd(memoryview(pil), "<")[tiffio.STRIP_BYTE_COUNTS] ==
                                                   tiffio._read_ifd(memoryview(files[0]), "<")[tiffio.STRIP_BYTE_COUNTS])
-                r["pillow_save_ms"] = per_picture_ms(lambda a: pil_float_tiff(a, predictor), planes, False, args.runs)
+                r["pillow_save_ms"] = per_picture_ms(lambda a: pil_float_tiff(a, predictor, comp), planes, False, args.runs)
                 r["encode_speedup"] = r["pillow_save_ms"] / r["encode_tiff_f32_ms"]
-            key = name + ("_predictor3" if predictor else "")
+            key = name + tag + ("_predictor3" if predictor else "")
             res["kinds"][key] = r
             print(key, json.dumps(r), flush=True)
         # the three index planes of one picture as files: on the device all the way, or down as arrays and up again
-        mode = "predictor"
+        mode = "deflate+predictor" if deflate else "predictor"
 
         def on_device(a):
             return lars.process_image(a, want_arrays=False, want_tiff=mode)
 
         def through_host(a):
             got = lars.process_image(a, want_arrays=True)
-            return {t: lars.encode_tiff_f32(got["indices"][t]["index"], predictor=True) for t in got["indices"]}
+            return {t: lars.encode_tiff_f32(got["indices"][t]["index"], predictor=True, compression=comp) for t in got["indices"]}
 
         one, two = on_device(rgb[0]), through_host(rgb[0])
         assert all(one["indices"][t]["tiff"] == two[t] for t in two)
@@ -160,8 +176,8 @@ def float_leg(args, res):
              "process_image_want_tiff_ms": per_picture_ms(on_device, rgb, True, args.runs),
              "process_image_arrays_then_encode_ms": per_picture_ms(through_host, rgb, True, args.runs)}
         r["speedup"] = r["process_image_arrays_then_encode_ms"] / r["process_image_want_tiff_ms"]
-        res["kinds"][name + "_process_image"] = r
-        print(name + "_process_image", json.dumps(r), flush=True)
+        res["kinds"][name + tag + "_process_image"] = r
+        print(name + tag + "_process_image", json.dumps(r), flush=True)
 
 
 def main():
@@ -173,6 +189,8 @@ def main():
     ap.add_argument("--sweep", action="store_true", help='also sweep "tiff_strip_bytes"')
     ap.add_argument("--legs", choices=["picture", "float", "all"], default="picture",
                     help="picture: the RGB pictures through encode_tiff; float: NDVI planes through encode_tiff_f32; all: both")
+    ap.add_argument("--compression", choices=["lzw", "deflate", "both"], default="lzw",
+                    help="lzw: the LZW legs; deflate: the same legs with compression=\"deflate\"; both: one after the other in the same run")
     ap.add_argument("--json", help="also write the figures to this file")
     args = ap.parse_args()
     if _ffi.device_count() < 1:
@@ -180,38 +198,44 @@ def main():
     import PIL
     res = {"device": _ffi.device_name(), "pillow": PIL.__version__, "files": args.files, "runs": args.runs,
            "tiff_strip_bytes": _ffi.get_tuning("tiff_strip_bytes"), "kinds": {}}
-    if args.legs in ("float", "all"):
-        float_leg(args, res)
-    for name, shape in KINDS.items() if args.legs in ("picture", "all") else ():
-        arrays = many_pictures(shape, args.files, seed=11)
-        for predictor in (False, True):
-            files = [lars.encode_tiff(a, predictor=predictor) for a in arrays[:DISTINCT]]
-            for a, b in list(zip(arrays, files))[:2]:          # a fast wrong answer is no answer
-                assert np.array_equal(tiffio.read_tiff(b), a) and np.array_equal(np.asarray(Image.open(io.BytesIO(b))), a)
-            r = {"files": len(arrays), "mean_file_bytes": int(np.mean([len(b) for b in files])), "shape": [shape[0], shape[1], 3],
-                 "strips": len(tiffio._read_ifd(memoryview(files[0]), "<")[tiffio.STRIP_OFFSETS]),
-                 "encode_tiff_ms": per_picture_ms(lambda a: lars.encode_tiff(a, predictor=predictor), arrays, True, args.runs)}
-            if not args.gpu_only:
-                pil = pil_tiff(arrays[0], predictor)
-                r["pillow_file_bytes"] = len(pil)
-                r["pillow_strips"] = len(tiffio._read_ifd(memoryview(pil), "<")[tiffio.STRIP_OFFSETS])
-                r["pillow_save_ms"] = per_picture_ms(lambda a: pil_tiff(a, predictor), arrays, False, args.runs)
-                r["encode_speedup"] = r["pillow_save_ms"] / r["encode_tiff_ms"]
-            if args.split:
-                r["split"] = split_ms(arrays[0], predictor)
-            if args.sweep:
-                r["sweep_encode_tiff_ms"] = {}
-                for v in SWEEP:
-                    with _ffi.tuning(tiff_strip_bytes=v):
-                        r["sweep_encode_tiff_ms"][str(v)] = per_picture_ms(lambda a: lars.encode_tiff(a, predictor=predictor),
-                                                                           arrays[:DISTINCT + 1], True, args.runs)
-            key = name + ("_predictor" if predictor else "")
-            res["kinds"][key] = r
-            print(key, json.dumps(r), flush=True)
+    for comp in ("lzw", "deflate") if args.compression == "both" else (args.compression,):
+        picture_and_float_legs(args, res, comp)
     if args.json:
         with open(args.json, "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
+
+
+def picture_and_float_legs(args, res, comp):
+    deflate = comp == "deflate"
+    if args.legs in ("float", "all"):
+        float_leg(args, res, comp)
+    for name, shape in KINDS.items() if args.legs in ("picture", "all") else ():
+        arrays = many_pictures(shape, args.files, seed=11)
+        for predictor in (False, True):
+            files = [lars.encode_tiff(a, predictor=predictor, compression=comp) for a in arrays[:DISTINCT]]
+            for a, b in list(zip(arrays, files))[:2]:          # a fast wrong answer is no answer
+                assert np.array_equal(tiffio.read_tiff(b), a) and np.array_equal(np.asarray(Image.open(io.BytesIO(b))), a)
+            r = {"files": len(arrays), "mean_file_bytes": int(np.mean([len(b) for b in files])), "shape": [shape[0], shape[1], 3],
+                 "strips": len(tiffio._read_ifd(memoryview(files[0]), "<")[tiffio.STRIP_OFFSETS]),
+                 "encode_tiff_ms": per_picture_ms(lambda a: lars.encode_tiff(a, predictor=predictor, compression=comp), arrays, True, args.runs)}
+            if not args.gpu_only:
+                pil = pil_tiff(arrays[0], predictor, comp)
+                r["pillow_file_bytes"] = len(pil)
+                r["pillow_strips"] = len(tiffio._read_ifd(memoryview(pil), "<")[tiffio.STRIP_OFFSETS])
+                r["pillow_save_ms"] = per_picture_ms(lambda a: pil_tiff(a, predictor, comp), arrays, False, args.runs)
+                r["encode_speedup"] = r["pillow_save_ms"] / r["encode_tiff_ms"]
+            if args.split:
+                r["split"] = split_ms(arrays[0], predictor, compression=comp)
+            if args.sweep:
+                r["sweep_encode_tiff_ms"] = {}
+                for v in SWEEP:
+                    with _ffi.tuning(tiff_strip_bytes=v):
+                        r["sweep_encode_tiff_ms"][str(v)] = per_picture_ms(lambda a: lars.encode_tiff(a, predictor=predictor, compression=comp),
+                                                                           arrays[:DISTINCT + 1], True, args.runs)
+            key = name + ("_deflate" if deflate else "") + ("_predictor" if predictor else "")
+            res["kinds"][key] = r
+            print(key, json.dumps(r), flush=True)
 
 
 if __name__ == "__main__":
