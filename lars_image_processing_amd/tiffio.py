@@ -454,17 +454,17 @@ def read_image(path, full_depth=False, png_decoder="pillow", jpeg_decoder="pillo
         raise ValueError(f"tiff_decoder must be 'pillow', 'device' or 'device+deflate', got {tiff_decoder!r}")
     p = str(path)
     if tiff_decoder != "pillow" and p.lower().endswith((".tif", ".tiff")):
-        from . import api
+        from . import api, codecs
         with open(p, "rb") as f:
             data = f.read()
         # a file without the byte-order mark (a PNG under a .tif name, say) or with a broken directory is not the decoder's
         if data[:2] in (b"II", b"MM"):
             try:
-                i = api._tiff_info(np.frombuffer(data, dtype=np.uint8), tiff_decoder == "device+deflate")
+                i = codecs._tiff_info(np.frombuffer(data, dtype=np.uint8), tiff_decoder == "device+deflate")
             except ValueError:
                 i = None
             if i is not None and i.supported:
-                if (full_depth and i.bits == 16 and i.samples > 1) or (not full_depth and api._tiff_is_pillow_u8(i)):
+                if (full_depth and i.bits == 16 and i.samples > 1) or (not full_depth and codecs._tiff_is_pillow_u8(i)):
                     return api.decode_tiff(data, deflate=True) if tiff_decoder == "device+deflate" else api.decode_tiff(data)
     if jpeg_decoder == "device" and p.lower().endswith((".jpg", ".jpeg")):
         from . import api

@@ -77,7 +77,7 @@ def header_enum(prefix):
 def test_info_field_order_matches_header():
     """The Python names of lars_png_info's / lars_jpeg_info's info[] (_ffi.PngInfo, _ffi.JpegInfo) stand at the positions the
     header's LARS_PNG_INFO_* / LARS_JPEG_INFO_* enumerators give, and api's table of reasons follows LARS_JPEG_REASON_*."""
-    from lars_image_processing_amd import api
+    from lars_image_processing_amd import codecs
     text = open(os.path.join(ROOT, "include", "lars_hip.h")).read()
     png, jpeg = header_enum("LARS_PNG_INFO_"), header_enum("LARS_JPEG_INFO_")
     assert len(png) == len(_ffi.PngInfo._fields) == int(re.search(r"#define LARS_PNG_INFO_N (\d+)", text).group(1)) == 10
@@ -95,7 +95,7 @@ def test_info_field_order_matches_header():
     assert len(_ffi.PngInfo.array()) == 10 and len(_ffi.JpegInfo.array()) == 16
     reasons = header_enum("LARS_JPEG_REASON_")
     assert sorted(reasons.values()) == list(range(len(reasons))) and len(reasons) == 10
-    assert list(api._JPEG_REASONS) == sorted(reasons, key=reasons.get)
+    assert list(codecs._JPEG_REASONS) == sorted(reasons, key=reasons.get)
 
 
 def test_struct_layouts_match_header():

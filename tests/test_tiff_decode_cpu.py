@@ -14,7 +14,7 @@ from PIL import Image
 import tiff_cases as tc
 import tiff_lzw_model as model
 from conftest import ROOT
-from lars_image_processing_amd import _ffi, api, tiffio
+from lars_image_processing_amd import _ffi, api, codecs, tiffio
 from test_tiffio import lzw_encode, sample
 
 
@@ -264,6 +264,6 @@ def test_info_field_order_matches_header():
         assert _ffi.TiffInfo._fields[k] == name.lower(), (name, k)
     reasons = header_enum("LARS_TIFF_REASON_")
     assert sorted(reasons.values()) == list(range(len(reasons))) and len(reasons) == 12
-    assert list(api._TIFF_REASONS) == sorted(reasons, key=reasons.get)
+    assert list(codecs._TIFF_REASONS) == sorted(reasons, key=reasons.get)
     for name in ("lars_tiff_info", "lars_h_decode_tiff", "lars_h_thumbnail_tiff_u8"):
         assert name in _ffi.SIGNATURES and hasattr(_ffi.load(), name)

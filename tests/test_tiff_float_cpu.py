@@ -14,7 +14,7 @@ from PIL import Image
 import lars_image_processing_amd as lars
 import lzw_writer as lz
 import tiff_float_model as fm
-from lars_image_processing_amd import _ffi, api, tiffio
+from lars_image_processing_amd import _ffi, api, codecs, tiffio
 from test_abi_cpu import exported_symbols, header_symbols
 from test_tiff_decode_cpu import agree, asan_bin, fnv  # noqa: F401  (asan_bin is a fixture)
 
@@ -216,7 +216,7 @@ def patched(blob, tag, value):
 
 
 def test_refusals_that_stay(tmp_path):
-    reasons = api._TIFF_REASONS
+    reasons = codecs._TIFF_REASONS
     f32 = written(fm.values("smooth", (8, 8), 0), predictor=3)
     assert api.tiff_info(f32)["supported"]
     # predictor 3 without float samples
