@@ -457,7 +457,9 @@ int lars_h_colormap_norm_f32(const float *x, int64_t n, float vmin, float vmax, 
  * 1 (L, or P when palette_rgba is given: palette_len RGBA entries, written as PLTE + tRNS), 3 (RGB) or 4 (RGBA); 8 bits,
  * no interlace, 1 <= h, w <= 2^24.  The pixels decode exactly to img; the compressed bytes are this library's own (libpng's
  * filter heuristic per row, one literal-only dynamic Huffman block per 32 KiB of filtered data, one IDAT chunk each).  The
- * same input always gives the same bytes.
+ * same input always gives the same bytes.  With the knob deflate_matching at 1 (lars_set_tuning: 0 or 1, default 0) the coder
+ * searches every 32 KiB for repeats and writes a block of literals and length / distance pairs where that is shorter than both
+ * other forms; where it is not, the 32 KiB are coded as at 0.  Same pixels, same bound, another (never a longer) file.
  * lars_png_bound: the largest file any input of that shape can give (0 for a shape that cannot be encoded); pure host code.
  * lars_png_scratch_bytes: device scratch of lars_d_encode_png_u8.
  * lars_d_encode_png_u8: device img / palette_rgba / out (out_cap >= lars_png_bound) / scratch; enqueues on stream and
@@ -821,6 +823,9 @@ int lars_h_process_image_tiff_f32(const void *img, int64_t h, int64_t w, int cha
  * Z_HUFFMAN_ONLY), or stored where that is not shorter; behind a dynamic block that is not the strip's last an empty stored
  * block (00 00 FF FF after three zero bits and the padding), so that every part ends on a byte boundary; BFINAL on the last;
  * the Adler-32 of the n bytes.  A function of the strip's bytes alone; any inflate reads it (lars_h_decode_tiff_deflate too).
+ * With the knob deflate_matching at 1 (lars_set_tuning: 0 or 1, default 0) a part whose block of literals and length / distance
+ * pairs (matches within the part only, tests/deflate_lz_model.py) is shorter than both other forms is written as that block;
+ * every other part, the framing and the bounds are as at 0.
  * lars_tiff_deflate_bound: pure host code; per strip 2 header bytes, its n bytes, 5 bytes per part (a stored block's header;
  * a dynamic block with its flush is only chosen where it is no longer), 4 checksum bytes and one pad byte, then the header and
  * the directory with its arrays as in lars_tiff_bound; 0 for a shape that cannot be encoded.

@@ -1,10 +1,12 @@
 """The file codecs: PNG, JPEG and TIFF files built and decoded on the device, their ``*_info`` readers on the host and the
-thumbnails made straight from a file's bytes.  ``api`` re-exports every public name here; this module does not import ``api``.
+thumbnails made straight from a file's bytes.  ``api`` re-exports every public name here but ``deflate_matching`` (a setting, not
+a codec: the package exports it itself); this module does not import ``api``.
 Every operation takes one path through the helpers below.  ``_ffi.call`` and ``_ffi.load`` are looked up on ``_ffi`` at every
 call: the CPU tests replace them to see what is asked of the library.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -52,6 +54,19 @@ def _encode_call(name, nbytes, *args):
     n = C.c_int64(0)
     _ffi.call(name, *args, _ffi.ptr(out), out.nbytes, C.byref(n))
     return out[:n.value].tobytes()
+
+
+@contextlib.contextmanager
+def deflate_matching(on=True):
+    """``with deflate_matching(): ...`` -- inside the block the Deflate coder of ``encode_png``, ``encode_tiff(...,
+    compression="deflate")``, ``encode_tiff_f32(..., compression="deflate")`` and of ``process_image``'s ``want_png`` /
+    ``want_tiff="deflate..."`` files searches every 32 KiB segment for repeats (LZ77 length / distance pairs) instead of coding
+    literals only: the same pixels and the same bounds, smaller files on masks, class pictures, flat areas and colormap
+    pictures, never a larger one (a segment that gains nothing is written as without it).  The tuning knob
+    ``deflate_matching``, one per process: do not enter it from threads that encode at the same time with different wishes.
+    On leaving, the knob is what it was."""
+    with _ffi.tuning(deflate_matching=1 if on else 0):
+        yield
 
 
 # ---------------------------------------------------------------------------

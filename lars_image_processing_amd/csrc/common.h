@@ -140,6 +140,7 @@ struct Tuning {
     int jpeg_subseq_bits = 512;  // jpeg_decode.hip: bits of entropy data per lane of the self-synchronising decode
     int jpeg_last_rounds = 0;  // read-only: rounds of k_jd_pass that decoded anything in the last lars_h_decode_jpeg_u8 / lars_h_thumbnail_jpeg_u8 (+100: k_jd_finish ran)
     int tiff_strip_bytes = 65536;  // tiff_encode.hip: uncompressed bytes of a strip when the caller names no rows_per_strip (Pillow's / libtiff's 64 KiB)
+    int deflate_matching = 0;  // png.hip, tiff_encode.hip: the Deflate coder searches each segment for repeats (deflate_lz_device.h) or codes literals only
     int joint_window = 1;      // joint_win.hip: windowed pair tables (one reader per tile chunk) where they fit, never, or test hooks (windows that miss)
 };
 Tuning &tuning();

@@ -23,6 +23,7 @@
 
 #include "codec_host.h"
 #include "deflate_device.h"
+#include "deflate_lz_device.h"
 
 namespace lars {
 
@@ -104,6 +105,17 @@ __global__ __launch_bounds__(PNG_THREADS) void k_png_deflate(const uint8_t *__re
     const long long base = seg * PNG_SEG;
     const int n = (int)(total - base < PNG_SEG ? total - base : PNG_SEG);
     deflate_segment(filt + base, n, seg == 0, seg == nseg - 1, Z + seg * PNG_ZCAP, seglen + seg, adl + 2 * seg);
+}
+
+// the same with string matching (deflate_lz_device.h), where the tuning knob deflate_matching is 1
+__global__ __launch_bounds__(DLZ_THREADS) void k_png_deflate_lz(const uint8_t *__restrict__ filt, long long total, long long nseg,
+                                                               uint8_t *__restrict__ Z, unsigned int *__restrict__ seglen,
+                                                               unsigned int *__restrict__ adl)
+{
+    const long long seg = blockIdx.x;
+    const long long base = seg * PNG_SEG;
+    const int n = (int)(total - base < PNG_SEG ? total - base : PNG_SEG);
+    deflate_lz_segment(filt + base, n, seg == 0, seg == nseg - 1, Z + seg * PNG_ZCAP, seglen + seg, adl + 2 * seg);
 }
 
 // ---- CRC-32 -----------------------------------------------------------------------------------------------------------
@@ -368,7 +380,10 @@ int lars_d_encode_png_u8(const uint8_t *img, int64_t h, int64_t w, int channels,
     const int color_type = palette_rgba ? 3 : (channels == 1 ? 0 : (channels == 3 ? 2 : 6));
     hipStream_t s = pick_stream(c, stream);
     hipLaunchKernelGGL(k_png_filter, dim3((unsigned)h), dim3(PNG_THREADS), 0, s, img, P.rowb, channels, P.filt);
-    hipLaunchKernelGGL(k_png_deflate, dim3((unsigned)P.nseg), dim3(PNG_THREADS), 0, s, P.filt, P.total, P.nseg, P.z, P.seglen, P.adl);
+    if (tuning().deflate_matching)
+        hipLaunchKernelGGL(k_png_deflate_lz, dim3((unsigned)P.nseg), dim3(DLZ_THREADS), 0, s, P.filt, P.total, P.nseg, P.z, P.seglen, P.adl);
+    else
+        hipLaunchKernelGGL(k_png_deflate, dim3((unsigned)P.nseg), dim3(PNG_THREADS), 0, s, P.filt, P.total, P.nseg, P.z, P.seglen, P.adl);
     hipLaunchKernelGGL(k_png_frame, dim3(1), dim3(PNG_FRAME_THREADS), 0, s, P.nseg, P.total, P.z, P.seglen, P.adl, P.off, (int)w, (int)h,
                        color_type, palette_rgba, palette_rgba ? palette_len : 0, png_head_bytes(color_type, palette_len), out,
                        (unsigned long long)out_cap, reinterpret_cast<long long *>(out_len_dev));

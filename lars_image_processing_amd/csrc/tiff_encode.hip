@@ -30,6 +30,7 @@
 #include "codec_host.h"
 #include "common.h"
 #include "deflate_device.h"
+#include "deflate_lz_device.h"
 
 namespace lars {
 
@@ -345,6 +346,19 @@ __global__ __launch_bounds__(DEFLATE_THREADS) void k_tz_deflate(const uint8_t *_
     deflate_segment(stored + k * g.rps * g.rowb + at, m, i == 0, at + m == n, Z + slot * DEFLATE_ZCAP, seglen + slot, adl + 2 * slot);
 }
 
+// the same with string matching (deflate_lz_device.h), where the tuning knob deflate_matching is 1
+__global__ __launch_bounds__(DLZ_THREADS) void k_tz_deflate_lz(const uint8_t *__restrict__ stored, TeGeom g, long long pf,
+                                                              uint8_t *__restrict__ Z, unsigned int *__restrict__ seglen,
+                                                              unsigned int *__restrict__ adl)
+{
+    const long long slot = blockIdx.x, k = slot / pf, i = slot - k * pf;
+    if (k >= g.nstrips) return;
+    const long long n = tz_strip_bytes(g, k), at = i * DEFLATE_SEG;
+    if (at >= n) return;                                  // uniform: the whole workgroup leaves
+    const int m = (int)(n - at < DEFLATE_SEG ? n - at : DEFLATE_SEG);
+    deflate_lz_segment(stored + k * g.rps * g.rowb + at, m, i == 0, at + m == n, Z + slot * DEFLATE_ZCAP, seglen + slot, adl + 2 * slot);
+}
+
 // One workgroup per strip: where each part starts within the strip's stream (an exclusive scan of the parts' lengths, 256 parts
 // per round, the sum carried on), the strip's length, and the Adler-32 of the strip behind its last part.  With a_i = sum of part
 // i's bytes and b_i = sum of (n_i - j) * byte_j, both mod 65521, and r_i bytes of the strip behind part i, the checksum's halves
@@ -550,7 +564,10 @@ static int encode_on_device(const char *who, const void *img, int64_t h, int64_t
             hipLaunchKernelGGL(k_tz_stage, dim3((unsigned)(g.height * P.chunks)), dim3(TZ_STAGE_THREADS), 0, s, stored, g, P.chunks, P.stage);
             stored = P.stage;
         }
-        hipLaunchKernelGGL(k_tz_deflate, dim3((unsigned)P.slots), dim3(DEFLATE_THREADS), 0, s, stored, g, P.pf, P.z, P.seglen, P.adl);
+        if (tuning().deflate_matching)
+            hipLaunchKernelGGL(k_tz_deflate_lz, dim3((unsigned)P.slots), dim3(DLZ_THREADS), 0, s, stored, g, P.pf, P.z, P.seglen, P.adl);
+        else
+            hipLaunchKernelGGL(k_tz_deflate, dim3((unsigned)P.slots), dim3(DEFLATE_THREADS), 0, s, stored, g, P.pf, P.z, P.seglen, P.adl);
         hipLaunchKernelGGL(k_tz_join, dim3((unsigned)g.nstrips), dim3(TZ_JOIN_THREADS), 0, s, g, P.pf, P.z, P.seglen, P.adl, P.partoff, P.zlen);
         hipLaunchKernelGGL(k_te_frame, dim3(1), dim3(TE_FRAME_THREADS), 0, s, g, 8, P.zlen, P.off, out, (unsigned long long)out_cap,
                            reinterpret_cast<long long *>(out_len_dev), status_dev);

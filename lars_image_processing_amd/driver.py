@@ -13,13 +13,14 @@ The index pictures are the per-pixel RGBA images of the reference's colormaps at
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 import numpy as np
 
-from . import api
+from . import api, codecs
 
 EXTENSIONS = {".tif", ".tiff", ".png", ".jpg", ".jpeg"}      # backend-process.py:89
 # zlib level of the per-pixel colormap PNGs: encoding, not the GPU, bounds the directory driver (a 2048x2048 RGBA map takes
@@ -30,11 +31,14 @@ PNG_DECODERS = ("pillow", "device", "device+extended")
 JPEG_DECODERS = ("pillow", "device")
 TIFF_DECODERS = ("pillow", "device", "device+deflate")
 TIFF_ENCODERS = ("pillow", "device", "device+deflate")
+MATCHING = "+matching"                                       # the encoder values that turn the Deflate coder's string matching on:
+PNG_ENCODERS_MATCHING = ("device" + MATCHING,)               # "device" and "device+deflate" inside codecs.deflate_matching()
+TIFF_ENCODERS_MATCHING = ("device+deflate" + MATCHING,)
 
 
 def _check_png_encoder(png_encoder):
-    if png_encoder not in PNG_ENCODERS:
-        raise ValueError(f"png_encoder must be 'pillow' or 'device', got {png_encoder!r}")
+    if png_encoder not in PNG_ENCODERS + PNG_ENCODERS_MATCHING:
+        raise ValueError(f"png_encoder must be 'pillow' or 'device' ('device+matching' for Deflate with string matching), got {png_encoder!r}")
 
 
 def _check_png_decoder(png_decoder):
@@ -53,8 +57,16 @@ def _check_tiff_decoder(tiff_decoder):
 
 
 def _check_tiff_encoder(tiff_encoder):
-    if tiff_encoder not in TIFF_ENCODERS:
-        raise ValueError(f"tiff_encoder must be 'pillow' or 'device' ('device+deflate' for Deflate strips), got {tiff_encoder!r}")
+    if tiff_encoder not in TIFF_ENCODERS + TIFF_ENCODERS_MATCHING:
+        raise ValueError(f"tiff_encoder must be 'pillow' or 'device' ('device+deflate' for Deflate strips, 'device+deflate+matching' for those with string matching), got {tiff_encoder!r}")
+
+
+def _matching(png_encoder, tiff_encoder):
+    """(the block that holds the knob ``deflate_matching`` at 1 where an encoder asks for it, the encoders without that suffix).
+    The knob is one per process: ``batch_process`` enters the block once around its thread pool, not per file."""
+    on = png_encoder.endswith(MATCHING) or tiff_encoder.endswith(MATCHING)
+    block = codecs.deflate_matching() if on else contextlib.nullcontext()
+    return block, png_encoder.removesuffix(MATCHING), tiff_encoder.removesuffix(MATCHING)
 
 
 def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png",
@@ -78,7 +90,9 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     index plane itself, ``<INDEX>/<name>_<index>_f32.tif``: a single-band float32 LZW TIFF with Predictor 3, encoded on the
     GPU (``api.encode_tiff_f32``), the exact values the picture only colours; every other output is the same file.
     ``tiff_encoder="device+deflate"`` is ``"device"`` with Deflate strips (Compression 8, ``compression="deflate"``), and the
-    ``index_tiff`` file follows it: Deflate with Predictor 3."""
+    ``index_tiff`` file follows it: Deflate with Predictor 3.  ``png_encoder="device+matching"`` and
+    ``tiff_encoder="device+deflate+matching"`` are ``"device"`` and ``"device+deflate"`` with string matching in the Deflate
+    coder (``codecs.deflate_matching``, a per-process setting held for the call): smaller files, the same pixels."""
     if lut_format not in ("png", "png8", "tiff"):
         raise ValueError(f"lut_format must be 'png', 'png8' or 'tiff', got {lut_format!r}")
     _check_png_encoder(png_encoder)
@@ -86,6 +100,15 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     _check_jpeg_decoder(jpeg_decoder)
     _check_tiff_decoder(tiff_decoder)
     _check_tiff_encoder(tiff_encoder)
+    block, png_encoder, tiff_encoder = _matching(png_encoder, tiff_encoder)
+    with block:
+        return _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder,
+                              tiff_decoder, tiff_encoder, index_tiff)
+
+
+def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder, tiff_decoder,
+                   tiff_encoder, index_tiff):
+    """``process_image`` behind its checks, for ``"pillow"``, ``"device"`` and ``"device+deflate"``."""
     from PIL import Image
     from .tiffio import read_image
     image_path, output_dir = Path(image_path), Path(output_dir)
@@ -170,6 +193,7 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
     _check_png_decoder(png_decoder)
     _check_jpeg_decoder(jpeg_decoder)
     _check_tiff_decoder(tiff_decoder)
+    block, png_encoder, tiff_encoder = _matching(png_encoder, tiff_encoder)
     input_path, output_path = Path(input_dir), Path(output_dir)
     indices = [t for t, on in (("NDVI", process_ndvi), ("GNDVI", process_gndvi), ("NDWI", process_ndwi)) if on]
     files = files_of_rank(sorted(f for f in input_path.glob("*") if f.suffix.lower() in EXTENSIONS), rank, world)
@@ -181,8 +205,8 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
         try:
             if verbose:
                 print(f"Processing {idx}/{total}: {f.name}")
-            return f.name, process_image(f, output_path, process_wb, indices or None, full_depth, lut_format, png_encoder,
-                                         png_decoder, jpeg_decoder, tiff_decoder, tiff_encoder, index_tiff)
+            return f.name, _process_image(f, output_path, process_wb, indices or None, full_depth, lut_format, png_encoder,
+                                          png_decoder, jpeg_decoder, tiff_decoder, tiff_encoder, index_tiff)
         except Exception as e:                              # same policy as upstream :96-97
             if verbose:
                 print(f"Error processing {f.name}: {str(e)}")
@@ -193,15 +217,16 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
             from . import _ffi
             _ffi.call("lars_set_device", int(device))
 
-    if workers <= 1:
-        bind()
-        for job in enumerate(files, 1):
-            k, v = one(job)
-            results[k] = v
-    else:
-        with ThreadPoolExecutor(max_workers=min(workers, os.cpu_count() or 1), initializer=bind) as pool:
-            for k, v in pool.map(one, enumerate(files, 1)):
+    with block:
+        if workers <= 1:
+            bind()
+            for job in enumerate(files, 1):
+                k, v = one(job)
                 results[k] = v
+        else:
+            with ThreadPoolExecutor(max_workers=min(workers, os.cpu_count() or 1), initializer=bind) as pool:
+                for k, v in pool.map(one, enumerate(files, 1)):
+                    results[k] = v
     return results
 
 
@@ -211,9 +236,16 @@ def export_zip(image_array, selected_indices, corrected_array=None, png_encoder=
     full-resolution per-pixel colormap images (one GPU pass for white balance, every index and every colormap).
     ``corrected_array`` (the cached white-balanced image the UI keeps, process-images.py:1132) skips the
     white-balance step.  ``png_encoder="device"`` encodes every PNG of the archive on the GPU (``api.encode_png``; same
-    pixels): the colormap pictures never leave the device.
+    pixels): the colormap pictures never leave the device; ``"device+matching"`` does so with string matching in the
+    Deflate coder (``process_image``).
     """
     _check_png_encoder(png_encoder)
+    block, png_encoder, _ = _matching(png_encoder, "pillow")
+    with block:
+        return _export_zip(image_array, selected_indices, corrected_array, png_encoder)
+
+
+def _export_zip(image_array, selected_indices, corrected_array, png_encoder):
     import io
     import zipfile
     from PIL import Image
@@ -260,8 +292,9 @@ def main(argv=None):
     ap.add_argument("--workers", type=int, default=4)
     ap.add_argument("--full-depth", action="store_true")
     ap.add_argument("--lut-format", default="png", choices=["png", "png8", "tiff"])
-    ap.add_argument("--png-encoder", default="pillow", choices=list(PNG_ENCODERS),
-                    help="'device' encodes the index PNGs on the GPU (same pixels, only the files cross PCIe)")
+    ap.add_argument("--png-encoder", default="pillow", choices=list(PNG_ENCODERS + PNG_ENCODERS_MATCHING),
+                    help="'device' encodes the index PNGs on the GPU (same pixels, only the files cross PCIe), "
+                         "'device+matching' with string matching in the Deflate coder (smaller files)")
     ap.add_argument("--png-decoder", default="pillow", choices=list(PNG_DECODERS),
                     help="'device' decodes 8-bit non-interlaced PNG inputs on the GPU (same pixels; other files stay with Pillow), "
                          "'device+extended' also 1-, 2-, 4- and 16-bit and interlaced ones")
@@ -270,9 +303,9 @@ def main(argv=None):
     ap.add_argument("--tiff-decoder", default="pillow", choices=list(TIFF_DECODERS),
                     help="'device' decodes supported TIFF inputs on the GPU (same samples; other files take today's path); "
                          "'device+deflate' decodes Deflate TIFF files there too")
-    ap.add_argument("--tiff-encoder", default="pillow", choices=list(TIFF_ENCODERS),
+    ap.add_argument("--tiff-encoder", default="pillow", choices=list(TIFF_ENCODERS + TIFF_ENCODERS_MATCHING),
                     help="'device' builds <name>_wb.tif and the --lut-format tiff pictures on the GPU (LZW strips, same samples); "
-                         "'device+deflate' the same with Deflate strips, also for --index-tiff")
+                         "'device+deflate' the same with Deflate strips, also for --index-tiff; 'device+deflate+matching' those with string matching")
     ap.add_argument("--index-tiff", action="store_true",
                     help="also write <INDEX>/<name>_<index>_f32.tif: the float32 index plane as an LZW TIFF with Predictor 3, built on the GPU")
     ap.add_argument("--quiet", action="store_true")

@@ -20,7 +20,11 @@ call with ``want_arrays=True`` followed by ``encode_tiff_f32`` on the three host
 ``compression="tiff_adobe_deflate"`` instead, ``--compression both`` the LZW legs and then the Deflate legs in the same run, by
 the same rules; the Deflate entries carry ``_deflate`` in their names.
 
-    python tools/tiffencodebench.py [--legs picture] [--compression lzw] [--files 20] [--runs 2] [--split] [--sweep] [--gpu-only] [--json out.json]
+``--matching`` adds to every Deflate entry, in the same run, the file size and the time with the tuning knob ``deflate_matching``
+at 1 (``lars.deflate_matching()``: string matching in the Deflate coder), and a leg of its own with the rasters it is for: a
+two-class mask and a flat raster, uint8 4096 x 4096, knob 0 and 1 next to Pillow's ``tiff_adobe_deflate``.
+
+    python tools/tiffencodebench.py [--legs picture] [--compression lzw] [--files 20] [--runs 2] [--split] [--sweep] [--matching] [--gpu-only] [--json out.json]
 
 Kernel times come from a separate run:  rocprofv3 --kernel-trace --stats -- python tools/tiffencodebench.py --gpu-only
 """
@@ -149,6 +153,13 @@ def float_leg(args, res, comp="lzw"):
                  "strips": len(tiffio._read_ifd(memoryview(files[0]), "<")[tiffio.STRIP_OFFSETS]),
                  "encode_tiff_f32_ms": per_picture_ms(lambda a: lars.encode_tiff_f32(a, predictor=predictor, compression=comp), planes, True,
                                                       args.runs)}
+            if args.matching and deflate:
+                with lars.deflate_matching():
+                    files = [lars.encode_tiff_f32(a, predictor=predictor, compression=comp) for a in planes[:2]]
+                    assert all(same_bits(tiffio.read_tiff(b), a) for a, b in zip(planes, files))
+                    r["matching_mean_file_bytes"] = int(np.mean([len(b) for b in files]))
+                    r["encode_tiff_f32_matching_ms"] = per_picture_ms(lambda a: lars.encode_tiff_f32(a, predictor=predictor, compression=comp), planes,
+                                                                      True, args.runs)
             if not args.gpu_only:
                 pil = pil_float_tiff(planes[0], predictor, comp)
                 r["pillow_file_bytes"] = len(pil)
@@ -191,6 +202,8 @@ def main():
                     help="picture: the RGB pictures through encode_tiff; float: NDVI planes through encode_tiff_f32; all: both")
     ap.add_argument("--compression", choices=["lzw", "deflate", "both"], default="lzw",
                     help="lzw: the LZW legs; deflate: the same legs with compression=\"deflate\"; both: one after the other in the same run")
+    ap.add_argument("--matching", action="store_true",
+                    help='Deflate legs also under the knob "deflate_matching" = 1, and the mask and flat rasters (with --compression deflate or both)')
     ap.add_argument("--json", help="also write the figures to this file")
     args = ap.parse_args()
     if _ffi.device_count() < 1:
@@ -200,10 +213,32 @@ def main():
            "tiff_strip_bytes": _ffi.get_tuning("tiff_strip_bytes"), "kinds": {}}
     for comp in ("lzw", "deflate") if args.compression == "both" else (args.compression,):
         picture_and_float_legs(args, res, comp)
+        if args.matching and comp == "deflate":
+            mask_leg(args, res)
     if args.json:
         with open(args.json, "w") as f:
             json.dump(res, f, indent=1)
             f.write("\n")
+
+
+def mask_leg(args, res):
+    """The rasters string matching is for, uint8 4096 x 4096 through encode_tiff(compression="deflate"): knob 0, knob 1, Pillow."""
+    from pngbench import field_1f
+    f = field_1f(4096, 1.5, 7)
+    for name, a in (("mask_4096x4096_deflate", (f > 0.05).astype(np.uint8)), ("flat_4096x4096_deflate", np.full((4096, 4096), 90, np.uint8))):
+        arrays = [a, np.ascontiguousarray(np.roll(a, (97, 131), (0, 1)))]
+        r = {"shape": list(a.shape), "raw_bytes": int(a.nbytes)}
+        for key, block in (("", lars.deflate_matching(False)), ("matching_", lars.deflate_matching())):
+            with block:
+                b = lars.encode_tiff(a, compression="deflate")
+                assert np.array_equal(tiffio.read_tiff(b), a)
+                r[key + "file_bytes"] = len(b)
+                r[key + "encode_tiff_ms"] = per_picture_ms(lambda x: lars.encode_tiff(x, compression="deflate"), arrays, True, max(args.runs, 3))
+        if not args.gpu_only:
+            r["pillow_file_bytes"] = len(pil_tiff(a, False, "deflate"))
+            r["pillow_save_ms"] = per_picture_ms(lambda x: pil_tiff(x, False, "deflate"), arrays, False, args.runs)
+        res["kinds"][name] = r
+        print(name, json.dumps(r), flush=True)
 
 
 def picture_and_float_legs(args, res, comp):
@@ -219,6 +254,13 @@ def picture_and_float_legs(args, res, comp):
             r = {"files": len(arrays), "mean_file_bytes": int(np.mean([len(b) for b in files])), "shape": [shape[0], shape[1], 3],
                  "strips": len(tiffio._read_ifd(memoryview(files[0]), "<")[tiffio.STRIP_OFFSETS]),
                  "encode_tiff_ms": per_picture_ms(lambda a: lars.encode_tiff(a, predictor=predictor, compression=comp), arrays, True, args.runs)}
+            if args.matching and deflate:
+                with lars.deflate_matching():
+                    files = [lars.encode_tiff(a, predictor=predictor, compression=comp) for a in arrays[:DISTINCT]]
+                    assert all(np.array_equal(tiffio.read_tiff(b), a) for a, b in list(zip(arrays, files))[:2])
+                    r["matching_mean_file_bytes"] = int(np.mean([len(b) for b in files]))
+                    r["encode_tiff_matching_ms"] = per_picture_ms(lambda a: lars.encode_tiff(a, predictor=predictor, compression=comp), arrays, True,
+                                                                  args.runs)
             if not args.gpu_only:
                 pil = pil_tiff(arrays[0], predictor, comp)
                 r["pillow_file_bytes"] = len(pil)
