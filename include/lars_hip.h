@@ -854,6 +854,57 @@ int lars_h_process_image_tiff_float32(const void *img, int64_t h, int64_t w, int
                                               int compression, int predictor, int64_t rows_per_strip,
                                               uint8_t *const out_tiff[3], size_t tiff_cap, int64_t tiff_len[3]);
 
+/* ------------------------------------------------- nodata-aware processing (csrc/masked.hip) */
+/* The per-pixel path for pictures that are not picture everywhere: an orthomosaic's transparent or black frame, the reflected
+ * border align_images leaves, a plot cut out with a mask.  With V the valid pixels in raster order, every result is the
+ * reference's on the image img[valid][None, :, :] of shape [1][|V|][channels], scattered back:
+ *   np.percentile(ch, (2, 98)) of fix_white_balance     process-images.py:437      over the valid samples only
+ *   corrected image                                     process-images.py:438-441  0 in every channel outside
+ *   calculate_index                                     process-images.py:449-490  float32 NaN 0x7FC00000 outside
+ *   analyze_index, plt.hist(bins=50, range=(-1, 1))     process-images.py:492-513, process-ndvi.py:97
+ *                                                       of the valid values; coverage relative to |V| (numpy.ma's rules)
+ *   imshow(cmap, vmin=-1, vmax=1)                       process-images.py:695      (0, 0, 0, 0) outside: Colormap.set_bad's default
+ *
+ * lars_d_valid_mask: which pixels count, one byte each (1 = valid, 0 = not; [npix] uint8 in raster order, no bit packing),
+ * and their number.  A pixel is valid where user_valid (device, [npix] uint8, nonzero = allowed; NULL = all; may be out_mask
+ * itself) allows it AND, with use_alpha, its channel 3 is nonzero (channels >= 4) AND, with has_nodata, its R, G and NIR samples
+ * are not all equal to nodata.  uint8 / uint16 samples, channels >= 3.  *count_dev (device uint64) is zeroed by the call and
+ * receives |V|: a wave reduction, then one atomic per workgroup.  Masks 4-byte, count_dev 8-byte aligned.
+ * lars_d_masked_channel_hist: lars_d_channel_hist of one image over the valid pixels only -- hist [3][256] (LARS_U8: private
+ * copies in LDS) or [3][65536] (LARS_U16: global atomics) uint32, zeroed by the call.  lars_d_wb_table(hist, 1, |V|, ...)
+ * then gives the percentiles and the table, the degenerate p98 == p2 channel and the uint16 threshold form included.
+ * lars_d_masked_fused: lars_d_fused for one image (a->ntiles == 1) under a mask.  Outside the mask out_wb is 0, out_index
+ * NaN, out_rgba (0, 0, 0, 0).  a->stats must be NULL and a->flags 0: instead compact[k] (device, room for npix float32; NULL
+ * = not wanted; compact itself may be NULL) receives the valid values of index k in any order -- every wave takes its slots
+ * from *cursor_dev (device uint64, zeroed by the call, |V| afterwards) with one atomic -- and lars_d_array_stats_f32 /
+ * lars_d_median_pair_f32 over those |V| values give the record and the median.  out_rgba[k] needs cmap_lut[k].  Planes and
+ * out_wb 16-byte aligned. */
+int lars_d_valid_mask(const void *img, int64_t npix, int channels, int dtype, const uint8_t *user_valid, int use_alpha,
+                      int has_nodata, int nodata, uint8_t *out_mask, uint64_t *count_dev, void *stream);
+int lars_d_masked_channel_hist(const void *img, int64_t npix, int channels, int dtype, const uint8_t *valid,
+                               uint32_t *hist, void *stream);
+int lars_d_masked_fused(const lars_fused_args *a, const uint8_t *valid, float *const compact[3], uint64_t *cursor_dev);
+/* valid_mask(img_array, nodata, alpha): lars_d_valid_mask of a host image; out_mask is host [h][w] uint8. */
+int lars_h_valid_mask(const void *img, int64_t h, int64_t w, int channels, int dtype, int use_alpha, int has_nodata, int nodata,
+                      uint8_t *out_mask, int64_t *valid_pixels /* may be NULL */);
+/* lars_h_process_image under a mask, and its file-writing twins in one call.  valid: host [h][w] uint8, nonzero = valid, or
+ * NULL; use_alpha / has_nodata / nodata as above; the three rules combine with AND.  *valid_pixels receives |V|; with
+ * |V| == 0 the call fails with LARS_ERR_INVALID ("no valid pixel") and *valid_pixels is 0 (-1 after any earlier failure).
+ * file_kind 0: no files, out_rgba[k] with cmap_lut[k] receives the RGBA picture.  file_kind 1: lars_h_process_image_png's
+ * RGBA files (png_mode 1; a transparent frame).  file_kind 5 / 8: lars_h_process_image_tiff_float32's LZW / Deflate files
+ * of the planes (NaN outside) with predictor and rows_per_strip.  out_file[k] (host, file_cap bytes: at least that call's
+ * bound) and file_len[k] as there.  Colormap entry planes and palette PNGs are refused: the 256-entry palette has no
+ * free entry for "no data".  Statistics, histogram and medians are those of the valid values; everything else as in
+ * lars_h_process_image. */
+int lars_h_process_image_masked(const void *img, int64_t h, int64_t w, int channels, int dtype,
+                                int apply_wb, uint32_t index_mask, int want_hist,
+                                uint8_t *out_wb, float *const out_index[3],
+                                lars_stats *stats /* [3] */, float *medians /* [3][2] */,
+                                uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3],
+                                const uint8_t *valid, int use_alpha, int has_nodata, int nodata, int64_t *valid_pixels,
+                                int file_kind, int predictor, int64_t rows_per_strip,
+                                uint8_t *const out_file[3], size_t file_cap, int64_t file_len[3]);
+
 /* ------------------------------------------------------------------ multi-GPU */
 /* One process per GPU.  RCCL (librccl.so) is loaded on first use.  unique_id is
  * LARS_COMM_ID_BYTES bytes produced by lars_comm_unique_id() on rank 0 and

@@ -272,6 +272,13 @@ SIGNATURES = {
     "lars_h_encode_tiff_deflate_float32": (_I, [_P, _I64, _I64, _I, _I64, _I, _P, _SZ, C.POINTER(_I64)]),
     "lars_h_process_image_tiff_float32": (_I, [_P, _I64, _I64, _I, _I, _I, _U32, _I, _P, C.POINTER(_P * 3), _P, _P,
                                                        C.POINTER(_P * 3), C.POINTER(_P * 3), _I, _I, _I64, C.POINTER(_P * 3), _SZ, _P]),
+    "lars_d_valid_mask": (_I, [_P, _I64, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
+    "lars_d_masked_channel_hist": (_I, [_P, _I64, _I, _I, _P, _P, _P]),
+    "lars_d_masked_fused": (_I, [C.POINTER(FusedArgs), _P, C.POINTER(_P * 3), _P]),
+    "lars_h_valid_mask": (_I, [_P, _I64, _I64, _I, _I, _I, _I, _I, _P, C.POINTER(_I64)]),
+    "lars_h_process_image_masked": (_I, [_P, _I64, _I64, _I, _I, _I, _U32, _I, _P, C.POINTER(_P * 3), _P, _P,
+                                         C.POINTER(_P * 3), C.POINTER(_P * 3), _P, _I, _I, _I, C.POINTER(_I64),
+                                         _I, _I, _I64, C.POINTER(_P * 3), _SZ, _P]),
     "lars_jpeg_bound": (_SZ, [_I64, _I64, _I, _I]),
     "lars_jpeg_header": (_I64, [_I64, _I64, _I, _I, _I, _P, _SZ]),
     "lars_jpeg_encode_scratch_bytes": (_SZ, [_I64, _I64, _I, _I]),

@@ -54,6 +54,7 @@ import os
 import numpy as np
 
 from . import _ffi
+from . import nodata as _nodata
 from ._ffi import INDEX_IDS, INDEX_NAMES, Stats
 from .batch import index_mask
 from .codecs import (_shape, decode_jpeg, decode_png, decode_tiff, encode_jpeg, encode_png, encode_tiff, encode_tiff_f32,  # noqa: F401
@@ -468,6 +469,13 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
     not cross PCIe (``want_arrays=False``).  ``want_tiff="deflate"`` and ``"deflate+predictor"`` write the Deflate file instead
     (``encode_tiff_f32(..., compression="deflate")``).  Not together with ``want_png`` (one kind of file per call).
     """
+    return _process_image(img_array, indices, white_balance, want_arrays, want_hist, want_rgba, want_entries, want_png, want_tiff)
+
+
+def _process_image(img_array, indices, white_balance, want_arrays, want_hist, want_rgba, want_entries, want_png, want_tiff,
+                   valid=None, nodata=None):
+    """``process_image`` behind its signature, and ``nodata.process_image_masked`` with ``valid`` / ``nodata``: without them it
+    binds the entry points it always bound; with either, ``lars_h_process_image_masked`` for all three routes."""
     tiff_modes = {"predictor": 2, "deflate": 3, "deflate+predictor": 4}
     tiff_mode = 0 if want_tiff is False else 1 if want_tiff is True else tiff_modes.get(want_tiff) if isinstance(want_tiff, str) else None
     if tiff_mode is None:
@@ -490,6 +498,11 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
         if t not in INDEX_IDS:
             raise ValueError(f"Unknown index type: {t}")
     h, w, c = arr.shape
+    valid_arr, use_alpha = _nodata.valid_argument(valid, arr.shape, "process_image_masked")
+    nd = _nodata.nodata_value(nodata, arr.dtype, "process_image_masked")
+    masked = valid is not None or nd is not None
+    if masked and (want_entries or png_mode == 2):
+        raise ValueError(f"process_image_masked: {_nodata.NO_PALETTE_WITH_MASK}")
     mask = index_mask(indices)
     out_wb = _empty((h, w, c), dtype=np.uint8) if white_balance else None
     outs, rgbas, luts = [None] * 3, [None] * 3, [None] * 3
@@ -509,7 +522,38 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
     p_out = _ffi.ptr3(outs)
     head = (_ffi.ptr(arr), h, w, c, code, int(bool(white_balance)), mask, int(want_hist), _ffi.ptr(out_wb), C.byref(p_out), C.byref(stats),
             _ffi.ptr(med))
-    if tiff_mode:
+    if masked:
+        # one entry point for the three routes: what follows `head` names the mask and the kind of file
+        kind, cap, files = 0, 0, [None] * 3
+        if tiff_mode:
+            kind = 8 if tiff_mode >= 3 else 5
+            cap = tiff_f32_bound(h, w, 1, compression="deflate" if kind == 8 else "lzw")
+            if cap == 0:
+                raise ValueError(f"process_image: a {h} x {w} plane is not encoded as a TIFF file (1 to 2^24 on each side)")
+        elif png_mode:
+            kind, cap = 1, png_bound(h, w, 4)
+        for t in indices:
+            k = INDEX_IDS[t]
+            if png_mode:
+                luts[k] = colormap_lut(_colormap_for(t))
+            if kind:
+                files[k] = np.empty(cap, dtype=np.uint8)
+        lens = np.zeros(3, dtype=np.int64)
+        nvalid = C.c_int64(-1)
+        p_rgba, p_lut, p_file = _ffi.ptr3(rgbas), _ffi.ptr3(luts), _ffi.ptr3(files)
+        try:
+            _ffi.call("lars_h_process_image_masked", *head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(valid_arr), int(use_alpha),
+                      int(nd is not None), nd or 0, C.byref(nvalid), kind, int(tiff_mode in (2, 4)), 0, C.byref(p_file), cap, _ffi.ptr(lens))
+        except _ffi.LarsError:
+            if nvalid.value == 0:
+                raise ValueError("process_image: no valid pixel") from None
+            raise
+        files = [None if p is None else p[:lens[k]].tobytes() for k, p in enumerate(files)]
+        if tiff_mode:
+            tiffs = files
+        elif png_mode:
+            pngs = files
+    elif tiff_mode:
         tiff_deflate = tiff_mode >= 3
         cap = tiff_f32_bound(h, w, 1, compression="deflate" if tiff_deflate else "lzw")
         if cap == 0:
@@ -538,6 +582,8 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
         p_rgba, p_lut = _ffi.ptr3(rgbas), _ffi.ptr3(luts)
         _ffi.call("lars_h_process_image", *head, C.byref(p_rgba), C.byref(p_lut))
     result = {"corrected": out_wb, "indices": {}}
+    if masked:
+        result["valid_pixels"] = int(nvalid.value)
     for t in indices:
         k = INDEX_IDS[t]
         st = stats[k]

@@ -36,6 +36,11 @@ struct ImageJob {
     uint8_t *out_tiff[3];
     size_t tiff_cap;
     int64_t *tiff_len;            // [3]
+    // nodata-aware job (masked.hip): pixels outside the mask take no part in the percentiles and the statistics
+    int masked;
+    const uint8_t *valid;         // [h][w], nonzero = picture, or null
+    int use_alpha, has_nodata, nodata;
+    int64_t *valid_pixels;
 };
 
 struct TiffAnswer { int64_t len; int32_t status[2]; };
@@ -51,13 +56,17 @@ struct Layout {
     uint8_t *tif[3];               // float32 TIFF files of the index planes
     TiffAnswer *tif_ans; char *tif_scratch;
     size_t tif_bound;
+    uint8_t *vmask;                // masked jobs: one byte per pixel, 1 = picture
+    uint64_t *vcount;              // {|V|, cursor of the compaction}
+    uint32_t *vhist;               // channel histograms of the valid pixels
+    float *vals[3];                // the valid values of each index, compacted
 };
 
 // Medians of uint8 RGNir images come from the two-level select on recomputed values (select_q.hip): two passes over the
 // 3-byte pixels instead of four or more over each 4-byte plane, whether or not the planes are written as well.
 bool select_route(const ImageJob &j)
 {
-    if (!j.want_median || !j.medians || !j.mask || j.dtype != LARS_U8 || j.channels != 3) return false;
+    if (j.masked || !j.want_median || !j.medians || !j.mask || j.dtype != LARS_U8 || j.channels != 3) return false;
     return (long long)j.h * j.w * 6 < (1ll << 30);
 }
 // ... and when no plane is wanted (one index or all three), the statistics kernel counts the select's first pass itself:
@@ -79,7 +88,6 @@ Layout plan(const ImageJob &j, Carver &c)
     const size_t nval = j.dtype == LARS_U8 ? 256 : 65536;
     L.img = c.take<uint8_t>(npix * j.channels * esz);
     L.hist = nullptr;
-    (void)nval;
     L.table = j.apply_wb ? c.take<uint8_t>(lars_wb_table_bytes(j.dtype)) : nullptr;
     L.pcts = j.apply_wb ? c.take<double>(6) : nullptr;
     L.wb = (j.apply_wb && j.out_wb) ? c.take<uint8_t>(npix * j.channels) : nullptr;
@@ -91,7 +99,7 @@ Layout plan(const ImageJob &j, Carver &c)
         // the entry plane is derived from the float32 plane on the device
         const bool entries = on && ((j.out_rgba[k] && !j.cmap[k]) || j.png_mode == 2);
         const bool rgba = on && j.cmap[k] && (j.out_rgba[k] || j.png_mode == 1);
-        L.idx[k] = (on && (j.out_index[k] || entries || j.tiff || (j.want_median && !select))) ? c.take<float>(npix) : nullptr;
+        L.idx[k] = (on && (j.out_index[k] || entries || j.tiff || (j.want_median && !select && !j.masked))) ? c.take<float>(npix) : nullptr;
         L.rgba[k] = rgba ? c.take<uint8_t>(npix * 4) : nullptr;
         L.cmap[k] = rgba ? c.take<uint8_t>(1024) : nullptr;
         L.entry[k] = entries ? c.take<uint8_t>(npix + 4) : nullptr;
@@ -111,7 +119,55 @@ Layout plan(const ImageJob &j, Carver &c)
     L.sel = c.take<char>(3 * ((lars_select_scratch_bytes() + 255) & ~(size_t)255));
     L.pairs = select ? c.take<float>(4) : nullptr;
     L.selq = select ? c.take<char>(lars_quotient_median_scratch_bytes(1)) : nullptr;
+    L.vmask = j.masked ? c.take<uint8_t>(npix + 4) : nullptr;
+    L.vcount = j.masked ? c.take<uint64_t>(2) : nullptr;
+    L.vhist = (j.masked && j.apply_wb) ? c.take<uint32_t>(3 * nval) : nullptr;
+    for (int k = 0; k < 3; ++k)
+        L.vals[k] = (j.masked && ((j.mask >> k) & 1u) && (j.want_stats || j.want_median)) ? c.take<float>(npix) : nullptr;
     return L;
+}
+
+// A masked job's white-balance pre-pass and fused step (everything after them is run_image's): the mask and |V|, the
+// histograms of the valid pixels and their tables, the planes, and the record and the median of each index from its
+// compacted values.  |V| crosses to the host once: the table, statistics and select launches are sized by it.
+int run_masked(const ImageJob &j, const Layout &L, hipStream_t s)
+{
+    const int64_t npix = j.h * j.w;
+    if (j.valid) LARS_HIP_TRY(hipMemcpyAsync(L.vmask, j.valid, (size_t)npix, hipMemcpyHostToDevice, s));
+    LARS_TRY(lars_d_valid_mask(L.img, npix, j.channels, j.dtype, j.valid ? L.vmask : nullptr, j.use_alpha, j.has_nodata, j.nodata, L.vmask,
+                               L.vcount, s));
+    uint64_t nvalid = 0;
+    LARS_HIP_TRY(hipMemcpyAsync(&nvalid, L.vcount, sizeof nvalid, hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipStreamSynchronize(s));
+    if (j.valid_pixels) *j.valid_pixels = (int64_t)nvalid;
+    if (!nvalid) return fail(LARS_ERR_INVALID, "lars_h_process_image_masked: no valid pixel");
+    if (j.apply_wb) {
+        LARS_TRY(lars_d_masked_channel_hist(L.img, npix, j.channels, j.dtype, L.vmask, L.vhist, s));
+        LARS_TRY(lars_d_wb_table(L.vhist, 1, (int64_t)nvalid, j.dtype, L.table, L.pcts, j.wb_variant, s));
+    }
+    if (!j.mask && !L.wb) return LARS_OK;
+    lars_fused_args a;
+    memset(&a, 0, sizeof a);
+    a.tiles = L.img; a.ntiles = 1; a.npix = npix; a.channels = j.channels; a.dtype = j.dtype;
+    a.wb_table = j.apply_wb ? L.table : nullptr;
+    a.index_mask = j.mask;
+    for (int k = 0; k < 3; ++k) {
+        a.out_index[k] = L.idx[k];
+        a.out_rgba[k] = L.rgba[k];
+        a.cmap_lut[k] = L.cmap[k];
+        if (L.cmap[k]) LARS_HIP_TRY(hipMemcpyAsync(L.cmap[k], j.cmap[k], 1024, hipMemcpyHostToDevice, s));
+    }
+    a.out_wb = L.wb;
+    a.stream = s;
+    LARS_TRY(lars_d_masked_fused(&a, L.vmask, L.vals, L.vcount + 1));
+    const size_t selsz = (lars_select_scratch_bytes() + 255) & ~(size_t)255;
+    for (int k = 0; k < 3; ++k) {
+        if (!L.vals[k]) continue;
+        // process-images.py:498-504: coverage above 0.2, water (NDWI) above 0
+        if (j.want_stats) LARS_TRY(lars_d_array_stats_f32(L.vals[k], (int64_t)nvalid, k == LARS_NDWI ? 0.0f : 0.2f, j.want_hist, L.stats + k, s));
+        if (j.want_median && j.medians) LARS_TRY(lars_d_median_pair_f32(L.vals[k], (int64_t)nvalid, L.med + 2 * k, L.sel + k * selsz, s));
+    }
+    return LARS_OK;
 }
 
 int run_image(const ImageJob &j)
@@ -129,11 +185,13 @@ int run_image(const ImageJob &j)
     hipStream_t s = c->stream;
 
     LARS_HIP_TRY(hipMemcpyAsync(L.img, j.img, npix * j.channels * esz, hipMemcpyHostToDevice, s));
-    if (j.apply_wb) {
+    const bool stats = j.want_stats && j.mask;
+    if (j.masked) {
+        LARS_TRY(run_masked(j, L, s));
+    } else if (j.apply_wb) {
         LARS_TRY(lars_d_wb_prepare(L.img, 1, (int64_t)npix, j.channels, j.dtype, L.table, L.pcts, j.wb_variant, s));
     }
-    const bool stats = j.want_stats && j.mask;
-    if (j.mask || L.wb) {
+    if (!j.masked && (j.mask || L.wb)) {
         lars_fused_args a;
         memset(&a, 0, sizeof a);
         a.tiles = L.img; a.ntiles = 1; a.npix = (int64_t)npix; a.channels = j.channels; a.dtype = j.dtype;
@@ -166,7 +224,7 @@ int run_image(const ImageJob &j)
     }
     const size_t selsz = (lars_select_scratch_bytes() + 255) & ~(size_t)255;
     for (int k = 0; k < 3; ++k) {
-        if (!((j.mask >> k) & 1u) || L.pairs) continue;
+        if (!((j.mask >> k) & 1u) || L.pairs || j.masked) continue;
         if (j.want_median && j.medians)
             LARS_TRY(lars_d_median_pair_f32(L.idx[k], (int64_t)npix, L.med + 2 * k, L.sel + k * selsz, s));
     }
@@ -407,6 +465,83 @@ int lars_h_process_image_tiff_float32(const void *img, int64_t h, int64_t w, int
     if (compression != 5 && compression != 8) return fail(LARS_ERR_INVALID, "%s: compression must be 5 (LZW) or 8 (Deflate), got %d", who, compression);
     return process_image_tiff(who, compression, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians,
                               out_rgba, cmap_lut, predictor, rows_per_strip, out_tiff, tiff_cap, tiff_len);
+}
+
+int lars_h_process_image_masked(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                                int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                                uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], const uint8_t *valid, int use_alpha,
+                                int has_nodata, int nodata, int64_t *valid_pixels, int file_kind, int predictor, int64_t rows_per_strip,
+                                uint8_t *const out_file[3], size_t file_cap, int64_t file_len[3])
+{
+    static const char *who = "lars_h_process_image_masked";
+    if (valid_pixels) *valid_pixels = -1;
+    if (!img || h <= 0 || w <= 0 || channels < 3) return fail(LARS_ERR_INVALID, "%s: image must be a non-empty [h][w][>=3] array", who);
+    if (dtype != LARS_U8 && dtype != LARS_U16) return fail(LARS_ERR_INVALID, "%s: dtype must be LARS_U8 or LARS_U16", who);
+    if (index_mask & ~LARS_MASK_ALL) return fail(LARS_ERR_INVALID, "%s: unknown index bits in mask", who);
+    if (!index_mask && !(apply_wb && out_wb)) return fail(LARS_ERR_INVALID, "%s: nothing requested", who);
+    if (use_alpha && channels < 4) return fail(LARS_ERR_INVALID, "%s: the alpha rule needs 4 or more channels, got %d", who, channels);
+    if (has_nodata && (nodata < 0 || nodata > (dtype == LARS_U8 ? 255 : 65535)))
+        return fail(LARS_ERR_INVALID, "%s: nodata %d is outside the sample type's range", who, nodata);
+    if (file_kind != 0 && file_kind != 1 && file_kind != 5 && file_kind != 8)
+        return fail(LARS_ERR_INVALID, "%s: file_kind must be 0 (none), 1 (RGBA PNG), 5 (LZW TIFF) or 8 (Deflate TIFF), got %d", who, file_kind);
+    for (int k = 0; k < 3; ++k)
+        if (((index_mask >> k) & 1u) && out_rgba && out_rgba[k] && !(cmap_lut && cmap_lut[k]))
+            return fail(LARS_ERR_INVALID, "%s: out_rgba[%d] needs cmap_lut[%d] (the 256 colormap entries leave no free one for \"no data\": "
+                                          "entry planes are not built with a mask)", who, k, k);
+    ImageJob j;
+    memset(&j, 0, sizeof j);
+    if (file_kind) {
+        if (!index_mask || !out_file || !file_len) return fail(LARS_ERR_INVALID, "%s: indices and file outputs are required", who);
+        const size_t bound = file_kind == 1 ? ((h > (1 << 24) || w > (1 << 24)) ? 0 : lars_png_bound(h, w, 4))
+                           : file_kind == 8 ? lars_tiff_float32_deflate_bound(h, w, 1, rows_per_strip) : lars_tiff_f32_bound(h, w, 1, rows_per_strip);
+        if (!bound) return fail(LARS_ERR_INVALID, "%s: a %lld x %lld picture is not encoded as this kind of file", who, (long long)h, (long long)w);
+        if (file_cap < bound) return fail(LARS_ERR_INVALID, "%s: file_cap %zu < the bound %zu of this kind of file", who, file_cap, bound);
+        for (int k = 0; k < 3; ++k) {
+            if (!((index_mask >> k) & 1u)) continue;
+            if (!out_file[k]) return fail(LARS_ERR_INVALID, "%s: index %d needs out_file", who, k);
+            if (file_kind == 1 && !(cmap_lut && cmap_lut[k])) return fail(LARS_ERR_INVALID, "%s: index %d needs cmap_lut for its PNG", who, k);
+        }
+    }
+    j.img = img; j.h = h; j.w = w; j.channels = channels; j.dtype = dtype;
+    j.apply_wb = apply_wb; j.mask = index_mask; j.out_wb = out_wb;
+    for (int k = 0; k < 3; ++k) {
+        j.out_index[k] = out_index ? out_index[k] : nullptr;
+        j.out_rgba[k] = (out_rgba && file_kind != 1) ? out_rgba[k] : nullptr;
+        j.cmap[k] = cmap_lut ? cmap_lut[k] : nullptr;
+        if (file_kind == 1) j.out_png[k] = out_file[k];
+        else if (file_kind) j.out_tiff[k] = out_file[k];
+    }
+    j.stats = stats; j.want_stats = stats != nullptr; j.want_hist = want_hist;
+    j.medians = medians; j.want_median = medians != nullptr;
+    if (file_kind == 1) { j.png_mode = 1; j.png_cap = file_cap; j.png_len = file_len; }
+    else if (file_kind) {
+        j.tiff = 1; j.tiff_compression = file_kind; j.tiff_predictor = predictor; j.tiff_rps = rows_per_strip; j.tiff_cap = file_cap;
+        j.tiff_len = file_len;
+    }
+    j.masked = 1; j.valid = valid; j.use_alpha = use_alpha; j.has_nodata = has_nodata; j.nodata = nodata; j.valid_pixels = valid_pixels;
+    return run_image(j);
+}
+
+int lars_h_valid_mask(const void *img, int64_t h, int64_t w, int channels, int dtype, int use_alpha, int has_nodata, int nodata,
+                      uint8_t *out_mask, int64_t *valid_pixels)
+{
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!img || !out_mask || h <= 0 || w <= 0 || channels < 3) return fail(LARS_ERR_INVALID, "lars_h_valid_mask: bad arguments");
+    if (dtype != LARS_U8 && dtype != LARS_U16) return fail(LARS_ERR_INVALID, "lars_h_valid_mask: dtype must be LARS_U8 or LARS_U16");
+    const size_t npix = (size_t)h * w, esz = dtype == LARS_U8 ? 1 : 2;
+    uint8_t *dimg, *dmask;
+    uint64_t *dcount;
+    LARS_TRY(ws_plan(c, [&](Carver &d) { dimg = d.take<uint8_t>(npix * channels * esz), dmask = d.take<uint8_t>(npix + 4), dcount = d.take<uint64_t>(1); }));
+    hipStream_t s = c->stream;
+    LARS_HIP_TRY(hipMemcpyAsync(dimg, img, npix * channels * esz, hipMemcpyHostToDevice, s));
+    LARS_TRY(lars_d_valid_mask(dimg, (int64_t)npix, channels, dtype, nullptr, use_alpha, has_nodata, nodata, dmask, dcount, s));
+    uint64_t n = 0;
+    LARS_HIP_TRY(hipMemcpyAsync(out_mask, dmask, npix, hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipMemcpyAsync(&n, dcount, sizeof n, hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipStreamSynchronize(s));
+    if (valid_pixels) *valid_pixels = (int64_t)n;
+    return LARS_OK;
 }
 
 int lars_h_calculate_index_planes(const float *red, const float *green, const float *nir, int64_t n, int index_id,

@@ -20,7 +20,7 @@ from pathlib import Path
 
 import numpy as np
 
-from . import api, codecs
+from . import api, codecs, nodata as nodata_rules
 
 EXTENSIONS = {".tif", ".tiff", ".png", ".jpg", ".jpeg"}      # backend-process.py:89
 # zlib level of the per-pixel colormap PNGs: encoding, not the GPU, bounds the directory driver (a 2048x2048 RGBA map takes
@@ -61,6 +61,23 @@ def _check_tiff_encoder(tiff_encoder):
         raise ValueError(f"tiff_encoder must be 'pillow' or 'device' ('device+deflate' for Deflate strips, 'device+deflate+matching' for those with string matching), got {tiff_encoder!r}")
 
 
+def _mask_options(nodata, alpha_mask, lut_format):
+    """``nodata`` / ``alpha_mask`` as the keywords ``nodata.process_image_masked`` takes ({} = every pixel is picture)."""
+    kw = {}
+    if nodata is not None:
+        kw["nodata"] = nodata
+    if alpha_mask:
+        kw["valid"] = "alpha"
+    if kw and lut_format == "png8":
+        raise ValueError(f"lut_format='png8' with nodata / alpha_mask: {nodata_rules.NO_PALETTE_WITH_MASK.split(':')[0]}; use 'png' or 'tiff'")
+    return kw
+
+
+def _mask_argument(mask_kw):
+    """``_process_image``'s last argument, handed over only where a mask is set: without one the call is the one it always was."""
+    return (mask_kw,) if mask_kw else ()
+
+
 def _matching(png_encoder, tiff_encoder):
     """(the block that holds the knob ``deflate_matching`` at 1 where an encoder asks for it, the encoders without that suffix).
     The knob is one per process: ``batch_process`` enters the block once around its thread pool, not per file."""
@@ -71,7 +88,7 @@ def _matching(png_encoder, tiff_encoder):
 
 def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png",
                   png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow", tiff_encoder="pillow",
-                  index_tiff=False):
+                  index_tiff=False, nodata=None, alpha_mask=False):
     """One file: same outputs as backend-process.py:49-73.  Returns the statistics dicts.
     ``full_depth=True`` reads three-sample 16-bit TIFFs at their full depth (``tiffio.read_image``; Pillow, hence the
     reference, keeps their high bytes only).  ``lut_format="tiff"`` writes the colormap images as
@@ -92,7 +109,10 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     ``tiff_encoder="device+deflate"`` is ``"device"`` with Deflate strips (Compression 8, ``compression="deflate"``), and the
     ``index_tiff`` file follows it: Deflate with Predictor 3.  ``png_encoder="device+matching"`` and
     ``tiff_encoder="device+deflate+matching"`` are ``"device"`` and ``"device+deflate"`` with string matching in the Deflate
-    coder (``codecs.deflate_matching``, a per-process setting held for the call): smaller files, the same pixels."""
+    coder (``codecs.deflate_matching``, a per-process setting held for the call): smaller files, the same pixels.
+    ``nodata=N`` (pixels whose R, G and NIR all equal ``N`` are no picture) and ``alpha_mask=True`` (neither are pixels whose
+    channel 3 is 0) go to ``nodata.process_image_masked`` as ``nodata`` / ``valid="alpha"``: white balance and statistics of the valid
+    pixels only, transparent pictures and NaN planes outside.  Not with ``lut_format="png8"``: the palette has no free entry."""
     if lut_format not in ("png", "png8", "tiff"):
         raise ValueError(f"lut_format must be 'png', 'png8' or 'tiff', got {lut_format!r}")
     _check_png_encoder(png_encoder)
@@ -100,14 +120,15 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     _check_jpeg_decoder(jpeg_decoder)
     _check_tiff_decoder(tiff_decoder)
     _check_tiff_encoder(tiff_encoder)
+    mask_kw = _mask_options(nodata, alpha_mask, lut_format)
     block, png_encoder, tiff_encoder = _matching(png_encoder, tiff_encoder)
     with block:
         return _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder,
-                              tiff_decoder, tiff_encoder, index_tiff)
+                              tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw))
 
 
 def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder, tiff_decoder,
-                   tiff_encoder, index_tiff):
+                   tiff_encoder, index_tiff, mask_kw=None):
     """``process_image`` behind its checks, for ``"pillow"``, ``"device"`` and ``"device+deflate"``."""
     from PIL import Image
     from .tiffio import read_image
@@ -117,24 +138,35 @@ def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_
     if arr.ndim != 3 or arr.shape[2] < 3:
         raise ValueError(f"{image_path.name}: expected an image with at least 3 channels, got shape {arr.shape}")
     indices = list(indices or [])
+    mask_kw = mask_kw or {}
+
+    def run(**kw):
+        """``api.process_image`` of the file, or its masked form where a mask is set."""
+        if not mask_kw:
+            return api.process_image(arr, **kw)
+        return nodata_rules.process_image_masked(arr, **mask_kw, **kw)
+
     palette = lut_format == "png8"
     device_png = png_encoder == "device" and lut_format != "tiff"
     planes = None                                   # the call whose entries hold the float32 TIFF files
     compression = "deflate" if tiff_encoder == "device+deflate" else "lzw"
     plane_tiff = "deflate+predictor" if compression == "deflate" else "predictor"
     if device_png:                                  # the pictures stay on the device, their PNG files come back
-        res = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False,
-                                want_png="palette" if palette else True) if indices else None
+        res = run(indices=indices, white_balance=True, want_arrays=False, want_png="palette" if palette else True) if indices else None
         if index_tiff and indices:                  # one kind of file per call
-            planes = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False, want_tiff=plane_tiff)
+            planes = run(indices=indices, white_balance=True, want_arrays=False, want_tiff=plane_tiff)
     elif index_tiff and indices:
-        res = planes = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False, want_rgba=not palette,
-                                         want_entries=palette, want_tiff=plane_tiff)
+        res = planes = run(indices=indices, white_balance=True, want_arrays=False, want_rgba=not palette, want_entries=palette,
+                           want_tiff=plane_tiff)
     else:
         # palette files: the colormap entry of every pixel comes from the device, one byte per pixel (lars_h_process_image)
-        res = api.process_image(arr, indices=indices, white_balance=True, want_arrays=False, want_rgba=not palette,
-                                want_entries=palette) if indices else None
-    corrected = res["corrected"] if res else api.fix_white_balance(arr)
+        res = run(indices=indices, white_balance=True, want_arrays=False, want_rgba=not palette, want_entries=palette) if indices else None
+    if res:
+        corrected = res["corrected"]
+    elif mask_kw:
+        corrected = run(indices=[], white_balance=True)["corrected"]
+    else:
+        corrected = api.fix_white_balance(arr)
     if process_wb:
         (output_dir / "white_balanced").mkdir(parents=True, exist_ok=True)
         wb = corrected[:, :, :3] if corrected.shape[2] > 4 else corrected
@@ -182,12 +214,14 @@ def files_of_rank(files, rank=0, world=1):
 def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, process_gndvi=False,
                   process_ndwi=True, workers=4, verbose=True, full_depth=False, lut_format="png", rank=0, world=1,
                   device=None, png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow",
-                  tiff_encoder="pillow", index_tiff=False):
+                  tiff_encoder="pillow", index_tiff=False, nodata=None, alpha_mask=False):
     """backend-process.py:75-97 with its module constants as arguments.  Returns ``{file name: stats | error}``.
     ``rank`` / ``world``: one process per GPU, each takes its block of the sorted file list (``files_of_rank``); the output
     directories are shared, the file names distinct.  ``device``: the GPU ordinal every worker thread binds (the library's
     context is per thread and defaults to device 0); None leaves the threads' binding alone.  ``png_encoder``,
-    ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``, ``tiff_encoder``, ``index_tiff``: see ``process_image``."""
+    ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``, ``tiff_encoder``, ``index_tiff``, ``nodata``, ``alpha_mask``: see
+    ``process_image``."""
+    mask_kw = _mask_options(nodata, alpha_mask, lut_format)
     _check_tiff_encoder(tiff_encoder)
     _check_png_encoder(png_encoder)
     _check_png_decoder(png_decoder)
@@ -206,7 +240,7 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
             if verbose:
                 print(f"Processing {idx}/{total}: {f.name}")
             return f.name, _process_image(f, output_path, process_wb, indices or None, full_depth, lut_format, png_encoder,
-                                          png_decoder, jpeg_decoder, tiff_decoder, tiff_encoder, index_tiff)
+                                          png_decoder, jpeg_decoder, tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw))
         except Exception as e:                              # same policy as upstream :96-97
             if verbose:
                 print(f"Error processing {f.name}: {str(e)}")
@@ -308,6 +342,11 @@ def main(argv=None):
                          "'device+deflate' the same with Deflate strips, also for --index-tiff; 'device+deflate+matching' those with string matching")
     ap.add_argument("--index-tiff", action="store_true",
                     help="also write <INDEX>/<name>_<index>_f32.tif: the float32 index plane as an LZW TIFF with Predictor 3, built on the GPU")
+    ap.add_argument("--nodata", type=int, default=None, metavar="N",
+                    help="pixels whose R, G and NIR samples all equal N are no picture: left out of the white balance and the statistics, "
+                         "transparent in the index pictures, NaN in the --index-tiff planes (not with --lut-format png8)")
+    ap.add_argument("--alpha-mask", action="store_true",
+                    help="pixels whose channel 3 (alpha) is 0 are no picture; combines with --nodata")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     from .dist import env_rank_world
@@ -316,7 +355,7 @@ def main(argv=None):
                         not args.quiet, args.full_depth, args.lut_format, rank, world,
                         device=local_rank if world > 1 else None, png_encoder=args.png_encoder,
                         png_decoder=args.png_decoder, jpeg_decoder=args.jpeg_decoder, tiff_decoder=args.tiff_decoder,
-                        tiff_encoder=args.tiff_encoder, index_tiff=args.index_tiff)
+                        tiff_encoder=args.tiff_encoder, index_tiff=args.index_tiff, nodata=args.nodata, alpha_mask=args.alpha_mask)
     failed = {k: str(v) for k, v in res.items() if isinstance(v, Exception)}
     print(json.dumps({"rank": rank, "world": world, "files": len(res), "failed": failed}))
     return 1 if failed else 0
