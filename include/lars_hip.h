@@ -905,6 +905,59 @@ int lars_h_process_image_masked(const void *img, int64_t h, int64_t w, int chann
                                 int file_kind, int predictor, int64_t rows_per_strip,
                                 uint8_t *const out_file[3], size_t file_cap, int64_t file_len[3]);
 
+/* ------------------------------------------------- zonal statistics (csrc/zonal.hip) */
+/* One record per plot.  zones is an [npix] raster of labels 0 .. nzones in raster order, zone_bytes wide: 1 (uint8), 2 (uint16)
+ * or 4 (int32); label 0 is "in no zone"; nzones is 1 .. LARS_ZONES_MAX.  valid is lars_d_valid_mask's byte mask or NULL (every
+ * pixel counts).  With S_z = x[valid & (zones == z)], zone z's record and median pair are lars_d_array_stats_f32's and
+ * lars_d_median_pair_f32's of S_z (analyze_index on each plot, process-images.py:492-513; plt.hist, process-ndvi.py:97): count =
+ * |S_z|, coverage relative to it, NaN samples counted in nans as there.  An empty zone has count 0 and a NaN pair.  Everything
+ * is bit-reproducible except sum / sumsq: the values of a zone are added in the order the scatter placed them.
+ *
+ * lars_d_zone_count: counts_dev[nzones + 1] (device uint64, zeroed by the call) receives |S_z| at z, and at 0 the pixels with
+ * label 0 or outside valid; *bad_dev (device uint64, zeroed by the call) the labels below 0 or above nzones, which are counted
+ * nowhere else.  Waves aggregate equal labels with ballots before they add: one atomic per run of a label, not per pixel.
+ * lars_d_zone_offsets: offsets_dev[nzones + 1] (device uint64) receives the segment ends -- offsets[0] = 0, offsets[z] =
+ * counts[1] + .. + counts[z]: zone z owns the slots offsets[z - 1] .. offsets[z] - 1 -- and cursors_dev[nzones + 1] zeros.
+ * lars_d_zone_scatter: for every index k of index_mask, out[k] (device, room for offsets[nzones] float32) receives planes[k]'s
+ * values zone by zone: out[k][offsets[z - 1] ..] holds S_z in any order.  The indices share the slots (one cursor per zone,
+ * zeroed by the call).  zones, valid and nzones must be those the counts were taken from; a slot outside its segment is not
+ * written.
+ * lars_d_zone_stats: stats_dev[nzones] and medians_dev[nzones][2] (entry z - 1 for zone z) from one plane's scattered values,
+ * one workgroup per zone.  Zones with more than split_pixels values are left untouched: the caller runs
+ * lars_d_array_stats_f32 / lars_d_median_pair_f32 on values + offsets[z - 1] for them, as lars_h_zonal_stats_f32 does with
+ * the knob zone_split_pixels (lars_set_tuning: 64 .. 1073741824, default 131072; results never depend on it). */
+#define LARS_ZONES_MAX 65535
+int lars_d_zone_count(const void *zones, int zone_bytes, const uint8_t *valid, int64_t npix, int64_t nzones,
+                      uint64_t *counts_dev, uint64_t *bad_dev, void *stream);
+int lars_d_zone_offsets(const uint64_t *counts_dev, int64_t nzones, uint64_t *offsets_dev, uint64_t *cursors_dev, void *stream);
+int lars_d_zone_scatter(const float *const planes[3], uint32_t index_mask, const void *zones, int zone_bytes, const uint8_t *valid,
+                        int64_t npix, int64_t nzones, const uint64_t *offsets_dev, uint64_t *cursors_dev, float *const out[3],
+                        void *stream);
+int lars_d_zone_stats(const float *values, const uint64_t *offsets_dev, const uint64_t *counts_dev, int64_t nzones, float threshold,
+                      int want_hist, int64_t split_pixels, lars_stats *stats_dev /* [nzones] */, float *medians_dev /* [nzones][2] */,
+                      void *stream);
+/* zonal_statistics(index_array, zones, ...): the four stages on a host float32 [h][w] plane -- one upload, one download.
+ * valid: host [h][w] uint8, nonzero = counts, or NULL.  stats[nzones] and medians[nzones][2] are host arrays.  Labels
+ * outside 0 .. nzones: LARS_ERR_INVALID with their number in *bad_labels (0 on success, -1 after any earlier failure). */
+int lars_h_zonal_stats_f32(const float *x, const void *zones, int zone_bytes, const uint8_t *valid /* may be NULL */, int64_t h, int64_t w,
+                           int64_t nzones, float threshold, int want_hist, lars_stats *stats /* [nzones] */,
+                           float *medians /* [nzones][2] */, int64_t *bad_labels);
+/* process_image_zones: lars_h_process_image_masked without files (its file_kind 0) plus one record per zone and index.  The
+ * picture-level results -- percentiles, corrected image, planes, pictures, stats, medians, *valid_pixels -- are that call's
+ * with the same valid / use_alpha / has_nodata / nodata: zones do not change which pixels the white balance sees.  zones:
+ * host [h][w] labels as above.  zone_stats[3][nzones] and zone_medians[3][nzones][2] (host; rows of indices outside
+ * index_mask untouched) describe S_z = plane[valid & (zones == z)] with the coverage thresholds of the picture-level
+ * records.  Bad labels as in lars_h_zonal_stats_f32.  index_mask must not be empty. */
+int lars_h_process_image_zones(const void *img, int64_t h, int64_t w, int channels, int dtype,
+                               int apply_wb, uint32_t index_mask, int want_hist,
+                               uint8_t *out_wb, float *const out_index[3],
+                               lars_stats *stats /* [3] */, float *medians /* [3][2] */,
+                               uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3],
+                               const uint8_t *valid, int use_alpha, int has_nodata, int nodata, int64_t *valid_pixels,
+                               const void *zones, int zone_bytes, int64_t nzones,
+                               lars_stats *zone_stats /* [3][nzones] */, float *zone_medians /* [3][nzones][2] */,
+                               int64_t *bad_labels);
+
 /* ------------------------------------------------------------------ multi-GPU */
 /* One process per GPU.  RCCL (librccl.so) is loaded on first use.  unique_id is
  * LARS_COMM_ID_BYTES bytes produced by lars_comm_unique_id() on rank 0 and

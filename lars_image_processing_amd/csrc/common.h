@@ -142,6 +142,8 @@ struct Tuning {
     int tiff_strip_bytes = 65536;  // tiff_encode.hip: uncompressed bytes of a strip when the caller names no rows_per_strip (Pillow's / libtiff's 64 KiB)
     int deflate_matching = 0;  // png.hip, tiff_encode.hip: the Deflate coder searches each segment for repeats (deflate_lz_device.h) or codes literals only
     int joint_window = 1;      // joint_win.hip: windowed pair tables (one reader per tile chunk) where they fit, never, or test hooks (windows that miss)
+    int zone_split_pixels = 131072;  // zonal.hip: a zone with more values than this is left out by k_zone_stats; the host runs the array statistics and the
+                               // select over its segment instead (many workgroups for one zone instead of one)
 };
 Tuning &tuning();
 

@@ -4,12 +4,83 @@
 // thread's grow-only device workspace and stream, so concurrent Streamlit
 // sessions (threads) do not share mutable state.
 #include <string.h>
+#include <vector>
 
 #include "common.h"
 
 using namespace lars;
 
 namespace {
+
+// ---- zonal statistics (zonal.hip): the device buffers of the four stages and their run, for both host entry points ----
+struct ZoneBufs {
+    char *labels;                  // [npix] labels, zone_bytes wide
+    uint64_t *counts;              // [nzones + 1], then the count of bad labels
+    uint64_t *ends, *cursors;      // [nzones + 1] each
+    float *out[3];                 // the values of each index, zone by zone
+    lars_stats *stats;             // [3][nzones]
+    float *med;                    // [3][nzones][2]
+    char *sel;                     // select scratch of the large zones
+};
+
+ZoneBufs zone_plan(Carver &c, size_t npix, int zone_bytes, int64_t nzones, uint32_t mask)
+{
+    ZoneBufs B;
+    const size_t nz = (size_t)nzones;
+    B.labels = c.take<char>(npix * (size_t)zone_bytes);
+    B.counts = c.take<uint64_t>(nz + 2);
+    B.ends = c.take<uint64_t>(nz + 1);
+    B.cursors = c.take<uint64_t>(nz + 1);
+    for (int k = 0; k < 3; ++k) B.out[k] = ((mask >> k) & 1u) ? c.take<float>(npix) : nullptr;
+    B.stats = c.take<lars_stats>(3 * nz);
+    B.med = c.take<float>(6 * nz);
+    B.sel = c.take<char>(lars_select_scratch_bytes());
+    return B;
+}
+
+// labels up, the four stages, the records down (host_stats[3][nzones], host_med[3][nzones][2]; rows outside mask untouched).
+// The counts cross to the host once: bad labels end the call there, and zones above the knob zone_split_pixels take the array
+// kernels, which spread one zone over many workgroups.  The copies down are on the stream when this returns: the caller waits.
+int run_zones(const char *who, const ZoneBufs &B, const void *zones, int zone_bytes, const uint8_t *valid_dev, int64_t npix, int64_t nzones,
+              const float *const planes[3], uint32_t mask, const float thr[3], int want_hist, lars_stats *host_stats, float *host_med,
+              int64_t *bad_labels, hipStream_t s)
+{
+    const size_t nz = (size_t)nzones;
+    LARS_HIP_TRY(hipMemcpyAsync(B.labels, zones, (size_t)npix * zone_bytes, hipMemcpyHostToDevice, s));
+    LARS_TRY(lars_d_zone_count(B.labels, zone_bytes, valid_dev, npix, nzones, B.counts, B.counts + nz + 1, s));
+    std::vector<uint64_t> counts(nz + 2);
+    LARS_HIP_TRY(hipMemcpyAsync(counts.data(), B.counts, (nz + 2) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipStreamSynchronize(s));
+    if (bad_labels) *bad_labels = (int64_t)counts[nz + 1];
+    if (counts[nz + 1])
+        return fail(LARS_ERR_INVALID, "%s: %llu labels outside 0 .. %lld", who, (unsigned long long)counts[nz + 1], (long long)nzones);
+    LARS_TRY(lars_d_zone_offsets(B.counts, nzones, B.ends, B.cursors, s));
+    LARS_TRY(lars_d_zone_scatter(planes, mask, B.labels, zone_bytes, valid_dev, npix, nzones, B.ends, B.cursors, B.out, s));
+    const int64_t split = tuning().zone_split_pixels;
+    for (int k = 0; k < 3; ++k) {
+        if (!((mask >> k) & 1u)) continue;
+        lars_stats *st = B.stats + k * nz;
+        float *med = B.med + 2 * k * nz;
+        LARS_TRY(lars_d_zone_stats(B.out[k], B.ends, B.counts, nzones, thr[k], want_hist, split, st, med, s));
+        uint64_t lo = 0;
+        for (size_t z = 1; z <= nz; lo += counts[z], ++z) {
+            if (counts[z] <= (uint64_t)split) continue;
+            LARS_TRY(lars_d_array_stats_f32(B.out[k] + lo, (int64_t)counts[z], thr[k], want_hist, st + (z - 1), s));
+            LARS_TRY(lars_d_median_pair_f32(B.out[k] + lo, (int64_t)counts[z], med + 2 * (z - 1), B.sel, s));
+        }
+        LARS_HIP_TRY(hipMemcpyAsync(host_stats + k * nz, st, nz * sizeof(lars_stats), hipMemcpyDeviceToHost, s));
+        LARS_HIP_TRY(hipMemcpyAsync(host_med + 2 * k * nz, med, 2 * nz * sizeof(float), hipMemcpyDeviceToHost, s));
+    }
+    return LARS_OK;
+}
+
+int zone_arguments(const char *who, const void *zones, int zone_bytes, int64_t nzones, const void *stats, const void *medians)
+{
+    if (!zones || !stats || !medians) return fail(LARS_ERR_INVALID, "%s: zones, their records and their medians are required", who);
+    if (zone_bytes != 1 && zone_bytes != 2 && zone_bytes != 4) return fail(LARS_ERR_INVALID, "%s: labels are 1, 2 or 4 bytes wide, got %d", who, zone_bytes);
+    if (nzones < 1 || nzones > LARS_ZONES_MAX) return fail(LARS_ERR_INVALID, "%s: 1 to %d zones, got %lld", who, LARS_ZONES_MAX, (long long)nzones);
+    return LARS_OK;
+}
 
 struct ImageJob {
     const void *img;
@@ -41,6 +112,13 @@ struct ImageJob {
     const uint8_t *valid;         // [h][w], nonzero = picture, or null
     int use_alpha, has_nodata, nodata;
     int64_t *valid_pixels;
+    // ... with one record per zone and index as well (zonal.hip): the planes stay on the device for the zone stages
+    const void *zones;            // [h][w] labels 0 .. nzones, zone_bytes wide, or null
+    int zone_bytes;
+    int64_t nzones;
+    lars_stats *zone_stats;       // [3][nzones]
+    float *zone_medians;          // [3][nzones][2]
+    int64_t *bad_labels;
 };
 
 struct TiffAnswer { int64_t len; int32_t status[2]; };
@@ -60,6 +138,7 @@ struct Layout {
     uint64_t *vcount;              // {|V|, cursor of the compaction}
     uint32_t *vhist;               // channel histograms of the valid pixels
     float *vals[3];                // the valid values of each index, compacted
+    ZoneBufs zone;                 // jobs with zones
 };
 
 // Medians of uint8 RGNir images come from the two-level select on recomputed values (select_q.hip): two passes over the
@@ -99,7 +178,7 @@ Layout plan(const ImageJob &j, Carver &c)
         // the entry plane is derived from the float32 plane on the device
         const bool entries = on && ((j.out_rgba[k] && !j.cmap[k]) || j.png_mode == 2);
         const bool rgba = on && j.cmap[k] && (j.out_rgba[k] || j.png_mode == 1);
-        L.idx[k] = (on && (j.out_index[k] || entries || j.tiff || (j.want_median && !select && !j.masked))) ? c.take<float>(npix) : nullptr;
+        L.idx[k] = (on && (j.out_index[k] || entries || j.tiff || j.zones || (j.want_median && !select && !j.masked))) ? c.take<float>(npix) : nullptr;
         L.rgba[k] = rgba ? c.take<uint8_t>(npix * 4) : nullptr;
         L.cmap[k] = rgba ? c.take<uint8_t>(1024) : nullptr;
         L.entry[k] = entries ? c.take<uint8_t>(npix + 4) : nullptr;
@@ -124,6 +203,7 @@ Layout plan(const ImageJob &j, Carver &c)
     L.vhist = (j.masked && j.apply_wb) ? c.take<uint32_t>(3 * nval) : nullptr;
     for (int k = 0; k < 3; ++k)
         L.vals[k] = (j.masked && ((j.mask >> k) & 1u) && (j.want_stats || j.want_median)) ? c.take<float>(npix) : nullptr;
+    if (j.zones) L.zone = zone_plan(c, npix, j.zone_bytes, j.nzones, j.mask);
     return L;
 }
 
@@ -188,6 +268,12 @@ int run_image(const ImageJob &j)
     const bool stats = j.want_stats && j.mask;
     if (j.masked) {
         LARS_TRY(run_masked(j, L, s));
+        if (j.zones) {
+            // process-images.py:498-504, as run_masked's records
+            const float thr[3] = {0.2f, 0.2f, 0.0f};
+            LARS_TRY(run_zones("lars_h_process_image_zones", L.zone, j.zones, j.zone_bytes, L.vmask, (int64_t)npix, j.nzones, L.idx, j.mask, thr,
+                               j.want_hist, j.zone_stats, j.zone_medians, j.bad_labels, s));
+        }
     } else if (j.apply_wb) {
         LARS_TRY(lars_d_wb_prepare(L.img, 1, (int64_t)npix, j.channels, j.dtype, L.table, L.pcts, j.wb_variant, s));
     }
@@ -520,6 +606,71 @@ int lars_h_process_image_masked(const void *img, int64_t h, int64_t w, int chann
     }
     j.masked = 1; j.valid = valid; j.use_alpha = use_alpha; j.has_nodata = has_nodata; j.nodata = nodata; j.valid_pixels = valid_pixels;
     return run_image(j);
+}
+
+int lars_h_process_image_zones(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                               int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                               uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], const uint8_t *valid, int use_alpha,
+                               int has_nodata, int nodata, int64_t *valid_pixels, const void *zones, int zone_bytes, int64_t nzones,
+                               lars_stats *zone_stats, float *zone_medians, int64_t *bad_labels)
+{
+    static const char *who = "lars_h_process_image_zones";
+    if (valid_pixels) *valid_pixels = -1;
+    if (bad_labels) *bad_labels = -1;
+    if (!img || h <= 0 || w <= 0 || channels < 3) return fail(LARS_ERR_INVALID, "%s: image must be a non-empty [h][w][>=3] array", who);
+    if (dtype != LARS_U8 && dtype != LARS_U16) return fail(LARS_ERR_INVALID, "%s: dtype must be LARS_U8 or LARS_U16", who);
+    if (!index_mask || (index_mask & ~LARS_MASK_ALL)) return fail(LARS_ERR_INVALID, "%s: index_mask must name one to three indices", who);
+    if (use_alpha && channels < 4) return fail(LARS_ERR_INVALID, "%s: the alpha rule needs 4 or more channels, got %d", who, channels);
+    if (has_nodata && (nodata < 0 || nodata > (dtype == LARS_U8 ? 255 : 65535)))
+        return fail(LARS_ERR_INVALID, "%s: nodata %d is outside the sample type's range", who, nodata);
+    LARS_TRY(zone_arguments(who, zones, zone_bytes, nzones, zone_stats, zone_medians));
+    for (int k = 0; k < 3; ++k)
+        if (((index_mask >> k) & 1u) && out_rgba && out_rgba[k] && !(cmap_lut && cmap_lut[k]))
+            return fail(LARS_ERR_INVALID, "%s: out_rgba[%d] needs cmap_lut[%d] (entry planes are not built with a mask)", who, k, k);
+    ImageJob j;
+    memset(&j, 0, sizeof j);
+    j.img = img; j.h = h; j.w = w; j.channels = channels; j.dtype = dtype;
+    j.apply_wb = apply_wb; j.mask = index_mask; j.out_wb = out_wb;
+    for (int k = 0; k < 3; ++k) {
+        j.out_index[k] = out_index ? out_index[k] : nullptr;
+        j.out_rgba[k] = out_rgba ? out_rgba[k] : nullptr;
+        j.cmap[k] = cmap_lut ? cmap_lut[k] : nullptr;
+    }
+    j.stats = stats; j.want_stats = stats != nullptr; j.want_hist = want_hist;
+    j.medians = medians; j.want_median = medians != nullptr;
+    // the masked route even when no mask is given: the results are the same by definition
+    j.masked = 1; j.valid = valid; j.use_alpha = use_alpha; j.has_nodata = has_nodata; j.nodata = nodata; j.valid_pixels = valid_pixels;
+    j.zones = zones; j.zone_bytes = zone_bytes; j.nzones = nzones; j.zone_stats = zone_stats; j.zone_medians = zone_medians;
+    j.bad_labels = bad_labels;
+    return run_image(j);
+}
+
+int lars_h_zonal_stats_f32(const float *x, const void *zones, int zone_bytes, const uint8_t *valid, int64_t h, int64_t w, int64_t nzones,
+                           float threshold, int want_hist, lars_stats *stats, float *medians, int64_t *bad_labels)
+{
+    static const char *who = "lars_h_zonal_stats_f32";
+    if (bad_labels) *bad_labels = -1;
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!x || h <= 0 || w <= 0) return fail(LARS_ERR_INVALID, "%s: x must be a non-empty [h][w] float32 array", who);
+    LARS_TRY(zone_arguments(who, zones, zone_bytes, nzones, stats, medians));
+    const size_t npix = (size_t)h * w;
+    float *dx;
+    uint8_t *dvalid;
+    ZoneBufs B;
+    LARS_TRY(ws_plan(c, [&](Carver &d) {
+        dx = d.take<float>(npix);
+        dvalid = valid ? d.take<uint8_t>(npix) : nullptr;
+        B = zone_plan(d, npix, zone_bytes, nzones, 1u);
+    }));
+    hipStream_t s = c->stream;
+    LARS_HIP_TRY(hipMemcpyAsync(dx, x, npix * sizeof(float), hipMemcpyHostToDevice, s));
+    if (valid) LARS_HIP_TRY(hipMemcpyAsync(dvalid, valid, npix, hipMemcpyHostToDevice, s));
+    const float *planes[3] = {dx, nullptr, nullptr};
+    const float thr[3] = {threshold, threshold, threshold};
+    LARS_TRY(run_zones(who, B, zones, zone_bytes, dvalid, (int64_t)npix, nzones, planes, 1u, thr, want_hist, stats, medians, bad_labels, s));
+    LARS_HIP_TRY(hipStreamSynchronize(s));
+    return LARS_OK;
 }
 
 int lars_h_valid_mask(const void *img, int64_t h, int64_t w, int channels, int dtype, int use_alpha, int has_nodata, int nodata,

@@ -115,6 +115,7 @@ static const Knob KNOBS[] = {
     {"jpeg_subseq_bits", &Tuning::jpeg_subseq_bits, Knob::SET, [](int v) { return v >= 32 && v <= 65536; }, "32 .. 65536"},
     {"tiff_strip_bytes", &Tuning::tiff_strip_bytes, Knob::SET, [](int v) { return v >= 1 && v <= (1 << 30); }, "1 .. 1073741824"},
     {"deflate_matching", &Tuning::deflate_matching, Knob::SET, [](int v) { return v == 0 || v == 1; }, "0 or 1"},
+    {"zone_split_pixels", &Tuning::zone_split_pixels, Knob::SET, [](int v) { return v >= 64 && v <= (1 << 30); }, "64 .. 1073741824"},
     {"last_fused_kernel", &Tuning::last_fused_kernel, Knob::READ_ONLY, nullptr, nullptr},
     {"jpeg_last_rounds", &Tuning::jpeg_last_rounds, Knob::READ_ONLY, nullptr, nullptr},
 };

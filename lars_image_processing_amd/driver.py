@@ -78,6 +78,27 @@ def _mask_argument(mask_kw):
     return (mask_kw,) if mask_kw else ()
 
 
+def _zones_argument(zones):
+    """``_process_image``'s ``zones`` keyword, handed over only where a label raster is named: without one the call is the one it always was."""
+    return {} if zones is None else {"zones": zones}
+
+
+ZONE_CSV_COLUMNS = ("Zone", "Index", "Pixels", "Mean", "Median", "Min", "Max", "Coverage (%)")
+
+
+def _write_zones_csv(path, result, indices):
+    """``<stem>_zones.csv``: one row per zone and index from ``zones.zonal_rows``, floats written with ``repr`` (they read back exactly)."""
+    import csv
+    from .zones import zonal_rows
+    with open(path, "w", newline="") as f:
+        out = csv.writer(f)
+        out.writerow(ZONE_CSV_COLUMNS)
+        for t in indices:
+            for row in zonal_rows(result, t):
+                figures = [v for k, v in row.items() if k not in ("Zone", "Pixels")]      # analyze_index's five, in its order
+                out.writerow([row["Zone"], t, row["Pixels"]] + [repr(v) for v in figures])
+
+
 def _matching(png_encoder, tiff_encoder):
     """(the block that holds the knob ``deflate_matching`` at 1 where an encoder asks for it, the encoders without that suffix).
     The knob is one per process: ``batch_process`` enters the block once around its thread pool, not per file."""
@@ -88,7 +109,7 @@ def _matching(png_encoder, tiff_encoder):
 
 def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png",
                   png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow", tiff_encoder="pillow",
-                  index_tiff=False, nodata=None, alpha_mask=False):
+                  index_tiff=False, nodata=None, alpha_mask=False, zones=None):
     """One file: same outputs as backend-process.py:49-73.  Returns the statistics dicts.
     ``full_depth=True`` reads three-sample 16-bit TIFFs at their full depth (``tiffio.read_image``; Pillow, hence the
     reference, keeps their high bytes only).  ``lut_format="tiff"`` writes the colormap images as
@@ -112,7 +133,11 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     coder (``codecs.deflate_matching``, a per-process setting held for the call): smaller files, the same pixels.
     ``nodata=N`` (pixels whose R, G and NIR all equal ``N`` are no picture) and ``alpha_mask=True`` (neither are pixels whose
     channel 3 is 0) go to ``nodata.process_image_masked`` as ``nodata`` / ``valid="alpha"``: white balance and statistics of the valid
-    pixels only, transparent pictures and NaN planes outside.  Not with ``lut_format="png8"``: the palette has no free entry."""
+    pixels only, transparent pictures and NaN planes outside.  Not with ``lut_format="png8"``: the palette has no free entry.
+    ``zones=PATH`` names a single-band integer label raster of the picture's size (0 = in no zone; ``tiffio.read_image`` reads it)
+    and adds ``<name>_zones.csv`` next to the outputs: one row per zone and requested index (``zones.process_image_zones``,
+    ``zones.zonal_rows``), with the picture's white balance and under the same ``nodata`` / ``alpha_mask``.  Every other file is
+    unchanged; the statistics come from a call of their own."""
     if lut_format not in ("png", "png8", "tiff"):
         raise ValueError(f"lut_format must be 'png', 'png8' or 'tiff', got {lut_format!r}")
     _check_png_encoder(png_encoder)
@@ -124,11 +149,11 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     block, png_encoder, tiff_encoder = _matching(png_encoder, tiff_encoder)
     with block:
         return _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder,
-                              tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw))
+                              tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw), **_zones_argument(zones))
 
 
 def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder, tiff_decoder,
-                   tiff_encoder, index_tiff, mask_kw=None):
+                   tiff_encoder, index_tiff, mask_kw=None, zones=None):
     """``process_image`` behind its checks, for ``"pillow"``, ``"device"`` and ``"device+deflate"``."""
     from PIL import Image
     from .tiffio import read_image
@@ -139,6 +164,14 @@ def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_
         raise ValueError(f"{image_path.name}: expected an image with at least 3 channels, got shape {arr.shape}")
     indices = list(indices or [])
     mask_kw = mask_kw or {}
+    if zones is not None and indices:
+        from .zones import process_image_zones
+        labels = read_image(zones)
+        if labels.shape != arr.shape[:2]:
+            raise ValueError(f"{Path(zones).name}: the label raster has shape {labels.shape}, {image_path.name} is {arr.shape[:2]}")
+        output_dir.mkdir(parents=True, exist_ok=True)
+        _write_zones_csv(output_dir / f"{name}_zones.csv",
+                         process_image_zones(arr, labels, **mask_kw, indices=indices, white_balance=True, want_arrays=False), indices)
 
     def run(**kw):
         """``api.process_image`` of the file, or its masked form where a mask is set."""
@@ -214,13 +247,13 @@ def files_of_rank(files, rank=0, world=1):
 def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, process_gndvi=False,
                   process_ndwi=True, workers=4, verbose=True, full_depth=False, lut_format="png", rank=0, world=1,
                   device=None, png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow",
-                  tiff_encoder="pillow", index_tiff=False, nodata=None, alpha_mask=False):
+                  tiff_encoder="pillow", index_tiff=False, nodata=None, alpha_mask=False, zones=None):
     """backend-process.py:75-97 with its module constants as arguments.  Returns ``{file name: stats | error}``.
     ``rank`` / ``world``: one process per GPU, each takes its block of the sorted file list (``files_of_rank``); the output
     directories are shared, the file names distinct.  ``device``: the GPU ordinal every worker thread binds (the library's
     context is per thread and defaults to device 0); None leaves the threads' binding alone.  ``png_encoder``,
-    ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``, ``tiff_encoder``, ``index_tiff``, ``nodata``, ``alpha_mask``: see
-    ``process_image``."""
+    ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``, ``tiff_encoder``, ``index_tiff``, ``nodata``, ``alpha_mask``, ``zones`` (one label
+    raster for every file of the directory): see ``process_image``."""
     mask_kw = _mask_options(nodata, alpha_mask, lut_format)
     _check_tiff_encoder(tiff_encoder)
     _check_png_encoder(png_encoder)
@@ -240,7 +273,8 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
             if verbose:
                 print(f"Processing {idx}/{total}: {f.name}")
             return f.name, _process_image(f, output_path, process_wb, indices or None, full_depth, lut_format, png_encoder,
-                                          png_decoder, jpeg_decoder, tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw))
+                                          png_decoder, jpeg_decoder, tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw),
+                                          **_zones_argument(zones))
         except Exception as e:                              # same policy as upstream :96-97
             if verbose:
                 print(f"Error processing {f.name}: {str(e)}")
@@ -347,6 +381,9 @@ def main(argv=None):
                          "transparent in the index pictures, NaN in the --index-tiff planes (not with --lut-format png8)")
     ap.add_argument("--alpha-mask", action="store_true",
                     help="pixels whose channel 3 (alpha) is 0 are no picture; combines with --nodata")
+    ap.add_argument("--zones", default=None, metavar="PATH",
+                    help="a single-band integer label raster of the pictures' size (0 = in no zone): also write <name>_zones.csv, one row "
+                         "per zone and index, with the picture's white balance; combines with --nodata / --alpha-mask")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     from .dist import env_rank_world
@@ -355,7 +392,8 @@ def main(argv=None):
                         not args.quiet, args.full_depth, args.lut_format, rank, world,
                         device=local_rank if world > 1 else None, png_encoder=args.png_encoder,
                         png_decoder=args.png_decoder, jpeg_decoder=args.jpeg_decoder, tiff_decoder=args.tiff_decoder,
-                        tiff_encoder=args.tiff_encoder, index_tiff=args.index_tiff, nodata=args.nodata, alpha_mask=args.alpha_mask)
+                        tiff_encoder=args.tiff_encoder, index_tiff=args.index_tiff, nodata=args.nodata, alpha_mask=args.alpha_mask,
+                        **_zones_argument(args.zones))
     failed = {k: str(v) for k, v in res.items() if isinstance(v, Exception)}
     print(json.dumps({"rank": rank, "world": world, "files": len(res), "failed": failed}))
     return 1 if failed else 0
