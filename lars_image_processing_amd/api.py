@@ -50,6 +50,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import types
 
 import numpy as np
 
@@ -472,6 +473,83 @@ def process_image(img_array, indices=INDEX_NAMES, white_balance=True, want_array
     return _process_image(img_array, indices, white_balance, want_arrays, want_hist, want_rgba, want_entries, want_png, want_tiff)
 
 
+def _picture(who, mask_who, img_array, indices, white_balance, want_arrays, want_hist, want_rgba, want_entries, valid=None, nodata=None,
+             need_index=None):
+    """What ``_process_image`` and ``zones.process_image_zones`` open with: the image, the indices and the mask arguments validated
+    (``need_index``: the complaint about an empty index list, where there is one), the output buffers allocated, and ``head``: the
+    arguments every picture entry point's prototype opens with.  ``want_hist`` is bound as ``int(want_hist)``."""
+    p = types.SimpleNamespace(indices=indices)
+    p.arr = arr = _as_image(img_array, who)
+    code = _ffi.dtype_code(arr.dtype)
+    if code is None:
+        raise TypeError(f"{who}: unsupported sample type {arr.dtype}")
+    for t in indices:
+        if t not in INDEX_IDS:
+            raise ValueError(f"Unknown index type: {t}")
+    if need_index and not indices:
+        raise ValueError(f"{who}: {need_index}")
+    p.h, p.w, p.c = h, w, c = arr.shape
+    p.valid, p.use_alpha = _nodata.valid_argument(valid, arr.shape, mask_who)
+    p.nodata = _nodata.nodata_value(nodata, arr.dtype, mask_who)
+    p.out_wb = _empty((h, w, c), dtype=np.uint8) if white_balance else None
+    p.outs, p.rgbas, p.luts = [None] * 3, [None] * 3, [None] * 3
+    for t in indices:
+        k = INDEX_IDS[t]
+        if want_arrays:
+            p.outs[k] = _empty((h, w), dtype=np.float32)
+        if want_rgba:
+            p.rgbas[k] = _empty((h, w, 4), dtype=np.uint8)
+            p.luts[k] = colormap_lut(_colormap_for(t))
+        elif want_entries:
+            p.rgbas[k] = _empty((h, w), dtype=np.uint8)        # no table: the entry plane comes back in the RGBA slot
+    p.stats = (Stats * 3)()
+    p.med = np.zeros((3, 2), dtype=np.float32)
+    p.p_out = _ffi.ptr3(p.outs)
+    p.head = (_ffi.ptr(arr), h, w, c, code, int(bool(white_balance)), index_mask(indices), int(want_hist), _ffi.ptr(p.out_wb),
+              C.byref(p.p_out), C.byref(p.stats), _ffi.ptr(p.med))
+    return p
+
+
+def _picture_result(p, want_hist, want_rgba, want_entries, pngs=(None,) * 3, tiffs=(None,) * 3, valid_pixels=None):
+    """The dict ``process_image`` returns, from what ``_picture`` allocated and the call filled."""
+    result = {"corrected": p.out_wb, "indices": {}}
+    if valid_pixels is not None:
+        result["valid_pixels"] = int(valid_pixels)
+    for t in p.indices:
+        k = INDEX_IDS[t]
+        st = p.stats[k]
+        feature_name, _ = _coverage_rule(t)
+        median = float(np.float32(np.float32(p.med[k, 0] + p.med[k, 1]) / 2))
+        result["indices"][t] = {
+            "index": p.outs[k],
+            "rgba": p.rgbas[k] if want_rgba else None,
+            "entry": p.rgbas[k] if want_entries else None,
+            "png": pngs[k],
+            "tiff": tiffs[k],
+            "hist": np.array(list(st.hist), dtype=np.int64) if want_hist else None,
+            "stats": {
+                f"Mean {t}": st.sum / st.count,
+                f"Median {t}": median,
+                f"Min {t}": st.min,
+                f"Max {t}": st.max,
+                f"{feature_name} Coverage (%)": st.above / st.count * 100,
+            },
+        }
+    return result
+
+
+def _with_files(indices, cap, call):
+    """The file tail of an entry point: ``call(out_file, cap, file_len)`` with ``cap`` bytes for the file of each index; the files
+    come back as ``bytes``, ``None`` where there is no index."""
+    files = [None] * 3
+    for t in indices:
+        files[INDEX_IDS[t]] = np.empty(cap, dtype=np.uint8)
+    lens = np.zeros(3, dtype=np.int64)
+    p_file = _ffi.ptr3(files)
+    call(C.byref(p_file), cap, _ffi.ptr(lens))
+    return [None if f is None else f[:lens[k]].tobytes() for k, f in enumerate(files)]
+
+
 def _process_image(img_array, indices, white_balance, want_arrays, want_hist, want_rgba, want_entries, want_png, want_tiff,
                    valid=None, nodata=None):
     """``process_image`` behind its signature, and ``nodata.process_image_masked`` with ``valid`` / ``nodata``: without them it
@@ -490,121 +568,53 @@ def _process_image(img_array, indices, white_balance, want_arrays, want_hist, wa
         raise ValueError("process_image: want_png replaces want_rgba / want_entries (the pictures stay on the device)")
     if want_rgba and want_entries:
         raise ValueError("process_image: want_rgba or want_entries, not both (they share the output slot of the C ABI)")
-    arr = _as_image(img_array, "process_image")
-    code = _ffi.dtype_code(arr.dtype)
-    if code is None:
-        raise TypeError(f"process_image: unsupported sample type {arr.dtype}")
-    for t in indices:
-        if t not in INDEX_IDS:
-            raise ValueError(f"Unknown index type: {t}")
-    h, w, c = arr.shape
-    valid_arr, use_alpha = _nodata.valid_argument(valid, arr.shape, "process_image_masked")
-    nd = _nodata.nodata_value(nodata, arr.dtype, "process_image_masked")
-    masked = valid is not None or nd is not None
+    p = _picture("process_image", "process_image_masked", img_array, indices, white_balance, want_arrays, want_hist, want_rgba, want_entries,
+                 valid, nodata)
+    masked = valid is not None or p.nodata is not None
     if masked and (want_entries or png_mode == 2):
         raise ValueError(f"process_image_masked: {_nodata.NO_PALETTE_WITH_MASK}")
-    mask = index_mask(indices)
-    out_wb = _empty((h, w, c), dtype=np.uint8) if white_balance else None
-    outs, rgbas, luts = [None] * 3, [None] * 3, [None] * 3
-    for t in indices:
-        k = INDEX_IDS[t]
-        if want_arrays:
-            outs[k] = _empty((h, w), dtype=np.float32)
-        if want_rgba:
-            rgbas[k] = _empty((h, w, 4), dtype=np.uint8)
-            luts[k] = colormap_lut(_colormap_for(t))
-        elif want_entries:
-            rgbas[k] = _empty((h, w), dtype=np.uint8)          # no table: the entry plane comes back in the RGBA slot
-    stats = (Stats * 3)()
-    med = np.zeros((3, 2), dtype=np.float32)
-    pngs, tiffs = [None] * 3, [None] * 3
-    # what the three routes' entry points open with
-    p_out = _ffi.ptr3(outs)
-    head = (_ffi.ptr(arr), h, w, c, code, int(bool(white_balance)), mask, int(want_hist), _ffi.ptr(out_wb), C.byref(p_out), C.byref(stats),
-            _ffi.ptr(med))
+    # the kind of file as lars_h_process_image_masked names it, and the bytes one may take
+    kind, cap, predictor = 0, 0, int(tiff_mode in (2, 4))
+    if tiff_mode:
+        kind = 8 if tiff_mode >= 3 else 5
+        cap = tiff_f32_bound(p.h, p.w, 1, compression="deflate" if kind == 8 else "lzw")
+        if cap == 0:
+            raise ValueError(f"process_image: a {p.h} x {p.w} plane is not encoded as a TIFF file (1 to 2^24 on each side)")
+    elif png_mode:
+        kind = 1
+        cap = png_bound(p.h, p.w, 4 if png_mode == 1 else 1)
+        for t in indices:
+            p.luts[INDEX_IDS[t]] = colormap_lut(_colormap_for(t))
+    p_rgba, p_lut = _ffi.ptr3(p.rgbas), _ffi.ptr3(p.luts)
+    pictures = (C.byref(p_rgba), C.byref(p_lut))
+    pngs, tiffs, nvalid = (None,) * 3, (None,) * 3, None
     if masked:
         # one entry point for the three routes: what follows `head` names the mask and the kind of file
-        kind, cap, files = 0, 0, [None] * 3
-        if tiff_mode:
-            kind = 8 if tiff_mode >= 3 else 5
-            cap = tiff_f32_bound(h, w, 1, compression="deflate" if kind == 8 else "lzw")
-            if cap == 0:
-                raise ValueError(f"process_image: a {h} x {w} plane is not encoded as a TIFF file (1 to 2^24 on each side)")
-        elif png_mode:
-            kind, cap = 1, png_bound(h, w, 4)
-        for t in indices:
-            k = INDEX_IDS[t]
-            if png_mode:
-                luts[k] = colormap_lut(_colormap_for(t))
-            if kind:
-                files[k] = np.empty(cap, dtype=np.uint8)
-        lens = np.zeros(3, dtype=np.int64)
         nvalid = C.c_int64(-1)
-        p_rgba, p_lut, p_file = _ffi.ptr3(rgbas), _ffi.ptr3(luts), _ffi.ptr3(files)
+
+        def masked_call(*tail):
+            _ffi.call("lars_h_process_image_masked", *p.head, *pictures, _ffi.ptr(p.valid), int(p.use_alpha), int(p.nodata is not None),
+                      p.nodata or 0, C.byref(nvalid), kind, predictor, 0, *tail)
         try:
-            _ffi.call("lars_h_process_image_masked", *head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(valid_arr), int(use_alpha),
-                      int(nd is not None), nd or 0, C.byref(nvalid), kind, int(tiff_mode in (2, 4)), 0, C.byref(p_file), cap, _ffi.ptr(lens))
+            files = _with_files(indices if kind else (), cap, masked_call)       # no kind of file: no buffers, cap 0
         except _ffi.LarsError:
             if nvalid.value == 0:
                 raise ValueError("process_image: no valid pixel") from None
             raise
-        files = [None if p is None else p[:lens[k]].tobytes() for k, p in enumerate(files)]
-        if tiff_mode:
-            tiffs = files
-        elif png_mode:
+        nvalid = nvalid.value
+        if png_mode:
             pngs = files
-    elif tiff_mode:
-        tiff_deflate = tiff_mode >= 3
-        cap = tiff_f32_bound(h, w, 1, compression="deflate" if tiff_deflate else "lzw")
-        if cap == 0:
-            raise ValueError(f"process_image: a {h} x {w} plane is not encoded as a TIFF file (1 to 2^24 on each side)")
-        for t in indices:
-            tiffs[INDEX_IDS[t]] = np.empty(cap, dtype=np.uint8)
-        lens = np.zeros(3, dtype=np.int64)
-        p_rgba, p_lut, p_tiff = _ffi.ptr3(rgbas), _ffi.ptr3(luts), _ffi.ptr3(tiffs)
-        tail = (int(tiff_mode in (2, 4)), 0, C.byref(p_tiff), cap, _ffi.ptr(lens))
-        if tiff_deflate:
-            _ffi.call("lars_h_process_image_tiff_float32", *head, C.byref(p_rgba), C.byref(p_lut), 8, *tail)
-        else:
-            _ffi.call("lars_h_process_image_tiff_f32", *head, C.byref(p_rgba), C.byref(p_lut), *tail)
-        tiffs = [None if p is None else p[:lens[k]].tobytes() for k, p in enumerate(tiffs)]
-    elif png_mode:
-        cap = png_bound(h, w, 4 if png_mode == 1 else 1)
-        for t in indices:
-            k = INDEX_IDS[t]
-            luts[k] = colormap_lut(_colormap_for(t))
-            pngs[k] = np.empty(cap, dtype=np.uint8)
-        lens = np.zeros(3, dtype=np.int64)
-        p_lut, p_png = _ffi.ptr3(luts), _ffi.ptr3(pngs)
-        _ffi.call("lars_h_process_image_png", *head, C.byref(p_lut), png_mode, C.byref(p_png), cap, _ffi.ptr(lens))
-        pngs = [None if p is None else p[:lens[k]].tobytes() for k, p in enumerate(pngs)]
+        elif tiff_mode:
+            tiffs = files
+    elif kind == 8:
+        tiffs = _with_files(indices, cap, lambda *tail: _ffi.call("lars_h_process_image_tiff_float32", *p.head, *pictures, 8, predictor, 0, *tail))
+    elif kind == 5:
+        tiffs = _with_files(indices, cap, lambda *tail: _ffi.call("lars_h_process_image_tiff_f32", *p.head, *pictures, predictor, 0, *tail))
+    elif kind == 1:
+        pngs = _with_files(indices, cap, lambda *tail: _ffi.call("lars_h_process_image_png", *p.head, C.byref(p_lut), png_mode, *tail))
     else:
-        p_rgba, p_lut = _ffi.ptr3(rgbas), _ffi.ptr3(luts)
-        _ffi.call("lars_h_process_image", *head, C.byref(p_rgba), C.byref(p_lut))
-    result = {"corrected": out_wb, "indices": {}}
-    if masked:
-        result["valid_pixels"] = int(nvalid.value)
-    for t in indices:
-        k = INDEX_IDS[t]
-        st = stats[k]
-        feature_name, _ = _coverage_rule(t)
-        median = float(np.float32(np.float32(med[k, 0] + med[k, 1]) / 2))
-        result["indices"][t] = {
-            "index": outs[k],
-            "rgba": rgbas[k] if want_rgba else None,
-            "entry": rgbas[k] if want_entries else None,
-            "png": pngs[k],
-            "tiff": tiffs[k],
-            "hist": np.array(list(st.hist), dtype=np.int64) if want_hist else None,
-            "stats": {
-                f"Mean {t}": st.sum / st.count,
-                f"Median {t}": median,
-                f"Min {t}": st.min,
-                f"Max {t}": st.max,
-                f"{feature_name} Coverage (%)": st.above / st.count * 100,
-            },
-        }
-    return result
+        _ffi.call("lars_h_process_image", *p.head, *pictures)
+    return _picture_result(p, want_hist, want_rgba, want_entries, pngs, tiffs, nvalid)
 
 
 # ---------------------------------------------------------------------------

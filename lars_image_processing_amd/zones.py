@@ -13,6 +13,7 @@ import numpy as np
 from . import _ffi
 from . import nodata as _nodata
 from ._ffi import INDEX_IDS
+from .api import _coverage_rule, _picture, _picture_result
 
 ZONES_MAX = 65535
 _FIGURES = ("mean", "median", "min", "max", "coverage")
@@ -84,7 +85,6 @@ def zonal_statistics(index_array, zones, index_type, valid=None, n_zones=None, w
     mean / median / min / max.  A label below 0 or above ``n_zones`` raises ``ValueError`` with the number of such pixels.
     Everything but ``mean`` is bit-reproducible; the mean's double sum follows the order the device placed the values in."""
     who = "zonal_statistics"
-    from .api import _coverage_rule
     if index_type not in INDEX_IDS:
         raise ValueError(f"{who}: Unknown index type: {index_type}")
     x = np.asarray(index_array)
@@ -123,81 +123,34 @@ def process_image_zones(img_array, zones, valid=None, nodata=None, n_zones=None,
     picture-level statistics and ``valid_pixels`` are exactly ``process_image_masked``'s with the same ``valid`` / ``nodata``; the
     zone figures are ``zonal_statistics``'s of each plane under the derived mask.  At least one index must be asked for."""
     who = "process_image_zones"
-    from .api import _as_image, _colormap_for, _coverage_rule, colormap_lut
-    from .batch import index_mask
-    from .hostpool import empty
-    arr = _as_image(img_array, who)
-    code = _ffi.dtype_code(arr.dtype)
-    if code is None:
-        raise TypeError(f"{who}: unsupported sample type {arr.dtype}")
-    indices = list(indices)
-    for t in indices:
-        if t not in INDEX_IDS:
-            raise ValueError(f"Unknown index type: {t}")
-    if not indices:
-        raise ValueError(f"{who}: zone statistics need at least one index")
-    h, w, c = arr.shape
-    valid_arr, use_alpha = _nodata.valid_argument(valid, arr.shape, who)
-    nd = _nodata.nodata_value(nodata, arr.dtype, who)
-    lab, nz = _labels(zones, (h, w), n_zones, who)
-    mask = index_mask(indices)
-    out_wb = empty((h, w, c), dtype=np.uint8) if white_balance else None
-    outs, rgbas, luts = [None] * 3, [None] * 3, [None] * 3
-    for t in indices:
-        k = INDEX_IDS[t]
-        if want_arrays:
-            outs[k] = empty((h, w), dtype=np.float32)
-        if want_rgba:
-            rgbas[k] = empty((h, w, 4), dtype=np.uint8)
-            luts[k] = colormap_lut(_colormap_for(t))
-    stats = (_ffi.Stats * 3)()
-    med = np.zeros((3, 2), dtype=np.float32)
+    p = _picture(who, who, img_array, list(indices), white_balance, want_arrays, bool(want_hist), want_rgba, False, valid, nodata,
+                 need_index="zone statistics need at least one index")
+    indices = p.indices
+    lab, nz = _labels(zones, (p.h, p.w), n_zones, who)
     records = np.zeros((3, nz), dtype=_ffi.STATS_DTYPE)
     medians = np.zeros((3, nz, 2), dtype=np.float32)
     nvalid, bad = C.c_int64(-1), C.c_int64(-1)
-    p_out, p_rgba, p_lut = _ffi.ptr3(outs), _ffi.ptr3(rgbas), _ffi.ptr3(luts)
+    p_rgba, p_lut = _ffi.ptr3(p.rgbas), _ffi.ptr3(p.luts)
     try:
-        _ffi.call("lars_h_process_image_zones", _ffi.ptr(arr), h, w, c, code, int(bool(white_balance)), mask, int(bool(want_hist)),
-                  _ffi.ptr(out_wb), C.byref(p_out), C.byref(stats), _ffi.ptr(med), C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(valid_arr),
-                  int(use_alpha), int(nd is not None), nd or 0, C.byref(nvalid), _ffi.ptr(lab), lab.dtype.itemsize, nz,
-                  _ffi.ptr(records), _ffi.ptr(medians), C.byref(bad))
+        _ffi.call("lars_h_process_image_zones", *p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha),
+                  int(p.nodata is not None), p.nodata or 0, C.byref(nvalid), _ffi.ptr(lab), lab.dtype.itemsize, nz, _ffi.ptr(records),
+                  _ffi.ptr(medians), C.byref(bad))
     except _ffi.LarsError:
         if nvalid.value == 0:
             raise ValueError("process_image: no valid pixel") from None
         if bad.value > 0:
             raise _bad_labels(who, bad.value, nz) from None
         raise
-    result = {"corrected": out_wb, "indices": {}, "valid_pixels": int(nvalid.value)}
-    zone_part = {"zone": np.arange(1, nz + 1, dtype=np.int64)}
+    result = _picture_result(p, want_hist, want_rgba, False, valid_pixels=nvalid.value)
+    result["zones"] = {"zone": np.arange(1, nz + 1, dtype=np.int64)}
     for t in indices:
-        k = INDEX_IDS[t]
-        st = stats[k]
-        feature_name, _ = _coverage_rule(t)
-        median = float(np.float32(np.float32(med[k, 0] + med[k, 1]) / 2))
-        result["indices"][t] = {
-            "index": outs[k],
-            "rgba": rgbas[k] if want_rgba else None,
-            "entry": None,
-            "png": None,
-            "tiff": None,
-            "hist": np.array(list(st.hist), dtype=np.int64) if want_hist else None,
-            "stats": {
-                f"Mean {t}": st.sum / st.count,
-                f"Median {t}": median,
-                f"Min {t}": st.min,
-                f"Max {t}": st.max,
-                f"{feature_name} Coverage (%)": st.above / st.count * 100,
-            },
-        }
-        zone_part["pixels"], zone_part[t] = _figures(records[k], medians[k], want_hist)
-    result["zones"] = zone_part
+        result["zones"]["pixels"], result["zones"][t] = _figures(records[INDEX_IDS[t]], medians[INDEX_IDS[t]], want_hist)
     return result
 
 
 def zonal_rows(result_or_stats, index_type):
     """One dict per zone -- ``"Zone"``, ``"Pixels"`` and ``analyze_index``'s five keys for ``index_type`` -- from ``zonal_statistics``'s
     dict, ``process_image_zones``'s result or its ``"zones"`` part: the rows of a per-plot table or CSV."""
-    from .api import _coverage_rule
     if index_type not in INDEX_IDS:
         raise ValueError(f"zonal_rows: Unknown index type: {index_type}")
     part = result_or_stats.get("zones", result_or_stats)
