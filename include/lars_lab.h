@@ -33,6 +33,21 @@ int lars_lab_copy(int mode, int to_device, void *host, void *dev, size_t bytes);
  * (profiles/r04_arena_two_kinds.txt); this is the probe for a placement that splits the planes between them. */
 int lars_d_probe_mix3(const void *src, void *d0, void *d1, void *d2, int64_t nquads, int blocks, void *stream);
 
+/* One workgroup primitive of csrc/wg_device.h or csrc/checksum_device.h, run by one workgroup on device buffers
+ * (csrc/lab/wg_check.hip; tests/test_gpu_wg.py):
+ *   EXSCAN32 / EXSCAN64  wg_exscan<n> (n = 64, 256, 1024 threads) of in[n]: out[0 .. n) the prefixes, out[n] the total, then the
+ *                        same of a second call on the inclusive values at out[n + 1 .. 2n + 2)
+ *   SCAN_WIDEN           wg_scan_array of uint32 in[n] into uint64 out[n], out[n] = the total
+ *   SCAN_SATURATING      in place on uint32 out[n]: prefixes stored as min(prefix, 2^32 - 1), out[n] = min(total, a)
+ *   CRC32                wg_crc32<256> of the n bytes at in -> uint32 out[0]
+ *   ADLER                Adler-32 of the n bytes at in joined from the segments [0, a), [a, b), [b, n) -> uint32 out[0] */
+#define LARS_LAB_WG_EXSCAN32 0
+#define LARS_LAB_WG_EXSCAN64 1
+#define LARS_LAB_WG_SCAN_WIDEN 2
+#define LARS_LAB_WG_SCAN_SATURATING 3
+#define LARS_LAB_WG_CRC32 4
+#define LARS_LAB_WG_ADLER 5
+int lars_lab_wg_check(int prim, const void *in, void *out, int64_t n, uint64_t a, uint64_t b, void *stream);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@
 //   process-images.py:695       imshow(cmap, vmin=-1, vmax=1)
 #include "common.h"
 #include "device_common.h"
+#include "wg_device.h"
 
 namespace lars {
 
@@ -16,93 +17,44 @@ namespace lars {
 // Statistics of a float32 / float64 array
 // ===========================================================================
 // Deterministic: every block writes one partial record, a single block folds
-// them in block order.
-struct ArrPartial {
-    double sum, sumsq, mn, mx;
-    unsigned long long above, nans, count;
-    unsigned long long pad;
-};
-
+// them in block order (StatPartial: wg_device.h).
 template <typename T>
 __global__ __launch_bounds__(256) void k_array_stats(const T *__restrict__ x, long long n, T thr, int want_hist,
-                                                     ArrPartial *__restrict__ partials,
+                                                     StatPartial *__restrict__ partials,
                                                      unsigned long long *__restrict__ ghist)
 {
     __shared__ unsigned int s_hist[LARS_HIST_BINS];
     __shared__ HistCell<T> s_edges[LARS_HIST_CELLS];
-    __shared__ ArrPartial s_part[4];
+    __shared__ StatPartial s_part[4];
     const int tid = threadIdx.x;
     if (want_hist) {
         if (tid < LARS_HIST_BINS) s_hist[tid] = 0;
         hist_cells_init<T>(s_edges, tid);
         __syncthreads();
     }
-    double sum = 0, sumsq = 0;
-    double mn = __builtin_inf(), mx = -__builtin_inf();
-    unsigned long long above = 0, nans = 0, count = 0;
+    StatPartial p;
+    p.init();
     for (long long i = (long long)blockIdx.x * 256 + tid; i < n; i += (long long)gridDim.x * 256) {
         const T v = x[i];
-        if (v != v) { ++nans; continue; }
-        const double d = (double)v;
-        sum += d; sumsq += d * d;
-        mn = fmin(mn, d); mx = fmax(mx, d);
-        above += (v > thr) ? 1 : 0;
-        ++count;
+        if (!p.push(v, thr)) continue;
         if (want_hist && v >= (T)-1 && v <= (T)1) atomicAdd(&s_hist[hist_bin_cell<T>(v, s_edges)], 1u);
     }
-    for (int off = 32; off >= 1; off >>= 1) {
-        sum += __shfl_xor(sum, off); sumsq += __shfl_xor(sumsq, off);
-        mn = fmin(mn, __shfl_xor(mn, off)); mx = fmax(mx, __shfl_xor(mx, off));
-        above += __shfl_xor(above, off); nans += __shfl_xor(nans, off); count += __shfl_xor(count, off);
-    }
-    if ((tid & 63) == 0) {
-        ArrPartial p; p.sum = sum; p.sumsq = sumsq; p.mn = mn; p.mx = mx; p.above = above; p.nans = nans; p.count = count; p.pad = 0;
-        s_part[tid >> 6] = p;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        ArrPartial p = s_part[0];
-        for (int w = 1; w < 4; ++w) {
-            p.sum += s_part[w].sum; p.sumsq += s_part[w].sumsq;
-            p.mn = fmin(p.mn, s_part[w].mn); p.mx = fmax(p.mx, s_part[w].mx);
-            p.above += s_part[w].above; p.nans += s_part[w].nans; p.count += s_part[w].count;
-        }
-        partials[blockIdx.x] = p;
-    }
+    p.block_reduce(s_part);
+    if (tid == 0) partials[blockIdx.x] = p;
     if (want_hist && tid < LARS_HIST_BINS && s_hist[tid]) atomicAdd(&ghist[tid], (unsigned long long)s_hist[tid]);
 }
 
 // one block of 256 threads folds the per-block partials (a fixed tree: the double sums do not depend on timing)
-__global__ __launch_bounds__(256) void k_array_stats_fold(const ArrPartial *__restrict__ partials, int nblocks, double thr,
+__global__ __launch_bounds__(256) void k_array_stats_fold(const StatPartial *__restrict__ partials, int nblocks, double thr,
                                                           const unsigned long long *__restrict__ ghist, int want_hist, lars_stats *out)
 {
-    __shared__ ArrPartial s_p[4];
+    __shared__ StatPartial s_p[4];
     const int tid = threadIdx.x;
-    ArrPartial p;
-    p.sum = 0; p.sumsq = 0; p.mn = __builtin_inf(); p.mx = -__builtin_inf(); p.above = 0; p.nans = 0; p.count = 0; p.pad = 0;
-    for (int b = tid; b < nblocks; b += 256) {
-        const ArrPartial q = partials[b];
-        p.sum += q.sum; p.sumsq += q.sumsq;
-        p.mn = fmin(p.mn, q.mn); p.mx = fmax(p.mx, q.mx);
-        p.above += q.above; p.nans += q.nans; p.count += q.count;
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-        p.sum += __shfl_xor(p.sum, off); p.sumsq += __shfl_xor(p.sumsq, off);
-        p.mn = fmin(p.mn, __shfl_xor(p.mn, off)); p.mx = fmax(p.mx, __shfl_xor(p.mx, off));
-        p.above += __shfl_xor(p.above, off); p.nans += __shfl_xor(p.nans, off); p.count += __shfl_xor(p.count, off);
-    }
-    if ((tid & 63) == 0) s_p[tid >> 6] = p;
-    __syncthreads();
-    if (tid == 0) {
-        p = s_p[0];
-        for (int w = 1; w < 4; ++w) {
-            p.sum += s_p[w].sum; p.sumsq += s_p[w].sumsq;
-            p.mn = fmin(p.mn, s_p[w].mn); p.mx = fmax(p.mx, s_p[w].mx);
-            p.above += s_p[w].above; p.nans += s_p[w].nans; p.count += s_p[w].count;
-        }
-        out->sum = p.sum; out->sumsq = p.sumsq; out->count = p.count + p.nans; out->above = p.above; out->nans = p.nans;
-        out->min = p.mn; out->max = p.mx; out->threshold = thr; out->index_id = 0xFFFFFFFFu; out->reserved = 0;
-    }
+    StatPartial p;
+    p.init();
+    for (int b = tid; b < nblocks; b += 256) p.merge(partials[b]);
+    p.block_reduce(s_p);
+    if (tid == 0) p.to_stats(out, thr);
     if (tid < LARS_HIST_BINS) out->hist[tid] = want_hist ? ghist[tid] : 0ull;
 }
 
@@ -203,24 +155,15 @@ __global__ __launch_bounds__(256) void k_sel_hist(const T *__restrict__ x, long 
 __global__ __launch_bounds__(256) void k_sel_pick(SelectState *st, int shift, int bits)
 {
     // one block per item: find the digit whose cumulative count covers rank k
-    __shared__ unsigned long long s_cum[256];
+    __shared__ unsigned long long s_cum[4];
     SelectState *s = st + blockIdx.y;
     const int tid = threadIdx.x;
     const int nb = 1 << bits;
     const int per = (nb + 255) / 256;
     unsigned long long local = 0;
     for (int j = 0; j < per; ++j) { const int b = tid * per + j; if (b < nb) local += s->hist[b]; }
-    s_cum[tid] = local;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        unsigned long long v = tid >= off ? s_cum[tid - off] : 0;
-        __syncthreads();
-        s_cum[tid] += v;
-        __syncthreads();
-    }
-    const unsigned long long k = s->k;
-    unsigned long long cum = s_cum[tid] - local;
-    __syncthreads();
+    const unsigned long long k = s->k;                             // read by every thread before the scan's barriers, written after them
+    unsigned long long cum = wg_exscan<256>(local, s_cum);
     for (int j = 0; j < per; ++j) {
         const int b = tid * per + j;
         if (b < nb) {
@@ -239,7 +182,7 @@ __global__ __launch_bounds__(256) void k_sel_pick(SelectState *st, int shift, in
 template <typename T>
 __global__ __launch_bounds__(256) void k_sel_next(const T *__restrict__ x, long long n, long long stride, SelectState *st)
 {
-    __shared__ unsigned long long s_c[4], s_m[4];
+    __shared__ unsigned long long s_w[8];
     SelectState *s = st + blockIdx.y;
     x += (long long)blockIdx.y * stride;
     const unsigned long long sel = s->prefix;
@@ -249,19 +192,10 @@ __global__ __launch_bounds__(256) void k_sel_next(const T *__restrict__ x, long 
         if (key <= sel) ++c_le;
         else nxt = key < nxt ? key : nxt;
     }
-    for (int off = 32; off >= 1; off >>= 1) {
-        c_le += __shfl_xor(c_le, off);
-        const unsigned long long o = __shfl_xor(nxt, off);
-        nxt = o < nxt ? o : nxt;
-    }
-    if ((threadIdx.x & 63) == 0) { s_c[threadIdx.x >> 6] = c_le; s_m[threadIdx.x >> 6] = nxt; }
-    __syncthreads();
+    wg_count_le_next<256>(c_le, nxt, s_w);
     if (threadIdx.x == 0) {
-        unsigned long long c = s_c[0] + s_c[1] + s_c[2] + s_c[3];
-        unsigned long long m = s_m[0];
-        for (int w = 1; w < 4; ++w) m = s_m[w] < m ? s_m[w] : m;
-        atomicAdd(&s->c_le, c);
-        atomicMin(&s->next_key, m);
+        atomicAdd(&s->c_le, c_le);
+        atomicMin(&s->next_key, nxt);
     }
 }
 
@@ -353,21 +287,8 @@ __global__ __launch_bounds__(256) void k_colormap_entry(const float *__restrict_
 
 using namespace lars;
 
-static int grid_for(long long n)
-{
-    long long b = (n + 255) / 256;
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
 // reductions that end in atomics or a per-block partial: fewer blocks with at least 16 elements per thread
-static int grid_for_reduce(long long n)
-{
-    long long b = (n + 4095) / 4096;
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
+static int grid_for_reduce(long long n) { return grid_1d(n, 4096); }
 
 template <typename T>
 static int array_stats_impl(const T *x, int64_t n, T thr, int want_hist, lars_stats *out_dev, double *sumsqdev_dev,
@@ -378,9 +299,9 @@ static int array_stats_impl(const T *x, int64_t n, T thr, int want_hist, lars_st
     if (!x || n <= 0 || !out_dev) return fail(LARS_ERR_INVALID, "lars_d_array_stats: bad arguments");
     hipStream_t s = pick_stream(c, stream);
     const int nb = grid_for_reduce(n);
-    const size_t need = (size_t)nb * sizeof(ArrPartial) + LARS_HIST_BINS * sizeof(unsigned long long) + (size_t)nb * sizeof(double);
+    const size_t need = (size_t)nb * sizeof(StatPartial) + LARS_HIST_BINS * sizeof(unsigned long long) + (size_t)nb * sizeof(double);
     LARS_TRY(scratch_reserve(c, need));
-    ArrPartial *parts = static_cast<ArrPartial *>(c->scratch);
+    StatPartial *parts = static_cast<StatPartial *>(c->scratch);
     unsigned long long *ghist = reinterpret_cast<unsigned long long *>(parts + nb);
     double *dparts = reinterpret_cast<double *>(ghist + LARS_HIST_BINS);
     LARS_HIP_TRY(hipMemsetAsync(ghist, 0, LARS_HIST_BINS * sizeof(unsigned long long), s));
@@ -473,7 +394,7 @@ extern "C" int lars_d_index_planes_f32(const float *red, const float *green, con
     if (!red || !green || !nir || !out || n <= 0 || index_id < 0 || index_id > 2)
         return fail(LARS_ERR_INVALID, "lars_d_index_planes_f32: bad arguments");
     hipStream_t s = pick_stream(c, stream);
-    hipLaunchKernelGGL(k_index_planes, dim3(grid_for(n)), dim3(256), 0, s, red, green, nir, (long long)n, index_id, out);
+    hipLaunchKernelGGL(k_index_planes, dim3(grid_1d(n)), dim3(256), 0, s, red, green, nir, (long long)n, index_id, out);
     return launch_check("lars_d_index_planes_f32");
 }
 
@@ -484,10 +405,10 @@ extern "C" int lars_d_ndvi_f64(const void *img, int64_t npix, int channels, int 
     if (!img || !out || npix <= 0 || channels < 3) return fail(LARS_ERR_INVALID, "lars_d_ndvi_f64: bad arguments");
     hipStream_t s = pick_stream(c, stream);
     if (dtype == LARS_U8)
-        hipLaunchKernelGGL((k_ndvi_f64<uint8_t>), dim3(grid_for(npix)), dim3(256), 0, s, static_cast<const uint8_t *>(img),
+        hipLaunchKernelGGL((k_ndvi_f64<uint8_t>), dim3(grid_1d(npix)), dim3(256), 0, s, static_cast<const uint8_t *>(img),
                            (long long)npix, channels, out);
     else if (dtype == LARS_U16)
-        hipLaunchKernelGGL((k_ndvi_f64<uint16_t>), dim3(grid_for(npix)), dim3(256), 0, s,
+        hipLaunchKernelGGL((k_ndvi_f64<uint16_t>), dim3(grid_1d(npix)), dim3(256), 0, s,
                            static_cast<const uint16_t *>(img), (long long)npix, channels, out);
     else
         return fail(LARS_ERR_INVALID, "lars_d_ndvi_f64: dtype");
@@ -513,9 +434,9 @@ extern "C" int lars_d_threshold_mask_f32(const float *x, int64_t n, float thresh
 {
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
-    if (!x || !out_mask || n <= 0 || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(out_mask) & 3))
+    if (!x || !out_mask || n <= 0 || !aligned_to(x, 16) || !aligned_to(out_mask, 4))
         return fail(LARS_ERR_INVALID, "lars_d_threshold_mask_f32: bad arguments (x 16-byte, out_mask 4-byte aligned)");
-    hipLaunchKernelGGL(k_threshold_mask, dim3(grid_for((n + 3) / 4)), dim3(256), 0, pick_stream(c, stream), x, (long long)n, threshold,
+    hipLaunchKernelGGL(k_threshold_mask, dim3(grid_1d((n + 3) / 4)), dim3(256), 0, pick_stream(c, stream), x, (long long)n, threshold,
                        out_mask);
     return launch_check("lars_d_threshold_mask_f32");
 }
@@ -526,7 +447,7 @@ extern "C" int lars_d_colormap_f32(const float *x, int64_t n, const uint8_t *lut
     LARS_TRY(ensure_ctx(&c));
     if (!x || !lut_rgba || !out_rgba || n <= 0) return fail(LARS_ERR_INVALID, "lars_d_colormap_f32: bad arguments");
     hipStream_t s = pick_stream(c, stream);
-    hipLaunchKernelGGL(k_colormap, dim3(grid_for(n)), dim3(256), 0, s, x, (long long)n,
+    hipLaunchKernelGGL(k_colormap, dim3(grid_1d(n)), dim3(256), 0, s, x, (long long)n,
                        reinterpret_cast<const unsigned int *>(lut_rgba), reinterpret_cast<unsigned int *>(out_rgba));
     return launch_check("lars_d_colormap_f32");
 }
@@ -536,9 +457,9 @@ extern "C" int lars_d_colormap_entry_f32(const float *x, int64_t n, uint8_t *out
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (!x || !out_entry || n <= 0) return fail(LARS_ERR_INVALID, "lars_d_colormap_entry_f32: bad arguments");
-    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(out_entry) & 3))
+    if (!aligned_to(x, 16) || !aligned_to(out_entry, 4))
         return fail(LARS_ERR_INVALID, "lars_d_colormap_entry_f32: x on a 16-byte, out_entry on a 4-byte boundary");
     hipStream_t s = pick_stream(c, stream);
-    hipLaunchKernelGGL(k_colormap_entry, dim3(grid_for((n + 3) / 4)), dim3(256), 0, s, x, (long long)n, out_entry);
+    hipLaunchKernelGGL(k_colormap_entry, dim3(grid_1d((n + 3) / 4)), dim3(256), 0, s, x, (long long)n, out_entry);
     return launch_check("lars_d_colormap_entry_f32");
 }

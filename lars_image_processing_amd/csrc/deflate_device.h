@@ -7,6 +7,7 @@
 // larger is stored instead.  Each segment also leaves its Adler-32 partial sums.  tests/png_encode_model.py restates lane 0's work.
 #pragma once
 
+#include "checksum_device.h"
 #include "common.h"
 
 namespace lars {
@@ -95,7 +96,7 @@ __device__ inline void put_bits(unsigned int *buf, unsigned int &pos, unsigned i
 // DEFLATE_SEG, becomes one block at z (DEFLATE_ZCAP bytes).  first: the segment opens its zlib stream and writes the header 78 01.
 // last: the block carries BFINAL, no empty stored block follows it, and *seglen counts four more bytes, which the caller fills
 // with the stream's Adler-32 behind the block.  *seglen = bytes at z; adl[0] = sum of the bytes, adl[1] = sum of (n - j) * byte_j,
-// both mod 65521.  LDS: 43.0 KiB of static arrays.
+// both mod ADLER_MOD.  LDS: 38.0 KiB of static arrays.
 __device__ __forceinline__ void deflate_segment(const uint8_t *__restrict__ in, const int n, const bool first, const bool last,
                                                 uint8_t *__restrict__ z, unsigned int *__restrict__ seglen, unsigned int *__restrict__ adl)
 {
@@ -104,8 +105,8 @@ __device__ __forceinline__ void deflate_segment(const uint8_t *__restrict__ in, 
     __shared__ unsigned int key[288];
     __shared__ unsigned short sym[288];
     __shared__ unsigned int obuf[DEFLATE_OUT_WORDS];
-    __shared__ unsigned long long red[2][DEFLATE_THREADS];
-    __shared__ unsigned int scan[DEFLATE_THREADS];
+    __shared__ unsigned long long s_red[2 * DEFLATE_THREADS / 64];
+    __shared__ unsigned int s_scan[DEFLATE_THREADS / 64];
     __shared__ uint8_t lens[260], rsym[260], rext[260];   // lane 0's work arrays
     __shared__ unsigned int s_nused, s_hdr_bits, s_data_bits, s_huff, s_body;
     const int tid = threadIdx.x;
@@ -121,17 +122,11 @@ __device__ __forceinline__ void deflate_segment(const uint8_t *__restrict__ in, 
         s1 += b;
         s2 += (unsigned long long)(n - j) * b;
     }
-    red[0][tid] = s1;
-    red[1][tid] = s2;
-    __syncthreads();
-    for (int half = DEFLATE_THREADS / 2; half > 0; half >>= 1) {
-        if (tid < half) { red[0][tid] += red[0][tid + half]; red[1][tid] += red[1][tid + half]; }
-        __syncthreads();
-    }
+    adler_wg<DEFLATE_THREADS>(s1, s2, s_red);
     if (tid == 0) {
         hist[256] = 1;                           // end of block
-        adl[0] = (unsigned int)(red[0][0] % 65521ull);
-        adl[1] = (unsigned int)(red[1][0] % 65521ull);
+        adl[0] = (unsigned int)s1;
+        adl[1] = (unsigned int)s2;
     }
     __syncthreads();
     // rank sort of the used symbols by (frequency, symbol)
@@ -231,15 +226,7 @@ __device__ __forceinline__ void deflate_segment(const uint8_t *__restrict__ in, 
         const int lo = min(n, tid * chunk), hi = min(n, lo + chunk);
         unsigned int bits = 0;
         for (int j = lo; j < hi; ++j) bits += table[in[j]] >> 16;
-        scan[tid] = bits;
-        __syncthreads();
-        for (int off = 1; off < DEFLATE_THREADS; off <<= 1) {
-            const unsigned int v = tid >= off ? scan[tid - off] : 0u;
-            __syncthreads();
-            scan[tid] += v;
-            __syncthreads();
-        }
-        unsigned int pos = s_hdr_bits + scan[tid] - bits;
+        unsigned int pos = s_hdr_bits + wg_exscan<DEFLATE_THREADS>(bits, s_scan);
         unsigned long long acc = 0;
         unsigned int nacc = pos & 31u, w = pos >> 5;
         for (int j = lo; j < hi; ++j) {

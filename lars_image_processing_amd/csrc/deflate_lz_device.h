@@ -45,7 +45,7 @@ struct DlzForm {
     uint8_t lens[320], rsym[320], rext[320], clen[20];
     unsigned int hdr_bits, data_bits, bytes;
 };
-static_assert(2 * sizeof(DlzForm) + DLZ_THREADS * 4 <= DLZ_POOL_WORDS * 4, "two forms and the scan share the pool");
+static_assert(2 * sizeof(DlzForm) + DLZ_THREADS / 64 * 4 <= DLZ_POOL_WORDS * 4, "two forms and the scan's words share the pool");
 
 __device__ inline void dlz_length_symbol(unsigned int length, unsigned int &s, unsigned int &eb, unsigned int &ev)
 {
@@ -271,20 +271,18 @@ __device__ __forceinline__ void deflate_lz_segment(const uint8_t *__restrict__ i
     __shared__ __attribute__((aligned(16))) unsigned int s_segw[DEFLATE_SEG / 4 + 2];   // the segment, and 8 bytes a word read may touch
     __shared__ uint8_t s_len[DEFLATE_SEG];                 // match length - 3 of a position's taken match
     __shared__ unsigned short s_dist[DEFLATE_SEG];         // its distance, 0 = no match taken (the hash rounds keep head + 1 here)
-    __shared__ unsigned int s_onpath[DEFLATE_SEG / 32];    // bit j: the greedy parse visits j
+    __shared__ __attribute__((aligned(8))) unsigned int s_onpath[DEFLATE_SEG / 32];   // bit j: the greedy parse visits j (before step 4: the Adler sums' words)
     __shared__ __attribute__((aligned(16))) unsigned int s_pool[DLZ_POOL_WORDS];
     __shared__ unsigned int s_hm[288], s_hl[288], s_hd[32];   // histograms: matched literal/length, literal-only, distance
     __shared__ unsigned short s_entry[DLZ_PARSE_ROUND / DLZ_PARSE_BLOCK];
-    __shared__ unsigned long long s_sum[2];
+    static_assert(sizeof(s_onpath) >= 2 * (DLZ_THREADS / 64) * sizeof(unsigned long long), "adler_wg's words fit");
     __shared__ unsigned int s_pos;
     const int tid = threadIdx.x;
     const int pre = first ? 2 : 0;
     uint8_t *seg = reinterpret_cast<uint8_t *>(s_segw);
 
     // 1. stage, Adler sums
-    if (tid < 2) s_sum[tid] = 0;
     if (tid == 0) s_pos = 0;
-    __syncthreads();
     {
         unsigned long long s1 = 0, s2 = 0;
         for (int j = tid; j < n; j += DLZ_THREADS) {
@@ -293,8 +291,11 @@ __device__ __forceinline__ void deflate_lz_segment(const uint8_t *__restrict__ i
             s1 += b;
             s2 += (unsigned long long)(n - j) * b;
         }
-        atomicAdd(&s_sum[0], s1);
-        atomicAdd(&s_sum[1], s2);
+        adler_wg<DLZ_THREADS>(s1, s2, reinterpret_cast<unsigned long long *>(s_onpath));
+        if (tid == 0) {
+            adl[0] = (unsigned int)s1;
+            adl[1] = (unsigned int)s2;
+        }
     }
     auto word_at = [&](int p) -> unsigned int {          // the 4 bytes at p, little-endian (p + 3 may pass n: callers cap)
         const unsigned long long both = ((unsigned long long)s_segw[(p >> 2) + 1] << 32) | s_segw[p >> 2];
@@ -314,10 +315,6 @@ __device__ __forceinline__ void deflate_lz_segment(const uint8_t *__restrict__ i
     unsigned int *head = s_pool;                          // position + 1, 0 = none
     for (int i = tid; i < (1 << DLZ_HASH_BITS); i += DLZ_THREADS) head[i] = 0;
     __syncthreads();
-    if (tid == 0) {
-        adl[0] = (unsigned int)(s_sum[0] % 65521ull);
-        adl[1] = (unsigned int)(s_sum[1] % 65521ull);
-    }
     const int nh = n - 3;                                 // positions below nh have a hash
     for (int t0 = 0; t0 < nh; t0 += DLZ_TILE) {
         const int j = t0 + tid;
@@ -459,17 +456,10 @@ __device__ __forceinline__ void deflate_lz_segment(const uint8_t *__restrict__ i
                 bits += F.table[seg[j]] >> 16;
             }
         }
-        scan[tid] = bits;
-        __syncthreads();                                  // also: the zeroed words are visible to the whole workgroup
-        for (int off = 1; off < DLZ_THREADS; off <<= 1) {
-            const unsigned int v = tid >= off ? scan[tid - off] : 0u;
-            __syncthreads();
-            scan[tid] += v;
-            __syncthreads();
-        }
+        const unsigned int before = wg_exscan<DLZ_THREADS>(bits, scan);   // its barriers also make the zeroed words visible to the whole workgroup
         const unsigned int bit0 = 8u * (unsigned int)pre;
         DlzSink sink;
-        sink.open(zw, bit0 + F.hdr_bits + scan[tid] - bits);
+        sink.open(zw, bit0 + F.hdr_bits + before);
         for (int j = lo; j < hi; ++j) {
             if (!matched) { const unsigned int e = F.table[seg[j]]; sink.add(e & 0xFFFFu, e >> 16); continue; }
             if (!((s_onpath[j >> 5] >> (j & 31)) & 1u)) continue;

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "device_common.h"
 #include "fused_device.h"
+#include "wg_device.h"
 
 namespace lars {
 
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(256) void k_wb_table(const unsigned int *__restrict
                                                   int rgn_variant)
 {
     constexpr int PER = NVAL / 256;                   // bins per thread
-    __shared__ unsigned long long s_scan[256];
+    __shared__ unsigned long long s_scan[4];
     __shared__ double s_val[4];                       // order statistics: q2.lo q2.hi q98.lo q98.hi
     __shared__ double s_p[2];
     __shared__ unsigned int s_thr[NVAL == 256 ? 4 : 260];
@@ -122,16 +123,7 @@ __global__ __launch_bounds__(256) void k_wb_table(const unsigned int *__restrict
 
     unsigned long long local = 0;
     for (int j = 0; j < PER; ++j) local += h[tid * PER + j];
-    s_scan[tid] = local;
-    __syncthreads();
-    // inclusive Hillis-Steele scan over 256 thread sums
-    for (int off = 1; off < 256; off <<= 1) {
-        unsigned long long v = (tid >= off) ? s_scan[tid - off] : 0;
-        __syncthreads();
-        s_scan[tid] += v;
-        __syncthreads();
-    }
-    const unsigned long long before = s_scan[tid] - local;   // samples in bins below this thread's
+    const unsigned long long before = wg_exscan<256>(local, s_scan);   // samples in bins below this thread's
 
     const double nm1 = (double)(npix - 1);
     double tq[2];

@@ -18,4 +18,14 @@ int fail(int code, const char *fmt, ...);
         if (_s != LARS_OK) return _s; \
     } while (0)
 
+// workgroups of a one-dimensional grid-stride launch over n items, per_block items to a workgroup's first sweep: 1 .. 2048
+inline int grid_1d(long long n, long long per_block = 256)
+{
+    const long long b = (n + per_block - 1) / per_block;
+    return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
+}
+
+// p on a multiple of a (a power of two)
+inline bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
 }  // namespace lars

@@ -53,6 +53,7 @@
 
 #include "codec_host.h"
 #include "jpeg_parse.h"
+#include "wg_device.h"
 
 namespace lars {
 
@@ -186,38 +187,10 @@ __global__ __launch_bounds__(JD_MARK_THREADS) void k_jd_mark(const uint8_t *seg,
 // exclusive scan of in[0..n) by one workgroup per channel (blockIdx.x * stride), chunk after chunk; in == out is fine
 __global__ __launch_bounds__(1024) void k_jd_exscan(const unsigned int *in, unsigned int *out, long long n, long long stride, unsigned int *total)
 {
-    __shared__ unsigned int wsum[16];
-    __shared__ unsigned int chunk_sum;
     in += (long long)blockIdx.x * stride;
     out += (long long)blockIdx.x * stride;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    unsigned int carry = 0;
-    for (long long base = 0; base < n; base += 1024) {
-        const long long i = base + tid;
-        const unsigned int v = i < n ? in[i] : 0u;
-        unsigned int incl = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned int t = __shfl_up(incl, d);
-            if (lane >= d) incl += t;
-        }
-        if (lane == 63) wsum[wv] = incl;
-        __syncthreads();
-        if (wv == 0) {
-            const unsigned int s = lane < 16 ? wsum[lane] : 0u;
-            unsigned int si = s;
-            for (int d = 1; d < 16; d <<= 1) {
-                const unsigned int t = __shfl_up(si, d);
-                if (lane >= d) si += t;
-            }
-            if (lane < 16) wsum[lane] = si - s;
-            if (lane == 15) chunk_sum = si;
-        }
-        __syncthreads();
-        if (i < n) out[i] = carry + wsum[wv] + incl - v;
-        carry += chunk_sum;
-        __syncthreads();
-    }
-    if (tid == 0 && total) total[blockIdx.x] = carry;
+    const unsigned int sum = wg_scan_array<unsigned int>(n, [&](long long i) { return in[i]; }, [&](long long i, unsigned int before) { out[i] = before; });
+    if (threadIdx.x == 0 && total) total[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(JD_MARK_THREADS) void k_jd_compact(const uint8_t *seg, long long n, const unsigned int *keepoff,

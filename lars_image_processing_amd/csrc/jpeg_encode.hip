@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "codec_host.h"
+#include "wg_device.h"
 #include "jpeg_tables.h"
 
 namespace lars {
@@ -261,38 +262,17 @@ __device__ inline void je_load_codes(JpegEncCodes *dst, const JeTables *T)
     __syncthreads();
 }
 
-// exclusive scan of one value per lane over the workgroup (JE_THREADS lanes); *total = the sum.  Every lane must call it.
-__device__ inline unsigned int je_wg_exscan(unsigned int v, unsigned int *total)
-{
-    __shared__ unsigned int wsum[JE_THREADS / 64 + 1];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    unsigned int incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned int t = __shfl_up(incl, d);
-        if (lane >= d) incl += t;
-    }
-    __syncthreads();                                         // a second call must not overwrite sums still being read
-    if (lane == 63) wsum[wv] = incl;
-    __syncthreads();
-    unsigned int before = 0, all = 0;
-    for (int i = 0; i < JE_THREADS / 64; ++i) {
-        if (i < wv) before += wsum[i];
-        all += wsum[i];
-    }
-    *total = all;
-    return before + incl - v;
-}
-
 __global__ __launch_bounds__(JE_THREADS) void k_je_size(const short *__restrict__ coef, JpegEncGeo g, const JeTables *__restrict__ T,
                                                         unsigned int *__restrict__ loc, unsigned int *__restrict__ wgsum)
 {
     __shared__ JpegEncCodes C;
+    __shared__ unsigned int s_w[JE_THREADS / 64];
     je_load_codes(&C, T);
     const long long gb = (long long)blockIdx.x * JE_THREADS + threadIdx.x;
     unsigned int bits = 0;
     if (gb < g.nblocks) je_block_codes(coef, g, C, gb, [&](unsigned int, int n) { bits += (unsigned int)n; });
     unsigned int total;
-    const unsigned int excl = je_wg_exscan(bits, &total);
+    const unsigned int excl = wg_exscan<JE_THREADS>(bits, s_w, &total);
     if (gb < g.nblocks) loc[gb] = excl;
     if (threadIdx.x == 0) wgsum[blockIdx.x] = total;
 }
@@ -302,37 +282,9 @@ __global__ __launch_bounds__(JE_THREADS) void k_je_size(const short *__restrict_
 __global__ __launch_bounds__(1024) void k_je_exscan64(const unsigned int *__restrict__ in, je_u64 *__restrict__ out, long long n,
                                                       const je_u64 *bits, je_u64 *total)
 {
-    __shared__ je_u64 wsum[16];
-    __shared__ je_u64 chunk_sum;
     if (bits) n = min(n, (long long)(((*bits + 7) / 8 + JE_CHUNK - 1) / JE_CHUNK));
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    je_u64 carry = 0;
-    for (long long base = 0; base < n; base += 1024) {
-        const long long i = base + tid;
-        const je_u64 v = i < n ? in[i] : 0u;
-        je_u64 incl = v;
-        for (int d = 1; d < 64; d <<= 1) {
-            const je_u64 t = __shfl_up(incl, d);
-            if (lane >= d) incl += t;
-        }
-        if (lane == 63) wsum[wv] = incl;
-        __syncthreads();
-        if (wv == 0) {
-            const je_u64 sv = lane < 16 ? wsum[lane] : 0u;
-            je_u64 si = sv;
-            for (int d = 1; d < 16; d <<= 1) {
-                const je_u64 t = __shfl_up(si, d);
-                if (lane >= d) si += t;
-            }
-            if (lane < 16) wsum[lane] = si - sv;
-            if (lane == 15) chunk_sum = si;
-        }
-        __syncthreads();
-        if (i < n) out[i] = carry + wsum[wv] + incl - v;
-        carry += chunk_sum;
-        __syncthreads();
-    }
-    if (tid == 0) *total = carry;
+    const je_u64 sum = wg_scan_array<je_u64>(n, [&](long long i) { return in[i]; }, [&](long long i, je_u64 before) { out[i] = before; });
+    if (threadIdx.x == 0) *total = sum;
 }
 
 __global__ __launch_bounds__(JE_THREADS) void k_je_zero(unsigned int *__restrict__ words, je_u64 cap_words, const JeCtl *ctl)
@@ -400,6 +352,7 @@ __device__ inline unsigned int je_stream_byte(unsigned int word, int j) { return
 
 __global__ __launch_bounds__(JE_THREADS) void k_je_count(const unsigned int *__restrict__ words, const JeCtl *ctl, unsigned int *__restrict__ ffcnt)
 {
+    __shared__ unsigned int s_w[JE_THREADS / 64];
     const je_u64 nbytes = (ctl->total_bits + 7) / 8;
     const je_u64 base = (je_u64)blockIdx.x * JE_CHUNK;
     if (base >= nbytes) return;
@@ -410,7 +363,7 @@ __global__ __launch_bounds__(JE_THREADS) void k_je_count(const unsigned int *__r
         for (int j = 0; j < 4; ++j) n += (at + j < nbytes && je_stream_byte(w, j) == 255u) ? 1u : 0u;
     }
     unsigned int total;
-    je_wg_exscan(n, &total);
+    wg_exscan<JE_THREADS>(n, s_w, &total);
     if (threadIdx.x == 0) ffcnt[blockIdx.x] = total;
 }
 
@@ -418,6 +371,7 @@ __global__ __launch_bounds__(JE_THREADS) void k_je_stuff(const unsigned int *__r
                                                          const JeTables *__restrict__ T, JeCtl *ctl, uint8_t *__restrict__ out, je_u64 out_cap,
                                                          long long *out_len)
 {
+    __shared__ unsigned int s_w[JE_THREADS / 64];
     const je_u64 nbytes = (ctl->total_bits + 7) / 8;
     const je_u64 base = (je_u64)blockIdx.x * JE_CHUNK;
     const je_u64 nhead = (je_u64)T->nhead;
@@ -442,7 +396,7 @@ __global__ __launch_bounds__(JE_THREADS) void k_je_stuff(const unsigned int *__r
         for (int j = 0; j < 4; ++j) n += (at + j < nbytes && je_stream_byte(w, j) == 255u) ? 1u : 0u;
     }
     unsigned int total;
-    const unsigned int excl = je_wg_exscan(n, &total);
+    const unsigned int excl = wg_exscan<JE_THREADS>(n, s_w, &total);
     if (at >= nbytes) return;
     je_u64 o = nhead + at + ffoff[blockIdx.x] + excl;
     for (int j = 0; j < 4 && at + j < nbytes; ++j) {

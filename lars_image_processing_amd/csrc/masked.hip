@@ -307,24 +307,14 @@ __global__ __launch_bounds__(256) void k_masked_fused(MaskedParams P)
     }
 }
 
-int grid_for_quads(long long npix)
-{
-    long long b = ((npix >> 2) + 255) / 256;
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 // 3 / 4: a uint8 image of that many channels whose pointer allows the dword loads; 0: sample by sample
 int channel_form(const void *img, int channels, int dtype)
 {
     if (dtype != LARS_U8) return 0;
-    if (channels == 3 && (reinterpret_cast<uintptr_t>(img) & 3) == 0) return 3;
-    if (channels == 4 && (reinterpret_cast<uintptr_t>(img) & 15) == 0) return 4;
+    if (channels == 3 && aligned_to(img, 4)) return 3;
+    if (channels == 4 && aligned_to(img, 16)) return 4;
     return 0;
 }
-
-bool aligned_to(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 }  // namespace
 }  // namespace lars
@@ -345,7 +335,7 @@ extern "C" int lars_d_valid_mask(const void *img, int64_t npix, int channels, in
         return fail(LARS_ERR_INVALID, "lars_d_valid_mask: the masks must be 4-byte aligned, the counter 8-byte aligned");
     hipStream_t s = pick_stream(c, stream);
     LARS_HIP_TRY(hipMemsetAsync(count_dev, 0, sizeof(uint64_t), s));
-    const dim3 grid(grid_for_quads(npix)), block(256);
+    const dim3 grid(grid_1d(npix >> 2)), block(256);
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(count_dev);
     const unsigned int nd = (unsigned int)nodata;
     const int form = channel_form(img, channels, dtype);
@@ -375,7 +365,7 @@ extern "C" int lars_d_masked_channel_hist(const void *img, int64_t npix, int cha
     hipStream_t s = pick_stream(c, stream);
     const int nval = dtype == LARS_U8 ? 256 : 65536;
     LARS_HIP_TRY(hipMemsetAsync(hist, 0, (size_t)3 * nval * sizeof(uint32_t), s));
-    const dim3 grid(grid_for_quads(npix)), block(256);
+    const dim3 grid(grid_1d(npix >> 2)), block(256);
     const int form = channel_form(img, channels, dtype);
     if (form == 3)
         hipLaunchKernelGGL((k_masked_hist<uint8_t, 256, 3>), grid, block, 0, s, static_cast<const uint8_t *>(img), (long long)npix, channels, valid, hist);
@@ -422,7 +412,7 @@ extern "C" int lars_d_masked_fused(const lars_fused_args *a, const uint8_t *vali
     if (compacting) LARS_HIP_TRY(hipMemsetAsync(cursor_dev, 0, sizeof(uint64_t), s));
     P.img = a->tiles; P.valid = valid; P.npix = a->npix; P.channels = a->channels; P.wb_table = a->wb_table; P.mask = a->index_mask;
     P.out_wb = a->out_wb; P.cursor = reinterpret_cast<unsigned long long *>(cursor_dev);
-    const dim3 grid(grid_for_quads(a->npix)), block(256);
+    const dim3 grid(grid_1d(a->npix >> 2)), block(256);
     if (form == 3) hipLaunchKernelGGL((k_masked_fused<uint8_t, 256, 3>), grid, block, 0, s, P);
     else if (form == 4) hipLaunchKernelGGL((k_masked_fused<uint8_t, 256, 4>), grid, block, 0, s, P);
     else if (a->dtype == LARS_U8) hipLaunchKernelGGL((k_masked_fused<uint8_t, 256, 0>), grid, block, 0, s, P);

@@ -21,6 +21,7 @@
 //                  chunk's CRC-32 (per-thread pieces shifted by x^(8 * bytes after them) mod P, then XOR).
 #include <string.h>
 
+#include "checksum_device.h"
 #include "codec_host.h"
 #include "deflate_device.h"
 #include "deflate_lz_device.h"
@@ -30,7 +31,6 @@ namespace lars {
 #define PNG_SEG DEFLATE_SEG                     // bytes of filtered stream per deflate block (one workgroup)
 #define PNG_THREADS DEFLATE_THREADS
 #define PNG_ZCAP DEFLATE_ZCAP                   // per-segment output capacity
-#define PNG_CRC_POLY 0xEDB88320u
 
 __device__ inline unsigned int abs_s8(unsigned int v) { return v < 128u ? v : 256u - v; }
 
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(PNG_THREADS) void k_png_filter(const uint8_t *__res
 }
 
 // one workgroup per segment of the filtered stream -> Z + seg * PNG_ZCAP, seglen[seg] bytes; adl[2 seg] = sum of the bytes,
-// adl[2 seg + 1] = sum of (n - j) * byte_j, both mod 65521 (deflate_device.h)
+// adl[2 seg + 1] = sum of (n - j) * byte_j, both mod ADLER_MOD (deflate_device.h)
 __global__ __launch_bounds__(PNG_THREADS) void k_png_deflate(const uint8_t *__restrict__ filt, long long total, long long nseg,
                                                             uint8_t *__restrict__ Z, unsigned int *__restrict__ seglen,
                                                             unsigned int *__restrict__ adl)
@@ -116,48 +116,6 @@ __global__ __launch_bounds__(DLZ_THREADS) void k_png_deflate_lz(const uint8_t *_
     const long long base = seg * PNG_SEG;
     const int n = (int)(total - base < PNG_SEG ? total - base : PNG_SEG);
     deflate_lz_segment(filt + base, n, seg == 0, seg == nseg - 1, Z + seg * PNG_ZCAP, seglen + seg, adl + 2 * seg);
-}
-
-// ---- CRC-32 -----------------------------------------------------------------------------------------------------------
-__device__ void crc_table_fill(unsigned int *tab, int tid, int nthreads)
-{
-    for (int i = tid; i < 256; i += nthreads) {
-        unsigned int c = (unsigned int)i;
-        for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ PNG_CRC_POLY : c >> 1;
-        tab[i] = c;
-    }
-}
-
-__device__ inline unsigned int crc_update(const unsigned int *tab, unsigned int crc, unsigned int byte)
-{
-    return tab[(crc ^ byte) & 255u] ^ (crc >> 8);
-}
-
-// a * b mod P (reflected)
-__device__ unsigned int crc_multmodp(unsigned int a, unsigned int b)
-{
-    unsigned int m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0) break;
-        }
-        m >>= 1;
-        b = (b & 1u) ? (b >> 1) ^ PNG_CRC_POLY : b >> 1;
-    }
-    return p;
-}
-
-// x^(n * 2^k) mod P from x2n[i] = x^(2^i) mod P
-__device__ unsigned int crc_x2nmodp(const unsigned int *x2n, unsigned long long n, unsigned int k)
-{
-    unsigned int p = 1u << 31;
-    while (n) {
-        if (n & 1) p = crc_multmodp(x2n[k & 31], p);
-        n >>= 1;
-        ++k;
-    }
-    return p;
 }
 
 __device__ void put_be32(uint8_t *p, unsigned int v)
@@ -194,8 +152,7 @@ __global__ __launch_bounds__(PNG_FRAME_THREADS) void k_png_frame(long long nseg,
                                                                 uint8_t *__restrict__ out, unsigned long long out_cap,
                                                                 long long *__restrict__ out_len)
 {
-    __shared__ unsigned long long sums[PNG_FRAME_THREADS];
-    __shared__ unsigned long long a1[PNG_FRAME_THREADS], a2[PNG_FRAME_THREADS];
+    __shared__ unsigned long long s_w[2 * PNG_FRAME_THREADS / 64];
     __shared__ unsigned int tab[256];
     const int tid = threadIdx.x;
     crc_table_fill(tab, tid, PNG_FRAME_THREADS);
@@ -205,35 +162,19 @@ __global__ __launch_bounds__(PNG_FRAME_THREADS) void k_png_frame(long long nseg,
     for (long long k = lo; k < hi; ++k) {
         s += 12ull + seglen[k];
         const long long o = k * PNG_SEG, nk = min((long long)PNG_SEG, total - o);
-        const unsigned long long after = (unsigned long long)(total - o - nk) % 65521ull;
-        A = (A + adl[2 * k]) % 65521ull;
-        B = (B + adl[2 * k + 1] + after * adl[2 * k]) % 65521ull;
+        adler_append(A, B, adl[2 * k], adl[2 * k + 1], (unsigned long long)(total - o - nk));
     }
-    sums[tid] = s;
-    a1[tid] = A;
-    a2[tid] = B;
-    __syncthreads();
-    for (int d = 1; d < PNG_FRAME_THREADS; d <<= 1) {       // inclusive scan of the chunk bytes
-        const unsigned long long v = tid >= d ? sums[tid - d] : 0ull;
-        __syncthreads();
-        sums[tid] += v;
-        __syncthreads();
-    }
-    unsigned long long o = head + sums[tid] - s;
+    unsigned long long chunks;                              // the bytes of all IDAT chunks
+    unsigned long long o = head + wg_exscan<PNG_FRAME_THREADS>(s, s_w, &chunks);
     for (long long k = lo; k < hi; ++k) {
         off[k] = o;
         o += 12ull + seglen[k];
     }
-    for (int half = PNG_FRAME_THREADS / 2; half > 0; half >>= 1) {
-        if (tid < half) { a1[tid] = (a1[tid] + a1[tid + half]) % 65521ull; a2[tid] = (a2[tid] + a2[tid + half]) % 65521ull; }
-        __syncthreads();
-    }
+    adler_wg<PNG_FRAME_THREADS>(A, B, s_w);
     if (tid == 0) {
-        const unsigned int s1 = (unsigned int)((1ull + a1[0]) % 65521ull);
-        const unsigned int s2 = (unsigned int)(((unsigned long long)total % 65521ull + a2[0]) % 65521ull);
         uint8_t *zl = Z + (nseg - 1) * PNG_ZCAP + seglen[nseg - 1] - 4;
-        put_be32(zl, (s2 << 16) | s1);
-        const unsigned long long file = head + sums[PNG_FRAME_THREADS - 1] + 12ull;
+        put_be32(zl, adler_value(A, B, (unsigned long long)total));
+        const unsigned long long file = head + chunks + 12ull;
         if (file > out_cap) { *out_len = -1; return; }
         const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
         for (int i = 0; i < 8; ++i) out[i] = sig[i];
@@ -261,18 +202,14 @@ __global__ __launch_bounds__(PNG_THREADS) void k_png_idat(const uint8_t *__restr
 {
     __shared__ unsigned int tab[256];
     __shared__ unsigned int x2n[32];
-    __shared__ unsigned int part[PNG_THREADS];
+    __shared__ unsigned int part[PNG_THREADS / 64];
     const int tid = threadIdx.x;
     const long long seg = blockIdx.x;
     const unsigned int m = seglen[seg];
     const unsigned long long o = off[seg];
     if (o + 12ull + m > out_cap) return;         // k_png_frame refused the file (cannot happen within lars_png_bound)
     crc_table_fill(tab, tid, PNG_THREADS);
-    if (tid == 0) {
-        unsigned int p = 1u << 30;               // x^1
-        x2n[0] = p;
-        for (int i = 1; i < 32; ++i) x2n[i] = p = crc_multmodp(p, p);
-    }
+    if (tid == 0) crc_x2n_fill(x2n);
     const uint8_t *z = Z + seg * PNG_ZCAP;
     uint8_t *dst = out + o;
     for (unsigned int j = tid; j < m; j += PNG_THREADS) dst[8 + j] = z[j];
@@ -281,22 +218,11 @@ __global__ __launch_bounds__(PNG_THREADS) void k_png_idat(const uint8_t *__restr
         dst[4] = 'I'; dst[5] = 'D'; dst[6] = 'A'; dst[7] = 'T';
     }
     __syncthreads();
-    // CRC-32 of "IDAT" + data: crc(A B) = crc(A) x^(8 |B|) ^ crc(B) for finished CRCs, so each thread's piece is shifted by
-    // the bytes after it and the pieces XOR together
-    const unsigned int len = m + 4u;
-    const unsigned int chunk = (len + PNG_THREADS - 1) / PNG_THREADS;
-    const unsigned int lo = min(len, tid * chunk), hi = min(len, lo + chunk);
-    const char idat[4] = {'I', 'D', 'A', 'T'};
-    unsigned int crc = 0xFFFFFFFFu;
-    for (unsigned int j = lo; j < hi; ++j) crc = crc_update(tab, crc, j < 4 ? (unsigned int)(uint8_t)idat[j] : z[j - 4]);
-    crc = hi > lo ? ~crc : 0u;
-    part[tid] = crc ? crc_multmodp(crc_x2nmodp(x2n, len - hi, 3), crc) : 0u;
-    __syncthreads();
-    for (int half = PNG_THREADS / 2; half > 0; half >>= 1) {
-        if (tid < half) part[tid] ^= part[tid + half];
-        __syncthreads();
-    }
-    if (tid == 0) put_be32(dst + 8 + m, part[0]);
+    // CRC-32 of "IDAT" + data
+    const unsigned int idat = 0x54414449u;       // "IDAT", first letter in the low byte
+    const unsigned int crc = wg_crc32<PNG_THREADS>(m + 4u, [&](unsigned int j) { return j < 4 ? (idat >> (8 * j)) & 255u : (unsigned int)z[j - 4]; },
+                                                   tab, x2n, part);
+    if (tid == 0) put_be32(dst + 8 + m, crc);
 }
 
 static bool png_shape_ok(int64_t h, int64_t w, int channels)

@@ -44,6 +44,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "checksum_device.h"
 #include "codec_host.h"
 #include "inflate_device.h"
 
@@ -57,8 +58,6 @@ namespace lars {
 #define PD_TILE 2048                   // unfilter: columns per tile (a multiple of 16)
 #define PD_UNF_WAVES 16
 #define PD_AHEAD 4                     // unfilter: loads issued this many steps before their use
-#define PD_CRC_POLY 0xEDB88320u
-#define PD_ADLER_MOD 65521u
 #define PD_RESOLVE_BYTES 64            // bytes per thread of k_pd_resolve
 #define PD_WAIT_TICKS 1000000000ull    // wall-clock ticks (100 MHz) of one bounded unfilter wait: 10 s
 
@@ -300,50 +299,11 @@ __device__ __forceinline__ void pd_block(PdLds &L, const unsigned int *words, un
     __syncthreads();
 }
 
-// ---- CRC-32 pieces (as png.hip's k_png_idat) -------------------------------------------------------------------------
-__device__ inline unsigned int pd_crc_multmodp(unsigned int a, unsigned int b)
-{
-    unsigned int m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0) break;
-        }
-        m >>= 1;
-        b = (b & 1u) ? (b >> 1) ^ PD_CRC_POLY : b >> 1;
-    }
-    return p;
-}
-
-__device__ inline unsigned int pd_crc_x2nmodp(const unsigned int *x2n, unsigned long long n, unsigned int k)
-{
-    unsigned int p = 1u << 31;
-    while (n) {
-        if (n & 1) p = pd_crc_multmodp(x2n[k & 31], p);
-        n >>= 1;
-        ++k;
-    }
-    return p;
-}
-
 // one workgroup: off[i] = sum of len[0..i) over the IDAT table { offset, length } pairs
 __global__ __launch_bounds__(1024) void k_pd_chunk_scan(const long long *__restrict__ table, long long n,
                                                          unsigned long long *__restrict__ off)
 {
-    __shared__ unsigned long long part[1024];
-    const int tid = threadIdx.x;
-    const long long per = (n + 1023) / 1024, lo = min(n, tid * per), hi = min(n, lo + per);
-    unsigned long long s = 0;
-    for (long long i = lo; i < hi; ++i) s += (unsigned long long)table[2 * i + 1];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long run = 0;
-        for (int t = 0; t < 1024; ++t) { const unsigned long long v = part[t]; part[t] = run; run += v; }
-    }
-    __syncthreads();
-    unsigned long long run = part[tid];
-    for (long long i = lo; i < hi; ++i) { off[i] = run; run += (unsigned long long)table[2 * i + 1]; }
+    wg_scan_array<unsigned long long>(n, [&](long long i) { return table[2 * i + 1]; }, [&](long long i, unsigned long long before) { off[i] = before; });
 }
 
 #define PD_GATHER_THREADS 256
@@ -355,18 +315,10 @@ __global__ __launch_bounds__(PD_GATHER_THREADS) void k_pd_gather(const uint8_t *
 {
     __shared__ unsigned int tab[256];
     __shared__ unsigned int x2n[32];
-    __shared__ unsigned int part[PD_GATHER_THREADS];
+    __shared__ unsigned int part[PD_GATHER_THREADS / 64];
     const int tid = threadIdx.x;
-    for (int i = tid; i < 256; i += PD_GATHER_THREADS) {
-        unsigned int c = (unsigned int)i;
-        for (int k = 0; k < 8; ++k) c = (c & 1u) ? PD_CRC_POLY ^ (c >> 1) : c >> 1;
-        tab[i] = c;
-    }
-    if (tid == 0) {
-        unsigned int p = 1u << 30;               // x^1
-        x2n[0] = p;
-        for (int i = 1; i < 32; ++i) x2n[i] = p = pd_crc_multmodp(p, p);
-    }
+    crc_table_fill(tab, tid, PD_GATHER_THREADS);
+    if (tid == 0) crc_x2n_fill(x2n);
     __syncthreads();
     for (long long k = blockIdx.x; k < n; k += gridDim.x) {
         const unsigned long long src = (unsigned long long)table[2 * k];
@@ -374,24 +326,13 @@ __global__ __launch_bounds__(PD_GATHER_THREADS) void k_pd_gather(const uint8_t *
         const uint8_t *z = file + src;
         uint8_t *dst = stream + off[k];
         for (unsigned int j = tid; j < m; j += PD_GATHER_THREADS) dst[j] = z[j];
-        const unsigned int len = m + 4u;
-        const unsigned int chunk = (len + PD_GATHER_THREADS - 1) / PD_GATHER_THREADS;
-        const unsigned int lo = min(len, tid * chunk), hi = min(len, lo + chunk);
-        unsigned int crc = 0xFFFFFFFFu;
-        for (unsigned int j = lo; j < hi; ++j) crc = tab[(crc ^ (unsigned int)z[(long long)j - 4]) & 255u] ^ (crc >> 8);  // z - 4: "IDAT"
-        crc = hi > lo ? ~crc : 0u;
-        part[tid] = crc ? pd_crc_multmodp(pd_crc_x2nmodp(x2n, len - hi, 3), crc) : 0u;
-        __syncthreads();
-        for (int half = PD_GATHER_THREADS / 2; half > 0; half >>= 1) {
-            if (tid < half) part[tid] ^= part[tid + half];
-            __syncthreads();
-        }
+        const unsigned int crc = wg_crc32<PD_GATHER_THREADS>(m + 4u, [&](unsigned int j) { return (unsigned int)z[(long long)j - 4]; },   // z - 4: "IDAT"
+                                                             tab, x2n, part);
         if (tid == 0) {
             const uint8_t *c = z + m;
             const unsigned int want = (unsigned int)c[0] << 24 | (unsigned int)c[1] << 16 | (unsigned int)c[2] << 8 | c[3];
-            if (part[0] != want) pd_fail(ctl, LARS_PNGD_CRC, (int)min(k, 0x7FFFFFFFll));
+            if (crc != want) pd_fail(ctl, LARS_PNGD_CRC, (int)min(k, 0x7FFFFFFFll));
         }
-        __syncthreads();
     }
 }
 
@@ -420,25 +361,9 @@ __global__ __launch_bounds__(PD_MARK_THREADS) void k_pd_mark(const unsigned int 
 // one workgroup: exclusive scan of n counts in place; ctl->ncand = min(total, cap)
 __global__ __launch_bounds__(1024) void k_pd_scan_u32(unsigned int *__restrict__ v, long long n, unsigned int cap, PdCtl *ctl)
 {
-    __shared__ unsigned long long part[1024];
-    const int tid = threadIdx.x;
-    const long long per = (n + 1023) / 1024, lo = min(n, tid * per), hi = min(n, lo + per);
-    unsigned long long s = 0;
-    for (long long i = lo; i < hi; ++i) s += v[i];
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long run = 0;
-        for (int t = 0; t < 1024; ++t) { const unsigned long long x = part[t]; part[t] = run; run += x; }
-        ctl->ncand = (unsigned int)min(run, (unsigned long long)cap);
-    }
-    __syncthreads();
-    unsigned long long run = part[tid];
-    for (long long i = lo; i < hi; ++i) {
-        const unsigned int x = v[i];
-        v[i] = (unsigned int)min(run, 0xFFFFFFFFull);
-        run += x;
-    }
+    const unsigned long long total = wg_scan_array<unsigned long long>(
+        n, [&](long long i) { return v[i]; }, [&](long long i, unsigned long long before) { v[i] = (unsigned int)min(before, 0xFFFFFFFFull); });
+    if (threadIdx.x == 0) ctl->ncand = (unsigned int)min(total, (unsigned long long)cap);
 }
 
 __global__ __launch_bounds__(PD_MARK_THREADS) void k_pd_compact(const unsigned long long *__restrict__ masks,
@@ -605,59 +530,56 @@ __global__ __launch_bounds__(256) void k_pd_jump(int *__restrict__ src, long lon
     if (__ballot(ch) && (threadIdx.x & 63) == 0) ctl->changed[round] = 1u;
 }
 
-// bytes from their sources (a source is always a literal), into rows padded to rbp bytes and a filter byte per row;
-// Adler-32 partial sums
+// byte i of the stream from its source (a source is always a literal)
+__device__ inline unsigned int pd_source_byte(const uint8_t *__restrict__ lit, const int *__restrict__ src, long long i, PdCtl *ctl)
+{
+    const int s = src[i];
+    if (s == (int)i) return lit[i];
+    if (s >= 0 && (long long)s < i) return lit[s];
+    pd_fail(ctl, LARS_PNGD_INTERNAL, 3);
+    return 0u;
+}
+
+// a workgroup's Adler-32 partial sums (of 256 threads) -> parts[2 * blockIdx.x ..]
+__device__ inline void pd_adler_parts(unsigned long long s1, unsigned long long s2, unsigned long long *s_w, unsigned long long *__restrict__ parts)
+{
+    adler_wg<256>(s1, s2, s_w);
+    if (threadIdx.x == 0) { parts[2 * blockIdx.x] = s1; parts[2 * blockIdx.x + 1] = s2; }
+}
+
+// bytes from their sources, into rows padded to rbp bytes and a filter byte per row; Adler-32 partial sums
 __global__ __launch_bounds__(256) void k_pd_resolve(const uint8_t *__restrict__ lit, const int *__restrict__ src, long long n,
                                                     unsigned int rb, unsigned int rbp, uint8_t *__restrict__ fpad,
                                                     uint8_t *__restrict__ ftype, unsigned long long *__restrict__ parts, PdCtl *ctl)
 {
-    __shared__ unsigned long long r1[256], r2[256];
+    __shared__ unsigned long long s_w[8];
     if (pd_failed(ctl)) return;
     const long long lo = ((long long)blockIdx.x * 256 + threadIdx.x) * PD_RESOLVE_BYTES, hi = min(n, lo + PD_RESOLVE_BYTES);
     unsigned long long s1 = 0, s2 = 0;
     for (long long i = lo; i < hi; ++i) {
-        const int s = src[i];
-        unsigned int v;
-        if (s == (int)i) v = lit[i];
-        else if (s >= 0 && (long long)s < i) v = lit[s];
-        else { pd_fail(ctl, LARS_PNGD_INTERNAL, 3); v = 0; }
+        const unsigned int v = pd_source_byte(lit, src, i, ctl);
         const unsigned int r = (unsigned int)i / (rb + 1u), col = (unsigned int)i - r * (rb + 1u);
         if (col == 0) ftype[r] = (uint8_t)v;
         else fpad[(unsigned long long)r * rbp + col - 1] = (uint8_t)v;
         s1 += v;
         s2 += (unsigned long long)(n - i) * v;
     }
-    r1[threadIdx.x] = s1 % PD_ADLER_MOD;
-    r2[threadIdx.x] = s2 % PD_ADLER_MOD;
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {
-        if (threadIdx.x < half) { r1[threadIdx.x] += r1[threadIdx.x + half]; r2[threadIdx.x] += r2[threadIdx.x + half]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { parts[2 * blockIdx.x] = r1[0] % PD_ADLER_MOD; parts[2 * blockIdx.x + 1] = r2[0] % PD_ADLER_MOD; }
+    pd_adler_parts(s1, s2, s_w, parts);
 }
 
-// one workgroup: Adler-32 = (n + sum (n - i) x_i) << 16 | (1 + sum x_i), mod 65521, against the trailer
+// one workgroup: the Adler-32 of the partial sums (checksum_device.h) against the trailer
 __global__ __launch_bounds__(256) void k_pd_adler(const unsigned long long *__restrict__ parts, long long nparts, long long n,
                                                   const uint8_t *__restrict__ stream, PdCtl *ctl)
 {
-    __shared__ unsigned long long r1[256], r2[256];
+    __shared__ unsigned long long s_w[8];
     if (pd_failed(ctl)) return;
     unsigned long long s1 = 0, s2 = 0;
     for (long long i = threadIdx.x; i < nparts; i += 256) { s1 += parts[2 * i]; s2 += parts[2 * i + 1]; }
-    r1[threadIdx.x] = s1 % PD_ADLER_MOD;
-    r2[threadIdx.x] = s2 % PD_ADLER_MOD;
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {
-        if (threadIdx.x < half) { r1[threadIdx.x] += r1[threadIdx.x + half]; r2[threadIdx.x] += r2[threadIdx.x + half]; }
-        __syncthreads();
-    }
+    adler_wg<256>(s1, s2, s_w);
     if (threadIdx.x == 0 && ctl->total == (unsigned long long)n) {        // more data than the image: not checked
-        const unsigned int a = (unsigned int)((1 + r1[0]) % PD_ADLER_MOD);
-        const unsigned int b = (unsigned int)(((unsigned long long)n % PD_ADLER_MOD + r2[0]) % PD_ADLER_MOD);
         const uint8_t *t = stream + ctl->adler_byte;
         const unsigned int want = (unsigned int)t[0] << 24 | (unsigned int)t[1] << 16 | (unsigned int)t[2] << 8 | t[3];
-        if ((b << 16 | a) != want) pd_fail(ctl, LARS_PNGD_ADLER, 0);
+        if (adler_value(s1, s2, (unsigned long long)n) != want) pd_fail(ctl, LARS_PNGD_ADLER, 0);
     }
 }
 
@@ -689,9 +611,11 @@ __device__ __forceinline__ uint4 pd_shfl_up(const uint4 &v)
 
 // one workgroup of PD_UNF_WAVES waves: the skewed wavefront (see the top of the file), 16 bytes per lane and step.  Rows are
 // padded to rbp (a multiple of 16) bytes in fpad and opad; lane i of a wave reconstructs chunk t - i of its row at step t.
-__global__ __launch_bounds__(64 * PD_UNF_WAVES) void k_pd_unfilter(const uint8_t *__restrict__ fpad, const uint8_t *__restrict__ ftype,
-                                                                   long long h, long long rbp, int bpp, uint8_t *__restrict__ opad,
-                                                                   PdCtl *ctl)
+// HIST holds the last bpp bytes of the row and of the row above: 32 bits reach bpp 4, 64 bits bpp 8 (16-bit RGBA).
+// filter_detail(row): what a bad filter byte reports.  The bounded wait is workgroup-scope; nothing waits across workgroups.
+template <typename HIST, typename Detail>
+__device__ __forceinline__ void pd_unfilter_rows(const uint8_t *__restrict__ fpad, const uint8_t *__restrict__ ftype, long long h,
+                                                 long long rbp, int bpp, uint8_t *__restrict__ opad, PdCtl *ctl, Detail filter_detail)
 {
     __shared__ unsigned int prog[PD_UNF_WAVES];
     __shared__ int abort_;
@@ -706,188 +630,11 @@ __global__ __launch_bounds__(64 * PD_UNF_WAVES) void k_pd_unfilter(const uint8_t
         const long long row = g * 64 + lane;
         const bool active = row < h;
         int f = active ? ftype[row] : 0;
-        if (f > 4) { pd_fail(ctl, LARS_PNGD_FILTER, (int)min(row, 0x7FFFFFFFll)); f = 0; }
+        if (f > 4) { pd_fail(ctl, LARS_PNGD_FILTER, filter_detail(row)); f = 0; }
         const uint4 *xrow = reinterpret_cast<const uint4 *>(fpad + row * rbp);
         uint4 *orow = reinterpret_cast<uint4 *>(opad + row * rbp);
         const uint4 *uprow = reinterpret_cast<const uint4 *>(opad + (row - 1) * rbp);
-        unsigned int ha = 0, hc = 0;
-        uint4 prev = make_uint4(0u, 0u, 0u, 0u);
-        for (long long cb = 0; cb < ncb; ++cb) {
-            if (g > 0) {
-                // the tile above: group g - 1, tile cb, finished by wave (g - 1) % nwaves
-                const unsigned int want = (unsigned int)((g - 1) * ncb + cb + 1);
-                const unsigned int *p = &prog[(g - 1) % nwaves];
-                const unsigned long long t0 = wall_clock64();
-                while (__hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < want) {
-                    if (__hip_atomic_load(&abort_, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) return;
-                    if (wall_clock64() - t0 > PD_WAIT_TICKS) {
-                        if (lane == 0) {
-                            pd_fail(ctl, LARS_PNGD_INTERNAL, 4);
-                            __hip_atomic_store(&abort_, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
-                        return;
-                    }
-                    __builtin_amdgcn_s_sleep(2);
-                }
-            }
-            const long long k0 = cb * tchunks, k1 = min(nchunk, k0 + tchunks);
-            const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
-            // loads run PD_AHEAD steps ahead of their use (a ring of registers, indexed by constants after unrolling)
-            uint4 xr[PD_AHEAD], ur[PD_AHEAD];
-#pragma unroll
-            for (int q = 0; q < PD_AHEAD; ++q) {
-                const long long kq = k0 + q - lane;
-                const bool vq = active && kq >= k0 && kq < k1;
-                xr[q] = vq ? xrow[kq] : zero;
-                ur[q] = (vq && lane == 0 && row > 0) ? uprow[kq] : zero;
-            }
-            const long long steps = (k1 - k0) + 63;
-            for (long long t = 0; t < steps; t += PD_AHEAD) {
-#pragma unroll
-                for (int q = 0; q < PD_AHEAD; ++q) {
-                    const long long k = k0 + t + q - lane;
-                    const bool v = active && k >= k0 && k < k1;
-                    const uint4 x = xr[q], u0 = ur[q];
-                    const long long kf = k + PD_AHEAD;
-                    const bool vf = active && kf >= k0 && kf < k1;
-                    xr[q] = vf ? xrow[kf] : zero;
-                    ur[q] = (vf && lane == 0 && row > 0) ? uprow[kf] : zero;
-                    const uint4 fromleft = pd_shfl_up(prev);   // lane - 1's chunk k of the row above, made one step earlier
-                    const uint4 up = lane == 0 ? u0 : fromleft;
-                    if (v) {
-                        unsigned int o[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                        for (int j = 0; j < 16; ++j) {
-                            const unsigned int bb = pd_byte(up, j);
-                            const unsigned int a = (ha >> sh) & 255u, c = (hc >> sh) & 255u;
-                            const unsigned int r = pd_recon(f, pd_byte(x, j), a, bb, c);
-                            ha = (ha << 8) | r;
-                            hc = (hc << 8) | bb;
-                            o[j >> 2] |= r << (8 * (j & 3));
-                        }
-                        prev = make_uint4(o[0], o[1], o[2], o[3]);
-                        orow[k] = prev;
-                    }
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            if (lane == 0) __hip_atomic_store(&prog[wave], (unsigned int)(g * ncb + cb + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-    }
-}
-
-// padded rows -> [h][rb]
-__global__ __launch_bounds__(256) void k_pd_rows(const uint8_t *__restrict__ opad, long long h, long long rb, long long rbp,
-                                                 uint8_t *__restrict__ out, const PdCtl *ctl)
-{
-    if (pd_failed(ctl)) return;
-    const long long n = h * rb;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const long long r = i / rb;
-        out[i] = opad[r * rbp + (i - r * rb)];
-    }
-}
-
-// ---- the extended decoder: rows per pass, any bit depth --------------------------------------------------------------
-// What the kernels after the stream know of a file, passed by value.  Every pass has its own block of 16-byte-padded rows
-// in fpad / opad (pad_base) and its own stretch of filter bytes (row_base).
-struct PdxPass {
-    unsigned int off, rb, rbp, ph;      // first stream byte, row bytes, padded row bytes, rows
-    unsigned int x0, y0, ldx, ldy;      // first column and row, log2 of the column and row step
-    unsigned long long pad_base, row_base;
-    int index;                          // Adam7 pass number 1..7, 0 without interlace
-    unsigned int pw;                    // columns
-};
-#define PDX_SUB 0                       // 1, 2, 4 bits: one byte per sample, times mult
-#define PDX_BYTES 1                     // 8 bits: the pixel's bytes
-#define PDX_GRAY16 2                    // native-endian uint16
-#define PDX_HIGH 3                      // 16 bits: the high byte of every sample
-#define PDX_LA16 4                      // 16-bit LA: L, L, L, A of the high bytes
-struct PdxDev {
-    int npass, interlace, depth, inc;   // inc: samples per pixel in the file
-    int kind, mult, bpp, pad_;
-    int slot[8];                        // Adam7 pass number -> position in p, -1 for an empty pass
-    PdxPass p[7];
-};
-
-// k_pd_resolve with rows of a length per pass: each thread finds the pass, row and column of its first byte once and
-// steps from there
-__global__ __launch_bounds__(256) void k_pdx_resolve(const uint8_t *__restrict__ lit, const int *__restrict__ src, long long n,
-                                                     const PdxDev D, uint8_t *__restrict__ fpad, uint8_t *__restrict__ ftype,
-                                                     unsigned long long *__restrict__ parts, PdCtl *ctl)
-{
-    __shared__ unsigned long long r1[256], r2[256];
-    if (pd_failed(ctl)) return;
-    const long long lo = ((long long)blockIdx.x * 256 + threadIdx.x) * PD_RESOLVE_BYTES, hi = min(n, lo + PD_RESOLVE_BYTES);
-    unsigned long long s1 = 0, s2 = 0;
-    if (lo < hi) {
-        int p = 0;
-        while (p + 1 < D.npass && (unsigned int)lo >= D.p[p + 1].off) ++p;
-        PdxPass P = D.p[p];
-        long long end = p + 1 < D.npass ? (long long)D.p[p + 1].off : n;
-        unsigned int r = ((unsigned int)lo - P.off) / (P.rb + 1u), col = ((unsigned int)lo - P.off) - r * (P.rb + 1u);
-        for (long long i = lo; i < hi; ++i) {
-            if (i == end) {
-                ++p;
-                if (p >= D.npass) break;                 // cannot happen: the passes cover [0, n)
-                P = D.p[p];
-                end = p + 1 < D.npass ? (long long)D.p[p + 1].off : n;
-                r = 0; col = 0;
-            }
-            const int s = src[i];
-            unsigned int v;
-            if (s == (int)i) v = lit[i];
-            else if (s >= 0 && (long long)s < i) v = lit[s];
-            else { pd_fail(ctl, LARS_PNGD_INTERNAL, 3); v = 0; }
-            if (r < P.ph) {
-                if (col == 0) ftype[P.row_base + r] = (uint8_t)v;
-                else fpad[P.pad_base + (unsigned long long)r * P.rbp + col - 1] = (uint8_t)v;
-            }
-            if (++col > P.rb) { col = 0; ++r; }
-            s1 += v;
-            s2 += (unsigned long long)(n - i) * v;
-        }
-    }
-    r1[threadIdx.x] = s1 % PD_ADLER_MOD;
-    r2[threadIdx.x] = s2 % PD_ADLER_MOD;
-    __syncthreads();
-    for (int half = 128; half > 0; half >>= 1) {
-        if (threadIdx.x < half) { r1[threadIdx.x] += r1[threadIdx.x + half]; r2[threadIdx.x] += r2[threadIdx.x + half]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { parts[2 * blockIdx.x] = r1[0] % PD_ADLER_MOD; parts[2 * blockIdx.x + 1] = r2[0] % PD_ADLER_MOD; }
-}
-
-// one workgroup per pass: the passes are independent pictures, each unfiltered by k_pd_unfilter's skewed wavefront.  The
-// history of the last bpp bytes of the row and of the row above takes 64 bits here, which reaches bpp 8 (16-bit RGBA); the
-// kernel stands apart from k_pd_unfilter so that the 8-bit decoder compiles as it did.  Waves a small pass has no 64-row
-// group for do nothing; the bounded wait is workgroup-scope as there, and nothing waits across workgroups.  A bad filter
-// byte reports pass << 24 | row within the pass.
-__global__ __launch_bounds__(64 * PD_UNF_WAVES) void k_pdx_unfilter(const uint8_t *__restrict__ fpad, const uint8_t *__restrict__ ftype,
-                                                                    const PdxDev D, uint8_t *__restrict__ opad, PdCtl *ctl)
-{
-    __shared__ unsigned int prog[PD_UNF_WAVES];
-    __shared__ int abort_;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x / 64, nwaves = blockDim.x / 64;
-    if (threadIdx.x < PD_UNF_WAVES) prog[threadIdx.x] = 0;
-    if (threadIdx.x == 0) abort_ = 0;
-    __syncthreads();
-    if (pd_failed(ctl) || (int)blockIdx.x >= D.npass) return;
-    const PdxPass P = D.p[blockIdx.x];
-    const long long h = P.ph, rbp = P.rbp;
-    const int bpp = D.bpp;
-    fpad += P.pad_base; opad += P.pad_base; ftype += P.row_base;
-    const long long nchunk = rbp / 16, ngroups = (h + 63) / 64, tchunks = PD_TILE / 16, ncb = (nchunk + tchunks - 1) / tchunks;
-    const int sh = 8 * (bpp - 1);
-    for (long long g = wave; g < ngroups; g += nwaves) {
-        const long long row = g * 64 + lane;
-        const bool active = row < h;
-        int f = active ? ftype[row] : 0;
-        if (f > 4) { pd_fail(ctl, LARS_PNGD_FILTER, P.index << 24 | (int)min(row, 0xFFFFFFll)); f = 0; }
-        const uint4 *xrow = reinterpret_cast<const uint4 *>(fpad + row * rbp);
-        uint4 *orow = reinterpret_cast<uint4 *>(opad + row * rbp);
-        const uint4 *uprow = reinterpret_cast<const uint4 *>(opad + (row - 1) * rbp);
-        unsigned long long ha = 0, hc = 0;
+        HIST ha = 0, hc = 0;
         uint4 prev = make_uint4(0u, 0u, 0u, 0u);
         for (long long cb = 0; cb < ncb; ++cb) {
             if (g > 0) {
@@ -951,6 +698,95 @@ __global__ __launch_bounds__(64 * PD_UNF_WAVES) void k_pdx_unfilter(const uint8_
             if (lane == 0) __hip_atomic_store(&prog[wave], (unsigned int)(g * ncb + cb + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
+}
+
+__global__ __launch_bounds__(64 * PD_UNF_WAVES) void k_pd_unfilter(const uint8_t *__restrict__ fpad, const uint8_t *__restrict__ ftype,
+                                                                   long long h, long long rbp, int bpp, uint8_t *__restrict__ opad,
+                                                                   PdCtl *ctl)
+{
+    pd_unfilter_rows<unsigned int>(fpad, ftype, h, rbp, bpp, opad, ctl, [](long long row) { return (int)min(row, 0x7FFFFFFFll); });
+}
+
+// padded rows -> [h][rb]
+__global__ __launch_bounds__(256) void k_pd_rows(const uint8_t *__restrict__ opad, long long h, long long rb, long long rbp,
+                                                 uint8_t *__restrict__ out, const PdCtl *ctl)
+{
+    if (pd_failed(ctl)) return;
+    const long long n = h * rb;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / rb;
+        out[i] = opad[r * rbp + (i - r * rb)];
+    }
+}
+
+// ---- the extended decoder: rows per pass, any bit depth --------------------------------------------------------------
+// What the kernels after the stream know of a file, passed by value.  Every pass has its own block of 16-byte-padded rows
+// in fpad / opad (pad_base) and its own stretch of filter bytes (row_base).
+struct PdxPass {
+    unsigned int off, rb, rbp, ph;      // first stream byte, row bytes, padded row bytes, rows
+    unsigned int x0, y0, ldx, ldy;      // first column and row, log2 of the column and row step
+    unsigned long long pad_base, row_base;
+    int index;                          // Adam7 pass number 1..7, 0 without interlace
+    unsigned int pw;                    // columns
+};
+#define PDX_SUB 0                       // 1, 2, 4 bits: one byte per sample, times mult
+#define PDX_BYTES 1                     // 8 bits: the pixel's bytes
+#define PDX_GRAY16 2                    // native-endian uint16
+#define PDX_HIGH 3                      // 16 bits: the high byte of every sample
+#define PDX_LA16 4                      // 16-bit LA: L, L, L, A of the high bytes
+struct PdxDev {
+    int npass, interlace, depth, inc;   // inc: samples per pixel in the file
+    int kind, mult, bpp, pad_;
+    int slot[8];                        // Adam7 pass number -> position in p, -1 for an empty pass
+    PdxPass p[7];
+};
+
+// k_pd_resolve with rows of a length per pass: each thread finds the pass, row and column of its first byte once and
+// steps from there
+__global__ __launch_bounds__(256) void k_pdx_resolve(const uint8_t *__restrict__ lit, const int *__restrict__ src, long long n,
+                                                     const PdxDev D, uint8_t *__restrict__ fpad, uint8_t *__restrict__ ftype,
+                                                     unsigned long long *__restrict__ parts, PdCtl *ctl)
+{
+    __shared__ unsigned long long s_w[8];
+    if (pd_failed(ctl)) return;
+    const long long lo = ((long long)blockIdx.x * 256 + threadIdx.x) * PD_RESOLVE_BYTES, hi = min(n, lo + PD_RESOLVE_BYTES);
+    unsigned long long s1 = 0, s2 = 0;
+    if (lo < hi) {
+        int p = 0;
+        while (p + 1 < D.npass && (unsigned int)lo >= D.p[p + 1].off) ++p;
+        PdxPass P = D.p[p];
+        long long end = p + 1 < D.npass ? (long long)D.p[p + 1].off : n;
+        unsigned int r = ((unsigned int)lo - P.off) / (P.rb + 1u), col = ((unsigned int)lo - P.off) - r * (P.rb + 1u);
+        for (long long i = lo; i < hi; ++i) {
+            if (i == end) {
+                ++p;
+                if (p >= D.npass) break;                 // cannot happen: the passes cover [0, n)
+                P = D.p[p];
+                end = p + 1 < D.npass ? (long long)D.p[p + 1].off : n;
+                r = 0; col = 0;
+            }
+            const unsigned int v = pd_source_byte(lit, src, i, ctl);
+            if (r < P.ph) {
+                if (col == 0) ftype[P.row_base + r] = (uint8_t)v;
+                else fpad[P.pad_base + (unsigned long long)r * P.rbp + col - 1] = (uint8_t)v;
+            }
+            if (++col > P.rb) { col = 0; ++r; }
+            s1 += v;
+            s2 += (unsigned long long)(n - i) * v;
+        }
+    }
+    pd_adler_parts(s1, s2, s_w, parts);
+}
+
+// one workgroup per pass: the passes are independent pictures, each unfiltered by pd_unfilter_rows with a 64-bit history.  Waves
+// a small pass has no 64-row group for do nothing.  A bad filter byte reports pass << 24 | row within the pass.
+__global__ __launch_bounds__(64 * PD_UNF_WAVES) void k_pdx_unfilter(const uint8_t *__restrict__ fpad, const uint8_t *__restrict__ ftype,
+                                                                    const PdxDev D, uint8_t *__restrict__ opad, PdCtl *ctl)
+{
+    if ((int)blockIdx.x >= D.npass) return;                // uniform: the whole workgroup leaves
+    const PdxPass P = D.p[blockIdx.x];
+    pd_unfilter_rows<unsigned long long>(fpad + P.pad_base, ftype + P.row_base, (long long)P.ph, (long long)P.rbp, D.bpp, opad + P.pad_base, ctl,
+                                         [&](long long row) { return P.index << 24 | (int)min(row, 0xFFFFFFll); });
 }
 
 // unfiltered pass rows -> the array Pillow gives.  One thread per output pixel, a workgroup along an output row, so the

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "checksum_device.h"
 #include "codec_host.h"
 #include "common.h"
 #include "inflate_device.h"
@@ -33,7 +34,6 @@ constexpr int TD_CLEAR = 256, TD_EOI = 257, TD_FIRST = 258;
 constexpr int TD_NONE = 0, TD_LZW = 1, TD_DEFLATE = 2;   // TdGeom.codec
 constexpr int TD_ZBATCH = 256;     // Deflate: records one lane decodes between two expansions by the wave
 constexpr int TD_ZWIN = 2048;      // Deflate: bytes of the stream the wave stages in LDS for one batch (a record takes at most 48 bits)
-constexpr unsigned int TD_ADLER = 65521u;
 
 struct TdGeom {
     long long nchunks, full;       // bytes of a whole strip / tile = the pitch of the chunk buffers
@@ -54,7 +54,6 @@ __device__ inline unsigned long long td_bits_before(unsigned long long i)
                              d = i < 1790 ? 0 : i - 1790;
     return 9 * a + 10 * b + 11 * c + 12 * d;
 }
-__device__ inline int td_width(unsigned long long i) { return i <= 253 ? 9 : i <= 765 ? 10 : i <= 1789 ? 11 : 12; }
 
 // stored rows of chunk k and the bytes the directory says it holds
 __device__ __host__ inline long long td_want(const TdGeom &g, long long k)
@@ -94,7 +93,7 @@ __global__ __launch_bounds__(64) void k_td_lzw(const uint8_t *__restrict__ file,
         // ---- 64 codes by closed-form offsets
         const unsigned long long i = seg_i + lane;
         const unsigned long long at = seg_bit + td_bits_before(i);
-        const int width = td_width(i);
+        const int width = tiff_lzw_width(i);
         const bool avail = at + width <= nbits;
         int code = 0;
         if (avail) {
@@ -191,7 +190,7 @@ __global__ __launch_bounds__(64) void k_td_lzw(const uint8_t *__restrict__ file,
         const int tcode = __shfl(code, n_term);
         const int tavail = __shfl((int)avail, n_term);
         if (!tavail || tcode == TD_EOI) break;                                // out of input: what was decoded stands
-        seg_bit += td_bits_before(seg_i) + td_width(seg_i);                   // past the Clear
+        seg_bit += td_bits_before(seg_i) + tiff_lzw_width(seg_i);                   // past the Clear
         seg_i = 0;
     }
     if (lane == 0) produced[k] = (int)op, bad[k] = err;
@@ -236,7 +235,7 @@ __global__ __launch_bounds__(64) void k_td_inflate(const uint8_t *__restrict__ f
     uint8_t *dst = bufs + k * g.full;
     const unsigned int want = (unsigned int)want64;
     const unsigned long long nbytes = (unsigned long long)cnt, nbits = nbytes * 8;
-    unsigned long long s1 = 0, s2 = 0;             // this lane's sum x_i and sum i x_i, below TD_ADLER between batches
+    unsigned long long s1 = 0, s2 = 0;             // this lane's sum x_i and sum i x_i, below ADLER_MOD between batches
     unsigned long long pos = 16;
     unsigned int op = 0;                           // bytes written
     int status = 0;
@@ -265,7 +264,7 @@ __global__ __launch_bounds__(64) void k_td_inflate(const uint8_t *__restrict__ f
                 dst[i] = (uint8_t)v;
                 s1 += v; s2 += (unsigned long long)i * v;
             }
-            s1 %= TD_ADLER; s2 %= TD_ADLER;
+            s1 %= ADLER_MOD; s2 %= ADLER_MOD;
             op += take;
             __syncthreads();
             if (there > take) { status = 2; break; }                      // a stored byte that is there and has no room
@@ -348,7 +347,7 @@ __global__ __launch_bounds__(64) void k_td_inflate(const uint8_t *__restrict__ f
                             s1 += v; s2 += (unsigned long long)i * v;
                         }
                     }
-                    s1 %= TD_ADLER; s2 %= TD_ADLER;
+                    s1 %= ADLER_MOD; s2 %= ADLER_MOD;
                     op = Z.out;
                 }
                 pos = Z.pos;
@@ -364,10 +363,10 @@ __global__ __launch_bounds__(64) void k_td_inflate(const uint8_t *__restrict__ f
     if (ended && status == 0) {
         const unsigned long long p = (pos + 7) >> 3;
         unsigned int a1 = (unsigned int)s1, a2 = (unsigned int)s2;
-        for (int dlt = 32; dlt > 0; dlt >>= 1) a1 += __shfl_xor(a1, dlt), a2 += __shfl_xor(a2, dlt);   // 64 values below 65521
+        for (int dlt = 32; dlt > 0; dlt >>= 1) a1 += __shfl_xor(a1, dlt), a2 += __shfl_xor(a2, dlt);   // 64 values below ADLER_MOD
         if (p + 4 <= nbytes) {
-            const unsigned long long n = op % TD_ADLER, t1 = a1 % TD_ADLER, t2 = a2 % TD_ADLER;
-            const unsigned int a = (unsigned int)((1 + t1) % TD_ADLER), b = (unsigned int)((n + n * t1 + TD_ADLER - t2) % TD_ADLER);
+            const unsigned long long n = op % ADLER_MOD, t1 = a1 % ADLER_MOD, t2 = a2 % ADLER_MOD;
+            const unsigned int a = (unsigned int)((1 + t1) % ADLER_MOD), b = (unsigned int)((n + n * t1 + ADLER_MOD - t2) % ADLER_MOD);
             const unsigned int stored = (unsigned int)src[p] << 24 | (unsigned int)src[p + 1] << 16 | (unsigned int)src[p + 2] << 8 | src[p + 3];
             if ((b << 16 | a) != stored) status = 1;
         }

@@ -27,6 +27,7 @@
 // the n bytes, big-endian, ends the stream.  The stream is a function of the strip's bytes alone.
 #include <algorithm>
 
+#include "checksum_device.h"
 #include "codec_host.h"
 #include "common.h"
 #include "deflate_device.h"
@@ -60,7 +61,6 @@ __host__ __device__ inline long long te_strip_cap(long long n)
     return bytes + (bytes & 1);
 }
 
-__device__ inline int te_width(int i) { return i <= 253 ? 9 : i <= 765 ? 10 : i <= 1789 ? 11 : 12; }
 __device__ inline unsigned int te_hash(unsigned int key) { return (key * 2654435761u) >> 19; }      // 13 bits
 
 // byte B of the picture as the file stores it: the sample's byte, or with the predictor the byte of the sample minus the
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(64) void k_te_lzw(const uint8_t *__restrict__ img, 
     int nbits = 0, i = 0, nxt = TE_FIRST, w = -1;
     bool over = false;
     auto emit = [&](int code) {
-        const int width = te_width(i);
+        const int width = tiff_lzw_width(i);
         acc = (acc << width) | (unsigned int)code;
         nbits += width;                                   // <= 7 + 12; 7 + 12 + 9 for EndOfInformation behind the last Clear
         while (nbits >= 8) {
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(TE_FRAME_THREADS) void k_te_frame(TeGeom g, int com
                                                               unsigned long long *__restrict__ off, uint8_t *__restrict__ out,
                                                               unsigned long long out_cap, long long *out_len, int *status)
 {
-    __shared__ unsigned long long sums[TE_FRAME_THREADS];
+    __shared__ unsigned long long s_w[TE_FRAME_THREADS / 64];
     const int tid = threadIdx.x;
     if (status[0]) {                                      // uniform: nothing has written status since k_te_lzw ended
         if (tid == 0) *out_len = 0;
@@ -218,19 +218,13 @@ __global__ __launch_bounds__(TE_FRAME_THREADS) void k_te_frame(TeGeom g, int com
     const long long lo = min(g.nstrips, tid * per), hi = min(g.nstrips, lo + per);
     unsigned long long s = 0;
     for (long long k = lo; k < hi; ++k) s += (unsigned long long)zlen[k] + (zlen[k] & 1u);
-    sums[tid] = s;
-    __syncthreads();
-    for (int d = 1; d < TE_FRAME_THREADS; d <<= 1) {      // inclusive scan
-        const unsigned long long v = tid >= d ? sums[tid - d] : 0ull;
-        __syncthreads();
-        sums[tid] += v;
-        __syncthreads();
-    }
+    unsigned long long strips;                            // the bytes of all strips
+    const unsigned long long before = wg_exscan<TE_FRAME_THREADS>(s, s_w, &strips);
     const unsigned long long n = (unsigned long long)g.nstrips;
     const int c = g.spp;
     const int extra = c > 3 ? c - 3 : (c == 2 ? 1 : 0);
     const int nent = 11 + (g.predictor ? 1 : 0) + (extra ? 1 : 0);
-    const unsigned long long ifd_at = 8ull + sums[TE_FRAME_THREADS - 1];
+    const unsigned long long ifd_at = 8ull + strips;
     const unsigned long long over_at = ifd_at + 2ull + 12ull * nent + 4ull;
     const unsigned long long bits_at = over_at;                                   // BitsPerSample, c >= 3
     const unsigned long long offs_at = bits_at + (c >= 3 ? 2ull * c : 0ull);      // StripOffsets, n > 1
@@ -238,7 +232,7 @@ __global__ __launch_bounds__(TE_FRAME_THREADS) void k_te_frame(TeGeom g, int com
     const unsigned long long fmt_at = cnts_at + (n > 1 ? 4ull * n : 0ull);        // SampleFormat, c >= 3
     const unsigned long long file = fmt_at + (c >= 3 ? 2ull * c : 0ull);
     const bool too_large = file >= (1ull << 32), no_space = !too_large && file > out_cap;
-    unsigned long long o = 8ull + sums[tid] - s;
+    unsigned long long o = 8ull + before;
     for (long long k = lo; k < hi; ++k) {
         off[k] = o;
         if (!too_large && !no_space && n > 1) {
@@ -361,14 +355,14 @@ __global__ __launch_bounds__(DLZ_THREADS) void k_tz_deflate_lz(const uint8_t *__
 
 // One workgroup per strip: where each part starts within the strip's stream (an exclusive scan of the parts' lengths, 256 parts
 // per round, the sum carried on), the strip's length, and the Adler-32 of the strip behind its last part.  With a_i = sum of part
-// i's bytes and b_i = sum of (n_i - j) * byte_j, both mod 65521, and r_i bytes of the strip behind part i, the checksum's halves
-// are 1 + sum a_i and n + sum (b_i + r_i a_i), reduced mod 65521 at every step: no product exceeds 65520^2 < 2^32.
+// i's bytes and b_i = sum of (n_i - j) * byte_j, both mod ADLER_MOD, and r_i bytes of the strip behind part i, the checksum's halves
+// are 1 + sum a_i and n + sum (b_i + r_i a_i) (adler_append, adler_value: checksum_device.h).
 __global__ __launch_bounds__(TZ_JOIN_THREADS) void k_tz_join(TeGeom g, long long pf, uint8_t *__restrict__ Z,
                                                             const unsigned int *__restrict__ seglen, const unsigned int *__restrict__ adl,
                                                             unsigned int *__restrict__ partoff, unsigned int *__restrict__ zlen)
 {
-    __shared__ unsigned int scan[TZ_JOIN_THREADS];
-    __shared__ unsigned long long a1[TZ_JOIN_THREADS], a2[TZ_JOIN_THREADS];
+    __shared__ unsigned int s_scan[TZ_JOIN_THREADS / 64];
+    __shared__ unsigned long long s_red[2 * TZ_JOIN_THREADS / 64];
     const int tid = threadIdx.x;
     const long long k = blockIdx.x;
     if (k >= g.nstrips) return;
@@ -378,36 +372,20 @@ __global__ __launch_bounds__(TZ_JOIN_THREADS) void k_tz_join(TeGeom g, long long
     for (long long i0 = 0; i0 < p; i0 += TZ_JOIN_THREADS) {
         const long long i = i0 + tid;
         const unsigned int len = i < p ? seglen[slot0 + i] : 0u;
-        scan[tid] = len;
-        __syncthreads();
-        for (int d = 1; d < TZ_JOIN_THREADS; d <<= 1) {   // inclusive scan
-            const unsigned int v = tid >= d ? scan[tid - d] : 0u;
-            __syncthreads();
-            scan[tid] += v;
-            __syncthreads();
-        }
+        unsigned int round;
+        const unsigned int before = wg_exscan<TZ_JOIN_THREADS>(len, s_scan, &round);
         if (i < p) {
-            partoff[slot0 + i] = carry + scan[tid] - len;
+            partoff[slot0 + i] = carry + before;
             const long long at = i * DEFLATE_SEG, ni = n - at < DEFLATE_SEG ? n - at : DEFLATE_SEG;
-            const unsigned long long after = (unsigned long long)(n - at - ni) % 65521ull;
-            A = (A + adl[2 * (slot0 + i)]) % 65521ull;
-            B = (B + adl[2 * (slot0 + i) + 1] + after * adl[2 * (slot0 + i)]) % 65521ull;
+            adler_append(A, B, adl[2 * (slot0 + i)], adl[2 * (slot0 + i) + 1], (unsigned long long)(n - at - ni));
         }
-        carry += scan[TZ_JOIN_THREADS - 1];
-        __syncthreads();
+        carry += round;
     }
-    a1[tid] = A;
-    a2[tid] = B;
-    __syncthreads();
-    for (int half = TZ_JOIN_THREADS / 2; half > 0; half >>= 1) {
-        if (tid < half) { a1[tid] = (a1[tid] + a1[tid + half]) % 65521ull; a2[tid] = (a2[tid] + a2[tid + half]) % 65521ull; }
-        __syncthreads();
-    }
+    adler_wg<TZ_JOIN_THREADS>(A, B, s_red);
     if (tid == 0) {
-        const unsigned int s1 = (unsigned int)((1ull + a1[0]) % 65521ull);
-        const unsigned int s2 = (unsigned int)(((unsigned long long)n % 65521ull + a2[0]) % 65521ull);
+        const unsigned int sum = adler_value(A, B, (unsigned long long)n);
         uint8_t *zl = Z + (slot0 + p - 1) * DEFLATE_ZCAP + seglen[slot0 + p - 1] - 4;      // the last part's length counts these four
-        zl[0] = (uint8_t)(s2 >> 8); zl[1] = (uint8_t)s2; zl[2] = (uint8_t)(s1 >> 8); zl[3] = (uint8_t)s1;
+        zl[0] = (uint8_t)(sum >> 24); zl[1] = (uint8_t)(sum >> 16); zl[2] = (uint8_t)(sum >> 8); zl[3] = (uint8_t)sum;
         zlen[k] = carry;
     }
 }

@@ -21,6 +21,7 @@
 // serve, and as the fall-back of a tile whose window missed.
 #include "common.h"
 #include "device_common.h"
+#include "wg_device.h"
 
 namespace lars {
 
@@ -104,21 +105,13 @@ __global__ __launch_bounds__(256) void k_hist_u16_hi_generic(const uint16_t *__r
 __global__ __launch_bounds__(256) void k_u16_pick(const unsigned int *__restrict__ hist, long long npix,
                                                   U16Pick *__restrict__ picks, const unsigned int *__restrict__ only = nullptr)
 {
-    __shared__ unsigned long long s_scan[256];
+    __shared__ unsigned long long s_scan[4];
     __shared__ U16Pick s_pick;
     const int tid = threadIdx.x;
     if (only && !only[blockIdx.y]) return;
     const long long slot = (long long)blockIdx.y * 3 + blockIdx.x;
     const unsigned long long c = hist[slot * 256 + tid];
-    s_scan[tid] = c;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        unsigned long long v = (tid >= off) ? s_scan[tid - off] : 0;
-        __syncthreads();
-        s_scan[tid] += v;
-        __syncthreads();
-    }
-    const unsigned long long before = s_scan[tid] - c;
+    const unsigned long long before = wg_exscan<256>(c, s_scan);
     const double nm1 = (double)(npix - 1);
     for (int k = 0; k < 2; ++k) {
         const double q = (k == 0 ? 2.0 : 98.0) / 100.0;
@@ -274,7 +267,7 @@ __global__ __launch_bounds__(1024) void k_u16_sample12(const uint16_t *__restric
 __global__ __launch_bounds__(256) void k_u16_window(const unsigned int *__restrict__ hist12, U16Win *__restrict__ win, int test_wrong)
 {
     constexpr int PER = U16_SAMPLE_BINS / 256;              // 16 bins per thread
-    __shared__ unsigned long long s_scan[256];
+    __shared__ unsigned long long s_scan[4];
     __shared__ unsigned int s_b[2][2];                     // [mark][first, last] bin of the sample histogram
     const int tid = threadIdx.x;
     const long long slot = (long long)blockIdx.y * 3 + blockIdx.x;
@@ -283,15 +276,8 @@ __global__ __launch_bounds__(256) void k_u16_window(const unsigned int *__restri
     unsigned long long local = 0;
 #pragma unroll
     for (int j = 0; j < PER; ++j) { mine[j] = h[tid * PER + j]; local += mine[j]; }
-    s_scan[tid] = local;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        unsigned long long v = (tid >= off) ? s_scan[tid - off] : 0;
-        __syncthreads();
-        s_scan[tid] += v;
-        __syncthreads();
-    }
-    const unsigned long long total = s_scan[255], before = s_scan[tid] - local;
+    unsigned long long total;
+    const unsigned long long before = wg_exscan<256>(local, s_scan, &total);
     if (tid < 4) s_b[tid >> 1][tid & 1] = (tid & 1) ? 0u : (unsigned)U16_SAMPLE_BINS;       // first = 4096, last = 0: no window
     __syncthreads();
     if (total > 0) {
@@ -442,7 +428,7 @@ __global__ __launch_bounds__(256) void k_u16_pick_win(const U16Win *__restrict__
                                                       const unsigned int *__restrict__ winhist, long long npix, unsigned int *__restrict__ flags,
                                                       uint8_t *__restrict__ blobs, double *__restrict__ pcts, int rgn_variant)
 {
-    __shared__ unsigned long long s_scan[256];
+    __shared__ unsigned long long s_scan[4];
     __shared__ double s_val[4];
     __shared__ int s_found[4];
     __shared__ double s_p[2];
@@ -468,16 +454,7 @@ __global__ __launch_bounds__(256) void k_u16_pick_win(const U16Win *__restrict__
         unsigned int mine[4];
         unsigned long long local = 0;
         for (int j = 0; j < 4; ++j) { mine[j] = h[tid * 4 + j]; local += mine[j]; }
-        __syncthreads();
-        s_scan[tid] = local;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            unsigned long long v = (tid >= off) ? s_scan[tid - off] : 0;
-            __syncthreads();
-            s_scan[tid] += v;
-            __syncthreads();
-        }
-        const unsigned long long before = below + s_scan[tid] - local;
+        const unsigned long long before = below + wg_exscan<256>(local, s_scan);
         const long long rank[2] = {lo, hi};
         for (int j2 = 0; j2 < 2; ++j2) {
             const unsigned long long r = (unsigned long long)rank[j2];
@@ -513,7 +490,7 @@ __global__ __launch_bounds__(256) void k_wb_table_u16(const unsigned int *__rest
                                                       uint8_t *__restrict__ blobs, double *__restrict__ pcts, int rgn_variant, int nslots,
                                                       const unsigned int *__restrict__ only = nullptr)
 {
-    __shared__ unsigned long long s_scan[256];
+    __shared__ unsigned long long s_scan[4];
     __shared__ double s_val[4];
     __shared__ double s_p[2];
     __shared__ unsigned int s_thr[260];
@@ -528,16 +505,7 @@ __global__ __launch_bounds__(256) void k_wb_table_u16(const unsigned int *__rest
         // scan the slot of rank r (ranks sharing a high byte rescan the same slot)
         const unsigned int *h = lohist + ((tile * 3 + c) * nslots + pk.slot[r]) * 256;
         const unsigned long long cnt = h[tid];
-        __syncthreads();
-        s_scan[tid] = cnt;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            unsigned long long v = (tid >= off) ? s_scan[tid - off] : 0;
-            __syncthreads();
-            s_scan[tid] += v;
-            __syncthreads();
-        }
-        const unsigned long long before = s_scan[tid] - cnt;
+        const unsigned long long before = wg_exscan<256>(cnt, s_scan);
         if (cnt && pk.resid[r] >= before && pk.resid[r] < before + cnt) s_val[r] = (double)(pk.target[r] * 256u + (unsigned)tid);
     }
     __syncthreads();

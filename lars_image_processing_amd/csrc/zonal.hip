@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "device_common.h"
+#include "wg_device.h"
 
 namespace lars {
 
@@ -88,22 +89,14 @@ __global__ __launch_bounds__(256) void k_zone_count(const LAB *__restrict__ labe
 __global__ __launch_bounds__(256) void k_zone_offsets(const unsigned long long *__restrict__ counts, unsigned int nzones,
                                                       unsigned long long *__restrict__ ends, unsigned long long *__restrict__ cursors)
 {
-    __shared__ unsigned long long s_cum[256];
+    __shared__ unsigned long long s_cum[4];
     const int tid = threadIdx.x;
     const unsigned int per = (nzones + 255u) / 256u;             // consecutive zones per thread
     const unsigned int z0 = 1u + (unsigned int)tid * per;
     unsigned long long local = 0;
     for (unsigned int j = 0; j < per; ++j)
         if (z0 + j <= nzones) local += counts[z0 + j];
-    s_cum[tid] = local;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const unsigned long long v = tid >= off ? s_cum[tid - off] : 0ull;
-        __syncthreads();
-        s_cum[tid] += v;
-        __syncthreads();
-    }
-    unsigned long long run = s_cum[tid] - local;
+    unsigned long long run = wg_exscan<256>(local, s_cum);
     for (unsigned int j = 0; j < per; ++j) {
         const unsigned int z = z0 + j;
         if (z > nzones) break;
@@ -167,29 +160,17 @@ __global__ __launch_bounds__(256) void k_zone_scatter(const LAB *__restrict__ la
 // A workgroup takes a zone, zones are grid-strided.  The record follows k_array_stats; the rank (n - 1) / 2 comes from a
 // radix select over KeyOf<float>'s key, eight bits a pass with the histogram in LDS, and the rank n / 2 from the count of the
 // keys up to the selected one and the smallest key above it, as k_sel_next / k_sel_finish form it.
-__device__ inline void block_sync_scan256(unsigned long long *s_cum, int tid)
-{
-    for (int off = 1; off < 256; off <<= 1) {
-        const unsigned long long v = tid >= off ? s_cum[tid - off] : 0ull;
-        __syncthreads();
-        s_cum[tid] += v;
-        __syncthreads();
-    }
-}
-
 __global__ __launch_bounds__(256) void k_zone_stats(const float *__restrict__ values, const unsigned long long *__restrict__ ends,
                                                     unsigned int nzones, float thr, int want_hist, unsigned long long split,
                                                     lars_stats *__restrict__ stats, float *__restrict__ medians)
 {
     __shared__ unsigned int s_hist[LARS_HIST_BINS];
     __shared__ HistCell<float> s_edges[LARS_HIST_CELLS];
-    __shared__ double s_sum[4], s_sumsq[4], s_mn[4], s_mx[4];
-    __shared__ unsigned long long s_above[4], s_nans[4], s_count[4];
+    __shared__ StatPartial s_part[4];
     __shared__ unsigned int s_bins[256];
-    __shared__ unsigned long long s_cum[256];
+    __shared__ unsigned long long s_w[8];                                       // the scans' and the reductions' words
     __shared__ unsigned int s_prefix;
-    __shared__ unsigned long long s_rank, s_cle;
-    __shared__ unsigned int s_next;
+    __shared__ unsigned long long s_rank;
     const int tid = threadIdx.x;
     hist_cells_init<float>(s_edges, tid);
     __syncthreads();
@@ -200,38 +181,15 @@ __global__ __launch_bounds__(256) void k_zone_stats(const float *__restrict__ va
         const float *x = values + lo;
         if (tid < LARS_HIST_BINS) s_hist[tid] = 0;
         __syncthreads();
-        double sum = 0, sumsq = 0;
-        double mn = __builtin_inf(), mx = -__builtin_inf();
-        unsigned long long above = 0, nans = 0, count = 0;
+        StatPartial p;
+        p.init();
         for (unsigned long long i = tid; i < n; i += 256) {
             const float v = x[i];
-            if (v != v) { ++nans; continue; }
-            const double d = (double)v;
-            sum += d; sumsq += d * d;
-            mn = fmin(mn, d); mx = fmax(mx, d);
-            above += (v > thr) ? 1 : 0;
-            ++count;
+            if (!p.push(v, thr)) continue;
             if (want_hist && v >= -1.0f && v <= 1.0f) atomicAdd(&s_hist[hist_bin_cell<float>(v, s_edges)], 1u);
         }
-        for (int off = 32; off >= 1; off >>= 1) {
-            sum += __shfl_xor(sum, off); sumsq += __shfl_xor(sumsq, off);
-            mn = fmin(mn, __shfl_xor(mn, off)); mx = fmax(mx, __shfl_xor(mx, off));
-            above += __shfl_xor(above, off); nans += __shfl_xor(nans, off); count += __shfl_xor(count, off);
-        }
-        if ((tid & 63) == 0) {
-            const int w = tid >> 6;
-            s_sum[w] = sum; s_sumsq[w] = sumsq; s_mn[w] = mn; s_mx[w] = mx; s_above[w] = above; s_nans[w] = nans; s_count[w] = count;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < 4; ++w) {
-                sum += s_sum[w]; sumsq += s_sumsq[w];
-                mn = fmin(mn, s_mn[w]); mx = fmax(mx, s_mx[w]);
-                above += s_above[w]; nans += s_nans[w]; count += s_count[w];
-            }
-            out->sum = sum; out->sumsq = sumsq; out->count = count + nans; out->above = above; out->nans = nans;
-            out->min = mn; out->max = mx; out->threshold = (double)thr; out->index_id = 0xFFFFFFFFu; out->reserved = 0;
-        }
+        p.block_reduce(s_part);
+        if (tid == 0) p.to_stats(out, (double)thr);
         if (tid < LARS_HIST_BINS) out->hist[tid] = want_hist ? (unsigned long long)s_hist[tid] : 0ull;
         if (n == 0) {                                                           // an empty zone: count 0 says so, the pair is never read
             if (tid < 2) medians[2 * (size_t)(z - 1) + tid] = __builtin_bit_cast(float, 0x7FC00000u);
@@ -249,12 +207,8 @@ __global__ __launch_bounds__(256) void k_zone_stats(const float *__restrict__ va
                 if (shift == 24 || (key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&s_bins[(key >> shift) & 0xFFu], 1u);
             }
             __syncthreads();
-            const unsigned long long c = s_bins[tid];
-            s_cum[tid] = c;
-            __syncthreads();
-            block_sync_scan256(s_cum, tid);
-            const unsigned long long before = s_cum[tid] - c, k = s_rank;
-            __syncthreads();
+            const unsigned long long c = s_bins[tid], k = s_rank;
+            const unsigned long long before = wg_exscan<256>(c, s_w);
             if (c && k >= before && k < before + c) {                           // exactly one thread
                 s_prefix = prefix | ((unsigned int)tid << shift);
                 s_rank = k - before;
@@ -263,27 +217,18 @@ __global__ __launch_bounds__(256) void k_zone_stats(const float *__restrict__ va
         }
         // keys up to the selected one, and the smallest key above it
         const unsigned int sel = s_prefix;
-        if (tid == 0) { s_cle = 0ull; s_next = 0xFFFFFFFFu; }
-        __syncthreads();
-        unsigned long long c_le = 0;
-        unsigned int nxt = 0xFFFFFFFFu;
+        unsigned long long c_le = 0, nxt = ~0ull;
         for (unsigned long long i = tid; i < n; i += 256) {
-            const unsigned int key = f32_key(x[i]);
+            const unsigned long long key = f32_key(x[i]);
             if (key <= sel) ++c_le;
             else nxt = key < nxt ? key : nxt;
         }
-        for (int off = 32; off >= 1; off >>= 1) {
-            c_le += __shfl_xor(c_le, off);
-            const unsigned int o = __shfl_xor(nxt, off);
-            nxt = o < nxt ? o : nxt;
-        }
-        if ((tid & 63) == 0) { atomicAdd(&s_cle, c_le); atomicMin(&s_next, nxt); }
-        __syncthreads();
+        wg_count_le_next<256>(c_le, nxt, s_w);
         if (tid == 0) {
             const unsigned long long k0 = (n - 1) / 2, k1 = n / 2;
             const float v1 = key_f32(sel);
             float v2 = v1;
-            if (k1 != k0 && k1 >= s_cle) v2 = key_f32(s_next);
+            if (k1 != k0 && k1 >= c_le) v2 = key_f32((unsigned int)nxt);   // k1 >= c_le: a key above the selected one exists
             medians[2 * (size_t)(z - 1)] = v1;
             medians[2 * (size_t)(z - 1) + 1] = v2;
         }
@@ -291,19 +236,11 @@ __global__ __launch_bounds__(256) void k_zone_stats(const float *__restrict__ va
     }
 }
 
-int grid_for_pixels(long long npix)
-{
-    long long b = (npix + 255) / 256;
-    if (b > 2048) b = 2048;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
 bool zone_args_ok(const void *zones, int zone_bytes, int64_t npix, int64_t nzones)
 {
     if (!zones || npix <= 0 || nzones < 1 || nzones > LARS_ZONES_MAX) return false;
     if (zone_bytes != 1 && zone_bytes != 2 && zone_bytes != 4) return false;
-    return (reinterpret_cast<uintptr_t>(zones) & (uintptr_t)(zone_bytes - 1)) == 0;
+    return aligned_to(zones, (uintptr_t)zone_bytes);
 }
 
 }  // namespace
@@ -321,7 +258,7 @@ extern "C" int lars_d_zone_count(const void *zones, int zone_bytes, const uint8_
     hipStream_t s = pick_stream(c, stream);
     LARS_HIP_TRY(hipMemsetAsync(counts_dev, 0, (size_t)(nzones + 1) * sizeof(uint64_t), s));
     LARS_HIP_TRY(hipMemsetAsync(bad_dev, 0, sizeof(uint64_t), s));
-    const dim3 grid(grid_for_pixels(npix)), block(256);
+    const dim3 grid(grid_1d(npix)), block(256);
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(counts_dev), *bad = reinterpret_cast<unsigned long long *>(bad_dev);
     if (zone_bytes == 1)
         hipLaunchKernelGGL((k_zone_count<uint8_t>), grid, block, 0, s, static_cast<const uint8_t *>(zones), valid, (long long)npix, (unsigned int)nzones, cnt, bad);
@@ -363,7 +300,7 @@ extern "C" int lars_d_zone_scatter(const float *const planes[3], uint32_t index_
     P.cursors = reinterpret_cast<unsigned long long *>(cursors_dev);
     hipStream_t s = pick_stream(c, stream);
     LARS_HIP_TRY(hipMemsetAsync(cursors_dev, 0, (size_t)(nzones + 1) * sizeof(uint64_t), s));
-    const dim3 grid(grid_for_pixels(npix)), block(256);
+    const dim3 grid(grid_1d(npix)), block(256);
     if (zone_bytes == 1) hipLaunchKernelGGL((k_zone_scatter<uint8_t>), grid, block, 0, s, static_cast<const uint8_t *>(zones), P);
     else if (zone_bytes == 2) hipLaunchKernelGGL((k_zone_scatter<uint16_t>), grid, block, 0, s, static_cast<const uint16_t *>(zones), P);
     else hipLaunchKernelGGL((k_zone_scatter<int32_t>), grid, block, 0, s, static_cast<const int32_t *>(zones), P);

@@ -22,6 +22,7 @@ SIGNATURES = {
     "lars_d_probe": (_I, [_I, _I, _I, _P, _P, _I64, _P]),
     "lars_d_probe_mix3": (_I, [_P, _P, _P, _P, _I64, _I, _P]),
     "lars_lab_copy": (_I, [_I, _I, _P, _P, _SZ]),
+    "lars_lab_wg_check": (_I, [_I, _P, _P, _I64, C.c_uint64, C.c_uint64, _P]),
 }
 _lib = None
 
@@ -80,3 +81,10 @@ def probe(kind, unroll, blocks, src, dst, nbytes, stream=None):
 def probe_mix3(src, d0, d1, d2, nquads, blocks=65536, stream=None):
     call("lars_d_probe_mix3", C.c_void_p(src), C.c_void_p(d0), C.c_void_p(d1), C.c_void_p(d2), int(nquads), int(blocks), stream)
 
+
+WG_EXSCAN32, WG_EXSCAN64, WG_SCAN_WIDEN, WG_SCAN_SATURATING, WG_CRC32, WG_ADLER = range(6)
+
+
+def wg_check(prim, src, dst, n, a=0, b=0, stream=None):
+    """One workgroup primitive on device buffers (include/lars_lab.h: lars_lab_wg_check)."""
+    call("lars_lab_wg_check", int(prim), C.c_void_p(src) if src else None, C.c_void_p(dst), int(n), int(a), int(b), stream)
