@@ -958,6 +958,58 @@ int lars_h_process_image_zones(const void *img, int64_t h, int64_t w, int channe
                                lars_stats *zone_stats /* [3][nzones] */, float *zone_medians /* [3][nzones][2] */,
                                int64_t *bad_labels);
 
+/* ------------------------------------------------- zones from polygons (csrc/zone_raster.hip) */
+/* The label raster of the zone stages, made on the device from plot outlines: analyze_index per plot (process-images.py:492-513)
+ * for callers who hold the outlines of their plots and no raster.
+ *
+ * The polygons.  verts is double [nverts][2], (x, y) in pixel units: x along the columns, y along the rows, pixel (row i, column j)
+ * has the centre cx = j + 0.5, cy = i + 0.5.  Ring r has the vertices ring_starts[r] .. ring_starts[r + 1] - 1 (three or more,
+ * closed implicitly; a first vertex repeated at the end makes a zero-length edge, which counts for nothing); polygon k has the
+ * rings poly_starts[k] .. poly_starts[k + 1] - 1 (one or more).  ring_starts[nrings + 1] and poly_starts[npolys + 1] are int32,
+ * start at 0, rise, and end at nverts and nrings.  The edges of all rings of a polygon are pooled: holes and parts need no other
+ * rule.  1 <= npolys <= LARS_ZONES_MAX, nverts <= LARS_ZONE_VERTS_MAX, every coordinate finite with |v| <= 1e9.
+ *
+ * The rule, in IEEE float64 with every operation rounded once.  An edge (x0, y0) - (x1, y1) with y0 == y1 crosses no row.
+ * Otherwise (xa, ya) is its end with the smaller y and (xb, yb) the other; it crosses row i iff ya <= cy < yb, at
+ *     xc = xa + ((cy - ya) * (xb - xa)) / (yb - ya)                     evaluated in exactly this order,
+ * so an edge two plots share crosses at the same xc for both, whichever way their rings run.  Pixel (i, j) is inside a polygon iff
+ * the number of its crossings of row i with xc <= cx is odd (even-odd, half-open on both axes).  Polygon k labels its pixels k + 1;
+ * a pixel inside several takes the largest label (the later polygon wins, as painting in order would), a pixel inside none is 0.
+ * A polygon that covers no pixel centre is an empty zone.  The result is this definition bit for bit on every run.
+ *
+ * lars_d_zone_rasterize: all three arrays and labels[h][w] (int32, zeroed by the call) on the device; scratch:
+ * lars_zone_rasterize_scratch_bytes(npolys) bytes, 256-byte aligned; verts 16-byte aligned.  The arrays are not checked on the device: indices that
+ * leave them are clamped, so arrays that break the rules above give wrong labels and no access outside the buffers.  The labels
+ * feed lars_d_zone_count / lars_d_zone_scatter as they are, with zone_bytes 4 and nzones = npolys.
+ * lars_d_zone_labels_narrow: out[npix] uint8 (zone_bytes 1) or uint16 (2) = the int32 labels, for a raster that goes to the host. */
+#define LARS_ZONE_VERTS_MAX 16777216
+size_t lars_zone_rasterize_scratch_bytes(int64_t npolys);
+int lars_d_zone_rasterize(const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts,
+                          int64_t npolys, int64_t h, int64_t w, int32_t *labels, void *scratch, void *stream);
+int lars_d_zone_labels_narrow(const int32_t *labels, int64_t npix, int zone_bytes, void *out, void *stream);
+/* rasterize_zones(polygons, shape): host arrays in (checked: the rules above, LARS_ERR_INVALID names the first ring or vertex that
+ * breaks them), host labels[h][w] out, zone_bytes 1, 2 or 4 wide; npolys must fit the width (255, 65535). */
+int lars_h_rasterize_zones(const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts,
+                           int64_t npolys, int64_t h, int64_t w, int zone_bytes, void *labels);
+/* lars_h_zonal_stats_f32 with the labels rasterised on the device from host polygon arrays instead of uploaded: nzones = npolys,
+ * stats[npolys], medians[npolys][2].  labels_out: NULL (the labels never leave the device) or host [h][w] labels, label_bytes 1,
+ * 2 or 4 wide.  By definition the records are those of lars_h_zonal_stats_f32 on lars_h_rasterize_zones's raster. */
+int lars_h_zonal_stats_polygons_f32(const float *x, const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings,
+                                    const int32_t *poly_starts, int64_t npolys, const uint8_t *valid /* may be NULL */, int64_t h, int64_t w,
+                                    float threshold, int want_hist, lars_stats *stats /* [npolys] */, float *medians /* [npolys][2] */,
+                                    void *labels_out /* may be NULL */, int label_bytes);
+/* lars_h_process_image_zones likewise: zone_stats[3][npolys], zone_medians[3][npolys][2]. */
+int lars_h_process_image_zones_polygons(const void *img, int64_t h, int64_t w, int channels, int dtype,
+                                        int apply_wb, uint32_t index_mask, int want_hist,
+                                        uint8_t *out_wb, float *const out_index[3],
+                                        lars_stats *stats /* [3] */, float *medians /* [3][2] */,
+                                        uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3],
+                                        const uint8_t *valid, int use_alpha, int has_nodata, int nodata, int64_t *valid_pixels,
+                                        const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings,
+                                        const int32_t *poly_starts, int64_t npolys,
+                                        lars_stats *zone_stats /* [3][npolys] */, float *zone_medians /* [3][npolys][2] */,
+                                        void *labels_out /* may be NULL */, int label_bytes);
+
 /* ------------------------------------------------------------------ multi-GPU */
 /* One process per GPU.  RCCL (librccl.so) is loaded on first use.  unique_id is
  * LARS_COMM_ID_BYTES bytes produced by lars_comm_unique_id() on rank 0 and

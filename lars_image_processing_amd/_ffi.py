@@ -287,6 +287,14 @@ SIGNATURES = {
     "lars_h_process_image_zones": (_I, [_P, _I64, _I64, _I, _I, _I, _U32, _I, _P, C.POINTER(_P * 3), _P, _P,
                                         C.POINTER(_P * 3), C.POINTER(_P * 3), _P, _I, _I, _I, C.POINTER(_I64),
                                         _P, _I, _I64, _P, _P, C.POINTER(_I64)]),
+    "lars_zone_rasterize_scratch_bytes": (_SZ, [_I64]),
+    "lars_d_zone_rasterize": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _P]),
+    "lars_d_zone_labels_narrow": (_I, [_P, _I64, _I, _P, _P]),
+    "lars_h_rasterize_zones": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _I, _P]),
+    "lars_h_zonal_stats_polygons_f32": (_I, [_P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _F, _I, _P, _P, _P, _I]),
+    "lars_h_process_image_zones_polygons": (_I, [_P, _I64, _I64, _I, _I, _I, _U32, _I, _P, C.POINTER(_P * 3), _P, _P,
+                                                 C.POINTER(_P * 3), C.POINTER(_P * 3), _P, _I, _I, _I, C.POINTER(_I64),
+                                                 _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I]),
     "lars_jpeg_bound": (_SZ, [_I64, _I64, _I, _I]),
     "lars_jpeg_header": (_I64, [_I64, _I64, _I, _I, _I, _P, _SZ]),
     "lars_jpeg_encode_scratch_bytes": (_SZ, [_I64, _I64, _I, _I]),

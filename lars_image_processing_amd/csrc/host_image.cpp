@@ -2,6 +2,7 @@
 // masked and zones variants, zonal_stats and valid_mask.  Every picture entry point fills an ImageJob (picture_job plus what is
 // its own) and hands it to run_image, which decides the route once (route_of) and then runs a short sequence of stages:
 // plan, upload, planes and statistics (one runner per route), pictures, TIFF, collect, fetch files.
+#include <math.h>
 #include <string.h>
 #include <vector>
 
@@ -20,12 +21,33 @@ struct ZoneBufs {
     lars_stats *stats;             // [3][nzones]
     float *med;                    // [3][nzones][2]
     char *sel;                     // select scratch of the large zones
+    // labels made from polygons (zone_raster.hip): B.labels is then the int32 raster the rasteriser writes
+    double *verts;
+    int32_t *rings, *polys;
+    char *raster_scratch;
+    char *narrow;                  // the labels at the width the caller wants them back in, where that is not 4
 };
 
-ZoneBufs zone_plan(Carver &c, size_t npix, int zone_bytes, int64_t nzones, uint32_t mask)
+// The polygons of a job, as the entry points take them (include/lars_hip.h "zones from polygons"); nzones = npolys.
+struct ZonePolys {
+    const double *verts; int64_t nverts;
+    const int32_t *ring_starts; int64_t nrings;
+    const int32_t *poly_starts; int64_t npolys;
+    void *labels_out; int label_bytes;     // host [h][w] labels back, or null
+};
+
+ZoneBufs zone_plan(Carver &c, size_t npix, int zone_bytes, int64_t nzones, uint32_t mask, const ZonePolys *P = nullptr)
 {
     ZoneBufs B;
+    memset(&B, 0, sizeof B);
     const size_t nz = (size_t)nzones;
+    if (P) {
+        B.verts = c.take<double>(2 * (size_t)P->nverts);
+        B.rings = c.take<int32_t>((size_t)P->nrings + 1);
+        B.polys = c.take<int32_t>((size_t)P->npolys + 1);
+        B.raster_scratch = c.take<char>(lars_zone_rasterize_scratch_bytes(P->npolys));
+        B.narrow = (P->labels_out && P->label_bytes != 4) ? c.take<char>(npix * (size_t)P->label_bytes) : nullptr;
+    }
     B.labels = c.take<char>(npix * (size_t)zone_bytes);
     B.counts = c.take<uint64_t>(nz + 2);
     B.ends = c.take<uint64_t>(nz + 1);
@@ -37,15 +59,58 @@ ZoneBufs zone_plan(Carver &c, size_t npix, int zone_bytes, int64_t nzones, uint3
     return B;
 }
 
-// labels up, the four stages, the records down (host_stats[3][nzones], host_med[3][nzones][2]; rows outside mask untouched).
+// Everything about the polygons that needs no device: the first ring or vertex that breaks a rule is named.
+int check_polygons(const char *who, const ZonePolys &P, int64_t h, int64_t w)
+{
+    if (!P.verts || !P.ring_starts || !P.poly_starts) return fail(LARS_ERR_INVALID, "%s: verts, ring_starts and poly_starts are required", who);
+    if (P.npolys < 1 || P.npolys > LARS_ZONES_MAX) return fail(LARS_ERR_INVALID, "%s: 1 to %d polygons, got %lld", who, LARS_ZONES_MAX, (long long)P.npolys);
+    if (P.nrings < P.npolys || P.nverts < 3 * P.nrings || P.nverts > LARS_ZONE_VERTS_MAX)
+        return fail(LARS_ERR_INVALID, "%s: %lld polygons need as many rings or more (got %lld) of three vertices or more each (got %lld in all, at most %d)",
+                    who, (long long)P.npolys, (long long)P.nrings, (long long)P.nverts, LARS_ZONE_VERTS_MAX);
+    if (h <= 0 || w <= 0 || h > (1 << 24) || w > (1 << 24)) return fail(LARS_ERR_INVALID, "%s: the raster is 1 to 2^24 on each side", who);
+    if (P.labels_out && P.label_bytes != 1 && P.label_bytes != 2 && P.label_bytes != 4)
+        return fail(LARS_ERR_INVALID, "%s: labels come back 1, 2 or 4 bytes wide, got %d", who, P.label_bytes);
+    if (P.labels_out && ((P.label_bytes == 1 && P.npolys > 255) || !aligned_to(P.labels_out, (uintptr_t)P.label_bytes)))
+        return fail(LARS_ERR_INVALID, "%s: %lld labels do not fit %d-byte labels, or the labels are not aligned", who, (long long)P.npolys, P.label_bytes);
+    if (P.poly_starts[0] != 0 || P.poly_starts[P.npolys] != P.nrings || P.ring_starts[0] != 0 || P.ring_starts[P.nrings] != P.nverts)
+        return fail(LARS_ERR_INVALID, "%s: poly_starts must run from 0 to nrings and ring_starts from 0 to nverts", who);
+    for (int64_t k = 0; k < P.npolys; ++k)
+        if (P.poly_starts[k + 1] <= P.poly_starts[k] || P.poly_starts[k + 1] > P.nrings)
+            return fail(LARS_ERR_INVALID, "%s: polygon %lld has no ring (poly_starts must rise)", who, (long long)k);
+    for (int64_t r = 0; r < P.nrings; ++r)
+        if ((int64_t)P.ring_starts[r + 1] - P.ring_starts[r] < 3 || P.ring_starts[r + 1] > P.nverts)
+            return fail(LARS_ERR_INVALID, "%s: ring %lld has fewer than three vertices (ring_starts must rise by three or more)", who, (long long)r);
+    for (int64_t i = 0; i < 2 * P.nverts; ++i)
+        if (!(fabs(P.verts[i]) <= 1e9))
+            return fail(LARS_ERR_INVALID, "%s: vertex %lld has a coordinate that is not finite or beyond 1e9 in size", who, (long long)(i / 2));
+    return LARS_OK;
+}
+
+// the polygons up, their labels into B.labels (int32) and, where the caller wants them, back at his width: on the stream
+int raster_zones(const ZoneBufs &B, const ZonePolys &P, int64_t h, int64_t w, hipStream_t s)
+{
+    LARS_HIP_TRY(hipMemcpyAsync(B.verts, P.verts, 2 * (size_t)P.nverts * sizeof(double), hipMemcpyHostToDevice, s));
+    LARS_HIP_TRY(hipMemcpyAsync(B.rings, P.ring_starts, ((size_t)P.nrings + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    LARS_HIP_TRY(hipMemcpyAsync(B.polys, P.poly_starts, ((size_t)P.npolys + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    int32_t *labels = reinterpret_cast<int32_t *>(B.labels);
+    LARS_TRY(lars_d_zone_rasterize(B.verts, P.nverts, B.rings, P.nrings, B.polys, P.npolys, h, w, labels, B.raster_scratch, s));
+    if (!P.labels_out) return LARS_OK;
+    const size_t npix = (size_t)h * (size_t)w;
+    if (B.narrow) LARS_TRY(lars_d_zone_labels_narrow(labels, (int64_t)npix, P.label_bytes, B.narrow, s));
+    LARS_HIP_TRY(hipMemcpyAsync(P.labels_out, B.narrow ? B.narrow : B.labels, npix * (size_t)P.label_bytes, hipMemcpyDeviceToHost, s));
+    return LARS_OK;
+}
+
+// labels up (or made from the polygons P, zone_bytes 4), the four stages, the records down (host_stats[3][nzones], host_med[3][nzones][2]; rows outside mask untouched).
 // The counts cross to the host once: bad labels end the call there, and zones above the knob zone_split_pixels take the array
 // kernels, which spread one zone over many workgroups.  The copies down are on the stream when this returns: the caller waits.
 int run_zones(const char *who, const ZoneBufs &B, const void *zones, int zone_bytes, const uint8_t *valid_dev, int64_t npix, int64_t nzones,
               const float *const planes[3], uint32_t mask, const float thr[3], int want_hist, lars_stats *host_stats, float *host_med,
-              int64_t *bad_labels, hipStream_t s)
+              int64_t *bad_labels, hipStream_t s, const ZonePolys *P = nullptr, int64_t h = 0, int64_t w = 0)
 {
     const size_t nz = (size_t)nzones;
-    LARS_HIP_TRY(hipMemcpyAsync(B.labels, zones, (size_t)npix * zone_bytes, hipMemcpyHostToDevice, s));
+    if (P) LARS_TRY(raster_zones(B, *P, h, w, s));
+    else LARS_HIP_TRY(hipMemcpyAsync(B.labels, zones, (size_t)npix * zone_bytes, hipMemcpyHostToDevice, s));
     LARS_TRY(lars_d_zone_count(B.labels, zone_bytes, valid_dev, npix, nzones, B.counts, B.counts + nz + 1, s));
     std::vector<uint64_t> counts(nz + 2);
     LARS_HIP_TRY(hipMemcpyAsync(counts.data(), B.counts, (nz + 2) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -117,6 +182,7 @@ struct ImageJob {
     lars_stats *zone_stats;       // [3][nzones]
     float *zone_medians;          // [3][nzones][2]
     int64_t *bad_labels;
+    const ZonePolys *polys;       // ... or the plots' outlines instead of zones: the labels are made on the device (zone_raster.hip)
 };
 
 // The head every picture entry point shares, in the order of their prototypes; each entry point adds only what is its own.
@@ -228,7 +294,7 @@ Route route_of(const ImageJob &j)
         const bool for_caller = j.out_index[k] != nullptr;                       // it is copied back
         const bool for_entries = r.entry[k];                                     // the entry plane is derived from it on the device
         const bool for_tiff = j.tiff != 0;                                       // its file is encoded from it
-        const bool for_zones = j.zones != nullptr;                               // the zone stages scatter it
+        const bool for_zones = j.zones != nullptr || j.polys != nullptr;         // the zone stages scatter it
         const bool for_median = r.medians && r.planes == Route::FUSED;           // the select over the plane reads it
         r.plane[k] = on && (for_caller || for_entries || for_tiff || for_zones || for_median);
     }
@@ -296,7 +362,7 @@ Layout plan(const ImageJob &j, const Route &r, Carver &c)
     L.vhist = (j.masked && j.apply_wb) ? c.take<uint32_t>(3 * nval) : nullptr;
     for (int k = 0; k < 3; ++k)
         L.vals[k] = (j.masked && ((j.mask >> k) & 1u) && (j.stats || j.medians)) ? c.take<float>(npix) : nullptr;
-    if (j.zones) L.zone = zone_plan(c, npix, j.zone_bytes, j.nzones, j.mask);
+    if (j.zones || j.polys) L.zone = zone_plan(c, npix, j.zone_bytes, j.nzones, j.mask, j.polys);
     return L;
 }
 
@@ -380,10 +446,10 @@ int run_masked(const ImageJob &j, const Layout &L, hipStream_t s)
         if (j.stats) LARS_TRY(lars_d_array_stats_f32(L.vals[k], (int64_t)nvalid, k == LARS_NDWI ? 0.0f : 0.2f, j.want_hist, L.stats + k, s));
         if (j.medians) LARS_TRY(lars_d_median_pair_f32(L.vals[k], (int64_t)nvalid, L.med + 2 * k, L.sel + k * select_slot(), s));
     }
-    if (!j.zones) return LARS_OK;
+    if (!j.zones && !j.polys) return LARS_OK;
     const float thr[3] = {0.2f, 0.2f, 0.0f};                // as the records above
     return run_zones(j.who, L.zone, j.zones, j.zone_bytes, L.vmask, npix, j.nzones, L.idx, j.mask, thr, j.want_hist, j.zone_stats,
-                     j.zone_medians, j.bad_labels, s);
+                     j.zone_medians, j.bad_labels, s, j.polys, j.h, j.w);
 }
 
 // ---- stage 4: the planes and pictures back, entry planes and PNG files built from what stays on the device ----
@@ -592,15 +658,43 @@ int lars_h_process_image_zones(const void *img, int64_t h, int64_t w, int channe
     return run_image(j);
 }
 
-int lars_h_zonal_stats_f32(const float *x, const void *zones, int zone_bytes, const uint8_t *valid, int64_t h, int64_t w, int64_t nzones,
-                           float threshold, int want_hist, lars_stats *stats, float *medians, int64_t *bad_labels)
+int lars_h_process_image_zones_polygons(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                                        int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                                        uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], const uint8_t *valid, int use_alpha,
+                                        int has_nodata, int nodata, int64_t *valid_pixels, const double *verts, int64_t nverts,
+                                        const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts, int64_t npolys,
+                                        lars_stats *zone_stats, float *zone_medians, void *labels_out, int label_bytes)
 {
-    static const char *who = "lars_h_zonal_stats_f32";
-    if (bad_labels) *bad_labels = -1;
+    static const char *who = "lars_h_process_image_zones_polygons";
+    if (valid_pixels) *valid_pixels = -1;
+    LARS_TRY(check_picture(who, img, h, w, channels, dtype, index_mask, use_alpha, has_nodata, nodata, out_rgba, cmap_lut));
+    if (!index_mask || (index_mask & ~LARS_MASK_ALL)) return fail(LARS_ERR_INVALID, "%s: index_mask must name one to three indices", who);
+    if (!zone_stats || !zone_medians) return fail(LARS_ERR_INVALID, "%s: the zones' records and medians are required", who);
+    const ZonePolys P = {verts, nverts, ring_starts, nrings, poly_starts, npolys, labels_out, label_bytes};
+    LARS_TRY(check_polygons(who, P, h, w));
+    ImageJob j = picture_job(who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut);
+    under_mask(j, valid, use_alpha, has_nodata, nodata, valid_pixels);
+    j.polys = &P; j.zone_bytes = 4; j.nzones = npolys; j.zone_stats = zone_stats; j.zone_medians = zone_medians;
+    return run_image(j);
+}
+
+}  // extern "C"
+
+namespace {
+
+// zonal_statistics of a host plane, with the labels uploaded (zones) or rasterised (P)
+int zonal_stats(const char *who, const float *x, const void *zones, int zone_bytes, const ZonePolys *P, const uint8_t *valid, int64_t h, int64_t w,
+                int64_t nzones, float threshold, int want_hist, lars_stats *stats, float *medians, int64_t *bad_labels)
+{
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (!x || h <= 0 || w <= 0) return fail(LARS_ERR_INVALID, "%s: x must be a non-empty [h][w] float32 array", who);
-    LARS_TRY(zone_arguments(who, zones, zone_bytes, nzones, stats, medians));
+    if (P) {
+        if (!stats || !medians) return fail(LARS_ERR_INVALID, "%s: the zones' records and medians are required", who);
+        LARS_TRY(check_polygons(who, *P, h, w));
+    } else {
+        LARS_TRY(zone_arguments(who, zones, zone_bytes, nzones, stats, medians));
+    }
     const size_t npix = (size_t)h * w;
     float *dx;
     uint8_t *dvalid;
@@ -608,15 +702,50 @@ int lars_h_zonal_stats_f32(const float *x, const void *zones, int zone_bytes, co
     LARS_TRY(ws_plan(c, [&](Carver &d) {
         dx = d.take<float>(npix);
         dvalid = valid ? d.take<uint8_t>(npix) : nullptr;
-        B = zone_plan(d, npix, zone_bytes, nzones, 1u);
+        B = zone_plan(d, npix, zone_bytes, nzones, 1u, P);
     }));
     hipStream_t s = c->stream;
     LARS_HIP_TRY(hipMemcpyAsync(dx, x, npix * sizeof(float), hipMemcpyHostToDevice, s));
     if (valid) LARS_HIP_TRY(hipMemcpyAsync(dvalid, valid, npix, hipMemcpyHostToDevice, s));
     const float *planes[3] = {dx, nullptr, nullptr};
     const float thr[3] = {threshold, threshold, threshold};
-    LARS_TRY(run_zones(who, B, zones, zone_bytes, dvalid, (int64_t)npix, nzones, planes, 1u, thr, want_hist, stats, medians, bad_labels, s));
+    LARS_TRY(run_zones(who, B, zones, zone_bytes, dvalid, (int64_t)npix, nzones, planes, 1u, thr, want_hist, stats, medians, bad_labels, s, P, h, w));
     LARS_HIP_TRY(hipStreamSynchronize(s));
+    return LARS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lars_h_zonal_stats_f32(const float *x, const void *zones, int zone_bytes, const uint8_t *valid, int64_t h, int64_t w, int64_t nzones,
+                           float threshold, int want_hist, lars_stats *stats, float *medians, int64_t *bad_labels)
+{
+    if (bad_labels) *bad_labels = -1;
+    return zonal_stats("lars_h_zonal_stats_f32", x, zones, zone_bytes, nullptr, valid, h, w, nzones, threshold, want_hist, stats, medians, bad_labels);
+}
+
+int lars_h_zonal_stats_polygons_f32(const float *x, const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings,
+                                    const int32_t *poly_starts, int64_t npolys, const uint8_t *valid, int64_t h, int64_t w, float threshold,
+                                    int want_hist, lars_stats *stats, float *medians, void *labels_out, int label_bytes)
+{
+    const ZonePolys P = {verts, nverts, ring_starts, nrings, poly_starts, npolys, labels_out, label_bytes};
+    return zonal_stats("lars_h_zonal_stats_polygons_f32", x, nullptr, 4, &P, valid, h, w, npolys, threshold, want_hist, stats, medians, nullptr);
+}
+
+int lars_h_rasterize_zones(const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts,
+                           int64_t npolys, int64_t h, int64_t w, int zone_bytes, void *labels)
+{
+    static const char *who = "lars_h_rasterize_zones";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!labels) return fail(LARS_ERR_INVALID, "%s: labels == NULL", who);
+    const ZonePolys P = {verts, nverts, ring_starts, nrings, poly_starts, npolys, labels, zone_bytes};
+    LARS_TRY(check_polygons(who, P, h, w));
+    ZoneBufs B;
+    LARS_TRY(ws_plan(c, [&](Carver &d) { B = zone_plan(d, (size_t)h * (size_t)w, 4, npolys, 0u, &P); }));
+    LARS_TRY(raster_zones(B, P, h, w, c->stream));
+    LARS_HIP_TRY(hipStreamSynchronize(c->stream));
     return LARS_OK;
 }
 

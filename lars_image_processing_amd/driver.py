@@ -78,9 +78,43 @@ def _mask_argument(mask_kw):
     return (mask_kw,) if mask_kw else ()
 
 
-def _zones_argument(zones):
-    """``_process_image``'s ``zones`` keyword, handed over only where a label raster is named: without one the call is the one it always was."""
-    return {} if zones is None else {"zones": zones}
+def _zones_argument(zones, zones_transform=None):
+    """``_process_image``'s ``zones`` (and ``zones_transform``) keywords, handed over only where they are named: without them the call is
+    the one it always was."""
+    kw = {} if zones is None else {"zones": zones}
+    if zones_transform is not None:
+        kw["zones_transform"] = zones_transform
+    return kw
+
+
+POLYGON_SUFFIXES = (".geojson", ".json")
+
+
+def _read_zones(zones, zones_transform, shape, image_name):
+    """``zones=PATH`` -> what ``process_image_zones`` takes: the polygons of a ``.geojson`` / ``.json`` file (rasterised on the device,
+    ``zones_transform``: the six numbers of the geotransform their coordinates are in), or the label raster of any other file."""
+    from .tiffio import read_image
+    if Path(zones).suffix.lower() in POLYGON_SUFFIXES:
+        from .zones import Polygons, polygons_from_geojson
+        return Polygons(polygons_from_geojson(zones), transform=zones_transform, who=Path(zones).name)
+    if zones_transform is not None:
+        raise ValueError(f"{Path(zones).name}: zones_transform goes with a .geojson / .json file of polygons, not with a label raster")
+    labels = read_image(zones)
+    if labels.shape != shape:
+        raise ValueError(f"{Path(zones).name}: the label raster has shape {labels.shape}, {image_name} is {shape}")
+    return labels
+
+
+def _transform_numbers(text):
+    """``--zones-transform a,b,c,d,e,f`` -> six floats."""
+    import argparse
+    try:
+        numbers = tuple(float(v) for v in text.split(","))
+    except ValueError:
+        numbers = ()
+    if len(numbers) != 6:
+        raise argparse.ArgumentTypeError(f"six comma-separated numbers x0,dx,rx,y0,ry,dy are needed, got {text!r}")
+    return numbers
 
 
 ZONE_CSV_COLUMNS = ("Zone", "Index", "Pixels", "Mean", "Median", "Min", "Max", "Coverage (%)")
@@ -109,7 +143,7 @@ def _matching(png_encoder, tiff_encoder):
 
 def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png",
                   png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow", tiff_encoder="pillow",
-                  index_tiff=False, nodata=None, alpha_mask=False, zones=None):
+                  index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None):
     """One file: same outputs as backend-process.py:49-73.  Returns the statistics dicts.
     ``full_depth=True`` reads three-sample 16-bit TIFFs at their full depth (``tiffio.read_image``; Pillow, hence the
     reference, keeps their high bytes only).  ``lut_format="tiff"`` writes the colormap images as
@@ -137,7 +171,10 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     ``zones=PATH`` names a single-band integer label raster of the picture's size (0 = in no zone; ``tiffio.read_image`` reads it)
     and adds ``<name>_zones.csv`` next to the outputs: one row per zone and requested index (``zones.process_image_zones``,
     ``zones.zonal_rows``), with the picture's white balance and under the same ``nodata`` / ``alpha_mask``.  Every other file is
-    unchanged; the statistics come from a call of their own."""
+    unchanged; the statistics come from a call of their own.  A ``zones`` path that ends in ``.geojson`` / ``.json`` holds the plots'
+    outlines instead (``zones.polygons_from_geojson``; zone ``k`` is the ``k``-th geometry of the file): they are rasterised on the
+    device (``zones.rasterize_zones``'s rule), in pixel coordinates or, with ``zones_transform=(x0, dx, rx, y0, ry, dy)``, in the
+    world coordinates of that GDAL geotransform.  The CSV has the same columns either way."""
     if lut_format not in ("png", "png8", "tiff"):
         raise ValueError(f"lut_format must be 'png', 'png8' or 'tiff', got {lut_format!r}")
     _check_png_encoder(png_encoder)
@@ -149,11 +186,11 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     block, png_encoder, tiff_encoder = _matching(png_encoder, tiff_encoder)
     with block:
         return _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder,
-                              tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw), **_zones_argument(zones))
+                              tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw), **_zones_argument(zones, zones_transform))
 
 
 def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder, tiff_decoder,
-                   tiff_encoder, index_tiff, mask_kw=None, zones=None):
+                   tiff_encoder, index_tiff, mask_kw=None, zones=None, zones_transform=None):
     """``process_image`` behind its checks, for ``"pillow"``, ``"device"`` and ``"device+deflate"``."""
     from PIL import Image
     from .tiffio import read_image
@@ -166,9 +203,7 @@ def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_
     mask_kw = mask_kw or {}
     if zones is not None and indices:
         from .zones import process_image_zones
-        labels = read_image(zones)
-        if labels.shape != arr.shape[:2]:
-            raise ValueError(f"{Path(zones).name}: the label raster has shape {labels.shape}, {image_path.name} is {arr.shape[:2]}")
+        labels = _read_zones(zones, zones_transform, arr.shape[:2], image_path.name)
         output_dir.mkdir(parents=True, exist_ok=True)
         _write_zones_csv(output_dir / f"{name}_zones.csv",
                          process_image_zones(arr, labels, **mask_kw, indices=indices, white_balance=True, want_arrays=False), indices)
@@ -247,13 +282,13 @@ def files_of_rank(files, rank=0, world=1):
 def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, process_gndvi=False,
                   process_ndwi=True, workers=4, verbose=True, full_depth=False, lut_format="png", rank=0, world=1,
                   device=None, png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow",
-                  tiff_encoder="pillow", index_tiff=False, nodata=None, alpha_mask=False, zones=None):
+                  tiff_encoder="pillow", index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None):
     """backend-process.py:75-97 with its module constants as arguments.  Returns ``{file name: stats | error}``.
     ``rank`` / ``world``: one process per GPU, each takes its block of the sorted file list (``files_of_rank``); the output
     directories are shared, the file names distinct.  ``device``: the GPU ordinal every worker thread binds (the library's
     context is per thread and defaults to device 0); None leaves the threads' binding alone.  ``png_encoder``,
     ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``, ``tiff_encoder``, ``index_tiff``, ``nodata``, ``alpha_mask``, ``zones`` (one label
-    raster for every file of the directory): see ``process_image``."""
+    raster, or one file of polygons with its ``zones_transform``, for every file of the directory): see ``process_image``."""
     mask_kw = _mask_options(nodata, alpha_mask, lut_format)
     _check_tiff_encoder(tiff_encoder)
     _check_png_encoder(png_encoder)
@@ -274,7 +309,7 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
                 print(f"Processing {idx}/{total}: {f.name}")
             return f.name, _process_image(f, output_path, process_wb, indices or None, full_depth, lut_format, png_encoder,
                                           png_decoder, jpeg_decoder, tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw),
-                                          **_zones_argument(zones))
+                                          **_zones_argument(zones, zones_transform))
         except Exception as e:                              # same policy as upstream :96-97
             if verbose:
                 print(f"Error processing {f.name}: {str(e)}")
@@ -383,7 +418,10 @@ def main(argv=None):
                     help="pixels whose channel 3 (alpha) is 0 are no picture; combines with --nodata")
     ap.add_argument("--zones", default=None, metavar="PATH",
                     help="a single-band integer label raster of the pictures' size (0 = in no zone): also write <name>_zones.csv, one row "
-                         "per zone and index, with the picture's white balance; combines with --nodata / --alpha-mask")
+                         "per zone and index, with the picture's white balance; combines with --nodata / --alpha-mask.  A .geojson / "
+                         ".json file holds the plots' outlines instead: they are rasterised on the GPU, zone k is the k-th geometry")
+    ap.add_argument("--zones-transform", default=None, type=_transform_numbers, metavar="x0,dx,rx,y0,ry,dy",
+                    help="the GDAL geotransform (pixel -> world) the polygons of --zones are in; without it they are in pixel units")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     from .dist import env_rank_world
@@ -393,7 +431,7 @@ def main(argv=None):
                         device=local_rank if world > 1 else None, png_encoder=args.png_encoder,
                         png_decoder=args.png_decoder, jpeg_decoder=args.jpeg_decoder, tiff_decoder=args.tiff_decoder,
                         tiff_encoder=args.tiff_encoder, index_tiff=args.index_tiff, nodata=args.nodata, alpha_mask=args.alpha_mask,
-                        **_zones_argument(args.zones))
+                        **_zones_argument(args.zones, args.zones_transform))
     failed = {k: str(v) for k, v in res.items() if isinstance(v, Exception)}
     print(json.dumps({"rank": rank, "world": world, "files": len(res), "failed": failed}))
     return 1 if failed else 0

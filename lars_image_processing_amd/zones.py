@@ -3,10 +3,16 @@
 ``zones`` is an integer ``[H, W]`` array of labels ``0 .. Z``; 0 is "in no zone".  For zone ``z`` the figures are
 ``analyze_index``'s on ``index[valid & (zones == z)]``: ``zonal_statistics`` for any float32 plane, ``process_image_zones`` for a
 picture, whose white balance stays the whole valid picture's, never the plot's.  ``zonal_rows`` turns either result into the rows a
-table or a CSV wants.  The kernels are csrc/zonal.hip; there is no NumPy fallback."""
+table or a CSV wants.  The kernels are csrc/zonal.hip; there is no NumPy fallback.
+
+Where ``zones`` is wanted, plot outlines serve as well (DESIGN.md "Zones from polygons", csrc/zone_raster.hip): a list of polygons, or
+``Polygons(list, transform=, want_labels=)``.  The labels are then made on the device and never cross PCIe; ``rasterize_zones`` returns
+them, ``polygons_from_geojson`` reads the outlines from a GeoJSON export and ``to_pixel`` undoes a GDAL geotransform."""
 from __future__ import annotations
 
 import ctypes as C
+import json
+import os
 
 import numpy as np
 
@@ -16,6 +22,8 @@ from ._ffi import INDEX_IDS
 from .api import _coverage_rule, _picture, _picture_result
 
 ZONES_MAX = 65535
+VERTICES_MAX = 1 << 24
+COORDINATE_MAX = 1e9
 _FIGURES = ("mean", "median", "min", "max", "coverage")
 
 
@@ -50,6 +58,247 @@ def _labels(zones, shape, n_zones, who):
             raise ValueError(f"{who}: {above} pixels have a label outside 0 .. {n_zones}")
         z = z.astype(np.int32)
     return np.ascontiguousarray(z), n_zones
+
+
+def to_pixel(points, transform):
+    """World coordinates ``[..., 2]`` -> pixel coordinates (x along the columns, y along the rows; pixel (i, j) has its centre at
+    (j + 0.5, i + 0.5)) by the inverse of a GDAL geotransform ``(x0, dx, rx, y0, ry, dy)``: X = x0 + x * dx + y * rx, Y = y0 + x * ry +
+    y * dy.  Float64 NumPy on the host.  A transform that is not six finite numbers or has no inverse raises ``ValueError``."""
+    try:
+        t = np.asarray(transform, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"to_pixel: transform must be six numbers (x0, dx, rx, y0, ry, dy), got {transform!r}") from None
+    if t.shape != (6,) or not np.isfinite(t).all():
+        raise ValueError(f"to_pixel: transform must be six finite numbers (x0, dx, rx, y0, ry, dy), got {transform!r}")
+    x0, dx, rx, y0, ry, dy = t
+    det = dx * dy - rx * ry
+    if det == 0 or not np.isfinite(det):
+        raise ValueError(f"to_pixel: the transform {tuple(t)} is singular: dx * dy - rx * ry = {det}")
+    pts = np.asarray(points, dtype=np.float64)
+    if pts.ndim < 1 or pts.shape[-1] != 2:
+        raise ValueError(f"to_pixel: points must be [..., 2] (x, y), got shape {pts.shape}")
+    u, v = pts[..., 0] - x0, pts[..., 1] - y0
+    return np.stack(((u * dy - v * rx) / det, (v * dx - u * ry) / det), axis=-1)
+
+
+def _rings_of(item, k, who):
+    """The rings of polygon ``k``: an ``[n, 2]`` array-like is one ring, anything else a sequence of rings."""
+    if isinstance(item, (str, bytes)) or item is None:
+        raise TypeError(f"{who}: polygon {k} must be an [n, 2] array-like or a sequence of such rings, got {type(item).__name__}")
+    try:
+        a = np.asarray(item, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = None                                                   # rings of different lengths
+    if a is not None and a.ndim == 2:
+        return [a]
+    if a is not None and a.ndim == 3:
+        return list(a)
+    try:
+        return list(item)
+    except TypeError:
+        raise TypeError(f"{who}: polygon {k} must be an [n, 2] array-like or a sequence of such rings, got {type(item).__name__}") from None
+
+
+class Polygons:
+    """Plot outlines, checked and packed as the library takes them: ``Polygons(polygons, transform=None, want_labels=False)``.
+
+    ``polygons`` is a sequence; each item is an ``[n, 2]`` array-like of (x, y) vertices (one ring) or a sequence of such rings, whose
+    edges are pooled (holes, parts).  Polygon ``k`` (0-based) labels its pixels ``k + 1``; where polygons overlap the later one wins.
+    ``transform``: the six numbers of a GDAL geotransform when the vertices are world coordinates (``to_pixel`` is applied here).
+    ``want_labels=True`` asks ``process_image_zones`` / ``zonal_statistics`` to return the label raster as well.  Every check runs
+    here, on the host: ``TypeError`` / ``ValueError`` name the polygon and the ring."""
+
+    def __init__(self, polygons, transform=None, want_labels=False, who="Polygons"):
+        if isinstance(polygons, Polygons):
+            if transform is not None:
+                raise ValueError(f"{who}: these Polygons are in pixel coordinates already: transform cannot be applied again")
+            self.verts, self.ring_starts, self.poly_starts = polygons.verts, polygons.ring_starts, polygons.poly_starts
+            self.want_labels = bool(want_labels or polygons.want_labels)
+            return
+        if isinstance(polygons, (str, bytes, dict)) or polygons is None:
+            raise TypeError(f"{who}: polygons must be a sequence of polygons, got {type(polygons).__name__} (polygons_from_geojson reads GeoJSON)")
+        try:
+            items = list(polygons)
+        except TypeError:
+            raise TypeError(f"{who}: polygons must be a sequence of polygons, got {type(polygons).__name__}") from None
+        if not items:
+            raise ValueError(f"{who}: the list of polygons is empty")
+        if len(items) > ZONES_MAX:
+            raise ValueError(f"{who}: {len(items)} polygons; at most {ZONES_MAX} make one label raster")
+        rings, ring_starts, poly_starts, total = [], [0], [0], 0
+        try:
+            same = np.asarray(polygons if isinstance(polygons, np.ndarray) else items, dtype=np.float64) if len(items) > 1 else None
+        except (TypeError, ValueError):
+            same = None
+        if same is not None and same.ndim == 3 and same.shape[1] >= 3 and same.shape[2] == 2:
+            # Z single rings of one length, the usual export of a trial's plots: no step per polygon
+            n = same.shape[1]
+            ring_starts = list(range(0, len(items) * n + 1, n))
+            poly_starts = list(range(len(items) + 1))
+            total, items = len(items) * n, []
+            rings = [same.reshape(-1, 2)]
+        for k, item in enumerate(items):
+            mine = _rings_of(item, k, who)
+            if not mine:
+                raise ValueError(f"{who}: polygon {k} has no ring")
+            for r, ring in enumerate(mine):
+                try:
+                    a = np.asarray(ring, dtype=np.float64)
+                except (TypeError, ValueError):
+                    raise TypeError(f"{who}: polygon {k} ring {r} must be an [n, 2] array of numbers") from None
+                if a.ndim != 2 or a.shape[1] != 2:
+                    raise ValueError(f"{who}: polygon {k} ring {r} must have shape [n, 2] (x, y), got {a.shape}")
+                if a.shape[0] < 3:
+                    raise ValueError(f"{who}: polygon {k} ring {r} has {a.shape[0]} vertices; a ring needs 3 or more")
+                total += a.shape[0]
+                rings.append(a)
+                ring_starts.append(total)
+            poly_starts.append(len(rings))
+        if total > VERTICES_MAX:
+            raise ValueError(f"{who}: {total} vertices in all; at most 2**24 = {VERTICES_MAX}")
+        if transform is not None:
+            to_pixel(np.zeros((1, 2)), transform)                  # a bad transform is refused whatever the vertices are
+        verts = np.concatenate(rings)                              # one pass over all vertices; the ring is looked up for a message only
+
+        def ring_of(bad_rows):
+            ring = int(np.searchsorted(ring_starts, int(np.flatnonzero(bad_rows)[0]), side="right")) - 1
+            k = int(np.searchsorted(poly_starts, ring, side="right")) - 1
+            return f"polygon {k} ring {ring - poly_starts[k]}"
+        finite = np.isfinite(verts).all(axis=1)
+        if not finite.all():
+            raise ValueError(f"{who}: {ring_of(~finite)} has a coordinate that is not finite")
+        if transform is not None:
+            verts = to_pixel(verts, transform)
+        small = (np.abs(verts) <= COORDINATE_MAX).all(axis=1)
+        if not small.all():
+            raise ValueError(f"{who}: {ring_of(~small)} has a pixel coordinate beyond 1e9 in size")
+        self.verts = np.ascontiguousarray(verts)
+        self.ring_starts = np.asarray(ring_starts, dtype=np.int32)
+        self.poly_starts = np.asarray(poly_starts, dtype=np.int32)
+        self.want_labels = bool(want_labels)
+
+    def __len__(self):
+        return len(self.poly_starts) - 1
+
+    def _head(self):
+        """The six polygon arguments of the C entry points."""
+        return (_ffi.ptr(self.verts), len(self.verts), _ffi.ptr(self.ring_starts), len(self.ring_starts) - 1, _ffi.ptr(self.poly_starts),
+                len(self))
+
+    def _label_buffer(self, shape):
+        return np.zeros(shape, dtype=np.uint8 if len(self) <= 255 else np.uint16)
+
+
+def _zone_source(zones, n_zones, who):
+    """The split between the two kinds of ``zones``.  None for what ``_labels`` has always taken -- an integer ndarray of two
+    dimensions is a label raster -- and for everything it refuses; ``Polygons`` for outlines: a ``Polygons``, a list or tuple of
+    polygons, or a float ``[Z, n, 2]`` array of single-ring polygons."""
+    if isinstance(zones, Polygons):
+        polys = zones
+    elif isinstance(zones, np.ndarray) and zones.dtype.kind == "f" and zones.ndim == 3 and zones.shape[2] == 2:
+        polys = Polygons(zones, who=who)
+    elif isinstance(zones, (list, tuple)):
+        first = zones[0] if len(zones) else None
+        nested = False
+        rows_of_integers = (isinstance(first, (list, tuple)) and first and isinstance(first[0], (int, np.integer, bool, np.bool_))) or \
+            (isinstance(first, np.ndarray) and first.ndim == 1 and first.dtype.kind in "uib")
+        if rows_of_integers:
+            try:
+                as_array = np.asarray(zones)
+                nested = as_array.ndim == 2 and as_array.dtype.kind in "uib"
+            except ValueError:
+                pass
+        if nested:
+            return None                                            # a label raster written as nested lists
+        polys = Polygons(zones, who=who)
+    else:
+        return None
+    if n_zones is not None:
+        raise ValueError(f"{who}: n_zones cannot be given with polygons: Z = len(polygons) = {len(polys)}")
+    return polys
+
+
+def _raster_shape(shape, who):
+    try:
+        h, w = (int(v) for v in shape)
+        ok = len(tuple(shape)) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in shape)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not (1 <= h <= 1 << 24 and 1 <= w <= 1 << 24):
+        raise ValueError(f"{who}: shape must be (H, W), two ints of 1 to 2**24, got {shape!r}")
+    return h, w
+
+
+def rasterize_zones(polygons, shape, transform=None):
+    """The ``[H, W]`` label raster of plot outlines, made on the device: uint8 for up to 255 polygons, otherwise uint16.
+
+    Pixel (row i, column j) has its centre at (j + 0.5, i + 0.5); it is inside a polygon iff a ray to its left crosses the polygon's
+    pooled edges an odd number of times (even-odd, half-open: of two plots that share an edge exactly one takes each pixel).
+    Polygon ``k`` writes ``k + 1``, the largest label wins, 0 is "in no polygon"; a polygon that covers no pixel centre is an empty
+    zone.  ``polygons`` and ``transform``: see ``Polygons``.  The result is the definition bit for bit on every run, and equals what
+    ``process_image_zones`` / ``zonal_statistics`` use when they are handed the same polygons."""
+    who = "rasterize_zones"
+    polys = polygons if isinstance(polygons, Polygons) and transform is None else Polygons(polygons, transform, who=who)
+    h, w = _raster_shape(shape, who)
+    labels = polys._label_buffer((h, w))
+    _ffi.call("lars_h_rasterize_zones", *polys._head(), h, w, labels.dtype.itemsize, _ffi.ptr(labels))
+    return labels
+
+
+def _geometry_rings(geom, where):
+    kind = geom.get("type") if isinstance(geom, dict) else None
+    if kind == "Polygon":
+        parts = [geom.get("coordinates")]
+    elif kind == "MultiPolygon":
+        parts = geom.get("coordinates")
+    else:
+        raise ValueError(f"polygons_from_geojson: {where}: geometry type {kind!r} is no Polygon or MultiPolygon")
+    rings = []
+    for part in parts or []:
+        for ring in part or []:
+            a = np.asarray(ring, dtype=np.float64)
+            if a.ndim != 2 or a.shape[1] < 2:
+                raise ValueError(f"polygons_from_geojson: {where}: a ring must be a list of [x, y] positions, got shape {a.shape}")
+            rings.append(np.ascontiguousarray(a[:, :2]))
+    if not rings:
+        raise ValueError(f"polygons_from_geojson: {where}: the {kind} has no ring")
+    return rings
+
+
+def _collect(obj, where, out):
+    kind = obj.get("type") if isinstance(obj, dict) else None
+    if kind == "FeatureCollection":
+        for i, feature in enumerate(obj.get("features") or []):
+            _collect(feature, f"feature {i}", out)
+    elif kind == "Feature":
+        if obj.get("geometry") is None:
+            raise ValueError(f"polygons_from_geojson: {where}: the feature has no geometry")
+        _collect(obj["geometry"], where, out)
+    elif kind == "GeometryCollection":
+        for i, geom in enumerate(obj.get("geometries") or []):
+            _collect(geom, f"{where}, geometry {i}" if where else f"geometry {i}", out)
+    else:
+        out.append(_geometry_rings(obj, where or "the object"))
+
+
+def polygons_from_geojson(obj_or_path):
+    """The polygons of a GeoJSON object (a dict) or file (a path): ``Polygon``, ``MultiPolygon``, ``Feature``, ``FeatureCollection``
+    and ``GeometryCollection``.  One polygon per geometry, in file order -- so label ``k + 1`` is the ``k``-th of them -- as a list of
+    lists of ``[n, 2]`` float64 rings; the parts of a ``MultiPolygon`` are pooled into one polygon, a third coordinate is dropped.
+    Any other geometry type raises ``ValueError`` with the feature's position.  Host JSON only: the coordinates are returned as they
+    stand (``transform=`` maps world coordinates to pixels)."""
+    if isinstance(obj_or_path, dict):
+        obj = obj_or_path
+    elif isinstance(obj_or_path, (str, os.PathLike)):
+        with open(obj_or_path, encoding="utf-8") as f:
+            obj = json.load(f)
+    else:
+        raise TypeError(f"polygons_from_geojson: a GeoJSON dict or a path is needed, got {type(obj_or_path).__name__}")
+    out = []
+    _collect(obj, "", out)
+    if not out:
+        raise ValueError("polygons_from_geojson: no geometry in this object")
+    return out
 
 
 def _bad_labels(who, bad, n_zones):
@@ -93,7 +342,8 @@ def zonal_statistics(index_array, zones, index_type, valid=None, n_zones=None, w
     if x.ndim != 2 or x.size == 0:
         raise ValueError(f"{who}: index_array must be a non-empty [H, W] array, got shape {x.shape}")
     h, w = x.shape
-    lab, nz = _labels(zones, (h, w), n_zones, who)
+    polys = _zone_source(zones, n_zones, who)
+    lab, nz = (None, len(polys)) if polys else _labels(zones, (h, w), n_zones, who)
     if isinstance(valid, str):
         raise TypeError(f"{who}: valid must be an [H, W] bool or integer array or None: a plane has no alpha channel")
     valid_arr, _ = _nodata.valid_argument(valid, (h, w, 0), who)
@@ -102,15 +352,23 @@ def zonal_statistics(index_array, zones, index_type, valid=None, n_zones=None, w
     records = np.zeros(nz, dtype=_ffi.STATS_DTYPE)
     medians = np.zeros((nz, 2), dtype=np.float32)
     bad = C.c_int64(-1)
-    try:
-        _ffi.call("lars_h_zonal_stats_f32", _ffi.ptr(x), _ffi.ptr(lab), lab.dtype.itemsize, _ffi.ptr(valid_arr), h, w, nz,
-                  np.float32(threshold), int(bool(want_hist)), _ffi.ptr(records), _ffi.ptr(medians), C.byref(bad))
-    except _ffi.LarsError:
-        if bad.value > 0:
-            raise _bad_labels(who, bad.value, nz) from None
-        raise
+    extra = {}
+    if polys:
+        made = polys._label_buffer((h, w)) if polys.want_labels else None
+        _ffi.call("lars_h_zonal_stats_polygons_f32", _ffi.ptr(x), *polys._head(), _ffi.ptr(valid_arr), h, w, np.float32(threshold),
+                  int(bool(want_hist)), _ffi.ptr(records), _ffi.ptr(medians), _ffi.ptr(made), made.dtype.itemsize if polys.want_labels else 0)
+        if polys.want_labels:
+            extra["labels"] = made
+    else:
+        try:
+            _ffi.call("lars_h_zonal_stats_f32", _ffi.ptr(x), _ffi.ptr(lab), lab.dtype.itemsize, _ffi.ptr(valid_arr), h, w, nz,
+                      np.float32(threshold), int(bool(want_hist)), _ffi.ptr(records), _ffi.ptr(medians), C.byref(bad))
+        except _ffi.LarsError:
+            if bad.value > 0:
+                raise _bad_labels(who, bad.value, nz) from None
+            raise
     count, out = _figures(records, medians, want_hist)
-    return {"zone": np.arange(1, nz + 1, dtype=np.int64), "pixels": count, **out}
+    return {"zone": np.arange(1, nz + 1, dtype=np.int64), "pixels": count, **out, **extra}
 
 
 def process_image_zones(img_array, zones, valid=None, nodata=None, n_zones=None, indices=_ffi.INDEX_NAMES, white_balance=True,
@@ -126,15 +384,22 @@ def process_image_zones(img_array, zones, valid=None, nodata=None, n_zones=None,
     p = _picture(who, who, img_array, list(indices), white_balance, want_arrays, bool(want_hist), want_rgba, False, valid, nodata,
                  need_index="zone statistics need at least one index")
     indices = p.indices
-    lab, nz = _labels(zones, (p.h, p.w), n_zones, who)
+    polys = _zone_source(zones, n_zones, who)
+    lab, nz = (None, len(polys)) if polys else _labels(zones, (p.h, p.w), n_zones, who)
     records = np.zeros((3, nz), dtype=_ffi.STATS_DTYPE)
     medians = np.zeros((3, nz, 2), dtype=np.float32)
     nvalid, bad = C.c_int64(-1), C.c_int64(-1)
     p_rgba, p_lut = _ffi.ptr3(p.rgbas), _ffi.ptr3(p.luts)
+    made = polys._label_buffer((p.h, p.w)) if polys and polys.want_labels else None
     try:
-        _ffi.call("lars_h_process_image_zones", *p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha),
-                  int(p.nodata is not None), p.nodata or 0, C.byref(nvalid), _ffi.ptr(lab), lab.dtype.itemsize, nz, _ffi.ptr(records),
-                  _ffi.ptr(medians), C.byref(bad))
+        if polys:
+            _ffi.call("lars_h_process_image_zones_polygons", *p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha),
+                      int(p.nodata is not None), p.nodata or 0, C.byref(nvalid), *polys._head(), _ffi.ptr(records), _ffi.ptr(medians),
+                      _ffi.ptr(made), made.dtype.itemsize if made is not None else 0)
+        else:
+            _ffi.call("lars_h_process_image_zones", *p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha),
+                      int(p.nodata is not None), p.nodata or 0, C.byref(nvalid), _ffi.ptr(lab), lab.dtype.itemsize, nz, _ffi.ptr(records),
+                      _ffi.ptr(medians), C.byref(bad))
     except _ffi.LarsError:
         if nvalid.value == 0:
             raise ValueError("process_image: no valid pixel") from None
@@ -143,6 +408,8 @@ def process_image_zones(img_array, zones, valid=None, nodata=None, n_zones=None,
         raise
     result = _picture_result(p, want_hist, want_rgba, False, valid_pixels=nvalid.value)
     result["zones"] = {"zone": np.arange(1, nz + 1, dtype=np.int64)}
+    if made is not None:
+        result["zones"]["labels"] = made
     for t in indices:
         result["zones"]["pixels"], result["zones"][t] = _figures(records[INDEX_IDS[t]], medians[INDEX_IDS[t]], want_hist)
     return result

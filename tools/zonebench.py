@@ -18,10 +18,24 @@ alternating ``--rounds`` times in one process (median of the rounds' medians, th
 
 ``--sweep`` times the zones call on ``large`` and ``one`` with the knob zone_split_pixels at every power of two from 2^10 to
 2^24 and at 2^30 (no zone is split), the same alternation, and reports per layout each value's time over the best and the spread
-of the rounds.  ``--parent-lib PATH`` measures process_image and process_image_masked in fresh child processes, alternating
-between this build's library and the parent commit's.
+of the rounds.  ``--parent-lib PATH`` measures process_image, process_image_masked and process_image_zones with a label raster
+(``plots``) in fresh child processes, alternating between this build's library and the parent commit's.
 
-    python tools/zonebench.py [--sizes 2048x1536,4096x4096] [--reps 7] [--rounds 3] [--sweep] [--parent-lib PATH] [--json out.json]
+``--polygons`` times the zones made from outlines (csrc/zone_raster.hip) instead, by the same rules.  Layouts: ``plots`` 2000 rotated
+four-vertex plots on about 60 % of the raster, ``large`` 40 rotated zones, ``outline`` one polygon of 10 000 vertices over most of the
+raster.  Legs:
+
+  polygons    process_image_zones(img, polygons): the list is checked and packed on the host in every call
+  packed      process_image_zones(img, Polygons(polygons)) with the packing done once beforehand, as a time series would
+  labels      process_image_zones(img, labels) with the labels made beforehand: the call before this feature, and a floor that
+              polygons cannot beat by more than the saved upload
+  pillow      what a caller without GDAL does today: an ImageDraw.polygon loop into an I;16 image, then ``labels``.  Timing only:
+              Pillow paints the edge pixels of both neighbours, its raster is not the definition's
+  rasterize   rasterize_zones(polygons, shape) alone (labels downloaded), for the share of the rasteriser
+
+``--layouts ring_thin`` / ``ring_full`` (with ``--zones-only``, under the kernel trace) give the share of the label writes in k_zr_fill.
+
+    python tools/zonebench.py [--sizes 2048x1536,4096x4096] [--reps 7] [--rounds 3] [--sweep] [--polygons] [--parent-lib PATH] [--json out.json]
 
 Kernel times come from a separate run:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/zonebench.py --zones-only --sizes 4096x4096
@@ -40,9 +54,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from lars_image_processing_amd import _ffi  # noqa: E402
 
-ZONE_SYMBOLS = ("lars_d_zone_count", "lars_d_zone_offsets", "lars_d_zone_scatter", "lars_d_zone_stats", "lars_h_zonal_stats_f32",
-                "lars_h_process_image_zones")
+POLYGON_SYMBOLS = ("lars_zone_rasterize_scratch_bytes", "lars_d_zone_rasterize", "lars_d_zone_labels_narrow", "lars_h_rasterize_zones",
+                   "lars_h_zonal_stats_polygons_f32", "lars_h_process_image_zones_polygons")
 LAYOUTS = ("plots", "large", "one")
+POLYGON_LAYOUTS = ("plots", "large", "outline")
 SWEEP = [2 ** k for k in range(10, 25)] + [2 ** 30]
 
 
@@ -61,6 +76,81 @@ def labels(layout, h, w):
     if layout == "large":
         return ((y * 5 // h) * 8 + x * 8 // w + 1).astype(np.uint8), 40
     return np.ones((h, w), dtype=np.uint8), 1
+
+
+def rotated_grid(ny, nx, h, w, fill, angle):
+    """``ny * nx`` rectangles of ``fill`` of their cell's area, turned by ``angle`` about the raster's centre (some end up cut by the border)."""
+    side = fill ** 0.5
+    cy, cx = np.mgrid[0:ny, 0:nx]
+    y0, x0 = cy.ravel() * h / ny, cx.ravel() * w / nx
+    corners = np.array([(0.0, 0.0), (1.0, 0.0), (1.0, 1.0), (0.0, 1.0)])
+    x = x0[:, None] + corners[:, 0] * side * w / nx - w / 2
+    y = y0[:, None] + corners[:, 1] * side * h / ny - h / 2
+    c, s = np.cos(angle), np.sin(angle)
+    return list(np.stack((x * c - y * s + w / 2, x * s + y * c + h / 2), axis=2))
+
+
+def polygons_of(layout, h, w):
+    if layout == "plots":
+        return rotated_grid(40, 50, h, w, 0.6, np.radians(7.0))
+    if layout == "large":
+        return rotated_grid(5, 8, h, w, 0.9, np.radians(7.0))
+    k = np.arange(10000)                                       # a wavy outline over most of the raster
+    a = k * (2 * np.pi / 10000)
+    r = 0.46 + 0.03 * np.sin(37 * a)
+    outline = np.stack((w / 2 + r * w * np.cos(a), h / 2 + r * h * np.sin(a)), axis=1)
+    if layout == "outline":
+        return [outline]
+    # the outline with a hole: the same edges, rows and words for the kernel, but few (ring_thin) or nearly all (ring_full) of the
+    # pixels written -- the difference of their kernel times is the time of the atomicMax writes
+    scale = {"ring_thin": 0.98, "ring_full": 0.02}[layout]
+    centre = np.array((w / 2, h / 2))
+    return [[outline, centre + (outline - centre) * scale]]
+
+
+def pillow_labels(polygons, h, w):
+    from PIL import Image, ImageDraw
+    im = Image.new("I;16", (w, h), 0)
+    draw = ImageDraw.Draw(im)
+    for k, p in enumerate(polygons):
+        draw.polygon([tuple(v) for v in p], fill=k + 1)
+    return np.asarray(im)
+
+
+def polygon_legs(lars, args, out):
+    for w, h in sizes_of(args.sizes):
+        img = picture(h, w)
+        size_row = {"pixels": h * w, "layouts": {}}
+        for layout in (args.layouts.split(",") if args.layouts else POLYGON_LAYOUTS):
+            polys = polygons_of(layout, h, w)
+            packed = lars.Polygons(polys)
+            lab = lars.rasterize_zones(packed, (h, w))
+            nz = len(polys)
+            row = {"zones": nz, "vertices": int(len(packed.verts)), "label_type": str(lab.dtype), "covered": float(np.count_nonzero(lab) / lab.size)}
+            if args.zones_only:
+                for _ in range(2):
+                    lars.process_image_zones(img, packed)
+                size_row["layouts"][layout] = row
+                continue
+            legs = {"polygons": lambda: lars.process_image_zones(img, polys),
+                    "packed": lambda: lars.process_image_zones(img, packed),
+                    "labels": lambda: lars.process_image_zones(img, lab, n_zones=nz),
+                    "pillow": lambda: lars.process_image_zones(img, pillow_labels(polys, h, w), n_zones=nz),
+                    "rasterize": lambda: lars.rasterize_zones(packed, (h, w))}
+            for name, rounds in alternate(legs, args.reps, args.rounds).items():
+                row[name] = summary(rounds)
+            row["polygons_over_labels"] = row["polygons"]["ms"] / row["labels"]["ms"]
+            row["packed_over_labels"] = row["packed"]["ms"] / row["labels"]["ms"]
+            row["pillow_over_polygons"] = row["pillow"]["ms"] / row["polygons"]["ms"]
+            row["pillow_differs_in_pixels"] = int(np.count_nonzero(pillow_labels(polys, h, w) != lab))
+            a, b = lars.process_image_zones(img, packed), lars.process_image_zones(img, lab, n_zones=nz)     # the timed calls agree
+            assert np.array_equal(a["zones"]["pixels"], b["zones"]["pixels"])
+            for t in ("NDVI", "GNDVI", "NDWI"):
+                assert np.array_equal(a["zones"][t]["median"], b["zones"][t]["median"], equal_nan=True)
+            del a, b
+            size_row["layouts"][layout] = row
+            print(f"{w}x{h} polygons {layout}", json.dumps(row), flush=True)
+        out["sizes"][f"{w}x{h}"] = size_row
 
 
 def median_ms(fn, reps):
@@ -88,17 +178,19 @@ def sizes_of(text):
 
 
 def child(args):
-    """The calls without zones alone, on the library LARS_HIP_LIB names (the parent's lacks the zone entry points)."""
+    """The calls that exist on both sides alone, on the library LARS_HIP_LIB names (the parent's lacks the polygon entry points)."""
     if args.child == "parent":
-        for name in ZONE_SYMBOLS:
+        for name in POLYGON_SYMBOLS:
             _ffi.SIGNATURES.pop(name, None)
     import lars_image_processing_amd as lars
     out = {}
     for w, h in sizes_of(args.sizes):
         img = picture(h, w)
         ones = np.ones((h, w), dtype=bool)
+        lab, nz = labels("plots", h, w)
         out[f"{w}x{h}"] = {"unmasked": median_ms(lambda: lars.process_image(img), args.reps),
-                           "masked": median_ms(lambda: lars.process_image_masked(img, valid=ones), args.reps)}
+                           "masked": median_ms(lambda: lars.process_image_masked(img, valid=ones), args.reps),
+                           "zones": median_ms(lambda: lars.process_image_zones(img, lab, n_zones=nz), args.reps)}
     print("CHILD " + json.dumps(out), flush=True)
 
 
@@ -123,6 +215,8 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--sweep", action="store_true", help="also time zone_split_pixels at every power of two on the layouts large and one")
+    ap.add_argument("--polygons", action="store_true", help="the legs of the zones made from polygons instead of the label-raster layouts")
+    ap.add_argument("--layouts", help="with --polygons: these layouts only, comma separated (also ring_thin, ring_full: see polygons_of)")
     ap.add_argument("--parent-lib", help="liblars_hip.so built from the parent commit")
     ap.add_argument("--zones-only", action="store_true", help="the zones call alone, once per layout after a warm-up (for a kernel trace)")
     ap.add_argument("--json", help="also write the figures to this file")
@@ -136,7 +230,9 @@ def main():
     print("device:", _ffi.device_name(), flush=True)
     out = {"device": _ffi.device_name(), "reps": args.reps, "rounds": args.rounds, "zone_split_pixels": _ffi.get_tuning("zone_split_pixels"),
            "request": "three indices, statistics, float32 planes, corrected image; one row per zone and index", "sizes": {}}
-    for w, h in sizes_of(args.sizes):
+    if args.polygons:
+        polygon_legs(lars, args, out)
+    for w, h in ([] if args.polygons else sizes_of(args.sizes)):
         img = picture(h, w)
         ones = np.ones((h, w), dtype=bool)
         size_row = {"pixels": h * w, "layouts": {}}
@@ -194,7 +290,7 @@ def main():
             rounds["parent_lib"].append(run_child("parent", os.path.abspath(args.parent_lib), args))
         for key, size_row in out["sizes"].items():
             cmp_row = {}
-            for call in ("unmasked", "masked"):
+            for call in ("unmasked", "masked", "zones"):
                 for which, runs in rounds.items():
                     cmp_row[f"{which}_{call}"] = summary([r[key][call] for r in runs])
                 cmp_row[f"this_over_parent_{call}"] = cmp_row[f"this_lib_{call}"]["ms"] / cmp_row[f"parent_lib_{call}"]["ms"]
