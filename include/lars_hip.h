@@ -158,11 +158,19 @@ size_t lars_wb_table_bytes(int dtype);
 /* The whole white-balance pre-pass of a batch in one call (histogram pass(es) + tables), both
  * sample types.  For LARS_U16 the percentiles come from two radix levels (high-byte histograms,
  * then low-byte histograms of the bins that hold the order statistics) instead of a 65536-bin
- * histogram per channel -- usually in ONE full pass: a subsample predicts candidate bins, the pass
- * counts high bytes and the candidates' low bytes together, and only tiles whose exact bins were
- * not among their candidates are recounted.  Scratch comes from the calling thread's library workspace. */
+ * histogram per channel -- usually in ONE full pass: a subsample predicts a window of values around
+ * each percentile, the pass counts the samples below each window and those inside it value by value,
+ * and only tiles with an order statistic outside its window take the two radix passes.  Scratch comes
+ * from the calling thread's library workspace. */
 int lars_d_wb_prepare(const void *tiles, int64_t ntiles, int64_t npix, int channels, int dtype,
                       uint8_t *table, double *percentiles, int rgn_variant, void *stream);
+/* Laboratory / test helper: how the last lars_d_wb_prepare on the calling thread used value windows, once its stream has
+ * finished.  flags[ntiles] = 1 where a rank lay outside its window (or a mark had none) and the tile took the two radix
+ * passes, else 0; windows[ntiles][3][4] = per channel the first value of the 2 % and of the 98 % mark's window and their
+ * widths (lo[0], lo[1], wd[0], wd[1]; a width of 0: no window).  LARS_ERR_INVALID unless that call took the value-window
+ * route over exactly ntiles tiles (LARS_U16, 3 channels, 4-byte aligned tiles of about 258 k pixels or more, u16_hist_impl
+ * other than 1) and no other call on this thread has used the library's scratch since. */
+int lars_u16_window_report(int64_t ntiles, uint32_t *flags, uint32_t *windows);
 
 typedef struct lars_fused_args {
     const void    *tiles;          /* [ntiles][h*w][channels] interleaved R,G,NIR(,...) */

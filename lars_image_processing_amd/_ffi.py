@@ -167,6 +167,7 @@ SIGNATURES = {
     "lars_d_wb_table": (_I, [_P, _I64, _I64, _I, _P, _P, _I, _P]),
     "lars_wb_table_bytes": (_SZ, [_I]),
     "lars_d_wb_prepare": (_I, [_P, _I64, _I64, _I, _I, _P, _P, _I, _P]),
+    "lars_u16_window_report": (_I, [_I64, _P, _P]),
     "lars_d_fused": (_I, [C.POINTER(FusedArgs)]),
     "lars_d_stats_begin": (_I, [_P, _I64, _U32, _P]),
     "lars_d_stats_end": (_I, [_P, _I64, _U32, _I64, _P]),

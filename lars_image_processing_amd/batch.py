@@ -176,6 +176,18 @@ class TileBatch:
         self._rgn_variant = int(rgn_variant)
         return self
 
+    def u16_window_report(self):
+        """(flags[ntiles], windows[ntiles, 3, 4]) of the last ``compute_wb_tables`` of a uint16 batch on this thread, after its stream
+        has finished: ``flags[i]`` 1 where tile i's value windows missed and the two radix passes served it, ``windows[i, c]`` =
+        (lo of the 2 % mark's window, lo of the 98 % mark's, and their widths; width 0: no window).  Raises unless that pass took
+        the value-window route (``lars_u16_window_report``)."""
+        if self.code != _ffi.U16:
+            raise _ffi.LarsError(-1, "lars_u16_window_report: a uint8 batch's pre-pass does not take the value-window route")
+        flags = np.zeros(self.ntiles, np.uint32)
+        windows = np.zeros((self.ntiles, 3, 4), np.uint32)
+        _ffi.call("lars_u16_window_report", self.ntiles, _ffi.ptr(flags), _ffi.ptr(windows))
+        return flags, windows
+
     def _need_channels(self, partial):
         """The host_* getters hand out all three channels: after a one-read pass that served NDVI only (or GNDVI / NDWI
         only) the third channel's rows were never computed -- refuse unless the caller asks for them as they are."""

@@ -28,6 +28,8 @@ struct ThreadCtx {
     size_t ws_bytes = 0;
     void *scratch = nullptr;   // small device scratch of the device entry points
     size_t scratch_bytes = 0;
+    int64_t u16_win_tiles = 0; // tiles of the last lars_d_wb_prepare if it took the value-window route and nothing has reserved the
+                               // scratch since (lars_u16_window_report reads its flags and windows there), else 0
 };
 
 int ensure_ctx(ThreadCtx **out);                 // initialises device 0 on first use

@@ -205,7 +205,7 @@ __global__ __launch_bounds__(1024) void k_hist_u16_lo(const uint16_t *__restrict
 // ---- one full pass on VALUE windows (round 5): no histogram per sample at all ---------------------------------------------------
 // np.percentile needs, per channel, the order statistics at ranks floor((n - 1) q) and the next one for q = 2 % and 98 %.  A 1/64
 // subsample (12-bit histograms: k_u16_sample12) says where in the 16-bit range each mark lies to within a few dozen values
-// (k_u16_window: the sample's order statistics six standard deviations of the sampling error either side of the mark, rounded outwards
+// (k_u16_window: the sample's order statistics four standard deviations of the sampling error either side of the mark, rounded outwards
 // to the sample histogram's 16-value bins); the full pass then only has to know, per channel and mark, HOW MANY samples lie below the
 // window and the histogram of the samples INSIDE it (k_u16_count_win).  Below: the borrow of one subtraction, added to the lane's
 // counter -- v_subrev_co_u32 d, vcc, lo << 16, key; v_addc_co_u32 -- where key is the dword itself for its high sample and the dword
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(1024) void k_u16_sample12(const uint16_t *__restric
         if (s_h[i]) atomicAdd(&g[i], s_h[i]);
 }
 
-// test_wrong (lars_set_tuning("u16_hist_impl", 3)): windows of 64 values at 0, so that (almost) every tile is flagged
+// test_wrong (lars_set_tuning("u16_hist_impl", 3)): windows of 16 values at 0, so that (almost) every tile is flagged
 __global__ __launch_bounds__(256) void k_u16_window(const unsigned int *__restrict__ hist12, U16Win *__restrict__ win, int test_wrong)
 {
     constexpr int PER = U16_SAMPLE_BINS / 256;              // 16 bins per thread
@@ -530,6 +530,28 @@ extern "C" size_t lars_wb_table_bytes(int dtype)
     return dtype == LARS_U16 ? (size_t)LARS_U16_BLOB_BYTES : (size_t)768;
 }
 
+// The scratch of the uint16 pre-pass, cut once for the pre-pass and for lars_u16_window_report: offsets of 256-byte aligned stretches.
+// hi, lo, flags come first and s12, below, winhist next, so that one memset clears what either route counts into.
+struct U16Scratch { size_t hi, lo, flags, s12, below, winhist, picks, win, total; };
+
+static U16Scratch u16_scratch_layout(int64_t ntiles)
+{
+    const size_t n = (size_t)ntiles;
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; };
+    U16Scratch L;
+    L.hi = take(n * 768 * 4);                              // [ntiles][3][256] high-byte counts
+    L.lo = take(n * 3 * 4 * 256 * 4);                      // [ntiles][3][4 slots][256] low-byte counts
+    L.flags = take(n * 4);                                 // [ntiles]: 1 = the tile takes the classic passes
+    L.s12 = take(n * 3 * U16_SAMPLE_BINS * 4);             // [ntiles][3][4096] counts of the subsample
+    L.below = take(n * 6 * 4);                             // [ntiles][3][2] samples below each window
+    L.winhist = take(n * 3 * 2 * U16_WIN_MAX * 4);         // [ntiles][3][2][1024] counts inside each window
+    L.picks = take(n * 3 * sizeof(U16Pick));
+    L.win = take(n * 3 * sizeof(U16Win));
+    L.total = off + 512;
+    return L;
+}
+
 // One call for the whole white-balance pre-pass of a batch, both sample types.
 extern "C" int lars_d_wb_prepare(const void *tiles, int64_t ntiles, int64_t npix, int channels, int dtype, uint8_t *table,
                                  double *percentiles, int rgn_variant, void *stream)
@@ -539,6 +561,7 @@ extern "C" int lars_d_wb_prepare(const void *tiles, int64_t ntiles, int64_t npix
     if (!tiles || !table || ntiles <= 0 || npix <= 0 || channels < 3 || ntiles > 65535)
         return fail(LARS_ERR_INVALID, "lars_d_wb_prepare: bad arguments");
     hipStream_t s = pick_stream(c, stream);
+    c->u16_win_tiles = 0;
     if (dtype == LARS_U8) {
         LARS_TRY(scratch_reserve(c, (size_t)ntiles * 768 * sizeof(uint32_t)));
         uint32_t *hist = static_cast<uint32_t *>(c->scratch);
@@ -546,22 +569,17 @@ extern "C" int lars_d_wb_prepare(const void *tiles, int64_t ntiles, int64_t npix
         return lars_d_wb_table(hist, ntiles, npix, dtype, table, percentiles, rgn_variant, s);
     }
     if (dtype != LARS_U16) return fail(LARS_ERR_INVALID, "lars_d_wb_prepare: dtype");
-    const size_t hi_bytes = (size_t)ntiles * 768 * 4, pick_bytes = (size_t)ntiles * 3 * sizeof(U16Pick),
-                 lo_bytes = (size_t)ntiles * 3 * 4 * 256 * 4,
-                 flag_bytes = (size_t)ntiles * 4, s12_bytes = (size_t)ntiles * 3 * U16_SAMPLE_BINS * 4,
-                 below_bytes = (size_t)ntiles * 6 * 4, wh_bytes = (size_t)ntiles * 3 * 2 * U16_WIN_MAX * 4, win_bytes = (size_t)ntiles * 3 * sizeof(U16Win);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    LARS_TRY(scratch_reserve(c, up(hi_bytes) + up(pick_bytes) + up(lo_bytes) + up(flag_bytes) + up(s12_bytes) + up(below_bytes) +
-                                    up(wh_bytes) + up(win_bytes) + 512));
+    const U16Scratch L = u16_scratch_layout(ntiles);
+    LARS_TRY(scratch_reserve(c, L.total));
     char *p = static_cast<char *>(c->scratch);
-    unsigned int *hi = reinterpret_cast<unsigned int *>(p);                  p += up(hi_bytes);
-    unsigned int *lo = reinterpret_cast<unsigned int *>(p);                  p += up(lo_bytes);
-    unsigned int *flags = reinterpret_cast<unsigned int *>(p);               p += up(flag_bytes);
-    unsigned int *s12 = reinterpret_cast<unsigned int *>(p);                 p += up(s12_bytes);
-    unsigned int *below = reinterpret_cast<unsigned int *>(p);               p += up(below_bytes);
-    unsigned int *winhist = reinterpret_cast<unsigned int *>(p);             p += up(wh_bytes);
-    U16Pick *picks = reinterpret_cast<U16Pick *>(p);                         p += up(pick_bytes);
-    U16Win *win = reinterpret_cast<U16Win *>(p);
+    unsigned int *hi = reinterpret_cast<unsigned int *>(p + L.hi);
+    unsigned int *lo = reinterpret_cast<unsigned int *>(p + L.lo);
+    unsigned int *flags = reinterpret_cast<unsigned int *>(p + L.flags);
+    unsigned int *s12 = reinterpret_cast<unsigned int *>(p + L.s12);
+    unsigned int *below = reinterpret_cast<unsigned int *>(p + L.below);
+    unsigned int *winhist = reinterpret_cast<unsigned int *>(p + L.winhist);
+    U16Pick *picks = reinterpret_cast<U16Pick *>(p + L.picks);
+    U16Win *win = reinterpret_cast<U16Win *>(p + L.win);
     const uint16_t *t16 = static_cast<const uint16_t *>(tiles);
     const bool fast = channels == 3 && (ntiles == 1 || (npix & 3) == 0) && ((reinterpret_cast<uintptr_t>(tiles) & 3) == 0) &&
                       (long long)npix * 6 < (1ll << 30);
@@ -575,7 +593,7 @@ extern "C" int lars_d_wb_prepare(const void *tiles, int64_t ntiles, int64_t npix
     if (fast && cap >= 64 && impl != 1) {
         // ONE full pass on value windows (round 5): per channel and mark the count of the samples below a predicted window and the histogram
         // inside it; a rank outside its window flags the tile, and only flagged tiles take the two classic passes (all of them with impl 3)
-        LARS_HIP_TRY(hipMemsetAsync(hi, 0, up(hi_bytes) + up(lo_bytes) + up(flag_bytes) + up(s12_bytes) + up(below_bytes) + up(wh_bytes), s));
+        LARS_HIP_TRY(hipMemsetAsync(hi, 0, L.picks, s));                  // hi, lo, flags, s12, below, winhist are contiguous
         hipLaunchKernelGGL(k_u16_sample12, grid, dim3(1024), 0, s, t16, (long long)npix, s12, 64);     // 1 / 64 of the samples: 1 M per 8192 x 8192 tile and channel
         hipLaunchKernelGGL(k_u16_window, per_channel, dim3(256), 0, s, s12, win, impl == 3 ? 1 : 0);
         hipLaunchKernelGGL(k_u16_count_win, grid, dim3(1024), 0, s, t16, (long long)npix, win, below, winhist);
@@ -584,9 +602,10 @@ extern "C" int lars_d_wb_prepare(const void *tiles, int64_t ntiles, int64_t npix
         hipLaunchKernelGGL(k_u16_pick, per_channel, dim3(256), 0, s, hi, (long long)npix, picks, flags);
         hipLaunchKernelGGL((k_hist_u16_lo<true>), grid, dim3(1024), 0, s, t16, (long long)npix, channels, picks, lo, flags);
         hipLaunchKernelGGL(k_wb_table_u16, per_channel, dim3(256), 0, s, lo, picks, table, percentiles, rgn_variant, 4, flags);
+        c->u16_win_tiles = ntiles;                         // lars_u16_window_report: flags and windows of this many tiles are in the scratch
         return launch_check("lars_d_wb_prepare (value windows)");
     }
-    LARS_HIP_TRY(hipMemsetAsync(hi, 0, up(hi_bytes) + up(lo_bytes) + up(flag_bytes), s));     // hi, lo, flags are contiguous
+    LARS_HIP_TRY(hipMemsetAsync(hi, 0, L.s12, s));                        // hi, lo, flags are contiguous
     if (fast) hipLaunchKernelGGL(k_hist_u16_hi, grid, dim3(1024), 0, s, t16, (long long)npix, hi, 1, (const unsigned int *)nullptr);
     else hipLaunchKernelGGL(k_hist_u16_hi_generic, dim3((unsigned)want * 4, (unsigned)ntiles), dim3(256), 0, s, t16, (long long)npix, channels, hi);
     hipLaunchKernelGGL(k_u16_pick, per_channel, dim3(256), 0, s, hi, (long long)npix, picks, (const unsigned int *)nullptr);
@@ -594,4 +613,23 @@ extern "C" int lars_d_wb_prepare(const void *tiles, int64_t ntiles, int64_t npix
     else hipLaunchKernelGGL((k_hist_u16_lo<false>), grid, dim3(1024), 0, s, t16, (long long)npix, channels, picks, lo, (const unsigned int *)nullptr);
     hipLaunchKernelGGL(k_wb_table_u16, per_channel, dim3(256), 0, s, lo, picks, table, percentiles, rgn_variant, 4, (const unsigned int *)nullptr);
     return launch_check("lars_d_wb_prepare");
+}
+
+// How the last lars_d_wb_prepare on the calling thread used value windows (after its stream has finished): flags[ntiles] = 1 where the
+// tile took the classic passes, windows[ntiles][3][4] = lo[0], lo[1], wd[0], wd[1] of every channel's U16Win.  Laboratory / test helper.
+extern "C" int lars_u16_window_report(int64_t ntiles, uint32_t *flags, uint32_t *windows)
+{
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (ntiles <= 0 || !flags || !windows) return fail(LARS_ERR_INVALID, "lars_u16_window_report: bad arguments");
+    if (c->u16_win_tiles != ntiles)
+        return fail(LARS_ERR_INVALID, "lars_u16_window_report: the last lars_d_wb_prepare on this thread did not take the value-window "
+                                      "route over %lld tiles (it %s)", (long long)ntiles,
+                    c->u16_win_tiles ? "covered another number of tiles" : "took another route, or the scratch has been used since");
+    static_assert(sizeof(U16Win) == 4 * sizeof(uint32_t), "windows[][3][4] is U16Win as it stands");
+    const U16Scratch L = u16_scratch_layout(ntiles);
+    const char *p = static_cast<const char *>(c->scratch);
+    LARS_HIP_TRY(hipMemcpy(flags, p + L.flags, (size_t)ntiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    LARS_HIP_TRY(hipMemcpy(windows, p + L.win, (size_t)ntiles * 3 * sizeof(U16Win), hipMemcpyDeviceToHost));
+    return LARS_OK;
 }

@@ -367,6 +367,7 @@ def test_uint16_percentiles_one_pass_and_its_recount(lars):
     """lars_d_wb_prepare for uint16 tiles: ONE full pass on value windows predicted from a subsample (the count of the samples below
     each window and the histogram inside it), the two radix passes, and np.percentile; with windows that miss on purpose every tile
     takes the two passes after the one.  Heavy-tailed, constant and few-level channels included, and marks next to a bin boundary."""
+    import u16_window_model
     from lars_image_processing_amd import _ffi
     rng = np.random.default_rng(21)
     h, w = 512, 768
@@ -391,6 +392,11 @@ def test_uint16_percentiles_one_pass_and_its_recount(lars):
             b.table.zero(); b.percentiles.zero()
             b.compute_wb_tables()
             _ffi.call("lars_synchronize", None)
+            if impl != 1:
+                # which tiles the windows served, by the model of the predictor (tests/u16_window_model.py): with 5 the tiles whose
+                # prediction really misses, with 3 every tile except those whose marks really lie in [0, 16)
+                want_flags = [u16_window_model.tile_flag(t, test_wrong=impl == 3) for t in tiles]
+                assert b.u16_window_report()[0].tolist() == want_flags, impl
         got[impl] = (b.host_percentiles().tobytes(), b.table.download(np.uint8, (b.ntiles, b.table_bytes)).tobytes())
     assert got[1] == got[3] == got[5]
     pcts = b.host_percentiles()
