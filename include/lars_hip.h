@@ -350,6 +350,8 @@ int lars_d_synth_u8(uint8_t *tiles, int64_t ntiles, int64_t first_tile, int64_t 
  * "selq_window" 1 (one-pass medians)|0 (always two select passes)|2 (wrong windows: exercises the fallback), "selq_list_wgs"
  * workgroups per select pass over the tiles a window missed (0 = 2048), "jpeg_subseq_bits" 32 .. 65536: the bits of entropy data one
  * lane of the JPEG decoder takes (lars_d_decode_jpeg_u8; 32 = the longest code plus its extra bits, rounded up).
+ * The knob load_policy (0 .. 2) is the cache policy of the kernels' streaming tile loads: 0 = each kernel's measured choice
+ * (profiles/load_policy_kernels.txt), 1 = plain loads everywhere, 2 = non-temporal (nt) loads everywhere.
  * Results never depend on them.  Read-only:
  * "last_fused_kernel" = the kernel family the last lars_d_fused launched (1 k_fused_u8c3, 2 k_fused_v2, 3 its uint16 form,
  * 4 k_fused_generic: one pixel per lane, 5 k_fused_u8c3 for RGBA uint8 tiles), "jpeg_last_rounds" = the synchronisation rounds

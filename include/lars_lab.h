@@ -23,7 +23,9 @@ int lars_lab_free(void *dptr);
  * (traffic = 2 x bytes), 3 writes 16 B/lane.  src/dst are device buffers of `bytes`.  Further kinds (csrc/lab/probe.hip):
  * 5-19 shapes of the 12 B read / 48 B written mix, 31-34 / 41-44 shared readers of one chunk, 60-64 the two passes of a
  * tile interleaved tile by tile in one launch (unroll = read-only blocks per tile, blocks = plane-writing blocks per tile,
- * bytes = ntiles x 48 MiB of source, dst = 64 tile slots x 3 planes x 64 MiB; tools/lab/twopass.py). */
+ * bytes = ntiles x 48 MiB of source, dst = 64 tile slots x 3 planes x 64 MiB; tools/lab/twopass.py), 200-247 the hot path's tile
+ * loads under each cache policy (200 + 16 x condition + 4 x shape + policy: read only | the 12 B : 48 B mix | shared readers;
+ * 12 B | 16 B + 8 B | 16 B per lane; plain | nt | sc1 | nt sc1; tools/lab/loadpolicy.py). */
 int lars_d_probe(int kind, int unroll, int blocks, const void *src, void *dst, int64_t bytes, void *stream);
 /* One host <-> device copy two ways (tools/pciebench.py): mode 0 hipMemcpy, 1 hipMemcpyAsync on the calling thread's (non-blocking) library
  * stream + hipStreamSynchronize -- what the host entry points do.  to_device != 0: host -> device. */

@@ -131,6 +131,7 @@ struct Tuning {
     int hist_impl = 2;         // generation of the channel-histogram kernel
     int nt_stores = 0;         // non-temporal stores for the float32 planes
     int blocks_per_tile = 0;   // workgroups (chunks) per tile; 0 = automatic
+    int load_policy = 0;       // cache policy of the streaming tile loads (stream_load.h): each kernel's measured choice, plain everywhere, or nt everywhere
     int selq_window = 1;       // one-pass medians (select_q.hip): predicted windows, always two passes, or wrong windows (test hook)
     int selq_list_wgs = 0;     // workgroups per launch of the classic select passes over the tiles a window missed (0 = 2048)
     int last_fused_kernel = 0; // read-only: the kernel family lars_d_fused launched last -- 1 k_fused_u8c3, 2 k_fused_v2, 3 uint16, 4 generic, 5 RGBA uint8
@@ -148,6 +149,12 @@ struct Tuning {
                                // select over its segment instead (many workgroups for one zone instead of one)
 };
 Tuning &tuning();
+// Does a kernel whose measured choice is `kernel_default_nt` (profiles/load_policy_kernels.txt) take its tile loads with nt now?
+inline bool stream_loads_nt(bool kernel_default_nt)
+{
+    const int k = tuning().load_policy;
+    return k == 0 ? kernel_default_nt : k == 2;
+}
 
 struct FusedParams;
 #ifndef LARS_V2_STATS_THREADS

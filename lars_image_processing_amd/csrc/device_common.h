@@ -1,6 +1,7 @@
 // Device-side pieces shared by the fused kernels (fused.hip, fused_v2.hip).
 #pragma once
 #include "common.h"
+#include "stream_load.h"
 
 namespace lars {
 

@@ -352,7 +352,8 @@ __device__ inline void acc_flush(Acc a, StatsAccView *rec, double (*s_red)[4], i
 // bench.py modes: planes only 0.774 -> 0.808 of 8 TB/s where its 58 registers would allow eight; one plane + statistics 0.682 ->
 // 0.689; three planes + statistics, four by its registers, unchanged).  The variants with histograms (124 registers) lose 4 %
 // below four and keep what their registers give.
-template <typename PIX, unsigned MASK, bool WB, int STATS, int CH = 3>
+// POLICY: cache policy of the tile loads (stream_load.h).
+template <typename PIX, unsigned MASK, bool WB, int STATS, int CH = 3, int POLICY = LOAD_PLAIN>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(1, (sizeof(PIX) == 1 && CH == 3 && MASK != 0u && STATS <= 1) ? 3 : 8))) void k_fused_u8c3(FusedParams P)
 {
@@ -433,18 +434,17 @@ __attribute__((amdgpu_waves_per_eu(1, (sizeof(PIX) == 1 && CH == 3 && MASK != 0u
     auto load_quad = [&](long long q, unsigned int (&w)[NW]) {
         if (U16) {
             const unsigned int off = (unsigned int)q * 24u;
-            const fu32x4 a4 = __builtin_amdgcn_raw_buffer_load_b128(rsrc16, off, 0, 0);
-            const fu32x2 a2 = __builtin_amdgcn_raw_buffer_load_b64(rsrc16, off + 16u, 0, 0);
+            const fu32x4 a4 = stream_load_b128<POLICY>(rsrc16, off, 0);
+            const fu32x2 a2 = stream_load_b64<POLICY>(rsrc16, off + 16u, 0);
             w[0] = a4.x; w[1] = a4.y; w[2] = a4.z; w[NW - 3] = a4.w; w[NW - 2] = a2.x; w[NW - 1] = a2.y;
         } else if (CH == 4) {
             // r0 g0 n0 a0 | r1 g1 n1 a1 | r2 g2 n2 a2 | r3 g3 n3 a3  ->  r0 g0 n0 r1 | g1 n1 r2 g2 | n2 r3 g3 n3
-            const uint4 p = *reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(base) + q * 16);
-            w[0] = __builtin_amdgcn_perm(p.y, p.x, 0x04020100u);
-            w[1] = __builtin_amdgcn_perm(p.z, p.y, 0x05040201u);
-            w[2] = __builtin_amdgcn_perm(p.w, p.z, 0x06050402u);
+            const sl_u32x3 a = rgba_quad_to_rgb(
+                stream_load_ptr<POLICY>(reinterpret_cast<const sl_u32x4 *>(reinterpret_cast<const uint8_t *>(base) + q * 16)));
+            w[0] = a.x; w[1] = a.y; w[2] = a.z;
         } else {
             const unsigned int *p = reinterpret_cast<const unsigned int *>(reinterpret_cast<const uint8_t *>(base) + q * 12);
-            w[0] = p[0]; w[1] = p[1]; w[2] = p[2];
+            w[0] = stream_load_ptr<POLICY>(p); w[1] = stream_load_ptr<POLICY>(p + 1); w[2] = stream_load_ptr<POLICY>(p + 2);
         }
     };
     auto do_quad = [&](long long q, const unsigned int (&w)[NW]) {
@@ -767,31 +767,39 @@ extern "C" int lars_d_wb_table(const uint32_t *hist, int64_t ntiles, int64_t npi
     return launch_check("lars_d_wb_table");
 }
 
-template <typename PIX, unsigned MASK, bool WB, int CH>
+template <typename PIX, unsigned MASK, bool WB, int CH, int POLICY>
 static void launch_fast_stats(int stats_mode, dim3 grid, hipStream_t s, const FusedParams &P)
 {
-    if (stats_mode == 0) hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 0, CH>), grid, dim3(256), 0, s, P);
-    else if (stats_mode == 1) hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 1, CH>), grid, dim3(256), 0, s, P);
-    else if (stats_mode == 3) hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 3, CH>), grid, dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 2, CH>), grid, dim3(256), 0, s, P);
+    if (stats_mode == 0) hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 0, CH, POLICY>), grid, dim3(256), 0, s, P);
+    else if (stats_mode == 1) hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 1, CH, POLICY>), grid, dim3(256), 0, s, P);
+    else if (stats_mode == 3) hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 3, CH, POLICY>), grid, dim3(256), 0, s, P);
+    else hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 2, CH, POLICY>), grid, dim3(256), 0, s, P);
 }
-template <typename PIX, unsigned MASK, int CH>
+template <typename PIX, unsigned MASK, int CH, int POLICY>
 static void launch_fast_wb(bool wb, int stats_mode, dim3 grid, hipStream_t s, const FusedParams &P)
 {
-    if (wb) launch_fast_stats<PIX, MASK, true, CH>(stats_mode, grid, s, P);
-    else launch_fast_stats<PIX, MASK, false, CH>(stats_mode, grid, s, P);
+    if (wb) launch_fast_stats<PIX, MASK, true, CH, POLICY>(stats_mode, grid, s, P);
+    else launch_fast_stats<PIX, MASK, false, CH, POLICY>(stats_mode, grid, s, P);
 }
 // mask: the template's mask (two-index masks come in as 7, with P.mask = the requested bits)
-template <typename PIX, int CH = 3>
-static void launch_fast(unsigned mask, bool wb, int stats_mode, dim3 grid, hipStream_t s, const FusedParams &P)
+template <typename PIX, int CH, int POLICY>
+static void launch_fast_policy(unsigned mask, bool wb, int stats_mode, dim3 grid, hipStream_t s, const FusedParams &P)
 {
     switch (mask) {
-    case 0u: hipLaunchKernelGGL((k_fused_u8c3<PIX, 0u, true, 0, CH>), grid, dim3(256), 0, s, P); break;
-    case 1u: launch_fast_wb<PIX, 1u, CH>(wb, stats_mode, grid, s, P); break;
-    case 2u: launch_fast_wb<PIX, 2u, CH>(wb, stats_mode, grid, s, P); break;
-    case 4u: launch_fast_wb<PIX, 4u, CH>(wb, stats_mode, grid, s, P); break;
-    default: launch_fast_wb<PIX, 7u, CH>(wb, stats_mode, grid, s, P); break;
+    case 0u: hipLaunchKernelGGL((k_fused_u8c3<PIX, 0u, true, 0, CH, POLICY>), grid, dim3(256), 0, s, P); break;
+    case 1u: launch_fast_wb<PIX, 1u, CH, POLICY>(wb, stats_mode, grid, s, P); break;
+    case 2u: launch_fast_wb<PIX, 2u, CH, POLICY>(wb, stats_mode, grid, s, P); break;
+    case 4u: launch_fast_wb<PIX, 4u, CH, POLICY>(wb, stats_mode, grid, s, P); break;
+    default: launch_fast_wb<PIX, 7u, CH, POLICY>(wb, stats_mode, grid, s, P); break;
     }
+}
+// default_nt: the launch's measured choice (profiles/load_policy_kernels.txt) -- nt tile loads for three uint8 planes + basic statistics,
+// plain loads for everything else
+template <typename PIX, int CH = 3>
+static void launch_fast(unsigned mask, bool wb, int stats_mode, dim3 grid, hipStream_t s, const FusedParams &P, bool default_nt = false)
+{
+    if (stream_loads_nt(default_nt)) launch_fast_policy<PIX, CH, LOAD_NT>(mask, wb, stats_mode, grid, s, P);
+    else launch_fast_policy<PIX, CH, LOAD_PLAIN>(mask, wb, stats_mode, grid, s, P);
 }
 
 extern "C" int lars_d_fused(const lars_fused_args *a)
@@ -866,7 +874,8 @@ extern "C" int lars_d_fused(const lars_fused_args *a)
         ran = 5;
     } else if (fast && a->dtype == LARS_U8) {
         dim3 grid(blocks_per_tile(a->npix / 4 + 1, a->ntiles, 256, 32768), (unsigned)a->ntiles);
-        launch_fast<uint8_t>(tmask, a->wb_table != nullptr, stats_mode, grid, s, P);
+        const bool three_planes_stats = tmask == 7u && stats_mode == 1 && a->wb_table && P.out_index[0] && P.out_index[1] && P.out_index[2];
+        launch_fast<uint8_t>(tmask, a->wb_table != nullptr, stats_mode, grid, s, P, three_planes_stats);
         ran = 1;
     } else if (fast && a->dtype == LARS_U16 && small_tile) {
         dim3 grid(blocks_per_tile(a->npix / 4 + 1, a->ntiles, 256, 32768), (unsigned)a->ntiles);

@@ -64,7 +64,8 @@ __global__ __launch_bounds__(256) void k_quot_check(unsigned int max_den, unsign
 // ---------------------------------------------------------------------------
 // LDS: [3 channels][256 bins][32 copies] u32 = 96 KiB; copy = lane % 32.
 // CH = 4: RGBA tiles, one 16-byte load per lane repacked into the three dwords of an RGB quad (alpha is not counted).
-template <int CH>
+// POLICY: cache policy of the tile loads (stream_load.h).
+template <int CH, int POLICY = LOAD_PLAIN>
 __global__ __launch_bounds__(1024) void k_chan_hist_u8c3_v2(const uint8_t *__restrict__ tiles, long long npix,
                                                             unsigned int *__restrict__ hist)
 {
@@ -93,17 +94,14 @@ __global__ __launch_bounds__(1024) void k_chan_hist_u8c3_v2(const uint8_t *__res
             __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(base), 0, (int)(nquads * 16), 0x00020000);
         const unsigned int voff = (unsigned int)q0 * 16u;
         const unsigned int step_b = (unsigned int)step * 16u;
-        typedef unsigned int u32x4h __attribute__((ext_vector_type(4)));
-        u32x4h w[4];
+        sl_u32x4 w[4];
 #define HQUAD4(p)                                                                                       \
         {                                                                                               \
-            const unsigned int a0 = __builtin_amdgcn_perm((p).y, (p).x, 0x04020100u);                  \
-            const unsigned int a1 = __builtin_amdgcn_perm((p).z, (p).y, 0x05040201u);                  \
-            const unsigned int a2 = __builtin_amdgcn_perm((p).w, (p).z, 0x06050402u);                  \
-            HQUAD(a0, a1, a2)                                                                           \
+            const u32x3 a = rgba_quad_to_rgb(p);                                                        \
+            HQUAD(a.x, a.y, a.z)                                                                        \
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, (unsigned)k * step_b, 0);
+        for (int k = 0; k < 4; ++k) w[k] = stream_load_b128<POLICY>(rsrc, voff, (unsigned)k * step_b);
         long long it = 0;
         unsigned int soff = 4u * step_b;
         for (; it + 4 <= niter - 1; it += 4) {
@@ -111,7 +109,7 @@ __global__ __launch_bounds__(1024) void k_chan_hist_u8c3_v2(const uint8_t *__res
             for (int k = 0; k < 4; ++k) {
                 HQUAD4(w[k])
                 __builtin_amdgcn_sched_barrier(0);
-                w[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff + (unsigned)k * step_b, 0);
+                w[k] = stream_load_b128<POLICY>(rsrc, voff, soff + (unsigned)k * step_b);
                 __builtin_amdgcn_sched_barrier(0);
             }
             soff += 4u * step_b;
@@ -128,7 +126,7 @@ __global__ __launch_bounds__(1024) void k_chan_hist_u8c3_v2(const uint8_t *__res
         const unsigned int step_b = (unsigned int)step * 12u;
         u32x3 w[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = __builtin_amdgcn_raw_buffer_load_b96(rsrc, voff, (unsigned)k * step_b, 0);
+        for (int k = 0; k < 4; ++k) w[k] = stream_load_b96<POLICY>(rsrc, voff, (unsigned)k * step_b);
         long long it = 0;
         unsigned int soff = 4u * step_b;
         for (; it + 4 <= niter - 1; it += 4) {
@@ -136,7 +134,7 @@ __global__ __launch_bounds__(1024) void k_chan_hist_u8c3_v2(const uint8_t *__res
             for (int k = 0; k < 4; ++k) {
                 HQUAD(w[k].x, w[k].y, w[k].z)
                 __builtin_amdgcn_sched_barrier(0);
-                w[k] = __builtin_amdgcn_raw_buffer_load_b96(rsrc, voff, soff + (unsigned)k * step_b, 0);
+                w[k] = stream_load_b96<POLICY>(rsrc, voff, soff + (unsigned)k * step_b);
                 __builtin_amdgcn_sched_barrier(0);
             }
             soff += 4u * step_b;
@@ -526,7 +524,7 @@ __global__ __launch_bounds__(V2Block<OUT>::threads, OUT ? 4 : LARS_V2_STATS_WAVE
         const unsigned int step_b = (unsigned int)stride * 12u;
         u32x3 w[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = __builtin_amdgcn_raw_buffer_load_b96(rsrc, voff, (unsigned)k * step_b, 0);
+        for (int k = 0; k < 4; ++k) w[k] = stream_load_b96<LOAD_PLAIN>(rsrc, voff, (unsigned)k * step_b);
         long long it = 0;
         unsigned int soff = 4u * step_b;
         // every lane's quad is in range while it < niter - 1
@@ -537,7 +535,7 @@ __global__ __launch_bounds__(V2Block<OUT>::threads, OUT ? 4 : LARS_V2_STATS_WAVE
                 // (no copies, no vmcnt(0) at the loop head) and has three quads of work to hide behind
                 do_quad(q0 + (it + k) * stride, w[k].x, w[k].y, w[k].z);
                 __builtin_amdgcn_sched_barrier(0);
-                w[k] = __builtin_amdgcn_raw_buffer_load_b96(rsrc, voff, soff + (unsigned)k * step_b, 0);
+                w[k] = stream_load_b96<LOAD_PLAIN>(rsrc, voff, soff + (unsigned)k * step_b);
                 __builtin_amdgcn_sched_barrier(0);
             }
             soff += 4u * step_b;
@@ -787,8 +785,12 @@ void fused_v2_launch(unsigned mask, bool wb, int stats, bool nt, dim3 grid, hipS
 
 void chan_hist_v2_launch(const uint8_t *tiles, long long npix, unsigned int *hist, dim3 grid, hipStream_t s, int channels)
 {
-    if (channels == 4) hipLaunchKernelGGL(k_chan_hist_u8c3_v2<4>, grid, dim3(1024), 0, s, tiles, npix, hist);
-    else hipLaunchKernelGGL(k_chan_hist_u8c3_v2<3>, grid, dim3(1024), 0, s, tiles, npix, hist);
+    // nt tile loads by default: profiles/load_policy_kernels.txt
+    const bool nt = stream_loads_nt(true);
+    if (channels == 4 && nt) hipLaunchKernelGGL((k_chan_hist_u8c3_v2<4, LOAD_NT>), grid, dim3(1024), 0, s, tiles, npix, hist);
+    else if (channels == 4) hipLaunchKernelGGL((k_chan_hist_u8c3_v2<4, LOAD_PLAIN>), grid, dim3(1024), 0, s, tiles, npix, hist);
+    else if (nt) hipLaunchKernelGGL((k_chan_hist_u8c3_v2<3, LOAD_NT>), grid, dim3(1024), 0, s, tiles, npix, hist);
+    else hipLaunchKernelGGL((k_chan_hist_u8c3_v2<3, LOAD_PLAIN>), grid, dim3(1024), 0, s, tiles, npix, hist);
 }
 
 int quot_check_launch(unsigned int max_den, unsigned long long *mismatches_dev, unsigned int *first_bad_dev, hipStream_t s)

@@ -43,7 +43,9 @@
 namespace lars {
 
 // CH = 4: RGBA tiles, one 16-byte load per lane and step, repacked into the three dwords of an RGB quad.
-template <int DEPTH, int CH = 3>
+// POLICY: cache policy of the tile loads (stream_load.h).  With two streams the second reader of a chunk lives on the first one's lines
+// in the XCD's L2, which nt loads do not leave there (profiles/load_policy_probe.txt): that form stays on plain loads.
+template <int DEPTH, int CH = 3, int POLICY = LOAD_PLAIN>
 __global__ __launch_bounds__(JH_THREADS, 4) void k_joint_count(JointCountParams P)
 {
     // a period is a whole number of ring turns and adds at most 65535 - 16383 = 49152 pixels (12 steps) to any one dword
@@ -171,17 +173,16 @@ __global__ __launch_bounds__(JH_THREADS, 4) void k_joint_count(JointCountParams 
             __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(tile_base + q_begin * (CH * 4)), 0, (int)(nq * (CH * 4)), 0x00020000);
         const unsigned int voff = (unsigned int)tid * (CH * 4u);
         constexpr unsigned int STEP_B = JH_THREADS * CH * 4u;
-        typedef unsigned int u32x4j __attribute__((ext_vector_type(4)));
-        typename std::conditional<CH == 4, u32x4j, u32x3>::type w[DEPTH];
+        typename std::conditional<CH == 4, sl_u32x4, u32x3>::type w[DEPTH];
         auto load = [&](unsigned int soff_b) {
-            if constexpr (CH == 4) return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff_b, 0);
-            else return __builtin_amdgcn_raw_buffer_load_b96(rsrc, voff, soff_b, 0);
+            if constexpr (CH == 4) return stream_load_b128<POLICY>(rsrc, voff, soff_b);
+            else return stream_load_b96<POLICY>(rsrc, voff, soff_b);
         };
         auto count = [&](const auto &v) {
-            if constexpr (CH == 4)
-                do_quad(__builtin_amdgcn_perm(v.y, v.x, 0x04020100u), __builtin_amdgcn_perm(v.z, v.y, 0x05040201u),
-                        __builtin_amdgcn_perm(v.w, v.z, 0x06050402u));
-            else do_quad(v.x, v.y, v.z);
+            if constexpr (CH == 4) {
+                const u32x3 a = rgba_quad_to_rgb(v);
+                do_quad(a.x, a.y, a.z);
+            } else do_quad(v.x, v.y, v.z);
         };
 #pragma unroll
         for (int k = 0; k < DEPTH; ++k) w[k] = load((unsigned)k * STEP_B);
@@ -668,6 +669,9 @@ __global__ __launch_bounds__(JH_THREADS, 8) void k_joint_finish(JointFinishParam
 
 using namespace lars;
 
+// measured choices of the counting kernels' tile loads (profiles/load_policy_kernels.txt)
+static const bool JOINT_ONE_STREAM_NT = true;            // 7 - 10 % on every content class of tools/jointbench.py
+
 // K: chunks per tile.  Enough workgroups to fill the chip (one per CU, a few rounds), at least npix / 2^24 (the 16-bit
 // counters' list bound), chunks of whole steps.
 static int joint_chunks(long long ntiles, long long npix, int S)
@@ -773,7 +777,13 @@ extern "C" int lars_d_stats_joint(const lars_fused_args *a, int white_balance, i
     // (profiles/r04_joint_depths.txt), although the bare two-reader pattern gains 5 % from 6 to 12 (profiles/r04_shared_readers_depths.txt)
     const int depth = tuning().joint_depth;
     auto count_full = [&]() {
-#define LARS_JOINT(DD, CC) hipLaunchKernelGGL((k_joint_count<DD, CC>), dim3((unsigned)nwg), dim3(JH_THREADS), 0, s, C)
+    // the two-reader form keeps plain loads; the one-stream form takes its own choice (profiles/load_policy_kernels.txt)
+    const bool nt = stream_loads_nt(S == 2 ? false : JOINT_ONE_STREAM_NT);
+#define LARS_JOINT(DD, CC)                                                                                                          \
+    do {                                                                                                                            \
+        if (nt) hipLaunchKernelGGL((k_joint_count<DD, CC, LOAD_NT>), dim3((unsigned)nwg), dim3(JH_THREADS), 0, s, C);               \
+        else hipLaunchKernelGGL((k_joint_count<DD, CC, LOAD_PLAIN>), dim3((unsigned)nwg), dim3(JH_THREADS), 0, s, C);               \
+    } while (0)
         if (c4) LARS_JOINT(6, 4);
         else if (depth == 4) LARS_JOINT(4, 3);
         else if (depth == 8) LARS_JOINT(8, 3);

@@ -220,7 +220,8 @@ __device__ inline unsigned int jw_addr(unsigned int d, unsigned int two)
 
 // NWIN: NIR has a window as well (JointWin mode 2): rows of win.pitch dwords, cell n' = clamp(n - lo_n) in dword n' mod half, half n' >= half.
 // Three more packed instructions per pixel pair than the NIR-whole form, whose rows are 128 + 5 dwords and whose half is bit 7 of n.
-template <int DEPTH, int CH = 3, bool NWIN = false>
+// POLICY: cache policy of the tile loads (stream_load.h).
+template <int DEPTH, int CH = 3, bool NWIN = false, int POLICY = LOAD_PLAIN>
 __global__ __launch_bounds__(JH_THREADS, 4) void k_joint_count_win(JointCountParams P)
 {
     // a period is a whole number of ring turns and adds at most 65535 - 4095 = 61440 pixels (15 steps) to any one dword
@@ -366,17 +367,16 @@ __global__ __launch_bounds__(JH_THREADS, 4) void k_joint_count_win(JointCountPar
             __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(tile_base + q_begin * (CH * 4)), 0, (int)(nq * (CH * 4)), 0x00020000);
         const unsigned int voff = (unsigned int)tid * (CH * 4u);
         constexpr unsigned int STEP_B = JH_THREADS * CH * 4u;
-        typedef unsigned int u32x4j __attribute__((ext_vector_type(4)));
-        typename std::conditional<CH == 4, u32x4j, u32x3>::type w[DEPTH];
+        typename std::conditional<CH == 4, sl_u32x4, u32x3>::type w[DEPTH];
         auto load = [&](unsigned int soff_b) {
-            if constexpr (CH == 4) return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff_b, 0);
-            else return __builtin_amdgcn_raw_buffer_load_b96(rsrc, voff, soff_b, 0);
+            if constexpr (CH == 4) return stream_load_b128<POLICY>(rsrc, voff, soff_b);
+            else return stream_load_b96<POLICY>(rsrc, voff, soff_b);
         };
         auto count = [&](const auto &v) {
-            if constexpr (CH == 4)
-                do_quad(__builtin_amdgcn_perm(v.y, v.x, 0x04020100u), __builtin_amdgcn_perm(v.z, v.y, 0x05040201u),
-                        __builtin_amdgcn_perm(v.w, v.z, 0x06050402u));
-            else do_quad(v.x, v.y, v.z);
+            if constexpr (CH == 4) {
+                const u32x3 a = rgba_quad_to_rgb(v);
+                do_quad(a.x, a.y, a.z);
+            } else do_quad(v.x, v.y, v.z);
         };
 #pragma unroll
         for (int k = 0; k < DEPTH; ++k) w[k] = load((unsigned)k * STEP_B);
@@ -463,6 +463,8 @@ __global__ __launch_bounds__(JH_THREADS, 4) void k_joint_count_win(JointCountPar
     }
 }
 
+static const bool JOINT_WIN_NT = false;
+
 // ---- launchers (called by lars_d_stats_joint, joint.hip) --------------------------------------------------------------------
 void joint_predict_launch(const uint8_t *tiles, long long ntiles, long long npix, int channels, JointWin *win, int test_mode, hipStream_t s)
 {
@@ -474,17 +476,23 @@ void joint_predict_launch(const uint8_t *tiles, long long ntiles, long long npix
 void joint_count_win_launch(const JointCountParams &C, int channels, int depth, hipStream_t s)
 {
     const long long units = C.ntiles * C.K;
-#define LARS_JOINT_WIN(DD, CC) hipLaunchKernelGGL((k_joint_count_win<DD, CC, false>), dim3((unsigned)units), dim3(JH_THREADS), 0, s, C)
-    if (channels == 4) LARS_JOINT_WIN(5, 4);
-    else if (depth == 4) LARS_JOINT_WIN(4, 3);
-    else if (depth == 5) LARS_JOINT_WIN(5, 3);
-    else if (depth == 6) LARS_JOINT_WIN(6, 3);
-    else if (depth == 12) LARS_JOINT_WIN(12, 3);
-    else LARS_JOINT_WIN(15, 3);
-#undef LARS_JOINT_WIN
+    // one reader per tile chunk: the measured choice of its tile loads (profiles/load_policy_kernels.txt)
+    const bool nt = stream_loads_nt(JOINT_WIN_NT);
+#define LARS_JOINT_WIN(DD, CC, NW)                                                                                                      \
+    do {                                                                                                                                \
+        if (nt) hipLaunchKernelGGL((k_joint_count_win<DD, CC, NW, LOAD_NT>), dim3((unsigned)units), dim3(JH_THREADS), 0, s, C);         \
+        else hipLaunchKernelGGL((k_joint_count_win<DD, CC, NW, LOAD_PLAIN>), dim3((unsigned)units), dim3(JH_THREADS), 0, s, C);         \
+    } while (0)
+    if (channels == 4) LARS_JOINT_WIN(5, 4, false);
+    else if (depth == 4) LARS_JOINT_WIN(4, 3, false);
+    else if (depth == 5) LARS_JOINT_WIN(5, 3, false);
+    else if (depth == 6) LARS_JOINT_WIN(6, 3, false);
+    else if (depth == 12) LARS_JOINT_WIN(12, 3, false);
+    else LARS_JOINT_WIN(15, 3, false);
     // the tiles with a NIR window as well (the depth of the load ring is noise: one build per pixel format)
-    if (channels == 4) hipLaunchKernelGGL((k_joint_count_win<5, 4, true>), dim3((unsigned)units), dim3(JH_THREADS), 0, s, C);
-    else hipLaunchKernelGGL((k_joint_count_win<15, 3, true>), dim3((unsigned)units), dim3(JH_THREADS), 0, s, C);
+    if (channels == 4) LARS_JOINT_WIN(5, 4, true);
+    else LARS_JOINT_WIN(15, 3, true);
+#undef LARS_JOINT_WIN
 }
 
 }  // namespace lars

@@ -2,6 +2,7 @@
 // with the access shapes the hot path uses.  Reported by bench.py next to the
 // kernel numbers ("verify the peak with a STREAM-like kernel").
 #include "lab.h"
+#include "../stream_load.h"
 
 namespace lars {
 
@@ -493,10 +494,69 @@ __global__ __launch_bounds__(1024, 4) void k_probe_lds_atomics(int iters, unsign
     if (acc == 0x12345677u) sink[0] = acc + s_hits;
 }
 
+// Load-policy probes (kinds 200..): the hot path's tile loads under each cache policy of stream_load.h.  One chunk per blockIdx.y
+// (a 4096 x 4096 tile's worth of vectors) behind its own raw-buffer descriptor, gridDim.x workgroups grid-striding through it with
+// four vectors in flight per lane, as k_chan_hist_u8c3_v2 and the v2 plane-writing loop do.  Loads past the chunk return zeros.
+// SHAPE 0: 12 B per lane (b96); 1: 16 B + 8 B per lane (the uint16 quad: b128 and b64 of 24 contiguous bytes); 2: 16 B per lane (RGBA).
+// MIX: per vector three 16-byte stores, one to each plane of slot blockIdx.y % slots of dst (the headline's 12 B : 48 B mix).
+template <int SHAPE, int POLICY, bool MIX>
+__global__ __launch_bounds__(256) void k_probe_policy(const unsigned char *__restrict__ src, long long chunk_bytes, pu32x4 *__restrict__ dst,
+                                                      int slots, unsigned int *__restrict__ sink)
+{
+    constexpr unsigned int VB = SHAPE == 0 ? 12u : (SHAPE == 1 ? 24u : 16u);
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<unsigned char *>(src) + (long long)blockIdx.y * chunk_bytes, 0, (int)chunk_bytes, 0x00020000);
+    const long long nvec = chunk_bytes / VB;
+    const long long step = (long long)gridDim.x * 256;
+    const long long q0 = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long niter = (nvec + step - 1) / step;
+    const unsigned int voff = (unsigned int)q0 * VB, step_b = (unsigned int)step * VB;
+    pu32x4 *d0 = dst + (long long)(blockIdx.y % (unsigned)slots) * 3 * nvec, *d1 = d0 + nvec, *d2 = d1 + nvec;
+    auto load = [&](unsigned int soff) {
+        pu32x4 r;
+        if constexpr (SHAPE == 0) { const sl_u32x3 t = stream_load_b96<POLICY>(rsrc, voff, soff); r = pu32x4{t.x, t.y, t.z, 0u}; }
+        else if constexpr (SHAPE == 1) {
+            const sl_u32x4 a = stream_load_b128<POLICY>(rsrc, voff, soff);
+            const sl_u32x2 b = stream_load_b64<POLICY>(rsrc, voff + 16u, soff);
+            r = pu32x4{a.x ^ b.x, a.y ^ b.y, a.z, a.w};
+        } else r = stream_load_b128<POLICY>(rsrc, voff, soff);
+        return r;
+    };
+    unsigned int acc = 0;
+    pu32x4 w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = load((unsigned)k * step_b);
+    unsigned int soff = 4u * step_b;
+    for (long long it = 0; it < niter; it += 4) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (MIX) {
+                const long long q = q0 + (it + k) * step;
+                if (q < nvec) {
+                    const unsigned int a = w[k].x, b = w[k].y, c = w[k].z;
+                    d0[q] = pu32x4{a, b, c, a ^ b}; d1[q] = pu32x4{b, c, a, b ^ c}; d2[q] = pu32x4{c, a, b, c ^ a};
+                }
+            } else {
+                acc ^= w[k].x ^ w[k].y ^ w[k].z ^ w[k].w;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            w[k] = load(soff + (unsigned)k * step_b);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        soff += 4u * step_b;
+    }
+    if (!MIX && acc == 0x12345678u) sink[0] = acc;
+}
+
 }  // namespace lars
 
 using namespace lars;
 
+template <int SHAPE, int POLICY, bool MIX>
+static void policy_launch(dim3 grid, const unsigned char *src, long long chunk_bytes, pu32x4 *dst, int slots, unsigned int *sink, hipStream_t s)
+{
+    hipLaunchKernelGGL((k_probe_policy<SHAPE, POLICY, MIX>), grid, dim3(256), 0, s, src, chunk_bytes, dst, slots, sink);
+}
 template <int OP>
 static void issue_launch(int iters, int blocks, unsigned int *sink, hipStream_t s)
 {
@@ -507,7 +567,8 @@ static void issue_launch(int iters, int blocks, unsigned int *sink, hipStream_t 
 // is reader r of chunk 8 a + x, so the readers of a chunk sit 8 apart in dispatch order (one XCD) -- with 128 KiB of LDS
 // reserved so that one workgroup fills a CU, as the counting kernel of csrc/joint.hip does.  W dwords per lane and load (3 | 4),
 // six loads in flight.  What a CU can take in from the XCD's L2 when the HBM side delivers each byte once.
-template <int W, int D = 6>
+// POLICY: the loads' cache-policy immediate (stream_load.h); kinds 232.. run the two-reader arrangement under each policy.
+template <int W, int D = 6, int POLICY = LOAD_PLAIN>
 __global__ __launch_bounds__(1024, 4) void k_probe_shared(const unsigned int *__restrict__ src, long long chunk_vecs, long long nchunks,
                                                           int readers, unsigned int *sink)
 {
@@ -525,8 +586,8 @@ __global__ __launch_bounds__(1024, 4) void k_probe_shared(const unsigned int *__
     constexpr unsigned int STEP_B = 1024u * W * 4u;
     auto load = [&](unsigned int soff) {
         v4 r;
-        if constexpr (W == 3) { const v3 t = __builtin_amdgcn_raw_buffer_load_b96(rsrc, voff, soff, 0); r = v4{t.x, t.y, t.z, 0u}; }
-        else r = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
+        if constexpr (W == 3) { const v3 t = stream_load_b96<POLICY>(rsrc, voff, soff); r = v4{t.x, t.y, t.z, 0u}; }
+        else r = stream_load_b128<POLICY>(rsrc, voff, soff);
         return r;
     };
     const long long nsteps = (chunk_vecs + 1023) / 1024;
@@ -546,6 +607,13 @@ __global__ __launch_bounds__(1024, 4) void k_probe_shared(const unsigned int *__
         soff += (unsigned)D * STEP_B;
     }
     if (acc == 0x12345677u) sink[0] = acc + s_pad[1];
+}
+
+template <int W, int POLICY>
+static void shared_policy_launch(dim3 grid, const unsigned int *src, long long chunk_vecs, long long nchunks, int readers, unsigned int *sink,
+                                 hipStream_t s)
+{
+    hipLaunchKernelGGL((k_probe_shared<W, 6, POLICY>), grid, dim3(1024), 0, s, src, chunk_vecs, nchunks, readers, sink);
 }
 
 // kind: 0 read 16 B/lane, 1 read 12 B/lane, 2 copy 16 B/lane (bytes read + bytes written = 2*bytes), 3 write 16 B/lane,
@@ -571,6 +639,45 @@ extern "C" int lars_d_probe(int kind, int unroll, int blocks, const void *src, v
         hipLaunchKernelGGL(k_probe_two_pass, dim3((unsigned)grid), dim3(256), 0, s, p, static_cast<pu32x4 *>(dst), ntiles, unroll, blocks,
                            kind - 60, sink);
         return launch_check("lars_d_probe (two passes)");
+    }
+    if (kind >= 200 && kind < 248) {
+        // load-policy probes: kind = 200 + 16 * condition + 4 * shape + policy; policy 0 plain, 1 nt, 2 sc1, 3 nt sc1.
+        // Condition 0 (read-only) and 1 (12 B : 48 B mix, shape 0 only): bytes = source bytes, cut into chunks of one 4096 x 4096 tile's
+        // vectors (48 / 96 / 64 MiB for shape 0 / 1 / 2), blocks = workgroups per chunk; the mix writes into `unroll` slots (1..64) of dst,
+        // which holds unroll x 4 x 48 MiB.  Condition 2 (shared readers, shapes 0 and 2): unroll = readers (1 | 2), blocks = chunks.
+        const int cond = (kind - 200) / 16, shape = (kind - 200) / 4 % 4, pol = (kind - 200) % 4;
+        if (shape > 2 || (cond == 1 && shape != 0) || (cond == 2 && shape == 1)) return fail(LARS_ERR_INVALID, "lars_d_probe (load policy): shape");
+        const unsigned char *b = static_cast<const unsigned char *>(src);
+        if (cond == 2) {
+            if (unroll < 1 || unroll > 2) return fail(LARS_ERR_INVALID, "lars_d_probe (load policy): 1 or 2 readers");
+            const long long per = shape == 2 ? 16 : 12, chunk_vecs = bytes / per / blocks;
+            if (chunk_vecs < 1 || chunk_vecs * per > 0x7FFFFFFFll) return fail(LARS_ERR_INVALID, "lars_d_probe (load policy): chunk size");
+            const dim3 grid((unsigned)((blocks + 7) / 8 * 8 * unroll));
+            typedef void (*fn_t)(dim3, const unsigned int *, long long, long long, int, unsigned int *, hipStream_t);
+            static const fn_t tab[2][4] = {
+                {shared_policy_launch<3, LOAD_PLAIN>, shared_policy_launch<3, LOAD_NT>, shared_policy_launch<3, LOAD_SC1>, shared_policy_launch<3, LOAD_NT_SC1>},
+                {shared_policy_launch<4, LOAD_PLAIN>, shared_policy_launch<4, LOAD_NT>, shared_policy_launch<4, LOAD_SC1>, shared_policy_launch<4, LOAD_NT_SC1>}};
+            tab[shape == 2][pol](grid, p, chunk_vecs, (long long)blocks, unroll, sink, s);
+            return launch_check("lars_d_probe (load policy, shared readers)");
+        }
+        const long long chunk_bytes = 4194304ll * (shape == 0 ? 12 : (shape == 1 ? 24 : 16));
+        const long long nchunks = bytes / chunk_bytes;
+        if (nchunks < 1 || nchunks > 65535 || blocks > 65536) return fail(LARS_ERR_INVALID, "lars_d_probe (load policy): 1..65535 chunks");
+        const dim3 grid((unsigned)blocks, (unsigned)nchunks);
+        typedef void (*fn_t)(dim3, const unsigned char *, long long, pu32x4 *, int, unsigned int *, hipStream_t);
+        if (cond == 1) {
+            if (!dst || unroll < 1 || unroll > 64) return fail(LARS_ERR_INVALID, "lars_d_probe (load policy): the mix needs dst and 1..64 slots");
+            static const fn_t tab[4] = {policy_launch<0, LOAD_PLAIN, true>, policy_launch<0, LOAD_NT, true>, policy_launch<0, LOAD_SC1, true>,
+                                        policy_launch<0, LOAD_NT_SC1, true>};
+            tab[pol](grid, b, chunk_bytes, static_cast<pu32x4 *>(dst), unroll, sink, s);
+        } else {
+            static const fn_t tab[3][4] = {
+                {policy_launch<0, LOAD_PLAIN, false>, policy_launch<0, LOAD_NT, false>, policy_launch<0, LOAD_SC1, false>, policy_launch<0, LOAD_NT_SC1, false>},
+                {policy_launch<1, LOAD_PLAIN, false>, policy_launch<1, LOAD_NT, false>, policy_launch<1, LOAD_SC1, false>, policy_launch<1, LOAD_NT_SC1, false>},
+                {policy_launch<2, LOAD_PLAIN, false>, policy_launch<2, LOAD_NT, false>, policy_launch<2, LOAD_SC1, false>, policy_launch<2, LOAD_NT_SC1, false>}};
+            tab[shape][pol](grid, b, chunk_bytes, static_cast<pu32x4 *>(dst), 1, sink, s);
+        }
+        return launch_check("lars_d_probe (load policy)");
     }
     if (kind > 30 && kind < 50) {
         // 31..34: R = kind - 30 readers, 12 B per lane; 41..44: 16 B per lane; `blocks` = chunks

@@ -111,6 +111,7 @@ static const Knob KNOBS[] = {
     {"hist_impl", &Tuning::hist_impl, Knob::SET, nullptr, nullptr},
     {"nt_stores", &Tuning::nt_stores, Knob::SET, nullptr, nullptr},
     {"blocks_per_tile", &Tuning::blocks_per_tile, Knob::SET, nullptr, nullptr},
+    {"load_policy", &Tuning::load_policy, Knob::SET, [](int v) { return v >= 0 && v <= 2; }, "0 .. 2"},
     {"selq_window", &Tuning::selq_window, Knob::SET, nullptr, nullptr},
     {"selq_list_wgs", &Tuning::selq_list_wgs, Knob::SET, nullptr, nullptr},
     {"joint_depth", &Tuning::joint_depth, Knob::SET, [](int v) { return v == 4 || v == 6 || v == 8 || v == 12; }, "4, 6, 8 or 12"},

@@ -60,7 +60,8 @@ struct SelQTile {
 };
 
 // STREAMS: bit 0 NDVI, bit 1 GNDVI -- a stream nobody asked for is neither sampled nor divided nor counted
-template <bool WB, bool PER_TILE, unsigned STREAMS>
+// POLICY: cache policy of the tile loads (stream_load.h)
+template <bool WB, bool PER_TILE, unsigned STREAMS, int POLICY = LOAD_PLAIN>
 __global__ __launch_bounds__(1024, 8) void k_selq_pass(SelQParams P)
 {
     // 64 KiB table + one 2048-word row per stream = exactly 80 KiB: two blocks per CU, 8 waves per SIMD
@@ -111,7 +112,7 @@ __global__ __launch_bounds__(1024, 8) void k_selq_pass(SelQParams P)
                 atomicAdd(&s_h[stream * SELQ_BINS + (d < dummy_idx ? d : dummy_idx)], 1u);
             }
         };
-        for_each_quad_ring<1024>(base, nquads, [&](long long, unsigned int w0, unsigned int w1, unsigned int w2) {
+        for_each_quad_ring<1024, POLICY>(base, nquads, [&](long long, unsigned int w0, unsigned int w1, unsigned int w2) {
             const unsigned int wr[4] = {w0, w0, w1, w2}, wg[4] = {w0, w1, w1, w2}, wn[4] = {w0, w1, w2, w2};
             constexpr int br[4] = {0, 3, 2, 1}, bg[4] = {1, 0, 3, 2}, bn[4] = {2, 1, 0, 3};
             float fn[4], fr[4], fg[4], qv[4], qg[4];
@@ -536,7 +537,13 @@ static dim3 selq_grid(long long ntiles, long long npix, long long total = 2048)
 template <bool PER_TILE>
 static void selq_launch(bool wb, unsigned streams, dim3 grid, hipStream_t s, const SelQParams &P)
 {
-#define SELQ_GO(W, S) hipLaunchKernelGGL((k_selq_pass<W, PER_TILE, S>), grid, dim3(1024), 0, s, P)
+    // plain tile loads by default: profiles/load_policy_kernels.txt
+    const bool nt = stream_loads_nt(false);
+#define SELQ_GO(W, S)                                                                                          \
+    do {                                                                                                       \
+        if (nt) hipLaunchKernelGGL((k_selq_pass<W, PER_TILE, S, LOAD_NT>), grid, dim3(1024), 0, s, P);         \
+        else hipLaunchKernelGGL((k_selq_pass<W, PER_TILE, S, LOAD_PLAIN>), grid, dim3(1024), 0, s, P);         \
+    } while (0)
     if (wb) { if (streams == 1u) SELQ_GO(true, 1u); else if (streams == 2u) SELQ_GO(true, 2u); else SELQ_GO(true, 3u); }
     else { if (streams == 1u) SELQ_GO(false, 1u); else if (streams == 2u) SELQ_GO(false, 2u); else SELQ_GO(false, 3u); }
 #undef SELQ_GO

@@ -39,6 +39,7 @@ struct U16Pick {
 // lane owns 4 pixels = 24 bytes (6 dwords: r0g0 n0r1 g1n1 r2g2 n2r3 g3n3, two samples per dword)
 // every > 1: only every `every`-th grid stride is counted (the subsample that predicts the candidate bins)
 // only: null, or flags per tile -- tiles whose flag is 0 are skipped (the classic passes as the fall-back of the one-pass forms)
+template <int POLICY = LOAD_PLAIN>      // cache policy of the tile loads (stream_load.h)
 __global__ __launch_bounds__(1024) void k_hist_u16_hi(const uint16_t *__restrict__ tiles, long long npix,
                                                       unsigned int *__restrict__ hist, int every, const unsigned int *__restrict__ only = nullptr)
 {
@@ -60,8 +61,8 @@ __global__ __launch_bounds__(1024) void k_hist_u16_hi(const uint16_t *__restrict
             __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(base), 0, (int)(nquads * 24), 0x00020000);
         for (long long q = (long long)blockIdx.x * 1024 + tid; q < nquads; q += step) {
             const unsigned int off = (unsigned int)q * 24u;
-            const u32x4v a = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-            const u32x2v b = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off + 16u, 0, 0);
+            const u32x4v a = stream_load_b128<POLICY>(rsrc, off, 0);
+            const u32x2v b = stream_load_b64<POLICY>(rsrc, off + 16u, 0);
             HADD16(a.x, 0, 0); HADD16(a.x, 1, 1); HADD16(a.y, 0, 2); HADD16(a.y, 1, 0);
             HADD16(a.z, 0, 1); HADD16(a.z, 1, 2); HADD16(a.w, 0, 0); HADD16(a.w, 1, 1);
             HADD16(b.x, 0, 2); HADD16(b.x, 1, 0); HADD16(b.y, 0, 1); HADD16(b.y, 1, 2);
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(256) void k_u16_pick(const unsigned int *__restrict
 }
 
 // ---- pass 2: low-byte histograms of the samples in the picked high-byte bins ---------------
-template <bool FAST>
+template <bool FAST, int POLICY = LOAD_PLAIN>      // POLICY: cache policy of the tile loads (stream_load.h)
 __global__ __launch_bounds__(1024) void k_hist_u16_lo(const uint16_t *__restrict__ tiles, long long npix, int channels,
                                                       const U16Pick *__restrict__ picks, unsigned int *__restrict__ lohist,
                                                       const unsigned int *__restrict__ only = nullptr)
@@ -176,8 +177,8 @@ __global__ __launch_bounds__(1024) void k_hist_u16_lo(const uint16_t *__restrict
                 __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(base), 0, (int)(nquads * 24), 0x00020000);
             for (long long q = (long long)blockIdx.x * 1024 + tid; q < nquads; q += step) {
                 const unsigned int off = (unsigned int)q * 24u;
-                const u32x4v a = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-                const u32x2v b = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off + 16u, 0, 0);
+                const u32x4v a = stream_load_b128<POLICY>(rsrc, off, 0);
+                const u32x2v b = stream_load_b64<POLICY>(rsrc, off + 16u, 0);
                 LADD(a.x & 0xFFFFu, 0) LADD(a.x >> 16, 1) LADD(a.y & 0xFFFFu, 2) LADD(a.y >> 16, 0)
                 LADD(a.z & 0xFFFFu, 1) LADD(a.z >> 16, 2) LADD(a.w & 0xFFFFu, 0) LADD(a.w >> 16, 1)
                 LADD(b.x & 0xFFFFu, 2) LADD(b.x >> 16, 0) LADD(b.y & 0xFFFFu, 1) LADD(b.y >> 16, 2)
@@ -220,6 +221,7 @@ __global__ __launch_bounds__(1024) void k_hist_u16_lo(const uint16_t *__restrict
 #define U16_SAMPLE_SPAN 16          /* values per bin of the sample histogram */
 struct U16Win { unsigned int lo[2], wd[2]; };     // per (tile, channel): mark m's window = values [lo, lo + wd); wd == 0: none (the tile is flagged)
 
+template <int POLICY = LOAD_PLAIN>      // cache policy of the tile loads (stream_load.h)
 __global__ __launch_bounds__(1024) void k_u16_sample12(const uint16_t *__restrict__ tiles, long long npix, unsigned int *__restrict__ hist12, int every)
 {
     __shared__ unsigned int s_h[3 * U16_SAMPLE_BINS];
@@ -242,10 +244,10 @@ __global__ __launch_bounds__(1024) void k_u16_sample12(const uint16_t *__restric
             const long long q = sidx * every * 1024 + tid, q2 = (sidx + gridDim.x) * every * 1024 + tid;
             const unsigned int off = (unsigned int)q * 24u, off2 = (unsigned int)q2 * 24u;
             const bool second = sidx + gridDim.x < nsampled;
-            const u32x4v a = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-            const u32x2v b = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off + 16u, 0, 0);
-            const u32x4v a2 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, second ? off2 : off, 0, 0);
-            const u32x2v b2 = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (second ? off2 : off) + 16u, 0, 0);
+            const u32x4v a = stream_load_b128<POLICY>(rsrc, off, 0);
+            const u32x2v b = stream_load_b64<POLICY>(rsrc, off + 16u, 0);
+            const u32x4v a2 = stream_load_b128<POLICY>(rsrc, second ? off2 : off, 0);
+            const u32x2v b2 = stream_load_b64<POLICY>(rsrc, (second ? off2 : off) + 16u, 0);
             if (q < nquads) {
                 SADD(a.x, 0, 0); SADD(a.x, 1, 1); SADD(a.y, 0, 2); SADD(a.y, 1, 0); SADD(a.z, 0, 1); SADD(a.z, 1, 2);
                 SADD(a.w, 0, 0); SADD(a.w, 1, 1); SADD(b.x, 0, 2); SADD(b.x, 1, 0); SADD(b.y, 0, 1); SADD(b.y, 1, 2);
@@ -338,6 +340,7 @@ __device__ inline unsigned int u16_below(unsigned int key, unsigned int lo16, un
     return d;
 }
 
+template <int POLICY = LOAD_PLAIN>      // cache policy of the tile loads (stream_load.h)
 __global__ __launch_bounds__(1024) void k_u16_count_win(const uint16_t *__restrict__ tiles, long long npix, const U16Win *__restrict__ win,
                                                         unsigned int *__restrict__ below_out /*[ntiles][3][2]*/,
                                                         unsigned int *__restrict__ winhist /*[ntiles][3][2][U16_WIN_MAX]*/)
@@ -382,8 +385,8 @@ __global__ __launch_bounds__(1024) void k_u16_count_win(const uint16_t *__restri
 #pragma unroll
         for (int d = 0; d < U16_DEPTH; ++d) {
             const unsigned int off = (unsigned int)(q + d * step) * 24u;
-            ra[d] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
-            rb[d] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off + 16u, 0, 0);
+            ra[d] = stream_load_b128<POLICY>(rsrc, off, 0);
+            rb[d] = stream_load_b64<POLICY>(rsrc, off + 16u, 0);
         }
         for (; q < nquads; q += U16_DEPTH * step) {
 #pragma unroll
@@ -392,8 +395,8 @@ __global__ __launch_bounds__(1024) void k_u16_count_win(const uint16_t *__restri
                 const u32x4v a = ra[d];
                 const u32x2v b = rb[d];
                 const unsigned int off = (unsigned int)(qq + U16_DEPTH * step) * 24u;
-                ra[d] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);      // past the tile: zeros, never counted
-                rb[d] = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off + 16u, 0, 0);
+                ra[d] = stream_load_b128<POLICY>(rsrc, off, 0);      // past the tile: zeros, never counted
+                rb[d] = stream_load_b64<POLICY>(rsrc, off + 16u, 0);
                 if (qq < nquads) {
                     const unsigned int w[6] = {a.x, a.y, a.z, a.w, b.x, b.y};
 #pragma unroll
@@ -590,26 +593,33 @@ extern "C" int lars_d_wb_prepare(const void *tiles, int64_t ntiles, int64_t npix
     dim3 grid((unsigned)want, (unsigned)ntiles);
     const dim3 per_channel(3, (unsigned)ntiles);
     const int impl = tuning().u16_hist_impl;
+    const bool nt = stream_loads_nt(false);               // plain tile loads by default: profiles/load_policy_kernels.txt
     if (fast && cap >= 64 && impl != 1) {
         // ONE full pass on value windows (round 5): per channel and mark the count of the samples below a predicted window and the histogram
         // inside it; a rank outside its window flags the tile, and only flagged tiles take the two classic passes (all of them with impl 3)
         LARS_HIP_TRY(hipMemsetAsync(hi, 0, L.picks, s));                  // hi, lo, flags, s12, below, winhist are contiguous
-        hipLaunchKernelGGL(k_u16_sample12, grid, dim3(1024), 0, s, t16, (long long)npix, s12, 64);     // 1 / 64 of the samples: 1 M per 8192 x 8192 tile and channel
+        if (nt) hipLaunchKernelGGL(k_u16_sample12<LOAD_NT>, grid, dim3(1024), 0, s, t16, (long long)npix, s12, 64);     // 1 / 64 of the samples: 1 M per 8192 x 8192 tile and channel
+        else hipLaunchKernelGGL(k_u16_sample12<LOAD_PLAIN>, grid, dim3(1024), 0, s, t16, (long long)npix, s12, 64);
         hipLaunchKernelGGL(k_u16_window, per_channel, dim3(256), 0, s, s12, win, impl == 3 ? 1 : 0);
-        hipLaunchKernelGGL(k_u16_count_win, grid, dim3(1024), 0, s, t16, (long long)npix, win, below, winhist);
+        if (nt) hipLaunchKernelGGL(k_u16_count_win<LOAD_NT>, grid, dim3(1024), 0, s, t16, (long long)npix, win, below, winhist);
+        else hipLaunchKernelGGL(k_u16_count_win<LOAD_PLAIN>, grid, dim3(1024), 0, s, t16, (long long)npix, win, below, winhist);
         hipLaunchKernelGGL(k_u16_pick_win, per_channel, dim3(256), 0, s, win, below, winhist, (long long)npix, flags, table, percentiles, rgn_variant);
-        hipLaunchKernelGGL(k_hist_u16_hi, grid, dim3(1024), 0, s, t16, (long long)npix, hi, 1, flags);
+        if (nt) hipLaunchKernelGGL(k_hist_u16_hi<LOAD_NT>, grid, dim3(1024), 0, s, t16, (long long)npix, hi, 1, flags);
+        else hipLaunchKernelGGL(k_hist_u16_hi<LOAD_PLAIN>, grid, dim3(1024), 0, s, t16, (long long)npix, hi, 1, flags);
         hipLaunchKernelGGL(k_u16_pick, per_channel, dim3(256), 0, s, hi, (long long)npix, picks, flags);
-        hipLaunchKernelGGL((k_hist_u16_lo<true>), grid, dim3(1024), 0, s, t16, (long long)npix, channels, picks, lo, flags);
+        if (nt) hipLaunchKernelGGL((k_hist_u16_lo<true, LOAD_NT>), grid, dim3(1024), 0, s, t16, (long long)npix, channels, picks, lo, flags);
+        else hipLaunchKernelGGL((k_hist_u16_lo<true, LOAD_PLAIN>), grid, dim3(1024), 0, s, t16, (long long)npix, channels, picks, lo, flags);
         hipLaunchKernelGGL(k_wb_table_u16, per_channel, dim3(256), 0, s, lo, picks, table, percentiles, rgn_variant, 4, flags);
         c->u16_win_tiles = ntiles;                         // lars_u16_window_report: flags and windows of this many tiles are in the scratch
         return launch_check("lars_d_wb_prepare (value windows)");
     }
     LARS_HIP_TRY(hipMemsetAsync(hi, 0, L.s12, s));                        // hi, lo, flags are contiguous
-    if (fast) hipLaunchKernelGGL(k_hist_u16_hi, grid, dim3(1024), 0, s, t16, (long long)npix, hi, 1, (const unsigned int *)nullptr);
+    if (fast && nt) hipLaunchKernelGGL(k_hist_u16_hi<LOAD_NT>, grid, dim3(1024), 0, s, t16, (long long)npix, hi, 1, (const unsigned int *)nullptr);
+    else if (fast) hipLaunchKernelGGL(k_hist_u16_hi<LOAD_PLAIN>, grid, dim3(1024), 0, s, t16, (long long)npix, hi, 1, (const unsigned int *)nullptr);
     else hipLaunchKernelGGL(k_hist_u16_hi_generic, dim3((unsigned)want * 4, (unsigned)ntiles), dim3(256), 0, s, t16, (long long)npix, channels, hi);
     hipLaunchKernelGGL(k_u16_pick, per_channel, dim3(256), 0, s, hi, (long long)npix, picks, (const unsigned int *)nullptr);
-    if (fast) hipLaunchKernelGGL((k_hist_u16_lo<true>), grid, dim3(1024), 0, s, t16, (long long)npix, channels, picks, lo, (const unsigned int *)nullptr);
+    if (fast && nt) hipLaunchKernelGGL((k_hist_u16_lo<true, LOAD_NT>), grid, dim3(1024), 0, s, t16, (long long)npix, channels, picks, lo, (const unsigned int *)nullptr);
+    else if (fast) hipLaunchKernelGGL((k_hist_u16_lo<true, LOAD_PLAIN>), grid, dim3(1024), 0, s, t16, (long long)npix, channels, picks, lo, (const unsigned int *)nullptr);
     else hipLaunchKernelGGL((k_hist_u16_lo<false>), grid, dim3(1024), 0, s, t16, (long long)npix, channels, picks, lo, (const unsigned int *)nullptr);
     hipLaunchKernelGGL(k_wb_table_u16, per_channel, dim3(256), 0, s, lo, picks, table, percentiles, rgn_variant, 4, (const unsigned int *)nullptr);
     return launch_check("lars_d_wb_prepare");

@@ -140,7 +140,8 @@ __device__ inline void selq_window_add(float u, unsigned int row_rel, int lo, in
 // The fused kernel's load pipeline as a reusable loop: four 12-byte buffer loads in flight per lane, slot k is
 // consumed and refilled in place.  f(q, w0, w1, w2) sees every quad of the tile exactly once.
 // `every` > 1: only every `every`-th grid stride is visited (a subsample in chunks of gridDim.x * NTHR quads).
-template <int NTHR, typename F>
+// POLICY: cache policy of the loads (stream_load.h).
+template <int NTHR, int POLICY = LOAD_PLAIN, typename F>
 __device__ inline void for_each_quad_ring(const uint8_t *base, long long nquads, F &&f, int every = 1)
 {
     const long long stride = (long long)gridDim.x * NTHR * every;
@@ -153,7 +154,7 @@ __device__ inline void for_each_quad_ring(const uint8_t *base, long long nquads,
     const unsigned int step_b = (unsigned int)stride * 12u;
     u32x3 w[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) w[k] = __builtin_amdgcn_raw_buffer_load_b96(rsrc, voff, (unsigned)k * step_b, 0);
+    for (int k = 0; k < 4; ++k) w[k] = stream_load_b96<POLICY>(rsrc, voff, (unsigned)k * step_b);
     long long it = 0;
     unsigned int soff = 4u * step_b;
     for (; it + 4 <= niter - 1; it += 4) {
@@ -161,7 +162,7 @@ __device__ inline void for_each_quad_ring(const uint8_t *base, long long nquads,
         for (int k = 0; k < 4; ++k) {
             f(q0 + (it + k) * stride, w[k].x, w[k].y, w[k].z);
             __builtin_amdgcn_sched_barrier(0);
-            w[k] = __builtin_amdgcn_raw_buffer_load_b96(rsrc, voff, soff + (unsigned)k * step_b, 0);
+            w[k] = stream_load_b96<POLICY>(rsrc, voff, soff + (unsigned)k * step_b);
             __builtin_amdgcn_sched_barrier(0);
         }
         soff += 4u * step_b;

@@ -36,20 +36,20 @@ def headline_launches(rnd, src):
     per_step = int(line["roofline"]["launches_per_step"])
     trace = max(glob.glob(f"{src}/trace/**/*kernel_trace.csv", recursive=True), key=os.path.getmtime)
     allrows = sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"]))
-    head = "void lars::k_fused_u8c3<unsigned char, 7u, true, 1, 3>"
+    head = "void lars::k_fused_u8c3<unsigned char, 7u, true, 1, 3,"     # whatever its load policy
 
     def grid(r):
         return (r.get("Grid_Size_X", r.get("Grid_Size")), r.get("Grid_Size_Y", ""))
     rows = [r for r in allrows if r["Kernel_Name"].startswith(head)]
     ring_grid = max(set(grid(r) for r in rows), key=lambda g: sum(1 for r in rows if grid(r) == g))
-    hist = [r for r in allrows if "k_chan_hist_u8c3_v2<3>" in r["Kernel_Name"]]
+    hist = [r for r in allrows if "k_chan_hist_u8c3_v2<3," in r["Kernel_Name"]]
     hist_grid = max(set(grid(r) for r in hist), key=lambda g: int(g[1] or 1))        # grid.y = tiles: the pass over the whole batch
     # groups of headline launches between a k_stats_init and the next k_stats_finalize: a step's group has exactly `launches_per_step`
     # of them and a full-batch histogram pass since the previous group; the arena probe's groups are longer (untimed + timed passes)
     steps, search, group, saw_hist = [], [], [], False
     for r in allrows:
         name = r["Kernel_Name"]
-        if "k_chan_hist_u8c3_v2<3>" in name and grid(r) == hist_grid:
+        if "k_chan_hist_u8c3_v2<3," in name and grid(r) == hist_grid:
             saw_hist = True
         elif name.startswith(head) and grid(r) == ring_grid:
             group.append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
@@ -121,21 +121,21 @@ def main():
     px64, px256 = 64 * 4096 * 4096, 256 * 4096 * 4096
     # kernel names as rocprofv3 prints them, up to the template arguments that only tuning knobs change (matched by prefix)
     rows = {
-        "wb3idx_out_stats": ("k_fused_u8c3<unsigned char, 7u, true, 1, 3>", px64),
-        "wb3idx_out_stats_hist": ("k_fused_u8c3<unsigned char, 7u, true, 2, 3>", px64),
-        "wb_ndvi_out_stats": ("k_fused_u8c3<unsigned char, 1u, true, 0, 3>", px64),       # planes only; its statistics pass is k_joint_count
-        "wb3idx_out_stats_medians": ("k_fused_u8c3<unsigned char, 7u, true, 0, 3>", px64),      # planes only; its statistics pass is k_joint_count
+        "wb3idx_out_stats": ("k_fused_u8c3<unsigned char, 7u, true, 1, 3,", px64),
+        "wb3idx_out_stats_hist": ("k_fused_u8c3<unsigned char, 7u, true, 2, 3,", px64),
+        "wb_ndvi_out_stats": ("k_fused_u8c3<unsigned char, 1u, true, 0, 3,", px64),       # planes only; its statistics pass is k_joint_count
+        "wb3idx_out_stats_medians": ("k_fused_u8c3<unsigned char, 7u, true, 0, 3,", px64),      # planes only; its statistics pass is k_joint_count
         # the one-read statistics route: one counting launch per step over the whole batch.  Two value streams on the bench's tiles:
         # windowed tables, one reader per tile chunk (k_joint_count_win); one stream: the full table (k_joint_count).  The launches of
         # lars_d_stats_joint whose workgroups find nothing to do are left out of the means (tools/pmc_summary.py)
         "wb3idx_stats_only": ("k_joint_count_win<", px256),
-        "wb_ndvi_stats_only": ("k_joint_count<6, 3>", px256),
+        "wb_ndvi_stats_only": ("k_joint_count<6, 3, 2>", px256),          # one value stream: nt tile loads (the <6, 3, 0> launches are the two-reader form)
         "wb3idx_stats_medians": ("k_joint_count_win<", px256),
         "joint_predict": ("k_joint_predict<3>", px256),
         "joint_finish": ("k_joint_finish", px256),
         "wb3idx_stats_only_classic": ("k_fused_v2<7u, true, 1, false, false, 0,", px256),
         "wb_ndvi_stats_only_classic": ("k_fused_v2<1u, true, 1, false, false, 0,", px256),
-        "channel_hist": ("k_chan_hist_u8c3_v2<3>", px256),
+        "channel_hist": ("k_chan_hist_u8c3_v2<3,", px256),
     }
 
     def find(table, prefix):

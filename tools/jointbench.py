@@ -129,6 +129,26 @@ def timed(fn, rounds):
     return float(np.median(out[1:])), float(min(out[1:]))
 
 
+def timed_policies(fn, rounds, policies):
+    """fn under each load_policy setting in turn, round by round (one warm-up round) -> [(setting, median ms, min ms)]."""
+    ev = [C.c_void_p(), C.c_void_p()]
+    for e in ev:
+        _ffi.call("lars_event_create", C.byref(e))
+    out = [[] for _ in policies]
+    for _ in range(rounds + 1):
+        for j, lp in enumerate(policies):
+            with _ffi.tuning(**({} if lp is None else {"load_policy": lp})):
+                _ffi.call("lars_event_record", ev[0], None)
+                fn()
+                _ffi.call("lars_event_record", ev[1], None)
+            ms = C.c_float(0)
+            _ffi.call("lars_event_elapsed_ms", ev[0], ev[1], C.byref(ms))
+            out[j].append(ms.value)
+    for e in ev:
+        _ffi.call("lars_event_destroy", e)
+    return [(lp, float(np.median(t[1:])), float(min(t[1:]))) for lp, t in zip(policies, out)]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tiles", type=int, default=256)
@@ -139,6 +159,8 @@ def main():
     ap.add_argument("--blocks", default="0", help="chunks per tile of the counting kernel (blocks_per_tile), 0 = automatic")
     ap.add_argument("--windows", default="1,0", help="joint_window settings to time: 1 windowed tables where they fit, 0 never, 2 windows that miss")
     ap.add_argument("--skip-classic-medians", action="store_true")
+    ap.add_argument("--load-policy", default="", help="load_policy settings of the joint route, alternating round by round, e.g. 1,2,1; empty: the knob is left alone")
+    ap.add_argument("--skip-classic", action="store_true", help="time the joint route only (no comparison against the classic route's results)")
     ap.add_argument("--no-roll", action="store_true", help="hand-made contents: plain replicas of one tile instead of row-rolled ones")
     args = ap.parse_args()
     lib = _ffi.load()
@@ -156,7 +178,7 @@ def main():
                   flush=True)
 
         ref = {}
-        for mname, indices in MODES.items():
+        for mname, indices in ({} if args.skip_classic else MODES).items():
             def classic():
                 b.compute_wb_tables()
                 b.run_fused(b.fused_args(indices, True, stats))
@@ -189,21 +211,27 @@ def main():
                     if window != 1 and len(indices) == 1:
                         continue                                    # one stream: never windowed
                     for med in (False, True):
-                        ms, mn = timed(lambda: b.run_joint(indices, True, stats, pairs=pairs if med else None), args.rounds)
-                        b.check_joint()
-                        nw, nrec = b.joint_window_report()
-                        n3 = b.joint_window_modes()[2]
-                        report(f"joint   {mname} statistics{' + medians' if med else ''} depth {depth} blocks {blocks} window {window} "
-                               f"[{nw} windowed{f' ({n3} on three windows)' if n3 else ''}, {nrec} recounted]", ms, mn)
-                        rec = stats.download(_ffi.STATS_DTYPE, (b.ntiles, 3))
-                        ids = [_ffi.INDEX_IDS[t] for t in indices]
-                        assert rec[:, ids].tobytes() == ref[mname][:, ids].tobytes(), "records differ between the routes"
-                        chans = sorted(lars.batch.channels_of(indices))
-                        assert np.array_equal(b.host_tables(partial=True)[:, chans], ref["tables"][:, chans]), "tables differ between the routes"
-                        assert b.host_percentiles(partial=True)[:, chans].tobytes() == ref["pcts"][:, chans].tobytes(), "percentiles differ"
-                        if med and mname + "_med" in ref:
-                            got = pairs.download(np.float32, (b.ntiles, 2, 2))
-                            assert np.array_equal(got, ref[mname + "_med"], equal_nan=True), "medians differ between the routes"
+                        run = lambda: b.run_joint(indices, True, stats, pairs=pairs if med else None)
+                        lps = [int(x) for x in args.load_policy.split(",")] if args.load_policy else [None]
+                        for pos, (lp, ms, mn) in enumerate(timed_policies(run, args.rounds, lps)):
+                            with _ffi.tuning(**({} if lp is None else {"load_policy": lp})):
+                                run()
+                            b.check_joint()
+                            nw, nrec = b.joint_window_report()
+                            n3 = b.joint_window_modes()[2]
+                            report(f"joint   {mname} statistics{' + medians' if med else ''} depth {depth} blocks {blocks} window {window} "
+                                   f"load_policy {lp} #{pos} [{nw} windowed{f' ({n3} on three windows)' if n3 else ''}, {nrec} recounted]", ms, mn)
+                            if args.skip_classic:
+                                continue
+                            rec = stats.download(_ffi.STATS_DTYPE, (b.ntiles, 3))
+                            ids = [_ffi.INDEX_IDS[t] for t in indices]
+                            assert rec[:, ids].tobytes() == ref[mname][:, ids].tobytes(), "records differ between the routes"
+                            chans = sorted(lars.batch.channels_of(indices))
+                            assert np.array_equal(b.host_tables(partial=True)[:, chans], ref["tables"][:, chans]), "tables differ between the routes"
+                            assert b.host_percentiles(partial=True)[:, chans].tobytes() == ref["pcts"][:, chans].tobytes(), "percentiles differ"
+                            if med and mname + "_med" in ref:
+                                got = pairs.download(np.float32, (b.ntiles, 2, 2))
+                                assert np.array_equal(got, ref[mname + "_med"], equal_nan=True), "medians differ between the routes"
         stats.free(); pairs.free(); med_scratch.free(); b.free()
 
 

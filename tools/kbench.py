@@ -58,7 +58,13 @@ def main():
     ap.add_argument("--bpt", default="0")
     ap.add_argument("--wb", default="1")
     ap.add_argument("--profile", default="vegetation")
+    ap.add_argument("--load-policy", default="", help="load_policy settings to alternate, e.g. 1,2,1 (a repeated value is timed as a variant of its own); "
+                    "empty: the knob is left alone")
     args = ap.parse_args()
+    policies = [int(x) for x in args.load_policy.split(",")] if args.load_policy else [None]
+
+    def policy(lp):
+        return {} if lp is None else {"load_policy": lp}
 
     if args.profile in ("uniform", "vegetation"):
         b = lars.TileBatch.synthetic(args.tiles, args.tile, args.tile, seed=1234, profile=args.profile)
@@ -73,17 +79,18 @@ def main():
     results = {}
 
     if "hist" in args.what:
-        variants = [(i, bp) for i in map(int, args.impls.split(",")) for bp in map(int, args.bpt.split(","))]
+        variants = [(i, bp, lp, pos) for i in map(int, args.impls.split(",")) for bp in map(int, args.bpt.split(","))
+                    for pos, lp in enumerate(policies)]
         times = {v: [] for v in variants}
         for _ in range(args.rounds + 1):
             for v in variants:
-                with _ffi.tuning(hist_impl=v[0], blocks_per_tile=v[1]):
+                with _ffi.tuning(hist_impl=v[0], blocks_per_tile=v[1], **policy(v[2])):
                     times[v].append(timer.time(lambda: _ffi.call(
                         "lars_d_channel_hist", C.c_void_p(b.tiles.ptr), b.ntiles, b.npix, 3, _ffi.U8,
                         C.c_void_p(b.hist.ptr), None)))
         for v, t in times.items():
             med = float(np.median(t[1:]))
-            results[f"hist impl={v[0]} bpt={v[1]}"] = {"ms": med, "min_ms": float(min(t[1:])), "GBs": npix * 3 / med / 1e6}
+            results[f"hist impl={v[0]} bpt={v[1]} load_policy={v[2]} #{v[3]}"] = {"ms": med, "min_ms": float(min(t[1:])), "GBs": npix * 3 / med / 1e6}
 
     if "fused" in args.what:
         modes = [m for m in args.modes.split(",") if m]
@@ -96,11 +103,12 @@ def main():
                         continue
                     for bp in map(int, args.bpt.split(",")):
                         for wb in map(int, args.wb.split(",")):
-                            variants.append((m, impl, nt, bp, wb))
+                            for pos, lp in enumerate(policies):
+                                variants.append((m, impl, nt, bp, wb, lp, pos))
         times = {v: [] for v in variants}
         for _ in range(args.rounds + 1):
             for v in variants:
-                m, impl, nt, bp, wb = v
+                m, impl, nt, bp, wb, lp, pos = v
                 indices, write, hist, bpp = MODES[m]
                 outs = None
                 if write:
@@ -115,15 +123,30 @@ def main():
                         for start in range(0, b.ntiles, outs.slots):
                             cnt = min(outs.slots, b.ntiles - start)
                             b.run_fused(b.fused_args(indices, bool(wb), stats, hist, outs, None, start, cnt))
-                with _ffi.tuning(fused_impl=impl, nt_stores=nt, blocks_per_tile=bp):
+                with _ffi.tuning(fused_impl=impl, nt_stores=nt, blocks_per_tile=bp, **policy(lp)):
                     times[v].append(timer.time(run))
         for v, t in times.items():
-            m, impl, nt, bp, wb = v
+            m, impl, nt, bp, wb, lp, pos = v
             med = float(np.median(t[1:]))
             bpp = MODES[m][3]
-            results[f"fused {m} impl={impl} nt={nt} bpt={bp} wb={wb}"] = {
+            results[f"fused {m} impl={impl} nt={nt} bpt={bp} wb={wb} load_policy={lp} #{pos}"] = {
                 "ms": med, "min_ms": float(min(t[1:])), "GBs": npix * bpp / med / 1e6,
                 "frac_8TBs": npix * bpp / med / 1e6 / 8000.0, "Gpix_s": npix / med / 1e6}
+    if "select" in args.what:
+        # the select passes of global_medians (pure reads of 3 B per pixel each), host-timed: the passes end in small downloads
+        import time
+        variants = list(enumerate(policies))
+        times = {v: [] for v in variants}
+        for _ in range(args.rounds + 1):
+            for v in variants:
+                with _ffi.tuning(**policy(v[1])):
+                    _ffi.call("lars_synchronize", None)
+                    t0 = time.perf_counter()
+                    b.global_medians(recompute_tables=False)
+                    times[v].append((time.perf_counter() - t0) * 1e3)
+        for v, t in times.items():
+            med = float(np.median(t[1:]))
+            results[f"select global_medians load_policy={v[1]} #{v[0]}"] = {"ms": med, "min_ms": float(min(t[1:]))}
     if "medians" in args.what:
         # time-series table of the whole batch (statistics + median per tile): without planes, and with the planes written as well
         import time

@@ -78,6 +78,22 @@ def probe(kind, unroll, blocks, src, dst, nbytes, stream=None):
          int(nbytes), stream)
 
 
+# load-policy probes (csrc/lab/probe.hip, kinds 200 .. 247): condition x tile-load shape x cache policy of csrc/stream_load.h
+POLICY_READ, POLICY_MIX, POLICY_SHARED = range(3)                   # read only | 12 B read : 48 B written (12 B shape only) | shared readers
+SHAPE_B96, SHAPE_B128_B64, SHAPE_B128 = range(3)                    # 12 B | 16 B + 8 B (the uint16 quad; not with shared readers) | 16 B per lane
+LOAD_PLAIN, LOAD_NT, LOAD_SC1, LOAD_NT_SC1 = range(4)
+
+
+def policy_kind(condition, shape, policy):
+    return 200 + 16 * int(condition) + 4 * int(shape) + int(policy)
+
+
+def probe_policy(condition, shape, policy, unroll, blocks, src, dst, nbytes, stream=None):
+    """``unroll``: output slots of the mix (1 .. 64; dst holds that many x 4 x 48 MiB) or readers per chunk (1 | 2); ``blocks``:
+    workgroups per chunk of one 4096 x 4096 tile's vectors, or chunks for the shared readers."""
+    probe(policy_kind(condition, shape, policy), unroll, blocks, src, dst, nbytes, stream)
+
+
 def probe_mix3(src, d0, d1, d2, nquads, blocks=65536, stream=None):
     call("lars_d_probe_mix3", C.c_void_p(src), C.c_void_p(d0), C.c_void_p(d1), C.c_void_p(d2), int(nquads), int(blocks), stream)
 

@@ -9,6 +9,8 @@ from lars_image_processing_amd import _ffi
 def main():
     tiles = int(sys.argv[1]) if len(sys.argv) > 1 else 16
     edge = int(sys.argv[2]) if len(sys.argv) > 2 else 8192
+    # load_policy settings to alternate launch by launch, e.g. 1,2,1 (a repeated value is timed as a variant of its own)
+    policies = [int(x) for x in sys.argv[3].split(",")] if len(sys.argv) > 3 else [None]      # None: the knob is left alone
     b = lars.TileBatch(tiles, edge, edge, 3, np.uint16)
     # random 16-bit samples: the byte generator over twice the bytes
     _ffi.call("lars_d_synth_u8", C.c_void_p(b.tiles.ptr), tiles, 0, b.npix * 2, 3, 1234, 0, None)
@@ -16,11 +18,15 @@ def main():
     a, e = C.c_void_p(), C.c_void_p()
     _ffi.call("lars_event_create", C.byref(a)); _ffi.call("lars_event_create", C.byref(e))
     def timed(fn, n=4):
-        ts = []
+        ts = [[] for _ in policies]
         for _ in range(n):
-            _ffi.call("lars_event_record", a, None); fn(); _ffi.call("lars_event_record", e, None)
-            ms = C.c_float(0); _ffi.call("lars_event_elapsed_ms", a, e, C.byref(ms)); ts.append(ms.value)
-        return float(np.median(ts[1:]))
+            for j, lp in enumerate(policies):
+                with _ffi.tuning(**({} if lp is None else {"load_policy": lp})):
+                    _ffi.call("lars_event_record", a, None); fn(); _ffi.call("lars_event_record", e, None)
+                ms = C.c_float(0); _ffi.call("lars_event_elapsed_ms", a, e, C.byref(ms)); ts[j].append(ms.value)
+        return [float(np.median(t[1:])) for t in ts]
+    def label(name, j):
+        return name if policies == [None] else f"{name} load_policy={policies[j]} #{j}"
     npix = tiles * edge * edge
     res = {}
     for impl, name in ((5, "wb_prepare (one full pass on VALUE windows: counts below + histograms inside; round 5)"),
@@ -29,15 +35,15 @@ def main():
                        (50, "wb_prepare (value windows once more)")):
         impl = 5 if impl == 50 else impl
         with _ffi.tuning(u16_hist_impl=impl):
-            t = timed(lambda: b.compute_wb_tables())
-        res[name] = {"ms": t, "GBs_input_once": npix * 6 / t / 1e6, "frac_8TBs": npix * 6 / t / 1e6 / 8000}
+            for j, t in enumerate(timed(lambda: b.compute_wb_tables())):
+                res[label(name, j)] = {"ms": t, "GBs_input_once": npix * 6 / t / 1e6, "frac_8TBs": npix * 6 / t / 1e6 / 8000}
     stats = b.new_stats()
     outs = b.make_outputs(indices=("NDVI",), index=True, rgba=True)
     for name, kw, bpp in (("ndvi_f32+rgba+stats (configs[4])", dict(indices=("NDVI",), outputs=outs), 14),
                           ("ndvi stats only", dict(indices=("NDVI",), outputs=None), 6),
                           ("3idx stats only", dict(indices=("NDVI", "GNDVI", "NDWI"), outputs=None), 6)):
-        t = timed(lambda: b.run_fused(b.fused_args(kw["indices"], True, stats, False, kw["outputs"])))
-        res[name] = {"ms": t, "GBs": npix * bpp / t / 1e6, "frac_8TBs": npix * bpp / t / 1e6 / 8000, "Gpix_s": npix / t / 1e6}
+        for j, t in enumerate(timed(lambda: b.run_fused(b.fused_args(kw["indices"], True, stats, False, kw["outputs"])))):
+            res[label(name, j)] = {"ms": t, "GBs": npix * bpp / t / 1e6, "frac_8TBs": npix * bpp / t / 1e6 / 8000, "Gpix_s": npix / t / 1e6}
     for k, v in res.items():
         print(f"{k:96s} " + "  ".join(f"{kk}={vv:9.3f}" for kk, vv in v.items()))
     print(json.dumps(res))
