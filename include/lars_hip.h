@@ -361,11 +361,11 @@ int lars_get_tuning(const char *key, int *value);
 
 /* Build-time switches of the kernel sources this library was compiled with: 0 for the product (what `make` builds and the
  * package loads).  Laboratory builds (csrc/Makefile `lablayout`, `EXTRA=-D...`) report what they changed: the plane-layout knob
- * (one more kernel argument: other register counts), IEEE division instead of rcp + fma (same results, slower), vector instead of
- * scalar coverage counters (same results), another geometry of the statistics-only kernels.  Needs no device. */
+ * (one more kernel argument: other register counts), IEEE division instead of rcp + fma (same results, slower), another
+ * geometry of the statistics-only kernels.  Needs no device. */
 #define LARS_BUILD_LAB_LAYOUT 1u
 #define LARS_BUILD_IEEE_DIV 2u
-#define LARS_BUILD_COUNT_MODE 4u
+#define LARS_BUILD_COUNT_MODE 4u        /* retired and never set (vector coverage counters; the switch left the sources): do not reuse 4u */
 #define LARS_BUILD_STATS_GEOMETRY 8u
 unsigned int lars_build_flags(void);
 

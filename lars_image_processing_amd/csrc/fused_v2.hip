@@ -1,13 +1,16 @@
 // The per-pixel statistics kernels ("classic" route), written for the CDNA4 issue budget.
 //
-// WHAT STILL DEPENDS ON THIS FILE (round 4).  Since round 3 the statistics of uint8 RGNir / RGBA batches come from the one-read
-// route (joint.hip) by default; these kernels serve
-//   * statistics-only passes the one-read route does not take: uint16 tiles, channel counts other than 3 / 4, unaligned tiles,
-//     passes over tables the caller supplied (process(recompute_tables=False)), and route="auto" on content where it measures faster;
-//   * lars_d_stats_medians / lars_d_quotient_select_hist (the first select pass lives inside k_fused_v2<..., SEL>) and with them
-//     TileBatch.global_medians, the exact median over all tiles of all ranks;
-//   * k_chan_hist_u8c3_v2: the channel-histogram pre-pass of every launch that writes planes from tables (the bench headline);
+// WHAT DEPENDS ON THIS FILE.  The statistics of uint8 RGNir / RGBA batches come from the one-read route (joint.hip, joint_win.hip)
+// by default.  k_fused_v2 (uint8, 3 channels, 4-byte aligned tiles of fewer than 2^30 / 6 pixels) serves
+//   * the statistics-only passes that route does not take: passes over tables the batch already holds
+//     (process(recompute_tables=False)), route="classic", a batch of several tiles whose pixel count is no multiple of 4 apart,
+//     and route="auto" on content where the per-pixel route measures faster;
+//   * lars_d_stats_medians: the statistics kernel also counts the select's first pass (SEL == 1: the 2048 buckets; SEL == 2: the
+//     predicted windows of the one-pass medians), select_q.hip's passes finish the tiles whose window missed;
+//   * plane-writing launches under fused_impl = 2 (the default takes fused.hip's kernels when planes are written);
 //   * the other side of every route-equality test (tests/test_gpu_joint.py, tests/fuzz_routes.py) and of bench.py's self-check.
+// k_chan_hist_u8c3_v2 is the channel-histogram pre-pass of every launch that writes planes from tables (the bench headline).
+// The tile walker, the RGB-quad decoder, the table fill and the tail pixel are v2_device.h's, shared with select_q.hip.
 //
 // The stats-only configurations move 3 bytes per pixel, so at HBM rate a CU has
 // only ~35 vector-instruction slots per pixel.  What this file does about it:
@@ -189,21 +192,9 @@ struct WaveAcc {
 // ballot/popcount form hipcc kept a dozen 64-bit masks alive per quad, ran out of SGPRs and spilled
 // them with v_writelane_b32 (4.5 extra VALU instructions per pixel in the three-index kernel).
 // Inactive lanes contribute zero bits; scalar instructions ignore EXEC.
-// LARS_COUNT_MODE (build-time, tools/kbench A/B): 0 scalar counters everywhere, 1 per-lane vector
-// counters everywhere (v_cmp + v_addc, no SALU), 2 NDVI on the vector pipe and GNDVI/NDWI on the scalar pipe.
-// (Also tried and dropped: per-lane float counters fed by a saturating packed fma, sat((x - thr) * 2^40) --
-// exact, no compare / SALU / VCC, but the same VALU time and 2 % slower at 8 waves per SIMD.)
-#ifndef LARS_COUNT_MODE
-#define LARS_COUNT_MODE 0
-#endif
-__device__ inline void vcount_gt(unsigned int &lane_counter, float x, float thr) { lane_counter += (x > thr) ? 1u : 0u; }
-__device__ inline void vcount_lt(unsigned int &lane_counter, float x, float thr) { lane_counter += (x < thr) ? 1u : 0u; }
-__device__ inline unsigned int wave_sum_u32(unsigned int v)
-{
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
+// (Tried and dropped: per-lane vector counters (v_cmp + v_addc), and per-lane float counters fed by a saturating packed
+// fma, sat((x - thr) * 2^40) -- exact, no compare / SALU / VCC, but the same VALU time and 2 % slower at 8 waves per SIMD:
+// profiles/r02_count_mode_ab.txt.)
 __device__ inline void count_gt(unsigned int &counter, float x, float thr)      // counter += #lanes(x > thr)
 {
     unsigned int c;
@@ -240,17 +231,6 @@ __device__ inline void count4_lt(unsigned int &counter, const float (&x)[4], flo
     counter += c;
 }
 
-// LARS_COUNT_MODE 3 / template CM == 3: per-lane float counters, two values per instruction:
-//   c = sat(fma(x, +-2^40, -+thr * 2^40))   is exactly 1.0 where x > thr (resp. x < thr) and 0.0 elsewhere -- a value
-// above the threshold is above it by at least one unit in the last place (>= 2^-32 here), which the factor turns into
-// >= 256 -- and   counter += c.   No compare, no VCC, no scalar instruction.  Per-lane sums stay below 2^24.
-__device__ inline void fcount2(f32x2 &counter, f32x2 x, f32x2 k, f32x2 b)
-{
-    f32x2 c;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 clamp" : "=v"(c) : "v"(x), "v"(k), "v"(b));
-    counter += c;
-}
-
 // (Round 2 timed this kernel with single ingredients compiled out -- minimum / maximum, the float64 sums, the coverage counters, the
 // quotient's correction step: profiles/r02_ablation_stats_kernel.txt.  Those builds gave wrong results by construction; the switch
 // left the sources in round 5.)
@@ -262,10 +242,7 @@ __device__ inline void push(WaveAcc &a, unsigned int &above, float x, float thr)
     const double xd = (double)x;
     a.sum += xd;
     if (STATS >= 3) a.sumsq += xd * xd;
-    if (COUNT) {
-        if (LARS_COUNT_MODE == 0) count_gt(above, x, thr);           // wave-uniform scalar counter
-        else vcount_gt(above, x, thr);                               // per-lane counter, folded at flush
-    }
+    if (COUNT) count_gt(above, x, thr);      // COUNT == false: the caller counts, four values at a time or a second threshold
 }
 
 // Histogram bin of an index value of a uint8 tile without looking at the edges.  x = (a-b)/(a+b)
@@ -301,7 +278,7 @@ template <bool OUT> struct V2Block { static constexpr int threads = OUT ? 512 : 
 // SEL >= 1: also count every NDVI / GNDVI value in the 2048 linear buckets of the exact-median select (its first pass,
 // fused: P.sel_hist[tile][stream][track 0][bucket]).  With the 64 KiB table that is exactly 80 KiB of LDS (two blocks
 // per CU) because the reduction scratch then reuses the table's space once the loop is over.
-template <unsigned MASK, bool WB, int STATS, bool OUT, bool NT, int SEL = 0, int CM = LARS_COUNT_MODE>
+template <unsigned MASK, bool WB, int STATS, bool OUT, bool NT, int SEL = 0>
 __global__ __launch_bounds__(V2Block<OUT>::threads, OUT ? 4 : LARS_V2_STATS_WAVES) void k_fused_v2(FusedParams P)
 {
     constexpr int NTHR = V2Block<OUT>::threads;
@@ -341,15 +318,7 @@ __global__ __launch_bounds__(V2Block<OUT>::threads, OUT ? 4 : LARS_V2_STATS_WAVE
     const long long npix = P.npix;
     const uint8_t *base = static_cast<const uint8_t *>(P.tiles) + tile * npix * 3;
 
-    if (WB) {
-        const uint8_t *t = P.wb_table + tile * 768;
-        unsigned int *tab = reinterpret_cast<unsigned int *>(s_tab);
-        // entry (v, copy) at dword v*64 + copy
-        for (int i = tid; i < 256 * 64; i += NTHR) {
-            const int v = i >> 6;
-            tab[i] = (unsigned)t[v] | ((unsigned)t[256 + v] << 8) | ((unsigned)t[512 + v] << 16);
-        }
-    }
+    if (WB) v2_fill_table<NTHR>(s_tab, P.wb_table + tile * 768);
     if (STATS >= 2) {
         for (int i = tid; i < V2_HIST_WORDS; i += NTHR) s_hist[i] = 0;
     }
@@ -366,10 +335,7 @@ __global__ __launch_bounds__(V2Block<OUT>::threads, OUT ? 4 : LARS_V2_STATS_WAVE
     WaveAcc acc_v, acc_g;                                  // NDVI, GNDVI-quotient (NDWI derives from it)
     acc_v.mn = acc_g.mn = __builtin_inff(); acc_v.mx = acc_g.mx = -__builtin_inff();
     acc_v.sum = acc_g.sum = 0; acc_v.sumsq = acc_g.sumsq = 0;
-    unsigned int above_v = 0, above_g = 0, above_w = 0;
-    f32x2 fc_v = {0.0f, 0.0f}, fc_g = {0.0f, 0.0f}, fc_w = {0.0f, 0.0f};          // CM == 3: float counters
-    const f32x2 fc_kp = {1099511627776.0f, 1099511627776.0f}, fc_kn = {-1099511627776.0f, -1099511627776.0f};
-    const f32x2 fc_bt = {-0.2f * 1099511627776.0f, -0.2f * 1099511627776.0f}, fc_b0 = {0.0f, 0.0f};
+    unsigned int above_v = 0, above_g = 0, above_w = 0;    // wave totals (scalar registers)
 
     // OUT == false: statistics only, every output pointer is known to be null at compile time
     float *const oi0 = (OUT && P.out_index[0]) ? P.out_index[0] + tile * npix : nullptr;
@@ -384,19 +350,32 @@ __global__ __launch_bounds__(V2Block<OUT>::threads, OUT ? 4 : LARS_V2_STATS_WAVE
     const unsigned int *lut2 = reinterpret_cast<const unsigned int *>(P.cmap_lut[2]);
 
     const long long nquads = npix >> 2;
-    const long long stride = (long long)gridDim.x * NTHR;
+
+    // what a quotient pair adds to the LDS counters: its histogram bins; its select buckets (SEL == 1) or its words of the
+    // stream's window row (SEL == 2)
+    auto hist_add2 = [&](f32x2 x, float sign, unsigned int bin0) {
+        const f32x2 p = hist_pos2(x, sign);
+        hist_add_pos(p.x, bin0); hist_add_pos(p.y, bin0);
+    };
+    auto select_add2 = [&](f32x2 x, unsigned int bucket_row, float win_bias, unsigned int win_row) {
+        if (SEL == 1) {
+            const f32x2 p = selq_t2(x);
+            selq_add_bucket(p.x, bucket_row); selq_add_bucket(p.y, bucket_row);
+        }
+        if (SEL == 2) {
+            const f32x2 p = __builtin_elementwise_fma(x, (f32x2){SELQ_WIN_SCALE, SELQ_WIN_SCALE}, (f32x2){win_bias, win_bias});
+            selq_window_add(p.x, win_row, win_lo, win_hi); selq_window_add(p.y, win_row, win_lo, win_hi);
+        }
+    };
 
     auto do_quad = [&](long long q, unsigned int w0, unsigned int w1, unsigned int w2) {
-        // bytes: r0 g0 n0 r1 | g1 n1 r2 g2 | n2 r3 g3 n3
-        const unsigned int wr[4] = {w0, w0, w1, w2}, wg[4] = {w0, w1, w1, w2}, wn[4] = {w0, w1, w2, w2};
-        constexpr int br[4] = {0, 3, 2, 1}, bg[4] = {1, 0, 3, 2}, bn[4] = {2, 1, 0, 3};
+        const unsigned int w[3] = {w0, w1, w2};
         if (WB && owb) {
-            unsigned int e[12];
+            unsigned int e[12];                            // the quad's white-balanced bytes, in memory order
 #pragma unroll
             for (int px = 0; px < 4; ++px) {
-                e[3 * px] = sample_entry<WB>(wr[px], br[px], lane_off4, s_tab) & 0xFFu;
-                e[3 * px + 1] = (sample_entry<WB>(wg[px], bg[px], lane_off4, s_tab) >> 8) & 0xFFu;
-                e[3 * px + 2] = (sample_entry<WB>(wn[px], bn[px], lane_off4, s_tab) >> 16) & 0xFFu;
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) e[3 * px + ch] = (quad_entry(w, px, ch, lane_off4, s_tab) >> (8 * ch)) & 0xFFu;
             }
             unsigned int *o = reinterpret_cast<unsigned int *>(owb + q * 12);
             o[0] = e[0] | (e[1] << 8) | (e[2] << 16) | (e[3] << 24);
@@ -404,103 +383,33 @@ __global__ __launch_bounds__(V2Block<OUT>::threads, OUT ? 4 : LARS_V2_STATS_WAVE
             o[2] = e[8] | (e[9] << 8) | (e[10] << 16) | (e[11] << 24);
         }
         if (MASK == 0u) return;
-        // samples -> float (white balanced through the LDS table when WB)
-        float fn[4], fr[4], fg[4];
-#pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            fn[px] = sample<WB>(wn[px], bn[px], 2, lane_off4, s_tab);
-            if (NEED_R) fr[px] = sample<WB>(wr[px], br[px], 0, lane_off4, s_tab);
-            if (NEED_G) fg[px] = sample<WB>(wg[px], bg[px], 1, lane_off4, s_tab);
-        }
-        // quotients, two pixels per packed instruction (v_pk_add/mul/fma_f32)
-        float v0[4], v1[4], v2[4];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const f32x2 N = {fn[2 * h], fn[2 * h + 1]};
-            const f32x2 Ne = N + (f32x2){LARS_DEN_EPS, LARS_DEN_EPS};
-            if (WANT_NDVI) {
-                const f32x2 R = {fr[2 * h], fr[2 * h + 1]};
-                const f32x2 x = exact_quot2(N - R, Ne + R);
+        float v0[4], v1[4], v2[4];                         // NDVI, GNDVI, NDWI
+        quad_quotients<WB, NEED_R, NEED_G>(w, lane_off4, s_tab, [&](auto stream, int h, f32x2 x) {
+            if (decltype(stream)::value == 0) {
                 v0[2 * h] = x.x; v0[2 * h + 1] = x.y;
-                if (STATS >= 1 && CM == 3) fcount2(fc_v, x, fc_kp, fc_bt);
-                if (STATS >= 2) {
-                    const f32x2 p = hist_pos2(x, 1.0f);
-                    hist_add_pos(p.x, hb0); hist_add_pos(p.y, hb0);
-                }
-                if (SEL == 1) {
-                    const f32x2 p = selq_t2(x);
-                    selq_add_bucket(p.x, sb0); selq_add_bucket(p.y, sb0);
-                }
-                if (SEL == 2) {
-                    const f32x2 p = __builtin_elementwise_fma(x, (f32x2){SELQ_WIN_SCALE, SELQ_WIN_SCALE}, (f32x2){wt0, wt0});
-                    selq_window_add(p.x, wr0, win_lo, win_hi); selq_window_add(p.y, wr0, win_lo, win_hi);
-                }
-            }
-            if (NEED_G) {
-                const f32x2 G = {fg[2 * h], fg[2 * h + 1]};
-                const f32x2 x = exact_quot2(N - G, Ne + G);
+                if (STATS >= 2) hist_add2(x, 1.0f, hb0);
+                select_add2(x, sb0, wt0, wr0);
+            } else {
                 v1[2 * h] = x.x; v1[2 * h + 1] = x.y;
-                if (STATS >= 1 && CM == 3 && WANT_GNDVI) fcount2(fc_g, x, fc_kp, fc_bt);
-                if (STATS >= 1 && CM == 3 && WANT_NDWI) fcount2(fc_w, x, fc_kn, fc_b0);          // -x > 0
-                if (STATS >= 2 && WANT_GNDVI) {
-                    const f32x2 p = hist_pos2(x, 1.0f);
-                    hist_add_pos(p.x, hb1); hist_add_pos(p.y, hb1);
-                }
-                if (SEL == 1) {
-                    const f32x2 p = selq_t2(x);
-                    selq_add_bucket(p.x, sb1); selq_add_bucket(p.y, sb1);
-                }
-                if (SEL == 2) {
-                    const f32x2 p = __builtin_elementwise_fma(x, (f32x2){SELQ_WIN_SCALE, SELQ_WIN_SCALE}, (f32x2){wt1, wt1});
-                    selq_window_add(p.x, wr1, win_lo, win_hi); selq_window_add(p.y, wr1, win_lo, win_hi);
-                }
-                if (STATS >= 2 && WANT_NDWI) {
-                    const f32x2 p = hist_pos2(x, -1.0f);
-                    hist_add_pos(p.x, hb2); hist_add_pos(p.y, hb2);
-                }
+                if (STATS >= 2 && WANT_GNDVI) hist_add2(x, 1.0f, hb1);
+                select_add2(x, sb1, wt1, wr1);
+                if (STATS >= 2 && WANT_NDWI) hist_add2(x, -1.0f, hb2);
             }
-        }
+        });
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
-            if (WANT_NDVI) {
-                const float x = v0[px];
-                if (STATS >= 1) push<STATS, (CM == 1 || CM == 2)>(acc_v, above_v, x, 0.2f);
-            }
-            if (NEED_G) {
-                const float x = v1[px];
-                if (STATS >= 1) {
-                    acc_g.mn = fminf(acc_g.mn, x);
-                    acc_g.mx = fmaxf(acc_g.mx, x);
-                    const double xd = (double)x;
-                    acc_g.sum += xd;
-                    if (STATS >= 3) acc_g.sumsq += xd * xd;
-                    if (CM == 1) {
-                        if (WANT_GNDVI) vcount_gt(above_g, x, 0.2f);
-                        if (WANT_NDWI) vcount_lt(above_w, x, 0.0f);           // -x > 0
-                    }
-                }
-                if (WANT_NDWI) {
-                    v2[px] = 0.0f - x;                     // +0.0 where the quotient is zero
-                }
-            }
+            if (STATS >= 1 && WANT_NDVI) push<STATS, false>(acc_v, above_v, v0[px], 0.2f);
+            if (STATS >= 1 && NEED_G) push<STATS, false>(acc_g, above_g, v1[px], 0.2f);
+            if (WANT_NDWI) v2[px] = 0.0f - v1[px];         // +0.0 where the quotient is zero
         }
-        if (STATS >= 1 && CM == 0) {
+        if (STATS >= 1) {
             if (WANT_NDVI) count4_gt(above_v, v0, 0.2f);
             if (WANT_GNDVI) count4_gt(above_g, v1, 0.2f);
             if (WANT_NDWI) count4_lt(above_w, v1, 0.0f);                   // -x > 0
-        } else if (STATS >= 1 && CM == 2) {
-            if (WANT_GNDVI) count4_gt(above_g, v1, 0.2f);
-            if (WANT_NDWI) count4_lt(above_w, v1, 0.0f);
         }
-        if (WANT_NDVI && oi0) {
-            store4<NT>(oi0 + q * 4, v0[0], v0[1], v0[2], v0[3]);
-        }
-        if (WANT_GNDVI && oi1) {
-            store4<NT>(oi1 + q * 4, v1[0], v1[1], v1[2], v1[3]);
-        }
-        if (WANT_NDWI && oi2) {
-            store4<NT>(oi2 + q * 4, v2[0], v2[1], v2[2], v2[3]);
-        }
+        if (WANT_NDVI && oi0) store4<NT>(oi0 + q * 4, v0[0], v0[1], v0[2], v0[3]);
+        if (WANT_GNDVI && oi1) store4<NT>(oi1 + q * 4, v1[0], v1[1], v1[2], v1[3]);
+        if (WANT_NDWI && oi2) store4<NT>(oi2 + q * 4, v2[0], v2[1], v2[2], v2[3]);
         if (WANT_NDVI && oc0)
             *reinterpret_cast<uint4 *>(oc0 + q * 16) = make_uint4(lut0[cmap_index(v0[0])], lut0[cmap_index(v0[1])],
                                                                   lut0[cmap_index(v0[2])], lut0[cmap_index(v0[3])]);
@@ -511,55 +420,17 @@ __global__ __launch_bounds__(V2Block<OUT>::threads, OUT ? 4 : LARS_V2_STATS_WAVE
             *reinterpret_cast<uint4 *>(oc2 + q * 16) = make_uint4(lut2[cmap_index(v2[0])], lut2[cmap_index(v2[1])],
                                                                   lut2[cmap_index(v2[2])], lut2[cmap_index(v2[3])]);
     };
-
-    // Software pipeline: four 12-byte loads in flight per lane while the oldest quad is processed.
-    // buffer_load with the tile as a raw buffer: the lane offset is fixed, the per-iteration offset
-    // is a scalar (no vector address arithmetic), and loads past the end return zeros (no clamps).
-    const long long q0 = (long long)blockIdx.x * NTHR + tid;
-    const long long niter = (nquads + stride - 1) / stride;          // same for every lane of the grid
-    if (niter > 0) {
-        const __amdgpu_buffer_rsrc_t rsrc =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(base), 0, (int)(nquads * 12), 0x00020000);
-        const unsigned int voff = (unsigned int)q0 * 12u;
-        const unsigned int step_b = (unsigned int)stride * 12u;
-        u32x3 w[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = stream_load_b96<LOAD_PLAIN>(rsrc, voff, (unsigned)k * step_b);
-        long long it = 0;
-        unsigned int soff = 4u * step_b;
-        // every lane's quad is in range while it < niter - 1
-        for (; it + 4 <= niter - 1; it += 4) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                // consume slot k, then refill it: the refill lands in the registers just freed
-                // (no copies, no vmcnt(0) at the loop head) and has three quads of work to hide behind
-                do_quad(q0 + (it + k) * stride, w[k].x, w[k].y, w[k].z);
-                __builtin_amdgcn_sched_barrier(0);
-                w[k] = stream_load_b96<LOAD_PLAIN>(rsrc, voff, soff + (unsigned)k * step_b);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            soff += 4u * step_b;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const long long qq = q0 + (it + k) * stride;
-            if (it + k < niter && qq < nquads) do_quad(qq, w[k].x, w[k].y, w[k].z);
-        }
-    }
+    // plain tile loads: profiles/load_policy_kernels.txt
+    for_each_quad_ring<NTHR, LOAD_PLAIN>(base, nquads, do_quad);
 
     // tail pixels (npix % 4): lanes 0..2 of block 0, scalar path
     if (blockIdx.x == 0 && tid < (int)(npix & 3)) {
         const long long i = nquads * 4 + tid;
-        unsigned int r = base[i * 3], g = base[i * 3 + 1], n = base[i * 3 + 2];
-        if (WB) {
-            const unsigned int *tab = reinterpret_cast<const unsigned int *>(s_tab);
-            r = tab[r * 64] & 0xFFu; g = (tab[g * 64] >> 8) & 0xFFu; n = (tab[n * 64] >> 16) & 0xFFu;
-            if (owb) { owb[i * 3] = (uint8_t)r; owb[i * 3 + 1] = (uint8_t)g; owb[i * 3 + 2] = (uint8_t)n; }
-        }
-        const float fr = (float)r, fg = (float)g, fn = (float)n;
+        const TailPixel p = tail_pixel<WB>(base, i, s_tab);
+        if (WB && owb) { owb[i * 3] = (uint8_t)p.r; owb[i * 3 + 1] = (uint8_t)p.g; owb[i * 3 + 2] = (uint8_t)p.n; }
         if (WANT_NDVI) {
-            const float x = norm_diff_fast(fn, fr);
-            if (STATS >= 1) push<STATS>(acc_v, above_v, x, 0.2f);
+            const float x = p.ndvi;
+            if (STATS >= 1) push<STATS, true>(acc_v, above_v, x, 0.2f);
             if (STATS >= 2) hist_add(x, 1.0f, hb0);
             if (SEL == 1) selq_add_bucket(selq_t(x), sb0);
             if (SEL == 2) selq_window_add(__builtin_fmaf(x, SELQ_WIN_SCALE, wt0), wr0, win_lo, win_hi);
@@ -567,21 +438,13 @@ __global__ __launch_bounds__(V2Block<OUT>::threads, OUT ? 4 : LARS_V2_STATS_WAVE
             if (oc0) reinterpret_cast<unsigned int *>(oc0)[i] = lut0[cmap_index(x)];
         }
         if (NEED_G) {
-            const float x = norm_diff_fast(fn, fg);
+            const float x = p.gndvi;
             if (SEL == 1) selq_add_bucket(selq_t(x), sb1);
             if (SEL == 2) selq_window_add(__builtin_fmaf(x, SELQ_WIN_SCALE, wt1), wr1, win_lo, win_hi);
             if (STATS >= 1) {
-                acc_g.mn = fminf(acc_g.mn, x); acc_g.mx = fmaxf(acc_g.mx, x);
-                const double xd = (double)x;
-                acc_g.sum += xd;
-                if (STATS >= 3) acc_g.sumsq += xd * xd;
-                if (CM == 1) {
-                    if (WANT_GNDVI) vcount_gt(above_g, x, 0.2f);
-                    if (WANT_NDWI) vcount_lt(above_w, x, 0.0f);
-                } else {
-                    if (WANT_GNDVI) count_gt(above_g, x, 0.2f);
-                    if (WANT_NDWI) count_lt(above_w, x, 0.0f);
-                }
+                push<STATS, false>(acc_g, above_g, x, 0.2f);
+                if (WANT_GNDVI) count_gt(above_g, x, 0.2f);
+                if (WANT_NDWI) count_lt(above_w, x, 0.0f);             // -x > 0
             }
             if (WANT_GNDVI) {
                 if (STATS >= 2) hist_add(x, 1.0f, hb1);
@@ -601,14 +464,7 @@ __global__ __launch_bounds__(V2Block<OUT>::threads, OUT ? 4 : LARS_V2_STATS_WAVE
     if (STATS >= 2 || SEL) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (RED_ALIASES_TABLE) __syncthreads();               // every wave is done with the table before its space is reused
     if (STATS >= 1) {
-        // wave fold (scalar counters are already wave totals; per-lane ones are summed here)
-        if (CM == 3) {
-            above_v = wave_sum_u32((unsigned int)(fc_v.x + fc_v.y));
-            above_g = wave_sum_u32((unsigned int)(fc_g.x + fc_g.y));
-            above_w = wave_sum_u32((unsigned int)(fc_w.x + fc_w.y));
-        }
-        if ((CM == 1 || CM == 2)) above_v = wave_sum_u32(above_v);
-        if (CM == 1) { above_g = wave_sum_u32(above_g); above_w = wave_sum_u32(above_w); }
+        // wave fold (the counters are already wave totals)
         for (int off = 32; off >= 1; off >>= 1) {
             if (WANT_NDVI) {
                 acc_v.mn = fminf(acc_v.mn, __shfl_xor(acc_v.mn, off)); acc_v.mx = fmaxf(acc_v.mx, __shfl_xor(acc_v.mx, off));
@@ -718,54 +574,21 @@ using namespace lars;
 namespace lars {
 
 
-template <unsigned MASK, bool WB, int STATS>
-static void v2_launch_out(bool out, bool nt, dim3 grid, hipStream_t s, const FusedParams &P)
-{
-    if (!out) hipLaunchKernelGGL((k_fused_v2<MASK, WB, STATS, false, false>), grid, dim3(V2Block<false>::threads), 0, s, P);
-    else if (nt) hipLaunchKernelGGL((k_fused_v2<MASK, WB, STATS, true, true>), grid, dim3(512), 0, s, P);
-    else hipLaunchKernelGGL((k_fused_v2<MASK, WB, STATS, true, false>), grid, dim3(512), 0, s, P);
-}
-template <unsigned MASK, bool WB>
-static void v2_launch_stats(int stats, bool out, bool nt, dim3 grid, hipStream_t s, const FusedParams &P)
-{
-    if (stats == 0) v2_launch_out<MASK, WB, 0>(out, nt, grid, s, P);
-    else if (stats == 1) v2_launch_out<MASK, WB, 1>(out, nt, grid, s, P);
-    else if (stats == 2) v2_launch_out<MASK, WB, 2>(out, nt, grid, s, P);
-    else v2_launch_out<MASK, WB, 3>(out, nt, grid, s, P);
-}
-template <unsigned MASK>
-static void v2_launch_wb(bool wb, int stats, bool out, bool nt, dim3 grid, hipStream_t s, const FusedParams &P)
-{
-    if (wb) v2_launch_stats<MASK, true>(stats, out, nt, grid, s, P);
-    else v2_launch_stats<MASK, false>(stats, out, nt, grid, s, P);
-}
-
-template <unsigned MASK>
-static void v2_launch_sel(bool wb, int stats, dim3 grid, hipStream_t s, const FusedParams &P)
-{
-    const dim3 block(V2Block<false>::threads);
-    // with a predicted window (P.sel_win) the slots inside it are counted as well: basic statistics only
-    if (P.sel_win && stats == 1) {
-        if (wb) hipLaunchKernelGGL((k_fused_v2<MASK, true, 1, false, false, 2>), grid, block, 0, s, P);
-        else hipLaunchKernelGGL((k_fused_v2<MASK, false, 1, false, false, 2>), grid, block, 0, s, P);
-        return;
-    }
-    if (wb && stats >= 3) hipLaunchKernelGGL((k_fused_v2<MASK, true, 3, false, false, 1>), grid, block, 0, s, P);
-    else if (wb && stats == 2) hipLaunchKernelGGL((k_fused_v2<MASK, true, 2, false, false, 1>), grid, block, 0, s, P);
-    else if (wb) hipLaunchKernelGGL((k_fused_v2<MASK, true, 1, false, false, 1>), grid, block, 0, s, P);
-    else if (stats >= 3) hipLaunchKernelGGL((k_fused_v2<MASK, false, 3, false, false, 1>), grid, block, 0, s, P);
-    else if (stats == 2) hipLaunchKernelGGL((k_fused_v2<MASK, false, 2, false, false, 1>), grid, block, 0, s, P);
-    else hipLaunchKernelGGL((k_fused_v2<MASK, false, 1, false, false, 1>), grid, block, 0, s, P);
-}
-// statistics + the select's bucket pass in one kernel (mask 1, 2, 4 or 7; no output planes)
+// statistics + the select's counting pass in one kernel (mask 1, 2, 4 or 7; no output planes)
 void fused_v2_sel_launch(unsigned mask, bool wb, int stats, dim3 grid, hipStream_t s, const FusedParams &P)
 {
-    switch (mask) {
-    case 1u: v2_launch_sel<1u>(wb, stats, grid, s, P); break;
-    case 2u: v2_launch_sel<2u>(wb, stats, grid, s, P); break;
-    case 4u: v2_launch_sel<4u>(wb, stats, grid, s, P); break;
-    default: v2_launch_sel<7u>(wb, stats, grid, s, P); break;
-    }
+    // what is counted next to which statistics: with a predicted window (P.sel_win) the slots inside it, basic statistics
+    // only (0); otherwise the 2048 buckets next to statistics level 1, 2 or 3
+    const int what = (P.sel_win && stats == 1) ? 0 : stats >= 3 ? 3 : stats == 2 ? 2 : 1;
+    with_constant<1u, 2u, 4u, 7u>((int)mask, [&](auto M) {
+        with_constant<false, true>(wb, [&](auto W) {
+            with_constant<0, 1, 2, 3>(what, [&](auto X) {
+                constexpr int STATS = decltype(X)::value ? decltype(X)::value : 1, SEL = decltype(X)::value ? 1 : 2;
+                hipLaunchKernelGGL((k_fused_v2<decltype(M)::value, decltype(W)::value, STATS, false, false, SEL>), grid,
+                                   dim3(V2Block<false>::threads), 0, s, P);
+            });
+        });
+    });
 }
 
 int fused_v2_threads(bool any_out) { return any_out ? V2Block<true>::threads : V2Block<false>::threads; }
@@ -774,13 +597,22 @@ void fused_v2_launch(unsigned mask, bool wb, int stats, bool nt, dim3 grid, hipS
 {
     const bool out = P.out_wb || P.out_index[0] || P.out_index[1] || P.out_index[2] || P.out_rgba[0] || P.out_rgba[1] ||
                      P.out_rgba[2];
-    switch (mask) {
-    case 0u: hipLaunchKernelGGL((k_fused_v2<0u, true, 0, true, false>), grid, dim3(512), 0, s, P); break;
-    case 1u: v2_launch_wb<1u>(wb, stats, out, nt, grid, s, P); break;
-    case 2u: v2_launch_wb<2u>(wb, stats, out, nt, grid, s, P); break;
-    case 4u: v2_launch_wb<4u>(wb, stats, out, nt, grid, s, P); break;
-    default: v2_launch_wb<7u>(wb, stats, out, nt, grid, s, P); break;
+    if (mask == 0u) {                                      // the white-balanced image alone
+        hipLaunchKernelGGL((k_fused_v2<0u, true, 0, true, false>), grid, dim3(V2Block<true>::threads), 0, s, P);
+        return;
     }
+    const int planes = !out ? 0 : nt ? 2 : 1;              // none, plain stores, non-temporal stores
+    with_constant<1u, 2u, 4u, 7u>((int)mask, [&](auto M) {
+        with_constant<false, true>(wb, [&](auto W) {
+            with_constant<0, 1, 2, 3>(stats, [&](auto S) {
+                with_constant<0, 1, 2>(planes, [&](auto O) {
+                    constexpr bool OUT = decltype(O)::value != 0, NT = decltype(O)::value == 2;
+                    hipLaunchKernelGGL((k_fused_v2<decltype(M)::value, decltype(W)::value, decltype(S)::value, OUT, NT>), grid,
+                                       dim3(V2Block<OUT>::threads), 0, s, P);
+                });
+            });
+        });
+    });
 }
 
 void chan_hist_v2_launch(const uint8_t *tiles, long long npix, unsigned int *hist, dim3 grid, hipStream_t s, int channels)

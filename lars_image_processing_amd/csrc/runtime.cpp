@@ -310,9 +310,6 @@ unsigned int lars_build_flags(void)
 #ifdef LARS_IEEE_DIV
     f |= LARS_BUILD_IEEE_DIV;
 #endif
-#if defined(LARS_COUNT_MODE) && LARS_COUNT_MODE != 0
-    f |= LARS_BUILD_COUNT_MODE;
-#endif
 #if LARS_V2_STATS_THREADS != 1024 || LARS_V2_STATS_WAVES != 8
     f |= LARS_BUILD_STATS_GEOMETRY;
 #endif

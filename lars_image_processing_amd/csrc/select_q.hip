@@ -1,7 +1,7 @@
 // Exact medians without index planes: radix select on values recomputed from the tiles.
 // The first (bucket) pass also exists inside the statistics kernel (fused_v2.hip, SEL).
 //
-// WHAT STILL DEPENDS ON THIS FILE (round 4).  Per-tile medians of uint8 RGNir / RGBA batches come out of the one-read route's
+// WHAT DEPENDS ON THIS FILE.  Per-tile medians of uint8 RGNir / RGBA batches come out of the one-read route's
 // finish kernel (joint.hip) since round 3.  These passes remain for: TileBatch.global_medians (ONE median over all tiles of all
 // ranks: histograms are summed over the communicator between the passes, which a per-tile finish cannot do), tile_medians /
 // lars_d_quotient_median_pairs on tables the caller supplied or with planes that carry a white-balanced image, lars_d_stats_medians
@@ -72,14 +72,7 @@ __global__ __launch_bounds__(1024, 8) void k_selq_pass(SelQParams P)
     const long long tile = (PER_TILE && P.tile_list) ? (long long)P.tile_list[blockIdx.y] : (long long)blockIdx.y;
     const long long npix = P.npix;
     const uint8_t *base = P.tiles + tile * npix * 3;
-    if (WB) {
-        const uint8_t *t = P.wb_table + tile * 768;
-        unsigned int *tab = reinterpret_cast<unsigned int *>(s_tab);
-        for (int i = tid; i < 256 * 64; i += 1024) {
-            const int v = i >> 6;
-            tab[i] = (unsigned)t[v] | ((unsigned)t[256 + v] << 8) | ((unsigned)t[512 + v] << 16);
-        }
-    }
+    if (WB) v2_fill_table<1024>(s_tab, P.wb_table + tile * 768);
     for (int i = tid; i < 2 * SELQ_BINS; i += 1024) s_h[i] = 0;
     __syncthreads();
 
@@ -113,43 +106,19 @@ __global__ __launch_bounds__(1024, 8) void k_selq_pass(SelQParams P)
             }
         };
         for_each_quad_ring<1024, POLICY>(base, nquads, [&](long long, unsigned int w0, unsigned int w1, unsigned int w2) {
-            const unsigned int wr[4] = {w0, w0, w1, w2}, wg[4] = {w0, w1, w1, w2}, wn[4] = {w0, w1, w2, w2};
-            constexpr int br[4] = {0, 3, 2, 1}, bg[4] = {1, 0, 3, 2}, bn[4] = {2, 1, 0, 3};
-            float fn[4], fr[4], fg[4], qv[4], qg[4];
-#pragma unroll
-            for (int px = 0; px < 4; ++px) {
-                fn[px] = sample<WB>(wn[px], bn[px], 2, lane_off4, s_tab);
-                if (STREAMS & 1u) fr[px] = sample<WB>(wr[px], br[px], 0, lane_off4, s_tab);
-                if (STREAMS & 2u) fg[px] = sample<WB>(wg[px], bg[px], 1, lane_off4, s_tab);
-            }
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const f32x2 N = {fn[2 * h], fn[2 * h + 1]};
-                const f32x2 Ne = N + (f32x2){LARS_DEN_EPS, LARS_DEN_EPS};
-                if (STREAMS & 1u) {
-                    const f32x2 R = {fr[2 * h], fr[2 * h + 1]};
-                    const f32x2 v = exact_quot2(N - R, Ne + R);
-                    qv[2 * h] = v.x; qv[2 * h + 1] = v.y;
-                }
-                if (STREAMS & 2u) {
-                    const f32x2 G = {fg[2 * h], fg[2 * h + 1]};
-                    const f32x2 g = exact_quot2(N - G, Ne + G);
-                    qg[2 * h] = g.x; qg[2 * h + 1] = g.y;
-                }
-            }
+            const unsigned int w[3] = {w0, w1, w2};
+            float qv[4], qg[4];
+            quad_quotients<WB, (STREAMS & 1u) != 0, (STREAMS & 2u) != 0>(w, lane_off4, s_tab, [&](auto stream, int h, f32x2 x) {
+                float *q = decltype(stream)::value ? qg : qv;
+                q[2 * h] = x.x; q[2 * h + 1] = x.y;
+            });
             if (STREAMS & 1u) push_n(0, qv, 4);
             if (STREAMS & 2u) push_n(1, qg, 4);
         }, every);
         if (every == 1 && blockIdx.x == 0 && tid < (int)(npix & 3)) {
-            const long long i = nquads * 4 + tid;
-            unsigned int r = base[i * 3], g = base[i * 3 + 1], n = base[i * 3 + 2];
-            if (WB) {
-                const unsigned int *tab = reinterpret_cast<const unsigned int *>(s_tab);
-                r = tab[r * 64] & 0xFFu; g = (tab[g * 64] >> 8) & 0xFFu; n = (tab[n * 64] >> 16) & 0xFFu;
-            }
-            const float tv = norm_diff_fast((float)n, (float)r), tg = norm_diff_fast((float)n, (float)g);
-            if (STREAMS & 1u) push_n(0, &tv, 1);
-            if (STREAMS & 2u) push_n(1, &tg, 1);
+            const TailPixel p = tail_pixel<WB>(base, nquads * 4 + tid, s_tab);
+            if (STREAMS & 1u) push_n(0, &p.ndvi, 1);
+            if (STREAMS & 2u) push_n(1, &p.gndvi, 1);
         }
     };
     // rows -> the histogram of `track` (the dummy words are not part of it)
@@ -320,14 +289,7 @@ __global__ __launch_bounds__(1024) void k_selq_predict(const uint8_t *__restrict
     const unsigned int lane = tid & 63u, lane_off4 = lane << 2;
     const long long tile = blockIdx.x;
     const uint8_t *base = tiles + tile * npix * 3;
-    if (WB) {
-        const uint8_t *t = wb_table + tile * 768;
-        unsigned int *tab = reinterpret_cast<unsigned int *>(s_tab);
-        for (int i = tid; i < 256 * 64; i += 1024) {
-            const int v = i >> 6;
-            tab[i] = (unsigned)t[v] | ((unsigned)t[256 + v] << 8) | ((unsigned)t[512 + v] << 16);
-        }
-    }
+    if (WB) v2_fill_table<1024>(s_tab, wb_table + tile * 768);
     for (int i = tid; i < 2 * PRED_BINS; i += 1024) s_h[i] = 0;
     __syncthreads();
     auto pred_bin = [](float t) -> unsigned int { return (__builtin_bit_cast(unsigned int, t) >> 10) & (unsigned)(PRED_BINS - 1); };
@@ -347,18 +309,18 @@ __global__ __launch_bounds__(1024) void k_selq_predict(const uint8_t *__restrict
     auto count_step = [&](const unsigned int (&w)[4][3]) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const unsigned int w0 = w[j][0], w1 = w[j][1], w2 = w[j][2];
-            const unsigned int wr[4] = {w0, w0, w1, w2}, wg[4] = {w0, w1, w1, w2}, wn[4] = {w0, w1, w2, w2};
-            constexpr int br[4] = {0, 3, 2, 1}, bg[4] = {1, 0, 3, 2}, bn[4] = {2, 1, 0, 3};
+            // Not quad_quotients: `streams` is a run-time value here (one instantiation per WB), so a stream nobody asked
+            // for is skipped by a branch, not by a template argument, and these quotients only place the windows -- no
+            // median comes out of them -- so the per-pixel norm_diff_fast is good enough.  Layout and samples are shared.
 #pragma unroll
             for (int px = 0; px < 4; ++px) {
-                const float fn = sample<WB>(wn[px], bn[px], 2, lane_off4, s_tab);
+                const float fn = quad_sample<WB>(w[j], px, 2, lane_off4, s_tab);
                 if (streams & 1u) {
-                    const float fr = sample<WB>(wr[px], br[px], 0, lane_off4, s_tab);
+                    const float fr = quad_sample<WB>(w[j], px, 0, lane_off4, s_tab);
                     atomicAdd(&s_h[pred_bin(selq_t(norm_diff_fast(fn, fr)))], 1u);
                 }
                 if (streams & 2u) {
-                    const float fg = sample<WB>(wg[px], bg[px], 1, lane_off4, s_tab);
+                    const float fg = quad_sample<WB>(w[j], px, 1, lane_off4, s_tab);
                     atomicAdd(&s_h[PRED_BINS + pred_bin(selq_t(norm_diff_fast(fn, fg)))], 1u);
                 }
             }
@@ -539,14 +501,14 @@ static void selq_launch(bool wb, unsigned streams, dim3 grid, hipStream_t s, con
 {
     // plain tile loads by default: profiles/load_policy_kernels.txt
     const bool nt = stream_loads_nt(false);
-#define SELQ_GO(W, S)                                                                                          \
-    do {                                                                                                       \
-        if (nt) hipLaunchKernelGGL((k_selq_pass<W, PER_TILE, S, LOAD_NT>), grid, dim3(1024), 0, s, P);         \
-        else hipLaunchKernelGGL((k_selq_pass<W, PER_TILE, S, LOAD_PLAIN>), grid, dim3(1024), 0, s, P);         \
-    } while (0)
-    if (wb) { if (streams == 1u) SELQ_GO(true, 1u); else if (streams == 2u) SELQ_GO(true, 2u); else SELQ_GO(true, 3u); }
-    else { if (streams == 1u) SELQ_GO(false, 1u); else if (streams == 2u) SELQ_GO(false, 2u); else SELQ_GO(false, 3u); }
-#undef SELQ_GO
+    with_constant<false, true>(wb, [&](auto W) {
+        with_constant<1u, 2u, 3u>((int)streams, [&](auto S) {
+            with_constant<LOAD_PLAIN, LOAD_NT>(nt ? LOAD_NT : LOAD_PLAIN, [&](auto L) {
+                hipLaunchKernelGGL((k_selq_pass<decltype(W)::value, PER_TILE, decltype(S)::value, decltype(L)::value>), grid,
+                                   dim3(1024), 0, s, P);
+            });
+        });
+    });
 }
 
 int selq_pass_launch(const uint8_t *tiles, const uint8_t *wb_table, long long ntiles, long long npix, int first,

@@ -1,6 +1,9 @@
 // Device helpers shared by the second-generation kernels (fused_v2.hip) and the exact-median select
-// (select_q.hip): exact quotient, the white-balance table lookup, the ring load pipeline, the select's bucket.
+// (select_q.hip): exact quotient, the white-balance table and its lookup, the RGB-quad decoder, the tail pixel, the select's
+// bucket, the ring load pipeline, and the helper that picks a kernel instantiation from run-time values.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 #include "device_common.h"
 
@@ -82,6 +85,81 @@ __device__ inline unsigned int sample_entry(unsigned int word, int byte, unsigne
     const unsigned int sel = 0x0c0c0000u | ((4u + (unsigned)byte) << 8);
     const unsigned int addr = __builtin_amdgcn_perm(word, lane_off4, sel);
     return *reinterpret_cast<const unsigned int *>(s_tab + addr);
+}
+
+// The table in LDS, replicated 64x: entry (v, copy) = {R'[v], G'[v], N'[v], 0} at dword v * 64 + copy.
+template <int NTHR>
+__device__ inline void v2_fill_table(char *s_tab, const uint8_t *table768)
+{
+    unsigned int *tab = reinterpret_cast<unsigned int *>(s_tab);
+    for (int i = threadIdx.x; i < 256 * 64; i += NTHR) {
+        const int v = i >> 6;
+        tab[i] = (unsigned)table768[v] | ((unsigned)table768[256 + v] << 8) | ((unsigned)table768[512 + v] << 16);
+    }
+}
+
+// An RGB quad: four pixels in the three dwords w[0..2], bytes  r0 g0 n0 r1 | g1 n1 r2 g2 | n2 r3 g3 n3.
+// Channel ch (0 R, 1 G, 2 NIR) of pixel px is byte 3 * px + ch of the twelve.
+constexpr int quad_word(int px, int ch) { return (3 * px + ch) >> 2; }
+constexpr int quad_byte(int px, int ch) { return (3 * px + ch) & 3; }
+template <bool WB>
+__device__ inline float quad_sample(const unsigned int (&w)[3], int px, int ch, unsigned int lane_off4, const char *s_tab)
+{
+    return sample<WB>(w[quad_word(px, ch)], quad_byte(px, ch), ch, lane_off4, s_tab);
+}
+// the table's whole entry for that sample (the white-balanced byte is byte ch of it)
+__device__ inline unsigned int quad_entry(const unsigned int (&w)[3], int px, int ch, unsigned int lane_off4, const char *s_tab)
+{
+    return sample_entry<true>(w[quad_word(px, ch)], quad_byte(px, ch), lane_off4, s_tab);
+}
+
+// The quad's four NDVI (NEED_R) and / or four GNDVI (NEED_G) quotients, white balanced through the LDS table when WB.
+// Two pixels per packed instruction (v_pk_add / mul / fma_f32); the epsilon goes on NIR once per pair (LARS_DEN_EPS).
+// pair(stream, h, x): x = the quotients of pixels 2h and 2h + 1, stream = integral_constant 0 (NDVI) or 1 (GNDVI).  A callable,
+// not two arrays: the statistics kernel counts each pair in LDS where it is produced, and with all eight quotients first
+// hipcc held four more registers -- past the 64 of 8 waves per SIMD in the widest instantiation (tests/test_registers_cpu.py).
+template <bool WB, bool NEED_R, bool NEED_G, typename F>
+__device__ inline void quad_quotients(const unsigned int (&w)[3], unsigned int lane_off4, const char *s_tab, F &&pair)
+{
+    float fn[4], fr[4], fg[4];
+#pragma unroll
+    for (int px = 0; px < 4; ++px) {
+        fn[px] = quad_sample<WB>(w, px, 2, lane_off4, s_tab);
+        if (NEED_R) fr[px] = quad_sample<WB>(w, px, 0, lane_off4, s_tab);
+        if (NEED_G) fg[px] = quad_sample<WB>(w, px, 1, lane_off4, s_tab);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const f32x2 N = {fn[2 * h], fn[2 * h + 1]};
+        const f32x2 Ne = N + (f32x2){LARS_DEN_EPS, LARS_DEN_EPS};
+        if (NEED_R) {
+            const f32x2 R = {fr[2 * h], fr[2 * h + 1]};
+            pair(std::integral_constant<int, 0>{}, h, exact_quot2(N - R, Ne + R));
+        }
+        if (NEED_G) {
+            const f32x2 G = {fg[2 * h], fg[2 * h + 1]};
+            pair(std::integral_constant<int, 1>{}, h, exact_quot2(N - G, Ne + G));
+        }
+    }
+}
+
+// One pixel of the npix % 4 tail, read byte by byte: its samples (through copy 0 of the table when WB) and both quotients.
+struct TailPixel {
+    unsigned int r, g, n;
+    float ndvi, gndvi;
+};
+template <bool WB>
+__device__ inline TailPixel tail_pixel(const uint8_t *base, long long i, const char *s_tab)
+{
+    TailPixel p;
+    p.r = base[i * 3]; p.g = base[i * 3 + 1]; p.n = base[i * 3 + 2];
+    if (WB) {
+        const unsigned int *tab = reinterpret_cast<const unsigned int *>(s_tab);
+        p.r = tab[p.r * 64] & 0xFFu; p.g = (tab[p.g * 64] >> 8) & 0xFFu; p.n = (tab[p.n * 64] >> 16) & 0xFFu;
+    }
+    p.ndvi = norm_diff_fast((float)p.n, (float)p.r);
+    p.gndvi = norm_diff_fast((float)p.n, (float)p.g);
+    return p;
 }
 
 // Exact-median select on uint8 quotients (select_q.hip; its first pass also lives in the statistics kernel).
@@ -172,6 +250,16 @@ __device__ inline void for_each_quad_ring(const uint8_t *base, long long nquads,
         const long long qq = q0 + (it + k) * stride;
         if (it + k < niter && qq < nquads) f(qq, w[k].x, w[k].y, w[k].z);
     }
+}
+
+// Launch glue: a run-time value as a template argument.  f(std::integral_constant<T, V>{}) for the first V of the list that
+// equals v, and for the last V when none does; f is a generic lambda that names the kernel instantiation.
+template <auto V, auto... Rest, typename F>
+inline void with_constant(int v, F &&f)
+{
+    if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<decltype(V), V>{});
+    else if (v == (int)V) f(std::integral_constant<decltype(V), V>{});
+    else with_constant<Rest...>(v, f);
 }
 
 }  // namespace lars

@@ -69,3 +69,52 @@ def test_one_read_kernels_keep_their_residency(tmp_path):
         assert v["vgpr_count"] <= 128 and v["private_segment_fixed_size"] == 0, (name, v)
         assert v["group_segment_fixed_size"] <= 160 * 1024, (name, v)
     assert all(v["group_segment_fixed_size"] >= 306 * 133 * 4 for v in win.values())
+
+
+def _kernel_metadata(tmp_path, src):
+    """Mangled kernel name -> register, LDS and scratch counts of csrc/<src>, compiled to assembly for gfx950."""
+    out = tmp_path / (src + ".s")
+    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", f"-I{ROOT}/include",
+           "-Wno-pass-failed", "-S", "--cuda-device-only", f"{ROOT}/lars_image_processing_amd/csrc/{src}", "-o", str(out)]
+    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
+    meta = {}
+    for m in re.finditer(r"- \.agpr_count:.*?\n((?:    .*\n)+)", out.read_text()):
+        name = re.search(r"\.name:\s+(\S+)", m.group(1))
+        if name:
+            meta[name.group(1)] = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|group_segment_fixed_size|private_segment_fixed_size):\s+(\d+)", m.group(1))}
+    return meta
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_per_pixel_statistics_kernels_keep_their_shape(tmp_path):
+    """The per-pixel ("classic") route: k_fused_v2 (csrc/fused_v2.hip) and the select passes (csrc/select_q.hip).  The
+    statistics-only kernels and the select pass are VALU-bound and want all 8 waves per SIMD (64 registers, no scratch); with the
+    64 KiB white-balance table and one select row per stream they take exactly 80 KiB of LDS, so that two blocks share a CU (the
+    50-bin histograms of hist=True / sumsq=True add their 9792 bytes on top).  With output planes the budget is 128 registers;
+    the three-index kernels with white balance and planes spill 64 / 76 / 92 bytes (statistics level 1 / 2 / 3) and must not spill
+    more.  The sets of instantiations are what the launch glue selects from: 129 and 24."""
+    v2 = {}
+    for name, v in _kernel_metadata(tmp_path, "fused_v2.hip").items():
+        m = re.search(r"k_fused_v2ILj(\d)ELb([01])ELi(\d)ELb([01])ELb([01])ELi(\d)EEEv", name)
+        if m:
+            v2[tuple(int(x) for x in m.groups())] = v                      # (MASK, WB, STATS, OUT, NT, SEL)
+    assert len(v2) == 129, len(v2)
+    for (mask, wb, stats, out, nt, sel), v in v2.items():
+        key = (mask, wb, stats, out, nt, sel)
+        if not out:
+            assert v["vgpr_count"] <= 64 and v["private_segment_fixed_size"] == 0, (key, v)
+            if wb and sel and stats == 1:
+                assert v["group_segment_fixed_size"] <= 80 * 1024, (key, v)
+        else:
+            scratch = {1: 64, 2: 76, 3: 92}.get(stats, 0) if (mask == 7 and wb) else 0
+            assert v["vgpr_count"] <= 128 and v["private_segment_fixed_size"] <= scratch, (key, v)
+    selq = _kernel_metadata(tmp_path, "select_q.hip")
+    passes = {k: v for k, v in selq.items() if "k_selq_passILb" in k}
+    predict = {k: v for k, v in selq.items() if "k_selq_predictILb" in k}
+    assert len(passes) == 24 and len(predict) == 2, (sorted(passes), sorted(predict))
+    for name, v in passes.items():
+        assert v["vgpr_count"] <= 64 and v["private_segment_fixed_size"] == 0, (name, v)
+        if "k_selq_passILb1E" in name:
+            assert v["group_segment_fixed_size"] <= 80 * 1024, (name, v)
+    for name, v in predict.items():
+        assert v["private_segment_fixed_size"] == 0, (name, v)
