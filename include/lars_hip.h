@@ -1020,6 +1020,66 @@ int lars_h_process_image_zones_polygons(const void *img, int64_t h, int64_t w, i
                                         lars_stats *zone_stats /* [3][npolys] */, float *zone_medians /* [3][npolys][2] */,
                                         void *labels_out /* may be NULL */, int label_bytes);
 
+/* ------------------------------------------------- zones from regions (csrc/regions.hip) */
+/* The label raster of the zone stages, made on the device from the picture itself: the connected regions of a foreground mask
+ * (canopy patches, gaps, wet spots), for callers who hold no outlines at all.
+ *
+ * The definition.  mask is uint8 [h][w], nonzero = foreground; 1 <= h, w and h * w < 2^31.  Two foreground pixels are neighbours
+ * when they share an edge (connectivity 4) or an edge or a corner (connectivity 8).  A region is a maximal connected set of
+ * foreground pixels.  Regions are numbered 1 .. R in raster order of their first pixel, the one with the smallest flat index
+ * y * w + x (scipy.ndimage.label's numbering with the cross / the full 3 x 3 structure).  With min_pixels > 1 the regions of fewer
+ * pixels become 0 and the others are numbered 1 .. R in the same order.  A lars_region holds a region's pixel count, its box
+ * (row0, col0, row1, col1; half-open) and the sums of its pixels' rows and columns: the centroid is (row_sum / area,
+ * col_sum / area).  Integer arithmetic throughout: the result is this definition bit for bit on every run.  R == 0 is a result.
+ *
+ * lars_d_region_label: mask, labels[h][w] (int32), table[capacity] and *count_dev (int64) on the device; scratch:
+ * lars_region_label_scratch_bytes(h, w) bytes (0 for a raster outside the rules), 256-byte aligned.  *count_dev receives R whatever
+ * the capacity is; table rows 0 .. min(R, capacity) - 1 are written (row z - 1 for region z) and nothing beyond them, so a caller
+ * who reads R > capacity has labels and a table that is cut short.  capacity 0 takes table == NULL.  The labels feed
+ * lars_d_zone_count / lars_d_zone_scatter as they are, with zone_bytes 4 and nzones = R (1 .. LARS_ZONES_MAX), and narrow through
+ * lars_d_zone_labels_narrow.  The stages are launches on the stream; no workgroup waits for another.
+ * lars_d_region_mask_f32: mask[i] = (given == NULL || given[i]) && (valid == NULL || valid[i]) && (x == NULL || x[i] > t), or
+ * x[i] < t with below != 0; compared in float32 as the coverage count compares, a NaN is never inside.  x or given is required; given may be mask itself. */
+typedef struct lars_region {
+    int64_t area;
+    int32_t bbox[4];
+    uint64_t row_sum, col_sum;
+} lars_region;
+size_t lars_region_label_scratch_bytes(int64_t h, int64_t w);
+int lars_d_region_label(const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int32_t *labels,
+                        lars_region *table /* [capacity] */, int64_t capacity, int64_t *count_dev, void *scratch, void *stream);
+int lars_d_region_mask_f32(const float *x /* may be NULL */, const uint8_t *given /* may be NULL */, const uint8_t *valid /* may be NULL */,
+                           int64_t npix, float t, int below, uint8_t *mask, void *stream);
+/* label_regions(mask): host mask in, host labels[h][w] and table[capacity] out, *n_regions = R.  label_bytes 1, 2 or 4: the width
+ * of labels; 0: the narrowest of them that holds R, written to *label_bytes_out (labels then needs room for 4 bytes a pixel).
+ * R above capacity, or above what label_bytes holds: LARS_ERR_INVALID with R in *n_regions (-1 after any earlier failure) and
+ * nothing written to labels and table. */
+int lars_h_label_regions(const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int label_bytes, void *labels,
+                         int *label_bytes_out /* may be NULL */, lars_region *table /* [capacity] */, int64_t capacity, int64_t *n_regions);
+/* lars_h_zonal_stats_f32 with the labels made on the device from regions instead of uploaded.  The foreground is mask (host [h][w]
+ * uint8) where it is given, otherwise x > t (mode 1) or x < t (mode 2); pixels outside valid are never foreground.  The labels are
+ * made, the host reads R once, and the four zone stages run with nzones = R: stats[capacity], medians[capacity][2] and
+ * table[capacity] receive R rows.  capacity is 1 .. LARS_ZONES_MAX; R above it: LARS_ERR_INVALID with R in *n_regions.  R == 0
+ * succeeds with nothing written.  labels_out, label_bytes and label_bytes_out as in lars_h_label_regions, labels_out may be NULL. */
+int lars_h_zonal_stats_regions_f32(const float *x, const uint8_t *mask /* may be NULL */, int mode, float t, int connectivity,
+                                   int64_t min_pixels, const uint8_t *valid /* may be NULL */, int64_t h, int64_t w, float threshold,
+                                   int want_hist, int64_t capacity, lars_stats *stats /* [capacity] */, float *medians /* [capacity][2] */,
+                                   lars_region *table /* [capacity] */, int64_t *n_regions, void *labels_out /* may be NULL */,
+                                   int label_bytes, int *label_bytes_out /* may be NULL */);
+/* lars_h_process_image_zones likewise: zone_stats[3][capacity], zone_medians[3][capacity][2] (row k starts at k * capacity).  Without a
+ * mask the plane of index source_index (in index_mask) is compared, as the picture's white balance and mask left it. */
+int lars_h_process_image_regions(const void *img, int64_t h, int64_t w, int channels, int dtype,
+                                 int apply_wb, uint32_t index_mask, int want_hist,
+                                 uint8_t *out_wb, float *const out_index[3],
+                                 lars_stats *stats /* [3] */, float *medians /* [3][2] */,
+                                 uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3],
+                                 const uint8_t *valid, int use_alpha, int has_nodata, int nodata, int64_t *valid_pixels,
+                                 const uint8_t *mask /* may be NULL */, int source_index, int mode, float t, int connectivity,
+                                 int64_t min_pixels, int64_t capacity,
+                                 lars_stats *zone_stats /* [3][capacity] */, float *zone_medians /* [3][capacity][2] */,
+                                 lars_region *table /* [capacity] */, int64_t *n_regions, void *labels_out /* may be NULL */,
+                                 int label_bytes, int *label_bytes_out /* may be NULL */);
+
 /* ------------------------------------------------------------------ multi-GPU */
 /* One process per GPU.  RCCL (librccl.so) is loaded on first use.  unique_id is
  * LARS_COMM_ID_BYTES bytes produced by lars_comm_unique_id() on rank 0 and

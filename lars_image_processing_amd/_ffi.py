@@ -53,6 +53,10 @@ STATS_DTYPE = np.dtype([
 ])
 assert STATS_DTYPE.itemsize == C.sizeof(Stats) == 472
 
+# ``lars_region`` (include/lars_hip.h): one row of the table of label_regions
+REGION_DTYPE = np.dtype([("area", "<i8"), ("bbox", "<i4", (4,)), ("row_sum", "<u8"), ("col_sum", "<u8")])
+assert REGION_DTYPE.itemsize == 40
+
 
 class FusedArgs(C.Structure):
     """``lars_fused_args`` (include/lars_hip.h)."""
@@ -296,6 +300,15 @@ SIGNATURES = {
     "lars_h_process_image_zones_polygons": (_I, [_P, _I64, _I64, _I, _I, _I, _U32, _I, _P, C.POINTER(_P * 3), _P, _P,
                                                  C.POINTER(_P * 3), C.POINTER(_P * 3), _P, _I, _I, _I, C.POINTER(_I64),
                                                  _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I]),
+    "lars_region_label_scratch_bytes": (_SZ, [_I64, _I64]),
+    "lars_d_region_label": (_I, [_P, _I64, _I64, _I, _I64, _P, _P, _I64, _P, _P, _P]),
+    "lars_d_region_mask_f32": (_I, [_P, _P, _P, _I64, _F, _I, _P, _P]),
+    "lars_h_label_regions": (_I, [_P, _I64, _I64, _I, _I64, _I, _P, C.POINTER(_I), _P, _I64, C.POINTER(_I64)]),
+    "lars_h_zonal_stats_regions_f32": (_I, [_P, _P, _I, _F, _I, _I64, _P, _I64, _I64, _F, _I, _I64, _P, _P, _P, C.POINTER(_I64), _P, _I,
+                                            C.POINTER(_I)]),
+    "lars_h_process_image_regions": (_I, [_P, _I64, _I64, _I, _I, _I, _U32, _I, _P, C.POINTER(_P * 3), _P, _P,
+                                          C.POINTER(_P * 3), C.POINTER(_P * 3), _P, _I, _I, _I, C.POINTER(_I64),
+                                          _P, _I, _I, _F, _I, _I64, _I64, _P, _P, _P, C.POINTER(_I64), _P, _I, C.POINTER(_I)]),
     "lars_jpeg_bound": (_SZ, [_I64, _I64, _I, _I]),
     "lars_jpeg_header": (_I64, [_I64, _I64, _I, _I, _I, _P, _SZ]),
     "lars_jpeg_encode_scratch_bytes": (_SZ, [_I64, _I64, _I, _I]),

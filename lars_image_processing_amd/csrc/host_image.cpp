@@ -26,6 +26,10 @@ struct ZoneBufs {
     int32_t *rings, *polys;
     char *raster_scratch;
     char *narrow;                  // the labels at the width the caller wants them back in, where that is not 4
+    // labels made from regions (regions.hip): B.labels is the int32 raster the labelling writes, raster_scratch its scratch
+    uint8_t *rmask;                // [npix] the foreground
+    lars_region *rtable;           // [capacity]
+    int64_t *rcount;               // R
 };
 
 // The polygons of a job, as the entry points take them (include/lars_hip.h "zones from polygons"); nzones = npolys.
@@ -36,7 +40,22 @@ struct ZonePolys {
     void *labels_out; int label_bytes;     // host [h][w] labels back, or null
 };
 
-ZoneBufs zone_plan(Carver &c, size_t npix, int zone_bytes, int64_t nzones, uint32_t mask, const ZonePolys *P = nullptr)
+// The regions of a job (include/lars_hip.h "zones from regions"): nzones is known only once the labels exist, the buffers are sized
+// by the capacity of the caller's record arrays.
+struct ZoneRegions {
+    const uint8_t *mask;                   // host [h][w] foreground, or null: the plane `source` above (mode 1) or below (mode 2) t
+    int source, mode;
+    float t;
+    int connectivity;
+    int64_t min_pixels, capacity;
+    lars_region *table_out;                // host [capacity]
+    int64_t *n_regions;
+    void *labels_out; int label_bytes; int *label_bytes_out;     // host [h][w] labels back, or null; label_bytes 0: the narrowest
+    int64_t h, w;
+};
+
+ZoneBufs zone_plan(Carver &c, size_t npix, int zone_bytes, int64_t nzones, uint32_t mask, const ZonePolys *P = nullptr,
+                   const ZoneRegions *G = nullptr)
 {
     ZoneBufs B;
     memset(&B, 0, sizeof B);
@@ -47,6 +66,13 @@ ZoneBufs zone_plan(Carver &c, size_t npix, int zone_bytes, int64_t nzones, uint3
         B.polys = c.take<int32_t>((size_t)P->npolys + 1);
         B.raster_scratch = c.take<char>(lars_zone_rasterize_scratch_bytes(P->npolys));
         B.narrow = (P->labels_out && P->label_bytes != 4) ? c.take<char>(npix * (size_t)P->label_bytes) : nullptr;
+    }
+    if (G) {
+        B.rmask = c.take<uint8_t>(npix);
+        B.rtable = c.take<lars_region>((size_t)G->capacity);
+        B.rcount = c.take<int64_t>(1);
+        B.raster_scratch = c.take<char>(lars_region_label_scratch_bytes(G->h, G->w));
+        B.narrow = (G->labels_out && G->label_bytes != 4) ? c.take<char>(npix * 2) : nullptr;
     }
     B.labels = c.take<char>(npix * (size_t)zone_bytes);
     B.counts = c.take<uint64_t>(nz + 2);
@@ -101,16 +127,66 @@ int raster_zones(const ZoneBufs &B, const ZonePolys &P, int64_t h, int64_t w, hi
     return LARS_OK;
 }
 
-// labels up (or made from the polygons P, zone_bytes 4), the four stages, the records down (host_stats[3][nzones], host_med[3][nzones][2]; rows outside mask untouched).
+// What the region entry points check before they touch the device.
+int check_regions(const char *who, const ZoneRegions &G, int64_t most)
+{
+    if (G.h < 1 || G.w < 1 || !lars_region_label_scratch_bytes(G.h, G.w))
+        return fail(LARS_ERR_INVALID, "%s: the raster is 1 or more on each side and has fewer than 2^31 pixels", who);
+    if (!G.mask && G.mode != 1 && G.mode != 2) return fail(LARS_ERR_INVALID, "%s: a mask, or mode 1 (above t) or 2 (below t), is required", who);
+    if (G.connectivity != 4 && G.connectivity != 8) return fail(LARS_ERR_INVALID, "%s: connectivity must be 4 or 8, got %d", who, G.connectivity);
+    if (G.min_pixels < 1) return fail(LARS_ERR_INVALID, "%s: min_pixels must be 1 or more, got %lld", who, (long long)G.min_pixels);
+    if (G.capacity < 1 || G.capacity > most || !G.table_out || !G.n_regions)
+        return fail(LARS_ERR_INVALID, "%s: a table of capacity 1 to %lld and n_regions are required, got %lld", who, (long long)most, (long long)G.capacity);
+    if (G.labels_out && G.label_bytes != 0 && G.label_bytes != 1 && G.label_bytes != 2 && G.label_bytes != 4)
+        return fail(LARS_ERR_INVALID, "%s: labels come back 1, 2 or 4 bytes wide (0: the narrowest), got %d", who, G.label_bytes);
+    if (G.labels_out && !aligned_to(G.labels_out, 4)) return fail(LARS_ERR_INVALID, "%s: the labels are not aligned", who);
+    return LARS_OK;
+}
+
+// The foreground (uploaded, or the plane against t; never outside valid_dev), its labels into B.labels (int32) and R to the host: the one
+// wait of this route.  R above the capacity ends the call; otherwise the table's R rows and, where wanted, the labels follow on the stream.
+int label_zone_regions(const char *who, const ZoneBufs &B, const ZoneRegions &G, const float *plane, const uint8_t *valid_dev, int64_t *nzones,
+                       hipStream_t s)
+{
+    const size_t npix = (size_t)G.h * (size_t)G.w;
+    if (G.mask) LARS_HIP_TRY(hipMemcpyAsync(B.rmask, G.mask, npix, hipMemcpyHostToDevice, s));
+    if (!G.mask || valid_dev)
+        LARS_TRY(lars_d_region_mask_f32(G.mask ? nullptr : plane, G.mask ? B.rmask : nullptr, valid_dev, (int64_t)npix, G.t, G.mode == 2, B.rmask, s));
+    int32_t *labels = reinterpret_cast<int32_t *>(B.labels);
+    LARS_TRY(lars_d_region_label(B.rmask, G.h, G.w, G.connectivity, G.min_pixels, labels, B.rtable, G.capacity, B.rcount, B.raster_scratch, s));
+    int64_t r = -1;
+    LARS_HIP_TRY(hipMemcpyAsync(&r, B.rcount, sizeof r, hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipStreamSynchronize(s));
+    *G.n_regions = r;
+    int bytes = G.label_bytes ? G.label_bytes : r <= 255 ? 1 : r <= 65535 ? 2 : 4;
+    if (r < 0 || r > G.capacity || (G.labels_out && ((bytes == 1 && r > 255) || (bytes == 2 && r > 65535))))
+        return fail(LARS_ERR_INVALID, "%s: %lld regions; the capacity is %lld%s", who, (long long)r, (long long)G.capacity,
+                    r <= G.capacity ? " and the labels are too narrow for them" : "");
+    *nzones = r;
+    if (r) LARS_HIP_TRY(hipMemcpyAsync(G.table_out, B.rtable, (size_t)r * sizeof(lars_region), hipMemcpyDeviceToHost, s));
+    if (!G.labels_out) return LARS_OK;
+    if (G.label_bytes_out) *G.label_bytes_out = bytes;
+    if (bytes != 4) LARS_TRY(lars_d_zone_labels_narrow(labels, (int64_t)npix, bytes, B.narrow, s));
+    LARS_HIP_TRY(hipMemcpyAsync(G.labels_out, bytes != 4 ? B.narrow : B.labels, npix * (size_t)bytes, hipMemcpyDeviceToHost, s));
+    return LARS_OK;
+}
+
+// labels up (or made from the polygons P or the regions G, zone_bytes 4), the four stages, the records down (host_stats[3][nzones], host_med[3][nzones][2]; rows outside mask untouched).
 // The counts cross to the host once: bad labels end the call there, and zones above the knob zone_split_pixels take the array
 // kernels, which spread one zone over many workgroups.  The copies down are on the stream when this returns: the caller waits.
 int run_zones(const char *who, const ZoneBufs &B, const void *zones, int zone_bytes, const uint8_t *valid_dev, int64_t npix, int64_t nzones,
               const float *const planes[3], uint32_t mask, const float thr[3], int want_hist, lars_stats *host_stats, float *host_med,
-              int64_t *bad_labels, hipStream_t s, const ZonePolys *P = nullptr, int64_t h = 0, int64_t w = 0)
+              int64_t *bad_labels, hipStream_t s, const ZonePolys *P = nullptr, int64_t h = 0, int64_t w = 0, const ZoneRegions *G = nullptr)
 {
+    // with regions nzones becomes R here and the host rows keep the stride of the caller's capacity; no region is a result, not an error
+    const size_t host_stride = (size_t)(G ? G->capacity : nzones);
+    if (G) {
+        LARS_TRY(label_zone_regions(who, B, *G, planes[G->source], valid_dev, &nzones, s));
+        if (!nzones) return LARS_OK;
+    }
     const size_t nz = (size_t)nzones;
     if (P) LARS_TRY(raster_zones(B, *P, h, w, s));
-    else LARS_HIP_TRY(hipMemcpyAsync(B.labels, zones, (size_t)npix * zone_bytes, hipMemcpyHostToDevice, s));
+    else if (!G) LARS_HIP_TRY(hipMemcpyAsync(B.labels, zones, (size_t)npix * zone_bytes, hipMemcpyHostToDevice, s));
     LARS_TRY(lars_d_zone_count(B.labels, zone_bytes, valid_dev, npix, nzones, B.counts, B.counts + nz + 1, s));
     std::vector<uint64_t> counts(nz + 2);
     LARS_HIP_TRY(hipMemcpyAsync(counts.data(), B.counts, (nz + 2) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -132,8 +208,8 @@ int run_zones(const char *who, const ZoneBufs &B, const void *zones, int zone_by
             LARS_TRY(lars_d_array_stats_f32(B.out[k] + lo, (int64_t)counts[z], thr[k], want_hist, st + (z - 1), s));
             LARS_TRY(lars_d_median_pair_f32(B.out[k] + lo, (int64_t)counts[z], med + 2 * (z - 1), B.sel, s));
         }
-        LARS_HIP_TRY(hipMemcpyAsync(host_stats + k * nz, st, nz * sizeof(lars_stats), hipMemcpyDeviceToHost, s));
-        LARS_HIP_TRY(hipMemcpyAsync(host_med + 2 * k * nz, med, 2 * nz * sizeof(float), hipMemcpyDeviceToHost, s));
+        LARS_HIP_TRY(hipMemcpyAsync(host_stats + k * host_stride, st, nz * sizeof(lars_stats), hipMemcpyDeviceToHost, s));
+        LARS_HIP_TRY(hipMemcpyAsync(host_med + 2 * k * host_stride, med, 2 * nz * sizeof(float), hipMemcpyDeviceToHost, s));
     }
     return LARS_OK;
 }
@@ -183,6 +259,7 @@ struct ImageJob {
     float *zone_medians;          // [3][nzones][2]
     int64_t *bad_labels;
     const ZonePolys *polys;       // ... or the plots' outlines instead of zones: the labels are made on the device (zone_raster.hip)
+    const ZoneRegions *regions;   // ... or the connected regions of a mask or of a thresholded plane (regions.hip); nzones = their capacity
 };
 
 // The head every picture entry point shares, in the order of their prototypes; each entry point adds only what is its own.
@@ -294,7 +371,7 @@ Route route_of(const ImageJob &j)
         const bool for_caller = j.out_index[k] != nullptr;                       // it is copied back
         const bool for_entries = r.entry[k];                                     // the entry plane is derived from it on the device
         const bool for_tiff = j.tiff != 0;                                       // its file is encoded from it
-        const bool for_zones = j.zones != nullptr || j.polys != nullptr;         // the zone stages scatter it
+        const bool for_zones = j.zones != nullptr || j.polys != nullptr || j.regions != nullptr;   // the zone stages scatter it
         const bool for_median = r.medians && r.planes == Route::FUSED;           // the select over the plane reads it
         r.plane[k] = on && (for_caller || for_entries || for_tiff || for_zones || for_median);
     }
@@ -362,7 +439,7 @@ Layout plan(const ImageJob &j, const Route &r, Carver &c)
     L.vhist = (j.masked && j.apply_wb) ? c.take<uint32_t>(3 * nval) : nullptr;
     for (int k = 0; k < 3; ++k)
         L.vals[k] = (j.masked && ((j.mask >> k) & 1u) && (j.stats || j.medians)) ? c.take<float>(npix) : nullptr;
-    if (j.zones || j.polys) L.zone = zone_plan(c, npix, j.zone_bytes, j.nzones, j.mask, j.polys);
+    if (j.zones || j.polys || j.regions) L.zone = zone_plan(c, npix, j.zone_bytes, j.nzones, j.mask, j.polys, j.regions);
     return L;
 }
 
@@ -446,10 +523,10 @@ int run_masked(const ImageJob &j, const Layout &L, hipStream_t s)
         if (j.stats) LARS_TRY(lars_d_array_stats_f32(L.vals[k], (int64_t)nvalid, k == LARS_NDWI ? 0.0f : 0.2f, j.want_hist, L.stats + k, s));
         if (j.medians) LARS_TRY(lars_d_median_pair_f32(L.vals[k], (int64_t)nvalid, L.med + 2 * k, L.sel + k * select_slot(), s));
     }
-    if (!j.zones && !j.polys) return LARS_OK;
+    if (!j.zones && !j.polys && !j.regions) return LARS_OK;
     const float thr[3] = {0.2f, 0.2f, 0.0f};                // as the records above
     return run_zones(j.who, L.zone, j.zones, j.zone_bytes, L.vmask, npix, j.nzones, L.idx, j.mask, thr, j.want_hist, j.zone_stats,
-                     j.zone_medians, j.bad_labels, s, j.polys, j.h, j.w);
+                     j.zone_medians, j.bad_labels, s, j.polys, j.h, j.w, j.regions);
 }
 
 // ---- stage 4: the planes and pictures back, entry planes and PNG files built from what stays on the device ----
@@ -678,20 +755,44 @@ int lars_h_process_image_zones_polygons(const void *img, int64_t h, int64_t w, i
     return run_image(j);
 }
 
+int lars_h_process_image_regions(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                                 int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                                 uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], const uint8_t *valid, int use_alpha,
+                                 int has_nodata, int nodata, int64_t *valid_pixels, const uint8_t *mask, int source_index, int mode, float t,
+                                 int connectivity, int64_t min_pixels, int64_t capacity, lars_stats *zone_stats, float *zone_medians,
+                                 lars_region *table, int64_t *n_regions, void *labels_out, int label_bytes, int *label_bytes_out)
+{
+    static const char *who = "lars_h_process_image_regions";
+    if (valid_pixels) *valid_pixels = -1;
+    if (n_regions) *n_regions = -1;
+    LARS_TRY(check_picture(who, img, h, w, channels, dtype, index_mask, use_alpha, has_nodata, nodata, out_rgba, cmap_lut));
+    if (!index_mask || (index_mask & ~LARS_MASK_ALL)) return fail(LARS_ERR_INVALID, "%s: index_mask must name one to three indices", who);
+    if (!zone_stats || !zone_medians) return fail(LARS_ERR_INVALID, "%s: the zones' records and medians are required", who);
+    if (!mask && (source_index < 0 || source_index > 2 || !((index_mask >> source_index) & 1u)))
+        return fail(LARS_ERR_INVALID, "%s: source_index %d is not among the indices of index_mask", who, source_index);
+    const ZoneRegions G = {mask, mask ? 0 : source_index, mode, t, connectivity, min_pixels, capacity, table, n_regions, labels_out, label_bytes,
+                           label_bytes_out, h, w};
+    LARS_TRY(check_regions(who, G, LARS_ZONES_MAX));
+    ImageJob j = picture_job(who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut);
+    under_mask(j, valid, use_alpha, has_nodata, nodata, valid_pixels);
+    j.regions = &G; j.zone_bytes = 4; j.nzones = capacity; j.zone_stats = zone_stats; j.zone_medians = zone_medians;
+    return run_image(j);
+}
+
 }  // extern "C"
 
 namespace {
 
 // zonal_statistics of a host plane, with the labels uploaded (zones) or rasterised (P)
 int zonal_stats(const char *who, const float *x, const void *zones, int zone_bytes, const ZonePolys *P, const uint8_t *valid, int64_t h, int64_t w,
-                int64_t nzones, float threshold, int want_hist, lars_stats *stats, float *medians, int64_t *bad_labels)
+                int64_t nzones, float threshold, int want_hist, lars_stats *stats, float *medians, int64_t *bad_labels, const ZoneRegions *G = nullptr)
 {
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (!x || h <= 0 || w <= 0) return fail(LARS_ERR_INVALID, "%s: x must be a non-empty [h][w] float32 array", who);
-    if (P) {
+    if (P || G) {
         if (!stats || !medians) return fail(LARS_ERR_INVALID, "%s: the zones' records and medians are required", who);
-        LARS_TRY(check_polygons(who, *P, h, w));
+        LARS_TRY(P ? check_polygons(who, *P, h, w) : check_regions(who, *G, LARS_ZONES_MAX));
     } else {
         LARS_TRY(zone_arguments(who, zones, zone_bytes, nzones, stats, medians));
     }
@@ -702,14 +803,14 @@ int zonal_stats(const char *who, const float *x, const void *zones, int zone_byt
     LARS_TRY(ws_plan(c, [&](Carver &d) {
         dx = d.take<float>(npix);
         dvalid = valid ? d.take<uint8_t>(npix) : nullptr;
-        B = zone_plan(d, npix, zone_bytes, nzones, 1u, P);
+        B = zone_plan(d, npix, zone_bytes, nzones, 1u, P, G);
     }));
     hipStream_t s = c->stream;
     LARS_HIP_TRY(hipMemcpyAsync(dx, x, npix * sizeof(float), hipMemcpyHostToDevice, s));
     if (valid) LARS_HIP_TRY(hipMemcpyAsync(dvalid, valid, npix, hipMemcpyHostToDevice, s));
     const float *planes[3] = {dx, nullptr, nullptr};
     const float thr[3] = {threshold, threshold, threshold};
-    LARS_TRY(run_zones(who, B, zones, zone_bytes, dvalid, (int64_t)npix, nzones, planes, 1u, thr, want_hist, stats, medians, bad_labels, s, P, h, w));
+    LARS_TRY(run_zones(who, B, zones, zone_bytes, dvalid, (int64_t)npix, nzones, planes, 1u, thr, want_hist, stats, medians, bad_labels, s, P, h, w, G));
     LARS_HIP_TRY(hipStreamSynchronize(s));
     return LARS_OK;
 }
@@ -731,6 +832,42 @@ int lars_h_zonal_stats_polygons_f32(const float *x, const double *verts, int64_t
 {
     const ZonePolys P = {verts, nverts, ring_starts, nrings, poly_starts, npolys, labels_out, label_bytes};
     return zonal_stats("lars_h_zonal_stats_polygons_f32", x, nullptr, 4, &P, valid, h, w, npolys, threshold, want_hist, stats, medians, nullptr);
+}
+
+int lars_h_zonal_stats_regions_f32(const float *x, const uint8_t *mask, int mode, float t, int connectivity, int64_t min_pixels,
+                                   const uint8_t *valid, int64_t h, int64_t w, float threshold, int want_hist, int64_t capacity, lars_stats *stats,
+                                   float *medians, lars_region *table, int64_t *n_regions, void *labels_out, int label_bytes, int *label_bytes_out)
+{
+    if (n_regions) *n_regions = -1;
+    const ZoneRegions G = {mask, 0, mode, t, connectivity, min_pixels, capacity, table, n_regions, labels_out, label_bytes, label_bytes_out, h, w};
+    return zonal_stats("lars_h_zonal_stats_regions_f32", x, nullptr, 4, nullptr, valid, h, w, capacity, threshold, want_hist, stats, medians, nullptr, &G);
+}
+
+int lars_h_label_regions(const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int label_bytes, void *labels,
+                         int *label_bytes_out, lars_region *table, int64_t capacity, int64_t *n_regions)
+{
+    static const char *who = "lars_h_label_regions";
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (n_regions) *n_regions = -1;
+    if (!mask || !labels) return fail(LARS_ERR_INVALID, "%s: mask and labels are required", who);
+    const ZoneRegions G = {mask, 0, 0, 0.0f, connectivity, min_pixels, capacity, table, n_regions, labels, label_bytes, label_bytes_out, h, w};
+    LARS_TRY(check_regions(who, G, 0x7FFFFFFF));
+    ZoneBufs B;
+    memset(&B, 0, sizeof B);
+    const size_t npix = (size_t)h * (size_t)w;
+    LARS_TRY(ws_plan(c, [&](Carver &d) {
+        B.labels = d.take<char>(npix * 4);
+        B.rmask = d.take<uint8_t>(npix);
+        B.rtable = d.take<lars_region>((size_t)capacity);
+        B.rcount = d.take<int64_t>(1);
+        B.raster_scratch = d.take<char>(lars_region_label_scratch_bytes(h, w));
+        B.narrow = label_bytes != 4 ? d.take<char>(npix * 2) : nullptr;
+    }));
+    int64_t r = 0;
+    LARS_TRY(label_zone_regions(who, B, G, nullptr, nullptr, &r, c->stream));
+    LARS_HIP_TRY(hipStreamSynchronize(c->stream));
+    return LARS_OK;
 }
 
 int lars_h_rasterize_zones(const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts,

@@ -21,6 +21,7 @@ from pathlib import Path
 import numpy as np
 
 from . import api, codecs, nodata as nodata_rules
+from ._ffi import INDEX_NAMES
 
 EXTENSIONS = {".tif", ".tiff", ".png", ".jpg", ".jpeg"}      # backend-process.py:89
 # zlib level of the per-pixel colormap PNGs: encoding, not the GPU, bounds the directory driver (a 2048x2048 RGBA map takes
@@ -78,12 +79,14 @@ def _mask_argument(mask_kw):
     return (mask_kw,) if mask_kw else ()
 
 
-def _zones_argument(zones, zones_transform=None):
-    """``_process_image``'s ``zones`` (and ``zones_transform``) keywords, handed over only where they are named: without them the call is
-    the one it always was."""
+def _zones_argument(zones, zones_transform=None, regions=None):
+    """``_process_image``'s ``zones`` (and ``zones_transform``, ``regions``) keywords, handed over only where they are named: without them
+    the call is the one it always was."""
     kw = {} if zones is None else {"zones": zones}
     if zones_transform is not None:
         kw["zones_transform"] = zones_transform
+    if regions is not None:
+        kw["regions"] = regions
     return kw
 
 
@@ -117,20 +120,40 @@ def _transform_numbers(text):
     return numbers
 
 
+def _regions_spec(text):
+    """``--regions INDEX:above:T[:min_pixels]`` (or ``below``) -> (index, "above" / "below", T, min_pixels)."""
+    import argparse
+    parts = text.split(":")
+    try:
+        if len(parts) not in (3, 4) or parts[0] not in INDEX_NAMES or parts[1] not in ("above", "below"):
+            raise ValueError
+        spec = (parts[0], parts[1], float(parts[2]), int(parts[3]) if len(parts) == 4 else 1)
+        if spec[3] < 1 or spec[2] != spec[2]:
+            raise ValueError
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"INDEX:above:T[:min_pixels] or INDEX:below:T[:min_pixels] with INDEX one of {', '.join(INDEX_NAMES)} "
+                                         f"is needed, got {text!r}") from None
+    return spec
+
+
 ZONE_CSV_COLUMNS = ("Zone", "Index", "Pixels", "Mean", "Median", "Min", "Max", "Coverage (%)")
+REGION_CSV_COLUMNS = ("Area", "Row0", "Col0", "Row1", "Col1", "Centroid Row", "Centroid Col")
 
 
 def _write_zones_csv(path, result, indices):
-    """``<stem>_zones.csv``: one row per zone and index from ``zones.zonal_rows``, floats written with ``repr`` (they read back exactly)."""
+    """``<stem>_zones.csv``: one row per zone and index from ``zones.zonal_rows``, floats written with ``repr`` (they read back exactly).
+    Zones that are regions of the picture (``regions=``) add their area, box and centroid to every row."""
     import csv
     from .zones import zonal_rows
+    table = result["zones"].get("regions")
     with open(path, "w", newline="") as f:
         out = csv.writer(f)
-        out.writerow(ZONE_CSV_COLUMNS)
+        out.writerow(ZONE_CSV_COLUMNS + (REGION_CSV_COLUMNS if table is not None else ()))
         for t in indices:
-            for row in zonal_rows(result, t):
+            for i, row in enumerate(zonal_rows(result, t)):
                 figures = [v for k, v in row.items() if k not in ("Zone", "Pixels")]      # analyze_index's five, in its order
-                out.writerow([row["Zone"], t, row["Pixels"]] + [repr(v) for v in figures])
+                region = [] if table is None else [int(table["area"][i])] + [int(v) for v in table["bbox"][i]] + [repr(float(v)) for v in table["centroid"][i]]
+                out.writerow([row["Zone"], t, row["Pixels"]] + [repr(v) for v in figures] + region)
 
 
 def _matching(png_encoder, tiff_encoder):
@@ -143,7 +166,7 @@ def _matching(png_encoder, tiff_encoder):
 
 def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png",
                   png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow", tiff_encoder="pillow",
-                  index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None):
+                  index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None, regions=None):
     """One file: same outputs as backend-process.py:49-73.  Returns the statistics dicts.
     ``full_depth=True`` reads three-sample 16-bit TIFFs at their full depth (``tiffio.read_image``; Pillow, hence the
     reference, keeps their high bytes only).  ``lut_format="tiff"`` writes the colormap images as
@@ -174,7 +197,10 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     unchanged; the statistics come from a call of their own.  A ``zones`` path that ends in ``.geojson`` / ``.json`` holds the plots'
     outlines instead (``zones.polygons_from_geojson``; zone ``k`` is the ``k``-th geometry of the file): they are rasterised on the
     device (``zones.rasterize_zones``'s rule), in pixel coordinates or, with ``zones_transform=(x0, dx, rx, y0, ry, dy)``, in the
-    world coordinates of that GDAL geotransform.  The CSV has the same columns either way."""
+    world coordinates of that GDAL geotransform.  The CSV has the same columns either way.
+    ``regions=(index, "above" | "below", t, min_pixels)`` takes the zones from the picture instead (``zones.Regions``): the connected
+    patches of ``index`` above / below ``t`` with ``min_pixels`` pixels or more, labelled on the device; the same CSV with each region's
+    area, box and centroid added.  ``index`` must be among the requested indices; not together with ``zones``."""
     if lut_format not in ("png", "png8", "tiff"):
         raise ValueError(f"lut_format must be 'png', 'png8' or 'tiff', got {lut_format!r}")
     _check_png_encoder(png_encoder)
@@ -186,11 +212,11 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     block, png_encoder, tiff_encoder = _matching(png_encoder, tiff_encoder)
     with block:
         return _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder,
-                              tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw), **_zones_argument(zones, zones_transform))
+                              tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw), **_zones_argument(zones, zones_transform, regions))
 
 
 def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder, tiff_decoder,
-                   tiff_encoder, index_tiff, mask_kw=None, zones=None, zones_transform=None):
+                   tiff_encoder, index_tiff, mask_kw=None, zones=None, zones_transform=None, regions=None):
     """``process_image`` behind its checks, for ``"pillow"``, ``"device"`` and ``"device+deflate"``."""
     from PIL import Image
     from .tiffio import read_image
@@ -201,9 +227,17 @@ def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_
         raise ValueError(f"{image_path.name}: expected an image with at least 3 channels, got shape {arr.shape}")
     indices = list(indices or [])
     mask_kw = mask_kw or {}
+    if regions is not None and zones is not None:
+        raise ValueError("regions and zones both name the zones of the picture: give one of them")
+    if regions is not None:
+        from .zones import Regions
+        index, how, t, min_pixels = regions
+        if index not in indices:
+            raise ValueError(f"regions are taken from {index}, which is not among the requested indices {indices}")
+        zones = Regions(index=index, min_pixels=min_pixels, **{how: t})
     if zones is not None and indices:
         from .zones import process_image_zones
-        labels = _read_zones(zones, zones_transform, arr.shape[:2], image_path.name)
+        labels = zones if regions is not None else _read_zones(zones, zones_transform, arr.shape[:2], image_path.name)
         output_dir.mkdir(parents=True, exist_ok=True)
         _write_zones_csv(output_dir / f"{name}_zones.csv",
                          process_image_zones(arr, labels, **mask_kw, indices=indices, white_balance=True, want_arrays=False), indices)
@@ -282,13 +316,13 @@ def files_of_rank(files, rank=0, world=1):
 def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, process_gndvi=False,
                   process_ndwi=True, workers=4, verbose=True, full_depth=False, lut_format="png", rank=0, world=1,
                   device=None, png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow",
-                  tiff_encoder="pillow", index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None):
+                  tiff_encoder="pillow", index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None, regions=None):
     """backend-process.py:75-97 with its module constants as arguments.  Returns ``{file name: stats | error}``.
     ``rank`` / ``world``: one process per GPU, each takes its block of the sorted file list (``files_of_rank``); the output
     directories are shared, the file names distinct.  ``device``: the GPU ordinal every worker thread binds (the library's
     context is per thread and defaults to device 0); None leaves the threads' binding alone.  ``png_encoder``,
     ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``, ``tiff_encoder``, ``index_tiff``, ``nodata``, ``alpha_mask``, ``zones`` (one label
-    raster, or one file of polygons with its ``zones_transform``, for every file of the directory): see ``process_image``."""
+    raster, or one file of polygons with its ``zones_transform``, for every file of the directory), ``regions``: see ``process_image``."""
     mask_kw = _mask_options(nodata, alpha_mask, lut_format)
     _check_tiff_encoder(tiff_encoder)
     _check_png_encoder(png_encoder)
@@ -309,7 +343,7 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
                 print(f"Processing {idx}/{total}: {f.name}")
             return f.name, _process_image(f, output_path, process_wb, indices or None, full_depth, lut_format, png_encoder,
                                           png_decoder, jpeg_decoder, tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw),
-                                          **_zones_argument(zones, zones_transform))
+                                          **_zones_argument(zones, zones_transform, regions))
         except Exception as e:                              # same policy as upstream :96-97
             if verbose:
                 print(f"Error processing {f.name}: {str(e)}")
@@ -422,6 +456,9 @@ def main(argv=None):
                          ".json file holds the plots' outlines instead: they are rasterised on the GPU, zone k is the k-th geometry")
     ap.add_argument("--zones-transform", default=None, type=_transform_numbers, metavar="x0,dx,rx,y0,ry,dy",
                     help="the GDAL geotransform (pixel -> world) the polygons of --zones are in; without it they are in pixel units")
+    ap.add_argument("--regions", default=None, type=_regions_spec, metavar="INDEX:above:T[:min_pixels]",
+                    help="take the zones from the picture: the connected patches of INDEX above (or 'below') T with min_pixels pixels or more, "
+                         "labelled on the GPU; writes <name>_zones.csv with each region's area, box and centroid added.  Not with --zones")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     from .dist import env_rank_world
@@ -431,7 +468,7 @@ def main(argv=None):
                         device=local_rank if world > 1 else None, png_encoder=args.png_encoder,
                         png_decoder=args.png_decoder, jpeg_decoder=args.jpeg_decoder, tiff_decoder=args.tiff_decoder,
                         tiff_encoder=args.tiff_encoder, index_tiff=args.index_tiff, nodata=args.nodata, alpha_mask=args.alpha_mask,
-                        **_zones_argument(args.zones, args.zones_transform))
+                        **_zones_argument(args.zones, args.zones_transform, args.regions))
     failed = {k: str(v) for k, v in res.items() if isinstance(v, Exception)}
     print(json.dumps({"rank": rank, "world": world, "files": len(res), "failed": failed}))
     return 1 if failed else 0

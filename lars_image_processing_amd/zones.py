@@ -7,7 +7,11 @@ table or a CSV wants.  The kernels are csrc/zonal.hip; there is no NumPy fallbac
 
 Where ``zones`` is wanted, plot outlines serve as well (DESIGN.md "Zones from polygons", csrc/zone_raster.hip): a list of polygons, or
 ``Polygons(list, transform=, want_labels=)``.  The labels are then made on the device and never cross PCIe; ``rasterize_zones`` returns
-them, ``polygons_from_geojson`` reads the outlines from a GeoJSON export and ``to_pixel`` undoes a GDAL geotransform."""
+them, ``polygons_from_geojson`` reads the outlines from a GeoJSON export and ``to_pixel`` undoes a GDAL geotransform.
+
+And where nobody drew outlines, the picture's own connected regions serve (DESIGN.md "Zones from regions", csrc/regions.hip):
+``Regions(mask=...)`` or ``Regions(index=, above= / below=)`` labels the patches of a mask or of a thresholded plane on the device;
+``label_regions`` returns such labels with each region's area, box and centroid."""
 from __future__ import annotations
 
 import ctypes as C
@@ -189,10 +193,151 @@ class Polygons:
         return np.zeros(shape, dtype=np.uint8 if len(self) <= 255 else np.uint16)
 
 
+def _whole(value, name, lo, hi, who):
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)):
+        raise TypeError(f"{who}: {name} must be an int (got {type(value).__name__})")
+    if not lo <= int(value) <= hi:
+        raise ValueError(f"{who}: {name} must be {lo} to {hi}, got {int(value)}")
+    return int(value)
+
+
+def _foreground(mask, who):
+    """``mask`` -> a C-contiguous uint8 ``[H, W]`` array of 0 / 1 with fewer than 2**31 pixels: every check that needs no device."""
+    m = np.asarray(mask)
+    if m.dtype.kind not in "uib":
+        raise TypeError(f"{who}: mask must be a bool or integer array (nonzero = foreground), got {m.dtype}")
+    if m.ndim != 2 or m.size == 0:
+        raise ValueError(f"{who}: mask must be a non-empty [H, W] array, got shape {m.shape}")
+    if m.size >= 1 << 31:
+        raise ValueError(f"{who}: mask has {m.size} pixels; regions are labelled on fewer than 2**31")
+    return np.ascontiguousarray(m != 0).view(np.uint8)
+
+
+def _connectivity(connectivity, who):
+    if isinstance(connectivity, (bool, np.bool_)) or connectivity not in (4, 8):
+        raise ValueError(f"{who}: connectivity must be 4 (edge neighbours) or 8 (edge and corner neighbours), got {connectivity!r}")
+    return int(connectivity)
+
+
+def _region_table(table):
+    """``lars_region`` rows -> ``area`` (int64), ``bbox`` (int32 ``[R, 4]``: row0, col0, row1, col1, half-open) and ``centroid``
+    (float64 ``[R, 2]``: row, column), the quotient of the exact coordinate sums taken here in float64."""
+    area = table["area"].astype(np.int64)
+    centroid = np.stack((table["row_sum"].astype(np.float64) / area, table["col_sum"].astype(np.float64) / area), axis=-1)
+    return {"area": area, "bbox": np.ascontiguousarray(table["bbox"], dtype=np.int32), "centroid": centroid.reshape(-1, 2)}
+
+
+def _label_view(buffer, shape, label_bytes):
+    """The ``[H, W]`` labels of the width the library chose, out of the int32-sized buffer it was handed."""
+    dtype = {1: np.uint8, 2: np.uint16, 4: np.int32}[label_bytes]
+    h, w = shape
+    flat = buffer.reshape(-1).view(dtype)[:h * w].reshape(h, w)
+    return flat if label_bytes == 4 else flat.copy()
+
+
+def label_regions(mask, connectivity=8, min_pixels=1):
+    """The connected regions of a foreground mask, labelled on the device (DESIGN.md "Zones from regions", csrc/regions.hip).
+
+    ``mask``: a bool or integer ``[H, W]`` array, nonzero = foreground.  ``connectivity``: 4 (edge neighbours) or 8 (edge and corner
+    neighbours).  A region is a maximal connected set of foreground pixels; regions are numbered ``1 .. R`` in raster order of their
+    first pixel -- ``scipy.ndimage.label``'s numbering -- and those of fewer than ``min_pixels`` pixels become 0, the others keeping
+    their order.  Returns ``{"labels", "n_regions", "area", "bbox", "centroid"}``: ``labels`` is uint8 for up to 255 regions, uint16
+    for up to 65535, otherwise int32; ``area`` int64 ``[R]``; ``bbox`` int32 ``[R, 4]`` (row0, col0, row1, col1, half-open);
+    ``centroid`` float64 ``[R, 2]`` (row, column).  No region is a result: ``n_regions`` 0 and empty arrays.  Integer arithmetic on
+    the device: the same bytes on every run."""
+    who = "label_regions"
+    m = _foreground(mask, who)
+    connectivity = _connectivity(connectivity, who)
+    min_pixels = _whole(min_pixels, "min_pixels", 1, (1 << 63) - 1, who)
+    h, w = m.shape
+    labels = np.empty((h, w), dtype=np.int32)
+    # rows of the table: no more than there are foreground pixels, or pixels no two of which touch; a picture with more than 2**20
+    # regions is labelled a second time with the room it asked for
+    apart = ((h + 1) // 2) * ((w + 1) // 2) if connectivity == 8 else (h * w + 1) // 2
+    capacity = max(1, min(int(np.count_nonzero(m)), apart, 1 << 20))
+    while True:
+        table = np.zeros(capacity, dtype=_ffi.REGION_DTYPE)
+        count, width = C.c_int64(-1), C.c_int(0)
+        try:
+            _ffi.call("lars_h_label_regions", _ffi.ptr(m), h, w, connectivity, min_pixels, 0, _ffi.ptr(labels), C.byref(width), _ffi.ptr(table),
+                      capacity, C.byref(count))
+            break
+        except _ffi.LarsError:
+            if count.value <= capacity:
+                raise
+            capacity = count.value
+    r = count.value
+    return {"labels": _label_view(labels, (h, w), width.value), "n_regions": r, **_region_table(table[:r])}
+
+
+class Regions:
+    """Zones taken from the picture itself: ``Regions(mask=None, index=None, above=None, below=None, connectivity=8, min_pixels=1,
+    max_regions=4096, want_labels=False)``, a third kind of ``zones`` beside a label raster and ``Polygons``.
+
+    The foreground is a host ``mask`` (bool or integer ``[H, W]``, nonzero = foreground) or a threshold, ``above=t`` or ``below=t``,
+    compared in float32 with the plane handed to ``zonal_statistics`` or with the ``index`` plane of ``process_image_zones``
+    (required there, and among its ``indices``); exactly one of the three is given.  Pixels outside ``valid`` / nodata are never
+    foreground.  The regions are ``label_regions``'s with ``connectivity`` and ``min_pixels``, made on the device; zone ``z`` is region
+    ``z``.  ``max_regions`` (1 to 65535) is the room of the result arrays: more regions raise ``ValueError`` with their number.
+    ``want_labels=True`` asks for the label raster as well.  Every check runs here, on the host."""
+
+    def __init__(self, mask=None, index=None, above=None, below=None, connectivity=8, min_pixels=1, max_regions=4096, want_labels=False):
+        who = "Regions"
+        given = [name for name, v in (("mask", mask), ("above", above), ("below", below)) if v is not None]
+        if len(given) != 1:
+            raise ValueError(f"{who}: exactly one of mask, above and below must be given, got {', '.join(given) or 'none of them'}")
+        self.mask = _foreground(mask, who) if mask is not None else None
+        if index is not None and index not in INDEX_IDS:
+            raise ValueError(f"{who}: Unknown index type: {index}")
+        if index is not None and mask is not None:
+            raise ValueError(f"{who}: index names the plane a threshold is compared with; a mask needs none")
+        self.index = index
+        self.mode, self.threshold = 0, np.float32(0)
+        if mask is None:
+            t = above if above is not None else below
+            if isinstance(t, (bool, np.bool_, str, bytes)) or not isinstance(t, (int, float, np.integer, np.floating)):
+                raise TypeError(f"{who}: {given[0]} must be a number (got {type(t).__name__})")
+            with np.errstate(over="ignore"):
+                finite = bool(np.isfinite(np.float32(t)))
+            if not finite:
+                raise ValueError(f"{who}: {given[0]} must be finite in float32, got {t!r}")
+            self.mode, self.threshold = (1 if above is not None else 2), np.float32(t)                # compared as the coverage count compares
+        self.connectivity = _connectivity(connectivity, who)
+        self.min_pixels = _whole(min_pixels, "min_pixels", 1, (1 << 63) - 1, who)
+        self.max_regions = _whole(max_regions, "max_regions", 1, ZONES_MAX, who)
+        self.want_labels = bool(want_labels)
+
+    def _check(self, shape, picture_indices, who):
+        """What only the call knows: the mask's shape, and the plane of a threshold.  Returns the id of that plane."""
+        if self.mask is not None and self.mask.shape != tuple(shape):
+            raise ValueError(f"{who}: the Regions mask has shape {self.mask.shape}, the raster is {tuple(shape)}")
+        if int(shape[0]) * int(shape[1]) >= 1 << 31:
+            raise ValueError(f"{who}: the raster has {int(shape[0]) * int(shape[1])} pixels; regions are labelled on fewer than 2**31")
+        if picture_indices is None:
+            if self.index is not None:
+                raise ValueError(f"{who}: Regions(index={self.index!r}) names a plane of a picture; the threshold is compared with index_array here")
+            return 0
+        if self.mask is not None:
+            return 0
+        if self.index is None:
+            raise ValueError(f"{who}: Regions needs index=, the plane above / below is compared with")
+        if self.index not in picture_indices:
+            raise ValueError(f"{who}: Regions(index={self.index!r}) is not among indices {list(picture_indices)}")
+        return INDEX_IDS[self.index]
+
+    def _too_many(self, who, count):
+        return ValueError(f"{who}: {count} regions, more than max_regions = {self.max_regions}: raise min_pixels to drop the small ones, or "
+                          f"max_regions (at most {ZONES_MAX} regions make one label raster)")
+
+
 def _zone_source(zones, n_zones, who):
-    """The split between the two kinds of ``zones``.  None for what ``_labels`` has always taken -- an integer ndarray of two
+    """The split between the kinds of ``zones``.  None for what ``_labels`` has always taken -- an integer ndarray of two
     dimensions is a label raster -- and for everything it refuses; ``Polygons`` for outlines: a ``Polygons``, a list or tuple of
-    polygons, or a float ``[Z, n, 2]`` array of single-ring polygons."""
+    polygons, or a float ``[Z, n, 2]`` array of single-ring polygons; a ``Regions`` as it stands."""
+    if isinstance(zones, Regions):
+        if n_zones is not None:
+            raise ValueError(f"{who}: n_zones cannot be given with Regions: Z is the number of regions found")
+        return zones
     if isinstance(zones, Polygons):
         polys = zones
     elif isinstance(zones, np.ndarray) and zones.dtype.kind == "f" and zones.ndim == 3 and zones.shape[2] == 2:
@@ -343,7 +488,11 @@ def zonal_statistics(index_array, zones, index_type, valid=None, n_zones=None, w
         raise ValueError(f"{who}: index_array must be a non-empty [H, W] array, got shape {x.shape}")
     h, w = x.shape
     polys = _zone_source(zones, n_zones, who)
-    lab, nz = (None, len(polys)) if polys else _labels(zones, (h, w), n_zones, who)
+    regions = polys if isinstance(polys, Regions) else None
+    if regions:
+        polys = None
+        regions._check((h, w), None, who)
+    lab, nz = (None, regions.max_regions) if regions else (None, len(polys)) if polys else _labels(zones, (h, w), n_zones, who)
     if isinstance(valid, str):
         raise TypeError(f"{who}: valid must be an [H, W] bool or integer array or None: a plane has no alpha channel")
     valid_arr, _ = _nodata.valid_argument(valid, (h, w, 0), who)
@@ -353,7 +502,24 @@ def zonal_statistics(index_array, zones, index_type, valid=None, n_zones=None, w
     medians = np.zeros((nz, 2), dtype=np.float32)
     bad = C.c_int64(-1)
     extra = {}
-    if polys:
+    if regions:
+        table = np.zeros(nz, dtype=_ffi.REGION_DTYPE)
+        made = np.empty((h, w), dtype=np.int32) if regions.want_labels else None
+        found, width = C.c_int64(-1), C.c_int(0)
+        try:
+            _ffi.call("lars_h_zonal_stats_regions_f32", _ffi.ptr(x), _ffi.ptr(regions.mask), regions.mode, regions.threshold, regions.connectivity,
+                      regions.min_pixels, _ffi.ptr(valid_arr), h, w, np.float32(threshold), int(bool(want_hist)), nz, _ffi.ptr(records),
+                      _ffi.ptr(medians), _ffi.ptr(table), C.byref(found), _ffi.ptr(made), 0, C.byref(width))
+        except _ffi.LarsError:
+            if found.value > nz:
+                raise regions._too_many(who, found.value) from None
+            raise
+        nz = found.value
+        records, medians = records[:nz], medians[:nz]
+        extra["regions"] = _region_table(table[:nz])
+        if regions.want_labels:
+            extra["labels"] = _label_view(made, (h, w), width.value)
+    elif polys:
         made = polys._label_buffer((h, w)) if polys.want_labels else None
         _ffi.call("lars_h_zonal_stats_polygons_f32", _ffi.ptr(x), *polys._head(), _ffi.ptr(valid_arr), h, w, np.float32(threshold),
                   int(bool(want_hist)), _ffi.ptr(records), _ffi.ptr(medians), _ffi.ptr(made), made.dtype.itemsize if polys.want_labels else 0)
@@ -385,14 +551,26 @@ def process_image_zones(img_array, zones, valid=None, nodata=None, n_zones=None,
                  need_index="zone statistics need at least one index")
     indices = p.indices
     polys = _zone_source(zones, n_zones, who)
-    lab, nz = (None, len(polys)) if polys else _labels(zones, (p.h, p.w), n_zones, who)
+    regions = polys if isinstance(polys, Regions) else None
+    if regions:
+        polys = None
+        source = regions._check((p.h, p.w), indices, who)
+    lab, nz = (None, regions.max_regions) if regions else (None, len(polys)) if polys else _labels(zones, (p.h, p.w), n_zones, who)
     records = np.zeros((3, nz), dtype=_ffi.STATS_DTYPE)
     medians = np.zeros((3, nz, 2), dtype=np.float32)
     nvalid, bad = C.c_int64(-1), C.c_int64(-1)
     p_rgba, p_lut = _ffi.ptr3(p.rgbas), _ffi.ptr3(p.luts)
     made = polys._label_buffer((p.h, p.w)) if polys and polys.want_labels else None
+    found, width = C.c_int64(-1), C.c_int(0)
     try:
-        if polys:
+        if regions:
+            table = np.zeros(nz, dtype=_ffi.REGION_DTYPE)
+            made = np.empty((p.h, p.w), dtype=np.int32) if regions.want_labels else None
+            _ffi.call("lars_h_process_image_regions", *p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha),
+                      int(p.nodata is not None), p.nodata or 0, C.byref(nvalid), _ffi.ptr(regions.mask), source, regions.mode, regions.threshold,
+                      regions.connectivity, regions.min_pixels, nz, _ffi.ptr(records), _ffi.ptr(medians), _ffi.ptr(table), C.byref(found),
+                      _ffi.ptr(made), 0, C.byref(width))
+        elif polys:
             _ffi.call("lars_h_process_image_zones_polygons", *p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha),
                       int(p.nodata is not None), p.nodata or 0, C.byref(nvalid), *polys._head(), _ffi.ptr(records), _ffi.ptr(medians),
                       _ffi.ptr(made), made.dtype.itemsize if made is not None else 0)
@@ -405,9 +583,17 @@ def process_image_zones(img_array, zones, valid=None, nodata=None, n_zones=None,
             raise ValueError("process_image: no valid pixel") from None
         if bad.value > 0:
             raise _bad_labels(who, bad.value, nz) from None
+        if regions and found.value > nz:
+            raise regions._too_many(who, found.value) from None
         raise
     result = _picture_result(p, want_hist, want_rgba, False, valid_pixels=nvalid.value)
+    if regions:
+        nz = found.value
+        records, medians = records[:, :nz], medians[:, :nz]
+        made = _label_view(made, (p.h, p.w), width.value) if made is not None else None
     result["zones"] = {"zone": np.arange(1, nz + 1, dtype=np.int64)}
+    if regions:
+        result["zones"]["regions"] = _region_table(table[:nz])
     if made is not None:
         result["zones"]["labels"] = made
     for t in indices:
