@@ -1080,6 +1080,76 @@ int lars_h_process_image_regions(const void *img, int64_t h, int64_t w, int chan
                                  lars_region *table /* [capacity] */, int64_t *n_regions, void *labels_out /* may be NULL */,
                                  int label_bytes, int *label_bytes_out /* may be NULL */);
 
+/* ------------------------------------------------- region outlines (csrc/outlines.hip) */
+/* The polygons of the labelled patches: the rings along the pixel borders of every region of a label raster, traced on the device.
+ *
+ * The definition.  labels is int32 [h][w], 0 = background, 1 .. R = regions as lars_d_region_label makes them with the same
+ * connectivity: every label one connected set.  1 <= h, w and h * w < 2^29, so that an edge id fits int32.  Vertices are pixel
+ * corners: corner (r, c) is the upper-left corner of pixel (r, c), 0 <= r <= h, 0 <= c <= w.  A pixel (y, x) of label L owns one
+ * directed edge per side whose neighbour is not L (a neighbour outside the raster is not L), clockwise on the screen: side 0, top,
+ * (y, x) -> (y, x + 1); 1, right, (y, x + 1) -> (y + 1, x + 1); 2, bottom, (y + 1, x + 1) -> (y + 1, x); 3, left, (y + 1, x) -> (y, x).
+ * An edge's id is 4 * (y * w + x) + side.  The successor of an edge is the first that exists, among the edges of L that start where it
+ * ends, of: the right turn (the next side of the same pixel), straight on (the same side of the next pixel along the edge), the left
+ * turn (the previous side of the pixel diagonally ahead on the outer side) -- in this order with connectivity 4, in the opposite
+ * order with 8: where L holds exactly two diagonal pixels of a corner, 8 crosses over and 4 stays with its own pixel.  The edges fall
+ * into rings.  A ring's key is its smallest edge id; its vertices are the start corners of its edges whose predecessor has another
+ * side, in ring order from the first such edge at or after the smallest edge: rows and columns alternate, no vertex lies inside a
+ * straight run, a ring has an even number of vertices, 4 or more.  area2 is the exact doubled signed area, the shoelace sum over
+ * (x, y) = (col, row): positive for an outer ring (clockwise on the screen), negative for a hole.  Rings are sorted by (label, key);
+ * a region's first ring is its one outer ring, the others are its holes.  Integers only: the same bytes on every run.
+ *
+ * lars_d_region_outline_count: *edges_dev (int64, device) = E, the number of edges of the raster: what sizes the scratch.
+ * lars_d_region_outline: labels, rings[ring_capacity], verts[vert_capacity][2] (row, col) and counts_dev[3] (int64: edges, rings,
+ * vertices) on the device; n_labels >= the largest label (it sets the passes of the ring sort: labels above it sort by their low bits).
+ * scratch: lars_region_outline_scratch_bytes(h, w, edge_capacity) bytes (0 for arguments outside the rules), 256-byte aligned: 4 bytes
+ * a pixel and 35.2 bytes an edge of edge_capacity.  The counts are written whatever the capacities are; rows and vertices below the
+ * capacities are written and nothing beyond them.  More edges than edge_capacity: counts_dev[0] says so, the other two counts are 0 and
+ * nothing is traced.  ceil(log2(edge_capacity)) rounds of pointer doubling and some forty other launches on the stream; no workgroup
+ * waits for another, and every index read from memory is range-checked before it is followed. */
+typedef struct lars_outline_ring {
+    int32_t label, key;            /* the region, and the ring's smallest edge id */
+    int32_t start, count;          /* its vertices: verts[start .. start + count - 1] */
+    int64_t area2;
+} lars_outline_ring;
+size_t lars_region_outline_scratch_bytes(int64_t h, int64_t w, int64_t edge_capacity);
+int lars_d_region_outline_count(const int32_t *labels, int64_t h, int64_t w, int64_t *edges_dev, void *stream);
+int lars_d_region_outline(const int32_t *labels, int64_t h, int64_t w, int connectivity, int64_t n_labels, int64_t edge_capacity,
+                          lars_outline_ring *rings /* [ring_capacity] */, int64_t ring_capacity, int32_t *verts /* [vert_capacity][2] */,
+                          int64_t vert_capacity, int64_t *counts_dev /* [3] */, void *scratch, void *stream);
+/* What the host entry points below fill: the caller's arrays and their room in, the counts out (-1 until they are known).  More rings
+ * or vertices than there is room for: LARS_ERR_INVALID with the counts set and nothing written to rings and verts; a caller retries
+ * with that room.  No region: all three counts 0. */
+typedef struct lars_outlines {
+    lars_outline_ring *rings;      /* host [ring_capacity] */
+    int64_t ring_capacity;
+    int32_t *verts;                /* host [vert_capacity][2]: (row, col) */
+    int64_t vert_capacity;
+    int64_t n_rings, n_vertices, n_edges;
+} lars_outlines;
+/* region_outlines(mask): lars_h_label_regions, and the outlines of the labels it made, traced where they stand on the device.  The
+ * host waits for R, for the edge count (which sizes a scratch area of its own) and for the ring and vertex counts. */
+int lars_h_region_outlines(const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int label_bytes, void *labels,
+                           int *label_bytes_out /* may be NULL */, lars_region *table /* [capacity] */, int64_t capacity, int64_t *n_regions,
+                           lars_outlines *outlines);
+/* lars_h_zonal_stats_regions_f32 and lars_h_process_image_regions with the outlines of the regions as well: traced after the zone
+ * stages from the labels they used, which never leave the device for it.  outlines == NULL: exactly the calls above. */
+int lars_h_zonal_stats_regions_outlines_f32(const float *x, const uint8_t *mask /* may be NULL */, int mode, float t, int connectivity,
+                                            int64_t min_pixels, const uint8_t *valid /* may be NULL */, int64_t h, int64_t w, float threshold,
+                                            int want_hist, int64_t capacity, lars_stats *stats /* [capacity] */, float *medians /* [capacity][2] */,
+                                            lars_region *table /* [capacity] */, int64_t *n_regions, void *labels_out /* may be NULL */,
+                                            int label_bytes, int *label_bytes_out /* may be NULL */, lars_outlines *outlines /* may be NULL */);
+int lars_h_process_image_regions_outlines(const void *img, int64_t h, int64_t w, int channels, int dtype,
+                                          int apply_wb, uint32_t index_mask, int want_hist,
+                                          uint8_t *out_wb, float *const out_index[3],
+                                          lars_stats *stats /* [3] */, float *medians /* [3][2] */,
+                                          uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3],
+                                          const uint8_t *valid, int use_alpha, int has_nodata, int nodata, int64_t *valid_pixels,
+                                          const uint8_t *mask /* may be NULL */, int source_index, int mode, float t, int connectivity,
+                                          int64_t min_pixels, int64_t capacity,
+                                          lars_stats *zone_stats /* [3][capacity] */, float *zone_medians /* [3][capacity][2] */,
+                                          lars_region *table /* [capacity] */, int64_t *n_regions, void *labels_out /* may be NULL */,
+                                          int label_bytes, int *label_bytes_out /* may be NULL */, lars_outlines *outlines /* may be NULL */);
+
 /* ------------------------------------------------------------------ multi-GPU */
 /* One process per GPU.  RCCL (librccl.so) is loaded on first use.  unique_id is
  * LARS_COMM_ID_BYTES bytes produced by lars_comm_unique_id() on rank 0 and

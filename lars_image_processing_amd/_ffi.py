@@ -57,6 +57,18 @@ assert STATS_DTYPE.itemsize == C.sizeof(Stats) == 472
 REGION_DTYPE = np.dtype([("area", "<i8"), ("bbox", "<i4", (4,)), ("row_sum", "<u8"), ("col_sum", "<u8")])
 assert REGION_DTYPE.itemsize == 40
 
+# ``lars_outline_ring`` (include/lars_hip.h): one row of the ring table of region_outlines
+RING_DTYPE = np.dtype([("label", "<i4"), ("key", "<i4"), ("start", "<i4"), ("count", "<i4"), ("area2", "<i8")])
+assert RING_DTYPE.itemsize == 24
+
+
+class Outlines(C.Structure):
+    """``lars_outlines`` (include/lars_hip.h): the caller's ring table and vertex array with their room, and the counts back."""
+    _fields_ = [
+        ("rings", C.c_void_p), ("ring_capacity", C.c_int64), ("verts", C.c_void_p), ("vert_capacity", C.c_int64),
+        ("n_rings", C.c_int64), ("n_vertices", C.c_int64), ("n_edges", C.c_int64),
+    ]
+
 
 class FusedArgs(C.Structure):
     """``lars_fused_args`` (include/lars_hip.h)."""
@@ -309,6 +321,16 @@ SIGNATURES = {
     "lars_h_process_image_regions": (_I, [_P, _I64, _I64, _I, _I, _I, _U32, _I, _P, C.POINTER(_P * 3), _P, _P,
                                           C.POINTER(_P * 3), C.POINTER(_P * 3), _P, _I, _I, _I, C.POINTER(_I64),
                                           _P, _I, _I, _F, _I, _I64, _I64, _P, _P, _P, C.POINTER(_I64), _P, _I, C.POINTER(_I)]),
+    "lars_region_outline_scratch_bytes": (_SZ, [_I64, _I64, _I64]),
+    "lars_d_region_outline_count": (_I, [_P, _I64, _I64, _P, _P]),
+    "lars_d_region_outline": (_I, [_P, _I64, _I64, _I, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _P]),
+    "lars_h_region_outlines": (_I, [_P, _I64, _I64, _I, _I64, _I, _P, C.POINTER(_I), _P, _I64, C.POINTER(_I64), C.POINTER(Outlines)]),
+    "lars_h_zonal_stats_regions_outlines_f32": (_I, [_P, _P, _I, _F, _I, _I64, _P, _I64, _I64, _F, _I, _I64, _P, _P, _P, C.POINTER(_I64), _P, _I,
+                                                     C.POINTER(_I), C.POINTER(Outlines)]),
+    "lars_h_process_image_regions_outlines": (_I, [_P, _I64, _I64, _I, _I, _I, _U32, _I, _P, C.POINTER(_P * 3), _P, _P,
+                                                   C.POINTER(_P * 3), C.POINTER(_P * 3), _P, _I, _I, _I, C.POINTER(_I64),
+                                                   _P, _I, _I, _F, _I, _I64, _I64, _P, _P, _P, C.POINTER(_I64), _P, _I, C.POINTER(_I),
+                                                   C.POINTER(Outlines)]),
     "lars_jpeg_bound": (_SZ, [_I64, _I64, _I, _I]),
     "lars_jpeg_header": (_I64, [_I64, _I64, _I, _I, _I, _P, _SZ]),
     "lars_jpeg_encode_scratch_bytes": (_SZ, [_I64, _I64, _I, _I]),

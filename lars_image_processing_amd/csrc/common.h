@@ -28,6 +28,8 @@ struct ThreadCtx {
     size_t ws_bytes = 0;
     void *scratch = nullptr;   // small device scratch of the device entry points
     size_t scratch_bytes = 0;
+    void *outline = nullptr;   // the tracer's area of the host entry points that trace outlines (outlines.hip): sized by the edge count,
+    size_t outline_bytes = 0;  // which is known only once the labels, which stand in ws, exist
     int64_t u16_win_tiles = 0; // tiles of the last lars_d_wb_prepare if it took the value-window route and nothing has reserved the
                                // scratch since (lars_u16_window_report reads its flags and windows there), else 0
 };
@@ -35,6 +37,7 @@ struct ThreadCtx {
 int ensure_ctx(ThreadCtx **out);                 // initialises device 0 on first use
 int ws_reserve(ThreadCtx *c, size_t bytes);      // grow-only; synchronises when it grows
 int scratch_reserve(ThreadCtx *c, size_t bytes);
+int outline_reserve(ThreadCtx *c, size_t bytes);
 
 // One allocation cut into buffers.  take<T>(count) gives the next 256-byte aligned stretch of count elements; on a null
 // base it only counts.  A plan (a function that lists the buffers of an area once) therefore runs twice: on Carver(nullptr)

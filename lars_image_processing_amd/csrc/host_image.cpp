@@ -30,6 +30,7 @@ struct ZoneBufs {
     uint8_t *rmask;                // [npix] the foreground
     lars_region *rtable;           // [capacity]
     int64_t *rcount;               // R
+    int64_t *ocounts;              // [3] the tracer's counts, where the regions' outlines are wanted (outlines.hip)
 };
 
 // The polygons of a job, as the entry points take them (include/lars_hip.h "zones from polygons"); nzones = npolys.
@@ -52,6 +53,7 @@ struct ZoneRegions {
     int64_t *n_regions;
     void *labels_out; int label_bytes; int *label_bytes_out;     // host [h][w] labels back, or null; label_bytes 0: the narrowest
     int64_t h, w;
+    lars_outlines *outlines;               // the regions' rings and vertices back as well (outlines.hip), or null
 };
 
 ZoneBufs zone_plan(Carver &c, size_t npix, int zone_bytes, int64_t nzones, uint32_t mask, const ZonePolys *P = nullptr,
@@ -71,6 +73,7 @@ ZoneBufs zone_plan(Carver &c, size_t npix, int zone_bytes, int64_t nzones, uint3
         B.rmask = c.take<uint8_t>(npix);
         B.rtable = c.take<lars_region>((size_t)G->capacity);
         B.rcount = c.take<int64_t>(1);
+        B.ocounts = G->outlines ? c.take<int64_t>(3) : nullptr;
         B.raster_scratch = c.take<char>(lars_region_label_scratch_bytes(G->h, G->w));
         B.narrow = (G->labels_out && G->label_bytes != 4) ? c.take<char>(npix * 2) : nullptr;
     }
@@ -140,6 +143,60 @@ int check_regions(const char *who, const ZoneRegions &G, int64_t most)
     if (G.labels_out && G.label_bytes != 0 && G.label_bytes != 1 && G.label_bytes != 2 && G.label_bytes != 4)
         return fail(LARS_ERR_INVALID, "%s: labels come back 1, 2 or 4 bytes wide (0: the narrowest), got %d", who, G.label_bytes);
     if (G.labels_out && !aligned_to(G.labels_out, 4)) return fail(LARS_ERR_INVALID, "%s: the labels are not aligned", who);
+    if (G.outlines) {
+        lars_outlines &O = *G.outlines;
+        O.n_rings = O.n_vertices = O.n_edges = -1;
+        if (!lars_region_outline_scratch_bytes(G.h, G.w, 0))
+            return fail(LARS_ERR_INVALID, "%s: outlines are traced on fewer than 2^29 pixels (an edge id fits int32), got %lld x %lld", who, (long long)G.h, (long long)G.w);
+        if (O.ring_capacity < 0 || O.vert_capacity < 0 || (O.ring_capacity > 0 && !O.rings) || (O.vert_capacity > 0 && !O.verts) ||
+            !aligned_to(O.rings, 8) || !aligned_to(O.verts, 4))
+            return fail(LARS_ERR_INVALID, "%s: the outlines need a ring table and a vertex array of capacity >= 0, 8- and 4-byte aligned", who);
+    }
+    return LARS_OK;
+}
+
+// The outlines of the nregions labels in B.labels (int32), once everything else of the call is on the stream.  Three waits: for the
+// edge count, which sizes the tracer's own area (the labels stand in the workspace, which cannot grow under them), for the ring and
+// vertex counts, which may exceed the caller's room, and for the rows and vertices.
+int trace_zone_outlines(const char *who, const ZoneBufs &B, const ZoneRegions &G, int64_t nregions, hipStream_t s)
+{
+    lars_outlines &O = *G.outlines;
+    O.n_rings = O.n_vertices = O.n_edges = 0;
+    if (!nregions) return LARS_OK;
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    const int32_t *labels = reinterpret_cast<const int32_t *>(B.labels);
+    int64_t counts[3] = {-1, -1, -1};
+    LARS_TRY(lars_d_region_outline_count(labels, G.h, G.w, B.ocounts, s));
+    LARS_HIP_TRY(hipMemcpyAsync(counts, B.ocounts, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipStreamSynchronize(s));
+    const int64_t edges = counts[0];
+    const size_t tracer = edges > 0 ? lars_region_outline_scratch_bytes(G.h, G.w, edges) : 0;
+    if (!tracer) return fail(LARS_ERR_INVALID, "%s: %lld regions with %lld edges", who, (long long)nregions, (long long)edges);
+    O.n_edges = edges;
+    // no more rings than the tracer's own ring arrays hold, no more vertices than edges
+    const int64_t rcap = O.ring_capacity < edges / 4 + 1 ? O.ring_capacity : edges / 4 + 1, vcap = O.vert_capacity < edges ? O.vert_capacity : edges;
+    char *scratch;
+    lars_outline_ring *rings;
+    int32_t *verts;
+    auto plan = [&](Carver &d) { scratch = d.take<char>(tracer), rings = d.take<lars_outline_ring>((size_t)rcap), verts = d.take<int32_t>(2 * (size_t)vcap); };
+    Carver size(nullptr);
+    plan(size);
+    LARS_TRY(outline_reserve(c, size.bytes() + 256));
+    Carver area(c->outline);
+    plan(area);
+    LARS_TRY(lars_d_region_outline(labels, G.h, G.w, G.connectivity, nregions, edges, rings, rcap, verts, vcap, B.ocounts, scratch, s));
+    LARS_HIP_TRY(hipMemcpyAsync(counts, B.ocounts, sizeof counts, hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipStreamSynchronize(s));
+    O.n_rings = counts[1];
+    O.n_vertices = counts[2];
+    if (counts[0] != edges || counts[1] < 1 || counts[2] < 4) return fail(LARS_ERR_HIP, "%s: the tracer counted %lld edges after %lld", who, (long long)counts[0], (long long)edges);
+    if (counts[1] > O.ring_capacity || counts[2] > O.vert_capacity)
+        return fail(LARS_ERR_INVALID, "%s: %lld rings and %lld vertices; the room is %lld and %lld", who, (long long)counts[1], (long long)counts[2],
+                    (long long)O.ring_capacity, (long long)O.vert_capacity);
+    LARS_HIP_TRY(hipMemcpyAsync(O.rings, rings, (size_t)counts[1] * sizeof(lars_outline_ring), hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipMemcpyAsync(O.verts, verts, 2 * (size_t)counts[2] * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipStreamSynchronize(s));
     return LARS_OK;
 }
 
@@ -182,7 +239,7 @@ int run_zones(const char *who, const ZoneBufs &B, const void *zones, int zone_by
     const size_t host_stride = (size_t)(G ? G->capacity : nzones);
     if (G) {
         LARS_TRY(label_zone_regions(who, B, *G, planes[G->source], valid_dev, &nzones, s));
-        if (!nzones) return LARS_OK;
+        if (!nzones) return G->outlines ? trace_zone_outlines(who, B, *G, 0, s) : LARS_OK;
     }
     const size_t nz = (size_t)nzones;
     if (P) LARS_TRY(raster_zones(B, *P, h, w, s));
@@ -211,6 +268,7 @@ int run_zones(const char *who, const ZoneBufs &B, const void *zones, int zone_by
         LARS_HIP_TRY(hipMemcpyAsync(host_stats + k * host_stride, st, nz * sizeof(lars_stats), hipMemcpyDeviceToHost, s));
         LARS_HIP_TRY(hipMemcpyAsync(host_med + 2 * k * host_stride, med, 2 * nz * sizeof(float), hipMemcpyDeviceToHost, s));
     }
+    if (G && G->outlines) LARS_TRY(trace_zone_outlines(who, B, *G, nzones, s));
     return LARS_OK;
 }
 
@@ -755,14 +813,15 @@ int lars_h_process_image_zones_polygons(const void *img, int64_t h, int64_t w, i
     return run_image(j);
 }
 
-int lars_h_process_image_regions(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
-                                 int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
-                                 uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], const uint8_t *valid, int use_alpha,
-                                 int has_nodata, int nodata, int64_t *valid_pixels, const uint8_t *mask, int source_index, int mode, float t,
-                                 int connectivity, int64_t min_pixels, int64_t capacity, lars_stats *zone_stats, float *zone_medians,
-                                 lars_region *table, int64_t *n_regions, void *labels_out, int label_bytes, int *label_bytes_out)
+int lars_h_process_image_regions_outlines(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                                          int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                                          uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], const uint8_t *valid, int use_alpha,
+                                          int has_nodata, int nodata, int64_t *valid_pixels, const uint8_t *mask, int source_index, int mode, float t,
+                                          int connectivity, int64_t min_pixels, int64_t capacity, lars_stats *zone_stats, float *zone_medians,
+                                          lars_region *table, int64_t *n_regions, void *labels_out, int label_bytes, int *label_bytes_out,
+                                          lars_outlines *outlines)
 {
-    static const char *who = "lars_h_process_image_regions";
+    const char *who = outlines ? "lars_h_process_image_regions_outlines" : "lars_h_process_image_regions";
     if (valid_pixels) *valid_pixels = -1;
     if (n_regions) *n_regions = -1;
     LARS_TRY(check_picture(who, img, h, w, channels, dtype, index_mask, use_alpha, has_nodata, nodata, out_rgba, cmap_lut));
@@ -771,12 +830,25 @@ int lars_h_process_image_regions(const void *img, int64_t h, int64_t w, int chan
     if (!mask && (source_index < 0 || source_index > 2 || !((index_mask >> source_index) & 1u)))
         return fail(LARS_ERR_INVALID, "%s: source_index %d is not among the indices of index_mask", who, source_index);
     const ZoneRegions G = {mask, mask ? 0 : source_index, mode, t, connectivity, min_pixels, capacity, table, n_regions, labels_out, label_bytes,
-                           label_bytes_out, h, w};
+                           label_bytes_out, h, w, outlines};
     LARS_TRY(check_regions(who, G, LARS_ZONES_MAX));
     ImageJob j = picture_job(who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut);
     under_mask(j, valid, use_alpha, has_nodata, nodata, valid_pixels);
     j.regions = &G; j.zone_bytes = 4; j.nzones = capacity; j.zone_stats = zone_stats; j.zone_medians = zone_medians;
     return run_image(j);
+}
+
+int lars_h_process_image_regions(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                                 int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                                 uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], const uint8_t *valid, int use_alpha,
+                                 int has_nodata, int nodata, int64_t *valid_pixels, const uint8_t *mask, int source_index, int mode, float t,
+                                 int connectivity, int64_t min_pixels, int64_t capacity, lars_stats *zone_stats, float *zone_medians,
+                                 lars_region *table, int64_t *n_regions, void *labels_out, int label_bytes, int *label_bytes_out)
+{
+    return lars_h_process_image_regions_outlines(img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba,
+                                                 cmap_lut, valid, use_alpha, has_nodata, nodata, valid_pixels, mask, source_index, mode, t, connectivity,
+                                                 min_pixels, capacity, zone_stats, zone_medians, table, n_regions, labels_out, label_bytes, label_bytes_out,
+                                                 nullptr);
 }
 
 }  // extern "C"
@@ -834,24 +906,34 @@ int lars_h_zonal_stats_polygons_f32(const float *x, const double *verts, int64_t
     return zonal_stats("lars_h_zonal_stats_polygons_f32", x, nullptr, 4, &P, valid, h, w, npolys, threshold, want_hist, stats, medians, nullptr);
 }
 
+int lars_h_zonal_stats_regions_outlines_f32(const float *x, const uint8_t *mask, int mode, float t, int connectivity, int64_t min_pixels,
+                                            const uint8_t *valid, int64_t h, int64_t w, float threshold, int want_hist, int64_t capacity,
+                                            lars_stats *stats, float *medians, lars_region *table, int64_t *n_regions, void *labels_out,
+                                            int label_bytes, int *label_bytes_out, lars_outlines *outlines)
+{
+    if (n_regions) *n_regions = -1;
+    const ZoneRegions G = {mask, 0, mode, t, connectivity, min_pixels, capacity, table, n_regions, labels_out, label_bytes, label_bytes_out, h, w, outlines};
+    return zonal_stats(outlines ? "lars_h_zonal_stats_regions_outlines_f32" : "lars_h_zonal_stats_regions_f32", x, nullptr, 4, nullptr, valid, h, w, capacity,
+                       threshold, want_hist, stats, medians, nullptr, &G);
+}
+
 int lars_h_zonal_stats_regions_f32(const float *x, const uint8_t *mask, int mode, float t, int connectivity, int64_t min_pixels,
                                    const uint8_t *valid, int64_t h, int64_t w, float threshold, int want_hist, int64_t capacity, lars_stats *stats,
                                    float *medians, lars_region *table, int64_t *n_regions, void *labels_out, int label_bytes, int *label_bytes_out)
 {
-    if (n_regions) *n_regions = -1;
-    const ZoneRegions G = {mask, 0, mode, t, connectivity, min_pixels, capacity, table, n_regions, labels_out, label_bytes, label_bytes_out, h, w};
-    return zonal_stats("lars_h_zonal_stats_regions_f32", x, nullptr, 4, nullptr, valid, h, w, capacity, threshold, want_hist, stats, medians, nullptr, &G);
+    return lars_h_zonal_stats_regions_outlines_f32(x, mask, mode, t, connectivity, min_pixels, valid, h, w, threshold, want_hist, capacity, stats, medians, table,
+                                                   n_regions, labels_out, label_bytes, label_bytes_out, nullptr);
 }
 
-int lars_h_label_regions(const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int label_bytes, void *labels,
-                         int *label_bytes_out, lars_region *table, int64_t capacity, int64_t *n_regions)
+// label_regions, and region_outlines where outlines are wanted: the labels stay in the workspace for the tracer
+static int label_regions_call(const char *who, const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int label_bytes, void *labels,
+                              int *label_bytes_out, lars_region *table, int64_t capacity, int64_t *n_regions, lars_outlines *outlines)
 {
-    static const char *who = "lars_h_label_regions";
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (n_regions) *n_regions = -1;
     if (!mask || !labels) return fail(LARS_ERR_INVALID, "%s: mask and labels are required", who);
-    const ZoneRegions G = {mask, 0, 0, 0.0f, connectivity, min_pixels, capacity, table, n_regions, labels, label_bytes, label_bytes_out, h, w};
+    const ZoneRegions G = {mask, 0, 0, 0.0f, connectivity, min_pixels, capacity, table, n_regions, labels, label_bytes, label_bytes_out, h, w, outlines};
     LARS_TRY(check_regions(who, G, 0x7FFFFFFF));
     ZoneBufs B;
     memset(&B, 0, sizeof B);
@@ -861,13 +943,30 @@ int lars_h_label_regions(const uint8_t *mask, int64_t h, int64_t w, int connecti
         B.rmask = d.take<uint8_t>(npix);
         B.rtable = d.take<lars_region>((size_t)capacity);
         B.rcount = d.take<int64_t>(1);
+        B.ocounts = outlines ? d.take<int64_t>(3) : nullptr;
         B.raster_scratch = d.take<char>(lars_region_label_scratch_bytes(h, w));
         B.narrow = label_bytes != 4 ? d.take<char>(npix * 2) : nullptr;
     }));
     int64_t r = 0;
     LARS_TRY(label_zone_regions(who, B, G, nullptr, nullptr, &r, c->stream));
+    if (outlines) LARS_TRY(trace_zone_outlines(who, B, G, r, c->stream));
     LARS_HIP_TRY(hipStreamSynchronize(c->stream));
     return LARS_OK;
+}
+
+int lars_h_label_regions(const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int label_bytes, void *labels,
+                         int *label_bytes_out, lars_region *table, int64_t capacity, int64_t *n_regions)
+{
+    return label_regions_call("lars_h_label_regions", mask, h, w, connectivity, min_pixels, label_bytes, labels, label_bytes_out, table, capacity, n_regions,
+                              nullptr);
+}
+
+int lars_h_region_outlines(const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int label_bytes, void *labels,
+                           int *label_bytes_out, lars_region *table, int64_t capacity, int64_t *n_regions, lars_outlines *outlines)
+{
+    static const char *who = "lars_h_region_outlines";
+    if (!outlines) return fail(LARS_ERR_INVALID, "%s: outlines == NULL", who);
+    return label_regions_call(who, mask, h, w, connectivity, min_pixels, label_bytes, labels, label_bytes_out, table, capacity, n_regions, outlines);
 }
 
 int lars_h_rasterize_zones(const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts,

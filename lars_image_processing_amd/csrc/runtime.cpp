@@ -22,6 +22,7 @@ static void release_ctx(ThreadCtx *c)
     if (c->stream) { hipStreamSynchronize(c->stream); hipStreamDestroy(c->stream); c->stream = nullptr; }
     if (c->ws) { hipFree(c->ws); c->ws = nullptr; c->ws_bytes = 0; }
     if (c->scratch) { hipFree(c->scratch); c->scratch = nullptr; c->scratch_bytes = 0; }
+    if (c->outline) { hipFree(c->outline); c->outline = nullptr; c->outline_bytes = 0; }
     c->u16_win_tiles = 0;
     c->device = -1;
 }
@@ -47,6 +48,7 @@ static int bind_device(ThreadCtx *c, int ordinal)
     if (c->stream) { hipStreamDestroy(c->stream); c->stream = nullptr; }
     if (c->ws) { hipFree(c->ws); c->ws = nullptr; c->ws_bytes = 0; }
     if (c->scratch) { hipFree(c->scratch); c->scratch = nullptr; c->scratch_bytes = 0; }
+    if (c->outline) { hipFree(c->outline); c->outline = nullptr; c->outline_bytes = 0; }
     c->u16_win_tiles = 0;
     LARS_HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     c->device = ordinal;
@@ -87,6 +89,8 @@ int scratch_reserve(ThreadCtx *c, size_t bytes)
     c->u16_win_tiles = 0;                                 // whoever reserves the scratch writes it: the last pre-pass's report is gone
     return reserve(&c->scratch, &c->scratch_bytes, bytes, c->stream);
 }
+
+int outline_reserve(ThreadCtx *c, size_t bytes) { return reserve(&c->outline, &c->outline_bytes, bytes, c->stream); }
 
 static Tuning g_tuning;
 Tuning &tuning() { return g_tuning; }

@@ -79,14 +79,18 @@ def _mask_argument(mask_kw):
     return (mask_kw,) if mask_kw else ()
 
 
-def _zones_argument(zones, zones_transform=None, regions=None):
-    """``_process_image``'s ``zones`` (and ``zones_transform``, ``regions``) keywords, handed over only where they are named: without them
-    the call is the one it always was."""
+def _zones_argument(zones, zones_transform=None, regions=None, regions_geojson=False):
+    """``_process_image``'s ``zones`` (and ``zones_transform``, ``regions``, ``regions_geojson``) keywords, handed over only where they are
+    named: without them the call is the one it always was."""
     kw = {} if zones is None else {"zones": zones}
     if zones_transform is not None:
         kw["zones_transform"] = zones_transform
     if regions is not None:
         kw["regions"] = regions
+    if regions_geojson:
+        if regions is None:
+            raise ValueError("regions_geojson writes the outlines of the regions: it goes with regions")
+        kw["regions_geojson"] = True
     return kw
 
 
@@ -156,6 +160,25 @@ def _write_zones_csv(path, result, indices):
                 out.writerow([row["Zone"], t, row["Pixels"]] + [repr(v) for v in figures] + region)
 
 
+def _write_regions_geojson(path, result, indices, transform):
+    """``<stem>_regions.geojson``: one ``Polygon`` feature per region (``zones.polygons_to_geojson``), in pixel coordinates or, with
+    ``transform``, in the world coordinates of that geotransform.  A feature's properties are its rows of the CSV: the region's id, area,
+    box and centroid, and per index the figures under ``zones.zonal_rows``'s keys (a NaN figure is written as null)."""
+    import json
+    from .zones import polygons_to_geojson, zonal_rows
+    zones = result["zones"]
+    table = zones["regions"]
+    props = [{"Zone": int(z), "Pixels": int(n), "Area": int(a), **{c: int(v) for c, v in zip(REGION_CSV_COLUMNS[1:5], box)},
+              "Centroid Row": float(mid[0]), "Centroid Col": float(mid[1])}
+             for z, n, a, box, mid in zip(zones["zone"], zones["pixels"], table["area"], table["bbox"], table["centroid"])]
+    for t in indices:
+        for i, row in enumerate(zonal_rows(result, t)):
+            props[i].update({k: (v if v == v else None) for k, v in row.items() if k not in ("Zone", "Pixels")})
+    doc = {"type": "FeatureCollection", "features": []} if zones["outlines"] is None else polygons_to_geojson(zones["outlines"], transform, props)
+    with open(path, "w", encoding="utf-8") as f:
+        json.dump(doc, f)
+
+
 def _matching(png_encoder, tiff_encoder):
     """(the block that holds the knob ``deflate_matching`` at 1 where an encoder asks for it, the encoders without that suffix).
     The knob is one per process: ``batch_process`` enters the block once around its thread pool, not per file."""
@@ -166,7 +189,7 @@ def _matching(png_encoder, tiff_encoder):
 
 def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png",
                   png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow", tiff_encoder="pillow",
-                  index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None, regions=None):
+                  index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None, regions=None, regions_geojson=False):
     """One file: same outputs as backend-process.py:49-73.  Returns the statistics dicts.
     ``full_depth=True`` reads three-sample 16-bit TIFFs at their full depth (``tiffio.read_image``; Pillow, hence the
     reference, keeps their high bytes only).  ``lut_format="tiff"`` writes the colormap images as
@@ -200,7 +223,10 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     world coordinates of that GDAL geotransform.  The CSV has the same columns either way.
     ``regions=(index, "above" | "below", t, min_pixels)`` takes the zones from the picture instead (``zones.Regions``): the connected
     patches of ``index`` above / below ``t`` with ``min_pixels`` pixels or more, labelled on the device; the same CSV with each region's
-    area, box and centroid added.  ``index`` must be among the requested indices; not together with ``zones``."""
+    area, box and centroid added.  ``index`` must be among the requested indices; not together with ``zones``.
+    ``regions_geojson=True`` (with ``regions``) also writes ``<name>_regions.geojson``: the outline of every region, traced on the
+    device (``zones.region_outlines``'s rings), one feature per region with its CSV figures as properties, in pixel coordinates or
+    through ``zones_transform`` in world coordinates."""
     if lut_format not in ("png", "png8", "tiff"):
         raise ValueError(f"lut_format must be 'png', 'png8' or 'tiff', got {lut_format!r}")
     _check_png_encoder(png_encoder)
@@ -212,11 +238,12 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     block, png_encoder, tiff_encoder = _matching(png_encoder, tiff_encoder)
     with block:
         return _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder,
-                              tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw), **_zones_argument(zones, zones_transform, regions))
+                              tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw),
+                              **_zones_argument(zones, zones_transform, regions, regions_geojson))
 
 
 def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder, tiff_decoder,
-                   tiff_encoder, index_tiff, mask_kw=None, zones=None, zones_transform=None, regions=None):
+                   tiff_encoder, index_tiff, mask_kw=None, zones=None, zones_transform=None, regions=None, regions_geojson=False):
     """``process_image`` behind its checks, for ``"pillow"``, ``"device"`` and ``"device+deflate"``."""
     from PIL import Image
     from .tiffio import read_image
@@ -234,13 +261,15 @@ def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_
         index, how, t, min_pixels = regions
         if index not in indices:
             raise ValueError(f"regions are taken from {index}, which is not among the requested indices {indices}")
-        zones = Regions(index=index, min_pixels=min_pixels, **{how: t})
+        zones = Regions(index=index, min_pixels=min_pixels, **{how: t}, **({"want_outlines": True} if regions_geojson else {}))
     if zones is not None and indices:
         from .zones import process_image_zones
         labels = zones if regions is not None else _read_zones(zones, zones_transform, arr.shape[:2], image_path.name)
         output_dir.mkdir(parents=True, exist_ok=True)
-        _write_zones_csv(output_dir / f"{name}_zones.csv",
-                         process_image_zones(arr, labels, **mask_kw, indices=indices, white_balance=True, want_arrays=False), indices)
+        zoned = process_image_zones(arr, labels, **mask_kw, indices=indices, white_balance=True, want_arrays=False)
+        _write_zones_csv(output_dir / f"{name}_zones.csv", zoned, indices)
+        if regions_geojson:
+            _write_regions_geojson(output_dir / f"{name}_regions.geojson", zoned, indices, zones_transform)
 
     def run(**kw):
         """``api.process_image`` of the file, or its masked form where a mask is set."""
@@ -316,14 +345,17 @@ def files_of_rank(files, rank=0, world=1):
 def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, process_gndvi=False,
                   process_ndwi=True, workers=4, verbose=True, full_depth=False, lut_format="png", rank=0, world=1,
                   device=None, png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow",
-                  tiff_encoder="pillow", index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None, regions=None):
+                  tiff_encoder="pillow", index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None, regions=None,
+                  regions_geojson=False):
     """backend-process.py:75-97 with its module constants as arguments.  Returns ``{file name: stats | error}``.
     ``rank`` / ``world``: one process per GPU, each takes its block of the sorted file list (``files_of_rank``); the output
     directories are shared, the file names distinct.  ``device``: the GPU ordinal every worker thread binds (the library's
     context is per thread and defaults to device 0); None leaves the threads' binding alone.  ``png_encoder``,
     ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``, ``tiff_encoder``, ``index_tiff``, ``nodata``, ``alpha_mask``, ``zones`` (one label
-    raster, or one file of polygons with its ``zones_transform``, for every file of the directory), ``regions``: see ``process_image``."""
+    raster, or one file of polygons with its ``zones_transform``, for every file of the directory), ``regions``, ``regions_geojson``: see
+    ``process_image``."""
     mask_kw = _mask_options(nodata, alpha_mask, lut_format)
+    zones_kw = _zones_argument(zones, zones_transform, regions, regions_geojson)
     _check_tiff_encoder(tiff_encoder)
     _check_png_encoder(png_encoder)
     _check_png_decoder(png_decoder)
@@ -342,8 +374,7 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
             if verbose:
                 print(f"Processing {idx}/{total}: {f.name}")
             return f.name, _process_image(f, output_path, process_wb, indices or None, full_depth, lut_format, png_encoder,
-                                          png_decoder, jpeg_decoder, tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw),
-                                          **_zones_argument(zones, zones_transform, regions))
+                                          png_decoder, jpeg_decoder, tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw), **zones_kw)
         except Exception as e:                              # same policy as upstream :96-97
             if verbose:
                 print(f"Error processing {f.name}: {str(e)}")
@@ -459,8 +490,13 @@ def main(argv=None):
     ap.add_argument("--regions", default=None, type=_regions_spec, metavar="INDEX:above:T[:min_pixels]",
                     help="take the zones from the picture: the connected patches of INDEX above (or 'below') T with min_pixels pixels or more, "
                          "labelled on the GPU; writes <name>_zones.csv with each region's area, box and centroid added.  Not with --zones")
+    ap.add_argument("--regions-geojson", action="store_true",
+                    help="with --regions: also write <name>_regions.geojson, the outline of every region traced on the GPU, one feature per "
+                         "region with its CSV figures as properties; --zones-transform puts it in world coordinates")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
+    if args.regions_geojson and args.regions is None:
+        ap.error("--regions-geojson writes the outlines of the regions: it goes with --regions")
     from .dist import env_rank_world
     rank, local_rank, world = env_rank_world()
     res = batch_process(args.input_dir, args.output_dir, args.wb, args.ndvi, args.gndvi, args.ndwi, args.workers,
@@ -468,7 +504,7 @@ def main(argv=None):
                         device=local_rank if world > 1 else None, png_encoder=args.png_encoder,
                         png_decoder=args.png_decoder, jpeg_decoder=args.jpeg_decoder, tiff_decoder=args.tiff_decoder,
                         tiff_encoder=args.tiff_encoder, index_tiff=args.index_tiff, nodata=args.nodata, alpha_mask=args.alpha_mask,
-                        **_zones_argument(args.zones, args.zones_transform, args.regions))
+                        **_zones_argument(args.zones, args.zones_transform, args.regions, args.regions_geojson))
     failed = {k: str(v) for k, v in res.items() if isinstance(v, Exception)}
     print(json.dumps({"rank": rank, "world": world, "files": len(res), "failed": failed}))
     return 1 if failed else 0

@@ -11,7 +11,11 @@ them, ``polygons_from_geojson`` reads the outlines from a GeoJSON export and ``t
 
 And where nobody drew outlines, the picture's own connected regions serve (DESIGN.md "Zones from regions", csrc/regions.hip):
 ``Regions(mask=...)`` or ``Regions(index=, above= / below=)`` labels the patches of a mask or of a thresholded plane on the device;
-``label_regions`` returns such labels with each region's area, box and centroid."""
+``label_regions`` returns such labels with each region's area, box and centroid.
+
+The regions leave as shapes too (DESIGN.md "Region outlines", csrc/outlines.hip): ``region_outlines``, or ``Regions(...,
+want_outlines=True)``, traces the ring of pixel borders around every region and every hole on the device, as ``Polygons`` that
+``rasterize_zones`` turns back into the same labels; ``polygons_to_geojson`` writes them, ``to_world`` applies a geotransform."""
 from __future__ import annotations
 
 import ctypes as C
@@ -28,6 +32,7 @@ from .api import _coverage_rule, _picture, _picture_result
 ZONES_MAX = 65535
 VERTICES_MAX = 1 << 24
 COORDINATE_MAX = 1e9
+OUTLINE_PIXELS_MAX = 1 << 29
 _FIGURES = ("mean", "median", "min", "max", "coverage")
 
 
@@ -64,25 +69,39 @@ def _labels(zones, shape, n_zones, who):
     return np.ascontiguousarray(z), n_zones
 
 
+def _geotransform(points, transform, who):
+    """``(points as float64 [..., 2], the six numbers, their determinant)``: the checks ``to_pixel`` and ``to_world`` share."""
+    try:
+        t = np.asarray(transform, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: transform must be six numbers (x0, dx, rx, y0, ry, dy), got {transform!r}") from None
+    if t.shape != (6,) or not np.isfinite(t).all():
+        raise ValueError(f"{who}: transform must be six finite numbers (x0, dx, rx, y0, ry, dy), got {transform!r}")
+    det = t[1] * t[5] - t[2] * t[4]
+    if det == 0 or not np.isfinite(det):
+        raise ValueError(f"{who}: the transform {tuple(t)} is singular: dx * dy - rx * ry = {det}")
+    pts = np.asarray(points, dtype=np.float64)
+    if pts.ndim < 1 or pts.shape[-1] != 2:
+        raise ValueError(f"{who}: points must be [..., 2] (x, y), got shape {pts.shape}")
+    return pts, t, det
+
+
 def to_pixel(points, transform):
     """World coordinates ``[..., 2]`` -> pixel coordinates (x along the columns, y along the rows; pixel (i, j) has its centre at
     (j + 0.5, i + 0.5)) by the inverse of a GDAL geotransform ``(x0, dx, rx, y0, ry, dy)``: X = x0 + x * dx + y * rx, Y = y0 + x * ry +
     y * dy.  Float64 NumPy on the host.  A transform that is not six finite numbers or has no inverse raises ``ValueError``."""
-    try:
-        t = np.asarray(transform, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f"to_pixel: transform must be six numbers (x0, dx, rx, y0, ry, dy), got {transform!r}") from None
-    if t.shape != (6,) or not np.isfinite(t).all():
-        raise ValueError(f"to_pixel: transform must be six finite numbers (x0, dx, rx, y0, ry, dy), got {transform!r}")
-    x0, dx, rx, y0, ry, dy = t
-    det = dx * dy - rx * ry
-    if det == 0 or not np.isfinite(det):
-        raise ValueError(f"to_pixel: the transform {tuple(t)} is singular: dx * dy - rx * ry = {det}")
-    pts = np.asarray(points, dtype=np.float64)
-    if pts.ndim < 1 or pts.shape[-1] != 2:
-        raise ValueError(f"to_pixel: points must be [..., 2] (x, y), got shape {pts.shape}")
+    pts, (x0, dx, rx, y0, ry, dy), det = _geotransform(points, transform, "to_pixel")
     u, v = pts[..., 0] - x0, pts[..., 1] - y0
     return np.stack(((u * dy - v * rx) / det, (v * dx - u * ry) / det), axis=-1)
+
+
+def to_world(points, transform):
+    """Pixel coordinates ``[..., 2]`` (x along the columns, y along the rows) -> world coordinates by a GDAL geotransform
+    ``(x0, dx, rx, y0, ry, dy)``: X = x0 + x * dx + y * rx, Y = y0 + x * ry + y * dy; the inverse of ``to_pixel``, with its checks.
+    Float64 NumPy on the host."""
+    pts, (x0, dx, rx, y0, ry, dy), _ = _geotransform(points, transform, "to_world")
+    x, y = pts[..., 0], pts[..., 1]
+    return np.stack((x0 + x * dx + y * rx, y0 + x * ry + y * dy), axis=-1)
 
 
 def _rings_of(item, k, who):
@@ -181,8 +200,19 @@ class Polygons:
         self.poly_starts = np.asarray(poly_starts, dtype=np.int32)
         self.want_labels = bool(want_labels)
 
+    @classmethod
+    def _packed(cls, verts, ring_starts, poly_starts):
+        """Arrays that are packed already, as the tracer of ``region_outlines`` leaves them: nothing to check."""
+        self = object.__new__(cls)
+        self.verts, self.ring_starts, self.poly_starts, self.want_labels = verts, ring_starts, poly_starts, False
+        return self
+
     def __len__(self):
         return len(self.poly_starts) - 1
+
+    def rings(self, k):
+        """The rings of polygon ``k`` (0-based): a list of ``[n, 2]`` views of ``verts``."""
+        return [self.verts[self.ring_starts[r]:self.ring_starts[r + 1]] for r in range(self.poly_starts[k], self.poly_starts[k + 1])]
 
     def _head(self):
         """The six polygon arguments of the C entry points."""
@@ -270,18 +300,98 @@ def label_regions(mask, connectivity=8, min_pixels=1):
     return {"labels": _label_view(labels, (h, w), width.value), "n_regions": r, **_region_table(table[:r])}
 
 
+class _OutlineRoom:
+    """The host arrays the tracer fills and the ``lars_outlines`` that names them: room for ``rings`` rows and ``verts`` vertices."""
+
+    def __init__(self, rings, verts):
+        self.rings = np.empty(rings, dtype=_ffi.RING_DTYPE)
+        self.verts = np.empty((verts, 2), dtype=np.int32)
+        self.c = _ffi.Outlines(self.rings.ctypes.data, rings, self.verts.ctypes.data, verts, -1, -1, -1)
+
+    def short(self):
+        """Did the call end because the rings or vertices found do not fit?"""
+        return self.c.n_rings > len(self.rings) or self.c.n_vertices > len(self.verts)
+
+    def result(self, n_regions):
+        """``"outlines"`` (a ``Polygons`` in pixel coordinates, or None where there is no region), ``"ring_area2"``, ``"n_rings"`` and
+        ``"n_vertices"``.  The vertices stay in the order the device wrote them: (row, col) int32 becomes (x, y) float64."""
+        q, v = self.c.n_rings, self.c.n_vertices
+        table = self.rings[:q]
+        out = {"outlines": None, "ring_area2": table["area2"].astype(np.int64), "n_rings": q, "n_vertices": v}
+        if n_regions:
+            ring_starts = np.append(table["start"], np.int32(v)).astype(np.int32)
+            poly_starts = np.searchsorted(table["label"], np.arange(1, n_regions + 2)).astype(np.int32)
+            out["outlines"] = Polygons._packed(np.ascontiguousarray(self.verts[:v, ::-1], dtype=np.float64), ring_starts, poly_starts)
+        return out
+
+
+def _outline_pixels(shape, who):
+    if int(shape[0]) * int(shape[1]) >= OUTLINE_PIXELS_MAX:
+        raise ValueError(f"{who}: the raster has {int(shape[0]) * int(shape[1])} pixels; outlines are traced on fewer than 2**29 (an edge id fits int32)")
+
+
+def region_outlines(mask, connectivity=8, min_pixels=1):
+    """``label_regions`` plus the outline of every region, traced on the device from the labels where they stand (DESIGN.md "Region
+    outlines", csrc/outlines.hip).
+
+    Returns ``label_regions``'s dict and ``"outlines"``: a ``Polygons`` in pixel coordinates, (x, y) = (column, row) float64 on the
+    pixel corners, polygon ``k - 1`` = region ``k``; its first ring is the region's outer ring, clockwise on the screen, the others
+    are its holes, counter-clockwise; rows and columns alternate along a ring and no vertex lies inside a straight run.  Under
+    connectivity 8 a ring passes twice through a corner where the region touches itself diagonally; under 4 it turns there.
+    ``"ring_area2"``: int64, the exact doubled signed area of each ring (positive: outer, negative: hole; a region's rings add up to
+    twice its pixels), ``"n_rings"`` and ``"n_vertices"``.  ``rasterize_zones(result["outlines"], mask.shape)`` gives the labels back
+    (up to 65535 regions).  No region: empty arrays and ``"outlines": None``.  Fewer than 2**29 pixels.  Integer arithmetic on the
+    device: the same bytes on every run."""
+    who = "region_outlines"
+    if np.ndim(mask) == 2:
+        _outline_pixels(np.shape(mask), who)                       # before anything is allocated
+    m = _foreground(mask, who)
+    connectivity = _connectivity(connectivity, who)
+    min_pixels = _whole(min_pixels, "min_pixels", 1, (1 << 63) - 1, who)
+    h, w = m.shape
+    labels = np.empty((h, w), dtype=np.int32)
+    apart = ((h + 1) // 2) * ((w + 1) // 2) if connectivity == 8 else (h * w + 1) // 2
+    foreground = int(np.count_nonzero(m))
+    capacity = max(1, min(foreground, apart, 1 << 20))                      # label_regions's rule
+    # a foreground pixel has four edges at most, a ring four at least: room that is never short, in pages nobody touches until they are
+    # written, up to 2**22 rings and 2**24 vertices; a call that finds more is repeated with the room it reported
+    rings, verts = max(1, min(foreground, 1 << 22)), max(4, min(4 * foreground, 1 << 24))
+    while True:
+        table = np.zeros(capacity, dtype=_ffi.REGION_DTYPE)
+        room = _OutlineRoom(rings, verts)
+        count, width = C.c_int64(-1), C.c_int(0)
+        try:
+            _ffi.call("lars_h_region_outlines", _ffi.ptr(m), h, w, connectivity, min_pixels, 0, _ffi.ptr(labels), C.byref(width), _ffi.ptr(table),
+                      capacity, C.byref(count), C.byref(room.c))
+            break
+        except _ffi.LarsError:
+            if count.value > capacity:
+                capacity = count.value
+            elif room.short():
+                rings, verts = max(rings, room.c.n_rings), max(verts, room.c.n_vertices)
+            else:
+                raise
+    r = count.value
+    return {"labels": _label_view(labels, (h, w), width.value), "n_regions": r, **_region_table(table[:r]), **room.result(r)}
+
+
 class Regions:
     """Zones taken from the picture itself: ``Regions(mask=None, index=None, above=None, below=None, connectivity=8, min_pixels=1,
-    max_regions=4096, want_labels=False)``, a third kind of ``zones`` beside a label raster and ``Polygons``.
+    max_regions=4096, want_labels=False, want_outlines=False, max_vertices=1 << 22)``, a third kind of ``zones`` beside a label raster
+    and ``Polygons``.
 
     The foreground is a host ``mask`` (bool or integer ``[H, W]``, nonzero = foreground) or a threshold, ``above=t`` or ``below=t``,
     compared in float32 with the plane handed to ``zonal_statistics`` or with the ``index`` plane of ``process_image_zones``
     (required there, and among its ``indices``); exactly one of the three is given.  Pixels outside ``valid`` / nodata are never
     foreground.  The regions are ``label_regions``'s with ``connectivity`` and ``min_pixels``, made on the device; zone ``z`` is region
     ``z``.  ``max_regions`` (1 to 65535) is the room of the result arrays: more regions raise ``ValueError`` with their number.
-    ``want_labels=True`` asks for the label raster as well.  Every check runs here, on the host."""
+    ``want_labels=True`` asks for the label raster as well.  ``want_outlines=True`` asks for the regions' outlines as
+    ``region_outlines`` returns them (``"outlines"``, ``"ring_area2"``, ``"n_rings"``, ``"n_vertices"``), traced from the labels the
+    zone stages used, on a raster of fewer than 2**29 pixels; ``max_vertices`` (4 to 2**31 - 1) is their room: more vertices raise
+    ``ValueError`` with their number.  Every check runs here, on the host."""
 
-    def __init__(self, mask=None, index=None, above=None, below=None, connectivity=8, min_pixels=1, max_regions=4096, want_labels=False):
+    def __init__(self, mask=None, index=None, above=None, below=None, connectivity=8, min_pixels=1, max_regions=4096, want_labels=False,
+                 want_outlines=False, max_vertices=1 << 22):
         who = "Regions"
         given = [name for name, v in (("mask", mask), ("above", above), ("below", below)) if v is not None]
         if len(given) != 1:
@@ -306,6 +416,8 @@ class Regions:
         self.min_pixels = _whole(min_pixels, "min_pixels", 1, (1 << 63) - 1, who)
         self.max_regions = _whole(max_regions, "max_regions", 1, ZONES_MAX, who)
         self.want_labels = bool(want_labels)
+        self.want_outlines = bool(want_outlines)
+        self.max_vertices = _whole(max_vertices, "max_vertices", 4, (1 << 31) - 1, who)
 
     def _check(self, shape, picture_indices, who):
         """What only the call knows: the mask's shape, and the plane of a threshold.  Returns the id of that plane."""
@@ -313,6 +425,8 @@ class Regions:
             raise ValueError(f"{who}: the Regions mask has shape {self.mask.shape}, the raster is {tuple(shape)}")
         if int(shape[0]) * int(shape[1]) >= 1 << 31:
             raise ValueError(f"{who}: the raster has {int(shape[0]) * int(shape[1])} pixels; regions are labelled on fewer than 2**31")
+        if self.want_outlines:
+            _outline_pixels(shape, who)
         if picture_indices is None:
             if self.index is not None:
                 raise ValueError(f"{who}: Regions(index={self.index!r}) names a plane of a picture; the threshold is compared with index_array here")
@@ -328,6 +442,14 @@ class Regions:
     def _too_many(self, who, count):
         return ValueError(f"{who}: {count} regions, more than max_regions = {self.max_regions}: raise min_pixels to drop the small ones, or "
                           f"max_regions (at most {ZONES_MAX} regions make one label raster)")
+
+    def _outline_room(self):
+        """Room for the outlines where they are wanted: a ring has four vertices or more."""
+        return _OutlineRoom(self.max_vertices // 4, self.max_vertices) if self.want_outlines else None
+
+    def _too_many_vertices(self, who, count):
+        return ValueError(f"{who}: the outlines have {count} vertices, more than max_vertices = {self.max_vertices}: raise min_pixels to drop the "
+                          f"small regions, or max_vertices")
 
 
 def _zone_source(zones, n_zones, who):
@@ -446,6 +568,38 @@ def polygons_from_geojson(obj_or_path):
     return out
 
 
+def polygons_to_geojson(polygons, transform=None, properties=None):
+    """A GeoJSON ``FeatureCollection`` dict of polygons: one ``Polygon`` feature per polygon, its rings in the order held, each closed
+    by repeating its first vertex.
+
+    ``polygons``: a ``Polygons`` (``region_outlines``'s ``"outlines"``) or anything ``Polygons`` takes, in pixel coordinates.
+    ``transform``: the six numbers of a GDAL geotransform; the coordinates then go through ``to_world``.  ``properties``: a list of
+    one dict per polygon, or None for empty ones.  ``polygons_from_geojson`` reads the result back ring for ring, the closing vertex
+    included (it returns rings as they stand, and a repeated vertex changes no label of ``rasterize_zones``).
+
+    Rings are not reversed.  ``region_outlines`` writes outer rings clockwise as the eye sees them on the screen and holes
+    counter-clockwise, and a north-up transform (``dy < 0``) shows the same picture: on the map they still run clockwise, their
+    shoelace sum with Y upwards is negative.  RFC 7946 recommends the other order (outer rings counter-clockwise) and asks readers not
+    to reject this one; a reader that insists wants every ring reversed.  Under connectivity 8 an outer ring may touch itself at a
+    corner: some readers call such a ring invalid; connectivity 4 never writes one."""
+    who = "polygons_to_geojson"
+    polys = polygons if isinstance(polygons, Polygons) else Polygons(polygons, who=who)
+    if properties is not None:
+        properties = list(properties)
+        if len(properties) != len(polys) or not all(isinstance(p, dict) for p in properties):
+            raise ValueError(f"{who}: properties must be a list of {len(polys)} dicts, one per polygon")
+    verts = polys.verts if transform is None else to_world(polys.verts, transform)
+    features = []
+    for k in range(len(polys)):
+        rings = []
+        for r in range(polys.poly_starts[k], polys.poly_starts[k + 1]):
+            ring = verts[polys.ring_starts[r]:polys.ring_starts[r + 1]]
+            rings.append(ring.tolist() + [ring[0].tolist()])
+        features.append({"type": "Feature", "properties": dict(properties[k]) if properties is not None else {},
+                         "geometry": {"type": "Polygon", "coordinates": rings}})
+    return {"type": "FeatureCollection", "features": features}
+
+
 def _bad_labels(who, bad, n_zones):
     return ValueError(f"{who}: {bad} pixels have a label outside 0 .. {n_zones}")
 
@@ -506,17 +660,26 @@ def zonal_statistics(index_array, zones, index_type, valid=None, n_zones=None, w
         table = np.zeros(nz, dtype=_ffi.REGION_DTYPE)
         made = np.empty((h, w), dtype=np.int32) if regions.want_labels else None
         found, width = C.c_int64(-1), C.c_int(0)
+        room = regions._outline_room()
+        head = (_ffi.ptr(x), _ffi.ptr(regions.mask), regions.mode, regions.threshold, regions.connectivity, regions.min_pixels, _ffi.ptr(valid_arr), h, w,
+                np.float32(threshold), int(bool(want_hist)), nz, _ffi.ptr(records), _ffi.ptr(medians), _ffi.ptr(table), C.byref(found), _ffi.ptr(made),
+                0, C.byref(width))
         try:
-            _ffi.call("lars_h_zonal_stats_regions_f32", _ffi.ptr(x), _ffi.ptr(regions.mask), regions.mode, regions.threshold, regions.connectivity,
-                      regions.min_pixels, _ffi.ptr(valid_arr), h, w, np.float32(threshold), int(bool(want_hist)), nz, _ffi.ptr(records),
-                      _ffi.ptr(medians), _ffi.ptr(table), C.byref(found), _ffi.ptr(made), 0, C.byref(width))
+            if room:
+                _ffi.call("lars_h_zonal_stats_regions_outlines_f32", *head, C.byref(room.c))
+            else:
+                _ffi.call("lars_h_zonal_stats_regions_f32", *head)
         except _ffi.LarsError:
             if found.value > nz:
                 raise regions._too_many(who, found.value) from None
+            if room and room.short():
+                raise regions._too_many_vertices(who, room.c.n_vertices) from None
             raise
         nz = found.value
         records, medians = records[:nz], medians[:nz]
         extra["regions"] = _region_table(table[:nz])
+        if room:
+            extra.update(room.result(nz))
         if regions.want_labels:
             extra["labels"] = _label_view(made, (h, w), width.value)
     elif polys:
@@ -562,14 +725,18 @@ def process_image_zones(img_array, zones, valid=None, nodata=None, n_zones=None,
     p_rgba, p_lut = _ffi.ptr3(p.rgbas), _ffi.ptr3(p.luts)
     made = polys._label_buffer((p.h, p.w)) if polys and polys.want_labels else None
     found, width = C.c_int64(-1), C.c_int(0)
+    room = regions._outline_room() if regions else None
     try:
         if regions:
             table = np.zeros(nz, dtype=_ffi.REGION_DTYPE)
             made = np.empty((p.h, p.w), dtype=np.int32) if regions.want_labels else None
-            _ffi.call("lars_h_process_image_regions", *p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha),
-                      int(p.nodata is not None), p.nodata or 0, C.byref(nvalid), _ffi.ptr(regions.mask), source, regions.mode, regions.threshold,
-                      regions.connectivity, regions.min_pixels, nz, _ffi.ptr(records), _ffi.ptr(medians), _ffi.ptr(table), C.byref(found),
-                      _ffi.ptr(made), 0, C.byref(width))
+            head = (*p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha), int(p.nodata is not None), p.nodata or 0,
+                    C.byref(nvalid), _ffi.ptr(regions.mask), source, regions.mode, regions.threshold, regions.connectivity, regions.min_pixels, nz,
+                    _ffi.ptr(records), _ffi.ptr(medians), _ffi.ptr(table), C.byref(found), _ffi.ptr(made), 0, C.byref(width))
+            if room:
+                _ffi.call("lars_h_process_image_regions_outlines", *head, C.byref(room.c))
+            else:
+                _ffi.call("lars_h_process_image_regions", *head)
         elif polys:
             _ffi.call("lars_h_process_image_zones_polygons", *p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha),
                       int(p.nodata is not None), p.nodata or 0, C.byref(nvalid), *polys._head(), _ffi.ptr(records), _ffi.ptr(medians),
@@ -585,6 +752,8 @@ def process_image_zones(img_array, zones, valid=None, nodata=None, n_zones=None,
             raise _bad_labels(who, bad.value, nz) from None
         if regions and found.value > nz:
             raise regions._too_many(who, found.value) from None
+        if room and room.short():
+            raise regions._too_many_vertices(who, room.c.n_vertices) from None
         raise
     result = _picture_result(p, want_hist, want_rgba, False, valid_pixels=nvalid.value)
     if regions:
@@ -594,6 +763,8 @@ def process_image_zones(img_array, zones, valid=None, nodata=None, n_zones=None,
     result["zones"] = {"zone": np.arange(1, nz + 1, dtype=np.int64)}
     if regions:
         result["zones"]["regions"] = _region_table(table[:nz])
+        if room:
+            result["zones"].update(room.result(nz))
     if made is not None:
         result["zones"]["labels"] = made
     for t in indices:
