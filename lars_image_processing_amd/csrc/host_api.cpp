@@ -3,8 +3,9 @@
 // reference function).  Each call stages through the calling
 // thread's grow-only device workspace and stream, so concurrent Streamlit
 // sessions (threads) do not share mutable state.  The array, colormap, alignment
-// and change-detection entry points are here; the single-picture path
-// (process_image and its variants) is host_image.cpp.
+// and change-detection entry points are here; the picture path (process_image
+// and its variants) is host_image.cpp, the zone path (zonal statistics of a
+// plane, label_regions, region_outlines, rasterize_zones) host_zones.cpp.
 #include <string.h>
 
 #include "common.h"

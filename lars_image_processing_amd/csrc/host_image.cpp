@@ -1,284 +1,15 @@
-// The single-picture path of the host entry points: fix_white_balance, calculate_index, process_image and its PNG, TIFF,
-// masked and zones variants, zonal_stats and valid_mask.  Every picture entry point fills an ImageJob (picture_job plus what is
-// its own) and hands it to run_image, which decides the route once (route_of) and then runs a short sequence of stages:
-// plan, upload, planes and statistics (one runner per route), pictures, TIFF, collect, fetch files.
-#include <math.h>
+// The picture path of the host entry points: fix_white_balance, calculate_index, process_image and its PNG, TIFF, masked, zones,
+// polygons and regions variants, and valid_mask.  Every picture entry point fills an ImageJob (picture_job plus what is its own) and
+// hands it to run_image, which decides the route once (route_of) and then runs a short sequence of stages: plan, upload, planes and
+// statistics (one runner per route), pictures, TIFF, collect, fetch files.  Zones are seen only through host_zones.h: a job names
+// where its labels come from (ZoneSource), and the masked runner ends with run_zones (host_zones.cpp).
 #include <string.h>
-#include <vector>
 
-#include "common.h"
+#include "host_zones.h"
 
 using namespace lars;
 
 namespace {
-
-// ---- zonal statistics (zonal.hip): the device buffers of the four stages and their run, for both host entry points ----
-struct ZoneBufs {
-    char *labels;                  // [npix] labels, zone_bytes wide
-    uint64_t *counts;              // [nzones + 1], then the count of bad labels
-    uint64_t *ends, *cursors;      // [nzones + 1] each
-    float *out[3];                 // the values of each index, zone by zone
-    lars_stats *stats;             // [3][nzones]
-    float *med;                    // [3][nzones][2]
-    char *sel;                     // select scratch of the large zones
-    // labels made from polygons (zone_raster.hip): B.labels is then the int32 raster the rasteriser writes
-    double *verts;
-    int32_t *rings, *polys;
-    char *raster_scratch;
-    char *narrow;                  // the labels at the width the caller wants them back in, where that is not 4
-    // labels made from regions (regions.hip): B.labels is the int32 raster the labelling writes, raster_scratch its scratch
-    uint8_t *rmask;                // [npix] the foreground
-    lars_region *rtable;           // [capacity]
-    int64_t *rcount;               // R
-    int64_t *ocounts;              // [3] the tracer's counts, where the regions' outlines are wanted (outlines.hip)
-};
-
-// The polygons of a job, as the entry points take them (include/lars_hip.h "zones from polygons"); nzones = npolys.
-struct ZonePolys {
-    const double *verts; int64_t nverts;
-    const int32_t *ring_starts; int64_t nrings;
-    const int32_t *poly_starts; int64_t npolys;
-    void *labels_out; int label_bytes;     // host [h][w] labels back, or null
-};
-
-// The regions of a job (include/lars_hip.h "zones from regions"): nzones is known only once the labels exist, the buffers are sized
-// by the capacity of the caller's record arrays.
-struct ZoneRegions {
-    const uint8_t *mask;                   // host [h][w] foreground, or null: the plane `source` above (mode 1) or below (mode 2) t
-    int source, mode;
-    float t;
-    int connectivity;
-    int64_t min_pixels, capacity;
-    lars_region *table_out;                // host [capacity]
-    int64_t *n_regions;
-    void *labels_out; int label_bytes; int *label_bytes_out;     // host [h][w] labels back, or null; label_bytes 0: the narrowest
-    int64_t h, w;
-    lars_outlines *outlines;               // the regions' rings and vertices back as well (outlines.hip), or null
-};
-
-ZoneBufs zone_plan(Carver &c, size_t npix, int zone_bytes, int64_t nzones, uint32_t mask, const ZonePolys *P = nullptr,
-                   const ZoneRegions *G = nullptr)
-{
-    ZoneBufs B;
-    memset(&B, 0, sizeof B);
-    const size_t nz = (size_t)nzones;
-    if (P) {
-        B.verts = c.take<double>(2 * (size_t)P->nverts);
-        B.rings = c.take<int32_t>((size_t)P->nrings + 1);
-        B.polys = c.take<int32_t>((size_t)P->npolys + 1);
-        B.raster_scratch = c.take<char>(lars_zone_rasterize_scratch_bytes(P->npolys));
-        B.narrow = (P->labels_out && P->label_bytes != 4) ? c.take<char>(npix * (size_t)P->label_bytes) : nullptr;
-    }
-    if (G) {
-        B.rmask = c.take<uint8_t>(npix);
-        B.rtable = c.take<lars_region>((size_t)G->capacity);
-        B.rcount = c.take<int64_t>(1);
-        B.ocounts = G->outlines ? c.take<int64_t>(3) : nullptr;
-        B.raster_scratch = c.take<char>(lars_region_label_scratch_bytes(G->h, G->w));
-        B.narrow = (G->labels_out && G->label_bytes != 4) ? c.take<char>(npix * 2) : nullptr;
-    }
-    B.labels = c.take<char>(npix * (size_t)zone_bytes);
-    B.counts = c.take<uint64_t>(nz + 2);
-    B.ends = c.take<uint64_t>(nz + 1);
-    B.cursors = c.take<uint64_t>(nz + 1);
-    for (int k = 0; k < 3; ++k) B.out[k] = ((mask >> k) & 1u) ? c.take<float>(npix) : nullptr;
-    B.stats = c.take<lars_stats>(3 * nz);
-    B.med = c.take<float>(6 * nz);
-    B.sel = c.take<char>(lars_select_scratch_bytes());
-    return B;
-}
-
-// Everything about the polygons that needs no device: the first ring or vertex that breaks a rule is named.
-int check_polygons(const char *who, const ZonePolys &P, int64_t h, int64_t w)
-{
-    if (!P.verts || !P.ring_starts || !P.poly_starts) return fail(LARS_ERR_INVALID, "%s: verts, ring_starts and poly_starts are required", who);
-    if (P.npolys < 1 || P.npolys > LARS_ZONES_MAX) return fail(LARS_ERR_INVALID, "%s: 1 to %d polygons, got %lld", who, LARS_ZONES_MAX, (long long)P.npolys);
-    if (P.nrings < P.npolys || P.nverts < 3 * P.nrings || P.nverts > LARS_ZONE_VERTS_MAX)
-        return fail(LARS_ERR_INVALID, "%s: %lld polygons need as many rings or more (got %lld) of three vertices or more each (got %lld in all, at most %d)",
-                    who, (long long)P.npolys, (long long)P.nrings, (long long)P.nverts, LARS_ZONE_VERTS_MAX);
-    if (h <= 0 || w <= 0 || h > (1 << 24) || w > (1 << 24)) return fail(LARS_ERR_INVALID, "%s: the raster is 1 to 2^24 on each side", who);
-    if (P.labels_out && P.label_bytes != 1 && P.label_bytes != 2 && P.label_bytes != 4)
-        return fail(LARS_ERR_INVALID, "%s: labels come back 1, 2 or 4 bytes wide, got %d", who, P.label_bytes);
-    if (P.labels_out && ((P.label_bytes == 1 && P.npolys > 255) || !aligned_to(P.labels_out, (uintptr_t)P.label_bytes)))
-        return fail(LARS_ERR_INVALID, "%s: %lld labels do not fit %d-byte labels, or the labels are not aligned", who, (long long)P.npolys, P.label_bytes);
-    if (P.poly_starts[0] != 0 || P.poly_starts[P.npolys] != P.nrings || P.ring_starts[0] != 0 || P.ring_starts[P.nrings] != P.nverts)
-        return fail(LARS_ERR_INVALID, "%s: poly_starts must run from 0 to nrings and ring_starts from 0 to nverts", who);
-    for (int64_t k = 0; k < P.npolys; ++k)
-        if (P.poly_starts[k + 1] <= P.poly_starts[k] || P.poly_starts[k + 1] > P.nrings)
-            return fail(LARS_ERR_INVALID, "%s: polygon %lld has no ring (poly_starts must rise)", who, (long long)k);
-    for (int64_t r = 0; r < P.nrings; ++r)
-        if ((int64_t)P.ring_starts[r + 1] - P.ring_starts[r] < 3 || P.ring_starts[r + 1] > P.nverts)
-            return fail(LARS_ERR_INVALID, "%s: ring %lld has fewer than three vertices (ring_starts must rise by three or more)", who, (long long)r);
-    for (int64_t i = 0; i < 2 * P.nverts; ++i)
-        if (!(fabs(P.verts[i]) <= 1e9))
-            return fail(LARS_ERR_INVALID, "%s: vertex %lld has a coordinate that is not finite or beyond 1e9 in size", who, (long long)(i / 2));
-    return LARS_OK;
-}
-
-// the polygons up, their labels into B.labels (int32) and, where the caller wants them, back at his width: on the stream
-int raster_zones(const ZoneBufs &B, const ZonePolys &P, int64_t h, int64_t w, hipStream_t s)
-{
-    LARS_HIP_TRY(hipMemcpyAsync(B.verts, P.verts, 2 * (size_t)P.nverts * sizeof(double), hipMemcpyHostToDevice, s));
-    LARS_HIP_TRY(hipMemcpyAsync(B.rings, P.ring_starts, ((size_t)P.nrings + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    LARS_HIP_TRY(hipMemcpyAsync(B.polys, P.poly_starts, ((size_t)P.npolys + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    int32_t *labels = reinterpret_cast<int32_t *>(B.labels);
-    LARS_TRY(lars_d_zone_rasterize(B.verts, P.nverts, B.rings, P.nrings, B.polys, P.npolys, h, w, labels, B.raster_scratch, s));
-    if (!P.labels_out) return LARS_OK;
-    const size_t npix = (size_t)h * (size_t)w;
-    if (B.narrow) LARS_TRY(lars_d_zone_labels_narrow(labels, (int64_t)npix, P.label_bytes, B.narrow, s));
-    LARS_HIP_TRY(hipMemcpyAsync(P.labels_out, B.narrow ? B.narrow : B.labels, npix * (size_t)P.label_bytes, hipMemcpyDeviceToHost, s));
-    return LARS_OK;
-}
-
-// What the region entry points check before they touch the device.
-int check_regions(const char *who, const ZoneRegions &G, int64_t most)
-{
-    if (G.h < 1 || G.w < 1 || !lars_region_label_scratch_bytes(G.h, G.w))
-        return fail(LARS_ERR_INVALID, "%s: the raster is 1 or more on each side and has fewer than 2^31 pixels", who);
-    if (!G.mask && G.mode != 1 && G.mode != 2) return fail(LARS_ERR_INVALID, "%s: a mask, or mode 1 (above t) or 2 (below t), is required", who);
-    if (G.connectivity != 4 && G.connectivity != 8) return fail(LARS_ERR_INVALID, "%s: connectivity must be 4 or 8, got %d", who, G.connectivity);
-    if (G.min_pixels < 1) return fail(LARS_ERR_INVALID, "%s: min_pixels must be 1 or more, got %lld", who, (long long)G.min_pixels);
-    if (G.capacity < 1 || G.capacity > most || !G.table_out || !G.n_regions)
-        return fail(LARS_ERR_INVALID, "%s: a table of capacity 1 to %lld and n_regions are required, got %lld", who, (long long)most, (long long)G.capacity);
-    if (G.labels_out && G.label_bytes != 0 && G.label_bytes != 1 && G.label_bytes != 2 && G.label_bytes != 4)
-        return fail(LARS_ERR_INVALID, "%s: labels come back 1, 2 or 4 bytes wide (0: the narrowest), got %d", who, G.label_bytes);
-    if (G.labels_out && !aligned_to(G.labels_out, 4)) return fail(LARS_ERR_INVALID, "%s: the labels are not aligned", who);
-    if (G.outlines) {
-        lars_outlines &O = *G.outlines;
-        O.n_rings = O.n_vertices = O.n_edges = -1;
-        if (!lars_region_outline_scratch_bytes(G.h, G.w, 0))
-            return fail(LARS_ERR_INVALID, "%s: outlines are traced on fewer than 2^29 pixels (an edge id fits int32), got %lld x %lld", who, (long long)G.h, (long long)G.w);
-        if (O.ring_capacity < 0 || O.vert_capacity < 0 || (O.ring_capacity > 0 && !O.rings) || (O.vert_capacity > 0 && !O.verts) ||
-            !aligned_to(O.rings, 8) || !aligned_to(O.verts, 4))
-            return fail(LARS_ERR_INVALID, "%s: the outlines need a ring table and a vertex array of capacity >= 0, 8- and 4-byte aligned", who);
-    }
-    return LARS_OK;
-}
-
-// The outlines of the nregions labels in B.labels (int32), once everything else of the call is on the stream.  Three waits: for the
-// edge count, which sizes the tracer's own area (the labels stand in the workspace, which cannot grow under them), for the ring and
-// vertex counts, which may exceed the caller's room, and for the rows and vertices.
-int trace_zone_outlines(const char *who, const ZoneBufs &B, const ZoneRegions &G, int64_t nregions, hipStream_t s)
-{
-    lars_outlines &O = *G.outlines;
-    O.n_rings = O.n_vertices = O.n_edges = 0;
-    if (!nregions) return LARS_OK;
-    ThreadCtx *c;
-    LARS_TRY(ensure_ctx(&c));
-    const int32_t *labels = reinterpret_cast<const int32_t *>(B.labels);
-    int64_t counts[3] = {-1, -1, -1};
-    LARS_TRY(lars_d_region_outline_count(labels, G.h, G.w, B.ocounts, s));
-    LARS_HIP_TRY(hipMemcpyAsync(counts, B.ocounts, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    const int64_t edges = counts[0];
-    const size_t tracer = edges > 0 ? lars_region_outline_scratch_bytes(G.h, G.w, edges) : 0;
-    if (!tracer) return fail(LARS_ERR_INVALID, "%s: %lld regions with %lld edges", who, (long long)nregions, (long long)edges);
-    O.n_edges = edges;
-    // no more rings than the tracer's own ring arrays hold, no more vertices than edges
-    const int64_t rcap = O.ring_capacity < edges / 4 + 1 ? O.ring_capacity : edges / 4 + 1, vcap = O.vert_capacity < edges ? O.vert_capacity : edges;
-    char *scratch;
-    lars_outline_ring *rings;
-    int32_t *verts;
-    auto plan = [&](Carver &d) { scratch = d.take<char>(tracer), rings = d.take<lars_outline_ring>((size_t)rcap), verts = d.take<int32_t>(2 * (size_t)vcap); };
-    Carver size(nullptr);
-    plan(size);
-    LARS_TRY(outline_reserve(c, size.bytes() + 256));
-    Carver area(c->outline);
-    plan(area);
-    LARS_TRY(lars_d_region_outline(labels, G.h, G.w, G.connectivity, nregions, edges, rings, rcap, verts, vcap, B.ocounts, scratch, s));
-    LARS_HIP_TRY(hipMemcpyAsync(counts, B.ocounts, sizeof counts, hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    O.n_rings = counts[1];
-    O.n_vertices = counts[2];
-    if (counts[0] != edges || counts[1] < 1 || counts[2] < 4) return fail(LARS_ERR_HIP, "%s: the tracer counted %lld edges after %lld", who, (long long)counts[0], (long long)edges);
-    if (counts[1] > O.ring_capacity || counts[2] > O.vert_capacity)
-        return fail(LARS_ERR_INVALID, "%s: %lld rings and %lld vertices; the room is %lld and %lld", who, (long long)counts[1], (long long)counts[2],
-                    (long long)O.ring_capacity, (long long)O.vert_capacity);
-    LARS_HIP_TRY(hipMemcpyAsync(O.rings, rings, (size_t)counts[1] * sizeof(lars_outline_ring), hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipMemcpyAsync(O.verts, verts, 2 * (size_t)counts[2] * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    return LARS_OK;
-}
-
-// The foreground (uploaded, or the plane against t; never outside valid_dev), its labels into B.labels (int32) and R to the host: the one
-// wait of this route.  R above the capacity ends the call; otherwise the table's R rows and, where wanted, the labels follow on the stream.
-int label_zone_regions(const char *who, const ZoneBufs &B, const ZoneRegions &G, const float *plane, const uint8_t *valid_dev, int64_t *nzones,
-                       hipStream_t s)
-{
-    const size_t npix = (size_t)G.h * (size_t)G.w;
-    if (G.mask) LARS_HIP_TRY(hipMemcpyAsync(B.rmask, G.mask, npix, hipMemcpyHostToDevice, s));
-    if (!G.mask || valid_dev)
-        LARS_TRY(lars_d_region_mask_f32(G.mask ? nullptr : plane, G.mask ? B.rmask : nullptr, valid_dev, (int64_t)npix, G.t, G.mode == 2, B.rmask, s));
-    int32_t *labels = reinterpret_cast<int32_t *>(B.labels);
-    LARS_TRY(lars_d_region_label(B.rmask, G.h, G.w, G.connectivity, G.min_pixels, labels, B.rtable, G.capacity, B.rcount, B.raster_scratch, s));
-    int64_t r = -1;
-    LARS_HIP_TRY(hipMemcpyAsync(&r, B.rcount, sizeof r, hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    *G.n_regions = r;
-    int bytes = G.label_bytes ? G.label_bytes : r <= 255 ? 1 : r <= 65535 ? 2 : 4;
-    if (r < 0 || r > G.capacity || (G.labels_out && ((bytes == 1 && r > 255) || (bytes == 2 && r > 65535))))
-        return fail(LARS_ERR_INVALID, "%s: %lld regions; the capacity is %lld%s", who, (long long)r, (long long)G.capacity,
-                    r <= G.capacity ? " and the labels are too narrow for them" : "");
-    *nzones = r;
-    if (r) LARS_HIP_TRY(hipMemcpyAsync(G.table_out, B.rtable, (size_t)r * sizeof(lars_region), hipMemcpyDeviceToHost, s));
-    if (!G.labels_out) return LARS_OK;
-    if (G.label_bytes_out) *G.label_bytes_out = bytes;
-    if (bytes != 4) LARS_TRY(lars_d_zone_labels_narrow(labels, (int64_t)npix, bytes, B.narrow, s));
-    LARS_HIP_TRY(hipMemcpyAsync(G.labels_out, bytes != 4 ? B.narrow : B.labels, npix * (size_t)bytes, hipMemcpyDeviceToHost, s));
-    return LARS_OK;
-}
-
-// labels up (or made from the polygons P or the regions G, zone_bytes 4), the four stages, the records down (host_stats[3][nzones], host_med[3][nzones][2]; rows outside mask untouched).
-// The counts cross to the host once: bad labels end the call there, and zones above the knob zone_split_pixels take the array
-// kernels, which spread one zone over many workgroups.  The copies down are on the stream when this returns: the caller waits.
-int run_zones(const char *who, const ZoneBufs &B, const void *zones, int zone_bytes, const uint8_t *valid_dev, int64_t npix, int64_t nzones,
-              const float *const planes[3], uint32_t mask, const float thr[3], int want_hist, lars_stats *host_stats, float *host_med,
-              int64_t *bad_labels, hipStream_t s, const ZonePolys *P = nullptr, int64_t h = 0, int64_t w = 0, const ZoneRegions *G = nullptr)
-{
-    // with regions nzones becomes R here and the host rows keep the stride of the caller's capacity; no region is a result, not an error
-    const size_t host_stride = (size_t)(G ? G->capacity : nzones);
-    if (G) {
-        LARS_TRY(label_zone_regions(who, B, *G, planes[G->source], valid_dev, &nzones, s));
-        if (!nzones) return G->outlines ? trace_zone_outlines(who, B, *G, 0, s) : LARS_OK;
-    }
-    const size_t nz = (size_t)nzones;
-    if (P) LARS_TRY(raster_zones(B, *P, h, w, s));
-    else if (!G) LARS_HIP_TRY(hipMemcpyAsync(B.labels, zones, (size_t)npix * zone_bytes, hipMemcpyHostToDevice, s));
-    LARS_TRY(lars_d_zone_count(B.labels, zone_bytes, valid_dev, npix, nzones, B.counts, B.counts + nz + 1, s));
-    std::vector<uint64_t> counts(nz + 2);
-    LARS_HIP_TRY(hipMemcpyAsync(counts.data(), B.counts, (nz + 2) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    if (bad_labels) *bad_labels = (int64_t)counts[nz + 1];
-    if (counts[nz + 1])
-        return fail(LARS_ERR_INVALID, "%s: %llu labels outside 0 .. %lld", who, (unsigned long long)counts[nz + 1], (long long)nzones);
-    LARS_TRY(lars_d_zone_offsets(B.counts, nzones, B.ends, B.cursors, s));
-    LARS_TRY(lars_d_zone_scatter(planes, mask, B.labels, zone_bytes, valid_dev, npix, nzones, B.ends, B.cursors, B.out, s));
-    const int64_t split = tuning().zone_split_pixels;
-    for (int k = 0; k < 3; ++k) {
-        if (!((mask >> k) & 1u)) continue;
-        lars_stats *st = B.stats + k * nz;
-        float *med = B.med + 2 * k * nz;
-        LARS_TRY(lars_d_zone_stats(B.out[k], B.ends, B.counts, nzones, thr[k], want_hist, split, st, med, s));
-        uint64_t lo = 0;
-        for (size_t z = 1; z <= nz; lo += counts[z], ++z) {
-            if (counts[z] <= (uint64_t)split) continue;
-            LARS_TRY(lars_d_array_stats_f32(B.out[k] + lo, (int64_t)counts[z], thr[k], want_hist, st + (z - 1), s));
-            LARS_TRY(lars_d_median_pair_f32(B.out[k] + lo, (int64_t)counts[z], med + 2 * (z - 1), B.sel, s));
-        }
-        LARS_HIP_TRY(hipMemcpyAsync(host_stats + k * host_stride, st, nz * sizeof(lars_stats), hipMemcpyDeviceToHost, s));
-        LARS_HIP_TRY(hipMemcpyAsync(host_med + 2 * k * host_stride, med, 2 * nz * sizeof(float), hipMemcpyDeviceToHost, s));
-    }
-    if (G && G->outlines) LARS_TRY(trace_zone_outlines(who, B, *G, nzones, s));
-    return LARS_OK;
-}
-
-int zone_arguments(const char *who, const void *zones, int zone_bytes, int64_t nzones, const void *stats, const void *medians)
-{
-    if (!zones || !stats || !medians) return fail(LARS_ERR_INVALID, "%s: zones, their records and their medians are required", who);
-    if (zone_bytes != 1 && zone_bytes != 2 && zone_bytes != 4) return fail(LARS_ERR_INVALID, "%s: labels are 1, 2 or 4 bytes wide, got %d", who, zone_bytes);
-    if (nzones < 1 || nzones > LARS_ZONES_MAX) return fail(LARS_ERR_INVALID, "%s: 1 to %d zones, got %lld", who, LARS_ZONES_MAX, (long long)nzones);
-    return LARS_OK;
-}
 
 // ---- the job: what an entry point asks for ----
 struct ImageJob {
@@ -310,14 +41,8 @@ struct ImageJob {
     int use_alpha, has_nodata, nodata;
     int64_t *valid_pixels;
     // ... with one record per zone and index as well (zonal.hip): the planes stay on the device for the zone stages
-    const void *zones;            // [h][w] labels 0 .. nzones, zone_bytes wide, or null
-    int zone_bytes;
-    int64_t nzones;
-    lars_stats *zone_stats;       // [3][nzones]
-    float *zone_medians;          // [3][nzones][2]
-    int64_t *bad_labels;
-    const ZonePolys *polys;       // ... or the plots' outlines instead of zones: the labels are made on the device (zone_raster.hip)
-    const ZoneRegions *regions;   // ... or the connected regions of a mask or of a thresholded plane (regions.hip); nzones = their capacity
+    const ZoneSource *zone_src;   // where the labels come from (a raster, polygons or regions), or null: no zones
+    ZoneOutputs zone_out;         // the caller's per-zone arrays, zone_src->rows() rows to each index
 };
 
 // The head every picture entry point shares, in the order of their prototypes; each entry point adds only what is its own.
@@ -394,6 +119,26 @@ int check_picture(const char *who, const void *img, int64_t h, int64_t w, int ch
     return LARS_OK;
 }
 
+// The head the picture-plus-zones entry points share: the out-parameters reset, every check that is not the source's own, and the
+// job with its mask and its zone outputs.  Each entry point adds only the checks of its source (src must outlive the job).
+int zones_job(ImageJob *j, const char *who, const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+              int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians, uint8_t *const out_rgba[3],
+              const uint8_t *const cmap_lut[3], const uint8_t *valid, int use_alpha, int has_nodata, int nodata, int64_t *valid_pixels,
+              const ZoneSource &src, const ZoneOutputs &out)
+{
+    if (valid_pixels) *valid_pixels = -1;
+    reset_zone_outputs(src, out.bad_labels);
+    LARS_TRY(check_picture(who, img, h, w, channels, dtype, index_mask, use_alpha, has_nodata, nodata, out_rgba, cmap_lut));
+    if (!index_mask || (index_mask & ~LARS_MASK_ALL)) return fail(LARS_ERR_INVALID, "%s: index_mask must name one to three indices", who);
+    LARS_TRY(check_zone_records(who, src, out.stats, out.medians));
+    *j = picture_job(who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut);
+    // the masked route even when no mask is given: the results are the same by definition
+    under_mask(*j, valid, use_alpha, has_nodata, nodata, valid_pixels);
+    j->zone_src = &src;
+    j->zone_out = out;
+    return LARS_OK;
+}
+
 // ---- the route: which path produces the planes and the statistics, and which float32 planes must exist on the device ----
 struct Route {
     enum Planes {
@@ -429,7 +174,7 @@ Route route_of(const ImageJob &j)
         const bool for_caller = j.out_index[k] != nullptr;                       // it is copied back
         const bool for_entries = r.entry[k];                                     // the entry plane is derived from it on the device
         const bool for_tiff = j.tiff != 0;                                       // its file is encoded from it
-        const bool for_zones = j.zones != nullptr || j.polys != nullptr || j.regions != nullptr;   // the zone stages scatter it
+        const bool for_zones = j.zone_src != nullptr;                            // the zone stages scatter it
         const bool for_median = r.medians && r.planes == Route::FUSED;           // the select over the plane reads it
         r.plane[k] = on && (for_caller || for_entries || for_tiff || for_zones || for_median);
     }
@@ -497,7 +242,7 @@ Layout plan(const ImageJob &j, const Route &r, Carver &c)
     L.vhist = (j.masked && j.apply_wb) ? c.take<uint32_t>(3 * nval) : nullptr;
     for (int k = 0; k < 3; ++k)
         L.vals[k] = (j.masked && ((j.mask >> k) & 1u) && (j.stats || j.medians)) ? c.take<float>(npix) : nullptr;
-    if (j.zones || j.polys || j.regions) L.zone = zone_plan(c, npix, j.zone_bytes, j.nzones, j.mask, j.polys, j.regions);
+    if (j.zone_src) L.zone = plan_zones(c, *j.zone_src, j.mask);
     return L;
 }
 
@@ -581,10 +326,9 @@ int run_masked(const ImageJob &j, const Layout &L, hipStream_t s)
         if (j.stats) LARS_TRY(lars_d_array_stats_f32(L.vals[k], (int64_t)nvalid, k == LARS_NDWI ? 0.0f : 0.2f, j.want_hist, L.stats + k, s));
         if (j.medians) LARS_TRY(lars_d_median_pair_f32(L.vals[k], (int64_t)nvalid, L.med + 2 * k, L.sel + k * select_slot(), s));
     }
-    if (!j.zones && !j.polys && !j.regions) return LARS_OK;
-    const float thr[3] = {0.2f, 0.2f, 0.0f};                // as the records above
-    return run_zones(j.who, L.zone, j.zones, j.zone_bytes, L.vmask, npix, j.nzones, L.idx, j.mask, thr, j.want_hist, j.zone_stats,
-                     j.zone_medians, j.bad_labels, s, j.polys, j.h, j.w, j.regions);
+    if (!j.zone_src) return LARS_OK;
+    const ZonePlanes in = {{L.idx[0], L.idx[1], L.idx[2]}, j.mask, L.vmask, {0.2f, 0.2f, 0.0f}, j.want_hist};     // the thresholds of the records above
+    return run_zones(j.who, *j.zone_src, L.zone, in, j.zone_out, s);
 }
 
 // ---- stage 4: the planes and pictures back, entry planes and PNG files built from what stays on the device ----
@@ -780,16 +524,11 @@ int lars_h_process_image_zones(const void *img, int64_t h, int64_t w, int channe
                                lars_stats *zone_stats, float *zone_medians, int64_t *bad_labels)
 {
     static const char *who = "lars_h_process_image_zones";
-    if (valid_pixels) *valid_pixels = -1;
-    if (bad_labels) *bad_labels = -1;
-    LARS_TRY(check_picture(who, img, h, w, channels, dtype, index_mask, use_alpha, has_nodata, nodata, out_rgba, cmap_lut));
-    if (!index_mask || (index_mask & ~LARS_MASK_ALL)) return fail(LARS_ERR_INVALID, "%s: index_mask must name one to three indices", who);
-    LARS_TRY(zone_arguments(who, zones, zone_bytes, nzones, zone_stats, zone_medians));
-    ImageJob j = picture_job(who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut);
-    // the masked route even when no mask is given: the results are the same by definition
-    under_mask(j, valid, use_alpha, has_nodata, nodata, valid_pixels);
-    j.zones = zones; j.zone_bytes = zone_bytes; j.nzones = nzones; j.zone_stats = zone_stats; j.zone_medians = zone_medians;
-    j.bad_labels = bad_labels;
+    const ZoneSource src = ZoneSource::raster(h, w, zones, zone_bytes, nzones);
+    ImageJob j;
+    LARS_TRY(zones_job(&j, who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut, valid,
+                       use_alpha, has_nodata, nodata, valid_pixels, src, {zone_stats, zone_medians, bad_labels}));
+    LARS_TRY(check_zone_source(who, src, LARS_ZONES_MAX));
     return run_image(j);
 }
 
@@ -801,15 +540,11 @@ int lars_h_process_image_zones_polygons(const void *img, int64_t h, int64_t w, i
                                         lars_stats *zone_stats, float *zone_medians, void *labels_out, int label_bytes)
 {
     static const char *who = "lars_h_process_image_zones_polygons";
-    if (valid_pixels) *valid_pixels = -1;
-    LARS_TRY(check_picture(who, img, h, w, channels, dtype, index_mask, use_alpha, has_nodata, nodata, out_rgba, cmap_lut));
-    if (!index_mask || (index_mask & ~LARS_MASK_ALL)) return fail(LARS_ERR_INVALID, "%s: index_mask must name one to three indices", who);
-    if (!zone_stats || !zone_medians) return fail(LARS_ERR_INVALID, "%s: the zones' records and medians are required", who);
-    const ZonePolys P = {verts, nverts, ring_starts, nrings, poly_starts, npolys, labels_out, label_bytes};
-    LARS_TRY(check_polygons(who, P, h, w));
-    ImageJob j = picture_job(who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut);
-    under_mask(j, valid, use_alpha, has_nodata, nodata, valid_pixels);
-    j.polys = &P; j.zone_bytes = 4; j.nzones = npolys; j.zone_stats = zone_stats; j.zone_medians = zone_medians;
+    const ZoneSource src = ZoneSource::of(h, w, ZonePolys{verts, nverts, ring_starts, nrings, poly_starts, npolys, labels_out, label_bytes});
+    ImageJob j;
+    LARS_TRY(zones_job(&j, who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut, valid,
+                       use_alpha, has_nodata, nodata, valid_pixels, src, {zone_stats, zone_medians, nullptr}));
+    LARS_TRY(check_zone_source(who, src, LARS_ZONES_MAX));
     return run_image(j);
 }
 
@@ -822,19 +557,14 @@ int lars_h_process_image_regions_outlines(const void *img, int64_t h, int64_t w,
                                           lars_outlines *outlines)
 {
     const char *who = outlines ? "lars_h_process_image_regions_outlines" : "lars_h_process_image_regions";
-    if (valid_pixels) *valid_pixels = -1;
-    if (n_regions) *n_regions = -1;
-    LARS_TRY(check_picture(who, img, h, w, channels, dtype, index_mask, use_alpha, has_nodata, nodata, out_rgba, cmap_lut));
-    if (!index_mask || (index_mask & ~LARS_MASK_ALL)) return fail(LARS_ERR_INVALID, "%s: index_mask must name one to three indices", who);
-    if (!zone_stats || !zone_medians) return fail(LARS_ERR_INVALID, "%s: the zones' records and medians are required", who);
+    const ZoneSource src = ZoneSource::of(h, w, ZoneRegions{mask, mask ? 0 : source_index, mode, t, connectivity, min_pixels, capacity, table, n_regions,
+                                                            labels_out, label_bytes, label_bytes_out, outlines});
+    ImageJob j;
+    LARS_TRY(zones_job(&j, who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut, valid,
+                       use_alpha, has_nodata, nodata, valid_pixels, src, {zone_stats, zone_medians, nullptr}));
     if (!mask && (source_index < 0 || source_index > 2 || !((index_mask >> source_index) & 1u)))
         return fail(LARS_ERR_INVALID, "%s: source_index %d is not among the indices of index_mask", who, source_index);
-    const ZoneRegions G = {mask, mask ? 0 : source_index, mode, t, connectivity, min_pixels, capacity, table, n_regions, labels_out, label_bytes,
-                           label_bytes_out, h, w, outlines};
-    LARS_TRY(check_regions(who, G, LARS_ZONES_MAX));
-    ImageJob j = picture_job(who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut);
-    under_mask(j, valid, use_alpha, has_nodata, nodata, valid_pixels);
-    j.regions = &G; j.zone_bytes = 4; j.nzones = capacity; j.zone_stats = zone_stats; j.zone_medians = zone_medians;
+    LARS_TRY(check_zone_source(who, src, LARS_ZONES_MAX));
     return run_image(j);
 }
 
@@ -849,140 +579,6 @@ int lars_h_process_image_regions(const void *img, int64_t h, int64_t w, int chan
                                                  cmap_lut, valid, use_alpha, has_nodata, nodata, valid_pixels, mask, source_index, mode, t, connectivity,
                                                  min_pixels, capacity, zone_stats, zone_medians, table, n_regions, labels_out, label_bytes, label_bytes_out,
                                                  nullptr);
-}
-
-}  // extern "C"
-
-namespace {
-
-// zonal_statistics of a host plane, with the labels uploaded (zones) or rasterised (P)
-int zonal_stats(const char *who, const float *x, const void *zones, int zone_bytes, const ZonePolys *P, const uint8_t *valid, int64_t h, int64_t w,
-                int64_t nzones, float threshold, int want_hist, lars_stats *stats, float *medians, int64_t *bad_labels, const ZoneRegions *G = nullptr)
-{
-    ThreadCtx *c;
-    LARS_TRY(ensure_ctx(&c));
-    if (!x || h <= 0 || w <= 0) return fail(LARS_ERR_INVALID, "%s: x must be a non-empty [h][w] float32 array", who);
-    if (P || G) {
-        if (!stats || !medians) return fail(LARS_ERR_INVALID, "%s: the zones' records and medians are required", who);
-        LARS_TRY(P ? check_polygons(who, *P, h, w) : check_regions(who, *G, LARS_ZONES_MAX));
-    } else {
-        LARS_TRY(zone_arguments(who, zones, zone_bytes, nzones, stats, medians));
-    }
-    const size_t npix = (size_t)h * w;
-    float *dx;
-    uint8_t *dvalid;
-    ZoneBufs B;
-    LARS_TRY(ws_plan(c, [&](Carver &d) {
-        dx = d.take<float>(npix);
-        dvalid = valid ? d.take<uint8_t>(npix) : nullptr;
-        B = zone_plan(d, npix, zone_bytes, nzones, 1u, P, G);
-    }));
-    hipStream_t s = c->stream;
-    LARS_HIP_TRY(hipMemcpyAsync(dx, x, npix * sizeof(float), hipMemcpyHostToDevice, s));
-    if (valid) LARS_HIP_TRY(hipMemcpyAsync(dvalid, valid, npix, hipMemcpyHostToDevice, s));
-    const float *planes[3] = {dx, nullptr, nullptr};
-    const float thr[3] = {threshold, threshold, threshold};
-    LARS_TRY(run_zones(who, B, zones, zone_bytes, dvalid, (int64_t)npix, nzones, planes, 1u, thr, want_hist, stats, medians, bad_labels, s, P, h, w, G));
-    LARS_HIP_TRY(hipStreamSynchronize(s));
-    return LARS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int lars_h_zonal_stats_f32(const float *x, const void *zones, int zone_bytes, const uint8_t *valid, int64_t h, int64_t w, int64_t nzones,
-                           float threshold, int want_hist, lars_stats *stats, float *medians, int64_t *bad_labels)
-{
-    if (bad_labels) *bad_labels = -1;
-    return zonal_stats("lars_h_zonal_stats_f32", x, zones, zone_bytes, nullptr, valid, h, w, nzones, threshold, want_hist, stats, medians, bad_labels);
-}
-
-int lars_h_zonal_stats_polygons_f32(const float *x, const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings,
-                                    const int32_t *poly_starts, int64_t npolys, const uint8_t *valid, int64_t h, int64_t w, float threshold,
-                                    int want_hist, lars_stats *stats, float *medians, void *labels_out, int label_bytes)
-{
-    const ZonePolys P = {verts, nverts, ring_starts, nrings, poly_starts, npolys, labels_out, label_bytes};
-    return zonal_stats("lars_h_zonal_stats_polygons_f32", x, nullptr, 4, &P, valid, h, w, npolys, threshold, want_hist, stats, medians, nullptr);
-}
-
-int lars_h_zonal_stats_regions_outlines_f32(const float *x, const uint8_t *mask, int mode, float t, int connectivity, int64_t min_pixels,
-                                            const uint8_t *valid, int64_t h, int64_t w, float threshold, int want_hist, int64_t capacity,
-                                            lars_stats *stats, float *medians, lars_region *table, int64_t *n_regions, void *labels_out,
-                                            int label_bytes, int *label_bytes_out, lars_outlines *outlines)
-{
-    if (n_regions) *n_regions = -1;
-    const ZoneRegions G = {mask, 0, mode, t, connectivity, min_pixels, capacity, table, n_regions, labels_out, label_bytes, label_bytes_out, h, w, outlines};
-    return zonal_stats(outlines ? "lars_h_zonal_stats_regions_outlines_f32" : "lars_h_zonal_stats_regions_f32", x, nullptr, 4, nullptr, valid, h, w, capacity,
-                       threshold, want_hist, stats, medians, nullptr, &G);
-}
-
-int lars_h_zonal_stats_regions_f32(const float *x, const uint8_t *mask, int mode, float t, int connectivity, int64_t min_pixels,
-                                   const uint8_t *valid, int64_t h, int64_t w, float threshold, int want_hist, int64_t capacity, lars_stats *stats,
-                                   float *medians, lars_region *table, int64_t *n_regions, void *labels_out, int label_bytes, int *label_bytes_out)
-{
-    return lars_h_zonal_stats_regions_outlines_f32(x, mask, mode, t, connectivity, min_pixels, valid, h, w, threshold, want_hist, capacity, stats, medians, table,
-                                                   n_regions, labels_out, label_bytes, label_bytes_out, nullptr);
-}
-
-// label_regions, and region_outlines where outlines are wanted: the labels stay in the workspace for the tracer
-static int label_regions_call(const char *who, const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int label_bytes, void *labels,
-                              int *label_bytes_out, lars_region *table, int64_t capacity, int64_t *n_regions, lars_outlines *outlines)
-{
-    ThreadCtx *c;
-    LARS_TRY(ensure_ctx(&c));
-    if (n_regions) *n_regions = -1;
-    if (!mask || !labels) return fail(LARS_ERR_INVALID, "%s: mask and labels are required", who);
-    const ZoneRegions G = {mask, 0, 0, 0.0f, connectivity, min_pixels, capacity, table, n_regions, labels, label_bytes, label_bytes_out, h, w, outlines};
-    LARS_TRY(check_regions(who, G, 0x7FFFFFFF));
-    ZoneBufs B;
-    memset(&B, 0, sizeof B);
-    const size_t npix = (size_t)h * (size_t)w;
-    LARS_TRY(ws_plan(c, [&](Carver &d) {
-        B.labels = d.take<char>(npix * 4);
-        B.rmask = d.take<uint8_t>(npix);
-        B.rtable = d.take<lars_region>((size_t)capacity);
-        B.rcount = d.take<int64_t>(1);
-        B.ocounts = outlines ? d.take<int64_t>(3) : nullptr;
-        B.raster_scratch = d.take<char>(lars_region_label_scratch_bytes(h, w));
-        B.narrow = label_bytes != 4 ? d.take<char>(npix * 2) : nullptr;
-    }));
-    int64_t r = 0;
-    LARS_TRY(label_zone_regions(who, B, G, nullptr, nullptr, &r, c->stream));
-    if (outlines) LARS_TRY(trace_zone_outlines(who, B, G, r, c->stream));
-    LARS_HIP_TRY(hipStreamSynchronize(c->stream));
-    return LARS_OK;
-}
-
-int lars_h_label_regions(const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int label_bytes, void *labels,
-                         int *label_bytes_out, lars_region *table, int64_t capacity, int64_t *n_regions)
-{
-    return label_regions_call("lars_h_label_regions", mask, h, w, connectivity, min_pixels, label_bytes, labels, label_bytes_out, table, capacity, n_regions,
-                              nullptr);
-}
-
-int lars_h_region_outlines(const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int label_bytes, void *labels,
-                           int *label_bytes_out, lars_region *table, int64_t capacity, int64_t *n_regions, lars_outlines *outlines)
-{
-    static const char *who = "lars_h_region_outlines";
-    if (!outlines) return fail(LARS_ERR_INVALID, "%s: outlines == NULL", who);
-    return label_regions_call(who, mask, h, w, connectivity, min_pixels, label_bytes, labels, label_bytes_out, table, capacity, n_regions, outlines);
-}
-
-int lars_h_rasterize_zones(const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts,
-                           int64_t npolys, int64_t h, int64_t w, int zone_bytes, void *labels)
-{
-    static const char *who = "lars_h_rasterize_zones";
-    ThreadCtx *c;
-    LARS_TRY(ensure_ctx(&c));
-    if (!labels) return fail(LARS_ERR_INVALID, "%s: labels == NULL", who);
-    const ZonePolys P = {verts, nverts, ring_starts, nrings, poly_starts, npolys, labels, zone_bytes};
-    LARS_TRY(check_polygons(who, P, h, w));
-    ZoneBufs B;
-    LARS_TRY(ws_plan(c, [&](Carver &d) { B = zone_plan(d, (size_t)h * (size_t)w, 4, npolys, 0u, &P); }));
-    LARS_TRY(raster_zones(B, P, h, w, c->stream));
-    LARS_HIP_TRY(hipStreamSynchronize(c->stream));
-    return LARS_OK;
 }
 
 int lars_h_valid_mask(const void *img, int64_t h, int64_t w, int channels, int dtype, int use_alpha, int has_nodata, int nodata,

@@ -275,29 +275,7 @@ def label_regions(mask, connectivity=8, min_pixels=1):
     for up to 65535, otherwise int32; ``area`` int64 ``[R]``; ``bbox`` int32 ``[R, 4]`` (row0, col0, row1, col1, half-open);
     ``centroid`` float64 ``[R, 2]`` (row, column).  No region is a result: ``n_regions`` 0 and empty arrays.  Integer arithmetic on
     the device: the same bytes on every run."""
-    who = "label_regions"
-    m = _foreground(mask, who)
-    connectivity = _connectivity(connectivity, who)
-    min_pixels = _whole(min_pixels, "min_pixels", 1, (1 << 63) - 1, who)
-    h, w = m.shape
-    labels = np.empty((h, w), dtype=np.int32)
-    # rows of the table: no more than there are foreground pixels, or pixels no two of which touch; a picture with more than 2**20
-    # regions is labelled a second time with the room it asked for
-    apart = ((h + 1) // 2) * ((w + 1) // 2) if connectivity == 8 else (h * w + 1) // 2
-    capacity = max(1, min(int(np.count_nonzero(m)), apart, 1 << 20))
-    while True:
-        table = np.zeros(capacity, dtype=_ffi.REGION_DTYPE)
-        count, width = C.c_int64(-1), C.c_int(0)
-        try:
-            _ffi.call("lars_h_label_regions", _ffi.ptr(m), h, w, connectivity, min_pixels, 0, _ffi.ptr(labels), C.byref(width), _ffi.ptr(table),
-                      capacity, C.byref(count))
-            break
-        except _ffi.LarsError:
-            if count.value <= capacity:
-                raise
-            capacity = count.value
-    r = count.value
-    return {"labels": _label_view(labels, (h, w), width.value), "n_regions": r, **_region_table(table[:r])}
+    return _label_regions(mask, connectivity, min_pixels, "label_regions", False)
 
 
 class _OutlineRoom:
@@ -325,6 +303,11 @@ class _OutlineRoom:
         return out
 
 
+def _outline_argument(room):
+    """The trailing ``lars_outlines *`` of the entry points that trace outlines: none for those that do not."""
+    return (C.byref(room.c),) if room else ()
+
+
 def _outline_pixels(shape, who):
     if int(shape[0]) * int(shape[1]) >= OUTLINE_PIXELS_MAX:
         raise ValueError(f"{who}: the raster has {int(shape[0]) * int(shape[1])} pixels; outlines are traced on fewer than 2**29 (an edge id fits int32)")
@@ -342,37 +325,44 @@ def region_outlines(mask, connectivity=8, min_pixels=1):
     twice its pixels), ``"n_rings"`` and ``"n_vertices"``.  ``rasterize_zones(result["outlines"], mask.shape)`` gives the labels back
     (up to 65535 regions).  No region: empty arrays and ``"outlines": None``.  Fewer than 2**29 pixels.  Integer arithmetic on the
     device: the same bytes on every run."""
-    who = "region_outlines"
-    if np.ndim(mask) == 2:
+    return _label_regions(mask, connectivity, min_pixels, "region_outlines", True)
+
+
+def _label_regions(mask, connectivity, min_pixels, who, want_outlines):
+    """``label_regions``, and ``region_outlines`` where the outlines are wanted: one call, repeated with the room it reported where
+    the first guess was short."""
+    if want_outlines and np.ndim(mask) == 2:
         _outline_pixels(np.shape(mask), who)                       # before anything is allocated
     m = _foreground(mask, who)
     connectivity = _connectivity(connectivity, who)
     min_pixels = _whole(min_pixels, "min_pixels", 1, (1 << 63) - 1, who)
     h, w = m.shape
     labels = np.empty((h, w), dtype=np.int32)
+    # rows of the table: no more than there are foreground pixels, or pixels no two of which touch; a picture with more than 2**20
+    # regions is labelled a second time with the room it asked for
     apart = ((h + 1) // 2) * ((w + 1) // 2) if connectivity == 8 else (h * w + 1) // 2
     foreground = int(np.count_nonzero(m))
-    capacity = max(1, min(foreground, apart, 1 << 20))                      # label_regions's rule
+    capacity = max(1, min(foreground, apart, 1 << 20))
     # a foreground pixel has four edges at most, a ring four at least: room that is never short, in pages nobody touches until they are
     # written, up to 2**22 rings and 2**24 vertices; a call that finds more is repeated with the room it reported
     rings, verts = max(1, min(foreground, 1 << 22)), max(4, min(4 * foreground, 1 << 24))
     while True:
         table = np.zeros(capacity, dtype=_ffi.REGION_DTYPE)
-        room = _OutlineRoom(rings, verts)
+        room = _OutlineRoom(rings, verts) if want_outlines else None
         count, width = C.c_int64(-1), C.c_int(0)
         try:
-            _ffi.call("lars_h_region_outlines", _ffi.ptr(m), h, w, connectivity, min_pixels, 0, _ffi.ptr(labels), C.byref(width), _ffi.ptr(table),
-                      capacity, C.byref(count), C.byref(room.c))
+            _ffi.call("lars_h_region_outlines" if room else "lars_h_label_regions", _ffi.ptr(m), h, w, connectivity, min_pixels, 0, _ffi.ptr(labels),
+                      C.byref(width), _ffi.ptr(table), capacity, C.byref(count), *_outline_argument(room))
             break
         except _ffi.LarsError:
             if count.value > capacity:
                 capacity = count.value
-            elif room.short():
+            elif room and room.short():
                 rings, verts = max(rings, room.c.n_rings), max(verts, room.c.n_vertices)
             else:
                 raise
     r = count.value
-    return {"labels": _label_view(labels, (h, w), width.value), "n_regions": r, **_region_table(table[:r]), **room.result(r)}
+    return {"labels": _label_view(labels, (h, w), width.value), "n_regions": r, **_region_table(table[:r]), **(room.result(r) if room else {})}
 
 
 class Regions:
@@ -439,17 +429,9 @@ class Regions:
             raise ValueError(f"{who}: Regions(index={self.index!r}) is not among indices {list(picture_indices)}")
         return INDEX_IDS[self.index]
 
-    def _too_many(self, who, count):
-        return ValueError(f"{who}: {count} regions, more than max_regions = {self.max_regions}: raise min_pixels to drop the small ones, or "
-                          f"max_regions (at most {ZONES_MAX} regions make one label raster)")
-
     def _outline_room(self):
         """Room for the outlines where they are wanted: a ring has four vertices or more."""
         return _OutlineRoom(self.max_vertices // 4, self.max_vertices) if self.want_outlines else None
-
-    def _too_many_vertices(self, who, count):
-        return ValueError(f"{who}: the outlines have {count} vertices, more than max_vertices = {self.max_vertices}: raise min_pixels to drop the "
-                          f"small regions, or max_vertices")
 
 
 def _zone_source(zones, n_zones, who):
@@ -600,8 +582,101 @@ def polygons_to_geojson(polygons, transform=None, properties=None):
     return {"type": "FeatureCollection", "features": features}
 
 
-def _bad_labels(who, bad, n_zones):
-    return ValueError(f"{who}: {bad} pixels have a label outside 0 .. {n_zones}")
+class _RasterZones:
+    """The zones of one call, of the three kinds below: ``rows`` to allocate for each index, the entry point of a ``plane`` and of a
+    ``picture``, the kind's arguments in the layout of either (``plane_args``, and ``picture_args`` behind the picture's own),
+    ``explain()`` -- the ``ValueError`` of this kind for a call that failed, or None -- and ``finish()`` -> (Z, the extra keys).
+
+    This one: a label raster, checked (``_labels``)."""
+    plane, picture = "lars_h_zonal_stats_f32", "lars_h_process_image_zones"
+
+    def __init__(self, zones, shape, n_zones, who):
+        self.who, self.bad = who, C.c_int64(-1)
+        self.lab, self.rows = _labels(zones, shape, n_zones, who)
+
+    def plane_args(self, x, valid, h, w, threshold, want_hist, records, medians):
+        return (x, _ffi.ptr(self.lab), self.lab.dtype.itemsize, valid, h, w, self.rows, threshold, want_hist, records, medians, C.byref(self.bad))
+
+    def picture_args(self, records, medians):
+        return (_ffi.ptr(self.lab), self.lab.dtype.itemsize, self.rows, records, medians, C.byref(self.bad))
+
+    def explain(self):
+        if self.bad.value > 0:
+            return ValueError(f"{self.who}: {self.bad.value} pixels have a label outside 0 .. {self.rows}")
+
+    def finish(self):
+        return self.rows, {}
+
+
+class _PolygonZones:
+    """... ``Polygons``: the labels are made on the device and come back where they are wanted."""
+    plane, picture = "lars_h_zonal_stats_polygons_f32", "lars_h_process_image_zones_polygons"
+
+    def __init__(self, polys, shape):
+        self.polys, self.rows = polys, len(polys)
+        self.made = polys._label_buffer(shape) if polys.want_labels else None
+        self.tail = (_ffi.ptr(self.made), self.made.dtype.itemsize if polys.want_labels else 0)
+
+    def plane_args(self, x, valid, h, w, threshold, want_hist, records, medians):
+        return (x, *self.polys._head(), valid, h, w, threshold, want_hist, records, medians, *self.tail)
+
+    def picture_args(self, records, medians):
+        return (*self.polys._head(), records, medians, *self.tail)
+
+    def explain(self):
+        return None
+
+    def finish(self):
+        return self.rows, ({"labels": self.made} if self.made is not None else {})
+
+
+class _RegionZones:
+    """... ``Regions``: Z is known once the labels exist, ``max_regions`` rows are allocated; the table, the labels and the outlines
+    come back with it.  ``picture_indices``: None for a plane."""
+
+    def __init__(self, regions, shape, picture_indices, who):
+        self.regions, self.shape, self.who, self.rows = regions, shape, who, regions.max_regions
+        self.source = regions._check(shape, picture_indices, who)
+        self.table = np.zeros(self.rows, dtype=_ffi.REGION_DTYPE)
+        self.made = np.empty(shape, dtype=np.int32) if regions.want_labels else None
+        self.found, self.width = C.c_int64(-1), C.c_int(0)
+        self.room = regions._outline_room()
+        self.plane = "lars_h_zonal_stats_regions_outlines_f32" if self.room else "lars_h_zonal_stats_regions_f32"
+        self.picture = "lars_h_process_image_regions_outlines" if self.room else "lars_h_process_image_regions"
+        self.foreground = (_ffi.ptr(regions.mask), regions.mode, regions.threshold, regions.connectivity, regions.min_pixels)
+
+    def _tail(self, records, medians):
+        return (self.rows, records, medians, _ffi.ptr(self.table), C.byref(self.found), _ffi.ptr(self.made), 0, C.byref(self.width),
+                *_outline_argument(self.room))
+
+    def plane_args(self, x, valid, h, w, threshold, want_hist, records, medians):
+        return (x, *self.foreground, valid, h, w, threshold, want_hist, *self._tail(records, medians))
+
+    def picture_args(self, records, medians):
+        return (self.foreground[0], self.source, *self.foreground[1:], *self._tail(records, medians))
+
+    def explain(self):
+        r = self.regions
+        if self.found.value > self.rows:
+            return ValueError(f"{self.who}: {self.found.value} regions, more than max_regions = {r.max_regions}: raise min_pixels to drop the small "
+                              f"ones, or max_regions (at most {ZONES_MAX} regions make one label raster)")
+        if self.room and self.room.short():
+            return ValueError(f"{self.who}: the outlines have {self.room.c.n_vertices} vertices, more than max_vertices = {r.max_vertices}: raise "
+                              f"min_pixels to drop the small regions, or max_vertices")
+
+    def finish(self):
+        nz = self.found.value
+        extra = {"regions": _region_table(self.table[:nz]), **(self.room.result(nz) if self.room else {})}
+        if self.made is not None:
+            extra["labels"] = _label_view(self.made, self.shape, self.width.value)
+        return nz, extra
+
+
+def _zones_of_call(zones, n_zones, shape, picture_indices, who):
+    source = _zone_source(zones, n_zones, who)
+    if isinstance(source, Regions):
+        return _RegionZones(source, shape, picture_indices, who)
+    return _PolygonZones(source, shape) if source is not None else _RasterZones(zones, shape, n_zones, who)
 
 
 def _figures(records, medians, want_hist):
@@ -641,62 +716,24 @@ def zonal_statistics(index_array, zones, index_type, valid=None, n_zones=None, w
     if x.ndim != 2 or x.size == 0:
         raise ValueError(f"{who}: index_array must be a non-empty [H, W] array, got shape {x.shape}")
     h, w = x.shape
-    polys = _zone_source(zones, n_zones, who)
-    regions = polys if isinstance(polys, Regions) else None
-    if regions:
-        polys = None
-        regions._check((h, w), None, who)
-    lab, nz = (None, regions.max_regions) if regions else (None, len(polys)) if polys else _labels(zones, (h, w), n_zones, who)
+    z = _zones_of_call(zones, n_zones, (h, w), None, who)
     if isinstance(valid, str):
         raise TypeError(f"{who}: valid must be an [H, W] bool or integer array or None: a plane has no alpha channel")
     valid_arr, _ = _nodata.valid_argument(valid, (h, w, 0), who)
     _, threshold = _coverage_rule(index_type)
     x = np.ascontiguousarray(x)
-    records = np.zeros(nz, dtype=_ffi.STATS_DTYPE)
-    medians = np.zeros((nz, 2), dtype=np.float32)
-    bad = C.c_int64(-1)
-    extra = {}
-    if regions:
-        table = np.zeros(nz, dtype=_ffi.REGION_DTYPE)
-        made = np.empty((h, w), dtype=np.int32) if regions.want_labels else None
-        found, width = C.c_int64(-1), C.c_int(0)
-        room = regions._outline_room()
-        head = (_ffi.ptr(x), _ffi.ptr(regions.mask), regions.mode, regions.threshold, regions.connectivity, regions.min_pixels, _ffi.ptr(valid_arr), h, w,
-                np.float32(threshold), int(bool(want_hist)), nz, _ffi.ptr(records), _ffi.ptr(medians), _ffi.ptr(table), C.byref(found), _ffi.ptr(made),
-                0, C.byref(width))
-        try:
-            if room:
-                _ffi.call("lars_h_zonal_stats_regions_outlines_f32", *head, C.byref(room.c))
-            else:
-                _ffi.call("lars_h_zonal_stats_regions_f32", *head)
-        except _ffi.LarsError:
-            if found.value > nz:
-                raise regions._too_many(who, found.value) from None
-            if room and room.short():
-                raise regions._too_many_vertices(who, room.c.n_vertices) from None
+    records = np.zeros(z.rows, dtype=_ffi.STATS_DTYPE)
+    medians = np.zeros((z.rows, 2), dtype=np.float32)
+    try:
+        _ffi.call(z.plane, *z.plane_args(_ffi.ptr(x), _ffi.ptr(valid_arr), h, w, np.float32(threshold), int(bool(want_hist)), _ffi.ptr(records),
+                                         _ffi.ptr(medians)))
+    except _ffi.LarsError:
+        explained = z.explain()
+        if explained is None:
             raise
-        nz = found.value
-        records, medians = records[:nz], medians[:nz]
-        extra["regions"] = _region_table(table[:nz])
-        if room:
-            extra.update(room.result(nz))
-        if regions.want_labels:
-            extra["labels"] = _label_view(made, (h, w), width.value)
-    elif polys:
-        made = polys._label_buffer((h, w)) if polys.want_labels else None
-        _ffi.call("lars_h_zonal_stats_polygons_f32", _ffi.ptr(x), *polys._head(), _ffi.ptr(valid_arr), h, w, np.float32(threshold),
-                  int(bool(want_hist)), _ffi.ptr(records), _ffi.ptr(medians), _ffi.ptr(made), made.dtype.itemsize if polys.want_labels else 0)
-        if polys.want_labels:
-            extra["labels"] = made
-    else:
-        try:
-            _ffi.call("lars_h_zonal_stats_f32", _ffi.ptr(x), _ffi.ptr(lab), lab.dtype.itemsize, _ffi.ptr(valid_arr), h, w, nz,
-                      np.float32(threshold), int(bool(want_hist)), _ffi.ptr(records), _ffi.ptr(medians), C.byref(bad))
-        except _ffi.LarsError:
-            if bad.value > 0:
-                raise _bad_labels(who, bad.value, nz) from None
-            raise
-    count, out = _figures(records, medians, want_hist)
+        raise explained from None
+    nz, extra = z.finish()
+    count, out = _figures(records[:nz], medians[:nz], want_hist)
     return {"zone": np.arange(1, nz + 1, dtype=np.int64), "pixels": count, **out, **extra}
 
 
@@ -713,62 +750,24 @@ def process_image_zones(img_array, zones, valid=None, nodata=None, n_zones=None,
     p = _picture(who, who, img_array, list(indices), white_balance, want_arrays, bool(want_hist), want_rgba, False, valid, nodata,
                  need_index="zone statistics need at least one index")
     indices = p.indices
-    polys = _zone_source(zones, n_zones, who)
-    regions = polys if isinstance(polys, Regions) else None
-    if regions:
-        polys = None
-        source = regions._check((p.h, p.w), indices, who)
-    lab, nz = (None, regions.max_regions) if regions else (None, len(polys)) if polys else _labels(zones, (p.h, p.w), n_zones, who)
-    records = np.zeros((3, nz), dtype=_ffi.STATS_DTYPE)
-    medians = np.zeros((3, nz, 2), dtype=np.float32)
-    nvalid, bad = C.c_int64(-1), C.c_int64(-1)
+    z = _zones_of_call(zones, n_zones, (p.h, p.w), indices, who)
+    records = np.zeros((3, z.rows), dtype=_ffi.STATS_DTYPE)
+    medians = np.zeros((3, z.rows, 2), dtype=np.float32)
+    nvalid = C.c_int64(-1)
     p_rgba, p_lut = _ffi.ptr3(p.rgbas), _ffi.ptr3(p.luts)
-    made = polys._label_buffer((p.h, p.w)) if polys and polys.want_labels else None
-    found, width = C.c_int64(-1), C.c_int(0)
-    room = regions._outline_room() if regions else None
     try:
-        if regions:
-            table = np.zeros(nz, dtype=_ffi.REGION_DTYPE)
-            made = np.empty((p.h, p.w), dtype=np.int32) if regions.want_labels else None
-            head = (*p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha), int(p.nodata is not None), p.nodata or 0,
-                    C.byref(nvalid), _ffi.ptr(regions.mask), source, regions.mode, regions.threshold, regions.connectivity, regions.min_pixels, nz,
-                    _ffi.ptr(records), _ffi.ptr(medians), _ffi.ptr(table), C.byref(found), _ffi.ptr(made), 0, C.byref(width))
-            if room:
-                _ffi.call("lars_h_process_image_regions_outlines", *head, C.byref(room.c))
-            else:
-                _ffi.call("lars_h_process_image_regions", *head)
-        elif polys:
-            _ffi.call("lars_h_process_image_zones_polygons", *p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha),
-                      int(p.nodata is not None), p.nodata or 0, C.byref(nvalid), *polys._head(), _ffi.ptr(records), _ffi.ptr(medians),
-                      _ffi.ptr(made), made.dtype.itemsize if made is not None else 0)
-        else:
-            _ffi.call("lars_h_process_image_zones", *p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha),
-                      int(p.nodata is not None), p.nodata or 0, C.byref(nvalid), _ffi.ptr(lab), lab.dtype.itemsize, nz, _ffi.ptr(records),
-                      _ffi.ptr(medians), C.byref(bad))
+        _ffi.call(z.picture, *p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha), int(p.nodata is not None), p.nodata or 0,
+                  C.byref(nvalid), *z.picture_args(_ffi.ptr(records), _ffi.ptr(medians)))
     except _ffi.LarsError:
-        if nvalid.value == 0:
-            raise ValueError("process_image: no valid pixel") from None
-        if bad.value > 0:
-            raise _bad_labels(who, bad.value, nz) from None
-        if regions and found.value > nz:
-            raise regions._too_many(who, found.value) from None
-        if room and room.short():
-            raise regions._too_many_vertices(who, room.c.n_vertices) from None
-        raise
+        explained = ValueError("process_image: no valid pixel") if nvalid.value == 0 else z.explain()
+        if explained is None:
+            raise
+        raise explained from None
     result = _picture_result(p, want_hist, want_rgba, False, valid_pixels=nvalid.value)
-    if regions:
-        nz = found.value
-        records, medians = records[:, :nz], medians[:, :nz]
-        made = _label_view(made, (p.h, p.w), width.value) if made is not None else None
-    result["zones"] = {"zone": np.arange(1, nz + 1, dtype=np.int64)}
-    if regions:
-        result["zones"]["regions"] = _region_table(table[:nz])
-        if room:
-            result["zones"].update(room.result(nz))
-    if made is not None:
-        result["zones"]["labels"] = made
+    nz, extra = z.finish()
+    result["zones"] = {"zone": np.arange(1, nz + 1, dtype=np.int64), **extra}
     for t in indices:
-        result["zones"]["pixels"], result["zones"][t] = _figures(records[INDEX_IDS[t]], medians[INDEX_IDS[t]], want_hist)
+        result["zones"]["pixels"], result["zones"][t] = _figures(records[INDEX_IDS[t], :nz], medians[INDEX_IDS[t], :nz], want_hist)
     return result
 
 
