@@ -1150,6 +1150,78 @@ int lars_h_process_image_regions_outlines(const void *img, int64_t h, int64_t w,
                                           lars_region *table /* [capacity] */, int64_t *n_regions, void *labels_out /* may be NULL */,
                                           int label_bytes, int *label_bytes_out /* may be NULL */, lars_outlines *outlines /* may be NULL */);
 
+/* ------------------------------------------------- zone margins (csrc/zone_margin.hip) */
+/* The labels of the zone stages with every zone shrunk inward by a distance: analyze_index per plot (process-images.py:492-513)
+ * without the mixed pixels along a plot's edge, for callers who buffer their plots inward before they take figures.
+ *
+ * The definition.  labels is [h][w], zone_bytes wide (1, 2 or 4), 0 = in no zone.  For a pixel p with L(p) != 0, D2(p) is the smallest
+ * (di)^2 + (dj)^2 between pixel centres to a pixel q of the raster with L(q) != L(p): background, another zone and a label above
+ * nzones all differ.  Outside the raster there are no pixels: the raster's edge shrinks nothing, and a zone that fills the raster has
+ * D2 = infinity.  With margin2 = m2, 0 .. LARS_ZONE_MARGIN2_MAX, the shrunk labels are L'(p) = L(p) if D2(p) > m2, else 0.  A margin
+ * of m pixels is m2 = the largest n with sqrt(n) <= m in float64 (m at most 254, so that a column distance fits a byte).  The number
+ * of zones does not change: a zone that vanishes is an empty zone; one that falls into pieces keeps its label.  Integers only: the
+ * same bytes on every run.
+ *
+ * lars_d_zone_shrink: labels, g_scratch (h * w bytes) and out (a second [h][w] buffer of the same width, never labels itself) on the
+ * device; two launches on the stream. */
+#define LARS_ZONE_MARGIN2_MAX 64516
+int lars_d_zone_shrink(const void *labels, int zone_bytes, int64_t h, int64_t w, int64_t margin2, void *g_scratch, void *out, void *stream);
+/* shrink_zones(zones, margin) of a label raster: host zones[h][w] in, host out[h][w] of the same width out, nzones as in
+ * lars_h_zonal_stats_f32.  Labels outside 0 .. nzones: LARS_ERR_INVALID with their number in *bad_labels (may be NULL; 0 on success,
+ * -1 after any earlier failure), counted before anything is shrunk. */
+int lars_h_shrink_zones(const void *zones, int zone_bytes, int64_t h, int64_t w, int64_t nzones, int64_t margin2, void *out,
+                        int64_t *bad_labels /* may be NULL */);
+/* lars_h_rasterize_zones with the polygons' labels shrunk on the device before they go back: shrink_zones(polygons, margin). */
+int lars_h_rasterize_zones_margin(const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts,
+                                  int64_t npolys, int64_t h, int64_t w, int zone_bytes, void *labels, int64_t margin2);
+/* The calls that make zone figures, with a trailing margin2: the labels are uploaded, rasterised or labelled as in the call of the
+ * same name without _margin, shrunk where they stand, and only then read by the zone stages; labels_out receives the shrunk ones, the
+ * regions' table describes the regions as found.  By definition the records are those of the call without a margin on
+ * lars_h_shrink_zones's raster.  Labels outside 0 .. nzones are counted and reported before anything is shrunk.  margin2 == -1: exactly
+ * the call without _margin, and no kernel more. */
+int lars_h_zonal_stats_margin_f32(const float *x, const void *zones, int zone_bytes, const uint8_t *valid /* may be NULL */, int64_t h, int64_t w,
+                                  int64_t nzones, float threshold, int want_hist, lars_stats *stats /* [nzones] */,
+                                  float *medians /* [nzones][2] */, int64_t *bad_labels, int64_t margin2);
+int lars_h_zonal_stats_polygons_margin_f32(const float *x, const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings,
+                                           const int32_t *poly_starts, int64_t npolys, const uint8_t *valid /* may be NULL */, int64_t h, int64_t w,
+                                           float threshold, int want_hist, lars_stats *stats /* [npolys] */, float *medians /* [npolys][2] */,
+                                           void *labels_out /* may be NULL */, int label_bytes, int64_t margin2);
+int lars_h_zonal_stats_regions_margin_f32(const float *x, const uint8_t *mask /* may be NULL */, int mode, float t, int connectivity,
+                                          int64_t min_pixels, const uint8_t *valid /* may be NULL */, int64_t h, int64_t w, float threshold,
+                                          int want_hist, int64_t capacity, lars_stats *stats /* [capacity] */, float *medians /* [capacity][2] */,
+                                          lars_region *table /* [capacity] */, int64_t *n_regions, void *labels_out /* may be NULL */,
+                                          int label_bytes, int *label_bytes_out /* may be NULL */, int64_t margin2);
+int lars_h_process_image_zones_margin(const void *img, int64_t h, int64_t w, int channels, int dtype,
+                                      int apply_wb, uint32_t index_mask, int want_hist,
+                                      uint8_t *out_wb, float *const out_index[3],
+                                      lars_stats *stats /* [3] */, float *medians /* [3][2] */,
+                                      uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3],
+                                      const uint8_t *valid, int use_alpha, int has_nodata, int nodata, int64_t *valid_pixels,
+                                      const void *zones, int zone_bytes, int64_t nzones,
+                                      lars_stats *zone_stats /* [3][nzones] */, float *zone_medians /* [3][nzones][2] */,
+                                      int64_t *bad_labels, int64_t margin2);
+int lars_h_process_image_zones_polygons_margin(const void *img, int64_t h, int64_t w, int channels, int dtype,
+                                               int apply_wb, uint32_t index_mask, int want_hist,
+                                               uint8_t *out_wb, float *const out_index[3],
+                                               lars_stats *stats /* [3] */, float *medians /* [3][2] */,
+                                               uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3],
+                                               const uint8_t *valid, int use_alpha, int has_nodata, int nodata, int64_t *valid_pixels,
+                                               const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings,
+                                               const int32_t *poly_starts, int64_t npolys,
+                                               lars_stats *zone_stats /* [3][npolys] */, float *zone_medians /* [3][npolys][2] */,
+                                               void *labels_out /* may be NULL */, int label_bytes, int64_t margin2);
+int lars_h_process_image_regions_margin(const void *img, int64_t h, int64_t w, int channels, int dtype,
+                                        int apply_wb, uint32_t index_mask, int want_hist,
+                                        uint8_t *out_wb, float *const out_index[3],
+                                        lars_stats *stats /* [3] */, float *medians /* [3][2] */,
+                                        uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3],
+                                        const uint8_t *valid, int use_alpha, int has_nodata, int nodata, int64_t *valid_pixels,
+                                        const uint8_t *mask /* may be NULL */, int source_index, int mode, float t, int connectivity,
+                                        int64_t min_pixels, int64_t capacity,
+                                        lars_stats *zone_stats /* [3][capacity] */, float *zone_medians /* [3][capacity][2] */,
+                                        lars_region *table /* [capacity] */, int64_t *n_regions, void *labels_out /* may be NULL */,
+                                        int label_bytes, int *label_bytes_out /* may be NULL */, int64_t margin2);
+
 /* ------------------------------------------------------------------ multi-GPU */
 /* One process per GPU.  RCCL (librccl.so) is loaded on first use.  unique_id is
  * LARS_COMM_ID_BYTES bytes produced by lars_comm_unique_id() on rank 0 and

@@ -523,8 +523,19 @@ int lars_h_process_image_zones(const void *img, int64_t h, int64_t w, int channe
                                int has_nodata, int nodata, int64_t *valid_pixels, const void *zones, int zone_bytes, int64_t nzones,
                                lars_stats *zone_stats, float *zone_medians, int64_t *bad_labels)
 {
-    static const char *who = "lars_h_process_image_zones";
-    const ZoneSource src = ZoneSource::raster(h, w, zones, zone_bytes, nzones);
+    return lars_h_process_image_zones_margin(img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut,
+                                             valid, use_alpha, has_nodata, nodata, valid_pixels, zones, zone_bytes, nzones, zone_stats, zone_medians, bad_labels,
+                                             -1);
+}
+
+int lars_h_process_image_zones_margin(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                                      int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                                      uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], const uint8_t *valid, int use_alpha,
+                                      int has_nodata, int nodata, int64_t *valid_pixels, const void *zones, int zone_bytes, int64_t nzones,
+                                      lars_stats *zone_stats, float *zone_medians, int64_t *bad_labels, int64_t margin2)
+{
+    const char *who = margin2 == -1 ? "lars_h_process_image_zones" : "lars_h_process_image_zones_margin";
+    const ZoneSource src = ZoneSource::raster(h, w, zones, zone_bytes, nzones).shrunk_by(margin2);
     ImageJob j;
     LARS_TRY(zones_job(&j, who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut, valid,
                        use_alpha, has_nodata, nodata, valid_pixels, src, {zone_stats, zone_medians, bad_labels}));
@@ -539,11 +550,43 @@ int lars_h_process_image_zones_polygons(const void *img, int64_t h, int64_t w, i
                                         const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts, int64_t npolys,
                                         lars_stats *zone_stats, float *zone_medians, void *labels_out, int label_bytes)
 {
-    static const char *who = "lars_h_process_image_zones_polygons";
-    const ZoneSource src = ZoneSource::of(h, w, ZonePolys{verts, nverts, ring_starts, nrings, poly_starts, npolys, labels_out, label_bytes});
+    return lars_h_process_image_zones_polygons_margin(img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba,
+                                                      cmap_lut, valid, use_alpha, has_nodata, nodata, valid_pixels, verts, nverts, ring_starts, nrings, poly_starts,
+                                                      npolys, zone_stats, zone_medians, labels_out, label_bytes, -1);
+}
+
+int lars_h_process_image_zones_polygons_margin(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                                               int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                                               uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], const uint8_t *valid, int use_alpha,
+                                               int has_nodata, int nodata, int64_t *valid_pixels, const double *verts, int64_t nverts,
+                                               const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts, int64_t npolys,
+                                               lars_stats *zone_stats, float *zone_medians, void *labels_out, int label_bytes, int64_t margin2)
+{
+    const char *who = margin2 == -1 ? "lars_h_process_image_zones_polygons" : "lars_h_process_image_zones_polygons_margin";
+    const ZoneSource src = ZoneSource::of(h, w, ZonePolys{verts, nverts, ring_starts, nrings, poly_starts, npolys, labels_out, label_bytes}).shrunk_by(margin2);
     ImageJob j;
     LARS_TRY(zones_job(&j, who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut, valid,
                        use_alpha, has_nodata, nodata, valid_pixels, src, {zone_stats, zone_medians, nullptr}));
+    LARS_TRY(check_zone_source(who, src, LARS_ZONES_MAX));
+    return run_image(j);
+}
+
+// process_image with regions as its zones: their outlines or a margin as well, never both
+static int process_image_regions(const char *who, const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                                 int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                                 uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], const uint8_t *valid, int use_alpha,
+                                 int has_nodata, int nodata, int64_t *valid_pixels, const uint8_t *mask, int source_index, int mode, float t,
+                                 int connectivity, int64_t min_pixels, int64_t capacity, lars_stats *zone_stats, float *zone_medians,
+                                 lars_region *table, int64_t *n_regions, void *labels_out, int label_bytes, int *label_bytes_out,
+                                 lars_outlines *outlines, int64_t margin2)
+{
+    const ZoneSource src = ZoneSource::of(h, w, ZoneRegions{mask, mask ? 0 : source_index, mode, t, connectivity, min_pixels, capacity, table, n_regions,
+                                                            labels_out, label_bytes, label_bytes_out, outlines}).shrunk_by(margin2);
+    ImageJob j;
+    LARS_TRY(zones_job(&j, who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut, valid,
+                       use_alpha, has_nodata, nodata, valid_pixels, src, {zone_stats, zone_medians, nullptr}));
+    if (!mask && (source_index < 0 || source_index > 2 || !((index_mask >> source_index) & 1u)))
+        return fail(LARS_ERR_INVALID, "%s: source_index %d is not among the indices of index_mask", who, source_index);
     LARS_TRY(check_zone_source(who, src, LARS_ZONES_MAX));
     return run_image(j);
 }
@@ -556,16 +599,23 @@ int lars_h_process_image_regions_outlines(const void *img, int64_t h, int64_t w,
                                           lars_region *table, int64_t *n_regions, void *labels_out, int label_bytes, int *label_bytes_out,
                                           lars_outlines *outlines)
 {
-    const char *who = outlines ? "lars_h_process_image_regions_outlines" : "lars_h_process_image_regions";
-    const ZoneSource src = ZoneSource::of(h, w, ZoneRegions{mask, mask ? 0 : source_index, mode, t, connectivity, min_pixels, capacity, table, n_regions,
-                                                            labels_out, label_bytes, label_bytes_out, outlines});
-    ImageJob j;
-    LARS_TRY(zones_job(&j, who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut, valid,
-                       use_alpha, has_nodata, nodata, valid_pixels, src, {zone_stats, zone_medians, nullptr}));
-    if (!mask && (source_index < 0 || source_index > 2 || !((index_mask >> source_index) & 1u)))
-        return fail(LARS_ERR_INVALID, "%s: source_index %d is not among the indices of index_mask", who, source_index);
-    LARS_TRY(check_zone_source(who, src, LARS_ZONES_MAX));
-    return run_image(j);
+    return process_image_regions(outlines ? "lars_h_process_image_regions_outlines" : "lars_h_process_image_regions", img, h, w, channels, dtype, apply_wb,
+                                 index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut, valid, use_alpha, has_nodata, nodata, valid_pixels,
+                                 mask, source_index, mode, t, connectivity, min_pixels, capacity, zone_stats, zone_medians, table, n_regions, labels_out,
+                                 label_bytes, label_bytes_out, outlines, -1);
+}
+
+int lars_h_process_image_regions_margin(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                                        int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                                        uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], const uint8_t *valid, int use_alpha,
+                                        int has_nodata, int nodata, int64_t *valid_pixels, const uint8_t *mask, int source_index, int mode, float t,
+                                        int connectivity, int64_t min_pixels, int64_t capacity, lars_stats *zone_stats, float *zone_medians,
+                                        lars_region *table, int64_t *n_regions, void *labels_out, int label_bytes, int *label_bytes_out,
+                                        int64_t margin2)
+{
+    return process_image_regions("lars_h_process_image_regions_margin", img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats,
+                                 medians, out_rgba, cmap_lut, valid, use_alpha, has_nodata, nodata, valid_pixels, mask, source_index, mode, t, connectivity,
+                                 min_pixels, capacity, zone_stats, zone_medians, table, n_regions, labels_out, label_bytes, label_bytes_out, nullptr, margin2);
 }
 
 int lars_h_process_image_regions(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,

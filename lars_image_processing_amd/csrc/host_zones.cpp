@@ -2,7 +2,8 @@
 // label_regions, region_outlines and rasterize_zones; process_image_zones and its kin (host_image.cpp) come through host_zones.h.
 // Every call states where its labels come from in one ZoneSource, which is checked once (check_zone_source), sizes the device
 // buffers once (plan_zone_labels, plus plan_zone_stats where statistics follow) and is turned into labels on the device by one step
-// (zone_labels).  run_zones is that step, the four stages of zonal.hip and, where wanted, the outline trace.
+// (zone_labels), which also shrinks them where the source has a margin (zone_margin.hip).  run_zones is that step, the four stages of
+// zonal.hip and, where wanted, the outline trace.
 #include <math.h>
 #include <string.h>
 #include <vector>
@@ -98,8 +99,13 @@ ZoneLabelBufs plan_zone_labels(Carver &c, const ZoneSource &src)
         B.label_scratch = c.take<char>(lars_region_label_scratch_bytes(src.h, src.w));
         if (G.labels_out && G.label_bytes != 4) B.narrow = c.take<char>(npix * 2);     // the narrowest is known once R is: 2 bytes at most
     }
-    if (src.kind == ZoneSource::RASTER) B.labels = c.take<char>(npix * (size_t)src.label_bytes);
-    else B.labels = B.made = c.take<int32_t>(npix);
+    if (src.kind == ZoneSource::RASTER) B.labels = B.raw = c.take<char>(npix * (size_t)src.label_bytes);
+    else B.labels = B.raw = B.made = c.take<int32_t>(npix);
+    if (src.margin2 >= 0) {
+        B.margin_g = c.take<uint8_t>(npix);
+        B.labels = c.take<char>(npix * (size_t)src.zone_bytes());     // shrinking in place would race with the neighbours' reads
+        if (src.kind == ZoneSource::RASTER) B.margin_counts = c.take<uint64_t>((size_t)src.nzones + 2);
+    }
     return B;
 }
 
@@ -118,24 +124,20 @@ ZoneStatBufs plan_zone_stats(Carver &c, size_t npix, int64_t rows, uint32_t mask
 }
 
 // ---- the labels onto the device ----
-// the polygons up, their labels made and, where the caller wants them, back at his width: on the stream
+// the polygons up and their labels made: on the stream
 int raster_zones(const ZoneSource &src, const ZoneLabelBufs &B, hipStream_t s)
 {
     const ZonePolys &P = src.polys;
     LARS_HIP_TRY(hipMemcpyAsync(B.verts, P.verts, 2 * (size_t)P.nverts * sizeof(double), hipMemcpyHostToDevice, s));
     LARS_HIP_TRY(hipMemcpyAsync(B.rings, P.ring_starts, ((size_t)P.nrings + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
     LARS_HIP_TRY(hipMemcpyAsync(B.polys, P.poly_starts, ((size_t)P.npolys + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    LARS_TRY(lars_d_zone_rasterize(B.verts, P.nverts, B.rings, P.nrings, B.polys, P.npolys, src.h, src.w, B.made, B.raster_scratch, s));
-    if (!P.labels_out) return LARS_OK;
-    if (B.narrow) LARS_TRY(lars_d_zone_labels_narrow(B.made, (int64_t)src.npix(), P.label_bytes, B.narrow, s));
-    LARS_HIP_TRY(hipMemcpyAsync(P.labels_out, B.narrow ? B.narrow : B.labels, src.npix() * (size_t)P.label_bytes, hipMemcpyDeviceToHost, s));
-    return LARS_OK;
+    return lars_d_zone_rasterize(B.verts, P.nverts, B.rings, P.nrings, B.polys, P.npolys, src.h, src.w, B.made, B.raster_scratch, s);
 }
 
 // The foreground (uploaded, or the plane against t; never outside valid_dev), its labels and R to the host: the one wait of this step.
-// R above the capacity ends the call; otherwise the table's R rows and, where wanted, the labels follow on the stream.
+// R above the capacity ends the call; otherwise the table's R rows follow on the stream.  *bytes: the width the labels go back in.
 int label_zone_regions(const char *who, const ZoneSource &src, const ZoneLabelBufs &B, const float *plane, const uint8_t *valid_dev, int64_t *nzones,
-                       hipStream_t s)
+                       int *bytes, hipStream_t s)
 {
     const ZoneRegions &G = src.regions;
     const size_t npix = src.npix();
@@ -147,28 +149,55 @@ int label_zone_regions(const char *who, const ZoneSource &src, const ZoneLabelBu
     LARS_HIP_TRY(hipMemcpyAsync(&r, B.count, sizeof r, hipMemcpyDeviceToHost, s));
     LARS_HIP_TRY(hipStreamSynchronize(s));
     *G.n_regions = r;
-    int bytes = G.label_bytes ? G.label_bytes : r <= 255 ? 1 : r <= 65535 ? 2 : 4;
-    if (r < 0 || r > G.capacity || (G.labels_out && ((bytes == 1 && r > 255) || (bytes == 2 && r > 65535))))
+    *bytes = G.label_bytes ? G.label_bytes : r <= 255 ? 1 : r <= 65535 ? 2 : 4;
+    if (r < 0 || r > G.capacity || (G.labels_out && ((*bytes == 1 && r > 255) || (*bytes == 2 && r > 65535))))
         return fail(LARS_ERR_INVALID, "%s: %lld regions; the capacity is %lld%s", who, (long long)r, (long long)G.capacity,
                     r <= G.capacity ? " and the labels are too narrow for them" : "");
     *nzones = r;
     if (r) LARS_HIP_TRY(hipMemcpyAsync(G.table_out, B.table, (size_t)r * sizeof(lars_region), hipMemcpyDeviceToHost, s));
-    if (!G.labels_out) return LARS_OK;
-    if (G.label_bytes_out) *G.label_bytes_out = bytes;
-    if (bytes != 4) LARS_TRY(lars_d_zone_labels_narrow(B.made, (int64_t)npix, bytes, B.narrow, s));
-    LARS_HIP_TRY(hipMemcpyAsync(G.labels_out, bytes != 4 ? B.narrow : B.labels, npix * (size_t)bytes, hipMemcpyDeviceToHost, s));
+    if (G.labels_out && G.label_bytes_out) *G.label_bytes_out = *bytes;
     return LARS_OK;
 }
 
-// Uploaded, rasterised or labelled: afterwards the labels stand in B.labels, src.zone_bytes() wide, and *nzones says how many zones
-// they name.  With regions that is R, which may be 0: no region is a result, not an error.  planes: what a threshold is compared with.
+// The margin (zone_margin.hip): B.raw shrunk into B.labels.  Labels above nzones can only come with an uploaded raster; they are
+// counted where they still stand and end the call as the stages would, which see none afterwards.
+int shrink_zone_labels(const char *who, const ZoneSource &src, const ZoneLabelBufs &B, int64_t *bad_labels, hipStream_t s)
+{
+    if (src.kind == ZoneSource::RASTER) {
+        const size_t nz = (size_t)src.nzones;
+        uint64_t bad = 0;
+        LARS_TRY(lars_d_zone_count(B.raw, src.label_bytes, nullptr, (int64_t)src.npix(), src.nzones, B.margin_counts, B.margin_counts + nz + 1, s));
+        LARS_HIP_TRY(hipMemcpyAsync(&bad, B.margin_counts + nz + 1, sizeof bad, hipMemcpyDeviceToHost, s));
+        LARS_HIP_TRY(hipStreamSynchronize(s));
+        if (bad_labels) *bad_labels = (int64_t)bad;
+        if (bad) return fail(LARS_ERR_INVALID, "%s: %llu labels outside 0 .. %lld", who, (unsigned long long)bad, (long long)src.nzones);
+    }
+    return lars_d_zone_shrink(B.raw, src.zone_bytes(), src.h, src.w, src.margin2, B.margin_g, B.labels, s);
+}
+
+// Uploaded, rasterised or labelled, and shrunk where the source has a margin: afterwards the labels stand in B.labels, src.zone_bytes()
+// wide, and *nzones says how many zones they name; where the caller wants them they are on their way back at his width.  With
+// regions that is R, which may be 0: no region is a result, not an error.  planes: what a threshold is compared with.
 int zone_labels(const char *who, const ZoneSource &src, const ZoneLabelBufs &B, const float *const planes[3], const uint8_t *valid_dev, int64_t *nzones,
-                hipStream_t s)
+                int64_t *bad_labels, hipStream_t s)
 {
     *nzones = src.rows();
-    if (src.kind == ZoneSource::REGIONS) return label_zone_regions(who, src, B, planes ? planes[src.regions.source] : nullptr, valid_dev, nzones, s);
-    if (src.kind == ZoneSource::POLYGONS) return raster_zones(src, B, s);
-    LARS_HIP_TRY(hipMemcpyAsync(B.labels, src.labels, src.npix() * (size_t)src.label_bytes, hipMemcpyHostToDevice, s));
+    void *back = src.raster_out;
+    int bytes = src.label_bytes;
+    if (src.kind == ZoneSource::REGIONS) {
+        LARS_TRY(label_zone_regions(who, src, B, planes ? planes[src.regions.source] : nullptr, valid_dev, nzones, &bytes, s));
+        back = src.regions.labels_out;
+    } else if (src.kind == ZoneSource::POLYGONS) {
+        LARS_TRY(raster_zones(src, B, s));
+        back = src.polys.labels_out, bytes = src.polys.label_bytes;
+    } else {
+        LARS_HIP_TRY(hipMemcpyAsync(B.raw, src.labels, src.npix() * (size_t)src.label_bytes, hipMemcpyHostToDevice, s));
+    }
+    if (src.margin2 >= 0) LARS_TRY(shrink_zone_labels(who, src, B, bad_labels, s));
+    if (!back) return LARS_OK;
+    const bool narrow = bytes != src.zone_bytes();
+    if (narrow) LARS_TRY(lars_d_zone_labels_narrow(static_cast<const int32_t *>(B.labels), (int64_t)src.npix(), bytes, B.narrow, s));
+    LARS_HIP_TRY(hipMemcpyAsync(back, narrow ? B.narrow : B.labels, src.npix() * (size_t)bytes, hipMemcpyDeviceToHost, s));
     return LARS_OK;
 }
 
@@ -282,12 +311,12 @@ int zonal_stats(const char *who, const float *x, const ZoneSource &src, const ui
 }
 
 // The calls that want the labels and no statistics: the labels step, the outlines where the source asks for them, the wait.
-int labels_only(const char *who, const ZoneSource &src, ThreadCtx *c)
+int labels_only(const char *who, const ZoneSource &src, ThreadCtx *c, int64_t *bad_labels = nullptr)
 {
     ZoneLabelBufs B;
     LARS_TRY(ws_plan(c, [&](Carver &d) { B = plan_zone_labels(d, src); }));
     int64_t nzones = 0;
-    LARS_TRY(zone_labels(who, src, B, nullptr, nullptr, &nzones, c->stream));
+    LARS_TRY(zone_labels(who, src, B, nullptr, nullptr, &nzones, bad_labels, c->stream));
     if (src.outlines()) LARS_TRY(trace_zone_outlines(who, src, B, nzones, c->stream));
     LARS_HIP_TRY(hipStreamSynchronize(c->stream));
     return LARS_OK;
@@ -324,6 +353,10 @@ int check_zone_records(const char *who, const ZoneSource &src, const void *stats
 
 int check_zone_source(const char *who, const ZoneSource &src, int64_t most_regions)
 {
+    if (src.margin2 < -1 || src.margin2 > LARS_ZONE_MARGIN2_MAX)
+        return fail(LARS_ERR_INVALID, "%s: margin2 must be 0 to %d, or -1 for no margin, got %lld", who, LARS_ZONE_MARGIN2_MAX, (long long)src.margin2);
+    if (src.margin2 >= 0 && src.outlines())
+        return fail(LARS_ERR_INVALID, "%s: outlines are traced from regions that are connected; a margin may break them apart", who);
     return src.kind == ZoneSource::RASTER     ? check_raster(who, src)
            : src.kind == ZoneSource::POLYGONS ? check_polygons(who, src.polys, src.h, src.w)
                                               : check_regions(who, src.regions, src.h, src.w, most_regions);
@@ -340,7 +373,7 @@ ZoneBufs plan_zones(Carver &c, const ZoneSource &src, uint32_t mask)
 int run_zones(const char *who, const ZoneSource &src, const ZoneBufs &B, const ZonePlanes &in, const ZoneOutputs &out, hipStream_t s)
 {
     int64_t nzones = 0;
-    LARS_TRY(zone_labels(who, src, B.lab, in.plane, in.valid, &nzones, s));
+    LARS_TRY(zone_labels(who, src, B.lab, in.plane, in.valid, &nzones, out.bad_labels, s));
     if (nzones) LARS_TRY(zone_stages(who, src, B, in, out, nzones, s));
     if (src.outlines()) LARS_TRY(trace_zone_outlines(who, src, B.lab, nzones, s));
     return LARS_OK;
@@ -352,19 +385,34 @@ using namespace lars;
 
 extern "C" {
 
+int lars_h_zonal_stats_margin_f32(const float *x, const void *zones, int zone_bytes, const uint8_t *valid, int64_t h, int64_t w, int64_t nzones,
+                                  float threshold, int want_hist, lars_stats *stats, float *medians, int64_t *bad_labels, int64_t margin2)
+{
+    return zonal_stats(margin2 == -1 ? "lars_h_zonal_stats_f32" : "lars_h_zonal_stats_margin_f32", x,
+                       ZoneSource::raster(h, w, zones, zone_bytes, nzones).shrunk_by(margin2), valid, threshold, want_hist, {stats, medians, bad_labels});
+}
+
 int lars_h_zonal_stats_f32(const float *x, const void *zones, int zone_bytes, const uint8_t *valid, int64_t h, int64_t w, int64_t nzones,
                            float threshold, int want_hist, lars_stats *stats, float *medians, int64_t *bad_labels)
 {
-    return zonal_stats("lars_h_zonal_stats_f32", x, ZoneSource::raster(h, w, zones, zone_bytes, nzones), valid, threshold, want_hist,
-                       {stats, medians, bad_labels});
+    return lars_h_zonal_stats_margin_f32(x, zones, zone_bytes, valid, h, w, nzones, threshold, want_hist, stats, medians, bad_labels, -1);
+}
+
+int lars_h_zonal_stats_polygons_margin_f32(const float *x, const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings,
+                                           const int32_t *poly_starts, int64_t npolys, const uint8_t *valid, int64_t h, int64_t w, float threshold,
+                                           int want_hist, lars_stats *stats, float *medians, void *labels_out, int label_bytes, int64_t margin2)
+{
+    const ZonePolys P = {verts, nverts, ring_starts, nrings, poly_starts, npolys, labels_out, label_bytes};
+    return zonal_stats(margin2 == -1 ? "lars_h_zonal_stats_polygons_f32" : "lars_h_zonal_stats_polygons_margin_f32", x, ZoneSource::of(h, w, P).shrunk_by(margin2),
+                       valid, threshold, want_hist, {stats, medians, nullptr});
 }
 
 int lars_h_zonal_stats_polygons_f32(const float *x, const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings,
                                     const int32_t *poly_starts, int64_t npolys, const uint8_t *valid, int64_t h, int64_t w, float threshold,
                                     int want_hist, lars_stats *stats, float *medians, void *labels_out, int label_bytes)
 {
-    const ZonePolys P = {verts, nverts, ring_starts, nrings, poly_starts, npolys, labels_out, label_bytes};
-    return zonal_stats("lars_h_zonal_stats_polygons_f32", x, ZoneSource::of(h, w, P), valid, threshold, want_hist, {stats, medians, nullptr});
+    return lars_h_zonal_stats_polygons_margin_f32(x, verts, nverts, ring_starts, nrings, poly_starts, npolys, valid, h, w, threshold, want_hist, stats, medians,
+                                                  labels_out, label_bytes, -1);
 }
 
 int lars_h_zonal_stats_regions_outlines_f32(const float *x, const uint8_t *mask, int mode, float t, int connectivity, int64_t min_pixels,
@@ -375,6 +423,16 @@ int lars_h_zonal_stats_regions_outlines_f32(const float *x, const uint8_t *mask,
     const ZoneRegions G = {mask, 0, mode, t, connectivity, min_pixels, capacity, table, n_regions, labels_out, label_bytes, label_bytes_out, outlines};
     return zonal_stats(outlines ? "lars_h_zonal_stats_regions_outlines_f32" : "lars_h_zonal_stats_regions_f32", x, ZoneSource::of(h, w, G), valid, threshold,
                        want_hist, {stats, medians, nullptr});
+}
+
+int lars_h_zonal_stats_regions_margin_f32(const float *x, const uint8_t *mask, int mode, float t, int connectivity, int64_t min_pixels,
+                                          const uint8_t *valid, int64_t h, int64_t w, float threshold, int want_hist, int64_t capacity, lars_stats *stats,
+                                          float *medians, lars_region *table, int64_t *n_regions, void *labels_out, int label_bytes, int *label_bytes_out,
+                                          int64_t margin2)
+{
+    const ZoneRegions G = {mask, 0, mode, t, connectivity, min_pixels, capacity, table, n_regions, labels_out, label_bytes, label_bytes_out, nullptr};
+    return zonal_stats("lars_h_zonal_stats_regions_margin_f32", x, ZoneSource::of(h, w, G).shrunk_by(margin2), valid, threshold, want_hist,
+                       {stats, medians, nullptr});
 }
 
 int lars_h_zonal_stats_regions_f32(const float *x, const uint8_t *mask, int mode, float t, int connectivity, int64_t min_pixels,
@@ -400,16 +458,37 @@ int lars_h_region_outlines(const uint8_t *mask, int64_t h, int64_t w, int connec
     return label_regions_call(who, mask, h, w, connectivity, min_pixels, label_bytes, labels, label_bytes_out, table, capacity, n_regions, outlines);
 }
 
-int lars_h_rasterize_zones(const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts,
-                           int64_t npolys, int64_t h, int64_t w, int zone_bytes, void *labels)
+int lars_h_rasterize_zones_margin(const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts,
+                                  int64_t npolys, int64_t h, int64_t w, int zone_bytes, void *labels, int64_t margin2)
 {
-    static const char *who = "lars_h_rasterize_zones";
+    const char *who = margin2 == -1 ? "lars_h_rasterize_zones" : "lars_h_rasterize_zones_margin";
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     if (!labels) return fail(LARS_ERR_INVALID, "%s: labels == NULL", who);
-    const ZoneSource src = ZoneSource::of(h, w, ZonePolys{verts, nverts, ring_starts, nrings, poly_starts, npolys, labels, zone_bytes});
+    const ZoneSource src = ZoneSource::of(h, w, ZonePolys{verts, nverts, ring_starts, nrings, poly_starts, npolys, labels, zone_bytes}).shrunk_by(margin2);
     LARS_TRY(check_zone_source(who, src, LARS_ZONES_MAX));
     return labels_only(who, src, c);
+}
+
+int lars_h_rasterize_zones(const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts,
+                           int64_t npolys, int64_t h, int64_t w, int zone_bytes, void *labels)
+{
+    return lars_h_rasterize_zones_margin(verts, nverts, ring_starts, nrings, poly_starts, npolys, h, w, zone_bytes, labels, -1);
+}
+
+int lars_h_shrink_zones(const void *zones, int zone_bytes, int64_t h, int64_t w, int64_t nzones, int64_t margin2, void *out, int64_t *bad_labels)
+{
+    static const char *who = "lars_h_shrink_zones";
+    if (bad_labels) *bad_labels = -1;
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!zones || !out || h <= 0 || w <= 0) return fail(LARS_ERR_INVALID, "%s: zones and out must be non-empty [h][w] label rasters", who);
+    if (margin2 < 0) return fail(LARS_ERR_INVALID, "%s: margin2 must be 0 to %d, got %lld", who, LARS_ZONE_MARGIN2_MAX, (long long)margin2);
+    ZoneSource src = ZoneSource::raster(h, w, zones, zone_bytes, nzones).shrunk_by(margin2);
+    src.raster_out = out;
+    LARS_TRY(check_zone_source(who, src, LARS_ZONES_MAX));
+    if (!aligned_to(zones, (uintptr_t)zone_bytes) || !aligned_to(out, (uintptr_t)zone_bytes)) return fail(LARS_ERR_INVALID, "%s: the labels are not aligned", who);
+    return labels_only(who, src, c, bad_labels);
 }
 
 }  // extern "C"

@@ -28,13 +28,16 @@ struct ZoneRegions {
 };
 
 // Where the labels of a call come from: exactly one of an uploaded raster, the rasteriser (zone_raster.hip) and the labeller
-// (regions.hip).
+// (regions.hip).  With a margin (zone_margin.hip) the labels are shrunk on the device before anything reads them: the stages and
+// every labels_out see the shrunk ones.
 struct ZoneSource {
     enum Kind { RASTER, POLYGONS, REGIONS } kind;
     int64_t h, w;
     const void *labels; int label_bytes; int64_t nzones;         // RASTER: host [h][w] labels 0 .. nzones, label_bytes wide
     ZonePolys polys;                                              // POLYGONS
     ZoneRegions regions;                                          // REGIONS
+    int64_t margin2 = -1;                                         // the squared margin 0 .. LARS_ZONE_MARGIN2_MAX, or -1: none
+    void *raster_out = nullptr;                                   // RASTER: host [h][w] labels back at label_bytes, or null
 
     static ZoneSource raster(int64_t h, int64_t w, const void *labels, int label_bytes, int64_t nzones)
     {
@@ -51,6 +54,12 @@ struct ZoneSource {
         ZoneSource s = {REGIONS, h, w, nullptr, 0, 0, {}, G};
         return s;
     }
+    ZoneSource shrunk_by(int64_t m2) const
+    {
+        ZoneSource s = *this;
+        s.margin2 = m2;
+        return s;
+    }
     size_t npix() const { return (size_t)h * (size_t)w; }
     // the rows of the caller's per-zone arrays, which is also the stride of their three parts
     int64_t rows() const { return kind == RASTER ? nzones : kind == POLYGONS ? polys.npolys : regions.capacity; }
@@ -61,8 +70,11 @@ struct ZoneSource {
 
 // The device buffers of a source: what makes the labels, and the labels.
 struct ZoneLabelBufs {
-    void *labels;                  // [npix] labels, zone_bytes() wide: what the zone stages read
-    int32_t *made;                 // ... the same buffer where the device wrote them, null for an uploaded raster
+    void *labels;                  // [npix] labels, zone_bytes() wide: what the zone stages read and what goes back to the caller
+    void *raw;                     // ... as uploaded or made: the same buffer without a margin, the one the margin shrinks with it
+    int32_t *made;                 // ... raw where the device wrote it, null for an uploaded raster
+    uint8_t *margin_g;             // [npix] the column distances of the margin (zone_margin.hip), where there is one
+    uint64_t *margin_counts;       // RASTER with a margin: [nzones + 2], the count of bad labels before they can be shrunk away
     void *narrow;                  // the labels at the width the caller wants them back in, where that is not 4
     double *verts;                 // POLYGONS
     int32_t *rings, *polys;

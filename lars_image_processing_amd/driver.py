@@ -79,9 +79,9 @@ def _mask_argument(mask_kw):
     return (mask_kw,) if mask_kw else ()
 
 
-def _zones_argument(zones, zones_transform=None, regions=None, regions_geojson=False):
-    """``_process_image``'s ``zones`` (and ``zones_transform``, ``regions``, ``regions_geojson``) keywords, handed over only where they are
-    named: without them the call is the one it always was."""
+def _zones_argument(zones, zones_transform=None, regions=None, regions_geojson=False, zone_margin=None):
+    """``_process_image``'s ``zones`` (and ``zones_transform``, ``regions``, ``regions_geojson``, ``zone_margin``) keywords, handed over only
+    where they are named: without them the call is the one it always was."""
     kw = {} if zones is None else {"zones": zones}
     if zones_transform is not None:
         kw["zones_transform"] = zones_transform
@@ -91,6 +91,12 @@ def _zones_argument(zones, zones_transform=None, regions=None, regions_geojson=F
         if regions is None:
             raise ValueError("regions_geojson writes the outlines of the regions: it goes with regions")
         kw["regions_geojson"] = True
+    if zone_margin is not None:
+        if zones is None and regions is None:
+            raise ValueError("zone_margin shrinks the zones of the picture: it goes with zones or regions")
+        if regions_geojson:
+            raise ValueError("zone_margin and regions_geojson do not go together: outlines are traced from regions as found")
+        kw["zone_margin"] = zone_margin
     return kw
 
 
@@ -189,7 +195,8 @@ def _matching(png_encoder, tiff_encoder):
 
 def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png",
                   png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow", tiff_encoder="pillow",
-                  index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None, regions=None, regions_geojson=False):
+                  index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None, regions=None, regions_geojson=False,
+                  zone_margin=None):
     """One file: same outputs as backend-process.py:49-73.  Returns the statistics dicts.
     ``full_depth=True`` reads three-sample 16-bit TIFFs at their full depth (``tiffio.read_image``; Pillow, hence the
     reference, keeps their high bytes only).  ``lut_format="tiff"`` writes the colormap images as
@@ -226,7 +233,10 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     area, box and centroid added.  ``index`` must be among the requested indices; not together with ``zones``.
     ``regions_geojson=True`` (with ``regions``) also writes ``<name>_regions.geojson``: the outline of every region, traced on the
     device (``zones.region_outlines``'s rings), one feature per region with its CSV figures as properties, in pixel coordinates or
-    through ``zones_transform`` in world coordinates."""
+    through ``zones_transform`` in world coordinates.
+    ``zone_margin=PX`` (with ``zones`` or ``regions``, not with ``regions_geojson``) shrinks every zone inward by that many pixels on
+    the device before its figures are taken (``zones.shrink_zones``'s rule); the CSV has the same columns, the regions' area, box and
+    centroid stay those of the regions as found."""
     if lut_format not in ("png", "png8", "tiff"):
         raise ValueError(f"lut_format must be 'png', 'png8' or 'tiff', got {lut_format!r}")
     _check_png_encoder(png_encoder)
@@ -239,11 +249,11 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     with block:
         return _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder,
                               tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw),
-                              **_zones_argument(zones, zones_transform, regions, regions_geojson))
+                              **_zones_argument(zones, zones_transform, regions, regions_geojson, zone_margin))
 
 
 def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder, tiff_decoder,
-                   tiff_encoder, index_tiff, mask_kw=None, zones=None, zones_transform=None, regions=None, regions_geojson=False):
+                   tiff_encoder, index_tiff, mask_kw=None, zones=None, zones_transform=None, regions=None, regions_geojson=False, zone_margin=None):
     """``process_image`` behind its checks, for ``"pillow"``, ``"device"`` and ``"device+deflate"``."""
     from PIL import Image
     from .tiffio import read_image
@@ -266,6 +276,9 @@ def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_
         from .zones import process_image_zones
         labels = zones if regions is not None else _read_zones(zones, zones_transform, arr.shape[:2], image_path.name)
         output_dir.mkdir(parents=True, exist_ok=True)
+        if zone_margin is not None:
+            from .zones import Shrunk
+            labels = Shrunk(labels, zone_margin)
         zoned = process_image_zones(arr, labels, **mask_kw, indices=indices, white_balance=True, want_arrays=False)
         _write_zones_csv(output_dir / f"{name}_zones.csv", zoned, indices)
         if regions_geojson:
@@ -346,16 +359,16 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
                   process_ndwi=True, workers=4, verbose=True, full_depth=False, lut_format="png", rank=0, world=1,
                   device=None, png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow",
                   tiff_encoder="pillow", index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None, regions=None,
-                  regions_geojson=False):
+                  regions_geojson=False, zone_margin=None):
     """backend-process.py:75-97 with its module constants as arguments.  Returns ``{file name: stats | error}``.
     ``rank`` / ``world``: one process per GPU, each takes its block of the sorted file list (``files_of_rank``); the output
     directories are shared, the file names distinct.  ``device``: the GPU ordinal every worker thread binds (the library's
     context is per thread and defaults to device 0); None leaves the threads' binding alone.  ``png_encoder``,
     ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``, ``tiff_encoder``, ``index_tiff``, ``nodata``, ``alpha_mask``, ``zones`` (one label
-    raster, or one file of polygons with its ``zones_transform``, for every file of the directory), ``regions``, ``regions_geojson``: see
-    ``process_image``."""
+    raster, or one file of polygons with its ``zones_transform``, for every file of the directory), ``regions``, ``regions_geojson``,
+    ``zone_margin``: see ``process_image``."""
     mask_kw = _mask_options(nodata, alpha_mask, lut_format)
-    zones_kw = _zones_argument(zones, zones_transform, regions, regions_geojson)
+    zones_kw = _zones_argument(zones, zones_transform, regions, regions_geojson, zone_margin)
     _check_tiff_encoder(tiff_encoder)
     _check_png_encoder(png_encoder)
     _check_png_decoder(png_decoder)
@@ -493,10 +506,20 @@ def main(argv=None):
     ap.add_argument("--regions-geojson", action="store_true",
                     help="with --regions: also write <name>_regions.geojson, the outline of every region traced on the GPU, one feature per "
                          "region with its CSV figures as properties; --zones-transform puts it in world coordinates")
+    ap.add_argument("--zone-margin", default=None, type=float, metavar="PX",
+                    help="with --zones or --regions: shrink every zone inward by PX pixels (0 to 254) on the GPU before its figures are "
+                         "taken, so that the mixed pixels along a plot's edge stay out; the CSV columns are unchanged.  Not with "
+                         "--regions-geojson")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
     if args.regions_geojson and args.regions is None:
         ap.error("--regions-geojson writes the outlines of the regions: it goes with --regions")
+    if args.zone_margin is not None and args.zones is None and args.regions is None:
+        ap.error("--zone-margin shrinks the zones of the picture: it goes with --zones or --regions")
+    if args.zone_margin is not None and args.regions_geojson:
+        ap.error("--zone-margin and --regions-geojson do not go together: outlines are traced from regions as found")
+    if args.zone_margin is not None and not 0 <= args.zone_margin <= 254:
+        ap.error(f"--zone-margin must be 0 to 254 pixels, got {args.zone_margin}")
     from .dist import env_rank_world
     rank, local_rank, world = env_rank_world()
     res = batch_process(args.input_dir, args.output_dir, args.wb, args.ndvi, args.gndvi, args.ndwi, args.workers,
@@ -504,7 +527,7 @@ def main(argv=None):
                         device=local_rank if world > 1 else None, png_encoder=args.png_encoder,
                         png_decoder=args.png_decoder, jpeg_decoder=args.jpeg_decoder, tiff_decoder=args.tiff_decoder,
                         tiff_encoder=args.tiff_encoder, index_tiff=args.index_tiff, nodata=args.nodata, alpha_mask=args.alpha_mask,
-                        **_zones_argument(args.zones, args.zones_transform, args.regions, args.regions_geojson))
+                        **_zones_argument(args.zones, args.zones_transform, args.regions, args.regions_geojson, args.zone_margin))
     failed = {k: str(v) for k, v in res.items() if isinstance(v, Exception)}
     print(json.dumps({"rank": rank, "world": world, "files": len(res), "failed": failed}))
     return 1 if failed else 0

@@ -15,11 +15,16 @@ And where nobody drew outlines, the picture's own connected regions serve (DESIG
 
 The regions leave as shapes too (DESIGN.md "Region outlines", csrc/outlines.hip): ``region_outlines``, or ``Regions(...,
 want_outlines=True)``, traces the ring of pixel borders around every region and every hole on the device, as ``Polygons`` that
-``rasterize_zones`` turns back into the same labels; ``polygons_to_geojson`` writes them, ``to_world`` applies a geotransform."""
+``rasterize_zones`` turns back into the same labels; ``polygons_to_geojson`` writes them, ``to_world`` applies a geotransform.
+
+The mixed pixels along a plot's edge stay out with a margin (DESIGN.md "Zone margins", csrc/zone_margin.hip): ``Shrunk(zones,
+margin)`` where ``zones`` is wanted shrinks every zone inward by that many pixels on the device before ``zonal_statistics`` and
+``process_image_zones`` take their figures, whichever of the three kinds made the labels; ``shrink_zones`` returns such labels."""
 from __future__ import annotations
 
 import ctypes as C
 import json
+import math
 import os
 
 import numpy as np
@@ -33,6 +38,7 @@ ZONES_MAX = 65535
 VERTICES_MAX = 1 << 24
 COORDINATE_MAX = 1e9
 OUTLINE_PIXELS_MAX = 1 << 29
+MARGIN_MAX = 254
 _FIGURES = ("mean", "median", "min", "max", "coverage")
 
 
@@ -67,6 +73,63 @@ def _labels(zones, shape, n_zones, who):
             raise ValueError(f"{who}: {above} pixels have a label outside 0 .. {n_zones}")
         z = z.astype(np.int32)
     return np.ascontiguousarray(z), n_zones
+
+
+def _margin2(margin, who):
+    """A margin in pixels -> the integer the device compares squared distances with: the largest ``n`` with float64
+    ``sqrt(n) <= margin``.  Every check of a margin, on the host."""
+    if isinstance(margin, (bool, np.bool_)) or not isinstance(margin, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{who}: margin must be a number of pixels (got {type(margin).__name__})")
+    m = float(margin)
+    if not math.isfinite(m):
+        raise ValueError(f"{who}: margin must be finite, got {margin!r}")
+    if not 0 <= m <= MARGIN_MAX:
+        raise ValueError(f"{who}: margin must be 0 to {MARGIN_MAX} pixels, got {margin!r}")
+    n = int(math.floor(m * m))
+    while n > 0 and math.sqrt(n) > m:                              # m * m rounded up past an integer
+        n -= 1
+    while math.sqrt(n + 1) <= m:
+        n += 1
+    return n
+
+
+class Shrunk:
+    """Zones without their edge pixels: ``Shrunk(zones, margin)``, handed to ``zonal_statistics`` or ``process_image_zones`` where
+    ``zones`` is wanted (DESIGN.md "Zone margins", csrc/zone_margin.hip).
+
+    ``zones`` is any of the three kinds -- a label raster, polygons / ``Polygons``, ``Regions`` -- and ``margin`` the pixels (0 to 254)
+    every zone is shrunk inward by on the device before its figures are taken, as ``shrink_zones`` does it: the figures are those of
+    the same call on ``shrink_zones``'s raster, labels that come back are the shrunk ones, the regions' table describes the regions as
+    found.  A margin of None or 0 is no margin: the call is the one on ``zones`` itself.  ``Regions(want_outlines=True)`` is refused:
+    outlines are traced from regions that are connected.  Every check runs here, on the host."""
+
+    def __init__(self, zones, margin):
+        who = "Shrunk"
+        if isinstance(zones, Shrunk):
+            raise TypeError(f"{who}: these zones are shrunk already: give one margin")
+        self.zones, self.margin = zones, margin
+        self.margin2 = None
+        if margin is None:
+            return
+        m2 = _margin2(margin, who)
+        if margin == 0:
+            return
+        if isinstance(zones, Regions) and zones.want_outlines:
+            raise ValueError(f"{who}: Regions(want_outlines=True) cannot be combined with a margin: outlines are traced from regions that "
+                             f"are connected, and a margin may break them apart")
+        self.margin2 = m2
+
+
+def _unshrunk(zones):
+    """``zones`` of a call -> (the zones themselves, margin2 or None)."""
+    return (zones.zones, zones.margin2) if isinstance(zones, Shrunk) else (zones, None)
+
+
+def _margin_entry(name, args, margin2):
+    """The entry point ``name`` and its arguments, or with a margin its ``_margin`` variant, which takes ``margin2`` last."""
+    if margin2 is None:
+        return name, args
+    return (name[:-4] + "_margin_f32" if name.endswith("_f32") else name + "_margin"), (*args, margin2)
 
 
 def _geotransform(points, transform, who):
@@ -494,6 +557,53 @@ def rasterize_zones(polygons, shape, transform=None):
     return labels
 
 
+def shrink_zones(zones, margin, shape=None, transform=None, n_zones=None):
+    """The ``[H, W]`` label raster of ``zones`` with every zone shrunk inward by ``margin`` pixels, made on the device (DESIGN.md "Zone
+    margins", csrc/zone_margin.hip): what ``zonal_statistics`` / ``process_image_zones`` take their figures from when they are handed
+    ``Shrunk(zones, margin)``.
+
+    A pixel keeps its label iff every pixel of the raster with another label -- background, another zone -- is further than
+    ``margin`` from it, centre to centre; otherwise it becomes 0.  Outside the raster there are no pixels: the raster's edge shrinks
+    nothing.  ``margin`` is a number of pixels, 0 to 254: below 1 nothing goes, 1 takes the 4-connected border layer, ``sqrt(2)`` the
+    8-connected one.  A zone may vanish or fall into pieces that keep its label; Z does not change.  ``zones``: a label raster as
+    ``zonal_statistics`` takes it (``shape`` must not be given; the result has its dtype; ``n_zones`` as there), or polygons as
+    ``rasterize_zones`` takes them with ``shape`` and ``transform`` (the result has its dtype; the labels never cross PCIe before
+    they are shrunk).  Integer arithmetic on the device: the same bytes on every run."""
+    who = "shrink_zones"
+    m2 = _margin2(margin, who)
+    if isinstance(zones, (Regions, Shrunk)):
+        raise TypeError(f"{who}: zones must be a label raster or polygons, got {type(zones).__name__}")
+    raster_like = isinstance(zones, np.ndarray) and zones.dtype.kind in "uib"
+    if transform is not None and not raster_like:
+        if n_zones is not None:
+            raise ValueError(f"{who}: n_zones cannot be given with polygons: Z = len(polygons)")
+        source = Polygons(zones, transform, who=who)
+    else:
+        source = _zone_source(zones, n_zones, who)
+    if source is None:
+        if shape is not None or transform is not None:
+            raise ValueError(f"{who}: shape and transform belong to polygons; a label raster has its own shape")
+        given = np.asarray(zones)
+        if given.ndim != 2:
+            raise ValueError(f"{who}: zones must be an [H, W] array of labels, got shape {given.shape}")
+        lab, rows = _labels(given, given.shape, n_zones, who)
+        out, bad = np.empty_like(lab), C.c_int64(-1)
+        h, w = lab.shape
+        try:
+            _ffi.call("lars_h_shrink_zones", _ffi.ptr(lab), lab.dtype.itemsize, h, w, rows, m2, _ffi.ptr(out), C.byref(bad))
+        except _ffi.LarsError:
+            if bad.value > 0:
+                raise ValueError(f"{who}: {bad.value} pixels have a label outside 0 .. {rows}") from None
+            raise
+        return out if out.dtype == given.dtype else out.astype(given.dtype)
+    if shape is None:
+        raise ValueError(f"{who}: shape is required with polygons: (H, W) of the raster")
+    h, w = _raster_shape(shape, who)
+    labels = source._label_buffer((h, w))
+    _ffi.call("lars_h_rasterize_zones_margin", *source._head(), h, w, labels.dtype.itemsize, _ffi.ptr(labels), m2)
+    return labels
+
+
 def _geometry_rings(geom, where):
     kind = geom.get("type") if isinstance(geom, dict) else None
     if kind == "Polygon":
@@ -706,10 +816,12 @@ def zonal_statistics(index_array, zones, index_type, valid=None, n_zones=None, w
     compared in float32.  ``valid``: an ``[H, W]`` bool or integer mask (nonzero = counts) or None.  ``n_zones=None`` takes the
     largest label.  A zone without pixels has ``pixels`` 0, NaN figures and an empty histogram; a zone that holds a NaN has NaN
     mean / median / min / max.  A label below 0 or above ``n_zones`` raises ``ValueError`` with the number of such pixels.
+    ``zones`` may be ``Shrunk(zones, margin)``: every zone is then shrunk inward by ``margin`` pixels before its figures are taken.
     Everything but ``mean`` is bit-reproducible; the mean's double sum follows the order the device placed the values in."""
     who = "zonal_statistics"
     if index_type not in INDEX_IDS:
         raise ValueError(f"{who}: Unknown index type: {index_type}")
+    zones, margin2 = _unshrunk(zones)
     x = np.asarray(index_array)
     if x.dtype != np.float32:
         raise TypeError(f"{who}: index_array must be float32 (got {x.dtype})")
@@ -725,8 +837,9 @@ def zonal_statistics(index_array, zones, index_type, valid=None, n_zones=None, w
     records = np.zeros(z.rows, dtype=_ffi.STATS_DTYPE)
     medians = np.zeros((z.rows, 2), dtype=np.float32)
     try:
-        _ffi.call(z.plane, *z.plane_args(_ffi.ptr(x), _ffi.ptr(valid_arr), h, w, np.float32(threshold), int(bool(want_hist)), _ffi.ptr(records),
-                                         _ffi.ptr(medians)))
+        name, args = _margin_entry(z.plane, z.plane_args(_ffi.ptr(x), _ffi.ptr(valid_arr), h, w, np.float32(threshold), int(bool(want_hist)),
+                                                         _ffi.ptr(records), _ffi.ptr(medians)), margin2)
+        _ffi.call(name, *args)
     except _ffi.LarsError:
         explained = z.explain()
         if explained is None:
@@ -745,8 +858,10 @@ def process_image_zones(img_array, zones, valid=None, nodata=None, n_zones=None,
     The picture crosses PCIe once, the white balance is taken over the whole valid picture -- zones do not change which pixels its
     percentiles see -- and one pass sorts every valid pixel's index value into its zone.  ``corrected``, the planes, ``rgba``, the
     picture-level statistics and ``valid_pixels`` are exactly ``process_image_masked``'s with the same ``valid`` / ``nodata``; the
-    zone figures are ``zonal_statistics``'s of each plane under the derived mask.  At least one index must be asked for."""
+    zone figures are ``zonal_statistics``'s of each plane under the derived mask, ``Shrunk(zones, margin)`` as there.  At least one
+    index must be asked for."""
     who = "process_image_zones"
+    zones, margin2 = _unshrunk(zones)
     p = _picture(who, who, img_array, list(indices), white_balance, want_arrays, bool(want_hist), want_rgba, False, valid, nodata,
                  need_index="zone statistics need at least one index")
     indices = p.indices
@@ -756,8 +871,9 @@ def process_image_zones(img_array, zones, valid=None, nodata=None, n_zones=None,
     nvalid = C.c_int64(-1)
     p_rgba, p_lut = _ffi.ptr3(p.rgbas), _ffi.ptr3(p.luts)
     try:
-        _ffi.call(z.picture, *p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha), int(p.nodata is not None), p.nodata or 0,
-                  C.byref(nvalid), *z.picture_args(_ffi.ptr(records), _ffi.ptr(medians)))
+        name, args = _margin_entry(z.picture, (*p.head, C.byref(p_rgba), C.byref(p_lut), _ffi.ptr(p.valid), int(p.use_alpha), int(p.nodata is not None),
+                                               p.nodata or 0, C.byref(nvalid), *z.picture_args(_ffi.ptr(records), _ffi.ptr(medians))), margin2)
+        _ffi.call(name, *args)
     except _ffi.LarsError:
         explained = ValueError("process_image: no valid pixel") if nvalid.value == 0 else z.explain()
         if explained is None:
