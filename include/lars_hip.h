@@ -1222,6 +1222,83 @@ int lars_h_process_image_regions_margin(const void *img, int64_t h, int64_t w, i
                                         lars_region *table /* [capacity] */, int64_t *n_regions, void *labels_out /* may be NULL */,
                                         int label_bytes, int *label_bytes_out /* may be NULL */, int64_t margin2);
 
+/* ------------------------------------------------- simplified outlines (csrc/outline_simplify.hip) */
+/* The rings of region outlines with fewer vertices: Douglas-Peucker with a tolerance, on the device, before the vertices cross PCIe --
+ * what every vectoriser pairs with polygonising (GDAL polygonize's simplify, shapely, QGIS).
+ *
+ * The definition.  The input is the ring table and the vertices as lars_d_region_outline writes them: rows sorted by (label, key),
+ * verts int32 (row, col).  Coordinates are 0 .. 32767 (the raster's sides are at most 32767), so every product below fits 64 bits.
+ * tq is the tolerance in sixteenths of a pixel, 1 .. LARS_SIMPLIFY_TQ_MAX: floor(tolerance * 16 + 0.5) for a tolerance of 0 to 254
+ * pixels; a tolerance with tq == 0 is no simplification and never reaches these entries' kernels.  For a chord from a to b and a
+ * vertex p let ab = b - a, ap = p - a, len2 = |ab|^2.  If len2 == 0 then m = |ap|^2 and p is far when 256 * m > tq^2.  Otherwise let
+ * dot = ap . ab; m = |ap|^2 * len2 if dot <= 0, m = |bp|^2 * len2 if dot >= len2, m = cross(ab, ap)^2 in all other cases: the squared
+ * distance to the segment, not to the line, times len2; p is far when 256 * m > tq^2 * len2, which for an integer m is
+ * m > (tq^2 * len2) >> 8 (m < 2^62, tq^2 * len2 < 2^56).  A ring of n vertices is the chain v[0] .. v[n] with v[n] = v[0], v[0] the
+ * vertex the tracer wrote first.  Both ends are kept.  For a stretch (a, b) with b - a >= 2 take the k in (a, b) with the largest m,
+ * on ties the smallest k; if that vertex is far, keep it and treat (a, k) and (k, b) the same way, otherwise the stretch is done.  The
+ * first stretch has a = b in position, as stretches between the pinch points of connectivity 8 can: both take the len2 == 0 rule.
+ * Collapse: a ring stays as given, with all its vertices, when its result would have fewer than 3 vertices, or when the doubled area
+ * of the result is 0 or has the other sign than the ring's own shoelace sum.  The rings, their order, label and key never change;
+ * start, count and area2 describe the vertices written, area2 being their shoelace sum over (x, y) = (col, row).  Nothing disappears.
+ * Every vertex given lies within the tolerance of the ring written.  Integers only: the same bytes on every run.
+ *
+ * lars_d_outline_simplify: rings[ring_capacity], verts[vert_capacity][2] and counts_dev[3] (edges, rings, vertices: the tracer's, of
+ * which the last two are read; a count above its capacity counts as 0) on the device; rings_out[ring_capacity],
+ * verts_out[vert_capacity_out][2] and counts_out_dev[3] (int64: rings, vertices written, rings that stay as given) too, apart from
+ * what is given.  The counts are written whatever vert_capacity_out is; vertices below it are written and nothing beyond.  h and w,
+ * 1 .. 32767: coordinates are clamped to 0 .. h and 0 .. w.  A row whose start or count leaves the vertex array is a ring without
+ * vertices: damaged rings give wrong rings, never an access outside the buffers.  scratch:
+ * lars_outline_simplify_scratch_bytes(ring_capacity, vert_capacity) bytes (0 for arguments outside the rules: capacities 0 to 2^31 - 1),
+ * 256-byte aligned: 29 bytes a vertex of vert_capacity and 58 bytes a ring of ring_capacity, and a little.  The recursion runs level
+ * by level, three launches a round over all vertices; the number of rounds is the depth of the deepest ring, which is not known before
+ * the run: the call WAITS for the stream once to read the longest ring's count, then enqueues eight rounds at a time and waits again
+ * to read 32 bytes of status (the splits of the batch among them; 0 ends the rounds), so unlike the other
+ * lars_d_ entries it returns only once the rounds are done (the last launches are still on the stream).  *rounds_out (host, may be
+ * NULL): the rounds in which a stretch was split.  A ring of n vertices splits in its first n - 1 rounds at most: no round beyond the
+ * longest ring's vertex count is enqueued, and a split in the last one allowed is LARS_ERR_HIP.  No workgroup waits
+ * for another, and every index read from memory is range-checked before it is followed. */
+#define LARS_SIMPLIFY_TQ_MAX 4064
+#define LARS_SIMPLIFY_SIDE_MAX 32767
+size_t lars_outline_simplify_scratch_bytes(int64_t ring_capacity, int64_t vert_capacity);
+int lars_d_outline_simplify(const lars_outline_ring *rings /* [ring_capacity] */, int64_t ring_capacity, const int32_t *verts /* [vert_capacity][2] */,
+                            int64_t vert_capacity, const int64_t *counts_dev /* [3] */, int64_t tq, int64_t h, int64_t w,
+                            lars_outline_ring *rings_out /* [ring_capacity] */, int32_t *verts_out /* [vert_capacity_out][2] */,
+                            int64_t vert_capacity_out, int64_t *counts_out_dev /* [3] */, void *scratch, int64_t *rounds_out /* may be NULL */,
+                            void *stream);
+/* simplify_outlines(result, tolerance): the same for host arrays, for outlines that came down earlier.  rings[n_rings] and
+ * verts[n_vertices][2] in, rings_out[n_rings] and verts_out[vert_capacity_out][2] out; counts_out[3] (host) as above.  More vertices
+ * than vert_capacity_out: LARS_ERR_INVALID with the counts set and nothing written; counts_out is -1 after any earlier failure. */
+int lars_h_outline_simplify(const lars_outline_ring *rings, int64_t n_rings, const int32_t *verts, int64_t n_vertices, int64_t tq, int64_t h, int64_t w,
+                            lars_outline_ring *rings_out, int32_t *verts_out, int64_t vert_capacity_out, int64_t *counts_out /* [3] */,
+                            int64_t *rounds_out /* may be NULL */);
+/* The three calls that trace outlines, with the simplification between the trace and the download: only the vertices written come
+ * down.  tq 1 .. LARS_SIMPLIFY_TQ_MAX on a raster of at most 32767 a side; tq == 0: exactly the call without _simplified, and no
+ * kernel more.  lars_outlines keeps its layout: n_vertices is the count written and what vert_capacity has to hold, n_edges is as
+ * before, *traced_vertices (may be NULL; -1 until it is known) the count the tracer wrote.  The retry protocol when the room is short
+ * stays the same, with the written count: all traced rings and vertices stay on the device, whatever the caller's room is. */
+int lars_h_region_outlines_simplified(const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int label_bytes, void *labels,
+                                      int *label_bytes_out /* may be NULL */, lars_region *table /* [capacity] */, int64_t capacity,
+                                      int64_t *n_regions, lars_outlines *outlines, int64_t *traced_vertices /* may be NULL */, int64_t tq);
+int lars_h_zonal_stats_regions_outlines_simplified_f32(const float *x, const uint8_t *mask /* may be NULL */, int mode, float t, int connectivity,
+                                                       int64_t min_pixels, const uint8_t *valid /* may be NULL */, int64_t h, int64_t w,
+                                                       float threshold, int want_hist, int64_t capacity, lars_stats *stats /* [capacity] */,
+                                                       float *medians /* [capacity][2] */, lars_region *table /* [capacity] */,
+                                                       int64_t *n_regions, void *labels_out /* may be NULL */, int label_bytes,
+                                                       int *label_bytes_out /* may be NULL */, lars_outlines *outlines,
+                                                       int64_t *traced_vertices /* may be NULL */, int64_t tq);
+int lars_h_process_image_regions_outlines_simplified(const void *img, int64_t h, int64_t w, int channels, int dtype,
+                                                     int apply_wb, uint32_t index_mask, int want_hist,
+                                                     uint8_t *out_wb, float *const out_index[3],
+                                                     lars_stats *stats /* [3] */, float *medians /* [3][2] */,
+                                                     uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3],
+                                                     const uint8_t *valid, int use_alpha, int has_nodata, int nodata, int64_t *valid_pixels,
+                                                     const uint8_t *mask /* may be NULL */, int source_index, int mode, float t, int connectivity,
+                                                     int64_t min_pixels, int64_t capacity,
+                                                     lars_stats *zone_stats /* [3][capacity] */, float *zone_medians /* [3][capacity][2] */,
+                                                     lars_region *table /* [capacity] */, int64_t *n_regions, void *labels_out /* may be NULL */,
+                                                     int label_bytes, int *label_bytes_out /* may be NULL */, lars_outlines *outlines,
+                                                     int64_t *traced_vertices /* may be NULL */, int64_t tq);
+
 /* ------------------------------------------------------------------ multi-GPU */
 /* One process per GPU.  RCCL (librccl.so) is loaded on first use.  unique_id is
  * LARS_COMM_ID_BYTES bytes produced by lars_comm_unique_id() on rank 0 and

@@ -50,7 +50,7 @@ from .api import (  # noqa: F401
 from .codecs import deflate_matching  # noqa: F401
 from .nodata import process_image_masked, valid_mask  # noqa: F401
 from .zones import (Polygons, Regions, Shrunk, label_regions, polygons_from_geojson, polygons_to_geojson, process_image_zones,  # noqa: F401
-                    rasterize_zones, region_outlines, shrink_zones, to_pixel, to_world, zonal_rows, zonal_statistics)
+                    rasterize_zones, region_outlines, shrink_zones, simplify_outlines, to_pixel, to_world, zonal_rows, zonal_statistics)
 from .batch import TileBatch, local_fold, merge_records, shard_range, summarize, timeseries_rows  # noqa: F401
 from .tiffio import read_image, read_tiff, write_float_tiff, write_tiff  # noqa: F401
 

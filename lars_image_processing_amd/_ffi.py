@@ -347,6 +347,17 @@ SIGNATURES = {
     "lars_h_process_image_regions_margin": (_I, [_P, _I64, _I64, _I, _I, _I, _U32, _I, _P, C.POINTER(_P * 3), _P, _P,
                                                  C.POINTER(_P * 3), C.POINTER(_P * 3), _P, _I, _I, _I, C.POINTER(_I64),
                                                  _P, _I, _I, _F, _I, _I64, _I64, _P, _P, _P, C.POINTER(_I64), _P, _I, C.POINTER(_I), _I64]),
+    "lars_outline_simplify_scratch_bytes": (_SZ, [_I64, _I64]),
+    "lars_d_outline_simplify": (_I, [_P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, _P, _I64, _P, _P, C.POINTER(_I64), _P]),
+    "lars_h_outline_simplify": (_I, [_P, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _I64, C.POINTER(_I64 * 3), C.POINTER(_I64)]),
+    "lars_h_region_outlines_simplified": (_I, [_P, _I64, _I64, _I, _I64, _I, _P, C.POINTER(_I), _P, _I64, C.POINTER(_I64), C.POINTER(Outlines),
+                                               C.POINTER(_I64), _I64]),
+    "lars_h_zonal_stats_regions_outlines_simplified_f32": (_I, [_P, _P, _I, _F, _I, _I64, _P, _I64, _I64, _F, _I, _I64, _P, _P, _P, C.POINTER(_I64), _P,
+                                                                _I, C.POINTER(_I), C.POINTER(Outlines), C.POINTER(_I64), _I64]),
+    "lars_h_process_image_regions_outlines_simplified": (_I, [_P, _I64, _I64, _I, _I, _I, _U32, _I, _P, C.POINTER(_P * 3), _P, _P,
+                                                              C.POINTER(_P * 3), C.POINTER(_P * 3), _P, _I, _I, _I, C.POINTER(_I64),
+                                                              _P, _I, _I, _F, _I, _I64, _I64, _P, _P, _P, C.POINTER(_I64), _P, _I, C.POINTER(_I),
+                                                              C.POINTER(Outlines), C.POINTER(_I64), _I64]),
     "lars_jpeg_bound": (_SZ, [_I64, _I64, _I, _I]),
     "lars_jpeg_header": (_I64, [_I64, _I64, _I, _I, _I, _P, _SZ]),
     "lars_jpeg_encode_scratch_bytes": (_SZ, [_I64, _I64, _I, _I]),

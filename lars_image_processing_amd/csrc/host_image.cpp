@@ -578,10 +578,10 @@ static int process_image_regions(const char *who, const void *img, int64_t h, in
                                  int has_nodata, int nodata, int64_t *valid_pixels, const uint8_t *mask, int source_index, int mode, float t,
                                  int connectivity, int64_t min_pixels, int64_t capacity, lars_stats *zone_stats, float *zone_medians,
                                  lars_region *table, int64_t *n_regions, void *labels_out, int label_bytes, int *label_bytes_out,
-                                 lars_outlines *outlines, int64_t margin2)
+                                 lars_outlines *outlines, int64_t margin2, int64_t *traced_vertices = nullptr, int64_t tq = 0)
 {
     const ZoneSource src = ZoneSource::of(h, w, ZoneRegions{mask, mask ? 0 : source_index, mode, t, connectivity, min_pixels, capacity, table, n_regions,
-                                                            labels_out, label_bytes, label_bytes_out, outlines}).shrunk_by(margin2);
+                                                            labels_out, label_bytes, label_bytes_out, outlines, tq, traced_vertices}).shrunk_by(margin2);
     ImageJob j;
     LARS_TRY(zones_job(&j, who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut, valid,
                        use_alpha, has_nodata, nodata, valid_pixels, src, {zone_stats, zone_medians, nullptr}));
@@ -603,6 +603,26 @@ int lars_h_process_image_regions_outlines(const void *img, int64_t h, int64_t w,
                                  index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut, valid, use_alpha, has_nodata, nodata, valid_pixels,
                                  mask, source_index, mode, t, connectivity, min_pixels, capacity, zone_stats, zone_medians, table, n_regions, labels_out,
                                  label_bytes, label_bytes_out, outlines, -1);
+}
+
+int lars_h_process_image_regions_outlines_simplified(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,
+                                                     int want_hist, uint8_t *out_wb, float *const out_index[3], lars_stats *stats, float *medians,
+                                                     uint8_t *const out_rgba[3], const uint8_t *const cmap_lut[3], const uint8_t *valid, int use_alpha,
+                                                     int has_nodata, int nodata, int64_t *valid_pixels, const uint8_t *mask, int source_index, int mode,
+                                                     float t, int connectivity, int64_t min_pixels, int64_t capacity, lars_stats *zone_stats,
+                                                     float *zone_medians, lars_region *table, int64_t *n_regions, void *labels_out, int label_bytes,
+                                                     int *label_bytes_out, lars_outlines *outlines, int64_t *traced_vertices, int64_t tq)
+{
+    if (!tq)
+        return lars_h_process_image_regions_outlines(img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba,
+                                                     cmap_lut, valid, use_alpha, has_nodata, nodata, valid_pixels, mask, source_index, mode, t, connectivity,
+                                                     min_pixels, capacity, zone_stats, zone_medians, table, n_regions, labels_out, label_bytes, label_bytes_out,
+                                                     outlines);
+    static const char *who = "lars_h_process_image_regions_outlines_simplified";
+    if (!outlines) return fail(LARS_ERR_INVALID, "%s: outlines == NULL", who);
+    return process_image_regions(who, img, h, w, channels, dtype, apply_wb, index_mask, want_hist, out_wb, out_index, stats, medians, out_rgba, cmap_lut, valid,
+                                 use_alpha, has_nodata, nodata, valid_pixels, mask, source_index, mode, t, connectivity, min_pixels, capacity, zone_stats,
+                                 zone_medians, table, n_regions, labels_out, label_bytes, label_bytes_out, outlines, -1, traced_vertices, tq);
 }
 
 int lars_h_process_image_regions_margin(const void *img, int64_t h, int64_t w, int channels, int dtype, int apply_wb, uint32_t index_mask,

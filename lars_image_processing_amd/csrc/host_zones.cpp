@@ -66,6 +66,12 @@ int check_regions(const char *who, const ZoneRegions &G, int64_t h, int64_t w, i
     if (G.outlines) {
         lars_outlines &O = *G.outlines;
         O.n_rings = O.n_vertices = O.n_edges = -1;
+        if (G.traced_vertices) *G.traced_vertices = -1;
+        if (G.simplify_tq < 0 || G.simplify_tq > LARS_SIMPLIFY_TQ_MAX)
+            return fail(LARS_ERR_INVALID, "%s: tq must be 0 to %d sixteenths of a pixel, got %lld", who, LARS_SIMPLIFY_TQ_MAX, (long long)G.simplify_tq);
+        if (G.simplify_tq && (h > LARS_SIMPLIFY_SIDE_MAX || w > LARS_SIMPLIFY_SIDE_MAX))
+            return fail(LARS_ERR_INVALID, "%s: outlines are simplified on a raster of at most %d a side (every product of coordinates fits 64 bits), got %lld x %lld",
+                        who, LARS_SIMPLIFY_SIDE_MAX, (long long)h, (long long)w);
         if (!lars_region_outline_scratch_bytes(h, w, 0))
             return fail(LARS_ERR_INVALID, "%s: outlines are traced on fewer than 2^29 pixels (an edge id fits int32), got %lld x %lld", who, (long long)h, (long long)w);
         if (O.ring_capacity < 0 || O.vert_capacity < 0 || (O.ring_capacity > 0 && !O.rings) || (O.vert_capacity > 0 && !O.verts) ||
@@ -240,12 +246,15 @@ int zone_stages(const char *who, const ZoneSource &src, const ZoneBufs &B, const
 
 // The outlines of the nregions labels in B.made, once everything else of the call is on the stream; no region: no ring.  Three waits:
 // for the edge count, which sizes the tracer's own area (the labels stand in the workspace, which cannot grow under them), for the ring
-// and vertex counts, which may exceed the caller's room, and for the rows and vertices.
+// and vertex counts, which may exceed the caller's room, and for the rows and vertices.  With a tolerance the rings are simplified
+// between the trace and the download (outline_simplify.hip, which waits once per batch of rounds): the traced vertices stay on the
+// device, in room for as many as there are edges, and only the vertices written have to fit the caller's room and come down.
 int trace_zone_outlines(const char *who, const ZoneSource &src, const ZoneLabelBufs &B, int64_t nregions, hipStream_t s)
 {
     lars_outlines &O = *src.regions.outlines;
-    const int64_t h = src.h, w = src.w;
+    const int64_t h = src.h, w = src.w, tq = src.regions.simplify_tq;
     O.n_rings = O.n_vertices = O.n_edges = 0;
+    if (src.regions.traced_vertices) *src.regions.traced_vertices = 0;
     if (!nregions) return LARS_OK;
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
@@ -257,12 +266,20 @@ int trace_zone_outlines(const char *who, const ZoneSource &src, const ZoneLabelB
     const size_t tracer = edges > 0 ? lars_region_outline_scratch_bytes(h, w, edges) : 0;
     if (!tracer) return fail(LARS_ERR_INVALID, "%s: %lld regions with %lld edges", who, (long long)nregions, (long long)edges);
     O.n_edges = edges;
-    // no more rings than the tracer's own ring arrays hold, no more vertices than edges
-    const int64_t rcap = O.ring_capacity < edges / 4 + 1 ? O.ring_capacity : edges / 4 + 1, vcap = O.vert_capacity < edges ? O.vert_capacity : edges;
+    // no more rings than the tracer's own ring arrays hold, no more vertices than edges; with a tolerance all of them stay on the device
+    const int64_t rcap = tq || O.ring_capacity > edges / 4 + 1 ? edges / 4 + 1 : O.ring_capacity;
+    const int64_t vcap = tq || O.vert_capacity > edges ? edges : O.vert_capacity, vcap_out = O.vert_capacity < edges ? O.vert_capacity : edges;
+    const size_t simplifier = tq ? lars_outline_simplify_scratch_bytes(rcap, vcap) : 0;
+    if (tq && !simplifier) return fail(LARS_ERR_INVALID, "%s: %lld rings and %lld vertices are more than can be simplified", who, (long long)rcap, (long long)vcap);
     char *scratch;
-    lars_outline_ring *rings;
-    int32_t *verts;
-    auto plan = [&](Carver &d) { scratch = d.take<char>(tracer), rings = d.take<lars_outline_ring>((size_t)rcap), verts = d.take<int32_t>(2 * (size_t)vcap); };
+    lars_outline_ring *rings, *rings_out = nullptr;
+    int32_t *verts, *verts_out = nullptr;
+    int64_t *counts_out = nullptr;
+    auto plan = [&](Carver &d) {
+        scratch = d.take<char>(tracer > simplifier ? tracer : simplifier);       // the simplifier starts when the tracer is done with it
+        rings = d.take<lars_outline_ring>((size_t)rcap), verts = d.take<int32_t>(2 * (size_t)vcap);
+        if (tq) rings_out = d.take<lars_outline_ring>((size_t)rcap), verts_out = d.take<int32_t>(2 * (size_t)vcap_out), counts_out = d.take<int64_t>(3);
+    };
     Carver size(nullptr);
     plan(size);
     LARS_TRY(outline_reserve(c, size.bytes() + 256));
@@ -273,12 +290,72 @@ int trace_zone_outlines(const char *who, const ZoneSource &src, const ZoneLabelB
     LARS_HIP_TRY(hipStreamSynchronize(s));
     O.n_rings = counts[1];
     O.n_vertices = counts[2];
+    if (src.regions.traced_vertices) *src.regions.traced_vertices = counts[2];
     if (counts[0] != edges || counts[1] < 1 || counts[2] < 4) return fail(LARS_ERR_HIP, "%s: the tracer counted %lld edges after %lld", who, (long long)counts[0], (long long)edges);
-    if (counts[1] > O.ring_capacity || counts[2] > O.vert_capacity)
+    if (!tq && (counts[1] > O.ring_capacity || counts[2] > O.vert_capacity))
         return fail(LARS_ERR_INVALID, "%s: %lld rings and %lld vertices; the room is %lld and %lld", who, (long long)counts[1], (long long)counts[2],
                     (long long)O.ring_capacity, (long long)O.vert_capacity);
+    if (tq) {
+        if (counts[1] > rcap || counts[2] > vcap)
+            return fail(LARS_ERR_HIP, "%s: the tracer wrote %lld rings and %lld vertices for %lld edges", who, (long long)counts[1], (long long)counts[2], (long long)edges);
+        int64_t written[3] = {-1, -1, -1};
+        LARS_TRY(lars_d_outline_simplify(rings, rcap, verts, vcap, B.outline_counts, tq, h, w, rings_out, verts_out, vcap_out, counts_out, scratch, nullptr, s));
+        LARS_HIP_TRY(hipMemcpyAsync(written, counts_out, sizeof written, hipMemcpyDeviceToHost, s));
+        LARS_HIP_TRY(hipStreamSynchronize(s));
+        if (written[0] != counts[1] || written[1] < 3 || written[1] > counts[2])
+            return fail(LARS_ERR_HIP, "%s: %lld rings and %lld vertices simplified after %lld and %lld traced", who, (long long)written[0], (long long)written[1],
+                        (long long)counts[1], (long long)counts[2]);
+        O.n_vertices = counts[2] = written[1];
+        if (counts[1] > O.ring_capacity || written[1] > O.vert_capacity)
+            return fail(LARS_ERR_INVALID, "%s: %lld rings and %lld vertices; the room is %lld and %lld", who, (long long)counts[1], (long long)written[1],
+                        (long long)O.ring_capacity, (long long)O.vert_capacity);
+        rings = rings_out, verts = verts_out;
+    }
     LARS_HIP_TRY(hipMemcpyAsync(O.rings, rings, (size_t)counts[1] * sizeof(lars_outline_ring), hipMemcpyDeviceToHost, s));
     LARS_HIP_TRY(hipMemcpyAsync(O.verts, verts, 2 * (size_t)counts[2] * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipStreamSynchronize(s));
+    return LARS_OK;
+}
+
+// Rings and vertices that came down earlier, simplified (simplify_outlines): up, lars_d_outline_simplify, down.
+int simplify_host_outlines(const char *who, const lars_outline_ring *rings, int64_t n_rings, const int32_t *verts, int64_t n_vertices, int64_t tq, int64_t h,
+                           int64_t w, lars_outline_ring *rings_out, int32_t *verts_out, int64_t vert_capacity_out, int64_t *counts_out, int64_t *rounds_out)
+{
+    ThreadCtx *c;
+    LARS_TRY(ensure_ctx(&c));
+    if (!counts_out) return fail(LARS_ERR_INVALID, "%s: counts_out == NULL", who);
+    counts_out[0] = counts_out[1] = counts_out[2] = -1;
+    if (n_rings < 0 || n_vertices < 0 || vert_capacity_out < 0 || (n_rings > 0 && (!rings || !rings_out)) || (n_vertices > 0 && !verts) ||
+        (vert_capacity_out > 0 && !verts_out) || !lars_outline_simplify_scratch_bytes(n_rings, n_vertices))
+        return fail(LARS_ERR_INVALID, "%s: ring tables of 0 to 2^31 - 1 rows and vertex arrays of as many vertices are required", who);
+    const int64_t vcap_out = vert_capacity_out < n_vertices ? vert_capacity_out : n_vertices;
+    lars_outline_ring *d_rings, *d_rings_out;
+    int32_t *d_verts, *d_verts_out;
+    int64_t *d_counts;
+    char *scratch;
+    LARS_TRY(ws_plan(c, [&](Carver &d) {
+        d_rings = d.take<lars_outline_ring>((size_t)n_rings), d_rings_out = d.take<lars_outline_ring>((size_t)n_rings);
+        d_verts = d.take<int32_t>(2 * (size_t)n_vertices), d_verts_out = d.take<int32_t>(2 * (size_t)vcap_out);
+        d_counts = d.take<int64_t>(6);
+        scratch = d.take<char>(lars_outline_simplify_scratch_bytes(n_rings, n_vertices));
+    }));
+    hipStream_t s = c->stream;
+    const int64_t given[3] = {0, n_rings, n_vertices};
+    int64_t written[3] = {-1, -1, -1};
+    LARS_HIP_TRY(hipMemcpyAsync(d_counts, given, sizeof given, hipMemcpyHostToDevice, s));
+    if (n_rings) LARS_HIP_TRY(hipMemcpyAsync(d_rings, rings, (size_t)n_rings * sizeof(lars_outline_ring), hipMemcpyHostToDevice, s));
+    if (n_vertices) LARS_HIP_TRY(hipMemcpyAsync(d_verts, verts, 2 * (size_t)n_vertices * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    LARS_TRY(lars_d_outline_simplify(d_rings, n_rings, d_verts, n_vertices, d_counts, tq, h, w, d_rings_out, d_verts_out, vcap_out, d_counts + 3, scratch, rounds_out, s));
+    LARS_HIP_TRY(hipMemcpyAsync(written, d_counts + 3, sizeof written, hipMemcpyDeviceToHost, s));
+    LARS_HIP_TRY(hipStreamSynchronize(s));
+    memcpy(counts_out, written, sizeof written);
+    if (written[0] != n_rings || written[1] < 0 || written[1] > n_vertices)
+        return fail(LARS_ERR_HIP, "%s: %lld rings and %lld vertices written for %lld and %lld given", who, (long long)written[0], (long long)written[1],
+                    (long long)n_rings, (long long)n_vertices);
+    if (written[1] > vert_capacity_out)
+        return fail(LARS_ERR_INVALID, "%s: %lld vertices; the room is %lld", who, (long long)written[1], (long long)vert_capacity_out);
+    if (n_rings) LARS_HIP_TRY(hipMemcpyAsync(rings_out, d_rings_out, (size_t)n_rings * sizeof(lars_outline_ring), hipMemcpyDeviceToHost, s));
+    if (written[1]) LARS_HIP_TRY(hipMemcpyAsync(verts_out, d_verts_out, 2 * (size_t)written[1] * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     LARS_HIP_TRY(hipStreamSynchronize(s));
     return LARS_OK;
 }
@@ -324,12 +401,13 @@ int labels_only(const char *who, const ZoneSource &src, ThreadCtx *c, int64_t *b
 
 // label_regions, and region_outlines where outlines are given: the labels stay in the workspace for the tracer
 int label_regions_call(const char *who, const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int label_bytes, void *labels,
-                       int *label_bytes_out, lars_region *table, int64_t capacity, int64_t *n_regions, lars_outlines *outlines)
+                       int *label_bytes_out, lars_region *table, int64_t capacity, int64_t *n_regions, lars_outlines *outlines,
+                       int64_t *traced_vertices = nullptr, int64_t tq = 0)
 {
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
     const ZoneSource src = ZoneSource::of(h, w, ZoneRegions{mask, 0, 0, 0.0f, connectivity, min_pixels, capacity, table, n_regions, labels, label_bytes,
-                                                            label_bytes_out, outlines});
+                                                            label_bytes_out, outlines, tq, traced_vertices});
     reset_zone_outputs(src, nullptr);
     if (!mask || !labels) return fail(LARS_ERR_INVALID, "%s: mask and labels are required", who);
     LARS_TRY(check_zone_source(who, src, 0x7FFFFFFF));
@@ -415,14 +493,27 @@ int lars_h_zonal_stats_polygons_f32(const float *x, const double *verts, int64_t
                                                   labels_out, label_bytes, -1);
 }
 
+int lars_h_zonal_stats_regions_outlines_simplified_f32(const float *x, const uint8_t *mask, int mode, float t, int connectivity, int64_t min_pixels,
+                                                       const uint8_t *valid, int64_t h, int64_t w, float threshold, int want_hist, int64_t capacity,
+                                                       lars_stats *stats, float *medians, lars_region *table, int64_t *n_regions, void *labels_out,
+                                                       int label_bytes, int *label_bytes_out, lars_outlines *outlines, int64_t *traced_vertices, int64_t tq)
+{
+    const char *who = tq        ? "lars_h_zonal_stats_regions_outlines_simplified_f32"
+                      : outlines ? "lars_h_zonal_stats_regions_outlines_f32"
+                                 : "lars_h_zonal_stats_regions_f32";
+    if (tq && !outlines) return fail(LARS_ERR_INVALID, "%s: outlines == NULL", who);
+    const ZoneRegions G = {mask, 0, mode, t, connectivity, min_pixels, capacity, table, n_regions, labels_out, label_bytes, label_bytes_out, outlines, tq,
+                           traced_vertices};
+    return zonal_stats(who, x, ZoneSource::of(h, w, G), valid, threshold, want_hist, {stats, medians, nullptr});
+}
+
 int lars_h_zonal_stats_regions_outlines_f32(const float *x, const uint8_t *mask, int mode, float t, int connectivity, int64_t min_pixels,
                                             const uint8_t *valid, int64_t h, int64_t w, float threshold, int want_hist, int64_t capacity,
                                             lars_stats *stats, float *medians, lars_region *table, int64_t *n_regions, void *labels_out,
                                             int label_bytes, int *label_bytes_out, lars_outlines *outlines)
 {
-    const ZoneRegions G = {mask, 0, mode, t, connectivity, min_pixels, capacity, table, n_regions, labels_out, label_bytes, label_bytes_out, outlines};
-    return zonal_stats(outlines ? "lars_h_zonal_stats_regions_outlines_f32" : "lars_h_zonal_stats_regions_f32", x, ZoneSource::of(h, w, G), valid, threshold,
-                       want_hist, {stats, medians, nullptr});
+    return lars_h_zonal_stats_regions_outlines_simplified_f32(x, mask, mode, t, connectivity, min_pixels, valid, h, w, threshold, want_hist, capacity, stats,
+                                                              medians, table, n_regions, labels_out, label_bytes, label_bytes_out, outlines, nullptr, 0);
 }
 
 int lars_h_zonal_stats_regions_margin_f32(const float *x, const uint8_t *mask, int mode, float t, int connectivity, int64_t min_pixels,
@@ -456,6 +547,23 @@ int lars_h_region_outlines(const uint8_t *mask, int64_t h, int64_t w, int connec
     static const char *who = "lars_h_region_outlines";
     if (!outlines) return fail(LARS_ERR_INVALID, "%s: outlines == NULL", who);
     return label_regions_call(who, mask, h, w, connectivity, min_pixels, label_bytes, labels, label_bytes_out, table, capacity, n_regions, outlines);
+}
+
+int lars_h_region_outlines_simplified(const uint8_t *mask, int64_t h, int64_t w, int connectivity, int64_t min_pixels, int label_bytes, void *labels,
+                                      int *label_bytes_out, lars_region *table, int64_t capacity, int64_t *n_regions, lars_outlines *outlines,
+                                      int64_t *traced_vertices, int64_t tq)
+{
+    const char *who = tq ? "lars_h_region_outlines_simplified" : "lars_h_region_outlines";
+    if (!outlines) return fail(LARS_ERR_INVALID, "%s: outlines == NULL", who);
+    return label_regions_call(who, mask, h, w, connectivity, min_pixels, label_bytes, labels, label_bytes_out, table, capacity, n_regions, outlines,
+                              traced_vertices, tq);
+}
+
+int lars_h_outline_simplify(const lars_outline_ring *rings, int64_t n_rings, const int32_t *verts, int64_t n_vertices, int64_t tq, int64_t h, int64_t w,
+                            lars_outline_ring *rings_out, int32_t *verts_out, int64_t vert_capacity_out, int64_t *counts_out, int64_t *rounds_out)
+{
+    return simplify_host_outlines("lars_h_outline_simplify", rings, n_rings, verts, n_vertices, tq, h, w, rings_out, verts_out, vert_capacity_out, counts_out,
+                                  rounds_out);
 }
 
 int lars_h_rasterize_zones_margin(const double *verts, int64_t nverts, const int32_t *ring_starts, int64_t nrings, const int32_t *poly_starts,

@@ -25,6 +25,8 @@ struct ZoneRegions {
     int64_t *n_regions;
     void *labels_out; int label_bytes; int *label_bytes_out;     // host [h][w] labels back, or null; label_bytes 0: the narrowest
     lars_outlines *outlines;               // the regions' rings and vertices back as well (outlines.hip), or null
+    int64_t simplify_tq = 0;               // ... simplified on the device before they come down (outline_simplify.hip): sixteenths of a pixel, 0: as traced
+    int64_t *traced_vertices = nullptr;    // ... and the count the tracer wrote, or null
 };
 
 // Where the labels of a call come from: exactly one of an uploaded raster, the rasteriser (zone_raster.hip) and the labeller

@@ -79,9 +79,9 @@ def _mask_argument(mask_kw):
     return (mask_kw,) if mask_kw else ()
 
 
-def _zones_argument(zones, zones_transform=None, regions=None, regions_geojson=False, zone_margin=None):
-    """``_process_image``'s ``zones`` (and ``zones_transform``, ``regions``, ``regions_geojson``, ``zone_margin``) keywords, handed over only
-    where they are named: without them the call is the one it always was."""
+def _zones_argument(zones, zones_transform=None, regions=None, regions_geojson=False, zone_margin=None, regions_simplify=None):
+    """``_process_image``'s ``zones`` (and ``zones_transform``, ``regions``, ``regions_geojson``, ``zone_margin``, ``regions_simplify``)
+    keywords, handed over only where they are named: without them the call is the one it always was."""
     kw = {} if zones is None else {"zones": zones}
     if zones_transform is not None:
         kw["zones_transform"] = zones_transform
@@ -97,6 +97,10 @@ def _zones_argument(zones, zones_transform=None, regions=None, regions_geojson=F
         if regions_geojson:
             raise ValueError("zone_margin and regions_geojson do not go together: outlines are traced from regions as found")
         kw["zone_margin"] = zone_margin
+    if regions_simplify is not None:
+        if not regions_geojson:
+            raise ValueError("regions_simplify is the tolerance of the outlines in the GeoJSON: it goes with regions_geojson")
+        kw["regions_simplify"] = regions_simplify
     return kw
 
 
@@ -196,7 +200,7 @@ def _matching(png_encoder, tiff_encoder):
 def process_image(image_path, output_dir, process_wb=False, indices=None, full_depth=False, lut_format="png",
                   png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow", tiff_encoder="pillow",
                   index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None, regions=None, regions_geojson=False,
-                  zone_margin=None):
+                  zone_margin=None, regions_simplify=None):
     """One file: same outputs as backend-process.py:49-73.  Returns the statistics dicts.
     ``full_depth=True`` reads three-sample 16-bit TIFFs at their full depth (``tiffio.read_image``; Pillow, hence the
     reference, keeps their high bytes only).  ``lut_format="tiff"`` writes the colormap images as
@@ -236,7 +240,9 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     through ``zones_transform`` in world coordinates.
     ``zone_margin=PX`` (with ``zones`` or ``regions``, not with ``regions_geojson``) shrinks every zone inward by that many pixels on
     the device before its figures are taken (``zones.shrink_zones``'s rule); the CSV has the same columns, the regions' area, box and
-    centroid stay those of the regions as found."""
+    centroid stay those of the regions as found.
+    ``regions_simplify=PX`` (with ``regions_geojson``) simplifies the outlines on the device before they are written
+    (``zones.region_outlines``'s ``simplify``: Douglas-Peucker with a tolerance of PX pixels, 0 to 254); the CSV does not change."""
     if lut_format not in ("png", "png8", "tiff"):
         raise ValueError(f"lut_format must be 'png', 'png8' or 'tiff', got {lut_format!r}")
     _check_png_encoder(png_encoder)
@@ -249,11 +255,12 @@ def process_image(image_path, output_dir, process_wb=False, indices=None, full_d
     with block:
         return _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder,
                               tiff_decoder, tiff_encoder, index_tiff, *_mask_argument(mask_kw),
-                              **_zones_argument(zones, zones_transform, regions, regions_geojson, zone_margin))
+                              **_zones_argument(zones, zones_transform, regions, regions_geojson, zone_margin, regions_simplify))
 
 
 def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_format, png_encoder, png_decoder, jpeg_decoder, tiff_decoder,
-                   tiff_encoder, index_tiff, mask_kw=None, zones=None, zones_transform=None, regions=None, regions_geojson=False, zone_margin=None):
+                   tiff_encoder, index_tiff, mask_kw=None, zones=None, zones_transform=None, regions=None, regions_geojson=False, zone_margin=None,
+                   regions_simplify=None):
     """``process_image`` behind its checks, for ``"pillow"``, ``"device"`` and ``"device+deflate"``."""
     from PIL import Image
     from .tiffio import read_image
@@ -271,7 +278,8 @@ def _process_image(image_path, output_dir, process_wb, indices, full_depth, lut_
         index, how, t, min_pixels = regions
         if index not in indices:
             raise ValueError(f"regions are taken from {index}, which is not among the requested indices {indices}")
-        zones = Regions(index=index, min_pixels=min_pixels, **{how: t}, **({"want_outlines": True} if regions_geojson else {}))
+        zones = Regions(index=index, min_pixels=min_pixels, **{how: t}, **({"want_outlines": True} if regions_geojson else {}),
+                        **({"simplify": regions_simplify} if regions_simplify is not None else {}))
     if zones is not None and indices:
         from .zones import process_image_zones
         labels = zones if regions is not None else _read_zones(zones, zones_transform, arr.shape[:2], image_path.name)
@@ -359,16 +367,16 @@ def batch_process(input_dir, output_dir, process_wb=False, process_ndvi=False, p
                   process_ndwi=True, workers=4, verbose=True, full_depth=False, lut_format="png", rank=0, world=1,
                   device=None, png_encoder="pillow", png_decoder="pillow", jpeg_decoder="pillow", tiff_decoder="pillow",
                   tiff_encoder="pillow", index_tiff=False, nodata=None, alpha_mask=False, zones=None, zones_transform=None, regions=None,
-                  regions_geojson=False, zone_margin=None):
+                  regions_geojson=False, zone_margin=None, regions_simplify=None):
     """backend-process.py:75-97 with its module constants as arguments.  Returns ``{file name: stats | error}``.
     ``rank`` / ``world``: one process per GPU, each takes its block of the sorted file list (``files_of_rank``); the output
     directories are shared, the file names distinct.  ``device``: the GPU ordinal every worker thread binds (the library's
     context is per thread and defaults to device 0); None leaves the threads' binding alone.  ``png_encoder``,
     ``png_decoder``, ``jpeg_decoder``, ``tiff_decoder``, ``tiff_encoder``, ``index_tiff``, ``nodata``, ``alpha_mask``, ``zones`` (one label
     raster, or one file of polygons with its ``zones_transform``, for every file of the directory), ``regions``, ``regions_geojson``,
-    ``zone_margin``: see ``process_image``."""
+    ``zone_margin``, ``regions_simplify``: see ``process_image``."""
     mask_kw = _mask_options(nodata, alpha_mask, lut_format)
-    zones_kw = _zones_argument(zones, zones_transform, regions, regions_geojson, zone_margin)
+    zones_kw = _zones_argument(zones, zones_transform, regions, regions_geojson, zone_margin, regions_simplify)
     _check_tiff_encoder(tiff_encoder)
     _check_png_encoder(png_encoder)
     _check_png_decoder(png_decoder)
@@ -506,6 +514,9 @@ def main(argv=None):
     ap.add_argument("--regions-geojson", action="store_true",
                     help="with --regions: also write <name>_regions.geojson, the outline of every region traced on the GPU, one feature per "
                          "region with its CSV figures as properties; --zones-transform puts it in world coordinates")
+    ap.add_argument("--regions-simplify", default=None, type=float, metavar="PX",
+                    help="with --regions-geojson: simplify the outlines on the GPU before they are written, Douglas-Peucker with a tolerance "
+                         "of PX pixels (0 to 254, in sixteenths); every traced vertex stays within PX of its ring")
     ap.add_argument("--zone-margin", default=None, type=float, metavar="PX",
                     help="with --zones or --regions: shrink every zone inward by PX pixels (0 to 254) on the GPU before its figures are "
                          "taken, so that the mixed pixels along a plot's edge stay out; the CSV columns are unchanged.  Not with "
@@ -514,6 +525,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.regions_geojson and args.regions is None:
         ap.error("--regions-geojson writes the outlines of the regions: it goes with --regions")
+    if args.regions_simplify is not None and not args.regions_geojson:
+        ap.error("--regions-simplify is the tolerance of the outlines in the GeoJSON: it goes with --regions-geojson")
+    if args.regions_simplify is not None and not 0 <= args.regions_simplify <= 254:
+        ap.error(f"--regions-simplify must be 0 to 254 pixels, got {args.regions_simplify}")
     if args.zone_margin is not None and args.zones is None and args.regions is None:
         ap.error("--zone-margin shrinks the zones of the picture: it goes with --zones or --regions")
     if args.zone_margin is not None and args.regions_geojson:
@@ -527,7 +542,8 @@ def main(argv=None):
                         device=local_rank if world > 1 else None, png_encoder=args.png_encoder,
                         png_decoder=args.png_decoder, jpeg_decoder=args.jpeg_decoder, tiff_decoder=args.tiff_decoder,
                         tiff_encoder=args.tiff_encoder, index_tiff=args.index_tiff, nodata=args.nodata, alpha_mask=args.alpha_mask,
-                        **_zones_argument(args.zones, args.zones_transform, args.regions, args.regions_geojson, args.zone_margin))
+                        **_zones_argument(args.zones, args.zones_transform, args.regions, args.regions_geojson, args.zone_margin,
+                                          args.regions_simplify))
     failed = {k: str(v) for k, v in res.items() if isinstance(v, Exception)}
     print(json.dumps({"rank": rank, "world": world, "files": len(res), "failed": failed}))
     return 1 if failed else 0

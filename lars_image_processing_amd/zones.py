@@ -19,7 +19,11 @@ want_outlines=True)``, traces the ring of pixel borders around every region and 
 
 The mixed pixels along a plot's edge stay out with a margin (DESIGN.md "Zone margins", csrc/zone_margin.hip): ``Shrunk(zones,
 margin)`` where ``zones`` is wanted shrinks every zone inward by that many pixels on the device before ``zonal_statistics`` and
-``process_image_zones`` take their figures, whichever of the three kinds made the labels; ``shrink_zones`` returns such labels."""
+``process_image_zones`` take their figures, whichever of the three kinds made the labels; ``shrink_zones`` returns such labels.
+
+And the outlines leave with a tolerance (DESIGN.md "Simplified outlines", csrc/outline_simplify.hip): ``region_outlines(...,
+simplify=t)`` and ``Regions(..., want_outlines=True, simplify=t)`` run Douglas-Peucker on the traced rings on the device, so that only
+the vertices kept cross PCIe; ``simplify_outlines`` does the same to outlines that came down earlier."""
 from __future__ import annotations
 
 import ctypes as C
@@ -39,6 +43,8 @@ VERTICES_MAX = 1 << 24
 COORDINATE_MAX = 1e9
 OUTLINE_PIXELS_MAX = 1 << 29
 MARGIN_MAX = 254
+SIMPLIFY_MAX = 254
+SIMPLIFY_SIDE_MAX = 32767
 _FIGURES = ("mean", "median", "min", "max", "coverage")
 
 
@@ -91,6 +97,27 @@ def _margin2(margin, who):
     while math.sqrt(n + 1) <= m:
         n += 1
     return n
+
+
+def _simplify_tq(tolerance, who):
+    """A tolerance in pixels -> the integer the device compares distances with, in sixteenths of a pixel: ``floor(tolerance * 16 +
+    0.5)``; None and every tolerance that rounds to 0 give 0, which is no simplification.  Every check of a tolerance, on the host."""
+    if tolerance is None:
+        return 0
+    if isinstance(tolerance, (bool, np.bool_)) or not isinstance(tolerance, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{who}: simplify must be a number of pixels or None (got {type(tolerance).__name__})")
+    t = float(tolerance)
+    if not math.isfinite(t):
+        raise ValueError(f"{who}: simplify must be finite, got {tolerance!r}")
+    if not 0 <= t <= SIMPLIFY_MAX:
+        raise ValueError(f"{who}: simplify must be 0 to {SIMPLIFY_MAX} pixels, got {tolerance!r}")
+    return int(math.floor(t * 16 + 0.5))
+
+
+def _simplify_sides(shape, who):
+    if max(int(shape[0]), int(shape[1])) > SIMPLIFY_SIDE_MAX:
+        raise ValueError(f"{who}: the raster is {int(shape[0])} x {int(shape[1])}; outlines are simplified on at most {SIMPLIFY_SIDE_MAX} a side "
+                         f"(every product of coordinates fits 64 bits)")
 
 
 class Shrunk:
@@ -344,10 +371,11 @@ def label_regions(mask, connectivity=8, min_pixels=1):
 class _OutlineRoom:
     """The host arrays the tracer fills and the ``lars_outlines`` that names them: room for ``rings`` rows and ``verts`` vertices."""
 
-    def __init__(self, rings, verts):
+    def __init__(self, rings, verts, tq=0):
         self.rings = np.empty(rings, dtype=_ffi.RING_DTYPE)
         self.verts = np.empty((verts, 2), dtype=np.int32)
         self.c = _ffi.Outlines(self.rings.ctypes.data, rings, self.verts.ctypes.data, verts, -1, -1, -1)
+        self.tq, self.traced = tq, C.c_int64(-1)                   # with a tolerance: the ``_simplified`` entry points, which report the traced count
 
     def short(self):
         """Did the call end because the rings or vertices found do not fit?"""
@@ -359,6 +387,8 @@ class _OutlineRoom:
         q, v = self.c.n_rings, self.c.n_vertices
         table = self.rings[:q]
         out = {"outlines": None, "ring_area2": table["area2"].astype(np.int64), "n_rings": q, "n_vertices": v}
+        if self.tq:
+            out["n_vertices_traced"] = self.traced.value
         if n_regions:
             ring_starts = np.append(table["start"], np.int32(v)).astype(np.int32)
             poly_starts = np.searchsorted(table["label"], np.arange(1, n_regions + 2)).astype(np.int32)
@@ -367,8 +397,18 @@ class _OutlineRoom:
 
 
 def _outline_argument(room):
-    """The trailing ``lars_outlines *`` of the entry points that trace outlines: none for those that do not."""
-    return (C.byref(room.c),) if room else ()
+    """The trailing ``lars_outlines *`` of the entry points that trace outlines, with the traced count and ``tq`` behind it for those
+    that simplify: none for those that do not trace."""
+    if not room:
+        return ()
+    return (C.byref(room.c), C.byref(room.traced), room.tq) if room.tq else (C.byref(room.c),)
+
+
+def _outline_entry(name, room):
+    """The entry point ``name`` that traces outlines, or its ``_simplified`` variant where the room has a tolerance."""
+    if not (room and room.tq):
+        return name
+    return name[:-4] + "_simplified_f32" if name.endswith("_f32") else name + "_simplified"
 
 
 def _outline_pixels(shape, who):
@@ -376,7 +416,7 @@ def _outline_pixels(shape, who):
         raise ValueError(f"{who}: the raster has {int(shape[0]) * int(shape[1])} pixels; outlines are traced on fewer than 2**29 (an edge id fits int32)")
 
 
-def region_outlines(mask, connectivity=8, min_pixels=1):
+def region_outlines(mask, connectivity=8, min_pixels=1, simplify=None):
     """``label_regions`` plus the outline of every region, traced on the device from the labels where they stand (DESIGN.md "Region
     outlines", csrc/outlines.hip).
 
@@ -387,15 +427,27 @@ def region_outlines(mask, connectivity=8, min_pixels=1):
     ``"ring_area2"``: int64, the exact doubled signed area of each ring (positive: outer, negative: hole; a region's rings add up to
     twice its pixels), ``"n_rings"`` and ``"n_vertices"``.  ``rasterize_zones(result["outlines"], mask.shape)`` gives the labels back
     (up to 65535 regions).  No region: empty arrays and ``"outlines": None``.  Fewer than 2**29 pixels.  Integer arithmetic on the
-    device: the same bytes on every run."""
-    return _label_regions(mask, connectivity, min_pixels, "region_outlines", True)
+    device: the same bytes on every run.
+
+    ``simplify``: a tolerance in pixels, 0 to 254, quantised to sixteenths; None, 0 or a tolerance below 1/32 is no simplification and
+    exactly the call above.  Otherwise every ring goes through Douglas-Peucker on the device before it comes down (DESIGN.md
+    "Simplified outlines", csrc/outline_simplify.hip), as the chain from its first vertex back to it, the distance taken to the
+    segment and compared in integers.  A ring whose result would have fewer than 3 vertices, no area or the other orientation stays
+    as traced: rings, their order and their regions never change, nothing disappears.  ``"n_vertices"`` and ``"ring_area2"`` then
+    describe the vertices written and ``"n_vertices_traced"`` is added.  ``rasterize_zones`` of simplified outlines no longer returns
+    the labels; what holds in its place: every traced vertex lies within the tolerance of its ring.  The raster is at most 32767 a
+    side."""
+    return _label_regions(mask, connectivity, min_pixels, "region_outlines", True, simplify)
 
 
-def _label_regions(mask, connectivity, min_pixels, who, want_outlines):
+def _label_regions(mask, connectivity, min_pixels, who, want_outlines, simplify=None):
     """``label_regions``, and ``region_outlines`` where the outlines are wanted: one call, repeated with the room it reported where
     the first guess was short."""
+    tq = _simplify_tq(simplify, who)
     if want_outlines and np.ndim(mask) == 2:
         _outline_pixels(np.shape(mask), who)                       # before anything is allocated
+        if tq:
+            _simplify_sides(np.shape(mask), who)
     m = _foreground(mask, who)
     connectivity = _connectivity(connectivity, who)
     min_pixels = _whole(min_pixels, "min_pixels", 1, (1 << 63) - 1, who)
@@ -411,10 +463,10 @@ def _label_regions(mask, connectivity, min_pixels, who, want_outlines):
     rings, verts = max(1, min(foreground, 1 << 22)), max(4, min(4 * foreground, 1 << 24))
     while True:
         table = np.zeros(capacity, dtype=_ffi.REGION_DTYPE)
-        room = _OutlineRoom(rings, verts) if want_outlines else None
+        room = _OutlineRoom(rings, verts, tq) if want_outlines else None
         count, width = C.c_int64(-1), C.c_int(0)
         try:
-            _ffi.call("lars_h_region_outlines" if room else "lars_h_label_regions", _ffi.ptr(m), h, w, connectivity, min_pixels, 0, _ffi.ptr(labels),
+            _ffi.call(_outline_entry("lars_h_region_outlines", room) if room else "lars_h_label_regions", _ffi.ptr(m), h, w, connectivity, min_pixels, 0, _ffi.ptr(labels),
                       C.byref(width), _ffi.ptr(table), capacity, C.byref(count), *_outline_argument(room))
             break
         except _ffi.LarsError:
@@ -430,8 +482,8 @@ def _label_regions(mask, connectivity, min_pixels, who, want_outlines):
 
 class Regions:
     """Zones taken from the picture itself: ``Regions(mask=None, index=None, above=None, below=None, connectivity=8, min_pixels=1,
-    max_regions=4096, want_labels=False, want_outlines=False, max_vertices=1 << 22)``, a third kind of ``zones`` beside a label raster
-    and ``Polygons``.
+    max_regions=4096, want_labels=False, want_outlines=False, max_vertices=1 << 22, simplify=None)``, a third kind of ``zones`` beside a
+    label raster and ``Polygons``.
 
     The foreground is a host ``mask`` (bool or integer ``[H, W]``, nonzero = foreground) or a threshold, ``above=t`` or ``below=t``,
     compared in float32 with the plane handed to ``zonal_statistics`` or with the ``index`` plane of ``process_image_zones``
@@ -441,10 +493,13 @@ class Regions:
     ``want_labels=True`` asks for the label raster as well.  ``want_outlines=True`` asks for the regions' outlines as
     ``region_outlines`` returns them (``"outlines"``, ``"ring_area2"``, ``"n_rings"``, ``"n_vertices"``), traced from the labels the
     zone stages used, on a raster of fewer than 2**29 pixels; ``max_vertices`` (4 to 2**31 - 1) is their room: more vertices raise
-    ``ValueError`` with their number.  Every check runs here, on the host."""
+    ``ValueError`` with their number.  ``simplify``: the tolerance in pixels ``region_outlines`` takes, with what it says there; it needs
+    ``want_outlines=True``, ``max_vertices`` is then the room of the vertices written, ``"n_vertices_traced"`` is added, and
+    ``rasterize_zones`` of such outlines no longer returns the labels: every traced vertex lies within the tolerance of its ring.  Every
+    check runs here, on the host."""
 
     def __init__(self, mask=None, index=None, above=None, below=None, connectivity=8, min_pixels=1, max_regions=4096, want_labels=False,
-                 want_outlines=False, max_vertices=1 << 22):
+                 want_outlines=False, max_vertices=1 << 22, simplify=None):
         who = "Regions"
         given = [name for name, v in (("mask", mask), ("above", above), ("below", below)) if v is not None]
         if len(given) != 1:
@@ -471,6 +526,9 @@ class Regions:
         self.want_labels = bool(want_labels)
         self.want_outlines = bool(want_outlines)
         self.max_vertices = _whole(max_vertices, "max_vertices", 4, (1 << 31) - 1, who)
+        self.simplify_tq = _simplify_tq(simplify, who)
+        if simplify is not None and not self.want_outlines:
+            raise ValueError(f"{who}: simplify is the tolerance of the outlines: it needs want_outlines=True")
 
     def _check(self, shape, picture_indices, who):
         """What only the call knows: the mask's shape, and the plane of a threshold.  Returns the id of that plane."""
@@ -480,6 +538,8 @@ class Regions:
             raise ValueError(f"{who}: the raster has {int(shape[0]) * int(shape[1])} pixels; regions are labelled on fewer than 2**31")
         if self.want_outlines:
             _outline_pixels(shape, who)
+            if self.simplify_tq:
+                _simplify_sides(shape, who)
         if picture_indices is None:
             if self.index is not None:
                 raise ValueError(f"{who}: Regions(index={self.index!r}) names a plane of a picture; the threshold is compared with index_array here")
@@ -493,8 +553,8 @@ class Regions:
         return INDEX_IDS[self.index]
 
     def _outline_room(self):
-        """Room for the outlines where they are wanted: a ring has four vertices or more."""
-        return _OutlineRoom(self.max_vertices // 4, self.max_vertices) if self.want_outlines else None
+        """Room for the outlines where they are wanted: a ring has four vertices or more, a simplified one three."""
+        return _OutlineRoom(self.max_vertices // (3 if self.simplify_tq else 4), self.max_vertices, self.simplify_tq) if self.want_outlines else None
 
 
 def _zone_source(zones, n_zones, who):
@@ -602,6 +662,49 @@ def shrink_zones(zones, margin, shape=None, transform=None, n_zones=None):
     labels = source._label_buffer((h, w))
     _ffi.call("lars_h_rasterize_zones_margin", *source._head(), h, w, labels.dtype.itemsize, _ffi.ptr(labels), m2)
     return labels
+
+
+def simplify_outlines(result, tolerance):
+    """The outlines of an earlier call with fewer vertices: ``region_outlines(..., simplify=tolerance)``'s rings from the rings of
+    ``region_outlines(...)``, on the device (DESIGN.md "Simplified outlines", csrc/outline_simplify.hip).
+
+    ``result``: the dict of ``region_outlines``, of ``zonal_statistics`` or of ``process_image_zones`` with outlines (there the
+    ``"zones"`` part is the one that changes).  A copy comes back whose ``"outlines"``, ``"ring_area2"`` and ``"n_vertices"`` describe
+    the vertices written, with ``"n_vertices_traced"`` added; everything else is shared.  The vertices must be whole numbers of 0 to
+    32767.  A tolerance of None, 0 or below 1/32 changes nothing: the copy has the keys and arrays it was given.  ``rasterize_zones`` of
+    simplified outlines no longer returns the labels; every vertex given lies within the tolerance of its ring."""
+    who = "simplify_outlines"
+    if not isinstance(result, dict):
+        raise TypeError(f"{who}: result must be the dict of region_outlines or of a zone call with outlines, got {type(result).__name__}")
+    if "zones" in result and isinstance(result["zones"], dict) and "outlines" in result["zones"]:
+        return {**result, "zones": simplify_outlines(result["zones"], tolerance)}
+    if "outlines" not in result or "ring_area2" not in result:
+        raise ValueError(f"{who}: this result holds no outlines (region_outlines, or Regions(want_outlines=True), returns them)")
+    tq = _simplify_tq(tolerance, who)
+    polys = result["outlines"]
+    if tq == 0 or polys is None:
+        return dict(result)
+    if not isinstance(polys, Polygons):
+        raise TypeError(f"{who}: result['outlines'] must be a Polygons, got {type(polys).__name__}")
+    xy = polys.verts
+    if not (np.isfinite(xy).all() and (xy == np.floor(xy)).all() and (xy >= 0).all() and (xy <= SIMPLIFY_SIDE_MAX).all()):
+        raise ValueError(f"{who}: the vertices must be whole numbers of 0 to {SIMPLIFY_SIDE_MAX}: pixel corners, as region_outlines writes them")
+    q, v = len(polys.ring_starts) - 1, len(xy)
+    area2 = np.asarray(result["ring_area2"])
+    if area2.shape != (q,):
+        raise ValueError(f"{who}: ring_area2 has shape {area2.shape} for {q} rings")
+    rings = np.zeros(q, dtype=_ffi.RING_DTYPE)
+    rings["label"] = np.repeat(np.arange(1, len(polys) + 1, dtype=np.int32), np.diff(polys.poly_starts))
+    rings["start"], rings["count"], rings["area2"] = polys.ring_starts[:-1], np.diff(polys.ring_starts), area2
+    verts = np.ascontiguousarray(xy[:, ::-1], dtype=np.int32)
+    rings_out, verts_out = np.empty(q, dtype=_ffi.RING_DTYPE), np.empty((v, 2), dtype=np.int32)
+    counts = (C.c_int64 * 3)(-1, -1, -1)
+    _ffi.call("lars_h_outline_simplify", _ffi.ptr(rings), q, _ffi.ptr(verts), v, tq, SIMPLIFY_SIDE_MAX, SIMPLIFY_SIDE_MAX, _ffi.ptr(rings_out),
+              _ffi.ptr(verts_out), v, C.byref(counts), None)
+    written = counts[1]
+    ring_starts = np.append(rings_out["start"], np.int32(written)).astype(np.int32)
+    outlines = Polygons._packed(np.ascontiguousarray(verts_out[:written, ::-1], dtype=np.float64), ring_starts, polys.poly_starts)
+    return {**result, "outlines": outlines, "ring_area2": rings_out["area2"].astype(np.int64), "n_vertices": written, "n_vertices_traced": v}
 
 
 def _geometry_rings(geom, where):
@@ -751,8 +854,8 @@ class _RegionZones:
         self.made = np.empty(shape, dtype=np.int32) if regions.want_labels else None
         self.found, self.width = C.c_int64(-1), C.c_int(0)
         self.room = regions._outline_room()
-        self.plane = "lars_h_zonal_stats_regions_outlines_f32" if self.room else "lars_h_zonal_stats_regions_f32"
-        self.picture = "lars_h_process_image_regions_outlines" if self.room else "lars_h_process_image_regions"
+        self.plane = _outline_entry("lars_h_zonal_stats_regions_outlines_f32", self.room) if self.room else "lars_h_zonal_stats_regions_f32"
+        self.picture = _outline_entry("lars_h_process_image_regions_outlines", self.room) if self.room else "lars_h_process_image_regions"
         self.foreground = (_ffi.ptr(regions.mask), regions.mode, regions.threshold, regions.connectivity, regions.min_pixels)
 
     def _tail(self, records, medians):

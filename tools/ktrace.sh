@@ -14,7 +14,7 @@ import csv, sys
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
 t0 = int(rows[0]["Start_Timestamp"])
 for r in rows:
-    name = r["Kernel_Name"].split("(")[0].replace("void lars::", "").replace("lars::", "")
+    name = r["Kernel_Name"].replace("(anonymous namespace)::", "").split("(")[0].replace("void lars::", "").replace("lars::", "")
     print("%10.0f us  %8.1f us  grid %-8s %s" % ((int(r["Start_Timestamp"]) - t0) / 1e3, (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3,
                                               r.get("Grid_Size", "?"), name))
 PY

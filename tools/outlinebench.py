@@ -17,16 +17,28 @@ unless ``--checkerboard-4`` asks for it.
              same Python above both: the calls that existed before must not have moved.  Twice ``--rounds`` rounds, the order of the
              legs reversed in every other one, so that neither library always follows the other's work.
 
+  simplify   with ``--simplify``: region_outlines(mask, simplify=t) (a) next to region_outlines(mask) (b) and to (b) followed by a host
+             simplification this tool brings itself (c: the rounds of the device in NumPy int64, ``host_simplify`` below -- no library;
+             checked equal to the model of the definition on the first rings and to (a) on all of them before anything is timed; timed
+             once a round, without a warm-up), for the tolerances of ``--tolerances`` on the ordinary masks and, at the sizes of
+             ``--corner-sizes``, on the slow corners: the checkerboard under connectivity 8 and a comb of growing teeth across the full
+             width, whose depth is linear in its teeth.  Per mask and tolerance: vertices traced and kept, rounds, rings kept as
+             traced, bytes down.  With ``--parent-lib`` also (d): region_outlines without the keyword, label_regions and
+             process_image_zones(img, Regions(...)) through the parent's library and this one in turn.
+
     python tools/outlinebench.py [--sizes 2048x1536,4096x4096] [--reps 5] [--rounds 3] [--hard] [--parent-lib PATH] [--json profiles/outlines.json]
+    python tools/outlinebench.py --simplify [--tolerances 0.5,1,2,8] [--parent-lib PATH] [--json profiles/outline_simplify.json]
 
 Kernel times come from a run of their own:
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/outlinebench.py --outlines-only --sizes 4096x4096
+    bash tools/ktrace.sh outline_simplify tools/outlinebench.py --simplify --simplify-only --masks field --sizes 4096x4096 --tolerances 1 --corner-sizes ''
 """
 import argparse
 import ctypes as C
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -87,6 +99,174 @@ def outline_row(lars, mask, connectivity, args, with_contourpy=False):
     return row
 
 
+def growing_comb(h, w):
+    """A spine along the top and a tooth in every other column, each a little longer than the one before: Douglas-Peucker takes them
+    off one or two a level, so the depth is about twice the teeth."""
+    mask = np.zeros((h, w), dtype=bool)
+    mask[0, :] = True
+    teeth = w // 2
+    for i in range(teeth):
+        mask[1:2 + i * (h - 3) // teeth, 2 * i] = True
+    return mask
+
+
+def host_simplify(ring_starts, xy, tq):
+    """Douglas-Peucker as csrc/outline_simplify.hip runs it, in NumPy int64 on the host: ``ring_starts`` int32 [Q + 1] and ``xy`` float64
+    [V, 2] (x, y) of a Polygons -> (ring_starts, xy, ring_area2, rounds, rings kept as traced) of the simplified rings."""
+    count = np.diff(ring_starts).astype(np.int64)
+    start = ring_starts[:-1].astype(np.int64)
+    q = len(count)
+    sbase = np.cumsum(count + 1) - (count + 1)
+    n = int((count + 1).sum())
+    ring = np.repeat(np.arange(q), count + 1)
+    pos = np.arange(n) - sbase[ring]
+    closing = pos == count[ring]
+    at = start[ring] + np.where(closing, 0, pos)
+    r, c = xy[at, 1].astype(np.int64), xy[at, 0].astype(np.int64)
+    a, b = sbase[ring].copy(), (sbase + count)[ring].copy()
+    kept = (pos == 0) | closing
+    inside = np.flatnonzero(~kept)
+    rounds, tq2 = 0, tq * tq
+    best_m, best_k = np.zeros(n, dtype=np.int64), np.full(n, n, dtype=np.int64)
+    while inside.size:
+        s = inside
+        sa, sb = a[s], b[s]
+        abr, abc, apr, apc = r[sb] - r[sa], c[sb] - c[sa], r[s] - r[sa], c[s] - c[sa]
+        len2, ap2, dot = abr * abr + abc * abc, apr * apr + apc * apc, apr * abr + apc * abc
+        bp2 = (r[s] - r[sb]) ** 2 + (c[s] - c[sb]) ** 2
+        cross = abr * apc - abc * apr
+        m = np.where(len2 == 0, ap2, np.where(dot <= 0, ap2 * len2, np.where(dot >= len2, bp2 * len2, cross * cross)))
+        best_m[sa] = 0
+        np.maximum.at(best_m, sa, m)
+        mine = (m == best_m[sa]) & (m > ((tq2 * np.where(len2 == 0, 1, len2)) >> 8))
+        best_k[sa] = n
+        np.minimum.at(best_k, sa[mine], s[mine])
+        k = best_k[sa]
+        split = k < n
+        if not split.any():
+            break
+        rounds += 1
+        kept[s[split & (s == k)]] = True
+        left, right = split & (s < k), split & (s > k)
+        b[s[left]] = k[left]
+        a[s[right]] = k[right]
+        inside = s[left | right]
+    nxt = np.where(np.append(kept[1:], True), np.arange(n) + 1, np.append(b[1:], n))
+    live, plain = kept & ~closing, ~closing
+    kc = np.bincount(ring[live], minlength=q)
+    karea, own = np.zeros(q, dtype=np.int64), np.zeros(q, dtype=np.int64)
+    np.add.at(karea, ring[live], c[live] * r[nxt[live]] - c[nxt[live]] * r[live])
+    after = np.flatnonzero(plain) + 1
+    np.add.at(own, ring[plain], c[plain] * r[after] - c[after] * r[plain])
+    back = (kc < 3) | (karea == 0) | ((karea > 0) != (own > 0))
+    written = plain & (back[ring] | kept)
+    out_count = np.where(back, count, kc)
+    starts = np.concatenate(([0], np.cumsum(out_count))).astype(np.int32)
+    return starts, np.stack((c[written], r[written]), axis=-1).astype(np.float64), np.where(back, own, karea), rounds, int(back.sum())
+
+
+def check_host_simplify(plain, tq, most=20000):
+    """``host_simplify`` is the model of the definition (tests/outline_simplify_model.py) on the first rings, ``most`` vertices of them."""
+    import outline_simplify_model as sm
+    p = plain["outlines"]
+    q = max(1, int(np.searchsorted(p.ring_starts, most, side="right")) - 1)
+    starts, verts = p.ring_starts[:q + 1], p.verts[:p.ring_starts[q]]
+    traced = {"verts": verts[:, ::-1].astype(np.int32), "ring_start": starts[:-1], "ring_count": np.diff(starts), "ring_area2": plain["ring_area2"][:q],
+              "n_rings": q, "n_vertices": len(verts), "ring_label": np.zeros(q, dtype=np.int32), "ring_key": np.zeros(q, dtype=np.int32), "n_edges": 0}
+    want = sm.simplify(traced, tq)
+    got = host_simplify(starts, verts, tq)
+    assert np.array_equal(got[0][:-1], want["ring_start"]) and np.array_equal(got[1], want["verts"][:, ::-1]) and np.array_equal(got[2], want["ring_area2"])
+    return q
+
+
+def simplify_row(lars, mask, connectivity, tolerances, args):
+    """The legs (a), (b), (c) on one mask for every tolerance."""
+    plain = lars.region_outlines(mask, connectivity=connectivity)
+    p = plain["outlines"]
+    row = {"n_regions": plain["n_regions"], "n_rings": plain["n_rings"], "n_vertices": plain["n_vertices"], "tolerances": {}}
+    ring_bytes, vert_bytes = _ffi.RING_DTYPE.itemsize, 8
+    for t in tolerances:
+        tq = int(np.floor(t * 16 + 0.5))
+        got = lars.region_outlines(mask, connectivity=connectivity, simplify=t)
+        if args.simplify_only:
+            for _ in range(2):
+                lars.region_outlines(mask, connectivity=connectivity, simplify=t)
+            row["tolerances"][str(t)] = {"kept": got["n_vertices"]}
+            continue
+        model_rings = check_host_simplify(plain, tq)
+        t0 = time.perf_counter()
+        starts, xy, area2, rounds, restored = host_simplify(p.ring_starts, p.verts, tq)
+        host_ms = (time.perf_counter() - t0) * 1e3
+        g = got["outlines"]
+        assert np.array_equal(starts, g.ring_starts) and np.array_equal(xy, g.verts) and np.array_equal(area2, got["ring_area2"])     # (c) is (a), byte for byte
+        assert got["n_vertices_traced"] == plain["n_vertices"]
+        legs = {"simplified": lambda: lars.region_outlines(mask, connectivity=connectivity, simplify=t),
+                "plain": lambda: lars.region_outlines(mask, connectivity=connectivity)}
+        out = {name: summary(rounds_) for name, rounds_ in alternate(legs, args.reps, args.rounds).items()}
+        host = []
+        for _ in range(args.host_rounds):
+            t0 = time.perf_counter()
+            again = lars.region_outlines(mask, connectivity=connectivity)
+            host_simplify(again["outlines"].ring_starts, again["outlines"].verts, tq)
+            host.append((time.perf_counter() - t0) * 1e3)
+        out["plain_then_host"] = summary(host)
+        out.update({"tq": tq, "traced": plain["n_vertices"], "kept": got["n_vertices"], "rounds": rounds, "rings_kept_as_traced": restored,
+                    "host_simplify_alone_ms": host_ms, "model_checked_rings": model_rings,
+                    "bytes_down": plain["n_rings"] * ring_bytes + got["n_vertices"] * vert_bytes,
+                    "bytes_down_plain": plain["n_rings"] * ring_bytes + plain["n_vertices"] * vert_bytes,
+                    "simplified_over_plain": out["simplified"]["ms"] / out["plain"]["ms"],
+                    "simplified_over_plain_then_host": out["simplified"]["ms"] / out["plain_then_host"]["ms"]})
+        row["tolerances"][str(t)] = out
+    return row
+
+
+def unchanged_row(lars, parent_path, h, w, args):
+    """(d): the calls that existed before, through the parent's library and this one, alternating, the order reversed every other round."""
+    here, parent = _ffi.load(), parent_library(parent_path)
+    mask, img = mask_of("field", h, w), picture(h, w)
+    regions = lars.Regions(index="NDVI", above=0.2, min_pixels=MIN_PIXELS, max_regions=65535)
+    a = lars.region_outlines(mask)
+    b = through(parent, lambda: lars.region_outlines(mask))()
+    assert all(np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes() for k in a if k != "outlines")          # the same bytes through both
+    assert all(getattr(a["outlines"], k).tobytes() == getattr(b["outlines"], k).tobytes() for k in ("verts", "ring_starts", "poly_starts"))
+    calls = {"region_outlines": lambda: lars.region_outlines(mask), "label_regions": lambda: lars.label_regions(mask),
+             "picture": lambda: lars.process_image_zones(img, regions)}
+    legs = {}
+    for name, fn in calls.items():
+        legs[name], legs[name + "_parent"] = through(here, fn), through(parent, fn)
+    times = {name: [] for name in legs}
+    for k in range(2 * args.rounds):
+        for name in list(legs)[::1 if k % 2 == 0 else -1]:
+            times[name].append(median_ms(legs[name], args.reps))
+    row = {name: summary(rounds) for name, rounds in times.items()}
+    for name in calls:
+        row[name + "_over_parent"] = row[name]["ms"] / row[name + "_parent"]["ms"]
+    return row
+
+
+def simplify_main(lars, args):
+    tolerances = [float(v) for v in args.tolerances.split(",")]
+    out = {"device": _ffi.device_name(), "reps": args.reps, "rounds": args.rounds, "host_rounds": args.host_rounds, "tolerances": tolerances, "sizes": {}}
+    corner_sizes = set(args.corner_sizes.split(",")) if args.corner_sizes else set()
+    for size in args.sizes.split(","):
+        w, h = (int(v) for v in size.split("x"))
+        size_row = {"pixels": h * w, "masks": {}}
+        cases = [] if args.no_ordinary else [(kind, 8, lambda kind=kind: mask_of(kind, h, w)) for kind in MASKS if kind in args.masks.split(",")]
+        if size in corner_sizes:
+            cases += [("checkerboard-8", 8, lambda: mask_of("checkerboard", h, w)), ("growing-comb", 8, lambda: growing_comb(h, w))]
+        for name, connectivity, make in cases:
+            size_row["masks"][name] = simplify_row(lars, make(), connectivity, tolerances, args)
+            print(f"{size} simplify {name}", json.dumps(size_row["masks"][name]), flush=True)
+        if args.parent_lib and not args.simplify_only:
+            size_row["unchanged"] = unchanged_row(lars, args.parent_lib, h, w, args)
+            print(f"{size} unchanged", json.dumps(size_row["unchanged"]), flush=True)
+        out["sizes"][size] = size_row
+    print(json.dumps(out))
+    if args.json:
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", default="2048x1536,4096x4096", help="WIDTHxHEIGHT, comma separated")
@@ -98,9 +278,17 @@ def main():
     ap.add_argument("--outlines-only", action="store_true", help="region_outlines alone, twice per mask after a first call (for a kernel trace)")
     ap.add_argument("--parent-lib", help="a liblars_hip.so of the parent commit: the calls that existed before, through both libraries in turn")
     ap.add_argument("--json", help="also write the figures to this file")
+    ap.add_argument("--simplify", action="store_true", help="the legs of region_outlines(simplify=): see above")
+    ap.add_argument("--tolerances", default="0.5,1,2,8", help="with --simplify: the tolerances in pixels, comma separated")
+    ap.add_argument("--corner-sizes", default="2048x1536", help="with --simplify: the sizes (of --sizes) at which the slow corners run as well; empty for none")
+    ap.add_argument("--masks", default=",".join(MASKS), help="with --simplify: which of the ordinary masks, comma separated")
+    ap.add_argument("--host-rounds", type=int, default=1, help="with --simplify: how often leg (c), which takes seconds, is timed")
+    ap.add_argument("--simplify-only", action="store_true", help="with --simplify: region_outlines(simplify=) alone, twice after a first call (for a kernel trace)")
     args = ap.parse_args()
     import lars_image_processing_amd as lars
     print("device:", _ffi.device_name(), flush=True)
+    if args.simplify:
+        return simplify_main(lars, args)
     out = {"device": _ffi.device_name(), "reps": args.reps, "rounds": args.rounds, "sizes": {}}
     for w, h in [tuple(int(v) for v in s.split("x")) for s in args.sizes.split(",")]:
         size_row = {"pixels": h * w, "outlines": {}}
