@@ -198,6 +198,42 @@ int lars_d_fused(const lars_fused_args *args);
 int lars_d_stats_begin(lars_stats *stats, int64_t ntiles, uint32_t index_mask, void *stream);
 int lars_d_stats_end(lars_stats *stats, int64_t ntiles, uint32_t index_mask, int64_t npix, void *stream);
 
+/* White-balance tables of a batch of LARS_U8 tiles from a SAMPLE of every tile (csrc/wb_predict.hip), proven exact while the
+ * planes are written.  lars_d_wb_predict stands where lars_d_channel_hist + lars_d_wb_table stood: per tile it counts a
+ * fraction of the tile (whole 4 KiB segments at hashed positions), takes per channel and mark the value whose bin holds the
+ * mark in the sample's CDF, and calls the mark confident when both edges of that bin lie k standard errors away from it (the
+ * error measured between 16 interleaved groups of segments).  A tile whose six marks are confident gets percentiles and table
+ * from the predicted values and is PREDICTED; every other tile takes the exact pass in the same call.  *predicted = 1 when the
+ * predictor ran at all (3-channel 4-byte aligned tiles of at least wb_predict_min_pixels pixels, knob wb_predict not 0), else
+ * the call was the exact pre-pass.  The hist rows of predicted tiles are zero until something counts them.
+ *   lars_d_fused_verified   lars_d_fused over tiles [tile_start, tile_start + args->ntiles) of that batch (args->wb_table,
+ *                           args->stats and the outputs start at tile_start as ever; v names the batch's arrays).  Where a
+ *                           verifying kernel exists (uint8 RGNir fast path, white balance, at most basic statistics) the launch
+ *                           counts, per channel and over all pixels, the samples below and up to each predicted value; a tile
+ *                           whose counts do not prove all six percentiles is repaired right behind it on the same stream: exact
+ *                           histogram pass, tables, its statistics records opened again, the launch repeated for it -- plain
+ *                           kernels whose blocks return early, each evaluating the counts itself.  Elsewhere the predicted tiles
+ *                           of the range take the exact pass first.  Either way everything the call leaves is exact.
+ *   lars_d_wb_settle        the exact pass for every tile still predicted: what any other reader of the tables calls first.
+ *   lars_wb_predict_report  (tiles the last lars_d_wb_predict called confident, tiles among them a verified launch has
+ *                           repaired since), after the stream has finished.
+ * scratch: lars_wb_predict_scratch_bytes(ntiles) bytes of device memory owned by the caller, the same for all four calls. */
+typedef struct lars_wb_verify {
+    void     *scratch;
+    int64_t   batch_tiles;         /* tiles of the batch the scratch, hist and percentiles belong to */
+    int64_t   tile_start;          /* the launch's first tile inside the batch */
+    uint32_t *hist;                /* [batch_tiles][3][256] */
+    double   *percentiles;         /* [batch_tiles][3][2] */
+    int32_t   rgn_variant;         /* flavour of the tables (lars_d_wb_table) */
+} lars_wb_verify;
+size_t lars_wb_predict_scratch_bytes(int64_t ntiles);
+int lars_d_wb_predict(const void *tiles, int64_t ntiles, int64_t npix, int channels, int dtype, uint32_t *hist, uint8_t *table,
+                      double *percentiles, int rgn_variant, void *scratch, int *predicted, void *stream);
+int lars_d_fused_verified(const lars_fused_args *args, const lars_wb_verify *v);
+int lars_d_wb_settle(const void *tiles, int64_t ntiles, int64_t npix, uint32_t *hist, uint8_t *table, double *percentiles,
+                     int rgn_variant, void *scratch, void *stream);
+int lars_wb_predict_report(const void *scratch, int64_t ntiles, int64_t *confident, int64_t *missed);
+
 /* float32 band planes -> index, backend-process.py:28-38 (literal formula with
  * the float32 epsilon add and the clip; any float input). */
 int lars_d_index_planes_f32(const float *red, const float *green, const float *nir,
@@ -352,6 +388,11 @@ int lars_d_synth_u8(uint8_t *tiles, int64_t ntiles, int64_t first_tile, int64_t 
  * lane of the JPEG decoder takes (lars_d_decode_jpeg_u8; 32 = the longest code plus its extra bits, rounded up).
  * The knob load_policy (0 .. 2) is the cache policy of the kernels' streaming tile loads: 0 = each kernel's measured choice
  * (profiles/load_policy_kernels.txt), 1 = plain loads everywhere, 2 = non-temporal (nt) loads everywhere.
+ * The knob wb_predict is how lars_d_wb_predict decides: 1 = tables predicted from a sample and proven while the planes are written,
+ * 0 = never (the exact pre-pass), 2 = every prediction one value off (every confident tile misses and is repaired: a test hook),
+ * 3 = the confidence gate always passes (test hook); wb_predict_sixteenths 2 .. 4 = sixteenths of a tile it samples,
+ * wb_predict_k 1 .. 16 = standard errors a mark must keep from the edges of its bin, wb_predict_min_pixels = smaller tiles always
+ * take the exact pass.
  * Results never depend on them.  Read-only:
  * "last_fused_kernel" = the kernel family the last lars_d_fused launched (1 k_fused_u8c3, 2 k_fused_v2, 3 its uint16 form,
  * 4 k_fused_generic: one pixel per lane, 5 k_fused_u8c3 for RGBA uint8 tiles), "jpeg_last_rounds" = the synchronisation rounds

@@ -82,6 +82,14 @@ class FusedArgs(C.Structure):
     ]
 
 
+class WbVerify(C.Structure):
+    """``lars_wb_verify`` (include/lars_hip.h)."""
+    _fields_ = [
+        ("scratch", C.c_void_p), ("batch_tiles", C.c_int64), ("tile_start", C.c_int64),
+        ("hist", C.c_void_p), ("percentiles", C.c_void_p), ("rgn_variant", C.c_int32),
+    ]
+
+
 class PngInfo(NamedTuple):
     """``info[LARS_PNG_INFO_N]`` of ``lars_png_info``: the field order is the header's ``LARS_PNG_INFO_*`` (tests/test_abi_cpu.py).
     ``PngInfo(*info)`` names a filled array, ``PngInfo.array()`` makes an empty one."""
@@ -187,6 +195,11 @@ SIGNATURES = {
     "lars_d_fused": (_I, [C.POINTER(FusedArgs)]),
     "lars_d_stats_begin": (_I, [_P, _I64, _U32, _P]),
     "lars_d_stats_end": (_I, [_P, _I64, _U32, _I64, _P]),
+    "lars_wb_predict_scratch_bytes": (_SZ, [_I64]),
+    "lars_d_wb_predict": (_I, [_P, _I64, _I64, _I, _I, _P, _P, _P, _I, _P, C.POINTER(_I), _P]),
+    "lars_d_fused_verified": (_I, [C.POINTER(FusedArgs), C.POINTER(WbVerify)]),
+    "lars_d_wb_settle": (_I, [_P, _I64, _I64, _P, _P, _P, _I, _P, _P]),
+    "lars_wb_predict_report": (_I, [_P, _I64, C.POINTER(_I64), C.POINTER(_I64)]),
     "lars_d_index_planes_f32": (_I, [_P, _P, _P, _I64, _I, _P, _P]),
     "lars_d_ndvi_f64": (_I, [_P, _I64, _I, _I, _P, _P]),
     "lars_d_array_stats_f32": (_I, [_P, _I64, _F, _I, _P, _P]),

@@ -86,6 +86,21 @@ def plan_process(code, channels, ntiles, npix, indices, white_balance, hist, med
     return "per-pixel+radix" if medians else "per-pixel"
 
 
+def _knob(name):
+    """A tuning knob read straight from the library (a query, not a launch: it does not go through ``_ffi.call``)."""
+    v = C.c_int(0)
+    if _ffi.load().lars_get_tuning(name.encode(), C.byref(v)) != 0:
+        raise _ffi.LarsError(-1, f"lars_get_tuning: unknown key {name}")
+    return v.value
+
+
+def wb_predict_serves(channels, npix):
+    """Does ``compute_wb_tables`` of a uint8 batch go through the sampling predictor (``lars_d_wb_predict``)?  RGNir tiles of at
+    least ``wb_predict_min_pixels`` pixels while the knob ``wb_predict`` is not 0; the library refuses what else it cannot sample
+    (alignment, tiles of 2^30 bytes) and runs the exact pre-pass itself."""
+    return channels == 3 and _knob("wb_predict") != 0 and npix >= _knob("wb_predict_min_pixels")
+
+
 def channels_of(indices, whole_image=False):
     """Channels (0 red, 1 green, 2 NIR) whose white-balance tables a pass over ``indices`` reads."""
     if whole_image:
@@ -130,6 +145,9 @@ class TileBatch:
         self._joint_tiles = self.ntiles    # tiles the last run_joint covered
         self._selq = None                  # select_histogram's counts
         self.last_route = None             # the route the last process() took (plan_process)
+        self._wbp_scratch = None           # compute_wb_tables' scratch for tables predicted from a sample (csrc/wb_predict.hip)
+        self._provisional = False          # tiles may run on predicted tables: a verified launch or settle_tables() makes them exact
+        self._hist_stale = False           # a verified launch has proven predicted tiles without counting them: host_hist counts first
 
     # -- construction -----------------------------------------------------
     @classmethod
@@ -163,10 +181,23 @@ class TileBatch:
         if self.code == _ffi.U8:
             if self.hist is None:
                 self.hist = DeviceBuffer(self.ntiles * 3 * 256 * 4)
-            _ffi.call("lars_d_channel_hist", C.c_void_p(self.tiles.ptr), self.ntiles, self.npix, self.channels,
-                      self.code, C.c_void_p(self.hist.ptr), stream)
-            _ffi.call("lars_d_wb_table", C.c_void_p(self.hist.ptr), self.ntiles, self.npix, self.code,
-                      C.c_void_p(self.table.ptr), C.c_void_p(self.percentiles.ptr), int(rgn_variant), stream)
+            self._provisional = self._hist_stale = False
+            if wb_predict_serves(self.channels, self.npix):
+                # tables of large tiles from a sample of each tile; a tile the sample cannot decide takes the exact pass in the same
+                # call.  Predicted tables are provisional: run_fused_chunks proves them while it writes, every other reader settles first.
+                # Tiles below the pixel threshold keep the two calls of the exact pre-pass
+                if self._wbp_scratch is None:
+                    self._wbp_scratch = DeviceBuffer(int(_ffi.load().lars_wb_predict_scratch_bytes(self.ntiles)))
+                predicted = C.c_int(0)
+                _ffi.call("lars_d_wb_predict", C.c_void_p(self.tiles.ptr), self.ntiles, self.npix, self.channels, self.code,
+                          C.c_void_p(self.hist.ptr), C.c_void_p(self.table.ptr), C.c_void_p(self.percentiles.ptr), int(rgn_variant),
+                          C.c_void_p(self._wbp_scratch.ptr), C.byref(predicted), stream)
+                self._provisional = bool(predicted.value)
+            else:
+                _ffi.call("lars_d_channel_hist", C.c_void_p(self.tiles.ptr), self.ntiles, self.npix, self.channels,
+                          self.code, C.c_void_p(self.hist.ptr), stream)
+                _ffi.call("lars_d_wb_table", C.c_void_p(self.hist.ptr), self.ntiles, self.npix, self.code,
+                          C.c_void_p(self.table.ptr), C.c_void_p(self.percentiles.ptr), int(rgn_variant), stream)
         else:
             # uint16: two-level radix percentiles, no 65536-bin histograms
             _ffi.call("lars_d_wb_prepare", C.c_void_p(self.tiles.ptr), self.ntiles, self.npix, self.channels,
@@ -175,6 +206,24 @@ class TileBatch:
         self._hist_channels = {0, 1, 2} if self.code == _ffi.U8 else set()
         self._rgn_variant = int(rgn_variant)
         return self
+
+    def settle_tables(self, stream=None):
+        """The exact pass for every tile whose table is still a prediction (``lars_d_wb_settle``); nothing to do otherwise.  Everything that
+        reads tables, percentiles or histograms other than the verified launches of ``run_fused_chunks`` calls this first."""
+        if self._provisional:
+            _ffi.call("lars_d_wb_settle", C.c_void_p(self.tiles.ptr), self.ntiles, self.npix, C.c_void_p(self.hist.ptr),
+                      C.c_void_p(self.table.ptr), C.c_void_p(self.percentiles.ptr), self._rgn_variant, C.c_void_p(self._wbp_scratch.ptr), stream)
+            self._provisional = False
+        return self
+
+    def wb_predict_report(self):
+        """(tiles the last ``compute_wb_tables`` predicted from their sample, tiles among them whose prediction a verified launch found
+        wrong and repaired) -- after the stream has finished."""
+        conf, missed = C.c_int64(0), C.c_int64(0)
+        if self._wbp_scratch is None:
+            return 0, 0
+        _ffi.call("lars_wb_predict_report", C.c_void_p(self._wbp_scratch.ptr), self.ntiles, C.byref(conf), C.byref(missed))
+        return int(conf.value), int(missed.value)
 
     def u16_window_report(self):
         """(flags[ntiles], windows[ntiles, 3, 4]) of the last ``compute_wb_tables`` of a uint16 batch on this thread, after its stream
@@ -200,11 +249,13 @@ class TileBatch:
 
     def host_tables(self, partial=False):
         self._need_channels(partial)
+        self.settle_tables()
         blob = self.table.download(np.uint8, (self.ntiles, self.table_bytes))
         return np.ascontiguousarray(blob[:, :3 * self.nvalues]).reshape(self.ntiles, 3, self.nvalues)
 
     def host_percentiles(self, partial=False):
         self._need_channels(partial)
+        self.settle_tables()
         return self.percentiles.download(np.float64, (self.ntiles, 3, 2))
 
     def host_hist(self, partial=False):
@@ -216,6 +267,12 @@ class TileBatch:
             missing = sorted({0, 1, 2} - self._hist_channels)
             raise RuntimeError(f"channel histograms of channel(s) {missing} are not valid: the last one-read pass was not asked for them "
                                f"(compute_wb_tables(), or run_joint(..., channel_hist=True); partial=True hands out what there is)")
+        self.settle_tables()
+        if self._hist_stale:
+            # a verified launch proved the predicted tiles' tables without counting them: count now
+            _ffi.call("lars_d_channel_hist", C.c_void_p(self.tiles.ptr), self.ntiles, self.npix, self.channels, self.code,
+                      C.c_void_p(self.hist.ptr), None)
+            self._hist_stale = False
         return self.hist.download(np.uint32, (self.ntiles, 3, 256))
 
     # -- pass 2: the fused kernel ------------------------------------------
@@ -312,7 +369,10 @@ class TileBatch:
         return timed / len(launches)
 
     def fused_args(self, indices=INDEX_NAMES, white_balance=True, stats=None, hist=False, outputs=None,
-                   stream=None, tile_start=0, tile_count=None, sumsq=False, raw=False):
+                   stream=None, tile_start=0, tile_count=None, sumsq=False, raw=False, settle=True):
+        """``settle=False``: the caller is a verified launch (``run_fused``'s ``verify``) and takes the tables as predicted."""
+        if white_balance and settle:
+            self.settle_tables(stream)
         tile_count = self.ntiles - tile_start if tile_count is None else tile_count
         a = FusedArgs()
         a.tiles = self.tiles.ptr + tile_start * self.tile_bytes
@@ -360,10 +420,14 @@ class TileBatch:
         launch.  Returns the number of fused launches.  ``launch_events``: event handles, [0] recorded before the first
         launch and [i + 1] after launch i (as many launches as there are handles for): per-launch times for diagnostics."""
         chunk = self.ntiles if outputs is None else outputs.slots
+        # tiles on predicted tables: every launch proves its tiles' tables while it writes and repairs those it cannot (lars_d_fused_verified)
+        verify = bool(white_balance and self._provisional)
         if chunk >= self.ntiles:
             if launch_events:
                 _ffi.call("lars_event_record", launch_events[0], stream)
-            self.run_fused(self.fused_args(indices, white_balance, stats, hist, outputs, stream, sumsq=sumsq))
+            self.run_fused(self.fused_args(indices, white_balance, stats, hist, outputs, stream, sumsq=sumsq, settle=not verify),
+                           0 if verify else None)
+            self._verified_pass_done(verify)
             if launch_events and len(launch_events) > 1:
                 _ffi.call("lars_event_record", launch_events[1], stream)
             return 1
@@ -376,16 +440,30 @@ class TileBatch:
         for start in range(0, self.ntiles, chunk):
             count = min(chunk, self.ntiles - start)
             self.run_fused(self.fused_args(indices, white_balance, stats, hist, outputs, stream, start, count, sumsq=sumsq,
-                                           raw=stats is not None))
+                                           raw=stats is not None, settle=not verify), start if verify else None)
             launches += 1
             if launch_events and launches < len(launch_events):
                 _ffi.call("lars_event_record", launch_events[launches], stream)
         if stats is not None:
             _ffi.call("lars_d_stats_end", C.c_void_p(stats.ptr), self.ntiles, mask, self.npix, stream)
+        self._verified_pass_done(verify)
         return launches
 
-    def run_fused(self, args):
-        _ffi.call("lars_d_fused", C.byref(args))
+    def _verified_pass_done(self, verify):
+        """Verified launches have covered the whole batch: every table is exact; the predicted tiles' histogram rows were never counted."""
+        if verify:
+            self._provisional = False
+            self._hist_stale = True
+
+    def run_fused(self, args, verify_start=None):
+        """``verify_start``: the launch's first tile when its tiles may run on predicted tables (``fused_args(settle=False)``)."""
+        if verify_start is None:
+            _ffi.call("lars_d_fused", C.byref(args))
+            return
+        v = _ffi.WbVerify()
+        v.scratch, v.batch_tiles, v.tile_start = self._wbp_scratch.ptr, self.ntiles, int(verify_start)
+        v.hist, v.percentiles, v.rgn_variant = self.hist.ptr, self.percentiles.ptr, self._rgn_variant
+        _ffi.call("lars_d_fused_verified", C.byref(args), C.byref(v))
 
     # -- statistics from one read: joint byte-pair histograms (csrc/joint.hip) ----
     def can_joint(self):
@@ -401,6 +479,7 @@ class TileBatch:
         ``self.hist``.  Without the histograms a pass over both value streams may count red and green clamped to windows
         around their percentiles, both pair tables of a tile chunk in ONE workgroup (csrc/joint_win.hip): same records,
         percentiles, tables and medians, one reader per byte instead of two."""
+        self.settle_tables(stream)
         mask = index_mask(indices)
         need = int(_ffi.load().lars_joint_scratch_bytes(self.ntiles, self.npix, mask))
         if self._joint_scratch is None or self._joint_scratch.nbytes < need:
@@ -483,6 +562,7 @@ class TileBatch:
         cache = self.__dict__.setdefault("_route_cache", {})
         if key in cache:
             return cache[key]
+        self.settle_tables()
         sample = min(int(sample), self.ntiles)
         if sample * self.npix < int(min_pixels) or self.channels != 3:
             cache[key] = "joint"
@@ -642,7 +722,7 @@ class TileBatch:
         return rec, med
 
     def free(self):
-        for b in (self.tiles, self.hist, self.table, self.percentiles, self._joint_scratch, self._selq):
+        for b in (self.tiles, self.hist, self.table, self.percentiles, self._joint_scratch, self._selq, self._wbp_scratch):
             if b is not None:
                 b.free()
 
@@ -651,6 +731,7 @@ class TileBatch:
         (``lars_d_quotient_median_pairs``: per-tile two-level select on recomputed values, all on the device)."""
         if white_balance and (self.table is None or not channels_of(indices) <= self._table_channels):
             raise RuntimeError("compute_wb_tables() first")
+        self.settle_tables(stream)
         return self._per_tile_select(indices, stream, lambda pairs, scratch: _ffi.call(
             "lars_d_quotient_median_pairs", C.c_void_p(self.tiles.ptr), self.ntiles, self.npix, self.channels, self.code,
             C.c_void_p(self.table.ptr) if white_balance else None, select_streams(indices), pairs, scratch, stream))
@@ -682,6 +763,7 @@ class TileBatch:
             raise TypeError("exact batch medians need uint8 tiles with 3 channels")
         if white_balance and self.table is None:
             raise RuntimeError("compute_wb_tables() first")
+        self.settle_tables(stream)
         if self._selq is None:
             self._selq = DeviceBuffer(2 * 2 * SELECT_BINS * 8)
         self._selq.zero(stream)

@@ -150,6 +150,11 @@ struct Tuning {
     int joint_window = 1;      // joint_win.hip: windowed pair tables (one reader per tile chunk) where they fit, never, or test hooks (windows that miss)
     int zone_split_pixels = 131072;  // zonal.hip: a zone with more values than this is left out by k_zone_stats; the host runs the array statistics and the
                                // select over its segment instead (many workgroups for one zone instead of one)
+    int wb_predict = 1;        // wb_predict.hip: white-balance tables of uint8 RGNir tiles predicted from a sample and proven while the planes are
+                               // written (1), never (0), or test hooks: every prediction one value off (2), the confidence gate always passes (3)
+    int wb_predict_sixteenths = 4;   // sixteenths of a tile the predictor samples: 2 (1/8), 3 or 4 (profiles/wb_predict_bench_ab.txt)
+    int wb_predict_k = 3;      // a mark is confident when both edges of its bin are this many standard errors away from it
+    int wb_predict_min_pixels = 1 << 20;   // smaller tiles always take the exact pass
 };
 Tuning &tuning();
 // Does a kernel whose measured choice is `kernel_default_nt` (profiles/load_policy_kernels.txt) take its tile loads with nt now?
@@ -166,9 +171,35 @@ struct FusedParams;
 #ifndef LARS_V2_STATS_WAVES
 #define LARS_V2_STATS_WAVES 8          // waves per SIMD the statistics-only kernels are compiled for (64 VGPRs)
 #endif
+// Per-tile state of the sampled white-balance tables (wb_predict.hip) as the gated kernels see it; every array starts at the launch's
+// first tile.  pred == nullptr: no gate, every tile is served.
+enum : int { WB_GATE_REFUSED = 0,      // serve the tiles the predictor refused (right after the prediction)
+             WB_GATE_PREDICTED = 1,    // serve the tiles that run on a predicted table (settling them without a verified launch)
+             WB_GATE_MISSED = 2 };     // serve the predicted tiles whose counts do not prove the prediction (repair after a verified launch)
+struct WbGate {
+    const unsigned int *pred = nullptr;     // [tile] 1 = the tile's table is predicted and not yet proven
+    const uint8_t *predv = nullptr;         // [tile][8]: the predicted value of channel c's mark k at c * 2 + k
+    unsigned int *counts = nullptr;         // [tile][12]: per channel #(x < v_lo), #(x <= v_lo), #(x < v_hi), #(x <= v_hi)
+    int mode = WB_GATE_REFUSED;
+};
 int fused_v2_threads(bool any_out);
 void fused_v2_launch(unsigned mask, bool wb, int stats, bool nt, dim3 grid, hipStream_t s, const FusedParams &P);
-void chan_hist_v2_launch(const uint8_t *tiles, long long npix, unsigned int *hist, dim3 grid, hipStream_t s, int channels = 3);
+void chan_hist_v2_launch(const uint8_t *tiles, long long npix, unsigned int *hist, dim3 grid, hipStream_t s, int channels = 3,
+                         const WbGate &gate = WbGate());
+// fused.hip: the gated exact pass over the 3-channel uint8 tiles of one launch (rows of hist that the gate opens must be zero): channel
+// histograms, then percentiles and tables; with stats, the records of the tiles served are put back to their opened state and *missed counts them
+void wb_exact_gated_launch(const uint8_t *tiles, long long ntiles, long long npix, unsigned int *hist, uint8_t *table, double *pcts,
+                           int rgn_variant, const WbGate &gate, lars_stats *stats, unsigned int stats_mask, unsigned int *missed, hipStream_t s);
+// wb_predict.hip: the scratch of a batch cut into its arrays
+struct WbPredictScratch {
+    unsigned int *head;       // [4]: confident tiles, missed tiles of the last prediction
+    unsigned int *pred;       // [ntiles]
+    uint8_t *predv;           // [ntiles][8]
+    unsigned int *counts;     // [ntiles][12]
+    unsigned int *ghist;      // [ntiles][16 groups][768]: the sample's histograms
+    size_t bytes;
+};
+WbPredictScratch wb_predict_carve(void *base, long long ntiles);
 int selq_pass_launch(const uint8_t *tiles, const uint8_t *wb_table, long long ntiles, long long npix, int first,
                      const unsigned int bucket[4], unsigned long long *hist, hipStream_t s, unsigned streams);
 size_t selq_tile_scratch_bytes(long long ntiles);

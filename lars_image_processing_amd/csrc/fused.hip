@@ -16,6 +16,7 @@
 #include "device_common.h"
 #include "fused_device.h"
 #include "wg_device.h"
+#include "wb_predict_device.h"
 
 namespace lars {
 
@@ -106,12 +107,22 @@ __global__ __launch_bounds__(256) void k_chan_hist_generic(const PIX *__restrict
 // One block per (channel, tile).  numpy's 'linear' method: virtual index
 // (n-1)*q in float64, order statistics floor(vi) and floor(vi)+1 (clamped),
 // _lerp: a + (b-a)*t, and b - (b-a)*(1-t) where t >= 0.5.
+// gate: which tiles of the launch get their tables (wb_predict_device.h); a block whose tile needs nothing returns at once.  With
+// stats (uint8 only), the tile's records of the indices in stats_mask go back to their opened state -- a verified launch
+// (k_fused_u8c3, VERIFY) has accumulated into them through a table that turned out wrong -- and *missed counts the tile.
 template <int NVAL>
 __global__ __launch_bounds__(256) void k_wb_table(const unsigned int *__restrict__ hist, long long npix,
                                                   uint8_t *__restrict__ table, double *__restrict__ pcts,
-                                                  int rgn_variant)
+                                                  int rgn_variant, WbGate gate, lars_stats *stats, unsigned int stats_mask,
+                                                  unsigned int *missed)
 {
     constexpr int PER = NVAL / 256;                   // bins per thread
+    if (NVAL == 256 && !wb_gate_open(gate, npix, blockIdx.y)) return;
+    if (NVAL == 256 && blockIdx.x == 0) {
+        if (stats && threadIdx.x < 3 && ((stats_mask >> threadIdx.x) & 1u))
+            stats_open(reinterpret_cast<StatsAccView *>(stats + (long long)blockIdx.y * 3 + threadIdx.x), (int)threadIdx.x);
+        if (threadIdx.x == 0 && missed) atomicAdd(missed, 1u);
+    }
     __shared__ unsigned long long s_scan[4];
     __shared__ double s_val[4];                       // order statistics: q2.lo q2.hi q98.lo q98.hi
     __shared__ double s_p[2];
@@ -125,20 +136,9 @@ __global__ __launch_bounds__(256) void k_wb_table(const unsigned int *__restrict
     for (int j = 0; j < PER; ++j) local += h[tid * PER + j];
     const unsigned long long before = wg_exscan<256>(local, s_scan);   // samples in bins below this thread's
 
-    const double nm1 = (double)(npix - 1);
     double tq[2];
     long long rank[4];
-    for (int k = 0; k < 2; ++k) {
-        const double q = (k == 0 ? 2.0 : 98.0) / 100.0;
-        const double vi = nm1 * q;
-        const double fl = floor(vi);
-        long long lo = (long long)fl;
-        long long hi = lo + 1;
-        if (hi > npix - 1) hi = npix - 1;
-        rank[2 * k] = lo;
-        rank[2 * k + 1] = hi;
-        tq[k] = vi - fl;
-    }
+    for (int k = 0; k < 2; ++k) wb_mark_ranks(npix, k, rank[2 * k], rank[2 * k + 1], tq[k]);
     // value of order statistic r = the bin whose cumulative count first exceeds r
     unsigned long long cum = before;
     for (int j = 0; j < PER; ++j) {
@@ -152,18 +152,14 @@ __global__ __launch_bounds__(256) void k_wb_table(const unsigned int *__restrict
     }
     __syncthreads();
     if (tid < 2) {
-        const double a = s_val[2 * tid], b = s_val[2 * tid + 1], t = tq[tid];
-        const double d = b - a;
-        double r = a + d * t;
-        if (t >= 0.5) r = b - d * (1.0 - t);
+        const double r = wb_lerp(s_val[2 * tid], s_val[2 * tid + 1], tq[tid]);
         s_p[tid] = r;
         if (pcts) pcts[slot * 2 + tid] = r;
     }
     __syncthreads();
     const double p_lo = s_p[0], p_hi = s_p[1];
     if (NVAL == 256) {
-        uint8_t *out = table + slot * 256;
-        out[tid] = (uint8_t)wb_level(tid, p_lo, p_hi, rgn_variant);
+        wb_fill_table_u8(table + slot * 256, tid, p_lo, p_hi, rgn_variant);
     } else {
         // uint16: the table lives in the tile's blob together with its threshold form
         u16_fill_blob(table + (long long)blockIdx.y * LARS_U16_BLOB_BYTES, (int)blockIdx.x, p_lo, p_hi, rgn_variant, s_thr, tid);
@@ -179,12 +175,7 @@ __global__ void k_stats_init(lars_stats *stats, long long nrec, unsigned int mas
     if (i >= nrec) return;
     const int k = (int)(i % 3);
     if (!((mask >> k) & 1u)) return;
-    StatsAccView *a = reinterpret_cast<StatsAccView *>(stats + i);
-    a->sum_fx = 0; a->sumsq_fx = 0; a->count = 0; a->above = 0; a->nans = 0;
-    a->min_key = ~0ull; a->max_key = 0ull;
-    a->threshold = (k == LARS_NDWI) ? 0.0 : (double)0.2f;        // process-images.py:498-502 (float32 compare)
-    a->index_id = (unsigned)k; a->reserved = 0;
-    for (int b = 0; b < LARS_HIST_BINS; ++b) a->hist[b] = 0;
+    stats_open(reinterpret_cast<StatsAccView *>(stats + i), k);
 }
 
 __global__ void k_stats_finalize(lars_stats *stats, long long nrec, unsigned int mask, long long npix)
@@ -353,13 +344,25 @@ __device__ inline void acc_flush(Acc a, StatsAccView *rec, double (*s_red)[4], i
 // 0.689; three planes + statistics, four by its registers, unchanged).  The variants with histograms (124 registers) lose 4 %
 // below four and keep what their registers give.
 // POLICY: cache policy of the tile loads (stream_load.h).
-template <typename PIX, unsigned MASK, bool WB, int STATS, int CH = 3, int POLICY = LOAD_PLAIN>
+// VERIFY (uint8 RGNir, white balance, STATS <= 1): the launch runs on tables predicted from a sample (wb_predict.hip) and proves them
+// while it writes.  The LDS table holds one dword per sample value: the output byte on top (v_cvt_f32_ubyte3 takes it from there) and
+// four one-hot 6-bit fields below it -- x < v_lo, x <= v_lo, x < v_hi, x <= v_hi for the channel's two predicted percentiles -- so
+// that ONE add per sample into a packed per-lane word counts all four; the word is unpacked into 32-bit counters after every step
+// (at most 4 * RUN = 48 samples per channel, a field holds 63), reduced once at the end and added to G.counts[tile][12], from which
+// wb_tile_exact decides.  All three channels are mapped and counted, whichever indices are asked for, and so are the tail pixels.
+// With G.mode == WB_GATE_MISSED the same kernel is the repair launch: only the tiles whose counts did not prove their table are
+// written again (their tables are exact by then) and nothing is counted.  G is dead in every other instantiation.
+template <typename PIX, unsigned MASK, bool WB, int STATS, int CH = 3, int VERIFY = 0, int POLICY = LOAD_PLAIN>
 __global__ __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(1, (sizeof(PIX) == 1 && CH == 3 && MASK != 0u && STATS <= 1) ? 3 : 8))) void k_fused_u8c3(FusedParams P)
+__attribute__((amdgpu_waves_per_eu(VERIFY ? 2 : 1, (sizeof(PIX) == 1 && CH == 3 && MASK != 0u && STATS <= 1) ? 3 : 8))) void k_fused_u8c3(FusedParams P, WbGate G)
 {
     constexpr bool U16 = sizeof(PIX) == 2;
     static_assert(CH == 3 || (CH == 4 && !U16), "4-channel fast path: uint8 tiles");
-    __shared__ uint8_t s_lut[U16 ? 16 : 3 * 256];
+    static_assert(!VERIFY || (!U16 && CH == 3 && WB && STATS <= 1), "the verifying form: uint8 RGNir, white balance, at most basic statistics");
+    if (VERIFY && G.mode == WB_GATE_MISSED && !wb_gate_open(G, P.npix, blockIdx.y)) return;
+    __shared__ unsigned int s_lutv[VERIFY ? 3 * 256 : 1];
+    __shared__ unsigned int s_cnt[VERIFY ? 4 * 12 : 1];
+    __shared__ uint8_t s_lut[(U16 || VERIFY) ? 16 : 3 * 256];
     __shared__ unsigned int s_thr[U16 ? 3 * 260 : 4];
     __shared__ double s_par[U16 ? 6 : 1];
     // sixteen lane-private copies of the three 50-bin histograms, interleaved bin by bin (copy = lane % 16): index values
@@ -384,6 +387,14 @@ __attribute__((amdgpu_waves_per_eu(1, (sizeof(PIX) == 1 && CH == 3 && MASK != 0u
             const double *par = reinterpret_cast<const double *>(blob + LARS_U16_PAR_OFFSET);
             for (int i = tid; i < 3 * 260; i += 256) s_thr[i] = thr[i];
             if (tid < 6) s_par[tid] = par[tid];
+        } else if (VERIFY) {
+            const uint8_t *t = P.wb_table + tile * 768;
+            const uint8_t *pv = G.predv + tile * 8;
+            for (int i = tid; i < 768; i += 256) {
+                const unsigned int x = (unsigned int)i & 255u, lo = pv[(i >> 8) * 2], hi = pv[(i >> 8) * 2 + 1];
+                s_lutv[i] = ((unsigned int)t[i] << 24) | (x < lo ? 1u : 0u) | (x <= lo ? 1u << 6 : 0u) | (x < hi ? 1u << 12 : 0u) |
+                            (x <= hi ? 1u << 18 : 0u);
+            }
         } else {
             const uint8_t *t = P.wb_table + tile * 768;
             for (int i = tid; i < 768; i += 256) s_lut[i] = t[i];
@@ -396,7 +407,24 @@ __attribute__((amdgpu_waves_per_eu(1, (sizeof(PIX) == 1 && CH == 3 && MASK != 0u
     if (WB || STATS >= 2) __syncthreads();
 
     // white balance of one sample of channel c
+    unsigned int vpack[3] = {0u, 0u, 0u};                      // VERIFY: this step's packed counts of each channel
+    unsigned int vcnt[12] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    auto verify_unpack = [&]() {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            vcnt[c * 4] += vpack[c] & 63u; vcnt[c * 4 + 1] += (vpack[c] >> 6) & 63u;
+            vcnt[c * 4 + 2] += (vpack[c] >> 12) & 63u; vcnt[c * 4 + 3] += (vpack[c] >> 18) & 63u;
+            vpack[c] = 0u;
+        }
+    };
     auto wb_map = [&](unsigned int v, int c) -> unsigned int {
+        if (VERIFY) {
+            const unsigned int e = s_lutv[c * 256 + v];
+            // the output bytes add up above bit 24 and fall out of the word.  An opaque add: as plain C++ the compiler re-associates the
+            // step's 48 adds per channel into one sum at the end of the step and keeps every table entry alive until then (357 registers)
+            asm("v_add_u32 %0, %0, %1" : "+v"(vpack[c]) : "v"(e));
+            return e >> 24;
+        }
         if (!U16) return s_lut[c * 256 + v];
         const double y = ((double)v - s_par[2 * c]) * s_par[2 * c + 1];
         int g = (int)y;                                        // saturating; NaN -> 0
@@ -462,7 +490,7 @@ __attribute__((amdgpu_waves_per_eu(1, (sizeof(PIX) == 1 && CH == 3 && MASK != 0u
         }
         if (WB) {
             // channels no requested index reads are only mapped when the white-balanced image is written
-            const bool need_r = (MASK & 1u) || owb, need_g = (MASK & 6u) || owb;
+            const bool need_r = (MASK & 1u) || owb || VERIFY, need_g = (MASK & 6u) || owb || VERIFY;
 #pragma unroll
             for (int i = 0; i < 12; ++i)
                 if (i % 3 == 2 || (i % 3 == 0 && need_r) || (i % 3 == 1 && need_g)) b[i] = wb_map(b[i], i % 3);
@@ -507,7 +535,8 @@ __attribute__((amdgpu_waves_per_eu(1, (sizeof(PIX) == 1 && CH == 3 && MASK != 0u
     // (profiles/r03_waves_ab.txt).  The other instantiations gain nothing from more than four or lose (one plane: 0.686 -> 0.672).
     // uint16 tiles, one index (+ its RGBA picture) + basic statistics -- BASELINE configs[4]: 2 / 4 / 8 quads = 0.636 / 0.669 / 0.681;
     // RGBA uint8 tiles: 4 is best (0.787 against 0.770 with 8).
-    constexpr int RUN = (!U16 && CH == 3 && MASK == 7u && STATS == 1) ? 16 : (U16 && MASK == 1u && STATS <= 1) ? 8 : 4;
+    // The verifying form of the headline instantiation runs 12: the counters need the twelve registers that frees (0.4 % by that table).
+    constexpr int RUN = (!U16 && CH == 3 && MASK == 7u && STATS == 1) ? (VERIFY ? 12 : 16) : (U16 && MASK == 1u && STATS <= 1) ? 8 : 4;
     const long long nsteps = (nquads + 64 * RUN - 1) / (64 * RUN);
     const long long wstride = (long long)gx * 4;
     const unsigned int lane = (unsigned int)tid & 63u;
@@ -529,6 +558,7 @@ __attribute__((amdgpu_waves_per_eu(1, (sizeof(PIX) == 1 && CH == 3 && MASK != 0u
                 if (q < nquads) { load_quad(q, w[0]); do_quad(q, w[0]); }
             }
         }
+        if (VERIFY) verify_unpack();
     }
     // tail pixels (npix % 4): lanes 0..2 of block 0
     if (bx == 0 && tid < (int)(npix & 3)) {
@@ -547,6 +577,22 @@ __attribute__((amdgpu_waves_per_eu(1, (sizeof(PIX) == 1 && CH == 3 && MASK != 0u
         if ((MASK & 1u) && oc0) reinterpret_cast<unsigned int *>(oc0)[i] = lut0[cmap_index(a)];
         if ((MASK & 2u) && oc1) reinterpret_cast<unsigned int *>(oc1)[i] = lut1[cmap_index(bq)];
         if ((MASK & 4u) && oc2) reinterpret_cast<unsigned int *>(oc2)[i] = lut2[cmap_index(c)];
+    }
+
+    if (VERIFY && G.mode != WB_GATE_MISSED) {
+        verify_unpack();                                       // the tail pixel
+#pragma unroll
+        for (int i = 0; i < 12; ++i)
+            for (int off = 32; off >= 1; off >>= 1) vcnt[i] += __shfl_xor(vcnt[i], off);
+        if ((tid & 63) == 0) {
+#pragma unroll
+            for (int i = 0; i < 12; ++i) s_cnt[(tid >> 6) * 12 + i] = vcnt[i];
+        }
+        __syncthreads();
+        if (tid < 12) {
+            const unsigned int v = s_cnt[tid] + s_cnt[12 + tid] + s_cnt[24 + tid] + s_cnt[36 + tid];
+            if (v) atomicAdd(&G.counts[tile * 12 + tid], v);
+        }
     }
 
     if (STATS >= 1) {
@@ -759,9 +805,11 @@ extern "C" int lars_d_wb_table(const uint32_t *hist, int64_t ntiles, int64_t npi
     hipStream_t s = pick_stream(c, stream);
     dim3 grid(3, (unsigned)ntiles);
     if (dtype == LARS_U8)
-        hipLaunchKernelGGL((k_wb_table<256>), grid, dim3(256), 0, s, hist, (long long)npix, table, percentiles, rgn_variant);
+        hipLaunchKernelGGL((k_wb_table<256>), grid, dim3(256), 0, s, hist, (long long)npix, table, percentiles, rgn_variant, WbGate(),
+                           (lars_stats *)nullptr, 0u, (unsigned int *)nullptr);
     else if (dtype == LARS_U16)
-        hipLaunchKernelGGL((k_wb_table<65536>), grid, dim3(256), 0, s, hist, (long long)npix, table, percentiles, rgn_variant);
+        hipLaunchKernelGGL((k_wb_table<65536>), grid, dim3(256), 0, s, hist, (long long)npix, table, percentiles, rgn_variant, WbGate(),
+                           (lars_stats *)nullptr, 0u, (unsigned int *)nullptr);
     else
         return fail(LARS_ERR_INVALID, "lars_d_wb_table: dtype");
     return launch_check("lars_d_wb_table");
@@ -770,10 +818,10 @@ extern "C" int lars_d_wb_table(const uint32_t *hist, int64_t ntiles, int64_t npi
 template <typename PIX, unsigned MASK, bool WB, int CH, int POLICY>
 static void launch_fast_stats(int stats_mode, dim3 grid, hipStream_t s, const FusedParams &P)
 {
-    if (stats_mode == 0) hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 0, CH, POLICY>), grid, dim3(256), 0, s, P);
-    else if (stats_mode == 1) hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 1, CH, POLICY>), grid, dim3(256), 0, s, P);
-    else if (stats_mode == 3) hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 3, CH, POLICY>), grid, dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 2, CH, POLICY>), grid, dim3(256), 0, s, P);
+    if (stats_mode == 0) hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 0, CH, 0, POLICY>), grid, dim3(256), 0, s, P, WbGate());
+    else if (stats_mode == 1) hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 1, CH, 0, POLICY>), grid, dim3(256), 0, s, P, WbGate());
+    else if (stats_mode == 3) hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 3, CH, 0, POLICY>), grid, dim3(256), 0, s, P, WbGate());
+    else hipLaunchKernelGGL((k_fused_u8c3<PIX, MASK, WB, 2, CH, 0, POLICY>), grid, dim3(256), 0, s, P, WbGate());
 }
 template <typename PIX, unsigned MASK, int CH, int POLICY>
 static void launch_fast_wb(bool wb, int stats_mode, dim3 grid, hipStream_t s, const FusedParams &P)
@@ -786,7 +834,7 @@ template <typename PIX, int CH, int POLICY>
 static void launch_fast_policy(unsigned mask, bool wb, int stats_mode, dim3 grid, hipStream_t s, const FusedParams &P)
 {
     switch (mask) {
-    case 0u: hipLaunchKernelGGL((k_fused_u8c3<PIX, 0u, true, 0, CH, POLICY>), grid, dim3(256), 0, s, P); break;
+    case 0u: hipLaunchKernelGGL((k_fused_u8c3<PIX, 0u, true, 0, CH, 0, POLICY>), grid, dim3(256), 0, s, P, WbGate()); break;
     case 1u: launch_fast_wb<PIX, 1u, CH, POLICY>(wb, stats_mode, grid, s, P); break;
     case 2u: launch_fast_wb<PIX, 2u, CH, POLICY>(wb, stats_mode, grid, s, P); break;
     case 4u: launch_fast_wb<PIX, 4u, CH, POLICY>(wb, stats_mode, grid, s, P); break;
@@ -802,7 +850,59 @@ static void launch_fast(unsigned mask, bool wb, int stats_mode, dim3 grid, hipSt
     else launch_fast_policy<PIX, CH, LOAD_PLAIN>(mask, wb, stats_mode, grid, s, P);
 }
 
-extern "C" int lars_d_fused(const lars_fused_args *a)
+// The verifying form (uint8 RGNir tiles, white balance, stats_mode 0 or 1, mask 1, 2, 4 or 7): G.mode < 0 counts, WB_GATE_MISSED repairs
+template <int POLICY>
+static void launch_verify_policy(unsigned mask, int stats_mode, dim3 grid, hipStream_t s, const FusedParams &P, const WbGate &G)
+{
+#define LARS_VERIFY_CASE(M)                                                                                              \
+    case M:                                                                                                              \
+        if (stats_mode) hipLaunchKernelGGL((k_fused_u8c3<uint8_t, M, true, 1, 3, 1, POLICY>), grid, dim3(256), 0, s, P, G);  \
+        else hipLaunchKernelGGL((k_fused_u8c3<uint8_t, M, true, 0, 3, 1, POLICY>), grid, dim3(256), 0, s, P, G);           \
+        break;
+    switch (mask) {
+        LARS_VERIFY_CASE(1u)
+        LARS_VERIFY_CASE(2u)
+        LARS_VERIFY_CASE(4u)
+    default:
+        LARS_VERIFY_CASE(7u)
+    }
+#undef LARS_VERIFY_CASE
+}
+static void launch_verify(unsigned mask, int stats_mode, dim3 grid, hipStream_t s, const FusedParams &P, const WbGate &G, bool default_nt)
+{
+    if (stream_loads_nt(default_nt)) launch_verify_policy<LOAD_NT>(mask, stats_mode, grid, s, P, G);
+    else launch_verify_policy<LOAD_PLAIN>(mask, stats_mode, grid, s, P, G);
+}
+
+namespace lars {
+void wb_exact_gated_launch(const uint8_t *tiles, long long ntiles, long long npix, unsigned int *hist, uint8_t *table, double *pcts,
+                           int rgn_variant, const WbGate &gate, lars_stats *stats, unsigned int stats_mask, unsigned int *missed, hipStream_t s)
+{
+    // the geometry of lars_d_channel_hist's fast path
+    long long want = tuning().blocks_per_tile > 0 ? tuning().blocks_per_tile : (1024 + ntiles - 1) / ntiles;
+    const long long cap = (npix / 4 + 1023) / 1024;
+    if (want > cap) want = cap;
+    if (want < 1) want = 1;
+    chan_hist_v2_launch(tiles, npix, hist, dim3((unsigned)want, (unsigned)ntiles), s, 3, gate);
+    hipLaunchKernelGGL((k_wb_table<256>), dim3(3, (unsigned)ntiles), dim3(256), 0, s, hist, npix, table, pcts, rgn_variant, gate, stats,
+                       stats_mask, missed);
+}
+}  // namespace lars
+
+static int fused_run(const lars_fused_args *a, const lars_wb_verify *v);
+
+extern "C" int lars_d_fused(const lars_fused_args *a) { return fused_run(a, nullptr); }
+
+extern "C" int lars_d_fused_verified(const lars_fused_args *a, const lars_wb_verify *v)
+{
+    if (!v || !v->scratch || !v->hist || !v->percentiles || v->batch_tiles <= 0 || v->tile_start < 0 || !a || a->ntiles <= 0 ||
+        v->tile_start + a->ntiles > v->batch_tiles || !a->wb_table)
+        return fail(LARS_ERR_INVALID, "lars_d_fused_verified: bad arguments");
+    return fused_run(a, v);
+}
+
+// v: the launch's tiles may run on predicted tables (lars_d_wb_predict); when the launch leaves, they are exact and so is what it wrote
+static int fused_run(const lars_fused_args *a, const lars_wb_verify *v)
 {
     ThreadCtx *c;
     LARS_TRY(ensure_ctx(&c));
@@ -864,7 +964,42 @@ extern "C" int lars_d_fused(const lars_fused_args *a)
     // the second-generation kernels address a tile through a raw buffer descriptor with 32-bit offsets
     const bool small_tile = (long long)a->npix * 6 < (1ll << 30);
     int &ran = tuning().last_fused_kernel;                    // which kernel family served the launch (tests, tools)
-    if (fast && a->dtype == LARS_U8 && a->channels == 3 && impl >= 2 && small_tile) {
+    // Tiles on predicted tables: the verifying kernel where it exists, else the exact pass first (the launch then runs as ever)
+    const bool verify = v && fast && a->dtype == LARS_U8 && a->channels == 3 && !(impl >= 2 && small_tile) && a->wb_table && stats_mode <= 1 &&
+                        tmask != 0u && a->npix < (1ll << 31);
+    WbPredictScratch ps{};
+    WbGate G;
+    unsigned int *v_hist = nullptr;
+    double *v_pcts = nullptr;
+    if (v) {
+        ps = wb_predict_carve(v->scratch, v->batch_tiles);
+        G.pred = ps.pred + v->tile_start; G.predv = ps.predv + v->tile_start * 8; G.counts = ps.counts + v->tile_start * 12;
+        v_hist = v->hist + v->tile_start * 768;
+        v_pcts = v->percentiles + v->tile_start * 6;
+        if (!verify) {
+            G.mode = WB_GATE_PREDICTED;
+            wb_exact_gated_launch(static_cast<const uint8_t *>(a->tiles), a->ntiles, a->npix, v_hist, const_cast<uint8_t *>(a->wb_table), v_pcts,
+                                  v->rgn_variant, G, nullptr, 0u, nullptr, s);
+            LARS_HIP_TRY(hipMemsetAsync(ps.pred + v->tile_start, 0, (size_t)a->ntiles * sizeof(unsigned int), s));
+        }
+    }
+    if (verify) {
+        dim3 grid(blocks_per_tile(a->npix / 4 + 1, a->ntiles, 256, 32768), (unsigned)a->ntiles);
+        const bool three_planes_stats = tmask == 7u && stats_mode == 1 && P.out_index[0] && P.out_index[1] && P.out_index[2];
+        G.mode = -1;                                           // count
+        launch_verify(tmask, stats_mode, grid, s, P, G, three_planes_stats);
+        // repair, on the same stream: the tiles whose counts do not prove their table get the exact pass, their records are opened
+        // again, and the same kernel writes them once more; every gate evaluates the counts itself
+        G.mode = WB_GATE_MISSED;
+        wb_exact_gated_launch(static_cast<const uint8_t *>(a->tiles), a->ntiles, a->npix, v_hist, const_cast<uint8_t *>(a->wb_table), v_pcts,
+                              v->rgn_variant, G, stats_mode ? a->stats : nullptr, mask, ps.head + 1, s);
+        // at most 32 workgroups per tile: nearly every block of this launch only evaluates its gate and leaves, and 32768 of them
+        // cost more to start than a missed tile costs to write with 128 waves (the kernel strides by its grid)
+        const dim3 repair_grid(grid.x < 32u ? grid.x : 32u, grid.y);
+        launch_verify(tmask, stats_mode, repair_grid, s, P, G, three_planes_stats);
+        LARS_HIP_TRY(hipMemsetAsync(ps.pred + v->tile_start, 0, (size_t)a->ntiles * sizeof(unsigned int), s));
+        ran = 1;
+    } else if (fast && a->dtype == LARS_U8 && a->channels == 3 && impl >= 2 && small_tile) {
         dim3 grid(blocks_per_tile(a->npix / 4 + 1, a->ntiles, fused_v2_threads(any_out || mask == 0u)), (unsigned)a->ntiles);
         fused_v2_launch(tmask, a->wb_table != nullptr, stats_mode, tuning().nt_stores != 0, grid, s, P);
         ran = 2;

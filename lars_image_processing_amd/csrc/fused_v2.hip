@@ -38,6 +38,7 @@
 #include <type_traits>
 
 #include "v2_device.h"
+#include "wb_predict_device.h"
 
 namespace lars {
 
@@ -68,11 +69,13 @@ __global__ __launch_bounds__(256) void k_quot_check(unsigned int max_den, unsign
 // LDS: [3 channels][256 bins][32 copies] u32 = 96 KiB; copy = lane % 32.
 // CH = 4: RGBA tiles, one 16-byte load per lane repacked into the three dwords of an RGB quad (alpha is not counted).
 // POLICY: cache policy of the tile loads (stream_load.h).
+// gate: which tiles of the launch are counted (wb_predict_device.h); a block whose tile needs nothing returns at once.
 template <int CH, int POLICY = LOAD_PLAIN>
 __global__ __launch_bounds__(1024) void k_chan_hist_u8c3_v2(const uint8_t *__restrict__ tiles, long long npix,
-                                                            unsigned int *__restrict__ hist)
+                                                            unsigned int *__restrict__ hist, WbGate gate)
 {
     __shared__ unsigned int s_h[3 * 256 * 32];             // 96 KiB
+    if (!wb_gate_open(gate, npix, blockIdx.y)) return;
     const int tid = threadIdx.x;
     for (int i = tid; i < 3 * 256 * 32; i += 1024) s_h[i] = 0;
     __syncthreads();
@@ -615,14 +618,14 @@ void fused_v2_launch(unsigned mask, bool wb, int stats, bool nt, dim3 grid, hipS
     });
 }
 
-void chan_hist_v2_launch(const uint8_t *tiles, long long npix, unsigned int *hist, dim3 grid, hipStream_t s, int channels)
+void chan_hist_v2_launch(const uint8_t *tiles, long long npix, unsigned int *hist, dim3 grid, hipStream_t s, int channels, const WbGate &gate)
 {
     // nt tile loads by default: profiles/load_policy_kernels.txt
     const bool nt = stream_loads_nt(true);
-    if (channels == 4 && nt) hipLaunchKernelGGL((k_chan_hist_u8c3_v2<4, LOAD_NT>), grid, dim3(1024), 0, s, tiles, npix, hist);
-    else if (channels == 4) hipLaunchKernelGGL((k_chan_hist_u8c3_v2<4, LOAD_PLAIN>), grid, dim3(1024), 0, s, tiles, npix, hist);
-    else if (nt) hipLaunchKernelGGL((k_chan_hist_u8c3_v2<3, LOAD_NT>), grid, dim3(1024), 0, s, tiles, npix, hist);
-    else hipLaunchKernelGGL((k_chan_hist_u8c3_v2<3, LOAD_PLAIN>), grid, dim3(1024), 0, s, tiles, npix, hist);
+    if (channels == 4 && nt) hipLaunchKernelGGL((k_chan_hist_u8c3_v2<4, LOAD_NT>), grid, dim3(1024), 0, s, tiles, npix, hist, gate);
+    else if (channels == 4) hipLaunchKernelGGL((k_chan_hist_u8c3_v2<4, LOAD_PLAIN>), grid, dim3(1024), 0, s, tiles, npix, hist, gate);
+    else if (nt) hipLaunchKernelGGL((k_chan_hist_u8c3_v2<3, LOAD_NT>), grid, dim3(1024), 0, s, tiles, npix, hist, gate);
+    else hipLaunchKernelGGL((k_chan_hist_u8c3_v2<3, LOAD_PLAIN>), grid, dim3(1024), 0, s, tiles, npix, hist, gate);
 }
 
 int quot_check_launch(unsigned int max_den, unsigned long long *mismatches_dev, unsigned int *first_bad_dev, hipStream_t s)

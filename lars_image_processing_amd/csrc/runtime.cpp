@@ -127,6 +127,10 @@ static const Knob KNOBS[] = {
     {"tiff_strip_bytes", &Tuning::tiff_strip_bytes, Knob::SET, [](int v) { return v >= 1 && v <= (1 << 30); }, "1 .. 1073741824"},
     {"deflate_matching", &Tuning::deflate_matching, Knob::SET, [](int v) { return v == 0 || v == 1; }, "0 or 1"},
     {"zone_split_pixels", &Tuning::zone_split_pixels, Knob::SET, [](int v) { return v >= 64 && v <= (1 << 30); }, "64 .. 1073741824"},
+    {"wb_predict", &Tuning::wb_predict, Knob::SET, [](int v) { return v >= 0 && v <= 3; }, "0 .. 3"},
+    {"wb_predict_sixteenths", &Tuning::wb_predict_sixteenths, Knob::SET, [](int v) { return v >= 2 && v <= 4; }, "2 .. 4"},
+    {"wb_predict_k", &Tuning::wb_predict_k, Knob::SET, [](int v) { return v >= 1 && v <= 16; }, "1 .. 16"},
+    {"wb_predict_min_pixels", &Tuning::wb_predict_min_pixels, Knob::SET, [](int v) { return v >= 1; }, "1 or more"},
     {"last_fused_kernel", &Tuning::last_fused_kernel, Knob::READ_ONLY, nullptr, nullptr},
     {"jpeg_last_rounds", &Tuning::jpeg_last_rounds, Knob::READ_ONLY, nullptr, nullptr},
 };
