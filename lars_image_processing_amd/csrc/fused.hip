@@ -352,17 +352,22 @@ __device__ inline void acc_flush(Acc a, StatsAccView *rec, double (*s_red)[4], i
 // wb_tile_exact decides.  All three channels are mapped and counted, whichever indices are asked for, and so are the tail pixels.
 // With G.mode == WB_GATE_MISSED the same kernel is the repair launch: only the tiles whose counts did not prove their table are
 // written again (their tables are exact by then) and nothing is counted.  G is dead in every other instantiation.
-template <typename PIX, unsigned MASK, bool WB, int STATS, int CH = 3, int VERIFY = 0, int POLICY = LOAD_PLAIN>
-__global__ __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(VERIFY ? 2 : 1, (sizeof(PIX) == 1 && CH == 3 && MASK != 0u && STATS <= 1) ? 3 : 8))) void k_fused_u8c3(FusedParams P, WbGate G)
+template <typename PIX, unsigned MASK, bool WB, int STATS, int CH, int VERIFY, int POLICY>
+__device__ __forceinline__ void fused_u8c3_body(const FusedParams &P, const WbGate &G)
 {
     constexpr bool U16 = sizeof(PIX) == 2;
     static_assert(CH == 3 || (CH == 4 && !U16), "4-channel fast path: uint8 tiles");
     static_assert(!VERIFY || (!U16 && CH == 3 && WB && STATS <= 1), "the verifying form: uint8 RGNir, white balance, at most basic statistics");
     if (VERIFY && G.mode == WB_GATE_MISSED && !wb_gate_open(G, P.npix, blockIdx.y)) return;
-    __shared__ unsigned int s_lutv[VERIFY ? 3 * 256 : 1];
-    __shared__ unsigned int s_cnt[VERIFY ? 4 * 12 : 1];
-    __shared__ uint8_t s_lut[(U16 || VERIFY) ? 16 : 3 * 256];
+    // VERIFY = 1 is the verifying body.  2, 3 and 4 exist in LARS_LAB_VERIFY builds only, one difference apart for
+    // tools/lab/verifysplit.py (profiles/wb_lean_verify_split.txt): 2 = the plain body with twelve quads per step, 3 = 2 with the dword
+    // table and the packed add but no reduction, 4 = the verifying body in a kernel of its own (k_fused_u8c3 below pairs it with the
+    // plain body).
+    constexpr bool V_TABLE = VERIFY == 1 || VERIFY >= 3;      // the dword table and the packed add
+    constexpr bool V_END = VERIFY == 1 || VERIFY >= 4;        // the reduction and the atomics at the end of the block
+    __shared__ unsigned int s_lutv[V_TABLE ? 3 * 256 : 1];
+    __shared__ unsigned int s_cnt[V_END ? 4 * 12 : 1];
+    __shared__ uint8_t s_lut[(U16 || V_TABLE) ? 16 : 3 * 256];
     __shared__ unsigned int s_thr[U16 ? 3 * 260 : 4];
     __shared__ double s_par[U16 ? 6 : 1];
     // sixteen lane-private copies of the three 50-bin histograms, interleaved bin by bin (copy = lane % 16): index values
@@ -387,7 +392,7 @@ __attribute__((amdgpu_waves_per_eu(VERIFY ? 2 : 1, (sizeof(PIX) == 1 && CH == 3 
             const double *par = reinterpret_cast<const double *>(blob + LARS_U16_PAR_OFFSET);
             for (int i = tid; i < 3 * 260; i += 256) s_thr[i] = thr[i];
             if (tid < 6) s_par[tid] = par[tid];
-        } else if (VERIFY) {
+        } else if (V_TABLE) {
             const uint8_t *t = P.wb_table + tile * 768;
             const uint8_t *pv = G.predv + tile * 8;
             for (int i = tid; i < 768; i += 256) {
@@ -418,7 +423,7 @@ __attribute__((amdgpu_waves_per_eu(VERIFY ? 2 : 1, (sizeof(PIX) == 1 && CH == 3 
         }
     };
     auto wb_map = [&](unsigned int v, int c) -> unsigned int {
-        if (VERIFY) {
+        if (V_TABLE) {
             const unsigned int e = s_lutv[c * 256 + v];
             // the output bytes add up above bit 24 and fall out of the word.  An opaque add: as plain C++ the compiler re-associates the
             // step's 48 adds per channel into one sum at the end of the step and keeps every table entry alive until then (357 registers)
@@ -490,7 +495,7 @@ __attribute__((amdgpu_waves_per_eu(VERIFY ? 2 : 1, (sizeof(PIX) == 1 && CH == 3 
         }
         if (WB) {
             // channels no requested index reads are only mapped when the white-balanced image is written
-            const bool need_r = (MASK & 1u) || owb || VERIFY, need_g = (MASK & 6u) || owb || VERIFY;
+            const bool need_r = (MASK & 1u) || owb || V_TABLE, need_g = (MASK & 6u) || owb || V_TABLE;
 #pragma unroll
             for (int i = 0; i < 12; ++i)
                 if (i % 3 == 2 || (i % 3 == 0 && need_r) || (i % 3 == 1 && need_g)) b[i] = wb_map(b[i], i % 3);
@@ -558,7 +563,7 @@ __attribute__((amdgpu_waves_per_eu(VERIFY ? 2 : 1, (sizeof(PIX) == 1 && CH == 3 
                 if (q < nquads) { load_quad(q, w[0]); do_quad(q, w[0]); }
             }
         }
-        if (VERIFY) verify_unpack();
+        if (V_TABLE) verify_unpack();
     }
     // tail pixels (npix % 4): lanes 0..2 of block 0
     if (bx == 0 && tid < (int)(npix & 3)) {
@@ -579,7 +584,14 @@ __attribute__((amdgpu_waves_per_eu(VERIFY ? 2 : 1, (sizeof(PIX) == 1 && CH == 3 
         if ((MASK & 4u) && oc2) reinterpret_cast<unsigned int *>(oc2)[i] = lut2[cmap_index(c)];
     }
 
-    if (VERIFY && G.mode != WB_GATE_MISSED) {
+    if (V_TABLE && !V_END) {                                   // laboratory form: the counters stay alive, nothing is reduced
+        verify_unpack();
+        unsigned int x = 0;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) x ^= vcnt[i];
+        if (x == 0xFFFFFFFFu) G.counts[tile * 12] = x;
+    }
+    if (V_END && G.mode != WB_GATE_MISSED) {
         verify_unpack();                                       // the tail pixel
 #pragma unroll
         for (int i = 0; i < 12; ++i)
@@ -611,6 +623,22 @@ __attribute__((amdgpu_waves_per_eu(VERIFY ? 2 : 1, (sizeof(PIX) == 1 && CH == 3 
             }
         }
     }
+}
+
+// The kernel.  A verifying launch cannot know which of its tiles carry a prediction; a block can: G.pred[tile] is one word, uniform
+// over the block.  A tile the predictor refused has exact tables already, so its blocks take the plain body (sixteen quads per step,
+// byte table, nothing counted: its counts stay zero and no gate reads them) and only the predicted tiles pay for their proof.
+template <typename PIX, unsigned MASK, bool WB, int STATS, int CH = 3, int VERIFY = 0, int POLICY = LOAD_PLAIN>
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(VERIFY ? 2 : 1, (sizeof(PIX) == 1 && CH == 3 && MASK != 0u && STATS <= 1) ? 3 : 8))) void k_fused_u8c3(FusedParams P, WbGate G)
+{
+    if constexpr (VERIFY == 1) {
+        if (G.mode != WB_GATE_MISSED && G.pred[blockIdx.y] == 0u) {
+            fused_u8c3_body<PIX, MASK, WB, STATS, CH, 0, POLICY>(P, G);
+            return;
+        }
+    }
+    fused_u8c3_body<PIX, MASK, WB, STATS, CH, VERIFY, POLICY>(P, G);
 }
 
 // ---- generic path: any channel count >= 3, uint8 / uint16, any alignment ---
@@ -868,6 +896,29 @@ static void launch_verify_policy(unsigned mask, int stats_mode, dim3 grid, hipSt
     }
 #undef LARS_VERIFY_CASE
 }
+#ifdef LARS_LAB_VERIFY
+// Laboratory build (make labverify, tools/lab/verifysplit.py): LARS_LAB_VERIFY_FORM names the form of k_fused_u8c3 that a verified launch
+// of three planes + basic statistics runs, alone, with no repair behind it; unset or negative, the build behaves as the product.
+static int lab_verify_form()
+{
+    const char *e = getenv("LARS_LAB_VERIFY_FORM");
+    return e && *e ? atoi(e) : -1;
+}
+static bool lab_verify_launch(int form, dim3 grid, hipStream_t s, const FusedParams &P, const WbGate &G)
+{
+#define LARS_LAB_FORM(V) \
+    case V: hipLaunchKernelGGL((k_fused_u8c3<uint8_t, 7u, true, 1, 3, V, LOAD_NT>), grid, dim3(256), 0, s, P, G); return true;
+    switch (form) {
+        LARS_LAB_FORM(0)
+        LARS_LAB_FORM(1)
+        LARS_LAB_FORM(2)
+        LARS_LAB_FORM(3)
+        LARS_LAB_FORM(4)
+    default: return false;
+    }
+#undef LARS_LAB_FORM
+}
+#endif
 static void launch_verify(unsigned mask, int stats_mode, dim3 grid, hipStream_t s, const FusedParams &P, const WbGate &G, bool default_nt)
 {
     if (stream_loads_nt(default_nt)) launch_verify_policy<LOAD_NT>(mask, stats_mode, grid, s, P, G);
@@ -987,6 +1038,12 @@ static int fused_run(const lars_fused_args *a, const lars_wb_verify *v)
         dim3 grid(blocks_per_tile(a->npix / 4 + 1, a->ntiles, 256, 32768), (unsigned)a->ntiles);
         const bool three_planes_stats = tmask == 7u && stats_mode == 1 && P.out_index[0] && P.out_index[1] && P.out_index[2];
         G.mode = -1;                                           // count
+#ifdef LARS_LAB_VERIFY
+        if (three_planes_stats && lab_verify_launch(lab_verify_form(), grid, s, P, G)) {
+            ran = 1;
+            return launch_check("lars_d_fused (laboratory form)");
+        }
+#endif
         launch_verify(tmask, stats_mode, grid, s, P, G, three_planes_stats);
         // repair, on the same stream: the tiles whose counts do not prove their table get the exact pass, their records are opened
         // again, and the same kernel writes them once more; every gate evaluates the counts itself

@@ -37,8 +37,16 @@ __host__ __device__ inline unsigned int wbp_segment(unsigned int tile, unsigned 
 }
 
 // One workgroup per (group, tile): group g counts samples g, g + 16, ... into 32 lane-private copies of the three histograms (96 KiB
-// of LDS, conflict-free as k_chan_hist_u8c3_v2's) and stores its 768 counts.  A wave reads a quarter segment (1 KiB) per load, up to four
-// loads in flight.  Byte o of a tile belongs to channel o % 3; 4096, 1024 and 16 are all 1 modulo 3.
+// of LDS, conflict-free as k_chan_hist_u8c3_v2's) and stores its 768 counts.  Four waves share a segment, a quarter (1 KiB) per wave and
+// load; wave (sub, quarter) reads the quarter of samples k = sub + 4 n, n = 0, 1, ...  Byte o of a tile belongs to channel o % 3; 4096,
+// 1024 and 16 are all 1 modulo 3.
+// The loads of a wave form a ring of WBP_RING, as k_chan_hist_u8c3_v2's: a slot is counted and filled again at once, so that eleven or
+// twelve loads stay in flight while the LDS atomics run (the first form issued four, waited for all four and counted them with nothing
+// in flight: 4.0 TB/s, profiles/wb_lean_pre_pass_trace.txt).  The segments of a chunk of 48 loads are worked out once, one per lane
+// (wbp_segment divides twice), and handed out through v_readlane; a load takes its segment as the scalar offset.  12 divides the loads
+// per wave at 2, 3 and 4 sixteenths of a 4096 x 4096 tile (24, 36, 48); what is left over goes one load at a time.
+constexpr int WBP_RING = 12;
+constexpr int WBP_CHUNK = 48;
 template <int POLICY>
 __global__ __launch_bounds__(1024) void k_wb_sample_hist(const uint8_t *__restrict__ tiles, long long npix, unsigned int nseg,
                                                          unsigned int nsample, unsigned int *__restrict__ ghist)
@@ -52,34 +60,58 @@ __global__ __launch_bounds__(1024) void k_wb_sample_hist(const uint8_t *__restri
     const uint8_t *base = tiles + (long long)tile * npix * 3;
     const __amdgpu_buffer_rsrc_t rsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(base), 0, (int)(nseg * WBP_SEG_BYTES), 0x00020000);
-    const unsigned int wave = (unsigned int)tid >> 6, lane = (unsigned int)tid & 63u;
+    const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane(tid >> 6), lane = (unsigned int)tid & 63u;    // scalar loop counts
     const unsigned int sub = wave >> 2, quarter = wave & 3u;
     const unsigned int per_group = nsample / WBP_GROUPS;
+    const unsigned int nloads = per_group > sub ? (per_group - sub + 3u) / 4u : 0u;      // samples k = sub + 4 n < per_group
     const unsigned int lane_off = ((unsigned int)tid & 31u) << 2;
+    const unsigned int voff = quarter * 1024u + lane * 16u;
+    // the channel of the lane's first byte is (seg + quarter + lane) % 3: the three rotations of the channel offsets, picked by seg % 3
+    const unsigned int pl = (quarter + lane) % 3u;
+    const unsigned int o0 = pl * 32768u, o1 = ((pl + 1u) % 3u) * 32768u, o2 = ((pl + 2u) % 3u) * 32768u;
     char *hb = reinterpret_cast<char *>(s_h);
 #define WBP_ADD(word, shift, choff)                                                                     \
     atomicAdd(reinterpret_cast<unsigned int *>(hb + (choff) + ((((word) >> (shift)) & 0xFFu) << 7) + lane_off), 1u)
-    for (unsigned int k0 = sub; k0 < per_group; k0 += 16u) {
-        sl_u32x4 w[4];
-        unsigned int ph[4];
+    auto count = [&](const sl_u32x4 &w, unsigned int seg) {                             // seg: uniform over the wave
+        const unsigned int s3 = seg % 3u;
+        const unsigned int c0 = s3 == 0u ? o0 : s3 == 1u ? o1 : o2, c1 = s3 == 0u ? o1 : s3 == 1u ? o2 : o0,
+                           c2 = s3 == 0u ? o2 : s3 == 1u ? o0 : o1;
+        WBP_ADD(w.x, 0, c0); WBP_ADD(w.x, 8, c1); WBP_ADD(w.x, 16, c2); WBP_ADD(w.x, 24, c0);
+        WBP_ADD(w.y, 0, c1); WBP_ADD(w.y, 8, c2); WBP_ADD(w.y, 16, c0); WBP_ADD(w.y, 24, c1);
+        WBP_ADD(w.z, 0, c2); WBP_ADD(w.z, 8, c0); WBP_ADD(w.z, 16, c1); WBP_ADD(w.z, 24, c2);
+        WBP_ADD(w.w, 0, c0); WBP_ADD(w.w, 8, c1); WBP_ADD(w.w, 16, c2); WBP_ADD(w.w, 24, c0);
+    };
+    for (unsigned int cb = 0; cb < nloads; cb += (unsigned int)WBP_CHUNK) {
+        const unsigned int cn = nloads - cb < (unsigned int)WBP_CHUNK ? nloads - cb : (unsigned int)WBP_CHUNK;
+        // lane l: the segment of the chunk's load l
+        unsigned int segv = 0u;
+        if (lane < cn) segv = wbp_segment(tile, (sub + 4u * (cb + lane)) * WBP_GROUPS + group, nseg, nsample);
+        auto seg_of = [&](unsigned int i) {                                             // i < cn, uniform
+            return (unsigned int)__builtin_amdgcn_readlane((int)segv, (int)i);
+        };
+        const unsigned int rounds = cn / (unsigned int)WBP_RING;
+        if (rounds > 0u) {
+            sl_u32x4 w[WBP_RING];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const unsigned int k = k0 + 4u * (unsigned int)j;
-            if (k < per_group) {                                                    // uniform over the wave
-                const unsigned int seg = wbp_segment(tile, k * WBP_GROUPS + group, nseg, nsample);
-                w[j] = stream_load_b128<POLICY>(rsrc, seg * WBP_SEG_BYTES + quarter * 1024u + lane * 16u, 0);
-                ph[j] = (seg + quarter + lane) % 3u;
+            for (int j = 0; j < WBP_RING; ++j) w[j] = stream_load_b128<POLICY>(rsrc, voff, seg_of((unsigned int)j) * WBP_SEG_BYTES);
+            for (unsigned int r = 0; r + 1u < rounds; ++r) {
+#pragma unroll
+                for (int j = 0; j < WBP_RING; ++j) {
+                    count(w[j], seg_of(r * (unsigned int)WBP_RING + (unsigned int)j));
+                    __builtin_amdgcn_sched_barrier(0);
+                    w[j] = stream_load_b128<POLICY>(rsrc, voff, seg_of((r + 1u) * (unsigned int)WBP_RING + (unsigned int)j) * WBP_SEG_BYTES);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < WBP_RING; ++j) {
+                count(w[j], seg_of((rounds - 1u) * (unsigned int)WBP_RING + (unsigned int)j));
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (k0 + 4u * (unsigned int)j < per_group) {
-                const unsigned int c0 = ph[j] * 32768u, c1 = ((ph[j] + 1u) % 3u) * 32768u, c2 = ((ph[j] + 2u) % 3u) * 32768u;
-                WBP_ADD(w[j].x, 0, c0); WBP_ADD(w[j].x, 8, c1); WBP_ADD(w[j].x, 16, c2); WBP_ADD(w[j].x, 24, c0);
-                WBP_ADD(w[j].y, 0, c1); WBP_ADD(w[j].y, 8, c2); WBP_ADD(w[j].y, 16, c0); WBP_ADD(w[j].y, 24, c1);
-                WBP_ADD(w[j].z, 0, c2); WBP_ADD(w[j].z, 8, c0); WBP_ADD(w[j].z, 16, c1); WBP_ADD(w[j].z, 24, c2);
-                WBP_ADD(w[j].w, 0, c0); WBP_ADD(w[j].w, 8, c1); WBP_ADD(w[j].w, 16, c2); WBP_ADD(w[j].w, 24, c0);
-            }
+        for (unsigned int i = rounds * (unsigned int)WBP_RING; i < cn; ++i) {
+            const unsigned int seg = seg_of(i);
+            count(stream_load_b128<POLICY>(rsrc, voff, seg * WBP_SEG_BYTES), seg);
         }
     }
 #undef WBP_ADD
